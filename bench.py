@@ -384,6 +384,23 @@ class PlaceholderEngine:
         pass
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, fluxes):
+    """--dump-outputs: the last timed step's [columns][12] integrated fluxes (float64, columns in global order) as
+    integrated_fluxes.npy.  Beyond DUMP_MAX_BYTES a fixed, seeded sample of columns is written instead, and
+    integrated_fluxes_columns.npy (float64) names the columns it holds."""
+    os.makedirs(dirname, exist_ok=True)
+    fluxes = np.ascontiguousarray(fluxes, dtype=np.float64)
+    if fluxes.nbytes > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // (fluxes.shape[1] * 8 + 8)
+        cols = np.sort(np.random.default_rng(20261015).choice(fluxes.shape[0], keep, replace=False))
+        fluxes = fluxes[cols]
+        np.save(os.path.join(dirname, "integrated_fluxes_columns.npy"), cols.astype(np.float64))
+    np.save(os.path.join(dirname, "integrated_fluxes.npy"), fluxes)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -413,6 +430,8 @@ def main():
     ap.add_argument("--sw-lines", type=int, default=None)
     ap.add_argument("--lw-dw", type=float, default=None, help="exploration only: longwave grid spacing (default 1 cm-1)")
     ap.add_argument("--sw-dw", type=float, default=None, help="exploration only: shortwave grid spacing (default 1 cm-1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last of them "
+                    "delivered (the integrated fluxes of every column of the step) as DIR/*.npy")
     args = ap.parse_args()
     if args.gpus < 1 or args.steps < 1 or args.cols < 1 or args.chunk < 1:
         raise SystemExit("bench.py: --gpus, --steps, --cols and --chunk must be positive")
@@ -604,6 +623,9 @@ def main():
             if placeholder:
                 want = np.array([[PlaceholderEngine.expected(c, k) for k in range(nfl)] for c in range(total_per_step)])
                 assert all(np.array_equal(allf[sl], want) for sl in range(slots)), "gathered blocks are not the columns in order"
+        if args.dump_outputs:
+            # taken before the measurements after the timed region, which reuse the job buffer
+            dump_outputs(args.dump_outputs, allf[(args.steps - 1) % slots] if use_dist else fluxes[:count])
         total_cols = total_per_step * args.steps
         dist_info = {"n_gpus": world, "rccl_ranks": world if backend == "nccl" else 0, "ms_per_step_by_rank": rank_ms,
                      "collective": {"backend": backend, "gathers_in_timed_region": gathers["count"],

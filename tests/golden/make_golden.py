@@ -98,6 +98,21 @@ def main():
     np.savez_compressed(path, **out)
     print(path, os.path.getsize(path), "bytes,", len(out), "arrays")
     stochastic_clouds()
+    live_reference()
+
+
+def live_reference():
+    """What oracle/_ref returns for the seeded cases of section 3 of tests/test_oracle_golden.py (reference_outputs there
+    lists them), so that those comparisons run where the reference tree is absent."""
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_oracle_golden as T
+    from grtcode_amd import api
+    from oracle.bindings import Oracle
+    with tempfile.TemporaryDirectory() as tmp:
+        out = T.reference_outputs(Ref(), Oracle(), api.load_library(), tmp)
+    np.savez_compressed(T.LIVE_FIXTURE, **out)
+    print(T.LIVE_FIXTURE, os.path.getsize(T.LIVE_FIXTURE), "bytes,", len(out), "arrays")
 
 
 def stochastic_clouds():

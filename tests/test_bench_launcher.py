@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -135,3 +136,28 @@ def test_both_launch_paths_give_a_rank_the_same_environment(tmp_path):
         dumps[how] = [json.load(open(str(tmp_path / how) + f".rank{k}")) for k in range(2)]
     assert dumps["spawned"] == dumps["torchrun"]
     assert all(d == {"HSA_ENABLE_IPC_MODE_LEGACY": "0"} for d in dumps["spawned"])
+
+
+def test_dump_outputs_writes_the_last_steps_fluxes_of_every_column(tmp_path):
+    """--dump-outputs DIR: what the last timed step delivered, every column of the job in order, as float64 .npy."""
+    from bench import PlaceholderEngine
+    r = run(["--gpus", "2", "--columns", "5", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")])
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert only_line(r)["steps"] == 2
+    got = np.load(tmp_path / "out" / "integrated_fluxes.npy")
+    assert got.dtype == np.float64 and got.shape == (5, 12)
+    assert np.array_equal(got, [[PlaceholderEngine.expected(c, k) for k in range(12)] for c in range(5)])
+    assert sorted(os.listdir(tmp_path / "out")) == ["integrated_fluxes.npy"]
+
+
+def test_dump_outputs_samples_columns_beyond_the_cap(tmp_path, monkeypatch):
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 10 * 13 * 8)
+    fluxes = np.arange(40 * 12, dtype=np.float64).reshape(40, 12)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), fluxes)
+    cols = np.load(tmp_path / "a" / "integrated_fluxes_columns.npy")
+    got = np.load(tmp_path / "a" / "integrated_fluxes.npy")
+    assert cols.dtype == np.float64 and cols.size == 10 and np.all(np.diff(cols) > 0)
+    assert np.array_equal(got, fluxes[cols.astype(int)]) and got.nbytes <= bench.DUMP_MAX_BYTES
+    assert np.array_equal(cols, np.load(tmp_path / "b" / "integrated_fluxes_columns.npy"))    # the same sample every run

@@ -5,7 +5,8 @@
    those tests print;
 2. outputs of the reference's own compiled C (tests/golden/ref_fixtures.npz, made by
    tests/golden/make_golden.py from oracle/_ref): bit for bit;
-3. live, against oracle/_ref when it is present (build container): bit for bit on fresh seeds.
+3. against oracle/_ref on seeded cases: live where it is built, else through its outputs committed in
+   tests/golden/live_reference.npz (same maker); bit for bit.
 """
 import json
 import os
@@ -149,64 +150,136 @@ def test_optics_and_solvers_bit_exact_vs_fixture(oracle, fx):
     assert np.array_equal(up, fx["fx_sw_up"]) and np.array_equal(dn, fx["fx_sw_dn"])
 
 
-# ---- 3. live against the reference build (build container only) --------------------------- #
-@pytest.mark.parametrize("seed,dw", [(11, 1.0), (12, 0.1), (13, 0.01)])
-def test_column_bit_exact_vs_live_reference(oracle, ref, lib, seed, dw, tmp_path):
+# ---- 3. against the reference build: live where oracle/_ref is built, its committed outputs elsewhere ---------- #
+LIVE_FIXTURE = os.path.join(HERE, "golden", "live_reference.npz")
+COLUMN_CASES = [(11, 1.0), (12, 0.1), (13, 0.01)]
+SWEEP_CASES = [(21, 1.0, 140.0), (22, 0.1, 60.0), (23, 0.25, 80.0), (24, 0.02, 40.0)]
+BRACKET_ARRAY = np.array([1.0, 2.0, 2.0, 3.5, 7.0, 7.0, 7.0, 9.25])
+BRACKET_VALUES = (0.5, 1.0, 1.5, 2.0, 3.0, 3.5, 7.0, 8.0, 9.25, 10.0)
+
+
+def column_case(root, seed, dw):
     from scenario import Band
-    band = Band(str(tmp_path), 300.0, 300.0 + 120 * dw * 4, dw, 400, mols=[syn.H2O, syn.CO2, syn.O3], seed=seed)
-    col = syn.profile(seed, 9)
+    band = Band(root, 300.0, 300.0 + 120 * dw * 4, dw, 400, mols=[syn.H2O, syn.CO2, syn.O3], seed=seed)
+    return band, syn.profile(seed, 9)
+
+
+def sweep_case(root, seed, dw, span):
+    from scenario import Band
+    w0 = 300.0
+    band = Band(root, w0, w0 + span, dw, 500, mols=[syn.H2O, syn.CO2, syn.O3], seed=seed, line_range=(w0, w0 + span - 26.5))
+    return band, syn.profile(seed, 8)
+
+
+def solver_inputs():
+    rng = np.random.default_rng(5)
+    L = 17
+    col = syn.profile(21, L + 1)
+    w0, wn, dw = 50.0, 2950.0, 5.0
+    n = int(round((wn - w0) / dw)) + 1
+    tau = 10.0 ** rng.uniform(-6, 1, (L, n))
+    om = rng.uniform(0, 0.98, (L, n))
+    g = rng.uniform(-0.9, 0.9, (L, n))
+    emis, alb, solar = rng.uniform(0.8, 1, n), rng.uniform(0, 1, n), rng.uniform(0, 1e-3, n)
+    return col, (w0, wn, dw, n), tau, om, g, emis, alb, solar
+
+
+def loader_inputs(root):
+    w = np.arange(40.0, 260.0, 7.0)
+    y = np.cos(w / 30.0) ** 2 + 0.1
+    path = os.path.join(root, "solar.csv")
+    syn.write_csv(path, w, y)
+    return path, w, y
+
+
+def reference_outputs(ref, orc, lib, root):
+    """What the reference build (oracle/_ref) returns for every case of this section, by key.  tests/golden/make_golden.py
+    writes it to tests/golden/live_reference.npz; the `live` fixture computes it again where oracle/_ref is built."""
+    import ctypes as C
+    from oracle.bindings import RefSpectralGrid
+    out = {}
+    for seed, dw in COLUMN_CASES:
+        band, col = column_case(os.path.join(root, f"column_{seed}"), seed, dw)
+        out[f"column_{seed}"] = band.oracle_tau(ref, orc, lib, col)
+    for seed, dw, span in SWEEP_CASES:
+        band, col = sweep_case(os.path.join(root, f"sweep_{seed}"), seed, dw, span)
+        for method in (0, 1):
+            out[f"sweep_{seed}_{method}"] = band.oracle_tau(ref, orc, lib, col, method=method)
+    # per value: [found (code 0), left, right]
+    out["bracket"] = np.array([(rc == 0, l, r) for rc, l, r in (ref.bracket(BRACKET_ARRAY, v) for v in BRACKET_VALUES)],
+                              dtype=np.int64)
+    col, (w0, wn, dw, n), tau, om, g, emis, alb, solar = solver_inputs()
+    grid = ref.grid(w0, wn, dw)
+    assert grid.n == n
+    out["lw_up"], out["lw_dn"] = ref.lw_fluxes(grid, col["t_surf"], col["t_layer"], col["t"], tau, om, emis)
+    out["sw_up"], out["sw_dn"] = ref.sw_fluxes(grid, om, g, tau, 0.3, 0.5, alb, alb, 1361.0, solar)
+    path, _, _ = loader_inputs(root)
+
+    class RefSolar(C.Structure):
+        _fields_ = [("grid", RefSpectralGrid), ("incident_flux", C.POINTER(C.c_double)), ("n", C.c_uint64)]
+    s = RefSolar()
+    grid = ref.grid(1.0, 300.0, 0.5)
+    assert ref.lib.create_solar_flux(C.byref(s), C.byref(grid), path.encode()) == 0
+    out["solar"] = np.ctypeslib.as_array(s.incident_flux, shape=(s.n,)).copy()
+    return out
+
+
+@pytest.fixture(scope="module")
+def live(oracle, lib, tmp_path_factory):
+    """The reference build's outputs for this section: computed by oracle/_ref where it is built (and then equal to the
+    committed copy), else the committed copy, tests/golden/live_reference.npz."""
+    from oracle.bindings import Ref, ref_available
+    with np.load(LIVE_FIXTURE) as z:
+        stored = {k: z[k] for k in z.files}
+    if ref_available():
+        fresh = reference_outputs(Ref(), oracle, lib, str(tmp_path_factory.mktemp("live_reference")))
+        assert sorted(fresh) == sorted(stored)
+        for k in stored:
+            assert np.array_equal(fresh[k], stored[k]), k
+        return fresh
+    return stored
+
+
+@pytest.mark.parametrize("seed,dw", COLUMN_CASES)
+def test_column_bit_exact_vs_live_reference(oracle, live, lib, seed, dw, tmp_path):
+    band, col = column_case(str(tmp_path), seed, dw)
     a = band.oracle_tau(oracle, oracle, lib, col)
-    b = band.oracle_tau(ref, oracle, lib, col)
-    assert np.array_equal(a, b)
+    assert np.array_equal(a, live[f"column_{seed}"])
 
 
 @pytest.mark.parametrize("method", [0, 1])
-@pytest.mark.parametrize("seed,dw,span", [(21, 1.0, 140.0), (22, 0.1, 60.0), (23, 0.25, 80.0), (24, 0.02, 40.0)])
-def test_sweep_methods_bit_exact_vs_live_reference(oracle, ref, lib, seed, dw, span, method, tmp_path):
+@pytest.mark.parametrize("seed,dw,span", SWEEP_CASES)
+def test_sweep_methods_bit_exact_vs_live_reference(oracle, live, lib, seed, dw, span, method, tmp_path):
     """wavenumber_sweep (0) and line_sweep (1): sort_lines, bracket, the local/remote split, the three
     interpolation points per bin and the final quadratic interpolation (kernels.c:135-406,514-581,
     kernel_utils.c:26-117, spectral_bin.c:30-99).  The reference holds no expected values for them (its
-    own tests return early, test_kernels.c:322-362), so the live build is the only pin.  Lines stay
+    own tests return early, test_kernels.c:322-362), so its build is the only pin.  Lines stay
     26.5 cm-1 below the top of the grid: for nearer ones the reference's line_sweep indexes one bin past
     its arrays (maxw = w0 + n*wres is a grid step beyond the last point) and lands in the next layer's first
     bin -- undefined behaviour the restatement does not copy."""
-    from scenario import Band
-    w0 = 300.0
-    band = Band(str(tmp_path), w0, w0 + span, dw, 500, mols=[syn.H2O, syn.CO2, syn.O3], seed=seed,
-                line_range=(w0, w0 + span - 26.5))
-    col = syn.profile(seed, 8)
+    band, col = sweep_case(str(tmp_path), seed, dw, span)
     a = band.oracle_tau(oracle, oracle, lib, col, method=method)
-    b = band.oracle_tau(ref, oracle, lib, col, method=method)
-    assert np.array_equal(a, b)
+    assert np.array_equal(a, live[f"sweep_{seed}_{method}"])
     sample = band.oracle_tau(oracle, oracle, lib, col)
     # the sweeps approximate the far wings by a quadratic per 1 cm-1 bin: close to, not equal to, line_sample
     scale = np.abs(sample).max(axis=1, keepdims=True)
     assert 0.0 < np.max(np.abs(a - sample) / scale) < 0.05
 
 
-def test_bracket_vs_live_reference(oracle, ref):
-    arr = np.array([1.0, 2.0, 2.0, 3.5, 7.0, 7.0, 7.0, 9.25])
-    for val in (0.5, 1.0, 1.5, 2.0, 3.0, 3.5, 7.0, 8.0, 9.25, 10.0):
-        ra, rb = oracle.bracket(arr, val), ref.bracket(arr, val)
-        assert (ra[0] == 0) == (rb[0] == 0)
-        assert ra[1:] == rb[1:]
+def test_bracket_vs_live_reference(oracle, live):
+    for val, rb in zip(BRACKET_VALUES, live["bracket"]):
+        ra = oracle.bracket(BRACKET_ARRAY, val)
+        assert (ra[0] == 0) == bool(rb[0])
+        assert ra[1:] == tuple(int(x) for x in rb[1:])
 
 
-def test_solvers_bit_exact_vs_live_reference(oracle, ref):
-    rng = np.random.default_rng(5)
-    L = 17
-    col = syn.profile(21, L + 1)
-    grid = ref.grid(50.0, 2950.0, 5.0)
-    n = grid.n
-    tau = 10.0 ** rng.uniform(-6, 1, (L, n))
-    om = rng.uniform(0, 0.98, (L, n))
-    g = rng.uniform(-0.9, 0.9, (L, n))
-    emis, alb, solar = rng.uniform(0.8, 1, n), rng.uniform(0, 1, n), rng.uniform(0, 1e-3, n)
-    a = oracle.lw_fluxes(50.0, 5.0, col["t_surf"], col["t_layer"], col["t"], tau, om, emis)
-    b = ref.lw_fluxes(grid, col["t_surf"], col["t_layer"], col["t"], tau, om, emis)
+def test_solvers_bit_exact_vs_live_reference(oracle, live):
+    col, (w0, wn, dw, n), tau, om, g, emis, alb, solar = solver_inputs()
+    a = oracle.lw_fluxes(w0, dw, col["t_surf"], col["t_layer"], col["t"], tau, om, emis)
+    b = live["lw_up"], live["lw_dn"]
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
     a = oracle.sw_fluxes(om, g, tau, 0.3, 0.5, alb, alb, 1361.0, solar)
-    b = ref.sw_fluxes(grid, om, g, tau, 0.3, 0.5, alb, alb, 1361.0, solar)
+    b = live["sw_up"], live["sw_dn"]
     # Where one of the reference's in-kernel range checks trips on a rounding-level excursion (e.g. a
     # diffuse beam of -1e-50, shortwave.c:318-320) sw_flux() returns early and sw_fluxes_kernel, which
     # ignores the code (:443), stores whatever its stack buffers held -- the previous wavenumber's
@@ -218,23 +291,14 @@ def test_solvers_bit_exact_vs_live_reference(oracle, ref):
     assert np.array_equal(a[0][:, ok], b[0][:, ok]) and np.array_equal(a[1][:, ok], b[1][:, ok])
 
 
-def test_loader_arithmetic_vs_live_reference(oracle, ref, tmp_path):
+def test_loader_arithmetic_vs_live_reference(oracle, live, tmp_path):
     """interp-to-grid (+ quirks) and solar normalisation against the reference's CSV loaders."""
-    import ctypes as C
-    from oracle.bindings import RefSpectralGrid
-    w = np.arange(40.0, 260.0, 7.0)
-    y = np.cos(w / 30.0) ** 2 + 0.1
-    path = str(tmp_path / "solar.csv")
-    syn.write_csv(path, w, y)
-    grid = ref.grid(1.0, 300.0, 0.5)
-
-    class RefSolar(C.Structure):
-        _fields_ = [("grid", RefSpectralGrid), ("incident_flux", C.POINTER(C.c_double)), ("n", C.c_uint64)]
-    s = RefSolar()
-    assert ref.lib.create_solar_flux(C.byref(s), C.byref(grid), path.encode()) == 0
-    want = np.ctypeslib.as_array(s.incident_flux, shape=(s.n,)).copy()
+    _, w, y = loader_inputs(str(tmp_path))
+    n = int(round((300.0 - 1.0) / 0.5)) + 1
+    want = live["solar"]
+    assert want.size == n
     ww = np.array([float("%.6f" % a) for a in w])
     yy = np.array([float("%.9e" % b) for b in y])
-    got = oracle.normalize_solar(1.0, 0.5, oracle.interp_to_grid(1.0, 0.5, grid.n, ww, yy))
+    got = oracle.normalize_solar(1.0, 0.5, oracle.interp_to_grid(1.0, 0.5, n, ww, yy))
     assert np.array_equal(got, want)
-    assert got[0] == 0.0 and got[-1] == 0.0 and got[(np.arange(grid.n) * 0.5 + 1.0) == 40.0][0] == 0.0   # w == x[0] stays 0
+    assert got[0] == 0.0 and got[-1] == 0.0 and got[(np.arange(n) * 0.5 + 1.0) == 40.0][0] == 0.0   # w == x[0] stays 0
