@@ -118,9 +118,9 @@ typedef struct GrtGasOpticsArgs
     int rcap;                 /* widest near field taken for the sake of Humlicek region 1 */
     int tree_levels;          /* > 0: far field by the cell hierarchy (fine grids), this many coarse levels */
     int mom_terms;            /* moments per cell: 8, or -- tree form on sparse lines -- 12 (near field 3.95 |z|max
-                                 instead of 7.8 |z|max); 0 means 8 */
+                                 instead of 7.8 |z|max); 0 means 8 in the one-pass form */
     int profile_tag;          /* != 0: time the line kernel under this tag (the two-pass gather under tag + 5) */
-    int near_block;           /* set by the launcher: 64 where the tree form's gather shares its walk per wave -- near
+    int near_block;           /* set by the plan: 64 where the tree form's gather shares its walk per wave -- near
                                  fields are then whole 64-point blocks (the halo leaves room for that); else 0 */
     int deterministic;        /* != 0 (GRT_DETERMINISTIC=1 / grt_set_deterministic): every floating-point sum in one fixed
                                  order, so that two runs agree to the last bit -- one wave of a workgroup takes all of its
@@ -135,15 +135,15 @@ typedef struct GrtGasOpticsArgs
                                  epilogue starts), 13: when the last wave left it; 14-21: clocks the waves spent in preparation,
                                  moment reduction and adds, near-centre walk and queue pushes, region-1 corrections, near
                                  field, the rest of the line loop, evaluating queued points, moment terms.  Zeroed by the caller. */
-    int direct_near;          /* set by the launcher: seven-point near fields (R = 3) by direct evaluation + row reduction
-                                 instead of the ring (GRT_DIRECT_NEAR=0 in the environment switches it off) */
+    int direct_near;          /* set by the plan (cell-moment forms): seven-point near fields (R = 3) by direct evaluation +
+                                 row reduction instead of the ring */
     int tile_phase, tile_nphase;   /* set by the launcher: this launch takes cell tiles t with t % tile_nphase == tile_phase
                                  (tile_nphase <= 1: all of them) */
     uint32_t const *tile_ranges;   /* two-pass form, or NULL: [tiles][2] first / one-past-last line of the store whose centre can
                                  fall in cell tile t under any pressure shift up to the bound the host built the table for
                                  (a superset: the kernel decides membership line by line) -- spares every workgroup the
                                  search of the sorted store, ten dependent loads before its waves can start */
-    int lean;                 /* set by the launcher (two-pass form, single-level gather, lines.lean_a built for this grid): the
+    int lean;                 /* set by the plan (two-pass form, single-level gather, lines.lean_a built for this grid): the
                                  first pass takes the lean fp32 form of the line loop wherever a workgroup's near fields are
                                  seven points wide (GRT_LEAN=0 in the environment switches it off: comparison runs) */
     uint32_t const *tile_items;    /* two-pass form, or NULL: the launch's work list [n_items][4] = {cell tile, first line, one past
@@ -183,9 +183,12 @@ int grt_launch_gas_optics(void *stream, GrtGasOpticsArgs const *a);
 /* HIP-event brackets on the library stream (grt_device.c; grt_ext.h: grt_profile_*) */
 int grt_profile_begin(void *stream, int tag);
 void grt_profile_end(void *stream, int slot);
-/* fast == 1 only: the cell-moment kernel (k_gas_optics_mp.hip) and whether it applies to a grid */
+/* fast == 1 / 3: the cell-moment kernels (k_gas_optics_mp.hip), launched with the arguments as given; whether they apply
+   to a grid and shape (no buffer pointer read), and whether the two-pass form's first pass can take the lean line loop */
 int grt_launch_gas_optics_mp(void *stream, GrtGasOpticsArgs const *a);
-int grt_gas_optics_mp_applicable(GrtGasOpticsArgs const *a);
+int grt_gas_optics_mp_shape(GrtGasOpticsArgs const *a);
+int grt_gas_optics_lean_shape(GrtGasOpticsArgs const *a);
+int grt_tree_gather_by_wave(long long fsteps);   /* k_gas_optics_far.hip: the tree gather's near fields in 64-point blocks */
 uint64_t grt_gas_optics_moment_floats(uint64_t nw, int levels, int terms);   /* per (column, layer) block of gmom */
 double grt_gas_optics_moment_separation(int terms);   /* near field / |z|max that keeps the series' remainder at 7e-8 */
 

@@ -412,6 +412,10 @@ size_t gas_optics_lds_bytes(int tile)
 
 extern "C" int grt_launch_gas_optics(void *stream, GrtGasOpticsArgs const *a)
 {
+    if (a->fast == 1 || a->fast == 3)
+    {
+        return grt_launch_gas_optics_mp(stream, a);
+    }
     if (a->tile <= 0 || (a->tile % 64) != 0 || a->nslice < 1 || a->ncol < 1)
     {
         return (int)hipErrorInvalidValue;
@@ -432,10 +436,6 @@ extern "C" int grt_launch_gas_optics(void *stream, GrtGasOpticsArgs const *a)
     unsigned const stride = golden_stride(ngroups);
     size_t const lds = gas_optics_lds_bytes(a->tile);
     hipStream_t const s = (hipStream_t)stream;
-    if (a->fast == 1 || a->fast == 3)
-    {
-        return grt_launch_gas_optics_mp(stream, a);
-    }
     if (a->fast)
     {
         hipLaunchKernelGGL(gas_optics_kernel<true>, grid, dim3(kBlock), lds, s, *a, fsteps, (unsigned)ngroups, stride);

@@ -904,8 +904,8 @@ extern "C" int grt_launch_near_radius(void *stream, GrtGasOpticsArgs const *bp, 
     return (int)hipGetLastError();
 }
 
-// The second pass of a launch whose first pass has been queued on `stream`: b as the first pass's launcher set it up (halo,
-// near_block, mom_terms, nslice = 1 ...), shift = log2 of the first pass's cell-tile size.
+// The second pass of a launch whose first pass has been queued on `stream`: b the launch's arguments with nslice = 1,
+// shift = log2 of the first pass's cell-tile size.
 extern "C" int grt_launch_far_field(void *stream, GrtGasOpticsArgs const *bp, long long fsteps, int shift)
 {
     hipStream_t const s = (hipStream_t)stream;
@@ -928,12 +928,8 @@ extern "C" int grt_launch_far_field(void *stream, GrtGasOpticsArgs const *bp, lo
     // The gather's workgroups own wider tiles than the first pass's cell tiles (each thread takes two grid points in
     // turn): a workgroup's fixed costs -- staging the column state and the moments of 2 fsteps extra cells, the
     // near-field radii of the cell tiles it touches, two barriers -- are shared by twice the points.
-    static int far_want = -1;           // GRT_FAR_TILE in the environment: exploration only
-    if (far_want < 0)
-    {
-        char const *env = getenv("GRT_FAR_TILE");
-        far_want = env != NULL && atoi(env) >= 64 ? atoi(env) : 512;      // shortwave launch of 64 columns (round 5): 256 -> 3.97 ms, 512 -> 3.12, 1 024 -> 3.86
-    }
+    // (at most 512 points: shortwave launch of 64 columns (round 5): 256 -> 3.97 ms, 512 -> 3.12, 1 024 -> 3.86)
+    int const far_want = 512;
     int far_tile = b.tile;
     while (2*far_tile <= far_want && (uint64_t)far_tile < b.nw
            && far_lds_bytes(2*far_tile, 2*far_tile + 2*(int)fsteps, (int)fsteps, b.lay.num_slots, shift) <= kLdsPerWorkgroup)

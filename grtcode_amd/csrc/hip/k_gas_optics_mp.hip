@@ -702,27 +702,6 @@ size_t mp_lds_bytes(int nacc, int ncell, int fsteps, int num_slots, bool tree = 
     return main_loop > subtree ? main_loop : subtree;
 }
 
-
-// GRT_LEAN=0 in the environment (read at every launch, so that a test can compare the two forms in one process): the
-// two-pass form's first pass keeps the general line loop everywhere
-int lean_wanted()
-{
-    char const *env = getenv("GRT_LEAN");
-    return (env != NULL && env[0] == '0') ? 0 : 1;
-}
-
-// GRT_DIRECT_NEAR=0 in the environment: seven-point near fields through the ring as well (comparison runs)
-int direct_near_wanted()
-{
-    static int want = -1;
-    if (want < 0)
-    {
-        char const *env = getenv("GRT_DIRECT_NEAR");
-        want = (env != NULL && env[0] == '0') ? 0 : 1;
-    }
-    return want;
-}
-
 int log2_exact(int v)
 {
     int s = 0;
@@ -730,12 +709,25 @@ int log2_exact(int v)
     return (1 << s) == v ? s : -1;
 }
 
+// whether what the host bound carries the launch's cell moments (two-pass form)
+bool mp_bound(GrtGasOpticsArgs const *a)
+{
+    if (a->fast != 3)
+    {
+        return true;
+    }
+    int const terms = a->mom_terms == 0 ? kMom : a->mom_terms;
+    uint64_t const need = a->tree_levels > 0 ? level_offset(a->nw, a->tree_levels + 1, terms, a->tree_levels) : (uint64_t)kMom*a->nw;
+    return a->gmom != NULL && a->gmom_stride >= need;
+}
+
 } // namespace
 
-// 0 when the moment kernel does not apply to this grid (narrow windows, or a window that does not fit LDS).
-// a->fast == 3 asks about the two-pass form (cell tiles must be a power of two); with a->tree_levels > 0 about
-// its tree form, whose first pass spans only the tile and `halo` points either side.
-extern "C" int grt_gas_optics_mp_applicable(GrtGasOpticsArgs const *a)
+// 0 when the moment kernel does not apply to this grid and shape (narrow windows, or a window that does not fit LDS); reads
+// no buffer pointer.  a->fast == 3 asks about the two-pass form (cell tiles must be a power of two); with a->tree_levels > 0
+// about its tree form, whose first pass spans only the tile and `halo` points either side -- without it, the first pass
+// spans the window (halo = fsteps).  The single-level forms take rcap = kRcap.
+extern "C" int grt_gas_optics_mp_shape(GrtGasOpticsArgs const *a)
 {
     long long const fsteps = (long long)ceil((double)25.f/a->wres);   // kernels.c:417
     if (fsteps < 1)
@@ -747,18 +739,17 @@ extern "C" int grt_gas_optics_mp_applicable(GrtGasOpticsArgs const *a)
         int const shift = log2_exact(a->tile);
         int const terms = a->mom_terms == 0 ? kMom : a->mom_terms;
         bool const direct = a->tile > kDirectTile;
-        return shift >= 6 && a->gmom != NULL && a->tree_levels <= kMaxLevels && a->halo >= 3 && a->rcap <= a->halo
+        return shift >= 6 && a->tree_levels <= kMaxLevels && a->halo >= 3 && a->rcap <= a->halo
                && ((terms == kMom && !direct) || (terms == kMomWide && direct))
                && (long long)a->rcap + 4 <= fsteps && a->halo <= fsteps && fsteps < (1ll << 30) && a->nw < (1ull << 30)
                && ((long long)1 << a->tree_levels) <= fsteps
-               && a->gmom_stride >= level_offset(a->nw, a->tree_levels + 1, terms, a->tree_levels)
                && level_offset(a->nw, a->tree_levels + 1, terms, a->tree_levels) < 0xffffffffull
                && a->tile + 2*a->halo <= 32767
                && mp_lds_bytes(a->tile + 2*a->halo, direct ? 0 : a->tile, 0, a->lay.num_slots, true, direct ? a->tile : 0) <= kLdsPerWorkgroup
                && grt_tree_lds_bytes(grt_tree_gather_tile(), a->lay.num_slots, grt_tree_gather_ntab(a->tile, a->halo)) <= kLdsPerWorkgroup
                && grt_tree_lds_bytes(a->tile, a->lay.num_slots, (a->tile + 2*a->halo)/a->tile + 2) <= kLdsPerWorkgroup;
     }
-    if (fsteps > 4096)
+    if (fsteps > 4096 || a->rcap != kRcap)
     {
         return 0;
     }
@@ -769,11 +760,22 @@ extern "C" int grt_gas_optics_mp_applicable(GrtGasOpticsArgs const *a)
     if (a->fast == 3)
     {
         int const shift = log2_exact(a->tile);
-        return shift >= 6 && a->gmom != NULL && a->gmom_stride >= (uint64_t)kMom*a->nw
+        return shift >= 6 && a->halo == fsteps && a->mom_terms == kMom
                && mp_lds_bytes(a->tile + 2*(int)fsteps, a->tile, 0, a->lay.num_slots) <= kLdsPerWorkgroup
                && grt_far_lds_bytes(a->tile, a->tile + 2*(int)fsteps, (int)fsteps, a->lay.num_slots, shift) <= kLdsPerWorkgroup;
     }
     return mp_lds_bytes(a->tile, a->tile + 2*(int)fsteps, (int)fsteps, a->lay.num_slots) <= kLdsPerWorkgroup;
+}
+
+// whether the two-pass form's first pass can take the lean line loop (GrtGasOpticsArgs.lean): single-level gather, packed
+// records built for this very grid, room for its tables in LDS
+extern "C" int grt_gas_optics_lean_shape(GrtGasOpticsArgs const *a)
+{
+    int const nacc = a->tile + 2*a->halo;
+    return a->fast == 3 && a->tree_levels == 0 && a->lines.lean_a != NULL && a->lines.lean_b != NULL
+           && a->lines.lean_c != NULL && a->lines.lean_x != NULL && a->lay.num_slots <= kLeanSlots && a->lines.lean_w0 == a->w0 && a->lines.lean_wres == a->wres
+           && a->lines.n < 0xffffffffull && a->halo >= 8 && nacc <= 4096
+           && mp_lds_bytes(nacc, a->tile, 0, a->lay.num_slots) + lean_lds_bytes(a->lay.num_slots) <= kLdsPerWorkgroup;
 }
 
 // floats per (column, layer) block of gmom that `levels` coarse levels need (the host sizes the buffer with it)
@@ -789,7 +791,7 @@ extern "C" double grt_gas_optics_moment_separation(int terms)
 
 extern "C" int grt_launch_gas_optics_mp(void *stream, GrtGasOpticsArgs const *a)
 {
-    if (a->tile <= 0 || (a->tile % 64) != 0 || a->nslice < 1 || a->ncol < 1 || !grt_gas_optics_mp_applicable(a))
+    if (a->tile <= 0 || (a->tile % 64) != 0 || a->nslice < 1 || a->ncol < 1 || !grt_gas_optics_mp_shape(a) || !mp_bound(a))
     {
         return (int)hipErrorInvalidValue;
     }
@@ -799,7 +801,14 @@ extern "C" int grt_launch_gas_optics_mp(void *stream, GrtGasOpticsArgs const *a)
         return (int)hipErrorInvalidValue;
     }
     unsigned long long const tiles = (a->nw + a->tile - 1)/a->tile;
-    bool const items = a->fast == 3 && a->tile_items != nullptr && a->tile_ranges != nullptr && a->n_items > 0;
+    bool const items = a->tile_items != nullptr;
+    bool const tree = a->tree_levels > 0;
+    // (a work list: flat two-pass form only, none of these launches; the lean loop where it fits; 64-point near blocks: tree form)
+    if ((items && (a->fast != 3 || a->tile_ranges == nullptr || a->n_items == 0 || tree || a->deterministic || a->probe != NULL))
+        || (a->lean && (a->probe != NULL || !grt_gas_optics_lean_shape(a))) || (a->near_block != 0 && (a->near_block != 64 || !tree)))
+    {
+        return (int)hipErrorInvalidValue;
+    }
     unsigned long long const ngroups = items ? a->n_items : tiles*a->nslice;
     unsigned long long const blocks = ngroups*a->lay.num_layers*a->ncol;
     if (blocks == 0 || blocks > 0x7fffffffull)
@@ -810,8 +819,7 @@ extern "C" int grt_launch_gas_optics_mp(void *stream, GrtGasOpticsArgs const *a)
     if (a->fast == 3)
     {
         // two passes: near fields and cell moments (every line prepared once), then the far-field gather
-        bool const tree = a->tree_levels > 0;
-        int const halo = tree ? a->halo : (int)fsteps;
+        int const halo = a->halo;
         int const nacc = a->tile + 2*halo, shift = log2_exact(a->tile);
         if (a->ncol > 65535 || a->lay.num_layers > 65535 || (tree && a->nslice != 1))
         {
@@ -830,23 +838,6 @@ extern "C" int grt_launch_gas_optics_mp(void *stream, GrtGasOpticsArgs const *a)
             return (int)e;
         }
         GrtGasOpticsArgs b = *a;
-        if (!items || tree || a->deterministic || a->probe != NULL)
-        {
-            if (items)
-            {
-                return (int)hipErrorInvalidValue;       // (the host builds a work list for none of these)
-            }
-            b.tile_items = nullptr;
-            b.n_items = 0;
-        }
-        b.halo = halo;
-        b.direct_near = direct_near_wanted();
-        b.near_block = (tree && grt_tree_gather_by_wave(fsteps)) ? 64 : 0;
-        b.mom_terms = wide ? kMomWide : kMom;
-        if (!tree)
-        {
-            b.rcap = kRcap;
-        }
         if (!tree && b.radius_table != nullptr)
         {
             int const rc_radius = grt_launch_near_radius(stream, &b, fsteps, shift);
@@ -858,12 +849,7 @@ extern "C" int grt_launch_gas_optics_mp(void *stream, GrtGasOpticsArgs const *a)
         int slot = a->profile_tag ? grt_profile_begin(stream, a->profile_tag) : -1;
         int const ncell = (tree && a->tile > kDirectTile) ? 0 : a->tile;
         size_t lds = mp_lds_bytes(nacc, ncell, 0, a->lay.num_slots, tree, tree && ncell == 0 ? a->tile : 0);
-        // the lean line loop: single-level gather, packed records built for this very grid, room for its tables in LDS
-        b.lean = !tree && a->probe == NULL && lean_wanted() && a->lines.lean_a != NULL && a->lines.lean_b != NULL
-                 && a->lines.lean_c != NULL && a->lines.lean_x != NULL && a->lay.num_slots <= kLeanSlots && a->lines.lean_w0 == a->w0 && a->lines.lean_wres == a->wres
-                 && a->lines.n < 0xffffffffull && halo >= 8 && nacc <= 4096
-                 && lds + lean_lds_bytes(a->lay.num_slots) <= kLdsPerWorkgroup;
-        if (b.lean)
+        if (a->lean)
         {
             lds += lean_lds_bytes(a->lay.num_slots);
         }
@@ -945,10 +931,7 @@ extern "C" int grt_launch_gas_optics_mp(void *stream, GrtGasOpticsArgs const *a)
     }
     int const ncell = a->tile + 2*(int)fsteps;
     size_t const lds = mp_lds_bytes(a->tile, ncell, (int)fsteps, a->lay.num_slots);
-    GrtGasOpticsArgs b = *a;
-    b.rcap = kRcap;
-    b.direct_near = direct_near_wanted();
-    hipLaunchKernelGGL((gas_optics_mp_kernel_w5<false, false, kMom>), dim3((unsigned)blocks), dim3(kBlock), lds, s, b, fsteps,
+    hipLaunchKernelGGL((gas_optics_mp_kernel_w5<false, false, kMom>), dim3((unsigned)blocks), dim3(kBlock), lds, s, *a, fsteps,
                        (unsigned)ngroups, golden_stride(ngroups), ncell, a->tile, 0);
     return (int)hipGetLastError();
 }

@@ -106,10 +106,7 @@ typedef struct GrtGasOpticsImpl
     size_t gmom_bytes;
     int *radius_table;             /* GrtGasOpticsArgs.radius_table */
     size_t radius_bytes;
-    size_t scratch_cap_bytes;      /* ... and what the object may hold of it (0: not asked yet; launch_columns) */
-    size_t scratch_per_column;     /* ... what ONE column of the current form needs of it (set by grt_fill_gas_args) */
-    int sizing_only;               /* grt_fill_gas_args: work the launch parameters out, allocate nothing */
-    int batch_cols;                /* columns of the batch in colstate_h while launch_columns runs it in groups, else 0 */
+    size_t scratch_cap_bytes;      /* ... and what the object may hold of it (0: not asked yet; grt_gas_launch_columns) */
     long long last_launch[8];    /* grt_gas_optics_last_launch */
     /* spectral tables on device, each [n]: */
     double *h2o_tables;            /* [4][n] F296,S296,CKDF,CKDS or NULL */
@@ -130,6 +127,7 @@ typedef struct GrtGasOpticsImpl
     unsigned long long *probe;     /* grt_gas_optics_probe: device buffer for the instrumented line kernel, or NULL */
     uint64_t probe_words;
 } GrtGasOpticsImpl;
+static inline GrtGasOpticsImpl *impl_of(GasOptics_t const *go) { return (GrtGasOpticsImpl *)go->impl; }
 
 int grt_gas_optics_prepare(GasOptics_t *go, int ncol);   /* build store/tables/layout if stale */
 int grt_gas_optics_wait_staging(GasOptics_t *go);        /* until the last batch's column state has been uploaded */
@@ -143,8 +141,11 @@ int grt_column_state(GasOptics_t const *go, fp_t const *p_mb, fp_t const *t,
    kernel needs to add that part for the columns of the object's last launch. */
 int grt_gas_optics_defer_tables(GasOptics_t *go, int on);
 void grt_gas_optics_continua(GasOptics_t *go, GrtContinua *c);
-int grt_fill_gas_args(GasOptics_t *go, int ncol, double *tau, uint64_t tau_col_stride,
-                      GrtGasOpticsArgs *args);
+
+/* grt_gas_launch.c: the fields every launcher reads, whatever the form (lines, layout, column state, tables, grid, tau);
+   and the launch of the ncol columns whose states are in colstate_h, writing tau [ncol] blocks of tau_col_stride doubles */
+void grt_gas_common_args(GasOptics_t const *go, int ncol, double *tau, uint64_t tau_col_stride, GrtGasOpticsArgs *a);
+int grt_gas_launch_columns(GasOptics_t *go, int ncol, double *tau_dev, uint64_t tau_col_stride);
 
 /* loaders */
 int grt_parse_hitran(char const *path, int mol_id, double w0, double wn, GrtHostLines *out);
