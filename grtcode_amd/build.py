@@ -42,7 +42,6 @@ HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-muns
             f"-I{ROOT}/include"]
 # -fno-slp-vectorize: the SLP vectoriser pairs neighbouring f32 operations into v_pk_* instructions and pays for the pairs
 # with register moves; measured on G1: longwave launch 45.7 -> 44.7 ms, far-field gather 6.0 -> 5.4, 367.7 -> 371.6 columns/s
-HIPFLAGS += os.environ.get("GRT_HIPFLAGS_EXTRA", "").split()       # exploration only
 
 
 def _newer(src, dst, extra=()):
@@ -66,8 +65,8 @@ def _flags_stamp():
 
 
 def _flags_changed():
-    """The flags the objects in lib/obj were built with are kept next to them: a build under other flags (GRT_HIPFLAGS_EXTRA
-    set or dropped, a new default) rebuilds everything instead of silently reusing objects of the other configuration.
+    """The flags the objects in lib/obj were built with are kept next to them: a build under other flags (a new default)
+    rebuilds everything instead of silently reusing objects of the other configuration.
     The stamp is removed here and written again only after the link succeeded (build()), so a build that fails half way
     cannot leave objects of two configurations under a stamp that matches."""
     stamp, want = _flags_stamp()

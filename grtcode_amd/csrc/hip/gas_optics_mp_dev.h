@@ -10,9 +10,7 @@
 namespace {
 
 constexpr int kMom = 8;         // moments per cell
-#ifndef GRT_FAR_GRADED_MIN
-#define GRT_FAR_GRADED_MIN 64   // single-level gather: windows wider than this many points a side take fewer terms for far cells
-#endif
+constexpr int kFarGradedMin = 64;   // single-level gather: windows wider than this many points a side take fewer terms for far cells
 constexpr int kMomWide = 12;    // ... of the tree form on sparse lines (args.mom_terms)
 
 // The series is geometric in |z|/r: K terms leave (|z|/r)^K.  Near field out to r = sep |z|max keeps that at 7e-8.
@@ -225,10 +223,7 @@ constexpr int kClassesSplit = 4;
 // workgroups per CU 80 ... 96 measured the same (104 cost the fourth workgroup: 14.4 -> 16.6 ms); at five (see
 // gas_optics_mp_kernel_w5) the LDS they take is what decides: 64 entries.  The tree form's first pass is short of LDS
 // anyway (0.001 cm-1: four workgroups per CU instead of three, 42 -> 39 ms) and its pushes mostly come as full batches
-#ifndef GRT_MP_QUEUE
-#define GRT_MP_QUEUE 64
-#endif
-constexpr int kMpQueue = GRT_MP_QUEUE;
+constexpr int kMpQueue = 64;
 constexpr int kMpQueueTree = 64;
 
 template <int CAP, int NCLS>

@@ -58,7 +58,7 @@ __global__ __launch_bounds__(kBlock) void gas_optics_far_kernel(GrtGasOpticsArgs
     double const *lay = cs + a.lay.off_lay + (uint64_t)layer*4;
     double *out = a.tau + (uint64_t)col*a.tau_col_stride + (uint64_t)layer*a.nw;
     // (with the radii of the cell tiles at hand and a short window the column state is not needed here)
-    bool const own_radii = a.radius_table == nullptr || fsteps > GRT_FAR_GRADED_MIN;
+    bool const own_radii = a.radius_table == nullptr || fsteps > kFarGradedMin;
     if (own_radii)
     {
         stage_column_state(a, cs, layer, ms_l, q_l, tid);
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(kBlock) void gas_optics_far_kernel(GrtGasOpticsArgs
     {
         rk[k] = fsteps + 1;
     }
-    if (fsteps > GRT_FAR_GRADED_MIN)
+    if (fsteps > kFarGradedMin)
     {
         bool um, cr;
         double zmax;
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(kBlock) void gas_optics_far_kernel(GrtGasOpticsArgs
     // Point f wants the cells f - r and f + r, point f + 1 the cells f + 1 - r and f + 1 + r: of the four, f + 1 - r and
     // f + r were read one step earlier (as f - (r - 1) and f + 1 + (r - 1)), so a step reads two cells for four series
     // instead of four for two (5.4 -> 4.8 ms per shortwave launch of 64 columns).
-    bool const pair_form = fsteps <= GRT_FAR_GRADED_MIN && rmin == rmax && rmin >= 1;
+    bool const pair_form = fsteps <= kFarGradedMin && rmin == rmax && rmin >= 1;
     if (pair_form)
     {
         // (all eight terms at every distance, as the general loop below takes them for short windows: the same terms per

@@ -44,9 +44,6 @@ namespace {
 template <int CLASS, int ONLY, bool PACKED4, typename Queue>
 __device__ __forceinline__ void drain_class(double *acc, Queue const *q, int wave, int first, int count, int lane)
 {
-#ifdef GRT_ABL_NOEVAL
-    if (count >= 0) return;         // (timing experiments only: scripts/lean_ablation.sh)
-#endif
     for (int i = first + lane; i < first + count; i += 64)
     {
         float const xi = q->xi[CLASS][wave][i], y = q->y[CLASS][wave][i];
@@ -642,12 +639,10 @@ __global__ __launch_bounds__(kBlock) void gas_optics_mp_kernel(GrtGasOpticsArgs 
 // (64-bit addressing of the line loads, their scalar reloads: -12 per block) or prefetching the next block's lines changed
 // nothing at four waves; measured on G1 (64 columns, LW + SW launch): 4 waves (120 VGPRs, 88-entry queues) 44.7 + 114.9 ms,
 // **5 waves 42.1 + 108.0** (80-entry queues: 43.3 + 109.1), 6 waves (80 VGPRs, 96 bytes of scratch) 43.1 + 110.7,
-// 7 waves 46.8 + 113.1.  (GRT_MP_WAVES / GRT_MP_QUEUE on the compiler's command line: exploration only.)
+// 7 waves 46.8 + 113.1.
+constexpr int kMpWaves = 5;
 template <bool TWO_PASS, bool TREE, int K, bool LEAN = false>
-#ifndef GRT_MP_WAVES
-#define GRT_MP_WAVES 5
-#endif
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(GRT_MP_WAVES, GRT_MP_WAVES)))
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kMpWaves, kMpWaves)))
 void gas_optics_mp_kernel_w5(GrtGasOpticsArgs a, long long fsteps_ll, unsigned ngroups, unsigned perm_stride, int ncell,
                              int nacc, int halo)
 {
@@ -655,14 +650,10 @@ void gas_optics_mp_kernel_w5(GrtGasOpticsArgs a, long long fsteps_ll, unsigned n
 }
 
 // First pass of the two-pass form with the LEAN line loop (see mp_kernel_body): LEANP lines per lane.
-#ifndef GRT_LEAN_WAVES
-#define GRT_LEAN_WAVES 4
-#endif
-#ifndef GRT_LEAN_P
-#define GRT_LEAN_P 2
-#endif
+constexpr int kLeanWaves = 4;
+constexpr int kLeanP = 2;
 template <bool LEAN, int LEANP>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(GRT_LEAN_WAVES, GRT_LEAN_WAVES)))
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kLeanWaves, kLeanWaves)))
 void gas_optics_lean_kernel(GrtGasOpticsArgs a, long long fsteps_ll, unsigned ngroups, unsigned perm_stride, int ncell,
                             int nacc, int halo)
 {
@@ -900,12 +891,12 @@ extern "C" int grt_launch_gas_optics_mp(void *stream, GrtGasOpticsArgs const *a)
                 }
                 else if (b.lean && a->w0 + (double)a->nw*a->wres <= 4000.)
                 {
-                    hipLaunchKernelGGL((gas_optics_lean_kernel<true, GRT_LEAN_P>), dim3((unsigned)blocks), dim3(kBlock), lds, s, b,
+                    hipLaunchKernelGGL((gas_optics_lean_kernel<true, kLeanP>), dim3((unsigned)blocks), dim3(kBlock), lds, s, b,
                                        fsteps, (unsigned)ngroups, golden_stride(ngroups), ncell, nacc, halo);
                 }
                 else if (b.lean)
                 {
-                    hipLaunchKernelGGL((gas_optics_lean_kernel<false, GRT_LEAN_P>), dim3((unsigned)blocks), dim3(kBlock), lds, s, b,
+                    hipLaunchKernelGGL((gas_optics_lean_kernel<false, kLeanP>), dim3((unsigned)blocks), dim3(kBlock), lds, s, b,
                                        fsteps, (unsigned)ngroups, golden_stride(ngroups), ncell, nacc, halo);
                 }
                 else if (a->w0 + (double)a->nw*a->wres <= 4000.)

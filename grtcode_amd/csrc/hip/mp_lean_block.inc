@@ -90,9 +90,7 @@
             a_norm = (float)(1./(3.14159265358979323846*a.wres));
             wres_v = wres_f;
             inv_wres_v = inv_wres_f;
-#ifndef GRT_LEAN_NOPIN
             asm volatile("" : "+v"(kh), "+v"(kl), "+v"(c2t), "+v"(pw), "+v"(pavg_f), "+v"(a_norm), "+v"(wres_v), "+v"(inv_wres_v));
-#endif
             // (what the tile's near fields are made of: from the launch's table where there is one, as the radius)
             unsigned const tf = tile_flags_known ? tile_flags : lean_tile_flags(a, lay, ms_l, F0, F1, corrected);
             tflags = (unsigned)__builtin_amdgcn_readfirstlane((int)tf);
@@ -186,9 +184,6 @@
             int const hi = nrel - base < 128u ? (int)(nrel - base) : 128;
             float4 const ra0 = next_a0, ra1 = next_a1, rb0 = next_b0, rb1 = next_b1;
             uint2 const rcc = next_c;
-#ifdef GRT_LEAN_FETCH_EARLY
-            lean_fetch(base + walk_stride);
-#endif
             // (the tile's flags, tested where they are used: hoisted out of the loop, each test became a lane mask in two
             // scalar registers, spilled to a vector register's lanes and read back with v_readlane at every use)
             unsigned tfl = tflags;
@@ -295,9 +290,6 @@
             // ---- moments of the Lorentzian about the cell centre (see general_block) ----
             v2f const A = (amp*eta)*splat2(a_norm);                             // K(r) = A/((r - dl)^2 + eta^2)
             v2f m[kMom];
-#ifdef GRT_ABL_NOMOM     // (timing experiments only, scripts/lean_ablation.sh: results are wrong by construction)
-            for (int k = 0; k < kMom; ++k) m[k] = splat2(0.f);
-#else
             {
                 v2f uu = A, pk = splat2(0.f);
 #pragma unroll
@@ -309,7 +301,6 @@
                     m[k] = pk;
                 }
             }
-#endif
             // Voigt constants (RFM_voigt.c:97-126, :177-179); a pure Lorentz line (y >= 70.55) has no region 1
             v2f const yq = y*y;
             v2f const x0q = sel2(!valid[0] | (y.x >= 70.55f), !valid[1] | (y.y >= 70.55f), splat2(0.f), pk_fma(y, pk_fma(y, splat2(-3.6f), splat2(40.0f)), splat2(15100.0f)));   // XLIM0^2
@@ -359,11 +350,7 @@
                 }
             }
             // ---- the row's moment sums: eight per cell end in sixteen lanes (one cell: in eight) ----
-#ifdef GRT_ABL_NOREDUCE
-            if (hi < 0)
-#else
             if (single)
-#endif
             {
                 float g0[kMom];
 #pragma unroll
@@ -373,20 +360,12 @@
                 }
                 float tsum = row_sum_transposed(g0, (lane & 8) != 0, (lane & 4) != 0, (lane & 2) != 0);       // value (lane >> 1) & 7, twice
                 tsum = (lane & 1) == 0 ? tsum : 0.f;
-#ifdef GRT_ABL_NOLDSADD
-                if ((tsum == 123.456f) & (cr < F1))
-#else
                 if ((tsum != 0.f) & (cr < F1))
-#endif
                 {
                     mom_add((lane >> 1) & 7, cr, tsum);
                 }
             }
-#ifdef GRT_ABL_NOREDUCE
-            else if (hi < 0)
-#else
             else
-#endif
             {
                 float g0[kMom], g1[kMom];
 #pragma unroll
@@ -398,11 +377,7 @@
                 }
                 float const tsum = row_sum_two_groups(g0, g1, (lane & 8) != 0, (lane & 4) != 0, (lane & 2) != 0, (lane & 1) != 0);
                 int const cell = cr + ((lane >> 3) & 1);
-#ifdef GRT_ABL_NOLDSADD
-                if ((tsum == 123.456f) & (cell < F1))
-#else
                 if ((tsum != 0.f) & (cell < F1))
-#endif
                 {
                     mom_add(lane & 7, cell, tsum);
                 }
@@ -430,12 +405,7 @@
             v2f v[7];
             v2f xq[7];                                      // x^2 of the seven points (the regimes fill what they test)
             unsigned ncm[2] = {0u, 0u};
-#ifdef GRT_ABL_NOSLOTS
-            for (int k = 0; k < 7; ++k) v[k] = splat2(0.f);
-            if (hi < 0)
-#else
             if (tfl & kTfLreg)
-#endif
             {
                 // every point but the line's own: the Lorentzian, A/(rel^2 + eta^2) (RFM_voigt.c:103,170,278)
 #pragma unroll
@@ -458,11 +428,7 @@
                 ncm[1] = nc[1] ? 8u : 0u;
                 xq[3] = xq0;
             }
-#ifdef GRT_ABL_NOSLOTS
-            else if (hi < 0)
-#else
             else
-#endif
             {
                 v2f const acl = amp*cl;
 #pragma unroll
@@ -525,7 +491,6 @@
                     }
                 }
             }
-#ifndef GRT_NO_LEAN_REGION2
             // ---- Humlicek region 2 (XLIM2 = 6.8 - y <= |x| < XLIM1, RFM_voigt.c:113, :187-199) is evaluated HERE (round 5):
             // like region 1 it is one rational function of x^2 -- one reciprocal, nothing that cancels -- and out there the
             // line shape falls as y/x^2 (e^-x^2 is below 3e-15 of it for any y > 1e-12): a relative error of x comes back
@@ -563,11 +528,7 @@
                     ncm[1] = r2[1] ? (ncm[1] & ~(1u << k)) : ncm[1];
                 }
             }
-#endif
             // into the row's eight slots (grid points cr - 3 .. cr + 4): a line of cell cr + o has its points in slots o .. 6 + o
-#ifdef GRT_ABL_NOREDUCE
-            if (hi < 0)
-#endif
             {
                 float nvs[8];
                 if (single)
@@ -591,11 +552,7 @@
                     }
                 }
                 float const s8 = row_sum_transposed(nvs, (lane & 8) != 0, (lane & 4) != 0, (lane & 2) != 0);
-#ifdef GRT_ABL_NOLDSADD
-                if (((lane & 1) == 0) & (s8 == 123.456f))
-#else
                 if (((lane & 1) == 0) & (s8 != 0.f))
-#endif
                 {
                     GRT_ACC_ADD(&acc[cr - 3 + ((lane >> 1) & 7) - A0], (double)s8);
                 }
@@ -642,9 +599,6 @@
             // molecule slot and exponent index); full batches are given the reference's x and y (drain_raw).
             // Bits 0-6: points of the lane's first line, 7-13: of its second ----
             unsigned nc2 = ncm[0] | (ncm[1] << 7);
-#ifdef GRT_ABL_NORAW
-            nc2 = 0u;
-#endif
             // (the wave's last lean block also empties the raw queue: ONE place in the code prepares entries, so the kernel
             // carries one copy less of that and of the four evaluation formulas behind it)
             bool const flush = base + walk_stride >= nrel || xcount == kLeanListCap;
@@ -683,8 +637,6 @@
             // less alive across the queues' code, no scratch; the other waves cover the loads -- G1 shortwave 76.0 -> 75.4 ms.
             // Measured and dropped in the same round: the waves' leftover class queues evaluated as one list per workgroup
             // -- 75.4 ms either way)
-#ifndef GRT_LEAN_FETCH_EARLY
             lean_fetch(base + walk_stride);
-#endif
         }
     };

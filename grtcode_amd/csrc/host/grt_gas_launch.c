@@ -44,7 +44,7 @@ static void auto_tune(GasOptics_t const *go, int ncol, int moments, int *tile, i
         /* Round 4: the same with MANY columns too while a tile holds more than ~24 000 lines -- all the (layer, column)
            workgroups of a tile read one slice of the line store, which should stay in an XCD's 4 MB L2 next to everything
            else: G1 longwave, 64 columns per launch, 256-cell tiles (79 000 lines, 2.8 MB of packed records) 40.2 ms,
-           128-cell 36.5, 64-cell 34.9 (scripts/tile_sweep.sh). */
+           128-cell 36.5, 64-cell 34.9 (a tile-size sweep of bench.py; the script is at commit 625d7b3). */
         /* ONE column of that band with the round-4 lean first pass: 128-cell tiles in four slices 0.559 ms, 64-cell tiles
            in two 0.594, 256-cell in eight 0.581 (scripts/sweep_one_column.py) -- a lone column stops at 128 */
         /* Round 5 (all layers on the lean loop, region 2 inside it): with many columns the wide tile is ahead again -- G1
