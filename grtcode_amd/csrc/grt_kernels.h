@@ -160,6 +160,10 @@ typedef struct GrtGasOpticsArgs
     int skip_tables;          /* != 0: leave the spectral tables' part (continua, CFC, CIA) out of tau: the caller adds it where
                                  it reads tau (the pipeline's fused solvers, GrtContinua) -- a table entry is then read once
                                  per grid point and column instead of once per layer as well */
+    int narrow;               /* set by the plan (two-pass form, single-level gather): the band ends below 4 000 cm-1 (the
+                                 longwave: Doppler widths far below the grid step), and the first pass takes its narrow-Doppler
+                                 instance, whose ring and lean loop have a short form for waves in which only a line's OWN grid
+                                 point can be anything but Lorentzian.  (The last field: no kernel argument moved with it.) */
 } GrtGasOpticsArgs;
 
 /* What a kernel needs to add the spectral tables' part of the gas optical depth itself (write_tile's expressions in

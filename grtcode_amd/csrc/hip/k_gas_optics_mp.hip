@@ -65,12 +65,17 @@ __device__ __forceinline__ void drain_class(double *acc, Queue const *q, int wav
 // grids want: a tile is 512 points, so at 0.1 cm-1 the one-pass form prepares every line twice.
 // TREE (two-pass form on fine grids): the accumulator spans the tile and `halo` < fsteps points either side -- all
 // that a near field can reach -- and the far field is left to the cell hierarchy (gas_optics_tree_kernel).
-// LEAN: the launch covers wavenumbers whose Doppler widths lie far below the grid step (the longwave band at 1 cm-1):
-// the ring has a lean form for waves in which only a line's OWN grid point can be anything but Lorentzian.
+// K: moments per cell -- kMom, or kMomWide for the tree form on sparse lines (GrtGasOpticsArgs.mom_terms).
+// NARROW (GrtGasOpticsArgs.narrow): the launch covers wavenumbers whose Doppler widths lie far below the grid step (the
+// longwave band at 1 cm-1): the ring and the lean loop have a short form for waves in which only a line's OWN grid point
+// can be anything but Lorentzian.
 // PROBE: the instrumented instance (GrtGasOpticsArgs.probe): per-workgroup clocks and event counts, for the cost
 // analysis of scripts/line_cost_by_wavenumber.py; the production instances carry none of it.
+// LEAN_LOOP (GrtGasOpticsArgs.lean; two-pass form, single-level gather): the workgroup's lines go through the lean line
+// loop, kLeanP lines per lane (mp_lean_block.inc), wherever its near fields are seven points wide.
 constexpr int kProbeWords = 24;
-template <bool TWO_PASS, bool TREE, int K, bool LEAN = false, bool PROBE = false, int LEANP = 0>
+constexpr int kLeanP = 2;
+template <bool TWO_PASS, bool TREE, int K, bool NARROW = false, bool PROBE = false, bool LEAN_LOOP = false>
 __device__ __forceinline__ void mp_kernel_body(GrtGasOpticsArgs const &a, long long fsteps_ll, unsigned ngroups,
                                                unsigned perm_stride, int ncell, int nacc, int halo)
 {
@@ -318,7 +323,7 @@ __device__ __forceinline__ void mp_kernel_body(GrtGasOpticsArgs const &a, long l
         if constexpr (PROBE) t0 = __builtin_readcyclecounter();
         {
             // (region 4 in packed registers: the lean kernel's shortwave instance -- gas_optics_dev.h)
-            constexpr bool kPacked4 = LEANP > 0 && !LEAN;
+            constexpr bool kPacked4 = LEAN_LOOP && !NARROW;
             if (cls == 0) drain_class<0, kSplit ? 4 : 0, false>(acc, nq, wave, first, count, lane);
             else if (cls == 1) drain_class<1, 1, kPacked4>(acc, nq, wave, first, count, lane);
             else if (cls == 2) drain_class<2, 2, kPacked4>(acc, nq, wave, first, count, lane);
@@ -385,7 +390,7 @@ __device__ __forceinline__ void mp_kernel_body(GrtGasOpticsArgs const &a, long l
     // The workgroup's lines: lean blocks while that form applies and its list of handed-over lines has room; then the
     // general form for the listed lines and for every block the lean loop did not take.
     uint64_t base = walk_first;
-    if constexpr (LEANP > 0)
+    if constexpr (LEAN_LOOP)
     {
         if (lean_ok && walk_first < jend)
         {
@@ -407,7 +412,7 @@ __device__ __forceinline__ void mp_kernel_body(GrtGasOpticsArgs const &a, long l
     {
         bool listed = false;
         uint64_t bj = 0;
-        if constexpr (LEANP > 0)
+        if constexpr (LEAN_LOOP)
         {
             if (x < xcount)
             {
@@ -432,7 +437,7 @@ __device__ __forceinline__ void mp_kernel_body(GrtGasOpticsArgs const &a, long l
             {
                 // (lines the lean form handed over: flagged ones, and centres too close to halfway between two grid points)
                 unsigned long long mk = 0ull;
-                if constexpr (LEANP > 0)
+                if constexpr (LEAN_LOOP)
                 {
                     mk = raw->xl_mask[wave][x][p];
                 }
@@ -641,23 +646,22 @@ __global__ __launch_bounds__(kBlock) void gas_optics_mp_kernel(GrtGasOpticsArgs 
 // **5 waves 42.1 + 108.0** (80-entry queues: 43.3 + 109.1), 6 waves (80 VGPRs, 96 bytes of scratch) 43.1 + 110.7,
 // 7 waves 46.8 + 113.1.
 constexpr int kMpWaves = 5;
-template <bool TWO_PASS, bool TREE, int K, bool LEAN = false>
+template <bool TWO_PASS, bool TREE, int K, bool NARROW = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kMpWaves, kMpWaves)))
 void gas_optics_mp_kernel_w5(GrtGasOpticsArgs a, long long fsteps_ll, unsigned ngroups, unsigned perm_stride, int ncell,
                              int nacc, int halo)
 {
-    mp_kernel_body<TWO_PASS, TREE, K, LEAN>(a, fsteps_ll, ngroups, perm_stride, ncell, nacc, halo);
+    mp_kernel_body<TWO_PASS, TREE, K, NARROW>(a, fsteps_ll, ngroups, perm_stride, ncell, nacc, halo);
 }
 
-// First pass of the two-pass form with the LEAN line loop (see mp_kernel_body): LEANP lines per lane.
+// First pass of the two-pass form with the lean line loop (see mp_kernel_body<..., LEAN_LOOP>).
 constexpr int kLeanWaves = 4;
-constexpr int kLeanP = 2;
-template <bool LEAN, int LEANP>
+template <bool NARROW>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kLeanWaves, kLeanWaves)))
 void gas_optics_lean_kernel(GrtGasOpticsArgs a, long long fsteps_ll, unsigned ngroups, unsigned perm_stride, int ncell,
                             int nacc, int halo)
 {
-    mp_kernel_body<true, false, kMom, LEAN, false, LEANP>(a, fsteps_ll, ngroups, perm_stride, ncell, nacc, halo);
+    mp_kernel_body<true, false, kMom, NARROW, false, true>(a, fsteps_ll, ngroups, perm_stride, ncell, nacc, halo);
 }
 
 // The instrumented instance of the tree form on sparse lines (twelve moments), see mp_kernel_body<..., PROBE>.
@@ -669,12 +673,12 @@ void gas_optics_mp_probe_wide_kernel(GrtGasOpticsArgs a, long long fsteps_ll, un
 }
 
 // The instrumented instance of the two-pass first pass (single-level form), see mp_kernel_body<..., PROBE>.
-template <bool LEAN>
+template <bool NARROW>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void gas_optics_mp_probe_kernel(GrtGasOpticsArgs a, long long fsteps_ll, unsigned ngroups, unsigned perm_stride, int ncell,
                                 int nacc, int halo)
 {
-    mp_kernel_body<true, false, kMom, LEAN, true>(a, fsteps_ll, ngroups, perm_stride, ncell, nacc, halo);
+    mp_kernel_body<true, false, kMom, NARROW, true>(a, fsteps_ll, ngroups, perm_stride, ncell, nacc, halo);
 }
 
 // subtree_tile > 0: the tree form's first pass with moments straight to global memory, which ends by building the tile's
@@ -794,9 +798,11 @@ extern "C" int grt_launch_gas_optics_mp(void *stream, GrtGasOpticsArgs const *a)
     unsigned long long const tiles = (a->nw + a->tile - 1)/a->tile;
     bool const items = a->tile_items != nullptr;
     bool const tree = a->tree_levels > 0;
-    // (a work list: flat two-pass form only, none of these launches; the lean loop where it fits; 64-point near blocks: tree form)
+    // (a work list: flat two-pass form only, none of these launches; the lean loop where it fits; the narrow-Doppler instance:
+    // single-level two-pass form; 64-point near blocks: tree form)
     if ((items && (a->fast != 3 || a->tile_ranges == nullptr || a->n_items == 0 || tree || a->deterministic || a->probe != NULL))
-        || (a->lean && (a->probe != NULL || !grt_gas_optics_lean_shape(a))) || (a->near_block != 0 && (a->near_block != 64 || !tree)))
+        || (a->lean && (a->probe != NULL || !grt_gas_optics_lean_shape(a))) || (a->narrow && (a->fast != 3 || tree))
+        || (a->near_block != 0 && (a->near_block != 64 || !tree)))
     {
         return (int)hipErrorInvalidValue;
     }
@@ -853,63 +859,21 @@ extern "C" int grt_launch_gas_optics_mp(void *stream, GrtGasOpticsArgs const *a)
         {
             return (int)hipErrorInvalidValue;
         }
+        // the first pass's instance: the tree form's (twelve moments, instrumented or not; eight), or the single-level form's --
+        // instrumented, lean line loop or general loop, each for narrow Doppler widths (GrtGasOpticsArgs.narrow) or not
+        void (*first_pass)(GrtGasOpticsArgs, long long, unsigned, unsigned, int, int, int);
+        if (wide && a->probe != NULL) first_pass = gas_optics_mp_probe_wide_kernel;
+        else if (wide) first_pass = gas_optics_mp_kernel<true, true, kMomWide>;
+        else if (tree) first_pass = gas_optics_mp_kernel_w5<true, true, kMom>;
+        else if (a->probe != NULL) first_pass = a->narrow ? gas_optics_mp_probe_kernel<true> : gas_optics_mp_probe_kernel<false>;
+        else if (a->lean) first_pass = a->narrow ? gas_optics_lean_kernel<true> : gas_optics_lean_kernel<false>;
+        else first_pass = a->narrow ? gas_optics_mp_kernel_w5<true, false, kMom, true> : gas_optics_mp_kernel_w5<true, false, kMom>;
         for (int phase = 0; phase < nphase; ++phase)
         {
             b.tile_phase = phase;
             b.tile_nphase = nphase;
-            if (wide && a->probe != NULL)
-            {
-                hipLaunchKernelGGL(gas_optics_mp_probe_wide_kernel, dim3((unsigned)blocks), dim3(kBlock), lds, s, b,
-                                   fsteps, (unsigned)ngroups, golden_stride(ngroups), ncell, nacc, halo);
-            }
-            else if (wide)
-            {
-                hipLaunchKernelGGL((gas_optics_mp_kernel<true, true, kMomWide>), dim3((unsigned)blocks), dim3(kBlock), lds, s, b,
-                                   fsteps, (unsigned)ngroups, golden_stride(ngroups), ncell, nacc, halo);
-            }
-            else if (tree)
-            {
-                hipLaunchKernelGGL((gas_optics_mp_kernel_w5<true, true, kMom>), dim3((unsigned)blocks), dim3(kBlock), lds, s, b,
-                                   fsteps, (unsigned)ngroups, golden_stride(ngroups), ncell, nacc, halo);
-            }
-            else
-            {
-                // (a band that ends below 4 000 cm-1 -- the longwave -- takes the instance with the lean ring: 6.05 -> 5.9 ms at
-                // 1 cm-1; on the shortwave band the extra code cost more than the few waves it serves gained)
-                if (a->probe != NULL)
-                {
-                    if (a->w0 + (double)a->nw*a->wres <= 4000.)
-                    {
-                        hipLaunchKernelGGL((gas_optics_mp_probe_kernel<true>), dim3((unsigned)blocks), dim3(kBlock), lds, s, b,
-                                           fsteps, (unsigned)ngroups, golden_stride(ngroups), ncell, nacc, halo);
-                    }
-                    else
-                    {
-                        hipLaunchKernelGGL((gas_optics_mp_probe_kernel<false>), dim3((unsigned)blocks), dim3(kBlock), lds, s, b,
-                                           fsteps, (unsigned)ngroups, golden_stride(ngroups), ncell, nacc, halo);
-                    }
-                }
-                else if (b.lean && a->w0 + (double)a->nw*a->wres <= 4000.)
-                {
-                    hipLaunchKernelGGL((gas_optics_lean_kernel<true, kLeanP>), dim3((unsigned)blocks), dim3(kBlock), lds, s, b,
-                                       fsteps, (unsigned)ngroups, golden_stride(ngroups), ncell, nacc, halo);
-                }
-                else if (b.lean)
-                {
-                    hipLaunchKernelGGL((gas_optics_lean_kernel<false, kLeanP>), dim3((unsigned)blocks), dim3(kBlock), lds, s, b,
-                                       fsteps, (unsigned)ngroups, golden_stride(ngroups), ncell, nacc, halo);
-                }
-                else if (a->w0 + (double)a->nw*a->wres <= 4000.)
-                {
-                    hipLaunchKernelGGL((gas_optics_mp_kernel_w5<true, false, kMom, true>), dim3((unsigned)blocks), dim3(kBlock), lds, s, b,
-                                       fsteps, (unsigned)ngroups, golden_stride(ngroups), ncell, nacc, halo);
-                }
-                else
-                {
-                    hipLaunchKernelGGL((gas_optics_mp_kernel_w5<true, false, kMom>), dim3((unsigned)blocks), dim3(kBlock), lds, s, b,
-                                       fsteps, (unsigned)ngroups, golden_stride(ngroups), ncell, nacc, halo);
-                }
-            }
+            hipLaunchKernelGGL(first_pass, dim3((unsigned)blocks), dim3(kBlock), lds, s, b, fsteps, (unsigned)ngroups,
+                               golden_stride(ngroups), ncell, nacc, halo);
         }
         if (a->profile_tag) grt_profile_end(stream, slot);
         b.nslice = 1;

@@ -331,12 +331,12 @@
                     return;
                 }
                 float const amp_f32 = (float)amp;
-                bool lean = false;
-                if constexpr (LEAN)
+                bool narrow = false;
+                if constexpr (NARROW)
                 {
                     // (1 - |delta|) wr >= XLIM0 for every line of the wave: only a line's own grid point can be anything
                     // but Lorentzian (the longwave band: Doppler widths far below the grid step)
-                    lean = __ballot(valid & !lorentz & !((1.f - fabsf(delta_c))*wr >= 1.001f*xlim0)) == 0ull;
+                    narrow = __ballot(valid & !lorentz & !((1.f - fabsf(delta_c))*wr >= 1.001f*xlim0)) == 0ull;
                 }
                 float nv[8];
 #pragma unroll
@@ -348,7 +348,7 @@
                     float const d = fmaf(xi, xi, yq);
                     bool const inside = (f >= lo_n) & (f <= hi_n);
                     float kf;
-                    if (LEAN && lean && k != 3)
+                    if (NARROW && narrow && k != 3)
                     {
                         kf = cl*__builtin_amdgcn_rcpf(d);                     // beyond XLIM0: the Lorentzian (RFM_voigt.c:103)
                     }
@@ -438,14 +438,14 @@
             return;
         }
         float const amp_f32 = (float)amp;
-        // LEAN: where (1 - |delta|) wr >= XLIM0 for every line of the wave, region 1 and the near-centre points end within
+        // NARROW: where (1 - |delta|) wr >= XLIM0 for every line of the wave, region 1 and the near-centre points end within
         // a line's own grid point; k_own is the general form's value there, computed once with the same expressions
-        bool lean_ok = false;
+        bool narrow_ok = false;
         float k_own = 0.f;
-        if constexpr (LEAN)
+        if constexpr (NARROW)
         {
-            lean_ok = __ballot(valid & !lorentz & !((1.f - fabsf(delta_c))*wr >= 1.001f*xlim0)) == 0ull;
-            if (lean_ok)
+            narrow_ok = __ballot(valid & !lorentz & !((1.f - fabsf(delta_c))*wr >= 1.001f*xlim0)) == 0ull;
+            if (narrow_ok)
             {
                 float const xq0 = ndcr*ndcr, d0 = fmaf(ndcr, ndcr, yq);
                 bool const outer = xq0 >= xq_near;
@@ -572,7 +572,7 @@
                 GRT_ACC_ADD(&acc[f + 16 - A0], (double)token.y);
             }
         };
-        std::integral_constant<int, 3> const lean{};
+        std::integral_constant<int, 3> const narrow_form{};
         // the distance from the centre index within which a line has region-1 points (none: pure Lorentz line)
         float const reach1 = (valid & !lorentz) ? fmaf(xlim0, rwr, 1.5f) : -1e30f;
         for (int done = 0; done < span;)
@@ -580,13 +580,13 @@
             int const left = span - done;                                // grid points still to cover (longest row)
             if (left <= 4)
             {
-                if (LEAN && lean_ok) ring_block(fb + done, std::integral_constant<int, 4>{}, lean);
+                if (NARROW && narrow_ok) ring_block(fb + done, std::integral_constant<int, 4>{}, narrow_form);
                 else ring_block(fb + done, std::integral_constant<int, 4>{}, general);   // four tokens per grid point, four steps
                 done += 4;
             }
             else if (left <= 12)
             {
-                if (LEAN && lean_ok) ring_block(fb + done, std::integral_constant<int, 8>{}, lean);
+                if (NARROW && narrow_ok) ring_block(fb + done, std::integral_constant<int, 8>{}, narrow_form);
                 else ring_block(fb + done, std::integral_constant<int, 8>{}, general);   // 8, or 8 + 4 rather than 16
                 done += 8;
             }

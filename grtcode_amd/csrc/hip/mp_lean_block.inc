@@ -4,7 +4,7 @@
 // why these are lambdas of the kernel body.
 
     // ---------------------------------------------------------------------------------------------------------
-    // The LEAN form of the line loop (LEANP > 0: that many lines per lane; first pass of the two-pass form with the
+    // The LEAN form of the line loop (LEAN_LOOP: kLeanP lines per lane; first pass of the two-pass form with the
     // single-level gather).  Round 4's measurements (scripts/valu_mix*.hip, profiles/r4_*): the general loop above is not
     // waiting on latencies, it fills the vector pipe -- with instructions that run at half rate on this chip (everything
     // fp64, every conversion, compare, select, DPP move, min/max/floor; 4.5 cycles per wave against 2.4 for an fp32
@@ -26,8 +26,8 @@
     // A workgroup takes this form if its near fields are seven points wide (R = 3: near_radius); otherwise every block of
     // lines goes through general_block as before.
     // ---------------------------------------------------------------------------------------------------------
-    static_assert(LEANP == 0 || LEANP == 2, "the lean loop keeps the two lines of a lane in the halves of packed registers");
-    constexpr int kLinesPerLane = LEANP > 0 ? LEANP : 1;
+    static_assert(kLeanP == 2, "the lean loop keeps the two lines of a lane in the halves of packed registers");
+    constexpr int kLinesPerLane = LEAN_LOOP ? kLeanP : 1;
     [[maybe_unused]] bool lean_ok = false;
     // (per-slot and per-isotopologue tables, one array per quantity: a line's look-up then lands in its half of a register pair)
     [[maybe_unused]] LeanTables *lt = nullptr;
@@ -46,7 +46,7 @@
     //   nc_one       only a line's own grid point can be a near-centre point (|x| < XLIM1); nc_three: or its two neighbours
     [[maybe_unused]] unsigned tflags = 0u;          // (kTf*: gas_optics_mp_dev.h, lean_tile_flags)
     auto uniform_flag = [](bool b) { return __builtin_amdgcn_readfirstlane((int)b) != 0; };
-    if constexpr (LEANP > 0)
+    if constexpr (LEAN_LOOP)
     {
         size_t const lean_off = ((size_t)(reinterpret_cast<unsigned char *>(invr + 1) - smem) + 15) & ~(size_t)15;
         lt = reinterpret_cast<LeanTables *>(smem + lean_off);
@@ -111,7 +111,7 @@
     // the shortwave launch 3 % shorter and three of 600 soak cases 2e-6 to 4e-6 wrong.)
     [[maybe_unused]] auto drain_raw = [&](int const first, int const count)
     {
-        if constexpr (LEANP > 0)
+        if constexpr (LEAN_LOOP)
         {
             bool const on = lane < count;
             int const i = first + (on ? lane : 0);
@@ -150,7 +150,7 @@
     [[maybe_unused]] unsigned const lo_first = (unsigned)(jbeg - jal);      // 0, or 1: the range begins on an odd index
     [[maybe_unused]] auto lean_fetch = [&](unsigned const b)
     {
-        if constexpr (LEANP > 0)
+        if constexpr (LEAN_LOOP)
         {
             unsigned const qlast = (nrel - 1u) >> 1;
             unsigned const qb = b < nrel ? (b >> 1) : qlast;
@@ -177,7 +177,7 @@
     // (raw->xl_*).
     [[maybe_unused]] auto lean_block = [&](unsigned const base)      // (base: counted from jal)
     {
-        if constexpr (LEANP > 0)
+        if constexpr (LEAN_LOOP)
         {
             // lines of this block: base + lo .. base + hi - 1 (lo = 1: the workgroup's range begins on an odd index)
             int const lo = base == 0u ? (int)lo_first : 0;
@@ -282,9 +282,9 @@
             // on nothing asks about validity -- its XLIM0 and XLIM1 below are zero, so it has no region 1 and no core point)
             int const o[2] = {valid[0] ? c[0] - cr : 0, valid[1] ? c[1] - cr : 0};
             bool const odd[2] = {(unsigned)o[0] > 1u, (unsigned)o[1] > 1u};
-            // (the longwave band's usual case, 308 lines per cell: no second cell, no weights; the shortwave instance, 30
-            // lines per cell, does not ask)
-            bool const single = LEAN && ballot_b((o[0] | o[1]) != 0) == 0ull;
+            // (the longwave band's usual case, 308 lines per cell: no second cell, no weights; the instance that is not
+            // NARROW -- the shortwave band, 30 lines per cell -- does not ask)
+            bool const single = NARROW && ballot_b((o[0] | o[1]) != 0) == 0ull;
             v2f const W0 = {o[0] == 0 ? 1.f : 0.f, o[1] == 0 ? 1.f : 0.f};
             v2f const W1 = {o[0] == 1 ? 1.f : 0.f, o[1] == 1 ? 1.f : 0.f};
             // ---- moments of the Lorentzian about the cell centre (see general_block) ----

@@ -14,7 +14,7 @@
 typedef struct LaunchPlan
 {
     GrtGasOpticsArgs a;       /* the common fields and the form: fast, tile, nslice, tree_levels, mom_terms, rcap, halo, lean,
-                                 direct_near, near_block, deterministic, gmom_stride; no column group, no scratch */
+                                 narrow, direct_near, near_block, deterministic, gmom_stride; no column group, no scratch */
     int tables;               /* the tile tables are built for this launch (two-pass form, < 2^32 lines in the store) */
     int items;                /* ... and their work list taken in place of tiles x nslice equal slices (unless a probe is) */
     double pmax;              /* the batch's largest layer pressure: what the tile tables must cover */
@@ -375,6 +375,9 @@ static void plan(GasOptics_t const *go, int ncol, LaunchPlan *p)
     {
         char const *lean = getenv("GRT_LEAN");                 /* GRT_LEAN=0: the general line loop everywhere */
         a->lean = !(lean != NULL && lean[0] == '0') && grt_gas_optics_lean_shape(a);
+        /* a single-level band that ends below 4 000 cm-1 -- the longwave -- takes the narrow-Doppler instance: 6.05 -> 5.9 ms
+           at 1 cm-1; on the shortwave band the extra code cost more than the few waves it serves gained */
+        a->narrow = a->tree_levels == 0 && a->w0 + (double)a->nw*a->wres <= 4000.;
         a->near_block = a->tree_levels > 0 && grt_tree_gather_by_wave(fsteps) ? 64 : 0;
         p->moment_bytes = sizeof(float)*(size_t)a->gmom_stride*(size_t)go->num_layers;
         /* (the cell tiles' near-field radii, worked out once per launch for the single-level gather's workgroups) */
