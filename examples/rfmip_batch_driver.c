@@ -21,9 +21,12 @@
  * Usage:  rfmip_batch_driver HITRAN.par SOLAR.csv COLUMNS.bin [-h2o-ctm DIR] [-o3-ctm FILE] [-CFC-11 FILE ppmv]
  *             [-CFC-12 FILE ppmv] [-N2-N2 FILE] [-O2-N2 FILE] [-O2-O2 FILE] [-w-lw W0 -W-lw WN -r-lw DW]
  *             [-w-sw W0 -W-sw WN -r-sw DW] [-chunk N] [-fast 0|1|2|3] [-d DEVICE]
- *             [-ranks N -rank K -rendezvous DIR [-transport rccl|files]]
+ *             [-ranks N -rank K -rendezvous DIR [-transport rccl|files]] [-profiles]
  * Output: one line per column "col <i>: rlut rlus rldt rlds rsut rsus rsdt rsds" [W m-2] (zeros for the shortwave
- * of night columns).
+ * of night columns).  With -profiles each column's line is followed by its broadband fluxes at every level, top first,
+ * "lev <k>: rlu rld rsu rsd" [W m-2], and the heating rate of every layer, "lay <j>: hr_lw hr_sw" [K day-1]
+ * (grt_pipeline_run_profiles; its shortwave is the two-sweep form, so lev 0's rsu may differ from the col line's rsut
+ * in the last digits).
  *
  * Several GPUs of one node: start one process per GPU with the same arguments plus -ranks N -rank K (K = 0..N-1,
  * normally with -d K) and a directory all of them see.  Every rank computes its contiguous block of the columns
@@ -230,6 +233,15 @@ int main(int argc, char **argv)
     check(grt_pipeline_create(&pipe_night, &lbl[0], NULL, chunk, -1, emissivity, NULL, NULL));
     fp_t *fluxes_dev;
     check(grt_device_malloc(device, (void **)&fluxes_dev, sizeof(fp_t)*chunk*GRT_FLUXES_PER_COLUMN));
+    /* -profiles: per column a row of the level fluxes [4][V] and then the heating rates [2][L] */
+    int const profiles = option(argc, argv, "-profiles", 0) != NULL;
+    int const prow = GRT_PROFILE_ROWS_PER_COLUMN*V + GRT_HEATING_ROWS_PER_COLUMN*L;
+    fp_t *levels_dev = NULL, *heating_dev = NULL;
+    if (profiles)
+    {
+        check(grt_device_malloc(device, (void **)&levels_dev, sizeof(fp_t)*chunk*GRT_PROFILE_ROWS_PER_COLUMN*V));
+        check(grt_device_malloc(device, (void **)&heating_dev, sizeof(fp_t)*chunk*GRT_HEATING_ROWS_PER_COLUMN*L));
+    }
     /* this rank's block of the columns */
     int const world = (int)number(argc, argv, "-ranks", 1.), rank = (int)number(argc, argv, "-rank", 0.);
     int shard_first = 0, shard_count = ncol;
@@ -249,6 +261,9 @@ int main(int argc, char **argv)
     int const per_rank = (ncol + world - 1)/world;
     fp_t *fluxes = calloc((size_t)per_rank*world*GRT_FLUXES_PER_COLUMN, sizeof(fp_t));
     fp_t *host = malloc(sizeof(fp_t)*chunk*GRT_FLUXES_PER_COLUMN);
+    fp_t *profile = profiles ? calloc((size_t)per_rank*world*prow, sizeof(fp_t)) : NULL;
+    fp_t *host_levels = profiles ? malloc(sizeof(fp_t)*chunk*GRT_PROFILE_ROWS_PER_COLUMN*V) : NULL;
+    fp_t *host_heating = profiles ? malloc(sizeof(fp_t)*chunk*GRT_HEATING_ROWS_PER_COLUMN*L) : NULL;
     /* day and night columns go through different pipelines; keep chunks contiguous in each class */
     for (int night = 0; night < 2; ++night)
     {
@@ -286,6 +301,21 @@ int main(int argc, char **argv)
                 memcpy(fluxes + (size_t)ids[first + j]*GRT_FLUXES_PER_COLUMN, host + (size_t)j*GRT_FLUXES_PER_COLUMN,
                        sizeof(fp_t)*(night ? GRT_FLUXES_PER_BAND : GRT_FLUXES_PER_COLUMN));
             }
+            if (profiles)
+            {
+                /* (the night pipeline has no shortwave band: its shortwave rows come back zero) */
+                size_t const nl = (size_t)GRT_PROFILE_ROWS_PER_COLUMN*V, nh = (size_t)GRT_HEATING_ROWS_PER_COLUMN*L;
+                check(grt_pipeline_run_profiles(pipe, &cols, levels_dev, heating_dev, NULL));
+                check(grt_pipeline_sync(pipe));
+                check(grt_device_to_host(device, host_levels, levels_dev, sizeof(fp_t)*m*nl));
+                check(grt_device_to_host(device, host_heating, heating_dev, sizeof(fp_t)*m*nh));
+                for (int j = 0; j < m; ++j)
+                {
+                    fp_t *row = profile + (size_t)ids[first + j]*prow;
+                    memcpy(row, host_levels + j*nl, sizeof(fp_t)*nl);
+                    memcpy(row + nl, host_heating + j*nh, sizeof(fp_t)*nh);
+                }
+            }
             free(cp); free(ct); free(ctl); free(cts); free(cmu); free(ctsi); free(cmol); free(ccfc); free(ccia);
         }
         free(ids);
@@ -304,6 +334,16 @@ int main(int argc, char **argv)
                 memcpy(fluxes, all, sizeof(fp_t)*(size_t)ncol*GRT_FLUXES_PER_COLUMN);
                 free(all);
             }
+            if (profiles)
+            {
+                fp_t *all_rows = rank == 0 ? calloc((size_t)per_rank*world*prow, sizeof(fp_t)) : NULL;
+                check(grt_multi_gather_rows(multi, profile + (size_t)shard_first*prow, ncol, prow, all_rows, 0));
+                if (rank == 0)
+                {
+                    memcpy(profile, all_rows, sizeof(fp_t)*(size_t)ncol*prow);
+                    free(all_rows);
+                }
+            }
         }
         else
         {
@@ -317,6 +357,21 @@ int main(int argc, char **argv)
             if (rank == 0) check(grt_device_to_host(device, fluxes, all_dev, sizeof(fp_t)*(size_t)ncol*GRT_FLUXES_PER_COLUMN));
             check(grt_device_free(device, local_dev));
             check(grt_device_free(device, all_dev));
+            if (profiles)
+            {
+                size_t const rows = sizeof(fp_t)*(size_t)per_rank*prow;
+                local_dev = NULL;
+                all_dev = NULL;
+                check(grt_device_malloc(device, (void **)&local_dev, rows));
+                if (rank == 0) check(grt_device_malloc(device, (void **)&all_dev, rows*world));
+                if (shard_count > 0) check(grt_host_to_device(device, local_dev, profile + (size_t)shard_first*prow,
+                                                              sizeof(fp_t)*(size_t)shard_count*prow));
+                check(grt_multi_gather_rows(multi, local_dev, ncol, prow, all_dev, 1));
+                check(grt_pipeline_sync(pipe_day));
+                if (rank == 0) check(grt_device_to_host(device, profile, all_dev, sizeof(fp_t)*(size_t)ncol*prow));
+                check(grt_device_free(device, local_dev));
+                check(grt_device_free(device, all_dev));
+            }
         }
         double seconds = 0.;
         check(grt_multi_max(multi, &seconds));             /* everybody is done before anybody tears down */
@@ -326,10 +381,30 @@ int main(int argc, char **argv)
     {
         fp_t const *x = fluxes + (size_t)c*GRT_FLUXES_PER_COLUMN;
         printf("col %d: %.15e %.15e %.15e %.15e %.15e %.15e %.15e %.15e\n", c, x[0], x[1], x[3], x[4], x[6], x[7], x[9], x[10]);
+        if (profiles)
+        {
+            fp_t const *r = profile + (size_t)c*prow, *h = r + GRT_PROFILE_ROWS_PER_COLUMN*V;
+            for (int k = 0; k < V; ++k)
+            {
+                printf("lev %d: %.15e %.15e %.15e %.15e\n", k, r[k], r[V + k], r[2*V + k], r[3*V + k]);
+            }
+            for (int j = 0; j < L; ++j)
+            {
+                printf("lay %d: %.15e %.15e\n", j, h[j], h[L + j]);
+            }
+        }
     }
     check(grt_pipeline_destroy(&pipe_day));
     check(grt_pipeline_destroy(&pipe_night));
     check(grt_device_free(device, fluxes_dev));
+    if (profiles)
+    {
+        check(grt_device_free(device, levels_dev));
+        check(grt_device_free(device, heating_dev));
+    }
+    free(profile);
+    free(host_levels);
+    free(host_heating);
     check(destroy_solar_flux(&solar));
     check(destroy_gas_optics(&lbl[0]));
     check(destroy_gas_optics(&lbl[1]));

@@ -18,6 +18,8 @@ NUM_MOLS, NUM_CFCS, NUM_CIAS, MAX_NUM_CIAS = 53, 21, 2, 3
 DIR_PATH_LEN, MOL_NAME_LEN, CFC_NAME_LEN, CIA_NAME_LEN = 1024, 8, 16, 8
 LINE_SAMPLE = 2
 GRT_FLUXES_PER_COLUMN = 12
+GRT_PROFILE_ROWS_PER_COLUMN = 4     # LW up, LW down, SW up, SW down, each [V]
+GRT_HEATING_ROWS_PER_COLUMN = 2     # LW, SW, each [V-1]
 RETURN_CODES = ["GRTCODE_SUCCESS", "GRTCODE_INVALID_ERR", "GRTCODE_DIVBYZERO_ERR", "GRTCODE_OVERFLOW_ERR",
                 "GRTCODE_UNDERFLOW_ERR", "GRTCODE_SENTINEL_ERR", "GRTCODE_NULL_ERR", "GRTCODE_NON_NULL_ERR",
                 "GRTCODE_RANGE_ERR", "GRTCODE_VALUE_ERR", "GRTCODE_COMPILER_ERR", "GRTCODE_IO_ERR",
@@ -137,10 +139,10 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
-grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
+grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
 grt_err_begin grt_err_frame grt_log grt_gmalloc grt_gfree grt_gmemset grt_gmemcpy
 """.split()
 
@@ -175,6 +177,8 @@ def load_library(path=None):
     lib.grt_device_to_host.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
     lib.grt_host_to_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
     lib.grt_pipeline_run.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.c_void_p]
+    lib.grt_pipeline_run_profiles.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.grt_multi_gather_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.grt_pipeline_sync.argtypes = [C.c_void_p]
     lib.grt_pipeline_stream.argtypes = [C.c_void_p]
     lib.grt_pipeline_views.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_void_p)] * 6
@@ -452,6 +456,8 @@ class Pipeline:
                                               _dp(s) if s is not None else None, int(spectral)))
         self.out = DeviceBuffer(self.device, 8 * GRT_FLUXES_PER_COLUMN * max_columns)
         self.max_columns = max_columns
+        self.num_levels = (lw_gas or sw_gas).num_levels
+        self.prof = None        # run_profiles' device outputs: allocated at its first call
 
     def run(self, gcols, out_ptr=None):
         check(self.lib.grt_pipeline_run(self.p, C.byref(gcols), out_ptr if out_ptr is not None else self.out.ptr))
@@ -466,6 +472,27 @@ class Pipeline:
         self.sync()
         return self.out.to_host((ncol, GRT_FLUXES_PER_COLUMN))
 
+    def run_profiles(self, gcols):
+        """grt_pipeline_run_profiles into this object's device buffers (profiles() reads them)."""
+        V, n = self.num_levels, self.max_columns
+        if self.prof is None:
+            self.prof = {"levels": DeviceBuffer(self.device, 8 * n * GRT_PROFILE_ROWS_PER_COLUMN * V),
+                         "heating": DeviceBuffer(self.device, 8 * n * GRT_HEATING_ROWS_PER_COLUMN * (V - 1)),
+                         "fluxes": DeviceBuffer(self.device, 8 * n * GRT_FLUXES_PER_COLUMN)}
+        check(self.lib.grt_pipeline_run_profiles(self.p, C.byref(gcols), self.prof["levels"].ptr,
+                                                 self.prof["heating"].ptr, self.prof["fluxes"].ptr))
+
+    def profiles(self, ncol):
+        """The last run_profiles: lw_up, lw_down, sw_up, sw_down [ncol][V] (W m-2, levels top first), lw_heating,
+        sw_heating [ncol][V-1] (K day-1) and fluxes [ncol][12] (grt_pipeline_run's layout)."""
+        self.sync()
+        V = self.num_levels
+        lv = self.prof["levels"].to_host((ncol, GRT_PROFILE_ROWS_PER_COLUMN, V))
+        hr = self.prof["heating"].to_host((ncol, GRT_HEATING_ROWS_PER_COLUMN, V - 1))
+        return dict(lw_up=lv[:, 0].copy(), lw_down=lv[:, 1].copy(), sw_up=lv[:, 2].copy(), sw_down=lv[:, 3].copy(),
+                    lw_heating=hr[:, 0].copy(), sw_heating=hr[:, 1].copy(),
+                    fluxes=self.prof["fluxes"].to_host((ncol, GRT_FLUXES_PER_COLUMN)))
+
     def views(self, band):
         ptrs = [C.c_void_p() for _ in range(6)]
         if not self.spectral:
@@ -476,6 +503,9 @@ class Pipeline:
 
     def destroy(self):
         self.out.free()
+        for buf in (self.prof or {}).values():
+            buf.free()
+        self.prof = None
         check(self.lib.grt_pipeline_destroy(C.byref(self.p)))
 
 

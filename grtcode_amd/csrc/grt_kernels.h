@@ -311,6 +311,21 @@ typedef struct GrtSwArgs
 } GrtSwArgs;
 int grt_launch_sw(void *stream, GrtSwArgs const *a);
 
+/* Profile form of the fused solvers (grt_pipeline_run_profiles): the arguments of the fused form (tau_gas set), but every
+   level's upward and downward flux leaves as trapezoid partial sums, 2 V rows per column at
+   partials[(c*2 V + r)*nblocks + block], r = level (up) and V + level (down), levels top first; reduced with
+   grt_launch_reduce_partials(nrows = ncol*2 V).  The shortwave form always takes the two sweeps and needs `park`
+   (one_sweep and user_level are not read); each wave sums a level as the sweep produces it, in dynamic LDS of
+   2 V x 2 doubles per workgroup.  Rows 0, L and user_level are, bit for bit, the six-row form's (the shortwave's: its
+   two-sweep form's). */
+int grt_launch_lw_profile(void *stream, GrtLwArgs const *a);
+int grt_launch_sw_profile(void *stream, GrtSwArgs const *a);
+/* levels [ncol][4][V] (up, down of band 0, then of band 1) -> heating [ncol][2][V-1] K day-1 (NULL: not formed) from the
+   level pressures pressure [ncol][V] mb, and fluxes [ncol][12] (NULL: not formed) in grt_pipeline_run's layout; the rows of
+   a band whose bit in `bands` is clear are zeroed, level fluxes included. */
+int grt_launch_profile_finish(void *stream, int ncol, int num_levels, int bands, int user_level, double gravity,
+                              double cp, double const *pressure, double *levels, double *heating, double *fluxes);
+
 /* Fused Rayleigh + combine for the clear-sky driver sequence (rayleigh.c:39 +
    optics.c:138-145 with K=2, gas omega=g=0, Rayleigh omega=1,g=0):
    tau_tot = tau_gas + tau_R, omega = tau_R/tau_tot, g = 0/ tau_R.  n_layer [ncol][L]. */

@@ -13,7 +13,7 @@
 //
 // SURVEY.md §8a19 prices it at 1 944 B per wavenumber at 60 layers; measured it is a latency
 // chain -- 120 dependent layer steps with six fp64 exp each on 26 000 threads at 1 cm-1 -- which is why column
-// batches share a launch.  lw_kernel<true> is the fused form of the production pipeline.
+// batches share a launch.  lw_kernel<true, false> is the fused form of the production pipeline.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -62,7 +62,11 @@ __device__ __forceinline__ double extinction(double c1, double tau)
 // FUSED: the clear-sky tail of the pipeline in one kernel -- Rayleigh and the two-object optics combination are formed
 // per layer in registers from tau_gas (same expressions, same order as clear_sky_kernel: identical values), nothing
 // spectral is written, and the six integrated output rows leave as per-block trapezoid partial sums.
-template <bool FUSED>
+// PROFILE (fused form only): every level's upward and downward flux leaves instead, 2 V rows per column: each level's
+// weighted value is summed across the wave where the sweep produces it, the waves' sums wait in dynamic LDS
+// (2 V x kBlock/64 doubles) and the block's sums go to partials[(c*2 V + r)*nblocks + block], r = level (up),
+// V + level (down).  Same association as block_partials: the six-row form's rows come out the same to the bit.
+template <bool FUSED, bool PROFILE>
 __global__ __launch_bounds__(kBlock) void lw_kernel(GrtLwArgs a)
 {
     double const c1[4] = {-14.402613260847248, -3.0302159969901132,
@@ -90,6 +94,8 @@ __global__ __launch_bounds__(kBlock) void lw_kernel(GrtLwArgs a)
     double *fd = FUSED ? nullptr : a.flux_down + (uint64_t)col*a.flux_stride + ii;
     int const user = a.user_level;
     double out[6] = {0., 0., 0., 0., 0., 0.};     // up TOA, up surface, up user, down TOA, down surface, down user
+    extern __shared__ double level_sums[];        // PROFILE: [2 V][kBlock/64]
+    double const pwt = !PROFILE || !live ? 0. : ((i == 0 || i + 1 == a.nw) ? 0.5*a.dw : a.dw);
 
     // (the gas-optics launch left the spectral tables' part of tau to this kernel: a table entry read once per point)
     PointContinua pc;
@@ -128,6 +134,10 @@ __global__ __launch_bounds__(kBlock) void lw_kernel(GrtLwArgs a)
     {
         out[5] = 0.;
     }
+    if (PROFILE && (threadIdx.x & 63) == 0)
+    {
+        level_sums[V*(kBlock/64) + (threadIdx.x >> 6)] = 0.;          // down at the top
+    }
     for (int j = 0; j < L; ++j)
     {
         double const t = layer_tau(j);
@@ -141,7 +151,11 @@ __global__ __launch_bounds__(kBlock) void lw_kernel(GrtLwArgs a)
             I[s] = p + I[s]*ext;
             f += c2[s]*I[s];                                             // longwave.c:195
         }
-        if (FUSED)
+        if (PROFILE)
+        {
+            wave_row_sum<kBlock>(f*pwt, level_sums, V + j + 1);
+        }
+        else if (FUSED)
         {
             out[4] = j + 1 == L ? f : out[4];
             out[5] = j + 1 == user ? f : out[5];
@@ -159,7 +173,11 @@ __global__ __launch_bounds__(kBlock) void lw_kernel(GrtLwArgs a)
         I[s] = emis*bs + (1 - emis)*I[s];                                // longwave.c:202
         f += c2[s]*I[s];
     }
-    if (FUSED)
+    if (PROFILE)
+    {
+        wave_row_sum<kBlock>(f*pwt, level_sums, L);
+    }
+    else if (FUSED)
     {
         out[1] = f;
         out[2] = user == L ? f : out[2];
@@ -181,7 +199,11 @@ __global__ __launch_bounds__(kBlock) void lw_kernel(GrtLwArgs a)
             I[s] = p + I[s]*ext;
             g += c2[s]*I[s];
         }
-        if (FUSED)
+        if (PROFILE)
+        {
+            wave_row_sum<kBlock>(g*pwt, level_sums, j);
+        }
+        else if (FUSED)
         {
             out[0] = j == 0 ? g : out[0];
             out[2] = j == user ? g : out[2];
@@ -191,7 +213,11 @@ __global__ __launch_bounds__(kBlock) void lw_kernel(GrtLwArgs a)
             fu[(uint64_t)j*a.nw] = g;
         }
     }
-    if (FUSED)
+    if (PROFILE)
+    {
+        block_row_partials<kBlock>(level_sums, 2*V, a.partials, (uint64_t)col*2*V, gridDim.x, blockIdx.x);
+    }
+    else if (FUSED)
     {
         // driver.c:302-326: sum 0.5 (f_i + f_{i+1}) dw over the grid = sum weight_i f_i
         double const wt = !live ? 0. : ((i == 0 || i + 1 == a.nw) ? 0.5*a.dw : a.dw);
@@ -205,11 +231,11 @@ __global__ __launch_bounds__(kBlock) void lw_kernel(GrtLwArgs a)
 }
 
 // ---- spectral form of few columns: the layers' terms first, by one thread per (layer, wavenumber) ----
-// One column of the longwave band is 3 250 threads for lw_kernel<false> -- fifty waves on a thousand SIMDs, each with 120
+// One column of the longwave band is 3 250 threads for lw_kernel<false, false> -- fifty waves on a thousand SIMDs, each with 120
 // dependent layer steps of six exp.  What costs in a step does not depend on the step before: lw_terms_kernel fills
 // terms[col][6 j + k][nw] with the four streams' extinctions exp(c1[s] t) and the effective Planck terms of the
 // downward and of the upward sweep; lw_sweeps_kernel carries the four intensities through them, six layers' terms read
-// ahead of the chain at a time.  Same expressions, same order, same doubles as lw_kernel<false>: identical fluxes.
+// ahead of the chain at a time.  Same expressions, same order, same doubles as lw_kernel<false, false>: identical fluxes.
 constexpr int kTermsBlock = 256;
 constexpr int kSweepBlock = 64;
 constexpr int kSweepChunk = 6;
@@ -375,11 +401,24 @@ extern "C" int grt_launch_lw(void *stream, GrtLwArgs const *a)
     dim3 const grid(grt_solver_blocks(a->nw), a->ncol, 1);
     if (fused)
     {
-        hipLaunchKernelGGL(lw_kernel<true>, grid, dim3(kBlock), 0, (hipStream_t)stream, *a);
+        hipLaunchKernelGGL((lw_kernel<true, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, *a);
     }
     else
     {
-        hipLaunchKernelGGL(lw_kernel<false>, grid, dim3(kBlock), 0, (hipStream_t)stream, *a);
+        hipLaunchKernelGGL((lw_kernel<false, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, *a);
     }
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_lw_profile(void *stream, GrtLwArgs const *a)
+{
+    size_t const lds = sizeof(double)*2*(size_t)a->num_levels*(kBlock/64);
+    if (a->ncol < 1 || a->nw < 2 || a->num_levels < 2 || a->tau_gas == nullptr || a->n_layer == nullptr ||
+        a->partials == nullptr || lds > 65536)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL((lw_kernel<true, true>), dim3(grt_solver_blocks(a->nw), a->ncol, 1), dim3(kBlock), lds,
+                       (hipStream_t)stream, *a);
     return (int)hipGetLastError();
 }

@@ -197,7 +197,82 @@ __global__ __launch_bounds__(64) void reduce_partials_kernel(double const *parti
     }
 }
 
+// Last step of grt_pipeline_run_profiles: one thread per (column, band, layer j) reads the band's level fluxes
+// levels[c][2 band + {0: up, 1: down}][V] and forms the heating rate of layer j, between levels j (upper) and j + 1,
+//     H_j = (g/c_p) ((dn_j - up_j) - (dn_{j+1} - up_{j+1}))/(100 (p_{j+1} - p_j)) 86 400   [K day-1, p in mb],
+// and -- thread j = 0 -- the band's six rows of the six-row form (up top, up surface, up user, down top, down surface, down
+// user: grt_pipeline_run's layout).  A band that is not computed (bit clear in `bands`) gets zeros everywhere.
+__global__ __launch_bounds__(kBlock) void profile_finish_kernel(int ncol, int V, int bands, int user, double gravity,
+                                                                double cp, double const *pressure, double *levels,
+                                                                double *heating, double *fluxes)
+{
+    int const L = V - 1;
+    uint64_t const t = (uint64_t)blockIdx.x*kBlock + threadIdx.x;
+    if (t >= (uint64_t)ncol*2*L)
+    {
+        return;
+    }
+    int const j = (int)(t % L);
+    int const band = (int)((t/L) % 2);
+    int const c = (int)(t/(2*(uint64_t)L));
+    double *up = levels + ((uint64_t)c*4 + 2*band)*V;
+    double *dn = up + V;
+    double *six = fluxes ? fluxes + (uint64_t)c*12 + 6*band : nullptr;
+    double *h = heating ? heating + ((uint64_t)c*2 + band)*L + j : nullptr;
+    if (!((bands >> band) & 1))
+    {
+        up[j] = 0.;
+        dn[j] = 0.;
+        if (j + 1 == L)
+        {
+            up[L] = 0.;
+            dn[L] = 0.;
+        }
+        if (h)
+        {
+            *h = 0.;
+        }
+        if (six && j == 0)
+        {
+            for (int k = 0; k < 6; ++k)
+            {
+                six[k] = 0.;
+            }
+        }
+        return;
+    }
+    if (h)
+    {
+        double const *p = pressure + (uint64_t)c*V;
+        double const net_top = dn[j] - up[j], net_bottom = dn[j + 1] - up[j + 1];
+        *h = (gravity/cp)*((net_top - net_bottom)/(100.*(p[j + 1] - p[j])))*86400.;
+    }
+    if (six && j == 0)
+    {
+        six[0] = up[0];
+        six[1] = up[L];
+        six[2] = user >= 0 ? up[user] : 0.;
+        six[3] = dn[0];
+        six[4] = dn[L];
+        six[5] = user >= 0 ? dn[user] : 0.;
+    }
+}
+
 } // namespace
+
+extern "C" int grt_launch_profile_finish(void *stream, int ncol, int num_levels, int bands, int user_level, double gravity,
+                                         double cp, double const *pressure, double *levels, double *heating, double *fluxes)
+{
+    if (ncol < 1 || num_levels < 2 || user_level >= num_levels || levels == nullptr || (heating && pressure == nullptr))
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    uint64_t const threads = (uint64_t)ncol*2*(uint64_t)(num_levels - 1);
+    hipLaunchKernelGGL(profile_finish_kernel, dim3((unsigned)((threads + kBlock - 1)/kBlock)), dim3(kBlock), 0,
+                       (hipStream_t)stream, ncol, num_levels, bands, user_level, gravity, cp, pressure, levels, heating,
+                       fluxes);
+    return (int)hipGetLastError();
+}
 
 extern "C" int grt_launch_reduce_partials(void *stream, double const *partials, int nrows, unsigned nblocks,
                                           double *out, int group, int out_stride, int out_offset)

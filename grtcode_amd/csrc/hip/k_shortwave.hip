@@ -14,7 +14,7 @@
 //     pair is consumed and overwritten by the final fluxes of :308-329,401-405,447-451.
 // Every expression keeps the reference's evaluation order, so results are identical.  Measured: in that
 // form the kernel is fp64-VALU-bound (two delta-Eddington solutions per layer and sweep: 70 000 instructions per wave),
-// not HBM-bound.  sw_kernel<true>, the fused form of the production pipeline, therefore trades bytes for flops: its first
+// not HBM-bound.  sw_kernel<true, false>, the fused form of the production pipeline, therefore trades bytes for flops: its first
 // sweep parks the five properties of every layer with the reflectances and its second sweep reads them back (the same
 // doubles: identical fluxes) -- 0.69 instead of 1.04 ms for 8 columns, at 4.2 TB/s.
 // The in-kernel range checks of the reference are no-ops on device builds
@@ -158,7 +158,11 @@ __device__ __forceinline__ LayerProps layer_props(double omega, double g, double
 // Rayleigh optical depth (clear_sky_combine: the expressions and order of clear_sky_kernel, identical values), the
 // first sweep's reflectances are parked in a scratch block instead of the output rows, nothing spectral is written and
 // the six integrated output rows leave as per-block trapezoid partial sums.
-template <bool FUSED>
+// PROFILE (fused form only): the reference's two sweeps always (shortwave.c:280-329) -- the first parks the downward-beam
+// reflectances of EVERY level in rows 0 .. 2 V - 1 of the park block, the second produces up and down at every level and
+// sums each across the wave at once (wave_row_sum, as lw_kernel<true, true>); the block's sums of the 2 V rows go to
+// partials[(c*2 V + r)*nblocks + block], r = level (up), V + level (down).
+template <bool FUSED, bool PROFILE>
 __global__ __launch_bounds__(kBlock) void sw_kernel(GrtSwArgs a)
 {
     uint64_t const i = (uint64_t)blockIdx.x*kBlock + threadIdx.x;
@@ -189,6 +193,8 @@ __global__ __launch_bounds__(kBlock) void sw_kernel(GrtSwArgs a)
     double *pp = FUSED ? a.park + ((uint64_t)col*park_rows + 2*(uint64_t)V)*nw + ii : nullptr;
     int const user = a.user_level;
     double out[6] = {0., 0., 0., 0., 0., 0.};     // up TOA, up surface, up user, down TOA, down surface, down user
+    extern __shared__ double level_sums[];        // PROFILE: [2 V][kBlock/64]
+    double const pwt = !PROFILE || !live ? 0. : ((i == 0 || i + 1 == nw) ? 0.5*a.dw : a.dw);
 
     // (the gas-optics launch left the spectral tables' part of tau to this kernel: a table entry read once per point)
     PointContinua pc;
@@ -229,7 +235,7 @@ __global__ __launch_bounds__(kBlock) void sw_kernel(GrtSwArgs a)
     // the bottom (R_dir_downward[0]) -- the same number to rounding (1e-15), not to the bit; the surface fluxes are the
     // reference's own operations.  Two delta-Eddington solutions per layer instead of two plus 80 bytes per layer and
     // wavenumber written and read back (16.8 GB per launch of 64 columns).
-    if (FUSED && (user < 0 || user == 0 || user == L) && a.one_sweep)
+    if (FUSED && !PROFILE && (user < 0 || user == 0 || user == L) && a.one_sweep)
     {
         double dir = 1., dif = 0., Ru = 0., Rd = 0., Tu = 1.;
         for (int j = 0; j < L; ++j)
@@ -274,7 +280,7 @@ __global__ __launch_bounds__(kBlock) void sw_kernel(GrtSwArgs a)
     // back per column; the same doubles reach the same expressions, so the fluxes are the same to the last bit).
     double const surf_rdir = Rdir_dn, surf_rdif = Rdif_dn;
     double user_rdir = Rdir_dn, user_rdif = Rdif_dn;        // (the user level is the surface, or set below)
-    if (!FUSED)
+    if (!FUSED || PROFILE)
     {
         fu[(uint64_t)L*nw] = Rdir_dn;
         fd[(uint64_t)L*nw] = Rdif_dn;
@@ -294,7 +300,7 @@ __global__ __launch_bounds__(kBlock) void sw_kernel(GrtSwArgs a)
         double const ndif = p.Rdif + p.Tdif*p.Tdif*Rdif_dn*B;
         Rdir_dn = ndir;
         Rdif_dn = ndif;
-        if (FUSED)
+        if (FUSED && !PROFILE)
         {
             user_rdir = j == user ? Rdir_dn : user_rdir;
             user_rdif = j == user ? Rdif_dn : user_rdif;
@@ -316,7 +322,12 @@ __global__ __launch_bounds__(kBlock) void sw_kernel(GrtSwArgs a)
         double dn = dir_beam;             // T[0]
         up *= scale;
         dn *= scale;
-        if (FUSED)
+        if (PROFILE)
+        {
+            wave_row_sum<kBlock>((tsi*up)*pwt, level_sums, 0);
+            wave_row_sum<kBlock>((tsi*dn)*pwt, level_sums, V);
+        }
+        else if (FUSED)
         {
             out[0] = tsi*up;
             out[3] = tsi*dn;
@@ -365,18 +376,23 @@ __global__ __launch_bounds__(kBlock) void sw_kernel(GrtSwArgs a)
         }
         dir_beam *= p.Tpure;
         uint64_t const ol = (uint64_t)lev*nw;
-        if (FUSED && lev != L && lev != user)
+        if (FUSED && !PROFILE && lev != L && lev != user)
         {
             continue;                     // (no flux of this level is asked for)
         }
-        double const rdir = FUSED ? (lev == L ? surf_rdir : user_rdir) : fu[ol];       // R_dir_downward[lev] of sweep 1
-        double const rdif = FUSED ? (lev == L ? surf_rdif : user_rdif) : fd[ol];       // R_dif_downward[lev]
+        double const rdir = FUSED && !PROFILE ? (lev == L ? surf_rdir : user_rdir) : fu[ol];   // R_dir_downward[lev] of sweep 1
+        double const rdif = FUSED && !PROFILE ? (lev == L ? surf_rdif : user_rdif) : fd[ol];   // R_dif_downward[lev]
         double const B = 1./(1. - rdif*Rup_prev);
         double up = (dir_beam*rdir + dif_beam*rdif)*B;
         double dn = dir_beam*(1. + rdir*Rup_prev*B) + dif_beam*B;
         up *= scale;
         dn *= scale;
-        if (FUSED)
+        if (PROFILE)
+        {
+            wave_row_sum<kBlock>((tsi*up)*pwt, level_sums, lev);
+            wave_row_sum<kBlock>((tsi*dn)*pwt, level_sums, V + lev);
+        }
+        else if (FUSED)
         {
             out[1] = lev == L ? tsi*up : out[1];
             out[4] = lev == L ? tsi*dn : out[4];
@@ -389,7 +405,11 @@ __global__ __launch_bounds__(kBlock) void sw_kernel(GrtSwArgs a)
             fd[ol] = tsi*dn;
         }
     }
-    if (FUSED)
+    if (PROFILE)
+    {
+        block_row_partials<kBlock>(level_sums, 2*V, a.partials, (uint64_t)col*2*V, gridDim.x, blockIdx.x);
+    }
+    else if (FUSED)
     {
         // driver.c:302-326: sum 0.5 (f_i + f_{i+1}) dw over the grid = sum weight_i f_i
         double const wt = !live ? 0. : ((i == 0 || i + 1 == nw) ? 0.5*a.dw : a.dw);
@@ -403,12 +423,12 @@ __global__ __launch_bounds__(kBlock) void sw_kernel(GrtSwArgs a)
 }
 
 // ---- spectral form of few columns: the layer properties first, by one thread per (layer, wavenumber) ----
-// One column of the 1 cm-1 shortwave band is 50 000 threads for sw_kernel<false>: not one wave per SIMD, each working
+// One column of the 1 cm-1 shortwave band is 50 000 threads for sw_kernel<false, false>: not one wave per SIMD, each working
 // through 120 layer steps of two delta-Eddington solutions (six exp and a dozen divisions) one after the other.  The
 // solutions of different layers do not depend on each other; only the adding sweeps do, and they are a few operations
 // per layer.  So: sw_props_kernel fills props[col][5 j + k][nw] (k: Rdir, Tdir, Tpure, Rdif, Tdif -- the park layout of
 // the fused form) with layer_props() of every (layer, wavenumber), and sw_sweeps_kernel runs the two sweeps of
-// sw_kernel<false> -- the same expressions in the same order on the same doubles, so the fluxes are the same to the last
+// sw_kernel<false, false> -- the same expressions in the same order on the same doubles, so the fluxes are the same to the last
 // bit -- reading six layers' properties at a time ahead of the dependent chain.
 constexpr int kPropsBlock = 256;
 constexpr int kSweepBlock = 64;
@@ -455,7 +475,7 @@ __global__ __launch_bounds__(kSweepBlock) void sw_sweeps_kernel(GrtSwArgs a)
         return p;
     };
 
-    // sweep 1: shortwave.c:280-294 (as in sw_kernel<false>: the downward-beam reflectances are parked in the output rows)
+    // sweep 1: shortwave.c:280-294 (as in sw_kernel<false, false>: the downward-beam reflectances are parked in the output rows)
     double Rdir_dn = a.alb_dir[(uint64_t)col*a.alb_stride + i];
     double Rdif_dn = a.alb_dif[(uint64_t)col*a.alb_stride + i];
     fu[(uint64_t)L*nw] = Rdir_dn;
@@ -612,11 +632,24 @@ extern "C" int grt_launch_sw(void *stream, GrtSwArgs const *a)
     dim3 const grid((unsigned)((a->nw + kBlock - 1)/kBlock), a->ncol, 1);   // == grt_solver_blocks(nw): same kBlock
     if (fused)
     {
-        hipLaunchKernelGGL(sw_kernel<true>, grid, dim3(kBlock), 0, (hipStream_t)stream, *a);
+        hipLaunchKernelGGL((sw_kernel<true, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, *a);
     }
     else
     {
-        hipLaunchKernelGGL(sw_kernel<false>, grid, dim3(kBlock), 0, (hipStream_t)stream, *a);
+        hipLaunchKernelGGL((sw_kernel<false, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, *a);
     }
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_sw_profile(void *stream, GrtSwArgs const *a)
+{
+    size_t const lds = sizeof(double)*2*(size_t)a->num_levels*(kBlock/64);
+    if (a->ncol < 1 || a->nw < 2 || a->num_levels < 2 || a->tau_gas == nullptr || a->n_layer == nullptr ||
+        a->partials == nullptr || a->park == nullptr || lds > 65536)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL((sw_kernel<true, true>), dim3((unsigned)((a->nw + kBlock - 1)/kBlock), a->ncol, 1), dim3(kBlock),
+                       lds, (hipStream_t)stream, *a);
     return (int)hipGetLastError();
 }

@@ -146,4 +146,39 @@ __device__ __forceinline__ void block_partials(double (&val)[NV], double *partia
     }
 }
 
+// Profile form of the fused solvers: every level's flux is a row of its own, 2 V rows per column -- more accumulators than
+// a thread has registers for, so each level's weighted value is summed across the wave as soon as it is produced, by
+// block_partials' shuffle tree, and lane 0 parks the wave's sum at lds[row*(BLOCK/64) + wave].  lds: dynamic LDS of
+// nrows*(BLOCK/64) doubles.
+template <int BLOCK>
+__device__ __forceinline__ void wave_row_sum(double s, double *lds, int row)
+{
+    for (int off = 32; off > 0; off >>= 1)
+    {
+        s += __shfl_down(s, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0)
+    {
+        lds[row*(BLOCK/64) + (threadIdx.x >> 6)] = s;
+    }
+}
+
+// ... and after the sweeps: the waves' sums of each row added in wave order (block_partials' association: a row that is
+// also one of the six-row form's gets the same bits), stored at partials[(row_base + row)*nblocks + block].
+template <int BLOCK>
+__device__ __forceinline__ void block_row_partials(double const *lds, int nrows, double *partials, uint64_t row_base,
+                                                   unsigned nblocks, unsigned block)
+{
+    __syncthreads();
+    for (int r = threadIdx.x; r < nrows; r += BLOCK)
+    {
+        double s = lds[r*(BLOCK/64)];
+        for (int k = 1; k < BLOCK/64; ++k)
+        {
+            s += lds[r*(BLOCK/64) + k];
+        }
+        partials[(row_base + r)*nblocks + block] = s;
+    }
+}
+
 #endif

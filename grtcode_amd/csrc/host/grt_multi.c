@@ -45,8 +45,8 @@ struct GrtMulti
     unsigned long seen_epoch;       /* file transport: the last grt_multi_max call whose marker file is still there */
     int have_seen;
     ncclComm_t comm;
-    fp_t *pad_d;                    /* RCCL: padded send block [per][12] on the device */
-    size_t pad_rows;
+    fp_t *pad_d;                    /* RCCL: padded send block [per][row] on the device */
+    size_t pad_doubles;
 };
 
 /* ---- librccl, opened on demand ----------------------------------------------------- */
@@ -379,17 +379,19 @@ EXTERN int grt_multi_destroy(GrtMulti_t **multi)
     return GRTCODE_SUCCESS;
 }
 
-/* Gather the ranks' [count][GRT_FLUXES_PER_COLUMN] blocks of a num_columns-column set sharded by
-   grt_multi_shard.  local: this rank's block; all (rank 0 only): room for world*ceil(num_columns/world)
-   rows, of which the first num_columns are the columns in order.  RCCL: both are DEVICE pointers and the
-   gather is enqueued on the library stream (asynchronous).  FILES: host or device pointers (`on_device`). */
-EXTERN int grt_multi_gather_fluxes(GrtMulti_t *m, fp_t const *local, int num_columns, fp_t *all, int on_device)
+/* Gather the ranks' [count][row_doubles] blocks of a num_columns-column set sharded by grt_multi_shard.
+   local: this rank's block; all (rank 0 only): room for world*ceil(num_columns/world) rows, of which the first
+   num_columns are the columns in order.  RCCL: both are DEVICE pointers and the gather is enqueued on the library
+   stream (asynchronous).  FILES: host or device pointers (`on_device`). */
+EXTERN int grt_multi_gather_rows(GrtMulti_t *m, fp_t const *local, int num_columns, int row_doubles, fp_t *all,
+                                 int on_device)
 {
     GRT_REQUIRE_PTR(m);
     GRT_REQUIRE_RANGE(num_columns, 1, 1 << 30);
+    GRT_REQUIRE_RANGE(row_doubles, 1, 1 << 24);
     int first = 0, count = 0;
     GRT_TRY(grt_multi_shard(num_columns, m->rank, m->world, &first, &count));
-    size_t const per = (size_t)((num_columns + m->world - 1)/m->world), row = GRT_FLUXES_PER_COLUMN;
+    size_t const per = (size_t)((num_columns + m->world - 1)/m->world), row = (size_t)row_doubles;
     if (count > 0)
     {
         GRT_REQUIRE_PTR(local);
@@ -401,13 +403,14 @@ EXTERN int grt_multi_gather_fluxes(GrtMulti_t *m, fp_t const *local, int num_col
     if (m->transport == GRT_MULTI_RCCL)
     {
         void *s = grt_dev_stream(m->device);
-        if (m->pad_rows < per)
+        if (m->pad_doubles < per*row)
         {
             GRT_TRY(grt_dev_sync(m->device, s));
             GRT_TRY(grt_dev_free(m->device, m->pad_d));
             m->pad_d = NULL;
+            m->pad_doubles = 0;
             GRT_TRY(grt_dev_alloc(m->device, (void **)&m->pad_d, sizeof(fp_t)*per*row));
-            m->pad_rows = per;
+            m->pad_doubles = per*row;
         }
         fp_t const *send = local;
         if ((size_t)count < per)
@@ -486,6 +489,12 @@ EXTERN int grt_multi_gather_fluxes(GrtMulti_t *m, fp_t const *local, int num_col
     }
     free(host);
     GRT_TRY(rc);
+    return GRTCODE_SUCCESS;
+}
+
+EXTERN int grt_multi_gather_fluxes(GrtMulti_t *m, fp_t const *local, int num_columns, fp_t *all, int on_device)
+{
+    GRT_TRY(grt_multi_gather_rows(m, local, num_columns, GRT_FLUXES_PER_COLUMN, all, on_device));
     return GRTCODE_SUCCESS;
 }
 

@@ -14,6 +14,9 @@
  *   - or, for callers that want spectra (grt_pipeline_create_ex(..., keep_spectra = 1): parity tests, a
  *     driver without -integrated), the materialised form: one streaming Rayleigh + combine pass,
  *     solvers writing [level][wavenumber] fluxes, a row-wise trapezoid launch.
+ * grt_pipeline_run_profiles runs the same prologue and gas optics, then the profile form of the solvers (every level's
+ * flux summed per block in-kernel, or -- materialised form -- integrated row by row from the spectra) and one small
+ * kernel that forms the level fluxes, the heating rates and the six-row output from them.
  * All work is enqueued on the device's library stream; nothing synchronises.
  */
 #include <stdlib.h>
@@ -35,6 +38,9 @@ typedef struct GrtBand
     double *park;          /* shortwave: [cols][2 V + 5 L][n] first-sweep reflectances and layer properties */
     double *partials;      /* [cols][6][nblocks] trapezoid partial sums */
     unsigned nblocks;
+    /* grt_pipeline_run_profiles, allocated at its first call: */
+    double *level_partials;        /* fused form: [cols][2 V][nblocks] */
+    double **level_rows_d;         /* materialised form: [cols][2 V] device row pointers (up levels, then down levels) */
 } GrtBand;
 
 struct GrtPipeline
@@ -47,7 +53,7 @@ struct GrtPipeline
     /* per-batch small inputs: pinned host staging + device copies */
     double *small_h, *small_d;
     void *small_uploaded;  /* event: small_h has been copied out and may be refilled */
-    size_t off_n, off_tl, off_tv, off_ts, off_mu, off_tsi, small_doubles;
+    size_t off_n, off_tl, off_tv, off_ts, off_mu, off_tsi, off_p, small_doubles;
     double *emis_d, *albedo_d, *solar_d;
 };
 
@@ -125,7 +131,8 @@ static int pipeline_build(GrtPipeline_t *p, GasOptics_t *lw_gas, GasOptics_t *sw
     p->off_ts = p->off_tv + C*V;
     p->off_mu = p->off_ts + C;
     p->off_tsi = p->off_mu + C;
-    p->small_doubles = p->off_tsi + C;
+    p->off_p = p->off_tsi + C;         /* level pressures [C][V] mb: the heating rates of grt_pipeline_run_profiles */
+    p->small_doubles = p->off_p + C*V;
     GRT_TRY(grt_host_alloc_pinned((void **)&p->small_h, sizeof(double)*p->small_doubles));
     GRT_TRY(grt_dev_alloc(p->device, (void **)&p->small_d, sizeof(double)*p->small_doubles));
     void *s = grt_dev_stream(p->device);
@@ -211,6 +218,8 @@ static void grt_pipeline_release(GrtPipeline_t **pipeline)
         grt_dev_free(p->device, p->band[b].tau_gas);
         grt_dev_free(p->device, p->band[b].park);
         grt_dev_free(p->device, p->band[b].rows_d);
+        grt_dev_free(p->device, p->band[b].level_partials);
+        grt_dev_free(p->device, p->band[b].level_rows_d);
     }
     grt_dev_free(p->device, p->small_d);
     grt_host_free_pinned(p->small_h);
@@ -275,11 +284,10 @@ EXTERN int grt_pipeline_views(GrtPipeline_t *pipeline, int band, fp_t **tau_gas,
     return GRTCODE_SUCCESS;
 }
 
-EXTERN int grt_pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, fp_t *fluxes_dev)
+/* What grt_pipeline_run and grt_pipeline_run_profiles check and stage alike: the arguments, the lane, and the small
+   per-column inputs, uploaded to small_d on the library stream. */
+static int stage_columns(GrtPipeline_t *p, GrtColumns_t const *cols)
 {
-    GRT_REQUIRE_PTR(p);
-    GRT_REQUIRE_PTR(cols);
-    GRT_REQUIRE_PTR(fluxes_dev);
     GRT_REQUIRE_RANGE(cols->ncol, 1, p->max_cols);
     GRT_REQUIRE_EQ(cols->num_levels, p->num_levels);
     GRT_REQUIRE_PTR(cols->pressure);
@@ -312,6 +320,7 @@ EXTERN int grt_pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, fp_t *fl
             p->small_h[p->off_n + (size_t)c*L + i] = c_air*dp;
         }
     }
+    memcpy(p->small_h + p->off_p, cols->pressure, sizeof(double)*(size_t)C*V);
     if (p->band[0].gas != NULL)
     {
         GRT_REQUIRE_PTR(cols->layer_temperature);
@@ -345,7 +354,135 @@ EXTERN int grt_pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, fp_t *fl
     }
     GRT_TRY(grt_dev_upload(p->device, p->small_d, p->small_h, sizeof(double)*p->small_doubles, s));
     GRT_TRY(grt_dev_event_record(p->device, &p->small_uploaded, s));
+    return GRTCODE_SUCCESS;
+}
 
+/* gas optics of one band for the batch (launch.c:40-226).  Fused form: the spectral tables' part of tau (continua, CFC,
+   CIA) is left to the solver kernel, which reads a table entry once per grid point and column instead of once per layer
+   as well (the same expressions in the same order: the same doubles; GRT_DEFER_CONTINUA=0 in the environment: comparison
+   runs).  *defer: the solver adds that part, from *continua. */
+static int band_gas_optics(GrtPipeline_t *p, GrtBand *b, int bi, GrtColumns_t const *cols, GrtContinua *continua,
+                           int *defer)
+{
+    *defer = 0;
+    if (!p->keep_spectra && bi == 1)
+    {
+        /* (shortwave band only.  Measured per 64 columns of the 1 cm-1 grids: the shortwave gather 3.93 -> 3.01 ms, its
+           solver 3.09 -> 3.60; the longwave band, whose solver is the lighter kernel, 0.26 + 0.36 -> 0.21 + 0.48) */
+        char const *env = getenv("GRT_DEFER_CONTINUA");
+        *defer = grt_gas_optics_defer_tables(b->gas, !(env != NULL && env[0] == '0'));
+    }
+    int const rc_gas = grt_optical_depth_batch(b->gas, cols, b->tau_gas);
+    grt_gas_optics_defer_tables(b->gas, 0);                  /* (the object's own entry points deliver the whole tau) */
+    GRT_TRY(rc_gas);
+    grt_gas_optics_continua(b->gas, continua);               /* (the column state's place is known after the batch call) */
+    b->tau_gas_lacks_tables = *defer;
+    b->last_cols = cols->ncol;
+    return GRTCODE_SUCCESS;
+}
+
+/* The fused solvers' arguments: Rayleigh, add_optics({gas, rayleigh}) and the solver in one launch (driver.c:268,
+   382-424); the caller sets the partial sums and, shortwave, the sweep form and the park block. */
+static void fused_lw_args(GrtPipeline_t *p, GrtBand const *b, int C, int defer, GrtContinua const *continua, GrtLwArgs *a)
+{
+    SpectralGrid_t const *grid = &b->gas->grid;
+    int const V = p->num_levels, L = V - 1;
+    memset(a, 0, sizeof(*a));
+    a->num_levels = V; a->ncol = C; a->w0 = grid->w0; a->dw = grid->dw; a->nw = b->n;
+    a->tau_gas = b->tau_gas; a->n_layer = p->small_d + p->off_n; a->optics_stride = (uint64_t)L*b->n;
+    a->t_layers = p->small_d + p->off_tl; a->t_levels = p->small_d + p->off_tv;
+    a->t_surf = p->small_d + p->off_ts;
+    a->emis = p->emis_d; a->emis_stride = 0;
+    a->user_level = p->user_level;
+    a->add_continua = defer;
+    if (defer) a->continua = *continua;
+}
+
+static void fused_sw_args(GrtPipeline_t *p, GrtBand const *b, int C, int defer, GrtContinua const *continua, GrtSwArgs *a)
+{
+    SpectralGrid_t const *grid = &b->gas->grid;
+    int const V = p->num_levels, L = V - 1;
+    memset(a, 0, sizeof(*a));
+    a->num_levels = V; a->ncol = C; a->nw = b->n; a->dw = grid->dw; a->w0 = grid->w0;
+    a->tau_gas = b->tau_gas; a->n_layer = p->small_d + p->off_n; a->optics_stride = (uint64_t)L*b->n;
+    a->mu_dir = p->small_d + p->off_mu; a->mu_dif = 0.5;        /* driver.c:110 */
+    a->alb_dir = p->albedo_d; a->alb_dif = p->albedo_d; a->alb_stride = 0;   /* driver.c:118-119 */
+    a->tsi = p->small_d + p->off_tsi; a->solar = p->solar_d;
+    a->user_level = p->user_level;
+    a->add_continua = defer;
+    if (defer) a->continua = *continua;
+}
+
+/* the shortwave solver's two-sweep form: reflectances of 2 V levels and five properties of L layers per column and
+   wavenumber, allocated at the first launch that needs them */
+static int park_block(GrtPipeline_t *p, GrtBand *b)
+{
+    if (b->park == NULL)
+    {
+        size_t const V = (size_t)p->num_levels;
+        void *pk = NULL;
+        GRT_TRY(grt_dev_alloc(p->device, &pk, sizeof(double)*(size_t)p->max_cols*(2*V + 5*(V - 1))*b->n));
+        b->park = pk;
+    }
+    return GRTCODE_SUCCESS;
+}
+
+/* Materialised form: Rayleigh + add_optics({gas, rayleigh}) (driver.c:268, 382-383), then the solver writing
+   [level][wavenumber] fluxes. */
+static int band_spectral_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C)
+{
+    SpectralGrid_t const *grid = &b->gas->grid;
+    int const V = p->num_levels, L = V - 1;
+    uint64_t const per_opt = (uint64_t)L*b->n, per_flux = (uint64_t)V*b->n;
+    void *s = grt_dev_stream(p->device);
+    int slot = grt_profile_begin(s, 5);
+    int krc = grt_launch_clear_sky_optics(s, L, C, grid->w0, grid->dw, b->n, p->small_d + p->off_n,
+                                          b->tau_gas, b->tau, b->omega, b->g);
+    grt_profile_end(s, slot);
+    GRT_TRY(grt_dev_check(krc, "clear-sky optics kernel"));
+    if (bi == 0)
+    {
+        GrtLwArgs a;
+        memset(&a, 0, sizeof(a));
+        a.num_levels = V; a.ncol = C; a.w0 = grid->w0; a.dw = grid->dw; a.nw = b->n;
+        a.tau = b->tau; a.omega = b->omega; a.optics_stride = per_opt;
+        a.t_layers = p->small_d + p->off_tl; a.t_levels = p->small_d + p->off_tv;
+        a.t_surf = p->small_d + p->off_ts;
+        a.emis = p->emis_d; a.emis_stride = 0;
+        a.flux_up = b->flux_up; a.flux_down = b->flux_down; a.flux_stride = per_flux;
+        a.user_level = p->user_level;
+        slot = grt_profile_begin(s, 3);
+        krc = grt_launch_lw(s, &a);
+        grt_profile_end(s, slot);
+        GRT_TRY(grt_dev_check(krc, "longwave kernel"));
+    }
+    else
+    {
+        GrtSwArgs a;
+        memset(&a, 0, sizeof(a));
+        a.num_levels = V; a.ncol = C; a.nw = b->n; a.dw = grid->dw;
+        a.tau = b->tau; a.omega = b->omega; a.g = b->g; a.optics_stride = per_opt;
+        a.mu_dir = p->small_d + p->off_mu; a.mu_dif = 0.5;        /* driver.c:110 */
+        a.alb_dir = p->albedo_d; a.alb_dif = p->albedo_d; a.alb_stride = 0;   /* driver.c:118-119 */
+        a.tsi = p->small_d + p->off_tsi; a.solar = p->solar_d;
+        a.flux_up = b->flux_up; a.flux_down = b->flux_down; a.flux_stride = per_flux;
+        a.user_level = p->user_level;
+        slot = grt_profile_begin(s, 4);
+        krc = grt_launch_sw(s, &a);
+        grt_profile_end(s, slot);
+        GRT_TRY(grt_dev_check(krc, "shortwave kernel"));
+    }
+    return GRTCODE_SUCCESS;
+}
+
+EXTERN int grt_pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    GRT_REQUIRE_PTR(fluxes_dev);
+    GRT_TRY(stage_columns(p, cols));
+    int const V = p->num_levels, C = cols->ncol;
+    void *s = grt_dev_stream(p->device);
     for (int bi = 0; bi < 2; ++bi)
     {
         GrtBand *b = &p->band[bi];
@@ -354,25 +491,9 @@ EXTERN int grt_pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, fp_t *fl
             continue;
         }
         SpectralGrid_t const *grid = &b->gas->grid;
-        uint64_t const per_opt = (uint64_t)L*b->n, per_flux = (uint64_t)V*b->n;
-        /* gas optics (launch.c:40-226).  Fused form: the spectral tables' part of tau (continua, CFC, CIA) is left to the
-           solver kernel, which reads a table entry once per grid point and column instead of once per layer as well
-           (the same expressions in the same order: the same doubles; GRT_DEFER_CONTINUA=0 in the environment: comparison runs) */
         GrtContinua continua;
-        int defer = 0;
-        if (!p->keep_spectra && bi == 1)
-        {
-            /* (shortwave band only.  Measured per 64 columns of the 1 cm-1 grids: the shortwave gather 3.93 -> 3.01 ms, its
-               solver 3.09 -> 3.60; the longwave band, whose solver is the lighter kernel, 0.26 + 0.36 -> 0.21 + 0.48) */
-            char const *env = getenv("GRT_DEFER_CONTINUA");
-            defer = grt_gas_optics_defer_tables(b->gas, !(env != NULL && env[0] == '0'));
-        }
-        int const rc_gas = grt_optical_depth_batch(b->gas, cols, b->tau_gas);
-        grt_gas_optics_defer_tables(b->gas, 0);                  /* (the object's own entry points deliver the whole tau) */
-        GRT_TRY(rc_gas);
-        grt_gas_optics_continua(b->gas, &continua);              /* (the column state's place is known after the batch call) */
-        b->tau_gas_lacks_tables = defer;
-        b->last_cols = C;
+        int defer;
+        GRT_TRY(band_gas_optics(p, b, bi, cols, &continua, &defer));
         if (!p->keep_spectra)
         {
             /* Rayleigh, add_optics({gas, rayleigh}), solver and -integrated output (driver.c:268, 382-424, 302-326)
@@ -381,16 +502,8 @@ EXTERN int grt_pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, fp_t *fl
             if (bi == 0)
             {
                 GrtLwArgs a;
-                memset(&a, 0, sizeof(a));
-                a.num_levels = V; a.ncol = C; a.w0 = grid->w0; a.dw = grid->dw; a.nw = b->n;
-                a.tau_gas = b->tau_gas; a.n_layer = p->small_d + p->off_n; a.optics_stride = per_opt;
-                a.t_layers = p->small_d + p->off_tl; a.t_levels = p->small_d + p->off_tv;
-                a.t_surf = p->small_d + p->off_ts;
-                a.emis = p->emis_d; a.emis_stride = 0;
-                a.user_level = p->user_level;
+                fused_lw_args(p, b, C, defer, &continua, &a);
                 a.partials = b->partials;
-                a.add_continua = defer;
-                if (defer) a.continua = continua;
                 slot = grt_profile_begin(s, 3);
                 krc = grt_launch_lw(s, &a);
                 grt_profile_end(s, slot);
@@ -399,29 +512,18 @@ EXTERN int grt_pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, fp_t *fl
             else
             {
                 GrtSwArgs a;
-                memset(&a, 0, sizeof(a));
-                a.num_levels = V; a.ncol = C; a.nw = b->n; a.dw = grid->dw; a.w0 = grid->w0;
-                a.tau_gas = b->tau_gas; a.n_layer = p->small_d + p->off_n; a.optics_stride = per_opt;
-                a.mu_dir = p->small_d + p->off_mu; a.mu_dif = 0.5;        /* driver.c:110 */
-                a.alb_dir = p->albedo_d; a.alb_dif = p->albedo_d; a.alb_stride = 0;   /* driver.c:118-119 */
-                a.tsi = p->small_d + p->off_tsi; a.solar = p->solar_d;
-                a.user_level = p->user_level;
+                fused_sw_args(p, b, C, defer, &continua, &a);
                 a.partials = b->partials;
                 {
                     /* (read at every step, so that a test can compare the two forms in one process) */
                     char const *env = getenv("GRT_SW_TWO_SWEEPS");
                     a.one_sweep = !(env != NULL && env[0] == '1');
                 }
-                if (!(a.one_sweep && (p->user_level < 0 || p->user_level == 0 || p->user_level == V - 1)) && b->park == NULL)
+                if (!(a.one_sweep && (p->user_level < 0 || p->user_level == 0 || p->user_level == V - 1)))
                 {
-                    /* the two-sweep form: reflectances of 2 V levels and five properties of L layers per column and wavenumber */
-                    void *pk = NULL;
-                    GRT_TRY(grt_dev_alloc(p->device, &pk, sizeof(double)*(size_t)p->max_cols*(2*(size_t)V + 5*((size_t)V - 1))*b->n));
-                    b->park = pk;
+                    GRT_TRY(park_block(p, b));
                 }
                 a.park = b->park;
-                a.add_continua = defer;
-                if (defer) a.continua = continua;
                 slot = grt_profile_begin(s, 4);
                 krc = grt_launch_sw(s, &a);
                 grt_profile_end(s, slot);
@@ -432,49 +534,131 @@ EXTERN int grt_pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, fp_t *fl
                                                              bi*GRT_FLUXES_PER_BAND), "flux reduction kernel"));
             continue;
         }
-        /* Rayleigh + add_optics({gas, rayleigh}) (driver.c:268, 382-383) */
-        int slot = grt_profile_begin(s, 5);
-        int krc = grt_launch_clear_sky_optics(s, L, C, grid->w0, grid->dw, b->n, p->small_d + p->off_n,
-                                              b->tau_gas, b->tau, b->omega, b->g);
-        grt_profile_end(s, slot);
-        GRT_TRY(grt_dev_check(krc, "clear-sky optics kernel"));
-        if (bi == 0)
-        {
-            GrtLwArgs a;
-            memset(&a, 0, sizeof(a));
-            a.num_levels = V; a.ncol = C; a.w0 = grid->w0; a.dw = grid->dw; a.nw = b->n;
-            a.tau = b->tau; a.omega = b->omega; a.optics_stride = per_opt;
-            a.t_layers = p->small_d + p->off_tl; a.t_levels = p->small_d + p->off_tv;
-            a.t_surf = p->small_d + p->off_ts;
-            a.emis = p->emis_d; a.emis_stride = 0;
-            a.flux_up = b->flux_up; a.flux_down = b->flux_down; a.flux_stride = per_flux;
-            a.user_level = p->user_level;
-            slot = grt_profile_begin(s, 3);
-            krc = grt_launch_lw(s, &a);
-            grt_profile_end(s, slot);
-            GRT_TRY(grt_dev_check(krc, "longwave kernel"));
-        }
-        else
-        {
-            GrtSwArgs a;
-            memset(&a, 0, sizeof(a));
-            a.num_levels = V; a.ncol = C; a.nw = b->n; a.dw = grid->dw;
-            a.tau = b->tau; a.omega = b->omega; a.g = b->g; a.optics_stride = per_opt;
-            a.mu_dir = p->small_d + p->off_mu; a.mu_dif = 0.5;        /* driver.c:110 */
-            a.alb_dir = p->albedo_d; a.alb_dif = p->albedo_d; a.alb_stride = 0;   /* driver.c:118-119 */
-            a.tsi = p->small_d + p->off_tsi; a.solar = p->solar_d;
-            a.flux_up = b->flux_up; a.flux_down = b->flux_down; a.flux_stride = per_flux;
-            a.user_level = p->user_level;
-            slot = grt_profile_begin(s, 4);
-            krc = grt_launch_sw(s, &a);
-            grt_profile_end(s, slot);
-            GRT_TRY(grt_dev_check(krc, "shortwave kernel"));
-        }
+        GRT_TRY(band_spectral_solver(p, b, bi, C));
         /* -integrated output (driver.c:302-326) */
         GRT_TRY(grt_dev_check(grt_launch_integrate_rows(s, (double const *const *)b->rows_d, C*6, b->n,
                                                         grid->dw, fluxes_dev, GRT_FLUXES_PER_BAND,
                                                         GRT_FLUXES_PER_COLUMN, bi*GRT_FLUXES_PER_BAND),
                               "spectral integration kernel"));
     }
+    return GRTCODE_SUCCESS;
+}
+
+/* materialised form: the row table of every level's up and down flux, [max_cols][2 V] */
+static int level_rows(GrtPipeline_t *p, GrtBand *b)
+{
+    if (b->level_rows_d != NULL)
+    {
+        return GRTCODE_SUCCESS;
+    }
+    size_t const V = (size_t)p->num_levels, C = (size_t)p->max_cols;
+    double **rows_h = malloc(sizeof(double *)*C*2*V);
+    if (rows_h == NULL)
+    {
+        GRT_FAIL(GRTCODE_NULL_ERR, "out of host memory for the level row table of %zu columns.", C);
+    }
+    for (size_t c = 0; c < C; ++c)
+    {
+        for (size_t k = 0; k < V; ++k)
+        {
+            rows_h[(c*2 + 0)*V + k] = b->flux_up + (c*V + k)*b->n;
+            rows_h[(c*2 + 1)*V + k] = b->flux_down + (c*V + k)*b->n;
+        }
+    }
+    void *s = grt_dev_stream(p->device);
+    double **rows_d = NULL;
+    int rc = grt_dev_alloc(p->device, (void **)&rows_d, sizeof(double *)*C*2*V);
+    if (rc == GRTCODE_SUCCESS) rc = grt_dev_upload(p->device, rows_d, rows_h, sizeof(double *)*C*2*V, s);
+    if (rc == GRTCODE_SUCCESS) rc = grt_dev_sync(p->device, s);      /* (rows_h is freed next) */
+    free(rows_h);
+    if (rc != GRTCODE_SUCCESS)
+    {
+        grt_dev_free(p->device, rows_d);
+        GRT_TRY(rc);
+    }
+    b->level_rows_d = rows_d;
+    return GRTCODE_SUCCESS;
+}
+
+EXTERN int grt_pipeline_run_profiles(GrtPipeline_t *p, GrtColumns_t const *cols, fp_t *level_fluxes_dev,
+                                     fp_t *heating_dev, fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    if (level_fluxes_dev == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "level_fluxes_dev is NULL: the level fluxes [ncol][%d][%d] are the output.",
+                 GRT_PROFILE_ROWS_PER_COLUMN, p->num_levels);
+    }
+    if (cols->ncol < 1 || cols->ncol > p->max_cols)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d columns asked for, this pipeline was created for 1 to %d.", cols->ncol, p->max_cols);
+    }
+    if (p->num_levels < 2)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "heating rates need at least 2 levels (%d).", p->num_levels);
+    }
+    GRT_TRY(stage_columns(p, cols));
+    int const V = p->num_levels, C = cols->ncol;
+    void *s = grt_dev_stream(p->device);
+    int bands = 0;
+    for (int bi = 0; bi < 2; ++bi)
+    {
+        GrtBand *b = &p->band[bi];
+        if (b->gas == NULL)
+        {
+            continue;
+        }
+        bands |= 1 << bi;
+        SpectralGrid_t const *grid = &b->gas->grid;
+        GrtContinua continua;
+        int defer;
+        GRT_TRY(band_gas_optics(p, b, bi, cols, &continua, &defer));
+        if (!p->keep_spectra)
+        {
+            if (b->level_partials == NULL)
+            {
+                void *lp = NULL;
+                GRT_TRY(grt_dev_alloc(p->device, &lp, sizeof(double)*(size_t)p->max_cols*2*(size_t)V*b->nblocks));
+                b->level_partials = lp;
+            }
+            int slot, krc;
+            if (bi == 0)
+            {
+                GrtLwArgs a;
+                fused_lw_args(p, b, C, defer, &continua, &a);
+                a.partials = b->level_partials;
+                slot = grt_profile_begin(s, 3);
+                krc = grt_launch_lw_profile(s, &a);
+                grt_profile_end(s, slot);
+                GRT_TRY(grt_dev_check(krc, "longwave kernel (profile form)"));
+            }
+            else
+            {
+                GrtSwArgs a;
+                fused_sw_args(p, b, C, defer, &continua, &a);
+                a.partials = b->level_partials;
+                GRT_TRY(park_block(p, b));
+                a.park = b->park;
+                slot = grt_profile_begin(s, 4);
+                krc = grt_launch_sw_profile(s, &a);
+                grt_profile_end(s, slot);
+                GRT_TRY(grt_dev_check(krc, "shortwave kernel (profile form)"));
+            }
+            /* [c][2 V] rows -> level_fluxes_dev[c][2 bi + {0, 1}][V] */
+            GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, b->level_partials, C*2*V, b->nblocks, level_fluxes_dev,
+                                                             2*V, GRT_PROFILE_ROWS_PER_COLUMN*V, bi*2*V),
+                                  "level flux reduction kernel"));
+            continue;
+        }
+        GRT_TRY(band_spectral_solver(p, b, bi, C));
+        GRT_TRY(level_rows(p, b));
+        GRT_TRY(grt_dev_check(grt_launch_integrate_rows(s, (double const *const *)b->level_rows_d, C*2*V, b->n,
+                                                        grid->dw, level_fluxes_dev, 2*V, GRT_PROFILE_ROWS_PER_COLUMN*V,
+                                                        bi*2*V), "spectral integration kernel (levels)"));
+    }
+    GRT_TRY(grt_dev_check(grt_launch_profile_finish(s, C, V, bands, p->user_level, GRT_GRAVITY, GRT_SPECIFIC_HEAT_AIR,
+                                                    p->small_d + p->off_p, level_fluxes_dev, heating_dev, fluxes_dev),
+                          "heating rate kernel"));
     return GRTCODE_SUCCESS;
 }

@@ -76,6 +76,12 @@ class Multi:
         self.api.check(self.lib.grt_multi_gather_fluxes(self.m, C.c_void_p(local_ptr), num_columns, C.c_void_p(all_ptr),
                                                         int(on_device)))
 
+    def gather_rows(self, local_ptr, num_columns, row_doubles, all_ptr, on_device):
+        """grt_multi_gather_rows: as gather_fluxes with rows of `row_doubles` doubles (e.g. the level fluxes and heating
+        rates of Pipeline.run_profiles: 4 V + 2 (V - 1))."""
+        self.api.check(self.lib.grt_multi_gather_rows(self.m, C.c_void_p(local_ptr), num_columns, row_doubles,
+                                                      C.c_void_p(all_ptr), int(on_device)))
+
     def max(self, value):
         v = C.c_double(value)
         self.api.check(self.lib.grt_multi_max(self.m, C.byref(v)))

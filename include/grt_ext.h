@@ -149,6 +149,33 @@ EXTERN void *grt_pipeline_stream(GrtPipeline_t *pipeline);
 EXTERN int grt_pipeline_views(GrtPipeline_t *pipeline, int band, fp_t **tau_gas, fp_t **tau,
                               fp_t **omega, fp_t **g, fp_t **flux_up, fp_t **flux_down);
 
+/* ---- broadband flux profiles and heating rates ------------------------------------------
+ * The same batch as grt_pipeline_run, with the broadband flux at EVERY level and the heating rate of every layer:
+ *   level_fluxes_dev [ncol][GRT_PROFILE_ROWS_PER_COLUMN][V]: longwave up, longwave down, shortwave up, shortwave down,
+ *                    each over the levels top first, W m-2 (required);
+ *   heating_dev      [ncol][GRT_HEATING_ROWS_PER_COLUMN][V-1]: longwave, shortwave, K day-1, positive for warming (may be
+ *                    NULL): layer j, between levels j and j + 1,
+ *                    H_j = (GRT_GRAVITY/GRT_SPECIFIC_HEAT_AIR) ((dn_j - up_j) - (dn_{j+1} - up_{j+1}))/(100 (p_{j+1} - p_j))
+ *                          x 86 400 s day-1,  p the level pressures in mb (x 100: Pa);
+ *   fluxes_dev       [ncol][GRT_FLUXES_PER_COLUMN], as grt_pipeline_run writes it, from rows 0, L and the user level (may
+ *                    be NULL).
+ * All DEVICE memory; asynchronous on the pipeline's lane like grt_pipeline_run.  A band whose gas-optics object is NULL
+ * gives zero rows.  The production form (keep_spectra = 0) writes no spectra: each level is summed across the spectrum
+ * inside the solvers, and per band [max_columns][2 V][nblocks] partial sums (24 MB for 64 columns of a 50 000-point
+ * band at 61 levels) are allocated at the first call.  Its shortwave solver always takes the two sweeps of the
+ * reference and so needs the park block of the two-sweep form ([2 V + 5 L][n] per column: allocated at the first call
+ * too, 10.8 GB for 64 columns of the 1 cm-1 band): the upward flux at the top is then the two-sweep form's, within
+ * 1e-13 relative of the one-sweep form grt_pipeline_run takes by default.  Rows 0, L and the user level are, bit for
+ * bit, those of grt_pipeline_run (shortwave: with GRT_SW_TWO_SWEEPS=1) in the deterministic mode.  keep_spectra = 1:
+ * the same outputs from the materialised spectra, integrated row by row.  GRTCODE_VALUE_ERR for ncol outside
+ * 1 .. max_columns, a NULL level_fluxes_dev, fewer than 2 levels. */
+#define GRT_PROFILE_ROWS_PER_COLUMN 4    /* LW up, LW down, SW up, SW down; each [V], levels TOA first, W m-2 */
+#define GRT_HEATING_ROWS_PER_COLUMN 2    /* LW, SW; each [V-1], K day-1 */
+#define GRT_GRAVITY 9.80665              /* m s-2 */
+#define GRT_SPECIFIC_HEAT_AIR 1004.64    /* J kg-1 K-1, dry air at constant pressure */
+EXTERN int grt_pipeline_run_profiles(GrtPipeline_t *pipeline, GrtColumns_t const *columns,
+                                     fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev);
+
 /* ---- columns across the GPUs of one node ------------------------------------
  * One process per GPU; contiguous ceil-sized column blocks; one gather of the [columns][GRT_FLUXES_PER_COLUMN]
  * flux blocks to rank 0.  The reference fans out processes with -x/-X column ranges and merges per-shard files
@@ -170,8 +197,12 @@ EXTERN int grt_multi_shard(int num_columns, int rank, int world, int *first, int
 EXTERN int grt_multi_create(GrtMulti_t **multi, int transport, Device_t device, int rank, int world,
                             char const *rendezvous_dir);
 EXTERN int grt_multi_destroy(GrtMulti_t **multi);
-/* local: this rank's [count][12] block; all (rank 0 only): room for world*ceil(num_columns/world) rows, the first
-   num_columns of which are the columns in order (short blocks are padded, so no sizes are exchanged). */
+/* local: this rank's [count][row_doubles] block; all (rank 0 only): room for world*ceil(num_columns/world) rows, the first
+   num_columns of which are the columns in order (short blocks are padded, so no sizes are exchanged).  Any row width:
+   e.g. 4 V + 2 (V - 1) for the level fluxes and heating rates of grt_pipeline_run_profiles. */
+EXTERN int grt_multi_gather_rows(GrtMulti_t *multi, fp_t const *local, int num_columns, int row_doubles, fp_t *all,
+                                 int on_device);
+/* grt_multi_gather_rows with rows of GRT_FLUXES_PER_COLUMN: the [count][12] blocks of grt_pipeline_run. */
 EXTERN int grt_multi_gather_fluxes(GrtMulti_t *multi, fp_t const *local, int num_columns, fp_t *all, int on_device);
 EXTERN int grt_multi_broadcast(GrtMulti_t *multi, void *buffer_dev, size_t bytes);   /* RCCL only: replicate from rank 0 */
 EXTERN int grt_multi_max(GrtMulti_t *multi, double *value);    /* barrier + maximum over the ranks (timing brackets) */

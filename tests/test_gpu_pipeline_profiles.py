@@ -1,0 +1,221 @@
+"""grt_pipeline_run_profiles: broadband flux at every level and the heating rate of every layer from the batched pipeline,
+against the oracle's column-by-column restatement of the reference, against the pipeline's own six-row form, and at the
+bench's shortwave width."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from grtcode_amd import api, synthetic as syn
+from scenario import Band, MOL_ORDER
+from test_gpu_pipeline import oracle_column
+
+pytestmark = pytest.mark.gpu
+
+GRAVITY, CP = 9.80665, 1004.64       # grt_ext.h: GRT_GRAVITY, GRT_SPECIFIC_HEAT_AIR
+
+
+def heating(up, dn, p):
+    """K day-1 of every layer from level fluxes [.., V] and level pressures [V] in mb, levels top first."""
+    net = dn - up
+    return (GRAVITY / CP) * ((net[..., :-1] - net[..., 1:]) / (100.0 * (p[1:] - p[:-1]))) * 86400.0
+
+
+@pytest.fixture(scope="module")
+def bands(tmp_path_factory):
+    root = tmp_path_factory.mktemp("pipe_profiles")
+    lw = Band(str(root / "lw"), 1.0, 400.0, 1.0, 3000)
+    sw = Band(str(root / "sw"), 1.0, 5000.0, 10.0, 3000, sw=True)
+    return lw, sw
+
+
+def _setup(bands, device, V):
+    lwb, swb = bands
+    go_lw, _ = lwb.gas_optics(device, V)
+    go_sw, grid_sw = swb.gas_optics(device, V)
+    emis, alb = np.full(lwb.nw, 0.98), np.full(swb.nw, 0.2)
+    solar = api.create_solar_flux(grid_sw, swb.files["solar"])
+    return go_lw, go_sw, emis, alb, solar
+
+
+@pytest.mark.parametrize("spectral", [False, True])
+def test_level_fluxes_and_heating_rates_match_the_oracle(bands, oracle, lib, device, spectral):
+    lwb, swb = bands
+    V, ncol, user_level = 16, 3, 5
+    cols = [syn.profile(80 + c, V) for c in range(ncol)]
+    go_lw, go_sw, emis, alb, solar = _setup(bands, device, V)
+    pipe = api.Pipeline(go_lw, go_sw, ncol, user_level, emis, alb, solar, spectral=spectral)
+    gcols, keep = api.make_columns(cols, MOL_ORDER, cfc_order=(0, 1))
+    pipe.run_profiles(gcols)
+    got = pipe.profiles(ncol)
+    for c, col in enumerate(cols):
+        for band, lw, key in ((lwb, True, "lw"), (swb, False, "sw")):
+            w = oracle_column(oracle, lib, band, col, lw, emis, alb, solar, user_level)
+            want_up = np.array([oracle.integrate_row(w["up"][k], band.dw) for k in range(V)])
+            want_dn = np.array([oracle.integrate_row(w["dn"][k], band.dw) for k in range(V)])
+            up, dn, hr = got[key + "_up"][c], got[key + "_down"][c], got[key + "_heating"][c]
+            assert np.max(np.abs(up - want_up)) < 1e-9, key
+            assert np.max(np.abs(dn - want_dn)) < 1e-9, key
+            # the kernel's heating rates are the formula applied to its own level fluxes ...
+            hmax = np.abs(hr).max()
+            assert hmax > 0.0
+            assert np.max(np.abs(hr - heating(up, dn, col["p"]))) <= 1e-12 * hmax, key
+            # ... and the chain's are the reference's level fluxes through the formula
+            assert np.max(np.abs(hr - heating(want_up, want_dn, col["p"]))) <= 1e-6 * hmax, key
+            # energy closes: the column's absorbed flux is the net flux at the top minus the net flux at the surface
+            absorbed = np.sum(hr * 100.0 * (col["p"][1:] - col["p"][:-1]) * CP / (GRAVITY * 86400.0))
+            fmax = max(np.abs(up).max(), np.abs(dn).max())
+            assert abs(absorbed - ((dn[0] - up[0]) - (dn[-1] - up[-1]))) <= 1e-12 * fmax, key
+        assert np.all(got["fluxes"][c, [2, 5, 8, 11]] != 0.0)                           # a user level was asked for
+    pipe.destroy()
+    go_lw.destroy()
+    go_sw.destroy()
+
+
+@pytest.mark.parametrize("user_level", [-1, 0, 7, 15])
+def test_top_surface_and_user_rows_are_the_six_row_forms(bands, lib, device, user_level, monkeypatch):
+    V, ncol = 16, 3
+    L = V - 1
+    cols = [syn.profile(20 + c, V) for c in range(ncol)]
+    go_lw, go_sw, emis, alb, solar = _setup(bands, device, V)
+    pipe = api.Pipeline(go_lw, go_sw, ncol, user_level, emis, alb, solar, spectral=False)
+    gcols, keep = api.make_columns(cols, MOL_ORDER, cfc_order=(0, 1))
+    api.check(lib.grt_set_deterministic(1))
+    try:
+        monkeypatch.setenv("GRT_SW_TWO_SWEEPS", "0")
+        pipe.run(gcols)
+        one = pipe.fluxes(ncol)
+        monkeypatch.setenv("GRT_SW_TWO_SWEEPS", "1")
+        pipe.run(gcols)
+        two = pipe.fluxes(ncol)
+        monkeypatch.delenv("GRT_SW_TWO_SWEEPS")
+        pipe.run_profiles(gcols)
+        got = pipe.profiles(ncol)
+    finally:
+        api.check(lib.grt_set_deterministic(-1))
+    for bi, key, want in ((0, "lw", one), (1, "sw", two)):
+        up, dn = got[key + "_up"], got[key + "_down"]
+        six = want[:, 6 * bi: 6 * bi + 6]
+        assert np.array_equal(up[:, 0], six[:, 0]) and np.array_equal(up[:, L], six[:, 1])
+        assert np.array_equal(dn[:, 0], six[:, 3]) and np.array_equal(dn[:, L], six[:, 4])
+        if user_level >= 0:
+            assert np.array_equal(up[:, user_level], six[:, 2]) and np.array_equal(dn[:, user_level], six[:, 5])
+        else:
+            assert np.all(six[:, [2, 5]] == 0.0)
+    assert np.array_equal(one[:, :6], two[:, :6])
+    assert np.max(np.abs(got["fluxes"] - one)) <= 1e-13 * np.abs(one).max()   # the default one-sweep shortwave
+    assert np.array_equal(got["fluxes"], two)
+    pipe.destroy()
+    go_lw.destroy()
+    go_sw.destroy()
+
+
+def test_repeatable_and_no_interference_with_run(bands, lib, device):
+    V, ncol = 16, 3
+    cols = [syn.profile(30 + c, V) for c in range(ncol)]
+    go_lw, go_sw, emis, alb, solar = _setup(bands, device, V)
+    pipe = api.Pipeline(go_lw, go_sw, ncol, 7, emis, alb, solar, spectral=False)
+    gcols, keep = api.make_columns(cols, MOL_ORDER, cfc_order=(0, 1))
+    names = ("lw_up", "lw_down", "sw_up", "sw_down", "lw_heating", "sw_heating", "fluxes")
+    pipe.run_profiles(gcols)
+    a = pipe.profiles(ncol)
+    pipe.run_profiles(gcols)
+    b = pipe.profiles(ncol)
+    for k in names:
+        assert np.max(np.abs(a[k] - b[k])) <= 1e-12 * np.abs(a[k]).max(), k
+    api.check(lib.grt_set_deterministic(1))
+    try:
+        pipe.run_profiles(gcols)
+        a = pipe.profiles(ncol)
+        pipe.run_profiles(gcols)
+        b = pipe.profiles(ncol)
+        assert all(np.array_equal(a[k], b[k]) for k in names)
+        pipe.run(gcols)
+        first = pipe.fluxes(ncol)
+        pipe.run_profiles(gcols)
+        pipe.sync()
+        pipe.run(gcols)
+        assert np.array_equal(pipe.fluxes(ncol), first)
+    finally:
+        api.check(lib.grt_set_deterministic(-1))
+    pipe.destroy()
+    go_lw.destroy()
+    go_sw.destroy()
+
+
+def test_edge_cases(bands, lib, device):
+    lwb, swb = bands
+    V, ncol = 16, 2
+    cols = [syn.profile(50 + c, V) for c in range(ncol)]
+    go_lw, go_sw, emis, alb, solar = _setup(bands, device, V)
+    gcols, keep = api.make_columns(cols, MOL_ORDER, cfc_order=(0, 1))
+    # a longwave-only pipeline: zero shortwave rows, finite longwave ones
+    pipe = api.Pipeline(go_lw, None, ncol, -1, emis, None, None, spectral=False)
+    pipe.run_profiles(gcols)
+    got = pipe.profiles(ncol)
+    assert np.all(got["sw_up"] == 0.0) and np.all(got["sw_down"] == 0.0) and np.all(got["sw_heating"] == 0.0)
+    assert np.all(got["fluxes"][:, 6:] == 0.0)
+    for k in ("lw_up", "lw_down", "lw_heating"):
+        assert np.all(np.isfinite(got[k])), k
+    assert np.all(got["lw_up"] > 0.0) and np.abs(got["lw_heating"]).max() > 0.0
+    # more columns than the pipeline was made for; no level-flux buffer
+    big, keep_big = api.make_columns([syn.profile(50 + c, V) for c in range(ncol + 1)], MOL_ORDER, cfc_order=(0, 1))
+    with pytest.raises(api.GrtError) as e:
+        pipe.run_profiles(big)
+    assert e.value.code == api.VALUE_ERR
+    with pytest.raises(api.GrtError) as e:
+        api.check(lib.grt_pipeline_run_profiles(pipe.p, C.byref(gcols), None, pipe.prof["heating"].ptr, None))
+    assert e.value.code == api.VALUE_ERR
+    pipe.destroy()
+    # heating_dev and fluxes_dev may be NULL
+    pipe = api.Pipeline(go_lw, go_sw, ncol, -1, emis, alb, solar, spectral=False)
+    api.check(lib.grt_set_deterministic(1))
+    try:
+        pipe.run_profiles(gcols)
+        want = pipe.profiles(ncol)
+        levels = api.DeviceBuffer(device, 8 * ncol * 4 * V)
+        api.check(lib.grt_pipeline_run_profiles(pipe.p, C.byref(gcols), levels.ptr, None, None))
+        pipe.sync()
+        lv = levels.to_host((ncol, 4, V))
+        levels.free()
+    finally:
+        api.check(lib.grt_set_deterministic(-1))
+    for r, k in enumerate(("lw_up", "lw_down", "sw_up", "sw_down")):
+        assert np.array_equal(lv[:, r], want[k]), k
+    pipe.destroy()
+    go_lw.destroy()
+    go_sw.destroy()
+
+
+def test_full_shortwave_width(tmp_path, lib, device):
+    """The bench's shortwave grid (1-50 000 cm-1 @ 1: 391 workgroups per column), 61 levels, a small line list: the fused
+    profile form (its partial sums and the park block allocated at this first call) against the materialised one."""
+    band = Band(str(tmp_path), 1.0, 50000.0, 1.0, 2000, sw=True)
+    V, ncol = 61, 4
+    cols = [syn.profile(90 + c, V) for c in range(ncol)]
+    gcols, keep = api.make_columns(cols, MOL_ORDER, cfc_order=(0, 1))
+    got = {}
+    for spectral in (False, True):
+        go, grid = band.gas_optics(device, V)
+        solar = api.create_solar_flux(grid, band.files["solar"])
+        pipe = api.Pipeline(None, go, ncol, -1, None, np.full(band.nw, 0.3), solar, spectral=spectral)
+        pipe.run_profiles(gcols)
+        got[spectral] = pipe.profiles(ncol)
+        pipe.destroy()
+        go.destroy()
+    for k in ("sw_up", "sw_down", "fluxes"):
+        scale = np.abs(got[True][k]).max()
+        assert scale > 0.0
+        assert np.max(np.abs(got[False][k] - got[True][k])) <= 1e-12 * scale, k
+    # the heating rates differ by what the level fluxes do, divided by the layers' mass: no more than the bound of that
+    fmax = max(np.abs(got[True]["sw_up"]).max(), np.abs(got[True]["sw_down"]).max())
+    dp = np.array([c["p"][1:] - c["p"][:-1] for c in cols])
+    bound = (GRAVITY / CP) * 86400.0 * 4e-12 * fmax / (100.0 * dp)
+    assert np.all(np.abs(got[False]["sw_heating"] - got[True]["sw_heating"]) <= bound)
+    for form in (False, True):
+        g = got[form]
+        for c, col in enumerate(cols):
+            want = heating(g["sw_up"][c], g["sw_down"][c], col["p"])
+            assert np.max(np.abs(g["sw_heating"][c] - want)) <= 1e-12 * np.abs(want).max()
+    assert np.all(got[False]["lw_up"] == 0.0) and np.all(got[False]["lw_heating"] == 0.0)
+    assert np.all(got[False]["sw_down"][:, 0] > 0.0)
