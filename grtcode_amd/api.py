@@ -20,6 +20,8 @@ LINE_SAMPLE = 2
 GRT_FLUXES_PER_COLUMN = 12
 GRT_PROFILE_ROWS_PER_COLUMN = 4     # LW up, LW down, SW up, SW down, each [V]
 GRT_HEATING_ROWS_PER_COLUMN = 2     # LW, SW, each [V-1]
+GRT_ALLSKY_FLUXES_PER_COLUMN = 24   # grt_pipeline_run's twelve (clear sky), then the same twelve all-sky
+GRT_CLOUDS = 6                      # grt_sizeof kind of GrtClouds
 RETURN_CODES = ["GRTCODE_SUCCESS", "GRTCODE_INVALID_ERR", "GRTCODE_DIVBYZERO_ERR", "GRTCODE_OVERFLOW_ERR",
                 "GRTCODE_UNDERFLOW_ERR", "GRTCODE_SENTINEL_ERR", "GRTCODE_NULL_ERR", "GRTCODE_NON_NULL_ERR",
                 "GRTCODE_RANGE_ERR", "GRTCODE_VALUE_ERR", "GRTCODE_COMPILER_ERR", "GRTCODE_IO_ERR",
@@ -124,6 +126,13 @@ class GrtColumns(C.Structure):
                 ("cia_ppmv", c_double_p), ("cos_zenith", c_double_p), ("total_solar_irradiance", c_double_p)]
 
 
+class GrtClouds(C.Structure):
+    _fields_ = [("num_liquid_bands", C.c_int), ("num_ice_bands", C.c_int),
+                ("liquid_band_lo", c_double_p), ("liquid_band_hi", c_double_p),
+                ("ice_band_lo", c_double_p), ("ice_band_hi", c_double_p), ("thickness", c_double_p),
+                ("lw_liquid", c_double_p), ("lw_ice", c_double_p), ("sw_liquid", c_double_p), ("sw_ice", c_double_p)]
+
+
 #: every symbol include/*.h declares (checked by tests/test_abi_symbols.py against the headers too)
 EXPORTS = """
 grtcode_errstr grtcode_set_verbosity grtcode_verbosity create_device get_num_gpus
@@ -139,7 +148,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -178,6 +187,7 @@ def load_library(path=None):
     lib.grt_host_to_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
     lib.grt_pipeline_run.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.c_void_p]
     lib.grt_pipeline_run_profiles.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.grt_pipeline_run_allsky.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtClouds), C.c_void_p]
     lib.grt_multi_gather_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.grt_pipeline_sync.argtypes = [C.c_void_p]
     lib.grt_pipeline_stream.argtypes = [C.c_void_p]
@@ -439,6 +449,22 @@ def make_columns(cols, mol_order, cfc_order=(), num_levels=None):
     return gc, keep
 
 
+def make_clouds(liquid_bands, ice_bands, thickness, lw_liquid, lw_ice, sw_liquid, sw_ice):
+    """Pack cloud inputs into a GrtClouds struct (+ keep-alive arrays) for Pipeline.run_allsky.
+    liquid_bands / ice_bands: (lo, hi) band limits in cm-1 ([B] and [>= B]); thickness [ncol][L] m; each optics set
+    [ncol][3][B][L] (extinction m-1, single-scattering albedo, asymmetry), e.g. grt_clouds_band_optics' per column; a set
+    may be None for a band the pipeline does not have."""
+    keep = dict(llo=_f64(liquid_bands[0]), lhi=_f64(liquid_bands[1]), ilo=_f64(ice_bands[0]), ihi=_f64(ice_bands[1]),
+                th=_f64(thickness))
+    for k, v in (("lwl", lw_liquid), ("lwi", lw_ice), ("swl", sw_liquid), ("swi", sw_ice)):
+        keep[k] = _f64(v) if v is not None else None
+    ptr = lambda a: _dp(a) if a is not None else None
+    gc = GrtClouds(keep["llo"].size, keep["ilo"].size, ptr(keep["llo"]), ptr(keep["lhi"]), ptr(keep["ilo"]),
+                   ptr(keep["ihi"]), ptr(keep["th"]), ptr(keep["lwl"]), ptr(keep["lwi"]), ptr(keep["swl"]),
+                   ptr(keep["swi"]))
+    return gc, keep
+
+
 class Pipeline:
     def __init__(self, lw_gas, sw_gas, max_columns, user_level, emissivity, albedo, solar, spectral=True):
         """spectral=True keeps tau/omega/g and the spectral fluxes (views(): what parity tests read);
@@ -458,6 +484,7 @@ class Pipeline:
         self.max_columns = max_columns
         self.num_levels = (lw_gas or sw_gas).num_levels
         self.prof = None        # run_profiles' device outputs: allocated at its first call
+        self.allsky = None      # run_allsky's [max_columns][24]: allocated at its first call
 
     def run(self, gcols, out_ptr=None):
         check(self.lib.grt_pipeline_run(self.p, C.byref(gcols), out_ptr if out_ptr is not None else self.out.ptr))
@@ -493,6 +520,18 @@ class Pipeline:
                     lw_heating=hr[:, 0].copy(), sw_heating=hr[:, 1].copy(),
                     fluxes=self.prof["fluxes"].to_host((ncol, GRT_FLUXES_PER_COLUMN)))
 
+    def run_allsky(self, gcols, gclouds):
+        """grt_pipeline_run_allsky into this object's device buffer (allsky_fluxes() reads it)."""
+        if self.allsky is None:
+            self.allsky = DeviceBuffer(self.device, 8 * GRT_ALLSKY_FLUXES_PER_COLUMN * self.max_columns)
+        check(self.lib.grt_pipeline_run_allsky(self.p, C.byref(gcols), C.byref(gclouds), self.allsky.ptr))
+
+    def allsky_fluxes(self, ncol):
+        """The last run_allsky: (clear, all-sky), each [ncol][12] in grt_pipeline_run's layout."""
+        self.sync()
+        f = self.allsky.to_host((ncol, GRT_ALLSKY_FLUXES_PER_COLUMN))
+        return f[:, :GRT_FLUXES_PER_COLUMN].copy(), f[:, GRT_FLUXES_PER_COLUMN:].copy()
+
     def views(self, band):
         ptrs = [C.c_void_p() for _ in range(6)]
         if not self.spectral:
@@ -506,6 +545,9 @@ class Pipeline:
         for buf in (self.prof or {}).values():
             buf.free()
         self.prof = None
+        if self.allsky is not None:
+            self.allsky.free()
+            self.allsky = None
         check(self.lib.grt_pipeline_destroy(C.byref(self.p)))
 
 

@@ -326,6 +326,25 @@ int grt_launch_sw_profile(void *stream, GrtSwArgs const *a);
 int grt_launch_profile_finish(void *stream, int ncol, int num_levels, int bands, int user_level, double gravity,
                               double cp, double const *pressure, double *levels, double *heating, double *fluxes);
 
+/* All-sky form of the fused solvers (grt_pipeline_run_allsky): the fused form's arguments (tau_gas set, six-row partial
+   sums), and per layer the liquid and ice cloud objects formed in registers from the band tables below and combined with
+   gas and Rayleigh by allsky_combine (optics_dev.h).  band_liquid / band_ice: DEVICE [nw] band of each grid point, -1 for
+   none; thickness [ncol][L] m; liquid / ice [ncol][3][num_bands][L] (extinction m-1, albedo, asymmetry). */
+typedef struct GrtCloudArgs
+{
+    int num_bands;
+    int const *band_liquid, *band_ice;
+    double const *thickness;
+    double const *liquid, *ice;
+} GrtCloudArgs;
+int grt_launch_lw_allsky(void *stream, GrtLwArgs const *a, GrtCloudArgs const *c);
+int grt_launch_sw_allsky(void *stream, GrtSwArgs const *a, GrtCloudArgs const *c);
+/* Materialised form: the cloud objects of the same tables spread onto the grid, [ncol][L][nw] each (tau = extinction x
+   thickness; zero where a point has no band). */
+int grt_launch_spread_clouds(void *stream, int num_layers, int ncol, uint64_t nw, GrtCloudArgs const *c,
+                             double *liquid_tau, double *liquid_omega, double *liquid_g,
+                             double *ice_tau, double *ice_omega, double *ice_g);
+
 /* Fused Rayleigh + combine for the clear-sky driver sequence (rayleigh.c:39 +
    optics.c:138-145 with K=2, gas omega=g=0, Rayleigh omega=1,g=0):
    tau_tot = tau_gas + tau_R, omega = tau_R/tau_tot, g = 0/ tau_R.  n_layer [ncol][L]. */

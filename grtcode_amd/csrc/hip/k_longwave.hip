@@ -13,7 +13,8 @@
 //
 // SURVEY.md §8a19 prices it at 1 944 B per wavenumber at 60 layers; measured it is a latency
 // chain -- 120 dependent layer steps with six fp64 exp each on 26 000 threads at 1 cm-1 -- which is why column
-// batches share a launch.  lw_kernel<true, false> is the fused form of the production pipeline.
+// batches share a launch.  lw_kernel<true, false> is the fused form of the production pipeline, lw_kernel<true, false, true>
+// its all-sky form.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -66,9 +67,12 @@ __device__ __forceinline__ double extinction(double c1, double tau)
 // weighted value is summed across the wave where the sweep produces it, the waves' sums wait in dynamic LDS
 // (2 V x kBlock/64 doubles) and the block's sums go to partials[(c*2 V + r)*nblocks + block], r = level (up),
 // V + level (down).  Same association as block_partials: the six-row form's rows come out the same to the bit.
-template <bool FUSED, bool PROFILE>
-__global__ __launch_bounds__(kBlock) void lw_kernel(GrtLwArgs a)
+// ALLSKY (fused six-row form only): the liquid and ice cloud objects join per layer (GrtCloudArgs): each point reads its
+// two band indices once, each layer forms the two objects from the column's band tables and allsky_combine adds the four.
+template <bool FUSED, bool PROFILE, bool ALLSKY = false, typename... Clouds>
+__global__ __launch_bounds__(kBlock) void lw_kernel(GrtLwArgs a, Clouds... clouds)
 {
+    GrtCloudArgs const cl = cloud_args(clouds...);      // (ALLSKY: the one GrtCloudArgs argument)
     double const c1[4] = {-14.402613260847248, -3.0302159969901132,
                           -1.4925584280108841, -1.0746123148178333};   // longwave.c:160-163
     double const c2[4] = {0.07587638482015649, 0.676114979733751,
@@ -106,6 +110,8 @@ __global__ __launch_bounds__(kBlock) void lw_kernel(GrtLwArgs a)
     {
         continua_load(a.continua, a.nw, ii, blk_lo, blk_hi, pc);
     }
+    int const band_l = ALLSKY ? cl.band_liquid[ii] : -1, band_i = ALLSKY ? cl.band_ice[ii] : -1;
+    uint64_t const ctab = ALLSKY ? (uint64_t)col*3*(uint64_t)cl.num_bands*L : 0;
 
     // absorption optical depth of layer j: tau (1 - omega)  (longwave.c:252)
     auto layer_tau = [&](int j) -> double
@@ -119,7 +125,18 @@ __global__ __launch_bounds__(kBlock) void lw_kernel(GrtLwArgs a)
             {
                 tg = continua_add(a.continua, pc, cstate, j, a.nw, ii, blk_lo, blk_hi, tg);
             }
-            clear_sky_combine(tg, rayleigh_tau(w, nl[j]), t, om, gg);
+            if constexpr (ALLSKY)
+            {
+                double const th = cl.thickness[(uint64_t)col*L + j];
+                double lt, lo, lg, it, io, ig;
+                cloud_layer(cl.liquid + ctab, cl.num_bands, L, band_l, j, th, lt, lo, lg);
+                cloud_layer(cl.ice + ctab, cl.num_bands, L, band_i, j, th, it, io, ig);
+                allsky_combine(tg, rayleigh_tau(w, nl[j]), lt, lo, lg, it, io, ig, t, om, gg);
+            }
+            else
+            {
+                clear_sky_combine(tg, rayleigh_tau(w, nl[j]), t, om, gg);
+            }
             return t*(1. - om);
         }
         return omega ? tau[o]*(1. - omega[o]) : tau[o]*(1. - 0.);
@@ -420,5 +437,18 @@ extern "C" int grt_launch_lw_profile(void *stream, GrtLwArgs const *a)
     }
     hipLaunchKernelGGL((lw_kernel<true, true>), dim3(grt_solver_blocks(a->nw), a->ncol, 1), dim3(kBlock), lds,
                        (hipStream_t)stream, *a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_lw_allsky(void *stream, GrtLwArgs const *a, GrtCloudArgs const *c)
+{
+    if (a->ncol < 1 || a->nw < 2 || a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr ||
+        c->num_bands < 1 || c->band_liquid == nullptr || c->band_ice == nullptr || c->thickness == nullptr ||
+        c->liquid == nullptr || c->ice == nullptr)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL((lw_kernel<true, false, true, GrtCloudArgs>), dim3(grt_solver_blocks(a->nw), a->ncol, 1), dim3(kBlock), 0, (hipStream_t)stream,
+                       *a, *c);
     return (int)hipGetLastError();
 }

@@ -127,6 +127,28 @@ __global__ __launch_bounds__(kBlock) void clear_sky_kernel(int L, int ncol, doub
     }
 }
 
+// Materialised all-sky form: the liquid and ice cloud objects of grt_pipeline_run_allsky on the grid, [ncol][L][nw] each,
+// from the band tables (GrtCloudArgs; cloud_layer: tau = extinction x thickness, nothing where a point has no band), for
+// add_optics' kernel to add to gas and Rayleigh.
+__global__ __launch_bounds__(kBlock) void spread_clouds_kernel(int L, int ncol, uint64_t nw, GrtCloudArgs c,
+                                                               double *lt, double *lo, double *lg,
+                                                               double *it, double *io, double *ig)
+{
+    uint64_t const per_col = (uint64_t)L*nw;
+    uint64_t const total = per_col*ncol;
+    for (uint64_t o = (uint64_t)blockIdx.x*kBlock + threadIdx.x; o < total; o += (uint64_t)gridDim.x*kBlock)
+    {
+        uint64_t const col = o/per_col;
+        uint64_t const r = o - col*per_col;
+        int const j = (int)(r/nw);
+        uint64_t const i = r - (uint64_t)j*nw;
+        uint64_t const tab = col*3*(uint64_t)c.num_bands*L;
+        double const th = c.thickness[col*L + j];
+        cloud_layer(c.liquid + tab, c.num_bands, L, c.band_liquid[i], j, th, lt[o], lo[o], lg[o]);
+        cloud_layer(c.ice + tab, c.num_bands, L, c.band_ice[i], j, th, it[o], io[o], ig[o]);
+    }
+}
+
 // tau_gas += the spectral tables' part, for a tau the gas-optics launch wrote without it (GrtGasOpticsArgs.skip_tables):
 // the pipeline's fused solvers add it themselves; this completes the array for a caller that wants to LOOK at tau_gas
 // (grt_pipeline_views).  One thread per grid point and column, walking the layers: continua_add's doubles.
@@ -342,6 +364,21 @@ extern "C" int grt_launch_clear_sky_optics(void *stream, int num_layers, int nco
 {
     hipLaunchKernelGGL(clear_sky_kernel, dim3(grid_for((uint64_t)num_layers*nw*ncol)), dim3(kBlock), 0,
                        (hipStream_t)stream, num_layers, ncol, w0, dw, nw, n_layer, tau_gas, tau, omega, g);
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_spread_clouds(void *stream, int num_layers, int ncol, uint64_t nw, GrtCloudArgs const *c,
+                                        double *liquid_tau, double *liquid_omega, double *liquid_g,
+                                        double *ice_tau, double *ice_omega, double *ice_g)
+{
+    if (num_layers < 1 || ncol < 1 || c->num_bands < 1 || c->band_liquid == nullptr || c->band_ice == nullptr ||
+        c->thickness == nullptr || c->liquid == nullptr || c->ice == nullptr)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(spread_clouds_kernel, dim3(grid_for((uint64_t)num_layers*nw*ncol)), dim3(kBlock), 0,
+                       (hipStream_t)stream, num_layers, ncol, nw, *c, liquid_tau, liquid_omega, liquid_g,
+                       ice_tau, ice_omega, ice_g);
     return (int)hipGetLastError();
 }
 

@@ -162,9 +162,12 @@ __device__ __forceinline__ LayerProps layer_props(double omega, double g, double
 // reflectances of EVERY level in rows 0 .. 2 V - 1 of the park block, the second produces up and down at every level and
 // sums each across the wave at once (wave_row_sum, as lw_kernel<true, true>); the block's sums of the 2 V rows go to
 // partials[(c*2 V + r)*nblocks + block], r = level (up), V + level (down).
-template <bool FUSED, bool PROFILE>
-__global__ __launch_bounds__(kBlock) void sw_kernel(GrtSwArgs a)
+// ALLSKY (fused six-row form only): the liquid and ice cloud objects join per layer (GrtCloudArgs), as in lw_kernel; the
+// one-sweep and two-sweep rule is the fused form's.
+template <bool FUSED, bool PROFILE, bool ALLSKY = false, typename... Clouds>
+__global__ __launch_bounds__(kBlock) void sw_kernel(GrtSwArgs a, Clouds... clouds)
 {
+    GrtCloudArgs const cl = cloud_args(clouds...);      // (ALLSKY: the one GrtCloudArgs argument)
     uint64_t const i = (uint64_t)blockIdx.x*kBlock + threadIdx.x;
     int const col = blockIdx.y;
     bool const live = i < a.nw;
@@ -205,6 +208,8 @@ __global__ __launch_bounds__(kBlock) void sw_kernel(GrtSwArgs a)
     {
         continua_load(a.continua, nw, ii, blk_lo, blk_hi, pc);
     }
+    int const band_l = ALLSKY ? cl.band_liquid[ii] : -1, band_i = ALLSKY ? cl.band_ice[ii] : -1;
+    uint64_t const ctab = ALLSKY ? (uint64_t)col*3*(uint64_t)cl.num_bands*L : 0;
 
     auto props_of = [&](int j) -> LayerProps
     {
@@ -217,7 +222,18 @@ __global__ __launch_bounds__(kBlock) void sw_kernel(GrtSwArgs a)
             {
                 tg = continua_add(a.continua, pc, cstate, j, nw, ii, blk_lo, blk_hi, tg);
             }
-            clear_sky_combine(tg, rayleigh_tau(w, nl[j]), t, om, gg);
+            if constexpr (ALLSKY)
+            {
+                double const th = cl.thickness[(uint64_t)col*L + j];
+                double lt, lo, lg, it, io, ig;
+                cloud_layer(cl.liquid + ctab, cl.num_bands, L, band_l, j, th, lt, lo, lg);
+                cloud_layer(cl.ice + ctab, cl.num_bands, L, band_i, j, th, it, io, ig);
+                allsky_combine(tg, rayleigh_tau(w, nl[j]), lt, lo, lg, it, io, ig, t, om, gg);
+            }
+            else
+            {
+                clear_sky_combine(tg, rayleigh_tau(w, nl[j]), t, om, gg);
+            }
             return layer_props(om, gg, t, mu_dir, mu_dif);
         }
         return layer_props(omega[o], g[o], tau[o], mu_dir, mu_dif);
@@ -651,5 +667,19 @@ extern "C" int grt_launch_sw_profile(void *stream, GrtSwArgs const *a)
     }
     hipLaunchKernelGGL((sw_kernel<true, true>), dim3((unsigned)((a->nw + kBlock - 1)/kBlock), a->ncol, 1), dim3(kBlock),
                        lds, (hipStream_t)stream, *a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_sw_allsky(void *stream, GrtSwArgs const *a, GrtCloudArgs const *c)
+{
+    bool const one_sweep = a->one_sweep && (a->user_level < 0 || a->user_level == 0 || a->user_level == a->num_levels - 1);
+    if (a->ncol < 1 || a->nw < 2 || a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr ||
+        (a->park == nullptr && !one_sweep) || c->num_bands < 1 || c->band_liquid == nullptr || c->band_ice == nullptr ||
+        c->thickness == nullptr || c->liquid == nullptr || c->ice == nullptr)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL((sw_kernel<true, false, true, GrtCloudArgs>), dim3((unsigned)((a->nw + kBlock - 1)/kBlock), a->ncol, 1), dim3(kBlock), 0,
+                       (hipStream_t)stream, *a, *c);
     return (int)hipGetLastError();
 }

@@ -34,6 +34,55 @@ __device__ __forceinline__ void clear_sky_combine(double tg, double tr, double &
     tau = ts;
 }
 
+// add_optics({gas, rayleigh, liquid cloud, ice cloud}) for one (layer, wavenumber) (driver.c:518-530): the sums of
+// optics.c:138-145 term by term in that order, gas omega = g = 0 and Rayleigh omega = 1, g = 0 written out as in
+// clear_sky_combine.  Cloud terms of zero add exact zeros: a point with no cloud gets clear_sky_combine's doubles.
+__device__ __forceinline__ void allsky_combine(double tg, double tr, double tl, double ol, double gl, double ti, double oi,
+                                               double gi, double &tau, double &omega, double &g)
+{
+    double gs = 0., os = 0., ts = 0.;
+    gs += 0.*0.*tg;  os += 0.*tg;  ts += tg;
+    gs += 0.*1.*tr;  os += 1.*tr;  ts += tr;
+    gs += gl*ol*tl;  os += ol*tl;  ts += tl;
+    gs += gi*oi*ti;  os += oi*ti;  ts += ti;
+    if (!(gs == 0. && os > 0. && os < 1.7976931348623157e308))
+    {
+        gs /= os;           // (as clear_sky_combine: +0 over a positive finite number is +0)
+    }
+    os /= ts;
+    g = gs;
+    omega = os;
+    tau = ts;
+}
+
+// The solver kernels' cloud arguments: none in the clear-sky instances, one GrtCloudArgs in the all-sky ones (their
+// template parameter pack: the clear-sky instances keep their parameter list)
+__device__ __forceinline__ GrtCloudArgs cloud_args()
+{
+    return GrtCloudArgs{0, nullptr, nullptr, nullptr, nullptr, nullptr};
+}
+
+__device__ __forceinline__ GrtCloudArgs cloud_args(GrtCloudArgs const &c)
+{
+    return c;
+}
+
+// One cloud object's optics at (layer j, a point that takes band `band`) from a column's band table tab [3][B][L]
+// (extinction, albedo, asymmetry; GrtCloudArgs): optical depth = extinction x layer thickness (driver.c:518-526); no band
+// (band < 0): no cloud.
+__device__ __forceinline__ void cloud_layer(double const *tab, int B, int L, int band, int j, double thickness, double &t,
+                                            double &o, double &g)
+{
+    t = 0.; o = 0.; g = 0.;
+    if (band >= 0)
+    {
+        uint64_t const at = (uint64_t)band*L + j, plane = (uint64_t)B*L;
+        t = tab[at]*thickness;
+        o = tab[plane + at];
+        g = tab[2*plane + at];
+    }
+}
+
 // ---- the spectral tables' part of the gas optical depth, added where tau is read (GrtContinua, grt_kernels.h) ----
 // write_tile's expressions in write_tile's order (gas_optics_dev.h; kernels.c:484-487 and :585-630): the same doubles as
 // a gas-optics launch that adds them itself.  A thread owns one grid point and walks the layers: its table entries are

@@ -499,6 +499,67 @@ double grt_clouds_beta(int inverse, int p, int q, double x)
     return beta_lookup(&lib.beta, inverse ? lib.beta.inverse : lib.beta.value, p, q, x);
 }
 
+/* cloud_optics without the spreading: the optics of every liquid band and layer, liquid[3][B][L] and ice[3][B][L]
+   (extinction m-1, single-scattering albedo, asymmetry), B = the liquid parametrisation's band count.  The same subcolumn
+   draws as cloud_optics, in the same order (one sample_subcolumn per band), and the same pade_band values: spreading
+   band b of these with the band limits of grt_clouds_bands gives cloud_optics' arrays bit for bit. */
+int grt_clouds_band_optics(int num_layers, const double *mean_cloud_fraction, const double *mean_liquid_content,
+                           const double *mean_ice_content, const double *overlap, const double liquid_radius,
+                           const double *temperature, double *liquid, double *ice)
+{
+    if (!lib.ready)
+    {
+        fatal("grt_clouds_band_optics called before initialize_clouds_lib", NULL);
+    }
+    if (num_layers < 1 || liquid == NULL || ice == NULL)
+    {
+        return 1;
+    }
+    size_t const L = (size_t)num_layers, B = (size_t)lib.liquid.nband;
+    double *work = malloc(sizeof(double)*4*L);
+    if (work == NULL)
+    {
+        fatal("out of memory", NULL);
+    }
+    double *ice_radius = work, *rank = work + L, *ql = work + 2*L, *qi = work + 3*L;
+    for (size_t i = 0; i < L; ++i)
+    {
+        ice_radius[i] = ice_size(temperature[i])/2.0;
+    }
+    for (int band = 0; band < lib.liquid.nband; ++band)
+    {
+        sample_subcolumn(num_layers, mean_cloud_fraction, mean_liquid_content, mean_ice_content, overlap, rank, ql, qi);
+        for (size_t i = 0; i < L; ++i)
+        {
+            size_t const at = (size_t)band*L + i;
+            pade_band(&lib.liquid, ql[i], liquid_radius, band);
+            liquid[at] = lib.liquid.ext[band]; liquid[B*L + at] = lib.liquid.ssa[band]; liquid[2*B*L + at] = lib.liquid.asy[band];
+            pade_band(&lib.ice, qi[i], ice_radius[i], band);
+            ice[at] = lib.ice.ext[band]; ice[B*L + at] = lib.ice.ssa[band]; ice[2*B*L + at] = lib.ice.asy[band];
+        }
+    }
+    free(work);
+    return 0;
+}
+
+/* the loaded band limits [cm-1] of one parametrisation (ice != 0: ice, else liquid), after pade_load's rounding to single
+   precision; lo / hi may be NULL to ask for the count */
+int grt_clouds_bands(int ice, int *num_bands, double *lo, double *hi)
+{
+    if (!lib.ready || num_bands == NULL)
+    {
+        return 1;
+    }
+    PadeOptics const *o = ice ? &lib.ice : &lib.liquid;
+    *num_bands = o->nband;
+    for (int b = 0; b < o->nband; ++b)
+    {
+        if (lo) lo[b] = o->band_lo[b];
+        if (hi) hi[b] = o->band_hi[b];
+    }
+    return 0;
+}
+
 int cloud_optics(const double *wavenum, int num_wavenum, int num_layers, const double *mean_cloud_fraction,
                  const double *mean_liquid_content, const double *mean_ice_content, const double *overlap,
                  const double liquid_radius, const double *temperature, double *beta_liquid, double *omega_liquid,

@@ -481,6 +481,7 @@ EXTERN size_t grt_sizeof(int kind)
         case GRT_SOLAR_FLUX: return sizeof(SolarFlux_t);
         case GRT_LONGWAVE: return sizeof(Longwave_t);
         case GRT_SHORTWAVE: return sizeof(Shortwave_t);
+        case GRT_CLOUDS: return sizeof(GrtClouds_t);
         default: return 0;
     }
 }

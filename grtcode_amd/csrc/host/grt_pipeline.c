@@ -17,6 +17,9 @@
  * grt_pipeline_run_profiles runs the same prologue and gas optics, then the profile form of the solvers (every level's
  * flux summed per block in-kernel, or -- materialised form -- integrated row by row from the spectra) and one small
  * kernel that forms the level fluxes, the heating rates and the six-row output from them.
+ * grt_pipeline_run_allsky runs grt_pipeline_run's clear-sky pass and then, on the same tau_gas, the all-sky pass of
+ * driver.c:474-597: the cloud objects formed from band tables inside the solvers (or, materialised form, spread onto the
+ * grid and added by the add_optics kernel).
  * All work is enqueued on the device's library stream; nothing synchronises.
  */
 #include <stdlib.h>
@@ -41,6 +44,11 @@ typedef struct GrtBand
     /* grt_pipeline_run_profiles, allocated at its first call: */
     double *level_partials;        /* fused form: [cols][2 V][nblocks] */
     double **level_rows_d;         /* materialised form: [cols][2 V] device row pointers (up levels, then down levels) */
+    /* grt_pipeline_run_allsky: */
+    int *cloud_map;        /* [2][n] cloud band of each grid point (liquid, ice), -1: none */
+    double *cloud_key;     /* host: the band limits cloud_map was built for (B, num_ice_bands, liquid lo/hi, ice lo/hi) */
+    size_t cloud_key_n;
+    double *cloud_block;   /* materialised form: liquid and ice tau, omega, g [6][cols][L][n], Rayleigh [3][L][n], zeros [L][n] */
 } GrtBand;
 
 struct GrtPipeline
@@ -55,6 +63,11 @@ struct GrtPipeline
     void *small_uploaded;  /* event: small_h has been copied out and may be refilled */
     size_t off_n, off_tl, off_tv, off_ts, off_mu, off_tsi, off_p, small_doubles;
     double *emis_d, *albedo_d, *solar_d;
+    /* grt_pipeline_run_allsky's band tables: pinned host staging + device copy, [cols][L] thickness, then [cols][3][B][L]
+       of the longwave liquid, longwave ice, shortwave liquid, shortwave ice */
+    double *cloud_h, *cloud_d;
+    size_t cloud_doubles;
+    void *cloud_uploaded;
 };
 
 static void grt_pipeline_release(GrtPipeline_t **pipeline);
@@ -220,7 +233,13 @@ static void grt_pipeline_release(GrtPipeline_t **pipeline)
         grt_dev_free(p->device, p->band[b].rows_d);
         grt_dev_free(p->device, p->band[b].level_partials);
         grt_dev_free(p->device, p->band[b].level_rows_d);
+        grt_dev_free(p->device, p->band[b].cloud_map);
+        grt_dev_free(p->device, p->band[b].cloud_block);
+        free(p->band[b].cloud_key);
     }
+    grt_dev_free(p->device, p->cloud_d);
+    grt_host_free_pinned(p->cloud_h);
+    grt_dev_event_destroy(p->device, &p->cloud_uploaded);
     grt_dev_free(p->device, p->small_d);
     grt_host_free_pinned(p->small_h);
     grt_dev_event_destroy(p->device, &p->small_uploaded);
@@ -427,19 +446,76 @@ static int park_block(GrtPipeline_t *p, GrtBand *b)
     return GRTCODE_SUCCESS;
 }
 
+/* Fused form: Rayleigh, add_optics({gas, rayleigh}) -- or, with clouds, add_optics({gas, rayleigh, liquid, ice}) --, solver
+   and -integrated output (driver.c:268, 382-424, 302-326) in one launch, then the fixed-order sum of its per-block partial
+   sums into the six values at fluxes_dev[c*out_stride + out_offset ..] */
+static int band_fused_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, int defer, GrtContinua const *continua,
+                             GrtCloudArgs const *clouds, double *fluxes_dev, int out_stride, int out_offset)
+{
+    int const V = p->num_levels;
+    void *s = grt_dev_stream(p->device);
+    int slot, krc;
+    if (bi == 0)
+    {
+        GrtLwArgs a;
+        fused_lw_args(p, b, C, defer, continua, &a);
+        a.partials = b->partials;
+        slot = grt_profile_begin(s, clouds ? 8 : 3);
+        krc = clouds ? grt_launch_lw_allsky(s, &a, clouds) : grt_launch_lw(s, &a);
+        grt_profile_end(s, slot);
+        GRT_TRY(grt_dev_check(krc, clouds ? "longwave kernel (all-sky)" : "longwave kernel (fused)"));
+    }
+    else
+    {
+        GrtSwArgs a;
+        fused_sw_args(p, b, C, defer, continua, &a);
+        a.partials = b->partials;
+        {
+            /* (read at every step, so that a test can compare the two forms in one process) */
+            char const *env = getenv("GRT_SW_TWO_SWEEPS");
+            a.one_sweep = !(env != NULL && env[0] == '1');
+        }
+        if (!(a.one_sweep && (p->user_level < 0 || p->user_level == 0 || p->user_level == V - 1)))
+        {
+            GRT_TRY(park_block(p, b));
+        }
+        a.park = b->park;
+        slot = grt_profile_begin(s, clouds ? 9 : 4);
+        krc = clouds ? grt_launch_sw_allsky(s, &a, clouds) : grt_launch_sw(s, &a);
+        grt_profile_end(s, slot);
+        GRT_TRY(grt_dev_check(krc, clouds ? "shortwave kernel (all-sky)" : "shortwave kernel (fused)"));
+    }
+    GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, b->partials, C*6, b->nblocks, fluxes_dev, GRT_FLUXES_PER_BAND,
+                                                     out_stride, out_offset), "flux reduction kernel"));
+    return GRTCODE_SUCCESS;
+}
+
 /* Materialised form: Rayleigh + add_optics({gas, rayleigh}) (driver.c:268, 382-383), then the solver writing
    [level][wavenumber] fluxes. */
+static int band_spectral_fluxes(GrtPipeline_t *p, GrtBand *b, int bi, int C, int tag);
+
 static int band_spectral_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C)
 {
     SpectralGrid_t const *grid = &b->gas->grid;
     int const V = p->num_levels, L = V - 1;
-    uint64_t const per_opt = (uint64_t)L*b->n, per_flux = (uint64_t)V*b->n;
     void *s = grt_dev_stream(p->device);
     int slot = grt_profile_begin(s, 5);
     int krc = grt_launch_clear_sky_optics(s, L, C, grid->w0, grid->dw, b->n, p->small_d + p->off_n,
                                           b->tau_gas, b->tau, b->omega, b->g);
     grt_profile_end(s, slot);
     GRT_TRY(grt_dev_check(krc, "clear-sky optics kernel"));
+    GRT_TRY(band_spectral_fluxes(p, b, bi, C, bi == 0 ? 3 : 4));
+    return GRTCODE_SUCCESS;
+}
+
+/* the spectral solver of one band on the materialised tau, omega, g, under profile tag `tag` */
+static int band_spectral_fluxes(GrtPipeline_t *p, GrtBand *b, int bi, int C, int tag)
+{
+    SpectralGrid_t const *grid = &b->gas->grid;
+    int const V = p->num_levels, L = V - 1;
+    uint64_t const per_opt = (uint64_t)L*b->n, per_flux = (uint64_t)V*b->n;
+    void *s = grt_dev_stream(p->device);
+    int slot, krc;
     if (bi == 0)
     {
         GrtLwArgs a;
@@ -451,7 +527,7 @@ static int band_spectral_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C)
         a.emis = p->emis_d; a.emis_stride = 0;
         a.flux_up = b->flux_up; a.flux_down = b->flux_down; a.flux_stride = per_flux;
         a.user_level = p->user_level;
-        slot = grt_profile_begin(s, 3);
+        slot = grt_profile_begin(s, tag);
         krc = grt_launch_lw(s, &a);
         grt_profile_end(s, slot);
         GRT_TRY(grt_dev_check(krc, "longwave kernel"));
@@ -467,7 +543,7 @@ static int band_spectral_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C)
         a.tsi = p->small_d + p->off_tsi; a.solar = p->solar_d;
         a.flux_up = b->flux_up; a.flux_down = b->flux_down; a.flux_stride = per_flux;
         a.user_level = p->user_level;
-        slot = grt_profile_begin(s, 4);
+        slot = grt_profile_begin(s, tag);
         krc = grt_launch_sw(s, &a);
         grt_profile_end(s, slot);
         GRT_TRY(grt_dev_check(krc, "shortwave kernel"));
@@ -481,7 +557,7 @@ EXTERN int grt_pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, fp_t *fl
     GRT_REQUIRE_PTR(cols);
     GRT_REQUIRE_PTR(fluxes_dev);
     GRT_TRY(stage_columns(p, cols));
-    int const V = p->num_levels, C = cols->ncol;
+    int const C = cols->ncol;
     void *s = grt_dev_stream(p->device);
     for (int bi = 0; bi < 2; ++bi)
     {
@@ -498,40 +574,8 @@ EXTERN int grt_pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, fp_t *fl
         {
             /* Rayleigh, add_optics({gas, rayleigh}), solver and -integrated output (driver.c:268, 382-424, 302-326)
                in one launch, then the fixed-order sum of its per-block partial sums */
-            int slot, krc;
-            if (bi == 0)
-            {
-                GrtLwArgs a;
-                fused_lw_args(p, b, C, defer, &continua, &a);
-                a.partials = b->partials;
-                slot = grt_profile_begin(s, 3);
-                krc = grt_launch_lw(s, &a);
-                grt_profile_end(s, slot);
-                GRT_TRY(grt_dev_check(krc, "longwave kernel (fused)"));
-            }
-            else
-            {
-                GrtSwArgs a;
-                fused_sw_args(p, b, C, defer, &continua, &a);
-                a.partials = b->partials;
-                {
-                    /* (read at every step, so that a test can compare the two forms in one process) */
-                    char const *env = getenv("GRT_SW_TWO_SWEEPS");
-                    a.one_sweep = !(env != NULL && env[0] == '1');
-                }
-                if (!(a.one_sweep && (p->user_level < 0 || p->user_level == 0 || p->user_level == V - 1)))
-                {
-                    GRT_TRY(park_block(p, b));
-                }
-                a.park = b->park;
-                slot = grt_profile_begin(s, 4);
-                krc = grt_launch_sw(s, &a);
-                grt_profile_end(s, slot);
-                GRT_TRY(grt_dev_check(krc, "shortwave kernel (fused)"));
-            }
-            GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, b->partials, C*6, b->nblocks, fluxes_dev,
-                                                             GRT_FLUXES_PER_BAND, GRT_FLUXES_PER_COLUMN,
-                                                             bi*GRT_FLUXES_PER_BAND), "flux reduction kernel"));
+            GRT_TRY(band_fused_solver(p, b, bi, C, defer, &continua, NULL, fluxes_dev, GRT_FLUXES_PER_COLUMN,
+                                      bi*GRT_FLUXES_PER_BAND));
             continue;
         }
         GRT_TRY(band_spectral_solver(p, b, bi, C));
@@ -660,5 +704,272 @@ EXTERN int grt_pipeline_run_profiles(GrtPipeline_t *p, GrtColumns_t const *cols,
     GRT_TRY(grt_dev_check(grt_launch_profile_finish(s, C, V, bands, p->user_level, GRT_GRAVITY, GRT_SPECIFIC_HEAT_AIR,
                                                     p->small_d + p->off_p, level_fluxes_dev, heating_dev, fluxes_dev),
                           "heating rate kernel"));
+    return GRTCODE_SUCCESS;
+}
+
+/* ---- all-sky fluxes (grt_pipeline_run_allsky) ---------------------------------------------------------------------- */
+
+/* first index in [0, n) whose value is >= target (n if none), last index whose value is <= target (-1 if none) */
+static int first_not_below(double const *w, int n, double target)
+{
+    int lo = 0, hi = n;
+    while (lo < hi)
+    {
+        int const mid = (lo + hi)/2;
+        if (w[mid] < target) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+static int last_not_above(double const *w, int n, double target)
+{
+    int lo = 0, hi = n;
+    while (lo < hi)
+    {
+        int const mid = (lo + hi)/2;
+        if (w[mid] <= target) lo = mid + 1; else hi = mid;
+    }
+    return lo - 1;
+}
+
+/* The band each point of w [n] ends up with when bands 0 .. nb - 1 of a parametrisation of `own` bands are written in
+   order, as optics_utils.c:118-169 writes them: [first >= lo, last <= hi), band 0 extended down, band own - 1 up. */
+static void cloud_band_map(double const *lo, double const *hi, int own, int nb, double const *w, int n, int *idx)
+{
+    for (int j = 0; j < n; ++j)
+    {
+        idx[j] = -1;
+    }
+    for (int b = 0; b < nb; ++b)
+    {
+        int const from = first_not_below(w, n, lo[b]);
+        int const upto = last_not_above(w, n, hi[b]);
+        if (b == 0)
+        {
+            for (int j = 0; j < from; ++j) idx[j] = 0;
+        }
+        for (int j = from; j < upto; ++j) idx[j] = b;
+        if (b == own - 1)
+        {
+            for (int j = upto < 0 ? 0 : upto; j < n; ++j) idx[j] = b;
+        }
+    }
+}
+
+/* the band's per-point cloud bands for these band limits: built on the host when the limits differ from the last call's */
+static int band_cloud_map(GrtPipeline_t *p, GrtBand *b, GrtClouds_t const *cl)
+{
+    int const B = cl->num_liquid_bands, NI = cl->num_ice_bands;
+    size_t const nkey = 2 + 2*(size_t)B + 2*(size_t)NI;
+    double *key = malloc(sizeof(double)*nkey);
+    if (key == NULL)
+    {
+        GRT_FAIL(GRTCODE_NULL_ERR, "out of host memory for %zu band limits.", nkey);
+    }
+    key[0] = B; key[1] = NI;
+    memcpy(key + 2, cl->liquid_band_lo, sizeof(double)*B);
+    memcpy(key + 2 + B, cl->liquid_band_hi, sizeof(double)*B);
+    memcpy(key + 2 + 2*B, cl->ice_band_lo, sizeof(double)*NI);
+    memcpy(key + 2 + 2*B + NI, cl->ice_band_hi, sizeof(double)*NI);
+    if (b->cloud_map != NULL && b->cloud_key_n == nkey && memcmp(b->cloud_key, key, sizeof(double)*nkey) == 0)
+    {
+        free(key);
+        return GRTCODE_SUCCESS;
+    }
+    int const n = (int)b->n;
+    double *w = malloc(sizeof(double)*(size_t)n);
+    int *idx = malloc(sizeof(int)*2*(size_t)n);
+    int rc = (w == NULL || idx == NULL) ? GRTCODE_NULL_ERR : GRTCODE_SUCCESS;
+    if (rc == GRTCODE_SUCCESS)
+    {
+        /* what driver.c:476-488 passes to cloud_optics as the grid's "wavenumbers": band limits, not centres */
+        SpectralGrid_t const *grid = &b->gas->grid;
+        for (uint64_t j = 1; j < b->n; ++j)
+        {
+            w[j] = 0.5*((grid->w0 + (j - 1)*grid->dw) + (grid->w0 + j*grid->dw));
+        }
+        w[0] = grid->w0 - grid->dw;
+        if (w[0] < 0.)
+        {
+            w[0] = 0;
+        }
+        cloud_band_map(cl->liquid_band_lo, cl->liquid_band_hi, B, B, w, n, idx);
+        cloud_band_map(cl->ice_band_lo, cl->ice_band_hi, NI, B, w, n, idx + n);
+        void *s = grt_dev_stream(p->device);
+        if (b->cloud_map == NULL)
+        {
+            void *m = NULL;
+            rc = grt_dev_alloc(p->device, &m, sizeof(int)*2*(size_t)n);
+            b->cloud_map = m;
+        }
+        /* (the last batch's kernels may still read the old map; then idx is freed: wait both times) */
+        if (rc == GRTCODE_SUCCESS) rc = grt_dev_sync(p->device, s);
+        if (rc == GRTCODE_SUCCESS) rc = grt_dev_upload(p->device, b->cloud_map, idx, sizeof(int)*2*(size_t)n, s);
+        if (rc == GRTCODE_SUCCESS) rc = grt_dev_sync(p->device, s);
+    }
+    free(w);
+    free(idx);
+    if (rc != GRTCODE_SUCCESS)
+    {
+        free(key);
+        GRT_TRY(rc);
+    }
+    free(b->cloud_key);
+    b->cloud_key = key;
+    b->cloud_key_n = nkey;
+    return GRTCODE_SUCCESS;
+}
+
+/* the band tables of the batch to the device: [C][L] thickness, then the four [C][3][B][L] sets */
+static int stage_clouds(GrtPipeline_t *p, GrtClouds_t const *cl, int C)
+{
+    size_t const L = (size_t)p->num_levels - 1, B = (size_t)cl->num_liquid_bands;
+    size_t const set = (size_t)C*3*B*L, need = (size_t)C*L + 4*set;
+    GRT_TRY(grt_dev_event_wait(p->device, p->cloud_uploaded));
+    if (need > p->cloud_doubles)
+    {
+        /* (sized for max_columns at this band count: a later batch of the same bands reuses it) */
+        size_t const want = (size_t)p->max_cols*L*(1 + 12*B);
+        void *s = grt_dev_stream(p->device);
+        GRT_TRY(grt_dev_sync(p->device, s));
+        grt_dev_free(p->device, p->cloud_d);
+        grt_host_free_pinned(p->cloud_h);
+        p->cloud_d = NULL;
+        p->cloud_h = NULL;
+        p->cloud_doubles = 0;
+        GRT_TRY(grt_host_alloc_pinned((void **)&p->cloud_h, sizeof(double)*want));
+        GRT_TRY(grt_dev_alloc(p->device, (void **)&p->cloud_d, sizeof(double)*want));
+        p->cloud_doubles = want;
+    }
+    double *h = p->cloud_h;
+    memcpy(h, cl->thickness, sizeof(double)*(size_t)C*L);
+    h += (size_t)C*L;
+    fp_t const *sets[4] = {cl->lw_liquid, cl->lw_ice, cl->sw_liquid, cl->sw_ice};
+    for (int k = 0; k < 4; ++k)
+    {
+        if (sets[k] != NULL)
+        {
+            memcpy(h + k*set, sets[k], sizeof(double)*set);
+        }
+        else
+        {
+            memset(h + k*set, 0, sizeof(double)*set);
+        }
+    }
+    void *s = grt_dev_stream(p->device);
+    GRT_TRY(grt_dev_upload(p->device, p->cloud_d, p->cloud_h, sizeof(double)*need, s));
+    GRT_TRY(grt_dev_event_record(p->device, &p->cloud_uploaded, s));
+    return GRTCODE_SUCCESS;
+}
+
+/* Materialised form: the cloud objects spread onto the grid, Rayleigh, add_optics of the four objects per column
+   (driver.c:507-530), then the spectral solver -- tau, omega, g and the fluxes of the band are the all-sky pass's */
+static int band_allsky_spectral(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtCloudArgs const *ca)
+{
+    SpectralGrid_t const *grid = &b->gas->grid;
+    int const L = p->num_levels - 1;
+    uint64_t const per = (uint64_t)L*b->n, all = per*(uint64_t)p->max_cols;
+    void *s = grt_dev_stream(p->device);
+    if (b->cloud_block == NULL)
+    {
+        void *blk = NULL;
+        GRT_TRY(grt_dev_alloc(p->device, &blk, sizeof(double)*(6*all + 4*per)));
+        b->cloud_block = blk;
+        GRT_TRY(grt_dev_zero(p->device, b->cloud_block + 6*all + 3*per, sizeof(double)*per, s));
+    }
+    double *cloud[6];
+    for (int k = 0; k < 6; ++k)
+    {
+        cloud[k] = b->cloud_block + k*all;
+    }
+    double *ray = b->cloud_block + 6*all, *zero = ray + 3*per;
+    GRT_TRY(grt_dev_check(grt_launch_spread_clouds(s, L, C, b->n, ca, cloud[0], cloud[1], cloud[2], cloud[3], cloud[4],
+                                                   cloud[5]), "cloud spreading kernel"));
+    for (int c = 0; c < C; ++c)
+    {
+        /* Rayleigh of this column (rayleigh.c:29-68: its number densities travel as a kernel argument) */
+        GRT_TRY(grt_dev_check(grt_launch_rayleigh(s, L, grid->w0, grid->dw, b->n, p->small_h + p->off_n + (size_t)c*L,
+                                                  ray, ray + per, ray + 2*per), "Rayleigh kernel"));
+        GrtOpticsPtrs in;
+        memset(&in, 0, sizeof(in));
+        uint64_t const o = (uint64_t)c*per;
+        in.tau[0] = b->tau_gas + o; in.omega[0] = zero; in.g[0] = zero;
+        in.tau[1] = ray; in.omega[1] = ray + per; in.g[1] = ray + 2*per;
+        in.tau[2] = cloud[0] + o; in.omega[2] = cloud[1] + o; in.g[2] = cloud[2] + o;
+        in.tau[3] = cloud[3] + o; in.omega[3] = cloud[4] + o; in.g[3] = cloud[5] + o;
+        GRT_TRY(grt_dev_check(grt_launch_add_optics(s, per, 4, &in, b->tau + o, b->omega + o, b->g + o),
+                              "add_optics kernel (all-sky)"));
+    }
+    GRT_TRY(band_spectral_fluxes(p, b, bi, C, bi == 0 ? 8 : 9));
+    return GRTCODE_SUCCESS;
+}
+
+EXTERN int grt_pipeline_run_allsky(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl, fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    GRT_REQUIRE_PTR(fluxes_dev);
+    if (cl == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "no cloud inputs (GrtClouds_t is NULL).%s", "");
+    }
+    if (cl->num_liquid_bands < 1 || cl->num_ice_bands < cl->num_liquid_bands)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d liquid and %d ice bands: at least one liquid band, and no fewer ice bands.",
+                 cl->num_liquid_bands, cl->num_ice_bands);
+    }
+    if (cl->liquid_band_lo == NULL || cl->liquid_band_hi == NULL || cl->ice_band_lo == NULL || cl->ice_band_hi == NULL ||
+        cl->thickness == NULL || (p->band[0].gas != NULL && (cl->lw_liquid == NULL || cl->lw_ice == NULL)) ||
+        (p->band[1].gas != NULL && (cl->sw_liquid == NULL || cl->sw_ice == NULL)))
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "a NULL array in the cloud inputs.%s", "");
+    }
+    if (cols->ncol < 1 || cols->ncol > p->max_cols)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d columns asked for, this pipeline was created for 1 to %d.", cols->ncol, p->max_cols);
+    }
+    GRT_TRY(stage_columns(p, cols));
+    int const L = p->num_levels - 1, C = cols->ncol;
+    size_t const set = (size_t)C*3*(size_t)cl->num_liquid_bands*(size_t)L;
+    GRT_TRY(stage_clouds(p, cl, C));
+    void *s = grt_dev_stream(p->device);
+    for (int bi = 0; bi < 2; ++bi)
+    {
+        GrtBand *b = &p->band[bi];
+        if (b->gas == NULL)
+        {
+            continue;
+        }
+        GRT_TRY(band_cloud_map(p, b, cl));
+        GrtCloudArgs ca;
+        ca.num_bands = cl->num_liquid_bands;
+        ca.band_liquid = b->cloud_map;
+        ca.band_ice = b->cloud_map + b->n;
+        ca.thickness = p->cloud_d;
+        ca.liquid = p->cloud_d + (size_t)C*L + (size_t)(2*bi)*set;
+        ca.ice = ca.liquid + set;
+        SpectralGrid_t const *grid = &b->gas->grid;
+        GrtContinua continua;
+        int defer;
+        GRT_TRY(band_gas_optics(p, b, bi, cols, &continua, &defer));
+        if (!p->keep_spectra)
+        {
+            /* the clear-sky pass exactly as grt_pipeline_run takes it, then the all-sky instance of the same solver */
+            GRT_TRY(band_fused_solver(p, b, bi, C, defer, &continua, NULL, fluxes_dev, GRT_ALLSKY_FLUXES_PER_COLUMN,
+                                      bi*GRT_FLUXES_PER_BAND));
+            GRT_TRY(band_fused_solver(p, b, bi, C, defer, &continua, &ca, fluxes_dev, GRT_ALLSKY_FLUXES_PER_COLUMN,
+                                      GRT_FLUXES_PER_COLUMN + bi*GRT_FLUXES_PER_BAND));
+            continue;
+        }
+        GRT_TRY(band_spectral_solver(p, b, bi, C));
+        GRT_TRY(grt_dev_check(grt_launch_integrate_rows(s, (double const *const *)b->rows_d, C*6, b->n, grid->dw, fluxes_dev,
+                                                        GRT_FLUXES_PER_BAND, GRT_ALLSKY_FLUXES_PER_COLUMN,
+                                                        bi*GRT_FLUXES_PER_BAND), "spectral integration kernel"));
+        GRT_TRY(band_allsky_spectral(p, b, bi, C, &ca));
+        GRT_TRY(grt_dev_check(grt_launch_integrate_rows(s, (double const *const *)b->rows_d, C*6, b->n, grid->dw, fluxes_dev,
+                                                        GRT_FLUXES_PER_BAND, GRT_ALLSKY_FLUXES_PER_COLUMN,
+                                                        GRT_FLUXES_PER_COLUMN + bi*GRT_FLUXES_PER_BAND),
+                              "spectral integration kernel (all-sky)"));
+    }
     return GRTCODE_SUCCESS;
 }

@@ -29,4 +29,14 @@ int grt_clouds_sample_subcolumn(int num_layers, const double *cloud_fraction, co
                                 const double *overlap, double *ql, double *qi);
 double grt_clouds_beta(int inverse, int p, int q, double x);
 
+/* Band-level optics for the batched pipeline's all-sky pass (grt_pipeline_run_allsky, grt_ext.h), which takes the optics
+   per band and maps them onto its grids itself.  grt_clouds_band_optics: what cloud_optics computes before it spreads
+   the bands onto a grid -- the same rand() calls in the same order -- as liquid[3][B][L] and ice[3][B][L] (extinction m-1,
+   single-scattering albedo, asymmetry; band b of the ice is the ice parametrisation's band b), B the liquid
+   parametrisation's band count.  grt_clouds_bands: the loaded band limits in cm-1 (ice != 0: the ice's), as the library
+   uses them (rounded to single precision); lo / hi may be NULL to ask for the count. */
+int grt_clouds_band_optics(int num_layers, const double *cf, const double *lwc, const double *iwc, const double *overlap,
+                           const double liquid_radius, const double *layer_temperature, double *liquid, double *ice);
+int grt_clouds_bands(int ice, int *num_bands, double *lo, double *hi);
+
 #endif

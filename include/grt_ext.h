@@ -41,7 +41,7 @@ EXTERN int grt_hitran_index_stats(long long stats[3]);
 /* ---- struct sizes for FFI callers (ctypes; cf. fortran-bindings/malloc_structs.c:40-66) */
 enum grt_struct_kind
 {
-    GRT_SPECTRAL_GRID = 0, GRT_OPTICS, GRT_GAS_OPTICS, GRT_SOLAR_FLUX, GRT_LONGWAVE, GRT_SHORTWAVE
+    GRT_SPECTRAL_GRID = 0, GRT_OPTICS, GRT_GAS_OPTICS, GRT_SOLAR_FLUX, GRT_LONGWAVE, GRT_SHORTWAVE, GRT_CLOUDS
 };
 EXTERN size_t grt_sizeof(int kind);
 
@@ -176,6 +176,42 @@ EXTERN int grt_pipeline_views(GrtPipeline_t *pipeline, int band, fp_t **tau_gas,
 EXTERN int grt_pipeline_run_profiles(GrtPipeline_t *pipeline, GrtColumns_t const *columns,
                                      fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev);
 
+/* ---- all-sky (cloudy, aerosol-free) fluxes ------------------------------------------------------------------------
+ * driver.c:474-597 with one subcolumn: the clear-sky pass of grt_pipeline_run, then the same solvers on
+ * add_optics({gas, Rayleigh, liquid cloud, ice cloud}).  The cloud optics come per band, as the clouds library
+ * computes them before it spreads them onto a grid (clouds_lib.h: grt_clouds_band_optics, grt_clouds_bands); the
+ * pipeline never calls that library.  Separate longwave and shortwave sets: the driver draws the subcolumns once per pass.
+ * A grid point j takes the bands of the value driver.c:476-488 passes for it -- max(w0 - dw, 0) for j = 0, the midpoint
+ * of the centres j - 1 and j otherwise -- under optics_utils.c:118-169's rules: bands written in ascending order, later
+ * ones overwriting earlier ones; the first point at or above a band's lower limit up to, not including, the last point
+ * at or below its upper limit; band 0 extended down; a parametrisation's own last band extended up (the ice's only when
+ * num_ice_bands == num_liquid_bands); ice band b mapped with the ice limits for b < num_liquid_bands only.  A point no
+ * band covers has no cloud (the reference leaves whatever the arrays held there).  Layer optical depth =
+ * extinction x thickness.  All arrays are HOST memory, read during the call. */
+typedef struct GrtClouds
+{
+    int num_liquid_bands;               /* B >= 1 */
+    int num_ice_bands;                  /* >= B */
+    fp_t const *liquid_band_lo, *liquid_band_hi;   /* [B] cm-1 */
+    fp_t const *ice_band_lo, *ice_band_hi;         /* [num_ice_bands] cm-1 */
+    fp_t const *thickness;              /* [ncol][L] m */
+    fp_t const *lw_liquid, *lw_ice;     /* [ncol][3][B][L]: extinction m-1, single-scattering albedo, asymmetry */
+    fp_t const *sw_liquid, *sw_ice;     /* [ncol][3][B][L] */
+} GrtClouds_t;
+
+#define GRT_ALLSKY_FLUXES_PER_COLUMN (2*GRT_FLUXES_PER_COLUMN)   /* clear-sky twelve, then all-sky twelve */
+
+/* fluxes_dev [ncol][GRT_ALLSKY_FLUXES_PER_COLUMN] (DEVICE memory): values 0-11 are exactly what grt_pipeline_run writes,
+   values 12-23 the all-sky set in the same order.  Same solvers, surface inputs, user level and shortwave sweep rule as
+   grt_pipeline_run.  The production form (keep_spectra = 0) forms the cloud terms in the solver kernels from the band
+   tables (profile tags 8 and 9); the materialised form spreads them into [ncol][L][n] arrays, adds the four objects with
+   add_optics' kernel and runs the spectral solvers: afterwards grt_pipeline_views shows the all-sky pass's tau, omega, g
+   and fluxes.  GRTCODE_VALUE_ERR, with nothing launched, for: clouds NULL, num_liquid_bands < 1, num_ice_bands <
+   num_liquid_bands, a NULL array (the band limits, thickness and the two sets of each band the pipeline has), ncol outside
+   1 .. max_columns.  Asynchronous on the pipeline's lane like grt_pipeline_run. */
+EXTERN int grt_pipeline_run_allsky(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtClouds_t const *clouds,
+                                   fp_t *fluxes_dev);
+
 /* ---- columns across the GPUs of one node ------------------------------------
  * One process per GPU; contiguous ceil-sized column blocks; one gather of the [columns][GRT_FLUXES_PER_COLUMN]
  * flux blocks to rank 0.  The reference fans out processes with -x/-X column ranges and merges per-shard files
@@ -211,7 +247,8 @@ EXTERN int grt_multi_max(GrtMulti_t *multi, double *value);    /* barrier + maxi
  * Tags: 1 = line-by-line kernel on a grid of <= 10 000 points (longwave band at 1 cm-1),
  * 2 = line-by-line kernel on a larger grid (shortwave band), 3 = LW solver, 4 = SW solver,
  * 5 = clear-sky optics combine, 6 / 7 = far-field gather kernel of the two-pass line kernel (longwave /
- * shortwave band; tags 1 / 2 then cover its first pass).  Read after grt_pipeline_sync(). */
+ * shortwave band; tags 1 / 2 then cover its first pass), 8 / 9 = LW / SW solver of grt_pipeline_run_allsky's all-sky
+ * pass (its clear-sky pass counts under 3 / 4).  Read after grt_pipeline_sync(). */
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
 
