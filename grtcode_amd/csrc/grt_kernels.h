@@ -258,8 +258,8 @@ typedef struct GrtLwArgs
     double *flux_up, *flux_down;    /* [ncol][V][nw]; NULL in the fused form: nothing spectral is stored */
     uint64_t flux_stride;
     int user_level;                 /* -1: none */
-    /* Fused clear-sky form (driver.c:360-424 + 285-356 with -integrated in one kernel): tau_gas != NULL makes the
-       kernel form Rayleigh (rayleigh.c:38-39) and the two-object combination (optics.c:138-145) per layer in
+    /* Fused clear-sky form (driver.c:360-424 + 285-356 with -integrated in one kernel, GRT_SOLVER_FUSED): the
+       kernel forms Rayleigh (rayleigh.c:38-39) and the two-object combination (optics.c:138-145) per layer in
        registers from tau_gas [ncol][L][nw] (column stride optics_stride) and the air columns n_layer [ncol][L],
        and leave only the trapezoid partial sums of the six output rows (up TOA, up surface, up user, down TOA,
        down surface, down user) at partials[(c*6 + k)*nblocks + block]; grt_launch_reduce_partials finishes. */
@@ -267,12 +267,11 @@ typedef struct GrtLwArgs
     double *partials;
     int add_continua;               /* fused form: tau_gas was written without the tables' part -- add it (continua) */
     GrtContinua continua;
-    /* spectral form, optional: scratch [ncol][6 L][nw].  When set, the four streams' extinctions and the two effective
+    /* spectral form, GRT_SOLVER_LAYERS: scratch [ncol][6 L][nw].  The four streams' extinctions and the two effective
        Planck terms of every layer are worked out first by one thread per (layer, wavenumber), and the two sweeps read
        them (the same doubles through the same expressions: identical fluxes) -- see GrtSwArgs.layer_props */
     double *layer_terms;
 } GrtLwArgs;
-int grt_launch_lw(void *stream, GrtLwArgs const *a);
 unsigned grt_solver_blocks(uint64_t nw);     /* workgroups along the spectrum of one solver launch (size of `partials`) */
 int grt_launch_reduce_partials(void *stream, double const *partials, int nrows, unsigned nblocks,
                                double *out, int group, int out_stride, int out_offset);
@@ -303,31 +302,33 @@ typedef struct GrtSwArgs
     /* fused form, no flux asked for between top and surface (user_level -1, 0 or num_levels - 1): ONE sweep from the top,
        nothing parked (k_shortwave.hip); 0: the two sweeps of the reference's order (GRT_SW_TWO_SWEEPS=1 in the environment) */
     int one_sweep;
-    /* spectral form (flux_up/flux_down set), optional: scratch [ncol][5 L][nw].  When set, the five properties of every
+    /* spectral form, GRT_SOLVER_LAYERS: scratch [ncol][5 L][nw].  The five properties of every
        layer are worked out first by one thread per (layer, wavenumber) -- a column of 50 000 wavenumbers is then 3 million
        independent delta-Eddington pairs instead of 50 000 chains of 120 -- and the two sweeps read them (the same
        doubles through the same expressions: identical fluxes) */
     double *layer_props;
 } GrtSwArgs;
-int grt_launch_sw(void *stream, GrtSwArgs const *a);
+/* whether the fused form takes its one sweep (the rule above; sw_kernel keeps its own copy) */
+static inline int grt_sw_one_sweep(GrtSwArgs const *a)
+{
+    return a->one_sweep && (a->user_level < 0 || a->user_level == 0 || a->user_level == a->num_levels - 1);
+}
 
-/* Profile form of the fused solvers (grt_pipeline_run_profiles): the arguments of the fused form (tau_gas set), but every
+/* Profile form of the fused solvers (GRT_SOLVER_PROFILE, grt_pipeline_run_profiles): the fused form's arguments, but every
    level's upward and downward flux leaves as trapezoid partial sums, 2 V rows per column at
    partials[(c*2 V + r)*nblocks + block], r = level (up) and V + level (down), levels top first; reduced with
    grt_launch_reduce_partials(nrows = ncol*2 V).  The shortwave form always takes the two sweeps and needs `park`
    (one_sweep and user_level are not read); each wave sums a level as the sweep produces it, in dynamic LDS of
    2 V x 2 doubles per workgroup.  Rows 0, L and user_level are, bit for bit, the six-row form's (the shortwave's: its
    two-sweep form's). */
-int grt_launch_lw_profile(void *stream, GrtLwArgs const *a);
-int grt_launch_sw_profile(void *stream, GrtSwArgs const *a);
 /* levels [ncol][4][V] (up, down of band 0, then of band 1) -> heating [ncol][2][V-1] K day-1 (NULL: not formed) from the
    level pressures pressure [ncol][V] mb, and fluxes [ncol][12] (NULL: not formed) in grt_pipeline_run's layout; the rows of
    a band whose bit in `bands` is clear are zeroed, level fluxes included. */
 int grt_launch_profile_finish(void *stream, int ncol, int num_levels, int bands, int user_level, double gravity,
                               double cp, double const *pressure, double *levels, double *heating, double *fluxes);
 
-/* All-sky form of the fused solvers (grt_pipeline_run_allsky): the fused form's arguments (tau_gas set, six-row partial
-   sums), and per layer the liquid and ice cloud objects formed in registers from the band tables below and combined with
+/* All-sky form of the fused solvers (GRT_SOLVER_ALLSKY, grt_pipeline_run_allsky): the fused form's arguments (six-row
+   partial sums), and per layer the liquid and ice cloud objects formed in registers from the band tables below and combined with
    gas and Rayleigh by allsky_combine (optics_dev.h).  band_liquid / band_ice: DEVICE [nw] band of each grid point, -1 for
    none; thickness [ncol][L] m; liquid / ice [ncol][3][num_bands][L] (extinction m-1, albedo, asymmetry). */
 typedef struct GrtCloudArgs
@@ -337,8 +338,19 @@ typedef struct GrtCloudArgs
     double const *thickness;
     double const *liquid, *ice;
 } GrtCloudArgs;
-int grt_launch_lw_allsky(void *stream, GrtLwArgs const *a, GrtCloudArgs const *c);
-int grt_launch_sw_allsky(void *stream, GrtSwArgs const *a, GrtCloudArgs const *c);
+
+/* The kernel instances of each solver.  grt_launch_lw / grt_launch_sw launch the form they are given, after checking the
+   fields that form reads (hipErrorInvalidValue otherwise); `clouds` is read by GRT_SOLVER_ALLSKY only. */
+typedef enum GrtSolverForm
+{
+    GRT_SOLVER_CHAINS,      /* spectral: one thread per wavenumber and column through all the layers */
+    GRT_SOLVER_LAYERS,      /* spectral, the same fluxes: the layers' terms first (layer_terms / layer_props) */
+    GRT_SOLVER_FUSED,       /* fused clear-sky, six output rows */
+    GRT_SOLVER_PROFILE,     /* fused clear-sky, every level's up and down flux */
+    GRT_SOLVER_ALLSKY       /* fused all-sky, six output rows */
+} GrtSolverForm;
+int grt_launch_lw(void *stream, GrtSolverForm form, GrtLwArgs const *a, GrtCloudArgs const *clouds);
+int grt_launch_sw(void *stream, GrtSolverForm form, GrtSwArgs const *a, GrtCloudArgs const *clouds);
 /* Materialised form: the cloud objects of the same tables spread onto the grid, [ncol][L][nw] each (tau = extinction x
    thickness; zero where a point has no band). */
 int grt_launch_spread_clouds(void *stream, int num_layers, int ncol, uint64_t nw, GrtCloudArgs const *c,

@@ -394,61 +394,46 @@ extern "C" unsigned grt_solver_blocks(uint64_t nw)
     return (unsigned)((nw + kBlock - 1)/kBlock);
 }
 
-extern "C" int grt_launch_lw(void *stream, GrtLwArgs const *a)
+extern "C" int grt_launch_lw(void *stream, GrtSolverForm form, GrtLwArgs const *a, GrtCloudArgs const *c)
 {
-    bool const fused = a->tau_gas != nullptr;
-    if (a->ncol < 1 || a->nw < 2 || (fused ? (a->partials == nullptr || a->n_layer == nullptr)
-                                           : (a->flux_up == nullptr || a->flux_down == nullptr)))
+    bool const fused = form == GRT_SOLVER_FUSED || form == GRT_SOLVER_PROFILE || form == GRT_SOLVER_ALLSKY;
+    size_t const lds = form == GRT_SOLVER_PROFILE ? sizeof(double)*2*(size_t)a->num_levels*(kBlock/64) : 0;
+    uint64_t const cells = (uint64_t)(a->num_levels - 1)*a->nw;
+    if (a->ncol < 1 || a->nw < 2 ||
+        (fused ? (a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr)
+               : (a->flux_up == nullptr || a->flux_down == nullptr)) ||
+        (form == GRT_SOLVER_LAYERS && (a->layer_terms == nullptr || cells > 0xffffffffull*kTermsBlock)) ||
+        (form == GRT_SOLVER_PROFILE && (a->num_levels < 2 || lds > 65536)) ||
+        (form == GRT_SOLVER_ALLSKY && (c == nullptr || c->num_bands < 1 || c->band_liquid == nullptr ||
+                                       c->band_ice == nullptr || c->thickness == nullptr || c->liquid == nullptr ||
+                                       c->ice == nullptr)))
     {
         return (int)hipErrorInvalidValue;
     }
-    if (!fused && a->layer_terms != nullptr)
-    {
-        uint64_t const cells = (uint64_t)(a->num_levels - 1)*a->nw;
-        if (cells > 0xffffffffull*kTermsBlock)
-        {
-            return (int)hipErrorInvalidValue;
-        }
-        hipLaunchKernelGGL(lw_terms_kernel, dim3((unsigned)((cells + kTermsBlock - 1)/kTermsBlock), a->ncol, 1),
-                           dim3(kTermsBlock), 0, (hipStream_t)stream, *a);
-        hipLaunchKernelGGL(lw_sweeps_kernel, dim3((unsigned)((a->nw + kSweepBlock - 1)/kSweepBlock), a->ncol, 1),
-                           dim3(kSweepBlock), 0, (hipStream_t)stream, *a);
-        return (int)hipGetLastError();
-    }
+    hipStream_t const s = (hipStream_t)stream;
     dim3 const grid(grt_solver_blocks(a->nw), a->ncol, 1);
-    if (fused)
+    switch (form)
     {
-        hipLaunchKernelGGL((lw_kernel<true, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, *a);
-    }
-    else
-    {
-        hipLaunchKernelGGL((lw_kernel<false, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, *a);
-    }
-    return (int)hipGetLastError();
-}
-
-extern "C" int grt_launch_lw_profile(void *stream, GrtLwArgs const *a)
-{
-    size_t const lds = sizeof(double)*2*(size_t)a->num_levels*(kBlock/64);
-    if (a->ncol < 1 || a->nw < 2 || a->num_levels < 2 || a->tau_gas == nullptr || a->n_layer == nullptr ||
-        a->partials == nullptr || lds > 65536)
-    {
+    case GRT_SOLVER_LAYERS:
+        hipLaunchKernelGGL(lw_terms_kernel, dim3((unsigned)((cells + kTermsBlock - 1)/kTermsBlock), a->ncol, 1),
+                           dim3(kTermsBlock), 0, s, *a);
+        hipLaunchKernelGGL(lw_sweeps_kernel, dim3((unsigned)((a->nw + kSweepBlock - 1)/kSweepBlock), a->ncol, 1),
+                           dim3(kSweepBlock), 0, s, *a);
+        break;
+    case GRT_SOLVER_FUSED:
+        hipLaunchKernelGGL((lw_kernel<true, false>), grid, dim3(kBlock), 0, s, *a);
+        break;
+    case GRT_SOLVER_CHAINS:
+        hipLaunchKernelGGL((lw_kernel<false, false>), grid, dim3(kBlock), 0, s, *a);
+        break;
+    case GRT_SOLVER_PROFILE:
+        hipLaunchKernelGGL((lw_kernel<true, true>), grid, dim3(kBlock), lds, s, *a);
+        break;
+    case GRT_SOLVER_ALLSKY:
+        hipLaunchKernelGGL((lw_kernel<true, false, true, GrtCloudArgs>), grid, dim3(kBlock), 0, s, *a, *c);
+        break;
+    default:
         return (int)hipErrorInvalidValue;
     }
-    hipLaunchKernelGGL((lw_kernel<true, true>), dim3(grt_solver_blocks(a->nw), a->ncol, 1), dim3(kBlock), lds,
-                       (hipStream_t)stream, *a);
-    return (int)hipGetLastError();
-}
-
-extern "C" int grt_launch_lw_allsky(void *stream, GrtLwArgs const *a, GrtCloudArgs const *c)
-{
-    if (a->ncol < 1 || a->nw < 2 || a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr ||
-        c->num_bands < 1 || c->band_liquid == nullptr || c->band_ice == nullptr || c->thickness == nullptr ||
-        c->liquid == nullptr || c->ice == nullptr)
-    {
-        return (int)hipErrorInvalidValue;
-    }
-    hipLaunchKernelGGL((lw_kernel<true, false, true, GrtCloudArgs>), dim3(grt_solver_blocks(a->nw), a->ncol, 1), dim3(kBlock), 0, (hipStream_t)stream,
-                       *a, *c);
     return (int)hipGetLastError();
 }

@@ -623,63 +623,48 @@ __global__ __launch_bounds__(kSweepBlock) void sw_sweeps_kernel(GrtSwArgs a)
 
 } // namespace
 
-extern "C" int grt_launch_sw(void *stream, GrtSwArgs const *a)
+extern "C" int grt_launch_sw(void *stream, GrtSolverForm form, GrtSwArgs const *a, GrtCloudArgs const *c)
 {
-    bool const fused = a->tau_gas != nullptr;
-    bool const one_sweep = fused && a->one_sweep && (a->user_level < 0 || a->user_level == 0 || a->user_level == a->num_levels - 1);
-    if (a->ncol < 1 || a->nw < 2 || (fused ? (a->partials == nullptr || (a->park == nullptr && !one_sweep) || a->n_layer == nullptr)
-                                           : (a->flux_up == nullptr || a->flux_down == nullptr)))
+    bool const fused = form == GRT_SOLVER_FUSED || form == GRT_SOLVER_PROFILE || form == GRT_SOLVER_ALLSKY;
+    bool const park = form == GRT_SOLVER_PROFILE || (fused && !grt_sw_one_sweep(a));
+    size_t const lds = form == GRT_SOLVER_PROFILE ? sizeof(double)*2*(size_t)a->num_levels*(kBlock/64) : 0;
+    uint64_t const cells = (uint64_t)(a->num_levels - 1)*a->nw;
+    if (a->ncol < 1 || a->nw < 2 ||
+        (fused ? (a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr || (park && a->park == nullptr))
+               : (a->flux_up == nullptr || a->flux_down == nullptr)) ||
+        (form == GRT_SOLVER_LAYERS && (a->layer_props == nullptr || cells > 0xffffffffull*kPropsBlock ||
+                                       a->omega == nullptr || a->g == nullptr)) ||
+        (form == GRT_SOLVER_PROFILE && (a->num_levels < 2 || lds > 65536)) ||
+        (form == GRT_SOLVER_ALLSKY && (c == nullptr || c->num_bands < 1 || c->band_liquid == nullptr ||
+                                       c->band_ice == nullptr || c->thickness == nullptr || c->liquid == nullptr ||
+                                       c->ice == nullptr)))
     {
         return (int)hipErrorInvalidValue;
     }
-    if (!fused && a->layer_props != nullptr)
-    {
-        uint64_t const cells = (uint64_t)(a->num_levels - 1)*a->nw;
-        if (cells > 0xffffffffull*kPropsBlock || a->omega == nullptr || a->g == nullptr)
-        {
-            return (int)hipErrorInvalidValue;
-        }
-        hipLaunchKernelGGL(sw_props_kernel, dim3((unsigned)((cells + kPropsBlock - 1)/kPropsBlock), a->ncol, 1),
-                           dim3(kPropsBlock), 0, (hipStream_t)stream, *a);
-        hipLaunchKernelGGL(sw_sweeps_kernel, dim3((unsigned)((a->nw + kSweepBlock - 1)/kSweepBlock), a->ncol, 1),
-                           dim3(kSweepBlock), 0, (hipStream_t)stream, *a);
-        return (int)hipGetLastError();
-    }
+    hipStream_t const s = (hipStream_t)stream;
     dim3 const grid((unsigned)((a->nw + kBlock - 1)/kBlock), a->ncol, 1);   // == grt_solver_blocks(nw): same kBlock
-    if (fused)
+    switch (form)
     {
-        hipLaunchKernelGGL((sw_kernel<true, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, *a);
-    }
-    else
-    {
-        hipLaunchKernelGGL((sw_kernel<false, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, *a);
-    }
-    return (int)hipGetLastError();
-}
-
-extern "C" int grt_launch_sw_profile(void *stream, GrtSwArgs const *a)
-{
-    size_t const lds = sizeof(double)*2*(size_t)a->num_levels*(kBlock/64);
-    if (a->ncol < 1 || a->nw < 2 || a->num_levels < 2 || a->tau_gas == nullptr || a->n_layer == nullptr ||
-        a->partials == nullptr || a->park == nullptr || lds > 65536)
-    {
+    case GRT_SOLVER_LAYERS:
+        hipLaunchKernelGGL(sw_props_kernel, dim3((unsigned)((cells + kPropsBlock - 1)/kPropsBlock), a->ncol, 1),
+                           dim3(kPropsBlock), 0, s, *a);
+        hipLaunchKernelGGL(sw_sweeps_kernel, dim3((unsigned)((a->nw + kSweepBlock - 1)/kSweepBlock), a->ncol, 1),
+                           dim3(kSweepBlock), 0, s, *a);
+        break;
+    case GRT_SOLVER_FUSED:
+        hipLaunchKernelGGL((sw_kernel<true, false>), grid, dim3(kBlock), 0, s, *a);
+        break;
+    case GRT_SOLVER_CHAINS:
+        hipLaunchKernelGGL((sw_kernel<false, false>), grid, dim3(kBlock), 0, s, *a);
+        break;
+    case GRT_SOLVER_PROFILE:
+        hipLaunchKernelGGL((sw_kernel<true, true>), grid, dim3(kBlock), lds, s, *a);
+        break;
+    case GRT_SOLVER_ALLSKY:
+        hipLaunchKernelGGL((sw_kernel<true, false, true, GrtCloudArgs>), grid, dim3(kBlock), 0, s, *a, *c);
+        break;
+    default:
         return (int)hipErrorInvalidValue;
     }
-    hipLaunchKernelGGL((sw_kernel<true, true>), dim3((unsigned)((a->nw + kBlock - 1)/kBlock), a->ncol, 1), dim3(kBlock),
-                       lds, (hipStream_t)stream, *a);
-    return (int)hipGetLastError();
-}
-
-extern "C" int grt_launch_sw_allsky(void *stream, GrtSwArgs const *a, GrtCloudArgs const *c)
-{
-    bool const one_sweep = a->one_sweep && (a->user_level < 0 || a->user_level == 0 || a->user_level == a->num_levels - 1);
-    if (a->ncol < 1 || a->nw < 2 || a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr ||
-        (a->park == nullptr && !one_sweep) || c->num_bands < 1 || c->band_liquid == nullptr || c->band_ice == nullptr ||
-        c->thickness == nullptr || c->liquid == nullptr || c->ice == nullptr)
-    {
-        return (int)hipErrorInvalidValue;
-    }
-    hipLaunchKernelGGL((sw_kernel<true, false, true, GrtCloudArgs>), dim3((unsigned)((a->nw + kBlock - 1)/kBlock), a->ncol, 1), dim3(kBlock), 0,
-                       (hipStream_t)stream, *a, *c);
     return (int)hipGetLastError();
 }

@@ -72,6 +72,24 @@ struct GrtPipeline
 
 static void grt_pipeline_release(GrtPipeline_t **pipeline);
 
+/* the row-pointer table rows_h [n] (integrate_rows' rows) to the device at *rows_d; rows_h is freed (after the upload) */
+static int upload_rows(GrtPipeline_t *p, double **rows_h, size_t n, double ***rows_d)
+{
+    void *s = grt_dev_stream(p->device);
+    double **d = NULL;
+    int rc = grt_dev_alloc(p->device, (void **)&d, sizeof(double *)*n);
+    if (rc == GRTCODE_SUCCESS) rc = grt_dev_upload(p->device, d, rows_h, sizeof(double *)*n, s);
+    if (rc == GRTCODE_SUCCESS) rc = grt_dev_sync(p->device, s);
+    free(rows_h);
+    if (rc != GRTCODE_SUCCESS)
+    {
+        grt_dev_free(p->device, d);
+        GRT_TRY(rc);
+    }
+    *rows_d = d;
+    return GRTCODE_SUCCESS;
+}
+
 static int band_alloc(GrtPipeline_t *p, GrtBand *b, GasOptics_t *gas)
 {
     memset(b, 0, sizeof(*b));
@@ -123,11 +141,7 @@ static int band_alloc(GrtPipeline_t *p, GrtBand *b, GasOptics_t *gas)
         rows_h[c*6 + 4] = dn + (V - 1)*b->n;
         rows_h[c*6 + 5] = p->user_level >= 0 ? dn + (size_t)p->user_level*b->n : b->zero_row;
     }
-    int rc = grt_dev_alloc(p->device, (void **)&b->rows_d, sizeof(double *)*C*6);
-    if (rc == GRTCODE_SUCCESS) rc = grt_dev_upload(p->device, b->rows_d, rows_h, sizeof(double *)*C*6, s);
-    if (rc == GRTCODE_SUCCESS) rc = grt_dev_sync(p->device, s);
-    free(rows_h);
-    GRT_TRY(rc);
+    GRT_TRY(upload_rows(p, rows_h, C*6, &b->rows_d));
     return GRTCODE_SUCCESS;
 }
 
@@ -400,36 +414,60 @@ static int band_gas_optics(GrtPipeline_t *p, GrtBand *b, int bi, GrtColumns_t co
     return GRTCODE_SUCCESS;
 }
 
-/* The fused solvers' arguments: Rayleigh, add_optics({gas, rayleigh}) and the solver in one launch (driver.c:268,
-   382-424); the caller sets the partial sums and, shortwave, the sweep form and the park block. */
-static void fused_lw_args(GrtPipeline_t *p, GrtBand const *b, int C, int defer, GrtContinua const *continua, GrtLwArgs *a)
+/* The solvers' arguments.  Fused forms: Rayleigh, add_optics({gas, rayleigh}) and the solver in one launch (driver.c:268,
+   382-424) on tau_gas; spectral form: the materialised tau, omega (, g) in, [level][wavenumber] fluxes out.  The caller
+   sets the partial sums and, shortwave, the park block. */
+static void lw_args(GrtPipeline_t const *p, GrtBand const *b, int C, int fused, int defer, GrtContinua const *continua,
+                    GrtLwArgs *a)
 {
     SpectralGrid_t const *grid = &b->gas->grid;
     int const V = p->num_levels, L = V - 1;
     memset(a, 0, sizeof(*a));
     a->num_levels = V; a->ncol = C; a->w0 = grid->w0; a->dw = grid->dw; a->nw = b->n;
-    a->tau_gas = b->tau_gas; a->n_layer = p->small_d + p->off_n; a->optics_stride = (uint64_t)L*b->n;
+    a->optics_stride = (uint64_t)L*b->n;
     a->t_layers = p->small_d + p->off_tl; a->t_levels = p->small_d + p->off_tv;
     a->t_surf = p->small_d + p->off_ts;
     a->emis = p->emis_d; a->emis_stride = 0;
     a->user_level = p->user_level;
-    a->add_continua = defer;
-    if (defer) a->continua = *continua;
+    if (fused)
+    {
+        a->tau_gas = b->tau_gas; a->n_layer = p->small_d + p->off_n;
+        a->add_continua = defer;
+        if (defer) a->continua = *continua;
+    }
+    else
+    {
+        a->tau = b->tau; a->omega = b->omega;
+        a->flux_up = b->flux_up; a->flux_down = b->flux_down; a->flux_stride = (uint64_t)V*b->n;
+    }
 }
 
-static void fused_sw_args(GrtPipeline_t *p, GrtBand const *b, int C, int defer, GrtContinua const *continua, GrtSwArgs *a)
+static void sw_args(GrtPipeline_t const *p, GrtBand const *b, int C, int fused, int defer, GrtContinua const *continua,
+                    GrtSwArgs *a)
 {
     SpectralGrid_t const *grid = &b->gas->grid;
     int const V = p->num_levels, L = V - 1;
     memset(a, 0, sizeof(*a));
     a->num_levels = V; a->ncol = C; a->nw = b->n; a->dw = grid->dw; a->w0 = grid->w0;
-    a->tau_gas = b->tau_gas; a->n_layer = p->small_d + p->off_n; a->optics_stride = (uint64_t)L*b->n;
+    a->optics_stride = (uint64_t)L*b->n;
     a->mu_dir = p->small_d + p->off_mu; a->mu_dif = 0.5;        /* driver.c:110 */
     a->alb_dir = p->albedo_d; a->alb_dif = p->albedo_d; a->alb_stride = 0;   /* driver.c:118-119 */
     a->tsi = p->small_d + p->off_tsi; a->solar = p->solar_d;
     a->user_level = p->user_level;
-    a->add_continua = defer;
-    if (defer) a->continua = *continua;
+    if (fused)
+    {
+        a->tau_gas = b->tau_gas; a->n_layer = p->small_d + p->off_n;
+        a->add_continua = defer;
+        if (defer) a->continua = *continua;
+        /* (read at every step, so that a test can compare the two forms in one process) */
+        char const *env = getenv("GRT_SW_TWO_SWEEPS");
+        a->one_sweep = !(env != NULL && env[0] == '1');
+    }
+    else
+    {
+        a->tau = b->tau; a->omega = b->omega; a->g = b->g;
+        a->flux_up = b->flux_up; a->flux_down = b->flux_down; a->flux_stride = (uint64_t)V*b->n;
+    }
 }
 
 /* the shortwave solver's two-sweep form: reflectances of 2 V levels and five properties of L layers per column and
@@ -446,145 +484,49 @@ static int park_block(GrtPipeline_t *p, GrtBand *b)
     return GRTCODE_SUCCESS;
 }
 
-/* Fused form: Rayleigh, add_optics({gas, rayleigh}) -- or, with clouds, add_optics({gas, rayleigh, liquid, ice}) --, solver
-   and -integrated output (driver.c:268, 382-424, 302-326) in one launch, then the fixed-order sum of its per-block partial
-   sums into the six values at fluxes_dev[c*out_stride + out_offset ..] */
-static int band_fused_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, int defer, GrtContinua const *continua,
-                             GrtCloudArgs const *clouds, double *fluxes_dev, int out_stride, int out_offset)
+/* the band's solver in `form` (GRT_SOLVER_CHAINS: the spectral form), timed under profile tag 3/4, or 8/9 with clouds */
+static int band_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtSolverForm form, int defer,
+                       GrtContinua const *continua, GrtCloudArgs const *clouds, double *partials)
 {
-    int const V = p->num_levels;
+    int const fused = form != GRT_SOLVER_CHAINS;
     void *s = grt_dev_stream(p->device);
     int slot, krc;
     if (bi == 0)
     {
         GrtLwArgs a;
-        fused_lw_args(p, b, C, defer, continua, &a);
-        a.partials = b->partials;
+        lw_args(p, b, C, fused, defer, continua, &a);
+        a.partials = partials;
         slot = grt_profile_begin(s, clouds ? 8 : 3);
-        krc = clouds ? grt_launch_lw_allsky(s, &a, clouds) : grt_launch_lw(s, &a);
-        grt_profile_end(s, slot);
-        GRT_TRY(grt_dev_check(krc, clouds ? "longwave kernel (all-sky)" : "longwave kernel (fused)"));
+        krc = grt_launch_lw(s, form, &a, clouds);
     }
     else
     {
         GrtSwArgs a;
-        fused_sw_args(p, b, C, defer, continua, &a);
-        a.partials = b->partials;
-        {
-            /* (read at every step, so that a test can compare the two forms in one process) */
-            char const *env = getenv("GRT_SW_TWO_SWEEPS");
-            a.one_sweep = !(env != NULL && env[0] == '1');
-        }
-        if (!(a.one_sweep && (p->user_level < 0 || p->user_level == 0 || p->user_level == V - 1)))
+        sw_args(p, b, C, fused, defer, continua, &a);
+        a.partials = partials;
+        if (form == GRT_SOLVER_PROFILE || (fused && !grt_sw_one_sweep(&a)))
         {
             GRT_TRY(park_block(p, b));
         }
         a.park = b->park;
         slot = grt_profile_begin(s, clouds ? 9 : 4);
-        krc = clouds ? grt_launch_sw_allsky(s, &a, clouds) : grt_launch_sw(s, &a);
-        grt_profile_end(s, slot);
-        GRT_TRY(grt_dev_check(krc, clouds ? "shortwave kernel (all-sky)" : "shortwave kernel (fused)"));
+        krc = grt_launch_sw(s, form, &a, clouds);
     }
-    GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, b->partials, C*6, b->nblocks, fluxes_dev, GRT_FLUXES_PER_BAND,
-                                                     out_stride, out_offset), "flux reduction kernel"));
+    grt_profile_end(s, slot);
+    GRT_TRY(grt_dev_check(krc, bi == 0 ? "longwave kernel" : "shortwave kernel"));
     return GRTCODE_SUCCESS;
 }
 
-/* Materialised form: Rayleigh + add_optics({gas, rayleigh}) (driver.c:268, 382-383), then the solver writing
-   [level][wavenumber] fluxes. */
-static int band_spectral_fluxes(GrtPipeline_t *p, GrtBand *b, int bi, int C, int tag);
-
-static int band_spectral_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C)
+/* Materialised form: Rayleigh + add_optics({gas, rayleigh}) (driver.c:268, 382-383) into the band's tau, omega, g */
+static int band_clear_sky_optics(GrtPipeline_t *p, GrtBand *b, int C)
 {
     SpectralGrid_t const *grid = &b->gas->grid;
-    int const V = p->num_levels, L = V - 1;
     void *s = grt_dev_stream(p->device);
-    int slot = grt_profile_begin(s, 5);
-    int krc = grt_launch_clear_sky_optics(s, L, C, grid->w0, grid->dw, b->n, p->small_d + p->off_n,
-                                          b->tau_gas, b->tau, b->omega, b->g);
+    int const slot = grt_profile_begin(s, 5);
+    int const krc = grt_launch_clear_sky_optics(s, p->num_levels - 1, C, grid->w0, grid->dw, b->n, p->small_d + p->off_n,
+                                                b->tau_gas, b->tau, b->omega, b->g);
     grt_profile_end(s, slot);
     GRT_TRY(grt_dev_check(krc, "clear-sky optics kernel"));
-    GRT_TRY(band_spectral_fluxes(p, b, bi, C, bi == 0 ? 3 : 4));
-    return GRTCODE_SUCCESS;
-}
-
-/* the spectral solver of one band on the materialised tau, omega, g, under profile tag `tag` */
-static int band_spectral_fluxes(GrtPipeline_t *p, GrtBand *b, int bi, int C, int tag)
-{
-    SpectralGrid_t const *grid = &b->gas->grid;
-    int const V = p->num_levels, L = V - 1;
-    uint64_t const per_opt = (uint64_t)L*b->n, per_flux = (uint64_t)V*b->n;
-    void *s = grt_dev_stream(p->device);
-    int slot, krc;
-    if (bi == 0)
-    {
-        GrtLwArgs a;
-        memset(&a, 0, sizeof(a));
-        a.num_levels = V; a.ncol = C; a.w0 = grid->w0; a.dw = grid->dw; a.nw = b->n;
-        a.tau = b->tau; a.omega = b->omega; a.optics_stride = per_opt;
-        a.t_layers = p->small_d + p->off_tl; a.t_levels = p->small_d + p->off_tv;
-        a.t_surf = p->small_d + p->off_ts;
-        a.emis = p->emis_d; a.emis_stride = 0;
-        a.flux_up = b->flux_up; a.flux_down = b->flux_down; a.flux_stride = per_flux;
-        a.user_level = p->user_level;
-        slot = grt_profile_begin(s, tag);
-        krc = grt_launch_lw(s, &a);
-        grt_profile_end(s, slot);
-        GRT_TRY(grt_dev_check(krc, "longwave kernel"));
-    }
-    else
-    {
-        GrtSwArgs a;
-        memset(&a, 0, sizeof(a));
-        a.num_levels = V; a.ncol = C; a.nw = b->n; a.dw = grid->dw;
-        a.tau = b->tau; a.omega = b->omega; a.g = b->g; a.optics_stride = per_opt;
-        a.mu_dir = p->small_d + p->off_mu; a.mu_dif = 0.5;        /* driver.c:110 */
-        a.alb_dir = p->albedo_d; a.alb_dif = p->albedo_d; a.alb_stride = 0;   /* driver.c:118-119 */
-        a.tsi = p->small_d + p->off_tsi; a.solar = p->solar_d;
-        a.flux_up = b->flux_up; a.flux_down = b->flux_down; a.flux_stride = per_flux;
-        a.user_level = p->user_level;
-        slot = grt_profile_begin(s, tag);
-        krc = grt_launch_sw(s, &a);
-        grt_profile_end(s, slot);
-        GRT_TRY(grt_dev_check(krc, "shortwave kernel"));
-    }
-    return GRTCODE_SUCCESS;
-}
-
-EXTERN int grt_pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, fp_t *fluxes_dev)
-{
-    GRT_REQUIRE_PTR(p);
-    GRT_REQUIRE_PTR(cols);
-    GRT_REQUIRE_PTR(fluxes_dev);
-    GRT_TRY(stage_columns(p, cols));
-    int const C = cols->ncol;
-    void *s = grt_dev_stream(p->device);
-    for (int bi = 0; bi < 2; ++bi)
-    {
-        GrtBand *b = &p->band[bi];
-        if (b->gas == NULL)
-        {
-            continue;
-        }
-        SpectralGrid_t const *grid = &b->gas->grid;
-        GrtContinua continua;
-        int defer;
-        GRT_TRY(band_gas_optics(p, b, bi, cols, &continua, &defer));
-        if (!p->keep_spectra)
-        {
-            /* Rayleigh, add_optics({gas, rayleigh}), solver and -integrated output (driver.c:268, 382-424, 302-326)
-               in one launch, then the fixed-order sum of its per-block partial sums */
-            GRT_TRY(band_fused_solver(p, b, bi, C, defer, &continua, NULL, fluxes_dev, GRT_FLUXES_PER_COLUMN,
-                                      bi*GRT_FLUXES_PER_BAND));
-            continue;
-        }
-        GRT_TRY(band_spectral_solver(p, b, bi, C));
-        /* -integrated output (driver.c:302-326) */
-        GRT_TRY(grt_dev_check(grt_launch_integrate_rows(s, (double const *const *)b->rows_d, C*6, b->n,
-                                                        grid->dw, fluxes_dev, GRT_FLUXES_PER_BAND,
-                                                        GRT_FLUXES_PER_COLUMN, bi*GRT_FLUXES_PER_BAND),
-                              "spectral integration kernel"));
-    }
     return GRTCODE_SUCCESS;
 }
 
@@ -609,105 +551,11 @@ static int level_rows(GrtPipeline_t *p, GrtBand *b)
             rows_h[(c*2 + 1)*V + k] = b->flux_down + (c*V + k)*b->n;
         }
     }
-    void *s = grt_dev_stream(p->device);
-    double **rows_d = NULL;
-    int rc = grt_dev_alloc(p->device, (void **)&rows_d, sizeof(double *)*C*2*V);
-    if (rc == GRTCODE_SUCCESS) rc = grt_dev_upload(p->device, rows_d, rows_h, sizeof(double *)*C*2*V, s);
-    if (rc == GRTCODE_SUCCESS) rc = grt_dev_sync(p->device, s);      /* (rows_h is freed next) */
-    free(rows_h);
-    if (rc != GRTCODE_SUCCESS)
-    {
-        grt_dev_free(p->device, rows_d);
-        GRT_TRY(rc);
-    }
-    b->level_rows_d = rows_d;
+    GRT_TRY(upload_rows(p, rows_h, C*2*V, &b->level_rows_d));
     return GRTCODE_SUCCESS;
 }
 
-EXTERN int grt_pipeline_run_profiles(GrtPipeline_t *p, GrtColumns_t const *cols, fp_t *level_fluxes_dev,
-                                     fp_t *heating_dev, fp_t *fluxes_dev)
-{
-    GRT_REQUIRE_PTR(p);
-    GRT_REQUIRE_PTR(cols);
-    if (level_fluxes_dev == NULL)
-    {
-        GRT_FAIL(GRTCODE_VALUE_ERR, "level_fluxes_dev is NULL: the level fluxes [ncol][%d][%d] are the output.",
-                 GRT_PROFILE_ROWS_PER_COLUMN, p->num_levels);
-    }
-    if (cols->ncol < 1 || cols->ncol > p->max_cols)
-    {
-        GRT_FAIL(GRTCODE_VALUE_ERR, "%d columns asked for, this pipeline was created for 1 to %d.", cols->ncol, p->max_cols);
-    }
-    if (p->num_levels < 2)
-    {
-        GRT_FAIL(GRTCODE_VALUE_ERR, "heating rates need at least 2 levels (%d).", p->num_levels);
-    }
-    GRT_TRY(stage_columns(p, cols));
-    int const V = p->num_levels, C = cols->ncol;
-    void *s = grt_dev_stream(p->device);
-    int bands = 0;
-    for (int bi = 0; bi < 2; ++bi)
-    {
-        GrtBand *b = &p->band[bi];
-        if (b->gas == NULL)
-        {
-            continue;
-        }
-        bands |= 1 << bi;
-        SpectralGrid_t const *grid = &b->gas->grid;
-        GrtContinua continua;
-        int defer;
-        GRT_TRY(band_gas_optics(p, b, bi, cols, &continua, &defer));
-        if (!p->keep_spectra)
-        {
-            if (b->level_partials == NULL)
-            {
-                void *lp = NULL;
-                GRT_TRY(grt_dev_alloc(p->device, &lp, sizeof(double)*(size_t)p->max_cols*2*(size_t)V*b->nblocks));
-                b->level_partials = lp;
-            }
-            int slot, krc;
-            if (bi == 0)
-            {
-                GrtLwArgs a;
-                fused_lw_args(p, b, C, defer, &continua, &a);
-                a.partials = b->level_partials;
-                slot = grt_profile_begin(s, 3);
-                krc = grt_launch_lw_profile(s, &a);
-                grt_profile_end(s, slot);
-                GRT_TRY(grt_dev_check(krc, "longwave kernel (profile form)"));
-            }
-            else
-            {
-                GrtSwArgs a;
-                fused_sw_args(p, b, C, defer, &continua, &a);
-                a.partials = b->level_partials;
-                GRT_TRY(park_block(p, b));
-                a.park = b->park;
-                slot = grt_profile_begin(s, 4);
-                krc = grt_launch_sw_profile(s, &a);
-                grt_profile_end(s, slot);
-                GRT_TRY(grt_dev_check(krc, "shortwave kernel (profile form)"));
-            }
-            /* [c][2 V] rows -> level_fluxes_dev[c][2 bi + {0, 1}][V] */
-            GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, b->level_partials, C*2*V, b->nblocks, level_fluxes_dev,
-                                                             2*V, GRT_PROFILE_ROWS_PER_COLUMN*V, bi*2*V),
-                                  "level flux reduction kernel"));
-            continue;
-        }
-        GRT_TRY(band_spectral_solver(p, b, bi, C));
-        GRT_TRY(level_rows(p, b));
-        GRT_TRY(grt_dev_check(grt_launch_integrate_rows(s, (double const *const *)b->level_rows_d, C*2*V, b->n,
-                                                        grid->dw, level_fluxes_dev, 2*V, GRT_PROFILE_ROWS_PER_COLUMN*V,
-                                                        bi*2*V), "spectral integration kernel (levels)"));
-    }
-    GRT_TRY(grt_dev_check(grt_launch_profile_finish(s, C, V, bands, p->user_level, GRT_GRAVITY, GRT_SPECIFIC_HEAT_AIR,
-                                                    p->small_d + p->off_p, level_fluxes_dev, heating_dev, fluxes_dev),
-                          "heating rate kernel"));
-    return GRTCODE_SUCCESS;
-}
-
-/* ---- all-sky fluxes (grt_pipeline_run_allsky) ---------------------------------------------------------------------- */
+/* ---- all-sky inputs (grt_pipeline_run_allsky) ---------------------------------------------------------------------- */
 
 /* first index in [0, n) whose value is >= target (n if none), last index whose value is <= target (-1 if none) */
 static int first_not_below(double const *w, int n, double target)
@@ -756,10 +604,16 @@ static void cloud_band_map(double const *lo, double const *hi, int own, int nb, 
     }
 }
 
-/* the band's per-point cloud bands for these band limits: built on the host when the limits differ from the last call's */
-static int band_cloud_map(GrtPipeline_t *p, GrtBand *b, GrtClouds_t const *cl)
+/* the band's cloud arguments for a batch of C columns staged by stage_clouds: its per-point cloud bands for these band
+   limits are built on the host when the limits differ from the last call's */
+static int band_clouds(GrtPipeline_t *p, GrtBand *b, int bi, GrtClouds_t const *cl, int C, GrtCloudArgs *ca)
 {
     int const B = cl->num_liquid_bands, NI = cl->num_ice_bands;
+    size_t const L = (size_t)p->num_levels - 1, set = (size_t)C*3*(size_t)B*L;
+    ca->num_bands = B;
+    ca->thickness = p->cloud_d;
+    ca->liquid = p->cloud_d + (size_t)C*L + (size_t)(2*bi)*set;
+    ca->ice = ca->liquid + set;
     size_t const nkey = 2 + 2*(size_t)B + 2*(size_t)NI;
     double *key = malloc(sizeof(double)*nkey);
     if (key == NULL)
@@ -774,6 +628,8 @@ static int band_cloud_map(GrtPipeline_t *p, GrtBand *b, GrtClouds_t const *cl)
     if (b->cloud_map != NULL && b->cloud_key_n == nkey && memcmp(b->cloud_key, key, sizeof(double)*nkey) == 0)
     {
         free(key);
+        ca->band_liquid = b->cloud_map;
+        ca->band_ice = b->cloud_map + b->n;
         return GRTCODE_SUCCESS;
     }
     int const n = (int)b->n;
@@ -817,6 +673,8 @@ static int band_cloud_map(GrtPipeline_t *p, GrtBand *b, GrtClouds_t const *cl)
     free(b->cloud_key);
     b->cloud_key = key;
     b->cloud_key_n = nkey;
+    ca->band_liquid = b->cloud_map;
+    ca->band_ice = b->cloud_map + b->n;
     return GRTCODE_SUCCESS;
 }
 
@@ -863,8 +721,8 @@ static int stage_clouds(GrtPipeline_t *p, GrtClouds_t const *cl, int C)
 }
 
 /* Materialised form: the cloud objects spread onto the grid, Rayleigh, add_optics of the four objects per column
-   (driver.c:507-530), then the spectral solver -- tau, omega, g and the fluxes of the band are the all-sky pass's */
-static int band_allsky_spectral(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtCloudArgs const *ca)
+   (driver.c:507-530) -- tau, omega, g of the band are the all-sky pass's */
+static int band_allsky_optics(GrtPipeline_t *p, GrtBand *b, int C, GrtCloudArgs const *ca)
 {
     SpectralGrid_t const *grid = &b->gas->grid;
     int const L = p->num_levels - 1;
@@ -900,7 +758,120 @@ static int band_allsky_spectral(GrtPipeline_t *p, GrtBand *b, int bi, int C, Grt
         GRT_TRY(grt_dev_check(grt_launch_add_optics(s, per, 4, &in, b->tau + o, b->omega + o, b->g + o),
                               "add_optics kernel (all-sky)"));
     }
-    GRT_TRY(band_spectral_fluxes(p, b, bi, C, bi == 0 ? 8 : 9));
+    return GRTCODE_SUCCESS;
+}
+
+/* ---- the run ------------------------------------------------------------------------------------------------------ */
+
+/* One solve of a band on this run's tau_gas: Rayleigh, add_optics({gas, rayleigh}) -- or, with clouds, add_optics({gas,
+   rayleigh, liquid, ice}) --, the solver and the -integrated output (driver.c:268, 382-424, 507-530, 302-326) of `rows`
+   rows per column, the six of driver.c:272-280 or (profile) every level's up then down flux, to
+   out[c*out_stride + out_offset + bi*rows + r].  Fused form: all of it in one solver launch, then the fixed-order sum of
+   its per-block partial sums; materialised form: tau, omega, g and the spectral fluxes in the band's arrays, then the
+   row-wise trapezoid. */
+static int band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, int defer, GrtContinua const *continua,
+                      GrtCloudArgs const *clouds, int profile, double *out, int out_stride, int out_offset)
+{
+    int const V = p->num_levels, rows = profile ? 2*V : GRT_FLUXES_PER_BAND;
+    out_offset += bi*rows;
+    void *s = grt_dev_stream(p->device);
+    if (!p->keep_spectra)
+    {
+        if (profile && b->level_partials == NULL)
+        {
+            void *lp = NULL;
+            GRT_TRY(grt_dev_alloc(p->device, &lp, sizeof(double)*(size_t)p->max_cols*2*(size_t)V*b->nblocks));
+            b->level_partials = lp;
+        }
+        double *partials = profile ? b->level_partials : b->partials;
+        GrtSolverForm const form = profile ? GRT_SOLVER_PROFILE : clouds ? GRT_SOLVER_ALLSKY : GRT_SOLVER_FUSED;
+        GRT_TRY(band_solver(p, b, bi, C, form, defer, continua, clouds, partials));
+        GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, partials, C*rows, b->nblocks, out, rows, out_stride, out_offset),
+                              "flux reduction kernel"));
+        return GRTCODE_SUCCESS;
+    }
+    GRT_TRY(clouds ? band_allsky_optics(p, b, C, clouds) : band_clear_sky_optics(p, b, C));
+    GRT_TRY(band_solver(p, b, bi, C, GRT_SOLVER_CHAINS, defer, continua, clouds, NULL));
+    if (profile)
+    {
+        GRT_TRY(level_rows(p, b));
+    }
+    GRT_TRY(grt_dev_check(grt_launch_integrate_rows(s, (double const *const *)(profile ? b->level_rows_d : b->rows_d),
+                                                    C*rows, b->n, b->gas->grid.dw, out, rows, out_stride, out_offset),
+                          "spectral integration kernel"));
+    return GRTCODE_SUCCESS;
+}
+
+/* What grt_pipeline_run, grt_pipeline_run_profiles and grt_pipeline_run_allsky share after their argument checks: the
+   batch (and its clouds) staged, then per band the gas optics and the solve into out (band_solve) -- with clouds, the
+   clear-sky solve and then the all-sky one, whose rows follow the clear-sky GRT_FLUXES_PER_COLUMN. */
+static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl, int profile, double *out,
+                        int out_stride)
+{
+    GRT_TRY(stage_columns(p, cols));
+    int const C = cols->ncol;
+    if (cl != NULL)
+    {
+        GRT_TRY(stage_clouds(p, cl, C));
+    }
+    for (int bi = 0; bi < 2; ++bi)
+    {
+        GrtBand *b = &p->band[bi];
+        if (b->gas == NULL)
+        {
+            continue;
+        }
+        GrtCloudArgs ca;
+        if (cl != NULL)
+        {
+            GRT_TRY(band_clouds(p, b, bi, cl, C, &ca));
+        }
+        GrtContinua continua;
+        int defer;
+        GRT_TRY(band_gas_optics(p, b, bi, cols, &continua, &defer));
+        GRT_TRY(band_solve(p, b, bi, C, defer, &continua, NULL, profile, out, out_stride, 0));
+        if (cl != NULL)
+        {
+            GRT_TRY(band_solve(p, b, bi, C, defer, &continua, &ca, 0, out, out_stride, GRT_FLUXES_PER_COLUMN));
+        }
+    }
+    return GRTCODE_SUCCESS;
+}
+
+EXTERN int grt_pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    GRT_REQUIRE_PTR(fluxes_dev);
+    GRT_TRY(pipeline_run(p, cols, NULL, 0, fluxes_dev, GRT_FLUXES_PER_COLUMN));
+    return GRTCODE_SUCCESS;
+}
+
+EXTERN int grt_pipeline_run_profiles(GrtPipeline_t *p, GrtColumns_t const *cols, fp_t *level_fluxes_dev,
+                                     fp_t *heating_dev, fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    if (level_fluxes_dev == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "level_fluxes_dev is NULL: the level fluxes [ncol][%d][%d] are the output.",
+                 GRT_PROFILE_ROWS_PER_COLUMN, p->num_levels);
+    }
+    if (cols->ncol < 1 || cols->ncol > p->max_cols)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d columns asked for, this pipeline was created for 1 to %d.", cols->ncol, p->max_cols);
+    }
+    if (p->num_levels < 2)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "heating rates need at least 2 levels (%d).", p->num_levels);
+    }
+    int const V = p->num_levels;
+    /* [c][2 V] rows of band bi -> level_fluxes_dev[c][2 bi + {0, 1}][V], then the level fluxes' heating rates and six rows */
+    GRT_TRY(pipeline_run(p, cols, NULL, 1, level_fluxes_dev, GRT_PROFILE_ROWS_PER_COLUMN*V));
+    int const bands = (p->band[0].gas != NULL) | (p->band[1].gas != NULL) << 1;
+    GRT_TRY(grt_dev_check(grt_launch_profile_finish(grt_dev_stream(p->device), cols->ncol, V, bands, p->user_level,
+                                                    GRT_GRAVITY, GRT_SPECIFIC_HEAT_AIR, p->small_d + p->off_p,
+                                                    level_fluxes_dev, heating_dev, fluxes_dev), "heating rate kernel"));
     return GRTCODE_SUCCESS;
 }
 
@@ -928,48 +899,6 @@ EXTERN int grt_pipeline_run_allsky(GrtPipeline_t *p, GrtColumns_t const *cols, G
     {
         GRT_FAIL(GRTCODE_VALUE_ERR, "%d columns asked for, this pipeline was created for 1 to %d.", cols->ncol, p->max_cols);
     }
-    GRT_TRY(stage_columns(p, cols));
-    int const L = p->num_levels - 1, C = cols->ncol;
-    size_t const set = (size_t)C*3*(size_t)cl->num_liquid_bands*(size_t)L;
-    GRT_TRY(stage_clouds(p, cl, C));
-    void *s = grt_dev_stream(p->device);
-    for (int bi = 0; bi < 2; ++bi)
-    {
-        GrtBand *b = &p->band[bi];
-        if (b->gas == NULL)
-        {
-            continue;
-        }
-        GRT_TRY(band_cloud_map(p, b, cl));
-        GrtCloudArgs ca;
-        ca.num_bands = cl->num_liquid_bands;
-        ca.band_liquid = b->cloud_map;
-        ca.band_ice = b->cloud_map + b->n;
-        ca.thickness = p->cloud_d;
-        ca.liquid = p->cloud_d + (size_t)C*L + (size_t)(2*bi)*set;
-        ca.ice = ca.liquid + set;
-        SpectralGrid_t const *grid = &b->gas->grid;
-        GrtContinua continua;
-        int defer;
-        GRT_TRY(band_gas_optics(p, b, bi, cols, &continua, &defer));
-        if (!p->keep_spectra)
-        {
-            /* the clear-sky pass exactly as grt_pipeline_run takes it, then the all-sky instance of the same solver */
-            GRT_TRY(band_fused_solver(p, b, bi, C, defer, &continua, NULL, fluxes_dev, GRT_ALLSKY_FLUXES_PER_COLUMN,
-                                      bi*GRT_FLUXES_PER_BAND));
-            GRT_TRY(band_fused_solver(p, b, bi, C, defer, &continua, &ca, fluxes_dev, GRT_ALLSKY_FLUXES_PER_COLUMN,
-                                      GRT_FLUXES_PER_COLUMN + bi*GRT_FLUXES_PER_BAND));
-            continue;
-        }
-        GRT_TRY(band_spectral_solver(p, b, bi, C));
-        GRT_TRY(grt_dev_check(grt_launch_integrate_rows(s, (double const *const *)b->rows_d, C*6, b->n, grid->dw, fluxes_dev,
-                                                        GRT_FLUXES_PER_BAND, GRT_ALLSKY_FLUXES_PER_COLUMN,
-                                                        bi*GRT_FLUXES_PER_BAND), "spectral integration kernel"));
-        GRT_TRY(band_allsky_spectral(p, b, bi, C, &ca));
-        GRT_TRY(grt_dev_check(grt_launch_integrate_rows(s, (double const *const *)b->rows_d, C*6, b->n, grid->dw, fluxes_dev,
-                                                        GRT_FLUXES_PER_BAND, GRT_ALLSKY_FLUXES_PER_COLUMN,
-                                                        GRT_FLUXES_PER_COLUMN + bi*GRT_FLUXES_PER_BAND),
-                              "spectral integration kernel (all-sky)"));
-    }
+    GRT_TRY(pipeline_run(p, cols, cl, 0, fluxes_dev, GRT_ALLSKY_FLUXES_PER_COLUMN));
     return GRTCODE_SUCCESS;
 }
