@@ -21,6 +21,8 @@ GRT_FLUXES_PER_COLUMN = 12
 GRT_PROFILE_ROWS_PER_COLUMN = 4     # LW up, LW down, SW up, SW down, each [V]
 GRT_HEATING_ROWS_PER_COLUMN = 2     # LW, SW, each [V-1]
 GRT_ALLSKY_FLUXES_PER_COLUMN = 24   # grt_pipeline_run's twelve (clear sky), then the same twelve all-sky
+GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN = 2 * GRT_PROFILE_ROWS_PER_COLUMN   # the clear-sky four rows, then the all-sky four
+GRT_ALLSKY_HEATING_ROWS_PER_COLUMN = 2 * GRT_HEATING_ROWS_PER_COLUMN   # the clear-sky two rows, then the all-sky two
 GRT_CLOUDS = 6                      # grt_sizeof kind of GrtClouds
 RETURN_CODES = ["GRTCODE_SUCCESS", "GRTCODE_INVALID_ERR", "GRTCODE_DIVBYZERO_ERR", "GRTCODE_OVERFLOW_ERR",
                 "GRTCODE_UNDERFLOW_ERR", "GRTCODE_SENTINEL_ERR", "GRTCODE_NULL_ERR", "GRTCODE_NON_NULL_ERR",
@@ -148,7 +150,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -188,6 +190,8 @@ def load_library(path=None):
     lib.grt_pipeline_run.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.c_void_p]
     lib.grt_pipeline_run_profiles.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.grt_pipeline_run_allsky.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtClouds), C.c_void_p]
+    lib.grt_pipeline_run_allsky_profiles.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtClouds), C.c_void_p,
+                                                     C.c_void_p, C.c_void_p]
     lib.grt_multi_gather_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.grt_pipeline_sync.argtypes = [C.c_void_p]
     lib.grt_pipeline_stream.argtypes = [C.c_void_p]
@@ -485,6 +489,7 @@ class Pipeline:
         self.num_levels = (lw_gas or sw_gas).num_levels
         self.prof = None        # run_profiles' device outputs: allocated at its first call
         self.allsky = None      # run_allsky's [max_columns][24]: allocated at its first call
+        self.allsky_prof = None  # run_allsky_profiles' device outputs: allocated at its first call
 
     def run(self, gcols, out_ptr=None):
         check(self.lib.grt_pipeline_run(self.p, C.byref(gcols), out_ptr if out_ptr is not None else self.out.ptr))
@@ -532,6 +537,29 @@ class Pipeline:
         f = self.allsky.to_host((ncol, GRT_ALLSKY_FLUXES_PER_COLUMN))
         return f[:, :GRT_FLUXES_PER_COLUMN].copy(), f[:, GRT_FLUXES_PER_COLUMN:].copy()
 
+    def run_allsky_profiles(self, gcols, gclouds):
+        """grt_pipeline_run_allsky_profiles into this object's device buffers (allsky_profiles() reads them)."""
+        V, n = self.num_levels, self.max_columns
+        if self.allsky_prof is None:
+            self.allsky_prof = {"levels": DeviceBuffer(self.device, 8 * n * GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN * V),
+                                "heating": DeviceBuffer(self.device, 8 * n * GRT_ALLSKY_HEATING_ROWS_PER_COLUMN * (V - 1)),
+                                "fluxes": DeviceBuffer(self.device, 8 * n * GRT_ALLSKY_FLUXES_PER_COLUMN)}
+        check(self.lib.grt_pipeline_run_allsky_profiles(self.p, C.byref(gcols), C.byref(gclouds),
+                                                        self.allsky_prof["levels"].ptr, self.allsky_prof["heating"].ptr,
+                                                        self.allsky_prof["fluxes"].ptr))
+
+    def allsky_profiles(self, ncol):
+        """The last run_allsky_profiles: (clear, all-sky), each a dict with profiles()' keys and shapes -- lw_up, lw_down,
+        sw_up, sw_down [ncol][V], lw_heating, sw_heating [ncol][V-1] and fluxes [ncol][12]."""
+        self.sync()
+        V, P, H, F = self.num_levels, GRT_PROFILE_ROWS_PER_COLUMN, GRT_HEATING_ROWS_PER_COLUMN, GRT_FLUXES_PER_COLUMN
+        lv = self.allsky_prof["levels"].to_host((ncol, 2, P, V))
+        hr = self.allsky_prof["heating"].to_host((ncol, 2, H, V - 1))
+        fx = self.allsky_prof["fluxes"].to_host((ncol, 2, F))
+        return tuple(dict(lw_up=lv[:, s, 0].copy(), lw_down=lv[:, s, 1].copy(), sw_up=lv[:, s, 2].copy(),
+                          sw_down=lv[:, s, 3].copy(), lw_heating=hr[:, s, 0].copy(), sw_heating=hr[:, s, 1].copy(),
+                          fluxes=fx[:, s].copy()) for s in range(2))
+
     def views(self, band):
         ptrs = [C.c_void_p() for _ in range(6)]
         if not self.spectral:
@@ -542,9 +570,10 @@ class Pipeline:
 
     def destroy(self):
         self.out.free()
-        for buf in (self.prof or {}).values():
+        for buf in list((self.prof or {}).values()) + list((self.allsky_prof or {}).values()):
             buf.free()
         self.prof = None
+        self.allsky_prof = None
         if self.allsky is not None:
             self.allsky.free()
             self.allsky = None

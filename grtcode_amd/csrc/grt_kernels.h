@@ -321,16 +321,20 @@ static inline int grt_sw_one_sweep(GrtSwArgs const *a)
    (one_sweep and user_level are not read); each wave sums a level as the sweep produces it, in dynamic LDS of
    2 V x 2 doubles per workgroup.  Rows 0, L and user_level are, bit for bit, the six-row form's (the shortwave's: its
    two-sweep form's). */
-/* levels [ncol][4][V] (up, down of band 0, then of band 1) -> heating [ncol][2][V-1] K day-1 (NULL: not formed) from the
-   level pressures pressure [ncol][V] mb, and fluxes [ncol][12] (NULL: not formed) in grt_pipeline_run's layout; the rows of
-   a band whose bit in `bands` is clear are zeroed, level fluxes included. */
-int grt_launch_profile_finish(void *stream, int ncol, int num_levels, int bands, int user_level, double gravity,
+/* levels [ncol][sets][4][V] (up, down of band 0, then of band 1) -> heating [ncol][sets][2][V-1] K day-1 (NULL: not
+   formed) from the level pressures pressure [ncol][V] mb, and fluxes [ncol][sets][12] (NULL: not formed) in
+   grt_pipeline_run's layout; the rows of a band whose bit in `bands` is clear are zeroed, level fluxes included, in every
+   set.  sets = 1: grt_pipeline_run_profiles; 2: grt_pipeline_run_allsky_profiles (clear sky, then all-sky). */
+int grt_launch_profile_finish(void *stream, int ncol, int sets, int num_levels, int bands, int user_level, double gravity,
                               double cp, double const *pressure, double *levels, double *heating, double *fluxes);
 
 /* All-sky form of the fused solvers (GRT_SOLVER_ALLSKY, grt_pipeline_run_allsky): the fused form's arguments (six-row
    partial sums), and per layer the liquid and ice cloud objects formed in registers from the band tables below and combined with
    gas and Rayleigh by allsky_combine (optics_dev.h).  band_liquid / band_ice: DEVICE [nw] band of each grid point, -1 for
-   none; thickness [ncol][L] m; liquid / ice [ncol][3][num_bands][L] (extinction m-1, albedo, asymmetry). */
+   none; thickness [ncol][L] m; liquid / ice [ncol][3][num_bands][L] (extinction m-1, albedo, asymmetry).
+   GRT_SOLVER_ALLSKY_PROFILE (grt_pipeline_run_allsky_profiles): the same cloud objects in the profile form -- its
+   partial sums, dynamic LDS and, shortwave, its two sweeps and park block; the cloud tables are read in the first sweep
+   only. */
 typedef struct GrtCloudArgs
 {
     int num_bands;
@@ -340,14 +344,15 @@ typedef struct GrtCloudArgs
 } GrtCloudArgs;
 
 /* The kernel instances of each solver.  grt_launch_lw / grt_launch_sw launch the form they are given, after checking the
-   fields that form reads (hipErrorInvalidValue otherwise); `clouds` is read by GRT_SOLVER_ALLSKY only. */
+   fields that form reads (hipErrorInvalidValue otherwise); `clouds` is read by the two all-sky forms only. */
 typedef enum GrtSolverForm
 {
     GRT_SOLVER_CHAINS,      /* spectral: one thread per wavenumber and column through all the layers */
     GRT_SOLVER_LAYERS,      /* spectral, the same fluxes: the layers' terms first (layer_terms / layer_props) */
     GRT_SOLVER_FUSED,       /* fused clear-sky, six output rows */
     GRT_SOLVER_PROFILE,     /* fused clear-sky, every level's up and down flux */
-    GRT_SOLVER_ALLSKY       /* fused all-sky, six output rows */
+    GRT_SOLVER_ALLSKY,      /* fused all-sky, six output rows */
+    GRT_SOLVER_ALLSKY_PROFILE   /* fused all-sky, every level's up and down flux */
 } GrtSolverForm;
 int grt_launch_lw(void *stream, GrtSolverForm form, GrtLwArgs const *a, GrtCloudArgs const *clouds);
 int grt_launch_sw(void *stream, GrtSolverForm form, GrtSwArgs const *a, GrtCloudArgs const *clouds);

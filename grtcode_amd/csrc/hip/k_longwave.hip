@@ -14,7 +14,7 @@
 // SURVEY.md §8a19 prices it at 1 944 B per wavenumber at 60 layers; measured it is a latency
 // chain -- 120 dependent layer steps with six fp64 exp each on 26 000 threads at 1 cm-1 -- which is why column
 // batches share a launch.  lw_kernel<true, false> is the fused form of the production pipeline, lw_kernel<true, false, true>
-// its all-sky form.
+// its all-sky form, lw_kernel<true, true> and lw_kernel<true, true, true> the profile forms of the two.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -67,8 +67,9 @@ __device__ __forceinline__ double extinction(double c1, double tau)
 // weighted value is summed across the wave where the sweep produces it, the waves' sums wait in dynamic LDS
 // (2 V x kBlock/64 doubles) and the block's sums go to partials[(c*2 V + r)*nblocks + block], r = level (up),
 // V + level (down).  Same association as block_partials: the six-row form's rows come out the same to the bit.
-// ALLSKY (fused six-row form only): the liquid and ice cloud objects join per layer (GrtCloudArgs): each point reads its
-// two band indices once, each layer forms the two objects from the column's band tables and allsky_combine adds the four.
+// ALLSKY (fused forms, six-row or profile): the liquid and ice cloud objects join per layer (GrtCloudArgs): each point reads
+// its two band indices once, each layer forms the two objects from the column's band tables and allsky_combine adds the
+// four.  Only layer_tau changes: what leaves the kernel is the six-row or the profile form's.
 template <bool FUSED, bool PROFILE, bool ALLSKY = false, typename... Clouds>
 __global__ __launch_bounds__(kBlock) void lw_kernel(GrtLwArgs a, Clouds... clouds)
 {
@@ -396,17 +397,18 @@ extern "C" unsigned grt_solver_blocks(uint64_t nw)
 
 extern "C" int grt_launch_lw(void *stream, GrtSolverForm form, GrtLwArgs const *a, GrtCloudArgs const *c)
 {
-    bool const fused = form == GRT_SOLVER_FUSED || form == GRT_SOLVER_PROFILE || form == GRT_SOLVER_ALLSKY;
-    size_t const lds = form == GRT_SOLVER_PROFILE ? sizeof(double)*2*(size_t)a->num_levels*(kBlock/64) : 0;
+    bool const profile = form == GRT_SOLVER_PROFILE || form == GRT_SOLVER_ALLSKY_PROFILE;
+    bool const allsky = form == GRT_SOLVER_ALLSKY || form == GRT_SOLVER_ALLSKY_PROFILE;
+    bool const fused = form == GRT_SOLVER_FUSED || profile || allsky;
+    size_t const lds = profile ? sizeof(double)*2*(size_t)a->num_levels*(kBlock/64) : 0;
     uint64_t const cells = (uint64_t)(a->num_levels - 1)*a->nw;
     if (a->ncol < 1 || a->nw < 2 ||
         (fused ? (a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr)
                : (a->flux_up == nullptr || a->flux_down == nullptr)) ||
         (form == GRT_SOLVER_LAYERS && (a->layer_terms == nullptr || cells > 0xffffffffull*kTermsBlock)) ||
-        (form == GRT_SOLVER_PROFILE && (a->num_levels < 2 || lds > 65536)) ||
-        (form == GRT_SOLVER_ALLSKY && (c == nullptr || c->num_bands < 1 || c->band_liquid == nullptr ||
-                                       c->band_ice == nullptr || c->thickness == nullptr || c->liquid == nullptr ||
-                                       c->ice == nullptr)))
+        (profile && (a->num_levels < 2 || lds > 65536)) ||
+        (allsky && (c == nullptr || c->num_bands < 1 || c->band_liquid == nullptr || c->band_ice == nullptr ||
+                    c->thickness == nullptr || c->liquid == nullptr || c->ice == nullptr)))
     {
         return (int)hipErrorInvalidValue;
     }
@@ -431,6 +433,9 @@ extern "C" int grt_launch_lw(void *stream, GrtSolverForm form, GrtLwArgs const *
         break;
     case GRT_SOLVER_ALLSKY:
         hipLaunchKernelGGL((lw_kernel<true, false, true, GrtCloudArgs>), grid, dim3(kBlock), 0, s, *a, *c);
+        break;
+    case GRT_SOLVER_ALLSKY_PROFILE:
+        hipLaunchKernelGGL((lw_kernel<true, true, true, GrtCloudArgs>), grid, dim3(kBlock), lds, s, *a, *c);
         break;
     default:
         return (int)hipErrorInvalidValue;

@@ -219,28 +219,30 @@ __global__ __launch_bounds__(64) void reduce_partials_kernel(double const *parti
     }
 }
 
-// Last step of grt_pipeline_run_profiles: one thread per (column, band, layer j) reads the band's level fluxes
-// levels[c][2 band + {0: up, 1: down}][V] and forms the heating rate of layer j, between levels j (upper) and j + 1,
+// Last step of grt_pipeline_run_profiles (sets = 1) and grt_pipeline_run_allsky_profiles (sets = 2: clear sky, then
+// all-sky): one thread per (column, set, band, layer j) reads the band's level fluxes
+// levels[c][set][2 band + {0: up, 1: down}][V] and forms the heating rate of layer j, between levels j (upper) and j + 1,
 //     H_j = (g/c_p) ((dn_j - up_j) - (dn_{j+1} - up_{j+1}))/(100 (p_{j+1} - p_j)) 86 400   [K day-1, p in mb],
 // and -- thread j = 0 -- the band's six rows of the six-row form (up top, up surface, up user, down top, down surface, down
 // user: grt_pipeline_run's layout).  A band that is not computed (bit clear in `bands`) gets zeros everywhere.
-__global__ __launch_bounds__(kBlock) void profile_finish_kernel(int ncol, int V, int bands, int user, double gravity,
-                                                                double cp, double const *pressure, double *levels,
-                                                                double *heating, double *fluxes)
+__global__ __launch_bounds__(kBlock) void profile_finish_kernel(int ncol, int sets, int V, int bands, int user,
+                                                                double gravity, double cp, double const *pressure,
+                                                                double *levels, double *heating, double *fluxes)
 {
     int const L = V - 1;
     uint64_t const t = (uint64_t)blockIdx.x*kBlock + threadIdx.x;
-    if (t >= (uint64_t)ncol*2*L)
+    if (t >= (uint64_t)ncol*sets*2*L)
     {
         return;
     }
     int const j = (int)(t % L);
     int const band = (int)((t/L) % 2);
-    int const c = (int)(t/(2*(uint64_t)L));
-    double *up = levels + ((uint64_t)c*4 + 2*band)*V;
+    uint64_t const cs = t/(2*(uint64_t)L);         // c sets + set
+    int const c = (int)(cs/sets);
+    double *up = levels + (cs*4 + 2*band)*V;
     double *dn = up + V;
-    double *six = fluxes ? fluxes + (uint64_t)c*12 + 6*band : nullptr;
-    double *h = heating ? heating + ((uint64_t)c*2 + band)*L + j : nullptr;
+    double *six = fluxes ? fluxes + cs*12 + 6*band : nullptr;
+    double *h = heating ? heating + (cs*2 + band)*L + j : nullptr;
     if (!((bands >> band) & 1))
     {
         up[j] = 0.;
@@ -282,17 +284,19 @@ __global__ __launch_bounds__(kBlock) void profile_finish_kernel(int ncol, int V,
 
 } // namespace
 
-extern "C" int grt_launch_profile_finish(void *stream, int ncol, int num_levels, int bands, int user_level, double gravity,
-                                         double cp, double const *pressure, double *levels, double *heating, double *fluxes)
+extern "C" int grt_launch_profile_finish(void *stream, int ncol, int sets, int num_levels, int bands, int user_level,
+                                         double gravity, double cp, double const *pressure, double *levels, double *heating,
+                                         double *fluxes)
 {
-    if (ncol < 1 || num_levels < 2 || user_level >= num_levels || levels == nullptr || (heating && pressure == nullptr))
+    if (ncol < 1 || sets < 1 || sets > 2 || num_levels < 2 || user_level >= num_levels || levels == nullptr ||
+        (heating && pressure == nullptr))
     {
         return (int)hipErrorInvalidValue;
     }
-    uint64_t const threads = (uint64_t)ncol*2*(uint64_t)(num_levels - 1);
+    uint64_t const threads = (uint64_t)ncol*sets*2*(uint64_t)(num_levels - 1);
     hipLaunchKernelGGL(profile_finish_kernel, dim3((unsigned)((threads + kBlock - 1)/kBlock)), dim3(kBlock), 0,
-                       (hipStream_t)stream, ncol, num_levels, bands, user_level, gravity, cp, pressure, levels, heating,
-                       fluxes);
+                       (hipStream_t)stream, ncol, sets, num_levels, bands, user_level, gravity, cp, pressure, levels,
+                       heating, fluxes);
     return (int)hipGetLastError();
 }
 

@@ -16,7 +16,8 @@
 // form the kernel is fp64-VALU-bound (two delta-Eddington solutions per layer and sweep: 70 000 instructions per wave),
 // not HBM-bound.  sw_kernel<true, false>, the fused form of the production pipeline, therefore trades bytes for flops: its first
 // sweep parks the five properties of every layer with the reflectances and its second sweep reads them back (the same
-// doubles: identical fluxes) -- 0.69 instead of 1.04 ms for 8 columns, at 4.2 TB/s.
+// doubles: identical fluxes) -- 0.69 instead of 1.04 ms for 8 columns, at 4.2 TB/s.  sw_kernel<true, false, true> is its
+// all-sky form, sw_kernel<true, true> and sw_kernel<true, true, true> the profile forms of the two.
 // The in-kernel range checks of the reference are no-ops on device builds
 // (debug.h:105-116) and are not restated.
 #include <hip/hip_runtime.h>
@@ -162,8 +163,9 @@ __device__ __forceinline__ LayerProps layer_props(double omega, double g, double
 // reflectances of EVERY level in rows 0 .. 2 V - 1 of the park block, the second produces up and down at every level and
 // sums each across the wave at once (wave_row_sum, as lw_kernel<true, true>); the block's sums of the 2 V rows go to
 // partials[(c*2 V + r)*nblocks + block], r = level (up), V + level (down).
-// ALLSKY (fused six-row form only): the liquid and ice cloud objects join per layer (GrtCloudArgs), as in lw_kernel; the
-// one-sweep and two-sweep rule is the fused form's.
+// ALLSKY (fused forms, six-row or profile): the liquid and ice cloud objects join per layer (GrtCloudArgs), as in lw_kernel;
+// the one-sweep and two-sweep rule is the form's own.  props_of is the only place that reads the cloud tables, and the
+// fused forms call it in their first (or only) sweep: the two-sweep forms' second sweep reads the parked properties.
 template <bool FUSED, bool PROFILE, bool ALLSKY = false, typename... Clouds>
 __global__ __launch_bounds__(kBlock) void sw_kernel(GrtSwArgs a, Clouds... clouds)
 {
@@ -625,19 +627,20 @@ __global__ __launch_bounds__(kSweepBlock) void sw_sweeps_kernel(GrtSwArgs a)
 
 extern "C" int grt_launch_sw(void *stream, GrtSolverForm form, GrtSwArgs const *a, GrtCloudArgs const *c)
 {
-    bool const fused = form == GRT_SOLVER_FUSED || form == GRT_SOLVER_PROFILE || form == GRT_SOLVER_ALLSKY;
-    bool const park = form == GRT_SOLVER_PROFILE || (fused && !grt_sw_one_sweep(a));
-    size_t const lds = form == GRT_SOLVER_PROFILE ? sizeof(double)*2*(size_t)a->num_levels*(kBlock/64) : 0;
+    bool const profile = form == GRT_SOLVER_PROFILE || form == GRT_SOLVER_ALLSKY_PROFILE;
+    bool const allsky = form == GRT_SOLVER_ALLSKY || form == GRT_SOLVER_ALLSKY_PROFILE;
+    bool const fused = form == GRT_SOLVER_FUSED || profile || allsky;
+    bool const park = profile || (fused && !grt_sw_one_sweep(a));
+    size_t const lds = profile ? sizeof(double)*2*(size_t)a->num_levels*(kBlock/64) : 0;
     uint64_t const cells = (uint64_t)(a->num_levels - 1)*a->nw;
     if (a->ncol < 1 || a->nw < 2 ||
         (fused ? (a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr || (park && a->park == nullptr))
                : (a->flux_up == nullptr || a->flux_down == nullptr)) ||
         (form == GRT_SOLVER_LAYERS && (a->layer_props == nullptr || cells > 0xffffffffull*kPropsBlock ||
                                        a->omega == nullptr || a->g == nullptr)) ||
-        (form == GRT_SOLVER_PROFILE && (a->num_levels < 2 || lds > 65536)) ||
-        (form == GRT_SOLVER_ALLSKY && (c == nullptr || c->num_bands < 1 || c->band_liquid == nullptr ||
-                                       c->band_ice == nullptr || c->thickness == nullptr || c->liquid == nullptr ||
-                                       c->ice == nullptr)))
+        (profile && (a->num_levels < 2 || lds > 65536)) ||
+        (allsky && (c == nullptr || c->num_bands < 1 || c->band_liquid == nullptr || c->band_ice == nullptr ||
+                    c->thickness == nullptr || c->liquid == nullptr || c->ice == nullptr)))
     {
         return (int)hipErrorInvalidValue;
     }
@@ -662,6 +665,9 @@ extern "C" int grt_launch_sw(void *stream, GrtSolverForm form, GrtSwArgs const *
         break;
     case GRT_SOLVER_ALLSKY:
         hipLaunchKernelGGL((sw_kernel<true, false, true, GrtCloudArgs>), grid, dim3(kBlock), 0, s, *a, *c);
+        break;
+    case GRT_SOLVER_ALLSKY_PROFILE:
+        hipLaunchKernelGGL((sw_kernel<true, true, true, GrtCloudArgs>), grid, dim3(kBlock), lds, s, *a, *c);
         break;
     default:
         return (int)hipErrorInvalidValue;

@@ -20,6 +20,8 @@
  * grt_pipeline_run_allsky runs grt_pipeline_run's clear-sky pass and then, on the same tau_gas, the all-sky pass of
  * driver.c:474-597: the cloud objects formed from band tables inside the solvers (or, materialised form, spread onto the
  * grid and added by the add_optics kernel).
+ * grt_pipeline_run_allsky_profiles runs both: the profile form of the clear-sky pass, then of the all-sky pass, on one
+ * tau_gas, and one finishing launch for the two sets.
  * All work is enqueued on the device's library stream; nothing synchronises.
  */
 #include <stdlib.h>
@@ -41,10 +43,10 @@ typedef struct GrtBand
     double *park;          /* shortwave: [cols][2 V + 5 L][n] first-sweep reflectances and layer properties */
     double *partials;      /* [cols][6][nblocks] trapezoid partial sums */
     unsigned nblocks;
-    /* grt_pipeline_run_profiles, allocated at its first call: */
+    /* grt_pipeline_run_profiles (and _allsky_profiles: both passes in turn), allocated at the first call: */
     double *level_partials;        /* fused form: [cols][2 V][nblocks] */
     double **level_rows_d;         /* materialised form: [cols][2 V] device row pointers (up levels, then down levels) */
-    /* grt_pipeline_run_allsky: */
+    /* grt_pipeline_run_allsky (and _allsky_profiles): */
     int *cloud_map;        /* [2][n] cloud band of each grid point (liquid, ice), -1: none */
     double *cloud_key;     /* host: the band limits cloud_map was built for (B, num_ice_bands, liquid lo/hi, ice lo/hi) */
     size_t cloud_key_n;
@@ -484,7 +486,8 @@ static int park_block(GrtPipeline_t *p, GrtBand *b)
     return GRTCODE_SUCCESS;
 }
 
-/* the band's solver in `form` (GRT_SOLVER_CHAINS: the spectral form), timed under profile tag 3/4, or 8/9 with clouds */
+/* the band's solver in `form` (GRT_SOLVER_CHAINS: the spectral form), timed under profile tag 3/4, or 8/9 with clouds;
+   the profile forms share the band's park block with the two-sweep six-row forms (the passes run in stream order) */
 static int band_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtSolverForm form, int defer,
                        GrtContinua const *continua, GrtCloudArgs const *clouds, double *partials)
 {
@@ -504,7 +507,7 @@ static int band_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtSolverFor
         GrtSwArgs a;
         sw_args(p, b, C, fused, defer, continua, &a);
         a.partials = partials;
-        if (form == GRT_SOLVER_PROFILE || (fused && !grt_sw_one_sweep(&a)))
+        if (form == GRT_SOLVER_PROFILE || form == GRT_SOLVER_ALLSKY_PROFILE || (fused && !grt_sw_one_sweep(&a)))
         {
             GRT_TRY(park_block(p, b));
         }
@@ -767,8 +770,9 @@ static int band_allsky_optics(GrtPipeline_t *p, GrtBand *b, int C, GrtCloudArgs 
    rayleigh, liquid, ice}) --, the solver and the -integrated output (driver.c:268, 382-424, 507-530, 302-326) of `rows`
    rows per column, the six of driver.c:272-280 or (profile) every level's up then down flux, to
    out[c*out_stride + out_offset + bi*rows + r].  Fused form: all of it in one solver launch, then the fixed-order sum of
-   its per-block partial sums; materialised form: tau, omega, g and the spectral fluxes in the band's arrays, then the
-   row-wise trapezoid. */
+   its per-block partial sums (profile: in level_partials, which the clear-sky and the all-sky pass of
+   grt_pipeline_run_allsky_profiles take in turn); materialised form: tau, omega, g and the spectral fluxes in the band's
+   arrays, then the row-wise trapezoid. */
 static int band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, int defer, GrtContinua const *continua,
                       GrtCloudArgs const *clouds, int profile, double *out, int out_stride, int out_offset)
 {
@@ -784,7 +788,8 @@ static int band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, int defer, Gr
             b->level_partials = lp;
         }
         double *partials = profile ? b->level_partials : b->partials;
-        GrtSolverForm const form = profile ? GRT_SOLVER_PROFILE : clouds ? GRT_SOLVER_ALLSKY : GRT_SOLVER_FUSED;
+        GrtSolverForm const form = profile ? (clouds ? GRT_SOLVER_ALLSKY_PROFILE : GRT_SOLVER_PROFILE)
+                                           : (clouds ? GRT_SOLVER_ALLSKY : GRT_SOLVER_FUSED);
         GRT_TRY(band_solver(p, b, bi, C, form, defer, continua, clouds, partials));
         GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, partials, C*rows, b->nblocks, out, rows, out_stride, out_offset),
                               "flux reduction kernel"));
@@ -802,9 +807,9 @@ static int band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, int defer, Gr
     return GRTCODE_SUCCESS;
 }
 
-/* What grt_pipeline_run, grt_pipeline_run_profiles and grt_pipeline_run_allsky share after their argument checks: the
-   batch (and its clouds) staged, then per band the gas optics and the solve into out (band_solve) -- with clouds, the
-   clear-sky solve and then the all-sky one, whose rows follow the clear-sky GRT_FLUXES_PER_COLUMN. */
+/* What the four run entry points share after their argument checks: the batch (and its clouds) staged, then per band
+   the gas optics and the solve into out (band_solve) -- with clouds, the clear-sky solve and then the all-sky one, whose
+   rows follow the clear-sky set's GRT_FLUXES_PER_COLUMN or (profile) GRT_PROFILE_ROWS_PER_COLUMN V. */
 static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl, int profile, double *out,
                         int out_stride)
 {
@@ -832,7 +837,8 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t 
         GRT_TRY(band_solve(p, b, bi, C, defer, &continua, NULL, profile, out, out_stride, 0));
         if (cl != NULL)
         {
-            GRT_TRY(band_solve(p, b, bi, C, defer, &continua, &ca, 0, out, out_stride, GRT_FLUXES_PER_COLUMN));
+            int const set = profile ? GRT_PROFILE_ROWS_PER_COLUMN*p->num_levels : GRT_FLUXES_PER_COLUMN;
+            GRT_TRY(band_solve(p, b, bi, C, defer, &continua, &ca, profile, out, out_stride, set));
         }
     }
     return GRTCODE_SUCCESS;
@@ -869,17 +875,15 @@ EXTERN int grt_pipeline_run_profiles(GrtPipeline_t *p, GrtColumns_t const *cols,
     /* [c][2 V] rows of band bi -> level_fluxes_dev[c][2 bi + {0, 1}][V], then the level fluxes' heating rates and six rows */
     GRT_TRY(pipeline_run(p, cols, NULL, 1, level_fluxes_dev, GRT_PROFILE_ROWS_PER_COLUMN*V));
     int const bands = (p->band[0].gas != NULL) | (p->band[1].gas != NULL) << 1;
-    GRT_TRY(grt_dev_check(grt_launch_profile_finish(grt_dev_stream(p->device), cols->ncol, V, bands, p->user_level,
+    GRT_TRY(grt_dev_check(grt_launch_profile_finish(grt_dev_stream(p->device), cols->ncol, 1, V, bands, p->user_level,
                                                     GRT_GRAVITY, GRT_SPECIFIC_HEAT_AIR, p->small_d + p->off_p,
                                                     level_fluxes_dev, heating_dev, fluxes_dev), "heating rate kernel"));
     return GRTCODE_SUCCESS;
 }
 
-EXTERN int grt_pipeline_run_allsky(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl, fp_t *fluxes_dev)
+/* grt_pipeline_run_allsky's and grt_pipeline_run_allsky_profiles' checks of the cloud inputs and the batch size */
+static int check_clouds(GrtPipeline_t const *p, GrtColumns_t const *cols, GrtClouds_t const *cl)
 {
-    GRT_REQUIRE_PTR(p);
-    GRT_REQUIRE_PTR(cols);
-    GRT_REQUIRE_PTR(fluxes_dev);
     if (cl == NULL)
     {
         GRT_FAIL(GRTCODE_VALUE_ERR, "no cloud inputs (GrtClouds_t is NULL).%s", "");
@@ -899,6 +903,41 @@ EXTERN int grt_pipeline_run_allsky(GrtPipeline_t *p, GrtColumns_t const *cols, G
     {
         GRT_FAIL(GRTCODE_VALUE_ERR, "%d columns asked for, this pipeline was created for 1 to %d.", cols->ncol, p->max_cols);
     }
+    return GRTCODE_SUCCESS;
+}
+
+EXTERN int grt_pipeline_run_allsky(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl, fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    GRT_REQUIRE_PTR(fluxes_dev);
+    GRT_TRY(check_clouds(p, cols, cl));
     GRT_TRY(pipeline_run(p, cols, cl, 0, fluxes_dev, GRT_ALLSKY_FLUXES_PER_COLUMN));
+    return GRTCODE_SUCCESS;
+}
+
+EXTERN int grt_pipeline_run_allsky_profiles(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl,
+                                            fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    if (level_fluxes_dev == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "level_fluxes_dev is NULL: the level fluxes [ncol][%d][%d] are the output.",
+                 GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN, p->num_levels);
+    }
+    if (p->num_levels < 2)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "heating rates need at least 2 levels (%d).", p->num_levels);
+    }
+    GRT_TRY(check_clouds(p, cols, cl));
+    int const V = p->num_levels;
+    /* clear-sky [c][2 V] rows of band bi -> level_fluxes_dev[c][2 bi + {0, 1}][V], all-sky -> [c][4 + 2 bi + {0, 1}][V];
+       then both sets' heating rates and six rows */
+    GRT_TRY(pipeline_run(p, cols, cl, 1, level_fluxes_dev, GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN*V));
+    int const bands = (p->band[0].gas != NULL) | (p->band[1].gas != NULL) << 1;
+    GRT_TRY(grt_dev_check(grt_launch_profile_finish(grt_dev_stream(p->device), cols->ncol, 2, V, bands, p->user_level,
+                                                    GRT_GRAVITY, GRT_SPECIFIC_HEAT_AIR, p->small_d + p->off_p,
+                                                    level_fluxes_dev, heating_dev, fluxes_dev), "heating rate kernel"));
     return GRTCODE_SUCCESS;
 }

@@ -212,6 +212,34 @@ typedef struct GrtClouds
 EXTERN int grt_pipeline_run_allsky(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtClouds_t const *clouds,
                                    fp_t *fluxes_dev);
 
+/* ---- all-sky level fluxes and heating rates ----------------------------------------------------------------------
+ * grt_pipeline_run_profiles and grt_pipeline_run_allsky together: the same batch and cloud inputs as
+ * grt_pipeline_run_allsky, with the broadband flux at every level and the heating rate of every layer of the clear-sky
+ * pass and of the all-sky pass.  Each column's block of every output is the clear-sky set, laid out exactly as
+ * grt_pipeline_run_profiles writes it, followed by the all-sky set in the same layout:
+ *   level_fluxes_dev [ncol][GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN][V]: clear LW up, LW down, SW up, SW down, then the same
+ *                    four rows all-sky (required);
+ *   heating_dev      [ncol][GRT_ALLSKY_HEATING_ROWS_PER_COLUMN][V-1]: clear LW, clear SW, all-sky LW, all-sky SW, K day-1,
+ *                    grt_pipeline_run_profiles' formula and constants (may be NULL);
+ *   fluxes_dev       [ncol][GRT_ALLSKY_FLUXES_PER_COLUMN], grt_pipeline_run_allsky's layout, from rows 0, L and the user
+ *                    level of each set (may be NULL).
+ * All DEVICE memory; asynchronous on the pipeline's lane.  One gas-optics launch per band serves both passes; the cloud
+ * band maps, tables and subcolumn rule are grt_pipeline_run_allsky's; the shortwave always takes the reference's two
+ * sweeps, as grt_pipeline_run_profiles does; a band whose gas-optics object is NULL gives zero rows.  The production form
+ * (keep_spectra = 0) solves the all-sky pass in the profile form of the solvers with the cloud objects formed inside
+ * (profile tags 8 and 9); its partial sums, park block and cloud buffers are those grt_pipeline_run_profiles and
+ * grt_pipeline_run_allsky allocate, shared by the two passes in stream order.  keep_spectra = 1: the spectra of both
+ * passes, integrated row by row; afterwards grt_pipeline_views shows the all-sky pass.  In the deterministic mode the
+ * clear-sky set is, bit for bit, grt_pipeline_run_profiles', and rows 0, L and the user level of the all-sky set are
+ * grt_pipeline_run_allsky's (shortwave: with GRT_SW_TWO_SWEEPS=1).  GRTCODE_VALUE_ERR, with nothing launched, for what
+ * either of the two refuses: a NULL level_fluxes_dev, fewer than 2 levels, clouds NULL, num_liquid_bands < 1,
+ * num_ice_bands < num_liquid_bands, a NULL array in the cloud inputs, ncol outside 1 .. max_columns. */
+#define GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN (2*GRT_PROFILE_ROWS_PER_COLUMN)   /* 8: clear sky, then all-sky */
+#define GRT_ALLSKY_HEATING_ROWS_PER_COLUMN (2*GRT_HEATING_ROWS_PER_COLUMN)   /* 4: clear sky, then all-sky */
+EXTERN int grt_pipeline_run_allsky_profiles(GrtPipeline_t *pipeline, GrtColumns_t const *columns,
+                                            GrtClouds_t const *clouds, fp_t *level_fluxes_dev, fp_t *heating_dev,
+                                            fp_t *fluxes_dev);
+
 /* ---- columns across the GPUs of one node ------------------------------------
  * One process per GPU; contiguous ceil-sized column blocks; one gather of the [columns][GRT_FLUXES_PER_COLUMN]
  * flux blocks to rank 0.  The reference fans out processes with -x/-X column ranges and merges per-shard files
@@ -235,7 +263,8 @@ EXTERN int grt_multi_create(GrtMulti_t **multi, int transport, Device_t device, 
 EXTERN int grt_multi_destroy(GrtMulti_t **multi);
 /* local: this rank's [count][row_doubles] block; all (rank 0 only): room for world*ceil(num_columns/world) rows, the first
    num_columns of which are the columns in order (short blocks are padded, so no sizes are exchanged).  Any row width:
-   e.g. 4 V + 2 (V - 1) for the level fluxes and heating rates of grt_pipeline_run_profiles. */
+   e.g. 4 V + 2 (V - 1) for the level fluxes and heating rates of grt_pipeline_run_profiles, 8 V + 4 (V - 1) for those of
+   grt_pipeline_run_allsky_profiles. */
 EXTERN int grt_multi_gather_rows(GrtMulti_t *multi, fp_t const *local, int num_columns, int row_doubles, fp_t *all,
                                  int on_device);
 /* grt_multi_gather_rows with rows of GRT_FLUXES_PER_COLUMN: the [count][12] blocks of grt_pipeline_run. */
@@ -247,8 +276,8 @@ EXTERN int grt_multi_max(GrtMulti_t *multi, double *value);    /* barrier + maxi
  * Tags: 1 = line-by-line kernel on a grid of <= 10 000 points (longwave band at 1 cm-1),
  * 2 = line-by-line kernel on a larger grid (shortwave band), 3 = LW solver, 4 = SW solver,
  * 5 = clear-sky optics combine, 6 / 7 = far-field gather kernel of the two-pass line kernel (longwave /
- * shortwave band; tags 1 / 2 then cover its first pass), 8 / 9 = LW / SW solver of grt_pipeline_run_allsky's all-sky
- * pass (its clear-sky pass counts under 3 / 4).  Read after grt_pipeline_sync(). */
+ * shortwave band; tags 1 / 2 then cover its first pass), 8 / 9 = LW / SW solver of the all-sky pass of
+ * grt_pipeline_run_allsky and grt_pipeline_run_allsky_profiles (their clear-sky pass counts under 3 / 4).  Read after grt_pipeline_sync(). */
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
 
