@@ -8,6 +8,7 @@
 #ifndef GRT_KERNELS_H_
 #define GRT_KERNELS_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -354,6 +355,22 @@ typedef enum GrtSolverForm
     GRT_SOLVER_ALLSKY,      /* fused all-sky, six output rows */
     GRT_SOLVER_ALLSKY_PROFILE   /* fused all-sky, every level's up and down flux */
 } GrtSolverForm;
+/* what a form is: fused (the kernel integrates, nothing spectral leaves), profile (every level's fluxes), all-sky (clouds) */
+typedef struct GrtFormKind { int fused, profile, allsky; } GrtFormKind;
+static inline GrtFormKind grt_form_kind(GrtSolverForm form)
+{
+    GrtFormKind k;
+    k.profile = form == GRT_SOLVER_PROFILE || form == GRT_SOLVER_ALLSKY_PROFILE;
+    k.allsky = form == GRT_SOLVER_ALLSKY || form == GRT_SOLVER_ALLSKY_PROFILE;
+    k.fused = form == GRT_SOLVER_FUSED || k.profile || k.allsky;
+    return k;
+}
+/* whether an all-sky form can read `c` */
+static inline int grt_cloud_args_ok(GrtCloudArgs const *c)
+{
+    return c != NULL && c->num_bands >= 1 && c->band_liquid != NULL && c->band_ice != NULL && c->thickness != NULL &&
+           c->liquid != NULL && c->ice != NULL;
+}
 int grt_launch_lw(void *stream, GrtSolverForm form, GrtLwArgs const *a, GrtCloudArgs const *clouds);
 int grt_launch_sw(void *stream, GrtSolverForm form, GrtSwArgs const *a, GrtCloudArgs const *clouds);
 /* Materialised form: the cloud objects of the same tables spread onto the grid, [ncol][L][nw] each (tau = extinction x

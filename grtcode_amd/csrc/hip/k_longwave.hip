@@ -25,8 +25,10 @@
 
 namespace {
 
-constexpr int kBlock = 128;
 constexpr double kMaxExpArg = 700.;   // grtcode_config.h:41
+// the four streams' constants (longwave.c:160-168)
+constexpr double kC1[4] = {-14.402613260847248, -3.0302159969901132, -1.4925584280108841, -1.0746123148178333};
+constexpr double kC2[4] = {0.07587638482015649, 0.676114979733751, 1.3726594476601073, 1.0169418413757783};
 
 // longwave.c:68-94
 __device__ __forceinline__ double planck(double T, double w)
@@ -50,9 +52,10 @@ __device__ __forceinline__ double effective_planck(double bc, double be, double 
     return (bc + (a*tau + b*tau*tau)*be)/(1. + a*tau + b*tau*tau);
 }
 
-__device__ __forceinline__ double extinction(double c1, double tau)
+// extinction of stream s over optical depth tau (longwave.c:177-183)
+__device__ __forceinline__ double extinction(int s, double tau)
 {
-    double e = c1*tau;                     // longwave.c:177-183
+    double e = kC1[s]*tau;
     if (e > kMaxExpArg)
     {
         e = kMaxExpArg;
@@ -60,25 +63,46 @@ __device__ __forceinline__ double extinction(double c1, double tau)
     return exp(e);
 }
 
-// FUSED: the clear-sky tail of the pipeline in one kernel -- Rayleigh and the two-object optics combination are formed
-// per layer in registers from tau_gas (same expressions, same order as clear_sky_kernel: identical values), nothing
-// spectral is written, and the six integrated output rows leave as per-block trapezoid partial sums.
-// PROFILE (fused form only): every level's upward and downward flux leaves instead, 2 V rows per column: each level's
-// weighted value is summed across the wave where the sweep produces it, the waves' sums wait in dynamic LDS
-// (2 V x kBlock/64 doubles) and the block's sums go to partials[(c*2 V + r)*nblocks + block], r = level (up),
-// V + level (down).  Same association as block_partials: the six-row form's rows come out the same to the bit.
-// ALLSKY (fused forms, six-row or profile): the liquid and ice cloud objects join per layer (GrtCloudArgs): each point reads
-// its two band indices once, each layer forms the two objects from the column's band tables and allsky_combine adds the
-// four.  Only layer_tau changes: what leaves the kernel is the six-row or the profile form's.
-template <bool FUSED, bool PROFILE, bool ALLSKY = false, typename... Clouds>
-__global__ __launch_bounds__(kBlock) void lw_kernel(GrtLwArgs a, Clouds... clouds)
+// One layer of the four streams (longwave.c:186-195, 204-211): I_s <- (1 - ext_s) val + I_s ext_s; returns the flux
+// sum_s c2[s] I_s.  ext(s) gives stream s's extinction where the step needs it (worked out there, or read ahead).
+template <typename Ext>
+__device__ __forceinline__ double stream_step(double (&I)[4], double val, Ext ext)
 {
-    GrtCloudArgs const cl = cloud_args(clouds...);      // (ALLSKY: the one GrtCloudArgs argument)
-    double const c1[4] = {-14.402613260847248, -3.0302159969901132,
-                          -1.4925584280108841, -1.0746123148178333};   // longwave.c:160-163
-    double const c2[4] = {0.07587638482015649, 0.676114979733751,
-                          1.3726594476601073, 1.0169418413757783};     // longwave.c:165-168
-    uint64_t const i = (uint64_t)blockIdx.x*kBlock + threadIdx.x;
+    double f = 0.;
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+    {
+        double const e = ext(s);
+        double const p = (1. - e)*val;                                   // longwave.c:193
+        I[s] = p + I[s]*e;
+        f += kC2[s]*I[s];                                                // longwave.c:195
+    }
+    return f;
+}
+
+// The surface (longwave.c:202): emission bs at emissivity emis, the rest of each stream reflected; returns the flux
+__device__ __forceinline__ double surface_step(double (&I)[4], double emis, double bs)
+{
+    double f = 0.;
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+    {
+        I[s] = emis*bs + (1 - emis)*I[s];
+        f += kC2[s]*I[s];
+    }
+    return f;
+}
+
+// FUSED: the clear-sky tail of the pipeline in one kernel -- Rayleigh and the two-object optics combination are formed
+// per layer in registers from tau_gas (LayerOptics: identical values), nothing spectral is written, and the six
+// integrated output rows leave as per-block trapezoid partial sums (LevelSink).
+// PROFILE (fused form only): every level's upward and downward flux leaves instead, 2 V rows per column (LevelSink).
+// ALLSKY (fused forms, six-row or profile): the liquid and ice cloud objects join per layer (LayerOptics).  Only
+// layer_tau changes: what leaves the kernel is the six-row or the profile form's.
+template <bool FUSED, bool PROFILE, bool ALLSKY = false, typename... Clouds>
+__global__ __launch_bounds__(kSolverBlock) void lw_kernel(GrtLwArgs a, Clouds... clouds)
+{
+    uint64_t const i = (uint64_t)blockIdx.x*kSolverBlock + threadIdx.x;
     int const col = blockIdx.y;
     bool const live = i < a.nw;
     if (!FUSED && !live)
@@ -89,163 +113,43 @@ __global__ __launch_bounds__(kBlock) void lw_kernel(GrtLwArgs a, Clouds... cloud
     int const V = a.num_levels;
     int const L = V - 1;
     double const w = a.w0 + ii*a.dw;                                     // longwave.c:246
-    double const *tau = (FUSED ? a.tau_gas : a.tau) + (uint64_t)col*a.optics_stride + ii;
+    double const *tau = a.tau + (uint64_t)col*a.optics_stride + ii;
     double const *omega = (!FUSED && a.omega) ? a.omega + (uint64_t)col*a.optics_stride + ii : nullptr;
-    double const *nl = FUSED ? a.n_layer + (uint64_t)col*L : nullptr;
     double const *tl = a.t_layers + (uint64_t)col*L;
     double const *tv = a.t_levels + (uint64_t)col*V;
     double const emis = a.emis[(uint64_t)col*a.emis_stride + ii];
-    double *fu = FUSED ? nullptr : a.flux_up + (uint64_t)col*a.flux_stride + ii;
-    double *fd = FUSED ? nullptr : a.flux_down + (uint64_t)col*a.flux_stride + ii;
-    int const user = a.user_level;
-    double out[6] = {0., 0., 0., 0., 0., 0.};     // up TOA, up surface, up user, down TOA, down surface, down user
-    extern __shared__ double level_sums[];        // PROFILE: [2 V][kBlock/64]
-    double const pwt = !PROFILE || !live ? 0. : ((i == 0 || i + 1 == a.nw) ? 0.5*a.dw : a.dw);
-
-    // (the gas-optics launch left the spectral tables' part of tau to this kernel: a table entry read once per point)
-    PointContinua pc;
-    long long const blk_lo = (long long)blockIdx.x*kBlock, blk_hi = blk_lo + kBlock < (long long)a.nw ? blk_lo + kBlock : (long long)a.nw;
-    bool const add_continua = FUSED && a.add_continua;
-    double const *cstate = a.continua.colstate + (uint64_t)col*a.continua.stride;
-    if (add_continua)
-    {
-        continua_load(a.continua, a.nw, ii, blk_lo, blk_hi, pc);
-    }
-    int const band_l = ALLSKY ? cl.band_liquid[ii] : -1, band_i = ALLSKY ? cl.band_ice[ii] : -1;
-    uint64_t const ctab = ALLSKY ? (uint64_t)col*3*(uint64_t)cl.num_bands*L : 0;
+    LevelSink<FUSED, PROFILE> sink(a, col, i, live);
+    LayerOptics<FUSED, ALLSKY> const optics(a, cloud_args(clouds...), col, ii);   // (fused forms)
 
     // absorption optical depth of layer j: tau (1 - omega)  (longwave.c:252)
     auto layer_tau = [&](int j) -> double
     {
-        uint64_t const o = (uint64_t)j*a.nw;
         if (FUSED)
         {
             double t, om, gg;
-            double tg = tau[o];
-            if (add_continua)
-            {
-                tg = continua_add(a.continua, pc, cstate, j, a.nw, ii, blk_lo, blk_hi, tg);
-            }
-            if constexpr (ALLSKY)
-            {
-                double const th = cl.thickness[(uint64_t)col*L + j];
-                double lt, lo, lg, it, io, ig;
-                cloud_layer(cl.liquid + ctab, cl.num_bands, L, band_l, j, th, lt, lo, lg);
-                cloud_layer(cl.ice + ctab, cl.num_bands, L, band_i, j, th, it, io, ig);
-                allsky_combine(tg, rayleigh_tau(w, nl[j]), lt, lo, lg, it, io, ig, t, om, gg);
-            }
-            else
-            {
-                clear_sky_combine(tg, rayleigh_tau(w, nl[j]), t, om, gg);
-            }
+            optics.at(j, t, om, gg);
             return t*(1. - om);
         }
+        uint64_t const o = (uint64_t)j*a.nw;
         return omega ? tau[o]*(1. - omega[o]) : tau[o]*(1. - 0.);
     };
 
     double I[4] = {0., 0., 0., 0.};
-    if (!FUSED)
-    {
-        fd[0] = 0.;                                                      // longwave.c:171
-    }
-    if (FUSED && user == 0)
-    {
-        out[5] = 0.;
-    }
-    if (PROFILE && (threadIdx.x & 63) == 0)
-    {
-        level_sums[V*(kBlock/64) + (threadIdx.x >> 6)] = 0.;          // down at the top
-    }
+    sink.put_zero(0, true);                                              // longwave.c:171
     for (int j = 0; j < L; ++j)
     {
         double const t = layer_tau(j);
         double const val = effective_planck(planck(tl[j], w), planck(tv[j + 1], w), t);
-        double f = 0.;
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-        {
-            double const ext = extinction(c1[s], t);
-            double const p = (1. - ext)*val;                             // longwave.c:193
-            I[s] = p + I[s]*ext;
-            f += c2[s]*I[s];                                             // longwave.c:195
-        }
-        if (PROFILE)
-        {
-            wave_row_sum<kBlock>(f*pwt, level_sums, V + j + 1);
-        }
-        else if (FUSED)
-        {
-            out[4] = j + 1 == L ? f : out[4];
-            out[5] = j + 1 == user ? f : out[5];
-        }
-        else
-        {
-            fd[(uint64_t)(j + 1)*a.nw] = f;
-        }
+        sink.put(j + 1, true, stream_step(I, val, [&](int s) { return extinction(s, t); }));
     }
-    double const bs = planck(a.t_surf[col], w);
-    double f = 0.;
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-    {
-        I[s] = emis*bs + (1 - emis)*I[s];                                // longwave.c:202
-        f += c2[s]*I[s];
-    }
-    if (PROFILE)
-    {
-        wave_row_sum<kBlock>(f*pwt, level_sums, L);
-    }
-    else if (FUSED)
-    {
-        out[1] = f;
-        out[2] = user == L ? f : out[2];
-    }
-    else
-    {
-        fu[(uint64_t)L*a.nw] = f;
-    }
+    sink.put(L, false, surface_step(I, emis, planck(a.t_surf[col], w)));
     for (int j = L - 1; j >= 0; --j)
     {
         double const t = layer_tau(j);
         double const val = effective_planck(planck(tl[j], w), planck(tv[j], w), t);
-        double g = 0.;
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-        {
-            double const ext = extinction(c1[s], t);
-            double const p = (1. - ext)*val;                             // longwave.c:211
-            I[s] = p + I[s]*ext;
-            g += c2[s]*I[s];
-        }
-        if (PROFILE)
-        {
-            wave_row_sum<kBlock>(g*pwt, level_sums, j);
-        }
-        else if (FUSED)
-        {
-            out[0] = j == 0 ? g : out[0];
-            out[2] = j == user ? g : out[2];
-        }
-        else
-        {
-            fu[(uint64_t)j*a.nw] = g;
-        }
+        sink.put(j, false, stream_step(I, val, [&](int s) { return extinction(s, t); }));
     }
-    if (PROFILE)
-    {
-        block_row_partials<kBlock>(level_sums, 2*V, a.partials, (uint64_t)col*2*V, gridDim.x, blockIdx.x);
-    }
-    else if (FUSED)
-    {
-        // driver.c:302-326: sum 0.5 (f_i + f_{i+1}) dw over the grid = sum weight_i f_i
-        double const wt = !live ? 0. : ((i == 0 || i + 1 == a.nw) ? 0.5*a.dw : a.dw);
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-        {
-            out[k] *= wt;
-        }
-        block_partials<6, kBlock>(out, a.partials, (uint64_t)col*6, gridDim.x, blockIdx.x);
-    }
+    sink.finish(a);
 }
 
 // ---- spectral form of few columns: the layers' terms first, by one thread per (layer, wavenumber) ----
@@ -260,8 +164,6 @@ constexpr int kSweepChunk = 6;
 
 __global__ __launch_bounds__(kTermsBlock) void lw_terms_kernel(GrtLwArgs a)
 {
-    double const c1[4] = {-14.402613260847248, -3.0302159969901132,
-                          -1.4925584280108841, -1.0746123148178333};   // longwave.c:160-163
     int const col = blockIdx.y;
     int const V = a.num_levels;
     int const L = V - 1;
@@ -283,7 +185,7 @@ __global__ __launch_bounds__(kTermsBlock) void lw_terms_kernel(GrtLwArgs a)
 #pragma unroll
     for (int s = 0; s < 4; ++s)
     {
-        q[(uint64_t)s*nw] = extinction(c1[s], t);
+        q[(uint64_t)s*nw] = extinction(s, t);
     }
     q[4*nw] = effective_planck(bc, planck(tv[j + 1], w), t);             // the downward sweep's (longwave.c:186-193)
     q[5*nw] = effective_planck(bc, planck(tv[j], w), t);                 // the upward sweep's (:204-211)
@@ -291,8 +193,6 @@ __global__ __launch_bounds__(kTermsBlock) void lw_terms_kernel(GrtLwArgs a)
 
 __global__ __launch_bounds__(kSweepBlock) void lw_sweeps_kernel(GrtLwArgs a)
 {
-    double const c2[4] = {0.07587638482015649, 0.676114979733751,
-                          1.3726594476601073, 1.0169418413757783};     // longwave.c:165-168
     uint64_t const i = (uint64_t)blockIdx.x*kSweepBlock + threadIdx.x;
     int const col = blockIdx.y;
     if (i >= a.nw)
@@ -305,10 +205,9 @@ __global__ __launch_bounds__(kSweepBlock) void lw_sweeps_kernel(GrtLwArgs a)
     double const w = a.w0 + i*a.dw;
     double const emis = a.emis[(uint64_t)col*a.emis_stride + i];
     double const *tt = a.layer_terms + (uint64_t)col*6*(uint64_t)L*nw + i;
-    double *fu = a.flux_up + (uint64_t)col*a.flux_stride + i;
-    double *fd = a.flux_down + (uint64_t)col*a.flux_stride + i;
+    LevelSink<false, false> sink(a, col, i, true);
     double I[4] = {0., 0., 0., 0.};
-    fd[0] = 0.;                                                          // longwave.c:171
+    sink.put_zero(0, true);                                              // longwave.c:171
     for (int jb = 0; jb < L; jb += kSweepChunk)
     {
         double ex[kSweepChunk][4], vl[kSweepChunk];
@@ -329,29 +228,11 @@ __global__ __launch_bounds__(kSweepBlock) void lw_sweeps_kernel(GrtLwArgs a)
             int const j = jb + u;
             if (j < L)
             {
-                double const val = vl[u];
-                double f = 0.;
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-                {
-                    double const ext = ex[u][s];
-                    double const p = (1. - ext)*val;                     // longwave.c:193
-                    I[s] = p + I[s]*ext;
-                    f += c2[s]*I[s];                                     // longwave.c:195
-                }
-                fd[(uint64_t)(j + 1)*nw] = f;
+                sink.put(j + 1, true, stream_step(I, vl[u], [&](int s) { return ex[u][s]; }));
             }
         }
     }
-    double const bs = planck(a.t_surf[col], w);
-    double f = 0.;
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-    {
-        I[s] = emis*bs + (1 - emis)*I[s];                                // longwave.c:202
-        f += c2[s]*I[s];
-    }
-    fu[(uint64_t)L*nw] = f;
+    sink.put(L, false, surface_step(I, emis, planck(a.t_surf[col], w)));
     for (int jb = L - 1; jb >= 0; jb -= kSweepChunk)
     {
         double ex[kSweepChunk][4], vl[kSweepChunk];
@@ -372,17 +253,7 @@ __global__ __launch_bounds__(kSweepBlock) void lw_sweeps_kernel(GrtLwArgs a)
             int const j = jb - u;
             if (j >= 0)
             {
-                double const val = vl[u];
-                double g = 0.;
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-                {
-                    double const ext = ex[u][s];
-                    double const p = (1. - ext)*val;                     // longwave.c:211
-                    I[s] = p + I[s]*ext;
-                    g += c2[s]*I[s];
-                }
-                fu[(uint64_t)j*nw] = g;
+                sink.put(j, false, stream_step(I, vl[u], [&](int s) { return ex[u][s]; }));
             }
         }
     }
@@ -392,23 +263,19 @@ __global__ __launch_bounds__(kSweepBlock) void lw_sweeps_kernel(GrtLwArgs a)
 
 extern "C" unsigned grt_solver_blocks(uint64_t nw)
 {
-    return (unsigned)((nw + kBlock - 1)/kBlock);
+    return (unsigned)((nw + kSolverBlock - 1)/kSolverBlock);
 }
 
 extern "C" int grt_launch_lw(void *stream, GrtSolverForm form, GrtLwArgs const *a, GrtCloudArgs const *c)
 {
-    bool const profile = form == GRT_SOLVER_PROFILE || form == GRT_SOLVER_ALLSKY_PROFILE;
-    bool const allsky = form == GRT_SOLVER_ALLSKY || form == GRT_SOLVER_ALLSKY_PROFILE;
-    bool const fused = form == GRT_SOLVER_FUSED || profile || allsky;
-    size_t const lds = profile ? sizeof(double)*2*(size_t)a->num_levels*(kBlock/64) : 0;
+    GrtFormKind const k = grt_form_kind(form);
+    size_t const lds = k.profile ? sizeof(double)*2*(size_t)a->num_levels*(kSolverBlock/64) : 0;
     uint64_t const cells = (uint64_t)(a->num_levels - 1)*a->nw;
     if (a->ncol < 1 || a->nw < 2 ||
-        (fused ? (a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr)
-               : (a->flux_up == nullptr || a->flux_down == nullptr)) ||
+        (k.fused ? (a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr)
+                 : (a->flux_up == nullptr || a->flux_down == nullptr)) ||
         (form == GRT_SOLVER_LAYERS && (a->layer_terms == nullptr || cells > 0xffffffffull*kTermsBlock)) ||
-        (profile && (a->num_levels < 2 || lds > 65536)) ||
-        (allsky && (c == nullptr || c->num_bands < 1 || c->band_liquid == nullptr || c->band_ice == nullptr ||
-                    c->thickness == nullptr || c->liquid == nullptr || c->ice == nullptr)))
+        (k.profile && (a->num_levels < 2 || lds > 65536)) || (k.allsky && !grt_cloud_args_ok(c)))
     {
         return (int)hipErrorInvalidValue;
     }
@@ -423,19 +290,19 @@ extern "C" int grt_launch_lw(void *stream, GrtSolverForm form, GrtLwArgs const *
                            dim3(kSweepBlock), 0, s, *a);
         break;
     case GRT_SOLVER_FUSED:
-        hipLaunchKernelGGL((lw_kernel<true, false>), grid, dim3(kBlock), 0, s, *a);
+        hipLaunchKernelGGL((lw_kernel<true, false>), grid, dim3(kSolverBlock), 0, s, *a);
         break;
     case GRT_SOLVER_CHAINS:
-        hipLaunchKernelGGL((lw_kernel<false, false>), grid, dim3(kBlock), 0, s, *a);
+        hipLaunchKernelGGL((lw_kernel<false, false>), grid, dim3(kSolverBlock), 0, s, *a);
         break;
     case GRT_SOLVER_PROFILE:
-        hipLaunchKernelGGL((lw_kernel<true, true>), grid, dim3(kBlock), lds, s, *a);
+        hipLaunchKernelGGL((lw_kernel<true, true>), grid, dim3(kSolverBlock), lds, s, *a);
         break;
     case GRT_SOLVER_ALLSKY:
-        hipLaunchKernelGGL((lw_kernel<true, false, true, GrtCloudArgs>), grid, dim3(kBlock), 0, s, *a, *c);
+        hipLaunchKernelGGL((lw_kernel<true, false, true, GrtCloudArgs>), grid, dim3(kSolverBlock), 0, s, *a, *c);
         break;
     case GRT_SOLVER_ALLSKY_PROFILE:
-        hipLaunchKernelGGL((lw_kernel<true, true, true, GrtCloudArgs>), grid, dim3(kBlock), lds, s, *a, *c);
+        hipLaunchKernelGGL((lw_kernel<true, true, true, GrtCloudArgs>), grid, dim3(kSolverBlock), lds, s, *a, *c);
         break;
     default:
         return (int)hipErrorInvalidValue;

@@ -31,7 +31,6 @@
 
 namespace {
 
-constexpr int kBlock = 128;
 constexpr double kMaxExpArg = 700.;   // grtcode_config.h:41
 
 struct LayerRT { double R, T, Tpure; };
@@ -155,22 +154,100 @@ __device__ __forceinline__ LayerProps layer_props(double omega, double g, double
     return p;
 }
 
+// The five properties of a layer as rows q, q + nw, .. q + 4 nw: Rdir, Tdir, Tpure, Rdif, Tdif (the fused form's park,
+// the layers form's layer_props)
+__device__ __forceinline__ void store_props(double *q, uint64_t nw, LayerProps const &p)
+{
+    q[0] = p.Rdir; q[nw] = p.Tdir; q[2*nw] = p.Tpure; q[3*nw] = p.Rdif; q[4*nw] = p.Tdif;
+}
+
+__device__ __forceinline__ LayerProps load_props(double const *q, uint64_t nw)
+{
+    LayerProps p;
+    p.Rdir = q[0]; p.Tdir = q[nw]; p.Tpure = q[2*nw]; p.Rdif = q[3*nw]; p.Tdif = q[4*nw];
+    return p;
+}
+
+// sweep 1 (shortwave.c:280-294), one layer up: the downward-beam reflectances at the layer's top from those at its bottom
+__device__ __forceinline__ void sweep1_step(LayerProps const &p, double &Rdir_dn, double &Rdif_dn)
+{
+    double const A = p.Tpure;
+    double const B = 1./(1. - p.Rdif*Rdif_dn);
+    double const ndir = p.Rdir + (A*Rdir_dn + (p.Tdir - A)*Rdif_dn)*p.Tdif*B;
+    double const ndif = p.Rdif + p.Tdif*p.Tdif*Rdif_dn*B;
+    Rdir_dn = ndir;
+    Rdif_dn = ndif;
+}
+
+// sweep 2 (shortwave.c:299-316) from the top: the direct and diffuse beams at level lev and R_dif_upward above it
+struct Sweep2
+{
+    double dir = 1.;
+    double dif = 0.;
+    double Rup2 = 0.;     // R_dif_upward[lev-2]
+    double Rup = 0.;      // R_dif_upward[lev-1]
+};
+
+// ... one layer down: layer lev - 1 takes the sweep to level lev
+__device__ __forceinline__ void sweep2_step(Sweep2 &s, LayerProps const &p, int lev)
+{
+    // R_dif_upward[lev-1]  (:299-306)
+    s.Rup2 = s.Rup;
+    if (lev == 1)
+    {
+        s.Rup = p.Rdif;
+    }
+    else
+    {
+        double const Bu = 1./(1. - p.Rdif*s.Rup2);
+        s.Rup = p.Rdif + p.Tdif*p.Tdif*s.Rup2*Bu;
+    }
+    if (lev > 1)
+    {
+        double const C = 1./(1. - p.Rdif*s.Rup2);
+        s.dif = (s.dir*p.Rdir*s.Rup2 + s.dif)*p.Tdif*C + s.dir*(p.Tdir - p.Tpure);
+    }
+    else
+    {
+        s.dif = s.dir*(p.Tdir - p.Tpure);
+    }
+    s.dir *= p.Tpure;
+}
+
+// The fluxes at a level (shortwave.c:318-329) from the beams that reach it, the reflectance Rup of what lies above it to
+// diffuse light from below, and the downward-beam reflectances rdir, rdif of what lies below it
+__device__ __forceinline__ void level_flux(double dir, double dif, double Rup, double rdir, double rdif, double &up,
+                                           double &dn)
+{
+    double const B = 1./(1. - rdif*Rup);
+    up = (dir*rdir + dif*rdif)*B;
+    dn = dir*(1. + rdir*Rup*B) + dif*B;
+}
+
+// ... scaled as shortwave.c:401-405 and :447-451 and handed to the sink
+template <typename Sink>
+__device__ __forceinline__ void put_level(Sink &sink, int lev, double up, double dn, double scale, double tsi)
+{
+    up *= scale;
+    dn *= scale;
+    sink.put(lev, false, tsi*up);
+    sink.put(lev, true, tsi*dn);
+}
+
 // FUSED: the clear-sky tail in one kernel -- tau, omega, g of a layer are formed in registers from tau_gas and the
-// Rayleigh optical depth (clear_sky_combine: the expressions and order of clear_sky_kernel, identical values), the
-// first sweep's reflectances are parked in a scratch block instead of the output rows, nothing spectral is written and
-// the six integrated output rows leave as per-block trapezoid partial sums.
+// Rayleigh optical depth (LayerOptics: identical values), the first sweep's reflectances are parked in a scratch block
+// instead of the output rows, nothing spectral is written and the six integrated output rows leave as per-block
+// trapezoid partial sums (LevelSink).
 // PROFILE (fused form only): the reference's two sweeps always (shortwave.c:280-329) -- the first parks the downward-beam
 // reflectances of EVERY level in rows 0 .. 2 V - 1 of the park block, the second produces up and down at every level and
-// sums each across the wave at once (wave_row_sum, as lw_kernel<true, true>); the block's sums of the 2 V rows go to
-// partials[(c*2 V + r)*nblocks + block], r = level (up), V + level (down).
-// ALLSKY (fused forms, six-row or profile): the liquid and ice cloud objects join per layer (GrtCloudArgs), as in lw_kernel;
+// the sink sums each across the wave at once (as lw_kernel<true, true>).
+// ALLSKY (fused forms, six-row or profile): the liquid and ice cloud objects join per layer (LayerOptics), as in lw_kernel;
 // the one-sweep and two-sweep rule is the form's own.  props_of is the only place that reads the cloud tables, and the
 // fused forms call it in their first (or only) sweep: the two-sweep forms' second sweep reads the parked properties.
 template <bool FUSED, bool PROFILE, bool ALLSKY = false, typename... Clouds>
-__global__ __launch_bounds__(kBlock) void sw_kernel(GrtSwArgs a, Clouds... clouds)
+__global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Clouds... clouds)
 {
-    GrtCloudArgs const cl = cloud_args(clouds...);      // (ALLSKY: the one GrtCloudArgs argument)
-    uint64_t const i = (uint64_t)blockIdx.x*kBlock + threadIdx.x;
+    uint64_t const i = (uint64_t)blockIdx.x*kSolverBlock + threadIdx.x;
     int const col = blockIdx.y;
     bool const live = i < a.nw;
     if (!FUSED && !live)
@@ -181,11 +258,9 @@ __global__ __launch_bounds__(kBlock) void sw_kernel(GrtSwArgs a, Clouds... cloud
     int const V = a.num_levels;
     int const L = V - 1;
     uint64_t const nw = a.nw;
-    double const *tau = (FUSED ? a.tau_gas : a.tau) + (uint64_t)col*a.optics_stride + ii;
+    double const *tau = a.tau + (uint64_t)col*a.optics_stride + ii;
     double const *omega = FUSED ? nullptr : a.omega + (uint64_t)col*a.optics_stride + ii;
     double const *g = FUSED ? nullptr : a.g + (uint64_t)col*a.optics_stride + ii;
-    double const *nl = FUSED ? a.n_layer + (uint64_t)col*L : nullptr;
-    double const w = FUSED ? a.w0 + ii*a.dw : 0.;
     double const mu_dir = a.mu_dir[col];
     double const mu_dif = a.mu_dif;
     // where the first sweep parks R_dir_downward / R_dif_downward of every level
@@ -197,47 +272,18 @@ __global__ __launch_bounds__(kBlock) void sw_kernel(GrtSwArgs a, Clouds... cloud
     // divisions a layer, which is what this kernel's time is made of)
     double *pp = FUSED ? a.park + ((uint64_t)col*park_rows + 2*(uint64_t)V)*nw + ii : nullptr;
     int const user = a.user_level;
-    double out[6] = {0., 0., 0., 0., 0., 0.};     // up TOA, up surface, up user, down TOA, down surface, down user
-    extern __shared__ double level_sums[];        // PROFILE: [2 V][kBlock/64]
-    double const pwt = !PROFILE || !live ? 0. : ((i == 0 || i + 1 == nw) ? 0.5*a.dw : a.dw);
-
-    // (the gas-optics launch left the spectral tables' part of tau to this kernel: a table entry read once per point)
-    PointContinua pc;
-    long long const blk_lo = (long long)blockIdx.x*kBlock, blk_hi = blk_lo + kBlock < (long long)nw ? blk_lo + kBlock : (long long)nw;
-    bool const add_continua = FUSED && a.add_continua;
-    double const *cstate = a.continua.colstate + (uint64_t)col*a.continua.stride;
-    if (add_continua)
-    {
-        continua_load(a.continua, nw, ii, blk_lo, blk_hi, pc);
-    }
-    int const band_l = ALLSKY ? cl.band_liquid[ii] : -1, band_i = ALLSKY ? cl.band_ice[ii] : -1;
-    uint64_t const ctab = ALLSKY ? (uint64_t)col*3*(uint64_t)cl.num_bands*L : 0;
+    LevelSink<FUSED, PROFILE> sink(a, col, i, live);
+    LayerOptics<FUSED, ALLSKY> const optics(a, cloud_args(clouds...), col, ii);   // (fused forms)
 
     auto props_of = [&](int j) -> LayerProps
     {
-        uint64_t const o = (uint64_t)j*nw;
         if (FUSED)
         {
             double t, om, gg;
-            double tg = tau[o];
-            if (add_continua)
-            {
-                tg = continua_add(a.continua, pc, cstate, j, nw, ii, blk_lo, blk_hi, tg);
-            }
-            if constexpr (ALLSKY)
-            {
-                double const th = cl.thickness[(uint64_t)col*L + j];
-                double lt, lo, lg, it, io, ig;
-                cloud_layer(cl.liquid + ctab, cl.num_bands, L, band_l, j, th, lt, lo, lg);
-                cloud_layer(cl.ice + ctab, cl.num_bands, L, band_i, j, th, it, io, ig);
-                allsky_combine(tg, rayleigh_tau(w, nl[j]), lt, lo, lg, it, io, ig, t, om, gg);
-            }
-            else
-            {
-                clear_sky_combine(tg, rayleigh_tau(w, nl[j]), t, om, gg);
-            }
+            optics.at(j, t, om, gg);
             return layer_props(om, gg, t, mu_dir, mu_dif);
         }
+        uint64_t const o = (uint64_t)j*nw;
         return layer_props(omega[o], g[o], tau[o], mu_dir, mu_dif);
     };
 
@@ -268,24 +314,12 @@ __global__ __launch_bounds__(kBlock) void sw_kernel(GrtSwArgs a, Clouds... cloud
         }
         double const scale = a.solar[ii]*mu_dir;
         double const tsi = a.tsi[col];
-        double const rdir = a.alb_dir[(uint64_t)col*a.alb_stride + ii], rdif = a.alb_dif[(uint64_t)col*a.alb_stride + ii];
-        double const B = 1./(1. - rdif*Ru);
-        double const up_s = (dir*rdir + dif*rdif)*B;                                // :318-329 at the surface
-        double const dn_s = dir*(1. + rdir*Ru*B) + dif*B;
-        double const up_t = Rd + Tu*up_s;
-        out[0] = tsi*(up_t*scale);
-        out[3] = tsi*(1.*scale);
-        out[1] = tsi*(up_s*scale);
-        out[4] = tsi*(dn_s*scale);
-        out[2] = user == 0 ? out[0] : (user == L ? out[1] : 0.);
-        out[5] = user == 0 ? out[3] : (user == L ? out[4] : 0.);
-        double const wt = !live ? 0. : ((i == 0 || i + 1 == nw) ? 0.5*a.dw : a.dw);
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-        {
-            out[k] *= wt;
-        }
-        block_partials<6, kBlock>(out, a.partials, (uint64_t)col*6, gridDim.x, blockIdx.x);
+        double up_s, dn_s;                                                          // :318-329 at the surface
+        level_flux(dir, dif, Ru, a.alb_dir[(uint64_t)col*a.alb_stride + ii], a.alb_dif[(uint64_t)col*a.alb_stride + ii],
+                   up_s, dn_s);
+        put_level(sink, 0, Rd + Tu*up_s, 1., scale, tsi);
+        put_level(sink, L, up_s, dn_s, scale, tsi);
+        sink.finish(a);
         return;
     }
 
@@ -309,15 +343,9 @@ __global__ __launch_bounds__(kBlock) void sw_kernel(GrtSwArgs a, Clouds... cloud
         LayerProps const p = props_of(j);
         if (FUSED)
         {
-            double *q = pp + (uint64_t)(5*j)*nw;
-            q[0] = p.Rdir; q[nw] = p.Tdir; q[2*nw] = p.Tpure; q[3*nw] = p.Rdif; q[4*nw] = p.Tdif;
+            store_props(pp + (uint64_t)(5*j)*nw, nw, p);
         }
-        double const A = p.Tpure;
-        double const B = 1./(1. - p.Rdif*Rdif_dn);
-        double const ndir = p.Rdir + (A*Rdir_dn + (p.Tdir - A)*Rdif_dn)*p.Tdif*B;
-        double const ndif = p.Rdif + p.Tdif*p.Tdif*Rdif_dn*B;
-        Rdir_dn = ndir;
-        Rdif_dn = ndif;
+        sweep1_step(p, Rdir_dn, Rdif_dn);
         if (FUSED && !PROFILE)
         {
             user_rdir = j == user ? Rdir_dn : user_rdir;
@@ -333,111 +361,23 @@ __global__ __launch_bounds__(kBlock) void sw_kernel(GrtSwArgs a, Clouds... cloud
     // sweep 2: shortwave.c:299-329 fused, then the scalings of :401-405 and :447-451
     double const scale = a.solar[ii]*mu_dir;
     double const tsi = a.tsi[col];
-    double dir_beam = 1.;
-    double dif_beam = 0.;
-    {
-        double up = dir_beam*(FUSED ? Rdir_dn : fu[0]);       // R[0] = dir_beam*R_dir_downward[0]
-        double dn = dir_beam;             // T[0]
-        up *= scale;
-        dn *= scale;
-        if (PROFILE)
-        {
-            wave_row_sum<kBlock>((tsi*up)*pwt, level_sums, 0);
-            wave_row_sum<kBlock>((tsi*dn)*pwt, level_sums, V);
-        }
-        else if (FUSED)
-        {
-            out[0] = tsi*up;
-            out[3] = tsi*dn;
-            out[2] = user == 0 ? tsi*up : out[2];
-            out[5] = user == 0 ? tsi*dn : out[5];
-        }
-        else
-        {
-            fu[0] = tsi*up;
-            fd[0] = tsi*dn;
-        }
-    }
-    double Rup_prev2 = 0.;    // R_dif_upward[lev-2]
-    double Rup_prev = 0.;     // R_dif_upward[lev-1]
+    Sweep2 s;
+    put_level(sink, 0, s.dir*(FUSED ? Rdir_dn : fu[0]), s.dir, scale, tsi);   // R[0] = dir_beam*R_dir_downward[0], T[0]
     for (int lev = 1; lev < V; ++lev)
     {
-        LayerProps p;                              // layer lev-1
-        if (FUSED)
+        sweep2_step(s, FUSED ? load_props(pp + (uint64_t)(5*(lev - 1))*nw, nw) : props_of(lev - 1), lev);
+        if (!sink.wanted(lev))
         {
-            double const *q = pp + (uint64_t)(5*(lev - 1))*nw;
-            p.Rdir = q[0]; p.Tdir = q[nw]; p.Tpure = q[2*nw]; p.Rdif = q[3*nw]; p.Tdif = q[4*nw];
+            continue;
         }
-        else
-        {
-            p = props_of(lev - 1);
-        }
-        // R_dif_upward[lev-1]  (:299-306)
-        Rup_prev2 = Rup_prev;
-        if (lev == 1)
-        {
-            Rup_prev = p.Rdif;
-        }
-        else
-        {
-            double const Bu = 1./(1. - p.Rdif*Rup_prev2);
-            Rup_prev = p.Rdif + p.Tdif*p.Tdif*Rup_prev2*Bu;
-        }
-        if (lev > 1)
-        {
-            double const C = 1./(1. - p.Rdif*Rup_prev2);
-            dif_beam = (dir_beam*p.Rdir*Rup_prev2 + dif_beam)*p.Tdif*C + dir_beam*(p.Tdir - p.Tpure);
-        }
-        else
-        {
-            dif_beam = dir_beam*(p.Tdir - p.Tpure);
-        }
-        dir_beam *= p.Tpure;
         uint64_t const ol = (uint64_t)lev*nw;
-        if (FUSED && !PROFILE && lev != L && lev != user)
-        {
-            continue;                     // (no flux of this level is asked for)
-        }
         double const rdir = FUSED && !PROFILE ? (lev == L ? surf_rdir : user_rdir) : fu[ol];   // R_dir_downward[lev] of sweep 1
         double const rdif = FUSED && !PROFILE ? (lev == L ? surf_rdif : user_rdif) : fd[ol];   // R_dif_downward[lev]
-        double const B = 1./(1. - rdif*Rup_prev);
-        double up = (dir_beam*rdir + dif_beam*rdif)*B;
-        double dn = dir_beam*(1. + rdir*Rup_prev*B) + dif_beam*B;
-        up *= scale;
-        dn *= scale;
-        if (PROFILE)
-        {
-            wave_row_sum<kBlock>((tsi*up)*pwt, level_sums, lev);
-            wave_row_sum<kBlock>((tsi*dn)*pwt, level_sums, V + lev);
-        }
-        else if (FUSED)
-        {
-            out[1] = lev == L ? tsi*up : out[1];
-            out[4] = lev == L ? tsi*dn : out[4];
-            out[2] = lev == user ? tsi*up : out[2];
-            out[5] = lev == user ? tsi*dn : out[5];
-        }
-        else
-        {
-            fu[ol] = tsi*up;
-            fd[ol] = tsi*dn;
-        }
+        double up, dn;
+        level_flux(s.dir, s.dif, s.Rup, rdir, rdif, up, dn);
+        put_level(sink, lev, up, dn, scale, tsi);
     }
-    if (PROFILE)
-    {
-        block_row_partials<kBlock>(level_sums, 2*V, a.partials, (uint64_t)col*2*V, gridDim.x, blockIdx.x);
-    }
-    else if (FUSED)
-    {
-        // driver.c:302-326: sum 0.5 (f_i + f_{i+1}) dw over the grid = sum weight_i f_i
-        double const wt = !live ? 0. : ((i == 0 || i + 1 == nw) ? 0.5*a.dw : a.dw);
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-        {
-            out[k] *= wt;
-        }
-        block_partials<6, kBlock>(out, a.partials, (uint64_t)col*6, gridDim.x, blockIdx.x);
-    }
+    sink.finish(a);
 }
 
 // ---- spectral form of few columns: the layer properties first, by one thread per (layer, wavenumber) ----
@@ -465,9 +405,8 @@ __global__ __launch_bounds__(kPropsBlock) void sw_props_kernel(GrtSwArgs a)
     uint64_t const j = o/nw;
     uint64_t const i = o - j*nw;
     uint64_t const at = (uint64_t)col*a.optics_stride + o;
-    LayerProps const p = layer_props(a.omega[at], a.g[at], a.tau[at], a.mu_dir[col], a.mu_dif);
-    double *q = a.layer_props + ((uint64_t)col*5*(uint64_t)L + 5*j)*nw + i;
-    q[0] = p.Rdir; q[nw] = p.Tdir; q[2*nw] = p.Tpure; q[3*nw] = p.Rdif; q[4*nw] = p.Tdif;
+    store_props(a.layer_props + ((uint64_t)col*5*(uint64_t)L + 5*j)*nw + i, nw,
+                layer_props(a.omega[at], a.g[at], a.tau[at], a.mu_dir[col], a.mu_dif));
 }
 
 __global__ __launch_bounds__(kSweepBlock) void sw_sweeps_kernel(GrtSwArgs a)
@@ -485,12 +424,10 @@ __global__ __launch_bounds__(kSweepBlock) void sw_sweeps_kernel(GrtSwArgs a)
     double const *pp = a.layer_props + (uint64_t)col*5*(uint64_t)L*nw + i;
     double *fu = a.flux_up + (uint64_t)col*a.flux_stride + i;
     double *fd = a.flux_down + (uint64_t)col*a.flux_stride + i;
+    LevelSink<false, false> sink(a, col, i, true);
     auto load = [&](int j) -> LayerProps
     {
-        double const *q = pp + (uint64_t)(5*j)*nw;
-        LayerProps p;
-        p.Rdir = q[0]; p.Tdir = q[nw]; p.Tpure = q[2*nw]; p.Rdif = q[3*nw]; p.Tdif = q[4*nw];
-        return p;
+        return load_props(pp + (uint64_t)(5*j)*nw, nw);
     };
 
     // sweep 1: shortwave.c:280-294 (as in sw_kernel<false, false>: the downward-beam reflectances are parked in the output rows)
@@ -520,14 +457,8 @@ __global__ __launch_bounds__(kSweepBlock) void sw_sweeps_kernel(GrtSwArgs a)
             int const j = jb - u;
             if (j >= 0)
             {
-                LayerProps const p = pr[u];
                 uint64_t const o = (uint64_t)j*nw;
-                double const A = p.Tpure;
-                double const B = 1./(1. - p.Rdif*Rdif_dn);
-                double const ndir = p.Rdir + (A*Rdir_dn + (p.Tdir - A)*Rdif_dn)*p.Tdif*B;
-                double const ndif = p.Rdif + p.Tdif*p.Tdif*Rdif_dn*B;
-                Rdir_dn = ndir;
-                Rdif_dn = ndif;
+                sweep1_step(pr[u], Rdir_dn, Rdif_dn);
                 fu[o] = Rdir_dn;
                 fd[o] = Rdif_dn;
             }
@@ -542,18 +473,9 @@ __global__ __launch_bounds__(kSweepBlock) void sw_sweeps_kernel(GrtSwArgs a)
     // sweep 2: shortwave.c:299-329 fused, then the scalings of :401-405 and :447-451
     double const scale = a.solar[i]*mu_dir;
     double const tsi = a.tsi[col];
-    double dir_beam = 1.;
-    double dif_beam = 0.;
-    {
-        double up = dir_beam*Rdir_dn;     // R[0] = dir_beam*R_dir_downward[0] (the value sweep 1 has just stored in fu[0])
-        double dn = dir_beam;             // T[0]
-        up *= scale;
-        dn *= scale;
-        fu[0] = tsi*up;
-        fd[0] = tsi*dn;
-    }
-    double Rup_prev2 = 0.;    // R_dif_upward[lev-2]
-    double Rup_prev = 0.;     // R_dif_upward[lev-1]
+    Sweep2 s;
+    put_level(sink, 0, s.dir*Rdir_dn, s.dir, scale, tsi);   // R[0] = dir_beam*R_dir_downward[0] (the value sweep 1 has
+                                                             // just stored in fu[0]), T[0] = dir_beam
     double rd[kSweepChunk], rf[kSweepChunk], nrd[kSweepChunk], nrf[kSweepChunk];
 #pragma unroll
     for (int u = 0; u < kSweepChunk; ++u)
@@ -579,38 +501,10 @@ __global__ __launch_bounds__(kSweepBlock) void sw_sweeps_kernel(GrtSwArgs a)
             int const lev = lb + u;
             if (lev < V)
             {
-                LayerProps const p = pr[u];        // layer lev-1
-                // R_dif_upward[lev-1]  (:299-306)
-                Rup_prev2 = Rup_prev;
-                if (lev == 1)
-                {
-                    Rup_prev = p.Rdif;
-                }
-                else
-                {
-                    double const Bu = 1./(1. - p.Rdif*Rup_prev2);
-                    Rup_prev = p.Rdif + p.Tdif*p.Tdif*Rup_prev2*Bu;
-                }
-                if (lev > 1)
-                {
-                    double const C = 1./(1. - p.Rdif*Rup_prev2);
-                    dif_beam = (dir_beam*p.Rdir*Rup_prev2 + dif_beam)*p.Tdif*C + dir_beam*(p.Tdir - p.Tpure);
-                }
-                else
-                {
-                    dif_beam = dir_beam*(p.Tdir - p.Tpure);
-                }
-                dir_beam *= p.Tpure;
-                uint64_t const ol = (uint64_t)lev*nw;
-                double const rdir = rd[u];
-                double const rdif = rf[u];
-                double const B = 1./(1. - rdif*Rup_prev);
-                double up = (dir_beam*rdir + dif_beam*rdif)*B;
-                double dn = dir_beam*(1. + rdir*Rup_prev*B) + dif_beam*B;
-                up *= scale;
-                dn *= scale;
-                fu[ol] = tsi*up;
-                fd[ol] = tsi*dn;
+                sweep2_step(s, pr[u], lev);        // layer lev-1
+                double up, dn;
+                level_flux(s.dir, s.dif, s.Rup, rd[u], rf[u], up, dn);
+                put_level(sink, lev, up, dn, scale, tsi);
             }
         }
 #pragma unroll
@@ -627,25 +521,21 @@ __global__ __launch_bounds__(kSweepBlock) void sw_sweeps_kernel(GrtSwArgs a)
 
 extern "C" int grt_launch_sw(void *stream, GrtSolverForm form, GrtSwArgs const *a, GrtCloudArgs const *c)
 {
-    bool const profile = form == GRT_SOLVER_PROFILE || form == GRT_SOLVER_ALLSKY_PROFILE;
-    bool const allsky = form == GRT_SOLVER_ALLSKY || form == GRT_SOLVER_ALLSKY_PROFILE;
-    bool const fused = form == GRT_SOLVER_FUSED || profile || allsky;
-    bool const park = profile || (fused && !grt_sw_one_sweep(a));
-    size_t const lds = profile ? sizeof(double)*2*(size_t)a->num_levels*(kBlock/64) : 0;
+    GrtFormKind const k = grt_form_kind(form);
+    bool const park = k.profile || (k.fused && !grt_sw_one_sweep(a));
+    size_t const lds = k.profile ? sizeof(double)*2*(size_t)a->num_levels*(kSolverBlock/64) : 0;
     uint64_t const cells = (uint64_t)(a->num_levels - 1)*a->nw;
     if (a->ncol < 1 || a->nw < 2 ||
-        (fused ? (a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr || (park && a->park == nullptr))
-               : (a->flux_up == nullptr || a->flux_down == nullptr)) ||
+        (k.fused ? (a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr || (park && a->park == nullptr))
+                 : (a->flux_up == nullptr || a->flux_down == nullptr)) ||
         (form == GRT_SOLVER_LAYERS && (a->layer_props == nullptr || cells > 0xffffffffull*kPropsBlock ||
                                        a->omega == nullptr || a->g == nullptr)) ||
-        (profile && (a->num_levels < 2 || lds > 65536)) ||
-        (allsky && (c == nullptr || c->num_bands < 1 || c->band_liquid == nullptr || c->band_ice == nullptr ||
-                    c->thickness == nullptr || c->liquid == nullptr || c->ice == nullptr)))
+        (k.profile && (a->num_levels < 2 || lds > 65536)) || (k.allsky && !grt_cloud_args_ok(c)))
     {
         return (int)hipErrorInvalidValue;
     }
     hipStream_t const s = (hipStream_t)stream;
-    dim3 const grid((unsigned)((a->nw + kBlock - 1)/kBlock), a->ncol, 1);   // == grt_solver_blocks(nw): same kBlock
+    dim3 const grid((unsigned)((a->nw + kSolverBlock - 1)/kSolverBlock), a->ncol, 1);
     switch (form)
     {
     case GRT_SOLVER_LAYERS:
@@ -655,19 +545,19 @@ extern "C" int grt_launch_sw(void *stream, GrtSolverForm form, GrtSwArgs const *
                            dim3(kSweepBlock), 0, s, *a);
         break;
     case GRT_SOLVER_FUSED:
-        hipLaunchKernelGGL((sw_kernel<true, false>), grid, dim3(kBlock), 0, s, *a);
+        hipLaunchKernelGGL((sw_kernel<true, false>), grid, dim3(kSolverBlock), 0, s, *a);
         break;
     case GRT_SOLVER_CHAINS:
-        hipLaunchKernelGGL((sw_kernel<false, false>), grid, dim3(kBlock), 0, s, *a);
+        hipLaunchKernelGGL((sw_kernel<false, false>), grid, dim3(kSolverBlock), 0, s, *a);
         break;
     case GRT_SOLVER_PROFILE:
-        hipLaunchKernelGGL((sw_kernel<true, true>), grid, dim3(kBlock), lds, s, *a);
+        hipLaunchKernelGGL((sw_kernel<true, true>), grid, dim3(kSolverBlock), lds, s, *a);
         break;
     case GRT_SOLVER_ALLSKY:
-        hipLaunchKernelGGL((sw_kernel<true, false, true, GrtCloudArgs>), grid, dim3(kBlock), 0, s, *a, *c);
+        hipLaunchKernelGGL((sw_kernel<true, false, true, GrtCloudArgs>), grid, dim3(kSolverBlock), 0, s, *a, *c);
         break;
     case GRT_SOLVER_ALLSKY_PROFILE:
-        hipLaunchKernelGGL((sw_kernel<true, true, true, GrtCloudArgs>), grid, dim3(kBlock), lds, s, *a, *c);
+        hipLaunchKernelGGL((sw_kernel<true, true, true, GrtCloudArgs>), grid, dim3(kSolverBlock), lds, s, *a, *c);
         break;
     default:
         return (int)hipErrorInvalidValue;

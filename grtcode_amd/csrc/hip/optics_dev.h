@@ -1,5 +1,6 @@
 // optics_dev.h -- device helpers shared by the optics and solver kernels: Rayleigh optical depth, the two-object
-// clear-sky combination, and the block-level trapezoid partial sums of the fused (integrated-output) solvers.
+// clear-sky combination, the fused solvers' layer optics (LayerOptics), where a solver's level fluxes go (LevelSink),
+// and the block-level trapezoid partial sums of the fused (integrated-output) solvers.
 #ifndef GRT_OPTICS_DEV_H_
 #define GRT_OPTICS_DEV_H_
 #include <hip/hip_runtime.h>
@@ -8,6 +9,9 @@
 #include "exp_pair.h"
 
 #pragma clang fp contract(off)
+
+// workgroup of the solvers' chain and fused forms (grt_solver_blocks: the partial sums of one launch)
+constexpr int kSolverBlock = 128;
 
 // shortwave/src/rayleigh.c:38-39
 __device__ __forceinline__ double rayleigh_tau(double w, double n)
@@ -229,5 +233,184 @@ __device__ __forceinline__ void block_row_partials(double const *lds, int nrows,
         partials[(row_base + r)*nblocks + block] = s;
     }
 }
+
+// driver.c:302-326: sum 0.5 (f_i + f_{i+1}) dw over the grid = sum weight_i f_i -- dw, dw/2 at both ends, and 0 for
+// the idle lanes of the last block
+__device__ __forceinline__ double trapezoid_weight(uint64_t i, uint64_t nw, double dw, bool live)
+{
+    return !live ? 0. : ((i == 0 || i + 1 == nw) ? 0.5*dw : dw);
+}
+
+// The fused forms' layer optics: tau, omega, g of (layer j, point ii) formed in registers from tau_gas -- the spectral
+// tables' part added if the gas-optics launch left it to the solver (a table entry read once per point), Rayleigh, and
+// clear_sky_combine (the expressions and order of clear_sky_kernel: identical values).  ALLSKY: the liquid and ice cloud
+// objects join (GrtCloudArgs): the point reads its two band indices once, each layer forms the two objects from the
+// column's band tables and allsky_combine adds the four.  Built once per thread from the fields both solvers' argument
+// structs carry; FUSED false (the spectral forms, which read their optics): nothing is loaded.
+template <bool FUSED, bool ALLSKY>
+struct LayerOptics
+{
+    GrtContinua const *c;
+    double const *tau, *nl, *cstate;
+    double w;
+    uint64_t nw, ii;
+    long long blk_lo, blk_hi;
+    bool add_continua;
+    PointContinua pc;
+    GrtCloudArgs cl;
+    int L, col, band_l, band_i;
+    uint64_t ctab;
+
+    template <typename Args>
+    __device__ __forceinline__ LayerOptics(Args const &a, GrtCloudArgs const &cl_, int col_, uint64_t ii_)
+    {
+        L = a.num_levels - 1;
+        col = col_;
+        ii = ii_;
+        nw = a.nw;
+        w = a.w0 + ii*a.dw;
+        tau = a.tau_gas + (uint64_t)col*a.optics_stride + ii;
+        nl = a.n_layer + (uint64_t)col*L;
+        c = &a.continua;
+        blk_lo = (long long)blockIdx.x*kSolverBlock;
+        blk_hi = blk_lo + kSolverBlock < (long long)nw ? blk_lo + kSolverBlock : (long long)nw;
+        add_continua = FUSED && a.add_continua;
+        cstate = c->colstate + (uint64_t)col*c->stride;
+        if (add_continua)
+        {
+            continua_load(*c, nw, ii, blk_lo, blk_hi, pc);
+        }
+        cl = cl_;
+        band_l = ALLSKY ? cl.band_liquid[ii] : -1;
+        band_i = ALLSKY ? cl.band_ice[ii] : -1;
+        ctab = ALLSKY ? (uint64_t)col*3*(uint64_t)cl.num_bands*L : 0;
+    }
+
+    __device__ __forceinline__ void at(int j, double &t, double &om, double &gg) const
+    {
+        double tg = tau[(uint64_t)j*nw];
+        if (add_continua)
+        {
+            tg = continua_add(*c, pc, cstate, j, nw, ii, blk_lo, blk_hi, tg);
+        }
+        if constexpr (ALLSKY)
+        {
+            double const th = cl.thickness[(uint64_t)col*L + j];
+            double lt, lo, lg, it, io, ig;
+            cloud_layer(cl.liquid + ctab, cl.num_bands, L, band_l, j, th, lt, lo, lg);
+            cloud_layer(cl.ice + ctab, cl.num_bands, L, band_i, j, th, it, io, ig);
+            allsky_combine(tg, rayleigh_tau(w, nl[j]), lt, lo, lg, it, io, ig, t, om, gg);
+        }
+        else
+        {
+            clear_sky_combine(tg, rayleigh_tau(w, nl[j]), t, om, gg);
+        }
+    }
+};
+
+// Where a solver's level fluxes go, level lev top first.  Spectral forms (FUSED false): the rows flux_up / flux_down
+// [V][nw] at this thread's point.  Fused form: the six integrated output rows in registers (up TOA, up surface, up user,
+// down TOA, down surface, down user) and, at finish(), their trapezoid partial sums (block_partials).  PROFILE (fused
+// form only): every level's upward and downward flux leaves instead, 2 V rows per column: each level's weighted value is
+// summed across the wave where the sweep produces it, the waves' sums wait in dynamic LDS (2 V x kSolverBlock/64
+// doubles) and finish() stores the block's sums at partials[(c*2 V + r)*nblocks + block], r = level (up), V + level
+// (down).  Same association as block_partials: the six-row form's rows come out the same to the bit.
+template <bool FUSED, bool PROFILE>
+struct LevelSink
+{
+    double *fu, *fd;            // spectral forms: flux_up / flux_down at this thread's point
+    uint64_t nw, i;
+    int V, user, col;
+    double pwt;                 // PROFILE: this point's trapezoid weight
+    bool live;
+    double out[6];
+
+    template <typename Args>
+    __device__ __forceinline__ LevelSink(Args const &a, int col_, uint64_t i_, bool live_)
+    {
+        col = col_;
+        i = i_;
+        live = live_;
+        nw = a.nw;
+        V = a.num_levels;
+        user = a.user_level;
+        fu = FUSED ? nullptr : a.flux_up + (uint64_t)col*a.flux_stride + i;
+        fd = FUSED ? nullptr : a.flux_down + (uint64_t)col*a.flux_stride + i;
+        pwt = PROFILE ? trapezoid_weight(i, nw, a.dw, live) : 0.;
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+        {
+            out[k] = 0.;
+        }
+    }
+
+    static __device__ __forceinline__ double *level_sums()
+    {
+        extern __shared__ double level_sums_[];     // PROFILE: [2 V][kSolverBlock/64]
+        return level_sums_;
+    }
+
+    // whether a flux of level lev leaves the kernel
+    __device__ __forceinline__ bool wanted(int lev) const
+    {
+        return !FUSED || PROFILE || lev == 0 || lev == V - 1 || lev == user;
+    }
+
+    // level lev's upward (down false) or downward flux at this point is x
+    __device__ __forceinline__ void put(int lev, bool down, double x)
+    {
+        if (PROFILE)
+        {
+            wave_row_sum<kSolverBlock>(x*pwt, level_sums(), (down ? V : 0) + lev);
+        }
+        else if (FUSED)
+        {
+            int const k = down ? 3 : 0;
+            out[k] = lev == 0 ? x : out[k];
+            out[k + 1] = lev + 1 == V ? x : out[k + 1];
+            out[k + 2] = lev == user ? x : out[k + 2];
+        }
+        else
+        {
+            (down ? fd : fu)[(uint64_t)lev*nw] = x;
+        }
+    }
+
+    // ... is 0 at every point (its sums are 0 whatever the weights)
+    __device__ __forceinline__ void put_zero(int lev, bool down)
+    {
+        if (PROFILE)
+        {
+            if ((threadIdx.x & 63) == 0)
+            {
+                level_sums()[((down ? V : 0) + lev)*(kSolverBlock/64) + (threadIdx.x >> 6)] = 0.;
+            }
+        }
+        else
+        {
+            put(lev, down, 0.);
+        }
+    }
+
+    // (the fused forms' partials and weights are read here, where the kernel ends)
+    template <typename Args>
+    __device__ __forceinline__ void finish(Args const &a)
+    {
+        if (PROFILE)
+        {
+            block_row_partials<kSolverBlock>(level_sums(), 2*V, a.partials, (uint64_t)col*2*V, gridDim.x, blockIdx.x);
+        }
+        else if (FUSED)
+        {
+            double const wt = trapezoid_weight(i, nw, a.dw, live);
+#pragma unroll
+            for (int k = 0; k < 6; ++k)
+            {
+                out[k] *= wt;
+            }
+            block_partials<6, kSolverBlock>(out, a.partials, (uint64_t)col*6, gridDim.x, blockIdx.x);
+        }
+    }
+};
 
 #endif

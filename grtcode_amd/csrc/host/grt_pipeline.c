@@ -491,13 +491,13 @@ static int park_block(GrtPipeline_t *p, GrtBand *b)
 static int band_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtSolverForm form, int defer,
                        GrtContinua const *continua, GrtCloudArgs const *clouds, double *partials)
 {
-    int const fused = form != GRT_SOLVER_CHAINS;
+    GrtFormKind const k = grt_form_kind(form);
     void *s = grt_dev_stream(p->device);
     int slot, krc;
     if (bi == 0)
     {
         GrtLwArgs a;
-        lw_args(p, b, C, fused, defer, continua, &a);
+        lw_args(p, b, C, k.fused, defer, continua, &a);
         a.partials = partials;
         slot = grt_profile_begin(s, clouds ? 8 : 3);
         krc = grt_launch_lw(s, form, &a, clouds);
@@ -505,9 +505,9 @@ static int band_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtSolverFor
     else
     {
         GrtSwArgs a;
-        sw_args(p, b, C, fused, defer, continua, &a);
+        sw_args(p, b, C, k.fused, defer, continua, &a);
         a.partials = partials;
-        if (form == GRT_SOLVER_PROFILE || form == GRT_SOLVER_ALLSKY_PROFILE || (fused && !grt_sw_one_sweep(&a)))
+        if (k.profile || (k.fused && !grt_sw_one_sweep(&a)))
         {
             GRT_TRY(park_block(p, b));
         }
