@@ -482,8 +482,7 @@ static int launch_sweep_columns(GasOptics_t *go, int ncol, double *tau_dev, uint
     {
         GRT_TRY(grt_dev_alloc(go->device, (void **)&im->sweep_scratch, sizeof(double)*8*(size_t)L*nmax));
     }
-    GRT_TRY(grt_dev_upload(go->device, im->colstate_d, im->colstate_h, sizeof(double)*im->layout.stride*ncol, s));
-    GRT_TRY(grt_dev_event_record(go->device, &im->colstate_uploaded, s));
+    GRT_TRY(grt_gas_optics_upload_states(go, ncol));
     GrtSweepBins bins = {go->bins.w0, go->bins.wres, go->bins.num_wpoints, go->bins.n, go->bins.ppb,
                          go->bins.do_interp, go->bins.do_last_interp, go->bins.w, go->bins.tau, go->bins.l, go->bins.r};
     int const method = go->optical_depth_method == wavenumber_sweep ? 0 : 1;
@@ -601,10 +600,7 @@ int grt_gas_launch_columns(GasOptics_t *go, int ncol, double *tau_dev, uint64_t 
     {
         return launch_sweep_columns(go, ncol, tau_dev, tau_col_stride);
     }
-    void *s = grt_dev_stream(go->device);
-    GRT_TRY(grt_dev_upload(go->device, im->colstate_d, im->colstate_h,
-                           sizeof(double)*im->layout.stride*ncol, s));
-    GRT_TRY(grt_dev_event_record(go->device, &im->colstate_uploaded, s));
+    GRT_TRY(grt_gas_optics_upload_states(go, ncol));
     LaunchPlan p;
     plan(go, ncol, &p);
     int group = ncol;

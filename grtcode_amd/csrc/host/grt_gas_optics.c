@@ -1,16 +1,13 @@
-/* grt_gas_optics.c -- GasOptics_t: line lists, spectral tables, per-column prologue and
- * the launch of the line-by-line kernel.
+/* grt_gas_optics.c -- GasOptics_t: molecules, CFCs and CIAs, spectral tables, the per-column prologue and the entry
+ * points that compute optical depths (the launches themselves: grt_gas_launch.c).
  *
- * Contract: gas-optics/src/gas_optics.h:99-180 (gas_optics.c:51-464), the column
- * sequencing of launch.c:40-226, the HITRAN reader parse_HITRAN_file.c:224-413 and the
+ * Contract: gas-optics/src/gas_optics.h:99-180 (gas_optics.c:51-464), the column sequencing of launch.c:40-226 and the
  * table loaders water_vapor_continuum.c:32-122, ozone_continuum.c:31-88, cfcs.c:30-158,
- * collision_induced_absorption.c:29-108.
+ * collision_induced_absorption.c:29-108.  The HITRAN reader is grt_hitran.c, the device line store grt_line_store.c.
  *
  * Layout decisions (ours):
- *   - every molecule's lines are parsed ONCE into host staging and merged into one
- *     centre-sorted structure-of-arrays in HBM (v0,S as f64; the five parameters the
- *     reference itself reads through a float as f32; iso and molecule slot as u8):
- *     37 B/line instead of the reference's 60 B, and no (layer,line) scratch arrays;
+ *   - every molecule's lines are parsed ONCE into host staging and merged into one centre-sorted structure of arrays
+ *     in HBM (grt_line_store.c), with no (layer, line) scratch arrays;
  *   - per column, the 60-layer prologue (layer means, partial pressures, 1/Q, Doppler
  *     factors, continuum multipliers) is evaluated on the host in the reference's exact
  *     arithmetic and shipped as one small block (a few kB) per column;
@@ -20,8 +17,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/stat.h>
-#include <unistd.h>
 #include "grt_internal.h"
 #include "grt_molecule_table.h"
 
@@ -35,493 +30,8 @@ static char const *const cfc_names[NUM_CFCS] = {   /* cfcs.c:44-106 */
     "C2F6", "CF4", "CH2Cl2", "NF3", "SF6"};
 
 /* ------------------------------------------------------------------------------------ */
-/* Loaders                                                                               */
+/* Spectral tables                                                                       */
 /* ------------------------------------------------------------------------------------ */
-void grt_free_host_lines(GrtHostLines *l)
-{
-    free(l->v0); free(l->s0); free(l->yair); free(l->yself); free(l->en); free(l->nexp);
-    free(l->delta); free(l->iso);
-    memset(l, 0, sizeof(*l));
-}
-
-static int host_lines_reserve(GrtHostLines *l, uint64_t cap)
-{
-    l->v0 = realloc(l->v0, sizeof(double)*cap);
-    l->s0 = realloc(l->s0, sizeof(double)*cap);
-    l->yair = realloc(l->yair, sizeof(float)*cap);
-    l->yself = realloc(l->yself, sizeof(float)*cap);
-    l->en = realloc(l->en, sizeof(float)*cap);
-    l->nexp = realloc(l->nexp, sizeof(float)*cap);
-    l->delta = realloc(l->delta, sizeof(float)*cap);
-    l->iso = realloc(l->iso, sizeof(uint8_t)*cap);
-    if (!l->v0 || !l->s0 || !l->yair || !l->yself || !l->en || !l->nexp || !l->delta || !l->iso)
-    {
-        GRT_FAIL(GRTCODE_NULL_ERR, "out of host memory reserving %llu lines.", (unsigned long long)cap);
-    }
-    return GRTCODE_SUCCESS;
-}
-
-/* parse_HITRAN_file.c:372-384: S <- S * Q(296)/(e^{c2 E/296} (1 - e^{c2 nu/296})).  The host keeps the
-   tabulated 296 K strengths; this factor is applied when the device store is built (upload_lines), with
-   the partition sums of the provider current at that moment (grt_tips.c), so that a table loaded after
-   add_molecule() is never mixed with strengths scaled by another provider. */
-/* one line; q296 [GRT_MAX_ISO + 1]: this molecule's Q(296 K, iso), filled on first use (negative = not yet) */
-static inline void rescale_one(int mol_id, fp_t *q296, int iso, double v0, float en, double *s0)
-{
-    fp_t const tref = 296.f;
-    fp_t const c2 = -1.4387686f;
-    if (q296[iso] < 0.)
-    {
-        q296[iso] = Q(mol_id, tref, iso);
-    }
-    fp_t const e = en;
-    *s0 *= q296[iso]/(exp(c2*e/tref)*(1.f - exp(c2*v0/tref)));
-}
-
-void grt_rescale_strengths(int mol_id, uint64_t n, uint8_t const *iso, double const *v0, float const *en,
-                           double *s0)
-{
-    fp_t q296[GRT_MAX_ISO + 1];
-    for (int k = 0; k <= GRT_MAX_ISO; ++k)
-    {
-        q296[k] = -1.;
-    }
-    for (uint64_t i = 0; i < n; ++i)
-    {
-        rescale_one(mol_id, q296, iso[i], v0[i], en[i], &s0[i]);
-    }
-}
-
-static int fixed_field(char const *rec, int off, int len, char *buf)
-{
-    memcpy(buf, rec + off, (size_t)len);
-    buf[len] = '\0';
-    return off + len;
-}
-
-/* HITRAN-2012 160-character records (parse_HITRAN_file.c:77-100): mol(2) iso(1) nu(12)
-   S(10) A(10) g_air(5) g_self(5) E"(10) n(4) delta(8) + 93 unused.  A record is kept
-   when the molecule matches and w0 <= nu <= wn (:340).  Isotopologue codes: '0' -> 10,
-   'A'.. -> 11.. (:177-194). */
-/* One pass over the file.  mol_id != 0: the reference's behaviour -- keep this molecule's records with
-   w0 <= nu <= wn in `out` (one bucket).  mol_id == 0: every molecule's records, unfiltered, into
-   out[molecule - 1] (NUM_MOLS buckets; records of unknown molecule numbers are skipped) -- the parse-once
-   index below.  Strengths are left as tabulated (296 K). */
-static int scan_hitran(char const *path, int mol_id, double w0, double wn, GrtHostLines *out, uint64_t *bad_line)
-{
-    FILE *fp = NULL;
-    GRT_TRY(open_file(&fp, path, "r"));
-    uint64_t cap[NUM_MOLS];
-    memset(cap, 0, sizeof(cap));
-    char *line = NULL;
-    size_t linecap = 0;
-    ssize_t len;
-    size_t lineno = 0;
-    int rc = GRTCODE_SUCCESS;
-    while ((len = getline(&line, &linecap, fp)) != -1)
-    {
-        ++lineno;
-        if (len > 162 || len < 160)
-        {
-            grt_err_begin(GRTCODE_VALUE_ERR, __FILE__, __LINE__, "Found bad record at line %zu"
-                          " (%zd characters, expected 160-162) in file %s.", lineno, len, path);
-            rc = GRTCODE_VALUE_ERR;
-            break;
-        }
-        char buf[16];
-        int off = fixed_field(line, 0, 2, buf);
-        int mol = 0;
-        if ((rc = to_int(buf, &mol)) != GRTCODE_SUCCESS) break;
-        if (mol_id != 0 ? mol != mol_id : (mol < 1 || mol > NUM_MOLS))
-        {
-            continue;
-        }
-        int const bucket = mol_id != 0 ? 0 : mol - 1;
-        GrtHostLines *o = &out[bucket];
-        if (o->n == cap[bucket])
-        {
-            cap[bucket] = cap[bucket] ? 2*cap[bucket] : 65536;
-            if ((rc = host_lines_reserve(o, cap[bucket])) != GRTCODE_SUCCESS) break;
-        }
-        uint64_t const k = o->n;
-        /* the record's own fields.  One molecule at a time (the reference's behaviour) a field that does not
-           parse is an error; in index mode it is an error only for whoever asks for THAT molecule later
-           (parse_HITRAN_file.c:300-313 never looks at the fields of another molecule's records), so the
-           record is skipped and its line number remembered */
-        int frc = GRTCODE_SUCCESS;
-        off = fixed_field(line, off, 1, buf);
-        int iso = 0;
-        if (buf[0] == '0') iso = 10;
-        else if (buf[0] >= 'A' && buf[0] <= 'Z') iso = buf[0] - 'A' + 11;
-        else frc = to_int(buf, &iso);
-        if (frc == GRTCODE_SUCCESS && (iso < 1 || iso > GRT_MAX_ISO))
-        {
-            grt_err_begin(GRTCODE_VALUE_ERR, __FILE__, __LINE__, "isotopologue %d on line %zu of %s"
-                          " is outside 1-%d.", iso, lineno, path, GRT_MAX_ISO);
-            frc = GRTCODE_VALUE_ERR;
-        }
-        double d;
-        if (frc == GRTCODE_SUCCESS)
-        {
-            o->iso[k] = (uint8_t)iso;
-            off = fixed_field(line, off, 12, buf);
-            frc = to_double(buf, &d);
-            o->v0[k] = d;
-        }
-        if (frc == GRTCODE_SUCCESS)
-        {
-            off = fixed_field(line, off, 10, buf);
-            frc = to_double(buf, &d);
-            o->s0[k] = d;
-        }
-        if (frc == GRTCODE_SUCCESS)
-        {
-            off += 10;                                     /* Einstein A: unused */
-            float *f32dst[5] = {&o->yair[k], &o->yself[k], &o->en[k], &o->nexp[k], &o->delta[k]};
-            int const width[5] = {5, 5, 10, 4, 8};
-            for (int c = 0; c < 5 && frc == GRTCODE_SUCCESS; ++c)
-            {
-                off = fixed_field(line, off, width[c], buf);
-                if ((frc = to_double(buf, &d)) == GRTCODE_SUCCESS)
-                {
-                    *f32dst[c] = (float)d;                 /* parse_HITRAN_file.c:197-212 */
-                }
-            }
-        }
-        if (frc == GRTCODE_SUCCESS && !(isfinite(o->v0[k]) && isfinite(o->s0[k])))
-        {
-            grt_err_begin(GRTCODE_VALUE_ERR, __FILE__, __LINE__, "non-finite line centre or strength on line %zu"
-                          " of %s.", lineno, path);
-            frc = GRTCODE_VALUE_ERR;
-        }
-        if (frc != GRTCODE_SUCCESS)
-        {
-            if (mol_id == 0 && bad_line != NULL)
-            {
-                if (bad_line[bucket] == 0)
-                {
-                    bad_line[bucket] = lineno;
-                    GRT_WARN("record %zu of %s (molecule %d) does not parse; requests for that molecule will fail.",
-                             lineno, path, mol);
-                }
-                continue;
-            }
-            rc = frc;
-            break;
-        }
-        if (mol_id == 0 || (w0 < 0 && wn < 0) || (o->v0[k] >= w0 && o->v0[k] <= wn))
-        {
-            o->n++;
-        }
-    }
-    free(line);
-    if (fclose(fp) != 0 && rc == GRTCODE_SUCCESS)
-    {
-        grt_err_begin(GRTCODE_IO_ERR, __FILE__, __LINE__, "error closing file %s.", path);
-        rc = GRTCODE_IO_ERR;
-    }
-    if (rc != GRTCODE_SUCCESS)
-    {
-        for (int m = 0; m < (mol_id != 0 ? 1 : NUM_MOLS); ++m)
-        {
-            grt_free_host_lines(&out[m]);
-        }
-        grt_err_frame(__FILE__, __LINE__);
-    }
-    return rc;
-}
-
-/* Parse-once index (§8(f)-3).  The reference scans the whole .par file once per add_molecule -- seven
-   passes over a few hundred MB for one band, again for the second band.  Here the first request for a
-   file parses every molecule's records into memory once; later requests (any molecule, any gas-optics
-   object of this process) filter from memory.  Keyed by path, size and modification time; the two most
-   recent files are kept.  GRT_HITRAN_CACHE=0 in the environment restores one scan per call;
-   GRT_HITRAN_CACHE_DIR=<directory> keeps a binary copy of the index on disk for later processes. */
-typedef struct HitranIndex
-{
-    char path[DIR_PATH_LEN];
-    long long size, mtime;
-    unsigned long stamp;
-    GrtHostLines mol[NUM_MOLS];
-    uint64_t bad_line[NUM_MOLS];   /* first record of a molecule the parser refused (0: none): a request for THAT
-                                      molecule re-scans the file and fails like the reference; others are served */
-} HitranIndex;
-static HitranIndex g_hitran_index[2];
-static unsigned long g_hitran_stamp = 0;
-static long long g_hitran_stats[3];     /* requests served from memory, index files read, .par files scanned */
-
-/* On-disk copy of the index (GRT_HITRAN_CACHE_DIR=<directory> in the environment): one binary file per
-   (.par path, size, modification time), the arrays of every molecule as they sit in memory.  A later
-   process reads that instead of parsing text: a few hundred MB of %12lf fields become a few reads. */
-#define GRT_IDX_MAGIC "GRTIDX02"
-typedef struct IndexHeader
-{
-    char magic[8];
-    long long size, mtime;
-    uint64_t num_mols, path_hash;
-    uint64_t max_iso, record_bytes;    /* GRT_MAX_ISO and the bytes per line of the arrays below: a build with other limits re-parses */
-    uint64_t checksum;                 /* FNV-1a over every array, in file order */
-    uint64_t n[NUM_MOLS];
-    uint64_t bad_line[NUM_MOLS];       /* first record of that molecule the text parser refused (0: none) */
-} IndexHeader;
-
-static uint64_t fnv1a(char const *str)
-{
-    uint64_t h = 1469598103934665603ull;
-    for (; *str != '\0'; ++str)
-    {
-        h = (h ^ (unsigned char)*str)*1099511628211ull;
-    }
-    return h;
-}
-
-static int index_file_name(char const *par, long long size, long long mtime, char *out, size_t len)
-{
-    char const *dir = getenv("GRT_HITRAN_CACHE_DIR");
-    if (dir == NULL || dir[0] == '\0')
-    {
-        return 0;
-    }
-    int const w = snprintf(out, len, "%s/%016llx_%lld_%lld.grtidx", dir, (unsigned long long)fnv1a(par), size, mtime);
-    return w > 0 && (size_t)w < len;
-}
-
-static size_t const g_idx_width[8] = {sizeof(double), sizeof(double), sizeof(float), sizeof(float), sizeof(float),
-                                      sizeof(float), sizeof(float), sizeof(uint8_t)};
-#define GRT_IDX_RECORD_BYTES (2*sizeof(double) + 5*sizeof(float) + sizeof(uint8_t))
-
-static uint64_t fnv1a_bytes(uint64_t h, void const *data, size_t bytes)
-{
-    unsigned char const *p = data;
-    for (size_t i = 0; i < bytes; ++i)
-    {
-        h = (h ^ p[i])*1099511628211ull;
-    }
-    return h;
-}
-
-static uint64_t index_checksum(GrtHostLines *mol)
-{
-    uint64_t h = 1469598103934665603ull;
-    for (int m = 0; m < NUM_MOLS; ++m)
-    {
-        void *a[8];
-        a[0] = mol[m].v0; a[1] = mol[m].s0; a[2] = mol[m].yair; a[3] = mol[m].yself; a[4] = mol[m].en;
-        a[5] = mol[m].nexp; a[6] = mol[m].delta; a[7] = mol[m].iso;
-        for (int k = 0; k < 8 && mol[m].n > 0; ++k)
-        {
-            h = fnv1a_bytes(h, a[k], g_idx_width[k]*mol[m].n);
-        }
-    }
-    return h;
-}
-static void idx_arrays(GrtHostLines *l, void *a[8])
-{
-    a[0] = l->v0; a[1] = l->s0; a[2] = l->yair; a[3] = l->yself; a[4] = l->en; a[5] = l->nexp; a[6] = l->delta;
-    a[7] = l->iso;
-}
-
-/* 1 when the index was read from its file; 0 when there is none (or it does not match: the caller scans). */
-static int index_read(char const *file, char const *par, long long size, long long mtime, GrtHostLines *mol,
-                      uint64_t *bad_line)
-{
-    FILE *fp = fopen(file, "rb");
-    if (fp == NULL)
-    {
-        return 0;
-    }
-    IndexHeader h;
-    int ok = fread(&h, sizeof(h), 1, fp) == 1 && memcmp(h.magic, GRT_IDX_MAGIC, 8) == 0 && h.size == size
-             && h.mtime == mtime && h.num_mols == NUM_MOLS && h.path_hash == fnv1a(par)
-             && h.max_iso == GRT_MAX_ISO && h.record_bytes == GRT_IDX_RECORD_BYTES;
-    for (int m = 0; m < NUM_MOLS && ok; ++m)
-    {
-        if (h.n[m] == 0)
-        {
-            continue;
-        }
-        ok = h.n[m] < ((uint64_t)1 << 40) && host_lines_reserve(&mol[m], h.n[m]) == GRTCODE_SUCCESS;
-        void *a[8];
-        idx_arrays(&mol[m], a);
-        for (int k = 0; k < 8 && ok; ++k)
-        {
-            ok = fread(a[k], g_idx_width[k], h.n[m], fp) == h.n[m];
-        }
-        mol[m].n = ok ? h.n[m] : 0;
-    }
-    ok = ok && fgetc(fp) == EOF;        /* nothing may follow the last array */
-    fclose(fp);
-    /* the file is trusted no further than the text would be: same bytes as written (checksum), isotopologue codes
-       inside the range the kernels index 1/Q with, finite centres and strengths */
-    ok = ok && index_checksum(mol) == h.checksum;
-    for (int m = 0; m < NUM_MOLS && ok; ++m)
-    {
-        for (uint64_t k = 0; k < mol[m].n && ok; ++k)
-        {
-            ok = mol[m].iso[k] >= 1 && mol[m].iso[k] <= GRT_MAX_ISO && isfinite(mol[m].v0[k]) && isfinite(mol[m].s0[k]);
-        }
-    }
-    if (ok)
-    {
-        memcpy(bad_line, h.bad_line, sizeof(h.bad_line));
-    }
-    if (!ok)
-    {
-        for (int m = 0; m < NUM_MOLS; ++m)
-        {
-            grt_free_host_lines(&mol[m]);
-        }
-    }
-    return ok;
-}
-
-/* Best effort: a cache that cannot be written is not an error.  Written under a temporary name and renamed,
-   so that a reader never sees half a file. */
-static void index_write(char const *file, char const *par, long long size, long long mtime, GrtHostLines *mol,
-                        uint64_t const *bad_line)
-{
-    char tmp[DIR_PATH_LEN + 64];
-    if (snprintf(tmp, sizeof(tmp), "%s.%ld.tmp", file, (long)getpid()) >= (int)sizeof(tmp))
-    {
-        return;
-    }
-    FILE *fp = fopen(tmp, "wb");
-    if (fp == NULL)
-    {
-        return;
-    }
-    IndexHeader h;
-    memset(&h, 0, sizeof(h));
-    memcpy(h.magic, GRT_IDX_MAGIC, 8);
-    h.size = size; h.mtime = mtime; h.num_mols = NUM_MOLS; h.path_hash = fnv1a(par);
-    h.max_iso = GRT_MAX_ISO; h.record_bytes = GRT_IDX_RECORD_BYTES;
-    h.checksum = index_checksum(mol);
-    for (int m = 0; m < NUM_MOLS; ++m)
-    {
-        h.n[m] = mol[m].n;
-        h.bad_line[m] = bad_line[m];
-    }
-    int ok = fwrite(&h, sizeof(h), 1, fp) == 1;
-    for (int m = 0; m < NUM_MOLS && ok; ++m)
-    {
-        void *a[8];
-        idx_arrays(&mol[m], a);
-        for (int k = 0; k < 8 && ok && mol[m].n > 0; ++k)
-        {
-            ok = fwrite(a[k], g_idx_width[k], mol[m].n, fp) == mol[m].n;
-        }
-    }
-    ok = (fclose(fp) == 0) && ok;
-    if (!ok || rename(tmp, file) != 0)
-    {
-        remove(tmp);
-    }
-}
-
-static int hitran_index(char const *path, HitranIndex **out)
-{
-    struct stat st;
-    if (stat(path, &st) != 0)
-    {
-        GRT_FAIL(GRTCODE_IO_ERR, "failed to open file %s.", path);
-    }
-    long long const mtime = (long long)st.st_mtim.tv_sec*1000000000ll + st.st_mtim.tv_nsec;
-    HitranIndex *victim = &g_hitran_index[0];
-    for (int i = 0; i < 2; ++i)
-    {
-        HitranIndex *h = &g_hitran_index[i];
-        if (h->stamp != 0 && strcmp(h->path, path) == 0 && h->size == (long long)st.st_size && h->mtime == mtime)
-        {
-            h->stamp = ++g_hitran_stamp;
-            g_hitran_stats[0]++;
-            *out = h;
-            return GRTCODE_SUCCESS;
-        }
-        if (h->stamp < victim->stamp)
-        {
-            victim = h;
-        }
-    }
-    for (int m = 0; m < NUM_MOLS; ++m)
-    {
-        grt_free_host_lines(&victim->mol[m]);
-    }
-    victim->stamp = 0;
-    char file[DIR_PATH_LEN + 64];
-    int const on_disk = index_file_name(path, (long long)st.st_size, mtime, file, sizeof(file));
-    memset(victim->bad_line, 0, sizeof(victim->bad_line));
-    if (on_disk && index_read(file, path, (long long)st.st_size, mtime, victim->mol, victim->bad_line))
-    {
-        GRT_INFO("Read the index of %s from %s.", path, file);
-        g_hitran_stats[1]++;
-    }
-    else
-    {
-        GRT_INFO("Indexing HITRAN line parameters of every molecule in %s.", path);
-        GRT_TRY(scan_hitran(path, 0, 0., 0., victim->mol, victim->bad_line));
-        g_hitran_stats[2]++;
-        if (on_disk)
-        {
-            index_write(file, path, (long long)st.st_size, mtime, victim->mol, victim->bad_line);
-        }
-    }
-    GRT_TRY(copy_str(victim->path, path, DIR_PATH_LEN));
-    victim->size = (long long)st.st_size;
-    victim->mtime = mtime;
-    victim->stamp = ++g_hitran_stamp;
-    *out = victim;
-    return GRTCODE_SUCCESS;
-}
-
-/* {requests served from the in-memory index, index files read, .par files scanned for the index} since the
-   library was loaded (grt_ext.h) */
-EXTERN int grt_hitran_index_stats(long long stats[3])
-{
-    GRT_REQUIRE_PTR(stats);
-    memcpy(stats, g_hitran_stats, sizeof(g_hitran_stats));
-    return GRTCODE_SUCCESS;
-}
-
-int grt_parse_hitran(char const *path, int mol_id, double w0, double wn, GrtHostLines *out)
-{
-    GRT_REQUIRE_PTR(path);
-    GRT_REQUIRE_PTR(out);
-    memset(out, 0, sizeof(*out));
-    char const *env = getenv("GRT_HITRAN_CACHE");
-    if (mol_id < 1 || mol_id > NUM_MOLS || (env != NULL && env[0] == '0'))
-    {
-        GRT_INFO("Reading HITRAN line parameters for molecule %d from %s.", mol_id, path);
-        GRT_TRY(scan_hitran(path, mol_id, w0, wn, out, NULL));
-    }
-    else
-    {
-        HitranIndex *idx = NULL;
-        GRT_TRY(hitran_index(path, &idx));
-        if (idx->bad_line[mol_id - 1] != 0)
-        {
-            /* this molecule has a record the parser refused: scan for it alone, which fails there as the reference does */
-            GRT_TRY(scan_hitran(path, mol_id, w0, wn, out, NULL));
-            return GRTCODE_SUCCESS;
-        }
-        GrtHostLines const *src = &idx->mol[mol_id - 1];
-        if (src->n > 0)
-        {
-            GRT_TRY(host_lines_reserve(out, src->n));
-        }
-        for (uint64_t k = 0; k < src->n; ++k)
-        {
-            if ((w0 < 0 && wn < 0) || (src->v0[k] >= w0 && src->v0[k] <= wn))      /* parse_HITRAN_file.c:340 */
-            {
-                uint64_t const j = out->n++;
-                out->v0[j] = src->v0[k]; out->s0[j] = src->s0[k];
-                out->yair[j] = src->yair[k]; out->yself[j] = src->yself[k]; out->en[j] = src->en[k];
-                out->nexp[j] = src->nexp[k]; out->delta[j] = src->delta[k]; out->iso[j] = src->iso[k];
-            }
-        }
-    }
-    return GRTCODE_SUCCESS;      /* strengths as tabulated: see grt_rescale_strengths */
-}
-
 /* Two-column (or 1+k column) CSV -> values on the spectral grid: column 0 = wavenumber,
    column 1 = value, linear interpolation, zero outside the tabulated range
    (ozone_continuum.c:45-75 and the identical blocks in the other three loaders). */
@@ -728,34 +238,6 @@ EXTERN int create_gas_optics(GasOptics_t * const gas_optics, int const num_level
     return GRTCODE_SUCCESS;
 }
 
-static int free_store(GasOptics_t *go)
-{
-    GrtGasOpticsImpl *im = impl_of(go);
-    GRT_TRY(grt_dev_free(go->device, im->store_block));
-    im->store_block = NULL;
-    memset(&im->store, 0, sizeof(im->store));
-    for (int sl = 0; sl < NUM_MOLS; ++sl)
-    {
-        GRT_TRY(grt_dev_free(go->device, im->mstore_block[sl]));
-        im->mstore_block[sl] = NULL;
-        memset(&im->mstore[sl], 0, sizeof(im->mstore[sl]));
-    }
-    GRT_TRY(grt_dev_free(go->device, im->sweep_scratch));
-    im->sweep_scratch = NULL;
-    free(im->sorted_v0_h);
-    im->sorted_v0_h = NULL;
-    GRT_TRY(grt_dev_free(go->device, im->tile_ranges_d));
-    im->tile_ranges_d = NULL;
-    GRT_TRY(grt_dev_free(go->device, im->tile_items_d));
-    im->tile_items_d = NULL;
-    free(im->tile_items_h);
-    free(im->tile_ranges_h);
-    im->tile_items_h = im->tile_ranges_h = NULL;
-    im->n_items = 0;
-    im->tr_tile = 0;
-    return GRTCODE_SUCCESS;
-}
-
 EXTERN int destroy_gas_optics(GasOptics_t * const gas_optics)
 {
     GRT_REQUIRE_PTR(gas_optics);
@@ -766,7 +248,7 @@ EXTERN int destroy_gas_optics(GasOptics_t * const gas_optics)
         {
             grt_free_host_lines(&im->host[i]);
         }
-        GRT_TRY(free_store(gas_optics));
+        GRT_TRY(grt_free_line_store(gas_optics));
         GRT_TRY(grt_dev_free(gas_optics->device, im->bins_block));
         GRT_TRY(grt_dev_free(gas_optics->device, im->gmom));
         GRT_TRY(grt_dev_free(gas_optics->device, im->radius_table));
@@ -944,7 +426,7 @@ EXTERN int grt_add_molecule_lines(GasOptics_t *gas_optics, int molecule_id, uint
     {
         GRT_REQUIRE_PTR(iso); GRT_REQUIRE_PTR(v0); GRT_REQUIRE_PTR(s_raw); GRT_REQUIRE_PTR(yair);
         GRT_REQUIRE_PTR(yself); GRT_REQUIRE_PTR(en); GRT_REQUIRE_PTR(nexp); GRT_REQUIRE_PTR(delta);
-        GRT_TRY(host_lines_reserve(&lines, num_lines));
+        GRT_TRY(grt_reserve_host_lines(&lines, num_lines));
     }
     for (uint64_t j = 0; j < num_lines; ++j)
     {
@@ -1134,272 +616,6 @@ EXTERN int grt_gas_optics_tune(GasOptics_t *gas_optics, int tile, int nslice, in
     return GRTCODE_SUCCESS;
 }
 
-/* ------------------------------------------------------------------------------------ */
-/* Merged line store                                                                     */
-/* ------------------------------------------------------------------------------------ */
-typedef struct SortKey { double v0; uint32_t idx; uint8_t slot; } SortKey;
-
-static int sort_key_cmp(void const *a, void const *b)
-{
-    SortKey const *x = a, *y = b;
-    if (x->v0 < y->v0) return -1;
-    if (x->v0 > y->v0) return 1;
-    if (x->slot != y->slot) return x->slot < y->slot ? -1 : 1;
-    return x->idx < y->idx ? -1 : (x->idx > y->idx ? 1 : 0);
-}
-
-static size_t align256(size_t x)
-{
-    return (x + 255) & ~(size_t)255;
-}
-
-/* Upload the lines named by `keys` (already in the wanted order) as one structure of arrays. */
-/* with_lean: also the packed fp32 records of the lean first pass (GrtLineStore.lean_*), for the object's own grid. */
-static int upload_lines(GasOptics_t *go, SortKey const *keys, uint64_t total, GrtLineStore *st, void **block,
-                        size_t *bytes_out, int with_lean)
-{
-    GrtGasOpticsImpl *im = impl_of(go);
-    size_t off[14];
-    size_t bytes = 0;
-    size_t const sizes[13] = {8, 8, 4, 4, 4, 4, 4, 1, 1, 16, 16, 4, 16};
-    int const narr = with_lean ? 13 : 9;
-    uint64_t const npair = (total + 1)/2;
-    for (int a = 0; a < narr; ++a)
-    {
-        off[a] = bytes;
-        /* (the lean records are kept per PAIR of lines: an odd store has one line of padding) */
-        bytes = align256(bytes + sizes[a]*(a >= 9 ? 2*npair : total));
-    }
-    off[narr] = bytes;
-    unsigned char *host = malloc(bytes);
-    if (host == NULL)
-    {
-        GRT_FAIL(GRTCODE_NULL_ERR, "out of host memory staging %zu lines for the device.", (size_t)total);
-    }
-    double *v0 = (double *)(host + off[0]), *s0 = (double *)(host + off[1]);
-    float *yair = (float *)(host + off[2]), *yself = (float *)(host + off[3]);
-    float *en = (float *)(host + off[4]), *nexp = (float *)(host + off[5]), *delta = (float *)(host + off[6]);
-    uint8_t *iso = host + off[7], *slot = host + off[8];
-    st->n = total;
-    st->dmax = 0.;
-    st->nmax = 0.;
-    memset(st->yair_max, 0, sizeof(st->yair_max));
-    memset(st->yself_max, 0, sizeof(st->yself_max));
-    for (uint64_t k = 0; k < total; ++k)
-    {
-        GrtHostLines const *h = &im->host[keys[k].slot];
-        uint32_t const j = keys[k].idx;
-        v0[k] = h->v0[j]; s0[k] = h->s0[j];
-        yair[k] = h->yair[j]; yself[k] = h->yself[j]; en[k] = h->en[j]; nexp[k] = h->nexp[j];
-        delta[k] = h->delta[j];
-        iso[k] = h->iso[j]; slot[k] = keys[k].slot;
-        double const ad = fabs((double)h->delta[j]);
-        if (ad > st->dmax) st->dmax = ad;
-        if (h->yair[j] > st->yair_max[keys[k].slot]) st->yair_max[keys[k].slot] = h->yair[j];
-        if (h->yself[j] > st->yself_max[keys[k].slot]) st->yself_max[keys[k].slot] = h->yself[j];
-        if (fabs((double)h->nexp[j]) > st->nmax) st->nmax = fabs((double)h->nexp[j]);
-    }
-    /* strengths: tabulated -> the reference's pre-scaled form.  In a store merged by centre the molecules interleave
-       line by line, so Q(296 K) is kept per (slot, isotopologue) for the whole build -- a few dozen evaluations of the
-       provider instead of one per line */
-    {
-        static fp_t q296[GRT_MAX_SLOTS][GRT_MAX_ISO + 1];
-        for (int sl = 0; sl < GRT_MAX_SLOTS; ++sl)
-        {
-            for (int k = 0; k <= GRT_MAX_ISO; ++k)
-            {
-                q296[sl][k] = -1.;
-            }
-        }
-        for (uint64_t k = 0; k < total; ++k)
-        {
-            rescale_one(go->mols[slot[k]].id, q296[slot[k]], iso[k], v0[k], en[k], &s0[k]);
-        }
-    }
-    if (with_lean)
-    {
-        /* The lean first pass (k_gas_optics_mp.hip: lean_block) works in fp32 from quantities that depend on the line and
-           the grid only: the grid point nearest the unshifted centre and the centre's offset from it -- the pressure shift
-           (kernels.c:44) is added to the offset per layer, and whenever that sum comes within 1e-5 of the halfway mark the
-           line takes the general path, which forms kernels.c:431-432 in fp64 -- the strength scaled into fp32's range, and
-           the temperature exponent as an index into the per-layer table of (296/T)^(k/100) (kernels.c:105). */
-        float *la = (float *)(host + off[9]), *lb = (float *)(host + off[10]);
-        uint32_t *lc = (uint32_t *)(host + off[11]);
-        double *lx = (double *)(host + off[12]);
-        double const w0 = go->bins.w0, wres = go->bins.wres;
-        for (uint64_t k = 0; k < total; ++k)
-        {
-            double const uu = (v0[k] - w0)/wres;
-            double const c0 = floor(uu + 0.5);
-            uint32_t flags = 0;
-            int32_t ci = 0;
-            if (!(fabs(c0) < 1e9))
-            {
-                flags |= GRT_LEAN_GENERAL;
-            }
-            else
-            {
-                ci = (int32_t)c0;
-            }
-            double const ss = ldexp(s0[k], GRT_LEAN_S0_SHIFT);
-            if (!(ss >= 0x1p-100 && ss <= 0x1p100))
-            {
-                flags |= GRT_LEAN_GENERAL;      /* (zero, negative or NaN strengths included) */
-            }
-            float const n100 = nexp[k]*100.f, nk = rintf(n100);
-            uint32_t ik = 255;
-            if (fabsf(n100 - nk) <= 2e-5f && nk >= 0.f && nk < 128.f)       /* (the kernel's own test, kPowTable entries) */
-            {
-                ik = (uint32_t)nk;
-            }
-            else
-            {
-                flags |= GRT_LEAN_GENERAL;
-            }
-            if (iso[k] < 1 || iso[k] > GRT_MAX_ISO)
-            {
-                flags |= GRT_LEAN_GENERAL;
-            }
-            /* pair q = k/2, half h = k%2: every field of the two lines side by side (GrtLineStore) */
-            uint64_t const q = k >> 1, h = k & 1;
-            float const sv = (flags & GRT_LEAN_GENERAL) ? 0.f : (float)ss;
-            float const v0f = (float)v0[k];
-            la[4*q + h] = (float)(uu - c0);
-            memcpy(&la[4*q + 2 + h], &ci, sizeof(ci));
-            la[4*(npair + q) + h] = v0f;
-            la[4*(npair + q) + 2 + h] = sv;
-            lb[4*q + h] = yair[k]; lb[4*q + 2 + h] = yself[k];
-            lb[4*(npair + q) + h] = en[k]; lb[4*(npair + q) + 2 + h] = delta[k];
-            uint32_t const ti = (uint32_t)slot[k]*GRT_MAX_ISO + (uint32_t)(iso[k] >= 1 ? iso[k] - 1 : 0);
-            lc[k] = ik | ((uint32_t)slot[k] << 8) | ((ti & 1023u) << 14) | flags;
-            lx[2*k] = v0[k];
-            memcpy((char *)&lx[2*k + 1], &yair[k], 4);
-            memcpy((char *)&lx[2*k + 1] + 4, &yself[k], 4);
-            if (k + 1 == total && h == 0)
-            {
-                /* padding: the last line again, strength zero (never a line of any workgroup's range; finite numbers for
-                   the lanes that prepare it) */
-                la[4*q + 1] = la[4*q]; la[4*q + 3] = la[4*q + 2];
-                la[4*(npair + q) + 1] = v0f; la[4*(npair + q) + 3] = 0.f;
-                lb[4*q + 1] = yair[k]; lb[4*q + 3] = yself[k];
-                lb[4*(npair + q) + 1] = en[k]; lb[4*(npair + q) + 3] = delta[k];
-                lc[k + 1] = lc[k] | GRT_LEAN_GENERAL;
-            }
-        }
-    }
-    if (with_lean)
-    {
-        /* (the merged store only: the sorted centres stay on the host as well, for the launch's tile tables) */
-        free(im->sorted_v0_h);
-        im->sorted_v0_h = malloc(sizeof(double)*(size_t)(total ? total : 1));
-        if (im->sorted_v0_h != NULL)
-        {
-            memcpy(im->sorted_v0_h, v0, sizeof(double)*(size_t)total);
-        }
-        im->tr_tile = 0;            /* (any table built for the old store is stale) */
-    }
-    int rc = grt_dev_alloc(go->device, block, bytes);
-    void *s = grt_dev_stream(go->device);
-    if (rc == GRTCODE_SUCCESS) rc = grt_dev_upload(go->device, *block, host, bytes, s);
-    if (rc == GRTCODE_SUCCESS) rc = grt_dev_sync(go->device, s);
-    free(host);
-    GRT_TRY(rc);
-    unsigned char *d = *block;
-    st->v0 = (double const *)(d + off[0]);
-    st->s0 = (double const *)(d + off[1]);
-    st->yair = (float const *)(d + off[2]);
-    st->yself = (float const *)(d + off[3]);
-    st->en = (float const *)(d + off[4]);
-    st->nexp = (float const *)(d + off[5]);
-    st->delta = (float const *)(d + off[6]);
-    st->iso = d + off[7];
-    st->slot = d + off[8];
-    st->lean_a = st->lean_b = NULL;
-    st->lean_c = NULL;
-    st->lean_x = NULL;
-    st->lean_npair = 0;
-    st->lean_w0 = st->lean_wres = 0.;
-    if (with_lean)
-    {
-        st->lean_a = (float const *)(d + off[9]);
-        st->lean_b = (float const *)(d + off[10]);
-        st->lean_c = (uint32_t const *)(d + off[11]);
-        st->lean_x = (double const *)(d + off[12]);
-        st->lean_npair = npair;
-        st->lean_w0 = go->bins.w0;
-        st->lean_wres = go->bins.wres;
-    }
-    if (bytes_out != NULL) *bytes_out = bytes;
-    return GRTCODE_SUCCESS;
-}
-
-static int build_store(GasOptics_t *go)
-{
-    GrtGasOpticsImpl *im = impl_of(go);
-    GRT_TRY(free_store(go));
-    uint64_t total = 0;
-    for (int s = 0; s < go->num_molecules; ++s)
-    {
-        total += im->host[s].n;
-    }
-    im->store.n = total;
-    if (total == 0)
-    {
-        im->store_dirty = 0;
-        im->store_tips_generation = grt_tips_generation();
-        return GRTCODE_SUCCESS;
-    }
-    SortKey *keys = malloc(sizeof(SortKey)*total);
-    if (keys == NULL)
-    {
-        GRT_FAIL(GRTCODE_NULL_ERR, "out of host memory sorting %zu lines.", (size_t)total);
-    }
-    uint64_t k = 0;
-    for (int s = 0; s < go->num_molecules; ++s)
-    {
-        for (uint64_t j = 0; j < im->host[s].n; ++j, ++k)
-        {
-            keys[k].v0 = im->host[s].v0[j];
-            keys[k].idx = (uint32_t)j;
-            keys[k].slot = (uint8_t)s;
-        }
-    }
-    qsort(keys, total, sizeof(SortKey), sort_key_cmp);
-    size_t bytes = 0;
-    int rc = upload_lines(go, keys, total, &im->store, &im->store_block, &bytes, go->optical_depth_method == line_sample);
-    if (rc == GRTCODE_SUCCESS && go->optical_depth_method != line_sample)
-    {
-        /* the sweep methods work molecule by molecule (launch.c:78-159): one store each, sorted by centre */
-        SortKey *mk = malloc(sizeof(SortKey)*total);
-        if (mk == NULL)
-        {
-            grt_err_begin(GRTCODE_NULL_ERR, __FILE__, __LINE__, "out of host memory for the per-molecule stores.%s", "");
-            rc = GRTCODE_NULL_ERR;
-        }
-        for (int sl = 0; sl < go->num_molecules && rc == GRTCODE_SUCCESS; ++sl)
-        {
-            uint64_t n = 0;
-            for (uint64_t k = 0; k < total; ++k)
-            {
-                if (keys[k].slot == sl) mk[n++] = keys[k];
-            }
-            if (n > 0)
-            {
-                rc = upload_lines(go, mk, n, &im->mstore[sl], &im->mstore_block[sl], NULL, 0);
-            }
-        }
-        free(mk);
-    }
-    free(keys);
-    GRT_TRY(rc);
-    /* expose the device arrays through the public struct of the FIRST molecule only as
-       documentation of where they live; per-molecule views do not exist in a merged store */
-    im->store_dirty = 0;
-    im->store_tips_generation = grt_tips_generation();
-    GRT_INFO("Line store: %zu lines, %zu bytes on device %d.", (size_t)total, bytes, go->device);
-    return GRTCODE_SUCCESS;
-}
-
 /* spectral_bin.c:66-98: first/last grid index and the three interpolation wavenumbers of every bin,
    plus the (layer, bin, 3) line-wing accumulator, on the device (the sweep methods only). */
 static int create_bin_arrays(GasOptics_t *go)
@@ -1407,8 +623,8 @@ static int create_bin_arrays(GasOptics_t *go)
     GrtGasOpticsImpl *im = impl_of(go);
     SpectralBins_t *b = &go->bins;
     uint64_t const n = b->n;
-    size_t const bytes_l = align256(sizeof(uint64_t)*n), bytes_w = align256(sizeof(fp_t)*b->isize);
-    size_t const bytes_tau = align256(sizeof(fp_t)*b->isize*(size_t)b->num_layers);
+    size_t const bytes_l = grt_align256(sizeof(uint64_t)*n), bytes_w = grt_align256(sizeof(fp_t)*b->isize);
+    size_t const bytes_tau = grt_align256(sizeof(fp_t)*b->isize*(size_t)b->num_layers);
     unsigned char *host = calloc(1, 2*bytes_l + bytes_w);
     uint64_t *l = (uint64_t *)host, *r = (uint64_t *)(host + bytes_l);
     fp_t *w = (fp_t *)(host + 2*bytes_l);
@@ -1444,7 +660,7 @@ int grt_gas_optics_prepare(GasOptics_t *go, int ncol)
     if (im->store_dirty || im->store_tips_generation != grt_tips_generation())
     {
         /* (a partition-sum table loaded or dropped since the store was built changes Q(296) in every strength) */
-        GRT_TRY(build_store(go));
+        GRT_TRY(grt_build_line_store(go));
     }
     if (go->optical_depth_method != line_sample && im->bins_block == NULL)
     {
@@ -1594,11 +810,7 @@ EXTERN int calculate_optical_depth(GasOptics_t * const gas_optics, fp_t * const 
     GRT_TRY(compare_spectral_grids(&gas_optics->grid, &optics->grid, &same));
     GRT_REQUIRE_EQ(same, 1);
     GRT_TRY(grt_gas_optics_prepare(gas_optics, 1));
-    /* the pinned column-state buffer may still be feeding a batch upload (grt_optical_depth_batch is asynchronous) */
-    GRT_TRY(grt_gas_optics_wait_staging(gas_optics));
-    GrtGasOpticsImpl *im = impl_of(gas_optics);
-    GRT_TRY(grt_column_state(gas_optics, pressure, temperature, gas_optics->x, gas_optics->x_cfc,
-                             gas_optics->x_cia, im->colstate_h));
+    GRT_TRY(grt_gas_optics_stage_column(gas_optics, pressure, temperature));
     uint64_t const per_col = (uint64_t)gas_optics->num_layers*gas_optics->grid.n;
     GRT_TRY(grt_gas_launch_columns(gas_optics, 1, optics->tau, per_col));
     /* no wait here: what reads optics->tau next (rayleigh_scattering, add_optics, a solver, a download) is queued behind
@@ -1648,6 +860,24 @@ int grt_gas_optics_wait_staging(GasOptics_t *go)
     return GRTCODE_SUCCESS;
 }
 
+/* The pinned column-state buffer may still be feeding the upload of an earlier launch (grt_optical_depth_batch is
+   asynchronous): wait for it, then fill its column 0 from the object's own mixing ratios. */
+int grt_gas_optics_stage_column(GasOptics_t *go, fp_t const *p_mb, fp_t const *t)
+{
+    GRT_TRY(grt_gas_optics_wait_staging(go));
+    GRT_TRY(grt_column_state(go, p_mb, t, go->x, go->x_cfc, go->x_cia, impl_of(go)->colstate_h));
+    return GRTCODE_SUCCESS;
+}
+
+int grt_gas_optics_upload_states(GasOptics_t *go, int ncol)
+{
+    GrtGasOpticsImpl *im = impl_of(go);
+    void *s = grt_dev_stream(go->device);
+    GRT_TRY(grt_dev_upload(go->device, im->colstate_d, im->colstate_h, sizeof(double)*im->layout.stride*ncol, s));
+    GRT_TRY(grt_dev_event_record(go->device, &im->colstate_uploaded, s));
+    return GRTCODE_SUCCESS;
+}
+
 EXTERN int grt_optical_depth_batch(GasOptics_t *gas_optics, GrtColumns_t const *columns, fp_t *tau_dev)
 {
     GRT_REQUIRE_PTR(gas_optics);
@@ -1688,11 +918,8 @@ EXTERN int grt_debug_line_prep(GasOptics_t *gas_optics, fp_t *pressure, fp_t *te
     Device_t const dev = gas_optics->device;
     int const L = gas_optics->num_layers;
     void *s = grt_dev_stream(dev);
-    GRT_TRY(grt_gas_optics_wait_staging(gas_optics));
-    GRT_TRY(grt_column_state(gas_optics, pressure, temperature, gas_optics->x, gas_optics->x_cfc,
-                             gas_optics->x_cia, im->colstate_h));
-    GRT_TRY(grt_dev_upload(dev, im->colstate_d, im->colstate_h, sizeof(double)*im->layout.stride, s));
-    GRT_TRY(grt_dev_event_record(dev, &im->colstate_uploaded, s));
+    GRT_TRY(grt_gas_optics_stage_column(gas_optics, pressure, temperature));
+    GRT_TRY(grt_gas_optics_upload_states(gas_optics, 1));
     size_t const cells = (size_t)L*N;
     double *d = NULL;
     GRT_TRY(grt_dev_alloc(dev, (void **)&d, sizeof(double)*cells*6));
@@ -1701,13 +928,11 @@ EXTERN int grt_debug_line_prep(GasOptics_t *gas_optics, fp_t *pressure, fp_t *te
     int rc = grt_dev_check(grt_launch_line_prep(s, &args, 0, d, d + cells, d + 2*cells, d + 3*cells,
                                                 (int64_t *)(d + 4*cells), (int64_t *)(d + 5*cells)),
                            "line prep kernel");
-    double *outs[4] = {vnn, snn, gamma, alpha};
-    for (int k = 0; k < 4 && rc == GRTCODE_SUCCESS; ++k)
+    void *outs[6] = {vnn, snn, gamma, alpha, win_s, win_e};
+    for (int k = 0; k < 6 && rc == GRTCODE_SUCCESS; ++k)
     {
         if (outs[k] != NULL) rc = grt_dev_download(dev, outs[k], d + k*cells, sizeof(double)*cells, s);
     }
-    if (rc == GRTCODE_SUCCESS && win_s != NULL) rc = grt_dev_download(dev, win_s, d + 4*cells, sizeof(double)*cells, s);
-    if (rc == GRTCODE_SUCCESS && win_e != NULL) rc = grt_dev_download(dev, win_e, d + 5*cells, sizeof(double)*cells, s);
     if (rc == GRTCODE_SUCCESS && slot != NULL) rc = grt_dev_download(dev, slot, im->store.slot, N, s);
     if (rc == GRTCODE_SUCCESS && v0 != NULL) rc = grt_dev_download(dev, v0, im->store.v0, sizeof(double)*N, s);
     if (rc == GRTCODE_SUCCESS) rc = grt_dev_sync(dev, s);
@@ -1746,14 +971,11 @@ EXTERN int grt_debug_partition_functions(GasOptics_t *gas_optics, fp_t *pressure
     GRT_REQUIRE_PTR(temperature);
     GRT_REQUIRE_PTR(q_out);
     GRT_TRY(grt_gas_optics_prepare(gas_optics, 1));
-    GRT_TRY(grt_gas_optics_wait_staging(gas_optics));
+    GRT_TRY(grt_gas_optics_stage_column(gas_optics, pressure, temperature));
+    GRT_TRY(grt_gas_optics_upload_states(gas_optics, 1));
     GrtGasOpticsImpl *im = impl_of(gas_optics);
     Device_t const dev = gas_optics->device;
     void *s = grt_dev_stream(dev);
-    GRT_TRY(grt_column_state(gas_optics, pressure, temperature, gas_optics->x, gas_optics->x_cfc,
-                             gas_optics->x_cia, im->colstate_h));
-    GRT_TRY(grt_dev_upload(dev, im->colstate_d, im->colstate_h, sizeof(double)*im->layout.stride, s));
-    GRT_TRY(grt_dev_event_record(dev, &im->colstate_uploaded, s));
     size_t const count = (size_t)gas_optics->num_molecules*(size_t)gas_optics->num_layers*GRT_MAX_ISO;
     if (count > 0)
     {

@@ -129,8 +129,17 @@ typedef struct GrtGasOpticsImpl
 } GrtGasOpticsImpl;
 static inline GrtGasOpticsImpl *impl_of(GasOptics_t const *go) { return (GrtGasOpticsImpl *)go->impl; }
 
+/* Helpers shared by the host files only: kept out of the shared library's table of exported symbols. */
+#define GRT_PRIVATE __attribute__((visibility("hidden")))
+
+static inline size_t grt_align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
 int grt_gas_optics_prepare(GasOptics_t *go, int ncol);   /* build store/tables/layout if stale */
 int grt_gas_optics_wait_staging(GasOptics_t *go);        /* until the last batch's column state has been uploaded */
+/* waits as grt_gas_optics_wait_staging, then column 0 of colstate_h from the object's own go->x, x_cfc, x_cia */
+GRT_PRIVATE int grt_gas_optics_stage_column(GasOptics_t *go, fp_t const *p_mb, fp_t const *t);
+/* the first ncol states of colstate_h to colstate_d on the library stream; records colstate_uploaded */
+GRT_PRIVATE int grt_gas_optics_upload_states(GasOptics_t *go, int ncol);
 /* Host prologue for one column (curtis_godson.c + partition sums), written at dst. */
 int grt_column_state(GasOptics_t const *go, fp_t const *p_mb, fp_t const *t,
                      fp_t const *x_mol /* [NUM_MOLS][V] by id-1 */, fp_t const *x_cfc /* [NUM_CFCS][V] */,
@@ -147,10 +156,16 @@ void grt_gas_optics_continua(GasOptics_t *go, GrtContinua *c);
 void grt_gas_common_args(GasOptics_t const *go, int ncol, double *tau, uint64_t tau_col_stride, GrtGasOpticsArgs *a);
 int grt_gas_launch_columns(GasOptics_t *go, int ncol, double *tau_dev, uint64_t tau_col_stride);
 
-/* loaders */
+/* grt_hitran.c: lines of one molecule, strengths as tabulated */
 int grt_parse_hitran(char const *path, int mol_id, double w0, double wn, GrtHostLines *out);
 void grt_free_host_lines(GrtHostLines *l);
+GRT_PRIVATE int grt_reserve_host_lines(GrtHostLines *l, uint64_t cap);
+GRT_PRIVATE void grt_copy_host_line(GrtHostLines *dst, uint64_t j, GrtHostLines const *src, uint64_t k);  /* src line k -> dst line j */
+/* grt_line_store.c: the device stores of the object's host lines, strengths rescaled with the partition sums current now */
 void grt_rescale_strengths(int mol_id, uint64_t n, uint8_t const *iso, double const *v0, float const *en, double *s0);
+GRT_PRIVATE int grt_build_line_store(GasOptics_t *go);
+GRT_PRIVATE int grt_free_line_store(GasOptics_t *go);
+/* loaders */
 unsigned long grt_tips_generation(void);   /* bumped by grt_tips_load / grt_tips_reset */
 int grt_load_table_on_grid(char const *path, int expect_cols, SpectralGrid_t const *grid,
                            fp_t *out /* host [n], zero-filled then interpolated */);

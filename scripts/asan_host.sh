@@ -13,7 +13,10 @@ case "$1" in
 build)
   python -m grtcode_amd.build > /dev/null
   mkdir -p $OUT/obj
-  for f in grt_error grt_util grt_grid grt_device grt_optics grt_tips grt_gas_optics grt_solvers grt_pipeline grt_multi; do
+  # the host objects of libgrtcode_hip.so, as grtcode_amd/build.py lists them
+  HOST=$(PYTHONPATH=$ROOT python -c "from grtcode_amd.build import HOST_SRC, NOT_IN_SO
+print(' '.join(f[:-2] for f in HOST_SRC if f[:-2] not in NOT_IN_SO))")
+  for f in $HOST; do
     gcc -std=gnu99 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -ffp-contract=off -fPIC -D__HIP_PLATFORM_AMD__ \
         -I$ROOT/include -I/opt/rocm/include -I$ROOT/grtcode_amd/csrc/host -c $ROOT/grtcode_amd/csrc/host/$f.c -o $OUT/obj/$f.o
   done
