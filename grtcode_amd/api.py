@@ -293,6 +293,13 @@ def add_optics(objs):
     return OpticsObject(0, None, 0, _adopt=res)
 
 
+def sample_optics(dest, source, w0=None, wn=None):
+    """dest's points from w0 to wn (None: the ends of dest's grid, with the reference's counts) take source's values at
+    the same wavenumbers; every other point of dest is left as it was."""
+    check(load_library().sample_optics(C.byref(dest.c), C.byref(source.c), _opt_double(w0), _opt_double(wn)))
+    return dest
+
+
 class GasOpticsObject:
     def __init__(self, num_levels, grid, device, hitran_path="", h2o_ctm_dir=None, o3_ctm_file=None,
                  wcutoff=None, method=LINE_SAMPLE):

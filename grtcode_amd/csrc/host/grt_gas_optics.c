@@ -126,6 +126,7 @@ EXTERN int create_gas_optics(GasOptics_t * const gas_optics, int const num_level
     GRT_REQUIRE_PTR(gas_optics);
     GRT_REQUIRE_RANGE(num_levels, MIN_NUM_LEVELS, MAX_NUM_LEVELS);
     GRT_REQUIRE_PTR(grid);
+    GRT_REQUIRE_GRID_POINTS(grid);
     GRT_REQUIRE_PTR(device);
     GRT_REQUIRE_PTR(hitran_path);
     memset(gas_optics, 0, sizeof(*gas_optics));

@@ -33,6 +33,11 @@ void grt_log(int level, char const *file, int line, char const *fmt, ...);
          if (v_ > hi_) GRT_FAIL(GRTCODE_RANGE_ERR, "value (%e) greater than maximum allowed (%e).", v_, hi_); \
     } while (0)
 
+/* a solver's trapezoid and its endpoint weights need two grid points: a grid filled in by hand may hold fewer */
+#define GRT_REQUIRE_GRID_POINTS(grid) \
+    do { if ((grid)->n < 2) GRT_FAIL(GRTCODE_VALUE_ERR, "a spectral grid of %llu points: at least 2 are needed.", \
+                                     (unsigned long long)(grid)->n); } while (0)
+
 #define GRT_REQUIRE_EQ(a, b) \
     do { if ((a) != (b)) GRT_FAIL(GRTCODE_VALUE_ERR, "values (%lld, %lld) are not equal.", \
                                   (long long)(a), (long long)(b)); } while (0)

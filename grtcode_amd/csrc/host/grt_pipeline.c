@@ -214,6 +214,14 @@ EXTERN int grt_pipeline_create_ex(GrtPipeline_t **pipeline, GasOptics_t *lw_gas,
         GRT_REQUIRE_EQ(lw_gas->num_levels, sw_gas->num_levels);
     }
     GRT_REQUIRE_RANGE(user_level, -1, any->num_levels - 1);
+    if (lw_gas != NULL)
+    {
+        GRT_REQUIRE_GRID_POINTS(&lw_gas->grid);
+    }
+    if (sw_gas != NULL)
+    {
+        GRT_REQUIRE_GRID_POINTS(&sw_gas->grid);
+    }
     GrtPipeline_t *p = calloc(1, sizeof(*p));
     if (p == NULL)
     {
@@ -824,6 +832,21 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t 
         GrtBand *b = &p->band[bi];
         if (b->gas == NULL)
         {
+            if (!profile)
+            {
+                /* a skipped band's six values (and its all-sky six) are zeros, as the profile forms' rows are: the
+                   caller's buffer is not left holding whatever it held before */
+                void *s = grt_dev_stream(p->device);
+                for (int c = 0; c < C; ++c)
+                {
+                    double *six = out + (size_t)c*out_stride + GRT_FLUXES_PER_BAND*bi;
+                    GRT_TRY(grt_dev_zero(p->device, six, sizeof(double)*GRT_FLUXES_PER_BAND, s));
+                    if (cl != NULL)
+                    {
+                        GRT_TRY(grt_dev_zero(p->device, six + GRT_FLUXES_PER_COLUMN, sizeof(double)*GRT_FLUXES_PER_BAND, s));
+                    }
+                }
+            }
             continue;
         }
         GrtCloudArgs ca;

@@ -129,6 +129,7 @@ EXTERN int create_longwave(Longwave_t * const lw, int const num_levels,
 {
     GRT_REQUIRE_PTR(lw);
     GRT_REQUIRE_PTR(grid);
+    GRT_REQUIRE_GRID_POINTS(grid);
     GRT_REQUIRE_PTR(device);
     GRT_REQUIRE_RANGE(num_levels, MIN_NUM_LEVELS, MAX_NUM_LEVELS);
     GRT_TRY(grt_dev_require(*device));
@@ -221,6 +222,7 @@ EXTERN int create_shortwave(Shortwave_t * const sw, int const num_levels,
 {
     GRT_REQUIRE_PTR(sw);
     GRT_REQUIRE_PTR(grid);
+    GRT_REQUIRE_GRID_POINTS(grid);
     GRT_REQUIRE_PTR(device);
     GRT_REQUIRE_RANGE(num_levels, MIN_NUM_LEVELS, MAX_NUM_LEVELS);
     GRT_TRY(grt_dev_require(*device));

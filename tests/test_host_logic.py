@@ -39,6 +39,21 @@ def test_spectral_grid_size(w0, wn, dw, n):
     assert api.create_spectral_grid(w0, wn, dw).n == n      # ceil((wn-w0)/dw)+1 (spectral_grid.c:61)
 
 
+@pytest.mark.parametrize("n", [0, 1])
+def test_objects_refuse_a_grid_of_fewer_than_two_points(lib, n):
+    """create_spectral_grid never makes one (wn > w0), but a caller may fill the struct in: the gas-optics and solver
+    objects refuse it before they look at the device."""
+    assert lib.create_spectral_grid(C.byref(api.SpectralGrid()), 500.0, 500.0, 1.0) == api.RANGE_ERR
+    g = api.create_spectral_grid(500.0, 501.0, 1.0)
+    assert g.n == 2
+    g.n = n
+    dev = C.c_int(0)
+    assert lib.create_gas_optics(C.byref(api.GasOptics()), 3, C.byref(g), C.byref(dev), b"", None, None, None,
+                                 None) == api.VALUE_ERR
+    assert lib.create_longwave(C.byref(api.Longwave()), 3, C.byref(g), C.byref(dev)) == api.VALUE_ERR
+    assert lib.create_shortwave(C.byref(api.Shortwave()), 3, C.byref(g), C.byref(dev)) == api.VALUE_ERR
+
+
 def test_spectral_grid_index_and_compare(lib):
     g = api.create_spectral_grid(10.0, 20.0, 0.25)
     idx = C.c_uint64()
