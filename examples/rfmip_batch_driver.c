@@ -21,12 +21,16 @@
  * Usage:  rfmip_batch_driver HITRAN.par SOLAR.csv COLUMNS.bin [-h2o-ctm DIR] [-o3-ctm FILE] [-CFC-11 FILE ppmv]
  *             [-CFC-12 FILE ppmv] [-N2-N2 FILE] [-O2-N2 FILE] [-O2-O2 FILE] [-w-lw W0 -W-lw WN -r-lw DW]
  *             [-w-sw W0 -W-sw WN -r-sw DW] [-chunk N] [-fast 0|1|2|3] [-d DEVICE]
- *             [-ranks N -rank K -rendezvous DIR [-transport rccl|files]] [-profiles]
+ *             [-ranks N -rank K -rendezvous DIR [-transport rccl|files]] [-profiles] [-bin-width DW]
  * Output: one line per column "col <i>: rlut rlus rldt rlds rsut rsus rsdt rsds" [W m-2] (zeros for the shortwave
  * of night columns).  With -profiles each column's line is followed by its broadband fluxes at every level, top first,
  * "lev <k>: rlu rld rsu rsd" [W m-2], and the heating rate of every layer, "lay <j>: hr_lw hr_sw" [K day-1]
  * (grt_pipeline_run_profiles; its shortwave is the two-sweep form, so lev 0's rsu may differ from the col line's rsut
  * in the last digits).
+ * With -bin-width DW each column's line is followed by its fluxes integrated over wavenumber bins of round(DW/dw) grid
+ * points from each band's first point (the last bin shorter; adjacent bins share their edge point),
+ * "lwbin <b>: w_lo w_hi rlut rlus rldt rlds" and "swbin <b>: w_lo w_hi rsut rsus rsdt rsds" [cm-1, W m-2]
+ * (grt_pipeline_run_spectral; night columns get zeros in their shortwave bins).
  *
  * Several GPUs of one node: start one process per GPU with the same arguments plus -ranks N -rank K (K = 0..N-1,
  * normally with -d K) and a directory all of them see.  Every rank computes its contiguous block of the columns
@@ -75,6 +79,22 @@ static double number(int argc, char **argv, char const *name, double fallback)
 {
     char const *v = option(argc, argv, name, 1);
     return v != NULL ? atof(v) : fallback;
+}
+
+/* -bin-width: grid-point edges every round(width/dw) points from 0, the last at n - 1; returns the bin count */
+static int bin_edges(SpectralGrid_t const *grid, double width, int **edges)
+{
+    long long k = llround(width/grid->dw);
+    k = k < 1 ? 1 : k;
+    long long const n = (long long)grid->n;
+    int const nb = (int)((n - 1 + k - 1)/k);
+    *edges = malloc(sizeof(int)*((size_t)nb + 1));
+    for (int b = 0; b < nb; ++b)
+    {
+        (*edges)[b] = (int)(b*k);
+    }
+    (*edges)[nb] = (int)(n - 1);
+    return nb;
 }
 
 /* rfmip-irf.c:295-308 */
@@ -242,6 +262,22 @@ int main(int argc, char **argv)
         check(grt_device_malloc(device, (void **)&levels_dev, sizeof(fp_t)*chunk*GRT_PROFILE_ROWS_PER_COLUMN*V));
         check(grt_device_malloc(device, (void **)&heating_dev, sizeof(fp_t)*chunk*GRT_HEATING_ROWS_PER_COLUMN*L));
     }
+    /* -bin-width: per column a row of the longwave bins [6][nb_lw] and then the shortwave bins [6][nb_sw] */
+    double const bin_width = number(argc, argv, "-bin-width", 0.);
+    int const bins = bin_width > 0.;
+    int *edges[2] = {NULL, NULL}, nb[2] = {0, 0};
+    fp_t *spectral_dev = NULL, *binned_dev = NULL, *spectral_fluxes_dev = NULL;
+    if (bins)
+    {
+        for (int b = 0; b < 2; ++b)
+        {
+            nb[b] = bin_edges(grids[b], bin_width, &edges[b]);
+        }
+        check(grt_device_malloc(device, (void **)&spectral_dev, sizeof(fp_t)*chunk*6*(lw_grid.n + sw_grid.n)));
+        check(grt_device_malloc(device, (void **)&binned_dev, sizeof(fp_t)*chunk*6*(nb[0] + nb[1])));
+        check(grt_device_malloc(device, (void **)&spectral_fluxes_dev, sizeof(fp_t)*chunk*GRT_FLUXES_PER_COLUMN));
+    }
+    int const brow = 6*(nb[0] + nb[1]);
     /* this rank's block of the columns */
     int const world = (int)number(argc, argv, "-ranks", 1.), rank = (int)number(argc, argv, "-rank", 0.);
     int shard_first = 0, shard_count = ncol;
@@ -264,6 +300,8 @@ int main(int argc, char **argv)
     fp_t *profile = profiles ? calloc((size_t)per_rank*world*prow, sizeof(fp_t)) : NULL;
     fp_t *host_levels = profiles ? malloc(sizeof(fp_t)*chunk*GRT_PROFILE_ROWS_PER_COLUMN*V) : NULL;
     fp_t *host_heating = profiles ? malloc(sizeof(fp_t)*chunk*GRT_HEATING_ROWS_PER_COLUMN*L) : NULL;
+    fp_t *binned = bins ? calloc((size_t)per_rank*world*brow, sizeof(fp_t)) : NULL;
+    fp_t *host_bins = bins ? malloc(sizeof(fp_t)*chunk*brow) : NULL;
     /* day and night columns go through different pipelines; keep chunks contiguous in each class */
     for (int night = 0; night < 2; ++night)
     {
@@ -316,6 +354,19 @@ int main(int argc, char **argv)
                     memcpy(row + nl, host_heating + j*nh, sizeof(fp_t)*nh);
                 }
             }
+            if (bins)
+            {
+                /* (the night pipeline has no shortwave band: it takes no shortwave bins, and they stay zero) */
+                int const row = night ? 6*nb[0] : brow;
+                check(grt_pipeline_run_spectral(pipe, &cols, NULL, edges[0], nb[0], night ? NULL : edges[1],
+                                                night ? 0 : nb[1], spectral_dev, binned_dev, spectral_fluxes_dev));
+                check(grt_pipeline_sync(pipe));
+                check(grt_device_to_host(device, host_bins, binned_dev, sizeof(fp_t)*m*row));
+                for (int j = 0; j < m; ++j)
+                {
+                    memcpy(binned + (size_t)ids[first + j]*brow, host_bins + (size_t)j*row, sizeof(fp_t)*row);
+                }
+            }
             free(cp); free(ct); free(ctl); free(cts); free(cmu); free(ctsi); free(cmol); free(ccfc); free(ccia);
         }
         free(ids);
@@ -341,6 +392,16 @@ int main(int argc, char **argv)
                 if (rank == 0)
                 {
                     memcpy(profile, all_rows, sizeof(fp_t)*(size_t)ncol*prow);
+                    free(all_rows);
+                }
+            }
+            if (bins)
+            {
+                fp_t *all_rows = rank == 0 ? calloc((size_t)per_rank*world*brow, sizeof(fp_t)) : NULL;
+                check(grt_multi_gather_rows(multi, binned + (size_t)shard_first*brow, ncol, brow, all_rows, 0));
+                if (rank == 0)
+                {
+                    memcpy(binned, all_rows, sizeof(fp_t)*(size_t)ncol*brow);
                     free(all_rows);
                 }
             }
@@ -372,6 +433,21 @@ int main(int argc, char **argv)
                 check(grt_device_free(device, local_dev));
                 check(grt_device_free(device, all_dev));
             }
+            if (bins)
+            {
+                size_t const rows = sizeof(fp_t)*(size_t)per_rank*brow;
+                local_dev = NULL;
+                all_dev = NULL;
+                check(grt_device_malloc(device, (void **)&local_dev, rows));
+                if (rank == 0) check(grt_device_malloc(device, (void **)&all_dev, rows*world));
+                if (shard_count > 0) check(grt_host_to_device(device, local_dev, binned + (size_t)shard_first*brow,
+                                                              sizeof(fp_t)*(size_t)shard_count*brow));
+                check(grt_multi_gather_rows(multi, local_dev, ncol, brow, all_dev, 1));
+                check(grt_pipeline_sync(pipe_day));
+                if (rank == 0) check(grt_device_to_host(device, binned, all_dev, sizeof(fp_t)*(size_t)ncol*brow));
+                check(grt_device_free(device, local_dev));
+                check(grt_device_free(device, all_dev));
+            }
         }
         double seconds = 0.;
         check(grt_multi_max(multi, &seconds));             /* everybody is done before anybody tears down */
@@ -381,6 +457,18 @@ int main(int argc, char **argv)
     {
         fp_t const *x = fluxes + (size_t)c*GRT_FLUXES_PER_COLUMN;
         printf("col %d: %.15e %.15e %.15e %.15e %.15e %.15e %.15e %.15e\n", c, x[0], x[1], x[3], x[4], x[6], x[7], x[9], x[10]);
+        for (int band = 0; band < 2 && bins; ++band)
+        {
+            /* the band's six rows [6][nb] of this column: up TOA, up surface, up user, down TOA, down surface, down user */
+            fp_t const *r = binned + (size_t)c*brow + (band ? 6*nb[0] : 0);
+            SpectralGrid_t const *g = grids[band];
+            for (int b = 0; b < nb[band]; ++b)
+            {
+                printf("%s %d: %.15e %.15e %.15e %.15e %.15e %.15e\n", band ? "swbin" : "lwbin", b,
+                       g->w0 + edges[band][b]*g->dw, g->w0 + edges[band][b + 1]*g->dw, r[b], r[nb[band] + b],
+                       r[3*nb[band] + b], r[4*nb[band] + b]);
+            }
+        }
         if (profiles)
         {
             fp_t const *r = profile + (size_t)c*prow, *h = r + GRT_PROFILE_ROWS_PER_COLUMN*V;
@@ -402,6 +490,16 @@ int main(int argc, char **argv)
         check(grt_device_free(device, levels_dev));
         check(grt_device_free(device, heating_dev));
     }
+    if (bins)
+    {
+        check(grt_device_free(device, spectral_dev));
+        check(grt_device_free(device, binned_dev));
+        check(grt_device_free(device, spectral_fluxes_dev));
+    }
+    free(binned);
+    free(host_bins);
+    free(edges[0]);
+    free(edges[1]);
     free(profile);
     free(host_levels);
     free(host_heating);

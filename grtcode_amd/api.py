@@ -150,7 +150,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -192,6 +192,8 @@ def load_library(path=None):
     lib.grt_pipeline_run_allsky.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtClouds), C.c_void_p]
     lib.grt_pipeline_run_allsky_profiles.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtClouds), C.c_void_p,
                                                      C.c_void_p, C.c_void_p]
+    lib.grt_pipeline_run_spectral.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtClouds), C.c_void_p, C.c_int,
+                                              C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.grt_multi_gather_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.grt_pipeline_sync.argtypes = [C.c_void_p]
     lib.grt_pipeline_stream.argtypes = [C.c_void_p]
@@ -481,7 +483,7 @@ class Pipeline:
         """spectral=True keeps tau/omega/g and the spectral fluxes (views(): what parity tests read);
         spectral=False is the production form of grt_pipeline_create: fused solvers, integrated fluxes only."""
         self.lib = load_library()
-        self.spectral = spectral
+        self.keep_spectra = spectral
         self.p = C.c_void_p()
         self.device = (lw_gas or sw_gas).device
         e = _f64(emissivity) if emissivity is not None else None
@@ -497,6 +499,8 @@ class Pipeline:
         self.prof = None        # run_profiles' device outputs: allocated at its first call
         self.allsky = None      # run_allsky's [max_columns][24]: allocated at its first call
         self.allsky_prof = None  # run_allsky_profiles' device outputs: allocated at its first call
+        self.spec = None        # run_spectral's device outputs: allocated at its first call (and for a new bin count)
+        self.nw = tuple(g.grid.n if g is not None else 0 for g in (lw_gas, sw_gas))
 
     def run(self, gcols, out_ptr=None):
         check(self.lib.grt_pipeline_run(self.p, C.byref(gcols), out_ptr if out_ptr is not None else self.out.ptr))
@@ -567,9 +571,50 @@ class Pipeline:
                           sw_down=lv[:, s, 3].copy(), lw_heating=hr[:, s, 0].copy(), sw_heating=hr[:, s, 1].copy(),
                           fluxes=fx[:, s].copy()) for s in range(2))
 
+    def run_spectral(self, gcols, gclouds=None, lw_edges=None, sw_edges=None):
+        """grt_pipeline_run_spectral into this object's device buffers (spectral() reads them): the six rows at every grid
+        point and, for lw_edges / sw_edges (grid-point indices, num_bins + 1 of them), their bins; gclouds: all-sky too."""
+        sets = 1 if gclouds is None else 2
+        e = [None if x is None else np.ascontiguousarray(x, dtype=np.int32) for x in (lw_edges, sw_edges)]
+        nb = [0 if x is None else max(x.size - 1, 0) for x in e]
+        n = self.max_columns
+        need = (sets, nb[0], nb[1])
+        if self.spec is None or self.spec["shape"] != need:
+            for k in ("spectral", "binned", "fluxes"):
+                if self.spec is not None and self.spec[k] is not None:
+                    self.spec[k].free()
+            per = 6 * (self.nw[0] + self.nw[1])
+            self.spec = {"shape": need,
+                         "spectral": DeviceBuffer(self.device, 8 * n * sets * per),
+                         "binned": DeviceBuffer(self.device, 8 * n * sets * 6 * (nb[0] + nb[1])) if nb[0] + nb[1] else None,
+                         "fluxes": DeviceBuffer(self.device, 8 * n * sets * GRT_FLUXES_PER_COLUMN)}
+        ptr = [None if x is None else x.ctypes.data_as(C.c_void_p) for x in e]
+        binned = self.spec["binned"].ptr if self.spec["binned"] is not None else None
+        check(self.lib.grt_pipeline_run_spectral(self.p, C.byref(gcols), C.byref(gclouds) if gclouds is not None else None,
+                                                 ptr[0], nb[0], ptr[1], nb[1], self.spec["spectral"].ptr, binned,
+                                                 self.spec["fluxes"].ptr))
+
+    def spectral(self, ncol):
+        """The last run_spectral: lw, sw [ncol][sets][6][n] (W m-2 per cm-1, GRT_FLUXES_PER_BAND row order), lw_bins,
+        sw_bins [ncol][sets][6][num_bins] (W m-2) and fluxes [ncol][12 or 24] (grt_pipeline_run's or run_allsky's layout)."""
+        self.sync()
+        sets, nb_lw, nb_sw = self.spec["shape"]
+        nl, ns = self.nw
+        sp = self.spec["spectral"].to_host((ncol, sets, 6 * (nl + ns)))
+        out = {"lw": sp[:, :, :6 * nl].reshape(ncol, sets, 6, nl).copy(),
+               "sw": sp[:, :, 6 * nl:].reshape(ncol, sets, 6, ns).copy()}
+        if self.spec["binned"] is not None:
+            bn = self.spec["binned"].to_host((ncol, sets, 6 * (nb_lw + nb_sw)))
+        else:
+            bn = np.zeros((ncol, sets, 0))
+        out["lw_bins"] = bn[:, :, :6 * nb_lw].reshape(ncol, sets, 6, nb_lw).copy()
+        out["sw_bins"] = bn[:, :, 6 * nb_lw:].reshape(ncol, sets, 6, nb_sw).copy()
+        out["fluxes"] = self.spec["fluxes"].to_host((ncol, sets * GRT_FLUXES_PER_COLUMN))
+        return out
+
     def views(self, band):
         ptrs = [C.c_void_p() for _ in range(6)]
-        if not self.spectral:
+        if not self.keep_spectra:
             check(self.lib.grt_pipeline_views(self.p, band, C.byref(ptrs[0]), *([None] * 5)))
             return {"tau_gas": ptrs[0].value}
         check(self.lib.grt_pipeline_views(self.p, band, *[C.byref(p) for p in ptrs]))
@@ -581,6 +626,10 @@ class Pipeline:
             buf.free()
         self.prof = None
         self.allsky_prof = None
+        for k in ("spectral", "binned", "fluxes"):
+            if self.spec is not None and self.spec[k] is not None:
+                self.spec[k].free()
+        self.spec = None
         if self.allsky is not None:
             self.allsky.free()
             self.allsky = None

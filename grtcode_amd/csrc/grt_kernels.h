@@ -256,7 +256,8 @@ typedef struct GrtLwArgs
     uint64_t optics_stride;
     double const *t_layers, *t_levels, *t_surf;
     double const *emis; uint64_t emis_stride;
-    double *flux_up, *flux_down;    /* [ncol][V][nw]; NULL in the fused form: nothing spectral is stored */
+    double *flux_up, *flux_down;    /* [ncol][V][nw]; NULL in the fused form: nothing spectral is stored (spectral six-row
+                                       form: the six rows' bases, GrtFormKind) */
     uint64_t flux_stride;
     int user_level;                 /* -1: none */
     /* Fused clear-sky form (driver.c:360-424 + 285-356 with -integrated in one kernel, GRT_SOLVER_FUSED): the
@@ -290,7 +291,7 @@ typedef struct GrtSwArgs
     double const *alb_dir, *alb_dif; uint64_t alb_stride;
     double const *tsi;              /* [ncol] */
     double const *solar;            /* [nw] */
-    double *flux_up, *flux_down; uint64_t flux_stride;   /* NULL in the fused form */
+    double *flux_up, *flux_down; uint64_t flux_stride;   /* NULL in the fused form (spectral six-row form: as GrtLwArgs) */
     int user_level;
     /* fused clear-sky form, as in GrtLwArgs; the first sweep parks, per column, its downward-beam reflectances
        (2 V rows of nw) and the five properties of every layer (5 L rows) in park [ncol][2 V + 5 L][nw]: the second
@@ -353,16 +354,21 @@ typedef enum GrtSolverForm
     GRT_SOLVER_FUSED,       /* fused clear-sky, six output rows */
     GRT_SOLVER_PROFILE,     /* fused clear-sky, every level's up and down flux */
     GRT_SOLVER_ALLSKY,      /* fused all-sky, six output rows */
-    GRT_SOLVER_ALLSKY_PROFILE   /* fused all-sky, every level's up and down flux */
+    GRT_SOLVER_ALLSKY_PROFILE,  /* fused all-sky, every level's up and down flux */
+    GRT_SOLVER_SPECTRAL,    /* fused clear-sky, six output rows, and the six rows at every point */
+    GRT_SOLVER_ALLSKY_SPECTRAL  /* fused all-sky, six output rows, and the six rows at every point */
 } GrtSolverForm;
-/* what a form is: fused (the kernel integrates, nothing spectral leaves), profile (every level's fluxes), all-sky (clouds) */
-typedef struct GrtFormKind { int fused, profile, allsky; } GrtFormKind;
+/* what a form is: fused (the kernel integrates), profile (every level's fluxes), all-sky (clouds), spectral (a fused
+   six-row form that also stores its six rows at every point: up TOA, surface, user at flux_up + c flux_stride + k nw,
+   k = 0, 1, 2, down at flux_down + ...; grt_pipeline_run_spectral) */
+typedef struct GrtFormKind { int fused, profile, allsky, spectral; } GrtFormKind;
 static inline GrtFormKind grt_form_kind(GrtSolverForm form)
 {
     GrtFormKind k;
     k.profile = form == GRT_SOLVER_PROFILE || form == GRT_SOLVER_ALLSKY_PROFILE;
-    k.allsky = form == GRT_SOLVER_ALLSKY || form == GRT_SOLVER_ALLSKY_PROFILE;
-    k.fused = form == GRT_SOLVER_FUSED || k.profile || k.allsky;
+    k.spectral = form == GRT_SOLVER_SPECTRAL || form == GRT_SOLVER_ALLSKY_SPECTRAL;
+    k.allsky = form == GRT_SOLVER_ALLSKY || form == GRT_SOLVER_ALLSKY_PROFILE || form == GRT_SOLVER_ALLSKY_SPECTRAL;
+    k.fused = form == GRT_SOLVER_FUSED || k.profile || k.allsky || k.spectral;
     return k;
 }
 /* whether an all-sky form can read `c` */
@@ -391,6 +397,23 @@ int grt_launch_clear_sky_optics(void *stream, int num_layers, int ncol, double w
 int grt_launch_integrate_rows(void *stream, double const *const *rows_dev, int nrows,
                               uint64_t nw, double dw, double *out, int group, int out_stride,
                               int out_offset);
+/* Wavenumber bins of spectral rows (grt_pipeline_run_spectral), deterministic and in the fused solvers' association: bin b
+   of a row is sum_i x_i w_i over the row's points, w_i = dw inside edges[b] .. edges[b+1], dw/2 at those two points, 0
+   elsewhere; summed per 128-point solver block as block_partials does (a 64-lane shuffle tree, then wave 0 + wave 1),
+   then the bin's blocks in order from its first block as reduce_partials does.  A bin over the whole grid is the six-row
+   form's integral to the bit.  Row r (of nrows) is in + (r/6) in_stride + (r%6) nw; its bins go to
+   out + (r/6) out_stride + (r%6) nbins + b.  table_dev: grt_bin_table's ints; partials: nrows x the partial sums
+   per row that grt_bin_table returns, doubles. */
+size_t grt_bin_table_ints(int nbins, uint64_t nw);
+/* the table of edges_h [nbins + 1] (host, strictly increasing in 0 .. nw - 1) into table_h [grt_bin_table_ints]; returns
+   the partial sums per row */
+size_t grt_bin_table(int const *edges_h, int nbins, uint64_t nw, int *table_h);
+int grt_launch_bin_rows(void *stream, double const *in, uint64_t in_stride, int nrows, uint64_t nw, double dw,
+                        int nbins, int const *table_dev, size_t partials_per_row, double *partials, double *out,
+                        uint64_t out_stride);
+/* out + (r/6) out_stride + (r%6) nw  <-  rows_dev[r] [nw], r < nrows (the materialised form's spectral rows) */
+int grt_launch_copy_rows(void *stream, double const *const *rows_dev, int nrows, uint64_t nw, double *out,
+                         uint64_t out_stride);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,8 @@
 // SURVEY.md §8a19 prices it at 1 944 B per wavenumber at 60 layers; measured it is a latency
 // chain -- 120 dependent layer steps with six fp64 exp each on 26 000 threads at 1 cm-1 -- which is why column
 // batches share a launch.  lw_kernel<true, false> is the fused form of the production pipeline, lw_kernel<true, false, true>
-// its all-sky form, lw_kernel<true, true> and lw_kernel<true, true, true> the profile forms of the two.
+// its all-sky form, lw_kernel<true, true> and lw_kernel<true, true, true> the profile forms of the two,
+// lw_kernel<true, false, false, true> and lw_kernel<true, false, true, true> the spectral six-row forms of the two.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -99,7 +100,8 @@ __device__ __forceinline__ double surface_step(double (&I)[4], double emis, doub
 // PROFILE (fused form only): every level's upward and downward flux leaves instead, 2 V rows per column (LevelSink).
 // ALLSKY (fused forms, six-row or profile): the liquid and ice cloud objects join per layer (LayerOptics).  Only
 // layer_tau changes: what leaves the kernel is the six-row or the profile form's.
-template <bool FUSED, bool PROFILE, bool ALLSKY = false, typename... Clouds>
+// SPECTRAL (fused six-row form): the six rows also leave at every point, unweighted (LevelSink).
+template <bool FUSED, bool PROFILE, bool ALLSKY = false, bool SPECTRAL = false, typename... Clouds>
 __global__ __launch_bounds__(kSolverBlock) void lw_kernel(GrtLwArgs a, Clouds... clouds)
 {
     uint64_t const i = (uint64_t)blockIdx.x*kSolverBlock + threadIdx.x;
@@ -118,7 +120,7 @@ __global__ __launch_bounds__(kSolverBlock) void lw_kernel(GrtLwArgs a, Clouds...
     double const *tl = a.t_layers + (uint64_t)col*L;
     double const *tv = a.t_levels + (uint64_t)col*V;
     double const emis = a.emis[(uint64_t)col*a.emis_stride + ii];
-    LevelSink<FUSED, PROFILE> sink(a, col, i, live);
+    LevelSink<FUSED, PROFILE, SPECTRAL> sink(a, col, i, live);
     LayerOptics<FUSED, ALLSKY> const optics(a, cloud_args(clouds...), col, ii);   // (fused forms)
 
     // absorption optical depth of layer j: tau (1 - omega)  (longwave.c:252)
@@ -274,6 +276,7 @@ extern "C" int grt_launch_lw(void *stream, GrtSolverForm form, GrtLwArgs const *
     if (a->ncol < 1 || a->nw < 2 ||
         (k.fused ? (a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr)
                  : (a->flux_up == nullptr || a->flux_down == nullptr)) ||
+        (k.spectral && (a->flux_up == nullptr || a->flux_down == nullptr)) ||
         (form == GRT_SOLVER_LAYERS && (a->layer_terms == nullptr || cells > 0xffffffffull*kTermsBlock)) ||
         (k.profile && (a->num_levels < 2 || lds > 65536)) || (k.allsky && !grt_cloud_args_ok(c)))
     {
@@ -299,10 +302,16 @@ extern "C" int grt_launch_lw(void *stream, GrtSolverForm form, GrtLwArgs const *
         hipLaunchKernelGGL((lw_kernel<true, true>), grid, dim3(kSolverBlock), lds, s, *a);
         break;
     case GRT_SOLVER_ALLSKY:
-        hipLaunchKernelGGL((lw_kernel<true, false, true, GrtCloudArgs>), grid, dim3(kSolverBlock), 0, s, *a, *c);
+        hipLaunchKernelGGL((lw_kernel<true, false, true, false, GrtCloudArgs>), grid, dim3(kSolverBlock), 0, s, *a, *c);
         break;
     case GRT_SOLVER_ALLSKY_PROFILE:
-        hipLaunchKernelGGL((lw_kernel<true, true, true, GrtCloudArgs>), grid, dim3(kSolverBlock), lds, s, *a, *c);
+        hipLaunchKernelGGL((lw_kernel<true, true, true, false, GrtCloudArgs>), grid, dim3(kSolverBlock), lds, s, *a, *c);
+        break;
+    case GRT_SOLVER_SPECTRAL:
+        hipLaunchKernelGGL((lw_kernel<true, false, false, true>), grid, dim3(kSolverBlock), 0, s, *a);
+        break;
+    case GRT_SOLVER_ALLSKY_SPECTRAL:
+        hipLaunchKernelGGL((lw_kernel<true, false, true, true, GrtCloudArgs>), grid, dim3(kSolverBlock), 0, s, *a, *c);
         break;
     default:
         return (int)hipErrorInvalidValue;

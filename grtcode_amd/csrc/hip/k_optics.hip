@@ -1,5 +1,5 @@
 // k_optics.hip -- streaming (HBM-bound) optics kernels for gfx950: Rayleigh, optics
-// combination, sub-sampling, the fused clear-sky combine and the spectral trapezoid.
+// combination, sub-sampling, the fused clear-sky combine, the spectral trapezoid and its wavenumber bins.
 // One thread per wavenumber (or per element), coalesced fp64 reads/writes, grid-stride
 // so one launch covers any grid size with <= 2048 workgroups.
 #include <hip/hip_runtime.h>
@@ -219,6 +219,108 @@ __global__ __launch_bounds__(64) void reduce_partials_kernel(double const *parti
     }
 }
 
+// ---- wavenumber bins of spectral rows (grt_pipeline_run_spectral), in the fused solvers' association ----
+// Bin table (grt_bin_table): per bin {first edge, last edge, offset of its partial sums in a row's, first block}, then
+// per 128-point solver block {first bin, one past the last bin} that has a point in the block.  A bin over the whole
+// grid takes the fused six-row form's weights, block trees and block order: the same bits as its integral.
+constexpr int kBinChunk = 64;           // bins of one block summed before their block sums are stored
+constexpr int kBinRowGroups = 32;       // gridDim.y of the two binning launches
+
+inline unsigned bin_blocks(uint64_t nw)
+{
+    return (unsigned)((nw + kSolverBlock - 1)/kSolverBlock);
+}
+
+// one workgroup per (128-point block, row): per bin that has a point in the block, sum_i x_i w_i by block_partials'
+// tree, stored at partials[row P + offset(bin) + block - first_block(bin)]
+__global__ __launch_bounds__(kSolverBlock) void bin_partials_kernel(double const *in, uint64_t in_stride, int nrows,
+                                                                    uint64_t nw, double dw, int nbins, int const *tab,
+                                                                    uint64_t P, double *partials)
+{
+    __shared__ double part[kBinChunk][kSolverBlock/64];
+    unsigned const block = blockIdx.x;
+    int const b_lo = tab[4*nbins + 2*block], b_hi = tab[4*nbins + 2*block + 1];
+    long long const i = (long long)block*kSolverBlock + threadIdx.x;
+    bool const live = i < (long long)nw;
+    for (int r = blockIdx.y; r < nrows; r += gridDim.y)
+    {
+        double const x = live ? in[(uint64_t)(r/6)*in_stride + (uint64_t)(r % 6)*nw + i] : 0.;
+        double *prow = partials + (uint64_t)r*P;
+        for (int b0 = b_lo; b0 < b_hi; b0 += kBinChunk)
+        {
+            int const nb = b_hi - b0 < kBinChunk ? b_hi - b0 : kBinChunk;
+            for (int q = 0; q < nb; ++q)
+            {
+                int const *e = tab + 4*(b0 + q);
+                // (trapezoid_weight's doubles: dw/2 at the bin's two edges, dw between them)
+                double const w = (i == e[0] || i == e[1]) ? 0.5*dw : ((i > e[0] && i < e[1]) ? dw : 0.);
+                double s = x*w;
+                for (int off = 32; off > 0; off >>= 1)
+                {
+                    s += __shfl_down(s, off, 64);
+                }
+                if ((threadIdx.x & 63) == 0)
+                {
+                    part[q][threadIdx.x >> 6] = s;
+                }
+            }
+            __syncthreads();
+            if ((int)threadIdx.x < nb)
+            {
+                int const *e = tab + 4*(b0 + threadIdx.x);
+                double s = part[threadIdx.x][0];
+                for (int k = 1; k < kSolverBlock/64; ++k)
+                {
+                    s += part[threadIdx.x][k];
+                }
+                prow[e[2] + block - e[3]] = s;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// one wavefront per (bin, row): the bin's block sums in block order, reduce_partials_kernel's association
+__global__ __launch_bounds__(64) void bin_reduce_kernel(int nrows, int nbins, int const *tab, uint64_t P,
+                                                        double const *partials, double *out, uint64_t out_stride)
+{
+    int const b = blockIdx.x;
+    int const *e = tab + 4*b;
+    unsigned const nblk = (unsigned)(e[1]/kSolverBlock - e[3]) + 1;
+    for (int r = blockIdx.y; r < nrows; r += gridDim.y)
+    {
+        double const *p = partials + (uint64_t)r*P + e[2];
+        double s = 0.;
+        for (unsigned k = threadIdx.x; k < nblk; k += 64)
+        {
+            s += p[k];
+        }
+        for (int off = 32; off > 0; off >>= 1)
+        {
+            s += __shfl_down(s, off, 64);
+        }
+        if (threadIdx.x == 0)
+        {
+            out[(uint64_t)(r/6)*out_stride + (uint64_t)(r % 6)*nbins + b] = s;
+        }
+    }
+}
+
+// the materialised form's spectral rows: out + (r/6) out_stride + (r%6) nw <- rows[r]
+__global__ __launch_bounds__(kBlock) void copy_rows_kernel(double const *const *rows, int nrows, uint64_t nw, double *out,
+                                                           uint64_t out_stride)
+{
+    uint64_t const i = (uint64_t)blockIdx.x*kBlock + threadIdx.x;
+    if (i >= nw)
+    {
+        return;
+    }
+    for (int r = blockIdx.y; r < nrows; r += gridDim.y)
+    {
+        out[(uint64_t)(r/6)*out_stride + (uint64_t)(r % 6)*nw + i] = rows[r][i];
+    }
+}
+
 // Last step of grt_pipeline_run_profiles (sets = 1) and grt_pipeline_run_allsky_profiles (sets = 2: clear sky, then
 // all-sky): one thread per (column, set, band, layer j) reads the band's level fluxes
 // levels[c][set][2 band + {0: up, 1: down}][V] and forms the heating rate of layer j, between levels j (upper) and j + 1,
@@ -408,5 +510,81 @@ extern "C" int grt_launch_integrate_rows(void *stream, double const *const *rows
     }
     hipLaunchKernelGGL(integrate_rows_kernel, dim3(nrows), dim3(kBlock), 0, (hipStream_t)stream,
                        rows_dev, nw, dw, out, group, out_stride, out_offset);
+    return (int)hipGetLastError();
+}
+
+extern "C" size_t grt_bin_table_ints(int nbins, uint64_t nw)
+{
+    return 4*(size_t)nbins + 2*(size_t)bin_blocks(nw);
+}
+
+extern "C" size_t grt_bin_table(int const *edges_h, int nbins, uint64_t nw, int *table_h)
+{
+    unsigned const nblocks = bin_blocks(nw);
+    int *blk = table_h + 4*(size_t)nbins;
+    for (unsigned k = 0; k < nblocks; ++k)
+    {
+        blk[2*k] = nbins;
+        blk[2*k + 1] = 0;
+    }
+    size_t off = 0;
+    for (int b = 0; b < nbins; ++b)
+    {
+        int const e0 = edges_h[b], e1 = edges_h[b + 1];
+        int const first = e0/kSolverBlock, last = e1/kSolverBlock;
+        int *t = table_h + 4*(size_t)b;
+        t[0] = e0;
+        t[1] = e1;
+        t[2] = (int)off;
+        t[3] = first;
+        off += (size_t)(last - first + 1);
+        for (int k = first; k <= last; ++k)
+        {
+            blk[2*k] = b < blk[2*k] ? b : blk[2*k];
+            blk[2*k + 1] = b + 1 > blk[2*k + 1] ? b + 1 : blk[2*k + 1];
+        }
+    }
+    for (unsigned k = 0; k < nblocks; ++k)
+    {
+        if (blk[2*k] >= blk[2*k + 1])
+        {
+            blk[2*k] = blk[2*k + 1] = 0;            // (no bin has a point in this block)
+        }
+    }
+    return off;
+}
+
+extern "C" int grt_launch_bin_rows(void *stream, double const *in, uint64_t in_stride, int nrows, uint64_t nw, double dw,
+                                   int nbins, int const *table_dev, size_t partials_per_row, double *partials,
+                                   double *out, uint64_t out_stride)
+{
+    if (nrows < 1 || nbins < 1)
+    {
+        return 0;
+    }
+    if (in == nullptr || table_dev == nullptr || partials == nullptr || out == nullptr || nw < 2)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    // (each workgroup takes every kBinRowGroups-th row: a few thousand workgroups per launch, not one per row)
+    unsigned const gy = (unsigned)(nrows < kBinRowGroups ? nrows : kBinRowGroups);
+    hipStream_t const s = (hipStream_t)stream;
+    hipLaunchKernelGGL(bin_partials_kernel, dim3(bin_blocks(nw), gy), dim3(kSolverBlock), 0, s, in, in_stride, nrows, nw,
+                       dw, nbins, table_dev, (uint64_t)partials_per_row, partials);
+    hipLaunchKernelGGL(bin_reduce_kernel, dim3((unsigned)nbins, gy), dim3(64), 0, s, nrows, nbins, table_dev,
+                       (uint64_t)partials_per_row, (double const *)partials, out, out_stride);
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_copy_rows(void *stream, double const *const *rows_dev, int nrows, uint64_t nw, double *out,
+                                    uint64_t out_stride)
+{
+    if (nrows < 1)
+    {
+        return 0;
+    }
+    unsigned const gy = (unsigned)(nrows < 65535 ? nrows : 65535);
+    hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)((nw + kBlock - 1)/kBlock), gy), dim3(kBlock), 0,
+                       (hipStream_t)stream, rows_dev, nrows, nw, out, out_stride);
     return (int)hipGetLastError();
 }

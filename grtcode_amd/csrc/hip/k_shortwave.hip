@@ -17,7 +17,8 @@
 // not HBM-bound.  sw_kernel<true, false>, the fused form of the production pipeline, therefore trades bytes for flops: its first
 // sweep parks the five properties of every layer with the reflectances and its second sweep reads them back (the same
 // doubles: identical fluxes) -- 0.69 instead of 1.04 ms for 8 columns, at 4.2 TB/s.  sw_kernel<true, false, true> is its
-// all-sky form, sw_kernel<true, true> and sw_kernel<true, true, true> the profile forms of the two.
+// all-sky form, sw_kernel<true, true> and sw_kernel<true, true, true> the profile forms of the two, sw_kernel<true, false, false,
+// true> and sw_kernel<true, false, true, true> the spectral six-row forms of the two.
 // The in-kernel range checks of the reference are no-ops on device builds
 // (debug.h:105-116) and are not restated.
 #include <hip/hip_runtime.h>
@@ -244,7 +245,8 @@ __device__ __forceinline__ void put_level(Sink &sink, int lev, double up, double
 // ALLSKY (fused forms, six-row or profile): the liquid and ice cloud objects join per layer (LayerOptics), as in lw_kernel;
 // the one-sweep and two-sweep rule is the form's own.  props_of is the only place that reads the cloud tables, and the
 // fused forms call it in their first (or only) sweep: the two-sweep forms' second sweep reads the parked properties.
-template <bool FUSED, bool PROFILE, bool ALLSKY = false, typename... Clouds>
+// SPECTRAL (fused six-row form): the six rows also leave at every point, unweighted (LevelSink).
+template <bool FUSED, bool PROFILE, bool ALLSKY = false, bool SPECTRAL = false, typename... Clouds>
 __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Clouds... clouds)
 {
     uint64_t const i = (uint64_t)blockIdx.x*kSolverBlock + threadIdx.x;
@@ -272,7 +274,7 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Clouds...
     // divisions a layer, which is what this kernel's time is made of)
     double *pp = FUSED ? a.park + ((uint64_t)col*park_rows + 2*(uint64_t)V)*nw + ii : nullptr;
     int const user = a.user_level;
-    LevelSink<FUSED, PROFILE> sink(a, col, i, live);
+    LevelSink<FUSED, PROFILE, SPECTRAL> sink(a, col, i, live);
     LayerOptics<FUSED, ALLSKY> const optics(a, cloud_args(clouds...), col, ii);   // (fused forms)
 
     auto props_of = [&](int j) -> LayerProps
@@ -528,6 +530,7 @@ extern "C" int grt_launch_sw(void *stream, GrtSolverForm form, GrtSwArgs const *
     if (a->ncol < 1 || a->nw < 2 ||
         (k.fused ? (a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr || (park && a->park == nullptr))
                  : (a->flux_up == nullptr || a->flux_down == nullptr)) ||
+        (k.spectral && (a->flux_up == nullptr || a->flux_down == nullptr)) ||
         (form == GRT_SOLVER_LAYERS && (a->layer_props == nullptr || cells > 0xffffffffull*kPropsBlock ||
                                        a->omega == nullptr || a->g == nullptr)) ||
         (k.profile && (a->num_levels < 2 || lds > 65536)) || (k.allsky && !grt_cloud_args_ok(c)))
@@ -554,10 +557,16 @@ extern "C" int grt_launch_sw(void *stream, GrtSolverForm form, GrtSwArgs const *
         hipLaunchKernelGGL((sw_kernel<true, true>), grid, dim3(kSolverBlock), lds, s, *a);
         break;
     case GRT_SOLVER_ALLSKY:
-        hipLaunchKernelGGL((sw_kernel<true, false, true, GrtCloudArgs>), grid, dim3(kSolverBlock), 0, s, *a, *c);
+        hipLaunchKernelGGL((sw_kernel<true, false, true, false, GrtCloudArgs>), grid, dim3(kSolverBlock), 0, s, *a, *c);
         break;
     case GRT_SOLVER_ALLSKY_PROFILE:
-        hipLaunchKernelGGL((sw_kernel<true, true, true, GrtCloudArgs>), grid, dim3(kSolverBlock), lds, s, *a, *c);
+        hipLaunchKernelGGL((sw_kernel<true, true, true, false, GrtCloudArgs>), grid, dim3(kSolverBlock), lds, s, *a, *c);
+        break;
+    case GRT_SOLVER_SPECTRAL:
+        hipLaunchKernelGGL((sw_kernel<true, false, false, true>), grid, dim3(kSolverBlock), 0, s, *a);
+        break;
+    case GRT_SOLVER_ALLSKY_SPECTRAL:
+        hipLaunchKernelGGL((sw_kernel<true, false, true, true, GrtCloudArgs>), grid, dim3(kSolverBlock), 0, s, *a, *c);
         break;
     default:
         return (int)hipErrorInvalidValue;

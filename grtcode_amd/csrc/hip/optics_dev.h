@@ -315,10 +315,13 @@ struct LayerOptics
 // summed across the wave where the sweep produces it, the waves' sums wait in dynamic LDS (2 V x kSolverBlock/64
 // doubles) and finish() stores the block's sums at partials[(c*2 V + r)*nblocks + block], r = level (up), V + level
 // (down).  Same association as block_partials: the six-row form's rows come out the same to the bit.
-template <bool FUSED, bool PROFILE>
+// SPECTRAL (fused six-row form only): finish() also stores each live point's six values, unweighted, to the caller's
+// rows -- up TOA, surface, user at flux_up + c flux_stride + k nw (k = 0, 1, 2), down at flux_down + ... -- before it
+// weights them (grt_pipeline_run_spectral).
+template <bool FUSED, bool PROFILE, bool SPECTRAL = false>
 struct LevelSink
 {
-    double *fu, *fd;            // spectral forms: flux_up / flux_down at this thread's point
+    double *fu, *fd;            // spectral forms (and SPECTRAL): flux_up / flux_down at this thread's point
     uint64_t nw, i;
     int V, user, col;
     double pwt;                 // PROFILE: this point's trapezoid weight
@@ -334,8 +337,8 @@ struct LevelSink
         nw = a.nw;
         V = a.num_levels;
         user = a.user_level;
-        fu = FUSED ? nullptr : a.flux_up + (uint64_t)col*a.flux_stride + i;
-        fd = FUSED ? nullptr : a.flux_down + (uint64_t)col*a.flux_stride + i;
+        fu = FUSED && !SPECTRAL ? nullptr : a.flux_up + (uint64_t)col*a.flux_stride + i;
+        fd = FUSED && !SPECTRAL ? nullptr : a.flux_down + (uint64_t)col*a.flux_stride + i;
         pwt = PROFILE ? trapezoid_weight(i, nw, a.dw, live) : 0.;
 #pragma unroll
         for (int k = 0; k < 6; ++k)
@@ -402,6 +405,15 @@ struct LevelSink
         }
         else if (FUSED)
         {
+            if (SPECTRAL && live)
+            {
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                {
+                    fu[(uint64_t)k*nw] = out[k];
+                    fd[(uint64_t)k*nw] = out[3 + k];
+                }
+            }
             double const wt = trapezoid_weight(i, nw, a.dw, live);
 #pragma unroll
             for (int k = 0; k < 6; ++k)

@@ -51,6 +51,13 @@ typedef struct GrtBand
     double *cloud_key;     /* host: the band limits cloud_map was built for (B, num_ice_bands, liquid lo/hi, ice lo/hi) */
     size_t cloud_key_n;
     double *cloud_block;   /* materialised form: liquid and ice tau, omega, g [6][cols][L][n], Rayleigh [3][L][n], zeros [L][n] */
+    /* grt_pipeline_run_spectral's bins: */
+    int *bin_edges;        /* host: the edges bin_table was built for [bin_count + 1] */
+    int bin_count;
+    int *bin_table;        /* device: grt_bin_table of those edges */
+    size_t bin_per_row;    /* partial sums per row */
+    double *bin_partials;  /* [max_cols][6][bin_cap] */
+    size_t bin_cap;
 } GrtBand;
 
 struct GrtPipeline
@@ -260,6 +267,9 @@ static void grt_pipeline_release(GrtPipeline_t **pipeline)
         grt_dev_free(p->device, p->band[b].cloud_map);
         grt_dev_free(p->device, p->band[b].cloud_block);
         free(p->band[b].cloud_key);
+        grt_dev_free(p->device, p->band[b].bin_table);
+        grt_dev_free(p->device, p->band[b].bin_partials);
+        free(p->band[b].bin_edges);
     }
     grt_dev_free(p->device, p->cloud_d);
     grt_host_free_pinned(p->cloud_h);
@@ -494,10 +504,35 @@ static int park_block(GrtPipeline_t *p, GrtBand *b)
     return GRTCODE_SUCCESS;
 }
 
+/* grt_pipeline_run_spectral's outputs of one pass: the spectral rows and bins of set `set` of `sets` */
+typedef struct SpectralOut
+{
+    double *spectral, *binned;
+    int sets, set;
+    int const *edges[2];
+    int num_bins[2];
+} SpectralOut;
+
+/* where band bi's six spectral rows (or bins, per = bins) of column 0 start in a [ncol][sets][6 per_lw + 6 per_sw]
+   block, and the doubles from one column to the next */
+static size_t spectral_offset(SpectralOut const *so, int bi, size_t per_lw, size_t per_sw, size_t *col_stride)
+{
+    size_t const set_doubles = 6*(per_lw + per_sw);
+    *col_stride = (size_t)so->sets*set_doubles;
+    return (size_t)so->set*set_doubles + (bi == 1 ? 6*per_lw : 0);
+}
+
+static size_t band_points(GrtPipeline_t const *p, int bi)
+{
+    return p->band[bi].gas != NULL ? p->band[bi].n : 0;
+}
+
 /* the band's solver in `form` (GRT_SOLVER_CHAINS: the spectral form), timed under profile tag 3/4, or 8/9 with clouds;
-   the profile forms share the band's park block with the two-sweep six-row forms (the passes run in stream order) */
+   the profile forms share the band's park block with the two-sweep six-row forms (the passes run in stream order); the
+   spectral six-row forms store their rows where so places the band's */
 static int band_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtSolverForm form, int defer,
-                       GrtContinua const *continua, GrtCloudArgs const *clouds, double *partials)
+                       GrtContinua const *continua, GrtCloudArgs const *clouds, double *partials,
+                       SpectralOut const *so)
 {
     GrtFormKind const k = grt_form_kind(form);
     void *s = grt_dev_stream(p->device);
@@ -507,6 +542,13 @@ static int band_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtSolverFor
         GrtLwArgs a;
         lw_args(p, b, C, k.fused, defer, continua, &a);
         a.partials = partials;
+        if (k.spectral)
+        {
+            size_t stride;
+            a.flux_up = so->spectral + spectral_offset(so, bi, band_points(p, 0), band_points(p, 1), &stride);
+            a.flux_down = a.flux_up + 3*b->n;
+            a.flux_stride = stride;
+        }
         slot = grt_profile_begin(s, clouds ? 8 : 3);
         krc = grt_launch_lw(s, form, &a, clouds);
     }
@@ -515,6 +557,13 @@ static int band_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtSolverFor
         GrtSwArgs a;
         sw_args(p, b, C, k.fused, defer, continua, &a);
         a.partials = partials;
+        if (k.spectral)
+        {
+            size_t stride;
+            a.flux_up = so->spectral + spectral_offset(so, bi, band_points(p, 0), band_points(p, 1), &stride);
+            a.flux_down = a.flux_up + 3*b->n;
+            a.flux_stride = stride;
+        }
         if (k.profile || (k.fused && !grt_sw_one_sweep(&a)))
         {
             GRT_TRY(park_block(p, b));
@@ -772,6 +821,112 @@ static int band_allsky_optics(GrtPipeline_t *p, GrtBand *b, int C, GrtCloudArgs 
     return GRTCODE_SUCCESS;
 }
 
+/* ---- spectral rows and bins (grt_pipeline_run_spectral) ------------------------------------------------------------ */
+
+/* the band's bin table for these edges (built and uploaded when they differ from the last call's) and room for the partial
+   sums of max_cols x 6 rows */
+static int band_bins(GrtPipeline_t *p, GrtBand *b, int const *edges, int nbins)
+{
+    void *s = grt_dev_stream(p->device);
+    if (b->bin_table == NULL || b->bin_count != nbins ||
+        memcmp(b->bin_edges, edges, sizeof(int)*((size_t)nbins + 1)) != 0)
+    {
+        size_t const nt = grt_bin_table_ints(nbins, b->n);
+        int *tab = malloc(sizeof(int)*nt);
+        int *key = malloc(sizeof(int)*((size_t)nbins + 1));
+        if (tab == NULL || key == NULL)
+        {
+            free(tab);
+            free(key);
+            GRT_FAIL(GRTCODE_NULL_ERR, "out of host memory for the table of %d bins.", nbins);
+        }
+        size_t const per_row = grt_bin_table(edges, nbins, b->n, tab);
+        memcpy(key, edges, sizeof(int)*((size_t)nbins + 1));
+        /* (the last batch's kernels may still read the old table; then tab is freed: wait both times) */
+        int rc = grt_dev_sync(p->device, s);
+        if (rc == GRTCODE_SUCCESS)
+        {
+            grt_dev_free(p->device, b->bin_table);
+            b->bin_table = NULL;
+            free(b->bin_edges);
+            b->bin_edges = NULL;
+            void *t = NULL;
+            rc = grt_dev_alloc(p->device, &t, sizeof(int)*nt);
+            b->bin_table = t;
+        }
+        if (rc == GRTCODE_SUCCESS) rc = grt_dev_upload(p->device, b->bin_table, tab, sizeof(int)*nt, s);
+        if (rc == GRTCODE_SUCCESS) rc = grt_dev_sync(p->device, s);
+        free(tab);
+        if (rc != GRTCODE_SUCCESS)
+        {
+            free(key);
+            grt_dev_free(p->device, b->bin_table);
+            b->bin_table = NULL;
+            GRT_TRY(rc);
+        }
+        b->bin_edges = key;
+        b->bin_count = nbins;
+        b->bin_per_row = per_row;
+    }
+    if (b->bin_per_row > b->bin_cap)
+    {
+        GRT_TRY(grt_dev_sync(p->device, s));
+        grt_dev_free(p->device, b->bin_partials);
+        b->bin_partials = NULL;
+        b->bin_cap = 0;
+        void *pt = NULL;
+        GRT_TRY(grt_dev_alloc(p->device, &pt, sizeof(double)*(size_t)p->max_cols*6*b->bin_per_row));
+        b->bin_partials = pt;
+        b->bin_cap = b->bin_per_row;
+    }
+    return GRTCODE_SUCCESS;
+}
+
+/* One solve of a band for grt_pipeline_run_spectral: the six rows at every point into the caller's spectral block, the
+   -integrated six into out, and the bins.  Fused form: the spectral six-row solver (its rows stored where it weights
+   them) and the fixed-order sum of its partial sums; materialised form: the spectral solver, its rows 0, L and the user
+   level copied out, the row-wise trapezoid.  The bins are summed from the stored rows by the binning kernel (profile
+   tag 10). */
+static int band_solve_spectral(GrtPipeline_t *p, GrtBand *b, int bi, int C, int defer, GrtContinua const *continua,
+                               GrtCloudArgs const *clouds, double *out, int out_stride, int out_offset,
+                               SpectralOut const *so)
+{
+    void *s = grt_dev_stream(p->device);
+    size_t stride;
+    double *rows = so->spectral + spectral_offset(so, bi, band_points(p, 0), band_points(p, 1), &stride);
+    if (!p->keep_spectra)
+    {
+        GRT_TRY(band_solver(p, b, bi, C, clouds ? GRT_SOLVER_ALLSKY_SPECTRAL : GRT_SOLVER_SPECTRAL, defer, continua,
+                            clouds, b->partials, so));
+        GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, b->partials, C*GRT_FLUXES_PER_BAND, b->nblocks, out,
+                                                         GRT_FLUXES_PER_BAND, out_stride, out_offset),
+                              "flux reduction kernel"));
+    }
+    else
+    {
+        GRT_TRY(clouds ? band_allsky_optics(p, b, C, clouds) : band_clear_sky_optics(p, b, C));
+        GRT_TRY(band_solver(p, b, bi, C, GRT_SOLVER_CHAINS, defer, continua, clouds, NULL, NULL));
+        GRT_TRY(grt_dev_check(grt_launch_copy_rows(s, (double const *const *)b->rows_d, C*GRT_FLUXES_PER_BAND, b->n,
+                                                   rows, stride), "spectral row copy kernel"));
+        GRT_TRY(grt_dev_check(grt_launch_integrate_rows(s, (double const *const *)b->rows_d, C*GRT_FLUXES_PER_BAND, b->n,
+                                                        b->gas->grid.dw, out, GRT_FLUXES_PER_BAND, out_stride,
+                                                        out_offset), "spectral integration kernel"));
+    }
+    int const nbins = so->num_bins[bi];
+    if (nbins > 0)
+    {
+        GRT_TRY(band_bins(p, b, so->edges[bi], nbins));
+        size_t bstride;
+        double *binned = so->binned + spectral_offset(so, bi, (size_t)so->num_bins[0], (size_t)so->num_bins[1], &bstride);
+        int const slot = grt_profile_begin(s, 10);
+        int const krc = grt_launch_bin_rows(s, rows, stride, C*GRT_FLUXES_PER_BAND, b->n, b->gas->grid.dw, nbins,
+                                            b->bin_table, b->bin_per_row, b->bin_partials, binned, bstride);
+        grt_profile_end(s, slot);
+        GRT_TRY(grt_dev_check(krc, "spectral binning kernel"));
+    }
+    return GRTCODE_SUCCESS;
+}
+
 /* ---- the run ------------------------------------------------------------------------------------------------------ */
 
 /* One solve of a band on this run's tau_gas: Rayleigh, add_optics({gas, rayleigh}) -- or, with clouds, add_optics({gas,
@@ -782,11 +937,17 @@ static int band_allsky_optics(GrtPipeline_t *p, GrtBand *b, int C, GrtCloudArgs 
    grt_pipeline_run_allsky_profiles take in turn); materialised form: tau, omega, g and the spectral fluxes in the band's
    arrays, then the row-wise trapezoid. */
 static int band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, int defer, GrtContinua const *continua,
-                      GrtCloudArgs const *clouds, int profile, double *out, int out_stride, int out_offset)
+                      GrtCloudArgs const *clouds, int profile, double *out, int out_stride, int out_offset,
+                      SpectralOut const *so)
 {
     int const V = p->num_levels, rows = profile ? 2*V : GRT_FLUXES_PER_BAND;
     out_offset += bi*rows;
     void *s = grt_dev_stream(p->device);
+    if (so != NULL)
+    {
+        GRT_TRY(band_solve_spectral(p, b, bi, C, defer, continua, clouds, out, out_stride, out_offset, so));
+        return GRTCODE_SUCCESS;
+    }
     if (!p->keep_spectra)
     {
         if (profile && b->level_partials == NULL)
@@ -798,13 +959,13 @@ static int band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, int defer, Gr
         double *partials = profile ? b->level_partials : b->partials;
         GrtSolverForm const form = profile ? (clouds ? GRT_SOLVER_ALLSKY_PROFILE : GRT_SOLVER_PROFILE)
                                            : (clouds ? GRT_SOLVER_ALLSKY : GRT_SOLVER_FUSED);
-        GRT_TRY(band_solver(p, b, bi, C, form, defer, continua, clouds, partials));
+        GRT_TRY(band_solver(p, b, bi, C, form, defer, continua, clouds, partials, so));
         GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, partials, C*rows, b->nblocks, out, rows, out_stride, out_offset),
                               "flux reduction kernel"));
         return GRTCODE_SUCCESS;
     }
     GRT_TRY(clouds ? band_allsky_optics(p, b, C, clouds) : band_clear_sky_optics(p, b, C));
-    GRT_TRY(band_solver(p, b, bi, C, GRT_SOLVER_CHAINS, defer, continua, clouds, NULL));
+    GRT_TRY(band_solver(p, b, bi, C, GRT_SOLVER_CHAINS, defer, continua, clouds, NULL, NULL));
     if (profile)
     {
         GRT_TRY(level_rows(p, b));
@@ -819,7 +980,7 @@ static int band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, int defer, Gr
    the gas optics and the solve into out (band_solve) -- with clouds, the clear-sky solve and then the all-sky one, whose
    rows follow the clear-sky set's GRT_FLUXES_PER_COLUMN or (profile) GRT_PROFILE_ROWS_PER_COLUMN V. */
 static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl, int profile, double *out,
-                        int out_stride)
+                        int out_stride, SpectralOut *so)
 {
     GRT_TRY(stage_columns(p, cols));
     int const C = cols->ncol;
@@ -857,11 +1018,19 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t 
         GrtContinua continua;
         int defer;
         GRT_TRY(band_gas_optics(p, b, bi, cols, &continua, &defer));
-        GRT_TRY(band_solve(p, b, bi, C, defer, &continua, NULL, profile, out, out_stride, 0));
+        if (so != NULL)
+        {
+            so->set = 0;
+        }
+        GRT_TRY(band_solve(p, b, bi, C, defer, &continua, NULL, profile, out, out_stride, 0, so));
         if (cl != NULL)
         {
             int const set = profile ? GRT_PROFILE_ROWS_PER_COLUMN*p->num_levels : GRT_FLUXES_PER_COLUMN;
-            GRT_TRY(band_solve(p, b, bi, C, defer, &continua, &ca, profile, out, out_stride, set));
+            if (so != NULL)
+            {
+                so->set = 1;
+            }
+            GRT_TRY(band_solve(p, b, bi, C, defer, &continua, &ca, profile, out, out_stride, set, so));
         }
     }
     return GRTCODE_SUCCESS;
@@ -872,7 +1041,7 @@ EXTERN int grt_pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, fp_t *fl
     GRT_REQUIRE_PTR(p);
     GRT_REQUIRE_PTR(cols);
     GRT_REQUIRE_PTR(fluxes_dev);
-    GRT_TRY(pipeline_run(p, cols, NULL, 0, fluxes_dev, GRT_FLUXES_PER_COLUMN));
+    GRT_TRY(pipeline_run(p, cols, NULL, 0, fluxes_dev, GRT_FLUXES_PER_COLUMN, NULL));
     return GRTCODE_SUCCESS;
 }
 
@@ -896,7 +1065,7 @@ EXTERN int grt_pipeline_run_profiles(GrtPipeline_t *p, GrtColumns_t const *cols,
     }
     int const V = p->num_levels;
     /* [c][2 V] rows of band bi -> level_fluxes_dev[c][2 bi + {0, 1}][V], then the level fluxes' heating rates and six rows */
-    GRT_TRY(pipeline_run(p, cols, NULL, 1, level_fluxes_dev, GRT_PROFILE_ROWS_PER_COLUMN*V));
+    GRT_TRY(pipeline_run(p, cols, NULL, 1, level_fluxes_dev, GRT_PROFILE_ROWS_PER_COLUMN*V, NULL));
     int const bands = (p->band[0].gas != NULL) | (p->band[1].gas != NULL) << 1;
     GRT_TRY(grt_dev_check(grt_launch_profile_finish(grt_dev_stream(p->device), cols->ncol, 1, V, bands, p->user_level,
                                                     GRT_GRAVITY, GRT_SPECIFIC_HEAT_AIR, p->small_d + p->off_p,
@@ -935,7 +1104,7 @@ EXTERN int grt_pipeline_run_allsky(GrtPipeline_t *p, GrtColumns_t const *cols, G
     GRT_REQUIRE_PTR(cols);
     GRT_REQUIRE_PTR(fluxes_dev);
     GRT_TRY(check_clouds(p, cols, cl));
-    GRT_TRY(pipeline_run(p, cols, cl, 0, fluxes_dev, GRT_ALLSKY_FLUXES_PER_COLUMN));
+    GRT_TRY(pipeline_run(p, cols, cl, 0, fluxes_dev, GRT_ALLSKY_FLUXES_PER_COLUMN, NULL));
     return GRTCODE_SUCCESS;
 }
 
@@ -957,10 +1126,82 @@ EXTERN int grt_pipeline_run_allsky_profiles(GrtPipeline_t *p, GrtColumns_t const
     int const V = p->num_levels;
     /* clear-sky [c][2 V] rows of band bi -> level_fluxes_dev[c][2 bi + {0, 1}][V], all-sky -> [c][4 + 2 bi + {0, 1}][V];
        then both sets' heating rates and six rows */
-    GRT_TRY(pipeline_run(p, cols, cl, 1, level_fluxes_dev, GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN*V));
+    GRT_TRY(pipeline_run(p, cols, cl, 1, level_fluxes_dev, GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN*V, NULL));
     int const bands = (p->band[0].gas != NULL) | (p->band[1].gas != NULL) << 1;
     GRT_TRY(grt_dev_check(grt_launch_profile_finish(grt_dev_stream(p->device), cols->ncol, 2, V, bands, p->user_level,
                                                     GRT_GRAVITY, GRT_SPECIFIC_HEAT_AIR, p->small_d + p->off_p,
                                                     level_fluxes_dev, heating_dev, fluxes_dev), "heating rate kernel"));
+    return GRTCODE_SUCCESS;
+}
+
+/* one band's bins: none, or num_bins + 1 strictly increasing grid-point indices in 0 .. n - 1 of a band that is computed */
+static int check_bins(GrtPipeline_t const *p, int bi, int const *edges, int num_bins, fp_t const *binned_dev)
+{
+    char const *name = bi == 0 ? "longwave" : "shortwave";
+    if (num_bins < 0)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s bins.", num_bins, name);
+    }
+    if (num_bins == 0)
+    {
+        return GRTCODE_SUCCESS;
+    }
+    if (p->band[bi].gas == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s bins asked for, and this pipeline has no %s band.", num_bins, name, name);
+    }
+    if (edges == NULL || binned_dev == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s bins with NULL edges or a NULL binned_dev.", num_bins, name);
+    }
+    long long const n = (long long)p->band[bi].n;
+    if (edges[0] < 0 || (long long)edges[num_bins] > n - 1)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%s bin edges %d .. %d outside the grid's points 0 .. %lld.", name, edges[0],
+                 edges[num_bins], n - 1);
+    }
+    for (int b = 0; b < num_bins; ++b)
+    {
+        if (edges[b + 1] <= edges[b])
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "%s bin edges not strictly increasing (edges[%d] = %d, edges[%d] = %d).", name, b,
+                     edges[b], b + 1, edges[b + 1]);
+        }
+    }
+    return GRTCODE_SUCCESS;
+}
+
+EXTERN int grt_pipeline_run_spectral(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl,
+                                     int const *lw_edges, int lw_num_bins, int const *sw_edges, int sw_num_bins,
+                                     fp_t *spectral_dev, fp_t *binned_dev, fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    if (spectral_dev == NULL || fluxes_dev == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "spectral_dev and fluxes_dev are required (%s is NULL).",
+                 spectral_dev == NULL ? "spectral_dev" : "fluxes_dev");
+    }
+    GRT_TRY(check_bins(p, 0, lw_edges, lw_num_bins, binned_dev));
+    GRT_TRY(check_bins(p, 1, sw_edges, sw_num_bins, binned_dev));
+    if (cols->ncol < 1 || cols->ncol > p->max_cols)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d columns asked for, this pipeline was created for 1 to %d.", cols->ncol, p->max_cols);
+    }
+    if (cl != NULL)
+    {
+        GRT_TRY(check_clouds(p, cols, cl));
+    }
+    SpectralOut so;
+    so.spectral = spectral_dev;
+    so.binned = binned_dev;
+    so.sets = cl != NULL ? 2 : 1;
+    so.set = 0;
+    so.edges[0] = lw_edges;
+    so.edges[1] = sw_edges;
+    so.num_bins[0] = lw_num_bins;
+    so.num_bins[1] = sw_num_bins;
+    GRT_TRY(pipeline_run(p, cols, cl, 0, fluxes_dev, cl != NULL ? GRT_ALLSKY_FLUXES_PER_COLUMN : GRT_FLUXES_PER_COLUMN,
+                         &so));
     return GRTCODE_SUCCESS;
 }

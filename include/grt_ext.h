@@ -240,6 +240,37 @@ EXTERN int grt_pipeline_run_allsky_profiles(GrtPipeline_t *pipeline, GrtColumns_
                                             GrtClouds_t const *clouds, fp_t *level_fluxes_dev, fp_t *heating_dev,
                                             fp_t *fluxes_dev);
 
+/* ---- spectral and band-integrated fluxes ---------------------------------------------------------------------------
+ * driver.c's output without -integrated (output_fluxes, driver.c:285-356): the six rows of grt_pipeline_run at EVERY grid
+ * point, and -- where the caller gives bin edges -- the same rows integrated over wavenumber bins, for a batch of columns,
+ * clear sky (clouds NULL) or clear sky and all-sky (clouds as grt_pipeline_run_allsky takes them).  sets = 1 without
+ * clouds, 2 with them (the clear-sky set first, as grt_pipeline_run_allsky); n_lw, n_sw: the grid points of the
+ * pipeline's two gas-optics objects, 0 for a band whose object is NULL (it takes no room).
+ *   spectral_dev [ncol][sets][6 n_lw + 6 n_sw] (required): per set the longwave's six rows [6][n_lw], then the
+ *                shortwave's [6][n_sw], in GRT_FLUXES_PER_BAND order (up TOA, up surface, up user level, down TOA, down
+ *                surface, down user level), W m-2 per cm-1; with user_level < 0 the two user rows are zeros;
+ *   binned_dev   [ncol][sets][6 lw_num_bins + 6 sw_num_bins], each band [6][num_bins] in the same row order, W m-2
+ *                (required if either bin count is > 0, ignored otherwise): bin b of a band is the trapezoid over its
+ *                grid points edges[b] .. edges[b + 1],  sum_{i = edges[b]}^{edges[b+1] - 1} 0.5 (f_i + f_{i+1}) dw;
+ *                adjacent bins share their edge point, so contiguous bins add up to the bin over their union, and the
+ *                single bin {0, n - 1} is the broadband value;
+ *   fluxes_dev   [ncol][GRT_FLUXES_PER_COLUMN] without clouds, [ncol][GRT_ALLSKY_FLUXES_PER_COLUMN] with them (required):
+ *                exactly what grt_pipeline_run / grt_pipeline_run_allsky write, from the same solver launches.
+ * lw_edges, sw_edges: HOST arrays of num_bins + 1 strictly increasing grid-point indices in 0 .. n - 1 (NULL / 0: no bins
+ * for that band).  All outputs are DEVICE memory; asynchronous on the pipeline's lane like grt_pipeline_run; the
+ * shortwave sweep rule is grt_pipeline_run's.  The production form (keep_spectra = 0) runs the fused six-row solvers in a
+ * form that also stores the six rows at every point; the bins are summed from those rows by a deterministic kernel
+ * (profile tag 10) in the fused solvers' association, so that a bin {0, n - 1} is, bit for bit, the matching fluxes_dev
+ * value.  keep_spectra = 1: rows 0, L and the user level of the materialised fluxes, the same binning kernel, and
+ * fluxes_dev from the row-wise trapezoid.  A new set of edges is uploaded (the call then waits for the lane); the bins'
+ * partial sums, [max_columns][6][about num_bins + n/128] doubles per band, are allocated at the first call that needs
+ * them.  GRTCODE_VALUE_ERR, with nothing launched, for: a NULL spectral_dev or fluxes_dev, num_bins < 0, bins with NULL
+ * edges or a NULL binned_dev, edges not strictly increasing or outside 0 .. n - 1, bins for a band whose gas-optics
+ * object is NULL, ncol outside 1 .. max_columns, and what grt_pipeline_run_allsky refuses in clouds. */
+EXTERN int grt_pipeline_run_spectral(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtClouds_t const *clouds,
+                                     int const *lw_edges, int lw_num_bins, int const *sw_edges, int sw_num_bins,
+                                     fp_t *spectral_dev, fp_t *binned_dev, fp_t *fluxes_dev);
+
 /* ---- columns across the GPUs of one node ------------------------------------
  * One process per GPU; contiguous ceil-sized column blocks; one gather of the [columns][GRT_FLUXES_PER_COLUMN]
  * flux blocks to rank 0.  The reference fans out processes with -x/-X column ranges and merges per-shard files
@@ -277,7 +308,9 @@ EXTERN int grt_multi_max(GrtMulti_t *multi, double *value);    /* barrier + maxi
  * 2 = line-by-line kernel on a larger grid (shortwave band), 3 = LW solver, 4 = SW solver,
  * 5 = clear-sky optics combine, 6 / 7 = far-field gather kernel of the two-pass line kernel (longwave /
  * shortwave band; tags 1 / 2 then cover its first pass), 8 / 9 = LW / SW solver of the all-sky pass of
- * grt_pipeline_run_allsky and grt_pipeline_run_allsky_profiles (their clear-sky pass counts under 3 / 4).  Read after grt_pipeline_sync(). */
+ * grt_pipeline_run_allsky and grt_pipeline_run_allsky_profiles (their clear-sky pass counts under 3 / 4), 10 = the
+ * wavenumber-bin kernel of grt_pipeline_run_spectral (both of its launches; its solvers count under 3 / 4 and 8 / 9).
+ * Read after grt_pipeline_sync(). */
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
 
