@@ -24,6 +24,7 @@ GRT_ALLSKY_FLUXES_PER_COLUMN = 24   # grt_pipeline_run's twelve (clear sky), the
 GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN = 2 * GRT_PROFILE_ROWS_PER_COLUMN   # the clear-sky four rows, then the all-sky four
 GRT_ALLSKY_HEATING_ROWS_PER_COLUMN = 2 * GRT_HEATING_ROWS_PER_COLUMN   # the clear-sky two rows, then the all-sky two
 GRT_CLOUDS = 6                      # grt_sizeof kind of GrtClouds
+GRT_MAX_SUBCOLUMNS = 64             # grt_pipeline_run_subcolumns: subcolumns per column, 1 .. this
 RETURN_CODES = ["GRTCODE_SUCCESS", "GRTCODE_INVALID_ERR", "GRTCODE_DIVBYZERO_ERR", "GRTCODE_OVERFLOW_ERR",
                 "GRTCODE_UNDERFLOW_ERR", "GRTCODE_SENTINEL_ERR", "GRTCODE_NULL_ERR", "GRTCODE_NON_NULL_ERR",
                 "GRTCODE_RANGE_ERR", "GRTCODE_VALUE_ERR", "GRTCODE_COMPILER_ERR", "GRTCODE_IO_ERR",
@@ -150,7 +151,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -194,6 +195,8 @@ def load_library(path=None):
                                                      C.c_void_p, C.c_void_p]
     lib.grt_pipeline_run_spectral.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtClouds), C.c_void_p, C.c_int,
                                               C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.grt_pipeline_run_subcolumns.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtClouds), C.c_int,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]
     lib.grt_multi_gather_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.grt_pipeline_sync.argtypes = [C.c_void_p]
     lib.grt_pipeline_stream.argtypes = [C.c_void_p]
@@ -465,12 +468,19 @@ def make_columns(cols, mol_order, cfc_order=(), num_levels=None):
 def make_clouds(liquid_bands, ice_bands, thickness, lw_liquid, lw_ice, sw_liquid, sw_ice):
     """Pack cloud inputs into a GrtClouds struct (+ keep-alive arrays) for Pipeline.run_allsky.
     liquid_bands / ice_bands: (lo, hi) band limits in cm-1 ([B] and [>= B]); thickness [ncol][L] m; each optics set
-    [ncol][3][B][L] (extinction m-1, single-scattering albedo, asymmetry), e.g. grt_clouds_band_optics' per column; a set
-    may be None for a band the pipeline does not have."""
+    [ncol][3][B][L] (extinction m-1, single-scattering albedo, asymmetry), e.g. grt_clouds_band_optics' per column, or
+    [ncol][S][3][B][L]: S subcolumns per column (Pipeline.run_subcolumns; [ncol][3][B][L] is S = 1); a set may be None for
+    a band the pipeline does not have.  keep["subcolumns"] is S."""
     keep = dict(llo=_f64(liquid_bands[0]), lhi=_f64(liquid_bands[1]), ilo=_f64(ice_bands[0]), ihi=_f64(ice_bands[1]),
                 th=_f64(thickness))
+    shapes = set()
     for k, v in (("lwl", lw_liquid), ("lwi", lw_ice), ("swl", sw_liquid), ("swi", sw_ice)):
         keep[k] = _f64(v) if v is not None else None
+        if v is not None:
+            shapes.add(keep[k].shape[1] if keep[k].ndim == 5 else 1)
+    if len(shapes) > 1:
+        raise ValueError(f"optics sets of different subcolumn counts {sorted(shapes)}")
+    keep["subcolumns"] = shapes.pop() if shapes else 1
     ptr = lambda a: _dp(a) if a is not None else None
     gc = GrtClouds(keep["llo"].size, keep["ilo"].size, ptr(keep["llo"]), ptr(keep["lhi"]), ptr(keep["ilo"]),
                    ptr(keep["ihi"]), ptr(keep["th"]), ptr(keep["lwl"]), ptr(keep["lwi"]), ptr(keep["swl"]),
@@ -500,6 +510,8 @@ class Pipeline:
         self.allsky = None      # run_allsky's [max_columns][24]: allocated at its first call
         self.allsky_prof = None  # run_allsky_profiles' device outputs: allocated at its first call
         self.spec = None        # run_spectral's device outputs: allocated at its first call (and for a new bin count)
+        self.sub = None         # run_subcolumns' six-row output [max_columns][24]: allocated at its first call
+        self.sub_prof = None    # run_subcolumns(profiles=True)' device outputs: allocated at its first call
         self.nw = tuple(g.grid.n if g is not None else 0 for g in (lw_gas, sw_gas))
 
     def run(self, gcols, out_ptr=None):
@@ -612,6 +624,41 @@ class Pipeline:
         out["fluxes"] = self.spec["fluxes"].to_host((ncol, sets * GRT_FLUXES_PER_COLUMN))
         return out
 
+    def run_subcolumns(self, gcols, gclouds, S, profiles=False):
+        """grt_pipeline_run_subcolumns with S subcolumns per column into this object's device buffers: the six-row form
+        (subcolumn_fluxes() reads it) or, profiles=True, the profile form (subcolumn_profiles() reads it)."""
+        V, n = self.num_levels, self.max_columns
+        if not profiles:
+            if self.sub is None:
+                self.sub = DeviceBuffer(self.device, 8 * GRT_ALLSKY_FLUXES_PER_COLUMN * n)
+            check(self.lib.grt_pipeline_run_subcolumns(self.p, C.byref(gcols), C.byref(gclouds), int(S), None, None,
+                                                       self.sub.ptr))
+            return
+        if self.sub_prof is None:
+            self.sub_prof = {"levels": DeviceBuffer(self.device, 8 * n * GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN * V),
+                             "heating": DeviceBuffer(self.device, 8 * n * GRT_ALLSKY_HEATING_ROWS_PER_COLUMN * (V - 1)),
+                             "fluxes": DeviceBuffer(self.device, 8 * n * GRT_ALLSKY_FLUXES_PER_COLUMN)}
+        check(self.lib.grt_pipeline_run_subcolumns(self.p, C.byref(gcols), C.byref(gclouds), int(S),
+                                                   self.sub_prof["levels"].ptr, self.sub_prof["heating"].ptr,
+                                                   self.sub_prof["fluxes"].ptr))
+
+    def subcolumn_fluxes(self, ncol):
+        """The last six-row run_subcolumns: (clear, all-sky subcolumn mean), each [ncol][12] in grt_pipeline_run's layout."""
+        self.sync()
+        f = self.sub.to_host((ncol, GRT_ALLSKY_FLUXES_PER_COLUMN))
+        return f[:, :GRT_FLUXES_PER_COLUMN].copy(), f[:, GRT_FLUXES_PER_COLUMN:].copy()
+
+    def subcolumn_profiles(self, ncol):
+        """The last run_subcolumns(profiles=True): (clear, all-sky subcolumn mean), allsky_profiles()' keys and shapes."""
+        self.sync()
+        V, P, H, F = self.num_levels, GRT_PROFILE_ROWS_PER_COLUMN, GRT_HEATING_ROWS_PER_COLUMN, GRT_FLUXES_PER_COLUMN
+        lv = self.sub_prof["levels"].to_host((ncol, 2, P, V))
+        hr = self.sub_prof["heating"].to_host((ncol, 2, H, V - 1))
+        fx = self.sub_prof["fluxes"].to_host((ncol, 2, F))
+        return tuple(dict(lw_up=lv[:, s, 0].copy(), lw_down=lv[:, s, 1].copy(), sw_up=lv[:, s, 2].copy(),
+                          sw_down=lv[:, s, 3].copy(), lw_heating=hr[:, s, 0].copy(), sw_heating=hr[:, s, 1].copy(),
+                          fluxes=fx[:, s].copy()) for s in range(2))
+
     def views(self, band):
         ptrs = [C.c_void_p() for _ in range(6)]
         if not self.keep_spectra:
@@ -622,10 +669,15 @@ class Pipeline:
 
     def destroy(self):
         self.out.free()
-        for buf in list((self.prof or {}).values()) + list((self.allsky_prof or {}).values()):
+        for buf in (list((self.prof or {}).values()) + list((self.allsky_prof or {}).values()) +
+                    list((self.sub_prof or {}).values())):
             buf.free()
         self.prof = None
         self.allsky_prof = None
+        self.sub_prof = None
+        if self.sub is not None:
+            self.sub.free()
+            self.sub = None
         for k in ("spectral", "binned", "fluxes"):
             if self.spec is not None and self.spec[k] is not None:
                 self.spec[k].free()

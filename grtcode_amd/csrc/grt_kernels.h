@@ -379,6 +379,39 @@ static inline int grt_cloud_args_ok(GrtCloudArgs const *c)
 }
 int grt_launch_lw(void *stream, GrtSolverForm form, GrtLwArgs const *a, GrtCloudArgs const *clouds);
 int grt_launch_sw(void *stream, GrtSolverForm form, GrtSwArgs const *a, GrtCloudArgs const *clouds);
+
+/* Subcolumn form of the two all-sky forms (GRT_SOLVER_ALLSKY when profile == 0, GRT_SOLVER_ALLSKY_PROFILE when 1;
+   grt_pipeline_run_subcolumns): one launch solves subcolumns first .. first + count - 1 of every column, a->ncol columns of
+   gas state (tau_gas, n_layer, temperatures, sun, continua) and `subcolumns` cloud draws per column.  Row y of the grid
+   is column c = y / count, subcolumn s = first + y % count, so that the draws of one column run next to each other and
+   share its tau_gas in the caches.  clouds.liquid / .ice hold the tables subcolumn-major, [subcolumns][ncol][3][B][L]
+   (draw s of column c at (s ncol + c) 3 B L); thickness stays [ncol][L].  Partial sums go to the slot c subcolumns + s
+   (six-row: partials[((c S + s) 6 + k) nblocks + block]; profile: [((c S + s) 2 V + r) nblocks + block]); the shortwave's
+   park block is indexed by y: the two-sweep forms need it for ncol x count columns.  grt_launch_subcolumn_mean reduces. */
+typedef struct GrtSubcolumnArgs
+{
+    GrtCloudArgs clouds;
+    int subcolumns, first, count;
+} GrtSubcolumnArgs;
+/* whether a subcolumn launch can run: the fused all-sky form's fields, and a grid of at most 65 535 rows */
+static inline int grt_subcolumn_args_ok(int ncol, int num_levels, uint64_t nw, double const *tau_gas,
+                                        double const *n_layer, double const *partials, GrtSubcolumnArgs const *sc)
+{
+    return sc != NULL && ncol >= 1 && nw >= 2 && num_levels >= 2 && tau_gas != NULL && n_layer != NULL &&
+           partials != NULL && grt_cloud_args_ok(&sc->clouds) && sc->subcolumns >= 1 && sc->count >= 1 &&
+           sc->first >= 0 && sc->first + sc->count <= sc->subcolumns && (uint64_t)ncol*(uint64_t)sc->count <= 65535u;
+}
+int grt_launch_lw_subcolumns(void *stream, int profile, GrtLwArgs const *a, GrtSubcolumnArgs const *sc);
+int grt_launch_sw_subcolumns(void *stream, int profile, GrtSwArgs const *a, GrtSubcolumnArgs const *sc);
+/* The subcolumn mean of the partial sums above, in a fixed order: for column c and row r (of `rows` per slot) each
+   subcolumn's blocks are added as grt_launch_reduce_partials adds them, then the subcolumns s = 0 .. S - 1 in order, then
+   the sum is divided by S; out[c out_stride + out_offset + r].  S = 1 gives grt_launch_reduce_partials' bits. */
+int grt_launch_subcolumn_mean(void *stream, double const *partials, int ncol, int subcolumns, int rows, unsigned nblocks,
+                              double *out, int out_stride, int out_offset);
+/* Materialised form of grt_pipeline_run_subcolumns (driver.c:503-584): sum[i] = (first ? 0 : sum[i]) + x[i], i < n; and
+   at the end x[i] = sum[i]/S. */
+int grt_launch_flux_accumulate(void *stream, uint64_t n, double const *x, double *sum, int first);
+int grt_launch_flux_mean(void *stream, uint64_t n, double const *sum, int subcolumns, double *x);
 /* Materialised form: the cloud objects of the same tables spread onto the grid, [ncol][L][nw] each (tau = extinction x
    thickness; zero where a point has no band). */
 int grt_launch_spread_clouds(void *stream, int num_layers, int ncol, uint64_t nw, GrtCloudArgs const *c,

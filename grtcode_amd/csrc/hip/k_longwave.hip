@@ -15,7 +15,8 @@
 // chain -- 120 dependent layer steps with six fp64 exp each on 26 000 threads at 1 cm-1 -- which is why column
 // batches share a launch.  lw_kernel<true, false> is the fused form of the production pipeline, lw_kernel<true, false, true>
 // its all-sky form, lw_kernel<true, true> and lw_kernel<true, true, true> the profile forms of the two,
-// lw_kernel<true, false, false, true> and lw_kernel<true, false, true, true> the spectral six-row forms of the two.
+// lw_kernel<true, false, false, true> and lw_kernel<true, false, true, true> the spectral six-row forms of the two, and
+// lw_kernel<true, *, true, false, GrtSubcolumnArgs> the all-sky forms over several subcolumns per column.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -105,7 +106,8 @@ template <bool FUSED, bool PROFILE, bool ALLSKY = false, bool SPECTRAL = false, 
 __global__ __launch_bounds__(kSolverBlock) void lw_kernel(GrtLwArgs a, Clouds... clouds)
 {
     uint64_t const i = (uint64_t)blockIdx.x*kSolverBlock + threadIdx.x;
-    int const col = blockIdx.y;
+    SolverRow const row = solver_row(a.ncol, clouds...);
+    int const col = row.col;
     bool const live = i < a.nw;
     if (!FUSED && !live)
     {
@@ -120,8 +122,8 @@ __global__ __launch_bounds__(kSolverBlock) void lw_kernel(GrtLwArgs a, Clouds...
     double const *tl = a.t_layers + (uint64_t)col*L;
     double const *tv = a.t_levels + (uint64_t)col*V;
     double const emis = a.emis[(uint64_t)col*a.emis_stride + ii];
-    LevelSink<FUSED, PROFILE, SPECTRAL> sink(a, col, i, live);
-    LayerOptics<FUSED, ALLSKY> const optics(a, cloud_args(clouds...), col, ii);   // (fused forms)
+    LevelSink<FUSED, PROFILE, SPECTRAL> sink(a, row.slot, i, live);
+    LayerOptics<FUSED, ALLSKY> const optics(a, cloud_args(clouds...), col, row.tab, ii);   // (fused forms)
 
     // absorption optical depth of layer j: tau (1 - omega)  (longwave.c:252)
     auto layer_tau = [&](int j) -> double
@@ -315,6 +317,28 @@ extern "C" int grt_launch_lw(void *stream, GrtSolverForm form, GrtLwArgs const *
         break;
     default:
         return (int)hipErrorInvalidValue;
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_lw_subcolumns(void *stream, int profile, GrtLwArgs const *a, GrtSubcolumnArgs const *sc)
+{
+    size_t const lds = profile ? sizeof(double)*2*(size_t)a->num_levels*(kSolverBlock/64) : 0;
+    if (!grt_subcolumn_args_ok(a->ncol, a->num_levels, a->nw, a->tau_gas, a->n_layer, a->partials, sc) || lds > 65536)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipStream_t const s = (hipStream_t)stream;
+    dim3 const grid(grt_solver_blocks(a->nw), (unsigned)(a->ncol*sc->count), 1);
+    if (profile)
+    {
+        hipLaunchKernelGGL((lw_kernel<true, true, true, false, GrtSubcolumnArgs>), grid, dim3(kSolverBlock), lds, s, *a,
+                           *sc);
+    }
+    else
+    {
+        hipLaunchKernelGGL((lw_kernel<true, false, true, false, GrtSubcolumnArgs>), grid, dim3(kSolverBlock), 0, s, *a,
+                           *sc);
     }
     return (int)hipGetLastError();
 }

@@ -219,6 +219,53 @@ __global__ __launch_bounds__(64) void reduce_partials_kernel(double const *parti
     }
 }
 
+// grt_pipeline_run_subcolumns: the mean over a column's S subcolumns of one output row.  One wavefront per (column, row):
+// each subcolumn's block sums in reduce_partials_kernel's association (same lanes, same shuffle tree), then the
+// subcolumns in order, then one division by S (driver.c:585-589).  S = 1: reduce_partials_kernel's bits.
+__global__ __launch_bounds__(64) void subcolumn_mean_kernel(double const *partials, int S, int rows, unsigned nblocks,
+                                                            double *out, int out_stride, int out_offset)
+{
+    int const c = blockIdx.x/rows;
+    int const r = blockIdx.x - c*rows;
+    double m = 0.;
+    for (int s = 0; s < S; ++s)
+    {
+        double const *p = partials + ((uint64_t)(c*S + s)*rows + r)*nblocks;
+        double x = 0.;
+        for (unsigned b = threadIdx.x; b < nblocks; b += 64)
+        {
+            x += p[b];
+        }
+        for (int off = 32; off > 0; off >>= 1)
+        {
+            x += __shfl_down(x, off, 64);
+        }
+        m = s == 0 ? x : m + x;
+    }
+    if (threadIdx.x == 0)
+    {
+        out[(uint64_t)c*out_stride + out_offset + r] = m/(double)S;
+    }
+}
+
+// The materialised form's subcolumn loop (driver.c:503-589): sum += x per subcolumn (first: the sum starts at 0), then
+// x = sum/S
+__global__ __launch_bounds__(kBlock) void flux_accumulate_kernel(uint64_t n, double const *x, double *sum, int first)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x*kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x*kBlock)
+    {
+        sum[i] = (first ? 0. : sum[i]) + x[i];
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void flux_mean_kernel(uint64_t n, double const *sum, int S, double *x)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x*kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x*kBlock)
+    {
+        x[i] = sum[i]/(double)S;
+    }
+}
+
 // ---- wavenumber bins of spectral rows (grt_pipeline_run_spectral), in the fused solvers' association ----
 // Bin table (grt_bin_table): per bin {first edge, last edge, offset of its partial sums in a row's, first block}, then
 // per 128-point solver block {first bin, one past the last bin} that has a point in the block.  A bin over the whole
@@ -411,6 +458,35 @@ extern "C" int grt_launch_reduce_partials(void *stream, double const *partials, 
     }
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(nrows), dim3(64), 0, (hipStream_t)stream, partials, nblocks, out,
                        group, out_stride, out_offset);
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_subcolumn_mean(void *stream, double const *partials, int ncol, int subcolumns, int rows,
+                                          unsigned nblocks, double *out, int out_stride, int out_offset)
+{
+    if (ncol < 1 || subcolumns < 1 || rows < 1 || nblocks < 1 || (uint64_t)ncol*(uint64_t)rows > 0x7fffffffull ||
+        partials == nullptr || out == nullptr)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(subcolumn_mean_kernel, dim3((unsigned)(ncol*rows)), dim3(64), 0, (hipStream_t)stream, partials,
+                       subcolumns, rows, nblocks, out, out_stride, out_offset);
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_flux_accumulate(void *stream, uint64_t n, double const *x, double *sum, int first)
+{
+    hipLaunchKernelGGL(flux_accumulate_kernel, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, n, x, sum, first);
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_flux_mean(void *stream, uint64_t n, double const *sum, int subcolumns, double *x)
+{
+    if (subcolumns < 1)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(flux_mean_kernel, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, n, sum, subcolumns, x);
     return (int)hipGetLastError();
 }
 

@@ -71,6 +71,36 @@ __device__ __forceinline__ GrtCloudArgs cloud_args(GrtCloudArgs const &c)
     return c;
 }
 
+__device__ __forceinline__ GrtCloudArgs cloud_args(GrtSubcolumnArgs const &c)
+{
+    return c.clouds;
+}
+
+// What grid row blockIdx.y stands for: col, the column whose gas state (tau_gas, temperatures, sun) it reads; tab, its
+// cloud tables' column; slot, its partial sums' column; park, its rows of the shortwave park block.  All four are
+// blockIdx.y but in the subcolumn instances (GrtSubcolumnArgs: row y is column y / count, subcolumn first + y % count).
+struct SolverRow { int col, tab, slot, park; };
+
+__device__ __forceinline__ SolverRow solver_row(int)
+{
+    int const y = blockIdx.y;
+    return SolverRow{y, y, y, y};
+}
+
+__device__ __forceinline__ SolverRow solver_row(int, GrtCloudArgs const &)
+{
+    int const y = blockIdx.y;
+    return SolverRow{y, y, y, y};
+}
+
+__device__ __forceinline__ SolverRow solver_row(int ncol, GrtSubcolumnArgs const &sc)
+{
+    int const y = blockIdx.y;
+    int const c = y/sc.count;
+    int const s = sc.first + (y - c*sc.count);
+    return SolverRow{c, s*ncol + c, c*sc.subcolumns + s, y};
+}
+
 // One cloud object's optics at (layer j, a point that takes band `band`) from a column's band table tab [3][B][L]
 // (extinction, albedo, asymmetry; GrtCloudArgs): optical depth = extinction x layer thickness (driver.c:518-526); no band
 // (band < 0): no cloud.
@@ -246,7 +276,8 @@ __device__ __forceinline__ double trapezoid_weight(uint64_t i, uint64_t nw, doub
 // clear_sky_combine (the expressions and order of clear_sky_kernel: identical values).  ALLSKY: the liquid and ice cloud
 // objects join (GrtCloudArgs): the point reads its two band indices once, each layer forms the two objects from the
 // column's band tables and allsky_combine adds the four.  Built once per thread from the fields both solvers' argument
-// structs carry; FUSED false (the spectral forms, which read their optics): nothing is loaded.
+// structs carry; FUSED false (the spectral forms, which read their optics): nothing is loaded.  tab: the column of the
+// cloud tables (SolverRow; col but in the subcolumn instances).
 template <bool FUSED, bool ALLSKY>
 struct LayerOptics
 {
@@ -262,7 +293,7 @@ struct LayerOptics
     uint64_t ctab;
 
     template <typename Args>
-    __device__ __forceinline__ LayerOptics(Args const &a, GrtCloudArgs const &cl_, int col_, uint64_t ii_)
+    __device__ __forceinline__ LayerOptics(Args const &a, GrtCloudArgs const &cl_, int col_, int tab, uint64_t ii_)
     {
         L = a.num_levels - 1;
         col = col_;
@@ -283,7 +314,7 @@ struct LayerOptics
         cl = cl_;
         band_l = ALLSKY ? cl.band_liquid[ii] : -1;
         band_i = ALLSKY ? cl.band_ice[ii] : -1;
-        ctab = ALLSKY ? (uint64_t)col*3*(uint64_t)cl.num_bands*L : 0;
+        ctab = ALLSKY ? (uint64_t)tab*3*(uint64_t)cl.num_bands*L : 0;
     }
 
     __device__ __forceinline__ void at(int j, double &t, double &om, double &gg) const

@@ -22,6 +22,8 @@
  * grid and added by the add_optics kernel).
  * grt_pipeline_run_allsky_profiles runs both: the profile form of the clear-sky pass, then of the all-sky pass, on one
  * tau_gas, and one finishing launch for the two sets.
+ * grt_pipeline_run_subcolumns runs either of the two with the all-sky pass averaged over several cloud subcolumns, all of
+ * them on the one tau_gas.
  * All work is enqueued on the device's library stream; nothing synchronises.
  */
 #include <stdlib.h>
@@ -58,6 +60,10 @@ typedef struct GrtBand
     size_t bin_per_row;    /* partial sums per row */
     double *bin_partials;  /* [max_cols][6][bin_cap] */
     size_t bin_cap;
+    /* grt_pipeline_run_subcolumns, allocated at the first call that needs them (or more of them): */
+    double *sub_partials;  /* fused form: [max_cols][S][6 or 2 V][nblocks] partial sums of the all-sky pass */
+    size_t sub_cap;        /* its doubles */
+    double *flux_sum;      /* materialised form: [2][max_cols][V][n] sums of the subcolumns' up and down fluxes */
 } GrtBand;
 
 struct GrtPipeline
@@ -270,6 +276,8 @@ static void grt_pipeline_release(GrtPipeline_t **pipeline)
         grt_dev_free(p->device, p->band[b].bin_table);
         grt_dev_free(p->device, p->band[b].bin_partials);
         free(p->band[b].bin_edges);
+        grt_dev_free(p->device, p->band[b].sub_partials);
+        grt_dev_free(p->device, p->band[b].flux_sum);
     }
     grt_dev_free(p->device, p->cloud_d);
     grt_host_free_pinned(p->cloud_h);
@@ -664,12 +672,12 @@ static void cloud_band_map(double const *lo, double const *hi, int own, int nb, 
     }
 }
 
-/* the band's cloud arguments for a batch of C columns staged by stage_clouds: its per-point cloud bands for these band
-   limits are built on the host when the limits differ from the last call's */
-static int band_clouds(GrtPipeline_t *p, GrtBand *b, int bi, GrtClouds_t const *cl, int C, GrtCloudArgs *ca)
+/* the band's cloud arguments for a batch of C columns of S subcolumns staged by stage_clouds: its per-point cloud bands
+   for these band limits are built on the host when the limits differ from the last call's */
+static int band_clouds(GrtPipeline_t *p, GrtBand *b, int bi, GrtClouds_t const *cl, int C, int S, GrtCloudArgs *ca)
 {
     int const B = cl->num_liquid_bands, NI = cl->num_ice_bands;
-    size_t const L = (size_t)p->num_levels - 1, set = (size_t)C*3*(size_t)B*L;
+    size_t const L = (size_t)p->num_levels - 1, set = (size_t)S*(size_t)C*3*(size_t)B*L;
     ca->num_bands = B;
     ca->thickness = p->cloud_d;
     ca->liquid = p->cloud_d + (size_t)C*L + (size_t)(2*bi)*set;
@@ -738,16 +746,17 @@ static int band_clouds(GrtPipeline_t *p, GrtBand *b, int bi, GrtClouds_t const *
     return GRTCODE_SUCCESS;
 }
 
-/* the band tables of the batch to the device: [C][L] thickness, then the four [C][3][B][L] sets */
-static int stage_clouds(GrtPipeline_t *p, GrtClouds_t const *cl, int C)
+/* the band tables of the batch to the device: [C][L] thickness, then the four sets, each [S][C][3][B][L] -- the caller's
+   [C][S][3][B][L] subcolumn-major, so that subcolumn s of every column is one [C][3][B][L] block (S = 1: as given) */
+static int stage_clouds(GrtPipeline_t *p, GrtClouds_t const *cl, int C, int S)
 {
-    size_t const L = (size_t)p->num_levels - 1, B = (size_t)cl->num_liquid_bands;
-    size_t const set = (size_t)C*3*B*L, need = (size_t)C*L + 4*set;
+    size_t const L = (size_t)p->num_levels - 1, B = (size_t)cl->num_liquid_bands, tab = 3*B*L;
+    size_t const set = (size_t)S*(size_t)C*tab, need = (size_t)C*L + 4*set;
     GRT_TRY(grt_dev_event_wait(p->device, p->cloud_uploaded));
     if (need > p->cloud_doubles)
     {
-        /* (sized for max_columns at this band count: a later batch of the same bands reuses it) */
-        size_t const want = (size_t)p->max_cols*L*(1 + 12*B);
+        /* (sized for max_columns at this band and subcolumn count: a later batch of the same shape reuses it) */
+        size_t const want = (size_t)p->max_cols*L*(1 + 12*B*(size_t)S);
         void *s = grt_dev_stream(p->device);
         GRT_TRY(grt_dev_sync(p->device, s));
         grt_dev_free(p->device, p->cloud_d);
@@ -767,7 +776,13 @@ static int stage_clouds(GrtPipeline_t *p, GrtClouds_t const *cl, int C)
     {
         if (sets[k] != NULL)
         {
-            memcpy(h + k*set, sets[k], sizeof(double)*set);
+            for (size_t s = 0; s < (size_t)S; ++s)
+            {
+                for (size_t c = 0; c < (size_t)C; ++c)
+                {
+                    memcpy(h + k*set + (s*(size_t)C + c)*tab, sets[k] + (c*(size_t)S + s)*tab, sizeof(double)*tab);
+                }
+            }
         }
         else
         {
@@ -976,17 +991,122 @@ static int band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, int defer, Gr
     return GRTCODE_SUCCESS;
 }
 
-/* What the four run entry points share after their argument checks: the batch (and its clouds) staged, then per band
+/* The all-sky pass of grt_pipeline_run_subcolumns for one band, S subcolumns of every column on this run's tau_gas
+   (driver.c:503-589), its mean rows to out as band_solve writes them.  ca: the band's tables staged subcolumn-major.
+   Fused form: the subcolumn instance of the all-sky solver over C x S grid rows, each subcolumn's partial sums in
+   sub_partials, then their fixed-order mean (profile tag 11; S = 1: the fixed-order sum of band_solve).  The shortwave's
+   two-sweep forms park C x count columns at a time in the band's park block, count = what fits in its max_cols, in
+   stream order.  Materialised form: per subcolumn the all-sky optics, the spectral solver and the sum of its fluxes;
+   then the mean into the band's flux arrays, and the row-wise trapezoid. */
+static int band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S, int defer,
+                                 GrtContinua const *continua, GrtCloudArgs const *ca, int profile, double *out,
+                                 int out_stride, int out_offset)
+{
+    int const V = p->num_levels, rows = profile ? 2*V : GRT_FLUXES_PER_BAND;
+    out_offset += bi*rows;
+    void *s = grt_dev_stream(p->device);
+    size_t const tab = (size_t)C*3*(size_t)ca->num_bands*(size_t)(V - 1);
+    if (!p->keep_spectra)
+    {
+        size_t const need = (size_t)p->max_cols*(size_t)S*(size_t)rows*b->nblocks;
+        if (need > b->sub_cap)
+        {
+            GRT_TRY(grt_dev_sync(p->device, s));
+            grt_dev_free(p->device, b->sub_partials);
+            b->sub_partials = NULL;
+            b->sub_cap = 0;
+            void *sp = NULL;
+            GRT_TRY(grt_dev_alloc(p->device, &sp, sizeof(double)*need));
+            b->sub_partials = sp;
+            b->sub_cap = need;
+        }
+        GrtLwArgs lw;
+        GrtSwArgs sw;
+        int group = 65535/C;                   /* (grid rows) */
+        if (bi == 0)
+        {
+            lw_args(p, b, C, 1, defer, continua, &lw);
+            lw.partials = b->sub_partials;
+        }
+        else
+        {
+            sw_args(p, b, C, 1, defer, continua, &sw);
+            sw.partials = b->sub_partials;
+            if (profile || !grt_sw_one_sweep(&sw))
+            {
+                GRT_TRY(park_block(p, b));
+                group = p->max_cols/C;
+            }
+            sw.park = b->park;
+        }
+        group = group < S ? group : S;
+        int const slot = grt_profile_begin(s, bi == 0 ? 8 : 9);
+        int krc = 0;
+        for (int first = 0; first < S && krc == 0; first += group)
+        {
+            GrtSubcolumnArgs sc;
+            sc.clouds = *ca;
+            sc.subcolumns = S;
+            sc.first = first;
+            sc.count = S - first < group ? S - first : group;
+            krc = bi == 0 ? grt_launch_lw_subcolumns(s, profile, &lw, &sc) : grt_launch_sw_subcolumns(s, profile, &sw, &sc);
+        }
+        grt_profile_end(s, slot);
+        GRT_TRY(grt_dev_check(krc, bi == 0 ? "longwave subcolumn kernel" : "shortwave subcolumn kernel"));
+        if (S == 1)
+        {
+            GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, b->sub_partials, C*rows, b->nblocks, out, rows, out_stride,
+                                                             out_offset), "flux reduction kernel"));
+            return GRTCODE_SUCCESS;
+        }
+        int const mslot = grt_profile_begin(s, 11);
+        int const mrc = grt_launch_subcolumn_mean(s, b->sub_partials, C, S, rows, b->nblocks, out, out_stride, out_offset);
+        grt_profile_end(s, mslot);
+        GRT_TRY(grt_dev_check(mrc, "subcolumn mean kernel"));
+        return GRTCODE_SUCCESS;
+    }
+    uint64_t const per = (uint64_t)C*(uint64_t)V*b->n, all = (uint64_t)p->max_cols*(uint64_t)V*b->n;
+    if (b->flux_sum == NULL)
+    {
+        void *fs = NULL;
+        GRT_TRY(grt_dev_alloc(p->device, &fs, sizeof(double)*2*all));
+        b->flux_sum = fs;
+    }
+    for (int j = 0; j < S; ++j)
+    {
+        GrtCloudArgs cj = *ca;
+        cj.liquid += (size_t)j*tab;
+        cj.ice += (size_t)j*tab;
+        GRT_TRY(band_allsky_optics(p, b, C, &cj));
+        GRT_TRY(band_solver(p, b, bi, C, GRT_SOLVER_CHAINS, defer, continua, &cj, NULL, NULL));
+        GRT_TRY(grt_dev_check(grt_launch_flux_accumulate(s, per, b->flux_up, b->flux_sum, j == 0), "flux sum kernel"));
+        GRT_TRY(grt_dev_check(grt_launch_flux_accumulate(s, per, b->flux_down, b->flux_sum + all, j == 0),
+                              "flux sum kernel"));
+    }
+    GRT_TRY(grt_dev_check(grt_launch_flux_mean(s, per, b->flux_sum, S, b->flux_up), "flux mean kernel"));
+    GRT_TRY(grt_dev_check(grt_launch_flux_mean(s, per, b->flux_sum + all, S, b->flux_down), "flux mean kernel"));
+    if (profile)
+    {
+        GRT_TRY(level_rows(p, b));
+    }
+    GRT_TRY(grt_dev_check(grt_launch_integrate_rows(s, (double const *const *)(profile ? b->level_rows_d : b->rows_d),
+                                                    C*rows, b->n, b->gas->grid.dw, out, rows, out_stride, out_offset),
+                          "spectral integration kernel"));
+    return GRTCODE_SUCCESS;
+}
+
+/* What the run entry points share after their argument checks: the batch (and its clouds) staged, then per band
    the gas optics and the solve into out (band_solve) -- with clouds, the clear-sky solve and then the all-sky one, whose
-   rows follow the clear-sky set's GRT_FLUXES_PER_COLUMN or (profile) GRT_PROFILE_ROWS_PER_COLUMN V. */
-static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl, int profile, double *out,
-                        int out_stride, SpectralOut *so)
+   rows follow the clear-sky set's GRT_FLUXES_PER_COLUMN or (profile) GRT_PROFILE_ROWS_PER_COLUMN V.  subcolumns > 0
+   (grt_pipeline_run_subcolumns): the all-sky pass is the mean over that many subcolumns (band_solve_subcolumns). */
+static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl, int subcolumns, int profile,
+                        double *out, int out_stride, SpectralOut *so)
 {
     GRT_TRY(stage_columns(p, cols));
-    int const C = cols->ncol;
+    int const C = cols->ncol, S = subcolumns > 0 ? subcolumns : 1;
     if (cl != NULL)
     {
-        GRT_TRY(stage_clouds(p, cl, C));
+        GRT_TRY(stage_clouds(p, cl, C, S));
     }
     for (int bi = 0; bi < 2; ++bi)
     {
@@ -1013,7 +1133,7 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t 
         GrtCloudArgs ca;
         if (cl != NULL)
         {
-            GRT_TRY(band_clouds(p, b, bi, cl, C, &ca));
+            GRT_TRY(band_clouds(p, b, bi, cl, C, S, &ca));
         }
         GrtContinua continua;
         int defer;
@@ -1030,6 +1150,11 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t 
             {
                 so->set = 1;
             }
+            if (subcolumns > 0)
+            {
+                GRT_TRY(band_solve_subcolumns(p, b, bi, C, S, defer, &continua, &ca, profile, out, out_stride, set));
+                continue;
+            }
             GRT_TRY(band_solve(p, b, bi, C, defer, &continua, &ca, profile, out, out_stride, set, so));
         }
     }
@@ -1041,7 +1166,7 @@ EXTERN int grt_pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, fp_t *fl
     GRT_REQUIRE_PTR(p);
     GRT_REQUIRE_PTR(cols);
     GRT_REQUIRE_PTR(fluxes_dev);
-    GRT_TRY(pipeline_run(p, cols, NULL, 0, fluxes_dev, GRT_FLUXES_PER_COLUMN, NULL));
+    GRT_TRY(pipeline_run(p, cols, NULL, 0, 0, fluxes_dev, GRT_FLUXES_PER_COLUMN, NULL));
     return GRTCODE_SUCCESS;
 }
 
@@ -1065,7 +1190,7 @@ EXTERN int grt_pipeline_run_profiles(GrtPipeline_t *p, GrtColumns_t const *cols,
     }
     int const V = p->num_levels;
     /* [c][2 V] rows of band bi -> level_fluxes_dev[c][2 bi + {0, 1}][V], then the level fluxes' heating rates and six rows */
-    GRT_TRY(pipeline_run(p, cols, NULL, 1, level_fluxes_dev, GRT_PROFILE_ROWS_PER_COLUMN*V, NULL));
+    GRT_TRY(pipeline_run(p, cols, NULL, 0, 1, level_fluxes_dev, GRT_PROFILE_ROWS_PER_COLUMN*V, NULL));
     int const bands = (p->band[0].gas != NULL) | (p->band[1].gas != NULL) << 1;
     GRT_TRY(grt_dev_check(grt_launch_profile_finish(grt_dev_stream(p->device), cols->ncol, 1, V, bands, p->user_level,
                                                     GRT_GRAVITY, GRT_SPECIFIC_HEAT_AIR, p->small_d + p->off_p,
@@ -1104,7 +1229,7 @@ EXTERN int grt_pipeline_run_allsky(GrtPipeline_t *p, GrtColumns_t const *cols, G
     GRT_REQUIRE_PTR(cols);
     GRT_REQUIRE_PTR(fluxes_dev);
     GRT_TRY(check_clouds(p, cols, cl));
-    GRT_TRY(pipeline_run(p, cols, cl, 0, fluxes_dev, GRT_ALLSKY_FLUXES_PER_COLUMN, NULL));
+    GRT_TRY(pipeline_run(p, cols, cl, 0, 0, fluxes_dev, GRT_ALLSKY_FLUXES_PER_COLUMN, NULL));
     return GRTCODE_SUCCESS;
 }
 
@@ -1126,7 +1251,41 @@ EXTERN int grt_pipeline_run_allsky_profiles(GrtPipeline_t *p, GrtColumns_t const
     int const V = p->num_levels;
     /* clear-sky [c][2 V] rows of band bi -> level_fluxes_dev[c][2 bi + {0, 1}][V], all-sky -> [c][4 + 2 bi + {0, 1}][V];
        then both sets' heating rates and six rows */
-    GRT_TRY(pipeline_run(p, cols, cl, 1, level_fluxes_dev, GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN*V, NULL));
+    GRT_TRY(pipeline_run(p, cols, cl, 0, 1, level_fluxes_dev, GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN*V, NULL));
+    int const bands = (p->band[0].gas != NULL) | (p->band[1].gas != NULL) << 1;
+    GRT_TRY(grt_dev_check(grt_launch_profile_finish(grt_dev_stream(p->device), cols->ncol, 2, V, bands, p->user_level,
+                                                    GRT_GRAVITY, GRT_SPECIFIC_HEAT_AIR, p->small_d + p->off_p,
+                                                    level_fluxes_dev, heating_dev, fluxes_dev), "heating rate kernel"));
+    return GRTCODE_SUCCESS;
+}
+
+EXTERN int grt_pipeline_run_subcolumns(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl,
+                                       int num_subcolumns, fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    if (num_subcolumns < 1 || num_subcolumns > GRT_MAX_SUBCOLUMNS)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d subcolumns asked for: 1 to %d.", num_subcolumns, GRT_MAX_SUBCOLUMNS);
+    }
+    if (level_fluxes_dev == NULL && fluxes_dev == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "level_fluxes_dev and fluxes_dev are both NULL: nothing to write.%s", "");
+    }
+    if (level_fluxes_dev != NULL && p->num_levels < 2)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "heating rates need at least 2 levels (%d).", p->num_levels);
+    }
+    GRT_TRY(check_clouds(p, cols, cl));
+    if (level_fluxes_dev == NULL)
+    {
+        /* grt_pipeline_run_allsky's layout and shortwave sweep rule */
+        GRT_TRY(pipeline_run(p, cols, cl, num_subcolumns, 0, fluxes_dev, GRT_ALLSKY_FLUXES_PER_COLUMN, NULL));
+        return GRTCODE_SUCCESS;
+    }
+    /* grt_pipeline_run_allsky_profiles' layouts; the heating rates and six rows of the mean level fluxes */
+    int const V = p->num_levels;
+    GRT_TRY(pipeline_run(p, cols, cl, num_subcolumns, 1, level_fluxes_dev, GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN*V, NULL));
     int const bands = (p->band[0].gas != NULL) | (p->band[1].gas != NULL) << 1;
     GRT_TRY(grt_dev_check(grt_launch_profile_finish(grt_dev_stream(p->device), cols->ncol, 2, V, bands, p->user_level,
                                                     GRT_GRAVITY, GRT_SPECIFIC_HEAT_AIR, p->small_d + p->off_p,
@@ -1201,7 +1360,7 @@ EXTERN int grt_pipeline_run_spectral(GrtPipeline_t *p, GrtColumns_t const *cols,
     so.edges[1] = sw_edges;
     so.num_bins[0] = lw_num_bins;
     so.num_bins[1] = sw_num_bins;
-    GRT_TRY(pipeline_run(p, cols, cl, 0, fluxes_dev, cl != NULL ? GRT_ALLSKY_FLUXES_PER_COLUMN : GRT_FLUXES_PER_COLUMN,
+    GRT_TRY(pipeline_run(p, cols, cl, 0, 0, fluxes_dev, cl != NULL ? GRT_ALLSKY_FLUXES_PER_COLUMN : GRT_FLUXES_PER_COLUMN,
                          &so));
     return GRTCODE_SUCCESS;
 }

@@ -240,6 +240,38 @@ EXTERN int grt_pipeline_run_allsky_profiles(GrtPipeline_t *pipeline, GrtColumns_
                                             GrtClouds_t const *clouds, fp_t *level_fluxes_dev, fp_t *heating_dev,
                                             fp_t *fluxes_dev);
 
+/* ---- all-sky fluxes averaged over several cloud subcolumns ----------------------------------------------------------
+ * driver.c:474-597 with num_subcolumns = S: per column, S draws of the cloud objects, each added to gas and Rayleigh and
+ * solved, the spectral fluxes of the S solves summed and divided by S before they are integrated.  The clouds come as
+ * grt_pipeline_run_allsky takes them but for the four optics sets, which hold S draws per column:
+ * lw_liquid, lw_ice, sw_liquid, sw_ice [ncol][S][3][B][L], subcolumn s of column c at (c S + s) 3 B L; thickness stays
+ * [ncol][L].  Two forms:
+ *   level_fluxes_dev == NULL (six rows): fluxes_dev [ncol][GRT_ALLSKY_FLUXES_PER_COLUMN] (required) in
+ *                    grt_pipeline_run_allsky's layout -- values 0-11 its clear-sky set, values 12-23 the subcolumn mean of
+ *                    the all-sky set; grt_pipeline_run's shortwave sweep rule;
+ *   level_fluxes_dev != NULL (profiles): grt_pipeline_run_allsky_profiles' layouts -- level_fluxes_dev
+ *                    [ncol][GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN][V], heating_dev [ncol][GRT_ALLSKY_HEATING_ROWS_PER_COLUMN][V-1]
+ *                    and fluxes_dev [ncol][GRT_ALLSKY_FLUXES_PER_COLUMN] (both may be NULL) -- the all-sky rows the
+ *                    subcolumn means, the heating rates and six rows formed from those mean level fluxes; the shortwave
+ *                    always takes two sweeps.
+ * All DEVICE memory; asynchronous on the pipeline's lane.  One gas-optics launch per band serves the clear-sky pass and
+ * all S subcolumns; band maps, tables and cloud rules are grt_pipeline_run_allsky's.  The mean is taken in a fixed
+ * order: per subcolumn the blocks as the other entry points add them, then the subcolumns s = 0 .. S - 1, then one
+ * division by S; with S = 1 every value is, bit for bit, grt_pipeline_run_allsky's or grt_pipeline_run_allsky_profiles'.
+ * The production form (keep_spectra = 0) solves all S subcolumns of a band in one launch of the subcolumn instance of the
+ * all-sky solver (profile tags 8 / 9; the shortwave's two-sweep forms in as many launches as the park block of
+ * max_columns columns needs) and reduces with a deterministic kernel (profile tag 11); it allocates per band
+ * [max_columns][S][6 or 2 V][blocks] partial sums at the first call that needs more than it holds, and no larger park
+ * block.  keep_spectra = 1: driver.c's loop literally -- per subcolumn the all-sky optics, the spectral solver and the
+ * sum of its fluxes; afterwards grt_pipeline_views shows the last subcolumn's tau, omega, g and the mean fluxes.
+ * GRTCODE_VALUE_ERR, with nothing launched and the outputs untouched, for: num_subcolumns outside
+ * 1 .. GRT_MAX_SUBCOLUMNS, level_fluxes_dev and fluxes_dev both NULL, fewer than 2 levels in the profile form, and what
+ * grt_pipeline_run_allsky refuses in clouds and ncol. */
+#define GRT_MAX_SUBCOLUMNS 64
+EXTERN int grt_pipeline_run_subcolumns(GrtPipeline_t *pipeline, GrtColumns_t const *columns,
+                                       GrtClouds_t const *clouds, int num_subcolumns,
+                                       fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev);
+
 /* ---- spectral and band-integrated fluxes ---------------------------------------------------------------------------
  * driver.c's output without -integrated (output_fluxes, driver.c:285-356): the six rows of grt_pipeline_run at EVERY grid
  * point, and -- where the caller gives bin edges -- the same rows integrated over wavenumber bins, for a batch of columns,
@@ -309,7 +341,9 @@ EXTERN int grt_multi_max(GrtMulti_t *multi, double *value);    /* barrier + maxi
  * 5 = clear-sky optics combine, 6 / 7 = far-field gather kernel of the two-pass line kernel (longwave /
  * shortwave band; tags 1 / 2 then cover its first pass), 8 / 9 = LW / SW solver of the all-sky pass of
  * grt_pipeline_run_allsky and grt_pipeline_run_allsky_profiles (their clear-sky pass counts under 3 / 4), 10 = the
- * wavenumber-bin kernel of grt_pipeline_run_spectral (both of its launches; its solvers count under 3 / 4 and 8 / 9).
+ * wavenumber-bin kernel of grt_pipeline_run_spectral (both of its launches; its solvers count under 3 / 4 and 8 / 9),
+ * 11 = the subcolumn-mean kernel of grt_pipeline_run_subcolumns (with S > 1; its all-sky solvers count under 8 / 9, each
+ * band's launches together).
  * Read after grt_pipeline_sync(). */
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
