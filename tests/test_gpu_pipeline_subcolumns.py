@@ -105,7 +105,7 @@ def oracle_subcolumns(orc, lib, band, col, lw, tables, liquid, ice, thickness, e
     dn_sum /= float(S)
     up_int = np.array([orc.integrate_row(up_sum[k], band.dw) for k in range(L + 1)])
     dn_int = np.array([orc.integrate_row(dn_sum[k], band.dw) for k in range(L + 1)])
-    return dict(up_int=up_int, dn_int=dn_int)
+    return dict(up_int=up_int, dn_int=dn_int, up=up_sum, dn=dn_sum)
 
 
 def six(up_int, dn_int, user_level):
