@@ -136,6 +136,11 @@ class GrtClouds(C.Structure):
                 ("lw_liquid", c_double_p), ("lw_ice", c_double_p), ("sw_liquid", c_double_p), ("sw_ice", c_double_p)]
 
 
+class GrtAerosols(C.Structure):
+    _fields_ = [("lw_num_points", C.c_int), ("sw_num_points", C.c_int), ("lw_grid", c_double_p), ("sw_grid", c_double_p),
+                ("lw_optics", c_double_p), ("sw_optics", c_double_p)]
+
+
 #: every symbol include/*.h declares (checked by tests/test_abi_symbols.py against the headers too)
 EXPORTS = """
 grtcode_errstr grtcode_set_verbosity grtcode_verbosity create_device get_num_gpus
@@ -151,7 +156,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_aerosols grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -197,6 +202,8 @@ def load_library(path=None):
                                               C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.grt_pipeline_run_subcolumns.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtClouds), C.c_int,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.grt_pipeline_run_aerosols.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtAerosols), C.c_void_p,
+                                              C.c_void_p, C.c_void_p]
     lib.grt_multi_gather_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.grt_pipeline_sync.argtypes = [C.c_void_p]
     lib.grt_pipeline_stream.argtypes = [C.c_void_p]
@@ -488,6 +495,33 @@ def make_clouds(liquid_bands, ice_bands, thickness, lw_liquid, lw_ice, sw_liquid
     return gc, keep
 
 
+def make_aerosols(lw=None, sw=None):
+    """Pack aerosol inputs into a GrtAerosols struct (+ keep-alive arrays) for Pipeline.run_aerosols.
+    lw / sw: (grid, optics) of that band -- grid [NA] cm-1, strictly increasing, NA >= 2; optics [ncol][3][L][NA] (layer
+    optical depth, single-scattering albedo, asymmetry on the aerosol grid) -- or None: no aerosol in that band.
+    keep["num_points"] is (NA_lw, NA_sw), keep["shapes"] the two optics shapes (None for a band without aerosol)."""
+    keep = {"num_points": [], "shapes": []}
+    for name, band in (("lw", lw), ("sw", sw)):
+        if band is None:
+            keep[name + "_grid"], keep[name + "_optics"] = None, None
+            keep["num_points"].append(0)
+            keep["shapes"].append(None)
+            continue
+        grid, optics = _f64(band[0]), _f64(band[1])
+        if grid.ndim != 1 or grid.size < 2:
+            raise ValueError(f"{name} aerosol grid of {grid.size} point(s): at least 2")
+        if optics.ndim != 4 or optics.shape[1] != 3 or optics.shape[3] != grid.size:
+            raise ValueError(f"{name} aerosol optics of shape {optics.shape}: [ncol][3][L][{grid.size}]")
+        keep[name + "_grid"], keep[name + "_optics"] = grid, optics
+        keep["num_points"].append(grid.size)
+        keep["shapes"].append(optics.shape)
+    keep["num_points"], keep["shapes"] = tuple(keep["num_points"]), tuple(keep["shapes"])
+    ptr = lambda a: _dp(a) if a is not None else None
+    ga = GrtAerosols(keep["num_points"][0], keep["num_points"][1], ptr(keep["lw_grid"]), ptr(keep["sw_grid"]),
+                     ptr(keep["lw_optics"]), ptr(keep["sw_optics"]))
+    return ga, keep
+
+
 class Pipeline:
     def __init__(self, lw_gas, sw_gas, max_columns, user_level, emissivity, albedo, solar, spectral=True):
         """spectral=True keeps tau/omega/g and the spectral fluxes (views(): what parity tests read);
@@ -512,6 +546,8 @@ class Pipeline:
         self.spec = None        # run_spectral's device outputs: allocated at its first call (and for a new bin count)
         self.sub = None         # run_subcolumns' six-row output [max_columns][24]: allocated at its first call
         self.sub_prof = None    # run_subcolumns(profiles=True)' device outputs: allocated at its first call
+        self.aer = None         # run_aerosols' six-row output [max_columns][24]: allocated at its first call
+        self.aer_prof = None    # run_aerosols(profiles=True)' device outputs: allocated at its first call
         self.nw = tuple(g.grid.n if g is not None else 0 for g in (lw_gas, sw_gas))
 
     def run(self, gcols, out_ptr=None):
@@ -659,6 +695,39 @@ class Pipeline:
                           sw_down=lv[:, s, 3].copy(), lw_heating=hr[:, s, 0].copy(), sw_heating=hr[:, s, 1].copy(),
                           fluxes=fx[:, s].copy()) for s in range(2))
 
+    def run_aerosols(self, gcols, gaerosols, profiles=False):
+        """grt_pipeline_run_aerosols into this object's device buffers: the six-row form (aerosol_fluxes() reads it) or,
+        profiles=True, the profile form (aerosol_profiles() reads it)."""
+        V, n = self.num_levels, self.max_columns
+        if not profiles:
+            if self.aer is None:
+                self.aer = DeviceBuffer(self.device, 8 * GRT_ALLSKY_FLUXES_PER_COLUMN * n)
+            check(self.lib.grt_pipeline_run_aerosols(self.p, C.byref(gcols), C.byref(gaerosols), None, None, self.aer.ptr))
+            return
+        if self.aer_prof is None:
+            self.aer_prof = {"levels": DeviceBuffer(self.device, 8 * n * GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN * V),
+                             "heating": DeviceBuffer(self.device, 8 * n * GRT_ALLSKY_HEATING_ROWS_PER_COLUMN * (V - 1)),
+                             "fluxes": DeviceBuffer(self.device, 8 * n * GRT_ALLSKY_FLUXES_PER_COLUMN)}
+        check(self.lib.grt_pipeline_run_aerosols(self.p, C.byref(gcols), C.byref(gaerosols), self.aer_prof["levels"].ptr,
+                                                 self.aer_prof["heating"].ptr, self.aer_prof["fluxes"].ptr))
+
+    def aerosol_fluxes(self, ncol):
+        """The last six-row run_aerosols: (clean, aerosol), each [ncol][12] in grt_pipeline_run's layout."""
+        self.sync()
+        f = self.aer.to_host((ncol, GRT_ALLSKY_FLUXES_PER_COLUMN))
+        return f[:, :GRT_FLUXES_PER_COLUMN].copy(), f[:, GRT_FLUXES_PER_COLUMN:].copy()
+
+    def aerosol_profiles(self, ncol):
+        """The last run_aerosols(profiles=True): (clean, aerosol), allsky_profiles()' keys and shapes."""
+        self.sync()
+        V, P, H, F = self.num_levels, GRT_PROFILE_ROWS_PER_COLUMN, GRT_HEATING_ROWS_PER_COLUMN, GRT_FLUXES_PER_COLUMN
+        lv = self.aer_prof["levels"].to_host((ncol, 2, P, V))
+        hr = self.aer_prof["heating"].to_host((ncol, 2, H, V - 1))
+        fx = self.aer_prof["fluxes"].to_host((ncol, 2, F))
+        return tuple(dict(lw_up=lv[:, s, 0].copy(), lw_down=lv[:, s, 1].copy(), sw_up=lv[:, s, 2].copy(),
+                          sw_down=lv[:, s, 3].copy(), lw_heating=hr[:, s, 0].copy(), sw_heating=hr[:, s, 1].copy(),
+                          fluxes=fx[:, s].copy()) for s in range(2))
+
     def views(self, band):
         ptrs = [C.c_void_p() for _ in range(6)]
         if not self.keep_spectra:
@@ -670,8 +739,12 @@ class Pipeline:
     def destroy(self):
         self.out.free()
         for buf in (list((self.prof or {}).values()) + list((self.allsky_prof or {}).values()) +
-                    list((self.sub_prof or {}).values())):
+                    list((self.sub_prof or {}).values()) + list((self.aer_prof or {}).values())):
             buf.free()
+        self.aer_prof = None
+        if self.aer is not None:
+            self.aer.free()
+            self.aer = None
         self.prof = None
         self.allsky_prof = None
         self.sub_prof = None

@@ -356,19 +356,23 @@ typedef enum GrtSolverForm
     GRT_SOLVER_ALLSKY,      /* fused all-sky, six output rows */
     GRT_SOLVER_ALLSKY_PROFILE,  /* fused all-sky, every level's up and down flux */
     GRT_SOLVER_SPECTRAL,    /* fused clear-sky, six output rows, and the six rows at every point */
-    GRT_SOLVER_ALLSKY_SPECTRAL  /* fused all-sky, six output rows, and the six rows at every point */
+    GRT_SOLVER_ALLSKY_SPECTRAL, /* fused all-sky, six output rows, and the six rows at every point */
+    GRT_SOLVER_AEROSOL,     /* fused clear sky with aerosols, six output rows (grt_launch_lw_aerosols / _sw_aerosols) */
+    GRT_SOLVER_AEROSOL_PROFILE  /* fused clear sky with aerosols, every level's up and down flux */
 } GrtSolverForm;
 /* what a form is: fused (the kernel integrates), profile (every level's fluxes), all-sky (clouds), spectral (a fused
    six-row form that also stores its six rows at every point: up TOA, surface, user at flux_up + c flux_stride + k nw,
-   k = 0, 1, 2, down at flux_down + ...; grt_pipeline_run_spectral) */
-typedef struct GrtFormKind { int fused, profile, allsky, spectral; } GrtFormKind;
+   k = 0, 1, 2, down at flux_down + ...; grt_pipeline_run_spectral), aerosol (the aerosol object joins gas and Rayleigh:
+   GrtAerosolArgs) */
+typedef struct GrtFormKind { int fused, profile, allsky, spectral, aerosol; } GrtFormKind;
 static inline GrtFormKind grt_form_kind(GrtSolverForm form)
 {
     GrtFormKind k;
-    k.profile = form == GRT_SOLVER_PROFILE || form == GRT_SOLVER_ALLSKY_PROFILE;
+    k.profile = form == GRT_SOLVER_PROFILE || form == GRT_SOLVER_ALLSKY_PROFILE || form == GRT_SOLVER_AEROSOL_PROFILE;
     k.spectral = form == GRT_SOLVER_SPECTRAL || form == GRT_SOLVER_ALLSKY_SPECTRAL;
     k.allsky = form == GRT_SOLVER_ALLSKY || form == GRT_SOLVER_ALLSKY_PROFILE || form == GRT_SOLVER_ALLSKY_SPECTRAL;
-    k.fused = form == GRT_SOLVER_FUSED || k.profile || k.allsky || k.spectral;
+    k.aerosol = form == GRT_SOLVER_AEROSOL || form == GRT_SOLVER_AEROSOL_PROFILE;
+    k.fused = form == GRT_SOLVER_FUSED || k.profile || k.allsky || k.spectral || k.aerosol;
     return k;
 }
 /* whether an all-sky form can read `c` */
@@ -379,6 +383,32 @@ static inline int grt_cloud_args_ok(GrtCloudArgs const *c)
 }
 int grt_launch_lw(void *stream, GrtSolverForm form, GrtLwArgs const *a, GrtCloudArgs const *clouds);
 int grt_launch_sw(void *stream, GrtSolverForm form, GrtSwArgs const *a, GrtCloudArgs const *clouds);
+
+/* Aerosol form of the fused solvers (GRT_SOLVER_AEROSOL, GRT_SOLVER_AEROSOL_PROFILE; grt_pipeline_run_aerosols): the
+   fused or the profile form's arguments, and per layer the aerosol object formed in registers and combined with gas and
+   Rayleigh by aerosol_combine (optics_dev.h).  The aerosol's tau, omega, g are given per layer on a coarse wavenumber grid
+   of NA points and put on the spectral grid by the reference's linear_sample (utilities.c:235-246): the host turns each
+   interval's two points into a slope and an intercept once, and a grid point evaluates slope w + intercept.
+   interval: DEVICE [nw], the interval j of each grid point (x[j] < w <= x[j+1]), -1 for a point outside the aerosol grid
+   (no aerosol there); tables: DEVICE [ncol][3][num_intervals][2][L] (tau, omega, g; slope then intercept): a thread's walk
+   over the layers is contiguous, and the lanes of a wave that share an interval read the same addresses. */
+typedef struct GrtAerosolArgs
+{
+    int num_intervals;              /* NA - 1 >= 1 */
+    int const *interval;
+    double const *tables;
+} GrtAerosolArgs;
+static inline int grt_aerosol_args_ok(GrtAerosolArgs const *c)
+{
+    return c != NULL && c->num_intervals >= 1 && c->interval != NULL && c->tables != NULL;
+}
+/* form: GRT_SOLVER_AEROSOL or GRT_SOLVER_AEROSOL_PROFILE (hipErrorInvalidValue otherwise) */
+int grt_launch_lw_aerosols(void *stream, GrtSolverForm form, GrtLwArgs const *a, GrtAerosolArgs const *aerosols);
+int grt_launch_sw_aerosols(void *stream, GrtSolverForm form, GrtSwArgs const *a, GrtAerosolArgs const *aerosols);
+/* Materialised form: the aerosol object of the same tables spread onto the grid, [ncol][L][nw] each (zero where a point
+   has no interval). */
+int grt_launch_spread_aerosols(void *stream, int num_layers, int ncol, double w0, double dw, uint64_t nw,
+                               GrtAerosolArgs const *c, double *tau, double *omega, double *g);
 
 /* Subcolumn form of the two all-sky forms (GRT_SOLVER_ALLSKY when profile == 0, GRT_SOLVER_ALLSKY_PROFILE when 1;
    grt_pipeline_run_subcolumns): one launch solves subcolumns first .. first + count - 1 of every column, a->ncol columns of

@@ -16,7 +16,8 @@
 // batches share a launch.  lw_kernel<true, false> is the fused form of the production pipeline, lw_kernel<true, false, true>
 // its all-sky form, lw_kernel<true, true> and lw_kernel<true, true, true> the profile forms of the two,
 // lw_kernel<true, false, false, true> and lw_kernel<true, false, true, true> the spectral six-row forms of the two, and
-// lw_kernel<true, *, true, false, GrtSubcolumnArgs> the all-sky forms over several subcolumns per column.
+// lw_kernel<true, *, true, false, GrtSubcolumnArgs> the all-sky forms over several subcolumns per column, and lw_kernel<true, *, false, false,
+// GrtAerosolArgs> the clear-sky forms with the aerosol object (the argument's type selects them: LayerOptics).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -123,7 +124,8 @@ __global__ __launch_bounds__(kSolverBlock) void lw_kernel(GrtLwArgs a, Clouds...
     double const *tv = a.t_levels + (uint64_t)col*V;
     double const emis = a.emis[(uint64_t)col*a.emis_stride + ii];
     LevelSink<FUSED, PROFILE, SPECTRAL> sink(a, row.slot, i, live);
-    LayerOptics<FUSED, ALLSKY> const optics(a, cloud_args(clouds...), col, row.tab, ii);   // (fused forms)
+    LayerOptics<FUSED, ALLSKY, IsAerosolPack<Clouds...>::value> const optics(a, cloud_args(clouds...), col, row.tab, ii,
+                                                                             aerosol_args(clouds...));   // (fused forms)
 
     // absorption optical depth of layer j: tau (1 - omega)  (longwave.c:252)
     auto layer_tau = [&](int j) -> double
@@ -339,6 +341,28 @@ extern "C" int grt_launch_lw_subcolumns(void *stream, int profile, GrtLwArgs con
     {
         hipLaunchKernelGGL((lw_kernel<true, false, true, false, GrtSubcolumnArgs>), grid, dim3(kSolverBlock), 0, s, *a,
                            *sc);
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_lw_aerosols(void *stream, GrtSolverForm form, GrtLwArgs const *a, GrtAerosolArgs const *ae)
+{
+    bool const profile = form == GRT_SOLVER_AEROSOL_PROFILE;
+    size_t const lds = profile ? sizeof(double)*2*(size_t)a->num_levels*(kSolverBlock/64) : 0;
+    if ((form != GRT_SOLVER_AEROSOL && !profile) || a->ncol < 1 || a->nw < 2 || a->num_levels < 2 || a->tau_gas == nullptr ||
+        a->n_layer == nullptr || a->partials == nullptr || lds > 65536 || !grt_aerosol_args_ok(ae))
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipStream_t const s = (hipStream_t)stream;
+    dim3 const grid(grt_solver_blocks(a->nw), a->ncol, 1);
+    if (profile)
+    {
+        hipLaunchKernelGGL((lw_kernel<true, true, false, false, GrtAerosolArgs>), grid, dim3(kSolverBlock), lds, s, *a, *ae);
+    }
+    else
+    {
+        hipLaunchKernelGGL((lw_kernel<true, false, false, false, GrtAerosolArgs>), grid, dim3(kSolverBlock), 0, s, *a, *ae);
     }
     return (int)hipGetLastError();
 }

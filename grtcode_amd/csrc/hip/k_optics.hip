@@ -149,6 +149,26 @@ __global__ __launch_bounds__(kBlock) void spread_clouds_kernel(int L, int ncol, 
     }
 }
 
+// Materialised form of grt_pipeline_run_aerosols: the aerosol object of every column on the grid, [ncol][L][nw] each, from
+// the columns' slope and intercept tables (GrtAerosolArgs; aerosol_layer: the fused solvers' expressions).
+__global__ __launch_bounds__(kBlock) void spread_aerosols_kernel(int L, int ncol, double w0, double dw, uint64_t nw,
+                                                                 GrtAerosolArgs c, double *tau, double *omega, double *g)
+{
+    uint64_t const per_col = (uint64_t)L*nw;
+    uint64_t const total = per_col*ncol;
+    uint64_t const plane = 2*(uint64_t)c.num_intervals*L;
+    for (uint64_t o = (uint64_t)blockIdx.x*kBlock + threadIdx.x; o < total; o += (uint64_t)gridDim.x*kBlock)
+    {
+        uint64_t const col = o/per_col;
+        uint64_t const r = o - col*per_col;
+        int const j = (int)(r/nw);
+        uint64_t const i = r - (uint64_t)j*nw;
+        int const interval = c.interval[i];
+        double const *tab = c.tables + col*3*plane + (uint64_t)(interval < 0 ? 0 : interval)*2*L;
+        aerosol_layer(tab, plane, L, interval, j, w0 + i*dw, tau[o], omega[o], g[o]);
+    }
+}
+
 // tau_gas += the spectral tables' part, for a tau the gas-optics launch wrote without it (GrtGasOpticsArgs.skip_tables):
 // the pipeline's fused solvers add it themselves; this completes the array for a caller that wants to LOOK at tau_gas
 // (grt_pipeline_views).  One thread per grid point and column, walking the layers: continua_add's doubles.
@@ -561,6 +581,18 @@ extern "C" int grt_launch_spread_clouds(void *stream, int num_layers, int ncol, 
     hipLaunchKernelGGL(spread_clouds_kernel, dim3(grid_for((uint64_t)num_layers*nw*ncol)), dim3(kBlock), 0,
                        (hipStream_t)stream, num_layers, ncol, nw, *c, liquid_tau, liquid_omega, liquid_g,
                        ice_tau, ice_omega, ice_g);
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_spread_aerosols(void *stream, int num_layers, int ncol, double w0, double dw, uint64_t nw,
+                                          GrtAerosolArgs const *c, double *tau, double *omega, double *g)
+{
+    if (num_layers < 1 || ncol < 1 || !grt_aerosol_args_ok(c) || tau == nullptr || omega == nullptr || g == nullptr)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(spread_aerosols_kernel, dim3(grid_for((uint64_t)num_layers*nw*ncol)), dim3(kBlock), 0,
+                       (hipStream_t)stream, num_layers, ncol, w0, dw, nw, *c, tau, omega, g);
     return (int)hipGetLastError();
 }
 

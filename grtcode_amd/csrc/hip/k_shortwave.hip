@@ -19,7 +19,8 @@
 // doubles: identical fluxes) -- 0.69 instead of 1.04 ms for 8 columns, at 4.2 TB/s.  sw_kernel<true, false, true> is its
 // all-sky form, sw_kernel<true, true> and sw_kernel<true, true, true> the profile forms of the two, sw_kernel<true, false, false,
 // true> and sw_kernel<true, false, true, true> the spectral six-row forms of the two, and sw_kernel<true, *, true, false,
-// GrtSubcolumnArgs> the all-sky forms over several subcolumns per column.
+// GrtSubcolumnArgs> the all-sky forms over several subcolumns per column, and sw_kernel<true, *, false, false,
+// GrtAerosolArgs> the clear-sky forms with the aerosol object (the argument's type selects them: LayerOptics).
 // The in-kernel range checks of the reference are no-ops on device builds
 // (debug.h:105-116) and are not restated.
 #include <hip/hip_runtime.h>
@@ -277,7 +278,8 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Clouds...
     double *pp = FUSED ? a.park + ((uint64_t)row.park*park_rows + 2*(uint64_t)V)*nw + ii : nullptr;
     int const user = a.user_level;
     LevelSink<FUSED, PROFILE, SPECTRAL> sink(a, row.slot, i, live);
-    LayerOptics<FUSED, ALLSKY> const optics(a, cloud_args(clouds...), col, row.tab, ii);   // (fused forms)
+    LayerOptics<FUSED, ALLSKY, IsAerosolPack<Clouds...>::value> const optics(a, cloud_args(clouds...), col, row.tab, ii,
+                                                                             aerosol_args(clouds...));   // (fused forms)
 
     auto props_of = [&](int j) -> LayerProps
     {
@@ -596,6 +598,29 @@ extern "C" int grt_launch_sw_subcolumns(void *stream, int profile, GrtSwArgs con
     {
         hipLaunchKernelGGL((sw_kernel<true, false, true, false, GrtSubcolumnArgs>), grid, dim3(kSolverBlock), 0, s, *a,
                            *sc);
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_sw_aerosols(void *stream, GrtSolverForm form, GrtSwArgs const *a, GrtAerosolArgs const *ae)
+{
+    bool const profile = form == GRT_SOLVER_AEROSOL_PROFILE;
+    size_t const lds = profile ? sizeof(double)*2*(size_t)a->num_levels*(kSolverBlock/64) : 0;
+    bool const park = form == GRT_SOLVER_AEROSOL_PROFILE || !grt_sw_one_sweep(a);
+    if ((form != GRT_SOLVER_AEROSOL && !profile) || a->ncol < 1 || a->nw < 2 || a->num_levels < 2 || a->tau_gas == nullptr ||
+        a->n_layer == nullptr || a->partials == nullptr || lds > 65536 || !grt_aerosol_args_ok(ae) || (park && a->park == nullptr))
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipStream_t const s = (hipStream_t)stream;
+    dim3 const grid(grt_solver_blocks(a->nw), a->ncol, 1);
+    if (profile)
+    {
+        hipLaunchKernelGGL((sw_kernel<true, true, false, false, GrtAerosolArgs>), grid, dim3(kSolverBlock), lds, s, *a, *ae);
+    }
+    else
+    {
+        hipLaunchKernelGGL((sw_kernel<true, false, false, false, GrtAerosolArgs>), grid, dim3(kSolverBlock), 0, s, *a, *ae);
     }
     return (int)hipGetLastError();
 }

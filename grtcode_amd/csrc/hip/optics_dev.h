@@ -59,6 +59,26 @@ __device__ __forceinline__ void allsky_combine(double tg, double tr, double tl, 
     tau = ts;
 }
 
+// add_optics({gas, rayleigh, aerosol}) for one (layer, wavenumber) (driver.c:426-434): the sums of optics.c:138-145 term by
+// term in that order, as clear_sky_combine and allsky_combine write them.  An aerosol of exact zeros adds exact zeros: a
+// point with no aerosol gets clear_sky_combine's doubles.
+__device__ __forceinline__ void aerosol_combine(double tg, double tr, double ta, double oa, double ga, double &tau,
+                                                double &omega, double &g)
+{
+    double gs = 0., os = 0., ts = 0.;
+    gs += 0.*0.*tg;  os += 0.*tg;  ts += tg;
+    gs += 0.*1.*tr;  os += 1.*tr;  ts += tr;
+    gs += ga*oa*ta;  os += oa*ta;  ts += ta;
+    if (!(gs == 0. && os > 0. && os < 1.7976931348623157e308))
+    {
+        gs /= os;           // (as clear_sky_combine: +0 over a positive finite number is +0)
+    }
+    os /= ts;
+    g = gs;
+    omega = os;
+    tau = ts;
+}
+
 // The solver kernels' cloud arguments: none in the clear-sky instances, one GrtCloudArgs in the all-sky ones (their
 // template parameter pack: the clear-sky instances keep their parameter list)
 __device__ __forceinline__ GrtCloudArgs cloud_args()
@@ -76,6 +96,26 @@ __device__ __forceinline__ GrtCloudArgs cloud_args(GrtSubcolumnArgs const &c)
     return c.clouds;
 }
 
+__device__ __forceinline__ GrtCloudArgs cloud_args(GrtAerosolArgs const &)
+{
+    return cloud_args();
+}
+
+// ... and their aerosol arguments: one GrtAerosolArgs in the aerosol instances (the same pack), none in the others
+template <typename... Pack> struct IsAerosolPack { static constexpr bool value = false; };
+template <> struct IsAerosolPack<GrtAerosolArgs> { static constexpr bool value = true; };
+
+template <typename... Pack>
+__device__ __forceinline__ GrtAerosolArgs aerosol_args(Pack const &...)
+{
+    return GrtAerosolArgs{0, nullptr, nullptr};
+}
+
+__device__ __forceinline__ GrtAerosolArgs aerosol_args(GrtAerosolArgs const &c)
+{
+    return c;
+}
+
 // What grid row blockIdx.y stands for: col, the column whose gas state (tau_gas, temperatures, sun) it reads; tab, its
 // cloud tables' column; slot, its partial sums' column; park, its rows of the shortwave park block.  All four are
 // blockIdx.y but in the subcolumn instances (GrtSubcolumnArgs: row y is column y / count, subcolumn first + y % count).
@@ -88,6 +128,12 @@ __device__ __forceinline__ SolverRow solver_row(int)
 }
 
 __device__ __forceinline__ SolverRow solver_row(int, GrtCloudArgs const &)
+{
+    int const y = blockIdx.y;
+    return SolverRow{y, y, y, y};
+}
+
+__device__ __forceinline__ SolverRow solver_row(int, GrtAerosolArgs const &)
 {
     int const y = blockIdx.y;
     return SolverRow{y, y, y, y};
@@ -114,6 +160,22 @@ __device__ __forceinline__ void cloud_layer(double const *tab, int B, int L, int
         t = tab[at]*thickness;
         o = tab[plane + at];
         g = tab[2*plane + at];
+    }
+}
+
+// The aerosol object at (layer j, wavenumber w) from one interval's block tab [3][NI][2][L] + interval*2 L of a column's
+// table (GrtAerosolArgs: tau, omega, g; slope then intercept): linear_sample's m w + b (utilities.c:235-246); no interval
+// (interval < 0): no aerosol.  plane = NI 2 L, the doubles from one property to the next.
+__device__ __forceinline__ void aerosol_layer(double const *tab, uint64_t plane, int L, int interval, int j, double w,
+                                              double &t, double &o, double &g)
+{
+    t = 0.; o = 0.; g = 0.;
+    if (interval >= 0)
+    {
+        double const *q = tab + j;
+        t = q[0]*w + q[L];
+        o = q[plane]*w + q[plane + L];
+        g = q[2*plane]*w + q[2*plane + L];
     }
 }
 
@@ -277,8 +339,10 @@ __device__ __forceinline__ double trapezoid_weight(uint64_t i, uint64_t nw, doub
 // objects join (GrtCloudArgs): the point reads its two band indices once, each layer forms the two objects from the
 // column's band tables and allsky_combine adds the four.  Built once per thread from the fields both solvers' argument
 // structs carry; FUSED false (the spectral forms, which read their optics): nothing is loaded.  tab: the column of the
-// cloud tables (SolverRow; col but in the subcolumn instances).
-template <bool FUSED, bool ALLSKY>
+// cloud tables (SolverRow; col but in the subcolumn instances).  AEROSOL (clear-sky forms): the aerosol object joins
+// (GrtAerosolArgs): the point reads its interval once, each layer forms the object from the column's slope and intercept
+// table (six loads, three multiply-adds) and aerosol_combine adds the three.
+template <bool FUSED, bool ALLSKY, bool AEROSOL = false>
 struct LayerOptics
 {
     GrtContinua const *c;
@@ -291,9 +355,13 @@ struct LayerOptics
     GrtCloudArgs cl;
     int L, col, band_l, band_i;
     uint64_t ctab;
+    double const *atab;                     // AEROSOL: the column's table at this point's interval
+    uint64_t aplane;
+    int ainterval;
 
     template <typename Args>
-    __device__ __forceinline__ LayerOptics(Args const &a, GrtCloudArgs const &cl_, int col_, int tab, uint64_t ii_)
+    __device__ __forceinline__ LayerOptics(Args const &a, GrtCloudArgs const &cl_, int col_, int tab, uint64_t ii_,
+                                           GrtAerosolArgs const &ae = GrtAerosolArgs{0, nullptr, nullptr})
     {
         L = a.num_levels - 1;
         col = col_;
@@ -315,6 +383,9 @@ struct LayerOptics
         band_l = ALLSKY ? cl.band_liquid[ii] : -1;
         band_i = ALLSKY ? cl.band_ice[ii] : -1;
         ctab = ALLSKY ? (uint64_t)tab*3*(uint64_t)cl.num_bands*L : 0;
+        ainterval = AEROSOL ? ae.interval[ii] : -1;
+        aplane = AEROSOL ? 2*(uint64_t)ae.num_intervals*L : 0;
+        atab = AEROSOL ? ae.tables + (uint64_t)tab*3*aplane + (uint64_t)(ainterval < 0 ? 0 : ainterval)*2*L : nullptr;
     }
 
     __device__ __forceinline__ void at(int j, double &t, double &om, double &gg) const
@@ -331,6 +402,12 @@ struct LayerOptics
             cloud_layer(cl.liquid + ctab, cl.num_bands, L, band_l, j, th, lt, lo, lg);
             cloud_layer(cl.ice + ctab, cl.num_bands, L, band_i, j, th, it, io, ig);
             allsky_combine(tg, rayleigh_tau(w, nl[j]), lt, lo, lg, it, io, ig, t, om, gg);
+        }
+        else if constexpr (AEROSOL)
+        {
+            double at_, ao, ag;
+            aerosol_layer(atab, aplane, L, ainterval, j, w, at_, ao, ag);
+            aerosol_combine(tg, rayleigh_tau(w, nl[j]), at_, ao, ag, t, om, gg);
         }
         else
         {

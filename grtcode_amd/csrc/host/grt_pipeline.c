@@ -24,6 +24,9 @@
  * tau_gas, and one finishing launch for the two sets.
  * grt_pipeline_run_subcolumns runs either of the two with the all-sky pass averaged over several cloud subcolumns, all of
  * them on the one tau_gas.
+ * grt_pipeline_run_aerosols runs the clear-clean pass of grt_pipeline_run or grt_pipeline_run_profiles and then, on the
+ * same tau_gas, the clear-sky pass with aerosols of driver.c:426-472: the aerosol object formed inside the solvers from
+ * per-column slope and intercept tables (or, materialised form, spread onto the grid and added by the add_optics kernel).
  * All work is enqueued on the device's library stream; nothing synchronises.
  */
 #include <stdlib.h>
@@ -64,6 +67,11 @@ typedef struct GrtBand
     double *sub_partials;  /* fused form: [max_cols][S][6 or 2 V][nblocks] partial sums of the all-sky pass */
     size_t sub_cap;        /* its doubles */
     double *flux_sum;      /* materialised form: [2][max_cols][V][n] sums of the subcolumns' up and down fluxes */
+    /* grt_pipeline_run_aerosols: */
+    int *aer_map;          /* [n] interval of the band's aerosol grid each grid point lies in, -1: none */
+    double *aer_key;       /* host: the aerosol grid aer_map was built for */
+    int aer_key_n;
+    double *aer_block;     /* materialised form: aerosol tau, omega, g [3][max_cols][L][n], Rayleigh [3][L][n], zeros [L][n] */
 } GrtBand;
 
 struct GrtPipeline
@@ -83,6 +91,11 @@ struct GrtPipeline
     double *cloud_h, *cloud_d;
     size_t cloud_doubles;
     void *cloud_uploaded;
+    /* grt_pipeline_run_aerosols' slope and intercept tables: pinned host staging + device copy, the longwave's
+       [cols][3][NA - 1][2][L], then the shortwave's */
+    double *aer_h, *aer_d;
+    size_t aer_doubles;
+    void *aer_uploaded;
 };
 
 static void grt_pipeline_release(GrtPipeline_t **pipeline);
@@ -278,7 +291,13 @@ static void grt_pipeline_release(GrtPipeline_t **pipeline)
         free(p->band[b].bin_edges);
         grt_dev_free(p->device, p->band[b].sub_partials);
         grt_dev_free(p->device, p->band[b].flux_sum);
+        grt_dev_free(p->device, p->band[b].aer_map);
+        grt_dev_free(p->device, p->band[b].aer_block);
+        free(p->band[b].aer_key);
     }
+    grt_dev_free(p->device, p->aer_d);
+    grt_host_free_pinned(p->aer_h);
+    grt_dev_event_destroy(p->device, &p->aer_uploaded);
     grt_dev_free(p->device, p->cloud_d);
     grt_host_free_pinned(p->cloud_h);
     grt_dev_event_destroy(p->device, &p->cloud_uploaded);
@@ -535,12 +554,13 @@ static size_t band_points(GrtPipeline_t const *p, int bi)
     return p->band[bi].gas != NULL ? p->band[bi].n : 0;
 }
 
-/* the band's solver in `form` (GRT_SOLVER_CHAINS: the spectral form), timed under profile tag 3/4, or 8/9 with clouds;
+/* the band's solver in `form` (GRT_SOLVER_CHAINS: the spectral form), timed under profile tag 3/4, or 8/9 with clouds, or
+   12/13 in the aerosol pass (aer: the aerosol forms' tables; tagged: the materialised aerosol pass);
    the profile forms share the band's park block with the two-sweep six-row forms (the passes run in stream order); the
    spectral six-row forms store their rows where so places the band's */
 static int band_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtSolverForm form, int defer,
-                       GrtContinua const *continua, GrtCloudArgs const *clouds, double *partials,
-                       SpectralOut const *so)
+                       GrtContinua const *continua, GrtCloudArgs const *clouds, GrtAerosolArgs const *aer, int aer_pass,
+                       double *partials, SpectralOut const *so)
 {
     GrtFormKind const k = grt_form_kind(form);
     void *s = grt_dev_stream(p->device);
@@ -557,8 +577,8 @@ static int band_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtSolverFor
             a.flux_down = a.flux_up + 3*b->n;
             a.flux_stride = stride;
         }
-        slot = grt_profile_begin(s, clouds ? 8 : 3);
-        krc = grt_launch_lw(s, form, &a, clouds);
+        slot = grt_profile_begin(s, aer_pass ? 12 : (clouds ? 8 : 3));
+        krc = k.aerosol ? grt_launch_lw_aerosols(s, form, &a, aer) : grt_launch_lw(s, form, &a, clouds);
     }
     else
     {
@@ -577,8 +597,8 @@ static int band_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtSolverFor
             GRT_TRY(park_block(p, b));
         }
         a.park = b->park;
-        slot = grt_profile_begin(s, clouds ? 9 : 4);
-        krc = grt_launch_sw(s, form, &a, clouds);
+        slot = grt_profile_begin(s, aer_pass ? 13 : (clouds ? 9 : 4));
+        krc = k.aerosol ? grt_launch_sw_aerosols(s, form, &a, aer) : grt_launch_sw(s, form, &a, clouds);
     }
     grt_profile_end(s, slot);
     GRT_TRY(grt_dev_check(krc, bi == 0 ? "longwave kernel" : "shortwave kernel"));
@@ -836,6 +856,176 @@ static int band_allsky_optics(GrtPipeline_t *p, GrtBand *b, int C, GrtCloudArgs 
     return GRTCODE_SUCCESS;
 }
 
+/* ---- aerosol inputs (grt_pipeline_run_aerosols) ---------------------------------------------------------------------- */
+
+static int aerosol_points(GrtAerosols_t const *ae, int bi)
+{
+    return bi == 0 ? ae->lw_num_points : ae->sw_num_points;
+}
+
+/* The interval of the aerosol grid x [na] (strictly increasing) each of the n points w0 + i dw lies in, as
+   interpolate2 (utilities.c:149-222) assigns them: j with x[j] < w <= x[j+1]; -1 for w <= x[0] and for w > x[na-1],
+   which the reference does not write. */
+void grt_aerosol_interval_map(double w0, double dw, uint64_t n, double const *x, int na, int *interval)
+{
+    for (uint64_t i = 0; i < n; ++i)
+    {
+        double const w = w0 + i*dw;
+        interval[i] = (w <= x[0] || w > x[na - 1]) ? -1 : first_not_below(x, na, w) - 1;
+    }
+}
+
+/* linear_sample's (utilities.c:235-246) slope and intercept of every interval, layer and property of ncol columns:
+   optics [ncol][3][L][na] -> tables [ncol][3][na - 1][2][L] (GrtAerosolArgs) */
+void grt_aerosol_tables(double const *x, int na, int ncol, int num_layers, double const *optics, double *tables)
+{
+    size_t const L = (size_t)num_layers, NA = (size_t)na, NI = NA - 1;
+    for (size_t cp = 0; cp < (size_t)ncol*3; ++cp)
+    {
+        for (size_t l = 0; l < L; ++l)
+        {
+            double const *y = optics + (cp*L + l)*NA;
+            for (size_t j = 0; j < NI; ++j)
+            {
+                double const m = (y[j + 1] - y[j])/(x[j + 1] - x[j]);
+                double const b = y[j] - m*x[j];
+                tables[((cp*NI + j)*2 + 0)*L + l] = m;
+                tables[((cp*NI + j)*2 + 1)*L + l] = b;
+            }
+        }
+    }
+}
+
+/* the batch's slope and intercept tables to the device: the longwave's [C][3][NA - 1][2][L], then the shortwave's (a band
+   the pipeline does not have, or one given no aerosol, takes no room) */
+static int stage_aerosols(GrtPipeline_t *p, GrtAerosols_t const *ae, int C)
+{
+    size_t const L = (size_t)p->num_levels - 1;
+    size_t per[2], need = 0, want = 0;
+    for (int bi = 0; bi < 2; ++bi)
+    {
+        int const na = p->band[bi].gas != NULL ? aerosol_points(ae, bi) : 0;
+        per[bi] = na > 0 ? 6*L*((size_t)na - 1) : 0;
+        need += (size_t)C*per[bi];
+        want += (size_t)p->max_cols*per[bi];
+    }
+    if (need == 0)
+    {
+        return GRTCODE_SUCCESS;
+    }
+    GRT_TRY(grt_dev_event_wait(p->device, p->aer_uploaded));
+    void *s = grt_dev_stream(p->device);
+    if (need > p->aer_doubles)
+    {
+        /* (sized for max_columns at these grids: a later batch of the same shape reuses it) */
+        GRT_TRY(grt_dev_sync(p->device, s));
+        grt_dev_free(p->device, p->aer_d);
+        grt_host_free_pinned(p->aer_h);
+        p->aer_d = NULL;
+        p->aer_h = NULL;
+        p->aer_doubles = 0;
+        GRT_TRY(grt_host_alloc_pinned((void **)&p->aer_h, sizeof(double)*want));
+        GRT_TRY(grt_dev_alloc(p->device, (void **)&p->aer_d, sizeof(double)*want));
+        p->aer_doubles = want;
+    }
+    if (per[0] > 0)
+    {
+        grt_aerosol_tables(ae->lw_grid, ae->lw_num_points, C, (int)L, ae->lw_optics, p->aer_h);
+    }
+    if (per[1] > 0)
+    {
+        grt_aerosol_tables(ae->sw_grid, ae->sw_num_points, C, (int)L, ae->sw_optics, p->aer_h + (size_t)C*per[0]);
+    }
+    GRT_TRY(grt_dev_upload(p->device, p->aer_d, p->aer_h, sizeof(double)*need, s));
+    GRT_TRY(grt_dev_event_record(p->device, &p->aer_uploaded, s));
+    return GRTCODE_SUCCESS;
+}
+
+/* the band's aerosol arguments for a batch of C columns staged by stage_aerosols: its per-point intervals are built on the
+   host when the band's aerosol grid differs from the last call's */
+static int band_aerosols(GrtPipeline_t *p, GrtBand *b, int bi, GrtAerosols_t const *ae, int C, GrtAerosolArgs *aa)
+{
+    int const na = aerosol_points(ae, bi);
+    double const *x = bi == 0 ? ae->lw_grid : ae->sw_grid;
+    size_t const L = (size_t)p->num_levels - 1;
+    int const na_lw = p->band[0].gas != NULL ? ae->lw_num_points : 0;
+    aa->num_intervals = na - 1;
+    aa->tables = p->aer_d + (bi == 1 && na_lw > 0 ? (size_t)C*6*L*((size_t)na_lw - 1) : 0);
+    if (b->aer_map != NULL && b->aer_key_n == na && memcmp(b->aer_key, x, sizeof(double)*(size_t)na) == 0)
+    {
+        aa->interval = b->aer_map;
+        return GRTCODE_SUCCESS;
+    }
+    double *key = malloc(sizeof(double)*(size_t)na);
+    int *idx = malloc(sizeof(int)*b->n);
+    int rc = (key == NULL || idx == NULL) ? GRTCODE_NULL_ERR : GRTCODE_SUCCESS;
+    if (rc == GRTCODE_SUCCESS)
+    {
+        memcpy(key, x, sizeof(double)*(size_t)na);
+        grt_aerosol_interval_map(b->gas->grid.w0, b->gas->grid.dw, b->n, x, na, idx);
+        void *s = grt_dev_stream(p->device);
+        if (b->aer_map == NULL)
+        {
+            void *m = NULL;
+            rc = grt_dev_alloc(p->device, &m, sizeof(int)*b->n);
+            b->aer_map = m;
+        }
+        /* (the last batch's kernels may still read the old map; then idx is freed: wait both times) */
+        if (rc == GRTCODE_SUCCESS) rc = grt_dev_sync(p->device, s);
+        if (rc == GRTCODE_SUCCESS) rc = grt_dev_upload(p->device, b->aer_map, idx, sizeof(int)*b->n, s);
+        if (rc == GRTCODE_SUCCESS) rc = grt_dev_sync(p->device, s);
+    }
+    free(idx);
+    if (rc != GRTCODE_SUCCESS)
+    {
+        free(key);
+        free(b->aer_key);               /* (the device map may be half written: it is rebuilt at the next call) */
+        b->aer_key = NULL;
+        b->aer_key_n = 0;
+        GRT_TRY(rc);
+    }
+    free(b->aer_key);
+    b->aer_key = key;
+    b->aer_key_n = na;
+    aa->interval = b->aer_map;
+    return GRTCODE_SUCCESS;
+}
+
+/* Materialised form: the aerosol object spread onto the grid, Rayleigh, add_optics of the three objects per column
+   (driver.c:426-434) -- tau, omega, g of the band are the aerosol pass's */
+static int band_aerosol_optics(GrtPipeline_t *p, GrtBand *b, int C, GrtAerosolArgs const *aa)
+{
+    SpectralGrid_t const *grid = &b->gas->grid;
+    int const L = p->num_levels - 1;
+    uint64_t const per = (uint64_t)L*b->n, all = per*(uint64_t)p->max_cols;
+    void *s = grt_dev_stream(p->device);
+    if (b->aer_block == NULL)
+    {
+        void *blk = NULL;
+        GRT_TRY(grt_dev_alloc(p->device, &blk, sizeof(double)*(3*all + 4*per)));
+        b->aer_block = blk;
+        GRT_TRY(grt_dev_zero(p->device, b->aer_block + 3*all + 3*per, sizeof(double)*per, s));
+    }
+    double *aer[3] = {b->aer_block, b->aer_block + all, b->aer_block + 2*all};
+    double *ray = b->aer_block + 3*all, *zero = ray + 3*per;
+    GRT_TRY(grt_dev_check(grt_launch_spread_aerosols(s, L, C, grid->w0, grid->dw, b->n, aa, aer[0], aer[1], aer[2]),
+                          "aerosol spreading kernel"));
+    for (int c = 0; c < C; ++c)
+    {
+        GRT_TRY(grt_dev_check(grt_launch_rayleigh(s, L, grid->w0, grid->dw, b->n, p->small_h + p->off_n + (size_t)c*L,
+                                                  ray, ray + per, ray + 2*per), "Rayleigh kernel"));
+        GrtOpticsPtrs in;
+        memset(&in, 0, sizeof(in));
+        uint64_t const o = (uint64_t)c*per;
+        in.tau[0] = b->tau_gas + o; in.omega[0] = zero; in.g[0] = zero;
+        in.tau[1] = ray; in.omega[1] = ray + per; in.g[1] = ray + 2*per;
+        in.tau[2] = aer[0] + o; in.omega[2] = aer[1] + o; in.g[2] = aer[2] + o;
+        GRT_TRY(grt_dev_check(grt_launch_add_optics(s, per, 3, &in, b->tau + o, b->omega + o, b->g + o),
+                              "add_optics kernel (aerosols)"));
+    }
+    return GRTCODE_SUCCESS;
+}
+
 /* ---- spectral rows and bins (grt_pipeline_run_spectral) ------------------------------------------------------------ */
 
 /* the band's bin table for these edges (built and uploaded when they differ from the last call's) and room for the partial
@@ -912,7 +1102,7 @@ static int band_solve_spectral(GrtPipeline_t *p, GrtBand *b, int bi, int C, int 
     if (!p->keep_spectra)
     {
         GRT_TRY(band_solver(p, b, bi, C, clouds ? GRT_SOLVER_ALLSKY_SPECTRAL : GRT_SOLVER_SPECTRAL, defer, continua,
-                            clouds, b->partials, so));
+                            clouds, NULL, 0, b->partials, so));
         GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, b->partials, C*GRT_FLUXES_PER_BAND, b->nblocks, out,
                                                          GRT_FLUXES_PER_BAND, out_stride, out_offset),
                               "flux reduction kernel"));
@@ -920,7 +1110,7 @@ static int band_solve_spectral(GrtPipeline_t *p, GrtBand *b, int bi, int C, int 
     else
     {
         GRT_TRY(clouds ? band_allsky_optics(p, b, C, clouds) : band_clear_sky_optics(p, b, C));
-        GRT_TRY(band_solver(p, b, bi, C, GRT_SOLVER_CHAINS, defer, continua, clouds, NULL, NULL));
+        GRT_TRY(band_solver(p, b, bi, C, GRT_SOLVER_CHAINS, defer, continua, clouds, NULL, 0, NULL, NULL));
         GRT_TRY(grt_dev_check(grt_launch_copy_rows(s, (double const *const *)b->rows_d, C*GRT_FLUXES_PER_BAND, b->n,
                                                    rows, stride), "spectral row copy kernel"));
         GRT_TRY(grt_dev_check(grt_launch_integrate_rows(s, (double const *const *)b->rows_d, C*GRT_FLUXES_PER_BAND, b->n,
@@ -950,10 +1140,12 @@ static int band_solve_spectral(GrtPipeline_t *p, GrtBand *b, int bi, int C, int 
    out[c*out_stride + out_offset + bi*rows + r].  Fused form: all of it in one solver launch, then the fixed-order sum of
    its per-block partial sums (profile: in level_partials, which the clear-sky and the all-sky pass of
    grt_pipeline_run_allsky_profiles take in turn); materialised form: tau, omega, g and the spectral fluxes in the band's
-   arrays, then the row-wise trapezoid. */
+   arrays, then the row-wise trapezoid.  aer_pass: the aerosol pass of grt_pipeline_run_aerosols (profile tags 12 / 13) --
+   add_optics({gas, rayleigh, aerosol}) from aer's tables, or, aer NULL (a band given no aerosol), the clear-sky solve
+   again. */
 static int band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, int defer, GrtContinua const *continua,
-                      GrtCloudArgs const *clouds, int profile, double *out, int out_stride, int out_offset,
-                      SpectralOut const *so)
+                      GrtCloudArgs const *clouds, GrtAerosolArgs const *aer, int aer_pass, int profile, double *out,
+                      int out_stride, int out_offset, SpectralOut const *so)
 {
     int const V = p->num_levels, rows = profile ? 2*V : GRT_FLUXES_PER_BAND;
     out_offset += bi*rows;
@@ -972,15 +1164,17 @@ static int band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, int defer, Gr
             b->level_partials = lp;
         }
         double *partials = profile ? b->level_partials : b->partials;
-        GrtSolverForm const form = profile ? (clouds ? GRT_SOLVER_ALLSKY_PROFILE : GRT_SOLVER_PROFILE)
+        GrtSolverForm const form = aer ? (profile ? GRT_SOLVER_AEROSOL_PROFILE : GRT_SOLVER_AEROSOL)
+                                 : profile ? (clouds ? GRT_SOLVER_ALLSKY_PROFILE : GRT_SOLVER_PROFILE)
                                            : (clouds ? GRT_SOLVER_ALLSKY : GRT_SOLVER_FUSED);
-        GRT_TRY(band_solver(p, b, bi, C, form, defer, continua, clouds, partials, so));
+        GRT_TRY(band_solver(p, b, bi, C, form, defer, continua, clouds, aer, aer_pass, partials, so));
         GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, partials, C*rows, b->nblocks, out, rows, out_stride, out_offset),
                               "flux reduction kernel"));
         return GRTCODE_SUCCESS;
     }
-    GRT_TRY(clouds ? band_allsky_optics(p, b, C, clouds) : band_clear_sky_optics(p, b, C));
-    GRT_TRY(band_solver(p, b, bi, C, GRT_SOLVER_CHAINS, defer, continua, clouds, NULL, NULL));
+    GRT_TRY(aer ? band_aerosol_optics(p, b, C, aer) : clouds ? band_allsky_optics(p, b, C, clouds)
+                                                             : band_clear_sky_optics(p, b, C));
+    GRT_TRY(band_solver(p, b, bi, C, GRT_SOLVER_CHAINS, defer, continua, clouds, NULL, aer_pass, NULL, NULL));
     if (profile)
     {
         GRT_TRY(level_rows(p, b));
@@ -1078,7 +1272,7 @@ static int band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, in
         cj.liquid += (size_t)j*tab;
         cj.ice += (size_t)j*tab;
         GRT_TRY(band_allsky_optics(p, b, C, &cj));
-        GRT_TRY(band_solver(p, b, bi, C, GRT_SOLVER_CHAINS, defer, continua, &cj, NULL, NULL));
+        GRT_TRY(band_solver(p, b, bi, C, GRT_SOLVER_CHAINS, defer, continua, &cj, NULL, 0, NULL, NULL));
         GRT_TRY(grt_dev_check(grt_launch_flux_accumulate(s, per, b->flux_up, b->flux_sum, j == 0), "flux sum kernel"));
         GRT_TRY(grt_dev_check(grt_launch_flux_accumulate(s, per, b->flux_down, b->flux_sum + all, j == 0),
                               "flux sum kernel"));
@@ -1099,14 +1293,18 @@ static int band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, in
    the gas optics and the solve into out (band_solve) -- with clouds, the clear-sky solve and then the all-sky one, whose
    rows follow the clear-sky set's GRT_FLUXES_PER_COLUMN or (profile) GRT_PROFILE_ROWS_PER_COLUMN V.  subcolumns > 0
    (grt_pipeline_run_subcolumns): the all-sky pass is the mean over that many subcolumns (band_solve_subcolumns). */
-static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl, int subcolumns, int profile,
-                        double *out, int out_stride, SpectralOut *so)
+static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl, GrtAerosols_t const *ae,
+                        int subcolumns, int profile, double *out, int out_stride, SpectralOut *so)
 {
     GRT_TRY(stage_columns(p, cols));
     int const C = cols->ncol, S = subcolumns > 0 ? subcolumns : 1;
     if (cl != NULL)
     {
         GRT_TRY(stage_clouds(p, cl, C, S));
+    }
+    if (ae != NULL)
+    {
+        GRT_TRY(stage_aerosols(p, ae, C));
     }
     for (int bi = 0; bi < 2; ++bi)
     {
@@ -1122,7 +1320,7 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t 
                 {
                     double *six = out + (size_t)c*out_stride + GRT_FLUXES_PER_BAND*bi;
                     GRT_TRY(grt_dev_zero(p->device, six, sizeof(double)*GRT_FLUXES_PER_BAND, s));
-                    if (cl != NULL)
+                    if (cl != NULL || ae != NULL)
                     {
                         GRT_TRY(grt_dev_zero(p->device, six + GRT_FLUXES_PER_COLUMN, sizeof(double)*GRT_FLUXES_PER_BAND, s));
                     }
@@ -1142,7 +1340,20 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t 
         {
             so->set = 0;
         }
-        GRT_TRY(band_solve(p, b, bi, C, defer, &continua, NULL, profile, out, out_stride, 0, so));
+        GRT_TRY(band_solve(p, b, bi, C, defer, &continua, NULL, NULL, 0, profile, out, out_stride, 0, so));
+        if (ae != NULL)
+        {
+            /* the aerosol set follows the clear-clean one, as the all-sky set does */
+            int const set = profile ? GRT_PROFILE_ROWS_PER_COLUMN*p->num_levels : GRT_FLUXES_PER_COLUMN;
+            GrtAerosolArgs aa;
+            int const has = aerosol_points(ae, bi) > 0;
+            if (has)
+            {
+                GRT_TRY(band_aerosols(p, b, bi, ae, C, &aa));
+            }
+            GRT_TRY(band_solve(p, b, bi, C, defer, &continua, NULL, has ? &aa : NULL, 1, profile, out, out_stride, set,
+                               NULL));
+        }
         if (cl != NULL)
         {
             int const set = profile ? GRT_PROFILE_ROWS_PER_COLUMN*p->num_levels : GRT_FLUXES_PER_COLUMN;
@@ -1155,7 +1366,7 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t 
                 GRT_TRY(band_solve_subcolumns(p, b, bi, C, S, defer, &continua, &ca, profile, out, out_stride, set));
                 continue;
             }
-            GRT_TRY(band_solve(p, b, bi, C, defer, &continua, &ca, profile, out, out_stride, set, so));
+            GRT_TRY(band_solve(p, b, bi, C, defer, &continua, &ca, NULL, 0, profile, out, out_stride, set, so));
         }
     }
     return GRTCODE_SUCCESS;
@@ -1166,7 +1377,7 @@ EXTERN int grt_pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, fp_t *fl
     GRT_REQUIRE_PTR(p);
     GRT_REQUIRE_PTR(cols);
     GRT_REQUIRE_PTR(fluxes_dev);
-    GRT_TRY(pipeline_run(p, cols, NULL, 0, 0, fluxes_dev, GRT_FLUXES_PER_COLUMN, NULL));
+    GRT_TRY(pipeline_run(p, cols, NULL, NULL, 0, 0, fluxes_dev, GRT_FLUXES_PER_COLUMN, NULL));
     return GRTCODE_SUCCESS;
 }
 
@@ -1190,7 +1401,7 @@ EXTERN int grt_pipeline_run_profiles(GrtPipeline_t *p, GrtColumns_t const *cols,
     }
     int const V = p->num_levels;
     /* [c][2 V] rows of band bi -> level_fluxes_dev[c][2 bi + {0, 1}][V], then the level fluxes' heating rates and six rows */
-    GRT_TRY(pipeline_run(p, cols, NULL, 0, 1, level_fluxes_dev, GRT_PROFILE_ROWS_PER_COLUMN*V, NULL));
+    GRT_TRY(pipeline_run(p, cols, NULL, NULL, 0, 1, level_fluxes_dev, GRT_PROFILE_ROWS_PER_COLUMN*V, NULL));
     int const bands = (p->band[0].gas != NULL) | (p->band[1].gas != NULL) << 1;
     GRT_TRY(grt_dev_check(grt_launch_profile_finish(grt_dev_stream(p->device), cols->ncol, 1, V, bands, p->user_level,
                                                     GRT_GRAVITY, GRT_SPECIFIC_HEAT_AIR, p->small_d + p->off_p,
@@ -1229,7 +1440,7 @@ EXTERN int grt_pipeline_run_allsky(GrtPipeline_t *p, GrtColumns_t const *cols, G
     GRT_REQUIRE_PTR(cols);
     GRT_REQUIRE_PTR(fluxes_dev);
     GRT_TRY(check_clouds(p, cols, cl));
-    GRT_TRY(pipeline_run(p, cols, cl, 0, 0, fluxes_dev, GRT_ALLSKY_FLUXES_PER_COLUMN, NULL));
+    GRT_TRY(pipeline_run(p, cols, cl, NULL, 0, 0, fluxes_dev, GRT_ALLSKY_FLUXES_PER_COLUMN, NULL));
     return GRTCODE_SUCCESS;
 }
 
@@ -1251,7 +1462,7 @@ EXTERN int grt_pipeline_run_allsky_profiles(GrtPipeline_t *p, GrtColumns_t const
     int const V = p->num_levels;
     /* clear-sky [c][2 V] rows of band bi -> level_fluxes_dev[c][2 bi + {0, 1}][V], all-sky -> [c][4 + 2 bi + {0, 1}][V];
        then both sets' heating rates and six rows */
-    GRT_TRY(pipeline_run(p, cols, cl, 0, 1, level_fluxes_dev, GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN*V, NULL));
+    GRT_TRY(pipeline_run(p, cols, cl, NULL, 0, 1, level_fluxes_dev, GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN*V, NULL));
     int const bands = (p->band[0].gas != NULL) | (p->band[1].gas != NULL) << 1;
     GRT_TRY(grt_dev_check(grt_launch_profile_finish(grt_dev_stream(p->device), cols->ncol, 2, V, bands, p->user_level,
                                                     GRT_GRAVITY, GRT_SPECIFIC_HEAT_AIR, p->small_d + p->off_p,
@@ -1280,12 +1491,87 @@ EXTERN int grt_pipeline_run_subcolumns(GrtPipeline_t *p, GrtColumns_t const *col
     if (level_fluxes_dev == NULL)
     {
         /* grt_pipeline_run_allsky's layout and shortwave sweep rule */
-        GRT_TRY(pipeline_run(p, cols, cl, num_subcolumns, 0, fluxes_dev, GRT_ALLSKY_FLUXES_PER_COLUMN, NULL));
+        GRT_TRY(pipeline_run(p, cols, cl, NULL, num_subcolumns, 0, fluxes_dev, GRT_ALLSKY_FLUXES_PER_COLUMN, NULL));
         return GRTCODE_SUCCESS;
     }
     /* grt_pipeline_run_allsky_profiles' layouts; the heating rates and six rows of the mean level fluxes */
     int const V = p->num_levels;
-    GRT_TRY(pipeline_run(p, cols, cl, num_subcolumns, 1, level_fluxes_dev, GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN*V, NULL));
+    GRT_TRY(pipeline_run(p, cols, cl, NULL, num_subcolumns, 1, level_fluxes_dev, GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN*V, NULL));
+    int const bands = (p->band[0].gas != NULL) | (p->band[1].gas != NULL) << 1;
+    GRT_TRY(grt_dev_check(grt_launch_profile_finish(grt_dev_stream(p->device), cols->ncol, 2, V, bands, p->user_level,
+                                                    GRT_GRAVITY, GRT_SPECIFIC_HEAT_AIR, p->small_d + p->off_p,
+                                                    level_fluxes_dev, heating_dev, fluxes_dev), "heating rate kernel"));
+    return GRTCODE_SUCCESS;
+}
+
+/* one band's aerosol inputs: none, or at least two strictly increasing grid points and the optics */
+static int check_aerosol_band(char const *name, int na, fp_t const *grid, fp_t const *optics)
+{
+    if (na < 0 || na == 1)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s aerosol grid points: 0 (no aerosol) or at least 2.", na, name);
+    }
+    if (na == 0)
+    {
+        return GRTCODE_SUCCESS;
+    }
+    if (grid == NULL || optics == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s aerosol grid points with a NULL grid or NULL optics.", na, name);
+    }
+    for (int j = 0; j + 1 < na; ++j)
+    {
+        if (!(grid[j + 1] > grid[j]))
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "%s aerosol grid not strictly increasing (grid[%d] = %e, grid[%d] = %e).", name, j,
+                     grid[j], j + 1, grid[j + 1]);
+        }
+    }
+    return GRTCODE_SUCCESS;
+}
+
+EXTERN int grt_pipeline_run_aerosols(GrtPipeline_t *p, GrtColumns_t const *cols, GrtAerosols_t const *ae,
+                                     fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    if (ae == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "no aerosol inputs (GrtAerosols_t is NULL).%s", "");
+    }
+    if (level_fluxes_dev == NULL && fluxes_dev == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "level_fluxes_dev and fluxes_dev are both NULL: nothing to write.%s", "");
+    }
+    if (level_fluxes_dev != NULL && p->num_levels < 2)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "heating rates need at least 2 levels (%d).", p->num_levels);
+    }
+    /* (a band the pipeline does not have ignores its aerosol fields) */
+    GrtAerosols_t a = *ae;
+    if (p->band[0].gas == NULL)
+    {
+        a.lw_num_points = 0;
+    }
+    if (p->band[1].gas == NULL)
+    {
+        a.sw_num_points = 0;
+    }
+    GRT_TRY(check_aerosol_band("longwave", a.lw_num_points, a.lw_grid, a.lw_optics));
+    GRT_TRY(check_aerosol_band("shortwave", a.sw_num_points, a.sw_grid, a.sw_optics));
+    if (cols->ncol < 1 || cols->ncol > p->max_cols)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d columns asked for, this pipeline was created for 1 to %d.", cols->ncol, p->max_cols);
+    }
+    if (level_fluxes_dev == NULL)
+    {
+        /* grt_pipeline_run_allsky's layout (the aerosol set where the all-sky set is) and shortwave sweep rule */
+        GRT_TRY(pipeline_run(p, cols, NULL, &a, 0, 0, fluxes_dev, GRT_ALLSKY_FLUXES_PER_COLUMN, NULL));
+        return GRTCODE_SUCCESS;
+    }
+    /* grt_pipeline_run_allsky_profiles' layouts; both sets' heating rates and six rows */
+    int const V = p->num_levels;
+    GRT_TRY(pipeline_run(p, cols, NULL, &a, 0, 1, level_fluxes_dev, GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN*V, NULL));
     int const bands = (p->band[0].gas != NULL) | (p->band[1].gas != NULL) << 1;
     GRT_TRY(grt_dev_check(grt_launch_profile_finish(grt_dev_stream(p->device), cols->ncol, 2, V, bands, p->user_level,
                                                     GRT_GRAVITY, GRT_SPECIFIC_HEAT_AIR, p->small_d + p->off_p,
@@ -1360,7 +1646,7 @@ EXTERN int grt_pipeline_run_spectral(GrtPipeline_t *p, GrtColumns_t const *cols,
     so.edges[1] = sw_edges;
     so.num_bins[0] = lw_num_bins;
     so.num_bins[1] = sw_num_bins;
-    GRT_TRY(pipeline_run(p, cols, cl, 0, 0, fluxes_dev, cl != NULL ? GRT_ALLSKY_FLUXES_PER_COLUMN : GRT_FLUXES_PER_COLUMN,
+    GRT_TRY(pipeline_run(p, cols, cl, NULL, 0, 0, fluxes_dev, cl != NULL ? GRT_ALLSKY_FLUXES_PER_COLUMN : GRT_FLUXES_PER_COLUMN,
                          &so));
     return GRTCODE_SUCCESS;
 }

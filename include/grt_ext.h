@@ -272,6 +272,50 @@ EXTERN int grt_pipeline_run_subcolumns(GrtPipeline_t *pipeline, GrtColumns_t con
                                        GrtClouds_t const *clouds, int num_subcolumns,
                                        fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev);
 
+/* ---- clear-sky fluxes with aerosols ------------------------------------------------------------------------------
+ * driver.c:426-472: the clear-clean pass of grt_pipeline_run (gas and Rayleigh), then the same solvers on
+ * add_optics({gas, Rayleigh, aerosol}), both on ONE gas-optics launch per band -- what aerosol direct forcing (the
+ * difference of the two sets) needs.  The aerosol comes per band, layer and property (optical depth of the layer,
+ * single-scattering albedo, asymmetry) on a coarse wavenumber grid of NA points shared by the columns, and is put on the
+ * spectral grid as interpolate_to_grid(..., linear_sample, NULL) does (utilities.c:149-222, :235-246): a grid point w in
+ * the interval x[j] < w <= x[j+1] takes m w + b, m = (y[j+1] - y[j])/(x[j+1] - x[j]), b = y[j] - m x[j].  A point with
+ * w <= x[0] or w > x[NA-1] has NO aerosol here (tau = omega = g = 0; the reference leaves whatever its buffers held).
+ * Then the sums of optics.c:138-145 over gas (omega = g = 0), Rayleigh (omega = 1, g = 0) and the aerosol, in that order,
+ * and the solver with the clear-clean pass's surface inputs and user level.  num_points == 0: that band's aerosol set is
+ * its clear-clean set, bit for bit, and its grid and optics are not read.  All arrays are HOST memory, read during the
+ * call. */
+typedef struct GrtAerosols
+{
+    int lw_num_points, sw_num_points;   /* NA of each band's aerosol grid; 0: no aerosol in that band */
+    fp_t const *lw_grid, *sw_grid;      /* [NA] cm-1, strictly increasing, shared by the columns */
+    fp_t const *lw_optics, *sw_optics;  /* [ncol][3][L][NA]: optical depth of the layer, albedo, asymmetry */
+} GrtAerosols_t;
+
+/* Two forms, in grt_pipeline_run_subcolumns' manner, the aerosol set where the all-sky set is there:
+ *   level_fluxes_dev == NULL (six rows): fluxes_dev [ncol][GRT_ALLSKY_FLUXES_PER_COLUMN] (required) -- values 0-11 exactly
+ *                    what grt_pipeline_run writes, values 12-23 the aerosol set in the same order; grt_pipeline_run's
+ *                    shortwave sweep rule;
+ *   level_fluxes_dev != NULL (profiles): grt_pipeline_run_allsky_profiles' layouts -- level_fluxes_dev
+ *                    [ncol][GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN][V], heating_dev [ncol][GRT_ALLSKY_HEATING_ROWS_PER_COLUMN][V-1]
+ *                    and fluxes_dev [ncol][GRT_ALLSKY_FLUXES_PER_COLUMN] (both may be NULL) -- the clear-clean set as
+ *                    grt_pipeline_run_profiles writes it, then the aerosol set; the shortwave always takes two sweeps.
+ * All DEVICE memory; asynchronous on the pipeline's lane.  The production form (keep_spectra = 0) forms the aerosol
+ * object inside the aerosol instances of the fused solvers (profile tags 12 and 13): the host turns each column's
+ * [3][L][NA] into slope and intercept tables [3][NA-1][2][L] once (the divisions), a grid point reads its interval once
+ * and each layer does six loads and three multiply-adds; nothing spectral is stored.  keep_spectra = 1: driver.c's
+ * sequence literally -- the aerosol spread into [ncol][L][n] arrays, add_optics' kernel over the three objects, the
+ * spectral solvers, the row-wise trapezoid; afterwards grt_pipeline_views shows the aerosol pass's tau, omega, g and
+ * fluxes.  Allocated at the first call that needs them: the table staging (max_columns x 6 x L x (NA - 1) doubles per
+ * band, host and device) and one int per grid point and band (rebuilt when a band's aerosol grid changes; the call then
+ * waits for the lane); partial sums and the park block are those of the other entry points.  In the deterministic mode
+ * the clear-clean set is, bit for bit, grt_pipeline_run's / grt_pipeline_run_profiles'; an aerosol of zeros gives the
+ * clear-clean set in the aerosol rows, bit for bit, in every mode.  GRTCODE_VALUE_ERR, with nothing launched and the
+ * outputs untouched, for: aerosols NULL; num_points of 1 or negative; a NULL grid or optics with num_points >= 2; a grid
+ * that is not strictly increasing; level_fluxes_dev and fluxes_dev both NULL; fewer than 2 levels in the profile form;
+ * ncol outside 1 .. max_columns.  A band whose gas-optics object is NULL ignores its aerosol fields and gives zero rows. */
+EXTERN int grt_pipeline_run_aerosols(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtAerosols_t const *aerosols,
+                                     fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev);
+
 /* ---- spectral and band-integrated fluxes ---------------------------------------------------------------------------
  * driver.c's output without -integrated (output_fluxes, driver.c:285-356): the six rows of grt_pipeline_run at EVERY grid
  * point, and -- where the caller gives bin edges -- the same rows integrated over wavenumber bins, for a batch of columns,
@@ -343,7 +387,8 @@ EXTERN int grt_multi_max(GrtMulti_t *multi, double *value);    /* barrier + maxi
  * grt_pipeline_run_allsky and grt_pipeline_run_allsky_profiles (their clear-sky pass counts under 3 / 4), 10 = the
  * wavenumber-bin kernel of grt_pipeline_run_spectral (both of its launches; its solvers count under 3 / 4 and 8 / 9),
  * 11 = the subcolumn-mean kernel of grt_pipeline_run_subcolumns (with S > 1; its all-sky solvers count under 8 / 9, each
- * band's launches together).
+ * band's launches together), 12 / 13 = LW / SW solver of the aerosol pass of grt_pipeline_run_aerosols (its clear-clean
+ * pass counts under 3 / 4).
  * Read after grt_pipeline_sync(). */
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
