@@ -19,7 +19,7 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 SO = os.path.join(LIB, "libgrtcode_hip.so")
 
 HOST_SRC = ["grt_error.c", "grt_util.c", "grt_grid.c", "grt_device.c", "grt_optics.c", "grt_tips.c",
-            "grt_hitran.c", "grt_line_store.c", "grt_gas_optics.c", "grt_gas_launch.c", "grt_solvers.c", "grt_pipeline.c", "grt_multi.c", "grt_clouds.c"]
+            "grt_hitran.c", "grt_line_store.c", "grt_gas_optics.c", "grt_gas_launch.c", "grt_solvers.c", "grt_pipeline.c", "grt_pipeline_inputs.c", "grt_pipeline_solve.c", "grt_multi.c", "grt_clouds.c"]
 NOT_IN_SO = {"grt_clouds"}      # libclouds.a only: a maintainer links the reference's own libclouds.a in its place
 HIP_SRC = ["k_gas_optics.hip", "k_gas_optics_mp.hip", "k_gas_optics_far.hip", "k_gas_optics_sweep.hip", "k_optics.hip", "k_longwave.hip", "k_shortwave.hip"]
 
@@ -30,7 +30,7 @@ ARCHIVES = {
     "liblongwave.a": ["k_longwave"],
     "libshortwave.a": ["k_shortwave"],
     # solvers' host entry points and the batched pipeline reference both bands
-    "libgrtcode_hip_ext.a": ["grt_solvers", "grt_pipeline", "grt_multi"],
+    "libgrtcode_hip_ext.a": ["grt_solvers", "grt_pipeline", "grt_pipeline_inputs", "grt_pipeline_solve", "grt_multi"],
     # the reference's cloud-optics archive name: entry points only (SURVEY §8 f-4 is not built), so that
     # framework/src/driver.c links unchanged
     "libclouds.a": ["grt_clouds"],
@@ -84,7 +84,7 @@ def build(force=False, verbose=False):
     force = force or _flags_changed()
     headers = [os.path.join(ROOT, "include", h) for h in ("grtcode_hip_api.h", "grt_ext.h")]
     headers += [os.path.join(CSRC, "grt_kernels.h"), os.path.join(CSRC, "hip", "gas_optics_dev.h"), os.path.join(CSRC, "hip", "gas_optics_mp_dev.h"), os.path.join(CSRC, "hip", "mp_general_block.inc"), os.path.join(CSRC, "hip", "mp_lean_block.inc"),
-                os.path.join(CSRC, "hip", "optics_dev.h"), os.path.join(CSRC, "hip", "exp_pair.h"), os.path.join(CSRC, "host", "grt_internal.h"), os.path.join(CSRC, "host", "grt_molecule_table.h")]
+                os.path.join(CSRC, "hip", "optics_dev.h"), os.path.join(CSRC, "hip", "exp_pair.h"), os.path.join(CSRC, "host", "grt_internal.h"), os.path.join(CSRC, "host", "grt_pipeline_internal.h"), os.path.join(CSRC, "host", "grt_molecule_table.h")]
     objs, jobs = [], []
     for f in HOST_SRC:
         src, obj = os.path.join(CSRC, "host", f), os.path.join(OBJ, f[:-2] + ".o")

@@ -310,10 +310,16 @@ typedef struct GrtSwArgs
        doubles through the same expressions: identical fluxes) */
     double *layer_props;
 } GrtSwArgs;
-/* whether the fused form takes its one sweep (the rule above; sw_kernel keeps its own copy) */
+/* whether the fused form takes its one sweep (the rule above; sw_kernel keeps its own copy); whether a fused form takes
+   the two sweeps and needs `park`; the dynamic LDS of a profile form, 2 V doubles per wave of its workgroup */
 static inline int grt_sw_one_sweep(GrtSwArgs const *a)
 {
     return a->one_sweep && (a->user_level < 0 || a->user_level == 0 || a->user_level == a->num_levels - 1);
+}
+static inline int grt_sw_parks(int profile, GrtSwArgs const *a) { return profile || !grt_sw_one_sweep(a); }
+static inline size_t grt_profile_lds(int profile, int num_levels, int block_threads)
+{
+    return profile ? sizeof(double)*2*(size_t)num_levels*(size_t)(block_threads/64) : 0;
 }
 
 /* Profile form of the fused solvers (GRT_SOLVER_PROFILE, grt_pipeline_run_profiles): the fused form's arguments, but every
@@ -345,8 +351,28 @@ typedef struct GrtCloudArgs
     double const *liquid, *ice;
 } GrtCloudArgs;
 
+/* Aerosol form of the fused solvers (GRT_SOLVER_AEROSOL, GRT_SOLVER_AEROSOL_PROFILE; grt_pipeline_run_aerosols): the
+   fused or the profile form's arguments, and per layer the aerosol object formed in registers and combined with gas and
+   Rayleigh by aerosol_combine (optics_dev.h).  The aerosol's tau, omega, g are given per layer on a coarse wavenumber grid
+   of NA points and put on the spectral grid by the reference's linear_sample (utilities.c:235-246): the host turns each
+   interval's two points into a slope and an intercept once, and a grid point evaluates slope w + intercept.
+   interval: DEVICE [nw], the interval j of each grid point (x[j] < w <= x[j+1]), -1 for a point outside the aerosol grid
+   (no aerosol there); tables: DEVICE [ncol][3][num_intervals][2][L] (tau, omega, g; slope then intercept): a thread's walk
+   over the layers is contiguous, and the lanes of a wave that share an interval read the same addresses. */
+typedef struct GrtAerosolArgs
+{
+    int num_intervals;              /* NA - 1 >= 1 */
+    int const *interval;
+    double const *tables;
+} GrtAerosolArgs;
+static inline int grt_aerosol_args_ok(GrtAerosolArgs const *c)
+{
+    return c != NULL && c->num_intervals >= 1 && c->interval != NULL && c->tables != NULL;
+}
+
 /* The kernel instances of each solver.  grt_launch_lw / grt_launch_sw launch the form they are given, after checking the
-   fields that form reads (hipErrorInvalidValue otherwise); `clouds` is read by the two all-sky forms only. */
+   fields that form reads (hipErrorInvalidValue otherwise); `clouds` is read by the all-sky forms only, `aerosols` by the
+   two aerosol forms. */
 typedef enum GrtSolverForm
 {
     GRT_SOLVER_CHAINS,      /* spectral: one thread per wavenumber and column through all the layers */
@@ -357,7 +383,7 @@ typedef enum GrtSolverForm
     GRT_SOLVER_ALLSKY_PROFILE,  /* fused all-sky, every level's up and down flux */
     GRT_SOLVER_SPECTRAL,    /* fused clear-sky, six output rows, and the six rows at every point */
     GRT_SOLVER_ALLSKY_SPECTRAL, /* fused all-sky, six output rows, and the six rows at every point */
-    GRT_SOLVER_AEROSOL,     /* fused clear sky with aerosols, six output rows (grt_launch_lw_aerosols / _sw_aerosols) */
+    GRT_SOLVER_AEROSOL,     /* fused clear sky with aerosols, six output rows */
     GRT_SOLVER_AEROSOL_PROFILE  /* fused clear sky with aerosols, every level's up and down flux */
 } GrtSolverForm;
 /* what a form is: fused (the kernel integrates), profile (every level's fluxes), all-sky (clouds), spectral (a fused
@@ -381,30 +407,11 @@ static inline int grt_cloud_args_ok(GrtCloudArgs const *c)
     return c != NULL && c->num_bands >= 1 && c->band_liquid != NULL && c->band_ice != NULL && c->thickness != NULL &&
            c->liquid != NULL && c->ice != NULL;
 }
-int grt_launch_lw(void *stream, GrtSolverForm form, GrtLwArgs const *a, GrtCloudArgs const *clouds);
-int grt_launch_sw(void *stream, GrtSolverForm form, GrtSwArgs const *a, GrtCloudArgs const *clouds);
+int grt_launch_lw(void *stream, GrtSolverForm form, GrtLwArgs const *a, GrtCloudArgs const *clouds,
+                  GrtAerosolArgs const *aerosols);
+int grt_launch_sw(void *stream, GrtSolverForm form, GrtSwArgs const *a, GrtCloudArgs const *clouds,
+                  GrtAerosolArgs const *aerosols);
 
-/* Aerosol form of the fused solvers (GRT_SOLVER_AEROSOL, GRT_SOLVER_AEROSOL_PROFILE; grt_pipeline_run_aerosols): the
-   fused or the profile form's arguments, and per layer the aerosol object formed in registers and combined with gas and
-   Rayleigh by aerosol_combine (optics_dev.h).  The aerosol's tau, omega, g are given per layer on a coarse wavenumber grid
-   of NA points and put on the spectral grid by the reference's linear_sample (utilities.c:235-246): the host turns each
-   interval's two points into a slope and an intercept once, and a grid point evaluates slope w + intercept.
-   interval: DEVICE [nw], the interval j of each grid point (x[j] < w <= x[j+1]), -1 for a point outside the aerosol grid
-   (no aerosol there); tables: DEVICE [ncol][3][num_intervals][2][L] (tau, omega, g; slope then intercept): a thread's walk
-   over the layers is contiguous, and the lanes of a wave that share an interval read the same addresses. */
-typedef struct GrtAerosolArgs
-{
-    int num_intervals;              /* NA - 1 >= 1 */
-    int const *interval;
-    double const *tables;
-} GrtAerosolArgs;
-static inline int grt_aerosol_args_ok(GrtAerosolArgs const *c)
-{
-    return c != NULL && c->num_intervals >= 1 && c->interval != NULL && c->tables != NULL;
-}
-/* form: GRT_SOLVER_AEROSOL or GRT_SOLVER_AEROSOL_PROFILE (hipErrorInvalidValue otherwise) */
-int grt_launch_lw_aerosols(void *stream, GrtSolverForm form, GrtLwArgs const *a, GrtAerosolArgs const *aerosols);
-int grt_launch_sw_aerosols(void *stream, GrtSolverForm form, GrtSwArgs const *a, GrtAerosolArgs const *aerosols);
 /* Materialised form: the aerosol object of the same tables spread onto the grid, [ncol][L][nw] each (zero where a point
    has no interval). */
 int grt_launch_spread_aerosols(void *stream, int num_layers, int ncol, double w0, double dw, uint64_t nw,

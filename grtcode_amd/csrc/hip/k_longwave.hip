@@ -272,17 +272,19 @@ extern "C" unsigned grt_solver_blocks(uint64_t nw)
     return (unsigned)((nw + kSolverBlock - 1)/kSolverBlock);
 }
 
-extern "C" int grt_launch_lw(void *stream, GrtSolverForm form, GrtLwArgs const *a, GrtCloudArgs const *c)
+extern "C" int grt_launch_lw(void *stream, GrtSolverForm form, GrtLwArgs const *a, GrtCloudArgs const *c,
+                             GrtAerosolArgs const *ae)
 {
     GrtFormKind const k = grt_form_kind(form);
-    size_t const lds = k.profile ? sizeof(double)*2*(size_t)a->num_levels*(kSolverBlock/64) : 0;
+    size_t const lds = grt_profile_lds(k.profile, a->num_levels, kSolverBlock);
     uint64_t const cells = (uint64_t)(a->num_levels - 1)*a->nw;
     if (a->ncol < 1 || a->nw < 2 ||
         (k.fused ? (a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr)
                  : (a->flux_up == nullptr || a->flux_down == nullptr)) ||
         (k.spectral && (a->flux_up == nullptr || a->flux_down == nullptr)) ||
         (form == GRT_SOLVER_LAYERS && (a->layer_terms == nullptr || cells > 0xffffffffull*kTermsBlock)) ||
-        (k.profile && (a->num_levels < 2 || lds > 65536)) || (k.allsky && !grt_cloud_args_ok(c)))
+        ((k.profile || k.aerosol) && (a->num_levels < 2 || lds > 65536)) || (k.allsky && !grt_cloud_args_ok(c)) ||
+        (k.aerosol && !grt_aerosol_args_ok(ae)))
     {
         return (int)hipErrorInvalidValue;
     }
@@ -317,6 +319,12 @@ extern "C" int grt_launch_lw(void *stream, GrtSolverForm form, GrtLwArgs const *
     case GRT_SOLVER_ALLSKY_SPECTRAL:
         hipLaunchKernelGGL((lw_kernel<true, false, true, true, GrtCloudArgs>), grid, dim3(kSolverBlock), 0, s, *a, *c);
         break;
+    case GRT_SOLVER_AEROSOL:
+        hipLaunchKernelGGL((lw_kernel<true, false, false, false, GrtAerosolArgs>), grid, dim3(kSolverBlock), 0, s, *a, *ae);
+        break;
+    case GRT_SOLVER_AEROSOL_PROFILE:
+        hipLaunchKernelGGL((lw_kernel<true, true, false, false, GrtAerosolArgs>), grid, dim3(kSolverBlock), lds, s, *a, *ae);
+        break;
     default:
         return (int)hipErrorInvalidValue;
     }
@@ -325,7 +333,7 @@ extern "C" int grt_launch_lw(void *stream, GrtSolverForm form, GrtLwArgs const *
 
 extern "C" int grt_launch_lw_subcolumns(void *stream, int profile, GrtLwArgs const *a, GrtSubcolumnArgs const *sc)
 {
-    size_t const lds = profile ? sizeof(double)*2*(size_t)a->num_levels*(kSolverBlock/64) : 0;
+    size_t const lds = grt_profile_lds(profile, a->num_levels, kSolverBlock);
     if (!grt_subcolumn_args_ok(a->ncol, a->num_levels, a->nw, a->tau_gas, a->n_layer, a->partials, sc) || lds > 65536)
     {
         return (int)hipErrorInvalidValue;
@@ -341,28 +349,6 @@ extern "C" int grt_launch_lw_subcolumns(void *stream, int profile, GrtLwArgs con
     {
         hipLaunchKernelGGL((lw_kernel<true, false, true, false, GrtSubcolumnArgs>), grid, dim3(kSolverBlock), 0, s, *a,
                            *sc);
-    }
-    return (int)hipGetLastError();
-}
-
-extern "C" int grt_launch_lw_aerosols(void *stream, GrtSolverForm form, GrtLwArgs const *a, GrtAerosolArgs const *ae)
-{
-    bool const profile = form == GRT_SOLVER_AEROSOL_PROFILE;
-    size_t const lds = profile ? sizeof(double)*2*(size_t)a->num_levels*(kSolverBlock/64) : 0;
-    if ((form != GRT_SOLVER_AEROSOL && !profile) || a->ncol < 1 || a->nw < 2 || a->num_levels < 2 || a->tau_gas == nullptr ||
-        a->n_layer == nullptr || a->partials == nullptr || lds > 65536 || !grt_aerosol_args_ok(ae))
-    {
-        return (int)hipErrorInvalidValue;
-    }
-    hipStream_t const s = (hipStream_t)stream;
-    dim3 const grid(grt_solver_blocks(a->nw), a->ncol, 1);
-    if (profile)
-    {
-        hipLaunchKernelGGL((lw_kernel<true, true, false, false, GrtAerosolArgs>), grid, dim3(kSolverBlock), lds, s, *a, *ae);
-    }
-    else
-    {
-        hipLaunchKernelGGL((lw_kernel<true, false, false, false, GrtAerosolArgs>), grid, dim3(kSolverBlock), 0, s, *a, *ae);
     }
     return (int)hipGetLastError();
 }

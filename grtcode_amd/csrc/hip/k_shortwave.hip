@@ -525,11 +525,12 @@ __global__ __launch_bounds__(kSweepBlock) void sw_sweeps_kernel(GrtSwArgs a)
 
 } // namespace
 
-extern "C" int grt_launch_sw(void *stream, GrtSolverForm form, GrtSwArgs const *a, GrtCloudArgs const *c)
+extern "C" int grt_launch_sw(void *stream, GrtSolverForm form, GrtSwArgs const *a, GrtCloudArgs const *c,
+                             GrtAerosolArgs const *ae)
 {
     GrtFormKind const k = grt_form_kind(form);
-    bool const park = k.profile || (k.fused && !grt_sw_one_sweep(a));
-    size_t const lds = k.profile ? sizeof(double)*2*(size_t)a->num_levels*(kSolverBlock/64) : 0;
+    bool const park = k.fused && grt_sw_parks(k.profile, a);
+    size_t const lds = grt_profile_lds(k.profile, a->num_levels, kSolverBlock);
     uint64_t const cells = (uint64_t)(a->num_levels - 1)*a->nw;
     if (a->ncol < 1 || a->nw < 2 ||
         (k.fused ? (a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr || (park && a->park == nullptr))
@@ -537,7 +538,8 @@ extern "C" int grt_launch_sw(void *stream, GrtSolverForm form, GrtSwArgs const *
         (k.spectral && (a->flux_up == nullptr || a->flux_down == nullptr)) ||
         (form == GRT_SOLVER_LAYERS && (a->layer_props == nullptr || cells > 0xffffffffull*kPropsBlock ||
                                        a->omega == nullptr || a->g == nullptr)) ||
-        (k.profile && (a->num_levels < 2 || lds > 65536)) || (k.allsky && !grt_cloud_args_ok(c)))
+        ((k.profile || k.aerosol) && (a->num_levels < 2 || lds > 65536)) || (k.allsky && !grt_cloud_args_ok(c)) ||
+        (k.aerosol && !grt_aerosol_args_ok(ae)))
     {
         return (int)hipErrorInvalidValue;
     }
@@ -572,6 +574,12 @@ extern "C" int grt_launch_sw(void *stream, GrtSolverForm form, GrtSwArgs const *
     case GRT_SOLVER_ALLSKY_SPECTRAL:
         hipLaunchKernelGGL((sw_kernel<true, false, true, true, GrtCloudArgs>), grid, dim3(kSolverBlock), 0, s, *a, *c);
         break;
+    case GRT_SOLVER_AEROSOL:
+        hipLaunchKernelGGL((sw_kernel<true, false, false, false, GrtAerosolArgs>), grid, dim3(kSolverBlock), 0, s, *a, *ae);
+        break;
+    case GRT_SOLVER_AEROSOL_PROFILE:
+        hipLaunchKernelGGL((sw_kernel<true, true, false, false, GrtAerosolArgs>), grid, dim3(kSolverBlock), lds, s, *a, *ae);
+        break;
     default:
         return (int)hipErrorInvalidValue;
     }
@@ -580,8 +588,8 @@ extern "C" int grt_launch_sw(void *stream, GrtSolverForm form, GrtSwArgs const *
 
 extern "C" int grt_launch_sw_subcolumns(void *stream, int profile, GrtSwArgs const *a, GrtSubcolumnArgs const *sc)
 {
-    size_t const lds = profile ? sizeof(double)*2*(size_t)a->num_levels*(kSolverBlock/64) : 0;
-    bool const park = profile || !grt_sw_one_sweep(a);
+    size_t const lds = grt_profile_lds(profile, a->num_levels, kSolverBlock);
+    bool const park = grt_sw_parks(profile, a);
     if (!grt_subcolumn_args_ok(a->ncol, a->num_levels, a->nw, a->tau_gas, a->n_layer, a->partials, sc) || lds > 65536 ||
         (park && a->park == nullptr))
     {
@@ -598,29 +606,6 @@ extern "C" int grt_launch_sw_subcolumns(void *stream, int profile, GrtSwArgs con
     {
         hipLaunchKernelGGL((sw_kernel<true, false, true, false, GrtSubcolumnArgs>), grid, dim3(kSolverBlock), 0, s, *a,
                            *sc);
-    }
-    return (int)hipGetLastError();
-}
-
-extern "C" int grt_launch_sw_aerosols(void *stream, GrtSolverForm form, GrtSwArgs const *a, GrtAerosolArgs const *ae)
-{
-    bool const profile = form == GRT_SOLVER_AEROSOL_PROFILE;
-    size_t const lds = profile ? sizeof(double)*2*(size_t)a->num_levels*(kSolverBlock/64) : 0;
-    bool const park = form == GRT_SOLVER_AEROSOL_PROFILE || !grt_sw_one_sweep(a);
-    if ((form != GRT_SOLVER_AEROSOL && !profile) || a->ncol < 1 || a->nw < 2 || a->num_levels < 2 || a->tau_gas == nullptr ||
-        a->n_layer == nullptr || a->partials == nullptr || lds > 65536 || !grt_aerosol_args_ok(ae) || (park && a->park == nullptr))
-    {
-        return (int)hipErrorInvalidValue;
-    }
-    hipStream_t const s = (hipStream_t)stream;
-    dim3 const grid(grt_solver_blocks(a->nw), a->ncol, 1);
-    if (profile)
-    {
-        hipLaunchKernelGGL((sw_kernel<true, true, false, false, GrtAerosolArgs>), grid, dim3(kSolverBlock), lds, s, *a, *ae);
-    }
-    else
-    {
-        hipLaunchKernelGGL((sw_kernel<true, false, false, false, GrtAerosolArgs>), grid, dim3(kSolverBlock), 0, s, *a, *ae);
     }
     return (int)hipGetLastError();
 }

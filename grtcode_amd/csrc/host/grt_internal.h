@@ -175,10 +175,12 @@ unsigned long grt_tips_generation(void);   /* bumped by grt_tips_load / grt_tips
 int grt_load_table_on_grid(char const *path, int expect_cols, SpectralGrid_t const *grid,
                            fp_t *out /* host [n], zero-filled then interpolated */);
 
-/* grt_pipeline.c: the host staging of grt_pipeline_run_aerosols' inputs (pure host code; GrtAerosolArgs in grt_kernels.h
-   has the layouts): each grid point's interval of the aerosol grid x [na], and the slope and intercept tables
-   [ncol][3][na - 1][2][L] of optics [ncol][3][L][na] */
+/* grt_pipeline_inputs.c: the host staging of grt_pipeline_run_aerosols' inputs (pure host code; GrtAerosolArgs in
+   grt_kernels.h has the layouts): each grid point's interval of the aerosol grid x [na], and the slope and intercept tables
+   [ncol][3][na - 1][2][L] of optics [ncol][3][L][na]; and of grt_pipeline_run_allsky's: the band (of the first nb of a
+   parametrisation's `own` bands with limits lo, hi) each of the n ascending points w takes, -1: none */
 void grt_aerosol_interval_map(double w0, double dw, uint64_t n, double const *x, int na, int *interval);
 void grt_aerosol_tables(double const *x, int na, int ncol, int num_layers, double const *optics, double *tables);
+void grt_cloud_band_map(double const *lo, double const *hi, int own, int nb, double const *w, int n, int *idx);
 
 #endif

@@ -1,0 +1,342 @@
+/* grt_pipeline_inputs.c -- what turns a caller's clouds, aerosols and bin edges into device arguments of the batched
+ * pipeline: the per-batch tables staged through pinned memory, and the per-point maps that depend only on band limits,
+ * an aerosol grid or bin edges and are rebuilt when those change. */
+#include <stdlib.h>
+#include <string.h>
+#include "grt_pipeline_internal.h"
+
+/* The pinned buffer is reused every call: wait until the previous batch's copy of it has left -- not for its kernels, so
+   that this batch is prepared on the host while that one runs.  A buffer of fewer than `need` doubles is replaced by one
+   of `want` (sized for max_columns at this call's shape: a later batch of the same shape reuses it). */
+int grt_staging_reserve(GrtPipeline_t *p, GrtStaging *st, size_t need, size_t want)
+{
+    GRT_TRY(grt_dev_event_wait(p->device, st->uploaded));
+    if (need > st->doubles)
+    {
+        GRT_TRY(grt_dev_sync(p->device, grt_dev_stream(p->device)));
+        grt_dev_free(p->device, st->d);
+        grt_host_free_pinned(st->h);
+        st->d = NULL;
+        st->h = NULL;
+        st->doubles = 0;
+        GRT_TRY(grt_host_alloc_pinned((void **)&st->h, sizeof(double)*want));
+        GRT_TRY(grt_dev_alloc(p->device, (void **)&st->d, sizeof(double)*want));
+        st->doubles = want;
+    }
+    return GRTCODE_SUCCESS;
+}
+
+/* the first `need` doubles to the device on the library stream */
+int grt_staging_upload(GrtPipeline_t *p, GrtStaging *st, size_t need)
+{
+    void *s = grt_dev_stream(p->device);
+    GRT_TRY(grt_dev_upload(p->device, st->d, st->h, sizeof(double)*need, s));
+    GRT_TRY(grt_dev_event_record(p->device, &st->uploaded, s));
+    return GRTCODE_SUCCESS;
+}
+
+void grt_staging_free(GrtPipeline_t *p, GrtStaging *st)
+{
+    grt_dev_free(p->device, st->d);
+    grt_host_free_pinned(st->h);
+    grt_dev_event_destroy(p->device, &st->uploaded);
+}
+
+/* t->table for `key`: as it is when it was built for the same bytes, else `ints` ints written by fill(ctx, .) on the host
+   and uploaded.  The stored key is dropped before the device table is touched and set again only when the whole call
+   succeeded, so a failure half way leaves a table that the next call rebuilds, whatever its key. */
+static int grt_keyed_table(GrtPipeline_t *p, GrtKeyedTable *t, void const *key, size_t key_bytes, size_t ints,
+                           GrtTableFill fill, void *ctx)
+{
+    if (t->key != NULL && t->key_bytes == key_bytes && memcmp(t->key, key, key_bytes) == 0)
+    {
+        return GRTCODE_SUCCESS;
+    }
+    void *new_key = malloc(key_bytes);
+    int *host = malloc(sizeof(int)*ints);
+    if (new_key == NULL || host == NULL)
+    {
+        free(new_key);
+        free(host);
+        GRT_FAIL(GRTCODE_NULL_ERR, "out of host memory for a table of %zu ints.", ints);
+    }
+    int rc = fill(ctx, host);
+    if (rc == GRTCODE_SUCCESS)
+    {
+        memcpy(new_key, key, key_bytes);
+        free(t->key);
+        t->key = NULL;
+        void *s = grt_dev_stream(p->device);
+        /* (the last batch's kernels may still read the old table; then host is freed: wait both times) */
+        rc = grt_dev_sync(p->device, s);
+        if (rc == GRTCODE_SUCCESS)
+        {
+            /* (its size may depend on the key: grt_bin_table_ints) */
+            grt_dev_free(p->device, t->table);
+            t->table = NULL;
+            rc = grt_dev_alloc(p->device, (void **)&t->table, sizeof(int)*ints);
+        }
+        if (rc == GRTCODE_SUCCESS) rc = grt_dev_upload(p->device, t->table, host, sizeof(int)*ints, s);
+        if (rc == GRTCODE_SUCCESS) rc = grt_dev_sync(p->device, s);
+    }
+    free(host);
+    if (rc != GRTCODE_SUCCESS)
+    {
+        free(new_key);
+        GRT_TRY(rc);
+    }
+    t->key = new_key;
+    t->key_bytes = key_bytes;
+    return GRTCODE_SUCCESS;
+}
+
+void grt_keyed_table_free(GrtPipeline_t *p, GrtKeyedTable *t)
+{
+    grt_dev_free(p->device, t->table);
+    free(t->key);
+}
+
+/* how many of the ascending w [n] are < target (or_equal: <= target): the first index whose value is >= target (n if
+   none); or_equal, one more than the last index whose value is <= target */
+static int count_below(double const *w, int n, double target, int or_equal)
+{
+    int lo = 0, hi = n;
+    while (lo < hi)
+    {
+        int const mid = (lo + hi)/2;
+        if (w[mid] < target || (or_equal && w[mid] == target)) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+/* The band each point of w [n] ends up with when bands 0 .. nb - 1 of a parametrisation of `own` bands are written in
+   order, as optics_utils.c:118-169 writes them: [first >= lo, last <= hi), band 0 extended down, band own - 1 up. */
+void grt_cloud_band_map(double const *lo, double const *hi, int own, int nb, double const *w, int n, int *idx)
+{
+    for (int j = 0; j < n; ++j)
+    {
+        idx[j] = -1;
+    }
+    for (int b = 0; b < nb; ++b)
+    {
+        int const from = count_below(w, n, lo[b], 0);
+        int const upto = count_below(w, n, hi[b], 1) - 1;
+        if (b == 0)
+        {
+            for (int j = 0; j < from; ++j) idx[j] = 0;
+        }
+        for (int j = from; j < upto; ++j) idx[j] = b;
+        if (b == own - 1)
+        {
+            for (int j = upto < 0 ? 0 : upto; j < n; ++j) idx[j] = b;
+        }
+    }
+}
+
+typedef struct CloudMapFill { GrtClouds_t const *cl; SpectralGrid_t const *grid; } CloudMapFill;
+
+static int fill_cloud_map(void *ctx, int *idx)
+{
+    CloudMapFill const *f = ctx;
+    SpectralGrid_t const *grid = f->grid;
+    int const n = (int)grid->n, B = f->cl->num_liquid_bands;
+    double *w = malloc(sizeof(double)*grid->n);
+    if (w == NULL)
+    {
+        GRT_FAIL(GRTCODE_NULL_ERR, "out of host memory for the band limits of %d grid points.", n);
+    }
+    /* what driver.c:476-488 passes to cloud_optics as the grid's "wavenumbers": band limits, not centres */
+    for (uint64_t j = 1; j < grid->n; ++j)
+    {
+        w[j] = 0.5*((grid->w0 + (j - 1)*grid->dw) + (grid->w0 + j*grid->dw));
+    }
+    w[0] = grid->w0 - grid->dw;
+    if (w[0] < 0.)
+    {
+        w[0] = 0;
+    }
+    grt_cloud_band_map(f->cl->liquid_band_lo, f->cl->liquid_band_hi, B, B, w, n, idx);
+    grt_cloud_band_map(f->cl->ice_band_lo, f->cl->ice_band_hi, f->cl->num_ice_bands, B, w, n, idx + n);
+    free(w);
+    return GRTCODE_SUCCESS;
+}
+
+/* the band's cloud arguments for a batch of C columns of S subcolumns staged by grt_stage_clouds: its per-point cloud
+   bands for these band limits are built on the host when the limits differ from the last call's */
+int grt_band_clouds(GrtPipeline_t *p, GrtBand *b, int bi, GrtClouds_t const *cl, int C, int S, GrtCloudArgs *ca)
+{
+    int const B = cl->num_liquid_bands, NI = cl->num_ice_bands;
+    size_t const L = (size_t)p->num_levels - 1, set = (size_t)S*(size_t)C*3*(size_t)B*L;
+    ca->num_bands = B;
+    ca->thickness = p->cloud.d;
+    ca->liquid = p->cloud.d + (size_t)C*L + (size_t)(2*bi)*set;
+    ca->ice = ca->liquid + set;
+    size_t const nkey = 2 + 2*(size_t)B + 2*(size_t)NI;
+    double *key = malloc(sizeof(double)*nkey);
+    if (key == NULL)
+    {
+        GRT_FAIL(GRTCODE_NULL_ERR, "out of host memory for %zu band limits.", nkey);
+    }
+    key[0] = B; key[1] = NI;
+    memcpy(key + 2, cl->liquid_band_lo, sizeof(double)*B);
+    memcpy(key + 2 + B, cl->liquid_band_hi, sizeof(double)*B);
+    memcpy(key + 2 + 2*B, cl->ice_band_lo, sizeof(double)*NI);
+    memcpy(key + 2 + 2*B + NI, cl->ice_band_hi, sizeof(double)*NI);
+    CloudMapFill f = {cl, &b->gas->grid};
+    int const rc = grt_keyed_table(p, &b->cloud_map, key, sizeof(double)*nkey, 2*(size_t)b->n, fill_cloud_map, &f);
+    free(key);
+    GRT_TRY(rc);
+    ca->band_liquid = b->cloud_map.table;
+    ca->band_ice = b->cloud_map.table + b->n;
+    return GRTCODE_SUCCESS;
+}
+
+/* the band tables of the batch to the device: [C][L] thickness, then the four sets, each [S][C][3][B][L] -- the caller's
+   [C][S][3][B][L] subcolumn-major, so that subcolumn s of every column is one [C][3][B][L] block (S = 1: as given) */
+int grt_stage_clouds(GrtPipeline_t *p, GrtClouds_t const *cl, int C, int S)
+{
+    size_t const L = (size_t)p->num_levels - 1, B = (size_t)cl->num_liquid_bands, tab = 3*B*L;
+    size_t const set = (size_t)S*(size_t)C*tab, need = (size_t)C*L + 4*set;
+    GRT_TRY(grt_staging_reserve(p, &p->cloud, need, (size_t)p->max_cols*L*(1 + 12*B*(size_t)S)));
+    double *h = p->cloud.h;
+    memcpy(h, cl->thickness, sizeof(double)*(size_t)C*L);
+    h += (size_t)C*L;
+    fp_t const *sets[4] = {cl->lw_liquid, cl->lw_ice, cl->sw_liquid, cl->sw_ice};
+    for (int k = 0; k < 4; ++k)
+    {
+        if (sets[k] != NULL)
+        {
+            for (size_t s = 0; s < (size_t)S; ++s)
+            {
+                for (size_t c = 0; c < (size_t)C; ++c)
+                {
+                    memcpy(h + k*set + (s*(size_t)C + c)*tab, sets[k] + (c*(size_t)S + s)*tab, sizeof(double)*tab);
+                }
+            }
+        }
+        else
+        {
+            memset(h + k*set, 0, sizeof(double)*set);
+        }
+    }
+    GRT_TRY(grt_staging_upload(p, &p->cloud, need));
+    return GRTCODE_SUCCESS;
+}
+
+/* The interval of the aerosol grid x [na] (strictly increasing) each of the n points w0 + i dw lies in, as
+   interpolate2 (utilities.c:149-222) assigns them: j with x[j] < w <= x[j+1]; -1 for w <= x[0] and for w > x[na-1],
+   which the reference does not write. */
+void grt_aerosol_interval_map(double w0, double dw, uint64_t n, double const *x, int na, int *interval)
+{
+    for (uint64_t i = 0; i < n; ++i)
+    {
+        double const w = w0 + i*dw;
+        interval[i] = (w <= x[0] || w > x[na - 1]) ? -1 : count_below(x, na, w, 0) - 1;
+    }
+}
+
+/* linear_sample's (utilities.c:235-246) slope and intercept of every interval, layer and property of ncol columns:
+   optics [ncol][3][L][na] -> tables [ncol][3][na - 1][2][L] (GrtAerosolArgs) */
+void grt_aerosol_tables(double const *x, int na, int ncol, int num_layers, double const *optics, double *tables)
+{
+    size_t const L = (size_t)num_layers, NA = (size_t)na, NI = NA - 1;
+    for (size_t cp = 0; cp < (size_t)ncol*3; ++cp)
+    {
+        for (size_t l = 0; l < L; ++l)
+        {
+            double const *y = optics + (cp*L + l)*NA;
+            for (size_t j = 0; j < NI; ++j)
+            {
+                double const m = (y[j + 1] - y[j])/(x[j + 1] - x[j]);
+                double const b = y[j] - m*x[j];
+                tables[((cp*NI + j)*2 + 0)*L + l] = m;
+                tables[((cp*NI + j)*2 + 1)*L + l] = b;
+            }
+        }
+    }
+}
+
+/* the batch's slope and intercept tables to the device: the longwave's [C][3][NA - 1][2][L], then the shortwave's (a band
+   the pipeline does not have, or one given no aerosol, takes no room) */
+int grt_stage_aerosols(GrtPipeline_t *p, GrtAerosols_t const *ae, int C)
+{
+    size_t const L = (size_t)p->num_levels - 1;
+    size_t per[2], need = 0, want = 0;
+    for (int bi = 0; bi < 2; ++bi)
+    {
+        int const na = p->band[bi].gas != NULL ? grt_aerosol_points(ae, bi) : 0;
+        per[bi] = na > 0 ? 6*L*((size_t)na - 1) : 0;
+        need += (size_t)C*per[bi];
+        want += (size_t)p->max_cols*per[bi];
+    }
+    if (need == 0)
+    {
+        return GRTCODE_SUCCESS;
+    }
+    GRT_TRY(grt_staging_reserve(p, &p->aer, need, want));
+    if (per[0] > 0)
+    {
+        grt_aerosol_tables(ae->lw_grid, ae->lw_num_points, C, (int)L, ae->lw_optics, p->aer.h);
+    }
+    if (per[1] > 0)
+    {
+        grt_aerosol_tables(ae->sw_grid, ae->sw_num_points, C, (int)L, ae->sw_optics, p->aer.h + (size_t)C*per[0]);
+    }
+    GRT_TRY(grt_staging_upload(p, &p->aer, need));
+    return GRTCODE_SUCCESS;
+}
+
+typedef struct AerosolMapFill { SpectralGrid_t const *grid; double const *x; int na; } AerosolMapFill;
+
+static int fill_aerosol_map(void *ctx, int *interval)
+{
+    AerosolMapFill const *f = ctx;
+    grt_aerosol_interval_map(f->grid->w0, f->grid->dw, f->grid->n, f->x, f->na, interval);
+    return GRTCODE_SUCCESS;
+}
+
+/* the band's aerosol arguments for a batch of C columns staged by grt_stage_aerosols: its per-point intervals are built on
+   the host when the band's aerosol grid differs from the last call's */
+int grt_band_aerosols(GrtPipeline_t *p, GrtBand *b, int bi, GrtAerosols_t const *ae, int C, GrtAerosolArgs *aa)
+{
+    int const na = grt_aerosol_points(ae, bi);
+    size_t const L = (size_t)p->num_levels - 1;
+    int const na_lw = p->band[0].gas != NULL ? ae->lw_num_points : 0;
+    aa->num_intervals = na - 1;
+    aa->tables = p->aer.d + (bi == 1 && na_lw > 0 ? (size_t)C*6*L*((size_t)na_lw - 1) : 0);
+    AerosolMapFill f = {&b->gas->grid, bi == 0 ? ae->lw_grid : ae->sw_grid, na};
+    GRT_TRY(grt_keyed_table(p, &b->aer_map, f.x, sizeof(double)*(size_t)na, b->n, fill_aerosol_map, &f));
+    aa->interval = b->aer_map.table;
+    return GRTCODE_SUCCESS;
+}
+
+typedef struct BinTableFill { int const *edges; int nbins; uint64_t n; size_t per_row; } BinTableFill;
+
+static int fill_bin_table(void *ctx, int *table)
+{
+    BinTableFill *f = ctx;
+    f->per_row = grt_bin_table(f->edges, f->nbins, f->n, table);
+    return GRTCODE_SUCCESS;
+}
+
+/* the band's bin table for these edges (built and uploaded when they differ from the last call's) and room for the partial
+   sums of max_cols x 6 rows */
+int grt_band_bins(GrtPipeline_t *p, GrtBand *b, int const *edges, int nbins)
+{
+    BinTableFill f = {edges, nbins, b->n, b->bin_per_row};
+    GRT_TRY(grt_keyed_table(p, &b->bin_table, edges, sizeof(int)*((size_t)nbins + 1), grt_bin_table_ints(nbins, b->n),
+                            fill_bin_table, &f));
+    b->bin_per_row = f.per_row;
+    if (b->bin_per_row > b->bin_cap)
+    {
+        GRT_TRY(grt_dev_sync(p->device, grt_dev_stream(p->device)));
+        grt_dev_free(p->device, b->bin_partials);
+        b->bin_partials = NULL;
+        b->bin_cap = 0;
+        void *pt = NULL;
+        GRT_TRY(grt_dev_alloc(p->device, &pt, sizeof(double)*(size_t)p->max_cols*6*b->bin_per_row));
+        b->bin_partials = pt;
+        b->bin_cap = b->bin_per_row;
+    }
+    return GRTCODE_SUCCESS;
+}

@@ -1,0 +1,142 @@
+/* grt_pipeline_internal.h -- what the three files of the batched pipeline share: the object (grt_pipeline.c), what turns a
+ * caller's clouds, aerosols and bin edges into device arguments (grt_pipeline_inputs.c), and the solves of one band
+ * (grt_pipeline_solve.c).  Nothing here is exported from the shared library. */
+#ifndef GRT_PIPELINE_INTERNAL_H_
+#define GRT_PIPELINE_INTERNAL_H_
+
+#include "grt_internal.h"
+
+/* A device table of ints that depends only on a few host inputs (its key): rebuilt when a call's key differs from the
+   one it was built for (grt_keyed_table). */
+typedef struct GrtKeyedTable
+{
+    int *table;            /* device */
+    void *key;             /* host: the bytes the table was built from; NULL: the table holds nothing that can be relied on */
+    size_t key_bytes;
+} GrtKeyedTable;
+/* writes the host table for the key at hand from the caller's ctx */
+typedef int (*GrtTableFill)(void *ctx, int *table);
+
+/* Per-batch inputs: a pinned host buffer, refilled every call, and its device copy. */
+typedef struct GrtStaging
+{
+    double *h, *d;
+    size_t doubles;        /* capacity of each */
+    void *uploaded;        /* event: h has been copied out and may be refilled */
+} GrtStaging;
+
+typedef struct GrtBand
+{
+    GasOptics_t *gas;
+    uint64_t n;            /* grid points */
+    double *tau_gas;       /* [cols][L][n] */
+    int tau_gas_lacks_tables;      /* the last run left the spectral tables' part to the solver (grt_pipeline_views completes it) */
+    int last_cols;
+    double *tau, *omega, *g;
+    double *flux_up, *flux_down;   /* [cols][V][n] */
+    double **rows_d;       /* [cols][6] device row pointers for the trapezoid */
+    double *zero_row;      /* [n] zeros: stands in for the user level when there is none */
+    /* fused form (no spectra kept): */
+    double *park;          /* shortwave: [cols][2 V + 5 L][n] first-sweep reflectances and layer properties */
+    double *partials;      /* [cols][6][nblocks] trapezoid partial sums */
+    unsigned nblocks;
+    /* grt_pipeline_run_profiles (and _allsky_profiles: both passes in turn), allocated at the first call: */
+    double *level_partials;        /* fused form: [cols][2 V][nblocks] */
+    double **level_rows_d;         /* materialised form: [cols][2 V] device row pointers (up levels, then down levels) */
+    /* grt_pipeline_run_allsky (and _allsky_profiles): [2][n] cloud band of each grid point (liquid, ice), -1: none; its key:
+       the band limits (B, num_ice_bands, liquid lo/hi, ice lo/hi) */
+    GrtKeyedTable cloud_map;
+    /* grt_pipeline_run_aerosols: [n] interval of the band's aerosol grid each grid point lies in, -1: none; its key: that
+       grid */
+    GrtKeyedTable aer_map;
+    /* materialised form of the all-sky and the aerosol pass (they run in stream order, never in one call): Rayleigh
+       [3][L][n], zeros [L][n], then the spread objects' tau, omega, g [spread_arrays][max_cols][L][n] (liquid and ice: 6,
+       aerosol: 3), grown when a pass needs more arrays */
+    double *spread_block;
+    int spread_arrays;
+    /* grt_pipeline_run_spectral's bins: grt_bin_table of the edges [bin_count + 1] (its key) */
+    GrtKeyedTable bin_table;
+    size_t bin_per_row;    /* partial sums per row */
+    double *bin_partials;  /* [max_cols][6][bin_cap] */
+    size_t bin_cap;
+    /* grt_pipeline_run_subcolumns, allocated at the first call that needs them (or more of them): */
+    double *sub_partials;  /* fused form: [max_cols][S][6 or 2 V][nblocks] partial sums of the all-sky pass */
+    size_t sub_cap;        /* its doubles */
+    double *flux_sum;      /* materialised form: [2][max_cols][V][n] sums of the subcolumns' up and down fluxes */
+} GrtBand;
+
+struct GrtPipeline
+{
+    Device_t device;
+    int lane;              /* the lane selected when the pipeline was created: grt_pipeline_stream names THAT stream */
+    int max_cols, num_levels, user_level;
+    int keep_spectra;      /* 0: fused solvers, integrated fluxes only (production); 1: tau/omega/g and fluxes materialised */
+    GrtBand band[2];       /* 0: longwave, 1: shortwave */
+    GrtStaging small;      /* the small per-column inputs, at the offsets below */
+    size_t off_n, off_tl, off_tv, off_ts, off_mu, off_tsi, off_p, small_doubles;
+    double *emis_d, *albedo_d, *solar_d;
+    /* grt_pipeline_run_allsky's band tables: [cols][L] thickness, then [cols][3][B][L] of the longwave liquid, longwave ice,
+       shortwave liquid, shortwave ice */
+    GrtStaging cloud;
+    /* grt_pipeline_run_aerosols' slope and intercept tables: the longwave's [cols][3][NA - 1][2][L], then the shortwave's */
+    GrtStaging aer;
+};
+
+/* grt_pipeline_run_spectral's outputs: the spectral rows and bins of `sets` sets per column */
+typedef struct SpectralOut
+{
+    double *spectral, *binned;
+    int sets;
+    int const *edges[2];
+    int num_bins[2];
+} SpectralOut;
+
+/* One solve of a band on the run's tau_gas.  What joins gas and Rayleigh: nothing (clear sky), the cloud objects (all-sky
+   pass) or the aerosol object (aerosol pass; aer NULL there: a band that was given no aerosol, which runs the clear-sky
+   form under the aerosol pass's profile tags).  Which rows leave: the six of driver.c:272-280 or (profile) every level's
+   up then down flux, to set `set` of the column's out_stride doubles at out; with so, the six rows at every point and
+   their bins too (grt_pipeline_run_spectral). */
+typedef struct GrtPass
+{
+    GrtCloudArgs const *clouds;
+    GrtAerosolArgs const *aer;
+    int aer_pass;
+    int profile;
+    int defer;                     /* the solver adds the spectral tables' part of tau, from continua (band_gas_optics) */
+    GrtContinua const *continua;
+    double *out;
+    int out_stride;
+    int set;                       /* 0: the clear-sky set; 1: the all-sky or aerosol set that follows it */
+    SpectralOut const *so;
+} GrtPass;
+
+/* the doubles from a column's clear-sky set to its all-sky or aerosol set */
+static inline int grt_set_offset(GrtPipeline_t const *p, int profile)
+{
+    return profile ? GRT_PROFILE_ROWS_PER_COLUMN*p->num_levels : GRT_FLUXES_PER_COLUMN;
+}
+
+static inline int grt_aerosol_points(GrtAerosols_t const *ae, int bi)
+{
+    return bi == 0 ? ae->lw_num_points : ae->sw_num_points;
+}
+
+/* grt_pipeline.c: the row-pointer table rows_h [n] (integrate_rows' rows) to the device at *rows_d; rows_h is freed */
+GRT_PRIVATE int grt_upload_rows(GrtPipeline_t *p, double **rows_h, size_t n, double ***rows_d);
+
+/* grt_pipeline_inputs.c */
+GRT_PRIVATE int grt_staging_reserve(GrtPipeline_t *p, GrtStaging *st, size_t need, size_t want);
+GRT_PRIVATE int grt_staging_upload(GrtPipeline_t *p, GrtStaging *st, size_t need);
+GRT_PRIVATE void grt_staging_free(GrtPipeline_t *p, GrtStaging *st);
+GRT_PRIVATE void grt_keyed_table_free(GrtPipeline_t *p, GrtKeyedTable *t);
+GRT_PRIVATE int grt_stage_clouds(GrtPipeline_t *p, GrtClouds_t const *cl, int C, int S);
+GRT_PRIVATE int grt_band_clouds(GrtPipeline_t *p, GrtBand *b, int bi, GrtClouds_t const *cl, int C, int S, GrtCloudArgs *ca);
+GRT_PRIVATE int grt_stage_aerosols(GrtPipeline_t *p, GrtAerosols_t const *ae, int C);
+GRT_PRIVATE int grt_band_aerosols(GrtPipeline_t *p, GrtBand *b, int bi, GrtAerosols_t const *ae, int C, GrtAerosolArgs *aa);
+GRT_PRIVATE int grt_band_bins(GrtPipeline_t *p, GrtBand *b, int const *edges, int nbins);
+
+/* grt_pipeline_solve.c */
+GRT_PRIVATE int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps);
+GRT_PRIVATE int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S, GrtPass const *ps);
+
+#endif

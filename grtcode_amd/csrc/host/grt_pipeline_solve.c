@@ -1,0 +1,450 @@
+/* grt_pipeline_solve.c -- the solves of one band of the batched pipeline on the run's tau_gas, each described by a GrtPass:
+ * the solver launch, the materialised optics that precede it when spectra are kept, and what turns its partial sums or
+ * spectral fluxes into the rows the caller asked for. */
+#include <stdlib.h>
+#include <string.h>
+#include "grt_pipeline_internal.h"
+
+/* the profile tag its solver is timed under: 3 / 4, or 8 / 9 with clouds, or 12 / 13 in the aerosol pass */
+static int pass_tag(GrtPass const *ps, int bi)
+{
+    return (ps->aer_pass ? 12 : (ps->clouds ? 8 : 3)) + bi;
+}
+
+/* its solver form (materialised: the spectral form, after pass_optics) */
+static GrtSolverForm pass_form(GrtPipeline_t const *p, GrtPass const *ps)
+{
+    if (p->keep_spectra) return GRT_SOLVER_CHAINS;
+    if (ps->so != NULL) return ps->clouds ? GRT_SOLVER_ALLSKY_SPECTRAL : GRT_SOLVER_SPECTRAL;
+    if (ps->aer != NULL) return ps->profile ? GRT_SOLVER_AEROSOL_PROFILE : GRT_SOLVER_AEROSOL;
+    if (ps->clouds != NULL) return ps->profile ? GRT_SOLVER_ALLSKY_PROFILE : GRT_SOLVER_ALLSKY;
+    return ps->profile ? GRT_SOLVER_PROFILE : GRT_SOLVER_FUSED;
+}
+
+/* its rows per band and column, and where band bi's start in a column's out_stride doubles */
+static int pass_rows(GrtPipeline_t const *p, GrtPass const *ps)
+{
+    return ps->profile ? 2*p->num_levels : GRT_FLUXES_PER_BAND;
+}
+
+static int pass_offset(GrtPipeline_t const *p, GrtPass const *ps, int bi)
+{
+    return ps->set*grt_set_offset(p, ps->profile) + bi*pass_rows(p, ps);
+}
+
+/* where band bi's six spectral rows (or bins, per = bins) of column 0 start in a [ncol][sets][6 per_lw + 6 per_sw]
+   block, and the doubles from one column to the next */
+static size_t spectral_offset(GrtPass const *ps, int bi, size_t per_lw, size_t per_sw, size_t *col_stride)
+{
+    size_t const set_doubles = 6*(per_lw + per_sw);
+    *col_stride = (size_t)ps->so->sets*set_doubles;
+    return (size_t)ps->set*set_doubles + (bi == 1 ? 6*per_lw : 0);
+}
+
+static size_t band_points(GrtPipeline_t const *p, int bi)
+{
+    return p->band[bi].gas != NULL ? p->band[bi].n : 0;
+}
+
+/* The solvers' arguments.  Fused forms: Rayleigh, add_optics({gas, rayleigh}) and the solver in one launch (driver.c:268,
+   382-424) on tau_gas; spectral form: the materialised tau, omega (, g) in, [level][wavenumber] fluxes out.  The caller
+   sets the partial sums and, shortwave, the park block. */
+static void lw_args(GrtPipeline_t const *p, GrtBand const *b, int C, int fused, GrtPass const *ps, GrtLwArgs *a)
+{
+    SpectralGrid_t const *grid = &b->gas->grid;
+    int const V = p->num_levels, L = V - 1;
+    memset(a, 0, sizeof(*a));
+    a->num_levels = V; a->ncol = C; a->w0 = grid->w0; a->dw = grid->dw; a->nw = b->n;
+    a->optics_stride = (uint64_t)L*b->n;
+    a->t_layers = p->small.d + p->off_tl; a->t_levels = p->small.d + p->off_tv;
+    a->t_surf = p->small.d + p->off_ts;
+    a->emis = p->emis_d; a->emis_stride = 0;
+    a->user_level = p->user_level;
+    if (fused)
+    {
+        a->tau_gas = b->tau_gas; a->n_layer = p->small.d + p->off_n;
+        a->add_continua = ps->defer;
+        if (ps->defer) a->continua = *ps->continua;
+    }
+    else
+    {
+        a->tau = b->tau; a->omega = b->omega;
+        a->flux_up = b->flux_up; a->flux_down = b->flux_down; a->flux_stride = (uint64_t)V*b->n;
+    }
+}
+
+static void sw_args(GrtPipeline_t const *p, GrtBand const *b, int C, int fused, GrtPass const *ps, GrtSwArgs *a)
+{
+    SpectralGrid_t const *grid = &b->gas->grid;
+    int const V = p->num_levels, L = V - 1;
+    memset(a, 0, sizeof(*a));
+    a->num_levels = V; a->ncol = C; a->nw = b->n; a->dw = grid->dw; a->w0 = grid->w0;
+    a->optics_stride = (uint64_t)L*b->n;
+    a->mu_dir = p->small.d + p->off_mu; a->mu_dif = 0.5;        /* driver.c:110 */
+    a->alb_dir = p->albedo_d; a->alb_dif = p->albedo_d; a->alb_stride = 0;   /* driver.c:118-119 */
+    a->tsi = p->small.d + p->off_tsi; a->solar = p->solar_d;
+    a->user_level = p->user_level;
+    if (fused)
+    {
+        a->tau_gas = b->tau_gas; a->n_layer = p->small.d + p->off_n;
+        a->add_continua = ps->defer;
+        if (ps->defer) a->continua = *ps->continua;
+        /* (read at every step, so that a test can compare the two forms in one process) */
+        char const *env = getenv("GRT_SW_TWO_SWEEPS");
+        a->one_sweep = !(env != NULL && env[0] == '1');
+    }
+    else
+    {
+        a->tau = b->tau; a->omega = b->omega; a->g = b->g;
+        a->flux_up = b->flux_up; a->flux_down = b->flux_down; a->flux_stride = (uint64_t)V*b->n;
+    }
+}
+
+/* the shortwave solver's two-sweep form: reflectances of 2 V levels and five properties of L layers per column and
+   wavenumber, allocated at the first launch that needs them */
+static int park_block(GrtPipeline_t *p, GrtBand *b)
+{
+    if (b->park == NULL)
+    {
+        size_t const V = (size_t)p->num_levels;
+        void *pk = NULL;
+        GRT_TRY(grt_dev_alloc(p->device, &pk, sizeof(double)*(size_t)p->max_cols*(2*V + 5*(V - 1))*b->n));
+        b->park = pk;
+    }
+    return GRTCODE_SUCCESS;
+}
+
+/* the band's solver in the pass's form, timed under the pass's profile tag; the profile forms share the band's park block
+   with the two-sweep six-row forms (the passes run in stream order); the spectral six-row forms store their rows where
+   the pass's so places the band's */
+static int band_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps, double *partials)
+{
+    GrtSolverForm const form = pass_form(p, ps);
+    GrtFormKind const k = grt_form_kind(form);
+    void *s = grt_dev_stream(p->device);
+    size_t stride = 0;
+    double *rows = k.spectral ? ps->so->spectral + spectral_offset(ps, bi, band_points(p, 0), band_points(p, 1), &stride)
+                              : NULL;
+    int slot, krc;
+    if (bi == 0)
+    {
+        GrtLwArgs a;
+        lw_args(p, b, C, k.fused, ps, &a);
+        a.partials = partials;
+        if (k.spectral)
+        {
+            a.flux_up = rows;
+            a.flux_down = rows + 3*b->n;
+            a.flux_stride = stride;
+        }
+        slot = grt_profile_begin(s, pass_tag(ps, bi));
+        krc = grt_launch_lw(s, form, &a, ps->clouds, ps->aer);
+    }
+    else
+    {
+        GrtSwArgs a;
+        sw_args(p, b, C, k.fused, ps, &a);
+        a.partials = partials;
+        if (k.spectral)
+        {
+            a.flux_up = rows;
+            a.flux_down = rows + 3*b->n;
+            a.flux_stride = stride;
+        }
+        if (k.fused && grt_sw_parks(k.profile, &a))
+        {
+            GRT_TRY(park_block(p, b));
+        }
+        a.park = b->park;
+        slot = grt_profile_begin(s, pass_tag(ps, bi));
+        krc = grt_launch_sw(s, form, &a, ps->clouds, ps->aer);
+    }
+    grt_profile_end(s, slot);
+    GRT_TRY(grt_dev_check(krc, bi == 0 ? "longwave kernel" : "shortwave kernel"));
+    return GRTCODE_SUCCESS;
+}
+
+/* Rayleigh + add_optics({gas, rayleigh}) (driver.c:268, 382-383) into the band's tau, omega, g */
+static int clear_sky_optics(GrtPipeline_t *p, GrtBand *b, int C)
+{
+    SpectralGrid_t const *grid = &b->gas->grid;
+    void *s = grt_dev_stream(p->device);
+    int const slot = grt_profile_begin(s, 5);
+    int const krc = grt_launch_clear_sky_optics(s, p->num_levels - 1, C, grid->w0, grid->dw, b->n, p->small.d + p->off_n,
+                                                b->tau_gas, b->tau, b->omega, b->g);
+    grt_profile_end(s, slot);
+    GRT_TRY(grt_dev_check(krc, "clear-sky optics kernel"));
+    return GRTCODE_SUCCESS;
+}
+
+/* The cloud objects (driver.c:507-530: liquid, ice) or the aerosol object (driver.c:426-434) spread onto the grid, then
+   per column Rayleigh and add_optics({gas, rayleigh, the spread objects}) -- tau, omega, g of the band are the pass's */
+static int spread_optics(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *ps)
+{
+    SpectralGrid_t const *grid = &b->gas->grid;
+    int const L = p->num_levels - 1, objects = ps->aer != NULL ? 1 : 2;
+    uint64_t const per = (uint64_t)L*b->n, all = per*(uint64_t)p->max_cols;
+    void *s = grt_dev_stream(p->device);
+    if (3*objects > b->spread_arrays)
+    {
+        /* (the other pass's kernels of an earlier call may still read the smaller block) */
+        GRT_TRY(grt_dev_sync(p->device, s));
+        grt_dev_free(p->device, b->spread_block);
+        b->spread_block = NULL;
+        b->spread_arrays = 0;
+        void *blk = NULL;
+        GRT_TRY(grt_dev_alloc(p->device, &blk, sizeof(double)*(4*per + 3*objects*all)));
+        b->spread_block = blk;
+        b->spread_arrays = 3*objects;
+        GRT_TRY(grt_dev_zero(p->device, b->spread_block + 3*per, sizeof(double)*per, s));
+    }
+    double *ray = b->spread_block, *zero = ray + 3*per, *x[6];
+    for (int k = 0; k < 3*objects; ++k)
+    {
+        x[k] = zero + per + k*all;
+    }
+    if (ps->aer != NULL)
+    {
+        GRT_TRY(grt_dev_check(grt_launch_spread_aerosols(s, L, C, grid->w0, grid->dw, b->n, ps->aer, x[0], x[1], x[2]),
+                              "aerosol spreading kernel"));
+    }
+    else
+    {
+        GRT_TRY(grt_dev_check(grt_launch_spread_clouds(s, L, C, b->n, ps->clouds, x[0], x[1], x[2], x[3], x[4], x[5]),
+                              "cloud spreading kernel"));
+    }
+    for (int c = 0; c < C; ++c)
+    {
+        /* Rayleigh of this column (rayleigh.c:29-68: its number densities travel as a kernel argument) */
+        GRT_TRY(grt_dev_check(grt_launch_rayleigh(s, L, grid->w0, grid->dw, b->n, p->small.h + p->off_n + (size_t)c*L,
+                                                  ray, ray + per, ray + 2*per), "Rayleigh kernel"));
+        GrtOpticsPtrs in;
+        memset(&in, 0, sizeof(in));
+        uint64_t const o = (uint64_t)c*per;
+        in.tau[0] = b->tau_gas + o; in.omega[0] = zero; in.g[0] = zero;
+        in.tau[1] = ray; in.omega[1] = ray + per; in.g[1] = ray + 2*per;
+        for (int k = 0; k < objects; ++k)
+        {
+            in.tau[2 + k] = x[3*k] + o; in.omega[2 + k] = x[3*k + 1] + o; in.g[2 + k] = x[3*k + 2] + o;
+        }
+        GRT_TRY(grt_dev_check(grt_launch_add_optics(s, per, 2 + objects, &in, b->tau + o, b->omega + o, b->g + o),
+                              ps->aer != NULL ? "add_optics kernel (aerosols)" : "add_optics kernel (all-sky)"));
+    }
+    return GRTCODE_SUCCESS;
+}
+
+/* the materialised optics a pass runs before its spectral solver */
+static int pass_optics(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *ps)
+{
+    GRT_TRY(ps->aer != NULL || ps->clouds != NULL ? spread_optics(p, b, C, ps) : clear_sky_optics(p, b, C));
+    return GRTCODE_SUCCESS;
+}
+
+/* the row table of every level's up and down flux, [max_cols][2 V] */
+static int level_rows(GrtPipeline_t *p, GrtBand *b)
+{
+    if (b->level_rows_d != NULL)
+    {
+        return GRTCODE_SUCCESS;
+    }
+    size_t const V = (size_t)p->num_levels, C = (size_t)p->max_cols;
+    double **rows_h = malloc(sizeof(double *)*C*2*V);
+    if (rows_h == NULL)
+    {
+        GRT_FAIL(GRTCODE_NULL_ERR, "out of host memory for the level row table of %zu columns.", C);
+    }
+    for (size_t c = 0; c < C; ++c)
+    {
+        for (size_t k = 0; k < V; ++k)
+        {
+            rows_h[(c*2 + 0)*V + k] = b->flux_up + (c*V + k)*b->n;
+            rows_h[(c*2 + 1)*V + k] = b->flux_down + (c*V + k)*b->n;
+        }
+    }
+    GRT_TRY(grt_upload_rows(p, rows_h, C*2*V, &b->level_rows_d));
+    return GRTCODE_SUCCESS;
+}
+
+/* the row-wise trapezoid of the band's spectral fluxes into the pass's rows */
+static int integrate_rows(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps)
+{
+    int const rows = pass_rows(p, ps);
+    if (ps->profile)
+    {
+        GRT_TRY(level_rows(p, b));
+    }
+    GRT_TRY(grt_dev_check(grt_launch_integrate_rows(grt_dev_stream(p->device),
+                                                    (double const *const *)(ps->profile ? b->level_rows_d : b->rows_d),
+                                                    C*rows, b->n, b->gas->grid.dw, ps->out, rows, ps->out_stride,
+                                                    pass_offset(p, ps, bi)), "spectral integration kernel"));
+    return GRTCODE_SUCCESS;
+}
+
+/* One solve of a band for grt_pipeline_run_spectral: the six rows at every point into the caller's spectral block, the
+   -integrated six into out, and the bins.  Fused form: the spectral six-row solver (its rows stored where it weights
+   them) and the fixed-order sum of its partial sums; materialised form: the spectral solver, its rows 0, L and the user
+   level copied out, the row-wise trapezoid.  The bins are summed from the stored rows by the binning kernel (profile
+   tag 10). */
+static int band_solve_spectral(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps)
+{
+    void *s = grt_dev_stream(p->device);
+    SpectralOut const *so = ps->so;
+    size_t stride;
+    double *rows = so->spectral + spectral_offset(ps, bi, band_points(p, 0), band_points(p, 1), &stride);
+    if (!p->keep_spectra)
+    {
+        GRT_TRY(band_solver(p, b, bi, C, ps, b->partials));
+        GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, b->partials, C*GRT_FLUXES_PER_BAND, b->nblocks, ps->out,
+                                                         GRT_FLUXES_PER_BAND, ps->out_stride, pass_offset(p, ps, bi)),
+                              "flux reduction kernel"));
+    }
+    else
+    {
+        GRT_TRY(pass_optics(p, b, C, ps));
+        GRT_TRY(band_solver(p, b, bi, C, ps, NULL));
+        GRT_TRY(grt_dev_check(grt_launch_copy_rows(s, (double const *const *)b->rows_d, C*GRT_FLUXES_PER_BAND, b->n,
+                                                   rows, stride), "spectral row copy kernel"));
+        GRT_TRY(integrate_rows(p, b, bi, C, ps));
+    }
+    int const nbins = so->num_bins[bi];
+    if (nbins > 0)
+    {
+        GRT_TRY(grt_band_bins(p, b, so->edges[bi], nbins));
+        size_t bstride;
+        double *binned = so->binned + spectral_offset(ps, bi, (size_t)so->num_bins[0], (size_t)so->num_bins[1], &bstride);
+        int const slot = grt_profile_begin(s, 10);
+        int const krc = grt_launch_bin_rows(s, rows, stride, C*GRT_FLUXES_PER_BAND, b->n, b->gas->grid.dw, nbins,
+                                            b->bin_table.table, b->bin_per_row, b->bin_partials, binned, bstride);
+        grt_profile_end(s, slot);
+        GRT_TRY(grt_dev_check(krc, "spectral binning kernel"));
+    }
+    return GRTCODE_SUCCESS;
+}
+
+/* One solve of a band: Rayleigh, add_optics({gas, rayleigh} and what the pass joins to them), the solver and the
+   -integrated output (driver.c:268, 382-424, 426-434, 507-530, 302-326) of the pass's rows, to
+   out[c*out_stride + its offset + r].  Fused form: all of it in one solver launch, then the fixed-order sum of its
+   per-block partial sums (profile: in level_partials, which the passes of one call take in turn); materialised form: tau,
+   omega, g and the spectral fluxes in the band's arrays, then the row-wise trapezoid. */
+int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps)
+{
+    if (ps->so != NULL)
+    {
+        GRT_TRY(band_solve_spectral(p, b, bi, C, ps));
+        return GRTCODE_SUCCESS;
+    }
+    if (p->keep_spectra)
+    {
+        GRT_TRY(pass_optics(p, b, C, ps));
+        GRT_TRY(band_solver(p, b, bi, C, ps, NULL));
+        GRT_TRY(integrate_rows(p, b, bi, C, ps));
+        return GRTCODE_SUCCESS;
+    }
+    int const rows = pass_rows(p, ps);
+    if (ps->profile && b->level_partials == NULL)
+    {
+        void *lp = NULL;
+        GRT_TRY(grt_dev_alloc(p->device, &lp, sizeof(double)*(size_t)p->max_cols*(size_t)rows*b->nblocks));
+        b->level_partials = lp;
+    }
+    double *partials = ps->profile ? b->level_partials : b->partials;
+    GRT_TRY(band_solver(p, b, bi, C, ps, partials));
+    GRT_TRY(grt_dev_check(grt_launch_reduce_partials(grt_dev_stream(p->device), partials, C*rows, b->nblocks, ps->out, rows,
+                                                     ps->out_stride, pass_offset(p, ps, bi)), "flux reduction kernel"));
+    return GRTCODE_SUCCESS;
+}
+
+/* The all-sky pass of grt_pipeline_run_subcolumns for one band, S subcolumns of every column on this run's tau_gas
+   (driver.c:503-589), its mean rows to out as grt_band_solve writes them.  ps->clouds: the band's tables staged
+   subcolumn-major.  Fused form: the subcolumn instance of the all-sky solver over C x S grid rows, each subcolumn's
+   partial sums in sub_partials, then their fixed-order mean (profile tag 11; S = 1: the fixed-order sum of
+   grt_band_solve).  The shortwave's two-sweep forms park C x count columns at a time in the band's park block, count =
+   what fits in its max_cols, in stream order.  Materialised form: per subcolumn the all-sky optics, the spectral solver
+   and the sum of its fluxes; then the mean into the band's flux arrays, and the row-wise trapezoid. */
+int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S, GrtPass const *ps)
+{
+    int const V = p->num_levels, rows = pass_rows(p, ps), out_offset = pass_offset(p, ps, bi);
+    void *s = grt_dev_stream(p->device);
+    if (!p->keep_spectra)
+    {
+        size_t const need = (size_t)p->max_cols*(size_t)S*(size_t)rows*b->nblocks;
+        if (need > b->sub_cap)
+        {
+            GRT_TRY(grt_dev_sync(p->device, s));
+            grt_dev_free(p->device, b->sub_partials);
+            b->sub_partials = NULL;
+            b->sub_cap = 0;
+            void *sp = NULL;
+            GRT_TRY(grt_dev_alloc(p->device, &sp, sizeof(double)*need));
+            b->sub_partials = sp;
+            b->sub_cap = need;
+        }
+        GrtLwArgs lw;
+        GrtSwArgs sw;
+        int group = 65535/C;                   /* (grid rows) */
+        if (bi == 0)
+        {
+            lw_args(p, b, C, 1, ps, &lw);
+            lw.partials = b->sub_partials;
+        }
+        else
+        {
+            sw_args(p, b, C, 1, ps, &sw);
+            sw.partials = b->sub_partials;
+            if (grt_sw_parks(ps->profile, &sw))
+            {
+                GRT_TRY(park_block(p, b));
+                group = p->max_cols/C;
+            }
+            sw.park = b->park;
+        }
+        group = group < S ? group : S;
+        int const slot = grt_profile_begin(s, pass_tag(ps, bi));
+        int krc = 0;
+        for (int first = 0; first < S && krc == 0; first += group)
+        {
+            GrtSubcolumnArgs const sc = {*ps->clouds, S, first, S - first < group ? S - first : group};
+            krc = bi == 0 ? grt_launch_lw_subcolumns(s, ps->profile, &lw, &sc)
+                          : grt_launch_sw_subcolumns(s, ps->profile, &sw, &sc);
+        }
+        grt_profile_end(s, slot);
+        GRT_TRY(grt_dev_check(krc, bi == 0 ? "longwave subcolumn kernel" : "shortwave subcolumn kernel"));
+        if (S == 1)
+        {
+            GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, b->sub_partials, C*rows, b->nblocks, ps->out, rows,
+                                                             ps->out_stride, out_offset), "flux reduction kernel"));
+            return GRTCODE_SUCCESS;
+        }
+        int const mslot = grt_profile_begin(s, 11);
+        int const mrc = grt_launch_subcolumn_mean(s, b->sub_partials, C, S, rows, b->nblocks, ps->out, ps->out_stride,
+                                                  out_offset);
+        grt_profile_end(s, mslot);
+        GRT_TRY(grt_dev_check(mrc, "subcolumn mean kernel"));
+        return GRTCODE_SUCCESS;
+    }
+    size_t const tab = (size_t)C*3*(size_t)ps->clouds->num_bands*(size_t)(V - 1);
+    uint64_t const per = (uint64_t)C*(uint64_t)V*b->n, all = (uint64_t)p->max_cols*(uint64_t)V*b->n;
+    if (b->flux_sum == NULL)
+    {
+        void *fs = NULL;
+        GRT_TRY(grt_dev_alloc(p->device, &fs, sizeof(double)*2*all));
+        b->flux_sum = fs;
+    }
+    for (int j = 0; j < S; ++j)
+    {
+        GrtCloudArgs cj = *ps->clouds;
+        cj.liquid += (size_t)j*tab;
+        cj.ice += (size_t)j*tab;
+        GrtPass pj = *ps;
+        pj.clouds = &cj;
+        GRT_TRY(pass_optics(p, b, C, &pj));
+        GRT_TRY(band_solver(p, b, bi, C, &pj, NULL));
+        GRT_TRY(grt_dev_check(grt_launch_flux_accumulate(s, per, b->flux_up, b->flux_sum, j == 0), "flux sum kernel"));
+        GRT_TRY(grt_dev_check(grt_launch_flux_accumulate(s, per, b->flux_down, b->flux_sum + all, j == 0),
+                              "flux sum kernel"));
+    }
+    GRT_TRY(grt_dev_check(grt_launch_flux_mean(s, per, b->flux_sum, S, b->flux_up), "flux mean kernel"));
+    GRT_TRY(grt_dev_check(grt_launch_flux_mean(s, per, b->flux_sum + all, S, b->flux_down), "flux mean kernel"));
+    GRT_TRY(integrate_rows(p, b, bi, C, ps));
+    return GRTCODE_SUCCESS;
+}

@@ -210,7 +210,7 @@ EXTERN int calculate_lw_fluxes(Longwave_t * const lw, Optics_t const * const opt
     GrtSolverForm const form = (chains != NULL && chains[0] == '1') || !block_has_scratch(lw->device, lw->layer_temperature, lw->flux_down + n*(size_t)V, sizeof(fp_t)*6*n*(size_t)(V - 1))
                                ? GRT_SOLVER_CHAINS : GRT_SOLVER_LAYERS;
     a.layer_terms = form == GRT_SOLVER_LAYERS ? lw->flux_down + n*(size_t)V : NULL;
-    GRT_TRY(grt_dev_check(grt_launch_lw(s, form, &a, NULL), "longwave kernel"));
+    GRT_TRY(grt_dev_check(grt_launch_lw(s, form, &a, NULL, NULL), "longwave kernel"));
     GRT_TRY(download_fluxes(lw->device, V, n, flux_up, flux_down, lw->flux_up, lw->flux_down, s));
     GRT_TRY(grt_dev_sync(lw->device, s));
     return GRTCODE_SUCCESS;
@@ -301,7 +301,7 @@ EXTERN int calculate_sw_fluxes(Shortwave_t * const sw, Optics_t const * const op
     GrtSolverForm const form = (chains != NULL && chains[0] == '1') || !block_has_scratch(sw->device, sw->solar_flux, sw->flux_down + n*(size_t)V, sizeof(fp_t)*5*n*(size_t)(V - 1))
                                ? GRT_SOLVER_CHAINS : GRT_SOLVER_LAYERS;
     a.layer_props = form == GRT_SOLVER_LAYERS ? sw->flux_down + n*(size_t)V : NULL;
-    GRT_TRY(grt_dev_check(grt_launch_sw(s, form, &a, NULL), "shortwave kernel"));
+    GRT_TRY(grt_dev_check(grt_launch_sw(s, form, &a, NULL, NULL), "shortwave kernel"));
     GRT_TRY(download_fluxes(sw->device, V, n, flux_up, flux_down, sw->flux_up, sw->flux_down, s));
     GRT_TRY(grt_dev_sync(sw->device, s));
     return GRTCODE_SUCCESS;

@@ -61,7 +61,7 @@ def main():
     (gcols, keep), _ = wl.columns(0, ncol)
     pipe = wl.pipe
     V = wl.num_levels
-    gclouds = subcolumn_clouds(keep["p"], keep["tl"], 1)[1][0]
+    gclouds, keep_clouds = subcolumn_clouds(keep["p"], keep["tl"], 1)[1]     # (the struct points into keep_clouds' arrays)
     gaer, keep_aer = api.make_aerosols(lw=synthetic_aerosols(wl.grid_lw, ncol, V - 1, 3, True),
                                        sw=synthetic_aerosols(wl.grid_sw, ncol, V - 1, 4, False))
     out = api.DeviceBuffer(device, 8 * ncol * api.GRT_ALLSKY_FLUXES_PER_COLUMN)
