@@ -226,6 +226,10 @@ def _dp(a):
     return a.ctypes.data_as(c_double_p)
 
 
+def _opt_dp(a):
+    return None if a is None else _dp(a)
+
+
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
@@ -467,7 +471,7 @@ def make_columns(cols, mol_order, cfc_order=(), num_levels=None):
         cia=_f64(np.stack([np.stack([c["ppmv"][22], c["ppmv"][7]]) for c in cols])),   # N2 (CIA_N2=0), O2 (CIA_O2=1)
         mu=_f64([c["mu0"] for c in cols]), tsi=_f64([c["tsi"] for c in cols]))
     gc = GrtColumns(len(cols), V, _dp(keep["p"]), _dp(keep["t"]), _dp(keep["tl"]), _dp(keep["ts"]),
-                    _dp(keep["mol"]), _dp(keep["cfc"]) if keep["cfc"] is not None else None,
+                    _dp(keep["mol"]), _opt_dp(keep["cfc"]),
                     _dp(keep["cia"]), _dp(keep["mu"]), _dp(keep["tsi"]))
     return gc, keep
 
@@ -488,10 +492,8 @@ def make_clouds(liquid_bands, ice_bands, thickness, lw_liquid, lw_ice, sw_liquid
     if len(shapes) > 1:
         raise ValueError(f"optics sets of different subcolumn counts {sorted(shapes)}")
     keep["subcolumns"] = shapes.pop() if shapes else 1
-    ptr = lambda a: _dp(a) if a is not None else None
-    gc = GrtClouds(keep["llo"].size, keep["ilo"].size, ptr(keep["llo"]), ptr(keep["lhi"]), ptr(keep["ilo"]),
-                   ptr(keep["ihi"]), ptr(keep["th"]), ptr(keep["lwl"]), ptr(keep["lwi"]), ptr(keep["swl"]),
-                   ptr(keep["swi"]))
+    gc = GrtClouds(keep["llo"].size, keep["ilo"].size,
+                   *[_opt_dp(keep[k]) for k in ("llo", "lhi", "ilo", "ihi", "th", "lwl", "lwi", "swl", "swi")])
     return gc, keep
 
 
@@ -516,9 +518,7 @@ def make_aerosols(lw=None, sw=None):
         keep["num_points"].append(grid.size)
         keep["shapes"].append(optics.shape)
     keep["num_points"], keep["shapes"] = tuple(keep["num_points"]), tuple(keep["shapes"])
-    ptr = lambda a: _dp(a) if a is not None else None
-    ga = GrtAerosols(keep["num_points"][0], keep["num_points"][1], ptr(keep["lw_grid"]), ptr(keep["sw_grid"]),
-                     ptr(keep["lw_optics"]), ptr(keep["sw_optics"]))
+    ga = GrtAerosols(*keep["num_points"], *[_opt_dp(keep[k]) for k in ("lw_grid", "sw_grid", "lw_optics", "sw_optics")])
     return ga, keep
 
 
@@ -530,25 +530,50 @@ class Pipeline:
         self.keep_spectra = spectral
         self.p = C.c_void_p()
         self.device = (lw_gas or sw_gas).device
-        e = _f64(emissivity) if emissivity is not None else None
-        a = _f64(albedo) if albedo is not None else None
-        s = _f64(solar) if solar is not None else None
+        e, a, s = (None if x is None else _f64(x) for x in (emissivity, albedo, solar))
         check(self.lib.grt_pipeline_create_ex(C.byref(self.p), C.byref(lw_gas.c) if lw_gas else None,
                                               C.byref(sw_gas.c) if sw_gas else None, max_columns, user_level,
-                                              _dp(e) if e is not None else None, _dp(a) if a is not None else None,
-                                              _dp(s) if s is not None else None, int(spectral)))
-        self.out = DeviceBuffer(self.device, 8 * GRT_FLUXES_PER_COLUMN * max_columns)
+                                              _opt_dp(e), _opt_dp(a), _opt_dp(s), int(spectral)))
         self.max_columns = max_columns
         self.num_levels = (lw_gas or sw_gas).num_levels
-        self.prof = None        # run_profiles' device outputs: allocated at its first call
-        self.allsky = None      # run_allsky's [max_columns][24]: allocated at its first call
-        self.allsky_prof = None  # run_allsky_profiles' device outputs: allocated at its first call
-        self.spec = None        # run_spectral's device outputs: allocated at its first call (and for a new bin count)
-        self.sub = None         # run_subcolumns' six-row output [max_columns][24]: allocated at its first call
-        self.sub_prof = None    # run_subcolumns(profiles=True)' device outputs: allocated at its first call
-        self.aer = None         # run_aerosols' six-row output [max_columns][24]: allocated at its first call
-        self.aer_prof = None    # run_aerosols(profiles=True)' device outputs: allocated at its first call
         self.nw = tuple(g.grid.n if g is not None else 0 for g in (lw_gas, sw_gas))
+        self.buffers = {}       # every device buffer of this object by name: each run form's at its first call
+        self.spec_shape = None  # (sets, longwave bins, shortwave bins) of the last run_spectral
+        self.out = self._buffer("run", 8 * GRT_FLUXES_PER_COLUMN * max_columns)
+
+    def _buffer(self, name, nbytes):
+        """The device buffer of that name and size: allocated when first asked for, and again when the size changes."""
+        buf = self.buffers.get(name)
+        if buf is None or buf.nbytes != nbytes:
+            if buf is not None:
+                buf.free()
+            buf = self.buffers[name] = DeviceBuffer(self.device, nbytes)
+        return buf
+
+    def _two_sets(self, name, ncol):
+        """Buffer `name`'s [ncol][24] as two sets of twelve: copies, so that they outlive the next run."""
+        self.sync()
+        f = self.buffers[name].to_host((ncol, GRT_ALLSKY_FLUXES_PER_COLUMN))
+        return f[:, :GRT_FLUXES_PER_COLUMN].copy(), f[:, GRT_FLUXES_PER_COLUMN:].copy()
+
+    def _profile_ptrs(self, name, sets):
+        """The levels, heating and fluxes pointers of run form `name`, `sets` sets per column (1 or 2)."""
+        V, n = self.num_levels, self.max_columns
+        rows = (("levels", GRT_PROFILE_ROWS_PER_COLUMN * V), ("heating", GRT_HEATING_ROWS_PER_COLUMN * (V - 1)),
+                ("fluxes", GRT_FLUXES_PER_COLUMN))
+        return [self._buffer(f"{name}.{k}", 8 * n * sets * r).ptr for k, r in rows]
+
+    def _read_profiles(self, name, sets, ncol):
+        """What _profile_ptrs(name, sets) was last written with: per set a dict of lw_up, lw_down, sw_up, sw_down
+        [ncol][V], lw_heating, sw_heating [ncol][V-1] and fluxes [ncol][12]."""
+        self.sync()
+        V = self.num_levels
+        lv = self.buffers[name + ".levels"].to_host((ncol, sets, GRT_PROFILE_ROWS_PER_COLUMN, V))
+        hr = self.buffers[name + ".heating"].to_host((ncol, sets, GRT_HEATING_ROWS_PER_COLUMN, V - 1))
+        fx = self.buffers[name + ".fluxes"].to_host((ncol, sets, GRT_FLUXES_PER_COLUMN))
+        return tuple(dict(lw_up=lv[:, s, 0].copy(), lw_down=lv[:, s, 1].copy(), sw_up=lv[:, s, 2].copy(),
+                          sw_down=lv[:, s, 3].copy(), lw_heating=hr[:, s, 0].copy(), sw_heating=hr[:, s, 1].copy(),
+                          fluxes=fx[:, s].copy()) for s in range(sets))
 
     def run(self, gcols, out_ptr=None):
         check(self.lib.grt_pipeline_run(self.p, C.byref(gcols), out_ptr if out_ptr is not None else self.out.ptr))
@@ -565,59 +590,31 @@ class Pipeline:
 
     def run_profiles(self, gcols):
         """grt_pipeline_run_profiles into this object's device buffers (profiles() reads them)."""
-        V, n = self.num_levels, self.max_columns
-        if self.prof is None:
-            self.prof = {"levels": DeviceBuffer(self.device, 8 * n * GRT_PROFILE_ROWS_PER_COLUMN * V),
-                         "heating": DeviceBuffer(self.device, 8 * n * GRT_HEATING_ROWS_PER_COLUMN * (V - 1)),
-                         "fluxes": DeviceBuffer(self.device, 8 * n * GRT_FLUXES_PER_COLUMN)}
-        check(self.lib.grt_pipeline_run_profiles(self.p, C.byref(gcols), self.prof["levels"].ptr,
-                                                 self.prof["heating"].ptr, self.prof["fluxes"].ptr))
+        check(self.lib.grt_pipeline_run_profiles(self.p, C.byref(gcols), *self._profile_ptrs("profiles", 1)))
 
     def profiles(self, ncol):
         """The last run_profiles: lw_up, lw_down, sw_up, sw_down [ncol][V] (W m-2, levels top first), lw_heating,
         sw_heating [ncol][V-1] (K day-1) and fluxes [ncol][12] (grt_pipeline_run's layout)."""
-        self.sync()
-        V = self.num_levels
-        lv = self.prof["levels"].to_host((ncol, GRT_PROFILE_ROWS_PER_COLUMN, V))
-        hr = self.prof["heating"].to_host((ncol, GRT_HEATING_ROWS_PER_COLUMN, V - 1))
-        return dict(lw_up=lv[:, 0].copy(), lw_down=lv[:, 1].copy(), sw_up=lv[:, 2].copy(), sw_down=lv[:, 3].copy(),
-                    lw_heating=hr[:, 0].copy(), sw_heating=hr[:, 1].copy(),
-                    fluxes=self.prof["fluxes"].to_host((ncol, GRT_FLUXES_PER_COLUMN)))
+        return self._read_profiles("profiles", 1, ncol)[0]
 
     def run_allsky(self, gcols, gclouds):
         """grt_pipeline_run_allsky into this object's device buffer (allsky_fluxes() reads it)."""
-        if self.allsky is None:
-            self.allsky = DeviceBuffer(self.device, 8 * GRT_ALLSKY_FLUXES_PER_COLUMN * self.max_columns)
-        check(self.lib.grt_pipeline_run_allsky(self.p, C.byref(gcols), C.byref(gclouds), self.allsky.ptr))
+        out = self._buffer("allsky", 8 * GRT_ALLSKY_FLUXES_PER_COLUMN * self.max_columns)
+        check(self.lib.grt_pipeline_run_allsky(self.p, C.byref(gcols), C.byref(gclouds), out.ptr))
 
     def allsky_fluxes(self, ncol):
         """The last run_allsky: (clear, all-sky), each [ncol][12] in grt_pipeline_run's layout."""
-        self.sync()
-        f = self.allsky.to_host((ncol, GRT_ALLSKY_FLUXES_PER_COLUMN))
-        return f[:, :GRT_FLUXES_PER_COLUMN].copy(), f[:, GRT_FLUXES_PER_COLUMN:].copy()
+        return self._two_sets("allsky", ncol)
 
     def run_allsky_profiles(self, gcols, gclouds):
         """grt_pipeline_run_allsky_profiles into this object's device buffers (allsky_profiles() reads them)."""
-        V, n = self.num_levels, self.max_columns
-        if self.allsky_prof is None:
-            self.allsky_prof = {"levels": DeviceBuffer(self.device, 8 * n * GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN * V),
-                                "heating": DeviceBuffer(self.device, 8 * n * GRT_ALLSKY_HEATING_ROWS_PER_COLUMN * (V - 1)),
-                                "fluxes": DeviceBuffer(self.device, 8 * n * GRT_ALLSKY_FLUXES_PER_COLUMN)}
         check(self.lib.grt_pipeline_run_allsky_profiles(self.p, C.byref(gcols), C.byref(gclouds),
-                                                        self.allsky_prof["levels"].ptr, self.allsky_prof["heating"].ptr,
-                                                        self.allsky_prof["fluxes"].ptr))
+                                                        *self._profile_ptrs("allsky_profiles", 2)))
 
     def allsky_profiles(self, ncol):
         """The last run_allsky_profiles: (clear, all-sky), each a dict with profiles()' keys and shapes -- lw_up, lw_down,
         sw_up, sw_down [ncol][V], lw_heating, sw_heating [ncol][V-1] and fluxes [ncol][12]."""
-        self.sync()
-        V, P, H, F = self.num_levels, GRT_PROFILE_ROWS_PER_COLUMN, GRT_HEATING_ROWS_PER_COLUMN, GRT_FLUXES_PER_COLUMN
-        lv = self.allsky_prof["levels"].to_host((ncol, 2, P, V))
-        hr = self.allsky_prof["heating"].to_host((ncol, 2, H, V - 1))
-        fx = self.allsky_prof["fluxes"].to_host((ncol, 2, F))
-        return tuple(dict(lw_up=lv[:, s, 0].copy(), lw_down=lv[:, s, 1].copy(), sw_up=lv[:, s, 2].copy(),
-                          sw_down=lv[:, s, 3].copy(), lw_heating=hr[:, s, 0].copy(), sw_heating=hr[:, s, 1].copy(),
-                          fluxes=fx[:, s].copy()) for s in range(2))
+        return self._read_profiles("allsky_profiles", 2, ncol)
 
     def run_spectral(self, gcols, gclouds=None, lw_edges=None, sw_edges=None):
         """grt_pipeline_run_spectral into this object's device buffers (spectral() reads them): the six rows at every grid
@@ -626,107 +623,67 @@ class Pipeline:
         e = [None if x is None else np.ascontiguousarray(x, dtype=np.int32) for x in (lw_edges, sw_edges)]
         nb = [0 if x is None else max(x.size - 1, 0) for x in e]
         n = self.max_columns
-        need = (sets, nb[0], nb[1])
-        if self.spec is None or self.spec["shape"] != need:
-            for k in ("spectral", "binned", "fluxes"):
-                if self.spec is not None and self.spec[k] is not None:
-                    self.spec[k].free()
-            per = 6 * (self.nw[0] + self.nw[1])
-            self.spec = {"shape": need,
-                         "spectral": DeviceBuffer(self.device, 8 * n * sets * per),
-                         "binned": DeviceBuffer(self.device, 8 * n * sets * 6 * (nb[0] + nb[1])) if nb[0] + nb[1] else None,
-                         "fluxes": DeviceBuffer(self.device, 8 * n * sets * GRT_FLUXES_PER_COLUMN)}
+        self.spec_shape = (sets, nb[0], nb[1])
+        spectral = self._buffer("spectral", 8 * n * sets * 6 * (self.nw[0] + self.nw[1]))
+        binned = self._buffer("spectral.binned", 8 * n * sets * 6 * (nb[0] + nb[1])) if nb[0] + nb[1] else None
+        fluxes = self._buffer("spectral.fluxes", 8 * n * sets * GRT_FLUXES_PER_COLUMN)
         ptr = [None if x is None else x.ctypes.data_as(C.c_void_p) for x in e]
-        binned = self.spec["binned"].ptr if self.spec["binned"] is not None else None
         check(self.lib.grt_pipeline_run_spectral(self.p, C.byref(gcols), C.byref(gclouds) if gclouds is not None else None,
-                                                 ptr[0], nb[0], ptr[1], nb[1], self.spec["spectral"].ptr, binned,
-                                                 self.spec["fluxes"].ptr))
+                                                 ptr[0], nb[0], ptr[1], nb[1], spectral.ptr,
+                                                 binned.ptr if binned is not None else None, fluxes.ptr))
 
     def spectral(self, ncol):
         """The last run_spectral: lw, sw [ncol][sets][6][n] (W m-2 per cm-1, GRT_FLUXES_PER_BAND row order), lw_bins,
         sw_bins [ncol][sets][6][num_bins] (W m-2) and fluxes [ncol][12 or 24] (grt_pipeline_run's or run_allsky's layout)."""
         self.sync()
-        sets, nb_lw, nb_sw = self.spec["shape"]
+        sets, nb_lw, nb_sw = self.spec_shape
         nl, ns = self.nw
-        sp = self.spec["spectral"].to_host((ncol, sets, 6 * (nl + ns)))
+        sp = self.buffers["spectral"].to_host((ncol, sets, 6 * (nl + ns)))
         out = {"lw": sp[:, :, :6 * nl].reshape(ncol, sets, 6, nl).copy(),
                "sw": sp[:, :, 6 * nl:].reshape(ncol, sets, 6, ns).copy()}
-        if self.spec["binned"] is not None:
-            bn = self.spec["binned"].to_host((ncol, sets, 6 * (nb_lw + nb_sw)))
+        if nb_lw + nb_sw:
+            bn = self.buffers["spectral.binned"].to_host((ncol, sets, 6 * (nb_lw + nb_sw)))
         else:
             bn = np.zeros((ncol, sets, 0))
         out["lw_bins"] = bn[:, :, :6 * nb_lw].reshape(ncol, sets, 6, nb_lw).copy()
         out["sw_bins"] = bn[:, :, 6 * nb_lw:].reshape(ncol, sets, 6, nb_sw).copy()
-        out["fluxes"] = self.spec["fluxes"].to_host((ncol, sets * GRT_FLUXES_PER_COLUMN))
+        out["fluxes"] = self.buffers["spectral.fluxes"].to_host((ncol, sets * GRT_FLUXES_PER_COLUMN))
         return out
+
+    def _six_row_or_profile_ptrs(self, name, profiles):
+        """The (levels, heating, fluxes) pointers of a two-set entry point that writes either form: the six-row form's
+        own [max_columns][24] with no levels and no heating rates, or the profile form's three buffers."""
+        if profiles:
+            return self._profile_ptrs(name + "_profiles", 2)
+        return [None, None, self._buffer(name, 8 * GRT_ALLSKY_FLUXES_PER_COLUMN * self.max_columns).ptr]
 
     def run_subcolumns(self, gcols, gclouds, S, profiles=False):
         """grt_pipeline_run_subcolumns with S subcolumns per column into this object's device buffers: the six-row form
         (subcolumn_fluxes() reads it) or, profiles=True, the profile form (subcolumn_profiles() reads it)."""
-        V, n = self.num_levels, self.max_columns
-        if not profiles:
-            if self.sub is None:
-                self.sub = DeviceBuffer(self.device, 8 * GRT_ALLSKY_FLUXES_PER_COLUMN * n)
-            check(self.lib.grt_pipeline_run_subcolumns(self.p, C.byref(gcols), C.byref(gclouds), int(S), None, None,
-                                                       self.sub.ptr))
-            return
-        if self.sub_prof is None:
-            self.sub_prof = {"levels": DeviceBuffer(self.device, 8 * n * GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN * V),
-                             "heating": DeviceBuffer(self.device, 8 * n * GRT_ALLSKY_HEATING_ROWS_PER_COLUMN * (V - 1)),
-                             "fluxes": DeviceBuffer(self.device, 8 * n * GRT_ALLSKY_FLUXES_PER_COLUMN)}
         check(self.lib.grt_pipeline_run_subcolumns(self.p, C.byref(gcols), C.byref(gclouds), int(S),
-                                                   self.sub_prof["levels"].ptr, self.sub_prof["heating"].ptr,
-                                                   self.sub_prof["fluxes"].ptr))
+                                                   *self._six_row_or_profile_ptrs("subcolumn", profiles)))
 
     def subcolumn_fluxes(self, ncol):
         """The last six-row run_subcolumns: (clear, all-sky subcolumn mean), each [ncol][12] in grt_pipeline_run's layout."""
-        self.sync()
-        f = self.sub.to_host((ncol, GRT_ALLSKY_FLUXES_PER_COLUMN))
-        return f[:, :GRT_FLUXES_PER_COLUMN].copy(), f[:, GRT_FLUXES_PER_COLUMN:].copy()
+        return self._two_sets("subcolumn", ncol)
 
     def subcolumn_profiles(self, ncol):
         """The last run_subcolumns(profiles=True): (clear, all-sky subcolumn mean), allsky_profiles()' keys and shapes."""
-        self.sync()
-        V, P, H, F = self.num_levels, GRT_PROFILE_ROWS_PER_COLUMN, GRT_HEATING_ROWS_PER_COLUMN, GRT_FLUXES_PER_COLUMN
-        lv = self.sub_prof["levels"].to_host((ncol, 2, P, V))
-        hr = self.sub_prof["heating"].to_host((ncol, 2, H, V - 1))
-        fx = self.sub_prof["fluxes"].to_host((ncol, 2, F))
-        return tuple(dict(lw_up=lv[:, s, 0].copy(), lw_down=lv[:, s, 1].copy(), sw_up=lv[:, s, 2].copy(),
-                          sw_down=lv[:, s, 3].copy(), lw_heating=hr[:, s, 0].copy(), sw_heating=hr[:, s, 1].copy(),
-                          fluxes=fx[:, s].copy()) for s in range(2))
+        return self._read_profiles("subcolumn_profiles", 2, ncol)
 
     def run_aerosols(self, gcols, gaerosols, profiles=False):
         """grt_pipeline_run_aerosols into this object's device buffers: the six-row form (aerosol_fluxes() reads it) or,
         profiles=True, the profile form (aerosol_profiles() reads it)."""
-        V, n = self.num_levels, self.max_columns
-        if not profiles:
-            if self.aer is None:
-                self.aer = DeviceBuffer(self.device, 8 * GRT_ALLSKY_FLUXES_PER_COLUMN * n)
-            check(self.lib.grt_pipeline_run_aerosols(self.p, C.byref(gcols), C.byref(gaerosols), None, None, self.aer.ptr))
-            return
-        if self.aer_prof is None:
-            self.aer_prof = {"levels": DeviceBuffer(self.device, 8 * n * GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN * V),
-                             "heating": DeviceBuffer(self.device, 8 * n * GRT_ALLSKY_HEATING_ROWS_PER_COLUMN * (V - 1)),
-                             "fluxes": DeviceBuffer(self.device, 8 * n * GRT_ALLSKY_FLUXES_PER_COLUMN)}
-        check(self.lib.grt_pipeline_run_aerosols(self.p, C.byref(gcols), C.byref(gaerosols), self.aer_prof["levels"].ptr,
-                                                 self.aer_prof["heating"].ptr, self.aer_prof["fluxes"].ptr))
+        check(self.lib.grt_pipeline_run_aerosols(self.p, C.byref(gcols), C.byref(gaerosols),
+                                                 *self._six_row_or_profile_ptrs("aerosol", profiles)))
 
     def aerosol_fluxes(self, ncol):
         """The last six-row run_aerosols: (clean, aerosol), each [ncol][12] in grt_pipeline_run's layout."""
-        self.sync()
-        f = self.aer.to_host((ncol, GRT_ALLSKY_FLUXES_PER_COLUMN))
-        return f[:, :GRT_FLUXES_PER_COLUMN].copy(), f[:, GRT_FLUXES_PER_COLUMN:].copy()
+        return self._two_sets("aerosol", ncol)
 
     def aerosol_profiles(self, ncol):
         """The last run_aerosols(profiles=True): (clean, aerosol), allsky_profiles()' keys and shapes."""
-        self.sync()
-        V, P, H, F = self.num_levels, GRT_PROFILE_ROWS_PER_COLUMN, GRT_HEATING_ROWS_PER_COLUMN, GRT_FLUXES_PER_COLUMN
-        lv = self.aer_prof["levels"].to_host((ncol, 2, P, V))
-        hr = self.aer_prof["heating"].to_host((ncol, 2, H, V - 1))
-        fx = self.aer_prof["fluxes"].to_host((ncol, 2, F))
-        return tuple(dict(lw_up=lv[:, s, 0].copy(), lw_down=lv[:, s, 1].copy(), sw_up=lv[:, s, 2].copy(),
-                          sw_down=lv[:, s, 3].copy(), lw_heating=hr[:, s, 0].copy(), sw_heating=hr[:, s, 1].copy(),
-                          fluxes=fx[:, s].copy()) for s in range(2))
+        return self._read_profiles("aerosol_profiles", 2, ncol)
 
     def views(self, band):
         ptrs = [C.c_void_p() for _ in range(6)]
@@ -737,27 +694,9 @@ class Pipeline:
         return dict(zip(("tau_gas", "tau", "omega", "g", "flux_up", "flux_down"), [p.value for p in ptrs]))
 
     def destroy(self):
-        self.out.free()
-        for buf in (list((self.prof or {}).values()) + list((self.allsky_prof or {}).values()) +
-                    list((self.sub_prof or {}).values()) + list((self.aer_prof or {}).values())):
+        for buf in self.buffers.values():
             buf.free()
-        self.aer_prof = None
-        if self.aer is not None:
-            self.aer.free()
-            self.aer = None
-        self.prof = None
-        self.allsky_prof = None
-        self.sub_prof = None
-        if self.sub is not None:
-            self.sub.free()
-            self.sub = None
-        for k in ("spectral", "binned", "fluxes"):
-            if self.spec is not None and self.spec[k] is not None:
-                self.spec[k].free()
-        self.spec = None
-        if self.allsky is not None:
-            self.allsky.free()
-            self.allsky = None
+        self.buffers = {}
         check(self.lib.grt_pipeline_destroy(C.byref(self.p)))
 
 

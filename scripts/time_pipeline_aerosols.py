@@ -1,6 +1,6 @@
 """Cost of grt_pipeline_run_aerosols against grt_pipeline_run, grt_pipeline_run_allsky and grt_pipeline_run_allsky_profiles
 on the G1 workload (grtcode_amd.workload: 64 columns, 61 levels, the bench's grids and line lists, fast = 3), with a
-synthetic aerosol on NA = 16 points per band and the synthetic clouds of scripts/time_pipeline_subcolumns.py.
+synthetic aerosol on NA = 16 points per band and the synthetic clouds of scripts/pipeline_timing.py.
 
 Five alternating repetitions of these steps on one pipeline, in one process:
   run               grt_pipeline_run
@@ -15,21 +15,10 @@ profiles/pipeline_aerosols_timing.json (or the path given).
 
     python scripts/time_pipeline_aerosols.py [--reps 5] [--out profiles/pipeline_aerosols_timing.json]
 """
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
-
-from grtcode_amd import api, workload as W  # noqa: E402
-from time_pipeline_subcolumns import subcolumn_clouds  # noqa: E402
+from pipeline_timing import Session, subcolumn_clouds  # (first: it puts the repository root on sys.path)
+from grtcode_amd import api
 
 TAGS = {"lw_clear_ms": 3, "sw_clear_ms": 4, "lw_allsky_ms": 8, "sw_allsky_ms": 9, "lw_aerosol_ms": 12, "sw_aerosol_ms": 13}
 NA = 16
@@ -50,26 +39,13 @@ def synthetic_aerosols(grid, ncol, L, seed, lw):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--columns", type=int, default=64)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pipeline_aerosols_timing.json"))
-    args = ap.parse_args()
-    device = api.create_device(0)
-    ncol = args.columns
-    wl = W.G1Workload(device, ncol, fast=3)
-    (gcols, keep), _ = wl.columns(0, ncol)
-    pipe = wl.pipe
-    V = wl.num_levels
-    gclouds, keep_clouds = subcolumn_clouds(keep["p"], keep["tl"], 1)[1]     # (the struct points into keep_clouds' arrays)
-    gaer, keep_aer = api.make_aerosols(lw=synthetic_aerosols(wl.grid_lw, ncol, V - 1, 3, True),
-                                       sw=synthetic_aerosols(wl.grid_sw, ncol, V - 1, 4, False))
-    out = api.DeviceBuffer(device, 8 * ncol * api.GRT_ALLSKY_FLUXES_PER_COLUMN)
-    levels = api.DeviceBuffer(device, 8 * ncol * api.GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN * V)
-    heating = api.DeviceBuffer(device, 8 * ncol * api.GRT_ALLSKY_HEATING_ROWS_PER_COLUMN * (V - 1))
-    prof_out = api.DeviceBuffer(device, 8 * ncol * api.GRT_ALLSKY_FLUXES_PER_COLUMN)
-    lib = api.load_library()
-    C = api.C
+    s = Session("pipeline_aerosols_timing.json")
+    pipe, gcols, lib, C, ncol, V = s.pipe, s.gcols, s.lib, api.C, s.ncol, s.V
+    gclouds, keep_clouds = subcolumn_clouds(s.keep["p"], s.keep["tl"], 1)[1]   # (the struct points into keep_clouds' arrays)
+    gaer, keep_aer = api.make_aerosols(lw=synthetic_aerosols(s.wl.grid_lw, ncol, V - 1, 3, True),
+                                       sw=synthetic_aerosols(s.wl.grid_sw, ncol, V - 1, 4, False))
+    out = s.buffer(api.GRT_ALLSKY_FLUXES_PER_COLUMN)
+    levels, heating, prof_out = s.profile_outputs(2)
 
     def step(mode):
         if mode == "run":
@@ -84,26 +60,9 @@ def main():
         else:
             api.check(lib.grt_pipeline_run_aerosols(pipe.p, C.byref(gcols), C.byref(gaer), levels.ptr, heating.ptr,
                                                     prof_out.ptr))
-        pipe.sync()
 
-    api.profile_enable(True)
     modes = ["run", "allsky", "allsky_profiles", "aerosols", "aerosol_profiles"]
-    for mode in modes:                       # warm-up: every buffer allocated, every kernel loaded
-        step(mode)
-    samples = {m: {**{k: [] for k in TAGS}, "wall_ms": []} for m in modes}
-    for rep in range(args.reps):
-        for mode in modes:
-            for tag in TAGS.values():
-                api.profile_read(tag, reset=True)
-            t0 = time.perf_counter()
-            step(mode)
-            wall = 1e3 * (time.perf_counter() - t0)
-            for k, tag in TAGS.items():
-                samples[mode][k].append(api.profile_read(tag)[0])
-            samples[mode]["wall_ms"].append(wall)
-    api.profile_enable(False)
-    median = {m: {k: statistics.median(v) for k, v in s.items()} for m, s in samples.items()}
-    spread = {m: {k: max(v) - min(v) for k, v in s.items()} for m, s in samples.items()}
+    samples, median, spread = s.measure(modes, step, TAGS)
 
     def target(new, new_key, yard, yard_key):
         got, limit = median[new][new_key], median[yard][yard_key] + spread[yard][yard_key]
@@ -116,18 +75,12 @@ def main():
               "six_row_sw_tag13_vs_tag9": target("aerosols", "sw_aerosol_ms", "allsky", "sw_allsky_ms"),
               "profile_lw_tag12_vs_tag8": target("aerosol_profiles", "lw_aerosol_ms", "allsky_profiles", "lw_allsky_ms"),
               "profile_sw_tag13_vs_tag9": target("aerosol_profiles", "sw_aerosol_ms", "allsky_profiles", "sw_allsky_ms")}
-    result = {"workload": f"G1: {ncol} columns, {V} levels, LW {wl.grid_lw.n} + SW {wl.grid_sw.n} points, fast 3; "
-                          f"synthetic aerosol on {NA} points per band, synthetic clouds in about a third of the layers",
-              "reps": args.reps, "order": ", ".join(modes) + " alternating; medians over the repetitions",
+    result = {"workload": s.workload + f"; synthetic aerosol on {NA} points per band, synthetic clouds in about a third of the "
+                                       "layers",
+              "reps": s.args.reps, "order": ", ".join(modes) + " alternating; medians over the repetitions",
               "median": median, "spread_max_minus_min": spread, "samples": samples, "targets": checks,
               "step_over_run_step": {m: median[m]["wall_ms"] / median["run"]["wall_ms"] for m in modes}}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fo:
-        json.dump(result, fo, indent=1)
-    print(json.dumps({"targets": checks, "step_over_run_step": result["step_over_run_step"]}))
-    for b in (out, levels, heating, prof_out):
-        b.free()
-    wl.destroy()
+    s.finish(result, ("targets", "step_over_run_step"))
 
 
 if __name__ == "__main__":

@@ -22,7 +22,7 @@ from grtcode_amd import api, multi, synthetic as syn
 from scenario import Band, MOL_ORDER, RUN_TO_RUN_FUSED_FLUX
 from test_gpu_circ_rfmip import circ1_column
 from test_gpu_gas_optics import tau_close
-from test_gpu_pipeline import oracle_column
+from pipeline_support import oracle_column
 
 pytestmark = pytest.mark.gpu
 FLUX_TOL = 1e-4

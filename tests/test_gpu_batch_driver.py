@@ -10,7 +10,7 @@ import pytest
 
 from grtcode_amd import api, synthetic as syn
 from scenario import Band
-from test_gpu_pipeline import oracle_column
+from pipeline_support import oracle_column
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

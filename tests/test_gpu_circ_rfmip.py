@@ -15,7 +15,7 @@ import pytest
 
 from grtcode_amd import api, synthetic as syn
 from scenario import Band, MOL_ORDER
-from test_gpu_pipeline import oracle_column
+from pipeline_support import oracle_column
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))

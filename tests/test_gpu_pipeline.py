@@ -4,35 +4,13 @@ import numpy as np
 import pytest
 
 from grtcode_amd import api, synthetic as syn
+from pipeline_support import oracle_column
+from pipeline_support import bands  # noqa: F401  (a module fixture)
 from scenario import Band, MOL_ORDER
 
 pytestmark = pytest.mark.gpu
 
 FLUX_TOL = 1e-3      # W m-2, BASELINE.json north_star tolerance on broadband fluxes
-
-
-def oracle_column(orc, lib, band, col, lw, emis=None, alb=None, solar=None, user_level=-1):
-    L = col["p"].size - 1
-    tau_gas = band.oracle_tau(orc, orc, lib, col)
-    tr, om_r, g_r = orc.rayleigh(L, col["p"], band.w0, band.dw, band.nw)
-    z = np.zeros_like(tau_gas)
-    tau, omega, g = orc.add_optics([tau_gas, tr], [z, om_r], [z, g_r])
-    if lw:
-        up, dn = orc.lw_fluxes(band.w0, band.dw, col["t_surf"], col["t_layer"], col["t"], tau, omega, emis)
-    else:
-        up, dn = orc.sw_fluxes(omega, g, tau, col["mu0"], 0.5, alb, alb, col["tsi"], solar)
-    rows = [up[0], up[-1], up[user_level] if user_level >= 0 else None,
-            dn[0], dn[-1], dn[user_level] if user_level >= 0 else None]
-    integ = [orc.integrate_row(r, band.dw) if r is not None else 0.0 for r in rows]
-    return dict(tau_gas=tau_gas, tau=tau, omega=omega, g=g, up=up, dn=dn, integ=np.array(integ))
-
-
-@pytest.fixture(scope="module")
-def bands(tmp_path_factory):
-    root = tmp_path_factory.mktemp("pipe")
-    lw = Band(str(root / "lw"), 1.0, 400.0, 1.0, 3000)
-    sw = Band(str(root / "sw"), 1.0, 5000.0, 10.0, 3000, sw=True)
-    return lw, sw
 
 
 def test_pipeline_matches_oracle_per_column(bands, oracle, lib, device):

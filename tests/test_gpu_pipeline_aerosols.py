@@ -9,33 +9,15 @@ import pytest
 
 from aerosol_model import AEROSOL_GRID, aerosol_fields, oracle_aerosol_column
 from grtcode_amd import api, synthetic as syn
-from scenario import Band, MOL_ORDER
-from test_gpu_pipeline import oracle_column
-from test_gpu_pipeline_profiles import CP, GRAVITY, heating
+from pipeline_support import CP, GRAVITY, _sentinel, _setup, check_levels, heating, make_shape_bands, oracle_column
+from pipeline_support import bands  # noqa: F401  (a module fixture)
+from scenario import MOL_ORDER
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ("lw_up", "lw_down", "sw_up", "sw_down", "lw_heating", "sw_heating", "fluxes")
 # Edge shapes: the bound test_gpu_solver_shapes.py holds the same solver kernels to at the same shapes, 1e-10 of the
 # column's largest level flux (the aerosol instances add three multiply-adds and one more term to the combination)
 LEVEL_TOL = 1e-10
-
-
-@pytest.fixture(scope="module")
-def bands(tmp_path_factory):
-    root = tmp_path_factory.mktemp("pipe_aerosols")
-    lw = Band(str(root / "lw"), 1.0, 400.0, 1.0, 3000)
-    sw = Band(str(root / "sw"), 1.0, 5000.0, 10.0, 3000, sw=True)
-    return lw, sw
-
-
-def _setup(bands, device, V):
-    lwb, swb = bands
-    go_lw, _ = lwb.gas_optics(device, V)
-    go_sw, grid_sw = swb.gas_optics(device, V)
-    emis, alb = np.full(lwb.nw, 0.98), np.full(swb.nw, 0.2)
-    solar = api.create_solar_flux(grid_sw, swb.files["solar"])
-    return go_lw, go_sw, emis, alb, solar
 
 
 def fields(ncol, L, seed, grid=AEROSOL_GRID):
@@ -53,17 +35,6 @@ def run(pipe, gcols, gaer, ncol, profiles):
 
 def same(a, b):
     return all(np.array_equal(a[k], b[k]) for k in a)
-
-
-def check_levels(got, c, key, col, want_up, want_dn):
-    """test_gpu_pipeline_allsky_profiles.py's bounds for one column, band and set."""
-    up, dn, hr = got[key + "_up"][c], got[key + "_down"][c], got[key + "_heating"][c]
-    assert np.max(np.abs(up - want_up)) < 1e-9, key
-    assert np.max(np.abs(dn - want_dn)) < 1e-9, key
-    hmax = np.abs(hr).max()
-    assert hmax > 0.0
-    assert np.max(np.abs(hr - heating(up, dn, col["p"]))) <= 1e-12 * hmax, key
-    assert np.max(np.abs(hr - heating(want_up, want_dn, col["p"]))) <= 1e-6 * hmax, key
 
 
 # ---- 1. against the oracle -------------------------------------------------------------------------------------------- #
@@ -262,17 +233,7 @@ NS = (2, 127, 128, 129, 257)
 SHAPES = [(2, 61, "more", "L", True), (127, 2, "two", "0", False), (128, 201, "more", "-1", False),
           (129, 3, "two", "L", True), (257, 61, "two", "0", True), (127, 3, "more", "-1", True),
           (129, 201, "more", "0", False), (2, 2, "two", "-1", False)]
-
-
-@pytest.fixture(scope="module")
-def shape_bands(tmp_path_factory):
-    root = tmp_path_factory.mktemp("aerosol_shapes")
-    out = {}
-    for n in NS:
-        out[n] = (Band(str(root / f"lw{n}"), 100.0, 100.0 + (n - 1) * 1.0, 1.0, 300),
-                  Band(str(root / f"sw{n}"), 2000.0, 2000.0 + (n - 1) * 10.0, 10.0, 300, sw=True))
-        assert out[n][0].nw == n and out[n][1].nw == n
-    return out
+shape_bands = make_shape_bands(NS, 100.0, 2000.0)
 
 
 def shape_grid(band, kind):
@@ -282,13 +243,6 @@ def shape_grid(band, kind):
             return np.array([band.w0 - 0.5 * band.dw, band.wn + 0.5 * band.dw])
         return np.array([band.w0 + 0.3 * span, band.w0 + 0.8 * span])           # points below, inside and above
     return np.linspace(band.w0 - 2.5 * band.dw, band.wn + 2.5 * band.dw, band.nw + 3)
-
-
-def _sentinel(device, n):
-    buf = api.DeviceBuffer(device, 8 * n)
-    fill = np.full(n, -7.25)
-    api.check(api.load_library().grt_host_to_device(device, buf.ptr, fill.ctypes.data_as(C.c_void_p), C.c_size_t(8 * n)))
-    return buf
 
 
 @pytest.mark.parametrize("n,V,na_kind,ul,profiles", SHAPES, ids=[f"n{n}-V{V}-{k}-ul{u}-{'prof' if p else 'six'}"

@@ -6,109 +6,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from cloud_bands import band_map, band_optics, driver_limits, grid_optics
-from cloud_model import synthetic_tables
 from grtcode_amd import api, synthetic as syn
+from pipeline_support import _setup, cloud_columns, limits, make, oracle_allsky_column, oracle_column
+from pipeline_support import bands, tables  # noqa: F401  (module fixtures)
 from scenario import Band, MOL_ORDER
-from test_gpu_pipeline import oracle_column
 
 pytestmark = pytest.mark.gpu
-
-LIQUID_EDGES = [10.0, 90.0, 170.0, 260.0, 350.0, 1800.0, 4200.0]                      # 6 liquid bands
-ICE_EDGES = [10.0, 120.0, 230.0, 330.0, 1500.0, 3000.0, 4400.0, 6000.0, 9000.0]       # 8 ice bands
-
-
-@pytest.fixture(scope="module")
-def bands(tmp_path_factory):
-    root = tmp_path_factory.mktemp("pipe_allsky")
-    lw = Band(str(root / "lw"), 1.0, 400.0, 1.0, 3000)
-    sw = Band(str(root / "sw"), 1.0, 5000.0, 10.0, 3000, sw=True)
-    return lw, sw
-
-
-@pytest.fixture(scope="module")
-def tables(tmp_path_factory):
-    """Synthetic cloud parametrisations: more ice bands than liquid ones, and a gap after liquid band 1."""
-    root = tmp_path_factory.mktemp("cloud_tables")
-    (root / "i").mkdir()
-    _, t = synthetic_tables(str(root), seed=4, band_edges=LIQUID_EDGES)
-    _, ti = synthetic_tables(str(root / "i"), seed=9, band_edges=ICE_EDGES)
-    t["ice"] = ti["ice"]
-    t["liquid"]["Band_limits_upr"][1] = np.float64(np.float32(150.0))
-    return t
-
-
-def limits(t, phase):
-    return t[phase]["Band_limits_lwr"].copy(), t[phase]["Band_limits_upr"].copy()
-
-
-def cloud_columns(cols, tables, seed, clear=False):
-    """Cloud fields of each column -- overcast, partial and clear layers, liquid-only (low) and ice-only (high) ones --,
-    layer thickness, and the band optics of a longwave and a shortwave draw: make_clouds' inputs."""
-    L = cols[0]["p"].size - 1
-    rng = np.random.default_rng(seed)
-    th, lw_l, lw_i, sw_l, sw_i = [], [], [], [], []
-    for c, col in enumerate(cols):
-        cf = np.where(rng.random(L) < 0.5, rng.random(L), 0.0)
-        cf[L - 3 - c] = 1.0                                         # overcast
-        cf[2] = 0.0                                                 # clear
-        lwc = np.where(cf > 0, 0.2 * rng.random(L), 0.0)
-        iwc = np.where(cf > 0, 0.03 * rng.random(L), 0.0)
-        high = np.arange(L) < L // 3
-        lwc[high] = 0.0                                             # ice only aloft
-        iwc[L - 2:] = 0.0                                           # liquid only at the bottom
-        cf[(lwc + iwc) == 0.0] = 0.0
-        if clear:
-            cf[:], lwc[:], iwc[:] = 0.0, 0.0, 0.0
-        overlap = np.exp(-np.abs(np.diff(np.log(col["p"][1:] + col["p"][:-1]))) / 0.5)
-        th.append(29.3 * col["t_layer"] * np.log(col["p"][1:] / col["p"][:-1]))          # m (hypsometric)
-        draw = np.random.default_rng(seed * 7 + c).random
-        for lq, ic in ((lw_l, lw_i), (sw_l, sw_i)):                                       # two passes, two draws
-            a, b = band_optics(tables, draw, cf, lwc, iwc, overlap, 10.0, col["t_layer"])
-            lq.append(a)
-            ic.append(b)
-    return dict(thickness=np.array(th), lw_liquid=np.array(lw_l), lw_ice=np.array(lw_i), sw_liquid=np.array(sw_l),
-                sw_ice=np.array(sw_i))
-
-
-def make(tables, cl):
-    return api.make_clouds(limits(tables, "liquid"), limits(tables, "ice"), cl["thickness"], cl["lw_liquid"],
-                           cl["lw_ice"], cl["sw_liquid"], cl["sw_ice"])
-
-
-def oracle_allsky_column(orc, lib, band, col, lw, tables, liquid, ice, thickness, emis=None, alb=None, solar=None,
-                         user_level=-1):
-    """driver.c:474-597 for one column and band: the cloud objects of cloud_optics' spreading onto the driver's
-    band-limit array (no cloud where no band lies), tau = extinction x thickness, add_optics of {gas, Rayleigh, liquid,
-    ice}, the solver, the -integrated rows."""
-    L = col["p"].size - 1
-    w = driver_limits(band.w0, band.dw, band.nw)
-    B = liquid.shape[1]
-    (llo, lhi), (ilo, ihi) = limits(tables, "liquid"), limits(tables, "ice")
-    maps = (band_map(llo, lhi, B, B, w), band_map(ilo, ihi, ilo.size, B, w))
-    lt, lo, lg, it, io, ig = grid_optics(liquid, ice, thickness, maps)
-    tau_gas = band.oracle_tau(orc, orc, lib, col)
-    tr, om_r, g_r = orc.rayleigh(L, col["p"], band.w0, band.dw, band.nw)
-    z = np.zeros_like(tau_gas)
-    tau, omega, g = orc.add_optics([tau_gas, tr, lt, it], [z, om_r, lo, io], [z, g_r, lg, ig])
-    if lw:
-        up, dn = orc.lw_fluxes(band.w0, band.dw, col["t_surf"], col["t_layer"], col["t"], tau, omega, emis)
-    else:
-        up, dn = orc.sw_fluxes(omega, g, tau, col["mu0"], 0.5, alb, alb, col["tsi"], solar)
-    rows = [up[0], up[-1], up[user_level] if user_level >= 0 else None,
-            dn[0], dn[-1], dn[user_level] if user_level >= 0 else None]
-    integ = [orc.integrate_row(r, band.dw) if r is not None else 0.0 for r in rows]
-    return dict(tau=tau, omega=omega, g=g, integ=np.array(integ), maps=maps)
-
-
-def _setup(bands, device, V):
-    lwb, swb = bands
-    go_lw, _ = lwb.gas_optics(device, V)
-    go_sw, grid_sw = swb.gas_optics(device, V)
-    emis, alb = np.full(lwb.nw, 0.98), np.full(swb.nw, 0.2)
-    solar = api.create_solar_flux(grid_sw, swb.files["solar"])
-    return go_lw, go_sw, emis, alb, solar
-
 
 @pytest.mark.parametrize("spectral", [False, True])
 def test_allsky_fluxes_match_the_oracle(bands, tables, oracle, lib, device, spectral):

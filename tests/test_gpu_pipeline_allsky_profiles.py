@@ -6,71 +6,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from cloud_bands import band_map, driver_limits, grid_optics
 from grtcode_amd import api, synthetic as syn
+from pipeline_support import (KEYS, LEVEL_KEYS, _sentinel, _setup, check_levels, cloud_columns, heating, limits, make,
+                              oracle_allsky_levels, oracle_column)
+from pipeline_support import bands, tables  # noqa: F401  (module fixtures)
 from scenario import Band, MOL_ORDER
-from test_gpu_pipeline import oracle_column
-from test_gpu_pipeline_allsky import cloud_columns, limits, make, tables  # noqa: F401  (tables: a module fixture)
-from test_gpu_pipeline_profiles import CP, GRAVITY, heating
 
 pytestmark = pytest.mark.gpu
-
-LEVEL_KEYS = ("lw_up", "lw_down", "sw_up", "sw_down")
-KEYS = LEVEL_KEYS + ("lw_heating", "sw_heating", "fluxes")
-
-
-@pytest.fixture(scope="module")
-def bands(tmp_path_factory):
-    root = tmp_path_factory.mktemp("pipe_allsky_profiles")
-    lw = Band(str(root / "lw"), 1.0, 400.0, 1.0, 3000)
-    sw = Band(str(root / "sw"), 1.0, 5000.0, 10.0, 3000, sw=True)
-    return lw, sw
-
-
-def _setup(bands, device, V):
-    lwb, swb = bands
-    go_lw, _ = lwb.gas_optics(device, V)
-    go_sw, grid_sw = swb.gas_optics(device, V)
-    emis, alb = np.full(lwb.nw, 0.98), np.full(swb.nw, 0.2)
-    solar = api.create_solar_flux(grid_sw, swb.files["solar"])
-    return go_lw, go_sw, emis, alb, solar
-
-
-def oracle_allsky_levels(orc, lib, band, col, lw, tables, liquid, ice, thickness, emis=None, alb=None, solar=None):
-    """driver.c:474-597 for one column and band, as oracle_allsky_column, but the spectra of every level are kept:
-    up, dn [V][nw], and their integrals up_int, dn_int [V]."""
-    L = col["p"].size - 1
-    w = driver_limits(band.w0, band.dw, band.nw)
-    B = liquid.shape[1]
-    (llo, lhi), (ilo, ihi) = limits(tables, "liquid"), limits(tables, "ice")
-    maps = (band_map(llo, lhi, B, B, w), band_map(ilo, ihi, ilo.size, B, w))
-    lt, lo, lg, it, io, ig = grid_optics(liquid, ice, thickness, maps)
-    tau_gas = band.oracle_tau(orc, orc, lib, col)
-    tr, om_r, g_r = orc.rayleigh(L, col["p"], band.w0, band.dw, band.nw)
-    z = np.zeros_like(tau_gas)
-    tau, omega, g = orc.add_optics([tau_gas, tr, lt, it], [z, om_r, lo, io], [z, g_r, lg, ig])
-    if lw:
-        up, dn = orc.lw_fluxes(band.w0, band.dw, col["t_surf"], col["t_layer"], col["t"], tau, omega, emis)
-    else:
-        up, dn = orc.sw_fluxes(omega, g, tau, col["mu0"], 0.5, alb, alb, col["tsi"], solar)
-    up_int = np.array([orc.integrate_row(up[k], band.dw) for k in range(L + 1)])
-    dn_int = np.array([orc.integrate_row(dn[k], band.dw) for k in range(L + 1)])
-    return dict(up=up, dn=dn, up_int=up_int, dn_int=dn_int)
-
-
-def _check_set(got, c, key, col, want_up, want_dn):
-    """One column, band and set: levels against the oracle's, the heating-rate formula, energy closure."""
-    up, dn, hr = got[key + "_up"][c], got[key + "_down"][c], got[key + "_heating"][c]
-    assert np.max(np.abs(up - want_up)) < 1e-9, key
-    assert np.max(np.abs(dn - want_dn)) < 1e-9, key
-    hmax = np.abs(hr).max()
-    assert hmax > 0.0
-    assert np.max(np.abs(hr - heating(up, dn, col["p"]))) <= 1e-12 * hmax, key
-    assert np.max(np.abs(hr - heating(want_up, want_dn, col["p"]))) <= 1e-6 * hmax, key
-    absorbed = np.sum(hr * 100.0 * (col["p"][1:] - col["p"][:-1]) * CP / (GRAVITY * 86400.0))
-    fmax = max(np.abs(up).max(), np.abs(dn).max())
-    assert abs(absorbed - ((dn[0] - up[0]) - (dn[-1] - up[-1]))) <= 1e-12 * fmax, key
-
 
 @pytest.mark.parametrize("spectral", [False, True])
 def test_level_fluxes_and_heating_rates_match_the_oracle(bands, tables, oracle, lib, device, spectral):
@@ -90,10 +32,10 @@ def test_level_fluxes_and_heating_rates_match_the_oracle(bands, tables, oracle, 
             w = oracle_column(oracle, lib, band, col, lw, emis, alb, solar, user_level)
             want_up = np.array([oracle.integrate_row(w["up"][k], band.dw) for k in range(V)])
             want_dn = np.array([oracle.integrate_row(w["dn"][k], band.dw) for k in range(V)])
-            _check_set(clear, c, key, col, want_up, want_dn)
+            check_levels(clear, c, key, col, want_up, want_dn, closure=True)
             a = oracle_allsky_levels(oracle, lib, band, col, lw, tables, cl[key + "_liquid"][c], cl[key + "_ice"][c],
                                      cl["thickness"][c], emis, alb, solar)
-            _check_set(cloudy, c, key, col, a["up_int"], a["dn_int"])
+            check_levels(cloudy, c, key, col, a["up_int"], a["dn_int"], closure=True)
             # every column has an overcast layer: the clouds change its all-sky rows
             effect = max(np.abs(cloudy[key + "_up"][c] - clear[key + "_up"][c]).max(),
                          np.abs(cloudy[key + "_down"][c] - clear[key + "_down"][c]).max())
@@ -212,13 +154,6 @@ def test_repeatable_and_no_interference(bands, tables, lib, device):
     pipe.destroy()
     go_lw.destroy()
     go_sw.destroy()
-
-
-def _sentinel(device, n):
-    buf = api.DeviceBuffer(device, 8 * n)
-    fill = np.full(n, -7.25)
-    api.check(api.load_library().grt_host_to_device(device, buf.ptr, fill.ctypes.data_as(C.c_void_p), C.c_size_t(8 * n)))
-    return buf
 
 
 def test_edge_cases(bands, tables, lib, device):

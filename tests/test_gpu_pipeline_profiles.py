@@ -7,36 +7,11 @@ import numpy as np
 import pytest
 
 from grtcode_amd import api, synthetic as syn
+from pipeline_support import CP, GRAVITY, _setup, heating, oracle_column
+from pipeline_support import bands  # noqa: F401  (a module fixture)
 from scenario import Band, MOL_ORDER
-from test_gpu_pipeline import oracle_column
 
 pytestmark = pytest.mark.gpu
-
-GRAVITY, CP = 9.80665, 1004.64       # grt_ext.h: GRT_GRAVITY, GRT_SPECIFIC_HEAT_AIR
-
-
-def heating(up, dn, p):
-    """K day-1 of every layer from level fluxes [.., V] and level pressures [V] in mb, levels top first."""
-    net = dn - up
-    return (GRAVITY / CP) * ((net[..., :-1] - net[..., 1:]) / (100.0 * (p[1:] - p[:-1]))) * 86400.0
-
-
-@pytest.fixture(scope="module")
-def bands(tmp_path_factory):
-    root = tmp_path_factory.mktemp("pipe_profiles")
-    lw = Band(str(root / "lw"), 1.0, 400.0, 1.0, 3000)
-    sw = Band(str(root / "sw"), 1.0, 5000.0, 10.0, 3000, sw=True)
-    return lw, sw
-
-
-def _setup(bands, device, V):
-    lwb, swb = bands
-    go_lw, _ = lwb.gas_optics(device, V)
-    go_sw, grid_sw = swb.gas_optics(device, V)
-    emis, alb = np.full(lwb.nw, 0.98), np.full(swb.nw, 0.2)
-    solar = api.create_solar_flux(grid_sw, swb.files["solar"])
-    return go_lw, go_sw, emis, alb, solar
-
 
 @pytest.mark.parametrize("spectral", [False, True])
 def test_level_fluxes_and_heating_rates_match_the_oracle(bands, oracle, lib, device, spectral):
@@ -164,7 +139,7 @@ def test_edge_cases(bands, lib, device):
         pipe.run_profiles(big)
     assert e.value.code == api.VALUE_ERR
     with pytest.raises(api.GrtError) as e:
-        api.check(lib.grt_pipeline_run_profiles(pipe.p, C.byref(gcols), None, pipe.prof["heating"].ptr, None))
+        api.check(lib.grt_pipeline_run_profiles(pipe.p, C.byref(gcols), None, pipe.buffers["profiles.heating"].ptr, None))
     assert e.value.code == api.VALUE_ERR
     pipe.destroy()
     # heating_dev and fluxes_dev may be NULL

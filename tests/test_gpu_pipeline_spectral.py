@@ -8,33 +8,15 @@ import numpy as np
 import pytest
 
 from grtcode_amd import api, synthetic as syn
+from pipeline_support import _setup, cloud_columns, limits, make, make_shape_bands, oracle_allsky_levels, oracle_column
+from pipeline_support import bands, tables  # noqa: F401  (module fixtures)
 from scenario import Band, MOL_ORDER
-from test_gpu_pipeline import oracle_column
-from test_gpu_pipeline_allsky import cloud_columns, limits, make, tables  # noqa: F401  (tables: a module fixture)
-from test_gpu_pipeline_allsky_profiles import oracle_allsky_levels
 
 pytestmark = pytest.mark.gpu
 
 ROW_TOL = 1e-10      # of the band's flux scale: the bound test_gpu_pipeline.py puts on the spectral views
 BIN_TOL = 1e-9       # W m-2
 MU0 = (1.0, 0.5, 0.05, 1e-3)
-
-
-@pytest.fixture(scope="module")
-def bands(tmp_path_factory):
-    root = tmp_path_factory.mktemp("pipe_spectral")
-    lw = Band(str(root / "lw"), 1.0, 400.0, 1.0, 3000)
-    sw = Band(str(root / "sw"), 1.0, 5000.0, 10.0, 3000, sw=True)
-    return lw, sw
-
-
-def _surface(lwb, swb, device, V):
-    go_lw, _ = lwb.gas_optics(device, V) if lwb is not None else (None, None)
-    go_sw, grid_sw = swb.gas_optics(device, V) if swb is not None else (None, None)
-    emis = np.full(lwb.nw, 0.98) if lwb is not None else None
-    alb = np.full(swb.nw, 0.2) if swb is not None else None
-    solar = api.create_solar_flux(grid_sw, swb.files["solar"]) if swb is not None else None
-    return go_lw, go_sw, emis, alb, solar
 
 
 def block_edges(n):
@@ -76,7 +58,7 @@ def test_spectral_rows_and_bins_match_the_oracle(bands, tables, oracle, lib, dev
     lwb, swb = bands
     V, ncol = 16, 2
     cols = [syn.profile(300 + c, V) for c in range(ncol)]
-    go_lw, go_sw, emis, alb, solar = _surface(lwb, swb, device, V)
+    go_lw, go_sw, emis, alb, solar = _setup((lwb, swb), device, V)
     pipe = api.Pipeline(go_lw, go_sw, ncol, user_level, emis, alb, solar, spectral=spectral)
     gcols, keep = api.make_columns(cols, MOL_ORDER, cfc_order=(0, 1))
     cl = cloud_columns(cols, tables, 31) if allsky else None
@@ -112,7 +94,7 @@ def test_a_bin_over_the_whole_grid_is_the_broadband_value(bands, tables, lib, de
     cols = [syn.profile(310 + c, V) for c in range(ncol)]
     for c, mu in zip(cols, MU0):
         c["mu0"] = mu
-    go_lw, go_sw, emis, alb, solar = _surface(lwb, swb, device, V)
+    go_lw, go_sw, emis, alb, solar = _setup((lwb, swb), device, V)
     pipe = api.Pipeline(go_lw, go_sw, ncol, 7, emis, alb, solar, spectral=spectral)
     gcols, keep = api.make_columns(cols, MOL_ORDER, cfc_order=(0, 1))
     gclouds, keep_clouds = make(tables, cloud_columns(cols, tables, 32))
@@ -143,7 +125,7 @@ def test_fluxes_are_those_of_run_and_run_allsky(bands, tables, lib, device, spec
     lwb, swb = bands
     V, ncol = 16, 3
     cols = [syn.profile(320 + c, V) for c in range(ncol)]
-    go_lw, go_sw, emis, alb, solar = _surface(lwb, swb, device, V)
+    go_lw, go_sw, emis, alb, solar = _setup((lwb, swb), device, V)
     pipe = api.Pipeline(go_lw, go_sw, ncol, 4, emis, alb, solar, spectral=spectral)
     gcols, keep = api.make_columns(cols, MOL_ORDER, cfc_order=(0, 1))
     gclouds, keep_clouds = make(tables, cloud_columns(cols, tables, 33))
@@ -179,7 +161,7 @@ def test_contiguous_bins_add_up_and_one_interval_bins_are_the_trapezoid(bands, l
     lwb, swb = bands
     V, ncol = 16, 2
     cols = [syn.profile(330 + c, V) for c in range(ncol)]
-    go_lw, go_sw, emis, alb, solar = _surface(lwb, swb, device, V)
+    go_lw, go_sw, emis, alb, solar = _setup((lwb, swb), device, V)
     pipe = api.Pipeline(go_lw, go_sw, ncol, 3, emis, alb, solar, spectral=spectral)
     gcols, keep = api.make_columns(cols, MOL_ORDER, cfc_order=(0, 1))
     fine = (np.array([0, 1, 2, 60, 127, 128, 129, 200, 256, 257, 390, 398, 399], np.int32),
@@ -214,17 +196,7 @@ def test_contiguous_bins_add_up_and_one_interval_bins_are_the_trapezoid(bands, l
 
 
 NS = (2, 127, 128, 129, 257)
-
-
-@pytest.fixture(scope="module")
-def shape_bands(tmp_path_factory):
-    root = tmp_path_factory.mktemp("spectral_shapes")
-    out = {}
-    for n in NS:
-        out[n] = (Band(str(root / f"lw{n}"), 100.0, 100.0 + (n - 1) * 1.0, 1.0, 300),
-                  Band(str(root / f"sw{n}"), 1000.0, 1000.0 + (n - 1) * 10.0, 10.0, 300, sw=True))
-        assert out[n][0].nw == n and out[n][1].nw == n
-    return out
+shape_bands = make_shape_bands(NS, 100.0, 1000.0)
 
 
 @pytest.mark.parametrize("spectral", [False, True])
@@ -240,7 +212,7 @@ def test_edge_shapes_against_the_oracle(shape_bands, tables, oracle, lib, device
     for c, mu in zip(cols, MU0):
         c["mu0"] = mu
     ncol = len(cols)
-    go_lw, go_sw, emis, alb, solar = _surface(lwb, swb, device, V)
+    go_lw, go_sw, emis, alb, solar = _setup((lwb, swb), device, V)
     pipe = api.Pipeline(go_lw, go_sw, ncol, user_level, emis, alb, solar, spectral=spectral)
     gcols, keep = api.make_columns(cols, MOL_ORDER, cfc_order=(0, 1))
     cl = cloud_columns(cols, tables, 34) if V > 2 else None
@@ -270,13 +242,13 @@ def test_a_null_band_takes_no_room_and_its_bins_are_refused(bands, lib, device, 
     V, ncol = 16, 2
     cols = [syn.profile(340 + c, V) for c in range(ncol)]
     gcols, keep = api.make_columns(cols, MOL_ORDER, cfc_order=(0, 1))
-    both = _surface(lwb, swb, device, V)
+    both = _setup((lwb, swb), device, V)
     ref = api.Pipeline(*both[:2], ncol, -1, *both[2:], spectral=spectral)
     ref.run_spectral(gcols, None, block_edges(lwb.nw), block_edges(swb.nw))
     full = ref.spectral(ncol)
     ref.destroy()
     for missing in (0, 1):
-        go_lw, go_sw, emis, alb, solar = _surface(lwb if missing else None, swb if not missing else None, device, V)
+        go_lw, go_sw, emis, alb, solar = _setup((lwb if missing else None, swb if not missing else None), device, V)
         pipe = api.Pipeline(go_lw, go_sw, ncol, -1, emis, alb, solar, spectral=spectral)
         have = 1 - missing
         edges = [None, None]
@@ -303,7 +275,7 @@ def test_refused_inputs_launch_nothing(bands, tables, lib, device):
     lwb, swb = bands
     V, ncol = 16, 2
     cols = [syn.profile(350 + c, V) for c in range(ncol)]
-    go_lw, go_sw, emis, alb, solar = _surface(lwb, swb, device, V)
+    go_lw, go_sw, emis, alb, solar = _setup((lwb, swb), device, V)
     pipe = api.Pipeline(go_lw, go_sw, ncol, -1, emis, alb, solar, spectral=False)
     gcols, keep = api.make_columns(cols, MOL_ORDER, cfc_order=(0, 1))
     cl = cloud_columns(cols, tables, 35)

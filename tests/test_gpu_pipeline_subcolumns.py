@@ -7,116 +7,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from cloud_bands import band_map, band_optics, driver_limits, grid_optics
 from grtcode_amd import api, synthetic as syn
+from pipeline_support import (KEYS, SETS, _deterministic, _sentinel, _setup, check_levels, limits, make,
+                              oracle_subcolumns, pick, six, subcolumn_clouds)
+from pipeline_support import bands, tables  # noqa: F401  (module fixtures)
 from scenario import Band, MOL_ORDER
-from test_gpu_pipeline_allsky import limits, tables  # noqa: F401  (tables: a module fixture)
-from test_gpu_pipeline_allsky_profiles import KEYS, _check_set, _sentinel
 
 pytestmark = pytest.mark.gpu
-
-SETS = ("lw_liquid", "lw_ice", "sw_liquid", "sw_ice")
-
-
-@pytest.fixture(scope="module")
-def bands(tmp_path_factory):
-    root = tmp_path_factory.mktemp("pipe_subcolumns")
-    lw = Band(str(root / "lw"), 1.0, 400.0, 1.0, 3000)
-    sw = Band(str(root / "sw"), 1.0, 5000.0, 10.0, 3000, sw=True)
-    return lw, sw
-
-
-def _setup(bands, device, V):
-    lwb, swb = bands
-    go_lw, _ = lwb.gas_optics(device, V)
-    go_sw, grid_sw = swb.gas_optics(device, V)
-    emis, alb = np.full(lwb.nw, 0.98), np.full(swb.nw, 0.2)
-    solar = api.create_solar_flux(grid_sw, swb.files["solar"])
-    return go_lw, go_sw, emis, alb, solar
-
-
-def subcolumn_clouds(cols, tables, seed, S, clear=False):
-    """Cloud fields of each column (overcast, partial and clear layers) and S draws of its band optics per pass, drawn as a
-    driver with num_subcolumns = S draws them: per column, S longwave draws, then S shortwave draws.  Optics sets
-    [ncol][S][3][B][L]."""
-    L = cols[0]["p"].size - 1
-    rng = np.random.default_rng(seed)
-    out = {k: [] for k in SETS}
-    th = []
-    for c, col in enumerate(cols):
-        cf = np.where(rng.random(L) < 0.5, rng.random(L), 0.0)
-        cf[L - 3 - c % 4] = 1.0
-        cf[2] = 0.0
-        lwc = np.where(cf > 0, 0.2 * rng.random(L), 0.0)
-        iwc = np.where(cf > 0, 0.03 * rng.random(L), 0.0)
-        lwc[np.arange(L) < L // 3] = 0.0
-        iwc[L - 2:] = 0.0
-        cf[(lwc + iwc) == 0.0] = 0.0
-        if clear:
-            cf[:], lwc[:], iwc[:] = 0.0, 0.0, 0.0
-        overlap = np.exp(-np.abs(np.diff(np.log(col["p"][1:] + col["p"][:-1]))) / 0.5)
-        th.append(29.3 * col["t_layer"] * np.log(col["p"][1:] / col["p"][:-1]))
-        draw = np.random.default_rng(seed * 7 + c).random
-        for kl, ki in (("lw_liquid", "lw_ice"), ("sw_liquid", "sw_ice")):
-            draws = [band_optics(tables, draw, cf, lwc, iwc, overlap, 10.0, col["t_layer"]) for _ in range(S)]
-            out[kl].append(np.array([d[0] for d in draws]))
-            out[ki].append(np.array([d[1] for d in draws]))
-    return dict(thickness=np.array(th), **{k: np.array(v) for k, v in out.items()})
-
-
-def make(tables, cl):
-    return api.make_clouds(limits(tables, "liquid"), limits(tables, "ice"), cl["thickness"], *[cl[k] for k in SETS])
-
-
-def pick(cl, columns=None, subcolumns=None):
-    """The cloud inputs of some columns (in that order) and some subcolumns of each (in that order)."""
-    columns = range(cl["thickness"].shape[0]) if columns is None else list(columns)
-    out = {"thickness": cl["thickness"][columns]}
-    for k in SETS:
-        a = cl[k][columns]
-        out[k] = a if subcolumns is None else a[:, list(subcolumns)]
-    return out
-
-
-def oracle_subcolumns(orc, lib, band, col, lw, tables, liquid, ice, thickness, emis=None, alb=None, solar=None):
-    """driver.c:503-589 for one column and band with liquid / ice [S][3][B][L]: per subcolumn the cloud objects, add_optics
-    of {gas, Rayleigh, liquid, ice}, the solver; the up and down fluxes summed, divided by S; every level integrated."""
-    L = col["p"].size - 1
-    S = liquid.shape[0]
-    w = driver_limits(band.w0, band.dw, band.nw)
-    B = liquid.shape[2]
-    (llo, lhi), (ilo, ihi) = limits(tables, "liquid"), limits(tables, "ice")
-    maps = (band_map(llo, lhi, B, B, w), band_map(ilo, ihi, ilo.size, B, w))
-    tau_gas = band.oracle_tau(orc, orc, lib, col)
-    tr, om_r, g_r = orc.rayleigh(L, col["p"], band.w0, band.dw, band.nw)
-    z = np.zeros_like(tau_gas)
-    up_sum = np.zeros((L + 1, band.nw))
-    dn_sum = np.zeros((L + 1, band.nw))
-    for j in range(S):
-        lt, lo, lg, it, io, ig = grid_optics(liquid[j], ice[j], thickness, maps)
-        tau, omega, g = orc.add_optics([tau_gas, tr, lt, it], [z, om_r, lo, io], [z, g_r, lg, ig])
-        if lw:
-            up, dn = orc.lw_fluxes(band.w0, band.dw, col["t_surf"], col["t_layer"], col["t"], tau, omega, emis)
-        else:
-            up, dn = orc.sw_fluxes(omega, g, tau, col["mu0"], 0.5, alb, alb, col["tsi"], solar)
-        up_sum += up
-        dn_sum += dn
-    up_sum /= float(S)
-    dn_sum /= float(S)
-    up_int = np.array([orc.integrate_row(up_sum[k], band.dw) for k in range(L + 1)])
-    dn_int = np.array([orc.integrate_row(dn_sum[k], band.dw) for k in range(L + 1)])
-    return dict(up_int=up_int, dn_int=dn_int, up=up_sum, dn=dn_sum)
-
-
-def six(up_int, dn_int, user_level):
-    u = user_level
-    return np.array([up_int[0], up_int[-1], up_int[u] if u >= 0 else 0.0,
-                     dn_int[0], dn_int[-1], dn_int[u] if u >= 0 else 0.0])
-
-
-def _deterministic(lib, on):
-    api.check(lib.grt_set_deterministic(1 if on else -1))
-
 
 @pytest.mark.parametrize("spectral", [False, True])
 def test_subcolumn_means_match_the_oracle(bands, tables, oracle, lib, device, spectral):
@@ -142,7 +39,7 @@ def test_subcolumn_means_match_the_oracle(bands, tables, oracle, lib, device, sp
             w = oracle_subcolumns(oracle, lib, band, col, lw, tables, cl[key + "_liquid"][c], cl[key + "_ice"][c],
                                   cl["thickness"][c], emis, alb, solar)
             assert np.max(np.abs(cloudy6[c, 6 * bi: 6 * bi + 6] - six(w["up_int"], w["dn_int"], user_level))) < 1e-9, key
-            _check_set(cloudy, c, key, col, w["up_int"], w["dn_int"])
+            check_levels(cloudy, c, key, col, w["up_int"], w["dn_int"], closure=True)
             assert np.max(np.abs(cloudy["fluxes"][c, 6 * bi: 6 * bi + 6] - cloudy6[c, 6 * bi: 6 * bi + 6])) < 1e-9, key
             spread = max(spread, np.max(np.abs(cloudy6[c, 6 * bi: 6 * bi + 6] - first[c, 6 * bi: 6 * bi + 6])))
         assert np.max(np.abs(clear["fluxes"][c] - clear6[c])) < 1e-9

@@ -21,7 +21,7 @@ from grtcode_amd import api, synthetic as syn
 from scenario import Band
 from test_gpu_c_driver import write_column
 from test_gpu_circ_rfmip import NAME, circ1_column
-from test_gpu_pipeline import oracle_column
+from pipeline_support import oracle_column
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DRIVER = os.path.join(ROOT, "oracle", "_ref", "grtcode_driver")

@@ -21,7 +21,7 @@ import pytest
 from grtcode_amd import api, synthetic as syn
 from grtcode_amd.dumpfile import read_dump, write_dump
 from scenario import Band
-from test_gpu_pipeline import oracle_column
+from pipeline_support import oracle_column
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DRIVER = os.path.join(ROOT, "oracle", "_ref", "grtcode_driver_dump")

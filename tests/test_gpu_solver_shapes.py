@@ -6,28 +6,20 @@ integrals against an exactly rounded trapezoid of the kernel's own spectra, and 
 deterministic mode.  Also: the spectral tables the shortwave solver adds beyond the ones it keeps in registers, the
 reference-shaped solvers at the same shapes, and what the library refuses."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
 
+from cloud_bands import band_optics
 from grtcode_amd import api, synthetic as syn
+from pipeline_support import (CP, GRAVITY, LEVEL_TOL, MU0, SOLVER_NS as NS, assert_trapezoid, cloud_columns, columns,
+                              heating, make, oracle_allsky_levels, oracle_column, surface, user_index)
+from pipeline_support import solver_bands as bands, tables  # noqa: F401  (module fixtures)
 from scenario import Band, MOL_ORDER
 from test_gpu_optics_solvers import random_optics
-from test_gpu_pipeline import oracle_column
-from test_gpu_pipeline_allsky import cloud_columns, make, tables  # noqa: F401  (tables: a module fixture)
-from test_gpu_pipeline_allsky_profiles import oracle_allsky_levels
-from test_gpu_pipeline_profiles import CP, GRAVITY, heating
-from cloud_bands import band_optics
 
 pytestmark = pytest.mark.gpu
 
-NS = (2, 3, 64, 65, 128, 129, 257)
-# first wavenumber of each grid: whole grids inside one cloud band (lw 100-101 cm-1: liquid band 1, sw 2000-2010 cm-1),
-# grids across the gap behind liquid band 1 (lw 140-203, 148-150 cm-1) and past the last ice band (sw 8990-9010 cm-1)
-LW_W0 = {2: 100.0, 3: 148.0, 64: 140.0, 65: 1.0, 128: 1.0, 129: 100.0, 257: 1.0}
-SW_W0 = {2: 2000.0, 3: 8990.0, 64: 1000.0, 65: 1.0, 128: 3000.0, 129: 100.0, 257: 1000.0}
-MU0 = (1.0, 0.5, 0.05, 1e-3)       # 0.5 = mu_dif: the two beams share t/mu; 1e-3 clamps tau/mu at 700 in most layers
 ENTRIES = ("run", "run_profiles", "run_allsky", "run_allsky_profiles")
 # Per entry point, one case per grid length; each level count and user level (-1, 0, 1, L-1, L) appears with every entry
 # point, and 201 levels only on grids of 65 points or fewer (the oracle's share of the run time).
@@ -36,36 +28,6 @@ VS = {"run": (201, 2, 3, 7, 8, 2, 3), "run_profiles": (2, 201, 7, 8, 3, 7, 8),
 ULS = {"run": ("-1", "0", "1", "L-1", "L", "0", "L"), "run_profiles": ("0", "1", "L-1", "L", "-1", "1", "L-1"),
        "run_allsky": ("1", "L-1", "L", "-1", "0", "L", "-1"), "run_allsky_profiles": ("L-1", "L", "-1", "0", "1", "-1", "0")}
 CASES = [(e, VS[e][k], n, ULS[e][k]) for e in ENTRIES for k, n in enumerate(NS)]
-TRAP_ULPS = 64                      # bound on the partial-sum tree's depth at these n (derived from the code, not measured)
-LEVEL_TOL = 1e-10                   # of the column's largest flux
-
-
-@pytest.fixture(scope="module")
-def bands(tmp_path_factory):
-    root = tmp_path_factory.mktemp("solver_shapes")
-    out = {}
-    for n in NS:
-        out[n] = (Band(str(root / f"lw{n}"), LW_W0[n], LW_W0[n] + (n - 1) * 1.0, 1.0, 300),
-                  Band(str(root / f"sw{n}"), SW_W0[n], SW_W0[n] + (n - 1) * 10.0, 10.0, 300, sw=True))
-        assert out[n][0].nw == n and out[n][1].nw == n
-    return out
-
-
-def columns(V):
-    cols = [syn.profile(500 + V + c, V) for c in range(len(MU0))]
-    for c, mu in zip(cols, MU0):
-        c["mu0"] = mu
-    return cols
-
-
-def surface(n, seed):
-    """Emissivity and albedo with 0 and 1 at some points (both ends at n = 2)."""
-    rng = np.random.default_rng(seed)
-    emis, alb = rng.uniform(0.3, 1.0, n), rng.uniform(0.0, 0.7, n)
-    emis[0], emis[-1], alb[0], alb[-1] = 0.0, 1.0, 1.0, 0.0
-    if n > 3:
-        emis[n // 2], alb[n // 2] = 1.0, 0.0
-    return emis, alb
 
 
 def few_layer_clouds(cols, tables, seed, clear=False):
@@ -93,17 +55,6 @@ def clouds_for(cols, tables, seed, clear=False):
     return few_layer_clouds(cols, tables, seed, clear=clear)
 
 
-def exact_trapezoid(f, dw):
-    f = [float(x) for x in f]
-    pts = [0.5 * f[0]] + f[1:-1] + [0.5 * f[-1]]
-    return dw * math.fsum(pts), dw * math.fsum(abs(x) for x in f)
-
-
-def assert_trapezoid(got, f, dw, what):
-    ref, mag = exact_trapezoid(f, dw)
-    assert abs(got - ref) <= TRAP_ULPS * 2.0 ** -52 * mag, (what, got, ref, mag)
-
-
 def run_entry(pipe, entry, gcols, gclouds, ncol):
     """-> dict(six=[ncol][12] of the set the entry is about (all-sky for the all-sky forms), clear=[ncol][12] or None,
     prof=profiles dict of that set or None)."""
@@ -121,10 +72,6 @@ def run_entry(pipe, entry, gcols, gclouds, ncol):
     pipe.run_allsky_profiles(gcols, gclouds)
     clear, cloudy = pipe.allsky_profiles(ncol)
     return dict(six=cloudy["fluxes"], clear=clear["fluxes"], prof=cloudy, clear_prof=clear)
-
-
-def user_index(kind, L):
-    return {"-1": -1, "0": 0, "1": 1, "L-1": L - 1, "L": L}[kind]
 
 
 @pytest.mark.parametrize("entry,V,n,ul", CASES, ids=[f"{e}-V{V}-n{n}-ul{u}" for e, V, n, u in CASES])

@@ -11,17 +11,14 @@ import numpy as np
 import pytest
 
 from grtcode_amd import api, synthetic as syn
+from pipeline_support import (CP, GRAVITY, KEYS, LEVEL_KEYS, LEVEL_TOL, SETS, SOLVER_NS as NS, _deterministic,
+                              _sentinel, assert_trapezoid, columns, heating, limits, make, oracle_subcolumns, pick, six,
+                              subcolumn_clouds, surface, user_index)
+from pipeline_support import solver_bands as bands, tables  # noqa: F401  (module fixtures)
 from scenario import MOL_ORDER
-from test_gpu_pipeline_allsky import limits, tables  # noqa: F401  (tables: a module fixture)
-from test_gpu_pipeline_allsky_profiles import KEYS, _sentinel
-from test_gpu_pipeline_profiles import CP, GRAVITY, heating
-from test_gpu_pipeline_subcolumns import SETS, make, oracle_subcolumns, pick, six, subcolumn_clouds
-from test_gpu_solver_shapes import (LEVEL_TOL, NS, assert_trapezoid, bands,  # noqa: F401  (bands: a module fixture)
-                                    columns, surface, user_index)
 
 pytestmark = pytest.mark.gpu
 
-LEVEL_KEYS = ("lw_up", "lw_down", "sw_up", "sw_down")
 ROW_CAP = 65535                     # grid rows of one subcolumn launch
 
 # ---- A: the Latin square.  Per (layout, form), one case per grid length; every level count, subcolumn count and user
@@ -39,10 +36,6 @@ assert all(set(VS[f]) == {2, 3, 7, 8, 201} and set(SS[f]) == {1, 2, 3, 7, 63, 64
            set(ULS[f]) == {"-1", "0", "1", "L-1", "L"} for f in FORMS)
 assert all(n <= 65 and S <= 7 for _, _, V, n, S, _ in CASES if V == 201)
 assert all(V <= 8 for _, _, V, _, S, _ in CASES if S >= 63)
-
-
-def _deterministic(lib, on):
-    api.check(lib.grt_set_deterministic(1 if on else -1))
 
 
 def drawn_clouds(cols, S, seed, B=6):

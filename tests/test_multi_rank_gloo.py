@@ -52,7 +52,7 @@ def cpu_flux_block(columns, root):
     from grtcode_amd import api, synthetic as syn
     from oracle.bindings import Oracle
     from scenario import Band
-    from test_gpu_pipeline import oracle_column
+    from pipeline_support import oracle_column
     orc, lib = Oracle(), api.load_library()
     lw = Band(os.path.join(root, "lw"), 600.0, 680.0, 1.0, 300)
     sw = Band(os.path.join(root, "sw"), 2000.0, 2400.0, 10.0, 300, sw=True)
