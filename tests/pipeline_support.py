@@ -1,6 +1,7 @@
 """What the batched pipeline's GPU tests (test_gpu_pipeline*.py, test_gpu_solver_shapes.py, test_gpu_subcolumn_shapes.py)
 share, once each: the oracle's column-by-column restatements of the reference driver, the bands and cloud tables the
-cases run on, their inputs, and the checks more than one module makes.  A plain module: a test module imports what it
+cases run on, their inputs, the four base entry points behind one call, a module's cache of oracle results, and the
+checks more than one module makes.  A plain module: a test module imports what it
 uses, the module fixtures (bands, tables, solver_bands) included, so each file shows what it depends on.  pytest does
 not rewrite the asserts of a plain module: the ones here carry their own messages."""
 import ctypes as C
@@ -48,11 +49,12 @@ def make_shape_bands(ns, lw_w0, sw_w0):
     return fixture
 
 
-def _setup(bands, device, V):
-    """Gas optics, surface and sun of a (longwave, shortwave) pair of bands, either of which may be None."""
+def _setup(bands, device, V, fast=0):
+    """Gas optics (tuned to the form `fast`, Band.gas_optics), surface and sun of a (longwave, shortwave) pair of bands,
+    either of which may be None."""
     lwb, swb = bands
-    go_lw, _ = lwb.gas_optics(device, V) if lwb is not None else (None, None)
-    go_sw, grid_sw = swb.gas_optics(device, V) if swb is not None else (None, None)
+    go_lw, _ = lwb.gas_optics(device, V, fast=fast) if lwb is not None else (None, None)
+    go_sw, grid_sw = swb.gas_optics(device, V, fast=fast) if swb is not None else (None, None)
     emis = np.full(lwb.nw, 0.98) if lwb is not None else None
     alb = np.full(swb.nw, 0.2) if swb is not None else None
     solar = api.create_solar_flux(grid_sw, swb.files["solar"]) if swb is not None else None
@@ -136,6 +138,54 @@ def pick(cl, columns=None, subcolumns=None):
 
 def make(tables, cl):
     return api.make_clouds(limits(tables, "liquid"), limits(tables, "ice"), cl["thickness"], *[cl[k] for k in SETS])
+
+
+def few_layer_clouds(cols, tables, seed, clear=False):
+    """cloud_columns' fields for columns of fewer layers than it places its overcast and clear layers in: every layer
+    cloudy (liquid and ice) in the first two columns, clear in the third, half cover in the fourth."""
+    L = cols[0]["p"].size - 1
+    th, sets = [], {k: [] for k in SETS}
+    for c, col in enumerate(cols):
+        cf = np.full(L, 0.0 if clear else (1.0, 1.0, 0.0, 0.5)[c % 4])
+        lwc, iwc = np.where(cf > 0, 0.15, 0.0), np.where(cf > 0, 0.02, 0.0)
+        overlap = np.exp(-np.abs(np.diff(np.log(col["p"][1:] + col["p"][:-1]))) / 0.5)
+        th.append(29.3 * col["t_layer"] * np.log(col["p"][1:] / col["p"][:-1]))
+        draw = np.random.default_rng(seed * 7 + c).random
+        for pre in ("lw", "sw"):
+            a, b = band_optics(tables, draw, cf, lwc, iwc, overlap, 10.0, col["t_layer"])
+            sets[pre + "_liquid"].append(a)
+            sets[pre + "_ice"].append(b)
+    return dict(thickness=np.array(th), **{k: np.array(v) for k, v in sets.items()})
+
+
+def clouds_for(cols, tables, seed, clear=False):
+    L = cols[0]["p"].size - 1
+    if L >= 6:
+        return cloud_columns(cols, tables, seed, clear=clear)
+    return few_layer_clouds(cols, tables, seed, clear=clear)
+
+
+# ---- the four base entry points ------------------------------------------------------------------------------------------ #
+ENTRIES = ("run", "run_profiles", "run_allsky", "run_allsky_profiles")
+
+
+def run_entry(pipe, entry, gcols, gclouds, ncol):
+    """-> dict(six=[ncol][12] of the set the entry is about (all-sky for the all-sky forms), clear=[ncol][12] or None,
+    prof=profiles dict of that set or None)."""
+    if entry == "run":
+        pipe.run(gcols)
+        return dict(six=pipe.fluxes(ncol), clear=None, prof=None, clear_prof=None)
+    if entry == "run_profiles":
+        pipe.run_profiles(gcols)
+        p = pipe.profiles(ncol)
+        return dict(six=p["fluxes"], clear=None, prof=p, clear_prof=None)
+    if entry == "run_allsky":
+        pipe.run_allsky(gcols, gclouds)
+        clear, cloudy = pipe.allsky_fluxes(ncol)
+        return dict(six=cloudy, clear=clear, prof=None, clear_prof=None)
+    pipe.run_allsky_profiles(gcols, gclouds)
+    clear, cloudy = pipe.allsky_profiles(ncol)
+    return dict(six=cloudy["fluxes"], clear=clear["fluxes"], prof=cloudy, clear_prof=clear)
 
 
 # ---- the oracle, column by column -------------------------------------------------------------------------------------- #
@@ -229,6 +279,44 @@ def oracle_subcolumns(orc, lib, band, col, lw, tables, liquid, ice, thickness, e
     dn_sum /= float(S)
     up_int, dn_int = _integrals(orc, band, up_sum, dn_sum)
     return dict(up_int=up_int, dn_int=dn_int, up=up_sum, dn=dn_sum)
+
+
+def spectral_rows(w, user_level):
+    """[6][nw]: the six rows of output_fluxes without -integrated from an oracle result's level spectra up, dn [V][nw]."""
+    up, dn = w["up"], w["dn"]
+    z = np.zeros(up.shape[1])
+    return np.array([up[0], up[-1], up[user_level] if user_level >= 0 else z,
+                     dn[0], dn[-1], dn[user_level] if user_level >= 0 else z])
+
+
+def oracle_rows(orc, lib, band, col, lw, user_level, cloud=None, tables=None, emis=None, alb=None, solar=None):
+    """[6][nw]: the six rows of output_fluxes without -integrated, from the oracle's spectra (clear or all-sky)"""
+    if cloud is None:
+        w = oracle_column(orc, lib, band, col, lw, emis, alb, solar, user_level)
+    else:
+        w = oracle_allsky_levels(orc, lib, band, col, lw, tables, *cloud, emis, alb, solar)
+    return spectral_rows(w, user_level)
+
+
+def block_edges(n):
+    """bins that start or end on a 128-point block boundary or one point either side, and one-interval bins at both ends"""
+    e = {0, 1, n - 2, n - 1}
+    for k in (128, 256):
+        e |= {k - 1, k, k + 1}
+    return np.array(sorted(x for x in e if 0 <= x <= n - 1), dtype=np.int32)
+
+
+@pytest.fixture(scope="module")
+def oracle_cache():
+    """The oracle's results of one test module, one per key: cached(oracle_cache, key, make).  The oracle is the expensive
+    part of a parity case; a key names everything its result depends on (kind, band, column, cloud or aerosol input)."""
+    return {}
+
+
+def cached(cache, key, make):
+    if key not in cache:
+        cache[key] = make()
+    return cache[key]
 
 
 # ---- checks ------------------------------------------------------------------------------------------------------------ #

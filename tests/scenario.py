@@ -72,7 +72,9 @@ class Band:
         return orc.interp_to_grid(self.w0, self.dw, self.nw, w, y, constant_extrap)
 
     # -- the product ------------------------------------------------------------------- #
-    def gas_optics(self, device, num_levels, from_file=True, method=api.LINE_SAMPLE):
+    def gas_optics(self, device, num_levels, from_file=True, method=api.LINE_SAMPLE, fast=0):
+        """fast: the arithmetic form the object is tuned to -- 0 unless a test asks otherwise; None: no tune() call at
+        all, the object as a caller who never heard of tune() gets it."""
         grid = api.create_spectral_grid(self.w0, self.wn, self.dw)
         go = api.GasOpticsObject(num_levels, grid, device, self.par,
                                  self.h2o_dir if self.with_ctm else None,
@@ -90,8 +92,9 @@ class Band:
                 go.add_cia(a, b, self.files[name])
         # A new object runs the production arithmetic (fast = 3) unless GRT_GAS_OPTICS_FAST says otherwise.  Tests state
         # the form they check: they start from the reference's operation order (1e-11 bounds) and tune() to a fused form
-        # where that is what they are about.
-        go.tune(fast=0)
+        # where that is what they are about (or ask for it here: fast=3, the production form).
+        if fast is not None:
+            go.tune(fast=fast)
         return go, grid
 
     def set_column(self, go, col):

@@ -36,10 +36,10 @@ BOUNDS = {
 }
 
 
-def record(name, payload):
+def record(name, payload, file="parity_full_g1.json"):
     out = os.path.join(ROOT, "gpurun_out")
     os.makedirs(out, exist_ok=True)
-    path = os.path.join(out, "parity_full_g1.json")
+    path = os.path.join(out, file)
     data = json.load(open(path)) if os.path.exists(path) else {}
     data[name] = payload
     json.dump(data, open(path, "w"), indent=1)

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from grtcode_amd import api, synthetic as syn
-from pipeline_support import _setup, cloud_columns, limits, make, make_shape_bands, oracle_allsky_levels, oracle_column
+from pipeline_support import _setup, block_edges, cloud_columns, limits, make, make_shape_bands, oracle_rows
 from pipeline_support import bands, tables  # noqa: F401  (module fixtures)
 from scenario import Band, MOL_ORDER
 
@@ -17,26 +17,6 @@ pytestmark = pytest.mark.gpu
 ROW_TOL = 1e-10      # of the band's flux scale: the bound test_gpu_pipeline.py puts on the spectral views
 BIN_TOL = 1e-9       # W m-2
 MU0 = (1.0, 0.5, 0.05, 1e-3)
-
-
-def block_edges(n):
-    """bins that start or end on a 128-point block boundary or one point either side, and one-interval bins at both ends"""
-    e = {0, 1, n - 2, n - 1}
-    for k in (128, 256):
-        e |= {k - 1, k, k + 1}
-    return np.array(sorted(x for x in e if 0 <= x <= n - 1), dtype=np.int32)
-
-
-def oracle_rows(orc, lib, band, col, lw, user_level, cloud=None, tables=None, emis=None, alb=None, solar=None):
-    """[6][nw]: the six rows of output_fluxes without -integrated, from the oracle's spectra (clear or all-sky)"""
-    if cloud is None:
-        w = oracle_column(orc, lib, band, col, lw, emis, alb, solar, user_level)
-    else:
-        w = oracle_allsky_levels(orc, lib, band, col, lw, tables, *cloud, emis, alb, solar)
-    up, dn = w["up"], w["dn"]
-    z = np.zeros(band.nw)
-    return np.array([up[0], up[-1], up[user_level] if user_level >= 0 else z,
-                     dn[0], dn[-1], dn[user_level] if user_level >= 0 else z])
 
 
 def want_bins(orc, rows, edges, dw):

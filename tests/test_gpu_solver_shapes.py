@@ -10,17 +10,15 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from cloud_bands import band_optics
 from grtcode_amd import api, synthetic as syn
-from pipeline_support import (CP, GRAVITY, LEVEL_TOL, MU0, SOLVER_NS as NS, assert_trapezoid, cloud_columns, columns,
-                              heating, make, oracle_allsky_levels, oracle_column, surface, user_index)
+from pipeline_support import (CP, ENTRIES, GRAVITY, LEVEL_TOL, MU0, SOLVER_NS as NS, assert_trapezoid, clouds_for, columns,
+                              heating, make, oracle_allsky_levels, oracle_column, run_entry, surface, user_index)
 from pipeline_support import solver_bands as bands, tables  # noqa: F401  (module fixtures)
 from scenario import Band, MOL_ORDER
 from test_gpu_optics_solvers import random_optics
 
 pytestmark = pytest.mark.gpu
 
-ENTRIES = ("run", "run_profiles", "run_allsky", "run_allsky_profiles")
 # Per entry point, one case per grid length; each level count and user level (-1, 0, 1, L-1, L) appears with every entry
 # point, and 201 levels only on grids of 65 points or fewer (the oracle's share of the run time).
 VS = {"run": (201, 2, 3, 7, 8, 2, 3), "run_profiles": (2, 201, 7, 8, 3, 7, 8),
@@ -28,50 +26,6 @@ VS = {"run": (201, 2, 3, 7, 8, 2, 3), "run_profiles": (2, 201, 7, 8, 3, 7, 8),
 ULS = {"run": ("-1", "0", "1", "L-1", "L", "0", "L"), "run_profiles": ("0", "1", "L-1", "L", "-1", "1", "L-1"),
        "run_allsky": ("1", "L-1", "L", "-1", "0", "L", "-1"), "run_allsky_profiles": ("L-1", "L", "-1", "0", "1", "-1", "0")}
 CASES = [(e, VS[e][k], n, ULS[e][k]) for e in ENTRIES for k, n in enumerate(NS)]
-
-
-def few_layer_clouds(cols, tables, seed, clear=False):
-    """cloud_columns' fields for columns of fewer layers than it places its overcast and clear layers in: every layer
-    cloudy (liquid and ice) in the first two columns, clear in the third, half cover in the fourth."""
-    L = cols[0]["p"].size - 1
-    th, sets = [], {k: [] for k in ("lw_liquid", "lw_ice", "sw_liquid", "sw_ice")}
-    for c, col in enumerate(cols):
-        cf = np.full(L, 0.0 if clear else (1.0, 1.0, 0.0, 0.5)[c % 4])
-        lwc, iwc = np.where(cf > 0, 0.15, 0.0), np.where(cf > 0, 0.02, 0.0)
-        overlap = np.exp(-np.abs(np.diff(np.log(col["p"][1:] + col["p"][:-1]))) / 0.5)
-        th.append(29.3 * col["t_layer"] * np.log(col["p"][1:] / col["p"][:-1]))
-        draw = np.random.default_rng(seed * 7 + c).random
-        for pre in ("lw", "sw"):
-            a, b = band_optics(tables, draw, cf, lwc, iwc, overlap, 10.0, col["t_layer"])
-            sets[pre + "_liquid"].append(a)
-            sets[pre + "_ice"].append(b)
-    return dict(thickness=np.array(th), **{k: np.array(v) for k, v in sets.items()})
-
-
-def clouds_for(cols, tables, seed, clear=False):
-    L = cols[0]["p"].size - 1
-    if L >= 6:
-        return cloud_columns(cols, tables, seed, clear=clear)
-    return few_layer_clouds(cols, tables, seed, clear=clear)
-
-
-def run_entry(pipe, entry, gcols, gclouds, ncol):
-    """-> dict(six=[ncol][12] of the set the entry is about (all-sky for the all-sky forms), clear=[ncol][12] or None,
-    prof=profiles dict of that set or None)."""
-    if entry == "run":
-        pipe.run(gcols)
-        return dict(six=pipe.fluxes(ncol), clear=None, prof=None, clear_prof=None)
-    if entry == "run_profiles":
-        pipe.run_profiles(gcols)
-        p = pipe.profiles(ncol)
-        return dict(six=p["fluxes"], clear=None, prof=p, clear_prof=None)
-    if entry == "run_allsky":
-        pipe.run_allsky(gcols, gclouds)
-        clear, cloudy = pipe.allsky_fluxes(ncol)
-        return dict(six=cloudy, clear=clear, prof=None, clear_prof=None)
-    pipe.run_allsky_profiles(gcols, gclouds)
-    clear, cloudy = pipe.allsky_profiles(ncol)
-    return dict(six=cloudy["fluxes"], clear=clear["fluxes"], prof=cloudy, clear_prof=clear)
 
 
 @pytest.mark.parametrize("entry,V,n,ul", CASES, ids=[f"{e}-V{V}-n{n}-ul{u}" for e, V, n, u in CASES])
