@@ -17,6 +17,7 @@
  *   surface_temperature, solar_zenith_angle [deg], toa_solar_irradiance [W m-2],
  *   and layer abundances (mole fraction) H2O CO2 O3 N2O CO CH4 O2 CFC11 CFC12.
  * Level abundances are pressure-interpolated from the layer values like circ/src/basic-circ-test.c:51-66.
+ * The reader, the flag tables and the interpolation are examples/example_support.h.
  *
  * Output: one line "fluxes: rlut rlus rlu@k rldt rlds rld@k rsut rsus rsu@k rsdt rsds rsd@k" [W m-2].
  */
@@ -30,103 +31,7 @@
 #include "rayleigh.h"
 #include "shortwave.h"
 #include "solar_flux.h"
-
-#define MAXV 201
-
-#define check(call) { int rc_ = (call); if (rc_ != GRTCODE_SUCCESS) { char b_[4096]; \
-    grtcode_errstr(rc_, b_, 4096); fprintf(stderr, "[%s:%d] %s\n", __FILE__, __LINE__, b_); return EXIT_FAILURE; } }
-
-typedef struct Column
-{
-    int num_levels;
-    fp_t level_pressure[MAXV], level_temperature[MAXV], layer_pressure[MAXV], layer_temperature[MAXV];
-    fp_t surface_temperature, solar_zenith_angle, toa_solar_irradiance;
-    fp_t abundance[9][MAXV];    /* H2O CO2 O3 N2O CO CH4 O2 CFC11 CFC12 (layer) */
-} Column_t;
-
-static char const *const species[9] = {"H2O", "CO2", "O3", "N2O", "CO", "CH4", "O2", "CFC11", "CFC12"};
-static int const hitran_id[7] = {H2O, CO2, O3, N2O, CO, CH4, O2};
-
-static int read_values(char *text, fp_t *dst, int max)
-{
-    int n = 0;
-    for (char *tok = strtok(text, " \t\r\n"); tok != NULL && n < max; tok = strtok(NULL, " \t\r\n"))
-    {
-        dst[n++] = atof(tok);
-    }
-    return n;
-}
-
-static int read_column(char const *path, Column_t *c)
-{
-    FILE *f = fopen(path, "r");
-    if (f == NULL)
-    {
-        fprintf(stderr, "cannot open column file %s\n", path);
-        return 1;
-    }
-    memset(c, 0, sizeof(*c));
-    static char line[1 << 16];
-    while (fgets(line, sizeof(line), f) != NULL)
-    {
-        char *colon = strchr(line, ':');
-        if (colon == NULL)
-        {
-            continue;
-        }
-        *colon = '\0';
-        char *vals = colon + 1;
-        if (strcmp(line, "level_pressure") == 0) c->num_levels = read_values(vals, c->level_pressure, MAXV);
-        else if (strcmp(line, "level_temperature") == 0) read_values(vals, c->level_temperature, MAXV);
-        else if (strcmp(line, "layer_pressure") == 0) read_values(vals, c->layer_pressure, MAXV);
-        else if (strcmp(line, "layer_temperature") == 0) read_values(vals, c->layer_temperature, MAXV);
-        else if (strcmp(line, "surface_temperature") == 0) read_values(vals, &c->surface_temperature, 1);
-        else if (strcmp(line, "solar_zenith_angle") == 0) read_values(vals, &c->solar_zenith_angle, 1);
-        else if (strcmp(line, "toa_solar_irradiance") == 0) read_values(vals, &c->toa_solar_irradiance, 1);
-        else
-        {
-            for (int k = 0; k < 9; ++k)
-            {
-                if (strcmp(line, species[k]) == 0) read_values(vals, c->abundance[k], MAXV);
-            }
-        }
-    }
-    fclose(f);
-    return c->num_levels < 2;
-}
-
-/* basic-circ-test.c:51-66 */
-static void pressure_interpolate(fp_t *ppmv, fp_t const *abundance, int num_layers, fp_t const *layer_pressure,
-                                 fp_t const *level_pressure)
-{
-    fp_t const to_ppmv = 1.e6;
-    ppmv[0] = abundance[0]*to_ppmv;
-    ppmv[num_layers] = abundance[num_layers - 1]*to_ppmv;
-    for (int i = 1; i < num_layers; ++i)
-    {
-        ppmv[i] = (abundance[i - 1] + (abundance[i] - abundance[i - 1])*
-                  (level_pressure[i] - layer_pressure[i - 1])/(layer_pressure[i] - layer_pressure[i - 1]));
-        ppmv[i] *= to_ppmv;
-    }
-}
-
-static char const *option(int argc, char **argv, char const *name, int takes_value)
-{
-    for (int i = 1; i < argc; ++i)
-    {
-        if (strcmp(argv[i], name) == 0)
-        {
-            return takes_value ? (i + 1 < argc ? argv[i + 1] : NULL) : argv[i];
-        }
-    }
-    return NULL;
-}
-
-static fp_t number(int argc, char **argv, char const *name, fp_t fallback)
-{
-    char const *v = option(argc, argv, name, 1);
-    return v != NULL ? atof(v) : fallback;
-}
+#include "example_support.h"
 
 /* driver.c:302-326 */
 static void integrate(SpectralGrid_t grid, fp_t const *flux_up, fp_t const *flux_down, int num_levels, int user_level,
@@ -157,11 +62,19 @@ int main(int argc, char **argv)
     }
     char const *v;
     grtcode_set_verbosity(option(argc, argv, "-v", 0) ? GRTCODE_INFO : GRTCODE_WARN);
-    Column_t col;
-    if (read_column(option(argc, argv, "-p", 1), &col))
+    /* one column: "column:" lines are not looked at, every block of the file falls into it */
+    Column_t *columns;
+    if (read_columns(option(argc, argv, "-p", 1), 1, &columns) < 0)
+    {
+        fprintf(stderr, "cannot open column file %s\n", option(argc, argv, "-p", 1));
+        return EXIT_FAILURE;
+    }
+    if (columns == NULL || columns[0].num_levels < 2)
     {
         return EXIT_FAILURE;
     }
+    Column_t col = columns[0];
+    free(columns);
     int const V = col.num_levels, L = V - 1;
     int const user_level = (v = option(argc, argv, "-flux-at-level", 1)) ? atoi(v) : -1;
 
@@ -179,9 +92,6 @@ int main(int argc, char **argv)
     int const method = line_sample;
     GasOptics_t lbl[2];
     SpectralGrid_t const *grids[2] = {&lw_grid, &sw_grid};
-    char const *cfc_files[2] = {option(argc, argv, "-CFC-11", 1), option(argc, argv, "-CFC-12", 1)};
-    char const *cia_files[3] = {option(argc, argv, "-N2-N2", 1), option(argc, argv, "-O2-N2", 1), option(argc, argv, "-O2-O2", 1)};
-    int const cia_pairs[3][2] = {{CIA_N2, CIA_N2}, {CIA_O2, CIA_N2}, {CIA_O2, CIA_O2}};
     for (int b = 0; b < 2; ++b)
     {
         check(create_gas_optics(&lbl[b], V, grids[b], &device, argv[1], option(argc, argv, "-h2o-ctm", 1),
@@ -192,11 +102,15 @@ int main(int argc, char **argv)
             snprintf(flag, sizeof(flag), "-%s", species[k]);
             if (option(argc, argv, flag, 0)) check(add_molecule(&lbl[b], hitran_id[k], NULL, NULL));
         }
-        if (cfc_files[0]) check(add_cfc(&lbl[b], CFC11, cfc_files[0]));
-        if (cfc_files[1]) check(add_cfc(&lbl[b], CFC12, cfc_files[1]));
+        for (int k = 0; k < 2; ++k)
+        {
+            char const *file = option(argc, argv, cfc_flags[k].flag, 1);
+            if (file) check(add_cfc(&lbl[b], cfc_flags[k].id, file));
+        }
         for (int k = 0; k < 3; ++k)
         {
-            if (cia_files[k]) check(add_cia(&lbl[b], cia_pairs[k][0], cia_pairs[k][1], cia_files[k]));
+            char const *file = option(argc, argv, cia_flags[k].flag, 1);
+            if (file) check(add_cia(&lbl[b], cia_flags[k].s1, cia_flags[k].s2, file));
         }
     }
 
@@ -218,7 +132,7 @@ int main(int argc, char **argv)
     fp_t ppmv[9][MAXV];
     for (int k = 0; k < 9; ++k)
     {
-        pressure_interpolate(ppmv[k], col.abundance[k], L, col.layer_pressure, col.level_pressure);
+        layers_to_levels(ppmv[k], col.abundance[k], L, col.layer_pressure, col.level_pressure);
     }
     fp_t n2[MAXV];
     for (int i = 0; i < V; ++i) n2[i] = 0.781e6;

@@ -30,101 +30,25 @@
  *
  * Output (-o PATH, default output.nc as driver.c names it -- but text): one line per write_output call,
  *   "<time> <column> <variable name> <count> v0 v1 ...", fluxes in W m-2 (or W m-2 cm with spectral output).
+ *
+ * create_atmosphere and create_flux_file are here; write_output, close_flux_file, destroy_atmosphere and the text flux
+ * file are examples/driver_app_support.h, the column reader and the interpolation examples/example_support.h.
  */
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include "driver.h"
-#include "gas_optics.h"
-#include "grtcode_utilities.h"
+#define APP_NAME "driver_app"
+#include "driver_app_support.h"
 
-#define MAXV 201
-#define NSPEC 9
-
-struct Output
+static Column_t *read_usable_columns(char const *path, int *count)
 {
-    FILE *file;
-    int integrated, user_level, num_levels;
-    uint64_t n_lw, n_sw;
-};
-
-static char const *const species[NSPEC] = {"H2O", "CO2", "O3", "N2O", "CO", "CH4", "O2", "CFC11", "CFC12"};
-
-typedef struct Column
-{
-    int num_levels;
-    fp_t level_pressure[MAXV], level_temperature[MAXV], layer_pressure[MAXV], layer_temperature[MAXV];
-    fp_t surface_temperature, solar_zenith_angle, toa_solar_irradiance;
-    fp_t abundance[NSPEC][MAXV];
-    fp_t cloud_fraction[MAXV], liquid_water_content[MAXV], ice_water_content[MAXV];
-} Column_t;
-
-static void die(char const *what, char const *arg)
-{
-    fprintf(stderr, "driver_app: %s%s\n", what, arg ? arg : "");
-    exit(EXIT_FAILURE);
-}
-
-static int read_values(char *text, fp_t *dst, int max)
-{
-    int n = 0;
-    for (char *tok = strtok(text, " \t\r\n"); tok != NULL && n < max; tok = strtok(NULL, " \t\r\n"))
-    {
-        dst[n++] = atof(tok);
-    }
-    return n;
-}
-
-static Column_t *read_columns(char const *path, int *count)
-{
-    FILE *f = fopen(path, "r");
-    if (f == NULL)
+    Column_t *cols;
+    int const n = read_columns(path, 0, &cols);
+    if (n < 0)
     {
         die("cannot open column file ", path);
     }
-    Column_t *cols = NULL;
-    int n = 0;
-    static char line[1 << 16];
-    while (fgets(line, sizeof(line), f) != NULL)
-    {
-        char *colon = strchr(line, ':');
-        if (colon == NULL)
-        {
-            continue;
-        }
-        *colon = '\0';
-        char *vals = colon + 1;
-        if (strcmp(line, "column") == 0 || n == 0)
-        {
-            cols = realloc(cols, sizeof(*cols)*(size_t)(n + 1));
-            memset(&cols[n], 0, sizeof(*cols));
-            ++n;
-            if (strcmp(line, "column") == 0)
-            {
-                continue;
-            }
-        }
-        Column_t *c = &cols[n - 1];
-        if (strcmp(line, "level_pressure") == 0) c->num_levels = read_values(vals, c->level_pressure, MAXV);
-        else if (strcmp(line, "level_temperature") == 0) read_values(vals, c->level_temperature, MAXV);
-        else if (strcmp(line, "layer_pressure") == 0) read_values(vals, c->layer_pressure, MAXV);
-        else if (strcmp(line, "layer_temperature") == 0) read_values(vals, c->layer_temperature, MAXV);
-        else if (strcmp(line, "surface_temperature") == 0) read_values(vals, &c->surface_temperature, 1);
-        else if (strcmp(line, "solar_zenith_angle") == 0) read_values(vals, &c->solar_zenith_angle, 1);
-        else if (strcmp(line, "toa_solar_irradiance") == 0) read_values(vals, &c->toa_solar_irradiance, 1);
-        else if (strcmp(line, "cloud_fraction") == 0) read_values(vals, c->cloud_fraction, MAXV);
-        else if (strcmp(line, "liquid_water_content") == 0) read_values(vals, c->liquid_water_content, MAXV);
-        else if (strcmp(line, "ice_water_content") == 0) read_values(vals, c->ice_water_content, MAXV);
-        else
-        {
-            for (int k = 0; k < NSPEC; ++k)
-            {
-                if (strcmp(line, species[k]) == 0) read_values(vals, c->abundance[k], MAXV);
-            }
-        }
-    }
-    fclose(f);
     if (n == 0 || cols[0].num_levels < 2)
     {
         die("no usable column in ", path);
@@ -140,19 +64,28 @@ static Column_t *read_columns(char const *path, int *count)
     return cols;
 }
 
-/* circ/src/basic-circ-test.c:51-66 */
-static void pressure_interpolate(fp_t *ppmv, fp_t const *abundance, int num_layers, fp_t const *layer_pressure,
-                                 fp_t const *level_pressure)
+/* the abundance of a CIA species on the levels of the selected columns: N2 constant, O2 from the column file */
+typedef struct CiaCtx { Column_t const *cols; Atmosphere_t const *atm; } CiaCtx;
+
+static fp_t *cia_ppmv_of(int species, void *ctx)
 {
-    fp_t const to_ppmv = 1.e6;
-    ppmv[0] = abundance[0]*to_ppmv;
-    ppmv[num_layers] = abundance[num_layers - 1]*to_ppmv;
-    for (int i = 1; i < num_layers; ++i)
+    CiaCtx const *x = ctx;
+    Atmosphere_t const *atm = x->atm;
+    size_t const C = (size_t)atm->num_columns, V = (size_t)atm->num_levels, L = (size_t)atm->num_layers;
+    fp_t *ppmv = malloc(sizeof(fp_t)*C*V);
+    for (size_t c = 0; c < C; ++c)
     {
-        ppmv[i] = (abundance[i - 1] + (abundance[i] - abundance[i - 1])*
-                  (level_pressure[i] - layer_pressure[i - 1])/(layer_pressure[i] - layer_pressure[i - 1]));
-        ppmv[i] *= to_ppmv;
+        if (species == CIA_N2)
+        {
+            for (size_t l = 0; l < V; ++l) ppmv[c*V + l] = 0.781*1.e6;       /* basic-circ-test.c:272-275 */
+        }
+        else
+        {
+            layers_to_levels(ppmv + c*V, x->cols[atm->x + (int)c].abundance[6], atm->num_layers,
+                             atm->layer_pressure + c*L, atm->level_pressure + c*V);
+        }
     }
+    return ppmv;
 }
 
 Atmosphere_t create_atmosphere(Parser_t * const parser)
@@ -185,7 +118,7 @@ Atmosphere_t create_atmosphere(Parser_t * const parser)
     char buffer[valuelen];
     get_argument(*parser, "column_file", buffer);
     int total = 0;
-    Column_t *cols = read_columns(buffer, &total);
+    Column_t *cols = read_usable_columns(buffer, &total);
     int const x = get_argument(*parser, "-x", buffer) ? atoi(buffer) : 0;
     int const X = get_argument(*parser, "-X", buffer) ? atoi(buffer) : total - 1;
     if (x < 0 || X >= total || X < x)
@@ -271,197 +204,39 @@ Atmosphere_t create_atmosphere(Parser_t * const parser)
             fp_t *ppmv = atm.ppmv[atm.num_molecules] = malloc(sizeof(fp_t)*C*V);
             for (size_t c = 0; c < C; ++c)
             {
-                pressure_interpolate(ppmv + c*V, cols[x + (int)c].abundance[mols[i].spec], atm.num_layers,
-                                     atm.layer_pressure + c*L, atm.level_pressure + c*V);
+                layers_to_levels(ppmv + c*V, cols[x + (int)c].abundance[mols[i].spec], atm.num_layers,
+                                 atm.layer_pressure + c*L, atm.level_pressure + c*V);
             }
             atm.num_molecules++;
         }
     }
-    if (!get_argument(*parser, "-h2o-ctm", atm.h2o_ctm))
-    {
-        snprintf(atm.h2o_ctm, valuelen, "%s", "none");
-    }
-    if (!get_argument(*parser, "-o3-ctm", atm.o3_ctm))
-    {
-        snprintf(atm.o3_ctm, valuelen, "%s", "none");
-    }
-    static struct { int id; char const *flag; int spec; } const cfcs[2] = {{CFC11, "-CFC-11", 7}, {CFC12, "-CFC-12", 8}};
+    continua(parser, &atm);
     atm.cfc = malloc(sizeof(Cfc_t)*2);
     atm.cfc_ppmv = malloc(sizeof(fp_t *)*2);
     for (int i = 0; i < 2; ++i)
     {
-        if (get_argument(*parser, (char *)cfcs[i].flag, atm.cfc[atm.num_cfcs].path))
+        if (get_argument(*parser, cfc_flags[i].flag, atm.cfc[atm.num_cfcs].path))
         {
-            atm.cfc[atm.num_cfcs].id = cfcs[i].id;
+            atm.cfc[atm.num_cfcs].id = cfc_flags[i].id;
             fp_t *ppmv = atm.cfc_ppmv[atm.num_cfcs] = malloc(sizeof(fp_t)*C*V);
             for (size_t c = 0; c < C; ++c)
             {
-                pressure_interpolate(ppmv + c*V, cols[x + (int)c].abundance[cfcs[i].spec], atm.num_layers,
-                                     atm.layer_pressure + c*L, atm.level_pressure + c*V);
+                layers_to_levels(ppmv + c*V, cols[x + (int)c].abundance[cfc_flags[i].spec], atm.num_layers,
+                                 atm.layer_pressure + c*L, atm.level_pressure + c*V);
             }
             atm.num_cfcs++;
         }
     }
-    static struct { int s1, s2; char const *flag; } const cias[3] = {
-        {CIA_N2, CIA_N2, "-N2-N2"}, {CIA_O2, CIA_N2, "-O2-N2"}, {CIA_O2, CIA_O2, "-O2-O2"}};
-    atm.cia = malloc(sizeof(Cia_t)*3);
-    atm.cia_species = malloc(sizeof(int)*2);
-    atm.cia_ppmv = malloc(sizeof(fp_t *)*2);
-    for (int i = 0; i < 3; ++i)
-    {
-        if (!get_argument(*parser, (char *)cias[i].flag, atm.cia[atm.num_cias].path))
-        {
-            continue;
-        }
-        atm.cia[atm.num_cias].id[0] = cias[i].s1;
-        atm.cia[atm.num_cias].id[1] = cias[i].s2;
-        for (int j = 0; j < 2; ++j)
-        {
-            int const sp = atm.cia[atm.num_cias].id[j];
-            int k = 0;
-            while (k < atm.num_cia_species && atm.cia_species[k] != sp) ++k;
-            if (k < atm.num_cia_species)
-            {
-                continue;
-            }
-            atm.cia_species[atm.num_cia_species] = sp;
-            fp_t *ppmv = atm.cia_ppmv[atm.num_cia_species] = malloc(sizeof(fp_t)*C*V);
-            for (size_t c = 0; c < C; ++c)
-            {
-                if (sp == CIA_N2)
-                {
-                    for (size_t l = 0; l < V; ++l) ppmv[c*V + l] = 0.781*1.e6;       /* basic-circ-test.c:272-275 */
-                }
-                else
-                {
-                    pressure_interpolate(ppmv + c*V, cols[x + (int)c].abundance[6], atm.num_layers,
-                                         atm.layer_pressure + c*L, atm.level_pressure + c*V);
-                }
-            }
-            atm.num_cia_species++;
-        }
-        atm.num_cias++;
-    }
+    CiaCtx ctx = {cols, &atm};
+    add_cias(parser, &atm, cia_ppmv_of, &ctx);
     free(cols);
     return atm;
-}
-
-void destroy_atmosphere(Atmosphere_t *atm)
-{
-    free(atm->level_pressure); free(atm->level_temperature); free(atm->layer_pressure);
-    free(atm->layer_temperature); free(atm->surface_temperature); free(atm->solar_zenith_angle);
-    free(atm->total_solar_irradiance); free(atm->albedo_grid); free(atm->surface_albedo);
-    free(atm->emissivity_grid); free(atm->surface_emissivity);
-    free(atm->cloud_fraction); free(atm->liquid_water_content); free(atm->ice_water_content); free(atm->layer_thickness);
-    for (int i = 0; i < atm->num_molecules; ++i) free(atm->ppmv[i]);
-    for (int i = 0; i < atm->num_cfcs; ++i) free(atm->cfc_ppmv[i]);
-    for (int i = 0; i < atm->num_cia_species; ++i) free(atm->cia_ppmv[i]);
-    free(atm->molecules); free(atm->ppmv); free(atm->cfc); free(atm->cfc_ppmv);
-    free(atm->cia); free(atm->cia_species); free(atm->cia_ppmv);
-    memset(atm, 0, sizeof(*atm));
 }
 
 void create_flux_file(Output_t **output, char const * const path, Atmosphere_t const * const atm,
                       SpectralGrid_t const * const lw_grid, SpectralGrid_t const * const sw_grid,
                       int const user_level, int const integrated)
 {
-    Output_t *o = malloc(sizeof(*o));
-    o->file = fopen(path, "w");
-    if (o->file == NULL)
-    {
-        die("cannot create output file ", path);
-    }
-    o->integrated = integrated;
-    o->user_level = user_level;
-    o->num_levels = atm->num_levels;
-    o->n_lw = lw_grid->n;
-    o->n_sw = sw_grid->n;
-    fprintf(o->file, "# time column variable count values  (lw grid %g-%g @%g, sw grid %g-%g @%g, %s)\n",
-            lw_grid->w0, lw_grid->wn, lw_grid->dw, sw_grid->w0, sw_grid->wn, sw_grid->dw,
-            integrated ? "integrated [W m-2]" : "spectral [W m-2 cm]");
-    *output = o;
-}
-
-static char const *variable_name(Variables_t id)
-{
-    switch (id)
-    {
-        case RLUTCSAF: return "rlutcsaf";
-        case RLUSCSAF: return "rluscsaf";
-        case RLDSCSAF: return "rldscsaf";
-        case RLUCSAF_USER_LEVEL: return "rlucsaf_user_level";
-        case RLDCSAF_USER_LEVEL: return "rldcsaf_user_level";
-        case RSUTCSAF: return "rsutcsaf";
-        case RSUSCSAF: return "rsuscsaf";
-        case RSDTCSAF: return "rsdtcsaf";
-        case RSDSCSAF: return "rsdscsaf";
-        case RSUCSAF_USER_LEVEL: return "rsucsaf_user_level";
-        case RSDCSAF_USER_LEVEL: return "rsdcsaf_user_level";
-        case RLUTAF: return "rlutaf";
-        case RLUSAF: return "rlusaf";
-        case RLDSAF: return "rldsaf";
-        case RLUAF_USER_LEVEL: return "rluaf_user_level";
-        case RLDAF_USER_LEVEL: return "rldaf_user_level";
-        case RSUTAF: return "rsutaf";
-        case RSUSAF: return "rsusaf";
-        case RSDTAF: return "rsdtaf";
-        case RSDSAF: return "rsdsaf";
-        case RSUAF_USER_LEVEL: return "rsuaf_user_level";
-        case RSDAF_USER_LEVEL: return "rsdaf_user_level";
-        case RLUTCS: return "rlutcs";
-        case RLUSCS: return "rluscs";
-        case RLDSCS: return "rldscs";
-        case RLUCS_USER_LEVEL: return "rlucs_user_level";
-        case RLDCS_USER_LEVEL: return "rldcs_user_level";
-        case RSUTCS: return "rsutcs";
-        case RSUSCS: return "rsuscs";
-        case RSDTCS: return "rsdtcs";
-        case RSDSCS: return "rsdscs";
-        case RSUCS_USER_LEVEL: return "rsucs_user_level";
-        case RSDCS_USER_LEVEL: return "rsdcs_user_level";
-        case LEVEL_PRESSURE: return "level_pressure";
-        case LEVEL_TEMPERATURE: return "level_temperature";
-        case LAYER_TEMPERATURE: return "layer_temperature";
-        case SURFACE_TEMPERATURE: return "surface_temperature";
-        case H2O_VMR: return "h2o_vmr";
-        default: return NULL;      /* variables this application does not keep */
-    }
-}
-
-void write_output(Output_t *output, Variables_t id, fp_t const *data, int time, int column)
-{
-    char const *name = variable_name(id);
-    if (name == NULL || data == NULL)
-    {
-        return;
-    }
-    size_t count = 1;
-    if (is_longwave_flux(id))
-    {
-        count = output->integrated ? 1 : output->n_lw;
-    }
-    else if (is_shortwave_flux(id))
-    {
-        count = output->integrated ? 1 : output->n_sw;
-    }
-    else if (id == LEVEL_PRESSURE || id == LEVEL_TEMPERATURE || id == H2O_VMR)
-    {
-        count = (size_t)output->num_levels;
-    }
-    else if (id == LAYER_TEMPERATURE)
-    {
-        count = (size_t)output->num_levels - 1;
-    }
-    fprintf(output->file, "%d %d %s %zu", time, column, name, count);
-    for (size_t i = 0; i < count; ++i)
-    {
-        fprintf(output->file, " %.17g", data[i]);
-    }
-    fprintf(output->file, "\n");
-}
-
-void close_flux_file(Output_t * const output)
-{
-    fclose(output->file);
-    free(output);
+    (void)user_level;
+    open_flux_file(output, path, atm, lw_grid, sw_grid, integrated, 0, "");
 }

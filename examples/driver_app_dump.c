@@ -32,35 +32,18 @@
  * Output (-o PATH): text, one line per write_output call, "<time> <column> <variable> <count> v0 v1 ...", column being
  * the GLOBAL site (rfmip) / cell (era5: lat*nlon + lon of the selected block) index, so that shards written with
  * different -x/-X ranges merge by concatenation (the reference merges per-shard netCDF files the same way,
- * GRTworkflow/run-rfmip-irf.sh:134-148).
+ * GRTworkflow/run-rfmip-irf.sh:134-148).  The flux file, write_output, close_flux_file and destroy_atmosphere are
+ * examples/driver_app_support.h, shared with driver_app.c.
  */
 #include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include "driver.h"
-#include "gas_optics.h"
-#include "grtcode_utilities.h"
+#define APP_NAME "driver_app_dump"
+#include "driver_app_support.h"
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846
 #endif
 
-struct Output
-{
-    FILE *file;
-    int integrated, num_levels, column_offset;
-    uint64_t n_lw, n_sw;
-};
-
 static int g_column_offset = 0;     /* global index of the first column of this shard (create_atmosphere -> create_flux_file) */
-
-static void die(char const *what, char const *arg)
-{
-    fprintf(stderr, "driver_app_dump: %s%s\n", what, arg ? arg : "");
-    exit(EXIT_FAILURE);
-}
 
 /* ---- the dump container ---------------------------------------------------------------------------------------- */
 typedef struct DumpVar
@@ -210,40 +193,6 @@ static fp_t *filled(size_t n, fp_t value)
     return p;
 }
 
-typedef struct CiaFlag { int s1, s2; char *flag; } CiaFlag;
-static CiaFlag const cia_flags[3] = {{CIA_N2, CIA_N2, "-N2-N2"}, {CIA_O2, CIA_N2, "-O2-N2"}, {CIA_O2, CIA_O2, "-O2-O2"}};
-
-/* the CIA pairs asked for and the abundance of each species they involve: value_of(species) [ppmv], everywhere */
-static void add_cias(Parser_t *parser, Atmosphere_t *atm, size_t nvalues, fp_t (*value_of)(int species, void *ctx), void *ctx)
-{
-    atm->cia = malloc(sizeof(Cia_t)*3);
-    atm->cia_species = malloc(sizeof(int)*2);
-    atm->cia_ppmv = malloc(sizeof(fp_t *)*2);
-    atm->num_cias = atm->num_cia_species = 0;
-    for (int i = 0; i < 3; ++i)
-    {
-        Cia_t *c = &atm->cia[atm->num_cias];
-        if (!get_argument(*parser, cia_flags[i].flag, c->path))
-        {
-            continue;
-        }
-        c->id[0] = cia_flags[i].s1;
-        c->id[1] = cia_flags[i].s2;
-        for (int j = 0; j < 2; ++j)
-        {
-            int k = 0;
-            while (k < atm->num_cia_species && atm->cia_species[k] != c->id[j]) ++k;
-            if (k == atm->num_cia_species)
-            {
-                atm->cia_species[k] = c->id[j];
-                atm->cia_ppmv[k] = filled(nvalues, value_of(c->id[j], ctx));
-                atm->num_cia_species++;
-            }
-        }
-        atm->num_cias++;
-    }
-}
-
 static void common_arguments(Parser_t *parser)
 {
     int one = 1;
@@ -264,18 +213,6 @@ static void common_arguments(Parser_t *parser)
     add_argument(parser, "-O3", NULL, "Include O3.", NULL);
 }
 
-static void continua(Parser_t *parser, Atmosphere_t *atm)
-{
-    if (!get_argument(*parser, "-h2o-ctm", atm->h2o_ctm))
-    {
-        snprintf(atm->h2o_ctm, valuelen, "%s", "none");
-    }
-    if (!get_argument(*parser, "-o3-ctm", atm->o3_ctm))
-    {
-        snprintf(atm->o3_ctm, valuelen, "%s", "none");
-    }
-}
-
 /* ---- RFMIP-IRF --------------------------------------------------------------------------------------------------- */
 typedef struct GasFlag { int id; char *flag; char *variable; int global_mean; } GasFlag;
 
@@ -289,12 +226,12 @@ static fp_t global_mean_ppmv(Dump const *d, char const *variable, int experiment
     return gm*atof(v->units)*1.e6;
 }
 
-typedef struct RfmipCtx { Dump const *d; int experiment; } RfmipCtx;
+typedef struct RfmipCtx { Dump const *d; int experiment; size_t nvalues; } RfmipCtx;
 
-static fp_t rfmip_cia_value(int species, void *ctx)
+static fp_t *rfmip_cia_ppmv(int species, void *ctx)
 {
     RfmipCtx const *c = ctx;
-    return global_mean_ppmv(c->d, species == CIA_N2 ? "nitrogen_GM" : "oxygen_GM", c->experiment);
+    return filled(c->nvalues, global_mean_ppmv(c->d, species == CIA_N2 ? "nitrogen_GM" : "oxygen_GM", c->experiment));
 }
 
 static Atmosphere_t rfmip_atmosphere(Parser_t *parser)
@@ -415,17 +352,9 @@ static Atmosphere_t rfmip_atmosphere(Parser_t *parser)
             ppmv = fp_alloc(C*V);
             int64_t const start[3] = {experiment, x, z}, count[3] = {1, (int64_t)C, (int64_t)L};
             dump_read(&d, gases[g].variable, start, count, layer_vmr);
-            fp_t const to_ppmv = 1.e6;
             for (size_t c = 0; c < C; ++c)
             {
-                fp_t const *a = layer_vmr + c*L, *play = atm.layer_pressure + c*L, *plev = atm.level_pressure + c*V;
-                fp_t *out = ppmv + c*V;
-                out[0] = a[0]*to_ppmv;
-                out[V - 1] = a[L - 1]*to_ppmv;
-                for (size_t k = 1; k < L; ++k)
-                {
-                    out[k] = to_ppmv*(a[k - 1] + (a[k] - a[k - 1])*(plev[k] - play[k - 1])/(play[k] - play[k - 1]));
-                }
+                layers_to_levels(ppmv + c*V, layer_vmr + c*L, atm.num_layers, atm.layer_pressure + c*L, atm.level_pressure + c*V);
             }
         }
         atm.ppmv[atm.num_molecules++] = ppmv;
@@ -443,8 +372,8 @@ static Atmosphere_t rfmip_atmosphere(Parser_t *parser)
             atm.num_cfcs++;
         }
     }
-    RfmipCtx ctx = {&d, experiment};
-    add_cias(parser, &atm, C*V, rfmip_cia_value, &ctx);
+    RfmipCtx ctx = {&d, experiment, C*V};
+    add_cias(parser, &atm, rfmip_cia_ppmv, &ctx);
     dump_close(&d);
     return atm;
 }
@@ -462,10 +391,9 @@ static void levels_last(fp_t *dst, fp_t const *src, size_t nt, size_t nz, size_t
                 }
 }
 
-static fp_t era5_cia_value(int species, void *ctx)
+static fp_t *era5_cia_ppmv(int species, void *ctx)
 {
-    (void)ctx;
-    return (species == CIA_N2 ? 0.781 : 0.21)*1.e6;
+    return filled(*(size_t const *)ctx, (species == CIA_N2 ? 0.781 : 0.21)*1.e6);
 }
 
 static Atmosphere_t era5_atmosphere(Parser_t *parser)
@@ -620,7 +548,8 @@ static Atmosphere_t era5_atmosphere(Parser_t *parser)
         }
     }
     dump_close(&g);
-    add_cias(parser, &atm, cells*V, era5_cia_value, NULL);
+    size_t nvalues = cells*V;
+    add_cias(parser, &atm, era5_cia_ppmv, &nvalues);
     return atm;
 }
 
@@ -668,100 +597,12 @@ Atmosphere_t create_atmosphere(Parser_t * const parser)
     return none;
 }
 
-void destroy_atmosphere(Atmosphere_t *atm)
-{
-    free(atm->level_pressure); free(atm->level_temperature); free(atm->layer_pressure);
-    free(atm->layer_temperature); free(atm->surface_temperature); free(atm->solar_zenith_angle);
-    free(atm->total_solar_irradiance); free(atm->albedo_grid); free(atm->surface_albedo);
-    free(atm->emissivity_grid); free(atm->surface_emissivity);
-    for (int i = 0; i < atm->num_molecules; ++i) free(atm->ppmv[i]);
-    for (int i = 0; i < atm->num_cfcs; ++i) free(atm->cfc_ppmv[i]);
-    for (int i = 0; i < atm->num_cia_species; ++i) free(atm->cia_ppmv[i]);
-    free(atm->molecules); free(atm->ppmv); free(atm->cfc); free(atm->cfc_ppmv);
-    free(atm->cia); free(atm->cia_species); free(atm->cia_ppmv);
-    memset(atm, 0, sizeof(*atm));
-}
-
 void create_flux_file(Output_t **output, char const * const path, Atmosphere_t const * const atm,
                       SpectralGrid_t const * const lw_grid, SpectralGrid_t const * const sw_grid,
                       int const user_level, int const integrated)
 {
     (void)user_level;
-    Output_t *o = malloc(sizeof(*o));
-    o->file = fopen(path, "w");
-    if (o->file == NULL)
-    {
-        die("cannot create output file ", path);
-    }
-    o->integrated = integrated;
-    o->num_levels = atm->num_levels;
-    o->column_offset = g_column_offset;
-    o->n_lw = lw_grid->n;
-    o->n_sw = sw_grid->n;
-    fprintf(o->file, "# time column variable count values  (lw grid %g-%g @%g, sw grid %g-%g @%g, %s; columns %d..%d)\n",
-            lw_grid->w0, lw_grid->wn, lw_grid->dw, sw_grid->w0, sw_grid->wn, sw_grid->dw,
-            integrated ? "integrated [W m-2]" : "spectral [W m-2 cm]", g_column_offset, g_column_offset + atm->num_columns - 1);
-    *output = o;
-}
-
-static char const *variable_name(Variables_t id)
-{
-    switch (id)
-    {
-        case RLUTCSAF: return "rlutcsaf";
-        case RLUSCSAF: return "rluscsaf";
-        case RLDSCSAF: return "rldscsaf";
-        case RLUCSAF_USER_LEVEL: return "rlucsaf_user_level";
-        case RLDCSAF_USER_LEVEL: return "rldcsaf_user_level";
-        case RSUTCSAF: return "rsutcsaf";
-        case RSUSCSAF: return "rsuscsaf";
-        case RSDTCSAF: return "rsdtcsaf";
-        case RSDSCSAF: return "rsdscsaf";
-        case RSUCSAF_USER_LEVEL: return "rsucsaf_user_level";
-        case RSDCSAF_USER_LEVEL: return "rsdcsaf_user_level";
-        case LEVEL_PRESSURE: return "level_pressure";
-        case LEVEL_TEMPERATURE: return "level_temperature";
-        case LAYER_TEMPERATURE: return "layer_temperature";
-        case SURFACE_TEMPERATURE: return "surface_temperature";
-        case H2O_VMR: return "h2o_vmr";
-        default: return NULL;      /* (all-sky and aerosol passes do not run on these inputs) */
-    }
-}
-
-void write_output(Output_t *output, Variables_t id, fp_t const *data, int time, int column)
-{
-    char const *name = variable_name(id);
-    if (name == NULL || data == NULL)
-    {
-        return;
-    }
-    size_t count = 1;
-    if (is_longwave_flux(id))
-    {
-        count = output->integrated ? 1 : output->n_lw;
-    }
-    else if (is_shortwave_flux(id))
-    {
-        count = output->integrated ? 1 : output->n_sw;
-    }
-    else if (id == LEVEL_PRESSURE || id == LEVEL_TEMPERATURE || id == H2O_VMR)
-    {
-        count = (size_t)output->num_levels;
-    }
-    else if (id == LAYER_TEMPERATURE)
-    {
-        count = (size_t)output->num_levels - 1;
-    }
-    fprintf(output->file, "%d %d %s %zu", time, output->column_offset + column, name, count);
-    for (size_t i = 0; i < count; ++i)
-    {
-        fprintf(output->file, " %.17g", data[i]);
-    }
-    fprintf(output->file, "\n");
-}
-
-void close_flux_file(Output_t * const output)
-{
-    fclose(output->file);
-    free(output);
+    char columns[64];
+    snprintf(columns, sizeof(columns), "; columns %d..%d", g_column_offset, g_column_offset + atm->num_columns - 1);
+    open_flux_file(output, path, atm, lw_grid, sw_grid, integrated, g_column_offset, columns);
 }

@@ -38,6 +38,10 @@
  * one gather brings the flux blocks to rank 0, which prints all columns: ncclGather over xGMI (-transport rccl, the
  * default) or per-rank files in the rendezvous directory (-transport files: the reference's per-shard outputs +
  * combiner in one step; also how several ranks share one GPU in tests).
+ *
+ * Each kind of result (the 12 fluxes, -profiles rows, -bin-width rows) is one Kind entry below: its row length, its
+ * buffers and the function that runs a chunk.  Allocation, the per-chunk scatter, the gather and the frees loop over
+ * the entries, so a further kind is one more entry and its run function.
  */
 #include <math.h>
 #include <stdio.h>
@@ -60,26 +64,36 @@ static void fatal_signal(int sig)
 }
 #endif
 
-#define check(call) { int rc_ = (call); if (rc_ != GRTCODE_SUCCESS) { char b_[4096]; \
-    grtcode_errstr(rc_, b_, 4096); fprintf(stderr, "[%s:%d] %s\n", __FILE__, __LINE__, b_); return EXIT_FAILURE; } }
+#include "example_support.h"
 
-static char const *option(int argc, char **argv, char const *name, int skip)
-{
-    for (int i = 1; i + skip < argc; ++i)
-    {
-        if (strcmp(argv[i], name) == 0)
-        {
-            return argv[i + skip];
-        }
-    }
-    return NULL;
-}
+enum { FLUXES, PROFILES, BINS, NUM_KINDS };
 
-static double number(int argc, char **argv, char const *name, double fallback)
+/* what a run function needs besides its own kind */
+typedef struct Run
 {
-    char const *v = option(argc, argv, name, 1);
-    return v != NULL ? atof(v) : fallback;
-}
+    Device_t device;
+    int V, L, chunk;
+    SpectralGrid_t const *grids[2];             /* longwave, shortwave */
+    int *edges[2], nb[2];                       /* -bin-width: grid-point edges and bin counts of the two bands */
+    GrtPipeline_t *pipe[2];                     /* day, night */
+} Run;
+
+/* One kind of result: `row` doubles per column.  run() sends a chunk of m columns through the pipeline and leaves m rows
+ * in `host`, *stride doubles apart, of which the first *keep are this class's (day or night) to take. */
+typedef struct Kind
+{
+    char const *name;
+    int row, enabled;
+    size_t dev_doubles[3];                      /* per column, of the device buffers this kind needs (0: none) */
+    fp_t *dev[3], *host, *all;                  /* device buffers and host staging of a chunk; [columns][row] of the run */
+    int (*run)(struct Kind *kind, Run const *r, GrtColumns_t const *cols, int night, size_t *stride, size_t *keep);
+} Kind;
+
+/* the host arrays of GrtColumns_t, for all the columns of the file or for one chunk */
+typedef struct Columns
+{
+    double *p, *t, *tl, *ts, *mu, *tsi, *mol, *cfc, *cia;
+} Columns;
 
 /* -bin-width: grid-point edges every round(width/dw) points from 0, the last at n - 1; returns the bin count */
 static int bin_edges(SpectralGrid_t const *grid, double width, int **edges)
@@ -97,17 +111,317 @@ static int bin_edges(SpectralGrid_t const *grid, double width, int **edges)
     return nb;
 }
 
-/* rfmip-irf.c:295-308 */
-static void layers_to_levels(double *ppmv, double const *abundance, int num_layers, double const *layer_pressure,
-                             double const *level_pressure)
+/* ---- the three kinds ---------------------------------------------------------------------------------------------- */
+static int run_fluxes(Kind *k, Run const *r, GrtColumns_t const *cols, int night, size_t *stride, size_t *keep)
 {
-    double const to_ppmv = 1.e6;
-    ppmv[0] = abundance[0]*to_ppmv;
-    ppmv[num_layers] = abundance[num_layers - 1]*to_ppmv;
-    for (int k = 1; k < num_layers; ++k)
+    check(grt_pipeline_run(r->pipe[night], cols, k->dev[0]));
+    check(grt_pipeline_sync(r->pipe[night]));
+    check(grt_device_to_host(r->device, k->host, k->dev[0], sizeof(fp_t)*cols->ncol*GRT_FLUXES_PER_COLUMN));
+    *stride = GRT_FLUXES_PER_COLUMN;
+    *keep = night ? GRT_FLUXES_PER_BAND : GRT_FLUXES_PER_COLUMN;
+    return EXIT_SUCCESS;
+}
+
+/* per column the level fluxes [4][V] and then the heating rates [2][L]; the two come back in device buffers of their own
+ * (the night pipeline has no shortwave band: its shortwave rows come back zero) */
+static int run_profiles(Kind *k, Run const *r, GrtColumns_t const *cols, int night, size_t *stride, size_t *keep)
+{
+    int const m = cols->ncol;
+    size_t const nl = (size_t)GRT_PROFILE_ROWS_PER_COLUMN*r->V, nh = (size_t)GRT_HEATING_ROWS_PER_COLUMN*r->L;
+    fp_t *levels = k->host + (size_t)r->chunk*k->row, *heating = levels + (size_t)r->chunk*nl;
+    check(grt_pipeline_run_profiles(r->pipe[night], cols, k->dev[0], k->dev[1], NULL));
+    check(grt_pipeline_sync(r->pipe[night]));
+    check(grt_device_to_host(r->device, levels, k->dev[0], sizeof(fp_t)*m*nl));
+    check(grt_device_to_host(r->device, heating, k->dev[1], sizeof(fp_t)*m*nh));
+    for (int j = 0; j < m; ++j)
     {
-        ppmv[k] = to_ppmv*(abundance[k - 1] + (abundance[k] - abundance[k - 1])*
-                  (level_pressure[k] - layer_pressure[k - 1])/(layer_pressure[k] - layer_pressure[k - 1]));
+        memcpy(k->host + (size_t)j*k->row, levels + j*nl, sizeof(fp_t)*nl);
+        memcpy(k->host + (size_t)j*k->row + nl, heating + j*nh, sizeof(fp_t)*nh);
+    }
+    *stride = *keep = (size_t)k->row;
+    return EXIT_SUCCESS;
+}
+
+/* per column the longwave bins [6][nb_lw] and then the shortwave bins [6][nb_sw]
+ * (the night pipeline has no shortwave band: it takes no shortwave bins, its rows are shorter, and the rest stays zero) */
+static int run_bins(Kind *k, Run const *r, GrtColumns_t const *cols, int night, size_t *stride, size_t *keep)
+{
+    int const row = night ? 6*r->nb[0] : k->row;
+    check(grt_pipeline_run_spectral(r->pipe[night], cols, NULL, r->edges[0], r->nb[0], night ? NULL : r->edges[1],
+                                    night ? 0 : r->nb[1], k->dev[0], k->dev[1], k->dev[2]));
+    check(grt_pipeline_sync(r->pipe[night]));
+    check(grt_device_to_host(r->device, k->host, k->dev[1], sizeof(fp_t)*cols->ncol*row));
+    *stride = *keep = (size_t)row;
+    return EXIT_SUCCESS;
+}
+
+/* ---- the steps of main -------------------------------------------------------------------------------------------- */
+static double *read_dump(char const *path, int *ncol, int *V, double gm[5], size_t *per_col)
+{
+    FILE *f = fopen(path, "rb");
+    if (f == NULL)
+    {
+        fprintf(stderr, "cannot open %s\n", path);
+        return NULL;
+    }
+    int header[3];
+    if (fread(header, sizeof(int), 3, f) != 3 || header[0] != 0x47525443 || fread(gm, sizeof(double), 5, f) != 5)
+    {
+        fprintf(stderr, "%s is not a GRTC column dump\n", path);
+        return NULL;
+    }
+    *ncol = header[1];
+    *V = header[2];
+    int const L = *V - 1;
+    *per_col = (size_t)*V + L + *V + L + 5 + 2*(size_t)L;
+    double *raw = malloc(sizeof(double)**per_col**ncol);
+    if (fread(raw, sizeof(double), *per_col**ncol, f) != *per_col*(size_t)*ncol)
+    {
+        fprintf(stderr, "%s is truncated\n", path);
+        return NULL;
+    }
+    fclose(f);
+    return raw;
+}
+
+/* the longwave and the shortwave gas optics (driver.c:617-625, 193-211); the CFCs asked for and their ppmv */
+static int build_gas_optics(int argc, char **argv, GasOptics_t lbl[2], int V, SpectralGrid_t const *const grids[2],
+                            Device_t const *device, int *ncfc, double cfc_ppmv[2])
+{
+    int const method = line_sample, fast = (int)number(argc, argv, "-fast", 3.);
+    for (int b = 0; b < 2; ++b)
+    {
+        check(create_gas_optics(&lbl[b], V, grids[b], device, argv[1], option(argc, argv, "-h2o-ctm", 1),
+                                option(argc, argv, "-o3-ctm", 1), NULL, &method));
+        for (int k = 0; k < 7; ++k)
+        {
+            check(add_molecule(&lbl[b], hitran_id[k], NULL, NULL));
+        }
+        *ncfc = 0;
+        for (int k = 0; k < 2; ++k)
+        {
+            if (option(argc, argv, cfc_flags[k].flag, 1))
+            {
+                check(add_cfc(&lbl[b], cfc_flags[k].id, option(argc, argv, cfc_flags[k].flag, 1)));
+                cfc_ppmv[(*ncfc)++] = atof(option(argc, argv, cfc_flags[k].flag, 2));
+            }
+        }
+        for (int k = 0; k < 3; ++k)
+        {
+            if (option(argc, argv, cia_flags[k].flag, 1))
+            {
+                check(add_cia(&lbl[b], cia_flags[k].s1, cia_flags[k].s2, option(argc, argv, cia_flags[k].flag, 1)));
+            }
+        }
+        check(grt_gas_optics_tune(&lbl[b], 0, 0, fast));
+    }
+    return EXIT_SUCCESS;
+}
+
+static Columns alloc_columns(int n, int V)
+{
+    int const L = V - 1;
+    Columns c = {malloc(sizeof(double)*n*V), malloc(sizeof(double)*n*V), malloc(sizeof(double)*n*L),
+                 malloc(sizeof(double)*n), malloc(sizeof(double)*n), malloc(sizeof(double)*n),
+                 malloc(sizeof(double)*n*7*V), malloc(sizeof(double)*(n*2*V + 1)), malloc(sizeof(double)*n*NUM_CIAS*V)};
+    return c;
+}
+
+static void free_columns(Columns *c)
+{
+    free(c->p); free(c->t); free(c->tl); free(c->ts); free(c->mu); free(c->tsi); free(c->mol); free(c->cfc); free(c->cia);
+}
+
+/* the buffers of the enabled kinds: for a chunk on the device and on the host, for `rows` columns (all ranks' blocks) */
+static int allocate_kinds(Run const *r, Kind *kinds, size_t rows)
+{
+    for (Kind *k = kinds; k < kinds + NUM_KINDS; ++k)
+    {
+        if (!k->enabled) continue;
+        for (int d = 0; d < 3; ++d)
+        {
+            if (k->dev_doubles[d]) check(grt_device_malloc(r->device, (void **)&k->dev[d], sizeof(fp_t)*r->chunk*k->dev_doubles[d]));
+        }
+        /* (the profiles stage their two device buffers behind the chunk's rows: twice the rows) */
+        k->host = malloc(sizeof(fp_t)*r->chunk*k->row*2);
+        k->all = calloc(rows*k->row, sizeof(fp_t));
+    }
+    return EXIT_SUCCESS;
+}
+
+static int free_kinds(Run const *r, Kind *kinds)
+{
+    for (Kind *k = kinds; k < kinds + NUM_KINDS; ++k)
+    {
+        for (int d = 0; d < 3 && k->enabled; ++d)
+        {
+            if (k->dev_doubles[d]) check(grt_device_free(r->device, k->dev[d]));
+        }
+        free(k->host);
+        free(k->all);
+    }
+    return EXIT_SUCCESS;
+}
+
+/* raw columns -> the batched layout of GrtColumns_t; the surface values are the LAST column's (one value for the run,
+ * like the app's -e / -a) */
+static Columns prepare_columns(double const *raw, size_t per_col, int ncol, int V, double const gm[5], int ncfc,
+                               double const cfc_ppmv[2], double *emis_value, double *albedo_value)
+{
+    int const L = V - 1;
+    Columns a = alloc_columns(ncol, V);
+    double *pl = malloc(sizeof(double)*L);
+    for (int c = 0; c < ncol; ++c)
+    {
+        double const *r = raw + per_col*c;
+        double const *plev = r, *play = r + V, *tlev = play + L, *tlay = tlev + V, *scal = tlay + L;
+        double const *h2o = scal + 5, *o3 = h2o + L;
+        for (int k = 0; k < V; ++k)
+        {
+            a.p[c*V + k] = plev[k]*0.01;                            /* Pa -> mb (rfmip-irf.c:186) */
+            a.t[c*V + k] = tlev[k];
+        }
+        for (int k = 0; k < L; ++k)
+        {
+            pl[k] = play[k]*0.01;
+            a.tl[c*L + k] = tlay[k];
+        }
+        a.ts[c] = scal[0];
+        *emis_value = scal[1];
+        *albedo_value = scal[2];
+        a.mu[c] = cos(2.*M_PI*scal[3]/360.);
+        a.tsi[c] = scal[4];
+        double *m = a.mol + (size_t)c*7*V;
+        layers_to_levels(m + 0*V, h2o, L, pl, a.p + c*V);            /* rfmip-irf.c:295-308 */
+        layers_to_levels(m + 2*V, o3, L, pl, a.p + c*V);
+        int const gm_slot[5] = {1, 5, 3, 4, 6};                      /* CO2, CH4, N2O, CO, O2 in hitran_id order */
+        for (int g = 0; g < 5; ++g)
+        {
+            for (int k = 0; k < V; ++k)
+            {
+                m[gm_slot[g]*V + k] = gm[g]*1.e6;
+            }
+        }
+        for (int k = 0; k < V; ++k)
+        {
+            for (int j = 0; j < ncfc; ++j)
+            {
+                a.cfc[((size_t)c*ncfc + j)*V + k] = cfc_ppmv[j];
+            }
+            a.cia[((size_t)c*NUM_CIAS + CIA_N2)*V + k] = 0.781e6;
+            a.cia[((size_t)c*NUM_CIAS + CIA_O2)*V + k] = gm[4]*1.e6;
+        }
+    }
+    free(pl);
+    return a;
+}
+
+/* One class of this rank's columns (day or night; they go through different pipelines), in chunks that are contiguous
+ * in the class: gather the chunk's columns (they need not be adjacent in the file), run every kind, scatter its rows. */
+static int run_class(Run const *r, Kind *kinds, Columns const *a, Columns *c, int ncfc, int const *ids, int n, int night)
+{
+    int const V = r->V, L = r->L;
+    for (int first = 0; first < n; first += r->chunk)
+    {
+        int const m = n - first < r->chunk ? n - first : r->chunk;
+        for (int j = 0; j < m; ++j)
+        {
+            int const i = ids[first + j];
+            memcpy(c->p + j*V, a->p + i*V, sizeof(double)*V);
+            memcpy(c->t + j*V, a->t + i*V, sizeof(double)*V);
+            memcpy(c->tl + j*L, a->tl + i*L, sizeof(double)*L);
+            c->ts[j] = a->ts[i]; c->mu[j] = a->mu[i]; c->tsi[j] = a->tsi[i];
+            memcpy(c->mol + (size_t)j*7*V, a->mol + (size_t)i*7*V, sizeof(double)*7*V);
+            memcpy(c->cfc + (size_t)j*ncfc*V, a->cfc + (size_t)i*ncfc*V, sizeof(double)*ncfc*V);
+            memcpy(c->cia + (size_t)j*NUM_CIAS*V, a->cia + (size_t)i*NUM_CIAS*V, sizeof(double)*NUM_CIAS*V);
+        }
+        GrtColumns_t cols = {m, V, c->p, c->t, c->tl, c->ts, c->mol, ncfc ? c->cfc : NULL, c->cia, c->mu, c->tsi};
+        for (Kind *k = kinds; k < kinds + NUM_KINDS; ++k)
+        {
+            if (!k->enabled) continue;
+            size_t stride = 0, keep = 0;
+            if (k->run(k, r, &cols, night, &stride, &keep)) return EXIT_FAILURE;
+            for (int j = 0; j < m; ++j)
+            {
+                memcpy(k->all + (size_t)ids[first + j]*k->row, k->host + j*stride, sizeof(fp_t)*keep);
+            }
+        }
+    }
+    return EXIT_SUCCESS;
+}
+
+/* one gather per kind of this rank's block of rows to rank 0: between host buffers with the file transport,
+ * between device buffers, on the library stream, with RCCL */
+static int gather(Run const *r, Kind *kinds, GrtMulti_t *multi, int files, int ncol, int rank, int world, int shard_first,
+                  int shard_count)
+{
+    size_t const per_rank = (size_t)((ncol + world - 1)/world);
+    for (Kind *k = kinds; k < kinds + NUM_KINDS; ++k)
+    {
+        if (!k->enabled) continue;
+        size_t const block = sizeof(fp_t)*per_rank*k->row, mine = sizeof(fp_t)*(size_t)shard_count*k->row;
+        fp_t *local = k->all + (size_t)shard_first*k->row, *all = NULL;
+        if (files)
+        {
+            all = rank == 0 ? calloc(per_rank*world*k->row, sizeof(fp_t)) : NULL;
+        }
+        else
+        {
+            fp_t *host = local;
+            local = NULL;
+            check(grt_device_malloc(r->device, (void **)&local, block));
+            if (rank == 0) check(grt_device_malloc(r->device, (void **)&all, block*world));
+            if (shard_count > 0) check(grt_host_to_device(r->device, local, host, mine));
+        }
+        check(grt_multi_gather_rows(multi, local, ncol, k->row, all, !files));
+        if (files)
+        {
+            if (rank == 0) memcpy(k->all, all, sizeof(fp_t)*(size_t)ncol*k->row);
+            free(all);
+        }
+        else
+        {
+            check(grt_pipeline_sync(r->pipe[0]));          /* the gather runs on the library stream */
+            if (rank == 0) check(grt_device_to_host(r->device, k->all, all, sizeof(fp_t)*(size_t)ncol*k->row));
+            check(grt_device_free(r->device, local));
+            check(grt_device_free(r->device, all));
+        }
+    }
+    return EXIT_SUCCESS;
+}
+
+static void print_columns(Run const *r, Kind const *kinds, int ncol)
+{
+    int const V = r->V, L = r->L;
+    for (int c = 0; c < ncol; ++c)
+    {
+        fp_t const *x = kinds[FLUXES].all + (size_t)c*GRT_FLUXES_PER_COLUMN;
+        printf("col %d: %.15e %.15e %.15e %.15e %.15e %.15e %.15e %.15e\n", c, x[0], x[1], x[3], x[4], x[6], x[7], x[9], x[10]);
+        for (int band = 0; band < 2 && kinds[BINS].enabled; ++band)
+        {
+            /* the band's six rows [6][nb] of this column: up TOA, up surface, up user, down TOA, down surface, down user */
+            int const nb = r->nb[band];
+            fp_t const *row = kinds[BINS].all + (size_t)c*kinds[BINS].row + (band ? 6*r->nb[0] : 0);
+            SpectralGrid_t const *g = r->grids[band];
+            for (int b = 0; b < nb; ++b)
+            {
+                printf("%s %d: %.15e %.15e %.15e %.15e %.15e %.15e\n", band ? "swbin" : "lwbin", b,
+                       g->w0 + r->edges[band][b]*g->dw, g->w0 + r->edges[band][b + 1]*g->dw, row[b], row[nb + b],
+                       row[3*nb + b], row[4*nb + b]);
+            }
+        }
+        if (kinds[PROFILES].enabled)
+        {
+            fp_t const *row = kinds[PROFILES].all + (size_t)c*kinds[PROFILES].row, *h = row + GRT_PROFILE_ROWS_PER_COLUMN*V;
+            for (int k = 0; k < V; ++k)
+            {
+                printf("lev %d: %.15e %.15e %.15e %.15e\n", k, row[k], row[V + k], row[2*V + k], row[3*V + k]);
+            }
+            for (int j = 0; j < L; ++j)
+            {
+                printf("lay %d: %.15e %.15e\n", j, h[j], h[L + j]);
+            }
+        }
     }
 }
 
@@ -124,30 +438,17 @@ int main(int argc, char **argv)
         fprintf(stderr, "usage: %s HITRAN.par SOLAR.csv COLUMNS.bin [options]\n", argv[0]);
         return EXIT_FAILURE;
     }
-    FILE *f = fopen(argv[3], "rb");
-    if (f == NULL)
-    {
-        fprintf(stderr, "cannot open %s\n", argv[3]);
-        return EXIT_FAILURE;
-    }
-    int header[3];
+    int ncol, V;
     double gm[5];
-    if (fread(header, sizeof(int), 3, f) != 3 || header[0] != 0x47525443 || fread(gm, sizeof(double), 5, f) != 5)
+    size_t per_col;
+    double *raw = read_dump(argv[3], &ncol, &V, gm, &per_col);
+    if (raw == NULL)
     {
-        fprintf(stderr, "%s is not a GRTC column dump\n", argv[3]);
         return EXIT_FAILURE;
     }
-    int const ncol = header[1], V = header[2], L = V - 1;
-    size_t const per_col = (size_t)V + L + V + L + 5 + 2*(size_t)L;
-    double *raw = malloc(sizeof(double)*per_col*ncol);
-    if (fread(raw, sizeof(double), per_col*ncol, f) != per_col*(size_t)ncol)
-    {
-        fprintf(stderr, "%s is truncated\n", argv[3]);
-        return EXIT_FAILURE;
-    }
-    fclose(f);
+    int const L = V - 1;
 
-    /* grids, device, gas optics (driver.c:912-931, 617-625, 193-211) */
+    /* grids, device, gas optics (driver.c:912-931) */
     SpectralGrid_t lw_grid, sw_grid;
     check(create_spectral_grid(&lw_grid, number(argc, argv, "-w-lw", 1.), number(argc, argv, "-W-lw", 3250.),
                                number(argc, argv, "-r-lw", 1.)));
@@ -156,353 +457,100 @@ int main(int argc, char **argv)
     Device_t device;
     int dev_id = (int)number(argc, argv, "-d", 0.);
     check(create_device(&device, option(argc, argv, "-d", 1) ? &dev_id : NULL));
-    int const method = line_sample, fast = (int)number(argc, argv, "-fast", 3.);
-    int const mol_ids[7] = {H2O, CO2, O3, N2O, CO, CH4, O2};
-    char const *cfc_flag[2] = {"-CFC-11", "-CFC-12"};
-    int const cfc_id[2] = {CFC11, CFC12};
-    char const *cia_flag[3] = {"-N2-N2", "-O2-N2", "-O2-O2"};
-    int const cia_pair[3][2] = {{CIA_N2, CIA_N2}, {CIA_O2, CIA_N2}, {CIA_O2, CIA_O2}};
+    Run r = {.device = device, .V = V, .L = L, .chunk = (int)number(argc, argv, "-chunk", 16.), .grids = {&lw_grid, &sw_grid}};
     GasOptics_t lbl[2];
-    SpectralGrid_t const *grids[2] = {&lw_grid, &sw_grid};
     int ncfc = 0;
     double cfc_ppmv[2] = {0., 0.};
-    for (int b = 0; b < 2; ++b)
+    if (build_gas_optics(argc, argv, lbl, V, r.grids, &device, &ncfc, cfc_ppmv))
     {
-        check(create_gas_optics(&lbl[b], V, grids[b], &device, argv[1], option(argc, argv, "-h2o-ctm", 1),
-                                option(argc, argv, "-o3-ctm", 1), NULL, &method));
-        for (int k = 0; k < 7; ++k)
-        {
-            check(add_molecule(&lbl[b], mol_ids[k], NULL, NULL));
-        }
-        ncfc = 0;
-        for (int k = 0; k < 2; ++k)
-        {
-            if (option(argc, argv, cfc_flag[k], 1))
-            {
-                check(add_cfc(&lbl[b], cfc_id[k], option(argc, argv, cfc_flag[k], 1)));
-                cfc_ppmv[ncfc++] = atof(option(argc, argv, cfc_flag[k], 2));
-            }
-        }
-        for (int k = 0; k < 3; ++k)
-        {
-            if (option(argc, argv, cia_flag[k], 1))
-            {
-                check(add_cia(&lbl[b], cia_pair[k][0], cia_pair[k][1], option(argc, argv, cia_flag[k], 1)));
-            }
-        }
-        check(grt_gas_optics_tune(&lbl[b], 0, 0, fast));
+        return EXIT_FAILURE;
     }
     SolarFlux_t solar;
     check(create_solar_flux(&solar, &sw_grid, argv[2]));
 
-    /* columns -> the batched layout of GrtColumns_t */
-    int const chunk = (int)number(argc, argv, "-chunk", 16.);
-    double *p = malloc(sizeof(double)*ncol*V), *t = malloc(sizeof(double)*ncol*V), *tl = malloc(sizeof(double)*ncol*L);
-    double *ts = malloc(sizeof(double)*ncol), *mu = malloc(sizeof(double)*ncol), *tsi = malloc(sizeof(double)*ncol);
-    double *mol = malloc(sizeof(double)*ncol*7*V), *cfc = malloc(sizeof(double)*ncol*2*V);
-    double *cia = malloc(sizeof(double)*ncol*NUM_CIAS*V);
     double emis_value = 0., albedo_value = 0.;
-    double *pl = malloc(sizeof(double)*L);
-    for (int c = 0; c < ncol; ++c)
-    {
-        double const *r = raw + per_col*c;
-        double const *plev = r, *play = r + V, *tlev = play + L, *tlay = tlev + V, *scal = tlay + L;
-        double const *h2o = scal + 5, *o3 = h2o + L;
-        for (int k = 0; k < V; ++k)
-        {
-            p[c*V + k] = plev[k]*0.01;                              /* Pa -> mb (rfmip-irf.c:186) */
-            t[c*V + k] = tlev[k];
-        }
-        for (int k = 0; k < L; ++k)
-        {
-            pl[k] = play[k]*0.01;
-            tl[c*L + k] = tlay[k];
-        }
-        ts[c] = scal[0];
-        emis_value = scal[1];                                       /* one value for the run, like the app's -e / -a */
-        albedo_value = scal[2];
-        mu[c] = cos(2.*M_PI*scal[3]/360.);
-        tsi[c] = scal[4];
-        double *m = mol + (size_t)c*7*V;
-        layers_to_levels(m + 0*V, h2o, L, pl, p + c*V);
-        layers_to_levels(m + 2*V, o3, L, pl, p + c*V);
-        int const gm_slot[5] = {1, 5, 3, 4, 6};                      /* CO2, CH4, N2O, CO, O2 in mol_ids order */
-        for (int g = 0; g < 5; ++g)
-        {
-            for (int k = 0; k < V; ++k)
-            {
-                m[gm_slot[g]*V + k] = gm[g]*1.e6;
-            }
-        }
-        for (int k = 0; k < V; ++k)
-        {
-            for (int j = 0; j < ncfc; ++j)
-            {
-                cfc[((size_t)c*ncfc + j)*V + k] = cfc_ppmv[j];
-            }
-            cia[((size_t)c*NUM_CIAS + CIA_N2)*V + k] = 0.781e6;
-            cia[((size_t)c*NUM_CIAS + CIA_O2)*V + k] = gm[4]*1.e6;
-        }
-    }
+    Columns all = prepare_columns(raw, per_col, ncol, V, gm, ncfc, cfc_ppmv, &emis_value, &albedo_value);
+    free(raw);
+    Columns part = alloc_columns(r.chunk, V);
     fp_t *emissivity = malloc(sizeof(fp_t)*lw_grid.n), *albedo = malloc(sizeof(fp_t)*sw_grid.n);
     for (uint64_t i = 0; i < lw_grid.n; ++i) emissivity[i] = emis_value;
     for (uint64_t i = 0; i < sw_grid.n; ++i) albedo[i] = albedo_value;
+    check(grt_pipeline_create(&r.pipe[0], &lbl[0], &lbl[1], r.chunk, -1, emissivity, albedo, solar.incident_flux));
+    check(grt_pipeline_create(&r.pipe[1], &lbl[0], NULL, r.chunk, -1, emissivity, NULL, NULL));
 
-    GrtPipeline_t *pipe_day, *pipe_night;
-    check(grt_pipeline_create(&pipe_day, &lbl[0], &lbl[1], chunk, -1, emissivity, albedo, solar.incident_flux));
-    check(grt_pipeline_create(&pipe_night, &lbl[0], NULL, chunk, -1, emissivity, NULL, NULL));
-    fp_t *fluxes_dev;
-    check(grt_device_malloc(device, (void **)&fluxes_dev, sizeof(fp_t)*chunk*GRT_FLUXES_PER_COLUMN));
-    /* -profiles: per column a row of the level fluxes [4][V] and then the heating rates [2][L] */
-    int const profiles = option(argc, argv, "-profiles", 0) != NULL;
-    int const prow = GRT_PROFILE_ROWS_PER_COLUMN*V + GRT_HEATING_ROWS_PER_COLUMN*L;
-    fp_t *levels_dev = NULL, *heating_dev = NULL;
-    if (profiles)
-    {
-        check(grt_device_malloc(device, (void **)&levels_dev, sizeof(fp_t)*chunk*GRT_PROFILE_ROWS_PER_COLUMN*V));
-        check(grt_device_malloc(device, (void **)&heating_dev, sizeof(fp_t)*chunk*GRT_HEATING_ROWS_PER_COLUMN*L));
-    }
-    /* -bin-width: per column a row of the longwave bins [6][nb_lw] and then the shortwave bins [6][nb_sw] */
+    /* the kinds of result: the 12 fluxes always, -profiles and -bin-width on request */
     double const bin_width = number(argc, argv, "-bin-width", 0.);
-    int const bins = bin_width > 0.;
-    int *edges[2] = {NULL, NULL}, nb[2] = {0, 0};
-    fp_t *spectral_dev = NULL, *binned_dev = NULL, *spectral_fluxes_dev = NULL;
-    if (bins)
+    for (int b = 0; b < 2 && bin_width > 0.; ++b)
     {
-        for (int b = 0; b < 2; ++b)
-        {
-            nb[b] = bin_edges(grids[b], bin_width, &edges[b]);
-        }
-        check(grt_device_malloc(device, (void **)&spectral_dev, sizeof(fp_t)*chunk*6*(lw_grid.n + sw_grid.n)));
-        check(grt_device_malloc(device, (void **)&binned_dev, sizeof(fp_t)*chunk*6*(nb[0] + nb[1])));
-        check(grt_device_malloc(device, (void **)&spectral_fluxes_dev, sizeof(fp_t)*chunk*GRT_FLUXES_PER_COLUMN));
+        r.nb[b] = bin_edges(r.grids[b], bin_width, &r.edges[b]);
     }
-    int const brow = 6*(nb[0] + nb[1]);
+    size_t const nl = (size_t)GRT_PROFILE_ROWS_PER_COLUMN*V, nh = (size_t)GRT_HEATING_ROWS_PER_COLUMN*L;
+    Kind kinds[NUM_KINDS] = {
+        [FLUXES] = {"fluxes", GRT_FLUXES_PER_COLUMN, 1, {GRT_FLUXES_PER_COLUMN}, .run = run_fluxes},
+        [PROFILES] = {"profiles", (int)(nl + nh), option(argc, argv, "-profiles", 0) != NULL, {nl, nh}, .run = run_profiles},
+        [BINS] = {"bins", 6*(r.nb[0] + r.nb[1]), bin_width > 0.,
+                  {6*(lw_grid.n + sw_grid.n), 6*(size_t)(r.nb[0] + r.nb[1]), GRT_FLUXES_PER_COLUMN}, .run = run_bins}};
+
     /* this rank's block of the columns */
     int const world = (int)number(argc, argv, "-ranks", 1.), rank = (int)number(argc, argv, "-rank", 0.);
+    char const *tr = option(argc, argv, "-transport", 1);
+    int const files = tr != NULL && strcmp(tr, "files") == 0;
     int shard_first = 0, shard_count = ncol;
     GrtMulti_t *multi = NULL;
     if (world > 1)
     {
-        char const *dir = option(argc, argv, "-rendezvous", 1), *tr = option(argc, argv, "-transport", 1);
+        char const *dir = option(argc, argv, "-rendezvous", 1);
         if (dir == NULL)
         {
             fprintf(stderr, "-ranks needs -rendezvous DIR\n");
             return EXIT_FAILURE;
         }
-        check(grt_multi_create(&multi, tr != NULL && strcmp(tr, "files") == 0 ? GRT_MULTI_FILES : GRT_MULTI_RCCL, device,
-                               rank, world, dir));
+        check(grt_multi_create(&multi, files ? GRT_MULTI_FILES : GRT_MULTI_RCCL, device, rank, world, dir));
         check(grt_multi_shard(ncol, rank, world, &shard_first, &shard_count));
     }
-    int const per_rank = (ncol + world - 1)/world;
-    fp_t *fluxes = calloc((size_t)per_rank*world*GRT_FLUXES_PER_COLUMN, sizeof(fp_t));
-    fp_t *host = malloc(sizeof(fp_t)*chunk*GRT_FLUXES_PER_COLUMN);
-    fp_t *profile = profiles ? calloc((size_t)per_rank*world*prow, sizeof(fp_t)) : NULL;
-    fp_t *host_levels = profiles ? malloc(sizeof(fp_t)*chunk*GRT_PROFILE_ROWS_PER_COLUMN*V) : NULL;
-    fp_t *host_heating = profiles ? malloc(sizeof(fp_t)*chunk*GRT_HEATING_ROWS_PER_COLUMN*L) : NULL;
-    fp_t *binned = bins ? calloc((size_t)per_rank*world*brow, sizeof(fp_t)) : NULL;
-    fp_t *host_bins = bins ? malloc(sizeof(fp_t)*chunk*brow) : NULL;
-    /* day and night columns go through different pipelines; keep chunks contiguous in each class */
+    if (allocate_kinds(&r, kinds, (size_t)((ncol + world - 1)/world)*world))
+    {
+        return EXIT_FAILURE;
+    }
+
+    int *ids = malloc(sizeof(int)*ncol);
     for (int night = 0; night < 2; ++night)
     {
-        int *ids = malloc(sizeof(int)*ncol), n = 0;
-        for (int c = 0; c < ncol; ++c)
+        int n = 0;
+        for (int c = shard_first; c < shard_first + shard_count; ++c)
         {
-            if (c >= shard_first && c < shard_first + shard_count && (mu[c] <= 0.) == (night == 1)) ids[n++] = c;
+            if ((all.mu[c] <= 0.) == (night == 1)) ids[n++] = c;
         }
-        for (int first = 0; first < n; first += chunk)
+        if (run_class(&r, kinds, &all, &part, ncfc, ids, n, night))
         {
-            int const m = n - first < chunk ? n - first : chunk;
-            /* gather the chunk's columns (they need not be adjacent in the file) */
-            double *cp = malloc(sizeof(double)*m*V), *ct = malloc(sizeof(double)*m*V), *ctl = malloc(sizeof(double)*m*L);
-            double *cts = malloc(sizeof(double)*m), *cmu = malloc(sizeof(double)*m), *ctsi = malloc(sizeof(double)*m);
-            double *cmol = malloc(sizeof(double)*m*7*V), *ccfc = malloc(sizeof(double)*(m*2*V + 1));
-            double *ccia = malloc(sizeof(double)*m*NUM_CIAS*V);
-            for (int j = 0; j < m; ++j)
-            {
-                int const c = ids[first + j];
-                memcpy(cp + j*V, p + c*V, sizeof(double)*V);
-                memcpy(ct + j*V, t + c*V, sizeof(double)*V);
-                memcpy(ctl + j*L, tl + c*L, sizeof(double)*L);
-                cts[j] = ts[c]; cmu[j] = mu[c]; ctsi[j] = tsi[c];
-                memcpy(cmol + (size_t)j*7*V, mol + (size_t)c*7*V, sizeof(double)*7*V);
-                memcpy(ccfc + (size_t)j*ncfc*V, cfc + (size_t)c*ncfc*V, sizeof(double)*ncfc*V);
-                memcpy(ccia + (size_t)j*NUM_CIAS*V, cia + (size_t)c*NUM_CIAS*V, sizeof(double)*NUM_CIAS*V);
-            }
-            GrtColumns_t cols = {m, V, cp, ct, ctl, cts, cmol, ncfc ? ccfc : NULL, ccia, cmu, ctsi};
-            GrtPipeline_t *pipe = night ? pipe_night : pipe_day;
-            check(grt_pipeline_run(pipe, &cols, fluxes_dev));
-            check(grt_pipeline_sync(pipe));
-            check(grt_device_to_host(device, host, fluxes_dev, sizeof(fp_t)*m*GRT_FLUXES_PER_COLUMN));
-            for (int j = 0; j < m; ++j)
-            {
-                memcpy(fluxes + (size_t)ids[first + j]*GRT_FLUXES_PER_COLUMN, host + (size_t)j*GRT_FLUXES_PER_COLUMN,
-                       sizeof(fp_t)*(night ? GRT_FLUXES_PER_BAND : GRT_FLUXES_PER_COLUMN));
-            }
-            if (profiles)
-            {
-                /* (the night pipeline has no shortwave band: its shortwave rows come back zero) */
-                size_t const nl = (size_t)GRT_PROFILE_ROWS_PER_COLUMN*V, nh = (size_t)GRT_HEATING_ROWS_PER_COLUMN*L;
-                check(grt_pipeline_run_profiles(pipe, &cols, levels_dev, heating_dev, NULL));
-                check(grt_pipeline_sync(pipe));
-                check(grt_device_to_host(device, host_levels, levels_dev, sizeof(fp_t)*m*nl));
-                check(grt_device_to_host(device, host_heating, heating_dev, sizeof(fp_t)*m*nh));
-                for (int j = 0; j < m; ++j)
-                {
-                    fp_t *row = profile + (size_t)ids[first + j]*prow;
-                    memcpy(row, host_levels + j*nl, sizeof(fp_t)*nl);
-                    memcpy(row + nl, host_heating + j*nh, sizeof(fp_t)*nh);
-                }
-            }
-            if (bins)
-            {
-                /* (the night pipeline has no shortwave band: it takes no shortwave bins, and they stay zero) */
-                int const row = night ? 6*nb[0] : brow;
-                check(grt_pipeline_run_spectral(pipe, &cols, NULL, edges[0], nb[0], night ? NULL : edges[1],
-                                                night ? 0 : nb[1], spectral_dev, binned_dev, spectral_fluxes_dev));
-                check(grt_pipeline_sync(pipe));
-                check(grt_device_to_host(device, host_bins, binned_dev, sizeof(fp_t)*m*row));
-                for (int j = 0; j < m; ++j)
-                {
-                    memcpy(binned + (size_t)ids[first + j]*brow, host_bins + (size_t)j*row, sizeof(fp_t)*row);
-                }
-            }
-            free(cp); free(ct); free(ctl); free(cts); free(cmu); free(ctsi); free(cmol); free(ccfc); free(ccia);
+            return EXIT_FAILURE;
         }
-        free(ids);
     }
+    free(ids);
+    free_columns(&part);
+    free_columns(&all);
     if (multi != NULL)
     {
-        /* one gather of the [columns][12] blocks to rank 0 */
-        fp_t *local = fluxes + (size_t)shard_first*GRT_FLUXES_PER_COLUMN;
-        char const *tr = option(argc, argv, "-transport", 1);
-        if (tr != NULL && strcmp(tr, "files") == 0)
+        if (gather(&r, kinds, multi, files, ncol, rank, world, shard_first, shard_count))
         {
-            fp_t *all = rank == 0 ? calloc((size_t)per_rank*world*GRT_FLUXES_PER_COLUMN, sizeof(fp_t)) : NULL;
-            check(grt_multi_gather_fluxes(multi, local, ncol, all, 0));
-            if (rank == 0)
-            {
-                memcpy(fluxes, all, sizeof(fp_t)*(size_t)ncol*GRT_FLUXES_PER_COLUMN);
-                free(all);
-            }
-            if (profiles)
-            {
-                fp_t *all_rows = rank == 0 ? calloc((size_t)per_rank*world*prow, sizeof(fp_t)) : NULL;
-                check(grt_multi_gather_rows(multi, profile + (size_t)shard_first*prow, ncol, prow, all_rows, 0));
-                if (rank == 0)
-                {
-                    memcpy(profile, all_rows, sizeof(fp_t)*(size_t)ncol*prow);
-                    free(all_rows);
-                }
-            }
-            if (bins)
-            {
-                fp_t *all_rows = rank == 0 ? calloc((size_t)per_rank*world*brow, sizeof(fp_t)) : NULL;
-                check(grt_multi_gather_rows(multi, binned + (size_t)shard_first*brow, ncol, brow, all_rows, 0));
-                if (rank == 0)
-                {
-                    memcpy(binned, all_rows, sizeof(fp_t)*(size_t)ncol*brow);
-                    free(all_rows);
-                }
-            }
-        }
-        else
-        {
-            size_t const block = sizeof(fp_t)*(size_t)per_rank*GRT_FLUXES_PER_COLUMN;
-            fp_t *local_dev = NULL, *all_dev = NULL;
-            check(grt_device_malloc(device, (void **)&local_dev, block));
-            if (rank == 0) check(grt_device_malloc(device, (void **)&all_dev, block*world));
-            if (shard_count > 0) check(grt_host_to_device(device, local_dev, local, sizeof(fp_t)*(size_t)shard_count*GRT_FLUXES_PER_COLUMN));
-            check(grt_multi_gather_fluxes(multi, local_dev, ncol, all_dev, 1));
-            check(grt_pipeline_sync(pipe_day));            /* the gather runs on the library stream */
-            if (rank == 0) check(grt_device_to_host(device, fluxes, all_dev, sizeof(fp_t)*(size_t)ncol*GRT_FLUXES_PER_COLUMN));
-            check(grt_device_free(device, local_dev));
-            check(grt_device_free(device, all_dev));
-            if (profiles)
-            {
-                size_t const rows = sizeof(fp_t)*(size_t)per_rank*prow;
-                local_dev = NULL;
-                all_dev = NULL;
-                check(grt_device_malloc(device, (void **)&local_dev, rows));
-                if (rank == 0) check(grt_device_malloc(device, (void **)&all_dev, rows*world));
-                if (shard_count > 0) check(grt_host_to_device(device, local_dev, profile + (size_t)shard_first*prow,
-                                                              sizeof(fp_t)*(size_t)shard_count*prow));
-                check(grt_multi_gather_rows(multi, local_dev, ncol, prow, all_dev, 1));
-                check(grt_pipeline_sync(pipe_day));
-                if (rank == 0) check(grt_device_to_host(device, profile, all_dev, sizeof(fp_t)*(size_t)ncol*prow));
-                check(grt_device_free(device, local_dev));
-                check(grt_device_free(device, all_dev));
-            }
-            if (bins)
-            {
-                size_t const rows = sizeof(fp_t)*(size_t)per_rank*brow;
-                local_dev = NULL;
-                all_dev = NULL;
-                check(grt_device_malloc(device, (void **)&local_dev, rows));
-                if (rank == 0) check(grt_device_malloc(device, (void **)&all_dev, rows*world));
-                if (shard_count > 0) check(grt_host_to_device(device, local_dev, binned + (size_t)shard_first*brow,
-                                                              sizeof(fp_t)*(size_t)shard_count*brow));
-                check(grt_multi_gather_rows(multi, local_dev, ncol, brow, all_dev, 1));
-                check(grt_pipeline_sync(pipe_day));
-                if (rank == 0) check(grt_device_to_host(device, binned, all_dev, sizeof(fp_t)*(size_t)ncol*brow));
-                check(grt_device_free(device, local_dev));
-                check(grt_device_free(device, all_dev));
-            }
+            return EXIT_FAILURE;
         }
         double seconds = 0.;
         check(grt_multi_max(multi, &seconds));             /* everybody is done before anybody tears down */
         check(grt_multi_destroy(&multi));
     }
-    for (int c = 0; c < ncol && rank == 0; ++c)
+    if (rank == 0)
     {
-        fp_t const *x = fluxes + (size_t)c*GRT_FLUXES_PER_COLUMN;
-        printf("col %d: %.15e %.15e %.15e %.15e %.15e %.15e %.15e %.15e\n", c, x[0], x[1], x[3], x[4], x[6], x[7], x[9], x[10]);
-        for (int band = 0; band < 2 && bins; ++band)
-        {
-            /* the band's six rows [6][nb] of this column: up TOA, up surface, up user, down TOA, down surface, down user */
-            fp_t const *r = binned + (size_t)c*brow + (band ? 6*nb[0] : 0);
-            SpectralGrid_t const *g = grids[band];
-            for (int b = 0; b < nb[band]; ++b)
-            {
-                printf("%s %d: %.15e %.15e %.15e %.15e %.15e %.15e\n", band ? "swbin" : "lwbin", b,
-                       g->w0 + edges[band][b]*g->dw, g->w0 + edges[band][b + 1]*g->dw, r[b], r[nb[band] + b],
-                       r[3*nb[band] + b], r[4*nb[band] + b]);
-            }
-        }
-        if (profiles)
-        {
-            fp_t const *r = profile + (size_t)c*prow, *h = r + GRT_PROFILE_ROWS_PER_COLUMN*V;
-            for (int k = 0; k < V; ++k)
-            {
-                printf("lev %d: %.15e %.15e %.15e %.15e\n", k, r[k], r[V + k], r[2*V + k], r[3*V + k]);
-            }
-            for (int j = 0; j < L; ++j)
-            {
-                printf("lay %d: %.15e %.15e\n", j, h[j], h[L + j]);
-            }
-        }
+        print_columns(&r, kinds, ncol);
     }
-    check(grt_pipeline_destroy(&pipe_day));
-    check(grt_pipeline_destroy(&pipe_night));
-    check(grt_device_free(device, fluxes_dev));
-    if (profiles)
+    check(grt_pipeline_destroy(&r.pipe[0]));
+    check(grt_pipeline_destroy(&r.pipe[1]));
+    if (free_kinds(&r, kinds))
     {
-        check(grt_device_free(device, levels_dev));
-        check(grt_device_free(device, heating_dev));
+        return EXIT_FAILURE;
     }
-    if (bins)
-    {
-        check(grt_device_free(device, spectral_dev));
-        check(grt_device_free(device, binned_dev));
-        check(grt_device_free(device, spectral_fluxes_dev));
-    }
-    free(binned);
-    free(host_bins);
-    free(edges[0]);
-    free(edges[1]);
-    free(profile);
-    free(host_levels);
-    free(host_heating);
+    free(r.edges[0]);
+    free(r.edges[1]);
     check(destroy_solar_flux(&solar));
     check(destroy_gas_optics(&lbl[0]));
     check(destroy_gas_optics(&lbl[1]));

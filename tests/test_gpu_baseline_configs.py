@@ -20,7 +20,7 @@ import pytest
 
 from grtcode_amd import api, multi, synthetic as syn
 from scenario import Band, MOL_ORDER, RUN_TO_RUN_FUSED_FLUX
-from test_gpu_circ_rfmip import circ1_column
+from driver_support import circ1_column
 from test_gpu_gas_optics import tau_close
 from pipeline_support import oracle_column
 

@@ -1,15 +1,13 @@
 """examples/rfmip_batch_driver.c -bin-width: every column's fluxes integrated over wavenumber bins through the C driver,
 on one rank and gathered from three (grt_multi_gather_rows, file transport)."""
 import os
-import struct
 import subprocess
 
 import numpy as np
 import pytest
 
-from grtcode_amd import synthetic as syn
 from scenario import Band
-from test_gpu_batch_driver import ARCHIVES, GM, LIBDIR, ROOT, rfmip_like_columns, run_driver
+from driver_support import batch_flags, build_example, rfmip_like_columns, run_driver, write_grtc_dump
 
 pytestmark = pytest.mark.gpu
 
@@ -38,25 +36,13 @@ def test_driver_prints_bins_on_one_and_three_ranks(tmp_path):
     V, ncol, width = 9, 5, 50.0
     cols, raw = rfmip_like_columns(ncol, V)
     swb = Band(str(tmp_path / "data"), 1.0, 6000.0, 2.0, 6000, sw=True)
-    dump = str(tmp_path / "columns.bin")
-    with open(dump, "wb") as f:
-        f.write(struct.pack("<iii", 0x47525443, ncol, V))
-        f.write(np.array([GM[syn.CO2], GM[syn.CH4], GM[syn.N2O], GM[syn.CO], GM[syn.O2]]).tobytes())
-        f.write(raw.astype("<f8").tobytes())
-    exe = str(tmp_path / "rfmip_batch_driver")
-    r = subprocess.run(["gcc", "-std=gnu99", "-O2", "-g", "-Wall", "-DGRT_BACKTRACE", "-rdynamic", "-I" + os.path.join(ROOT, "include"),
-                        os.path.join(ROOT, "examples", "rfmip_batch_driver.c"), "-L" + LIBDIR, *ARCHIVES,
-                        "-L/opt/rocm/lib", "-lamdhip64", "-lstdc++", "-lm", "-Wl,-rpath,/opt/rocm/lib", "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    dump = write_grtc_dump(str(tmp_path / "columns.bin"), ncol, V, raw)
+    exe = build_example("rfmip_batch_driver", str(tmp_path / "rfmip_batch_driver"), backtrace=True)
     (lw0, lwn, lwd), (sw0, swn, swd) = GRIDS["lwbin"], GRIDS["swbin"]
     # one column per batch: every gas-optics launch has the same shape on one rank and on three, so that the deterministic
     # mode makes the lines of the two runs the same text
-    args = [exe, swb.par, swb.files["solar"], dump, "-h2o-ctm", swb.h2o_dir, "-o3-ctm", swb.files["o3_ctm"],
-            "-CFC-11", swb.files["cfc11"], "2.3e-4", "-CFC-12", swb.files["cfc12"], "5.2e-4",
-            "-N2-N2", swb.files["cia_n2n2"], "-O2-N2", swb.files["cia_o2n2"], "-O2-O2", swb.files["cia_o2o2"],
-            "-w-lw", str(lw0), "-W-lw", str(lwn), "-r-lw", str(lwd), "-w-sw", str(sw0), "-W-sw", str(swn),
-            "-r-sw", str(swd), "-chunk", "1", "-fast", "3"]
+    args = [exe, swb.par, swb.files["solar"], dump,
+            *batch_flags(swb, (str(lw0), str(lwn), str(lwd)), (str(sw0), str(swn), str(swd)), 1)]
     env = dict(os.environ, GRT_DETERMINISTIC="1")
     plain = run_driver(args, env=env)
     assert plain.returncode == 0, plain.stderr[-3000:]

@@ -1,15 +1,13 @@
 """examples/rfmip_batch_driver.c -profiles: level fluxes and heating rates of every column through the C driver, on one
 rank and gathered from three (grt_multi_gather_rows, file transport)."""
 import os
-import struct
 import subprocess
 
 import numpy as np
 import pytest
 
-from grtcode_amd import synthetic as syn
 from scenario import Band
-from test_gpu_batch_driver import ARCHIVES, GM, LIBDIR, ROOT, rfmip_like_columns, run_driver
+from driver_support import batch_flags, build_example, rfmip_like_columns, run_driver, write_grtc_dump
 
 pytestmark = pytest.mark.gpu
 
@@ -36,22 +34,9 @@ def test_driver_prints_level_fluxes_and_heating_rates(tmp_path):
     L = V - 1
     cols, raw = rfmip_like_columns(ncol, V)
     swb = Band(str(tmp_path / "data"), 1.0, 6000.0, 2.0, 8000, sw=True)
-    dump = str(tmp_path / "columns.bin")
-    with open(dump, "wb") as f:
-        f.write(struct.pack("<iii", 0x47525443, ncol, V))
-        f.write(np.array([GM[syn.CO2], GM[syn.CH4], GM[syn.N2O], GM[syn.CO], GM[syn.O2]]).tobytes())
-        f.write(raw.astype("<f8").tobytes())
-    exe = str(tmp_path / "rfmip_batch_driver")
-    r = subprocess.run(["gcc", "-std=gnu99", "-O2", "-g", "-Wall", "-DGRT_BACKTRACE", "-rdynamic", "-I" + os.path.join(ROOT, "include"),
-                        os.path.join(ROOT, "examples", "rfmip_batch_driver.c"), "-L" + LIBDIR, *ARCHIVES,
-                        "-L/opt/rocm/lib", "-lamdhip64", "-lstdc++", "-lm", "-Wl,-rpath,/opt/rocm/lib", "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    args = [exe, swb.par, swb.files["solar"], dump, "-h2o-ctm", swb.h2o_dir, "-o3-ctm", swb.files["o3_ctm"],
-            "-CFC-11", swb.files["cfc11"], "2.3e-4", "-CFC-12", swb.files["cfc12"], "5.2e-4",
-            "-N2-N2", swb.files["cia_n2n2"], "-O2-N2", swb.files["cia_o2n2"], "-O2-O2", swb.files["cia_o2o2"],
-            "-w-lw", "1", "-W-lw", "2000", "-r-lw", "1", "-w-sw", "1", "-W-sw", "6000", "-r-sw", "2",
-            "-chunk", "3", "-fast", "3"]
+    dump = write_grtc_dump(str(tmp_path / "columns.bin"), ncol, V, raw)
+    exe = build_example("rfmip_batch_driver", str(tmp_path / "rfmip_batch_driver"), backtrace=True)
+    args = [exe, swb.par, swb.files["solar"], dump, *batch_flags(swb, ("1", "2000", "1"), ("1", "6000", "2"), 3)]
     env = dict(os.environ, GRT_DETERMINISTIC="1")
     plain = run_driver(args, env=env)
     assert plain.returncode == 0, plain.stderr[-3000:]

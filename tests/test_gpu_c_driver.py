@@ -11,35 +11,11 @@ import subprocess
 import numpy as np
 import pytest
 
-from grtcode_amd import synthetic as syn
 from scenario import Band
-from test_gpu_circ_rfmip import NAME, circ1_column
+from driver_support import NAME, build_example, circ1_column, write_column
 from pipeline_support import oracle_column
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "grtcode_amd", "lib")
-ARCHIVES = ["-lgrtcode_hip_ext", "-lshortwave", "-llongwave", "-lgas_optics", "-lgrtcode_utilities"]
-
-
-def build_driver(out):
-    cmd = ["gcc", "-std=gnu99", "-O2", "-Wall", "-I" + os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "examples", "circ_driver.c"), "-L" + LIBDIR, *ARCHIVES,
-           "-L/opt/rocm/lib", "-lamdhip64", "-lstdc++", "-lm", "-Wl,-rpath,/opt/rocm/lib", "-o", out]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return out
-
-
-def write_column(path, v):
-    rows = [("level_pressure", v["level_pressure_mb"]), ("level_temperature", v["level_temperature"]),
-            ("layer_pressure", v["layer_pressure_mb"]), ("layer_temperature", v["layer_temperature"]),
-            ("surface_temperature", [v["surface_temperature"]]), ("solar_zenith_angle", [v["solar_zenith_angle_deg"]]),
-            ("toa_solar_irradiance", [v["toa_solar_irradiance"]])]
-    rows += [(k, v["abundance"][k]) for k in ("H2O", "CO2", "O3", "N2O", "CO", "CH4", "O2", "CFC11", "CFC12")]
-    with open(path, "w") as f:
-        for name, vals in rows:
-            f.write(name + ": " + " ".join(repr(float(x)) for x in vals) + "\n")
 
 
 def test_c_driver_on_static_archives_matches_oracle(tmp_path, oracle, lib):
@@ -54,7 +30,7 @@ def test_c_driver_on_static_archives_matches_oracle(tmp_path, oracle, lib):
         keep = (ln["v0"] >= lwb.w0) & (ln["v0"] <= lwb.wn)
         lwb.lines[m] = {k: a[keep] for k, a in ln.items()}
     assert sum(a["v0"].size for a in lwb.lines.values()) > 1000
-    exe = build_driver(str(tmp_path / "circ_driver"))
+    exe = build_example("circ_driver", str(tmp_path / "circ_driver"))
     write_column(str(tmp_path / "column.txt"), v)
     args = [exe, swb.par, swb.files["solar"], "-p", str(tmp_path / "column.txt"),
             *("-" + NAME[m] for m in swb.mols), "-h2o-ctm", swb.h2o_dir, "-o3-ctm", swb.files["o3_ctm"],
@@ -86,7 +62,7 @@ def test_c_driver_on_static_archives_matches_oracle(tmp_path, oracle, lib):
 
 
 def test_c_driver_reports_reference_style_errors(tmp_path):
-    exe = build_driver(str(tmp_path / "circ_driver"))
+    exe = build_example("circ_driver", str(tmp_path / "circ_driver"))
     v = circ1_column()[1]
     write_column(str(tmp_path / "column.txt"), v)
     r = subprocess.run([exe, str(tmp_path / "missing.par"), str(tmp_path / "missing.csv"), "-p",

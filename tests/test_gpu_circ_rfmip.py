@@ -7,7 +7,6 @@
   reference), so the LBLRTM numbers quoted there are only an order-of-magnitude check.
 * RFMIP-IRF as BASELINE.json states it (config 3): 100 columns x 61 levels, LW and SW at 1 cm-1, production form.
 """
-import json
 import os
 
 import numpy as np
@@ -15,31 +14,10 @@ import pytest
 
 from grtcode_amd import api, synthetic as syn
 from scenario import Band, MOL_ORDER
+from driver_support import circ1_column
 from pipeline_support import oracle_column
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
-NAME = {syn.H2O: "H2O", syn.CO2: "CO2", syn.O3: "O3", syn.N2O: "N2O", syn.CO: "CO", syn.CH4: "CH4", syn.O2: "O2"}
-
-
-def circ1_column():
-    v = json.load(open(os.path.join(HERE, "golden", "reference_test_vectors.json")))["circ1"]
-    p, pl = np.array(v["level_pressure_mb"]), np.array(v["layer_pressure_mb"])
-    L = pl.size
-
-    def to_levels(ab):                                  # basic-circ-test.c:51-66
-        ab = np.array(ab)
-        out = np.zeros(L + 1)
-        out[0], out[L] = ab[0] * 1e6, ab[L - 1] * 1e6
-        for i in range(1, L):
-            out[i] = (ab[i - 1] + (ab[i] - ab[i - 1]) * (p[i] - pl[i - 1]) / (pl[i] - pl[i - 1])) * 1e6
-        return out
-    ppmv = {m: to_levels(v["abundance"][NAME[m]]) for m in MOL_ORDER}
-    ppmv[syn.N2] = np.full(L + 1, 0.781e6)
-    mu0 = float(np.cos(2.0 * np.pi * v["solar_zenith_angle_deg"] / 360.0))
-    return dict(p=p, t=np.array(v["level_temperature"]), t_layer=np.array(v["layer_temperature"]),
-                t_surf=v["surface_temperature"], ppmv=ppmv, mu0=mu0, tsi=v["toa_solar_irradiance"] / mu0,
-                cfc_ppmv={0: to_levels(v["abundance"]["CFC11"]), 1: to_levels(v["abundance"]["CFC12"])}), v
 
 
 @pytest.mark.parametrize("fast", [0, 1])

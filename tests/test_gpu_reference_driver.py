@@ -19,11 +19,9 @@ import pytest
 
 from grtcode_amd import api, synthetic as syn
 from scenario import Band
-from test_gpu_c_driver import write_column
-from test_gpu_circ_rfmip import NAME, circ1_column
+from driver_support import NAME, ROOT, as_column, circ1_column, parse_output, write_column
 from pipeline_support import oracle_column
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DRIVER = os.path.join(ROOT, "oracle", "_ref", "grtcode_driver")
 needs_driver = pytest.mark.skipif(not os.path.exists(DRIVER), reason="oracle/_ref/grtcode_driver not built (needs /root/reference at build time)")
 
@@ -36,38 +34,6 @@ def second_column(v):
     w["solar_zenith_angle_deg"] = 30.0
     w["abundance"] = dict(v["abundance"], H2O=[0.7 * x for x in v["abundance"]["H2O"]])
     return w
-
-
-def as_column(v):
-    """The column the driver builds from a dump (basic-circ-test.c semantics) as the checker wants it."""
-    p, pl = np.array(v["level_pressure_mb"]), np.array(v["layer_pressure_mb"])
-    L = pl.size
-
-    def to_levels(ab):
-        ab = np.array(ab)
-        out = np.zeros(L + 1)
-        out[0], out[L] = ab[0] * 1e6, ab[L - 1] * 1e6
-        for i in range(1, L):
-            out[i] = (ab[i - 1] + (ab[i] - ab[i - 1]) * (p[i] - pl[i - 1]) / (pl[i] - pl[i - 1])) * 1e6
-        return out
-    from scenario import MOL_ORDER
-    ppmv = {m: to_levels(v["abundance"][NAME[m]]) for m in MOL_ORDER}
-    ppmv[syn.N2] = np.full(L + 1, 0.781e6)
-    mu0 = float(np.cos(2.0 * np.pi * v["solar_zenith_angle_deg"] / 360.0))
-    return dict(p=p, t=np.array(v["level_temperature"]), t_layer=np.array(v["layer_temperature"]),
-                t_surf=v["surface_temperature"], ppmv=ppmv, mu0=mu0, tsi=v["toa_solar_irradiance"] / mu0,
-                cfc_ppmv={0: to_levels(v["abundance"]["CFC11"]), 1: to_levels(v["abundance"]["CFC12"])})
-
-
-def parse_output(path):
-    out = {}
-    for line in open(path):
-        if line.startswith("#"):
-            continue
-        t, c, name, count, *vals = line.split()
-        assert int(count) == len(vals)
-        out[(int(c), name)] = np.array([float(x) for x in vals])
-    return out
 
 
 @needs_driver

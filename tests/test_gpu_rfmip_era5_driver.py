@@ -21,11 +21,10 @@ import pytest
 from grtcode_amd import api, synthetic as syn
 from grtcode_amd.dumpfile import read_dump, write_dump
 from scenario import Band
+from driver_support import ROOT, build_example, layers_to_levels, parse_output
 from pipeline_support import oracle_column
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DRIVER = os.path.join(ROOT, "oracle", "_ref", "grtcode_driver_dump")
-LIBDIR = os.path.join(ROOT, "grtcode_amd", "lib")
 needs_driver = pytest.mark.skipif(not os.path.exists(DRIVER), reason="oracle/_ref/grtcode_driver_dump not built (needs /root/reference at build time)")
 MOLS = [syn.H2O, syn.CO2, syn.O3, syn.N2O, syn.CH4, syn.O2]
 
@@ -45,26 +44,6 @@ def bands(tmp_path, w_lw, w_sw, dw_sw, nlines):
     lwb.par, lwb.h2o_dir, lwb.files, lwb.tab = swb.par, swb.h2o_dir, swb.files, swb.tab
     lwb.lines = {m: {k: a[(ln["v0"] >= lwb.w0) & (ln["v0"] <= lwb.wn)] for k, a in ln.items()} for m, ln in swb.lines.items()}
     return lwb, swb
-
-
-def parse_output(path):
-    out = {}
-    for line in open(path):
-        if line.startswith("#"):
-            continue
-        t, c, name, count, *vals = line.split()
-        out[(int(t), int(c), name)] = np.array([float(x) for x in vals])
-    return out
-
-
-def layers_to_levels(ab, p, pl):
-    """rfmip-irf.c:295-308"""
-    L = pl.size
-    out = np.zeros(L + 1)
-    out[0], out[L] = ab[0] * 1e6, ab[L - 1] * 1e6
-    for k in range(1, L):
-        out[k] = 1e6 * (ab[k - 1] + (ab[k] - ab[k - 1]) * (p[k] - pl[k - 1]) / (pl[k] - pl[k - 1]))
-    return out
 
 
 def driver_flags(lwb, swb, dw_sw):
@@ -114,11 +93,7 @@ def test_rfmip_irf_100_sites_two_shards_gathered(tmp_path, oracle, lib):
         out, err = p.communicate(timeout=900)
         assert p.returncode == 0, (r, out[-1500:], err[-1500:])
     # ---- one gather of the shards' [columns][12] blocks to rank 0 -------------------------------------------------
-    exe = str(tmp_path / "gather_shards")
-    r = subprocess.run(["gcc", "-std=gnu99", "-O2", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                        os.path.join(ROOT, "examples", "gather_shards.c"), "-L" + LIBDIR, "-lgrtcode_hip", "-lm",
-                        "-Wl,-rpath," + LIBDIR, "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_example("gather_shards", str(tmp_path / "gather_shards"), shared=True)
     rdv = tmp_path / "rdv"
     rdv.mkdir()
     gprocs = [subprocess.Popen([exe, str(tmp_path / f"shard{k}.txt"), "-columns", str(nsite), "-ranks", "2", "-rank", str(k),
@@ -157,7 +132,7 @@ def test_rfmip_irf_100_sites_two_shards_gathered(tmp_path, oracle, lib):
     assert nights == sum(1 for c in range(nsite) if c % 6 == 2) and nights > 10
     assert worst < 1e-6
     # the shard files name GLOBAL site indices, and state variables are what the application derived
-    second = parse_output(str(tmp_path / "shard1.txt"))
+    second = parse_output(str(tmp_path / "shard1.txt"), with_time=True)
     assert (0, 50, "rlutcsaf") in second and (0, 99, "rlutcsaf") in second and (0, 49, "rlutcsaf") not in second
     assert np.allclose(second[(0, 73, "level_pressure")], pres_level[73] * 0.01, rtol=1e-15)
     assert np.allclose(second[(0, 73, "h2o_vmr")], layers_to_levels(h2o[experiment, 73], pres_level[73] * 0.01, pres_layer[73] * 0.01), rtol=1e-14)
@@ -194,7 +169,7 @@ def test_era5_block_through_the_unchanged_driver(tmp_path, oracle, lib):
            "-y", str(ys[0]), "-Y", str(ys[1]), "-x", str(xs[0]), "-X", str(xs[1]), "-clear", "-integrated", "-o", out]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ, GRT_GAS_OPTICS_FAST="0"))
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
-    got = parse_output(out)
+    got = parse_output(out, with_time=True)
     assert not any(name.startswith("rs") for _, _, name in got)       # cos(zenith) = -1: the shortwave never runs
     lwb.mols = swb.mols = mols
     lwb.lines = {m: lwb.lines[m] for m in mols}
