@@ -81,6 +81,48 @@ __device__ __forceinline__ double exp_fp64(double x)
     return ldexp(p, (int)n);
 }
 
+// kernels.c:431-432: fcenterid = floor((2*((vnn - w0)/wres) + 1)/2), bit-exact, as fp64 (the callers test it against
+// their ranges before they convert).  The quotient is first formed with the reciprocal (error <= 2 ulp); floor() of
+// the two can only differ when the argument sits within a few ulp of an integer, in which case the true division is
+// used.  Every kernel that asks which grid point a line belongs to asks here: they must agree bit for bit.
+__device__ __forceinline__ double centre_index(double wnoadj, double w0, double wres, double inv_wres)
+{
+    double const dv = wnoadj - w0;
+    double u = (2*(dv*inv_wres) + 1)/2;
+    if (fabs(u - rint(u)) <= 4e-15*fmax(1., fabs(u)))
+    {
+        u = (2*(dv/wres) + 1)/2;
+    }
+    return floor(u);
+}
+
+// RFM_voigt.c:94: REPWID = float(SQRLN2/DOPADJ) in the fused form.  It scales x inside exp(-x^2), where a 1-ulp
+// difference is amplified by 2x^2, so it must round as the reference's does: the hardware reciprocal and one fp64
+// Newton step (error ~1e-14, i.e. the correctly rounded float except on exact ties) instead of a full fp64 division.
+__device__ __forceinline__ float reference_repwid(double alpha)
+{
+    double const r0 = (double)__builtin_amdgcn_rcpf((float)alpha);
+    return (float)((double)kSqrln2*(r0*fma(-alpha, r0, 2.0)));
+}
+
+// REPWID and y of one line from the reference's fp64 expressions: the Lorentz width gamma (kernels.c:105-106; tpow =
+// (296/T)^n), the Doppler width alpha (kernels.c:127), y = REPWID gamma rounded to fp32 (RFM_voigt.c:95).
+// ms: ps, pavg - ps, ns, doppler factor.
+struct LineWidths
+{
+    float repwid, y;
+};
+
+__device__ __forceinline__ LineWidths reference_widths(double tpow, float yair, float yself, double const *ms, double wnoadj)
+{
+    double const gamma = tpow*((double)yair*ms[1] + (double)yself*ms[0]);
+    double const alpha = ((double)0.83255461115f*wnoadj)*ms[3];
+    LineWidths w;
+    w.repwid = reference_repwid(alpha);
+    w.y = (float)((double)w.repwid*gamma);
+    return w;
+}
+
 // kernels.c:34-131 for one (layer, line) + the window of kernels.c:431-437.
 // lay: pavg, tavg, 1/tavg, log(296/tavg); ms: ps, pavg-ps, ns, doppler factor.
 template <bool FAST>
@@ -112,16 +154,7 @@ __device__ __forceinline__ Prepared prepare_line(RawLine const &ln,
         p.gamma = pow(tref/T, nexp)*(yair*pf + yself*ps);                  // kernels.c:105-106
     }
     p.alpha = sqrt_ln2*p.vnn*dop;                                    // kernels.c:127
-    // kernels.c:431-432: fcenterid = floor((2*((vnn - w0)/wres) + 1)/2), bit-exact.  The quotient is
-    // first formed with the reciprocal (error <= 2 ulp); floor() of the two can only differ when the
-    // argument sits within a few ulp of an integer, in which case the true division is used.
-    double const dv = p.vnn - w0;
-    double u = (2*(dv*inv_wres) + 1)/2;
-    if (fabs(u - rint(u)) <= 4e-15*fmax(1., fabs(u)))
-    {
-        u = (2*(dv/wres) + 1)/2;
-    }
-    double const fc = floor(u);
+    double const fc = centre_index(p.vnn, w0, wres, inv_wres);
     p.s = 1;
     p.e = 0;
     p.c_minus_fsteps = 0;
@@ -431,6 +464,23 @@ __device__ __forceinline__ float voigt_reg1_corr_fast(float cl, float a0, float 
 {
     float const den = fmaf(xq, d2r + xq, d0r)*fmaf(xi, xi, yq);
     return cl*fmaf(1.5f, xq, -0.5f*a0)*__builtin_amdgcn_rcpf(den);
+}
+// fused form, a point of a near field (xq = x^2, d = x^2 + y^2 as the caller has it): region 1 (RFM_voigt.c:172-183),
+// K = cl (A0 + XQ)/(D0 + XQ (D2 + XQ)), where XLIM1^2 = xq_near <= xq < x0q = XLIM0^2; beyond it the Lorentzian cl/d; nothing
+// for the near-centre points (|x| < XLIM1), which are the queues' alone -- nor where the caller's `wanted` says no
+// (a callable: asked after the point's own test, as the expression written in place would).
+template <class Wanted>
+__device__ __forceinline__ float near_shape(float cl, float a0, float d0r, float d2r, float xq_near, float x0q, float xq, float d, Wanted wanted)
+{
+    bool const outer = xq >= xq_near;
+    bool const reg1 = outer & (xq < x0q);
+    float const den = reg1 ? fmaf(xq, d2r + xq, d0r) : d;
+    float const num = reg1 ? cl*(a0 + xq) : cl;
+    return (outer & wanted()) ? num*__builtin_amdgcn_rcpf(den) : 0.f;
+}
+__device__ __forceinline__ float near_shape(float cl, float a0, float d0r, float d2r, float xq_near, float x0q, float xq, float d)
+{
+    return near_shape(cl, a0, d0r, d2r, xq_near, x0q, xq, d, [] { return true; });
 }
 
 // x-coordinate of window point k of a line: RFM_voigt.c:102/165 with DWNO from

@@ -53,6 +53,24 @@ __device__ __forceinline__ int dpp_i(int v)
     return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true);
 }
 
+// A row's (16 lanes') smallest value, in every lane of the row: rotations inside the row
+__device__ __forceinline__ int row_min_i(int v)
+{
+    v = min(v, dpp_i<0x121>(v));
+    v = min(v, dpp_i<0x122>(v));
+    v = min(v, dpp_i<0x124>(v));
+    return min(v, dpp_i<0x128>(v));
+}
+
+// ... and of two values the smallest of one and the largest of the other (a row's span), step by step side by side
+__device__ __forceinline__ void row_min_max_i(int &lo, int &hi)
+{
+    lo = min(lo, dpp_i<0x121>(lo)); hi = max(hi, dpp_i<0x121>(hi));
+    lo = min(lo, dpp_i<0x122>(lo)); hi = max(hi, dpp_i<0x122>(hi));
+    lo = min(lo, dpp_i<0x124>(lo)); hi = max(hi, dpp_i<0x124>(hi));
+    lo = min(lo, dpp_i<0x128>(lo)); hi = max(hi, dpp_i<0x128>(hi));
+}
+
 // Wave-wide integer max as a scalar: rotations inside the rows of 16 lanes (every lane of a row
 // ends up with the row's extreme, whatever the direction of row_ror), then the four rows on the
 // scalar unit.

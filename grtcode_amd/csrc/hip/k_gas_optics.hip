@@ -132,19 +132,8 @@ __global__ __launch_bounds__(kBlock) void gas_optics_kernel(GrtGasOpticsArgs a, 
                 lo = s > F0 ? s : F0;
                 hi = (int)p.e < F1 - 1 ? (int)p.e : F1 - 1;
                 c = p.c_minus_fsteps + (int)fsteps;
-                // RFM_voigt.c:94: REPWID = float(SQRLN2/DOPADJ).  It scales x inside exp(-x^2), where a
-                // 1-ulp difference is amplified by 2x^2, so it must round as the reference's does: the
-                // fused form takes the hardware reciprocal and one fp64 Newton step (error ~1e-14, i.e.
-                // the correctly rounded float except on exact ties) instead of a full fp64 division.
-                if (FAST)
-                {
-                    double const r0 = (double)__builtin_amdgcn_rcpf((float)p.alpha);
-                    repwid = (float)((double)kSqrln2*(r0*fma(-p.alpha, r0, 2.0)));
-                }
-                else
-                {
-                    repwid = (float)((double)kSqrln2/p.alpha);
-                }
+                // RFM_voigt.c:94: REPWID = float(SQRLN2/DOPADJ), rounded as the reference's (reference_repwid)
+                repwid = FAST ? reference_repwid(p.alpha) : (float)((double)kSqrln2/p.alpha);
                 y = (float)((double)repwid*p.gamma);                                  // RFM_voigt.c:95
                 dwno = (double)p.s*a.wres + a.w0;                                     // kernels.c:438
                 wnoadj = p.vnn;
@@ -460,16 +449,7 @@ __global__ __launch_bounds__(kBlock) void voigt_debug_kernel(double w_start, uin
     {
         return;
     }
-    float repwid;
-    if (FAST)
-    {
-        double const r0 = (double)__builtin_amdgcn_rcpf((float)alpha);
-        repwid = (float)((double)kSqrln2*(r0*fma(-alpha, r0, 2.0)));
-    }
-    else
-    {
-        repwid = (float)((double)kSqrln2/alpha);                                      // RFM_voigt.c:94
-    }
+    float const repwid = FAST ? reference_repwid(alpha) : (float)((double)kSqrln2/alpha);     // RFM_voigt.c:94
     float const y = (float)((double)repwid*gamma);                                    // :95
     bool const lorentz = (y >= 70.55f);                                               // :97
     float const yq = y*y;

@@ -245,13 +245,7 @@ __device__ __forceinline__ void mp_kernel_body(GrtGasOpticsArgs const &a, long l
             for (uint64_t j = jbeg + tid; j < jend; j += kBlock)
             {
                 double const wnoadj = a.lines.v0[j] + (double)a.lines.delta[j]*lay[0];
-                double const dv = wnoadj - a.w0;
-                double u = (2*(dv*inv_wres) + 1)/2;
-                if (fabs(u - rint(u)) <= 4e-15*fmax(1., fabs(u)))
-                {
-                    u = (2*(dv/a.wres) + 1)/2;
-                }
-                double const fc = floor(u);
+                double const fc = centre_index(wnoadj, a.w0, a.wres, inv_wres);
                 if ((fc >= (double)F0) & (fc < (double)F1))
                 {
                     int const i = (int)fc - F0;

@@ -19,14 +19,7 @@
         // fp64 with hardware exp2.
         double const *ms = ms_l + ln.slot*4;
         double const wnoadj = ln.v0 + (double)ln.delta*lay[0];                         // kernels.c:44
-        // kernels.c:431-432: fcenterid = floor((2*((vnn - w0)/wres) + 1)/2), bit-exact (see prepare_line)
-        double const dv = wnoadj - a.w0;
-        double u = (2*(dv*inv_wres) + 1)/2;
-        if (fabs(u - rint(u)) <= 4e-15*fmax(1., fabs(u)))
-        {
-            u = (2*(dv/a.wres) + 1)/2;
-        }
-        double const fc = floor(u);
+        double const fc = centre_index(wnoadj, a.w0, a.wres, inv_wres);                 // kernels.c:431-432
         bool valid = have & (fc >= 0.) & (fc < (double)nw_i);
         int const c = valid ? (int)fc : 0;
         int const s = c - fsteps < 0 ? 0 : c - fsteps;                                 // kernels.c:435
@@ -72,12 +65,8 @@
             double const e = exp_fp64_call((double)ln.nexp*lay[3]);
             tpow = tabulated ? tpow : e;
         }
-        double const gamma = tpow*((double)ln.yair*ms[1] + (double)ln.yself*ms[0]);     // kernels.c:105-106
-        double const alpha = ((double)0.83255461115f*wnoadj)*ms[3];                    // kernels.c:127
-        // RFM_voigt.c:94, rounded as the reference's REPWID (see k_gas_optics.hip)
-        double const r0 = (double)__builtin_amdgcn_rcpf((float)alpha);
-        float const repwid = (float)((double)kSqrln2*(r0*fma(-alpha, r0, 2.0)));
-        float const y = (float)((double)repwid*gamma);                                 // RFM_voigt.c:95
+        LineWidths const lw = reference_widths(tpow, ln.yair, ln.yself, ms, wnoadj);    // kernels.c:105-106, :127; RFM_voigt.c:94-95
+        float const repwid = lw.repwid, y = lw.y;
         bool const lorentz = (y >= 70.55f);                                           // RFM_voigt.c:97
         float const yq = y*y;
         // thresholds: hardware square roots (1 ulp) -- they only decide which formula a point within
@@ -191,11 +180,7 @@
                 bool const sparse = __builtin_amdgcn_readlane(c, 63 - __builtin_clzll(vmask)) - c_ref >= 24;    // (sorted lines)
                 for (int pass = 0; pass < kCellLoop && !sparse && __ballot(pending) != 0ull; ++pass)
                 {
-                    int cr = pending ? c : 0x7fffffff;
-                    cr = min(cr, dpp_i<0x121>(cr));
-                    cr = min(cr, dpp_i<0x122>(cr));
-                    cr = min(cr, dpp_i<0x124>(cr));
-                    cr = min(cr, dpp_i<0x128>(cr));                      // the row's lowest pending cell, in every lane
+                    int const cr = row_min_i(pending ? c : 0x7fffffff);      // the row's lowest pending cell, in every lane
                     bool const mine = pending & (c == cr);
                     bool const next = pending & (c - cr == 1);
                     if constexpr (PROBE) ++pc_momred;
@@ -303,8 +288,7 @@
                     float const xq = xi*xi;
                     if ((rr <= reach0) & (f >= lo) & (f <= hi) & (xq < x0q) & (xq >= xq_near) & ((f < near_lo) | (f > near_hi)))
                     {
-                        float const den = fmaf(xq, d2r + xq, d0r)*fmaf(xi, xi, yq);
-                        float const corr = cl*fmaf(1.5f, xq, -0.5f*a0)*__builtin_amdgcn_rcpf(den);
+                        float const corr = voigt_reg1_corr_fast(cl, a0, d0r, d2r, xi, xq, yq);
                         GRT_ACC_ADD(&acc[f - A0], amp*(double)corr);
                     }
                 }
@@ -350,17 +334,11 @@
                     float kf;
                     if (NARROW && narrow && k != 3)
                     {
-                        kf = cl*__builtin_amdgcn_rcpf(d);                     // beyond XLIM0: the Lorentzian (RFM_voigt.c:103)
+                        kf = voigt_lorentzian_fast(cl, xi, yq);               // beyond XLIM0: the Lorentzian (RFM_voigt.c:103)
                     }
                     else
                     {
-                        // region 1 (RFM_voigt.c:172-183): K = c (A0+XQ)/(D0+XQ(D2+XQ)); beyond it the Lorentzian; the
-                        // near-centre points (|x| < XLIM1) are the queue's alone
-                        bool const outer = xq >= xq_near;
-                        bool const reg1 = outer & (xq < x0q);
-                        float const den = reg1 ? fmaf(xq, d2r + xq, d0r) : d;
-                        float const num = reg1 ? cl*(a0 + xq) : cl;
-                        kf = outer ? num*__builtin_amdgcn_rcpf(den) : 0.f;
+                        kf = near_shape(cl, a0, d0r, d2r, xq_near, x0q, xq, d);
                     }
                     nv[k] = inside ? amp_f32*kf : 0.f;
                 }
@@ -371,11 +349,7 @@
                 bool const sparse = __builtin_amdgcn_readlane(c, 63 - __builtin_clzll(pmask)) - __builtin_amdgcn_readlane(c, __builtin_ctzll(pmask)) >= 24;
                 for (int pass = 0; pass < kCellLoop && !sparse && __ballot(pending) != 0ull; ++pass)
                 {
-                    int cr = pending ? c : 0x7fffffff;
-                    cr = min(cr, dpp_i<0x121>(cr));
-                    cr = min(cr, dpp_i<0x122>(cr));
-                    cr = min(cr, dpp_i<0x124>(cr));
-                    cr = min(cr, dpp_i<0x128>(cr));                      // the row's lowest pending cell, in every lane
+                    int const cr = row_min_i(pending ? c : 0x7fffffff);      // the row's lowest pending cell, in every lane
                     // Eight slots: the grid points cr - 3 .. cr + 4.  The lines of cell cr fill slots 0 .. 6; where a row
                     // straddles two cells (the shortwave band: 30 lines per cell) the lines of cell cr + 1 fill slots 1 .. 7
                     // -- their seven values one slot up -- and ONE reduction serves both cells.
@@ -426,10 +400,7 @@
         // a row's 16 centres sit in one or two cells, the wave's 64 in two to four); the wave only shares the
         // number of steps, the longest row's.
         int fb = lo_n <= hi_n ? lo_n : 0x7fffffff, fe = lo_n <= hi_n ? hi_n : (int)0x80000000;
-        fb = min(fb, dpp_i<0x121>(fb)); fe = max(fe, dpp_i<0x121>(fe));
-        fb = min(fb, dpp_i<0x122>(fb)); fe = max(fe, dpp_i<0x122>(fe));
-        fb = min(fb, dpp_i<0x124>(fb)); fe = max(fe, dpp_i<0x124>(fe));
-        fb = min(fb, dpp_i<0x128>(fb)); fe = max(fe, dpp_i<0x128>(fe));       // the row's span, in every lane of the row
+        row_min_max_i(fb, fe);                                                // the row's span, in every lane of the row
         int const len = fb <= fe ? fe - fb + 1 : 0;
         int const span = max(max(__builtin_amdgcn_readlane(len, 0), __builtin_amdgcn_readlane(len, 16)),
                              max(__builtin_amdgcn_readlane(len, 32), __builtin_amdgcn_readlane(len, 48)));
@@ -447,12 +418,7 @@
             narrow_ok = __ballot(valid & !lorentz & !((1.f - fabsf(delta_c))*wr >= 1.001f*xlim0)) == 0ull;
             if (narrow_ok)
             {
-                float const xq0 = ndcr*ndcr, d0 = fmaf(ndcr, ndcr, yq);
-                bool const outer = xq0 >= xq_near;
-                bool const reg1 = outer & (xq0 < x0q);
-                float const den = reg1 ? fmaf(xq0, d2r + xq0, d0r) : d0;
-                float const num = reg1 ? cl*(a0 + xq0) : cl;
-                k_own = outer ? num*__builtin_amdgcn_rcpf(den) : 0.f;
+                k_own = near_shape(cl, a0, d0r, d2r, xq_near, x0q, ndcr*ndcr, fmaf(ndcr, ndcr, yq));
             }
         }
         float const mid = 0.5f*(float)(lo_n + hi_n) - (float)c;
@@ -488,25 +454,19 @@
                 float kf;
                 if (MODE == 2)
                 {
-                    kf = cl*__builtin_amdgcn_rcpf(d);
+                    kf = voigt_lorentzian_fast(cl, xi, yq);
                 }
                 else if (MODE == 3)
                 {
                     // every point but the line's own (rel = 0) lies beyond XLIM0: the Lorentzian, bit for bit what the
                     // general form computes there; the line's own point takes the value worked out once (k_own)
-                    kf = cl*__builtin_amdgcn_rcpf(d);
+                    kf = cl*__builtin_amdgcn_rcpf(d);       // (voigt_lorentzian_fast's value; calling it here as well changes the schedule)
                     kf = rel == 0.f ? k_own : kf;
                     kf = fabsf(rel - mid) <= half ? kf : 0.f;
                 }
                 else
                 {
-                    // region 1 (RFM_voigt.c:172-183): K = c (A0+XQ)/(D0+XQ(D2+XQ)); beyond it the Lorentzian; the
-                    // near-centre points (|x| < XLIM1) are the queue's alone
-                    bool const outer = xq >= xq_near;
-                    bool const reg1 = outer & (xq < x0q);
-                    float const den = reg1 ? fmaf(xq, d2r + xq, d0r) : d;
-                    float const num = reg1 ? cl*(a0 + xq) : cl;
-                    kf = (outer & (MODE == 1 || fabsf(rel - mid) <= half)) ? num*__builtin_amdgcn_rcpf(den) : 0.f;
+                    kf = near_shape(cl, a0, d0r, d2r, xq_near, x0q, xq, d, [&] { return MODE == 1 || fabsf(rel - mid) <= half; });
                 }
                 token = fmaf(amp_f32, kf, token);
                 token = dpp_f<0x121>(token);

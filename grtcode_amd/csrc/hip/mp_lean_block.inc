@@ -127,11 +127,8 @@
             double const *ms = ms_l + ((packed >> 16) & 63u)*4;
             double const wnoadj = lx.x + (double)raw->delta[wave][i]*lay[0];           // kernels.c:44
             int const s = c - fsteps < 0 ? 0 : c - fsteps;                             // kernels.c:435
-            double const gamma = ptab[(packed >> 22) & 127u]*((double)yair*ms[1] + (double)yself*ms[0]);    // kernels.c:105-106
-            double const alpha = ((double)0.83255461115f*wnoadj)*ms[3];                // kernels.c:127
-            double const r0 = (double)__builtin_amdgcn_rcpf((float)alpha);
-            float const repwid = (float)((double)kSqrln2*(r0*fma(-alpha, r0, 2.0)));   // RFM_voigt.c:94
-            float const y = (float)((double)repwid*gamma);                             // RFM_voigt.c:95
+            LineWidths const lw = reference_widths(ptab[(packed >> 22) & 127u], yair, yself, ms, wnoadj);
+            float const repwid = lw.repwid, y = lw.y;
             double const dwno = (double)s*a.wres + a.w0;                               // kernels.c:438
             float const xr = voigt_x(dwno, idx + A0 - s, a.wres, wnoadj, repwid);      // the reference's x
             int const cls = on ? voigt_class<true, kSplit>(xr, y) : -1;
