@@ -156,7 +156,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_aerosols grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_aerosols grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -200,6 +200,9 @@ def load_library(path=None):
                                                      C.c_void_p, C.c_void_p]
     lib.grt_pipeline_run_spectral.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtClouds), C.c_void_p, C.c_int,
                                               C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.grt_pipeline_run_band_profiles.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtClouds), C.c_void_p,
+                                                   C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.grt_pipeline_band_profile_bin_limit.argtypes = [C.c_void_p]
     lib.grt_pipeline_run_subcolumns.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtClouds), C.c_int,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]
     lib.grt_pipeline_run_aerosols.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtAerosols), C.c_void_p,
@@ -539,6 +542,7 @@ class Pipeline:
         self.nw = tuple(g.grid.n if g is not None else 0 for g in (lw_gas, sw_gas))
         self.buffers = {}       # every device buffer of this object by name: each run form's at its first call
         self.spec_shape = None  # (sets, longwave bins, shortwave bins) of the last run_spectral
+        self.band_shape = None  # ... of the last run_band_profiles
         self.out = self._buffer("run", 8 * GRT_FLUXES_PER_COLUMN * max_columns)
 
     def _buffer(self, name, nbytes):
@@ -649,6 +653,41 @@ class Pipeline:
         out["sw_bins"] = bn[:, :, 6 * nb_lw:].reshape(ncol, sets, 6, nb_sw).copy()
         out["fluxes"] = self.buffers["spectral.fluxes"].to_host((ncol, sets * GRT_FLUXES_PER_COLUMN))
         return out
+
+    def band_profile_bin_limit(self):
+        """grt_pipeline_band_profile_bin_limit: the most bins that may have a point in one block of 128 grid points."""
+        return self.lib.grt_pipeline_band_profile_bin_limit(self.p)
+
+    def run_band_profiles(self, gcols, gclouds=None, lw_edges=None, sw_edges=None):
+        """grt_pipeline_run_band_profiles into this object's device buffers (band_profiles() reads them): every level's
+        flux and every layer's heating rate per bin of lw_edges / sw_edges (grid-point indices, num_bins + 1 of them);
+        gclouds: all-sky too."""
+        sets = 1 if gclouds is None else 2
+        e = [None if x is None else np.ascontiguousarray(x, dtype=np.int32) for x in (lw_edges, sw_edges)]
+        nb = [0 if x is None else max(x.size - 1, 0) for x in e]
+        V, n = self.num_levels, self.max_columns
+        self.band_shape = (sets, nb[0], nb[1])
+        levels = self._buffer("band_profiles.levels", 8 * n * sets * 2 * max(nb[0] + nb[1], 1) * V)
+        heating = self._buffer("band_profiles.heating", 8 * n * sets * max(nb[0] + nb[1], 1) * (V - 1))
+        ptr = [None if x is None else x.ctypes.data_as(C.c_void_p) for x in e]
+        check(self.lib.grt_pipeline_run_band_profiles(self.p, C.byref(gcols),
+                                                      C.byref(gclouds) if gclouds is not None else None, ptr[0], nb[0],
+                                                      ptr[1], nb[1], levels.ptr, heating.ptr))
+
+    def band_profiles(self, ncol):
+        """The last run_band_profiles: lw_up, lw_down, sw_up, sw_down [ncol][sets][num_bins][V] (W m-2, levels top first)
+        and lw_heating, sw_heating [ncol][sets][num_bins][V-1] (K day-1)."""
+        self.sync()
+        sets, bl, bs = self.band_shape
+        V = self.num_levels
+        lv = self.buffers["band_profiles.levels"].to_host((ncol, sets, 2 * (bl + bs) * V))
+        hr = self.buffers["band_profiles.heating"].to_host((ncol, sets, (bl + bs) * (V - 1)))
+        lw = lv[:, :, :2 * bl * V].reshape(ncol, sets, 2, bl, V)
+        sw = lv[:, :, 2 * bl * V:].reshape(ncol, sets, 2, bs, V)
+        return {"lw_up": lw[:, :, 0].copy(), "lw_down": lw[:, :, 1].copy(), "sw_up": sw[:, :, 0].copy(),
+                "sw_down": sw[:, :, 1].copy(),
+                "lw_heating": hr[:, :, :bl * (V - 1)].reshape(ncol, sets, bl, V - 1).copy(),
+                "sw_heating": hr[:, :, bl * (V - 1):].reshape(ncol, sets, bs, V - 1).copy()}
 
     def _six_row_or_profile_ptrs(self, name, profiles):
         """The (levels, heating, fluxes) pointers of a two-set entry point that writes either form: the six-row form's

@@ -438,6 +438,34 @@ static inline int grt_subcolumn_args_ok(int ncol, int num_levels, uint64_t nw, d
            partials != NULL && grt_cloud_args_ok(&sc->clouds) && sc->subcolumns >= 1 && sc->count >= 1 &&
            sc->first >= 0 && sc->first + sc->count <= sc->subcolumns && (uint64_t)ncol*(uint64_t)sc->count <= 65535u;
 }
+
+/* Banded profile form of the two profile forms (GRT_SOLVER_PROFILE when clouds is NULL, GRT_SOLVER_ALLSKY_PROFILE
+   otherwise; grt_pipeline_run_band_profiles): the profile form's arguments, sweeps and park block, but every level's
+   flux leaves once per wavenumber bin that has a point in the workgroup's 128 grid points.  A point weights a level's
+   value with the trapezoid weight of the bin (grt_launch_bin_rows' rule: dw inside, dw/2 at the bin's two edges, 0
+   elsewhere and for idle lanes); a workgroup inside one bin -- all but the few that hold an edge -- does exactly the
+   profile form's work, one wave sum per level and direction; one that holds edges repeats the wave sum for each of its
+   bins.  Partial sums go where grt_bin_table places them, partials[(c*2 V + r)*per_row + offset(b) + block -
+   first_block(b)], r = level (up) and V + level (down); grt_launch_bin_reduce finishes.  Dynamic LDS: block_bins x 2 V x
+   2 doubles, block_bins = grt_bin_block_max of the edges.  The single bin {0, nw - 1} gives the profile form's partial
+   sums, bit for bit. */
+typedef struct GrtBandArgs
+{
+    int num_bins;
+    int block_bins;                 /* the most bins with a point in one workgroup: sizes the dynamic LDS */
+    int const *table;               /* DEVICE: grt_bin_table's ints */
+    uint64_t per_row;               /* partial sums per row (grt_bin_table's return value) */
+} GrtBandArgs;
+static inline size_t grt_band_profile_lds(GrtBandArgs const *bn, int num_levels, int block_threads)
+{
+    return sizeof(double)*2*(size_t)num_levels*(size_t)(block_threads/64)*(size_t)bn->block_bins;
+}
+static inline int grt_band_args_ok(GrtBandArgs const *bn)
+{
+    return bn != NULL && bn->num_bins >= 1 && bn->block_bins >= 1 && bn->table != NULL && bn->per_row >= 1;
+}
+int grt_launch_lw_bands(void *stream, GrtLwArgs const *a, GrtCloudArgs const *clouds, GrtBandArgs const *bins);
+int grt_launch_sw_bands(void *stream, GrtSwArgs const *a, GrtCloudArgs const *clouds, GrtBandArgs const *bins);
 int grt_launch_lw_subcolumns(void *stream, int profile, GrtLwArgs const *a, GrtSubcolumnArgs const *sc);
 int grt_launch_sw_subcolumns(void *stream, int profile, GrtSwArgs const *a, GrtSubcolumnArgs const *sc);
 /* The subcolumn mean of the partial sums above, in a fixed order: for column c and row r (of `rows` per slot) each
@@ -481,6 +509,27 @@ size_t grt_bin_table(int const *edges_h, int nbins, uint64_t nw, int *table_h);
 int grt_launch_bin_rows(void *stream, double const *in, uint64_t in_stride, int nrows, uint64_t nw, double dw,
                         int nbins, int const *table_dev, size_t partials_per_row, double *partials, double *out,
                         uint64_t out_stride);
+/* Wavenumber bins of level fluxes (grt_pipeline_run_band_profiles).  Row r (of nrows = ncol x 2 V) is level r % V of
+   column r / (2 V), upward when r % (2 V) < V; its bin b goes to out + (r / (2 V)) out_stride + ((r % (2 V) / V) nbins + b) V
+   + r % V: per column [2][nbins][V], up then down.
+   grt_bin_block_max: the most bins of edges_h [nbins + 1] that have a point in one 128-point solver block.
+   grt_launch_bin_reduce: the second stage alone, on the partial sums a banded profile solver left (GrtBandArgs), each
+   bin's blocks in order from its first as reduce_partials adds them: a bin over the whole grid is the profile form's
+   level flux to the bit.
+   grt_launch_bin_level_rows: both stages on the materialised form's spectra, row r at rows_dev[r] [nw] (DEVICE table),
+   weighted and summed as grt_launch_bin_rows does. */
+int grt_bin_block_max(int const *edges_h, int nbins);
+int grt_launch_bin_reduce(void *stream, int nrows, int num_levels, int nbins, int const *table_dev, size_t partials_per_row,
+                          double const *partials, double *out, uint64_t out_stride);
+int grt_launch_bin_level_rows(void *stream, double const *const *rows_dev, int nrows, int num_levels, uint64_t nw, double dw,
+                              int nbins, int const *table_dev, size_t partials_per_row, double *partials, double *out,
+                              uint64_t out_stride);
+/* Last step of grt_pipeline_run_band_profiles: levels [ncol][sets][2 lw_bins + 2 sw_bins][V] (per set the longwave's
+   [2][lw_bins][V], up then down, then the shortwave's) -> heating [ncol][sets][lw_bins + sw_bins][V-1] K day-1, by
+   grt_launch_profile_finish's formula and constants on each bin's level fluxes; pressure [ncol][V] mb. */
+int grt_launch_band_profile_finish(void *stream, int ncol, int sets, int num_levels, int lw_bins, int sw_bins,
+                                   double gravity, double cp, double const *pressure, double const *levels,
+                                   double *heating);
 /* out + (r/6) out_stride + (r%6) nw  <-  rows_dev[r] [nw], r < nrows (the materialised form's spectral rows) */
 int grt_launch_copy_rows(void *stream, double const *const *rows_dev, int nrows, uint64_t nw, double *out,
                          uint64_t out_stride);

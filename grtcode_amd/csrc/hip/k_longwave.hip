@@ -14,7 +14,8 @@
 // SURVEY.md §8a19 prices it at 1 944 B per wavenumber at 60 layers; measured it is a latency
 // chain -- 120 dependent layer steps with six fp64 exp each on 26 000 threads at 1 cm-1 -- which is why column
 // batches share a launch.  lw_kernel<true, false> is the fused form of the production pipeline, lw_kernel<true, false, true>
-// its all-sky form, lw_kernel<true, true> and lw_kernel<true, true, true> the profile forms of the two,
+// its all-sky form, lw_kernel<true, true> and lw_kernel<true, true, true> the profile forms of the two
+// (with a GrtBandArgs last: their banded forms, a level's flux per wavenumber bin),
 // lw_kernel<true, false, false, true> and lw_kernel<true, false, true, true> the spectral six-row forms of the two, and
 // lw_kernel<true, *, true, false, GrtSubcolumnArgs> the all-sky forms over several subcolumns per column, and lw_kernel<true, *, false, false,
 // GrtAerosolArgs> the clear-sky forms with the aerosol object (the argument's type selects them: LayerOptics).
@@ -123,7 +124,7 @@ __global__ __launch_bounds__(kSolverBlock) void lw_kernel(GrtLwArgs a, Clouds...
     double const *tl = a.t_layers + (uint64_t)col*L;
     double const *tv = a.t_levels + (uint64_t)col*V;
     double const emis = a.emis[(uint64_t)col*a.emis_stride + ii];
-    LevelSink<FUSED, PROFILE, SPECTRAL> sink(a, row.slot, i, live);
+    LevelSink<FUSED, PROFILE, SPECTRAL, IsBandPack<Clouds...>::value> sink(a, row.slot, i, live, band_args(clouds...));
     LayerOptics<FUSED, ALLSKY, IsAerosolPack<Clouds...>::value> const optics(a, cloud_args(clouds...), col, row.tab, ii,
                                                                              aerosol_args(clouds...));   // (fused forms)
 
@@ -349,6 +350,29 @@ extern "C" int grt_launch_lw_subcolumns(void *stream, int profile, GrtLwArgs con
     {
         hipLaunchKernelGGL((lw_kernel<true, false, true, false, GrtSubcolumnArgs>), grid, dim3(kSolverBlock), 0, s, *a,
                            *sc);
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_lw_bands(void *stream, GrtLwArgs const *a, GrtCloudArgs const *c, GrtBandArgs const *bn)
+{
+    if (!grt_band_args_ok(bn) || a->ncol < 1 || a->ncol > 65535 || a->nw < 2 || a->num_levels < 2 ||
+        a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr || (c != nullptr && !grt_cloud_args_ok(c)) ||
+        grt_band_profile_lds(bn, a->num_levels, kSolverBlock) > 65536)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    size_t const lds = grt_band_profile_lds(bn, a->num_levels, kSolverBlock);
+    hipStream_t const s = (hipStream_t)stream;
+    dim3 const grid(grt_solver_blocks(a->nw), a->ncol, 1);
+    if (c != nullptr)
+    {
+        hipLaunchKernelGGL((lw_kernel<true, true, true, false, GrtCloudArgs, GrtBandArgs>), grid, dim3(kSolverBlock), lds, s,
+                           *a, *c, *bn);
+    }
+    else
+    {
+        hipLaunchKernelGGL((lw_kernel<true, true, false, false, GrtBandArgs>), grid, dim3(kSolverBlock), lds, s, *a, *bn);
     }
     return (int)hipGetLastError();
 }

@@ -299,10 +299,12 @@ inline unsigned bin_blocks(uint64_t nw)
 }
 
 // one workgroup per (128-point block, row): per bin that has a point in the block, sum_i x_i w_i by block_partials'
-// tree, stored at partials[row P + offset(bin) + block - first_block(bin)]
-__global__ __launch_bounds__(kSolverBlock) void bin_partials_kernel(double const *in, uint64_t in_stride, int nrows,
-                                                                    uint64_t nw, double dw, int nbins, int const *tab,
-                                                                    uint64_t P, double *partials)
+// tree, stored at partials[row P + offset(bin) + block - first_block(bin)].  Row r: in + (r/6) in_stride + (r%6) nw, or
+// -- rows given (the level fluxes of grt_pipeline_run_band_profiles' materialised form) -- rows[r].
+__global__ __launch_bounds__(kSolverBlock) void bin_partials_kernel(double const *in, uint64_t in_stride,
+                                                                    double const *const *rows, int nrows, uint64_t nw,
+                                                                    double dw, int nbins, int const *tab, uint64_t P,
+                                                                    double *partials)
 {
     __shared__ double part[kBinChunk][kSolverBlock/64];
     unsigned const block = blockIdx.x;
@@ -311,7 +313,7 @@ __global__ __launch_bounds__(kSolverBlock) void bin_partials_kernel(double const
     bool const live = i < (long long)nw;
     for (int r = blockIdx.y; r < nrows; r += gridDim.y)
     {
-        double const x = live ? in[(uint64_t)(r/6)*in_stride + (uint64_t)(r % 6)*nw + i] : 0.;
+        double const x = !live ? 0. : (rows != nullptr ? rows[r][i] : in[(uint64_t)(r/6)*in_stride + (uint64_t)(r % 6)*nw + i]);
         double *prow = partials + (uint64_t)r*P;
         for (int b0 = b_lo; b0 < b_hi; b0 += kBinChunk)
         {
@@ -347,9 +349,12 @@ __global__ __launch_bounds__(kSolverBlock) void bin_partials_kernel(double const
     }
 }
 
-// one wavefront per (bin, row): the bin's block sums in block order, reduce_partials_kernel's association
-__global__ __launch_bounds__(64) void bin_reduce_kernel(int nrows, int nbins, int const *tab, uint64_t P,
-                                                        double const *partials, double *out, uint64_t out_stride)
+// one wavefront per (bin, row): the bin's block sums in block order, reduce_partials_kernel's association.  `group` rows
+// per column; bin b of row r goes to out + (r/group) out_stride + (r%group) nbins + b, or -- levels > 0: the rows are a
+// column's levels, up then down (group = 2 levels) -- + ((r%group/levels) nbins + b) levels + r%levels.
+__global__ __launch_bounds__(64) void bin_reduce_kernel(int nrows, int group, int levels, int nbins, int const *tab,
+                                                        uint64_t P, double const *partials, double *out,
+                                                        uint64_t out_stride)
 {
     int const b = blockIdx.x;
     int const *e = tab + 4*b;
@@ -368,7 +373,9 @@ __global__ __launch_bounds__(64) void bin_reduce_kernel(int nrows, int nbins, in
         }
         if (threadIdx.x == 0)
         {
-            out[(uint64_t)(r/6)*out_stride + (uint64_t)(r % 6)*nbins + b] = s;
+            int const k = r % group;
+            uint64_t const at = levels > 0 ? ((uint64_t)(k/levels)*nbins + b)*levels + k % levels : (uint64_t)k*nbins + b;
+            out[(uint64_t)(r/group)*out_stride + at] = s;
         }
     }
 }
@@ -451,7 +458,49 @@ __global__ __launch_bounds__(kBlock) void profile_finish_kernel(int ncol, int se
     }
 }
 
+// Last step of grt_pipeline_run_band_profiles: one thread per (column, set, bin q of the lw_bins + sw_bins, layer j) reads
+// the bin's level fluxes in levels[c][set][2 lw_bins + 2 sw_bins][V] (per set the longwave's [2][lw_bins][V], up then
+// down, then the shortwave's) and forms profile_finish_kernel's heating rate of layer j from them: the same expression
+// on the same constants.
+__global__ __launch_bounds__(kBlock) void band_profile_finish_kernel(int ncol, int sets, int V, int lw_bins, int sw_bins,
+                                                                     double gravity, double cp, double const *pressure,
+                                                                     double const *levels, double *heating)
+{
+    int const L = V - 1, nb = lw_bins + sw_bins;
+    uint64_t const t = (uint64_t)blockIdx.x*kBlock + threadIdx.x;
+    if (t >= (uint64_t)ncol*sets*nb*L)
+    {
+        return;
+    }
+    int const j = (int)(t % L);
+    int const q = (int)((t/L) % nb);
+    uint64_t const cs = t/((uint64_t)nb*L);        // c sets + set
+    int const c = (int)(cs/sets);
+    double const *set = levels + cs*2*(uint64_t)nb*V;
+    double const *up = q < lw_bins ? set + (uint64_t)q*V : set + (2*(uint64_t)lw_bins + (q - lw_bins))*V;
+    double const *dn = up + (uint64_t)(q < lw_bins ? lw_bins : sw_bins)*V;
+    double const *p = pressure + (uint64_t)c*V;
+    double const net_top = dn[j] - up[j], net_bottom = dn[j + 1] - up[j + 1];
+    heating[(cs*nb + q)*L + j] = (gravity/cp)*((net_top - net_bottom)/(100.*(p[j + 1] - p[j])))*86400.;
+}
+
 } // namespace
+
+extern "C" int grt_launch_band_profile_finish(void *stream, int ncol, int sets, int num_levels, int lw_bins, int sw_bins,
+                                              double gravity, double cp, double const *pressure, double const *levels,
+                                              double *heating)
+{
+    if (ncol < 1 || sets < 1 || sets > 2 || num_levels < 2 || lw_bins < 0 || sw_bins < 0 || lw_bins + sw_bins < 1 ||
+        levels == nullptr || heating == nullptr || pressure == nullptr)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    uint64_t const threads = (uint64_t)ncol*sets*(uint64_t)(lw_bins + sw_bins)*(uint64_t)(num_levels - 1);
+    hipLaunchKernelGGL(band_profile_finish_kernel, dim3((unsigned)((threads + kBlock - 1)/kBlock)), dim3(kBlock), 0,
+                       (hipStream_t)stream, ncol, sets, num_levels, lw_bins, sw_bins, gravity, cp, pressure, levels,
+                       heating);
+    return (int)hipGetLastError();
+}
 
 extern "C" int grt_launch_profile_finish(void *stream, int ncol, int sets, int num_levels, int bands, int user_level,
                                          double gravity, double cp, double const *pressure, double *levels, double *heating,
@@ -677,11 +726,65 @@ extern "C" int grt_launch_bin_rows(void *stream, double const *in, uint64_t in_s
     // (each workgroup takes every kBinRowGroups-th row: a few thousand workgroups per launch, not one per row)
     unsigned const gy = (unsigned)(nrows < kBinRowGroups ? nrows : kBinRowGroups);
     hipStream_t const s = (hipStream_t)stream;
-    hipLaunchKernelGGL(bin_partials_kernel, dim3(bin_blocks(nw), gy), dim3(kSolverBlock), 0, s, in, in_stride, nrows, nw,
-                       dw, nbins, table_dev, (uint64_t)partials_per_row, partials);
-    hipLaunchKernelGGL(bin_reduce_kernel, dim3((unsigned)nbins, gy), dim3(64), 0, s, nrows, nbins, table_dev,
+    hipLaunchKernelGGL(bin_partials_kernel, dim3(bin_blocks(nw), gy), dim3(kSolverBlock), 0, s, in, in_stride,
+                       (double const *const *)nullptr, nrows, nw, dw, nbins, table_dev, (uint64_t)partials_per_row,
+                       partials);
+    hipLaunchKernelGGL(bin_reduce_kernel, dim3((unsigned)nbins, gy), dim3(64), 0, s, nrows, 6, 0, nbins, table_dev,
                        (uint64_t)partials_per_row, (double const *)partials, out, out_stride);
     return (int)hipGetLastError();
+}
+
+extern "C" int grt_bin_block_max(int const *edges_h, int nbins)
+{
+    // (the bins of a block are consecutive; the fullest block is the last block of the first of its bins)
+    int most = 0;
+    for (int b = 0; b < nbins; ++b)
+    {
+        int const last = edges_h[b + 1]/kSolverBlock;
+        int j = b;
+        while (j < nbins && edges_h[j]/kSolverBlock <= last)
+        {
+            ++j;
+        }
+        most = j - b > most ? j - b : most;
+    }
+    return most;
+}
+
+extern "C" int grt_launch_bin_reduce(void *stream, int nrows, int num_levels, int nbins, int const *table_dev,
+                                     size_t partials_per_row, double const *partials, double *out, uint64_t out_stride)
+{
+    if (nrows < 1 || nbins < 1)
+    {
+        return 0;
+    }
+    if (num_levels < 1 || nrows % (2*num_levels) != 0 || table_dev == nullptr || partials == nullptr || out == nullptr)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    unsigned const gy = (unsigned)(nrows < kBinRowGroups ? nrows : kBinRowGroups);
+    hipLaunchKernelGGL(bin_reduce_kernel, dim3((unsigned)nbins, gy), dim3(64), 0, (hipStream_t)stream, nrows, 2*num_levels,
+                       num_levels, nbins, table_dev, (uint64_t)partials_per_row, partials, out, out_stride);
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_bin_level_rows(void *stream, double const *const *rows_dev, int nrows, int num_levels, uint64_t nw,
+                                         double dw, int nbins, int const *table_dev, size_t partials_per_row,
+                                         double *partials, double *out, uint64_t out_stride)
+{
+    if (nrows < 1 || nbins < 1)
+    {
+        return 0;
+    }
+    if (rows_dev == nullptr || table_dev == nullptr || partials == nullptr || nw < 2)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    unsigned const gy = (unsigned)(nrows < kBinRowGroups ? nrows : kBinRowGroups);
+    hipLaunchKernelGGL(bin_partials_kernel, dim3(bin_blocks(nw), gy), dim3(kSolverBlock), 0, (hipStream_t)stream,
+                       (double const *)nullptr, (uint64_t)0, rows_dev, nrows, nw, dw, nbins, table_dev,
+                       (uint64_t)partials_per_row, partials);
+    return grt_launch_bin_reduce(stream, nrows, num_levels, nbins, table_dev, partials_per_row, partials, out, out_stride);
 }
 
 extern "C" int grt_launch_copy_rows(void *stream, double const *const *rows_dev, int nrows, uint64_t nw, double *out,

@@ -17,7 +17,8 @@
 // not HBM-bound.  sw_kernel<true, false>, the fused form of the production pipeline, therefore trades bytes for flops: its first
 // sweep parks the five properties of every layer with the reflectances and its second sweep reads them back (the same
 // doubles: identical fluxes) -- 0.69 instead of 1.04 ms for 8 columns, at 4.2 TB/s.  sw_kernel<true, false, true> is its
-// all-sky form, sw_kernel<true, true> and sw_kernel<true, true, true> the profile forms of the two, sw_kernel<true, false, false,
+// all-sky form, sw_kernel<true, true> and sw_kernel<true, true, true> the profile forms of the two (with a GrtBandArgs
+// last: their banded forms, a level's flux per wavenumber bin), sw_kernel<true, false, false,
 // true> and sw_kernel<true, false, true, true> the spectral six-row forms of the two, and sw_kernel<true, *, true, false,
 // GrtSubcolumnArgs> the all-sky forms over several subcolumns per column, and sw_kernel<true, *, false, false,
 // GrtAerosolArgs> the clear-sky forms with the aerosol object (the argument's type selects them: LayerOptics).
@@ -277,7 +278,7 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Clouds...
     // divisions a layer, which is what this kernel's time is made of)
     double *pp = FUSED ? a.park + ((uint64_t)row.park*park_rows + 2*(uint64_t)V)*nw + ii : nullptr;
     int const user = a.user_level;
-    LevelSink<FUSED, PROFILE, SPECTRAL> sink(a, row.slot, i, live);
+    LevelSink<FUSED, PROFILE, SPECTRAL, IsBandPack<Clouds...>::value> sink(a, row.slot, i, live, band_args(clouds...));
     LayerOptics<FUSED, ALLSKY, IsAerosolPack<Clouds...>::value> const optics(a, cloud_args(clouds...), col, row.tab, ii,
                                                                              aerosol_args(clouds...));   // (fused forms)
 
@@ -606,6 +607,29 @@ extern "C" int grt_launch_sw_subcolumns(void *stream, int profile, GrtSwArgs con
     {
         hipLaunchKernelGGL((sw_kernel<true, false, true, false, GrtSubcolumnArgs>), grid, dim3(kSolverBlock), 0, s, *a,
                            *sc);
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_sw_bands(void *stream, GrtSwArgs const *a, GrtCloudArgs const *c, GrtBandArgs const *bn)
+{
+    if (!grt_band_args_ok(bn) || a->ncol < 1 || a->ncol > 65535 || a->nw < 2 || a->num_levels < 2 ||
+        a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr || a->park == nullptr ||
+        (c != nullptr && !grt_cloud_args_ok(c)) || grt_band_profile_lds(bn, a->num_levels, kSolverBlock) > 65536)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    size_t const lds = grt_band_profile_lds(bn, a->num_levels, kSolverBlock);
+    hipStream_t const s = (hipStream_t)stream;
+    dim3 const grid((unsigned)((a->nw + kSolverBlock - 1)/kSolverBlock), a->ncol, 1);
+    if (c != nullptr)
+    {
+        hipLaunchKernelGGL((sw_kernel<true, true, true, false, GrtCloudArgs, GrtBandArgs>), grid, dim3(kSolverBlock), lds, s,
+                           *a, *c, *bn);
+    }
+    else
+    {
+        hipLaunchKernelGGL((sw_kernel<true, true, false, false, GrtBandArgs>), grid, dim3(kSolverBlock), lds, s, *a, *bn);
     }
     return (int)hipGetLastError();
 }

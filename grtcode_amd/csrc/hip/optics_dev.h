@@ -101,6 +101,16 @@ __device__ __forceinline__ GrtCloudArgs cloud_args(GrtAerosolArgs const &)
     return cloud_args();
 }
 
+__device__ __forceinline__ GrtCloudArgs cloud_args(GrtBandArgs const &)
+{
+    return cloud_args();
+}
+
+__device__ __forceinline__ GrtCloudArgs cloud_args(GrtCloudArgs const &c, GrtBandArgs const &)
+{
+    return c;
+}
+
 // ... and their aerosol arguments: one GrtAerosolArgs in the aerosol instances (the same pack), none in the others
 template <typename... Pack> struct IsAerosolPack { static constexpr bool value = false; };
 template <> struct IsAerosolPack<GrtAerosolArgs> { static constexpr bool value = true; };
@@ -114,6 +124,27 @@ __device__ __forceinline__ GrtAerosolArgs aerosol_args(Pack const &...)
 __device__ __forceinline__ GrtAerosolArgs aerosol_args(GrtAerosolArgs const &c)
 {
     return c;
+}
+
+// ... and their wavenumber bins: a GrtBandArgs closes the pack of the banded profile instances (LevelSink), none in the others
+template <typename... Pack> struct IsBandPack { static constexpr bool value = false; };
+template <> struct IsBandPack<GrtBandArgs> { static constexpr bool value = true; };
+template <> struct IsBandPack<GrtCloudArgs, GrtBandArgs> { static constexpr bool value = true; };
+
+template <typename... Pack>
+__device__ __forceinline__ GrtBandArgs band_args(Pack const &...)
+{
+    return GrtBandArgs{0, 0, nullptr, 0};
+}
+
+__device__ __forceinline__ GrtBandArgs band_args(GrtBandArgs const &b)
+{
+    return b;
+}
+
+__device__ __forceinline__ GrtBandArgs band_args(GrtCloudArgs const &, GrtBandArgs const &b)
+{
+    return b;
 }
 
 // What grid row blockIdx.y stands for: col, the column whose gas state (tau_gas, temperatures, sun) it reads; tab, its
@@ -134,6 +165,18 @@ __device__ __forceinline__ SolverRow solver_row(int, GrtCloudArgs const &)
 }
 
 __device__ __forceinline__ SolverRow solver_row(int, GrtAerosolArgs const &)
+{
+    int const y = blockIdx.y;
+    return SolverRow{y, y, y, y};
+}
+
+__device__ __forceinline__ SolverRow solver_row(int, GrtBandArgs const &)
+{
+    int const y = blockIdx.y;
+    return SolverRow{y, y, y, y};
+}
+
+__device__ __forceinline__ SolverRow solver_row(int, GrtCloudArgs const &, GrtBandArgs const &)
 {
     int const y = blockIdx.y;
     return SolverRow{y, y, y, y};
@@ -426,7 +469,13 @@ struct LayerOptics
 // SPECTRAL (fused six-row form only): finish() also stores each live point's six values, unweighted, to the caller's
 // rows -- up TOA, surface, user at flux_up + c flux_stride + k nw (k = 0, 1, 2), down at flux_down + ... -- before it
 // weights them (grt_pipeline_run_spectral).
-template <bool FUSED, bool PROFILE, bool SPECTRAL = false>
+// BANDED (profile form only; grt_pipeline_run_band_profiles): a level's flux leaves once per wavenumber bin that has a
+// point in this workgroup (GrtBandArgs: grt_bin_table's list for the block), weighted with that bin's trapezoid weights
+// (bin_partials_kernel's rule).  A workgroup inside one bin keeps one weight per point and does the profile form's work;
+// one that holds edges sums each level once per bin, the weight formed from the bin's two edges where it is used.  The
+// waves' sums wait in dynamic LDS, [bins of the block][2 V][kSolverBlock/64], and finish() stores bin b's at
+// partials[(c*2 V + r)*per_row + offset(b) + block - first_block(b)].
+template <bool FUSED, bool PROFILE, bool SPECTRAL = false, bool BANDED = false>
 struct LevelSink
 {
     double *fu, *fd;            // spectral forms (and SPECTRAL): flux_up / flux_down at this thread's point
@@ -435,9 +484,13 @@ struct LevelSink
     double pwt;                 // PROFILE: this point's trapezoid weight
     bool live;
     double out[6];
+    GrtBandArgs bins;           // BANDED
+    int bin_lo, bin_count;      // ... the first bin with a point in this workgroup, and how many there are
+    double dw;
 
     template <typename Args>
-    __device__ __forceinline__ LevelSink(Args const &a, int col_, uint64_t i_, bool live_)
+    __device__ __forceinline__ LevelSink(Args const &a, int col_, uint64_t i_, bool live_,
+                                         GrtBandArgs const &bins_ = GrtBandArgs{0, 0, nullptr, 0})
     {
         col = col_;
         i = i_;
@@ -447,7 +500,17 @@ struct LevelSink
         user = a.user_level;
         fu = FUSED && !SPECTRAL ? nullptr : a.flux_up + (uint64_t)col*a.flux_stride + i;
         fd = FUSED && !SPECTRAL ? nullptr : a.flux_down + (uint64_t)col*a.flux_stride + i;
-        pwt = PROFILE ? trapezoid_weight(i, nw, a.dw, live) : 0.;
+        pwt = PROFILE && !BANDED ? trapezoid_weight(i, nw, a.dw, live) : 0.;
+        bins = bins_;
+        bin_lo = bin_count = 0;
+        dw = a.dw;
+        if (BANDED)
+        {
+            int const *blk = bins.table + 4*bins.num_bins + 2*blockIdx.x;
+            bin_lo = blk[0];
+            bin_count = blk[1] - blk[0];
+            pwt = bin_count == 1 ? bin_weight(bin_lo) : 0.;
+        }
 #pragma unroll
         for (int k = 0; k < 6; ++k)
         {
@@ -457,8 +520,17 @@ struct LevelSink
 
     static __device__ __forceinline__ double *level_sums()
     {
-        extern __shared__ double level_sums_[];     // PROFILE: [2 V][kSolverBlock/64]
+        extern __shared__ double level_sums_[];     // PROFILE: [2 V][kSolverBlock/64]; BANDED: that per bin of the block
         return level_sums_;
+    }
+
+    // BANDED: this point's trapezoid weight in bin b -- dw/2 at the bin's two edges, dw between them, 0 elsewhere (an idle
+    // lane lies beyond every edge)
+    __device__ __forceinline__ double bin_weight(int b) const
+    {
+        int const *e = bins.table + 4*b;
+        long long const at = (long long)i;
+        return (at == e[0] || at == e[1]) ? 0.5*dw : ((at > e[0] && at < e[1]) ? dw : 0.);
     }
 
     // whether a flux of level lev leaves the kernel
@@ -470,7 +542,14 @@ struct LevelSink
     // level lev's upward (down false) or downward flux at this point is x
     __device__ __forceinline__ void put(int lev, bool down, double x)
     {
-        if (PROFILE)
+        if (PROFILE && BANDED && bin_count != 1)
+        {
+            for (int q = 0; q < bin_count; ++q)
+            {
+                wave_row_sum<kSolverBlock>(x*bin_weight(bin_lo + q), level_sums(), q*2*V + (down ? V : 0) + lev);
+            }
+        }
+        else if (PROFILE)
         {
             wave_row_sum<kSolverBlock>(x*pwt, level_sums(), (down ? V : 0) + lev);
         }
@@ -494,7 +573,10 @@ struct LevelSink
         {
             if ((threadIdx.x & 63) == 0)
             {
-                level_sums()[((down ? V : 0) + lev)*(kSolverBlock/64) + (threadIdx.x >> 6)] = 0.;
+                for (int q = 0; q < (BANDED ? bin_count : 1); ++q)
+                {
+                    level_sums()[(q*2*V + (down ? V : 0) + lev)*(kSolverBlock/64) + (threadIdx.x >> 6)] = 0.;
+                }
             }
         }
         else
@@ -507,7 +589,24 @@ struct LevelSink
     template <typename Args>
     __device__ __forceinline__ void finish(Args const &a)
     {
-        if (PROFILE)
+        if (PROFILE && BANDED)
+        {
+            // (block_row_partials per bin of the block: the waves' sums in wave order)
+            __syncthreads();
+            double const *lds = level_sums();
+            for (int k = threadIdx.x; k < bin_count*2*V; k += kSolverBlock)
+            {
+                int const q = k/(2*V), r = k - q*2*V;
+                int const *e = bins.table + 4*(bin_lo + q);
+                double s = lds[k*(kSolverBlock/64)];
+                for (int w = 1; w < kSolverBlock/64; ++w)
+                {
+                    s += lds[k*(kSolverBlock/64) + w];
+                }
+                a.partials[((uint64_t)col*2*V + r)*bins.per_row + e[2] + (int)blockIdx.x - e[3]] = s;
+            }
+        }
+        else if (PROFILE)
         {
             block_row_partials<kSolverBlock>(level_sums(), 2*V, a.partials, (uint64_t)col*2*V, gridDim.x, blockIdx.x);
         }

@@ -27,7 +27,9 @@
  * grt_pipeline_run_aerosols runs the clear-clean pass of grt_pipeline_run or grt_pipeline_run_profiles and then, on the
  * same tau_gas, the clear-sky pass with aerosols of driver.c:426-472: the aerosol object formed inside the solvers from
  * per-column slope and intercept tables (or, materialised form, spread onto the grid and added by the add_optics kernel).
- * All work is enqueued on the device's library stream; nothing synchronises.
+ * grt_pipeline_run_band_profiles runs the profile form of the clear-sky pass and, with clouds, of the all-sky pass with
+ * every level's flux integrated per wavenumber bin instead of over the whole grid, and one finishing launch for the bins'
+ * heating rates.
  * All work is enqueued on the device's library stream; nothing synchronises.
  * Here: the object, the small per-column inputs, the gas optics, the run and the entry points with their checks;
  * grt_pipeline_inputs.c stages what a caller gives besides the columns, grt_pipeline_solve.c solves one band.
@@ -426,6 +428,10 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t 
             }
             continue;
         }
+        if (rows->bp != NULL && rows->bp->num_bins[bi] == 0)
+        {
+            continue;                  /* (a band without bins has no rows: nothing of it is computed) */
+        }
         GrtCloudArgs ca;
         if (cl != NULL)
         {
@@ -730,5 +736,64 @@ EXTERN int grt_pipeline_run_spectral(GrtPipeline_t *p, GrtColumns_t const *cols,
     GrtPass const rows = {.profile = 0, .out = fluxes_dev, .so = &so,
                           .out_stride = cl != NULL ? GRT_ALLSKY_FLUXES_PER_COLUMN : GRT_FLUXES_PER_COLUMN};
     GRT_TRY(pipeline_run(p, cols, cl, NULL, 0, &rows));
+    return GRTCODE_SUCCESS;
+}
+
+EXTERN int grt_pipeline_band_profile_bin_limit(GrtPipeline_t const *p)
+{
+    if (p == NULL || p->num_levels < 1)
+    {
+        return 0;
+    }
+    /* the fused solvers' wave sums of one workgroup, 2 V rows x 2 waves x 8 bytes per bin, in 64 KiB of LDS */
+    return 65536/(32*p->num_levels);
+}
+
+EXTERN int grt_pipeline_run_band_profiles(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl,
+                                          int const *lw_edges, int lw_num_bins, int const *sw_edges, int sw_num_bins,
+                                          fp_t *band_levels_dev, fp_t *band_heating_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    if (band_levels_dev == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "band_levels_dev is NULL: the level fluxes per bin are the output.%s", "");
+    }
+    GRT_TRY(check_bins(p, 0, lw_edges, lw_num_bins, band_levels_dev));
+    GRT_TRY(check_bins(p, 1, sw_edges, sw_num_bins, band_levels_dev));
+    if (lw_num_bins + sw_num_bins == 0)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "no bins in either band: nothing to write.%s", "");
+    }
+    GRT_TRY(check_two_levels(p));
+    int const *edges[2] = {lw_edges, sw_edges};
+    int const num_bins[2] = {lw_num_bins, sw_num_bins};
+    int const limit = grt_pipeline_band_profile_bin_limit(p);
+    for (int bi = 0; bi < 2; ++bi)
+    {
+        int const most = num_bins[bi] > 0 ? grt_bin_block_max(edges[bi], num_bins[bi]) : 0;
+        if (most > limit)
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s bins have a point in one block of 128 grid points: at most %d with %d levels "
+                     "(grt_pipeline_band_profile_bin_limit).", most, bi == 0 ? "longwave" : "shortwave", limit,
+                     p->num_levels);
+        }
+    }
+    GRT_TRY(cl != NULL ? check_clouds(p, cols, cl) : check_columns(p, cols));
+    int const sets = cl != NULL ? 2 : 1, V = p->num_levels;
+    BandProfileOut const bp = {.sets = sets, .edges = {lw_edges, sw_edges}, .num_bins = {lw_num_bins, sw_num_bins}};
+    GrtPass const rows = {.profile = 1, .out = band_levels_dev, .bp = &bp,
+                          .out_stride = sets*2*(lw_num_bins + sw_num_bins)*V};
+    GRT_TRY(pipeline_run(p, cols, cl, NULL, 0, &rows));
+    if (band_heating_dev != NULL)
+    {
+        void *s = grt_dev_stream(p->device);
+        int const slot = grt_profile_begin(s, 14);
+        int const krc = grt_launch_band_profile_finish(s, cols->ncol, sets, V, lw_num_bins, sw_num_bins, GRT_GRAVITY,
+                                                       GRT_SPECIFIC_HEAT_AIR, p->small.d + p->off_p, band_levels_dev,
+                                                       band_heating_dev);
+        grt_profile_end(s, slot);
+        GRT_TRY(grt_dev_check(krc, "band heating rate kernel"));
+    }
     return GRTCODE_SUCCESS;
 }

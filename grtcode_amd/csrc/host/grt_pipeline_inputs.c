@@ -320,23 +320,24 @@ static int fill_bin_table(void *ctx, int *table)
 }
 
 /* the band's bin table for these edges (built and uploaded when they differ from the last call's) and room for the partial
-   sums of max_cols x 6 rows */
-int grt_band_bins(GrtPipeline_t *p, GrtBand *b, int const *edges, int nbins)
+   sums of max_cols x `rows` rows */
+int grt_band_bins(GrtPipeline_t *p, GrtBand *b, int const *edges, int nbins, int rows)
 {
     BinTableFill f = {edges, nbins, b->n, b->bin_per_row};
     GRT_TRY(grt_keyed_table(p, &b->bin_table, edges, sizeof(int)*((size_t)nbins + 1), grt_bin_table_ints(nbins, b->n),
                             fill_bin_table, &f));
     b->bin_per_row = f.per_row;
-    if (b->bin_per_row > b->bin_cap)
+    size_t const need = (size_t)rows*b->bin_per_row;
+    if (need > b->bin_cap)
     {
         GRT_TRY(grt_dev_sync(p->device, grt_dev_stream(p->device)));
         grt_dev_free(p->device, b->bin_partials);
         b->bin_partials = NULL;
         b->bin_cap = 0;
         void *pt = NULL;
-        GRT_TRY(grt_dev_alloc(p->device, &pt, sizeof(double)*(size_t)p->max_cols*6*b->bin_per_row));
+        GRT_TRY(grt_dev_alloc(p->device, &pt, sizeof(double)*(size_t)p->max_cols*need));
         b->bin_partials = pt;
-        b->bin_cap = b->bin_per_row;
+        b->bin_cap = need;
     }
     return GRTCODE_SUCCESS;
 }

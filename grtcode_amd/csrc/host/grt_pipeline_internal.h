@@ -54,11 +54,12 @@ typedef struct GrtBand
        aerosol: 3), grown when a pass needs more arrays */
     double *spread_block;
     int spread_arrays;
-    /* grt_pipeline_run_spectral's bins: grt_bin_table of the edges [bin_count + 1] (its key) */
+    /* grt_pipeline_run_spectral's and grt_pipeline_run_band_profiles' bins (they run in stream order): grt_bin_table of
+       the edges [bin_count + 1] (its key) */
     GrtKeyedTable bin_table;
     size_t bin_per_row;    /* partial sums per row */
-    double *bin_partials;  /* [max_cols][6][bin_cap] */
-    size_t bin_cap;
+    double *bin_partials;  /* [max_cols][6 or 2 V][bin_per_row] */
+    size_t bin_cap;        /* its doubles per column */
     /* grt_pipeline_run_subcolumns, allocated at the first call that needs them (or more of them): */
     double *sub_partials;  /* fused form: [max_cols][S][6 or 2 V][nblocks] partial sums of the all-sky pass */
     size_t sub_cap;        /* its doubles */
@@ -91,11 +92,20 @@ typedef struct SpectralOut
     int num_bins[2];
 } SpectralOut;
 
+/* grt_pipeline_run_band_profiles' bins: every level's flux of `sets` sets per column, per bin of the band's edges */
+typedef struct BandProfileOut
+{
+    int sets;
+    int const *edges[2];
+    int num_bins[2];
+} BandProfileOut;
+
 /* One solve of a band on the run's tau_gas.  What joins gas and Rayleigh: nothing (clear sky), the cloud objects (all-sky
    pass) or the aerosol object (aerosol pass; aer NULL there: a band that was given no aerosol, which runs the clear-sky
    form under the aerosol pass's profile tags).  Which rows leave: the six of driver.c:272-280 or (profile) every level's
    up then down flux, to set `set` of the column's out_stride doubles at out; with so, the six rows at every point and
-   their bins too (grt_pipeline_run_spectral). */
+   their bins too (grt_pipeline_run_spectral); with bp (profile), every level's flux per bin of bp's edges instead, to
+   out's [ncol][sets][2 lw bins + 2 sw bins][V] (grt_pipeline_run_band_profiles). */
 typedef struct GrtPass
 {
     GrtCloudArgs const *clouds;
@@ -108,6 +118,7 @@ typedef struct GrtPass
     int out_stride;
     int set;                       /* 0: the clear-sky set; 1: the all-sky or aerosol set that follows it */
     SpectralOut const *so;
+    BandProfileOut const *bp;
 } GrtPass;
 
 /* the doubles from a column's clear-sky set to its all-sky or aerosol set */
@@ -133,7 +144,7 @@ GRT_PRIVATE int grt_stage_clouds(GrtPipeline_t *p, GrtClouds_t const *cl, int C,
 GRT_PRIVATE int grt_band_clouds(GrtPipeline_t *p, GrtBand *b, int bi, GrtClouds_t const *cl, int C, int S, GrtCloudArgs *ca);
 GRT_PRIVATE int grt_stage_aerosols(GrtPipeline_t *p, GrtAerosols_t const *ae, int C);
 GRT_PRIVATE int grt_band_aerosols(GrtPipeline_t *p, GrtBand *b, int bi, GrtAerosols_t const *ae, int C, GrtAerosolArgs *aa);
-GRT_PRIVATE int grt_band_bins(GrtPipeline_t *p, GrtBand *b, int const *edges, int nbins);
+GRT_PRIVATE int grt_band_bins(GrtPipeline_t *p, GrtBand *b, int const *edges, int nbins, int rows);
 
 /* grt_pipeline_solve.c */
 GRT_PRIVATE int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps);

@@ -116,8 +116,9 @@ static int park_block(GrtPipeline_t *p, GrtBand *b)
 
 /* the band's solver in the pass's form, timed under the pass's profile tag; the profile forms share the band's park block
    with the two-sweep six-row forms (the passes run in stream order); the spectral six-row forms store their rows where
-   the pass's so places the band's */
-static int band_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps, double *partials)
+   the pass's so places the band's; with bn (profile forms), their banded instances */
+static int band_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps, double *partials,
+                       GrtBandArgs const *bn)
 {
     GrtSolverForm const form = pass_form(p, ps);
     GrtFormKind const k = grt_form_kind(form);
@@ -138,7 +139,7 @@ static int band_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass cons
             a.flux_stride = stride;
         }
         slot = grt_profile_begin(s, pass_tag(ps, bi));
-        krc = grt_launch_lw(s, form, &a, ps->clouds, ps->aer);
+        krc = bn != NULL ? grt_launch_lw_bands(s, &a, ps->clouds, bn) : grt_launch_lw(s, form, &a, ps->clouds, ps->aer);
     }
     else
     {
@@ -157,7 +158,7 @@ static int band_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass cons
         }
         a.park = b->park;
         slot = grt_profile_begin(s, pass_tag(ps, bi));
-        krc = grt_launch_sw(s, form, &a, ps->clouds, ps->aer);
+        krc = bn != NULL ? grt_launch_sw_bands(s, &a, ps->clouds, bn) : grt_launch_sw(s, form, &a, ps->clouds, ps->aer);
     }
     grt_profile_end(s, slot);
     GRT_TRY(grt_dev_check(krc, bi == 0 ? "longwave kernel" : "shortwave kernel"));
@@ -293,7 +294,7 @@ static int band_solve_spectral(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtP
     double *rows = so->spectral + spectral_offset(ps, bi, band_points(p, 0), band_points(p, 1), &stride);
     if (!p->keep_spectra)
     {
-        GRT_TRY(band_solver(p, b, bi, C, ps, b->partials));
+        GRT_TRY(band_solver(p, b, bi, C, ps, b->partials, NULL));
         GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, b->partials, C*GRT_FLUXES_PER_BAND, b->nblocks, ps->out,
                                                          GRT_FLUXES_PER_BAND, ps->out_stride, pass_offset(p, ps, bi)),
                               "flux reduction kernel"));
@@ -301,7 +302,7 @@ static int band_solve_spectral(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtP
     else
     {
         GRT_TRY(pass_optics(p, b, C, ps));
-        GRT_TRY(band_solver(p, b, bi, C, ps, NULL));
+        GRT_TRY(band_solver(p, b, bi, C, ps, NULL, NULL));
         GRT_TRY(grt_dev_check(grt_launch_copy_rows(s, (double const *const *)b->rows_d, C*GRT_FLUXES_PER_BAND, b->n,
                                                    rows, stride), "spectral row copy kernel"));
         GRT_TRY(integrate_rows(p, b, bi, C, ps));
@@ -309,7 +310,7 @@ static int band_solve_spectral(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtP
     int const nbins = so->num_bins[bi];
     if (nbins > 0)
     {
-        GRT_TRY(grt_band_bins(p, b, so->edges[bi], nbins));
+        GRT_TRY(grt_band_bins(p, b, so->edges[bi], nbins, GRT_FLUXES_PER_BAND));
         size_t bstride;
         double *binned = so->binned + spectral_offset(ps, bi, (size_t)so->num_bins[0], (size_t)so->num_bins[1], &bstride);
         int const slot = grt_profile_begin(s, 10);
@@ -318,6 +319,42 @@ static int band_solve_spectral(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtP
         grt_profile_end(s, slot);
         GRT_TRY(grt_dev_check(krc, "spectral binning kernel"));
     }
+    return GRTCODE_SUCCESS;
+}
+
+/* One solve of a band for grt_pipeline_run_band_profiles: every level's up and down flux per bin of the band's edges,
+   into the band's [2][bins][V] of the pass's set.  Fused form: the banded instance of the profile solver, whose partial
+   sums lie where the bin table places them, and each bin's blocks added in a fixed order; materialised form: the
+   spectral solver, then the binning kernel on its 2 V flux rows per column.  The reduction counts under profile tag 14. */
+static int band_solve_band_profiles(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps)
+{
+    BandProfileOut const *bp = ps->bp;
+    void *s = grt_dev_stream(p->device);
+    int const V = p->num_levels, rows = 2*V, nbins = bp->num_bins[bi];
+    size_t const set_doubles = 2*((size_t)bp->num_bins[0] + (size_t)bp->num_bins[1])*(size_t)V;
+    double *out = ps->out + (size_t)ps->set*set_doubles + (bi == 1 ? 2*(size_t)bp->num_bins[0]*(size_t)V : 0);
+    uint64_t const out_stride = (uint64_t)bp->sets*set_doubles;
+    GRT_TRY(grt_band_bins(p, b, bp->edges[bi], nbins, rows));
+    int slot, krc;
+    if (!p->keep_spectra)
+    {
+        GrtBandArgs const bn = {nbins, grt_bin_block_max(bp->edges[bi], nbins), b->bin_table.table, b->bin_per_row};
+        GRT_TRY(band_solver(p, b, bi, C, ps, b->bin_partials, &bn));
+        slot = grt_profile_begin(s, 14);
+        krc = grt_launch_bin_reduce(s, C*rows, V, nbins, b->bin_table.table, b->bin_per_row, b->bin_partials, out,
+                                    out_stride);
+    }
+    else
+    {
+        GRT_TRY(pass_optics(p, b, C, ps));
+        GRT_TRY(band_solver(p, b, bi, C, ps, NULL, NULL));
+        GRT_TRY(level_rows(p, b));
+        slot = grt_profile_begin(s, 14);
+        krc = grt_launch_bin_level_rows(s, (double const *const *)b->level_rows_d, C*rows, V, b->n, b->gas->grid.dw, nbins,
+                                        b->bin_table.table, b->bin_per_row, b->bin_partials, out, out_stride);
+    }
+    grt_profile_end(s, slot);
+    GRT_TRY(grt_dev_check(krc, "level binning kernel"));
     return GRTCODE_SUCCESS;
 }
 
@@ -333,10 +370,15 @@ int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *p
         GRT_TRY(band_solve_spectral(p, b, bi, C, ps));
         return GRTCODE_SUCCESS;
     }
+    if (ps->bp != NULL)
+    {
+        GRT_TRY(band_solve_band_profiles(p, b, bi, C, ps));
+        return GRTCODE_SUCCESS;
+    }
     if (p->keep_spectra)
     {
         GRT_TRY(pass_optics(p, b, C, ps));
-        GRT_TRY(band_solver(p, b, bi, C, ps, NULL));
+        GRT_TRY(band_solver(p, b, bi, C, ps, NULL, NULL));
         GRT_TRY(integrate_rows(p, b, bi, C, ps));
         return GRTCODE_SUCCESS;
     }
@@ -348,7 +390,7 @@ int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *p
         b->level_partials = lp;
     }
     double *partials = ps->profile ? b->level_partials : b->partials;
-    GRT_TRY(band_solver(p, b, bi, C, ps, partials));
+    GRT_TRY(band_solver(p, b, bi, C, ps, partials, NULL));
     GRT_TRY(grt_dev_check(grt_launch_reduce_partials(grt_dev_stream(p->device), partials, C*rows, b->nblocks, ps->out, rows,
                                                      ps->out_stride, pass_offset(p, ps, bi)), "flux reduction kernel"));
     return GRTCODE_SUCCESS;
@@ -438,7 +480,7 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
         GrtPass pj = *ps;
         pj.clouds = &cj;
         GRT_TRY(pass_optics(p, b, C, &pj));
-        GRT_TRY(band_solver(p, b, bi, C, &pj, NULL));
+        GRT_TRY(band_solver(p, b, bi, C, &pj, NULL, NULL));
         GRT_TRY(grt_dev_check(grt_launch_flux_accumulate(s, per, b->flux_up, b->flux_sum, j == 0), "flux sum kernel"));
         GRT_TRY(grt_dev_check(grt_launch_flux_accumulate(s, per, b->flux_down, b->flux_sum + all, j == 0),
                               "flux sum kernel"));

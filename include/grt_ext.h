@@ -347,6 +347,44 @@ EXTERN int grt_pipeline_run_spectral(GrtPipeline_t *pipeline, GrtColumns_t const
                                      int const *lw_edges, int lw_num_bins, int const *sw_edges, int sw_num_bins,
                                      fp_t *spectral_dev, fp_t *binned_dev, fp_t *fluxes_dev);
 
+/* ---- level fluxes and heating rates per wavenumber bin ----------------------------------------------------------------
+ * What a band model is compared against: every level's upward and downward flux, and every layer's heating rate,
+ * integrated over wavenumber bins instead of over the whole grid, for a batch of columns, clear sky (clouds NULL) or clear
+ * sky and all-sky (clouds as grt_pipeline_run_allsky takes them).  sets = 1 without clouds, 2 with them (the clear-sky set
+ * first, as grt_pipeline_run_allsky_profiles).  lw_edges, sw_edges: as grt_pipeline_run_spectral takes them -- HOST arrays
+ * of num_bins + 1 strictly increasing grid-point indices in 0 .. n - 1, adjacent bins sharing their edge point; NULL / 0:
+ * no bins for that band, which is then not computed and takes no room; at least one band must have bins.
+ *   band_levels_dev  [ncol][sets][2 lw_num_bins + 2 sw_num_bins][V] (required): per set the longwave's [2][lw_num_bins][V]
+ *                    (upward, then downward), then the shortwave's [2][sw_num_bins][V]; W m-2, levels top first.  Bin b of
+ *                    a level is the trapezoid sum_{i = edges[b]}^{edges[b+1] - 1} 0.5 (f_i + f_{i+1}) dw of that level's
+ *                    spectral flux: contiguous bins add up to the bin over their union, and the single bin {0, n - 1} is
+ *                    the broadband level flux;
+ *   band_heating_dev [ncol][sets][lw_num_bins + sw_num_bins][V-1] (may be NULL), K day-1: grt_pipeline_run_profiles'
+ *                    formula and constants on each bin's level fluxes.
+ * Both are DEVICE memory; asynchronous on the pipeline's lane like grt_pipeline_run.  The shortwave always takes the
+ * reference's two sweeps, as grt_pipeline_run_profiles does; one gas-optics launch per band serves both sets.  The
+ * production form (keep_spectra = 0) runs the banded instances of the fused profile solvers: a point weights a level's
+ * value with the trapezoid weight of each bin it belongs to, a workgroup that lies inside one bin does the profile form's
+ * work, one that holds bin edges sums each level once per bin it holds; the partial sums, [max_columns][2 V][about
+ * num_bins + n/128] doubles per band (allocated at the first call that needs them, shared with
+ * grt_pipeline_run_spectral's), are added per bin in a fixed order (profile tag 14, with the heating-rate kernel).  In the
+ * deterministic mode the single bin {0, n - 1} per band gives grt_pipeline_run_profiles' level fluxes and heating rates
+ * bit for bit, and with clouds grt_pipeline_run_allsky_profiles' two sets.  keep_spectra = 1: the spectral solvers, then
+ * the same weights and sums on the [V][n] flux rows; afterwards grt_pipeline_views shows the last pass.  A new set of
+ * edges is uploaded (the call then waits for the lane).
+ * grt_pipeline_band_profile_bin_limit: the most bins that may have a point in one block of 128 consecutive grid points
+ * (block k: points 128 k .. 128 k + 127), floor(65536 / (32 V)) -- a workgroup's wave sums, 2 V rows x 2 waves x 8 bytes
+ * per bin, must fit the 64 KiB of LDS it gets; 33 at V = 61.  Bins of 128 or more points never come near it.
+ * GRTCODE_VALUE_ERR, with nothing launched and the outputs untouched, for: a NULL band_levels_dev; what
+ * grt_pipeline_run_spectral refuses in edges (bins for a band whose gas-optics object is NULL included); no bins in
+ * either band; fewer than 2 levels; more bins in one block than the limit; ncol outside 1 .. max_columns; and what
+ * grt_pipeline_run_allsky refuses in clouds. */
+EXTERN int grt_pipeline_run_band_profiles(GrtPipeline_t *pipeline, GrtColumns_t const *columns,
+                                          GrtClouds_t const *clouds, int const *lw_edges, int lw_num_bins,
+                                          int const *sw_edges, int sw_num_bins, fp_t *band_levels_dev,
+                                          fp_t *band_heating_dev);
+EXTERN int grt_pipeline_band_profile_bin_limit(GrtPipeline_t const *pipeline);
+
 /* ---- columns across the GPUs of one node ------------------------------------
  * One process per GPU; contiguous ceil-sized column blocks; one gather of the [columns][GRT_FLUXES_PER_COLUMN]
  * flux blocks to rank 0.  The reference fans out processes with -x/-X column ranges and merges per-shard files
@@ -371,7 +409,8 @@ EXTERN int grt_multi_destroy(GrtMulti_t **multi);
 /* local: this rank's [count][row_doubles] block; all (rank 0 only): room for world*ceil(num_columns/world) rows, the first
    num_columns of which are the columns in order (short blocks are padded, so no sizes are exchanged).  Any row width:
    e.g. 4 V + 2 (V - 1) for the level fluxes and heating rates of grt_pipeline_run_profiles, 8 V + 4 (V - 1) for those of
-   grt_pipeline_run_allsky_profiles. */
+   grt_pipeline_run_allsky_profiles, sets (2 NB V + NB (V - 1)) for the level fluxes and heating rates of
+   grt_pipeline_run_band_profiles with NB = lw_num_bins + sw_num_bins (two gathers: its two outputs are two buffers). */
 EXTERN int grt_multi_gather_rows(GrtMulti_t *multi, fp_t const *local, int num_columns, int row_doubles, fp_t *all,
                                  int on_device);
 /* grt_multi_gather_rows with rows of GRT_FLUXES_PER_COLUMN: the [count][12] blocks of grt_pipeline_run. */
@@ -388,7 +427,8 @@ EXTERN int grt_multi_max(GrtMulti_t *multi, double *value);    /* barrier + maxi
  * wavenumber-bin kernel of grt_pipeline_run_spectral (both of its launches; its solvers count under 3 / 4 and 8 / 9),
  * 11 = the subcolumn-mean kernel of grt_pipeline_run_subcolumns (with S > 1; its all-sky solvers count under 8 / 9, each
  * band's launches together), 12 / 13 = LW / SW solver of the aerosol pass of grt_pipeline_run_aerosols (its clear-clean
- * pass counts under 3 / 4).
+ * pass counts under 3 / 4), 14 = the per-bin reduction and the heating-rate kernel of grt_pipeline_run_band_profiles (its
+ * solvers count under 3 / 4 and 8 / 9).
  * Read after grt_pipeline_sync(). */
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
