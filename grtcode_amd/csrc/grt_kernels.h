@@ -257,10 +257,10 @@ typedef struct GrtLwArgs
     double const *t_layers, *t_levels, *t_surf;
     double const *emis; uint64_t emis_stride;
     double *flux_up, *flux_down;    /* [ncol][V][nw]; NULL in the fused form: nothing spectral is stored (spectral six-row
-                                       form: the six rows' bases, GrtFormKind) */
+                                       form: the six rows' bases, GRT_OUT_ROWS_POINTS) */
     uint64_t flux_stride;
     int user_level;                 /* -1: none */
-    /* Fused clear-sky form (driver.c:360-424 + 285-356 with -integrated in one kernel, GRT_SOLVER_FUSED): the
+    /* Fused clear-sky form (driver.c:360-424 + 285-356 with -integrated in one kernel, GRT_OUT_ROWS): the
        kernel forms Rayleigh (rayleigh.c:38-39) and the two-object combination (optics.c:138-145) per layer in
        registers from tau_gas [ncol][L][nw] (column stride optics_stride) and the air columns n_layer [ncol][L],
        and leave only the trapezoid partial sums of the six output rows (up TOA, up surface, up user, down TOA,
@@ -269,7 +269,7 @@ typedef struct GrtLwArgs
     double *partials;
     int add_continua;               /* fused form: tau_gas was written without the tables' part -- add it (continua) */
     GrtContinua continua;
-    /* spectral form, GRT_SOLVER_LAYERS: scratch [ncol][6 L][nw].  The four streams' extinctions and the two effective
+    /* spectral form, GRT_OUT_LAYERS: scratch [ncol][6 L][nw].  The four streams' extinctions and the two effective
        Planck terms of every layer are worked out first by one thread per (layer, wavenumber), and the two sweeps read
        them (the same doubles through the same expressions: identical fluxes) -- see GrtSwArgs.layer_props */
     double *layer_terms;
@@ -304,25 +304,19 @@ typedef struct GrtSwArgs
     /* fused form, no flux asked for between top and surface (user_level -1, 0 or num_levels - 1): ONE sweep from the top,
        nothing parked (k_shortwave.hip); 0: the two sweeps of the reference's order (GRT_SW_TWO_SWEEPS=1 in the environment) */
     int one_sweep;
-    /* spectral form, GRT_SOLVER_LAYERS: scratch [ncol][5 L][nw].  The five properties of every
+    /* spectral form, GRT_OUT_LAYERS: scratch [ncol][5 L][nw].  The five properties of every
        layer are worked out first by one thread per (layer, wavenumber) -- a column of 50 000 wavenumbers is then 3 million
        independent delta-Eddington pairs instead of 50 000 chains of 120 -- and the two sweeps read them (the same
        doubles through the same expressions: identical fluxes) */
     double *layer_props;
 } GrtSwArgs;
-/* whether the fused form takes its one sweep (the rule above; sw_kernel keeps its own copy); whether a fused form takes
-   the two sweeps and needs `park`; the dynamic LDS of a profile form, 2 V doubles per wave of its workgroup */
+/* whether the fused form takes its one sweep (the rule above; sw_kernel keeps its own copy) */
 static inline int grt_sw_one_sweep(GrtSwArgs const *a)
 {
     return a->one_sweep && (a->user_level < 0 || a->user_level == 0 || a->user_level == a->num_levels - 1);
 }
-static inline int grt_sw_parks(int profile, GrtSwArgs const *a) { return profile || !grt_sw_one_sweep(a); }
-static inline size_t grt_profile_lds(int profile, int num_levels, int block_threads)
-{
-    return profile ? sizeof(double)*2*(size_t)num_levels*(size_t)(block_threads/64) : 0;
-}
 
-/* Profile form of the fused solvers (GRT_SOLVER_PROFILE, grt_pipeline_run_profiles): the fused form's arguments, but every
+/* Profile form of the fused solvers (GRT_OUT_LEVELS, grt_pipeline_run_profiles): the fused form's arguments, but every
    level's upward and downward flux leaves as trapezoid partial sums, 2 V rows per column at
    partials[(c*2 V + r)*nblocks + block], r = level (up) and V + level (down), levels top first; reduced with
    grt_launch_reduce_partials(nrows = ncol*2 V).  The shortwave form always takes the two sweeps and needs `park`
@@ -336,11 +330,11 @@ static inline size_t grt_profile_lds(int profile, int num_levels, int block_thre
 int grt_launch_profile_finish(void *stream, int ncol, int sets, int num_levels, int bands, int user_level, double gravity,
                               double cp, double const *pressure, double *levels, double *heating, double *fluxes);
 
-/* All-sky form of the fused solvers (GRT_SOLVER_ALLSKY, grt_pipeline_run_allsky): the fused form's arguments (six-row
+/* All-sky form of the fused solvers (clouds joined, grt_pipeline_run_allsky): the fused form's arguments (six-row
    partial sums), and per layer the liquid and ice cloud objects formed in registers from the band tables below and combined with
    gas and Rayleigh by allsky_combine (optics_dev.h).  band_liquid / band_ice: DEVICE [nw] band of each grid point, -1 for
    none; thickness [ncol][L] m; liquid / ice [ncol][3][num_bands][L] (extinction m-1, albedo, asymmetry).
-   GRT_SOLVER_ALLSKY_PROFILE (grt_pipeline_run_allsky_profiles): the same cloud objects in the profile form -- its
+   With GRT_OUT_LEVELS (grt_pipeline_run_allsky_profiles): the same cloud objects in the profile form -- its
    partial sums, dynamic LDS and, shortwave, its two sweeps and park block; the cloud tables are read in the first sweep
    only. */
 typedef struct GrtCloudArgs
@@ -350,8 +344,13 @@ typedef struct GrtCloudArgs
     double const *thickness;
     double const *liquid, *ice;
 } GrtCloudArgs;
+static inline int grt_cloud_args_ok(GrtCloudArgs const *c)
+{
+    return c != NULL && c->num_bands >= 1 && c->band_liquid != NULL && c->band_ice != NULL && c->thickness != NULL &&
+           c->liquid != NULL && c->ice != NULL;
+}
 
-/* Aerosol form of the fused solvers (GRT_SOLVER_AEROSOL, GRT_SOLVER_AEROSOL_PROFILE; grt_pipeline_run_aerosols): the
+/* Aerosol form of the fused solvers (aerosols joined, six rows or every level; grt_pipeline_run_aerosols): the
    fused or the profile form's arguments, and per layer the aerosol object formed in registers and combined with gas and
    Rayleigh by aerosol_combine (optics_dev.h).  The aerosol's tau, omega, g are given per layer on a coarse wavenumber grid
    of NA points and put on the spectral grid by the reference's linear_sample (utilities.c:235-246): the host turns each
@@ -370,54 +369,12 @@ static inline int grt_aerosol_args_ok(GrtAerosolArgs const *c)
     return c != NULL && c->num_intervals >= 1 && c->interval != NULL && c->tables != NULL;
 }
 
-/* The kernel instances of each solver.  grt_launch_lw / grt_launch_sw launch the form they are given, after checking the
-   fields that form reads (hipErrorInvalidValue otherwise); `clouds` is read by the all-sky forms only, `aerosols` by the
-   two aerosol forms. */
-typedef enum GrtSolverForm
-{
-    GRT_SOLVER_CHAINS,      /* spectral: one thread per wavenumber and column through all the layers */
-    GRT_SOLVER_LAYERS,      /* spectral, the same fluxes: the layers' terms first (layer_terms / layer_props) */
-    GRT_SOLVER_FUSED,       /* fused clear-sky, six output rows */
-    GRT_SOLVER_PROFILE,     /* fused clear-sky, every level's up and down flux */
-    GRT_SOLVER_ALLSKY,      /* fused all-sky, six output rows */
-    GRT_SOLVER_ALLSKY_PROFILE,  /* fused all-sky, every level's up and down flux */
-    GRT_SOLVER_SPECTRAL,    /* fused clear-sky, six output rows, and the six rows at every point */
-    GRT_SOLVER_ALLSKY_SPECTRAL, /* fused all-sky, six output rows, and the six rows at every point */
-    GRT_SOLVER_AEROSOL,     /* fused clear sky with aerosols, six output rows */
-    GRT_SOLVER_AEROSOL_PROFILE  /* fused clear sky with aerosols, every level's up and down flux */
-} GrtSolverForm;
-/* what a form is: fused (the kernel integrates), profile (every level's fluxes), all-sky (clouds), spectral (a fused
-   six-row form that also stores its six rows at every point: up TOA, surface, user at flux_up + c flux_stride + k nw,
-   k = 0, 1, 2, down at flux_down + ...; grt_pipeline_run_spectral), aerosol (the aerosol object joins gas and Rayleigh:
-   GrtAerosolArgs) */
-typedef struct GrtFormKind { int fused, profile, allsky, spectral, aerosol; } GrtFormKind;
-static inline GrtFormKind grt_form_kind(GrtSolverForm form)
-{
-    GrtFormKind k;
-    k.profile = form == GRT_SOLVER_PROFILE || form == GRT_SOLVER_ALLSKY_PROFILE || form == GRT_SOLVER_AEROSOL_PROFILE;
-    k.spectral = form == GRT_SOLVER_SPECTRAL || form == GRT_SOLVER_ALLSKY_SPECTRAL;
-    k.allsky = form == GRT_SOLVER_ALLSKY || form == GRT_SOLVER_ALLSKY_PROFILE || form == GRT_SOLVER_ALLSKY_SPECTRAL;
-    k.aerosol = form == GRT_SOLVER_AEROSOL || form == GRT_SOLVER_AEROSOL_PROFILE;
-    k.fused = form == GRT_SOLVER_FUSED || k.profile || k.allsky || k.spectral || k.aerosol;
-    return k;
-}
-/* whether an all-sky form can read `c` */
-static inline int grt_cloud_args_ok(GrtCloudArgs const *c)
-{
-    return c != NULL && c->num_bands >= 1 && c->band_liquid != NULL && c->band_ice != NULL && c->thickness != NULL &&
-           c->liquid != NULL && c->ice != NULL;
-}
-int grt_launch_lw(void *stream, GrtSolverForm form, GrtLwArgs const *a, GrtCloudArgs const *clouds,
-                  GrtAerosolArgs const *aerosols);
-int grt_launch_sw(void *stream, GrtSolverForm form, GrtSwArgs const *a, GrtCloudArgs const *clouds,
-                  GrtAerosolArgs const *aerosols);
-
 /* Materialised form: the aerosol object of the same tables spread onto the grid, [ncol][L][nw] each (zero where a point
    has no interval). */
 int grt_launch_spread_aerosols(void *stream, int num_layers, int ncol, double w0, double dw, uint64_t nw,
                                GrtAerosolArgs const *c, double *tau, double *omega, double *g);
 
-/* Subcolumn form of the two all-sky forms (GRT_SOLVER_ALLSKY when profile == 0, GRT_SOLVER_ALLSKY_PROFILE when 1;
+/* Subcolumn form of the two all-sky forms (subcolumns joined in place of clouds, six rows or every level;
    grt_pipeline_run_subcolumns): one launch solves subcolumns first .. first + count - 1 of every column, a->ncol columns of
    gas state (tau_gas, n_layer, temperatures, sun, continua) and `subcolumns` cloud draws per column.  Row y of the grid
    is column c = y / count, subcolumn s = first + y % count, so that the draws of one column run next to each other and
@@ -430,17 +387,14 @@ typedef struct GrtSubcolumnArgs
     GrtCloudArgs clouds;
     int subcolumns, first, count;
 } GrtSubcolumnArgs;
-/* whether a subcolumn launch can run: the fused all-sky form's fields, and a grid of at most 65 535 rows */
-static inline int grt_subcolumn_args_ok(int ncol, int num_levels, uint64_t nw, double const *tau_gas,
-                                        double const *n_layer, double const *partials, GrtSubcolumnArgs const *sc)
+static inline int grt_subcolumn_args_ok(GrtSubcolumnArgs const *sc)
 {
-    return sc != NULL && ncol >= 1 && nw >= 2 && num_levels >= 2 && tau_gas != NULL && n_layer != NULL &&
-           partials != NULL && grt_cloud_args_ok(&sc->clouds) && sc->subcolumns >= 1 && sc->count >= 1 &&
-           sc->first >= 0 && sc->first + sc->count <= sc->subcolumns && (uint64_t)ncol*(uint64_t)sc->count <= 65535u;
+    return sc != NULL && grt_cloud_args_ok(&sc->clouds) && sc->subcolumns >= 1 && sc->count >= 1 && sc->first >= 0 &&
+           sc->first + sc->count <= sc->subcolumns;
 }
 
-/* Banded profile form of the two profile forms (GRT_SOLVER_PROFILE when clouds is NULL, GRT_SOLVER_ALLSKY_PROFILE
-   otherwise; grt_pipeline_run_band_profiles): the profile form's arguments, sweeps and park block, but every level's
+/* Banded profile form of the two profile forms (GRT_OUT_LEVEL_BINS, clear sky or clouds joined;
+   grt_pipeline_run_band_profiles): the profile form's arguments, sweeps and park block, but every level's
    flux leaves once per wavenumber bin that has a point in the workgroup's 128 grid points.  A point weights a level's
    value with the trapezoid weight of the bin (grt_launch_bin_rows' rule: dw inside, dw/2 at the bin's two edges, 0
    elsewhere and for idle lanes); a workgroup inside one bin -- all but the few that hold an edge -- does exactly the
@@ -456,18 +410,80 @@ typedef struct GrtBandArgs
     int const *table;               /* DEVICE: grt_bin_table's ints */
     uint64_t per_row;               /* partial sums per row (grt_bin_table's return value) */
 } GrtBandArgs;
-static inline size_t grt_band_profile_lds(GrtBandArgs const *bn, int num_levels, int block_threads)
-{
-    return sizeof(double)*2*(size_t)num_levels*(size_t)(block_threads/64)*(size_t)bn->block_bins;
-}
 static inline int grt_band_args_ok(GrtBandArgs const *bn)
 {
     return bn != NULL && bn->num_bins >= 1 && bn->block_bins >= 1 && bn->table != NULL && bn->per_row >= 1;
 }
-int grt_launch_lw_bands(void *stream, GrtLwArgs const *a, GrtCloudArgs const *clouds, GrtBandArgs const *bins);
-int grt_launch_sw_bands(void *stream, GrtSwArgs const *a, GrtCloudArgs const *clouds, GrtBandArgs const *bins);
-int grt_launch_lw_subcolumns(void *stream, int profile, GrtLwArgs const *a, GrtSubcolumnArgs const *sc);
-int grt_launch_sw_subcolumns(void *stream, int profile, GrtSwArgs const *a, GrtSubcolumnArgs const *sc);
+
+/* One instance of lw_kernel / sw_kernel (k_longwave.hip, k_shortwave.hip), described once for the launchers, the kernels
+   and the pipeline: what leaves the kernel ... */
+typedef enum GrtSolverOutput
+{
+    GRT_OUT_CHAINS,         /* spectral fluxes [V][nw]: one thread per wavenumber and column through all the layers */
+    GRT_OUT_LAYERS,         /* the same fluxes, the layers' terms first (layer_terms / layer_props), then the sweeps */
+    /* fused (the kernel forms the layer optics from tau_gas and integrates over the band): partial sums of ... */
+    GRT_OUT_ROWS,           /* the six output rows */
+    GRT_OUT_ROWS_POINTS,    /* the six rows, and the six rows at every point: up TOA, surface, user at flux_up + c
+                               flux_stride + k nw, k = 0, 1, 2, down at flux_down + ... (grt_pipeline_run_spectral) */
+    GRT_OUT_LEVELS,         /* every level's up and down flux */
+    GRT_OUT_LEVEL_BINS      /* every level's up and down flux per wavenumber bin of `bins` */
+} GrtSolverOutput;
+/* ... and what joins gas and Rayleigh in a fused instance: nothing (clear sky: every pointer NULL), the cloud objects,
+   the aerosol object, or the cloud objects of several subcolumns per column; `bins` goes with GRT_OUT_LEVEL_BINS and
+   with nothing else.  The kind of instance follows from which pointers are set, and a kernel takes the structs that are
+   set as arguments after its band's own.  The next joined object is a pointer here, a line in grt_solver_instance_ok
+   and a case in each band's list of instances. */
+typedef struct GrtSolverInstance
+{
+    GrtSolverOutput out;
+    GrtCloudArgs const *clouds;
+    GrtAerosolArgs const *aerosols;
+    GrtSubcolumnArgs const *subcolumns;
+    GrtBandArgs const *bins;
+} GrtSolverInstance;
+typedef enum GrtSolverJoin
+{
+    GRT_JOIN_NONE, GRT_JOIN_CLOUDS, GRT_JOIN_AEROSOLS, GRT_JOIN_SUBCOLUMNS, GRT_JOIN_COUNT
+} GrtSolverJoin;
+/* an instance as one integer: the case labels of a band's list of instances (the launchers' switches) */
+#define GRT_INSTANCE(out, join) ((int)(out)*(int)GRT_JOIN_COUNT + (int)(join))
+#ifdef __cplusplus
+#define GRT_FN constexpr
+#else
+#define GRT_FN static inline
+#endif
+GRT_FN int grt_out_fused(GrtSolverOutput out) { return out >= GRT_OUT_ROWS; }
+GRT_FN int grt_out_levels(GrtSolverOutput out) { return out >= GRT_OUT_LEVELS; }
+#undef GRT_FN
+/* which pointer is set -- of an instance grt_solver_instance_ok has passed: it refuses more than one join, and any join
+   of an output that is not fused, so the order of the tests here decides nothing and a band's switch sees no such case */
+static inline GrtSolverJoin grt_solver_join(GrtSolverInstance const *in)
+{
+    return in->clouds != NULL ? GRT_JOIN_CLOUDS : (in->aerosols != NULL ? GRT_JOIN_AEROSOLS :
+           (in->subcolumns != NULL ? GRT_JOIN_SUBCOLUMNS : GRT_JOIN_NONE));
+}
+/* the rows of its grid: a column each, or (subcolumns) `count` subcolumns of every column */
+static inline uint64_t grt_solver_grid_rows(GrtSolverInstance const *in, int ncol)
+{
+    return (uint64_t)ncol*(uint64_t)(in->subcolumns != NULL ? in->subcolumns->count : 1);
+}
+/* its dynamic LDS: 2 V doubles per wave of its workgroup where every level leaves, that per bin of a block with bins */
+#define GRT_SOLVER_BLOCK 128
+static inline size_t grt_solver_lds(GrtSolverInstance const *in, int num_levels)
+{
+    size_t const levels = sizeof(double)*2*(size_t)num_levels*(GRT_SOLVER_BLOCK/64);
+    return !grt_out_levels(in->out) ? 0 : (in->bins != NULL ? levels*(size_t)in->bins->block_bins : levels);
+}
+/* whether the shortwave instance takes the two sweeps and needs `park` */
+static inline int grt_sw_parks(GrtSolverInstance const *in, GrtSwArgs const *a)
+{
+    return grt_out_fused(in->out) && (grt_out_levels(in->out) || !grt_sw_one_sweep(a));
+}
+/* The one launcher of each band: checks the instance (grt_solver_instance_ok below and the fields only its own arguments
+   carry: the layers' scratch, the shortwave's park block) and launches it; hipErrorInvalidValue for an instance that
+   cannot run or has no kernel behind it. */
+int grt_launch_lw(void *stream, GrtSolverInstance const *in, GrtLwArgs const *a);
+int grt_launch_sw(void *stream, GrtSolverInstance const *in, GrtSwArgs const *a);
 /* The subcolumn mean of the partial sums above, in a fixed order: for column c and row r (of `rows` per slot) each
    subcolumn's blocks are added as grt_launch_reduce_partials adds them, then the subcolumns s = 0 .. S - 1 in order, then
    the sum is divided by S; out[c out_stride + out_offset + r].  S = 1 gives grt_launch_reduce_partials' bits. */
@@ -535,6 +551,25 @@ int grt_launch_copy_rows(void *stream, double const *const *rows_dev, int nrows,
                          uint64_t out_stride);
 
 #ifdef __cplusplus
+}
+
+/* Whether the instance `in` can run on `a` (GrtLwArgs or GrtSwArgs: the fields both carry), for both launchers: the
+   combinations that exist, each set pointer's own fields, what the output reads and writes, a grid of at most 65 535
+   rows and the 64 KiB of LDS. */
+template <typename Args>
+inline bool grt_solver_instance_ok(GrtSolverInstance const &in, Args const &a)
+{
+    bool const fused = grt_out_fused(in.out), flux_rows = a.flux_up != nullptr && a.flux_down != nullptr;
+    int const joined = (in.clouds != nullptr) + (in.aerosols != nullptr) + (in.subcolumns != nullptr);
+    return a.ncol >= 1 && a.nw >= 2 && a.num_levels >= 2 &&
+           joined <= (fused ? 1 : 0) && (in.bins != nullptr) == (in.out == GRT_OUT_LEVEL_BINS) &&
+           (in.clouds == nullptr || grt_cloud_args_ok(in.clouds)) &&
+           (in.aerosols == nullptr || grt_aerosol_args_ok(in.aerosols)) &&
+           (in.subcolumns == nullptr || grt_subcolumn_args_ok(in.subcolumns)) &&
+           (in.bins == nullptr || grt_band_args_ok(in.bins)) &&
+           (fused ? a.tau_gas != nullptr && a.n_layer != nullptr && a.partials != nullptr : flux_rows) &&
+           (in.out != GRT_OUT_ROWS_POINTS || flux_rows) &&
+           grt_solver_grid_rows(&in, a.ncol) <= 65535u && grt_solver_lds(&in, a.num_levels) <= 65536;
 }
 #endif
 #endif

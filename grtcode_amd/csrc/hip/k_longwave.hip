@@ -13,12 +13,11 @@
 //
 // SURVEY.md §8a19 prices it at 1 944 B per wavenumber at 60 layers; measured it is a latency
 // chain -- 120 dependent layer steps with six fp64 exp each on 26 000 threads at 1 cm-1 -- which is why column
-// batches share a launch.  lw_kernel<true, false> is the fused form of the production pipeline, lw_kernel<true, false, true>
-// its all-sky form, lw_kernel<true, true> and lw_kernel<true, true, true> the profile forms of the two
-// (with a GrtBandArgs last: their banded forms, a level's flux per wavenumber bin),
-// lw_kernel<true, false, false, true> and lw_kernel<true, false, true, true> the spectral six-row forms of the two, and
-// lw_kernel<true, *, true, false, GrtSubcolumnArgs> the all-sky forms over several subcolumns per column, and lw_kernel<true, *, false, false,
-// GrtAerosolArgs> the clear-sky forms with the aerosol object (the argument's type selects them: LayerOptics).
+// batches share a launch.  lw_kernel has one instance per GrtSolverInstance that exists (grt_kernels.h; the list is in
+// grt_launch_lw): what leaves it is its OUT -- spectral fluxes (GRT_OUT_CHAINS), or, fused, the partial sums of the six
+// rows, of the six rows that are also stored at every point, of every level, or of every level per wavenumber bin -- and
+// what joins gas and Rayleigh is the types of its pack: nothing, GrtCloudArgs, GrtAerosolArgs or GrtSubcolumnArgs, and a
+// GrtBandArgs last where OUT is per bin.  The fused six-row clear-sky instance is the production pipeline's.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -97,18 +96,21 @@ __device__ __forceinline__ double surface_step(double (&I)[4], double emis, doub
     return f;
 }
 
-// FUSED: the clear-sky tail of the pipeline in one kernel -- Rayleigh and the two-object optics combination are formed
-// per layer in registers from tau_gas (LayerOptics: identical values), nothing spectral is written, and the six
-// integrated output rows leave as per-block trapezoid partial sums (LevelSink).
-// PROFILE (fused form only): every level's upward and downward flux leaves instead, 2 V rows per column (LevelSink).
-// ALLSKY (fused forms, six-row or profile): the liquid and ice cloud objects join per layer (LayerOptics).  Only
-// layer_tau changes: what leaves the kernel is the six-row or the profile form's.
-// SPECTRAL (fused six-row form): the six rows also leave at every point, unweighted (LevelSink).
-template <bool FUSED, bool PROFILE, bool ALLSKY = false, bool SPECTRAL = false, typename... Clouds>
-__global__ __launch_bounds__(kSolverBlock) void lw_kernel(GrtLwArgs a, Clouds... clouds)
+// OUT fused (GRT_OUT_ROWS and after): the clear-sky tail of the pipeline in one kernel -- Rayleigh and the two-object
+// optics combination are formed per layer in registers from tau_gas (LayerOptics: identical values), nothing spectral is
+// written, and the six integrated output rows leave as per-block trapezoid partial sums (LevelSink).
+// GRT_OUT_LEVELS: every level's upward and downward flux leaves instead, 2 V rows per column; GRT_OUT_LEVEL_BINS: once per
+// wavenumber bin (the pack's GrtBandArgs); GRT_OUT_ROWS_POINTS: the six rows also leave at every point, unweighted
+// (LevelSink).
+// Joins (fused forms): clouds (a GrtCloudArgs, or the draws of a GrtSubcolumnArgs) or the aerosol object join per layer
+// (LayerOptics).  Only layer_tau changes: what leaves the kernel is OUT's.
+template <GrtSolverOutput OUT, typename... Joins>
+__global__ __launch_bounds__(kSolverBlock) void lw_kernel(GrtLwArgs a, Joins... joins)
 {
     uint64_t const i = (uint64_t)blockIdx.x*kSolverBlock + threadIdx.x;
-    SolverRow const row = solver_row(a.ncol, clouds...);
+    constexpr bool FUSED = grt_out_fused(OUT), PROFILE = grt_out_levels(OUT), SPECTRAL = OUT == GRT_OUT_ROWS_POINTS;
+    static_assert(has<GrtBandArgs, Joins...> == (OUT == GRT_OUT_LEVEL_BINS), "bins go with GRT_OUT_LEVEL_BINS alone");
+    SolverRow const row = solver_row(a.ncol, joins...);
     int const col = row.col;
     bool const live = i < a.nw;
     if (!FUSED && !live)
@@ -124,9 +126,9 @@ __global__ __launch_bounds__(kSolverBlock) void lw_kernel(GrtLwArgs a, Clouds...
     double const *tl = a.t_layers + (uint64_t)col*L;
     double const *tv = a.t_levels + (uint64_t)col*V;
     double const emis = a.emis[(uint64_t)col*a.emis_stride + ii];
-    LevelSink<FUSED, PROFILE, SPECTRAL, IsBandPack<Clouds...>::value> sink(a, row.slot, i, live, band_args(clouds...));
-    LayerOptics<FUSED, ALLSKY, IsAerosolPack<Clouds...>::value> const optics(a, cloud_args(clouds...), col, row.tab, ii,
-                                                                             aerosol_args(clouds...));   // (fused forms)
+    LevelSink<FUSED, PROFILE, SPECTRAL, has<GrtBandArgs, Joins...>> sink(a, row.slot, i, live, pick<GrtBandArgs>(joins...));
+    LayerOptics<FUSED, has_clouds<Joins...>, has<GrtAerosolArgs, Joins...>> const optics(
+        a, pick_clouds(joins...), col, row.tab, ii, pick<GrtAerosolArgs>(joins...));                    // (fused forms)
 
     // absorption optical depth of layer j: tau (1 - omega)  (longwave.c:252)
     auto layer_tau = [&](int j) -> double
@@ -160,11 +162,11 @@ __global__ __launch_bounds__(kSolverBlock) void lw_kernel(GrtLwArgs a, Clouds...
 }
 
 // ---- spectral form of few columns: the layers' terms first, by one thread per (layer, wavenumber) ----
-// One column of the longwave band is 3 250 threads for lw_kernel<false, false> -- fifty waves on a thousand SIMDs, each with 120
+// One column of the longwave band is 3 250 threads for lw_kernel<GRT_OUT_CHAINS> -- fifty waves on a thousand SIMDs, each with 120
 // dependent layer steps of six exp.  What costs in a step does not depend on the step before: lw_terms_kernel fills
 // terms[col][6 j + k][nw] with the four streams' extinctions exp(c1[s] t) and the effective Planck terms of the
 // downward and of the upward sweep; lw_sweeps_kernel carries the four intensities through them, six layers' terms read
-// ahead of the chain at a time.  Same expressions, same order, same doubles as lw_kernel<false, false>: identical fluxes.
+// ahead of the chain at a time.  Same expressions, same order, same doubles as lw_kernel<GRT_OUT_CHAINS>: identical fluxes.
 constexpr int kTermsBlock = 256;
 constexpr int kSweepBlock = 64;
 constexpr int kSweepChunk = 6;
@@ -266,6 +268,16 @@ __global__ __launch_bounds__(kSweepBlock) void lw_sweeps_kernel(GrtLwArgs a)
     }
 }
 
+// the one launch site of lw_kernel: the instance of OUT and of the joined arguments' types, on the instance's grid and LDS
+template <GrtSolverOutput OUT, typename... Joins>
+int launch(hipStream_t s, GrtSolverInstance const &in, GrtLwArgs const &a, Joins const &...joins)
+{
+    dim3 const grid(grt_solver_blocks(a.nw), (unsigned)grt_solver_grid_rows(&in, a.ncol), 1);
+    hipLaunchKernelGGL((lw_kernel<OUT, Joins...>), grid, dim3(kSolverBlock), grt_solver_lds(&in, a.num_levels), s, a,
+                       joins...);
+    return (int)hipGetLastError();
+}
+
 } // namespace
 
 extern "C" unsigned grt_solver_blocks(uint64_t nw)
@@ -273,106 +285,39 @@ extern "C" unsigned grt_solver_blocks(uint64_t nw)
     return (unsigned)((nw + kSolverBlock - 1)/kSolverBlock);
 }
 
-extern "C" int grt_launch_lw(void *stream, GrtSolverForm form, GrtLwArgs const *a, GrtCloudArgs const *c,
-                             GrtAerosolArgs const *ae)
+extern "C" int grt_launch_lw(void *stream, GrtSolverInstance const *in, GrtLwArgs const *a)
 {
-    GrtFormKind const k = grt_form_kind(form);
-    size_t const lds = grt_profile_lds(k.profile, a->num_levels, kSolverBlock);
     uint64_t const cells = (uint64_t)(a->num_levels - 1)*a->nw;
-    if (a->ncol < 1 || a->nw < 2 ||
-        (k.fused ? (a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr)
-                 : (a->flux_up == nullptr || a->flux_down == nullptr)) ||
-        (k.spectral && (a->flux_up == nullptr || a->flux_down == nullptr)) ||
-        (form == GRT_SOLVER_LAYERS && (a->layer_terms == nullptr || cells > 0xffffffffull*kTermsBlock)) ||
-        ((k.profile || k.aerosol) && (a->num_levels < 2 || lds > 65536)) || (k.allsky && !grt_cloud_args_ok(c)) ||
-        (k.aerosol && !grt_aerosol_args_ok(ae)))
+    if (!grt_solver_instance_ok(*in, *a) ||
+        (in->out == GRT_OUT_LAYERS && (a->layer_terms == nullptr || cells > 0xffffffffull*kTermsBlock)))
     {
         return (int)hipErrorInvalidValue;
     }
     hipStream_t const s = (hipStream_t)stream;
-    dim3 const grid(grt_solver_blocks(a->nw), a->ncol, 1);
-    switch (form)
+    // every instance of lw_kernel there is
+    switch (GRT_INSTANCE(in->out, grt_solver_join(in)))
     {
-    case GRT_SOLVER_LAYERS:
+    case GRT_INSTANCE(GRT_OUT_LAYERS, GRT_JOIN_NONE):
         hipLaunchKernelGGL(lw_terms_kernel, dim3((unsigned)((cells + kTermsBlock - 1)/kTermsBlock), a->ncol, 1),
                            dim3(kTermsBlock), 0, s, *a);
         hipLaunchKernelGGL(lw_sweeps_kernel, dim3((unsigned)((a->nw + kSweepBlock - 1)/kSweepBlock), a->ncol, 1),
                            dim3(kSweepBlock), 0, s, *a);
-        break;
-    case GRT_SOLVER_FUSED:
-        hipLaunchKernelGGL((lw_kernel<true, false>), grid, dim3(kSolverBlock), 0, s, *a);
-        break;
-    case GRT_SOLVER_CHAINS:
-        hipLaunchKernelGGL((lw_kernel<false, false>), grid, dim3(kSolverBlock), 0, s, *a);
-        break;
-    case GRT_SOLVER_PROFILE:
-        hipLaunchKernelGGL((lw_kernel<true, true>), grid, dim3(kSolverBlock), lds, s, *a);
-        break;
-    case GRT_SOLVER_ALLSKY:
-        hipLaunchKernelGGL((lw_kernel<true, false, true, false, GrtCloudArgs>), grid, dim3(kSolverBlock), 0, s, *a, *c);
-        break;
-    case GRT_SOLVER_ALLSKY_PROFILE:
-        hipLaunchKernelGGL((lw_kernel<true, true, true, false, GrtCloudArgs>), grid, dim3(kSolverBlock), lds, s, *a, *c);
-        break;
-    case GRT_SOLVER_SPECTRAL:
-        hipLaunchKernelGGL((lw_kernel<true, false, false, true>), grid, dim3(kSolverBlock), 0, s, *a);
-        break;
-    case GRT_SOLVER_ALLSKY_SPECTRAL:
-        hipLaunchKernelGGL((lw_kernel<true, false, true, true, GrtCloudArgs>), grid, dim3(kSolverBlock), 0, s, *a, *c);
-        break;
-    case GRT_SOLVER_AEROSOL:
-        hipLaunchKernelGGL((lw_kernel<true, false, false, false, GrtAerosolArgs>), grid, dim3(kSolverBlock), 0, s, *a, *ae);
-        break;
-    case GRT_SOLVER_AEROSOL_PROFILE:
-        hipLaunchKernelGGL((lw_kernel<true, true, false, false, GrtAerosolArgs>), grid, dim3(kSolverBlock), lds, s, *a, *ae);
-        break;
+        return (int)hipGetLastError();
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_NONE): return launch<GRT_OUT_ROWS>(s, *in, *a);
+    case GRT_INSTANCE(GRT_OUT_CHAINS, GRT_JOIN_NONE): return launch<GRT_OUT_CHAINS>(s, *in, *a);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_NONE): return launch<GRT_OUT_LEVELS>(s, *in, *a);
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->clouds);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds);
+    case GRT_INSTANCE(GRT_OUT_ROWS_POINTS, GRT_JOIN_NONE): return launch<GRT_OUT_ROWS_POINTS>(s, *in, *a);
+    case GRT_INSTANCE(GRT_OUT_ROWS_POINTS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_ROWS_POINTS>(s, *in, *a, *in->clouds);
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->aerosols);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->aerosols);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns);
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns);
+    case GRT_INSTANCE(GRT_OUT_LEVEL_BINS, GRT_JOIN_CLOUDS):
+        return launch<GRT_OUT_LEVEL_BINS>(s, *in, *a, *in->clouds, *in->bins);
+    case GRT_INSTANCE(GRT_OUT_LEVEL_BINS, GRT_JOIN_NONE): return launch<GRT_OUT_LEVEL_BINS>(s, *in, *a, *in->bins);
     default:
         return (int)hipErrorInvalidValue;
     }
-    return (int)hipGetLastError();
-}
-
-extern "C" int grt_launch_lw_subcolumns(void *stream, int profile, GrtLwArgs const *a, GrtSubcolumnArgs const *sc)
-{
-    size_t const lds = grt_profile_lds(profile, a->num_levels, kSolverBlock);
-    if (!grt_subcolumn_args_ok(a->ncol, a->num_levels, a->nw, a->tau_gas, a->n_layer, a->partials, sc) || lds > 65536)
-    {
-        return (int)hipErrorInvalidValue;
-    }
-    hipStream_t const s = (hipStream_t)stream;
-    dim3 const grid(grt_solver_blocks(a->nw), (unsigned)(a->ncol*sc->count), 1);
-    if (profile)
-    {
-        hipLaunchKernelGGL((lw_kernel<true, true, true, false, GrtSubcolumnArgs>), grid, dim3(kSolverBlock), lds, s, *a,
-                           *sc);
-    }
-    else
-    {
-        hipLaunchKernelGGL((lw_kernel<true, false, true, false, GrtSubcolumnArgs>), grid, dim3(kSolverBlock), 0, s, *a,
-                           *sc);
-    }
-    return (int)hipGetLastError();
-}
-
-extern "C" int grt_launch_lw_bands(void *stream, GrtLwArgs const *a, GrtCloudArgs const *c, GrtBandArgs const *bn)
-{
-    if (!grt_band_args_ok(bn) || a->ncol < 1 || a->ncol > 65535 || a->nw < 2 || a->num_levels < 2 ||
-        a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr || (c != nullptr && !grt_cloud_args_ok(c)) ||
-        grt_band_profile_lds(bn, a->num_levels, kSolverBlock) > 65536)
-    {
-        return (int)hipErrorInvalidValue;
-    }
-    size_t const lds = grt_band_profile_lds(bn, a->num_levels, kSolverBlock);
-    hipStream_t const s = (hipStream_t)stream;
-    dim3 const grid(grt_solver_blocks(a->nw), a->ncol, 1);
-    if (c != nullptr)
-    {
-        hipLaunchKernelGGL((lw_kernel<true, true, true, false, GrtCloudArgs, GrtBandArgs>), grid, dim3(kSolverBlock), lds, s,
-                           *a, *c, *bn);
-    }
-    else
-    {
-        hipLaunchKernelGGL((lw_kernel<true, true, false, false, GrtBandArgs>), grid, dim3(kSolverBlock), lds, s, *a, *bn);
-    }
-    return (int)hipGetLastError();
 }

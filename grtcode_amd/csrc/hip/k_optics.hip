@@ -201,10 +201,7 @@ __global__ __launch_bounds__(kBlock) void integrate_rows_kernel(double const *co
     {
         s += 0.5*(row[i] + row[i + 1])*dw;
     }
-    for (int off = 32; off > 0; off >>= 1)
-    {
-        s += __shfl_down(s, off, 64);
-    }
+    WAVE_SUM(s);
     if ((threadIdx.x & 63) == 0)
     {
         part[threadIdx.x >> 6] = s;
@@ -218,21 +215,12 @@ __global__ __launch_bounds__(kBlock) void integrate_rows_kernel(double const *co
 }
 
 // Second stage of the fused solvers' trapezoid: one wavefront per output row adds the blocks' partial sums in a
-// fixed order (lane-strided, then a shuffle tree): same bits every run.
+// fixed order (wave_strided_sum): same bits every run.
 __global__ __launch_bounds__(64) void reduce_partials_kernel(double const *partials, unsigned nblocks, double *out,
                                                              int group, int out_stride, int out_offset)
 {
     int const r = blockIdx.x;
-    double const *p = partials + (uint64_t)r*nblocks;
-    double s = 0.;
-    for (unsigned b = threadIdx.x; b < nblocks; b += 64)
-    {
-        s += p[b];
-    }
-    for (int off = 32; off > 0; off >>= 1)
-    {
-        s += __shfl_down(s, off, 64);
-    }
+    double const s = wave_strided_sum(partials + (uint64_t)r*nblocks, nblocks);
     if (threadIdx.x == 0)
     {
         out[(r/group)*out_stride + out_offset + (r % group)] = s;
@@ -240,7 +228,7 @@ __global__ __launch_bounds__(64) void reduce_partials_kernel(double const *parti
 }
 
 // grt_pipeline_run_subcolumns: the mean over a column's S subcolumns of one output row.  One wavefront per (column, row):
-// each subcolumn's block sums in reduce_partials_kernel's association (same lanes, same shuffle tree), then the
+// each subcolumn's block sums by wave_strided_sum as reduce_partials_kernel adds them, then the
 // subcolumns in order, then one division by S (driver.c:585-589).  S = 1: reduce_partials_kernel's bits.
 __global__ __launch_bounds__(64) void subcolumn_mean_kernel(double const *partials, int S, int rows, unsigned nblocks,
                                                             double *out, int out_stride, int out_offset)
@@ -250,16 +238,7 @@ __global__ __launch_bounds__(64) void subcolumn_mean_kernel(double const *partia
     double m = 0.;
     for (int s = 0; s < S; ++s)
     {
-        double const *p = partials + ((uint64_t)(c*S + s)*rows + r)*nblocks;
-        double x = 0.;
-        for (unsigned b = threadIdx.x; b < nblocks; b += 64)
-        {
-            x += p[b];
-        }
-        for (int off = 32; off > 0; off >>= 1)
-        {
-            x += __shfl_down(x, off, 64);
-        }
+        double const x = wave_strided_sum(partials + ((uint64_t)(c*S + s)*rows + r)*nblocks, nblocks);
         m = s == 0 ? x : m + x;
     }
     if (threadIdx.x == 0)
@@ -298,8 +277,8 @@ inline unsigned bin_blocks(uint64_t nw)
     return (unsigned)((nw + kSolverBlock - 1)/kSolverBlock);
 }
 
-// one workgroup per (128-point block, row): per bin that has a point in the block, sum_i x_i w_i by block_partials'
-// tree, stored at partials[row P + offset(bin) + block - first_block(bin)].  Row r: in + (r/6) in_stride + (r%6) nw, or
+// one workgroup per (128-point block, row): per bin that has a point in the block, sum_i x_i w_i as block_partials
+// sums a row (WAVE_SUM, then waves_sum), stored at partials[row P + offset(bin) + block - first_block(bin)].  Row r: in + (r/6) in_stride + (r%6) nw, or
 // -- rows given (the level fluxes of grt_pipeline_run_band_profiles' materialised form) -- rows[r].
 __global__ __launch_bounds__(kSolverBlock) void bin_partials_kernel(double const *in, uint64_t in_stride,
                                                                     double const *const *rows, int nrows, uint64_t nw,
@@ -324,10 +303,7 @@ __global__ __launch_bounds__(kSolverBlock) void bin_partials_kernel(double const
                 // (trapezoid_weight's doubles: dw/2 at the bin's two edges, dw between them)
                 double const w = (i == e[0] || i == e[1]) ? 0.5*dw : ((i > e[0] && i < e[1]) ? dw : 0.);
                 double s = x*w;
-                for (int off = 32; off > 0; off >>= 1)
-                {
-                    s += __shfl_down(s, off, 64);
-                }
+                WAVE_SUM(s);
                 if ((threadIdx.x & 63) == 0)
                 {
                     part[q][threadIdx.x >> 6] = s;
@@ -337,19 +313,14 @@ __global__ __launch_bounds__(kSolverBlock) void bin_partials_kernel(double const
             if ((int)threadIdx.x < nb)
             {
                 int const *e = tab + 4*(b0 + threadIdx.x);
-                double s = part[threadIdx.x][0];
-                for (int k = 1; k < kSolverBlock/64; ++k)
-                {
-                    s += part[threadIdx.x][k];
-                }
-                prow[e[2] + block - e[3]] = s;
+                prow[e[2] + block - e[3]] = waves_sum<kSolverBlock/64>(part[threadIdx.x]);
             }
             __syncthreads();
         }
     }
 }
 
-// one wavefront per (bin, row): the bin's block sums in block order, reduce_partials_kernel's association.  `group` rows
+// one wavefront per (bin, row): the bin's block sums in block order by wave_strided_sum, as reduce_partials_kernel's.  `group` rows
 // per column; bin b of row r goes to out + (r/group) out_stride + (r%group) nbins + b, or -- levels > 0: the rows are a
 // column's levels, up then down (group = 2 levels) -- + ((r%group/levels) nbins + b) levels + r%levels.
 __global__ __launch_bounds__(64) void bin_reduce_kernel(int nrows, int group, int levels, int nbins, int const *tab,
@@ -361,16 +332,14 @@ __global__ __launch_bounds__(64) void bin_reduce_kernel(int nrows, int group, in
     unsigned const nblk = (unsigned)(e[1]/kSolverBlock - e[3]) + 1;
     for (int r = blockIdx.y; r < nrows; r += gridDim.y)
     {
+        // (wave_strided_sum, written out: as a call the loop over the rows is scheduled differently)
         double const *p = partials + (uint64_t)r*P + e[2];
         double s = 0.;
         for (unsigned k = threadIdx.x; k < nblk; k += 64)
         {
             s += p[k];
         }
-        for (int off = 32; off > 0; off >>= 1)
-        {
-            s += __shfl_down(s, off, 64);
-        }
+        WAVE_SUM(s);
         if (threadIdx.x == 0)
         {
             int const k = r % group;
@@ -395,10 +364,18 @@ __global__ __launch_bounds__(kBlock) void copy_rows_kernel(double const *const *
     }
 }
 
+// The heating rate of layer j, between levels j (upper) and j + 1, from a column's level pressures p [V] mb and level
+// fluxes up, dn [V]:  H_j = (g/c_p) ((dn_j - up_j) - (dn_{j+1} - up_{j+1}))/(100 (p_{j+1} - p_j)) 86 400   [K day-1]
+__device__ __forceinline__ double heating_rate(double gravity, double cp, double const *p, double const *up,
+                                               double const *dn, int j)
+{
+    double const net_top = dn[j] - up[j], net_bottom = dn[j + 1] - up[j + 1];
+    return (gravity/cp)*((net_top - net_bottom)/(100.*(p[j + 1] - p[j])))*86400.;
+}
+
 // Last step of grt_pipeline_run_profiles (sets = 1) and grt_pipeline_run_allsky_profiles (sets = 2: clear sky, then
 // all-sky): one thread per (column, set, band, layer j) reads the band's level fluxes
-// levels[c][set][2 band + {0: up, 1: down}][V] and forms the heating rate of layer j, between levels j (upper) and j + 1,
-//     H_j = (g/c_p) ((dn_j - up_j) - (dn_{j+1} - up_{j+1}))/(100 (p_{j+1} - p_j)) 86 400   [K day-1, p in mb],
+// levels[c][set][2 band + {0: up, 1: down}][V] and forms the heating rate of layer j (heating_rate),
 // and -- thread j = 0 -- the band's six rows of the six-row form (up top, up surface, up user, down top, down surface, down
 // user: grt_pipeline_run's layout).  A band that is not computed (bit clear in `bands`) gets zeros everywhere.
 __global__ __launch_bounds__(kBlock) void profile_finish_kernel(int ncol, int sets, int V, int bands, int user,
@@ -443,9 +420,7 @@ __global__ __launch_bounds__(kBlock) void profile_finish_kernel(int ncol, int se
     }
     if (h)
     {
-        double const *p = pressure + (uint64_t)c*V;
-        double const net_top = dn[j] - up[j], net_bottom = dn[j + 1] - up[j + 1];
-        *h = (gravity/cp)*((net_top - net_bottom)/(100.*(p[j + 1] - p[j])))*86400.;
+        *h = heating_rate(gravity, cp, pressure + (uint64_t)c*V, up, dn, j);
     }
     if (six && j == 0)
     {
@@ -460,8 +435,7 @@ __global__ __launch_bounds__(kBlock) void profile_finish_kernel(int ncol, int se
 
 // Last step of grt_pipeline_run_band_profiles: one thread per (column, set, bin q of the lw_bins + sw_bins, layer j) reads
 // the bin's level fluxes in levels[c][set][2 lw_bins + 2 sw_bins][V] (per set the longwave's [2][lw_bins][V], up then
-// down, then the shortwave's) and forms profile_finish_kernel's heating rate of layer j from them: the same expression
-// on the same constants.
+// down, then the shortwave's) and forms heating_rate of layer j from them, as profile_finish_kernel does.
 __global__ __launch_bounds__(kBlock) void band_profile_finish_kernel(int ncol, int sets, int V, int lw_bins, int sw_bins,
                                                                      double gravity, double cp, double const *pressure,
                                                                      double const *levels, double *heating)
@@ -479,9 +453,7 @@ __global__ __launch_bounds__(kBlock) void band_profile_finish_kernel(int ncol, i
     double const *set = levels + cs*2*(uint64_t)nb*V;
     double const *up = q < lw_bins ? set + (uint64_t)q*V : set + (2*(uint64_t)lw_bins + (q - lw_bins))*V;
     double const *dn = up + (uint64_t)(q < lw_bins ? lw_bins : sw_bins)*V;
-    double const *p = pressure + (uint64_t)c*V;
-    double const net_top = dn[j] - up[j], net_bottom = dn[j + 1] - up[j + 1];
-    heating[(cs*nb + q)*L + j] = (gravity/cp)*((net_top - net_bottom)/(100.*(p[j + 1] - p[j])))*86400.;
+    heating[(cs*nb + q)*L + j] = heating_rate(gravity, cp, pressure + (uint64_t)c*V, up, dn, j);
 }
 
 } // namespace

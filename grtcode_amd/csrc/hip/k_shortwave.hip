@@ -14,14 +14,13 @@
 //     pair is consumed and overwritten by the final fluxes of :308-329,401-405,447-451.
 // Every expression keeps the reference's evaluation order, so results are identical.  Measured: in that
 // form the kernel is fp64-VALU-bound (two delta-Eddington solutions per layer and sweep: 70 000 instructions per wave),
-// not HBM-bound.  sw_kernel<true, false>, the fused form of the production pipeline, therefore trades bytes for flops: its first
-// sweep parks the five properties of every layer with the reflectances and its second sweep reads them back (the same
-// doubles: identical fluxes) -- 0.69 instead of 1.04 ms for 8 columns, at 4.2 TB/s.  sw_kernel<true, false, true> is its
-// all-sky form, sw_kernel<true, true> and sw_kernel<true, true, true> the profile forms of the two (with a GrtBandArgs
-// last: their banded forms, a level's flux per wavenumber bin), sw_kernel<true, false, false,
-// true> and sw_kernel<true, false, true, true> the spectral six-row forms of the two, and sw_kernel<true, *, true, false,
-// GrtSubcolumnArgs> the all-sky forms over several subcolumns per column, and sw_kernel<true, *, false, false,
-// GrtAerosolArgs> the clear-sky forms with the aerosol object (the argument's type selects them: LayerOptics).
+// not HBM-bound.  The fused six-row clear-sky instance, the production pipeline's, therefore trades bytes for flops: its
+// first sweep parks the five properties of every layer with the reflectances and its second sweep reads them back (the
+// same doubles: identical fluxes) -- 0.69 instead of 1.04 ms for 8 columns, at 4.2 TB/s.  sw_kernel has one instance per
+// GrtSolverInstance that exists (grt_kernels.h; the list is in grt_launch_sw): what leaves it is its OUT -- spectral
+// fluxes (GRT_OUT_CHAINS), or, fused, the partial sums of the six rows, of the six rows that are also stored at every
+// point, of every level, or of every level per wavenumber bin -- and what joins gas and Rayleigh is the types of its
+// pack: nothing, GrtCloudArgs, GrtAerosolArgs or GrtSubcolumnArgs, and a GrtBandArgs last where OUT is per bin.
 // The in-kernel range checks of the reference are no-ops on device builds
 // (debug.h:105-116) and are not restated.
 #include <hip/hip_runtime.h>
@@ -238,22 +237,25 @@ __device__ __forceinline__ void put_level(Sink &sink, int lev, double up, double
     sink.put(lev, true, tsi*dn);
 }
 
-// FUSED: the clear-sky tail in one kernel -- tau, omega, g of a layer are formed in registers from tau_gas and the
-// Rayleigh optical depth (LayerOptics: identical values), the first sweep's reflectances are parked in a scratch block
-// instead of the output rows, nothing spectral is written and the six integrated output rows leave as per-block
-// trapezoid partial sums (LevelSink).
-// PROFILE (fused form only): the reference's two sweeps always (shortwave.c:280-329) -- the first parks the downward-beam
-// reflectances of EVERY level in rows 0 .. 2 V - 1 of the park block, the second produces up and down at every level and
-// the sink sums each across the wave at once (as lw_kernel<true, true>).
-// ALLSKY (fused forms, six-row or profile): the liquid and ice cloud objects join per layer (LayerOptics), as in lw_kernel;
-// the one-sweep and two-sweep rule is the form's own.  props_of is the only place that reads the cloud tables, and the
-// fused forms call it in their first (or only) sweep: the two-sweep forms' second sweep reads the parked properties.
-// SPECTRAL (fused six-row form): the six rows also leave at every point, unweighted (LevelSink).
-template <bool FUSED, bool PROFILE, bool ALLSKY = false, bool SPECTRAL = false, typename... Clouds>
-__global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Clouds... clouds)
+// OUT fused (GRT_OUT_ROWS and after): the clear-sky tail in one kernel -- tau, omega, g of a layer are formed in registers
+// from tau_gas and the Rayleigh optical depth (LayerOptics: identical values), the first sweep's reflectances are parked
+// in a scratch block instead of the output rows, nothing spectral is written and the six integrated output rows leave as
+// per-block trapezoid partial sums (LevelSink).
+// GRT_OUT_LEVELS, GRT_OUT_LEVEL_BINS: the reference's two sweeps always (shortwave.c:280-329) -- the first parks the
+// downward-beam reflectances of EVERY level in rows 0 .. 2 V - 1 of the park block, the second produces up and down at
+// every level and the sink sums each across the wave at once (as lw_kernel's), per wavenumber bin with the pack's
+// GrtBandArgs.  GRT_OUT_ROWS_POINTS: the six rows also leave at every point, unweighted (LevelSink).
+// Joins (fused forms): clouds (a GrtCloudArgs, or the draws of a GrtSubcolumnArgs) or the aerosol object join per layer
+// (LayerOptics), as in lw_kernel; the one-sweep and two-sweep rule is OUT's own.  props_of is the only place that reads
+// the joined tables, and the fused forms call it in their first (or only) sweep: the two-sweep forms' second sweep reads
+// the parked properties.
+template <GrtSolverOutput OUT, typename... Joins>
+__global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Joins... joins)
 {
     uint64_t const i = (uint64_t)blockIdx.x*kSolverBlock + threadIdx.x;
-    SolverRow const row = solver_row(a.ncol, clouds...);
+    constexpr bool FUSED = grt_out_fused(OUT), PROFILE = grt_out_levels(OUT), SPECTRAL = OUT == GRT_OUT_ROWS_POINTS;
+    static_assert(has<GrtBandArgs, Joins...> == (OUT == GRT_OUT_LEVEL_BINS), "bins go with GRT_OUT_LEVEL_BINS alone");
+    SolverRow const row = solver_row(a.ncol, joins...);
     int const col = row.col;
     bool const live = i < a.nw;
     if (!FUSED && !live)
@@ -278,9 +280,9 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Clouds...
     // divisions a layer, which is what this kernel's time is made of)
     double *pp = FUSED ? a.park + ((uint64_t)row.park*park_rows + 2*(uint64_t)V)*nw + ii : nullptr;
     int const user = a.user_level;
-    LevelSink<FUSED, PROFILE, SPECTRAL, IsBandPack<Clouds...>::value> sink(a, row.slot, i, live, band_args(clouds...));
-    LayerOptics<FUSED, ALLSKY, IsAerosolPack<Clouds...>::value> const optics(a, cloud_args(clouds...), col, row.tab, ii,
-                                                                             aerosol_args(clouds...));   // (fused forms)
+    LevelSink<FUSED, PROFILE, SPECTRAL, has<GrtBandArgs, Joins...>> sink(a, row.slot, i, live, pick<GrtBandArgs>(joins...));
+    LayerOptics<FUSED, has_clouds<Joins...>, has<GrtAerosolArgs, Joins...>> const optics(
+        a, pick_clouds(joins...), col, row.tab, ii, pick<GrtAerosolArgs>(joins...));                    // (fused forms)
 
     auto props_of = [&](int j) -> LayerProps
     {
@@ -388,12 +390,12 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Clouds...
 }
 
 // ---- spectral form of few columns: the layer properties first, by one thread per (layer, wavenumber) ----
-// One column of the 1 cm-1 shortwave band is 50 000 threads for sw_kernel<false, false>: not one wave per SIMD, each working
+// One column of the 1 cm-1 shortwave band is 50 000 threads for sw_kernel<GRT_OUT_CHAINS>: not one wave per SIMD, each working
 // through 120 layer steps of two delta-Eddington solutions (six exp and a dozen divisions) one after the other.  The
 // solutions of different layers do not depend on each other; only the adding sweeps do, and they are a few operations
 // per layer.  So: sw_props_kernel fills props[col][5 j + k][nw] (k: Rdir, Tdir, Tpure, Rdif, Tdif -- the park layout of
 // the fused form) with layer_props() of every (layer, wavenumber), and sw_sweeps_kernel runs the two sweeps of
-// sw_kernel<false, false> -- the same expressions in the same order on the same doubles, so the fluxes are the same to the last
+// sw_kernel<GRT_OUT_CHAINS> -- the same expressions in the same order on the same doubles, so the fluxes are the same to the last
 // bit -- reading six layers' properties at a time ahead of the dependent chain.
 constexpr int kPropsBlock = 256;
 constexpr int kSweepBlock = 64;
@@ -437,7 +439,7 @@ __global__ __launch_bounds__(kSweepBlock) void sw_sweeps_kernel(GrtSwArgs a)
         return load_props(pp + (uint64_t)(5*j)*nw, nw);
     };
 
-    // sweep 1: shortwave.c:280-294 (as in sw_kernel<false, false>: the downward-beam reflectances are parked in the output rows)
+    // sweep 1: shortwave.c:280-294 (as in sw_kernel<GRT_OUT_CHAINS>: the downward-beam reflectances are parked in the output rows)
     double Rdir_dn = a.alb_dir[(uint64_t)col*a.alb_stride + i];
     double Rdif_dn = a.alb_dif[(uint64_t)col*a.alb_stride + i];
     fu[(uint64_t)L*nw] = Rdir_dn;
@@ -524,112 +526,52 @@ __global__ __launch_bounds__(kSweepBlock) void sw_sweeps_kernel(GrtSwArgs a)
     }
 }
 
+// the one launch site of sw_kernel: the instance of OUT and of the joined arguments' types, on the instance's grid and LDS
+template <GrtSolverOutput OUT, typename... Joins>
+int launch(hipStream_t s, GrtSolverInstance const &in, GrtSwArgs const &a, Joins const &...joins)
+{
+    dim3 const grid(grt_solver_blocks(a.nw), (unsigned)grt_solver_grid_rows(&in, a.ncol), 1);
+    hipLaunchKernelGGL((sw_kernel<OUT, Joins...>), grid, dim3(kSolverBlock), grt_solver_lds(&in, a.num_levels), s, a,
+                       joins...);
+    return (int)hipGetLastError();
+}
+
 } // namespace
 
-extern "C" int grt_launch_sw(void *stream, GrtSolverForm form, GrtSwArgs const *a, GrtCloudArgs const *c,
-                             GrtAerosolArgs const *ae)
+extern "C" int grt_launch_sw(void *stream, GrtSolverInstance const *in, GrtSwArgs const *a)
 {
-    GrtFormKind const k = grt_form_kind(form);
-    bool const park = k.fused && grt_sw_parks(k.profile, a);
-    size_t const lds = grt_profile_lds(k.profile, a->num_levels, kSolverBlock);
     uint64_t const cells = (uint64_t)(a->num_levels - 1)*a->nw;
-    if (a->ncol < 1 || a->nw < 2 ||
-        (k.fused ? (a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr || (park && a->park == nullptr))
-                 : (a->flux_up == nullptr || a->flux_down == nullptr)) ||
-        (k.spectral && (a->flux_up == nullptr || a->flux_down == nullptr)) ||
-        (form == GRT_SOLVER_LAYERS && (a->layer_props == nullptr || cells > 0xffffffffull*kPropsBlock ||
-                                       a->omega == nullptr || a->g == nullptr)) ||
-        ((k.profile || k.aerosol) && (a->num_levels < 2 || lds > 65536)) || (k.allsky && !grt_cloud_args_ok(c)) ||
-        (k.aerosol && !grt_aerosol_args_ok(ae)))
+    if (!grt_solver_instance_ok(*in, *a) || (grt_sw_parks(in, a) && a->park == nullptr) ||
+        (in->out == GRT_OUT_LAYERS && (a->layer_props == nullptr || cells > 0xffffffffull*kPropsBlock ||
+                                       a->omega == nullptr || a->g == nullptr)))
     {
         return (int)hipErrorInvalidValue;
     }
     hipStream_t const s = (hipStream_t)stream;
-    dim3 const grid((unsigned)((a->nw + kSolverBlock - 1)/kSolverBlock), a->ncol, 1);
-    switch (form)
+    // every instance of sw_kernel there is
+    switch (GRT_INSTANCE(in->out, grt_solver_join(in)))
     {
-    case GRT_SOLVER_LAYERS:
+    case GRT_INSTANCE(GRT_OUT_LAYERS, GRT_JOIN_NONE):
         hipLaunchKernelGGL(sw_props_kernel, dim3((unsigned)((cells + kPropsBlock - 1)/kPropsBlock), a->ncol, 1),
                            dim3(kPropsBlock), 0, s, *a);
         hipLaunchKernelGGL(sw_sweeps_kernel, dim3((unsigned)((a->nw + kSweepBlock - 1)/kSweepBlock), a->ncol, 1),
                            dim3(kSweepBlock), 0, s, *a);
-        break;
-    case GRT_SOLVER_FUSED:
-        hipLaunchKernelGGL((sw_kernel<true, false>), grid, dim3(kSolverBlock), 0, s, *a);
-        break;
-    case GRT_SOLVER_CHAINS:
-        hipLaunchKernelGGL((sw_kernel<false, false>), grid, dim3(kSolverBlock), 0, s, *a);
-        break;
-    case GRT_SOLVER_PROFILE:
-        hipLaunchKernelGGL((sw_kernel<true, true>), grid, dim3(kSolverBlock), lds, s, *a);
-        break;
-    case GRT_SOLVER_ALLSKY:
-        hipLaunchKernelGGL((sw_kernel<true, false, true, false, GrtCloudArgs>), grid, dim3(kSolverBlock), 0, s, *a, *c);
-        break;
-    case GRT_SOLVER_ALLSKY_PROFILE:
-        hipLaunchKernelGGL((sw_kernel<true, true, true, false, GrtCloudArgs>), grid, dim3(kSolverBlock), lds, s, *a, *c);
-        break;
-    case GRT_SOLVER_SPECTRAL:
-        hipLaunchKernelGGL((sw_kernel<true, false, false, true>), grid, dim3(kSolverBlock), 0, s, *a);
-        break;
-    case GRT_SOLVER_ALLSKY_SPECTRAL:
-        hipLaunchKernelGGL((sw_kernel<true, false, true, true, GrtCloudArgs>), grid, dim3(kSolverBlock), 0, s, *a, *c);
-        break;
-    case GRT_SOLVER_AEROSOL:
-        hipLaunchKernelGGL((sw_kernel<true, false, false, false, GrtAerosolArgs>), grid, dim3(kSolverBlock), 0, s, *a, *ae);
-        break;
-    case GRT_SOLVER_AEROSOL_PROFILE:
-        hipLaunchKernelGGL((sw_kernel<true, true, false, false, GrtAerosolArgs>), grid, dim3(kSolverBlock), lds, s, *a, *ae);
-        break;
+        return (int)hipGetLastError();
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_NONE): return launch<GRT_OUT_ROWS>(s, *in, *a);
+    case GRT_INSTANCE(GRT_OUT_CHAINS, GRT_JOIN_NONE): return launch<GRT_OUT_CHAINS>(s, *in, *a);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_NONE): return launch<GRT_OUT_LEVELS>(s, *in, *a);
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->clouds);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds);
+    case GRT_INSTANCE(GRT_OUT_ROWS_POINTS, GRT_JOIN_NONE): return launch<GRT_OUT_ROWS_POINTS>(s, *in, *a);
+    case GRT_INSTANCE(GRT_OUT_ROWS_POINTS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_ROWS_POINTS>(s, *in, *a, *in->clouds);
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->aerosols);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->aerosols);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns);
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns);
+    case GRT_INSTANCE(GRT_OUT_LEVEL_BINS, GRT_JOIN_CLOUDS):
+        return launch<GRT_OUT_LEVEL_BINS>(s, *in, *a, *in->clouds, *in->bins);
+    case GRT_INSTANCE(GRT_OUT_LEVEL_BINS, GRT_JOIN_NONE): return launch<GRT_OUT_LEVEL_BINS>(s, *in, *a, *in->bins);
     default:
         return (int)hipErrorInvalidValue;
     }
-    return (int)hipGetLastError();
-}
-
-extern "C" int grt_launch_sw_subcolumns(void *stream, int profile, GrtSwArgs const *a, GrtSubcolumnArgs const *sc)
-{
-    size_t const lds = grt_profile_lds(profile, a->num_levels, kSolverBlock);
-    bool const park = grt_sw_parks(profile, a);
-    if (!grt_subcolumn_args_ok(a->ncol, a->num_levels, a->nw, a->tau_gas, a->n_layer, a->partials, sc) || lds > 65536 ||
-        (park && a->park == nullptr))
-    {
-        return (int)hipErrorInvalidValue;
-    }
-    hipStream_t const s = (hipStream_t)stream;
-    dim3 const grid((unsigned)((a->nw + kSolverBlock - 1)/kSolverBlock), (unsigned)(a->ncol*sc->count), 1);
-    if (profile)
-    {
-        hipLaunchKernelGGL((sw_kernel<true, true, true, false, GrtSubcolumnArgs>), grid, dim3(kSolverBlock), lds, s, *a,
-                           *sc);
-    }
-    else
-    {
-        hipLaunchKernelGGL((sw_kernel<true, false, true, false, GrtSubcolumnArgs>), grid, dim3(kSolverBlock), 0, s, *a,
-                           *sc);
-    }
-    return (int)hipGetLastError();
-}
-
-extern "C" int grt_launch_sw_bands(void *stream, GrtSwArgs const *a, GrtCloudArgs const *c, GrtBandArgs const *bn)
-{
-    if (!grt_band_args_ok(bn) || a->ncol < 1 || a->ncol > 65535 || a->nw < 2 || a->num_levels < 2 ||
-        a->tau_gas == nullptr || a->n_layer == nullptr || a->partials == nullptr || a->park == nullptr ||
-        (c != nullptr && !grt_cloud_args_ok(c)) || grt_band_profile_lds(bn, a->num_levels, kSolverBlock) > 65536)
-    {
-        return (int)hipErrorInvalidValue;
-    }
-    size_t const lds = grt_band_profile_lds(bn, a->num_levels, kSolverBlock);
-    hipStream_t const s = (hipStream_t)stream;
-    dim3 const grid((unsigned)((a->nw + kSolverBlock - 1)/kSolverBlock), a->ncol, 1);
-    if (c != nullptr)
-    {
-        hipLaunchKernelGGL((sw_kernel<true, true, true, false, GrtCloudArgs, GrtBandArgs>), grid, dim3(kSolverBlock), lds, s,
-                           *a, *c, *bn);
-    }
-    else
-    {
-        hipLaunchKernelGGL((sw_kernel<true, true, false, false, GrtBandArgs>), grid, dim3(kSolverBlock), lds, s, *a, *bn);
-    }
-    return (int)hipGetLastError();
 }

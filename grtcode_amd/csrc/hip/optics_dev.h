@@ -5,13 +5,14 @@
 #define GRT_OPTICS_DEV_H_
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../grt_kernels.h"
 #include "exp_pair.h"
 
 #pragma clang fp contract(off)
 
 // workgroup of the solvers' chain and fused forms (grt_solver_blocks: the partial sums of one launch)
-constexpr int kSolverBlock = 128;
+constexpr int kSolverBlock = GRT_SOLVER_BLOCK;
 
 // shortwave/src/rayleigh.c:38-39
 __device__ __forceinline__ double rayleigh_tau(double w, double n)
@@ -79,72 +80,75 @@ __device__ __forceinline__ void aerosol_combine(double tg, double tr, double ta,
     tau = ts;
 }
 
-// The solver kernels' cloud arguments: none in the clear-sky instances, one GrtCloudArgs in the all-sky ones (their
-// template parameter pack: the clear-sky instances keep their parameter list)
-__device__ __forceinline__ GrtCloudArgs cloud_args()
+// ---- fixed-order sums: the bit identities between the fused forms rest on every one of them adding in these orders ----
+// WAVE_SUM(s);  the double variable s of the 64 lanes of a wave by a shuffle tree; lane 0's s holds the sum.  (A statement
+// macro: as a function the tree comes out of the compiler in another instruction order in the level-sum instances.)
+#define WAVE_SUM(s) do { for (int off_ = 32; off_ > 0; off_ >>= 1) { (s) += __shfl_down((s), off_, 64); } } while (0)
+
+// a row of n block partial sums by one wave: lane-strided, then WAVE_SUM; lane 0 holds the sum
+__device__ __forceinline__ double wave_strided_sum(double const *p, unsigned n)
 {
-    return GrtCloudArgs{0, nullptr, nullptr, nullptr, nullptr, nullptr};
+    double s = 0.;
+    for (unsigned b = threadIdx.x; b < n; b += 64)
+    {
+        s += p[b];
+    }
+    WAVE_SUM(s);
+    return s;
 }
 
-__device__ __forceinline__ GrtCloudArgs cloud_args(GrtCloudArgs const &c)
+// the sums the WAVES waves of a workgroup left at part[0 .. WAVES - 1], in wave order
+template <int WAVES>
+__device__ __forceinline__ double waves_sum(double const *part)
 {
-    return c;
+    double s = part[0];
+    for (int k = 1; k < WAVES; ++k)
+    {
+        s += part[k];
+    }
+    return s;
 }
 
-__device__ __forceinline__ GrtCloudArgs cloud_args(GrtSubcolumnArgs const &c)
+// ---- what joins gas and Rayleigh in a solver kernel instance: its parameter pack ----
+// lw_kernel / sw_kernel take their joined arguments as a pack after the band's own (GrtSolverInstance, grt_kernels.h:
+// nothing, GrtCloudArgs, GrtAerosolArgs or GrtSubcolumnArgs, and a GrtBandArgs last in the per-bin instances), so that an
+// instance's kernel arguments hold what it reads and nothing else.  has<T, Pack...>: whether the pack holds a T;
+// pick<T>(pack...): that element, or a T of zeros and null pointers.
+template <typename T, typename... Pack> constexpr bool has = (std::is_same_v<T, Pack> || ... || false);
+
+template <typename T>
+__device__ __forceinline__ T pick()
 {
-    return c.clouds;
+    return T{};
 }
 
-__device__ __forceinline__ GrtCloudArgs cloud_args(GrtAerosolArgs const &)
+template <typename T, typename First, typename... Rest>
+__device__ __forceinline__ T pick(First const &first, Rest const &...rest)
 {
-    return cloud_args();
+    if constexpr (std::is_same_v<T, First>)
+    {
+        return first;
+    }
+    else
+    {
+        return pick<T>(rest...);
+    }
 }
 
-__device__ __forceinline__ GrtCloudArgs cloud_args(GrtBandArgs const &)
-{
-    return cloud_args();
-}
-
-__device__ __forceinline__ GrtCloudArgs cloud_args(GrtCloudArgs const &c, GrtBandArgs const &)
-{
-    return c;
-}
-
-// ... and their aerosol arguments: one GrtAerosolArgs in the aerosol instances (the same pack), none in the others
-template <typename... Pack> struct IsAerosolPack { static constexpr bool value = false; };
-template <> struct IsAerosolPack<GrtAerosolArgs> { static constexpr bool value = true; };
+// the cloud tables of an instance: its GrtCloudArgs, or its GrtSubcolumnArgs' (all-sky: the pack holds either)
+template <typename... Pack> constexpr bool has_clouds = has<GrtCloudArgs, Pack...> || has<GrtSubcolumnArgs, Pack...>;
 
 template <typename... Pack>
-__device__ __forceinline__ GrtAerosolArgs aerosol_args(Pack const &...)
+__device__ __forceinline__ GrtCloudArgs pick_clouds(Pack const &...pack)
 {
-    return GrtAerosolArgs{0, nullptr, nullptr};
-}
-
-__device__ __forceinline__ GrtAerosolArgs aerosol_args(GrtAerosolArgs const &c)
-{
-    return c;
-}
-
-// ... and their wavenumber bins: a GrtBandArgs closes the pack of the banded profile instances (LevelSink), none in the others
-template <typename... Pack> struct IsBandPack { static constexpr bool value = false; };
-template <> struct IsBandPack<GrtBandArgs> { static constexpr bool value = true; };
-template <> struct IsBandPack<GrtCloudArgs, GrtBandArgs> { static constexpr bool value = true; };
-
-template <typename... Pack>
-__device__ __forceinline__ GrtBandArgs band_args(Pack const &...)
-{
-    return GrtBandArgs{0, 0, nullptr, 0};
-}
-
-__device__ __forceinline__ GrtBandArgs band_args(GrtBandArgs const &b)
-{
-    return b;
-}
-
-__device__ __forceinline__ GrtBandArgs band_args(GrtCloudArgs const &, GrtBandArgs const &b)
-{
-    return b;
+    if constexpr (has<GrtSubcolumnArgs, Pack...>)
+    {
+        return pick<GrtSubcolumnArgs>(pack...).clouds;
+    }
+    else
+    {
+        return pick<GrtCloudArgs>(pack...);
+    }
 }
 
 // What grid row blockIdx.y stands for: col, the column whose gas state (tau_gas, temperatures, sun) it reads; tab, its
@@ -152,42 +156,21 @@ __device__ __forceinline__ GrtBandArgs band_args(GrtCloudArgs const &, GrtBandAr
 // blockIdx.y but in the subcolumn instances (GrtSubcolumnArgs: row y is column y / count, subcolumn first + y % count).
 struct SolverRow { int col, tab, slot, park; };
 
-__device__ __forceinline__ SolverRow solver_row(int)
+template <typename... Pack>
+__device__ __forceinline__ SolverRow solver_row(int ncol, Pack const &...pack)
 {
     int const y = blockIdx.y;
-    return SolverRow{y, y, y, y};
-}
-
-__device__ __forceinline__ SolverRow solver_row(int, GrtCloudArgs const &)
-{
-    int const y = blockIdx.y;
-    return SolverRow{y, y, y, y};
-}
-
-__device__ __forceinline__ SolverRow solver_row(int, GrtAerosolArgs const &)
-{
-    int const y = blockIdx.y;
-    return SolverRow{y, y, y, y};
-}
-
-__device__ __forceinline__ SolverRow solver_row(int, GrtBandArgs const &)
-{
-    int const y = blockIdx.y;
-    return SolverRow{y, y, y, y};
-}
-
-__device__ __forceinline__ SolverRow solver_row(int, GrtCloudArgs const &, GrtBandArgs const &)
-{
-    int const y = blockIdx.y;
-    return SolverRow{y, y, y, y};
-}
-
-__device__ __forceinline__ SolverRow solver_row(int ncol, GrtSubcolumnArgs const &sc)
-{
-    int const y = blockIdx.y;
-    int const c = y/sc.count;
-    int const s = sc.first + (y - c*sc.count);
-    return SolverRow{c, s*ncol + c, c*sc.subcolumns + s, y};
+    if constexpr (has<GrtSubcolumnArgs, Pack...>)
+    {
+        GrtSubcolumnArgs const sc = pick<GrtSubcolumnArgs>(pack...);
+        int const c = y/sc.count;
+        int const s = sc.first + (y - c*sc.count);
+        return SolverRow{c, s*ncol + c, c*sc.subcolumns + s, y};
+    }
+    else
+    {
+        return SolverRow{y, y, y, y};
+    }
 }
 
 // One cloud object's optics at (layer j, a point that takes band `band`) from a column's band table tab [3][B][L]
@@ -302,7 +285,7 @@ __device__ __forceinline__ double continua_add(GrtContinua const &c, PointContin
 
 // Spectral trapezoid of driver.c:302-326 inside a solver: every thread holds its own wavenumber's values of the NV
 // rows that are integrated; sum_i 0.5 (f_i + f_{i+1}) dw = sum_i weight_i f_i with weight dw (dw/2 at both ends).
-// Wavefront shuffle reduction, then LDS across the block's waves; thread 0 stores the block's NV partial sums at
+// WAVE_SUM, then waves_sum across the block's waves through LDS; thread v stores row v's sum at
 // partials[(row_base + v)*nblocks + block].  A second tiny launch adds the blocks in a fixed order (deterministic).
 template <int NV, int BLOCK>
 __device__ __forceinline__ void block_partials(double (&val)[NV], double *partials, uint64_t row_base, unsigned nblocks,
@@ -313,10 +296,7 @@ __device__ __forceinline__ void block_partials(double (&val)[NV], double *partia
     for (int v = 0; v < NV; ++v)
     {
         double s = val[v];
-        for (int off = 32; off > 0; off >>= 1)
-        {
-            s += __shfl_down(s, off, 64);
-        }
+        WAVE_SUM(s);
         if ((threadIdx.x & 63) == 0)
         {
             part[v][threadIdx.x >> 6] = s;
@@ -325,34 +305,26 @@ __device__ __forceinline__ void block_partials(double (&val)[NV], double *partia
     __syncthreads();
     if (threadIdx.x < NV)
     {
-        double s = part[threadIdx.x][0];
-        for (int k = 1; k < BLOCK/64; ++k)
-        {
-            s += part[threadIdx.x][k];
-        }
-        partials[(row_base + threadIdx.x)*nblocks + block] = s;
+        partials[(row_base + threadIdx.x)*nblocks + block] = waves_sum<BLOCK/64>(part[threadIdx.x]);
     }
 }
 
 // Profile form of the fused solvers: every level's flux is a row of its own, 2 V rows per column -- more accumulators than
 // a thread has registers for, so each level's weighted value is summed across the wave as soon as it is produced, by
-// block_partials' shuffle tree, and lane 0 parks the wave's sum at lds[row*(BLOCK/64) + wave].  lds: dynamic LDS of
+// WAVE_SUM, and lane 0 parks the wave's sum at lds[row*(BLOCK/64) + wave].  lds: dynamic LDS of
 // nrows*(BLOCK/64) doubles.
 template <int BLOCK>
 __device__ __forceinline__ void wave_row_sum(double s, double *lds, int row)
 {
-    for (int off = 32; off > 0; off >>= 1)
-    {
-        s += __shfl_down(s, off, 64);
-    }
+    WAVE_SUM(s);
     if ((threadIdx.x & 63) == 0)
     {
         lds[row*(BLOCK/64) + (threadIdx.x >> 6)] = s;
     }
 }
 
-// ... and after the sweeps: the waves' sums of each row added in wave order (block_partials' association: a row that is
-// also one of the six-row form's gets the same bits), stored at partials[(row_base + row)*nblocks + block].
+// ... and after the sweeps: the waves' sums of each row by waves_sum (as block_partials: a row that is also one of the
+// six-row form's gets the same bits), stored at partials[(row_base + row)*nblocks + block].
 template <int BLOCK>
 __device__ __forceinline__ void block_row_partials(double const *lds, int nrows, double *partials, uint64_t row_base,
                                                    unsigned nblocks, unsigned block)
@@ -360,12 +332,7 @@ __device__ __forceinline__ void block_row_partials(double const *lds, int nrows,
     __syncthreads();
     for (int r = threadIdx.x; r < nrows; r += BLOCK)
     {
-        double s = lds[r*(BLOCK/64)];
-        for (int k = 1; k < BLOCK/64; ++k)
-        {
-            s += lds[r*(BLOCK/64) + k];
-        }
-        partials[(row_base + r)*nblocks + block] = s;
+        partials[(row_base + r)*nblocks + block] = waves_sum<BLOCK/64>(lds + r*(BLOCK/64));
     }
 }
 
@@ -591,19 +558,15 @@ struct LevelSink
     {
         if (PROFILE && BANDED)
         {
-            // (block_row_partials per bin of the block: the waves' sums in wave order)
+            // (block_row_partials per bin of the block)
             __syncthreads();
             double const *lds = level_sums();
             for (int k = threadIdx.x; k < bin_count*2*V; k += kSolverBlock)
             {
                 int const q = k/(2*V), r = k - q*2*V;
                 int const *e = bins.table + 4*(bin_lo + q);
-                double s = lds[k*(kSolverBlock/64)];
-                for (int w = 1; w < kSolverBlock/64; ++w)
-                {
-                    s += lds[k*(kSolverBlock/64) + w];
-                }
-                a.partials[((uint64_t)col*2*V + r)*bins.per_row + e[2] + (int)blockIdx.x - e[3]] = s;
+                a.partials[((uint64_t)col*2*V + r)*bins.per_row + e[2] + (int)blockIdx.x - e[3]] =
+                    waves_sum<kSolverBlock/64>(lds + k*(kSolverBlock/64));
             }
         }
         else if (PROFILE)

@@ -11,14 +11,22 @@ static int pass_tag(GrtPass const *ps, int bi)
     return (ps->aer_pass ? 12 : (ps->clouds ? 8 : 3)) + bi;
 }
 
-/* its solver form (materialised: the spectral form, after pass_optics) */
-static GrtSolverForm pass_form(GrtPipeline_t const *p, GrtPass const *ps)
+/* its solver instance (materialised: the spectral form, after pass_optics); bn: its per-bin instance; sc: the pass's
+   clouds as the subcolumns of sc */
+static GrtSolverInstance pass_instance(GrtPipeline_t const *p, GrtPass const *ps, GrtBandArgs const *bn,
+                                       GrtSubcolumnArgs const *sc)
 {
-    if (p->keep_spectra) return GRT_SOLVER_CHAINS;
-    if (ps->so != NULL) return ps->clouds ? GRT_SOLVER_ALLSKY_SPECTRAL : GRT_SOLVER_SPECTRAL;
-    if (ps->aer != NULL) return ps->profile ? GRT_SOLVER_AEROSOL_PROFILE : GRT_SOLVER_AEROSOL;
-    if (ps->clouds != NULL) return ps->profile ? GRT_SOLVER_ALLSKY_PROFILE : GRT_SOLVER_ALLSKY;
-    return ps->profile ? GRT_SOLVER_PROFILE : GRT_SOLVER_FUSED;
+    GrtSolverInstance in = {GRT_OUT_CHAINS, NULL, NULL, NULL, NULL};
+    if (!p->keep_spectra)
+    {
+        in.out = ps->so != NULL ? GRT_OUT_ROWS_POINTS : (bn != NULL ? GRT_OUT_LEVEL_BINS :
+                 (ps->profile ? GRT_OUT_LEVELS : GRT_OUT_ROWS));
+        in.clouds = sc != NULL ? NULL : ps->clouds;
+        in.aerosols = ps->aer;
+        in.subcolumns = sc;
+        in.bins = bn;
+    }
+    return in;
 }
 
 /* its rows per band and column, and where band bi's start in a column's out_stride doubles */
@@ -114,52 +122,60 @@ static int park_block(GrtPipeline_t *p, GrtBand *b)
     return GRTCODE_SUCCESS;
 }
 
-/* the band's solver in the pass's form, timed under the pass's profile tag; the profile forms share the band's park block
-   with the two-sweep six-row forms (the passes run in stream order); the spectral six-row forms store their rows where
-   the pass's so places the band's; with bn (profile forms), their banded instances */
+/* The arguments of the band's solver in the instance in, in whichever of the two structs is the band's: the partial sums,
+   where the six rows at every point go (the pass's so), and the shortwave's park block, which the level forms share with
+   the two-sweep six-row forms (the passes run in stream order) */
+typedef struct SolverArgs { GrtLwArgs lw; GrtSwArgs sw; } SolverArgs;
+
+static int solver_args(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps, GrtSolverInstance const *in,
+                       double *partials, SolverArgs *a)
+{
+    size_t stride = 0;
+    double *rows = in->out == GRT_OUT_ROWS_POINTS
+                       ? ps->so->spectral + spectral_offset(ps, bi, band_points(p, 0), band_points(p, 1), &stride) : NULL;
+    if (bi == 0)
+    {
+        lw_args(p, b, C, grt_out_fused(in->out), ps, &a->lw);
+        a->lw.partials = partials;
+        if (rows != NULL)
+        {
+            a->lw.flux_up = rows;
+            a->lw.flux_down = rows + 3*b->n;
+            a->lw.flux_stride = stride;
+        }
+        return GRTCODE_SUCCESS;
+    }
+    sw_args(p, b, C, grt_out_fused(in->out), ps, &a->sw);
+    a->sw.partials = partials;
+    if (rows != NULL)
+    {
+        a->sw.flux_up = rows;
+        a->sw.flux_down = rows + 3*b->n;
+        a->sw.flux_stride = stride;
+    }
+    if (grt_sw_parks(in, &a->sw))
+    {
+        GRT_TRY(park_block(p, b));
+    }
+    a->sw.park = b->park;
+    return GRTCODE_SUCCESS;
+}
+
+static int solver_launch(void *s, int bi, GrtSolverInstance const *in, SolverArgs const *a)
+{
+    return bi == 0 ? grt_launch_lw(s, in, &a->lw) : grt_launch_sw(s, in, &a->sw);
+}
+
+/* the band's solver in the pass's instance (bn: its per-bin one), timed under the pass's profile tag */
 static int band_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps, double *partials,
                        GrtBandArgs const *bn)
 {
-    GrtSolverForm const form = pass_form(p, ps);
-    GrtFormKind const k = grt_form_kind(form);
+    GrtSolverInstance const in = pass_instance(p, ps, bn, NULL);
     void *s = grt_dev_stream(p->device);
-    size_t stride = 0;
-    double *rows = k.spectral ? ps->so->spectral + spectral_offset(ps, bi, band_points(p, 0), band_points(p, 1), &stride)
-                              : NULL;
-    int slot, krc;
-    if (bi == 0)
-    {
-        GrtLwArgs a;
-        lw_args(p, b, C, k.fused, ps, &a);
-        a.partials = partials;
-        if (k.spectral)
-        {
-            a.flux_up = rows;
-            a.flux_down = rows + 3*b->n;
-            a.flux_stride = stride;
-        }
-        slot = grt_profile_begin(s, pass_tag(ps, bi));
-        krc = bn != NULL ? grt_launch_lw_bands(s, &a, ps->clouds, bn) : grt_launch_lw(s, form, &a, ps->clouds, ps->aer);
-    }
-    else
-    {
-        GrtSwArgs a;
-        sw_args(p, b, C, k.fused, ps, &a);
-        a.partials = partials;
-        if (k.spectral)
-        {
-            a.flux_up = rows;
-            a.flux_down = rows + 3*b->n;
-            a.flux_stride = stride;
-        }
-        if (k.fused && grt_sw_parks(k.profile, &a))
-        {
-            GRT_TRY(park_block(p, b));
-        }
-        a.park = b->park;
-        slot = grt_profile_begin(s, pass_tag(ps, bi));
-        krc = bn != NULL ? grt_launch_sw_bands(s, &a, ps->clouds, bn) : grt_launch_sw(s, form, &a, ps->clouds, ps->aer);
-    }
+    SolverArgs a;
+    GRT_TRY(solver_args(p, b, bi, C, ps, &in, partials, &a));
+    int const slot = grt_profile_begin(s, pass_tag(ps, bi));
+    int const krc = solver_launch(s, bi, &in, &a);
     grt_profile_end(s, slot);
     GRT_TRY(grt_dev_check(krc, bi == 0 ? "longwave kernel" : "shortwave kernel"));
     return GRTCODE_SUCCESS;
@@ -421,33 +437,20 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
             b->sub_partials = sp;
             b->sub_cap = need;
         }
-        GrtLwArgs lw;
-        GrtSwArgs sw;
-        int group = 65535/C;                   /* (grid rows) */
-        if (bi == 0)
-        {
-            lw_args(p, b, C, 1, ps, &lw);
-            lw.partials = b->sub_partials;
-        }
-        else
-        {
-            sw_args(p, b, C, 1, ps, &sw);
-            sw.partials = b->sub_partials;
-            if (grt_sw_parks(ps->profile, &sw))
-            {
-                GRT_TRY(park_block(p, b));
-                group = p->max_cols/C;
-            }
-            sw.park = b->park;
-        }
+        /* (in points at sc: the loop below walks sc.first and sc.count, which the launcher alone reads) */
+        GrtSubcolumnArgs sc = {*ps->clouds, S, 0, 0};
+        GrtSolverInstance const in = pass_instance(p, ps, NULL, &sc);
+        SolverArgs a;
+        GRT_TRY(solver_args(p, b, bi, C, ps, &in, b->sub_partials, &a));
+        /* (grid rows; a park block of max_cols columns) */
+        int group = bi == 1 && grt_sw_parks(&in, &a.sw) ? p->max_cols/C : 65535/C;
         group = group < S ? group : S;
         int const slot = grt_profile_begin(s, pass_tag(ps, bi));
         int krc = 0;
-        for (int first = 0; first < S && krc == 0; first += group)
+        for (sc.first = 0; sc.first < S && krc == 0; sc.first += group)
         {
-            GrtSubcolumnArgs const sc = {*ps->clouds, S, first, S - first < group ? S - first : group};
-            krc = bi == 0 ? grt_launch_lw_subcolumns(s, ps->profile, &lw, &sc)
-                          : grt_launch_sw_subcolumns(s, ps->profile, &sw, &sc);
+            sc.count = S - sc.first < group ? S - sc.first : group;
+            krc = solver_launch(s, bi, &in, &a);
         }
         grt_profile_end(s, slot);
         GRT_TRY(grt_dev_check(krc, bi == 0 ? "longwave subcolumn kernel" : "shortwave subcolumn kernel"));
