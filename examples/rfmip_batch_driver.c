@@ -8,7 +8,8 @@
  *     copied (:290-308); the well-mixed gases are one global-mean value per experiment (:310-325);
  *   - cos(zenith) from degrees, columns with the sun below the horizon get no shortwave (driver.c:706);
  *   - a spectrally constant surface albedo / emissivity (the two-point "constant" grids of :221-256 with
- *     constant_extrapolation, driver.c:102-115);
+ *     constant_extrapolation, driver.c:102-115): one value for the whole run, the last column's, or -- with
+ *     -surface-per-column -- each column's own, as the reference application takes them;
  *   - N2 for the collision-induced absorption at 0.781 (driver.c: set_cia_ppmv with a constant profile).
  *
  * Input file (little-endian, our own flat dump standing in for multiple_input4MIPs_radiation_RFMIP_*.nc):
@@ -21,7 +22,7 @@
  * Usage:  rfmip_batch_driver HITRAN.par SOLAR.csv COLUMNS.bin [-h2o-ctm DIR] [-o3-ctm FILE] [-CFC-11 FILE ppmv]
  *             [-CFC-12 FILE ppmv] [-N2-N2 FILE] [-O2-N2 FILE] [-O2-O2 FILE] [-w-lw W0 -W-lw WN -r-lw DW]
  *             [-w-sw W0 -W-sw WN -r-sw DW] [-chunk N] [-fast 0|1|2|3] [-d DEVICE]
- *             [-ranks N -rank K -rendezvous DIR [-transport rccl|files]] [-profiles] [-bin-width DW]
+ *             [-ranks N -rank K -rendezvous DIR [-transport rccl|files]] [-profiles] [-bin-width DW] [-surface-per-column]
  * Output: one line per column "col <i>: rlut rlus rldt rlds rsut rsus rsdt rsds" [W m-2] (zeros for the shortwave
  * of night columns).  With -profiles each column's line is followed by its broadband fluxes at every level, top first,
  * "lev <k>: rlu rld rsu rsd" [W m-2], and the heating rate of every layer, "lay <j>: hr_lw hr_sw" [K day-1]
@@ -31,6 +32,9 @@
  * points from each band's first point (the last bin shorter; adjacent bins share their edge point),
  * "lwbin <b>: w_lo w_hi rlut rlus rldt rlds" and "swbin <b>: w_lo w_hi rsut rsus rsdt rsds" [cm-1, W m-2]
  * (grt_pipeline_run_spectral; night columns get zeros in their shortwave bins).
+ * With -surface-per-column every column is solved over its own surface_emissivity and surface_albedo: per chunk the
+ * two-point grids of rfmip-irf.c:221-256 go to the chunk's pipeline with grt_pipeline_set_surface.  Without it the last
+ * column's two values serve all columns.
  *
  * Several GPUs of one node: start one process per GPU with the same arguments plus -ranks N -rank K (K = 0..N-1,
  * normally with -d K) and a directory all of them see.  Every rank computes its contiguous block of the columns
@@ -76,6 +80,7 @@ typedef struct Run
     SpectralGrid_t const *grids[2];             /* longwave, shortwave */
     int *edges[2], nb[2];                       /* -bin-width: grid-point edges and bin counts of the two bands */
     GrtPipeline_t *pipe[2];                     /* day, night */
+    int surface_per_column;                     /* -surface-per-column */
 } Run;
 
 /* One kind of result: `row` doubles per column.  run() sends a chunk of m columns through the pipeline and leaves m rows
@@ -93,6 +98,7 @@ typedef struct Kind
 typedef struct Columns
 {
     double *p, *t, *tl, *ts, *mu, *tsi, *mol, *cfc, *cia;
+    double *emis, *alb;                         /* [n][2]: each column's value at the two points of the constant grid */
 } Columns;
 
 /* -bin-width: grid-point edges every round(width/dw) points from 0, the last at n - 1; returns the bin count */
@@ -223,13 +229,15 @@ static Columns alloc_columns(int n, int V)
     int const L = V - 1;
     Columns c = {malloc(sizeof(double)*n*V), malloc(sizeof(double)*n*V), malloc(sizeof(double)*n*L),
                  malloc(sizeof(double)*n), malloc(sizeof(double)*n), malloc(sizeof(double)*n),
-                 malloc(sizeof(double)*n*7*V), malloc(sizeof(double)*(n*2*V + 1)), malloc(sizeof(double)*n*NUM_CIAS*V)};
+                 malloc(sizeof(double)*n*7*V), malloc(sizeof(double)*(n*2*V + 1)), malloc(sizeof(double)*n*NUM_CIAS*V),
+                 malloc(sizeof(double)*n*2), malloc(sizeof(double)*n*2)};
     return c;
 }
 
 static void free_columns(Columns *c)
 {
     free(c->p); free(c->t); free(c->tl); free(c->ts); free(c->mu); free(c->tsi); free(c->mol); free(c->cfc); free(c->cia);
+    free(c->emis); free(c->alb);
 }
 
 /* the buffers of the enabled kinds: for a chunk on the device and on the host, for `rows` columns (all ranks' blocks) */
@@ -263,8 +271,10 @@ static int free_kinds(Run const *r, Kind *kinds)
     return EXIT_SUCCESS;
 }
 
-/* raw columns -> the batched layout of GrtColumns_t; the surface values are the LAST column's (one value for the run,
- * like the app's -e / -a) */
+/* raw columns -> the batched layout of GrtColumns_t.  Every column's own surface emissivity and albedo are kept, at both
+ * points of the two-point constant grid (rfmip-irf.c:221-256), for -surface-per-column; *emis_value and *albedo_value are
+ * the LAST column's: without that flag one value serves the whole run, like the app's -e / -a, whatever the other columns
+ * of the file say. */
 static Columns prepare_columns(double const *raw, size_t per_col, int ncol, int V, double const gm[5], int ncfc,
                                double const cfc_ppmv[2], double *emis_value, double *albedo_value)
 {
@@ -287,8 +297,8 @@ static Columns prepare_columns(double const *raw, size_t per_col, int ncol, int 
             a.tl[c*L + k] = tlay[k];
         }
         a.ts[c] = scal[0];
-        *emis_value = scal[1];
-        *albedo_value = scal[2];
+        *emis_value = a.emis[2*c] = a.emis[2*c + 1] = scal[1];
+        *albedo_value = a.alb[2*c] = a.alb[2*c + 1] = scal[2];
         a.mu[c] = cos(2.*M_PI*scal[3]/360.);
         a.tsi[c] = scal[4];
         double *m = a.mol + (size_t)c*7*V;
@@ -331,11 +341,23 @@ static int run_class(Run const *r, Kind *kinds, Columns const *a, Columns *c, in
             memcpy(c->t + j*V, a->t + i*V, sizeof(double)*V);
             memcpy(c->tl + j*L, a->tl + i*L, sizeof(double)*L);
             c->ts[j] = a->ts[i]; c->mu[j] = a->mu[i]; c->tsi[j] = a->tsi[i];
+            memcpy(c->emis + 2*j, a->emis + 2*i, sizeof(double)*2);
+            memcpy(c->alb + 2*j, a->alb + 2*i, sizeof(double)*2);
             memcpy(c->mol + (size_t)j*7*V, a->mol + (size_t)i*7*V, sizeof(double)*7*V);
             memcpy(c->cfc + (size_t)j*ncfc*V, a->cfc + (size_t)i*ncfc*V, sizeof(double)*ncfc*V);
             memcpy(c->cia + (size_t)j*NUM_CIAS*V, a->cia + (size_t)i*NUM_CIAS*V, sizeof(double)*NUM_CIAS*V);
         }
         GrtColumns_t cols = {m, V, c->p, c->t, c->tl, c->ts, c->mol, ncfc ? c->cfc : NULL, c->cia, c->mu, c->tsi};
+        if (r->surface_per_column)
+        {
+            /* the chunk's own surface, on the constant grids of rfmip-irf.c:221-256: every grid point lies above them and
+               takes the value constant_extrapolation finds there (the night pipeline has no shortwave: no albedo) */
+            static fp_t const constant_grid[2] = {-1., 0.};
+            GrtSurface_t const surface = {.ncol = m, .emissivity_num_points = 2, .albedo_num_points = 2,
+                                          .emissivity_grid = constant_grid, .albedo_grid = constant_grid,
+                                          .emissivity = c->emis, .direct_albedo = c->alb, .diffuse_albedo = NULL};
+            check(grt_pipeline_set_surface(r->pipe[night], &surface));
+        }
         for (Kind *k = kinds; k < kinds + NUM_KINDS; ++k)
         {
             if (!k->enabled) continue;
@@ -457,7 +479,8 @@ int main(int argc, char **argv)
     Device_t device;
     int dev_id = (int)number(argc, argv, "-d", 0.);
     check(create_device(&device, option(argc, argv, "-d", 1) ? &dev_id : NULL));
-    Run r = {.device = device, .V = V, .L = L, .chunk = (int)number(argc, argv, "-chunk", 16.), .grids = {&lw_grid, &sw_grid}};
+    Run r = {.device = device, .V = V, .L = L, .chunk = (int)number(argc, argv, "-chunk", 16.), .grids = {&lw_grid, &sw_grid},
+             .surface_per_column = option(argc, argv, "-surface-per-column", 0) != NULL};
     GasOptics_t lbl[2];
     int ncfc = 0;
     double cfc_ppmv[2] = {0., 0.};

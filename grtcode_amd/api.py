@@ -141,6 +141,12 @@ class GrtAerosols(C.Structure):
                 ("lw_optics", c_double_p), ("sw_optics", c_double_p)]
 
 
+class GrtSurface(C.Structure):
+    _fields_ = [("ncol", C.c_int), ("emissivity_num_points", C.c_int), ("albedo_num_points", C.c_int),
+                ("emissivity_grid", c_double_p), ("albedo_grid", c_double_p), ("emissivity", c_double_p),
+                ("direct_albedo", c_double_p), ("diffuse_albedo", c_double_p)]
+
+
 #: every symbol include/*.h declares (checked by tests/test_abi_symbols.py against the headers too)
 EXPORTS = """
 grtcode_errstr grtcode_set_verbosity grtcode_verbosity create_device get_num_gpus
@@ -156,7 +162,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_aerosols grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_aerosols grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_pipeline_set_surface grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -207,6 +213,7 @@ def load_library(path=None):
                                                 C.c_void_p, C.c_void_p, C.c_void_p]
     lib.grt_pipeline_run_aerosols.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtAerosols), C.c_void_p,
                                               C.c_void_p, C.c_void_p]
+    lib.grt_pipeline_set_surface.argtypes = [C.c_void_p, C.POINTER(GrtSurface)]
     lib.grt_multi_gather_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.grt_pipeline_sync.argtypes = [C.c_void_p]
     lib.grt_pipeline_stream.argtypes = [C.c_void_p]
@@ -525,6 +532,37 @@ def make_aerosols(lw=None, sw=None):
     return ga, keep
 
 
+def make_surface(ncol, emissivity=None, albedo=None):
+    """Pack per-column surface inputs into a GrtSurface struct (+ keep-alive arrays) for Pipeline.set_surface.
+    emissivity: (grid, values) -- grid [NS] cm-1, strictly increasing, NS >= 2; values [ncol][NS] in [0, 1] -- or None: the
+    longwave keeps the pipeline's creation-time array.  albedo: (grid, direct) or (grid, direct, diffuse), each of values'
+    shape; diffuse None or left out: both beams take the direct one; None: the shortwave keeps its creation-time array."""
+    keep = {"ncol": int(ncol), "num_points": [0, 0]}
+    for k in ("emissivity_grid", "albedo_grid", "emissivity", "direct_albedo", "diffuse_albedo"):
+        keep[k] = None
+    for band, (name, given, arrays) in enumerate((("emissivity", emissivity, ("emissivity",)),
+                                                  ("albedo", albedo, ("direct_albedo", "diffuse_albedo")))):
+        if given is None:
+            continue
+        grid = _f64(given[0])
+        if grid.ndim != 1 or grid.size < 2:
+            raise ValueError(f"{name} grid of {grid.size} point(s): at least 2")
+        keep[name + "_grid"] = grid
+        keep["num_points"][band] = grid.size
+        for k, v in zip(arrays, given[1:]):
+            if v is None:
+                continue
+            keep[k] = _f64(v)
+            if keep[k].shape != (keep["ncol"], grid.size):
+                raise ValueError(f"{k} of shape {keep[k].shape}: [{keep['ncol']}][{grid.size}]")
+        if keep[arrays[0]] is None:
+            raise ValueError(f"{name} grid without values")
+    keep["num_points"] = tuple(keep["num_points"])
+    gs = GrtSurface(keep["ncol"], *keep["num_points"], *[_opt_dp(keep[k]) for k in (
+        "emissivity_grid", "albedo_grid", "emissivity", "direct_albedo", "diffuse_albedo")])
+    return gs, keep
+
+
 class Pipeline:
     def __init__(self, lw_gas, sw_gas, max_columns, user_level, emissivity, albedo, solar, spectral=True):
         """spectral=True keeps tau/omega/g and the spectral fluxes (views(): what parity tests read);
@@ -581,6 +619,11 @@ class Pipeline:
 
     def run(self, gcols, out_ptr=None):
         check(self.lib.grt_pipeline_run(self.p, C.byref(gcols), out_ptr if out_ptr is not None else self.out.ptr))
+
+    def set_surface(self, gsurface):
+        """grt_pipeline_set_surface: each column's own emissivity and albedo (make_surface) for every later run of this
+        object, whatever the entry point, until it is replaced or -- gsurface None -- cleared."""
+        check(self.lib.grt_pipeline_set_surface(self.p, C.byref(gsurface) if gsurface is not None else None))
 
     def sync(self):
         check(self.lib.grt_pipeline_sync(self.p))

@@ -374,6 +374,25 @@ static inline int grt_aerosol_args_ok(GrtAerosolArgs const *c)
 int grt_launch_spread_aerosols(void *stream, int num_layers, int ncol, double w0, double dw, uint64_t nw,
                                GrtAerosolArgs const *c, double *tau, double *omega, double *g);
 
+/* grt_pipeline_set_surface: a surface property (emissivity, direct or diffuse albedo) of every column on the band's grid,
+   rows [ncol][nw], as interpolate_to_grid(..., linear_sample, constant_extrapolation) puts a column's NS knots there
+   (utilities.c:149-246, :77-92).  The host turns a column's knots into num_entries = NS + 1 slope and intercept pairs --
+   entry 0: (0, y[0]) for w <= x[0]; entry 1 + j: interval j, x[j] < w <= x[j+1]; entry NS: (0, y[NS-2]) for w > x[NS-1]
+   (the reference's value there) --, so every point evaluates slope w + intercept.  entry: DEVICE [nw], each grid point's
+   entry, every value in 0 .. num_entries - 1; tables: DEVICE [ncol][num_entries][2]. */
+typedef struct GrtSurfaceArgs
+{
+    int num_entries;                /* NS + 1 >= 3 */
+    int const *entry;
+    double const *tables;
+} GrtSurfaceArgs;
+static inline int grt_surface_args_ok(GrtSurfaceArgs const *c)
+{
+    return c != NULL && c->num_entries >= 3 && c->entry != NULL && c->tables != NULL;
+}
+int grt_launch_spread_surface(void *stream, int ncol, double w0, double dw, uint64_t nw, GrtSurfaceArgs const *c,
+                              double *rows);
+
 /* Subcolumn form of the two all-sky forms (subcolumns joined in place of clouds, six rows or every level;
    grt_pipeline_run_subcolumns): one launch solves subcolumns first .. first + count - 1 of every column, a->ncol columns of
    gas state (tau_gas, n_layer, temperatures, sun, continua) and `subcolumns` cloud draws per column.  Row y of the grid

@@ -169,6 +169,24 @@ __global__ __launch_bounds__(kBlock) void spread_aerosols_kernel(int L, int ncol
     }
 }
 
+// grt_pipeline_set_surface: each column's surface emissivity or albedo on the band's grid, rows [ncol][nw], from the
+// columns' slope and intercept entries (GrtSurfaceArgs): one thread per column and grid point reads the point's entry
+// index and the column's (m, b) and stores m w + b -- linear_sample's expression (utilities.c:235-246); the entries of the
+// two constant ranges have m = 0, and 0 w + b is b.  Consecutive lanes store consecutive doubles.
+__global__ __launch_bounds__(kBlock) void spread_surface_kernel(int ncol, double w0, double dw, uint64_t nw, GrtSurfaceArgs c,
+                                                                double *rows)
+{
+    uint64_t const total = nw*(uint64_t)ncol;
+    for (uint64_t o = (uint64_t)blockIdx.x*kBlock + threadIdx.x; o < total; o += (uint64_t)gridDim.x*kBlock)
+    {
+        uint64_t const col = o/nw;
+        uint64_t const i = o - col*nw;
+        double const *mb = c.tables + (col*(uint64_t)c.num_entries + (uint64_t)c.entry[i])*2;
+        double const w = w0 + i*dw;
+        rows[o] = mb[0]*w + mb[1];
+    }
+}
+
 // tau_gas += the spectral tables' part, for a tau the gas-optics launch wrote without it (GrtGasOpticsArgs.skip_tables):
 // the pipeline's fused solvers add it themselves; this completes the array for a caller that wants to LOOK at tau_gas
 // (grt_pipeline_views).  One thread per grid point and column, walking the layers: continua_add's doubles.
@@ -614,6 +632,18 @@ extern "C" int grt_launch_spread_aerosols(void *stream, int num_layers, int ncol
     }
     hipLaunchKernelGGL(spread_aerosols_kernel, dim3(grid_for((uint64_t)num_layers*nw*ncol)), dim3(kBlock), 0,
                        (hipStream_t)stream, num_layers, ncol, w0, dw, nw, *c, tau, omega, g);
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_spread_surface(void *stream, int ncol, double w0, double dw, uint64_t nw, GrtSurfaceArgs const *c,
+                                         double *rows)
+{
+    if (ncol < 1 || nw < 1 || !grt_surface_args_ok(c) || rows == nullptr)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(spread_surface_kernel, dim3(grid_for(nw*(uint64_t)ncol)), dim3(kBlock), 0, (hipStream_t)stream, ncol,
+                       w0, dw, nw, *c, rows);
     return (int)hipGetLastError();
 }
 

@@ -181,6 +181,11 @@ int grt_load_table_on_grid(char const *path, int expect_cols, SpectralGrid_t con
    parametrisation's `own` bands with limits lo, hi) each of the n ascending points w takes, -1: none */
 void grt_aerosol_interval_map(double w0, double dw, uint64_t n, double const *x, int na, int *interval);
 void grt_aerosol_tables(double const *x, int na, int ncol, int num_layers, double const *optics, double *tables);
+/* ... and of grt_pipeline_set_surface's (GrtSurfaceArgs in grt_kernels.h): the entry of the surface grid x [ns] each of the
+   n points w0 + i dw takes -- 0 for w <= x[0], 1 + j for x[j] < w <= x[j+1], ns for w > x[ns-1] --, and the slope and
+   intercept entries [ncol][ns + 1][2] of values [ncol][ns] */
+void grt_surface_entry_map(double w0, double dw, uint64_t n, double const *x, int ns, int *entry);
+void grt_surface_tables(double const *x, int ns, int ncol, double const *values, double *tables);
 void grt_cloud_band_map(double const *lo, double const *hi, int own, int nb, double const *w, int n, int *idx);
 
 #endif

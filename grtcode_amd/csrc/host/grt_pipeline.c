@@ -30,6 +30,9 @@
  * grt_pipeline_run_band_profiles runs the profile form of the clear-sky pass and, with clouds, of the all-sky pass with
  * every level's flux integrated per wavenumber bin instead of over the whole grid, and one finishing launch for the bins'
  * heating rates.
+ * grt_pipeline_set_surface gives the columns of the runs that follow their own surface emissivity and albedo
+ * (driver.c:101-117): rows written on the device from each column's few knots, read by the solvers in place of the shared
+ * creation-time arrays.
  * All work is enqueued on the device's library stream; nothing synchronises.
  * Here: the object, the small per-column inputs, the gas optics, the run and the entry points with their checks;
  * grt_pipeline_inputs.c stages what a caller gives besides the columns, grt_pipeline_solve.c solves one band.
@@ -229,7 +232,11 @@ static void grt_pipeline_release(GrtPipeline_t **pipeline)
         grt_dev_free(p->device, p->band[b].bin_partials);
         grt_dev_free(p->device, p->band[b].sub_partials);
         grt_dev_free(p->device, p->band[b].flux_sum);
+        grt_keyed_table_free(p, &p->band[b].surf_map);
+        grt_dev_free(p->device, p->band[b].surf_rows);
+        grt_dev_free(p->device, p->band[b].surf_rows_dif);
     }
+    grt_staging_free(p, &p->surf);
     grt_staging_free(p, &p->aer);
     grt_staging_free(p, &p->cloud);
     grt_staging_free(p, &p->small);
@@ -293,6 +300,19 @@ EXTERN int grt_pipeline_views(GrtPipeline_t *pipeline, int band, fp_t **tau_gas,
     return GRTCODE_SUCCESS;
 }
 
+/* A pipeline belongs to the lane (HIP stream) that was selected when it was created: grt_pipeline_stream() hands THAT
+   stream to the caller (who orders a gather behind it), while the kernels of a call go to the lane selected now.  The two
+   must be the same: select the pipeline's lane before running it. */
+static int check_lane(GrtPipeline_t const *p)
+{
+    if (grt_dev_lane(p->device) != p->lane)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "this pipeline was created on lane %d, lane %d is selected: call grt_device_use_lane "
+                 "before grt_pipeline_run.", p->lane, grt_dev_lane(p->device));
+    }
+    return GRTCODE_SUCCESS;
+}
+
 /* What grt_pipeline_run and grt_pipeline_run_profiles check and stage alike: the arguments, the lane, and the small
    per-column inputs, uploaded to small.d on the library stream. */
 static int stage_columns(GrtPipeline_t *p, GrtColumns_t const *cols)
@@ -302,14 +322,7 @@ static int stage_columns(GrtPipeline_t *p, GrtColumns_t const *cols)
     GRT_REQUIRE_PTR(cols->pressure);
     GRT_REQUIRE_PTR(cols->temperature);
     int const V = p->num_levels, L = V - 1, C = cols->ncol;
-    /* A pipeline belongs to the lane (HIP stream) that was selected when it was created: grt_pipeline_stream() hands THAT
-       stream to the caller (who orders a gather behind it), while the kernels below go to the lane selected now.  The two
-       must be the same: select the pipeline's lane before running it. */
-    if (grt_dev_lane(p->device) != p->lane)
-    {
-        GRT_FAIL(GRTCODE_VALUE_ERR, "this pipeline was created on lane %d, lane %d is selected: call grt_device_use_lane "
-                 "before grt_pipeline_run.", p->lane, grt_dev_lane(p->device));
-    }
+    GRT_TRY(check_lane(p));
     GRT_TRY(grt_staging_reserve(p, &p->small, p->small_doubles, p->small_doubles));
 
     /* small per-column inputs: air column amounts for Rayleigh (rayleigh.c:104-128 via
@@ -386,6 +399,37 @@ static int band_gas_optics(GrtPipeline_t *p, GrtBand *b, int bi, GrtColumns_t co
     return GRTCODE_SUCCESS;
 }
 
+/* ---- the surface ------------------------------------------------------------------------------------------------------ */
+
+/* grt_ext.h.  Everything is checked before anything is touched, so a refused call leaves the surface in force as it was;
+   then the rows are written on the lane, behind the runs already queued there, which read the rows of the surface before. */
+EXTERN int grt_pipeline_set_surface(GrtPipeline_t *p, GrtSurface_t const *surface)
+{
+    GRT_REQUIRE_PTR(p);
+    if (surface == NULL)
+    {
+        p->surface_ncol = 0;
+        for (int bi = 0; bi < 2; ++bi)
+        {
+            p->band[bi].surf_set = p->band[bi].surf_dif_set = 0;
+        }
+        return GRTCODE_SUCCESS;
+    }
+    int np[2];
+    GRT_TRY(grt_check_surface(p, surface, np));
+    GRT_TRY(check_lane(p));
+    /* (a failure from here on is the device's: no surface is in force then, rather than rows half written) */
+    p->surface_ncol = 0;
+    GRT_TRY(grt_stage_surface(p, surface, np));
+    p->surface_ncol = surface->ncol;
+    for (int bi = 0; bi < 2; ++bi)
+    {
+        p->band[bi].surf_set = np[bi] > 0;
+        p->band[bi].surf_dif_set = bi == 1 && np[1] > 0 && surface->diffuse_albedo != NULL;
+    }
+    return GRTCODE_SUCCESS;
+}
+
 /* ---- the run ------------------------------------------------------------------------------------------------------ */
 
 /* What the run entry points share after their argument checks: the batch (and its clouds or aerosols) staged, then per
@@ -396,6 +440,11 @@ static int band_gas_optics(GrtPipeline_t *p, GrtBand *b, int bi, GrtColumns_t co
 static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl, GrtAerosols_t const *ae,
                         int subcolumns, GrtPass const *rows)
 {
+    if (p->surface_ncol > 0 && cols->ncol != p->surface_ncol)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d columns asked for, the surface in force (grt_pipeline_set_surface) has %d.",
+                 cols->ncol, p->surface_ncol);
+    }
     GRT_TRY(stage_columns(p, cols));
     int const C = cols->ncol, S = subcolumns > 0 ? subcolumns : 1;
     if (cl != NULL)

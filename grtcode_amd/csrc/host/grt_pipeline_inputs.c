@@ -1,4 +1,4 @@
-/* grt_pipeline_inputs.c -- what turns a caller's clouds, aerosols and bin edges into device arguments of the batched
+/* grt_pipeline_inputs.c -- what turns a caller's clouds, aerosols, surface and bin edges into device arguments of the batched
  * pipeline: the per-batch tables staged through pinned memory, and the per-point maps that depend only on band limits,
  * an aerosol grid or bin edges and are rebuilt when those change. */
 #include <stdlib.h>
@@ -307,6 +307,170 @@ int grt_band_aerosols(GrtPipeline_t *p, GrtBand *b, int bi, GrtAerosols_t const 
     AerosolMapFill f = {&b->gas->grid, bi == 0 ? ae->lw_grid : ae->sw_grid, na};
     GRT_TRY(grt_keyed_table(p, &b->aer_map, f.x, sizeof(double)*(size_t)na, b->n, fill_aerosol_map, &f));
     aa->interval = b->aer_map.table;
+    return GRTCODE_SUCCESS;
+}
+
+/* The entry of the surface grid x [ns] (strictly increasing) each of the n points w0 + i dw takes, as interpolate2 with
+   constant_extrapolation (utilities.c:149-222, :77-92) assigns them: 0 for w <= x[0], 1 + j for x[j] < w <= x[j+1], ns for
+   w > x[ns-1]. */
+void grt_surface_entry_map(double w0, double dw, uint64_t n, double const *x, int ns, int *entry)
+{
+    for (uint64_t i = 0; i < n; ++i)
+    {
+        double const w = w0 + i*dw;
+        entry[i] = w <= x[0] ? 0 : (w > x[ns - 1] ? ns : count_below(x, ns, w, 0));
+    }
+}
+
+/* values [ncol][ns] -> tables [ncol][ns + 1][2], slope then intercept: entry 0 the constant y[0] below the grid, entry
+   1 + j linear_sample's (utilities.c:235-246) pair of interval j, entry ns the constant above the grid -- y[ns-2], what
+   the reference's extrapolation takes from the last SEGMENT it is handed (utilities.c:215-219).  A constant entry has
+   slope 0: 0 w + b is b. */
+void grt_surface_tables(double const *x, int ns, int ncol, double const *values, double *tables)
+{
+    size_t const NS = (size_t)ns, NE = NS + 1;
+    for (size_t c = 0; c < (size_t)ncol; ++c)
+    {
+        double const *y = values + c*NS;
+        double *t = tables + c*NE*2;
+        t[0] = 0.;
+        t[1] = y[0];
+        for (size_t j = 0; j + 1 < NS; ++j)
+        {
+            double const m = (y[j + 1] - y[j])/(x[j + 1] - x[j]);
+            double const b = y[j] - m*x[j];
+            t[(1 + j)*2 + 0] = m;
+            t[(1 + j)*2 + 1] = b;
+        }
+        t[NS*2 + 0] = 0.;
+        t[NS*2 + 1] = y[NS - 2];
+    }
+}
+
+/* one band's surface inputs: none, or at least two strictly increasing grid points and knot values in [0, 1] */
+static int check_surface_band(char const *name, int ns, int ncol, fp_t const *grid, fp_t const *values, fp_t const *second)
+{
+    if (ns < 0 || ns == 1)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s grid points: 0 (the creation-time array) or at least 2.", ns, name);
+    }
+    if (ns == 0)
+    {
+        return GRTCODE_SUCCESS;
+    }
+    if (grid == NULL || values == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s grid points with a NULL grid or NULL values.", ns, name);
+    }
+    for (int j = 0; j + 1 < ns; ++j)
+    {
+        if (!(grid[j + 1] > grid[j]))
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "%s grid not strictly increasing (grid[%d] = %e, grid[%d] = %e).", name, j, grid[j],
+                     j + 1, grid[j + 1]);
+        }
+    }
+    fp_t const *arrays[2] = {values, second};
+    for (int k = 0; k < 2; ++k)
+    {
+        for (size_t i = 0; arrays[k] != NULL && i < (size_t)ncol*(size_t)ns; ++i)
+        {
+            if (!(arrays[k][i] >= 0. && arrays[k][i] <= 1.))
+            {
+                GRT_FAIL(GRTCODE_VALUE_ERR, "%s value %e of column %zu, point %zu outside [0, 1].", name, arrays[k][i],
+                         i/(size_t)ns, i%(size_t)ns);
+            }
+        }
+    }
+    return GRTCODE_SUCCESS;
+}
+
+/* what grt_pipeline_set_surface refuses; np: the points each band takes (0: a band the pipeline does not have, or one that
+   keeps its creation-time array) */
+int grt_check_surface(GrtPipeline_t const *p, GrtSurface_t const *sf, int np[2])
+{
+    if (sf->ncol < 1 || sf->ncol > p->max_cols)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "a surface of %d columns, this pipeline was created for 1 to %d.", sf->ncol, p->max_cols);
+    }
+    np[0] = p->band[0].gas != NULL ? sf->emissivity_num_points : 0;
+    np[1] = p->band[1].gas != NULL ? sf->albedo_num_points : 0;
+    GRT_TRY(check_surface_band("surface emissivity", np[0], sf->ncol, sf->emissivity_grid, sf->emissivity, NULL));
+    GRT_TRY(check_surface_band("surface albedo", np[1], sf->ncol, sf->albedo_grid, sf->direct_albedo, sf->diffuse_albedo));
+    return GRTCODE_SUCCESS;
+}
+
+typedef struct SurfaceMapFill { SpectralGrid_t const *grid; double const *x; int ns; } SurfaceMapFill;
+
+static int fill_surface_map(void *ctx, int *entry)
+{
+    SurfaceMapFill const *f = ctx;
+    grt_surface_entry_map(f->grid->w0, f->grid->dw, f->grid->n, f->x, f->ns, entry);
+    return GRTCODE_SUCCESS;
+}
+
+/* [max_cols][n] doubles at *rows, allocated when first needed */
+static int surface_rows(GrtPipeline_t *p, GrtBand const *b, double **rows)
+{
+    if (*rows == NULL)
+    {
+        void *blk = NULL;
+        GRT_TRY(grt_dev_alloc(p->device, &blk, sizeof(double)*(size_t)p->max_cols*b->n));
+        *rows = blk;
+    }
+    return GRTCODE_SUCCESS;
+}
+
+/* A checked surface (grt_check_surface's np) to the device: the columns' slope and intercept entries staged and uploaded,
+   each band's per-point entries built on the host when its surface grid differs from the last call's, and one launch per
+   band and array that writes the columns' rows (profile tag 15).  The bands' surf_set / surf_dif_set say what is in
+   force afterwards; the caller sets them when this has succeeded. */
+int grt_stage_surface(GrtPipeline_t *p, GrtSurface_t const *sf, int const np[2])
+{
+    size_t const C = (size_t)sf->ncol, M = (size_t)p->max_cols;
+    fp_t const *values[3] = {np[0] > 0 ? sf->emissivity : NULL, np[1] > 0 ? sf->direct_albedo : NULL,
+                             np[1] > 0 ? sf->diffuse_albedo : NULL};
+    size_t off[3], need = 0, want = 0;
+    for (int k = 0; k < 3; ++k)
+    {
+        size_t const per = values[k] != NULL ? 2*((size_t)np[k > 0] + 1) : 0;
+        off[k] = need;
+        need += C*per;
+        want += M*per;
+    }
+    if (need == 0)
+    {
+        return GRTCODE_SUCCESS;
+    }
+    GRT_TRY(grt_staging_reserve(p, &p->surf, need, want));
+    for (int k = 0; k < 3; ++k)
+    {
+        if (values[k] != NULL)
+        {
+            grt_surface_tables(k == 0 ? sf->emissivity_grid : sf->albedo_grid, np[k > 0], sf->ncol, values[k],
+                               p->surf.h + off[k]);
+        }
+    }
+    GRT_TRY(grt_staging_upload(p, &p->surf, need));
+    void *s = grt_dev_stream(p->device);
+    for (int k = 0; k < 3; ++k)
+    {
+        if (values[k] == NULL)
+        {
+            continue;
+        }
+        GrtBand *b = &p->band[k > 0];
+        SpectralGrid_t const *grid = &b->gas->grid;
+        SurfaceMapFill f = {grid, k == 0 ? sf->emissivity_grid : sf->albedo_grid, np[k > 0]};
+        GRT_TRY(grt_keyed_table(p, &b->surf_map, f.x, sizeof(double)*(size_t)f.ns, b->n, fill_surface_map, &f));
+        double **rows = k == 2 ? &b->surf_rows_dif : &b->surf_rows;
+        GRT_TRY(surface_rows(p, b, rows));
+        GrtSurfaceArgs const sa = {f.ns + 1, b->surf_map.table, p->surf.d + off[k]};
+        int const slot = grt_profile_begin(s, 15);
+        int const krc = grt_launch_spread_surface(s, sf->ncol, grid->w0, grid->dw, b->n, &sa, *rows);
+        grt_profile_end(s, slot);
+        GRT_TRY(grt_dev_check(krc, "surface row kernel"));
+    }
     return GRTCODE_SUCCESS;
 }
 

@@ -64,6 +64,13 @@ typedef struct GrtBand
     double *sub_partials;  /* fused form: [max_cols][S][6 or 2 V][nblocks] partial sums of the all-sky pass */
     size_t sub_cap;        /* its doubles */
     double *flux_sum;      /* materialised form: [2][max_cols][V][n] sums of the subcolumns' up and down fluxes */
+    /* grt_pipeline_set_surface: [n] entry of the band's surface grid each grid point takes (grt_surface_entry_map); its key:
+       that grid */
+    GrtKeyedTable surf_map;
+    /* ... and the columns' rows [max_cols][n], allocated at the first call that sets them: the emissivity (longwave) or
+       the direct albedo (shortwave), and -- shortwave, when a diffuse albedo was given -- the diffuse albedo */
+    double *surf_rows, *surf_rows_dif;
+    int surf_set, surf_dif_set;    /* the surface in force gives this band rows (, and diffuse rows of their own) */
 } GrtBand;
 
 struct GrtPipeline
@@ -81,6 +88,10 @@ struct GrtPipeline
     GrtStaging cloud;
     /* grt_pipeline_run_aerosols' slope and intercept tables: the longwave's [cols][3][NA - 1][2][L], then the shortwave's */
     GrtStaging aer;
+    /* grt_pipeline_set_surface's slope and intercept entries: the emissivity's [cols][NS + 1][2], then the direct albedo's,
+       then the diffuse albedo's */
+    GrtStaging surf;
+    int surface_ncol;      /* columns of the surface in force; 0: none (the creation-time arrays apply) */
 };
 
 /* grt_pipeline_run_spectral's outputs: the spectral rows and bins of `sets` sets per column */
@@ -144,6 +155,8 @@ GRT_PRIVATE int grt_stage_clouds(GrtPipeline_t *p, GrtClouds_t const *cl, int C,
 GRT_PRIVATE int grt_band_clouds(GrtPipeline_t *p, GrtBand *b, int bi, GrtClouds_t const *cl, int C, int S, GrtCloudArgs *ca);
 GRT_PRIVATE int grt_stage_aerosols(GrtPipeline_t *p, GrtAerosols_t const *ae, int C);
 GRT_PRIVATE int grt_band_aerosols(GrtPipeline_t *p, GrtBand *b, int bi, GrtAerosols_t const *ae, int C, GrtAerosolArgs *aa);
+GRT_PRIVATE int grt_check_surface(GrtPipeline_t const *p, GrtSurface_t const *sf, int np[2]);
+GRT_PRIVATE int grt_stage_surface(GrtPipeline_t *p, GrtSurface_t const *sf, int const np[2]);
 GRT_PRIVATE int grt_band_bins(GrtPipeline_t *p, GrtBand *b, int const *edges, int nbins, int rows);
 
 /* grt_pipeline_solve.c */

@@ -67,6 +67,10 @@ static void lw_args(GrtPipeline_t const *p, GrtBand const *b, int C, int fused, 
     a->t_layers = p->small.d + p->off_tl; a->t_levels = p->small.d + p->off_tv;
     a->t_surf = p->small.d + p->off_ts;
     a->emis = p->emis_d; a->emis_stride = 0;
+    if (b->surf_set)
+    {
+        a->emis = b->surf_rows; a->emis_stride = b->n;          /* grt_pipeline_set_surface: driver.c:101-107 */
+    }
     a->user_level = p->user_level;
     if (fused)
     {
@@ -90,6 +94,11 @@ static void sw_args(GrtPipeline_t const *p, GrtBand const *b, int C, int fused, 
     a->optics_stride = (uint64_t)L*b->n;
     a->mu_dir = p->small.d + p->off_mu; a->mu_dif = 0.5;        /* driver.c:110 */
     a->alb_dir = p->albedo_d; a->alb_dif = p->albedo_d; a->alb_stride = 0;   /* driver.c:118-119 */
+    if (b->surf_set)
+    {
+        /* grt_pipeline_set_surface: driver.c:111-117 */
+        a->alb_dir = b->surf_rows; a->alb_dif = b->surf_dif_set ? b->surf_rows_dif : b->surf_rows; a->alb_stride = b->n;
+    }
     a->tsi = p->small.d + p->off_tsi; a->solar = p->solar_d;
     a->user_level = p->user_level;
     if (fused)

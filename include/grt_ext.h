@@ -385,6 +385,44 @@ EXTERN int grt_pipeline_run_band_profiles(GrtPipeline_t *pipeline, GrtColumns_t 
                                           fp_t *band_heating_dev);
 EXTERN int grt_pipeline_band_profile_bin_limit(GrtPipeline_t const *pipeline);
 
+/* ---- per-column surface emissivity and albedo ----------------------------------------------------------------------
+ * driver.c:101-117: each column's own surface emissivity and albedo, given on coarse wavenumber grids of NS points shared
+ * by the columns and put on the band's grid as interpolate_to_grid(grid, x, y, NS, out, linear_sample,
+ * constant_extrapolation) does (utilities.c:149-246, :77-92).  A grid point w = w0 + i dw takes
+ *   y[0]                                    for w <= x[0],
+ *   m_j w + b_j                             for x[j] < w <= x[j+1],  m_j = (y[j+1] - y[j])/(x[j+1] - x[j]),
+ *                                           b_j = y[j] - m_j x[j]  (multiply, then add: no contraction),
+ *   y[NS-2]                                 for w > x[NS-1]  (the reference hands its extrapolation the LAST SEGMENT, so
+ *                                           the value above the grid is the one before the last; kept).
+ * Once set, the surface holds for every later grt_pipeline_run* call on this pipeline -- every entry point, both passes
+ * or sets of each, keep_spectra = 0 and 1 -- until it is replaced or cleared with surface == NULL; after a clear the
+ * arrays given to grt_pipeline_create apply again, bit for bit.  A run with a surface set needs columns->ncol ==
+ * surface->ncol: GRTCODE_VALUE_ERR otherwise, with nothing launched and the outputs untouched.  A band with a point
+ * count of 0 keeps its creation-time array; a band whose gas-optics object is NULL ignores its fields.
+ * The arrays are HOST memory, read during the call.  The host does the divisions once -- each column's [NS] becomes NS + 1
+ * slope and intercept pairs, the two constant ranges as (0, y[0]) and (0, y[NS-2]) --, and a kernel (profile tag 15) writes
+ * each column's row on the device, one thread per column and grid point: a few kB cross PCIe instead of
+ * [ncol][n_lw] + 2 [ncol][n_sw] doubles.  Asynchronous on the pipeline's lane like a run.  Allocated at the first call
+ * that needs them: [max_columns][n] doubles per band (twice that for the shortwave when diffuse_albedo is given: without
+ * it both beams read the direct rows), the small staging buffer, and one int per grid point and band (rebuilt when that
+ * band's surface grid changes; the call then waits for the lane).
+ * GRTCODE_VALUE_ERR, with nothing launched and the previous surface (or none) still in force, for: ncol outside
+ * 1 .. max_columns; a point count that is 1 or negative; a NULL grid or value array where the count is >= 2; a grid that
+ * is not strictly increasing; a knot value outside [0, 1] (the range grt_pipeline_create enforces).
+ * In the deterministic mode, column c of a batch with a surface equals, bit for bit, a pipeline created with column c's
+ * interpolated rows as its shared arrays; so does a surface of constant knots equal to the creation-time constants and a
+ * run without a surface. */
+typedef struct GrtSurface
+{
+    int ncol;
+    int emissivity_num_points, albedo_num_points;   /* NS >= 2 each; 0: that band keeps the creation-time array */
+    fp_t const *emissivity_grid, *albedo_grid;      /* [NS] cm-1, strictly increasing, shared by the columns */
+    fp_t const *emissivity;                         /* [ncol][NS] */
+    fp_t const *direct_albedo;                      /* [ncol][NS] */
+    fp_t const *diffuse_albedo;                     /* [ncol][NS], or NULL: the direct one (driver.c:116-117) */
+} GrtSurface_t;
+EXTERN int grt_pipeline_set_surface(GrtPipeline_t *pipeline, GrtSurface_t const *surface);
+
 /* ---- columns across the GPUs of one node ------------------------------------
  * One process per GPU; contiguous ceil-sized column blocks; one gather of the [columns][GRT_FLUXES_PER_COLUMN]
  * flux blocks to rank 0.  The reference fans out processes with -x/-X column ranges and merges per-shard files
@@ -428,7 +466,7 @@ EXTERN int grt_multi_max(GrtMulti_t *multi, double *value);    /* barrier + maxi
  * 11 = the subcolumn-mean kernel of grt_pipeline_run_subcolumns (with S > 1; its all-sky solvers count under 8 / 9, each
  * band's launches together), 12 / 13 = LW / SW solver of the aerosol pass of grt_pipeline_run_aerosols (its clear-clean
  * pass counts under 3 / 4), 14 = the per-bin reduction and the heating-rate kernel of grt_pipeline_run_band_profiles (its
- * solvers count under 3 / 4 and 8 / 9).
+ * solvers count under 3 / 4 and 8 / 9), 15 = the surface-row kernel of grt_pipeline_set_surface (all its launches).
  * Read after grt_pipeline_sync(). */
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
