@@ -24,6 +24,8 @@ GRT_ALLSKY_FLUXES_PER_COLUMN = 24   # grt_pipeline_run's twelve (clear sky), the
 GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN = 2 * GRT_PROFILE_ROWS_PER_COLUMN   # the clear-sky four rows, then the all-sky four
 GRT_ALLSKY_HEATING_ROWS_PER_COLUMN = 2 * GRT_HEATING_ROWS_PER_COLUMN   # the clear-sky two rows, then the all-sky two
 GRT_CLOUDS = 6                      # grt_sizeof kind of GrtClouds
+GRT_CLOUD_PHASE, GRT_CLOUD_MODEL, GRT_CLOUD_FIELDS = 7, 8, 9   # ... of GrtCloudPhase, GrtCloudModel, GrtCloudFields
+CLOUD_SAMPLER_TAG = 16              # grt_profile_read tag of the cloud-sampling kernel
 GRT_MAX_SUBCOLUMNS = 64             # grt_pipeline_run_subcolumns: subcolumns per column, 1 .. this
 RETURN_CODES = ["GRTCODE_SUCCESS", "GRTCODE_INVALID_ERR", "GRTCODE_DIVBYZERO_ERR", "GRTCODE_OVERFLOW_ERR",
                 "GRTCODE_UNDERFLOW_ERR", "GRTCODE_SENTINEL_ERR", "GRTCODE_NULL_ERR", "GRTCODE_NON_NULL_ERR",
@@ -136,6 +138,25 @@ class GrtClouds(C.Structure):
                 ("lw_liquid", c_double_p), ("lw_ice", c_double_p), ("sw_liquid", c_double_p), ("sw_ice", c_double_p)]
 
 
+class GrtCloudPhase(C.Structure):
+    _fields_ = [("nband", C.c_int), ("nsize", C.c_int), ("np", C.c_int), ("nq", C.c_int),
+                ("band_lo", c_double_p), ("band_hi", c_double_p), ("size_lo", c_double_p), ("size_hi", c_double_p),
+                ("size_ref", c_double_p), ("coef", c_double_p * 6)]
+
+
+class GrtCloudModel(C.Structure):
+    _fields_ = [("num_shape", C.c_int), ("num_x", C.c_int), ("x", c_double_p), ("value", c_double_p),
+                ("inverse", c_double_p), ("liquid", GrtCloudPhase), ("ice", GrtCloudPhase)]
+
+
+class GrtCloudFields(C.Structure):
+    _fields_ = [("ncol", C.c_int), ("num_layers", C.c_int), ("num_subcolumns", C.c_int),
+                ("cloud_fraction", c_double_p), ("liquid_content", c_double_p), ("ice_content", c_double_p),
+                ("temperature", c_double_p), ("thickness", c_double_p), ("overlap", c_double_p),
+                ("liquid_radius", C.c_double), ("seed", C.c_uint64), ("column_offset", C.c_int64),
+                ("uniforms", c_double_p)]
+
+
 class GrtAerosols(C.Structure):
     _fields_ = [("lw_num_points", C.c_int), ("sw_num_points", C.c_int), ("lw_grid", c_double_p), ("sw_grid", c_double_p),
                 ("lw_optics", c_double_p), ("sw_optics", c_double_p)]
@@ -162,7 +183,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_aerosols grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_pipeline_set_surface grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_pipeline_set_surface grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -211,6 +232,11 @@ def load_library(path=None):
     lib.grt_pipeline_band_profile_bin_limit.argtypes = [C.c_void_p]
     lib.grt_pipeline_run_subcolumns.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtClouds), C.c_int,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.grt_cloud_sampler_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(GrtCloudModel)]
+    lib.grt_cloud_sampler_destroy.argtypes = [C.POINTER(C.c_void_p)]
+    lib.grt_cloud_sampler_run.argtypes = [C.c_void_p, C.POINTER(GrtCloudFields), C.c_void_p]
+    lib.grt_pipeline_run_cloud_fields.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.c_void_p, C.POINTER(GrtCloudFields),
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]
     lib.grt_pipeline_run_aerosols.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtAerosols), C.c_void_p,
                                               C.c_void_p, C.c_void_p]
     lib.grt_pipeline_set_surface.argtypes = [C.c_void_p, C.POINTER(GrtSurface)]
@@ -507,6 +533,107 @@ def make_clouds(liquid_bands, ice_bands, thickness, lw_liquid, lw_ice, sw_liquid
     return gc, keep
 
 
+PADE_NAMES = ("Pade_ext_p", "Pade_ext_q", "Pade_ssa_p", "Pade_ssa_q", "Pade_asy_p", "Pade_asy_q")
+
+
+def make_cloud_model(tables):
+    """Pack the clouds library's three parameter tables into a GrtCloudModel struct (+ keep-alive arrays) for CloudSampler.
+    tables: {"beta": ..., "liquid": ..., "ice": ...}, each a dict under the parameter files' variable names (what
+    dumpfile.read_dump gives for a file) -- beta: p, x, data, inverse (q, p, x); a phase: Band_limits_lwr/_upr (Band),
+    Effective_Radius_limits_lwr/_upr, Effective_Radius_Ref (Re_range), Pade_{ext,ssa,asy}_{p,q} (coefficient, Re_range,
+    Band).  As the library's loader does, the phases' numbers are rounded to single precision and the coefficients are
+    transposed to [band][size regime][coefficient]; keep["liquid"] / keep["ice"] hold those arrays by field name."""
+    f32 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64).astype(np.float32).astype(np.float64))
+    beta = tables["beta"]
+    keep = {"x": _f64(beta["x"]), "value": _f64(beta["data"]), "inverse": _f64(beta["inverse"])}
+    num_shape, nx = np.asarray(beta["p"]).size, keep["x"].size
+    for k in ("value", "inverse"):
+        if keep[k].shape != (num_shape, num_shape, nx):
+            raise ValueError(f"beta table {k} of shape {keep[k].shape}: [{num_shape}][{num_shape}][{nx}]")
+    phases = []
+    for name in ("liquid", "ice"):
+        t = tables[name]
+        ph = {"band_lo": f32(t["Band_limits_lwr"]), "band_hi": f32(t["Band_limits_upr"]),
+              "size_lo": f32(t["Effective_Radius_limits_lwr"]), "size_hi": f32(t["Effective_Radius_limits_upr"]),
+              "size_ref": f32(t["Effective_Radius_Ref"])}
+        nband, nsize = ph["band_lo"].size, ph["size_lo"].size
+        ph["coef"] = []
+        for k, var in enumerate(PADE_NAMES):
+            c = np.asarray(t[var], dtype=np.float64)
+            if c.ndim != 3 or c.shape[1:] != (nsize, nband):
+                raise ValueError(f"{name} {var} of shape {c.shape}: (coefficient, {nsize}, {nband})")
+            ph["coef"].append(f32(c.transpose(2, 1, 0)))
+        np_, nq_ = ph["coef"][0].shape[2], ph["coef"][1].shape[2]
+        if any(c.shape[2] != (np_ if k % 2 == 0 else nq_) for k, c in enumerate(ph["coef"])):
+            raise ValueError(f"{name}: Pade tables of different orders")
+        keep[name] = ph
+        phases.append(GrtCloudPhase(nband, nsize, np_, nq_, *[_dp(ph[k]) for k in (
+            "band_lo", "band_hi", "size_lo", "size_hi", "size_ref")], (c_double_p * 6)(*[_dp(c) for c in ph["coef"]])))
+    gm = GrtCloudModel(num_shape, nx, _dp(keep["x"]), _dp(keep["value"]), _dp(keep["inverse"]), *phases)
+    gm.keep = keep             # (the struct's pointers do not hold the arrays: the struct alone keeps them alive)
+    return gm, keep
+
+
+def make_cloud_fields(cloud_fraction, liquid_content, ice_content, overlap, temperature=None, thickness=None,
+                      num_subcolumns=1, liquid_radius=10.0, seed=0, column_offset=0, uniforms=None):
+    """Pack a batch's cloud fields into a GrtCloudFields struct (+ keep-alive arrays) for CloudSampler.run and
+    Pipeline.run_cloud_fields.  cloud_fraction, liquid_content, ice_content (g m-3), temperature (K), thickness (m):
+    [ncol][L]; overlap [ncol][L-1]; temperature None: the pipeline takes the columns' layer temperatures; thickness is
+    read by the pipeline only.  uniforms None: the device draws with Philox4x32-10 from (seed, column_offset + column);
+    else [ncol][2][S][B][2 L - 1] draws in the driver's order (longwave pass then shortwave, subcolumn, band; L ranks
+    then L - 1 decisions).  keep["shape"] is (ncol, L, S)."""
+    keep = {"cf": _f64(cloud_fraction), "lwc": _f64(liquid_content), "iwc": _f64(ice_content), "ov": _f64(overlap)}
+    ncol, L = keep["cf"].shape
+    for k, v in (("t", temperature), ("th", thickness), ("u", uniforms)):
+        keep[k] = None if v is None else _f64(v)
+    for k in ("lwc", "iwc", "t", "th"):
+        if keep[k] is not None and keep[k].shape != (ncol, L):
+            raise ValueError(f"cloud field {k} of shape {keep[k].shape}: [{ncol}][{L}]")
+    if keep["ov"].size != ncol * (L - 1):
+        raise ValueError(f"overlap of shape {keep['ov'].shape}: [{ncol}][{L - 1}]")
+    S = int(num_subcolumns)
+    if keep["u"] is not None and (keep["u"].ndim != 5 or keep["u"].shape[:3] != (ncol, 2, S)
+                                  or keep["u"].shape[4] != 2 * L - 1):
+        raise ValueError(f"uniforms of shape {keep['u'].shape}: [{ncol}][2][{S}][B][{2 * L - 1}]")
+    keep["shape"] = (ncol, L, S)
+    gf = GrtCloudFields(ncol, L, S, _dp(keep["cf"]), _dp(keep["lwc"]), _dp(keep["iwc"]), _opt_dp(keep["t"]),
+                        _opt_dp(keep["th"]), _dp(keep["ov"]) if L > 1 else None, float(liquid_radius),
+                        int(seed) & (2 ** 64 - 1), int(column_offset), _opt_dp(keep["u"]))
+    gf.keep = keep             # (as make_cloud_model)
+    return gf, keep
+
+
+class CloudSampler:
+    """grt_cloud_sampler_*: the cloud model's tables on the device (make_cloud_model), and the kernel that makes the band
+    optics of a batch's cloud subcolumns from its cloud fields (make_cloud_fields)."""
+
+    def __init__(self, device, gmodel):
+        self.lib = load_library()
+        self.device = device
+        self.num_bands = gmodel.liquid.nband
+        self.p = C.c_void_p()
+        check(self.lib.grt_cloud_sampler_create(C.byref(self.p), device, C.byref(gmodel)))
+        self.out = None
+
+    def run(self, gfields):
+        """grt_cloud_sampler_run -> [4][S][ncol][3][B][L]: lw_liquid, lw_ice, sw_liquid, sw_ice, subcolumn-major, each
+        extinction m-1, single-scattering albedo, asymmetry per liquid band and layer."""
+        shape = (4, gfields.num_subcolumns, gfields.ncol, 3, self.num_bands, gfields.num_layers)
+        nbytes = 8 * int(np.prod(shape))
+        if self.out is None or self.out.nbytes != nbytes:
+            if self.out is not None:
+                self.out.free()
+            self.out = DeviceBuffer(self.device, nbytes)
+        check(self.lib.grt_cloud_sampler_run(self.p, C.byref(gfields), self.out.ptr))
+        return self.out.to_host(shape)
+
+    def destroy(self):
+        if self.out is not None:
+            self.out.free()
+            self.out = None
+        check(self.lib.grt_cloud_sampler_destroy(C.byref(self.p)))
+
+
 def make_aerosols(lw=None, sw=None):
     """Pack aerosol inputs into a GrtAerosols struct (+ keep-alive arrays) for Pipeline.run_aerosols.
     lw / sw: (grid, optics) of that band -- grid [NA] cm-1, strictly increasing, NA >= 2; optics [ncol][3][L][NA] (layer
@@ -752,6 +879,13 @@ class Pipeline:
     def subcolumn_profiles(self, ncol):
         """The last run_subcolumns(profiles=True): (clear, all-sky subcolumn mean), allsky_profiles()' keys and shapes."""
         return self._read_profiles("subcolumn_profiles", 2, ncol)
+
+    def run_cloud_fields(self, gcols, sampler, gfields, profiles=False):
+        """grt_pipeline_run_cloud_fields: run_subcolumns with gfields.num_subcolumns subcolumns whose tables `sampler` (a
+        CloudSampler) makes on the device from the cloud fields (make_cloud_fields); into run_subcolumns' buffers
+        (subcolumn_fluxes() / subcolumn_profiles() read them)."""
+        check(self.lib.grt_pipeline_run_cloud_fields(self.p, C.byref(gcols), sampler.p, C.byref(gfields),
+                                                     *self._six_row_or_profile_ptrs("subcolumn", profiles)))
 
     def run_aerosols(self, gcols, gaerosols, profiles=False):
         """grt_pipeline_run_aerosols into this object's device buffers: the six-row form (aerosol_fluxes() reads it) or,

@@ -518,6 +518,35 @@ int grt_launch_spread_clouds(void *stream, int num_layers, int ncol, uint64_t nw
                              double *liquid_tau, double *liquid_omega, double *liquid_g,
                              double *ice_tau, double *ice_omega, double *ice_g);
 
+/* The cloud sampler (k_cloud_sample.hip; grt_ext.h: grt_cloud_sampler_run): the band optics of `subcolumns` draws per
+   column and pass from the columns' cloud fields.  One wavefront per sample (column, pass, subcolumn, band), lanes over
+   layers in chunks of 64.  Everything is DEVICE memory.  Of the beta tables the kernel reads three rows only, the (5, 5)
+   water PDF's: inverse[q = 5][p = 5] twice and value[q = 5][p = 6]; x must ascend (the segment is found by bisection).
+   A phase's coef [band][size][coefficient] as PadeOptics holds them.  uniforms [ncol][2][S][B][2 L - 1] or NULL: then
+   Philox4x32-10 with key (key0, key1) and counter (layer, band, pass GRT_SAMPLER_MAX_SUBCOLUMNS + s, column0 + c).
+   tables [4][S][ncol][3][B][L]: lw_liquid, lw_ice, sw_liquid, sw_ice. */
+#define GRT_SAMPLER_MAX_SUBCOLUMNS 64   /* grt_ext.h: GRT_MAX_SUBCOLUMNS */
+typedef struct GrtCloudPhaseDev
+{
+    int nsize, np, nq;
+    double const *size_lo, *size_hi, *size_ref;
+    double const *coef[6];
+} GrtCloudPhaseDev;
+typedef struct GrtCloudSampleArgs
+{
+    int ncol, num_layers, subcolumns, num_bands;
+    int num_x;
+    double const *x, *inverse_pq, *value_p1q;       /* [num_x] each */
+    GrtCloudPhaseDev liquid, ice;
+    double const *cloud_fraction, *liquid_content, *ice_content, *temperature;   /* [ncol][L] */
+    double const *overlap;                           /* [ncol][L-1] */
+    double liquid_radius;
+    double const *uniforms;
+    uint32_t key0, key1, column0;
+    double *tables;
+} GrtCloudSampleArgs;
+int grt_launch_cloud_sample(void *stream, GrtCloudSampleArgs const *a);
+
 /* Fused Rayleigh + combine for the clear-sky driver sequence (rayleigh.c:39 +
    optics.c:138-145 with K=2, gas omega=g=0, Rayleigh omega=1,g=0):
    tau_tot = tau_gas + tau_R, omega = tau_R/tau_tot, g = 0/ tau_R.  n_layer [ncol][L]. */

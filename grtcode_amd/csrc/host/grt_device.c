@@ -482,6 +482,9 @@ EXTERN size_t grt_sizeof(int kind)
         case GRT_LONGWAVE: return sizeof(Longwave_t);
         case GRT_SHORTWAVE: return sizeof(Shortwave_t);
         case GRT_CLOUDS: return sizeof(GrtClouds_t);
+        case GRT_CLOUD_PHASE: return sizeof(GrtCloudPhase_t);
+        case GRT_CLOUD_MODEL: return sizeof(GrtCloudModel_t);
+        case GRT_CLOUD_FIELDS: return sizeof(GrtCloudFields_t);
         default: return 0;
     }
 }

@@ -188,4 +188,14 @@ void grt_surface_entry_map(double w0, double dw, uint64_t n, double const *x, in
 void grt_surface_tables(double const *x, int ns, int ncol, double const *values, double *tables);
 void grt_cloud_band_map(double const *lo, double const *hi, int own, int nb, double const *w, int n, int *idx);
 
+/* grt_cloud_sampler.c, for the pipeline's grt_pipeline_run_cloud_fields: the argument checks the two entry points share
+   (need_temperature: fields->temperature must be given), the fields staged and the kernel enqueued into tables_dev
+   [4][S][ncol][3][B][L] on the current lane with `temperature` [ncol][L] in fields->temperature's place, the sampler's
+   device, and its model's band limits put into a GrtClouds_t (nothing else of it is touched) */
+GRT_PRIVATE int grt_cloud_sampler_check(GrtCloudSampler_t const *sp, GrtCloudFields_t const *f, int need_temperature);
+GRT_PRIVATE int grt_cloud_sampler_enqueue(GrtCloudSampler_t *sp, GrtCloudFields_t const *f, fp_t const *temperature,
+                                          double *tables_dev);
+GRT_PRIVATE Device_t grt_cloud_sampler_device(GrtCloudSampler_t const *sp);
+GRT_PRIVATE void grt_cloud_sampler_bands(GrtCloudSampler_t const *sp, GrtClouds_t *cl);
+
 #endif

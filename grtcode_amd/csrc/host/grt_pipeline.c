@@ -24,6 +24,8 @@
  * tau_gas, and one finishing launch for the two sets.
  * grt_pipeline_run_subcolumns runs either of the two with the all-sky pass averaged over several cloud subcolumns, all of
  * them on the one tau_gas.
+ * grt_pipeline_run_cloud_fields is grt_pipeline_run_subcolumns with the subcolumns' band tables written into the cloud
+ * buffer by the device cloud sampler (grt_cloud_sampler.c, k_cloud_sample.hip) from the columns' cloud fields.
  * grt_pipeline_run_aerosols runs the clear-clean pass of grt_pipeline_run or grt_pipeline_run_profiles and then, on the
  * same tau_gas, the clear-sky pass with aerosols of driver.c:426-472: the aerosol object formed inside the solvers from
  * per-column slope and intercept tables (or, materialised form, spread onto the grid and added by the add_optics kernel).
@@ -437,8 +439,10 @@ EXTERN int grt_pipeline_set_surface(GrtPipeline_t *p, GrtSurface_t const *surfac
    outputs) completed into one pass: the clear-sky solve, then -- with aerosols or clouds -- the aerosol or all-sky one,
    whose rows follow the clear-sky set's (grt_set_offset).  subcolumns > 0 (grt_pipeline_run_subcolumns): the all-sky pass
    is the mean over that many subcolumns (grt_band_solve_subcolumns). */
-static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl, GrtAerosols_t const *ae,
-                        int subcolumns, GrtPass const *rows)
+typedef struct CloudFieldsRun { GrtCloudSampler_t *sampler; GrtCloudFields_t const *fields; } CloudFieldsRun;
+
+static int pipeline_run_from(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl, CloudFieldsRun const *cf,
+                             GrtAerosols_t const *ae, int subcolumns, GrtPass const *rows)
 {
     if (p->surface_ncol > 0 && cols->ncol != p->surface_ncol)
     {
@@ -447,7 +451,13 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t 
     }
     GRT_TRY(stage_columns(p, cols));
     int const C = cols->ncol, S = subcolumns > 0 ? subcolumns : 1;
-    if (cl != NULL)
+    if (cl != NULL && cf != NULL)
+    {
+        /* (cl holds the band limits and the thickness only: the kernel writes the tables where grt_stage_clouds puts them) */
+        fp_t const *t = cf->fields->temperature != NULL ? cf->fields->temperature : cols->layer_temperature;
+        GRT_TRY(grt_stage_cloud_fields(p, cl, cf->sampler, cf->fields, t, C, S));
+    }
+    else if (cl != NULL)
     {
         GRT_TRY(grt_stage_clouds(p, cl, C, S));
     }
@@ -510,6 +520,13 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t 
             GRT_TRY(subcolumns > 0 ? grt_band_solve_subcolumns(p, b, bi, C, S, &ps) : grt_band_solve(p, b, bi, C, &ps));
         }
     }
+    return GRTCODE_SUCCESS;
+}
+
+static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl, GrtAerosols_t const *ae,
+                        int subcolumns, GrtPass const *rows)
+{
+    GRT_TRY(pipeline_run_from(p, cols, cl, NULL, ae, subcolumns, rows));
     return GRTCODE_SUCCESS;
 }
 
@@ -649,6 +666,58 @@ EXTERN int grt_pipeline_run_subcolumns(GrtPipeline_t *p, GrtColumns_t const *col
     GrtPass const rows = {.profile = profile, .out = profile ? level_fluxes_dev : fluxes_dev, .out_stride =
                           profile ? GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN*p->num_levels : GRT_ALLSKY_FLUXES_PER_COLUMN};
     GRT_TRY(pipeline_run(p, cols, cl, NULL, num_subcolumns, &rows));
+    if (profile)
+    {
+        GRT_TRY(finish_profiles(p, cols->ncol, 2, level_fluxes_dev, heating_dev, fluxes_dev));
+    }
+    return GRTCODE_SUCCESS;
+}
+
+/* grt_ext.h: grt_pipeline_run_subcolumns with the tables sampled on the device from the cloud fields */
+EXTERN int grt_pipeline_run_cloud_fields(GrtPipeline_t *p, GrtColumns_t const *cols, GrtCloudSampler_t *sampler,
+                                         GrtCloudFields_t const *fields, fp_t *level_fluxes_dev, fp_t *heating_dev,
+                                         fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    GRT_TRY(grt_cloud_sampler_check(sampler, fields, 0));
+    if (fields->thickness == NULL || (fields->temperature == NULL && cols->layer_temperature == NULL))
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "a NULL array in the cloud fields (thickness; temperature with no layer temperatures "
+                 "in the columns).%s", "");
+    }
+    if (grt_cloud_sampler_device(sampler) != p->device)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "the sampler was created on device %d, the pipeline on device %d.",
+                 (int)grt_cloud_sampler_device(sampler), (int)p->device);
+    }
+    if (fields->ncol != cols->ncol)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "cloud fields of %d columns for a batch of %d.", fields->ncol, cols->ncol);
+    }
+    GRT_TRY(check_columns(p, cols));
+    if (fields->num_layers != p->num_levels - 1 || cols->num_levels != p->num_levels)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "cloud fields of %d layers, columns of %d levels: this pipeline has %d levels.",
+                 fields->num_layers, cols->num_levels, p->num_levels);
+    }
+    if (level_fluxes_dev == NULL && fluxes_dev == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "level_fluxes_dev and fluxes_dev are both NULL: nothing to write.%s", "");
+    }
+    if (level_fluxes_dev != NULL)
+    {
+        GRT_TRY(check_two_levels(p));
+    }
+    GrtClouds_t cl;
+    memset(&cl, 0, sizeof(cl));
+    grt_cloud_sampler_bands(sampler, &cl);
+    cl.thickness = fields->thickness;
+    CloudFieldsRun const cf = {sampler, fields};
+    int const profile = level_fluxes_dev != NULL;
+    GrtPass const rows = {.profile = profile, .out = profile ? level_fluxes_dev : fluxes_dev, .out_stride =
+                          profile ? GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN*p->num_levels : GRT_ALLSKY_FLUXES_PER_COLUMN};
+    GRT_TRY(pipeline_run_from(p, cols, &cl, &cf, NULL, fields->num_subcolumns, &rows));
     if (profile)
     {
         GRT_TRY(finish_profiles(p, cols->ncol, 2, level_fluxes_dev, heating_dev, fluxes_dev));

@@ -223,6 +223,21 @@ int grt_stage_clouds(GrtPipeline_t *p, GrtClouds_t const *cl, int C, int S)
     return GRTCODE_SUCCESS;
 }
 
+/* grt_stage_clouds for tables that are made on the device: the same buffer and layout, but only the thickness [C][L] is
+   uploaded; the sampler's kernel writes the four [S][C][3][B][L] sets behind it from the cloud fields (which it stages
+   itself), on the pipeline's lane and so ahead of the solvers that read them */
+int grt_stage_cloud_fields(GrtPipeline_t *p, GrtClouds_t const *cl, GrtCloudSampler_t *sampler, GrtCloudFields_t const *fields,
+                           fp_t const *temperature, int C, int S)
+{
+    size_t const L = (size_t)p->num_levels - 1, B = (size_t)cl->num_liquid_bands, tab = 3*B*L;
+    size_t const set = (size_t)S*(size_t)C*tab, need = (size_t)C*L + 4*set;
+    GRT_TRY(grt_staging_reserve(p, &p->cloud, need, (size_t)p->max_cols*L*(1 + 12*B*(size_t)S)));
+    memcpy(p->cloud.h, cl->thickness, sizeof(double)*(size_t)C*L);
+    GRT_TRY(grt_staging_upload(p, &p->cloud, (size_t)C*L));
+    GRT_TRY(grt_cloud_sampler_enqueue(sampler, fields, temperature, p->cloud.d + (size_t)C*L));
+    return GRTCODE_SUCCESS;
+}
+
 /* The interval of the aerosol grid x [na] (strictly increasing) each of the n points w0 + i dw lies in, as
    interpolate2 (utilities.c:149-222) assigns them: j with x[j] < w <= x[j+1]; -1 for w <= x[0] and for w > x[na-1],
    which the reference does not write. */

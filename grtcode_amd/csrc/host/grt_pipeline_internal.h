@@ -152,6 +152,8 @@ GRT_PRIVATE int grt_staging_upload(GrtPipeline_t *p, GrtStaging *st, size_t need
 GRT_PRIVATE void grt_staging_free(GrtPipeline_t *p, GrtStaging *st);
 GRT_PRIVATE void grt_keyed_table_free(GrtPipeline_t *p, GrtKeyedTable *t);
 GRT_PRIVATE int grt_stage_clouds(GrtPipeline_t *p, GrtClouds_t const *cl, int C, int S);
+GRT_PRIVATE int grt_stage_cloud_fields(GrtPipeline_t *p, GrtClouds_t const *cl, GrtCloudSampler_t *sampler,
+                                       GrtCloudFields_t const *fields, fp_t const *temperature, int C, int S);
 GRT_PRIVATE int grt_band_clouds(GrtPipeline_t *p, GrtBand *b, int bi, GrtClouds_t const *cl, int C, int S, GrtCloudArgs *ca);
 GRT_PRIVATE int grt_stage_aerosols(GrtPipeline_t *p, GrtAerosols_t const *ae, int C);
 GRT_PRIVATE int grt_band_aerosols(GrtPipeline_t *p, GrtBand *b, int bi, GrtAerosols_t const *ae, int C, GrtAerosolArgs *aa);

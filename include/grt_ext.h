@@ -41,7 +41,8 @@ EXTERN int grt_hitran_index_stats(long long stats[3]);
 /* ---- struct sizes for FFI callers (ctypes; cf. fortran-bindings/malloc_structs.c:40-66) */
 enum grt_struct_kind
 {
-    GRT_SPECTRAL_GRID = 0, GRT_OPTICS, GRT_GAS_OPTICS, GRT_SOLAR_FLUX, GRT_LONGWAVE, GRT_SHORTWAVE, GRT_CLOUDS
+    GRT_SPECTRAL_GRID = 0, GRT_OPTICS, GRT_GAS_OPTICS, GRT_SOLAR_FLUX, GRT_LONGWAVE, GRT_SHORTWAVE, GRT_CLOUDS,
+    GRT_CLOUD_PHASE, GRT_CLOUD_MODEL, GRT_CLOUD_FIELDS
 };
 EXTERN size_t grt_sizeof(int kind);
 
@@ -272,6 +273,88 @@ EXTERN int grt_pipeline_run_subcolumns(GrtPipeline_t *pipeline, GrtColumns_t con
                                        GrtClouds_t const *clouds, int num_subcolumns,
                                        fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev);
 
+/* ---- cloud subcolumns sampled on the device from cloud fields ------------------------------------------------------
+ * What grt_pipeline_run_subcolumns takes ready-made, made on the device: the band optics of S cloud subcolumns per column
+ * and pass from what a model holds -- cloud fraction, liquid and ice water content, overlap parameter, temperature.  One
+ * sample (column, pass, subcolumn, band) is one sample_subcolumn of the clouds library followed by its pade_band of liquid
+ * and ice for every layer (clouds/stochastic_clouds.c:11-28, 94-120, incomplete_beta.c:32-64, clouds_lib.c:47-82,
+ * cloud_pade_optics.c:152-213), operation for operation in double with no contraction: L rank values and L - 1 decision
+ * values are drawn; for ascending i, rank[i+1] = rank[i] where decide[i] <= overlap[i] (copies cascade); a layer is
+ * cloudy where rank > 1 - cf, strictly; the three beta lookups take the segment with the first x_i > at (the last one
+ * beyond the table), slope first, then intercept; the water PDF is (5, 5); the ice radius is the size of the layer's
+ * temperature class / 2; a radius no size regime holds, or a content that is not > 0, gives three zeros.  A fresh
+ * subcolumn is drawn for every band, as the reference does.  A cloudy layer with no water at all gives NaN contents and
+ * therefore zero optics, as in the library.  The pipeline never links libclouds.a (a site may substitute the reference's
+ * own), so the parametrisation arrives as data: */
+typedef struct GrtCloudPhase
+{
+    int nband, nsize, np, nq;           /* bands, size regimes, numerator and denominator coefficients */
+    fp_t const *band_lo, *band_hi;      /* [nband] cm-1 */
+    fp_t const *size_lo, *size_hi, *size_ref;   /* [nsize] microns */
+    fp_t const *coef[6];                /* ext_p, ext_q, ssa_p, ssa_q, asy_p, asy_q: [band][size][coefficient] */
+} GrtCloudPhase_t;
+/* The three tables as the clouds library holds them after loading, HOST arrays read by grt_cloud_sampler_create alone:
+   the Pade numbers already rounded to single precision (pade_load), the beta tables with x ascending and shapes up to 6. */
+typedef struct GrtCloudModel
+{
+    int num_shape, num_x;               /* beta tables: shape parameters 1 .. num_shape (>= 6), abscissae (>= 2) */
+    fp_t const *x;                      /* [num_x] */
+    fp_t const *value, *inverse;        /* [q - 1][p - 1][x] */
+    GrtCloudPhase_t liquid, ice;        /* ice.nband >= liquid.nband = B, whose bands drive the loop */
+} GrtCloudModel_t;
+typedef struct GrtCloudSampler GrtCloudSampler_t;
+/* uploads the tables once; GRTCODE_VALUE_ERR for a NULL argument or array, shapes outside the ranges above, x that
+   descends */
+EXTERN int grt_cloud_sampler_create(GrtCloudSampler_t **sampler, Device_t device, GrtCloudModel_t const *model);
+EXTERN int grt_cloud_sampler_destroy(GrtCloudSampler_t **sampler);
+
+/* Where the draws come from.
+ *   uniforms != NULL: from the caller, HOST [ncol][2][S][B][2 L - 1], in libc's order for a driver with num_subcolumns =
+ *     S -- per column the longwave pass, then the shortwave pass; per pass S subcolumns; per subcolumn B bands; per band L
+ *     ranks, then L - 1 decisions.  The parity hook, and the way to reproduce a rand()-driven run (rand()/RAND_MAX).
+ *   uniforms == NULL: from Philox4x32-10 on the device.  Key (seed's low 32 bits, seed's high 32 bits); counter (layer i,
+ *     band, pass GRT_MAX_SUBCOLUMNS + s, column_offset + c -- its low 32 bits); the four words r0 .. r3 of that ONE call
+ *     give layer i's rank, ((r0 >> 5) 2^26 + (r1 >> 6)) 2^-53, and the decision of the pair (i, i + 1) the same way from
+ *     (r2, r3).  Both lie in [0, 1), where the reference's rand()/RAND_MAX lie in [0, 1].  A column's clouds then depend
+ *     on the seed and its global index alone: not on the batch it is in, the rank that holds it or the order of calls. */
+typedef struct GrtCloudFields
+{
+    int ncol, num_layers;
+    int num_subcolumns;                 /* S, 1 .. GRT_MAX_SUBCOLUMNS */
+    fp_t const *cloud_fraction;         /* [ncol][L], each in [0, 1] */
+    fp_t const *liquid_content;         /* [ncol][L] g m-3, >= 0 */
+    fp_t const *ice_content;            /* [ncol][L] g m-3, >= 0 */
+    fp_t const *temperature;            /* [ncol][L] K; NULL (grt_pipeline_run_cloud_fields only): the columns' layer_temperature */
+    fp_t const *thickness;              /* [ncol][L] m (grt_pipeline_run_cloud_fields only) */
+    fp_t const *overlap;                /* [ncol][L-1] (calculate_overlap's alpha; not read when L == 1) */
+    fp_t liquid_radius;                 /* microns (the driver passes 10.0) */
+    uint64_t seed;
+    int64_t column_offset;              /* global index of column 0 */
+    fp_t const *uniforms;               /* [ncol][2][S][B][2 L - 1], or NULL: the generator */
+} GrtCloudFields_t;
+
+/* tables_dev (DEVICE memory) [4][S][ncol][3][B][L]: the sets lw_liquid, lw_ice, sw_liquid, sw_ice, each subcolumn-major
+   with extinction m-1, single-scattering albedo and asymmetry per liquid band and layer -- what grt_pipeline_run_subcolumns
+   leaves on the device after the thickness block.  One kernel (profile tag 16), one wavefront per sample; asynchronous on
+   the device's current lane (the fields are copied out before the call returns).  GRTCODE_VALUE_ERR, with nothing
+   launched and tables_dev untouched, for: a NULL sampler, fields, tables_dev or required array (temperature here); S
+   outside 1 .. GRT_MAX_SUBCOLUMNS; ncol or num_layers < 1; a cloud fraction outside [0, 1] or not finite; a content that
+   is negative or not finite. */
+EXTERN int grt_cloud_sampler_run(GrtCloudSampler_t *sampler, GrtCloudFields_t const *fields, fp_t *tables_dev);
+
+/* grt_pipeline_run_subcolumns with S = fields->num_subcolumns and the tables made by the sampler: its two output forms,
+   layouts, sweep rules and subcolumn mean.  The band limits of the cloud maps are the sampler's model's; the kernel writes
+   the tables straight into the pipeline's cloud buffer, and only the thickness crosses PCIe with the fields: no
+   [S][ncol][3][B][L] set is formed on the host.  Everything after the tables is grt_pipeline_run_subcolumns' code: the
+   result equals, bit for bit in the deterministic mode, grt_pipeline_run_subcolumns fed grt_cloud_sampler_run's tables.
+   GRTCODE_VALUE_ERR, with nothing launched and the outputs untouched, for what grt_cloud_sampler_run refuses (temperature
+   may be NULL here) and: a NULL thickness; fields->ncol != columns->ncol; ncol outside 1 .. max_columns; num_layers !=
+   num_levels - 1; level_fluxes_dev and fluxes_dev both NULL; fewer than 2 levels in the profile form; a sampler of
+   another device. */
+EXTERN int grt_pipeline_run_cloud_fields(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtCloudSampler_t *sampler,
+                                         GrtCloudFields_t const *fields, fp_t *level_fluxes_dev, fp_t *heating_dev,
+                                         fp_t *fluxes_dev);
+
 /* ---- clear-sky fluxes with aerosols ------------------------------------------------------------------------------
  * driver.c:426-472: the clear-clean pass of grt_pipeline_run (gas and Rayleigh), then the same solvers on
  * add_optics({gas, Rayleigh, aerosol}), both on ONE gas-optics launch per band -- what aerosol direct forcing (the
@@ -466,7 +549,8 @@ EXTERN int grt_multi_max(GrtMulti_t *multi, double *value);    /* barrier + maxi
  * 11 = the subcolumn-mean kernel of grt_pipeline_run_subcolumns (with S > 1; its all-sky solvers count under 8 / 9, each
  * band's launches together), 12 / 13 = LW / SW solver of the aerosol pass of grt_pipeline_run_aerosols (its clear-clean
  * pass counts under 3 / 4), 14 = the per-bin reduction and the heating-rate kernel of grt_pipeline_run_band_profiles (its
- * solvers count under 3 / 4 and 8 / 9), 15 = the surface-row kernel of grt_pipeline_set_surface (all its launches).
+ * solvers count under 3 / 4 and 8 / 9), 15 = the surface-row kernel of grt_pipeline_set_surface (all its launches),
+ * 16 = the cloud-sampling kernel of grt_cloud_sampler_run and grt_pipeline_run_cloud_fields.
  * Read after grt_pipeline_sync(). */
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
