@@ -25,7 +25,12 @@ GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN = 2 * GRT_PROFILE_ROWS_PER_COLUMN   # the cle
 GRT_ALLSKY_HEATING_ROWS_PER_COLUMN = 2 * GRT_HEATING_ROWS_PER_COLUMN   # the clear-sky two rows, then the all-sky two
 GRT_CLOUDS = 6                      # grt_sizeof kind of GrtClouds
 GRT_CLOUD_PHASE, GRT_CLOUD_MODEL, GRT_CLOUD_FIELDS = 7, 8, 9   # ... of GrtCloudPhase, GrtCloudModel, GrtCloudFields
-CLOUD_SAMPLER_TAG = 16              # grt_profile_read tag of the cloud-sampling kernel
+# grt_profile_read's tags (grt_ext.h: GRT_TAG_..., where each one's bracket is described)
+(TAG_GAS_LW, TAG_GAS_SW, TAG_SOLVER_LW, TAG_SOLVER_SW, TAG_CLEAR_OPTICS, TAG_FAR_LW, TAG_FAR_SW, TAG_ALLSKY_LW,
+ TAG_ALLSKY_SW, TAG_BINS, TAG_SUBCOLUMN_MEAN, TAG_AEROSOL_LW, TAG_AEROSOL_SW, TAG_BAND_PROFILES, TAG_SURFACE,
+ TAG_CLOUD_SAMPLER) = range(1, 17)
+TAG_FAR_OFFSET = TAG_FAR_LW - TAG_GAS_LW    # from a line kernel's tag to its far-field gather's
+CLOUD_SAMPLER_TAG = TAG_CLOUD_SAMPLER
 GRT_MAX_SUBCOLUMNS = 64             # grt_pipeline_run_subcolumns: subcolumns per column, 1 .. this
 RETURN_CODES = ["GRTCODE_SUCCESS", "GRTCODE_INVALID_ERR", "GRTCODE_DIVBYZERO_ERR", "GRTCODE_OVERFLOW_ERR",
                 "GRTCODE_UNDERFLOW_ERR", "GRTCODE_SENTINEL_ERR", "GRTCODE_NULL_ERR", "GRTCODE_NON_NULL_ERR",
@@ -790,18 +795,25 @@ class Pipeline:
         sw_up, sw_down [ncol][V], lw_heating, sw_heating [ncol][V-1] and fluxes [ncol][12]."""
         return self._read_profiles("allsky_profiles", 2, ncol)
 
+    @staticmethod
+    def _pack_edges(lw_edges, sw_edges):
+        """The two bands' bin edges as the bin entry points take them: (bins per band, edge pointers per band, the int32
+        arrays the pointers point into -- to be kept until the call has returned)."""
+        e = [None if x is None else np.ascontiguousarray(x, dtype=np.int32) for x in (lw_edges, sw_edges)]
+        nb = [0 if x is None else max(x.size - 1, 0) for x in e]
+        ptr = [None if x is None else x.ctypes.data_as(C.c_void_p) for x in e]
+        return nb, ptr, e
+
     def run_spectral(self, gcols, gclouds=None, lw_edges=None, sw_edges=None):
         """grt_pipeline_run_spectral into this object's device buffers (spectral() reads them): the six rows at every grid
         point and, for lw_edges / sw_edges (grid-point indices, num_bins + 1 of them), their bins; gclouds: all-sky too."""
         sets = 1 if gclouds is None else 2
-        e = [None if x is None else np.ascontiguousarray(x, dtype=np.int32) for x in (lw_edges, sw_edges)]
-        nb = [0 if x is None else max(x.size - 1, 0) for x in e]
+        nb, ptr, _keep = self._pack_edges(lw_edges, sw_edges)
         n = self.max_columns
         self.spec_shape = (sets, nb[0], nb[1])
         spectral = self._buffer("spectral", 8 * n * sets * 6 * (self.nw[0] + self.nw[1]))
         binned = self._buffer("spectral.binned", 8 * n * sets * 6 * (nb[0] + nb[1])) if nb[0] + nb[1] else None
         fluxes = self._buffer("spectral.fluxes", 8 * n * sets * GRT_FLUXES_PER_COLUMN)
-        ptr = [None if x is None else x.ctypes.data_as(C.c_void_p) for x in e]
         check(self.lib.grt_pipeline_run_spectral(self.p, C.byref(gcols), C.byref(gclouds) if gclouds is not None else None,
                                                  ptr[0], nb[0], ptr[1], nb[1], spectral.ptr,
                                                  binned.ptr if binned is not None else None, fluxes.ptr))
@@ -833,13 +845,11 @@ class Pipeline:
         flux and every layer's heating rate per bin of lw_edges / sw_edges (grid-point indices, num_bins + 1 of them);
         gclouds: all-sky too."""
         sets = 1 if gclouds is None else 2
-        e = [None if x is None else np.ascontiguousarray(x, dtype=np.int32) for x in (lw_edges, sw_edges)]
-        nb = [0 if x is None else max(x.size - 1, 0) for x in e]
+        nb, ptr, _keep = self._pack_edges(lw_edges, sw_edges)
         V, n = self.num_levels, self.max_columns
         self.band_shape = (sets, nb[0], nb[1])
         levels = self._buffer("band_profiles.levels", 8 * n * sets * 2 * max(nb[0] + nb[1], 1) * V)
         heating = self._buffer("band_profiles.heating", 8 * n * sets * max(nb[0] + nb[1], 1) * (V - 1))
-        ptr = [None if x is None else x.ctypes.data_as(C.c_void_p) for x in e]
         check(self.lib.grt_pipeline_run_band_profiles(self.p, C.byref(gcols),
                                                       C.byref(gclouds) if gclouds is not None else None, ptr[0], nb[0],
                                                       ptr[1], nb[1], levels.ptr, heating.ptr))

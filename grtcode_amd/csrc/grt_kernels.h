@@ -120,7 +120,8 @@ typedef struct GrtGasOpticsArgs
     int tree_levels;          /* > 0: far field by the cell hierarchy (fine grids), this many coarse levels */
     int mom_terms;            /* moments per cell: 8, or -- tree form on sparse lines -- 12 (near field 3.95 |z|max
                                  instead of 7.8 |z|max); 0 means 8 in the one-pass form */
-    int profile_tag;          /* != 0: time the line kernel under this tag (the two-pass gather under tag + 5) */
+    int profile_tag;          /* != 0: time the line kernel under this tag (the two-pass gather under tag +
+                                 GRT_TAG_FAR_OFFSET) */
     int near_block;           /* set by the plan: 64 where the tree form's gather shares its walk per wave -- near
                                  fields are then whole 64-point blocks (the halo leaves room for that); else 0 */
     int deterministic;        /* != 0 (GRT_DETERMINISTIC=1 / grt_set_deterministic): every floating-point sum in one fixed
@@ -185,7 +186,8 @@ int grt_launch_add_continua(void *stream, GrtContinua const *c, int num_layers, 
 
 
 int grt_launch_gas_optics(void *stream, GrtGasOpticsArgs const *a);
-/* HIP-event brackets on the library stream (grt_device.c; grt_ext.h: grt_profile_*) */
+/* HIP-event brackets on the library stream (grt_device.c; grt_ext.h: grt_profile_* and the tags, GRT_TAG_...) */
+enum { GRT_TAG_FAR_OFFSET = 5 };    /* from a line kernel's tag (GRT_TAG_GAS_LW / _SW) to its far-field gather's (GRT_TAG_FAR_LW / _SW) */
 int grt_profile_begin(void *stream, int tag);
 void grt_profile_end(void *stream, int slot);
 /* fast == 1 / 3: the cell-moment kernels (k_gas_optics_mp.hip), launched with the arguments as given; whether they apply

@@ -871,7 +871,7 @@ extern "C" int grt_launch_gas_optics_mp(void *stream, GrtGasOpticsArgs const *a)
         }
         if (a->profile_tag) grt_profile_end(stream, slot);
         b.nslice = 1;
-        slot = a->profile_tag ? grt_profile_begin(stream, a->profile_tag + 5) : -1;
+        slot = a->profile_tag ? grt_profile_begin(stream, a->profile_tag + GRT_TAG_FAR_OFFSET) : -1;
         // the second pass: k_gas_optics_far.hip (the coarse levels above the first pass's tiles and the hierarchy's gather, or
         // the single-level gather)
         int const rc_far = grt_launch_far_field(stream, &b, fsteps, shift);

@@ -295,7 +295,7 @@ int grt_cloud_sampler_enqueue(GrtCloudSampler_t *sp, GrtCloudFields_t const *f, 
     a.key1 = (uint32_t)(f->seed >> 32);
     a.column0 = (uint32_t)((uint64_t)f->column_offset & 0xffffffffu);
     a.tables = tables_dev;
-    int const slot = grt_profile_begin(s, 16);
+    int const slot = grt_profile_begin(s, GRT_TAG_CLOUD_SAMPLER);
     int const krc = grt_launch_cloud_sample(s, &a);
     grt_profile_end(s, slot);
     GRT_TRY(grt_dev_check(krc, "cloud sampling kernel"));

@@ -565,7 +565,9 @@ static int launch_column_group(GasOptics_t *go, LaunchPlan const *p, int c0, int
         /* slices accumulate with atomics (launch.c:61 zeroes tau in every case) */
         GRT_TRY(grt_dev_zero(go->device, args.tau, sizeof(double)*tau_col_stride*ncol, s));
     }
-    int const tag = im->profile_tag ? im->profile_tag : (args.nw <= 10000 ? 1 : 2);
+    _Static_assert(GRT_TAG_FAR_LW == GRT_TAG_GAS_LW + GRT_TAG_FAR_OFFSET && GRT_TAG_FAR_SW == GRT_TAG_GAS_SW + GRT_TAG_FAR_OFFSET,
+                   "the far-field gather's tags follow the line kernel's");
+    int const tag = im->profile_tag ? im->profile_tag : (args.nw <= 10000 ? GRT_TAG_GAS_LW : GRT_TAG_GAS_SW);
     /* (with a work list, "nslice" reports the largest number of pieces a tile was cut into) */
     long long const info[8] = {args.fast, args.tile, args.tile_items != NULL ? im->items_cut : args.nslice, args.tree_levels, args.fast == 3 ? args.halo : 0,
                                args.fast == 3 ? (long long)im->gmom_bytes : 0,

@@ -128,7 +128,7 @@ typedef struct GrtGasOpticsImpl
     void *colstate_uploaded;       /* event: colstate_h has been copied out and may be refilled */
     double *colstate_d;
     int tile, nslice, fast;        /* launch tuning (grt_gas_optics_tune) */
-    int profile_tag;               /* 0: by grid size; the pipeline sets 1 (longwave) / 2 (shortwave) */
+    int profile_tag;               /* 0: by grid size; the pipeline sets GRT_TAG_GAS_LW / _SW */
     unsigned long long *probe;     /* grt_gas_optics_probe: device buffer for the instrumented line kernel, or NULL */
     uint64_t probe_words;
 } GrtGasOpticsImpl;

@@ -63,6 +63,34 @@ int grt_upload_rows(GrtPipeline_t *p, double **rows_h, size_t n, double ***rows_
     return GRTCODE_SUCCESS;
 }
 
+/* buf holds at least `doubles` doubles afterwards.  One that is large enough stays as it is, contents included.  One that
+   is not is replaced, and a live buffer is replaced only after the lane's stream has drained: kernels of an earlier call
+   on this lane may still read the old block.  (A buffer that appears for the first time has no reader to wait for.)
+   *fresh (unless NULL): the buffer is new, its contents are not the last call's.  A failed allocation leaves it empty. */
+int grt_scratch_need(GrtPipeline_t *p, GrtScratch *buf, size_t doubles, int *fresh)
+{
+    if (fresh != NULL)
+    {
+        *fresh = doubles > buf->doubles;
+    }
+    if (doubles <= buf->doubles)
+    {
+        return GRTCODE_SUCCESS;
+    }
+    if (buf->d != NULL)
+    {
+        GRT_TRY(grt_dev_sync(p->device, grt_dev_stream(p->device)));
+        grt_dev_free(p->device, buf->d);
+        buf->d = NULL;
+        buf->doubles = 0;
+    }
+    void *blk = NULL;
+    GRT_TRY(grt_dev_alloc(p->device, &blk, sizeof(double)*doubles));
+    buf->d = blk;
+    buf->doubles = doubles;
+    return GRTCODE_SUCCESS;
+}
+
 static int band_alloc(GrtPipeline_t *p, GrtBand *b, GasOptics_t *gas)
 {
     memset(b, 0, sizeof(*b));
@@ -72,19 +100,18 @@ static int band_alloc(GrtPipeline_t *p, GrtBand *b, GasOptics_t *gas)
     }
     b->gas = gas;
     b->n = gas->grid.n;
-    ((GrtGasOpticsImpl *)gas->impl)->profile_tag = (b == &p->band[0]) ? 1 : 2;
+    ((GrtGasOpticsImpl *)gas->impl)->profile_tag = (b == &p->band[0]) ? GRT_TAG_GAS_LW : GRT_TAG_GAS_SW;
     size_t const L = (size_t)p->num_levels - 1, V = (size_t)p->num_levels, C = (size_t)p->max_cols;
     size_t const opt = sizeof(double)*C*L*b->n, flx = sizeof(double)*C*V*b->n;
     void *blk = NULL;
     if (!p->keep_spectra)
     {
-        /* fused form: tau_gas and the partial sums (the shortwave solver's park block -- 2 V + 5 L rows per column, 10.8 GB
-           for 64 columns of the 1 cm-1 band -- is allocated when a launch first needs it: its two-sweep form, see run) */
+        /* fused form: tau_gas and the partial sums (the shortwave solver's park block is allocated when a launch first
+           needs it: its two-sweep form, GRT_SCRATCH_PARK) */
         b->nblocks = grt_solver_blocks(b->n);
         size_t const part = sizeof(double)*C*6*b->nblocks;
         GRT_TRY(grt_dev_alloc(p->device, &blk, opt + part));
         b->tau_gas = blk;
-        b->park = NULL;
         b->partials = b->tau_gas + C*L*b->n;
         return GRTCODE_SUCCESS;
     }
@@ -223,20 +250,16 @@ static void grt_pipeline_release(GrtPipeline_t **pipeline)
     for (int b = 0; b < 2; ++b)
     {
         grt_dev_free(p->device, p->band[b].tau_gas);
-        grt_dev_free(p->device, p->band[b].park);
         grt_dev_free(p->device, p->band[b].rows_d);
-        grt_dev_free(p->device, p->band[b].level_partials);
         grt_dev_free(p->device, p->band[b].level_rows_d);
+        for (int k = 0; k < GRT_SCRATCH_COUNT; ++k)
+        {
+            grt_dev_free(p->device, p->band[b].scratch[k].d);
+        }
         grt_keyed_table_free(p, &p->band[b].cloud_map);
         grt_keyed_table_free(p, &p->band[b].aer_map);
         grt_keyed_table_free(p, &p->band[b].bin_table);
-        grt_dev_free(p->device, p->band[b].spread_block);
-        grt_dev_free(p->device, p->band[b].bin_partials);
-        grt_dev_free(p->device, p->band[b].sub_partials);
-        grt_dev_free(p->device, p->band[b].flux_sum);
         grt_keyed_table_free(p, &p->band[b].surf_map);
-        grt_dev_free(p->device, p->band[b].surf_rows);
-        grt_dev_free(p->device, p->band[b].surf_rows_dif);
     }
     grt_staging_free(p, &p->surf);
     grt_staging_free(p, &p->aer);
@@ -434,28 +457,39 @@ EXTERN int grt_pipeline_set_surface(GrtPipeline_t *p, GrtSurface_t const *surfac
 
 /* ---- the run ------------------------------------------------------------------------------------------------------ */
 
-/* What the run entry points share after their argument checks: the batch (and its clouds or aerosols) staged, then per
-   band the gas optics and the solves into rows->out, each a copy of `rows` (the run's profile flag, output and spectral
-   outputs) completed into one pass: the clear-sky solve, then -- with aerosols or clouds -- the aerosol or all-sky one,
-   whose rows follow the clear-sky set's (grt_set_offset).  subcolumns > 0 (grt_pipeline_run_subcolumns): the all-sky pass
-   is the mean over that many subcolumns (grt_band_solve_subcolumns). */
-typedef struct CloudFieldsRun { GrtCloudSampler_t *sampler; GrtCloudFields_t const *fields; } CloudFieldsRun;
-
-static int pipeline_run_from(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl, CloudFieldsRun const *cf,
-                             GrtAerosols_t const *ae, int subcolumns, GrtPass const *rows)
+/* What joins the gas in a run's second set: nothing (all zero: the run has one set), clouds, or aerosols.  subcolumns > 0
+   (grt_pipeline_run_subcolumns): the all-sky pass is the mean over that many subcolumns (grt_band_solve_subcolumns);
+   with a sampler (grt_pipeline_run_cloud_fields), their tables are written on the device from `fields`, and clouds holds
+   the band limits and the thickness only. */
+typedef struct GrtJoin
 {
+    GrtClouds_t const *clouds;
+    GrtCloudSampler_t *sampler;
+    GrtCloudFields_t const *fields;
+    GrtAerosols_t const *aerosols;
+    int subcolumns;
+} GrtJoin;
+
+/* What the run entry points share after their argument checks: the batch (and its clouds or aerosols) staged, then per
+   band the gas optics and the solves into rows->out, each a copy of `rows` (the run's form, output and bins) completed
+   into one pass: the clear-sky solve, then -- with aerosols or clouds -- the aerosol or all-sky one, whose rows follow the
+   clear-sky set's (grt_set_offset). */
+static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin const *join, GrtPass const *rows)
+{
+    GrtClouds_t const *cl = join->clouds;
+    GrtAerosols_t const *ae = join->aerosols;
     if (p->surface_ncol > 0 && cols->ncol != p->surface_ncol)
     {
         GRT_FAIL(GRTCODE_VALUE_ERR, "%d columns asked for, the surface in force (grt_pipeline_set_surface) has %d.",
                  cols->ncol, p->surface_ncol);
     }
     GRT_TRY(stage_columns(p, cols));
-    int const C = cols->ncol, S = subcolumns > 0 ? subcolumns : 1;
-    if (cl != NULL && cf != NULL)
+    int const C = cols->ncol, S = join->subcolumns > 0 ? join->subcolumns : 1;
+    if (cl != NULL && join->sampler != NULL)
     {
-        /* (cl holds the band limits and the thickness only: the kernel writes the tables where grt_stage_clouds puts them) */
-        fp_t const *t = cf->fields->temperature != NULL ? cf->fields->temperature : cols->layer_temperature;
-        GRT_TRY(grt_stage_cloud_fields(p, cl, cf->sampler, cf->fields, t, C, S));
+        /* (the kernel writes the tables where grt_stage_clouds puts them) */
+        fp_t const *t = join->fields->temperature != NULL ? join->fields->temperature : cols->layer_temperature;
+        GRT_TRY(grt_stage_cloud_fields(p, cl, join->sampler, join->fields, t, C, S));
     }
     else if (cl != NULL)
     {
@@ -487,7 +521,7 @@ static int pipeline_run_from(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClou
             }
             continue;
         }
-        if (rows->bp != NULL && rows->bp->num_bins[bi] == 0)
+        if (rows->bins != NULL && rows->profile && rows->bins->num_bins[bi] == 0)
         {
             continue;                  /* (a band without bins has no rows: nothing of it is computed) */
         }
@@ -517,16 +551,9 @@ static int pipeline_run_from(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClou
         if (cl != NULL)
         {
             ps.clouds = &ca;
-            GRT_TRY(subcolumns > 0 ? grt_band_solve_subcolumns(p, b, bi, C, S, &ps) : grt_band_solve(p, b, bi, C, &ps));
+            GRT_TRY(join->subcolumns > 0 ? grt_band_solve_subcolumns(p, b, bi, C, S, &ps) : grt_band_solve(p, b, bi, C, &ps));
         }
     }
-    return GRTCODE_SUCCESS;
-}
-
-static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl, GrtAerosols_t const *ae,
-                        int subcolumns, GrtPass const *rows)
-{
-    GRT_TRY(pipeline_run_from(p, cols, cl, NULL, ae, subcolumns, rows));
     return GRTCODE_SUCCESS;
 }
 
@@ -549,13 +576,40 @@ static int check_two_levels(GrtPipeline_t const *p)
     return GRTCODE_SUCCESS;
 }
 
-/* the level fluxes' heating rates and six rows, of `sets` sets per column */
-static int finish_profiles(GrtPipeline_t *p, int ncol, int sets, fp_t *levels, fp_t *heating, fp_t *fluxes)
+/* The rows of a run of `sets` sets per column in the form its two outputs ask for: the profile form, to
+   level_fluxes_dev, when that is given (it needs two levels), else the six-row form, to fluxes_dev; one of the two is
+   needed. */
+static int output_form(GrtPipeline_t const *p, int sets, fp_t *level_fluxes_dev, fp_t *fluxes_dev, GrtPass *rows)
 {
+    if (level_fluxes_dev == NULL && fluxes_dev == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "level_fluxes_dev and fluxes_dev are both NULL: nothing to write.%s", "");
+    }
+    int const profile = level_fluxes_dev != NULL;
+    if (profile)
+    {
+        GRT_TRY(check_two_levels(p));
+    }
+    memset(rows, 0, sizeof(*rows));
+    rows->profile = profile;
+    rows->out = profile ? level_fluxes_dev : fluxes_dev;
+    rows->sets = sets;
+    rows->out_stride = sets*grt_set_offset(p, profile);
+    return GRTCODE_SUCCESS;
+}
+
+/* what closes such a run: in the profile form, the level fluxes' heating rates and six rows, of every set */
+static int finish_profiles(GrtPipeline_t *p, int ncol, GrtPass const *rows, fp_t *heating, fp_t *fluxes)
+{
+    if (!rows->profile)
+    {
+        return GRTCODE_SUCCESS;
+    }
     int const bands = (p->band[0].gas != NULL) | (p->band[1].gas != NULL) << 1;
-    GRT_TRY(grt_dev_check(grt_launch_profile_finish(grt_dev_stream(p->device), ncol, sets, p->num_levels, bands,
+    GRT_TRY(grt_dev_check(grt_launch_profile_finish(grt_dev_stream(p->device), ncol, rows->sets, p->num_levels, bands,
                                                     p->user_level, GRT_GRAVITY, GRT_SPECIFIC_HEAT_AIR,
-                                                    p->small.d + p->off_p, levels, heating, fluxes), "heating rate kernel"));
+                                                    p->small.d + p->off_p, rows->out, heating, fluxes),
+                          "heating rate kernel"));
     return GRTCODE_SUCCESS;
 }
 
@@ -564,8 +618,10 @@ EXTERN int grt_pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, fp_t *fl
     GRT_REQUIRE_PTR(p);
     GRT_REQUIRE_PTR(cols);
     GRT_REQUIRE_PTR(fluxes_dev);
-    GrtPass const rows = {.profile = 0, .out = fluxes_dev, .out_stride = GRT_FLUXES_PER_COLUMN};
-    GRT_TRY(pipeline_run(p, cols, NULL, NULL, 0, &rows));
+    GrtJoin const join = {0};
+    GrtPass rows;
+    GRT_TRY(output_form(p, 1, NULL, fluxes_dev, &rows));
+    GRT_TRY(pipeline_run(p, cols, &join, &rows));
     return GRTCODE_SUCCESS;
 }
 
@@ -580,11 +636,12 @@ EXTERN int grt_pipeline_run_profiles(GrtPipeline_t *p, GrtColumns_t const *cols,
                  GRT_PROFILE_ROWS_PER_COLUMN, p->num_levels);
     }
     GRT_TRY(check_columns(p, cols));
-    GRT_TRY(check_two_levels(p));
     /* [c][2 V] rows of band bi -> level_fluxes_dev[c][2 bi + {0, 1}][V], then the level fluxes' heating rates and six rows */
-    GrtPass const rows = {.profile = 1, .out = level_fluxes_dev, .out_stride = GRT_PROFILE_ROWS_PER_COLUMN*p->num_levels};
-    GRT_TRY(pipeline_run(p, cols, NULL, NULL, 0, &rows));
-    GRT_TRY(finish_profiles(p, cols->ncol, 1, level_fluxes_dev, heating_dev, fluxes_dev));
+    GrtJoin const join = {0};
+    GrtPass rows;
+    GRT_TRY(output_form(p, 1, level_fluxes_dev, fluxes_dev, &rows));
+    GRT_TRY(pipeline_run(p, cols, &join, &rows));
+    GRT_TRY(finish_profiles(p, cols->ncol, &rows, heating_dev, fluxes_dev));
     return GRTCODE_SUCCESS;
 }
 
@@ -616,8 +673,10 @@ EXTERN int grt_pipeline_run_allsky(GrtPipeline_t *p, GrtColumns_t const *cols, G
     GRT_REQUIRE_PTR(cols);
     GRT_REQUIRE_PTR(fluxes_dev);
     GRT_TRY(check_clouds(p, cols, cl));
-    GrtPass const rows = {.profile = 0, .out = fluxes_dev, .out_stride = GRT_ALLSKY_FLUXES_PER_COLUMN};
-    GRT_TRY(pipeline_run(p, cols, cl, NULL, 0, &rows));
+    GrtJoin const join = {.clouds = cl};
+    GrtPass rows;
+    GRT_TRY(output_form(p, 2, NULL, fluxes_dev, &rows));
+    GRT_TRY(pipeline_run(p, cols, &join, &rows));
     return GRTCODE_SUCCESS;
 }
 
@@ -631,14 +690,14 @@ EXTERN int grt_pipeline_run_allsky_profiles(GrtPipeline_t *p, GrtColumns_t const
         GRT_FAIL(GRTCODE_VALUE_ERR, "level_fluxes_dev is NULL: the level fluxes [ncol][%d][%d] are the output.",
                  GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN, p->num_levels);
     }
-    GRT_TRY(check_two_levels(p));
-    GRT_TRY(check_clouds(p, cols, cl));
     /* clear-sky [c][2 V] rows of band bi -> level_fluxes_dev[c][2 bi + {0, 1}][V], all-sky -> [c][4 + 2 bi + {0, 1}][V];
        then both sets' heating rates and six rows */
-    GrtPass const rows = {.profile = 1, .out = level_fluxes_dev, .out_stride =
-                          GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN*p->num_levels};
-    GRT_TRY(pipeline_run(p, cols, cl, NULL, 0, &rows));
-    GRT_TRY(finish_profiles(p, cols->ncol, 2, level_fluxes_dev, heating_dev, fluxes_dev));
+    GrtJoin const join = {.clouds = cl};
+    GrtPass rows;
+    GRT_TRY(output_form(p, 2, level_fluxes_dev, fluxes_dev, &rows));
+    GRT_TRY(check_clouds(p, cols, cl));
+    GRT_TRY(pipeline_run(p, cols, &join, &rows));
+    GRT_TRY(finish_profiles(p, cols->ncol, &rows, heating_dev, fluxes_dev));
     return GRTCODE_SUCCESS;
 }
 
@@ -651,25 +710,14 @@ EXTERN int grt_pipeline_run_subcolumns(GrtPipeline_t *p, GrtColumns_t const *col
     {
         GRT_FAIL(GRTCODE_VALUE_ERR, "%d subcolumns asked for: 1 to %d.", num_subcolumns, GRT_MAX_SUBCOLUMNS);
     }
-    if (level_fluxes_dev == NULL && fluxes_dev == NULL)
-    {
-        GRT_FAIL(GRTCODE_VALUE_ERR, "level_fluxes_dev and fluxes_dev are both NULL: nothing to write.%s", "");
-    }
-    if (level_fluxes_dev != NULL)
-    {
-        GRT_TRY(check_two_levels(p));
-    }
-    GRT_TRY(check_clouds(p, cols, cl));
     /* grt_pipeline_run_allsky's layout and shortwave sweep rule; or grt_pipeline_run_allsky_profiles' layouts, the heating
        rates and six rows of the mean level fluxes */
-    int const profile = level_fluxes_dev != NULL;
-    GrtPass const rows = {.profile = profile, .out = profile ? level_fluxes_dev : fluxes_dev, .out_stride =
-                          profile ? GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN*p->num_levels : GRT_ALLSKY_FLUXES_PER_COLUMN};
-    GRT_TRY(pipeline_run(p, cols, cl, NULL, num_subcolumns, &rows));
-    if (profile)
-    {
-        GRT_TRY(finish_profiles(p, cols->ncol, 2, level_fluxes_dev, heating_dev, fluxes_dev));
-    }
+    GrtJoin const join = {.clouds = cl, .subcolumns = num_subcolumns};
+    GrtPass rows;
+    GRT_TRY(output_form(p, 2, level_fluxes_dev, fluxes_dev, &rows));
+    GRT_TRY(check_clouds(p, cols, cl));
+    GRT_TRY(pipeline_run(p, cols, &join, &rows));
+    GRT_TRY(finish_profiles(p, cols->ncol, &rows, heating_dev, fluxes_dev));
     return GRTCODE_SUCCESS;
 }
 
@@ -701,53 +749,22 @@ EXTERN int grt_pipeline_run_cloud_fields(GrtPipeline_t *p, GrtColumns_t const *c
         GRT_FAIL(GRTCODE_VALUE_ERR, "cloud fields of %d layers, columns of %d levels: this pipeline has %d levels.",
                  fields->num_layers, cols->num_levels, p->num_levels);
     }
-    if (level_fluxes_dev == NULL && fluxes_dev == NULL)
-    {
-        GRT_FAIL(GRTCODE_VALUE_ERR, "level_fluxes_dev and fluxes_dev are both NULL: nothing to write.%s", "");
-    }
-    if (level_fluxes_dev != NULL)
-    {
-        GRT_TRY(check_two_levels(p));
-    }
+    GrtPass rows;
+    GRT_TRY(output_form(p, 2, level_fluxes_dev, fluxes_dev, &rows));
     GrtClouds_t cl;
     memset(&cl, 0, sizeof(cl));
     grt_cloud_sampler_bands(sampler, &cl);
     cl.thickness = fields->thickness;
-    CloudFieldsRun const cf = {sampler, fields};
-    int const profile = level_fluxes_dev != NULL;
-    GrtPass const rows = {.profile = profile, .out = profile ? level_fluxes_dev : fluxes_dev, .out_stride =
-                          profile ? GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN*p->num_levels : GRT_ALLSKY_FLUXES_PER_COLUMN};
-    GRT_TRY(pipeline_run_from(p, cols, &cl, &cf, NULL, fields->num_subcolumns, &rows));
-    if (profile)
-    {
-        GRT_TRY(finish_profiles(p, cols->ncol, 2, level_fluxes_dev, heating_dev, fluxes_dev));
-    }
+    GrtJoin const join = {.clouds = &cl, .sampler = sampler, .fields = fields, .subcolumns = fields->num_subcolumns};
+    GRT_TRY(pipeline_run(p, cols, &join, &rows));
+    GRT_TRY(finish_profiles(p, cols->ncol, &rows, heating_dev, fluxes_dev));
     return GRTCODE_SUCCESS;
 }
 
 /* one band's aerosol inputs: none, or at least two strictly increasing grid points and the optics */
 static int check_aerosol_band(char const *name, int na, fp_t const *grid, fp_t const *optics)
 {
-    if (na < 0 || na == 1)
-    {
-        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s aerosol grid points: 0 (no aerosol) or at least 2.", na, name);
-    }
-    if (na == 0)
-    {
-        return GRTCODE_SUCCESS;
-    }
-    if (grid == NULL || optics == NULL)
-    {
-        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s aerosol grid points with a NULL grid or NULL optics.", na, name);
-    }
-    for (int j = 0; j + 1 < na; ++j)
-    {
-        if (!(grid[j + 1] > grid[j]))
-        {
-            GRT_FAIL(GRTCODE_VALUE_ERR, "%s aerosol grid not strictly increasing (grid[%d] = %e, grid[%d] = %e).", name, j,
-                     grid[j], j + 1, grid[j + 1]);
-        }
-    }
+    GRT_TRY(grt_check_grid(name, " aerosol", "no aerosol", "optics", na, grid, optics));
     return GRTCODE_SUCCESS;
 }
 
@@ -760,14 +777,10 @@ EXTERN int grt_pipeline_run_aerosols(GrtPipeline_t *p, GrtColumns_t const *cols,
     {
         GRT_FAIL(GRTCODE_VALUE_ERR, "no aerosol inputs (GrtAerosols_t is NULL).%s", "");
     }
-    if (level_fluxes_dev == NULL && fluxes_dev == NULL)
-    {
-        GRT_FAIL(GRTCODE_VALUE_ERR, "level_fluxes_dev and fluxes_dev are both NULL: nothing to write.%s", "");
-    }
-    if (level_fluxes_dev != NULL)
-    {
-        GRT_TRY(check_two_levels(p));
-    }
+    /* grt_pipeline_run_allsky's layout (the aerosol set where the all-sky set is) and shortwave sweep rule; or
+       grt_pipeline_run_allsky_profiles' layouts, both sets' heating rates and six rows */
+    GrtPass rows;
+    GRT_TRY(output_form(p, 2, level_fluxes_dev, fluxes_dev, &rows));
     /* (a band the pipeline does not have ignores its aerosol fields) */
     GrtAerosols_t a = *ae;
     if (p->band[0].gas == NULL)
@@ -781,16 +794,9 @@ EXTERN int grt_pipeline_run_aerosols(GrtPipeline_t *p, GrtColumns_t const *cols,
     GRT_TRY(check_aerosol_band("longwave", a.lw_num_points, a.lw_grid, a.lw_optics));
     GRT_TRY(check_aerosol_band("shortwave", a.sw_num_points, a.sw_grid, a.sw_optics));
     GRT_TRY(check_columns(p, cols));
-    /* grt_pipeline_run_allsky's layout (the aerosol set where the all-sky set is) and shortwave sweep rule; or
-       grt_pipeline_run_allsky_profiles' layouts, both sets' heating rates and six rows */
-    int const profile = level_fluxes_dev != NULL;
-    GrtPass const rows = {.profile = profile, .out = profile ? level_fluxes_dev : fluxes_dev, .out_stride =
-                          profile ? GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN*p->num_levels : GRT_ALLSKY_FLUXES_PER_COLUMN};
-    GRT_TRY(pipeline_run(p, cols, NULL, &a, 0, &rows));
-    if (profile)
-    {
-        GRT_TRY(finish_profiles(p, cols->ncol, 2, level_fluxes_dev, heating_dev, fluxes_dev));
-    }
+    GrtJoin const join = {.aerosols = &a};
+    GRT_TRY(pipeline_run(p, cols, &join, &rows));
+    GRT_TRY(finish_profiles(p, cols->ncol, &rows, heating_dev, fluxes_dev));
     return GRTCODE_SUCCESS;
 }
 
@@ -849,11 +855,13 @@ EXTERN int grt_pipeline_run_spectral(GrtPipeline_t *p, GrtColumns_t const *cols,
     {
         GRT_TRY(check_clouds(p, cols, cl));
     }
-    SpectralOut const so = {.spectral = spectral_dev, .binned = binned_dev, .sets = cl != NULL ? 2 : 1,
-                            .edges = {lw_edges, sw_edges}, .num_bins = {lw_num_bins, sw_num_bins}};
-    GrtPass const rows = {.profile = 0, .out = fluxes_dev, .so = &so,
-                          .out_stride = cl != NULL ? GRT_ALLSKY_FLUXES_PER_COLUMN : GRT_FLUXES_PER_COLUMN};
-    GRT_TRY(pipeline_run(p, cols, cl, NULL, 0, &rows));
+    GrtBins const bins = {.spectral = spectral_dev, .binned = binned_dev, .edges = {lw_edges, sw_edges},
+                          .num_bins = {lw_num_bins, sw_num_bins}};
+    GrtJoin const join = {.clouds = cl};
+    GrtPass rows;
+    GRT_TRY(output_form(p, cl != NULL ? 2 : 1, NULL, fluxes_dev, &rows));
+    rows.bins = &bins;
+    GRT_TRY(pipeline_run(p, cols, &join, &rows));
     return GRTCODE_SUCCESS;
 }
 
@@ -899,14 +907,15 @@ EXTERN int grt_pipeline_run_band_profiles(GrtPipeline_t *p, GrtColumns_t const *
     }
     GRT_TRY(cl != NULL ? check_clouds(p, cols, cl) : check_columns(p, cols));
     int const sets = cl != NULL ? 2 : 1, V = p->num_levels;
-    BandProfileOut const bp = {.sets = sets, .edges = {lw_edges, sw_edges}, .num_bins = {lw_num_bins, sw_num_bins}};
-    GrtPass const rows = {.profile = 1, .out = band_levels_dev, .bp = &bp,
+    GrtBins const bins = {.edges = {lw_edges, sw_edges}, .num_bins = {lw_num_bins, sw_num_bins}};
+    GrtJoin const join = {.clouds = cl};
+    GrtPass const rows = {.profile = 1, .out = band_levels_dev, .bins = &bins, .sets = sets,
                           .out_stride = sets*2*(lw_num_bins + sw_num_bins)*V};
-    GRT_TRY(pipeline_run(p, cols, cl, NULL, 0, &rows));
+    GRT_TRY(pipeline_run(p, cols, &join, &rows));
     if (band_heating_dev != NULL)
     {
         void *s = grt_dev_stream(p->device);
-        int const slot = grt_profile_begin(s, 14);
+        int const slot = grt_profile_begin(s, GRT_TAG_BAND_PROFILES);
         int const krc = grt_launch_band_profile_finish(s, cols->ncol, sets, V, lw_num_bins, sw_num_bins, GRT_GRAVITY,
                                                        GRT_SPECIFIC_HEAT_AIR, p->small.d + p->off_p, band_levels_dev,
                                                        band_heating_dev);

@@ -238,19 +238,76 @@ int grt_stage_cloud_fields(GrtPipeline_t *p, GrtClouds_t const *cl, GrtCloudSamp
     return GRTCODE_SUCCESS;
 }
 
-/* The interval of the aerosol grid x [na] (strictly increasing) each of the n points w0 + i dw lies in, as
-   interpolate2 (utilities.c:149-222) assigns them: j with x[j] < w <= x[j+1]; -1 for w <= x[0] and for w > x[na-1],
-   which the reference does not write. */
-void grt_aerosol_interval_map(double w0, double dw, uint64_t n, double const *x, int na, int *interval)
+/* ---- piecewise linear on a grid of the caller's own: the aerosol optics and the surface ------------------------------- */
+
+/* One band's input: no points, or at least two strictly increasing ones with values on them.  The messages call it `name`
+   + `kind`, and say what no points stand for (`none`) and what the values are (`what`). */
+int grt_check_grid(char const *name, char const *kind, char const *none, char const *what, int nx, fp_t const *grid,
+                   fp_t const *values)
+{
+    if (nx < 0 || nx == 1)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s%s grid points: 0 (%s) or at least 2.", nx, name, kind, none);
+    }
+    if (nx == 0)
+    {
+        return GRTCODE_SUCCESS;
+    }
+    if (grid == NULL || values == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s%s grid points with a NULL grid or NULL %s.", nx, name, kind, what);
+    }
+    for (int j = 0; j + 1 < nx; ++j)
+    {
+        if (!(grid[j + 1] > grid[j]))
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "%s%s grid not strictly increasing (grid[%d] = %e, grid[%d] = %e).", name, kind, j,
+                     grid[j], j + 1, grid[j + 1]);
+        }
+    }
+    return GRTCODE_SUCCESS;
+}
+
+/* Where each of the n points w0 + i dw lies in the grid x [nx] (strictly increasing), as interpolate2
+   (utilities.c:149-222) assigns them: k = 1 + j with x[j] < w <= x[j+1], 0 for w <= x[0], nx for w > x[nx-1].  ends: the
+   map is k, the two ranges outside the grid being entries of their own (constant_extrapolation, utilities.c:77-92);
+   else it is the interval j, and -1 outside the grid, which the reference does not write there. */
+static void grid_map(double w0, double dw, uint64_t n, double const *x, int nx, int ends, int *map)
 {
     for (uint64_t i = 0; i < n; ++i)
     {
-        double const w = w0 + i*dw;
-        interval[i] = (w <= x[0] || w > x[na - 1]) ? -1 : count_below(x, na, w, 0) - 1;
+        int const k = count_below(x, nx, w0 + i*dw, 0);
+        map[i] = ends ? k : (k == 0 || k == nx ? -1 : k - 1);
     }
 }
 
-/* linear_sample's (utilities.c:235-246) slope and intercept of every interval, layer and property of ncol columns:
+/* linear_sample's (utilities.c:235-246) slope and intercept of the interval from point j to point j + 1 */
+static inline void linear_pair(double const *x, double const *y, size_t j, double *slope, double *intercept)
+{
+    double const m = (y[j + 1] - y[j])/(x[j + 1] - x[j]);
+    double const b = y[j] - m*x[j];
+    *slope = m;
+    *intercept = b;
+}
+
+/* a band's map for the grid x, as grt_keyed_table fills it */
+typedef struct GridMapFill { SpectralGrid_t const *grid; double const *x; int nx, ends; } GridMapFill;
+
+static int fill_grid_map(void *ctx, int *map)
+{
+    GridMapFill const *f = ctx;
+    grid_map(f->grid->w0, f->grid->dw, f->grid->n, f->x, f->nx, f->ends, map);
+    return GRTCODE_SUCCESS;
+}
+
+/* The interval of the aerosol grid x [na] each of the n points lies in: j with x[j] < w <= x[j+1]; -1 for w <= x[0] and
+   for w > x[na-1]. */
+void grt_aerosol_interval_map(double w0, double dw, uint64_t n, double const *x, int na, int *interval)
+{
+    grid_map(w0, dw, n, x, na, 0, interval);
+}
+
+/* the slope and intercept of every interval, layer and property of ncol columns:
    optics [ncol][3][L][na] -> tables [ncol][3][na - 1][2][L] (GrtAerosolArgs) */
 void grt_aerosol_tables(double const *x, int na, int ncol, int num_layers, double const *optics, double *tables)
 {
@@ -262,10 +319,7 @@ void grt_aerosol_tables(double const *x, int na, int ncol, int num_layers, doubl
             double const *y = optics + (cp*L + l)*NA;
             for (size_t j = 0; j < NI; ++j)
             {
-                double const m = (y[j + 1] - y[j])/(x[j + 1] - x[j]);
-                double const b = y[j] - m*x[j];
-                tables[((cp*NI + j)*2 + 0)*L + l] = m;
-                tables[((cp*NI + j)*2 + 1)*L + l] = b;
+                linear_pair(x, y, j, &tables[((cp*NI + j)*2 + 0)*L + l], &tables[((cp*NI + j)*2 + 1)*L + l]);
             }
         }
     }
@@ -301,15 +355,6 @@ int grt_stage_aerosols(GrtPipeline_t *p, GrtAerosols_t const *ae, int C)
     return GRTCODE_SUCCESS;
 }
 
-typedef struct AerosolMapFill { SpectralGrid_t const *grid; double const *x; int na; } AerosolMapFill;
-
-static int fill_aerosol_map(void *ctx, int *interval)
-{
-    AerosolMapFill const *f = ctx;
-    grt_aerosol_interval_map(f->grid->w0, f->grid->dw, f->grid->n, f->x, f->na, interval);
-    return GRTCODE_SUCCESS;
-}
-
 /* the band's aerosol arguments for a batch of C columns staged by grt_stage_aerosols: its per-point intervals are built on
    the host when the band's aerosol grid differs from the last call's */
 int grt_band_aerosols(GrtPipeline_t *p, GrtBand *b, int bi, GrtAerosols_t const *ae, int C, GrtAerosolArgs *aa)
@@ -319,26 +364,21 @@ int grt_band_aerosols(GrtPipeline_t *p, GrtBand *b, int bi, GrtAerosols_t const 
     int const na_lw = p->band[0].gas != NULL ? ae->lw_num_points : 0;
     aa->num_intervals = na - 1;
     aa->tables = p->aer.d + (bi == 1 && na_lw > 0 ? (size_t)C*6*L*((size_t)na_lw - 1) : 0);
-    AerosolMapFill f = {&b->gas->grid, bi == 0 ? ae->lw_grid : ae->sw_grid, na};
-    GRT_TRY(grt_keyed_table(p, &b->aer_map, f.x, sizeof(double)*(size_t)na, b->n, fill_aerosol_map, &f));
+    GridMapFill f = {&b->gas->grid, bi == 0 ? ae->lw_grid : ae->sw_grid, na, 0};
+    GRT_TRY(grt_keyed_table(p, &b->aer_map, f.x, sizeof(double)*(size_t)na, b->n, fill_grid_map, &f));
     aa->interval = b->aer_map.table;
     return GRTCODE_SUCCESS;
 }
 
-/* The entry of the surface grid x [ns] (strictly increasing) each of the n points w0 + i dw takes, as interpolate2 with
-   constant_extrapolation (utilities.c:149-222, :77-92) assigns them: 0 for w <= x[0], 1 + j for x[j] < w <= x[j+1], ns for
+/* The entry of the surface grid x [ns] each of the n points takes: 0 for w <= x[0], 1 + j for x[j] < w <= x[j+1], ns for
    w > x[ns-1]. */
 void grt_surface_entry_map(double w0, double dw, uint64_t n, double const *x, int ns, int *entry)
 {
-    for (uint64_t i = 0; i < n; ++i)
-    {
-        double const w = w0 + i*dw;
-        entry[i] = w <= x[0] ? 0 : (w > x[ns - 1] ? ns : count_below(x, ns, w, 0));
-    }
+    grid_map(w0, dw, n, x, ns, 1, entry);
 }
 
 /* values [ncol][ns] -> tables [ncol][ns + 1][2], slope then intercept: entry 0 the constant y[0] below the grid, entry
-   1 + j linear_sample's (utilities.c:235-246) pair of interval j, entry ns the constant above the grid -- y[ns-2], what
+   1 + j the pair of interval j, entry ns the constant above the grid -- y[ns-2], what
    the reference's extrapolation takes from the last SEGMENT it is handed (utilities.c:215-219).  A constant entry has
    slope 0: 0 w + b is b. */
 void grt_surface_tables(double const *x, int ns, int ncol, double const *values, double *tables)
@@ -352,10 +392,7 @@ void grt_surface_tables(double const *x, int ns, int ncol, double const *values,
         t[1] = y[0];
         for (size_t j = 0; j + 1 < NS; ++j)
         {
-            double const m = (y[j + 1] - y[j])/(x[j + 1] - x[j]);
-            double const b = y[j] - m*x[j];
-            t[(1 + j)*2 + 0] = m;
-            t[(1 + j)*2 + 1] = b;
+            linear_pair(x, y, j, &t[(1 + j)*2 + 0], &t[(1 + j)*2 + 1]);
         }
         t[NS*2 + 0] = 0.;
         t[NS*2 + 1] = y[NS - 2];
@@ -365,28 +402,9 @@ void grt_surface_tables(double const *x, int ns, int ncol, double const *values,
 /* one band's surface inputs: none, or at least two strictly increasing grid points and knot values in [0, 1] */
 static int check_surface_band(char const *name, int ns, int ncol, fp_t const *grid, fp_t const *values, fp_t const *second)
 {
-    if (ns < 0 || ns == 1)
-    {
-        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s grid points: 0 (the creation-time array) or at least 2.", ns, name);
-    }
-    if (ns == 0)
-    {
-        return GRTCODE_SUCCESS;
-    }
-    if (grid == NULL || values == NULL)
-    {
-        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s grid points with a NULL grid or NULL values.", ns, name);
-    }
-    for (int j = 0; j + 1 < ns; ++j)
-    {
-        if (!(grid[j + 1] > grid[j]))
-        {
-            GRT_FAIL(GRTCODE_VALUE_ERR, "%s grid not strictly increasing (grid[%d] = %e, grid[%d] = %e).", name, j, grid[j],
-                     j + 1, grid[j + 1]);
-        }
-    }
+    GRT_TRY(grt_check_grid(name, "", "the creation-time array", "values", ns, grid, values));
     fp_t const *arrays[2] = {values, second};
-    for (int k = 0; k < 2; ++k)
+    for (int k = 0; k < 2 && ns > 0; ++k)
     {
         for (size_t i = 0; arrays[k] != NULL && i < (size_t)ncol*(size_t)ns; ++i)
         {
@@ -415,30 +433,9 @@ int grt_check_surface(GrtPipeline_t const *p, GrtSurface_t const *sf, int np[2])
     return GRTCODE_SUCCESS;
 }
 
-typedef struct SurfaceMapFill { SpectralGrid_t const *grid; double const *x; int ns; } SurfaceMapFill;
-
-static int fill_surface_map(void *ctx, int *entry)
-{
-    SurfaceMapFill const *f = ctx;
-    grt_surface_entry_map(f->grid->w0, f->grid->dw, f->grid->n, f->x, f->ns, entry);
-    return GRTCODE_SUCCESS;
-}
-
-/* [max_cols][n] doubles at *rows, allocated when first needed */
-static int surface_rows(GrtPipeline_t *p, GrtBand const *b, double **rows)
-{
-    if (*rows == NULL)
-    {
-        void *blk = NULL;
-        GRT_TRY(grt_dev_alloc(p->device, &blk, sizeof(double)*(size_t)p->max_cols*b->n));
-        *rows = blk;
-    }
-    return GRTCODE_SUCCESS;
-}
-
 /* A checked surface (grt_check_surface's np) to the device: the columns' slope and intercept entries staged and uploaded,
    each band's per-point entries built on the host when its surface grid differs from the last call's, and one launch per
-   band and array that writes the columns' rows (profile tag 15).  The bands' surf_set / surf_dif_set say what is in
+   band and array that writes the columns' rows (GRT_TAG_SURFACE).  The bands' surf_set / surf_dif_set say what is in
    force afterwards; the caller sets them when this has succeeded. */
 int grt_stage_surface(GrtPipeline_t *p, GrtSurface_t const *sf, int const np[2])
 {
@@ -476,13 +473,13 @@ int grt_stage_surface(GrtPipeline_t *p, GrtSurface_t const *sf, int const np[2])
         }
         GrtBand *b = &p->band[k > 0];
         SpectralGrid_t const *grid = &b->gas->grid;
-        SurfaceMapFill f = {grid, k == 0 ? sf->emissivity_grid : sf->albedo_grid, np[k > 0]};
-        GRT_TRY(grt_keyed_table(p, &b->surf_map, f.x, sizeof(double)*(size_t)f.ns, b->n, fill_surface_map, &f));
-        double **rows = k == 2 ? &b->surf_rows_dif : &b->surf_rows;
-        GRT_TRY(surface_rows(p, b, rows));
-        GrtSurfaceArgs const sa = {f.ns + 1, b->surf_map.table, p->surf.d + off[k]};
-        int const slot = grt_profile_begin(s, 15);
-        int const krc = grt_launch_spread_surface(s, sf->ncol, grid->w0, grid->dw, b->n, &sa, *rows);
+        GridMapFill f = {grid, k == 0 ? sf->emissivity_grid : sf->albedo_grid, np[k > 0], 1};
+        GRT_TRY(grt_keyed_table(p, &b->surf_map, f.x, sizeof(double)*(size_t)f.nx, b->n, fill_grid_map, &f));
+        GrtScratch *rows = &b->scratch[k == 2 ? GRT_SCRATCH_SURF_ROWS_DIF : GRT_SCRATCH_SURF_ROWS];
+        GRT_TRY(grt_scratch_need(p, rows, M*b->n, NULL));
+        GrtSurfaceArgs const sa = {f.nx + 1, b->surf_map.table, p->surf.d + off[k]};
+        int const slot = grt_profile_begin(s, GRT_TAG_SURFACE);
+        int const krc = grt_launch_spread_surface(s, sf->ncol, grid->w0, grid->dw, b->n, &sa, rows->d);
         grt_profile_end(s, slot);
         GRT_TRY(grt_dev_check(krc, "surface row kernel"));
     }
@@ -506,17 +503,6 @@ int grt_band_bins(GrtPipeline_t *p, GrtBand *b, int const *edges, int nbins, int
     GRT_TRY(grt_keyed_table(p, &b->bin_table, edges, sizeof(int)*((size_t)nbins + 1), grt_bin_table_ints(nbins, b->n),
                             fill_bin_table, &f));
     b->bin_per_row = f.per_row;
-    size_t const need = (size_t)rows*b->bin_per_row;
-    if (need > b->bin_cap)
-    {
-        GRT_TRY(grt_dev_sync(p->device, grt_dev_stream(p->device)));
-        grt_dev_free(p->device, b->bin_partials);
-        b->bin_partials = NULL;
-        b->bin_cap = 0;
-        void *pt = NULL;
-        GRT_TRY(grt_dev_alloc(p->device, &pt, sizeof(double)*(size_t)p->max_cols*need));
-        b->bin_partials = pt;
-        b->bin_cap = need;
-    }
+    GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_BIN_PARTIALS], (size_t)p->max_cols*(size_t)rows*b->bin_per_row, NULL));
     return GRTCODE_SUCCESS;
 }

@@ -25,6 +25,38 @@ typedef struct GrtStaging
     void *uploaded;        /* event: h has been copied out and may be refilled */
 } GrtStaging;
 
+/* A device buffer of doubles that a call allocates when it first needs it and replaces when it needs a larger one
+   (grt_scratch_need); every band's are freed by walking them (grt_pipeline_release). */
+typedef struct GrtScratch
+{
+    double *d;
+    size_t doubles;        /* its capacity */
+} GrtScratch;
+
+enum
+{
+    /* fused form, shortwave: [max_cols][2 V + 5 L][n] first-sweep reflectances and layer properties of the two-sweep form
+       (10.8 GB for 64 columns of the 1 cm-1 band), which the level forms share with the two-sweep six-row forms */
+    GRT_SCRATCH_PARK,
+    /* fused form, grt_pipeline_run_profiles (and _allsky_profiles: both passes in turn): [max_cols][2 V][nblocks] */
+    GRT_SCRATCH_LEVEL_PARTIALS,
+    /* materialised form of the all-sky and the aerosol pass (they run in stream order, never in one call): Rayleigh
+       [3][L][n], zeros [L][n], then the spread objects' tau, omega, g [3 objects][max_cols][L][n] (liquid and ice: 6 arrays,
+       aerosol: 3), replaced when a pass needs more arrays */
+    GRT_SCRATCH_SPREAD,
+    /* grt_pipeline_run_spectral's and grt_pipeline_run_band_profiles' partial sums: [max_cols][6 or 2 V][bin_per_row] */
+    GRT_SCRATCH_BIN_PARTIALS,
+    /* grt_pipeline_run_subcolumns, fused form: [max_cols][S][6 or 2 V][nblocks] partial sums of the all-sky pass */
+    GRT_SCRATCH_SUB_PARTIALS,
+    /* ... materialised form: [2][max_cols][V][n] sums of the subcolumns' up and down fluxes */
+    GRT_SCRATCH_FLUX_SUM,
+    /* grt_pipeline_set_surface: the columns' rows [max_cols][n] -- the emissivity (longwave) or the direct albedo
+       (shortwave), and -- shortwave, when a diffuse albedo was given -- the diffuse albedo */
+    GRT_SCRATCH_SURF_ROWS,
+    GRT_SCRATCH_SURF_ROWS_DIF,
+    GRT_SCRATCH_COUNT
+};
+
 typedef struct GrtBand
 {
     GasOptics_t *gas;
@@ -37,39 +69,25 @@ typedef struct GrtBand
     double **rows_d;       /* [cols][6] device row pointers for the trapezoid */
     double *zero_row;      /* [n] zeros: stands in for the user level when there is none */
     /* fused form (no spectra kept): */
-    double *park;          /* shortwave: [cols][2 V + 5 L][n] first-sweep reflectances and layer properties */
     double *partials;      /* [cols][6][nblocks] trapezoid partial sums */
     unsigned nblocks;
-    /* grt_pipeline_run_profiles (and _allsky_profiles: both passes in turn), allocated at the first call: */
-    double *level_partials;        /* fused form: [cols][2 V][nblocks] */
-    double **level_rows_d;         /* materialised form: [cols][2 V] device row pointers (up levels, then down levels) */
+    /* grt_pipeline_run_profiles (and _allsky_profiles), materialised form, allocated at the first call: [cols][2 V] device
+       row pointers (up levels, then down levels) */
+    double **level_rows_d;
+    GrtScratch scratch[GRT_SCRATCH_COUNT];     /* what the calls allocate on demand (GRT_SCRATCH_...) */
     /* grt_pipeline_run_allsky (and _allsky_profiles): [2][n] cloud band of each grid point (liquid, ice), -1: none; its key:
        the band limits (B, num_ice_bands, liquid lo/hi, ice lo/hi) */
     GrtKeyedTable cloud_map;
     /* grt_pipeline_run_aerosols: [n] interval of the band's aerosol grid each grid point lies in, -1: none; its key: that
        grid */
     GrtKeyedTable aer_map;
-    /* materialised form of the all-sky and the aerosol pass (they run in stream order, never in one call): Rayleigh
-       [3][L][n], zeros [L][n], then the spread objects' tau, omega, g [spread_arrays][max_cols][L][n] (liquid and ice: 6,
-       aerosol: 3), grown when a pass needs more arrays */
-    double *spread_block;
-    int spread_arrays;
     /* grt_pipeline_run_spectral's and grt_pipeline_run_band_profiles' bins (they run in stream order): grt_bin_table of
        the edges [bin_count + 1] (its key) */
     GrtKeyedTable bin_table;
     size_t bin_per_row;    /* partial sums per row */
-    double *bin_partials;  /* [max_cols][6 or 2 V][bin_per_row] */
-    size_t bin_cap;        /* its doubles per column */
-    /* grt_pipeline_run_subcolumns, allocated at the first call that needs them (or more of them): */
-    double *sub_partials;  /* fused form: [max_cols][S][6 or 2 V][nblocks] partial sums of the all-sky pass */
-    size_t sub_cap;        /* its doubles */
-    double *flux_sum;      /* materialised form: [2][max_cols][V][n] sums of the subcolumns' up and down fluxes */
     /* grt_pipeline_set_surface: [n] entry of the band's surface grid each grid point takes (grt_surface_entry_map); its key:
        that grid */
     GrtKeyedTable surf_map;
-    /* ... and the columns' rows [max_cols][n], allocated at the first call that sets them: the emissivity (longwave) or
-       the direct albedo (shortwave), and -- shortwave, when a diffuse albedo was given -- the diffuse albedo */
-    double *surf_rows, *surf_rows_dif;
     int surf_set, surf_dif_set;    /* the surface in force gives this band rows (, and diffuse rows of their own) */
 } GrtBand;
 
@@ -94,29 +112,22 @@ struct GrtPipeline
     int surface_ncol;      /* columns of the surface in force; 0: none (the creation-time arrays apply) */
 };
 
-/* grt_pipeline_run_spectral's outputs: the spectral rows and bins of `sets` sets per column */
-typedef struct SpectralOut
+/* The bins of a run, per band.  Of a six-row run (grt_pipeline_run_spectral): with the six rows at every point, to
+   spectral, and their bins, to binned; of a profile run (grt_pipeline_run_band_profiles): every level's flux per bin, the
+   run's output. */
+typedef struct GrtBins
 {
-    double *spectral, *binned;
-    int sets;
+    double *spectral, *binned;     /* the six-row run's */
     int const *edges[2];
     int num_bins[2];
-} SpectralOut;
-
-/* grt_pipeline_run_band_profiles' bins: every level's flux of `sets` sets per column, per bin of the band's edges */
-typedef struct BandProfileOut
-{
-    int sets;
-    int const *edges[2];
-    int num_bins[2];
-} BandProfileOut;
+} GrtBins;
 
 /* One solve of a band on the run's tau_gas.  What joins gas and Rayleigh: nothing (clear sky), the cloud objects (all-sky
    pass) or the aerosol object (aerosol pass; aer NULL there: a band that was given no aerosol, which runs the clear-sky
    form under the aerosol pass's profile tags).  Which rows leave: the six of driver.c:272-280 or (profile) every level's
-   up then down flux, to set `set` of the column's out_stride doubles at out; with so, the six rows at every point and
-   their bins too (grt_pipeline_run_spectral); with bp (profile), every level's flux per bin of bp's edges instead, to
-   out's [ncol][sets][2 lw bins + 2 sw bins][V] (grt_pipeline_run_band_profiles). */
+   up then down flux, to set `set` of the `sets` in the column's out_stride doubles at out; with bins, the six rows at
+   every point and their bins too (grt_pipeline_run_spectral) or (profile) every level's flux per bin of the edges
+   instead, to out's [ncol][sets][2 lw bins + 2 sw bins][V] (grt_pipeline_run_band_profiles). */
 typedef struct GrtPass
 {
     GrtCloudArgs const *clouds;
@@ -127,9 +138,9 @@ typedef struct GrtPass
     GrtContinua const *continua;
     double *out;
     int out_stride;
+    int sets;
     int set;                       /* 0: the clear-sky set; 1: the all-sky or aerosol set that follows it */
-    SpectralOut const *so;
-    BandProfileOut const *bp;
+    GrtBins const *bins;
 } GrtPass;
 
 /* the doubles from a column's clear-sky set to its all-sky or aerosol set */
@@ -143,7 +154,9 @@ static inline int grt_aerosol_points(GrtAerosols_t const *ae, int bi)
     return bi == 0 ? ae->lw_num_points : ae->sw_num_points;
 }
 
-/* grt_pipeline.c: the row-pointer table rows_h [n] (integrate_rows' rows) to the device at *rows_d; rows_h is freed */
+/* grt_pipeline.c */
+GRT_PRIVATE int grt_scratch_need(GrtPipeline_t *p, GrtScratch *buf, size_t doubles, int *fresh);
+/* the row-pointer table rows_h [n] (integrate_rows' rows) to the device at *rows_d; rows_h is freed */
 GRT_PRIVATE int grt_upload_rows(GrtPipeline_t *p, double **rows_h, size_t n, double ***rows_d);
 
 /* grt_pipeline_inputs.c */
@@ -157,6 +170,8 @@ GRT_PRIVATE int grt_stage_cloud_fields(GrtPipeline_t *p, GrtClouds_t const *cl, 
 GRT_PRIVATE int grt_band_clouds(GrtPipeline_t *p, GrtBand *b, int bi, GrtClouds_t const *cl, int C, int S, GrtCloudArgs *ca);
 GRT_PRIVATE int grt_stage_aerosols(GrtPipeline_t *p, GrtAerosols_t const *ae, int C);
 GRT_PRIVATE int grt_band_aerosols(GrtPipeline_t *p, GrtBand *b, int bi, GrtAerosols_t const *ae, int C, GrtAerosolArgs *aa);
+GRT_PRIVATE int grt_check_grid(char const *name, char const *kind, char const *none, char const *what, int nx,
+                               fp_t const *grid, fp_t const *values);
 GRT_PRIVATE int grt_check_surface(GrtPipeline_t const *p, GrtSurface_t const *sf, int np[2]);
 GRT_PRIVATE int grt_stage_surface(GrtPipeline_t *p, GrtSurface_t const *sf, int const np[2]);
 GRT_PRIVATE int grt_band_bins(GrtPipeline_t *p, GrtBand *b, int const *edges, int nbins, int rows);

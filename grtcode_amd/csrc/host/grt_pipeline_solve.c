@@ -5,10 +5,18 @@
 #include <string.h>
 #include "grt_pipeline_internal.h"
 
-/* the profile tag its solver is timed under: 3 / 4, or 8 / 9 with clouds, or 12 / 13 in the aerosol pass */
+/* the profile tag its solver is timed under */
 static int pass_tag(GrtPass const *ps, int bi)
 {
-    return (ps->aer_pass ? 12 : (ps->clouds ? 8 : 3)) + bi;
+    static int const tag[3][2] = {{GRT_TAG_SOLVER_LW, GRT_TAG_SOLVER_SW}, {GRT_TAG_ALLSKY_LW, GRT_TAG_ALLSKY_SW},
+                                  {GRT_TAG_AEROSOL_LW, GRT_TAG_AEROSOL_SW}};
+    return tag[ps->aer_pass ? 2 : (ps->clouds != NULL)][bi];
+}
+
+/* the six rows at every point leave too (grt_pipeline_run_spectral) */
+static int pass_spectral(GrtPass const *ps)
+{
+    return ps->bins != NULL && !ps->profile;
 }
 
 /* its solver instance (materialised: the spectral form, after pass_optics); bn: its per-bin instance; sc: the pass's
@@ -19,7 +27,7 @@ static GrtSolverInstance pass_instance(GrtPipeline_t const *p, GrtPass const *ps
     GrtSolverInstance in = {GRT_OUT_CHAINS, NULL, NULL, NULL, NULL};
     if (!p->keep_spectra)
     {
-        in.out = ps->so != NULL ? GRT_OUT_ROWS_POINTS : (bn != NULL ? GRT_OUT_LEVEL_BINS :
+        in.out = pass_spectral(ps) ? GRT_OUT_ROWS_POINTS : (bn != NULL ? GRT_OUT_LEVEL_BINS :
                  (ps->profile ? GRT_OUT_LEVELS : GRT_OUT_ROWS));
         in.clouds = sc != NULL ? NULL : ps->clouds;
         in.aerosols = ps->aer;
@@ -40,18 +48,24 @@ static int pass_offset(GrtPipeline_t const *p, GrtPass const *ps, int bi)
     return ps->set*grt_set_offset(p, ps->profile) + bi*pass_rows(p, ps);
 }
 
-/* where band bi's six spectral rows (or bins, per = bins) of column 0 start in a [ncol][sets][6 per_lw + 6 per_sw]
-   block, and the doubles from one column to the next */
-static size_t spectral_offset(GrtPass const *ps, int bi, size_t per_lw, size_t per_sw, size_t *col_stride)
-{
-    size_t const set_doubles = 6*(per_lw + per_sw);
-    *col_stride = (size_t)ps->so->sets*set_doubles;
-    return (size_t)ps->set*set_doubles + (bi == 1 ? 6*per_lw : 0);
-}
-
 static size_t band_points(GrtPipeline_t const *p, int bi)
 {
     return p->band[bi].gas != NULL ? p->band[bi].n : 0;
+}
+
+/* where band bi's rows of the pass's set and column 0 start in a [ncol][sets][rows (per_lw + per_sw)] block -- rows: 6 or
+   2 V; per: the bands' grid points, or their bins --, and the doubles from one column to the next */
+static size_t bins_offset(GrtPass const *ps, int bi, size_t rows, size_t per_lw, size_t per_sw, size_t *col_stride)
+{
+    size_t const set_doubles = rows*(per_lw + per_sw);
+    *col_stride = (size_t)ps->sets*set_doubles;
+    return (size_t)ps->set*set_doubles + (bi == 1 ? rows*per_lw : 0);
+}
+
+/* ... of the six rows at every point (pass_spectral) */
+static double *spectral_rows(GrtPipeline_t const *p, GrtPass const *ps, int bi, size_t *col_stride)
+{
+    return ps->bins->spectral + bins_offset(ps, bi, GRT_FLUXES_PER_BAND, band_points(p, 0), band_points(p, 1), col_stride);
 }
 
 /* The solvers' arguments.  Fused forms: Rayleigh, add_optics({gas, rayleigh}) and the solver in one launch (driver.c:268,
@@ -69,7 +83,7 @@ static void lw_args(GrtPipeline_t const *p, GrtBand const *b, int C, int fused, 
     a->emis = p->emis_d; a->emis_stride = 0;
     if (b->surf_set)
     {
-        a->emis = b->surf_rows; a->emis_stride = b->n;          /* grt_pipeline_set_surface: driver.c:101-107 */
+        a->emis = b->scratch[GRT_SCRATCH_SURF_ROWS].d; a->emis_stride = b->n;          /* grt_pipeline_set_surface: driver.c:101-107 */
     }
     a->user_level = p->user_level;
     if (fused)
@@ -97,7 +111,9 @@ static void sw_args(GrtPipeline_t const *p, GrtBand const *b, int C, int fused, 
     if (b->surf_set)
     {
         /* grt_pipeline_set_surface: driver.c:111-117 */
-        a->alb_dir = b->surf_rows; a->alb_dif = b->surf_dif_set ? b->surf_rows_dif : b->surf_rows; a->alb_stride = b->n;
+        a->alb_dir = b->scratch[GRT_SCRATCH_SURF_ROWS].d;
+        a->alb_dif = b->scratch[b->surf_dif_set ? GRT_SCRATCH_SURF_ROWS_DIF : GRT_SCRATCH_SURF_ROWS].d;
+        a->alb_stride = b->n;
     }
     a->tsi = p->small.d + p->off_tsi; a->solar = p->solar_d;
     a->user_level = p->user_level;
@@ -117,31 +133,17 @@ static void sw_args(GrtPipeline_t const *p, GrtBand const *b, int C, int fused, 
     }
 }
 
-/* the shortwave solver's two-sweep form: reflectances of 2 V levels and five properties of L layers per column and
-   wavenumber, allocated at the first launch that needs them */
-static int park_block(GrtPipeline_t *p, GrtBand *b)
-{
-    if (b->park == NULL)
-    {
-        size_t const V = (size_t)p->num_levels;
-        void *pk = NULL;
-        GRT_TRY(grt_dev_alloc(p->device, &pk, sizeof(double)*(size_t)p->max_cols*(2*V + 5*(V - 1))*b->n));
-        b->park = pk;
-    }
-    return GRTCODE_SUCCESS;
-}
-
 /* The arguments of the band's solver in the instance in, in whichever of the two structs is the band's: the partial sums,
-   where the six rows at every point go (the pass's so), and the shortwave's park block, which the level forms share with
-   the two-sweep six-row forms (the passes run in stream order) */
+   where the six rows at every point go, and the shortwave's park block (the two-sweep form: reflectances of 2 V levels
+   and five properties of L layers per column and wavenumber), which the level forms share with the two-sweep six-row
+   forms (the passes run in stream order) */
 typedef struct SolverArgs { GrtLwArgs lw; GrtSwArgs sw; } SolverArgs;
 
 static int solver_args(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps, GrtSolverInstance const *in,
                        double *partials, SolverArgs *a)
 {
     size_t stride = 0;
-    double *rows = in->out == GRT_OUT_ROWS_POINTS
-                       ? ps->so->spectral + spectral_offset(ps, bi, band_points(p, 0), band_points(p, 1), &stride) : NULL;
+    double *rows = in->out == GRT_OUT_ROWS_POINTS ? spectral_rows(p, ps, bi, &stride) : NULL;
     if (bi == 0)
     {
         lw_args(p, b, C, grt_out_fused(in->out), ps, &a->lw);
@@ -164,9 +166,10 @@ static int solver_args(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass cons
     }
     if (grt_sw_parks(in, &a->sw))
     {
-        GRT_TRY(park_block(p, b));
+        size_t const V = (size_t)p->num_levels;
+        GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_PARK], (size_t)p->max_cols*(2*V + 5*(V - 1))*b->n, NULL));
     }
-    a->sw.park = b->park;
+    a->sw.park = b->scratch[GRT_SCRATCH_PARK].d;
     return GRTCODE_SUCCESS;
 }
 
@@ -195,7 +198,7 @@ static int clear_sky_optics(GrtPipeline_t *p, GrtBand *b, int C)
 {
     SpectralGrid_t const *grid = &b->gas->grid;
     void *s = grt_dev_stream(p->device);
-    int const slot = grt_profile_begin(s, 5);
+    int const slot = grt_profile_begin(s, GRT_TAG_CLEAR_OPTICS);
     int const krc = grt_launch_clear_sky_optics(s, p->num_levels - 1, C, grid->w0, grid->dw, b->n, p->small.d + p->off_n,
                                                 b->tau_gas, b->tau, b->omega, b->g);
     grt_profile_end(s, slot);
@@ -211,20 +214,14 @@ static int spread_optics(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *ps)
     int const L = p->num_levels - 1, objects = ps->aer != NULL ? 1 : 2;
     uint64_t const per = (uint64_t)L*b->n, all = per*(uint64_t)p->max_cols;
     void *s = grt_dev_stream(p->device);
-    if (3*objects > b->spread_arrays)
+    GrtScratch *block = &b->scratch[GRT_SCRATCH_SPREAD];
+    int fresh;
+    GRT_TRY(grt_scratch_need(p, block, 4*per + 3*objects*all, &fresh));
+    if (fresh)
     {
-        /* (the other pass's kernels of an earlier call may still read the smaller block) */
-        GRT_TRY(grt_dev_sync(p->device, s));
-        grt_dev_free(p->device, b->spread_block);
-        b->spread_block = NULL;
-        b->spread_arrays = 0;
-        void *blk = NULL;
-        GRT_TRY(grt_dev_alloc(p->device, &blk, sizeof(double)*(4*per + 3*objects*all)));
-        b->spread_block = blk;
-        b->spread_arrays = 3*objects;
-        GRT_TRY(grt_dev_zero(p->device, b->spread_block + 3*per, sizeof(double)*per, s));
+        GRT_TRY(grt_dev_zero(p->device, block->d + 3*per, sizeof(double)*per, s));
     }
-    double *ray = b->spread_block, *zero = ray + 3*per, *x[6];
+    double *ray = block->d, *zero = ray + 3*per, *x[6];
     for (int k = 0; k < 3*objects; ++k)
     {
         x[k] = zero + per + k*all;
@@ -309,14 +306,14 @@ static int integrate_rows(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass c
 /* One solve of a band for grt_pipeline_run_spectral: the six rows at every point into the caller's spectral block, the
    -integrated six into out, and the bins.  Fused form: the spectral six-row solver (its rows stored where it weights
    them) and the fixed-order sum of its partial sums; materialised form: the spectral solver, its rows 0, L and the user
-   level copied out, the row-wise trapezoid.  The bins are summed from the stored rows by the binning kernel (profile
-   tag 10). */
+   level copied out, the row-wise trapezoid.  The bins are summed from the stored rows by the binning kernel
+   (GRT_TAG_BINS). */
 static int band_solve_spectral(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps)
 {
     void *s = grt_dev_stream(p->device);
-    SpectralOut const *so = ps->so;
+    GrtBins const *so = ps->bins;
     size_t stride;
-    double *rows = so->spectral + spectral_offset(ps, bi, band_points(p, 0), band_points(p, 1), &stride);
+    double *rows = spectral_rows(p, ps, bi, &stride);
     if (!p->keep_spectra)
     {
         GRT_TRY(band_solver(p, b, bi, C, ps, b->partials, NULL));
@@ -337,10 +334,12 @@ static int band_solve_spectral(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtP
     {
         GRT_TRY(grt_band_bins(p, b, so->edges[bi], nbins, GRT_FLUXES_PER_BAND));
         size_t bstride;
-        double *binned = so->binned + spectral_offset(ps, bi, (size_t)so->num_bins[0], (size_t)so->num_bins[1], &bstride);
-        int const slot = grt_profile_begin(s, 10);
+        double *binned = so->binned + bins_offset(ps, bi, GRT_FLUXES_PER_BAND, (size_t)so->num_bins[0],
+                                                  (size_t)so->num_bins[1], &bstride);
+        int const slot = grt_profile_begin(s, GRT_TAG_BINS);
         int const krc = grt_launch_bin_rows(s, rows, stride, C*GRT_FLUXES_PER_BAND, b->n, b->gas->grid.dw, nbins,
-                                            b->bin_table.table, b->bin_per_row, b->bin_partials, binned, bstride);
+                                            b->bin_table.table, b->bin_per_row, b->scratch[GRT_SCRATCH_BIN_PARTIALS].d, binned,
+                                            bstride);
         grt_profile_end(s, slot);
         GRT_TRY(grt_dev_check(krc, "spectral binning kernel"));
     }
@@ -350,33 +349,33 @@ static int band_solve_spectral(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtP
 /* One solve of a band for grt_pipeline_run_band_profiles: every level's up and down flux per bin of the band's edges,
    into the band's [2][bins][V] of the pass's set.  Fused form: the banded instance of the profile solver, whose partial
    sums lie where the bin table places them, and each bin's blocks added in a fixed order; materialised form: the
-   spectral solver, then the binning kernel on its 2 V flux rows per column.  The reduction counts under profile tag 14. */
+   spectral solver, then the binning kernel on its 2 V flux rows per column.  The reduction counts under
+   GRT_TAG_BAND_PROFILES. */
 static int band_solve_band_profiles(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps)
 {
-    BandProfileOut const *bp = ps->bp;
+    GrtBins const *bp = ps->bins;
     void *s = grt_dev_stream(p->device);
     int const V = p->num_levels, rows = 2*V, nbins = bp->num_bins[bi];
-    size_t const set_doubles = 2*((size_t)bp->num_bins[0] + (size_t)bp->num_bins[1])*(size_t)V;
-    double *out = ps->out + (size_t)ps->set*set_doubles + (bi == 1 ? 2*(size_t)bp->num_bins[0]*(size_t)V : 0);
-    uint64_t const out_stride = (uint64_t)bp->sets*set_doubles;
+    size_t out_stride;
+    double *out = ps->out + bins_offset(ps, bi, (size_t)rows, (size_t)bp->num_bins[0], (size_t)bp->num_bins[1], &out_stride);
     GRT_TRY(grt_band_bins(p, b, bp->edges[bi], nbins, rows));
+    double *bin_partials = b->scratch[GRT_SCRATCH_BIN_PARTIALS].d;
     int slot, krc;
     if (!p->keep_spectra)
     {
         GrtBandArgs const bn = {nbins, grt_bin_block_max(bp->edges[bi], nbins), b->bin_table.table, b->bin_per_row};
-        GRT_TRY(band_solver(p, b, bi, C, ps, b->bin_partials, &bn));
-        slot = grt_profile_begin(s, 14);
-        krc = grt_launch_bin_reduce(s, C*rows, V, nbins, b->bin_table.table, b->bin_per_row, b->bin_partials, out,
-                                    out_stride);
+        GRT_TRY(band_solver(p, b, bi, C, ps, bin_partials, &bn));
+        slot = grt_profile_begin(s, GRT_TAG_BAND_PROFILES);
+        krc = grt_launch_bin_reduce(s, C*rows, V, nbins, b->bin_table.table, b->bin_per_row, bin_partials, out, out_stride);
     }
     else
     {
         GRT_TRY(pass_optics(p, b, C, ps));
         GRT_TRY(band_solver(p, b, bi, C, ps, NULL, NULL));
         GRT_TRY(level_rows(p, b));
-        slot = grt_profile_begin(s, 14);
+        slot = grt_profile_begin(s, GRT_TAG_BAND_PROFILES);
         krc = grt_launch_bin_level_rows(s, (double const *const *)b->level_rows_d, C*rows, V, b->n, b->gas->grid.dw, nbins,
-                                        b->bin_table.table, b->bin_per_row, b->bin_partials, out, out_stride);
+                                        b->bin_table.table, b->bin_per_row, bin_partials, out, out_stride);
     }
     grt_profile_end(s, slot);
     GRT_TRY(grt_dev_check(krc, "level binning kernel"));
@@ -390,14 +389,9 @@ static int band_solve_band_profiles(GrtPipeline_t *p, GrtBand *b, int bi, int C,
    omega, g and the spectral fluxes in the band's arrays, then the row-wise trapezoid. */
 int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps)
 {
-    if (ps->so != NULL)
+    if (ps->bins != NULL)
     {
-        GRT_TRY(band_solve_spectral(p, b, bi, C, ps));
-        return GRTCODE_SUCCESS;
-    }
-    if (ps->bp != NULL)
-    {
-        GRT_TRY(band_solve_band_profiles(p, b, bi, C, ps));
+        GRT_TRY(ps->profile ? band_solve_band_profiles(p, b, bi, C, ps) : band_solve_spectral(p, b, bi, C, ps));
         return GRTCODE_SUCCESS;
     }
     if (p->keep_spectra)
@@ -408,13 +402,12 @@ int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *p
         return GRTCODE_SUCCESS;
     }
     int const rows = pass_rows(p, ps);
-    if (ps->profile && b->level_partials == NULL)
+    if (ps->profile)
     {
-        void *lp = NULL;
-        GRT_TRY(grt_dev_alloc(p->device, &lp, sizeof(double)*(size_t)p->max_cols*(size_t)rows*b->nblocks));
-        b->level_partials = lp;
+        GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_LEVEL_PARTIALS], (size_t)p->max_cols*(size_t)rows*b->nblocks,
+                                 NULL));
     }
-    double *partials = ps->profile ? b->level_partials : b->partials;
+    double *partials = ps->profile ? b->scratch[GRT_SCRATCH_LEVEL_PARTIALS].d : b->partials;
     GRT_TRY(band_solver(p, b, bi, C, ps, partials, NULL));
     GRT_TRY(grt_dev_check(grt_launch_reduce_partials(grt_dev_stream(p->device), partials, C*rows, b->nblocks, ps->out, rows,
                                                      ps->out_stride, pass_offset(p, ps, bi)), "flux reduction kernel"));
@@ -424,7 +417,7 @@ int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *p
 /* The all-sky pass of grt_pipeline_run_subcolumns for one band, S subcolumns of every column on this run's tau_gas
    (driver.c:503-589), its mean rows to out as grt_band_solve writes them.  ps->clouds: the band's tables staged
    subcolumn-major.  Fused form: the subcolumn instance of the all-sky solver over C x S grid rows, each subcolumn's
-   partial sums in sub_partials, then their fixed-order mean (profile tag 11; S = 1: the fixed-order sum of
+   partial sums in sub_partials, then their fixed-order mean (GRT_TAG_SUBCOLUMN_MEAN; S = 1: the fixed-order sum of
    grt_band_solve).  The shortwave's two-sweep forms park C x count columns at a time in the band's park block, count =
    what fits in its max_cols, in stream order.  Materialised form: per subcolumn the all-sky optics, the spectral solver
    and the sum of its fluxes; then the mean into the band's flux arrays, and the row-wise trapezoid. */
@@ -434,23 +427,14 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
     void *s = grt_dev_stream(p->device);
     if (!p->keep_spectra)
     {
-        size_t const need = (size_t)p->max_cols*(size_t)S*(size_t)rows*b->nblocks;
-        if (need > b->sub_cap)
-        {
-            GRT_TRY(grt_dev_sync(p->device, s));
-            grt_dev_free(p->device, b->sub_partials);
-            b->sub_partials = NULL;
-            b->sub_cap = 0;
-            void *sp = NULL;
-            GRT_TRY(grt_dev_alloc(p->device, &sp, sizeof(double)*need));
-            b->sub_partials = sp;
-            b->sub_cap = need;
-        }
+        GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_SUB_PARTIALS],
+                                 (size_t)p->max_cols*(size_t)S*(size_t)rows*b->nblocks, NULL));
+        double *sub_partials = b->scratch[GRT_SCRATCH_SUB_PARTIALS].d;
         /* (in points at sc: the loop below walks sc.first and sc.count, which the launcher alone reads) */
         GrtSubcolumnArgs sc = {*ps->clouds, S, 0, 0};
         GrtSolverInstance const in = pass_instance(p, ps, NULL, &sc);
         SolverArgs a;
-        GRT_TRY(solver_args(p, b, bi, C, ps, &in, b->sub_partials, &a));
+        GRT_TRY(solver_args(p, b, bi, C, ps, &in, sub_partials, &a));
         /* (grid rows; a park block of max_cols columns) */
         int group = bi == 1 && grt_sw_parks(&in, &a.sw) ? p->max_cols/C : 65535/C;
         group = group < S ? group : S;
@@ -465,12 +449,12 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
         GRT_TRY(grt_dev_check(krc, bi == 0 ? "longwave subcolumn kernel" : "shortwave subcolumn kernel"));
         if (S == 1)
         {
-            GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, b->sub_partials, C*rows, b->nblocks, ps->out, rows,
+            GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, sub_partials, C*rows, b->nblocks, ps->out, rows,
                                                              ps->out_stride, out_offset), "flux reduction kernel"));
             return GRTCODE_SUCCESS;
         }
-        int const mslot = grt_profile_begin(s, 11);
-        int const mrc = grt_launch_subcolumn_mean(s, b->sub_partials, C, S, rows, b->nblocks, ps->out, ps->out_stride,
+        int const mslot = grt_profile_begin(s, GRT_TAG_SUBCOLUMN_MEAN);
+        int const mrc = grt_launch_subcolumn_mean(s, sub_partials, C, S, rows, b->nblocks, ps->out, ps->out_stride,
                                                   out_offset);
         grt_profile_end(s, mslot);
         GRT_TRY(grt_dev_check(mrc, "subcolumn mean kernel"));
@@ -478,12 +462,8 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
     }
     size_t const tab = (size_t)C*3*(size_t)ps->clouds->num_bands*(size_t)(V - 1);
     uint64_t const per = (uint64_t)C*(uint64_t)V*b->n, all = (uint64_t)p->max_cols*(uint64_t)V*b->n;
-    if (b->flux_sum == NULL)
-    {
-        void *fs = NULL;
-        GRT_TRY(grt_dev_alloc(p->device, &fs, sizeof(double)*2*all));
-        b->flux_sum = fs;
-    }
+    GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_FLUX_SUM], 2*all, NULL));
+    double *flux_sum = b->scratch[GRT_SCRATCH_FLUX_SUM].d;
     for (int j = 0; j < S; ++j)
     {
         GrtCloudArgs cj = *ps->clouds;
@@ -493,12 +473,12 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
         pj.clouds = &cj;
         GRT_TRY(pass_optics(p, b, C, &pj));
         GRT_TRY(band_solver(p, b, bi, C, &pj, NULL, NULL));
-        GRT_TRY(grt_dev_check(grt_launch_flux_accumulate(s, per, b->flux_up, b->flux_sum, j == 0), "flux sum kernel"));
-        GRT_TRY(grt_dev_check(grt_launch_flux_accumulate(s, per, b->flux_down, b->flux_sum + all, j == 0),
+        GRT_TRY(grt_dev_check(grt_launch_flux_accumulate(s, per, b->flux_up, flux_sum, j == 0), "flux sum kernel"));
+        GRT_TRY(grt_dev_check(grt_launch_flux_accumulate(s, per, b->flux_down, flux_sum + all, j == 0),
                               "flux sum kernel"));
     }
-    GRT_TRY(grt_dev_check(grt_launch_flux_mean(s, per, b->flux_sum, S, b->flux_up), "flux mean kernel"));
-    GRT_TRY(grt_dev_check(grt_launch_flux_mean(s, per, b->flux_sum + all, S, b->flux_down), "flux mean kernel"));
+    GRT_TRY(grt_dev_check(grt_launch_flux_mean(s, per, flux_sum, S, b->flux_up), "flux mean kernel"));
+    GRT_TRY(grt_dev_check(grt_launch_flux_mean(s, per, flux_sum + all, S, b->flux_down), "flux mean kernel"));
     GRT_TRY(integrate_rows(p, b, bi, C, ps));
     return GRTCODE_SUCCESS;
 }

@@ -205,7 +205,7 @@ typedef struct GrtClouds
 /* fluxes_dev [ncol][GRT_ALLSKY_FLUXES_PER_COLUMN] (DEVICE memory): values 0-11 are exactly what grt_pipeline_run writes,
    values 12-23 the all-sky set in the same order.  Same solvers, surface inputs, user level and shortwave sweep rule as
    grt_pipeline_run.  The production form (keep_spectra = 0) forms the cloud terms in the solver kernels from the band
-   tables (profile tags 8 and 9); the materialised form spreads them into [ncol][L][n] arrays, adds the four objects with
+   tables (GRT_TAG_ALLSKY_LW and _SW); the materialised form spreads them into [ncol][L][n] arrays, adds the four objects with
    add_optics' kernel and runs the spectral solvers: afterwards grt_pipeline_views shows the all-sky pass's tau, omega, g
    and fluxes.  GRTCODE_VALUE_ERR, with nothing launched, for: clouds NULL, num_liquid_bands < 1, num_ice_bands <
    num_liquid_bands, a NULL array (the band limits, thickness and the two sets of each band the pipeline has), ncol outside
@@ -228,7 +228,7 @@ EXTERN int grt_pipeline_run_allsky(GrtPipeline_t *pipeline, GrtColumns_t const *
  * band maps, tables and subcolumn rule are grt_pipeline_run_allsky's; the shortwave always takes the reference's two
  * sweeps, as grt_pipeline_run_profiles does; a band whose gas-optics object is NULL gives zero rows.  The production form
  * (keep_spectra = 0) solves the all-sky pass in the profile form of the solvers with the cloud objects formed inside
- * (profile tags 8 and 9); its partial sums, park block and cloud buffers are those grt_pipeline_run_profiles and
+ * (GRT_TAG_ALLSKY_LW and _SW); its partial sums, park block and cloud buffers are those grt_pipeline_run_profiles and
  * grt_pipeline_run_allsky allocate, shared by the two passes in stream order.  keep_spectra = 1: the spectra of both
  * passes, integrated row by row; afterwards grt_pipeline_views shows the all-sky pass.  In the deterministic mode the
  * clear-sky set is, bit for bit, grt_pipeline_run_profiles', and rows 0, L and the user level of the all-sky set are
@@ -260,8 +260,8 @@ EXTERN int grt_pipeline_run_allsky_profiles(GrtPipeline_t *pipeline, GrtColumns_
  * order: per subcolumn the blocks as the other entry points add them, then the subcolumns s = 0 .. S - 1, then one
  * division by S; with S = 1 every value is, bit for bit, grt_pipeline_run_allsky's or grt_pipeline_run_allsky_profiles'.
  * The production form (keep_spectra = 0) solves all S subcolumns of a band in one launch of the subcolumn instance of the
- * all-sky solver (profile tags 8 / 9; the shortwave's two-sweep forms in as many launches as the park block of
- * max_columns columns needs) and reduces with a deterministic kernel (profile tag 11); it allocates per band
+ * all-sky solver (GRT_TAG_ALLSKY_LW / _SW; the shortwave's two-sweep forms in as many launches as the park block of
+ * max_columns columns needs) and reduces with a deterministic kernel (GRT_TAG_SUBCOLUMN_MEAN); it allocates per band
  * [max_columns][S][6 or 2 V][blocks] partial sums at the first call that needs more than it holds, and no larger park
  * block.  keep_spectra = 1: driver.c's loop literally -- per subcolumn the all-sky optics, the spectral solver and the
  * sum of its fluxes; afterwards grt_pipeline_views shows the last subcolumn's tau, omega, g and the mean fluxes.
@@ -335,7 +335,7 @@ typedef struct GrtCloudFields
 
 /* tables_dev (DEVICE memory) [4][S][ncol][3][B][L]: the sets lw_liquid, lw_ice, sw_liquid, sw_ice, each subcolumn-major
    with extinction m-1, single-scattering albedo and asymmetry per liquid band and layer -- what grt_pipeline_run_subcolumns
-   leaves on the device after the thickness block.  One kernel (profile tag 16), one wavefront per sample; asynchronous on
+   leaves on the device after the thickness block.  One kernel (GRT_TAG_CLOUD_SAMPLER), one wavefront per sample; asynchronous on
    the device's current lane (the fields are copied out before the call returns).  GRTCODE_VALUE_ERR, with nothing
    launched and tables_dev untouched, for: a NULL sampler, fields, tables_dev or required array (temperature here); S
    outside 1 .. GRT_MAX_SUBCOLUMNS; ncol or num_layers < 1; a cloud fraction outside [0, 1] or not finite; a content that
@@ -383,7 +383,7 @@ typedef struct GrtAerosols
  *                    and fluxes_dev [ncol][GRT_ALLSKY_FLUXES_PER_COLUMN] (both may be NULL) -- the clear-clean set as
  *                    grt_pipeline_run_profiles writes it, then the aerosol set; the shortwave always takes two sweeps.
  * All DEVICE memory; asynchronous on the pipeline's lane.  The production form (keep_spectra = 0) forms the aerosol
- * object inside the aerosol instances of the fused solvers (profile tags 12 and 13): the host turns each column's
+ * object inside the aerosol instances of the fused solvers (GRT_TAG_AEROSOL_LW and _SW): the host turns each column's
  * [3][L][NA] into slope and intercept tables [3][NA-1][2][L] once (the divisions), a grid point reads its interval once
  * and each layer does six loads and three multiply-adds; nothing spectral is stored.  keep_spectra = 1: driver.c's
  * sequence literally -- the aerosol spread into [ncol][L][n] arrays, add_optics' kernel over the three objects, the
@@ -419,7 +419,7 @@ EXTERN int grt_pipeline_run_aerosols(GrtPipeline_t *pipeline, GrtColumns_t const
  * for that band).  All outputs are DEVICE memory; asynchronous on the pipeline's lane like grt_pipeline_run; the
  * shortwave sweep rule is grt_pipeline_run's.  The production form (keep_spectra = 0) runs the fused six-row solvers in a
  * form that also stores the six rows at every point; the bins are summed from those rows by a deterministic kernel
- * (profile tag 10) in the fused solvers' association, so that a bin {0, n - 1} is, bit for bit, the matching fluxes_dev
+ * (GRT_TAG_BINS) in the fused solvers' association, so that a bin {0, n - 1} is, bit for bit, the matching fluxes_dev
  * value.  keep_spectra = 1: rows 0, L and the user level of the materialised fluxes, the same binning kernel, and
  * fluxes_dev from the row-wise trapezoid.  A new set of edges is uploaded (the call then waits for the lane); the bins'
  * partial sums, [max_columns][6][about num_bins + n/128] doubles per band, are allocated at the first call that needs
@@ -450,7 +450,7 @@ EXTERN int grt_pipeline_run_spectral(GrtPipeline_t *pipeline, GrtColumns_t const
  * value with the trapezoid weight of each bin it belongs to, a workgroup that lies inside one bin does the profile form's
  * work, one that holds bin edges sums each level once per bin it holds; the partial sums, [max_columns][2 V][about
  * num_bins + n/128] doubles per band (allocated at the first call that needs them, shared with
- * grt_pipeline_run_spectral's), are added per bin in a fixed order (profile tag 14, with the heating-rate kernel).  In the
+ * grt_pipeline_run_spectral's), are added per bin in a fixed order (GRT_TAG_BAND_PROFILES, with the heating-rate kernel).  In the
  * deterministic mode the single bin {0, n - 1} per band gives grt_pipeline_run_profiles' level fluxes and heating rates
  * bit for bit, and with clouds grt_pipeline_run_allsky_profiles' two sets.  keep_spectra = 1: the spectral solvers, then
  * the same weights and sums on the [V][n] flux rows; afterwards grt_pipeline_views shows the last pass.  A new set of
@@ -483,7 +483,7 @@ EXTERN int grt_pipeline_band_profile_bin_limit(GrtPipeline_t const *pipeline);
  * surface->ncol: GRTCODE_VALUE_ERR otherwise, with nothing launched and the outputs untouched.  A band with a point
  * count of 0 keeps its creation-time array; a band whose gas-optics object is NULL ignores its fields.
  * The arrays are HOST memory, read during the call.  The host does the divisions once -- each column's [NS] becomes NS + 1
- * slope and intercept pairs, the two constant ranges as (0, y[0]) and (0, y[NS-2]) --, and a kernel (profile tag 15) writes
+ * slope and intercept pairs, the two constant ranges as (0, y[0]) and (0, y[NS-2]) --, and a kernel (GRT_TAG_SURFACE) writes
  * each column's row on the device, one thread per column and grid point: a few kB cross PCIe instead of
  * [ncol][n_lw] + 2 [ncol][n_sw] doubles.  Asynchronous on the pipeline's lane like a run.  Allocated at the first call
  * that needs them: [max_columns][n] doubles per band (twice that for the shortwave when diffuse_albedo is given: without
@@ -540,18 +540,43 @@ EXTERN int grt_multi_broadcast(GrtMulti_t *multi, void *buffer_dev, size_t bytes
 EXTERN int grt_multi_max(GrtMulti_t *multi, double *value);    /* barrier + maximum over the ranks (timing brackets) */
 
 /* ---- HIP-event timing of individual kernels on the library stream -------------------
- * Tags: 1 = line-by-line kernel on a grid of <= 10 000 points (longwave band at 1 cm-1),
- * 2 = line-by-line kernel on a larger grid (shortwave band), 3 = LW solver, 4 = SW solver,
- * 5 = clear-sky optics combine, 6 / 7 = far-field gather kernel of the two-pass line kernel (longwave /
- * shortwave band; tags 1 / 2 then cover its first pass), 8 / 9 = LW / SW solver of the all-sky pass of
- * grt_pipeline_run_allsky and grt_pipeline_run_allsky_profiles (their clear-sky pass counts under 3 / 4), 10 = the
- * wavenumber-bin kernel of grt_pipeline_run_spectral (both of its launches; its solvers count under 3 / 4 and 8 / 9),
- * 11 = the subcolumn-mean kernel of grt_pipeline_run_subcolumns (with S > 1; its all-sky solvers count under 8 / 9, each
- * band's launches together), 12 / 13 = LW / SW solver of the aerosol pass of grt_pipeline_run_aerosols (its clear-clean
- * pass counts under 3 / 4), 14 = the per-bin reduction and the heating-rate kernel of grt_pipeline_run_band_profiles (its
- * solvers count under 3 / 4 and 8 / 9), 15 = the surface-row kernel of grt_pipeline_set_surface (all its launches),
- * 16 = the cloud-sampling kernel of grt_cloud_sampler_run and grt_pipeline_run_cloud_fields.
- * Read after grt_pipeline_sync(). */
+ * Each tag names what one pair of events brackets; grt_profile_read(tag, ...) gives the time and the launches counted
+ * under it.  Read after grt_pipeline_sync(). */
+enum
+{
+    /* 1 = line-by-line kernel on a grid of <= 10 000 points (longwave band at 1 cm-1), and of a pipeline's longwave band */
+    GRT_TAG_GAS_LW = 1,
+    /* 2 = line-by-line kernel on a larger grid (shortwave band), and of a pipeline's shortwave band */
+    GRT_TAG_GAS_SW = 2,
+    /* 3 / 4 = LW / SW solver of the clear-sky (clear-clean) pass of every grt_pipeline_run_... */
+    GRT_TAG_SOLVER_LW = 3,
+    GRT_TAG_SOLVER_SW = 4,
+    /* 5 = clear-sky optics combine (materialised form) */
+    GRT_TAG_CLEAR_OPTICS = 5,
+    /* 6 / 7 = far-field gather kernel of the two-pass line kernel (longwave / shortwave band; GRT_TAG_GAS_LW / _SW then
+       cover its first pass) */
+    GRT_TAG_FAR_LW = 6,
+    GRT_TAG_FAR_SW = 7,
+    /* 8 / 9 = LW / SW solver of the all-sky pass of grt_pipeline_run_allsky, _allsky_profiles, _subcolumns (each band's
+       launches together), _cloud_fields, _spectral and _band_profiles */
+    GRT_TAG_ALLSKY_LW = 8,
+    GRT_TAG_ALLSKY_SW = 9,
+    /* 10 = the wavenumber-bin kernel of grt_pipeline_run_spectral (both of its launches; its solvers count under
+       GRT_TAG_SOLVER_... and GRT_TAG_ALLSKY_...) */
+    GRT_TAG_BINS = 10,
+    /* 11 = the subcolumn-mean kernel of grt_pipeline_run_subcolumns (with S > 1) */
+    GRT_TAG_SUBCOLUMN_MEAN = 11,
+    /* 12 / 13 = LW / SW solver of the aerosol pass of grt_pipeline_run_aerosols */
+    GRT_TAG_AEROSOL_LW = 12,
+    GRT_TAG_AEROSOL_SW = 13,
+    /* 14 = the per-bin reduction and the heating-rate kernel of grt_pipeline_run_band_profiles (its solvers count under
+       GRT_TAG_SOLVER_... and GRT_TAG_ALLSKY_...) */
+    GRT_TAG_BAND_PROFILES = 14,
+    /* 15 = the surface-row kernel of grt_pipeline_set_surface (all its launches) */
+    GRT_TAG_SURFACE = 15,
+    /* 16 = the cloud-sampling kernel of grt_cloud_sampler_run and grt_pipeline_run_cloud_fields */
+    GRT_TAG_CLOUD_SAMPLER = 16
+};
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
 

@@ -51,7 +51,7 @@ def main():
         for _ in range(args.reps):
             go.calculate_optical_depth(col["p"], col["t"], opt)
         dt = (time.perf_counter() - t0) / args.reps
-        tags = {t: api.profile_read(t) for t in (1, 2, 6, 7)}
+        tags = {t: api.profile_read(t) for t in (api.TAG_GAS_LW, api.TAG_GAS_SW, api.TAG_FAR_LW, api.TAG_FAR_SW)}
         api.profile_enable(False)
         return dt, go.last_launch(), {k: round(v[0] / max(v[1], 1), 3) for k, v in tags.items() if v[1]}
 

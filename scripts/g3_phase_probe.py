@@ -44,8 +44,8 @@ def main():
     api.profile_enable(True)
     for _ in range(2):
         go.calculate_optical_depth(col["p"], col["t"], opt)
-    prod = {t: api.profile_read(t) for t in (1, 2, 6, 7)}
-    tag = 1 if prod[1][1] else 2
+    prod = {t: api.profile_read(t) for t in (api.TAG_GAS_LW, api.TAG_GAS_SW, api.TAG_FAR_LW, api.TAG_FAR_SW)}
+    tag = api.TAG_GAS_LW if prod[api.TAG_GAS_LW][1] else api.TAG_GAS_SW
     api.profile_read(tag, reset=True)              # (a reset clears every tag)
     info = go.last_launch()
     tile, nslice = int(info["tile"]), int(info["nslice"])
@@ -68,7 +68,7 @@ def main():
     cnt = ["blocks64", "ring_steps", "near_points", "moment_reductions", "moment_lane_adds", "reg1_steps", "walk_steps"]
     R = (rec[..., 3].astype(np.uint64) & np.uint64(0xffff)).astype(np.float64)
     out = {"what": "first pass of the tree form, one longwave column at %g cm-1" % args.dw, "ran": info,
-           "production_first_pass_ms": prod[tag][0] / max(prod[tag][1], 1), "production_gather_ms": prod[tag + 5][0] / max(prod[tag + 5][1], 1),
+           "production_first_pass_ms": prod[tag][0] / max(prod[tag][1], 1), "production_gather_ms": prod[tag + api.TAG_FAR_OFFSET][0] / max(prod[tag + api.TAG_FAR_OFFSET][1], 1),
            "probe_first_pass_ms": probe_ms,
            "workgroup_clock_shares": {k: float(v.sum() / wg.sum()) for k, v in phases.items()},
            "wave_clock_shares_inside_the_line_loop": {n: float(v.sum() / tot_in) for n, v in inloop.items()},

@@ -22,7 +22,7 @@ t0 = time.perf_counter(); n = 200
 for _ in range(n):
     go.calculate_optical_depth(col["p"], col["t"], opt)
 dt = (time.perf_counter() - t0)/n
-k = sum(api.profile_read(t)[0] for t in (1, 2, 6, 7))/n
+k = sum(api.profile_read(t)[0] for t in (api.TAG_GAS_LW, api.TAG_GAS_SW, api.TAG_FAR_LW, api.TAG_FAR_SW))/n
 print(f"tiny band: {dt*1e3:.3f} ms per call, kernels {k:.3f} ms")
 t0 = time.perf_counter()
 for _ in range(n):

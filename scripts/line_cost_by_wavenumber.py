@@ -112,7 +112,7 @@ def probe_band(api, wl, go, grid, tag, far_tag, cols, gcols):
         by_layer.append(d)
     return {"n": int(grid.n), "tile": tile, "nslice": nslice, "tiles": ntiles, "workgroups": int(nrec),
             "production_first_pass_ms": prod_ms, "production_gather_ms": far_ms, "probe_first_pass_ms": probe_ms,
-            "lines_in_store": int(sum(v["v0"].size for v in (wl.lw_lines if tag == 1 else wl.sw_lines).values())),
+            "lines_in_store": int(sum(v["v0"].size for v in (wl.lw_lines if tag == api.TAG_GAS_LW else wl.sw_lines).values())),
             "whole_launch": pick(), "by_wavenumber": by_w, "by_layer": by_layer,
             # where a workgroup's own clock goes: prologue (column state, temperature-power table, candidate range, clearing
             # LDS) | the loop over its lines, until the LAST of its four waves is through | epilogue (flush to tau and gmom)
@@ -136,8 +136,8 @@ def main():
     (gcols, keep), _ = wl.columns(0, args.cols)
     out = {"what": "cost of the two-pass line kernel's first pass by wavenumber and layer, G1 workload, "
                    f"{args.cols} columns per launch; launch time attributed in proportion to workgroup-cycles (see the script)",
-           "lw": probe_band(api, wl, wl.go_lw, wl.grid_lw, 1, 6, args.cols, gcols),
-           "sw": probe_band(api, wl, wl.go_sw, wl.grid_sw, 2, 7, args.cols, gcols)}
+           "lw": probe_band(api, wl, wl.go_lw, wl.grid_lw, api.TAG_GAS_LW, api.TAG_FAR_LW, args.cols, gcols),
+           "sw": probe_band(api, wl, wl.go_sw, wl.grid_sw, api.TAG_GAS_SW, api.TAG_FAR_SW, args.cols, gcols)}
     lw, sw = out["lw"]["whole_launch"], out["sw"]["whole_launch"]
     out["sw_over_lw_ns_per_line"] = sw["ns_per_line_layer_column"] / lw["ns_per_line_layer_column"]
     wl.destroy()

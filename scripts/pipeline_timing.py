@@ -96,7 +96,7 @@ class Session:
         samples = {m: {**{k: [] for k in tags}, "wall_ms": []} for m in modes}
         for rep in range(self.args.reps):
             for mode in modes:
-                api.profile_read(1, reset=True)         # (a reset clears the brackets of every tag)
+                api.profile_read(api.TAG_GAS_LW, reset=True)         # (a reset clears the brackets of every tag)
                 t0 = time.perf_counter()
                 step(mode)
                 self.pipe.sync()

@@ -22,11 +22,11 @@ api.profile_enable(True)
 def timed(label, reps=12):
     wl.pipe.run(gcols)
     wl.pipe.sync()
-    api.profile_read(2, reset=True)
+    api.profile_read(api.TAG_GAS_SW, reset=True)
     for _ in range(reps):
         wl.pipe.run(gcols)
     wl.pipe.sync()
-    sw, lw = api.profile_read(2)[0] / reps, api.profile_read(1)[0] / reps
+    sw, lw = api.profile_read(api.TAG_GAS_SW)[0] / reps, api.profile_read(api.TAG_GAS_LW)[0] / reps
     print(label, "sw first pass ms", round(sw, 3), "lw", round(lw, 3), flush=True)
     return sw
 

@@ -12,8 +12,8 @@ V = W.NUM_LEVELS
 col = syn.profile(0, V)
 api.profile_enable(True)
 out = {}
-for name, go, grid, tag, cases in (("lw", wl.go_lw, wl.grid_lw, 1, [(0, 0), (64, 1), (64, 2), (64, 4), (64, 8), (128, 2), (128, 4), (128, 8), (256, 4), (256, 8), (256, 16)]),
-                                   ("sw", wl.go_sw, wl.grid_sw, 2, [(0, 0), (64, 1), (128, 1), (128, 2), (256, 1), (256, 2), (256, 4), (512, 2)])):
+for name, go, grid, tag, cases in (("lw", wl.go_lw, wl.grid_lw, api.TAG_GAS_LW, [(0, 0), (64, 1), (64, 2), (64, 4), (64, 8), (128, 2), (128, 4), (128, 8), (256, 4), (256, 8), (256, 16)]),
+                                   ("sw", wl.go_sw, wl.grid_sw, api.TAG_GAS_SW, [(0, 0), (64, 1), (128, 1), (128, 2), (256, 1), (256, 2), (256, 4), (512, 2)])):
     for m in W.MOL_ORDER:
         go.set_molecule_ppmv(m, col["ppmv"][m])
     go.set_cfc_ppmv(0, col["cfc_ppmv"][0]); go.set_cfc_ppmv(1, col["cfc_ppmv"][1])
@@ -25,7 +25,7 @@ for name, go, grid, tag, cases in (("lw", wl.go_lw, wl.grid_lw, 1, [(0, 0), (64,
         api.profile_read(tag, reset=True)
         for _ in range(5):
             go.calculate_optical_depth(col["p"], col["t"], opt)
-        first, far = api.profile_read(tag)[0] / 5, api.profile_read(tag + 5)[0] / 5
+        first, far = api.profile_read(tag)[0] / 5, api.profile_read(tag + api.TAG_FAR_OFFSET)[0] / 5
         info = go.last_launch()
         out[f"{name} tile={tile} nslice={ns}"] = {"first_pass_ms": round(first, 3), "gather_ms": round(far, 3), "ran": (info["tile"], info["nslice"])}
         print(name, tile, ns, round(first, 3), round(far, 3), (info["tile"], info["nslice"]), flush=True)

@@ -12,7 +12,7 @@ wl = W.G1Workload(device, 1)
 V = W.NUM_LEVELS
 col = syn.profile(0, V)
 api.profile_enable(True)
-for name, go, grid, tag in (("lw", wl.go_lw, wl.grid_lw, 1), ("sw", wl.go_sw, wl.grid_sw, 2)):
+for name, go, grid, tag in (("lw", wl.go_lw, wl.grid_lw, api.TAG_GAS_LW), ("sw", wl.go_sw, wl.grid_sw, api.TAG_GAS_SW)):
     for m in W.MOL_ORDER:
         go.set_molecule_ppmv(m, col["ppmv"][m])
     go.set_cfc_ppmv(0, col["cfc_ppmv"][0]); go.set_cfc_ppmv(1, col["cfc_ppmv"][1])

@@ -20,7 +20,8 @@ import numpy as np
 from pipeline_timing import Session, subcolumn_clouds  # (first: it puts the repository root on sys.path)
 from grtcode_amd import api
 
-TAGS = {"lw_clear_ms": 3, "sw_clear_ms": 4, "lw_allsky_ms": 8, "sw_allsky_ms": 9, "lw_aerosol_ms": 12, "sw_aerosol_ms": 13}
+TAGS = {"lw_clear_ms": api.TAG_SOLVER_LW, "sw_clear_ms": api.TAG_SOLVER_SW, "lw_allsky_ms": api.TAG_ALLSKY_LW,
+        "sw_allsky_ms": api.TAG_ALLSKY_SW, "lw_aerosol_ms": api.TAG_AEROSOL_LW, "sw_aerosol_ms": api.TAG_AEROSOL_SW}
 NA = 16
 
 

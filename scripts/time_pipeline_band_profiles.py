@@ -17,7 +17,8 @@ import numpy as np
 from pipeline_timing import Session, synthetic_clouds  # (first: it puts the repository root on sys.path)
 from grtcode_amd import api
 
-TAGS = {"lw_solver_ms": 3, "sw_solver_ms": 4, "lw_allsky_solver_ms": 8, "sw_allsky_solver_ms": 9, "bins_ms": 14}
+TAGS = {"lw_solver_ms": api.TAG_SOLVER_LW, "sw_solver_ms": api.TAG_SOLVER_SW,
+        "lw_allsky_solver_ms": api.TAG_ALLSKY_LW, "sw_allsky_solver_ms": api.TAG_ALLSKY_SW, "bins_ms": api.TAG_BAND_PROFILES}
 
 
 def equal_bins(n, bins):

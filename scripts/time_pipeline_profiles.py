@@ -15,7 +15,7 @@ import os
 from pipeline_timing import Session  # (first: it puts the repository root on sys.path)
 from grtcode_amd import api
 
-TAGS = {"lw_solver_ms": 3, "sw_solver_ms": 4}
+TAGS = {"lw_solver_ms": api.TAG_SOLVER_LW, "sw_solver_ms": api.TAG_SOLVER_SW}
 
 
 def main():

@@ -16,7 +16,8 @@ given).
 from pipeline_timing import Session, subcolumn_clouds  # (first: it puts the repository root on sys.path)
 from grtcode_amd import api
 
-TAGS = {"lw_allsky_solver_ms": 8, "sw_allsky_solver_ms": 9, "subcolumn_mean_ms": 11}
+TAGS = {"lw_allsky_solver_ms": api.TAG_ALLSKY_LW, "sw_allsky_solver_ms": api.TAG_ALLSKY_SW,
+        "subcolumn_mean_ms": api.TAG_SUBCOLUMN_MEAN}
 COUNTS = (1, 2, 4, 8)
 
 

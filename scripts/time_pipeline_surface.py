@@ -13,7 +13,7 @@ Five alternating repetitions in one process of
 each synchronised; medians and spreads (max - min).  Required of (b): no slower than the yardstick's median plus the
 yardstick's spread in the same run; (a) is expected equal to the yardstick within the spreads.
 (c) one grt_pipeline_set_surface call for NS = 2 and NS = 16: host wall time until the call returns, wall time until the
-lane has drained, and the kernel time under profile tag 15 (three launches); next to it the upload it replaces, [ncol][n_lw]
+lane has drained, and the kernel time under api.TAG_SURFACE (three launches); next to it the upload it replaces, [ncol][n_lw]
 + 2 [ncol][n_sw] doubles through grt_host_to_device, timed once.
 Result: profiles/pipeline_surface_timing.json (or the path given).
 
@@ -129,13 +129,13 @@ def main():
         host, drained, kernel = [], [], []
         for rep in range(s.args.reps + 1):              # (the first call of a grid builds its per-point entries: left out)
             pipe.sync()
-            api.profile_read(1, reset=True)
+            api.profile_read(api.TAG_GAS_LW, reset=True)
             t0 = time.perf_counter()
             pipe.set_surface(gs)
             t1 = time.perf_counter()
             pipe.sync()
             t2 = time.perf_counter()
-            ms, launches = api.profile_read(15)
+            ms, launches = api.profile_read(api.TAG_SURFACE)
             assert launches == 3, launches
             if rep > 0:
                 host.append(1e3 * (t1 - t0))

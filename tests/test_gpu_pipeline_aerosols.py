@@ -149,8 +149,8 @@ def test_clean_set_is_run_and_the_forms_agree(bands, lib, device, monkeypatch, s
         first = pipe.fluxes(ncol)
         api.profile_enable(True)
         clean, aer = run(pipe, gcols, gaer, ncol, False)
-        lw_ms, lw_n = api.profile_read(12)
-        sw_ms, sw_n = api.profile_read(13)
+        lw_ms, lw_n = api.profile_read(api.TAG_AEROSOL_LW)
+        sw_ms, sw_n = api.profile_read(api.TAG_AEROSOL_SW)
         api.profile_enable(False)
         assert lw_n == 1 and sw_n == 1 and lw_ms > 0.0 and sw_ms > 0.0          # the aerosol solvers' tags
         assert np.array_equal(clean["fluxes"], first)

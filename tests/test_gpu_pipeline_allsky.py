@@ -66,8 +66,8 @@ def test_clear_rows_are_runs_and_run_is_undisturbed(bands, tables, lib, device):
         api.profile_enable(True)
         pipe.run_allsky(gcols, gclouds)
         clear, cloudy = pipe.allsky_fluxes(ncol)
-        lw_ms, lw_n = api.profile_read(8)
-        sw_ms, sw_n = api.profile_read(9)
+        lw_ms, lw_n = api.profile_read(api.TAG_ALLSKY_LW)
+        sw_ms, sw_n = api.profile_read(api.TAG_ALLSKY_SW)
         api.profile_enable(False)
         assert np.array_equal(clear, first)
         assert not np.array_equal(cloudy, first)

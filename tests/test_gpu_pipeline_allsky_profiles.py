@@ -128,11 +128,11 @@ def test_repeatable_and_no_interference(bands, tables, lib, device):
         pipe.run_allsky(gcols, gclouds)
         allsky0 = pipe.allsky_fluxes(ncol)
         api.profile_enable(True)
-        for tag in (3, 4, 8, 9):
+        for tag in (api.TAG_SOLVER_LW, api.TAG_SOLVER_SW, api.TAG_ALLSKY_LW, api.TAG_ALLSKY_SW):
             api.profile_read(tag, reset=True)
         pipe.run_allsky_profiles(gcols, gclouds)
         a = pipe.allsky_profiles(ncol)
-        counts = {tag: api.profile_read(tag) for tag in (3, 4, 8, 9)}
+        counts = {tag: api.profile_read(tag) for tag in (api.TAG_SOLVER_LW, api.TAG_SOLVER_SW, api.TAG_ALLSKY_LW, api.TAG_ALLSKY_SW)}
         api.profile_enable(False)
         for tag, (ms, n) in counts.items():
             assert n == 1 and ms > 0.0, tag                 # one clear-sky (3, 4) and one all-sky (8, 9) solver per band

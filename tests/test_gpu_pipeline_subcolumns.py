@@ -200,13 +200,14 @@ def test_refused_inputs_and_no_interference(bands, tables, lib, device):
         pipe.run_allsky_profiles(gcols, g0)
         prof0 = pipe.allsky_profiles(ncol)
         api.profile_enable(True)
-        for tag in (8, 9, 11):
+        for tag in (api.TAG_ALLSKY_LW, api.TAG_ALLSKY_SW, api.TAG_SUBCOLUMN_MEAN):
             api.profile_read(tag, reset=True)
         pipe.run_subcolumns(gcols, g8, 8)
         means = pipe.subcolumn_fluxes(ncol)
-        counts = {tag: api.profile_read(tag) for tag in (8, 9, 11)}
+        counts = {tag: api.profile_read(tag) for tag in (api.TAG_ALLSKY_LW, api.TAG_ALLSKY_SW, api.TAG_SUBCOLUMN_MEAN)}
         api.profile_enable(False)
-        assert counts[8][1] == 1 and counts[9][1] == 1 and counts[11][1] == 2, counts
+        assert counts[api.TAG_ALLSKY_LW][1] == 1 and counts[api.TAG_ALLSKY_SW][1] == 1, counts
+        assert counts[api.TAG_SUBCOLUMN_MEAN][1] == 2, counts
         assert all(ms > 0.0 for ms, n in counts.values())
         pipe.run_subcolumns(gcols, g8, 8, profiles=True)
         pmeans = pipe.subcolumn_profiles(ncol)

@@ -445,7 +445,7 @@ def test_the_surface_kernel_is_timed_under_tag_15(solver_bands, oracle_cache, or
             gsurf, keep_s = case.gsurface(diffuse=diffuse)
             pipe.set_surface(gsurf)
             pipe.sync()
-            ms, count = api.profile_read(15, reset=True)
+            ms, count = api.profile_read(api.TAG_SURFACE, reset=True)
             assert count == launches and ms > 0.0
     finally:
         api.profile_enable(False)
