@@ -28,10 +28,14 @@ GRT_CLOUD_PHASE, GRT_CLOUD_MODEL, GRT_CLOUD_FIELDS = 7, 8, 9   # ... of GrtCloud
 # grt_profile_read's tags (grt_ext.h: GRT_TAG_..., where each one's bracket is described)
 (TAG_GAS_LW, TAG_GAS_SW, TAG_SOLVER_LW, TAG_SOLVER_SW, TAG_CLEAR_OPTICS, TAG_FAR_LW, TAG_FAR_SW, TAG_ALLSKY_LW,
  TAG_ALLSKY_SW, TAG_BINS, TAG_SUBCOLUMN_MEAN, TAG_AEROSOL_LW, TAG_AEROSOL_SW, TAG_BAND_PROFILES, TAG_SURFACE,
- TAG_CLOUD_SAMPLER) = range(1, 17)
+ TAG_CLOUD_SAMPLER, TAG_SKY_LW, TAG_SKY_SW) = range(1, 19)
 TAG_FAR_OFFSET = TAG_FAR_LW - TAG_GAS_LW    # from a line kernel's tag to its far-field gather's
 CLOUD_SAMPLER_TAG = TAG_CLOUD_SAMPLER
 GRT_MAX_SUBCOLUMNS = 64             # grt_pipeline_run_subcolumns: subcolumns per column, 1 .. this
+# grt_pipeline_run_sky's sets: clean (always formed), + aerosol, + clouds, + aerosol and clouds; packed in bit order
+GRT_SKY_CLEAN, GRT_SKY_AEROSOL, GRT_SKY_CLOUD, GRT_SKY_CLOUD_AEROSOL = 1, 2, 4, 8
+GRT_SKY_ALL = GRT_SKY_CLEAN | GRT_SKY_AEROSOL | GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL
+GRT_SKY_MAX_SETS = 4
 RETURN_CODES = ["GRTCODE_SUCCESS", "GRTCODE_INVALID_ERR", "GRTCODE_DIVBYZERO_ERR", "GRTCODE_OVERFLOW_ERR",
                 "GRTCODE_UNDERFLOW_ERR", "GRTCODE_SENTINEL_ERR", "GRTCODE_NULL_ERR", "GRTCODE_NON_NULL_ERR",
                 "GRTCODE_RANGE_ERR", "GRTCODE_VALUE_ERR", "GRTCODE_COMPILER_ERR", "GRTCODE_IO_ERR",
@@ -167,6 +171,11 @@ class GrtAerosols(C.Structure):
                 ("lw_optics", c_double_p), ("sw_optics", c_double_p)]
 
 
+class GrtSky(C.Structure):
+    _fields_ = [("clouds", C.POINTER(GrtClouds)), ("aerosols", C.POINTER(GrtAerosols)), ("num_subcolumns", C.c_int),
+                ("sets", C.c_uint)]
+
+
 class GrtSurface(C.Structure):
     _fields_ = [("ncol", C.c_int), ("emissivity_num_points", C.c_int), ("albedo_num_points", C.c_int),
                 ("emissivity_grid", c_double_p), ("albedo_grid", c_double_p), ("emissivity", c_double_p),
@@ -188,7 +197,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_pipeline_set_surface grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_pipeline_set_surface grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -244,6 +253,9 @@ def load_library(path=None):
                                                   C.c_void_p, C.c_void_p, C.c_void_p]
     lib.grt_pipeline_run_aerosols.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtAerosols), C.c_void_p,
                                               C.c_void_p, C.c_void_p]
+    lib.grt_pipeline_run_sky.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky), C.c_void_p, C.c_void_p,
+                                         C.c_void_p]
+    lib.grt_pipeline_sky_set_count.argtypes = [C.c_uint]
     lib.grt_pipeline_set_surface.argtypes = [C.c_void_p, C.POINTER(GrtSurface)]
     lib.grt_multi_gather_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.grt_pipeline_sync.argtypes = [C.c_void_p]
@@ -664,6 +676,23 @@ def make_aerosols(lw=None, sw=None):
     return ga, keep
 
 
+def sky_set_count(sets):
+    """grt_pipeline_sky_set_count: the sets per column a run_sky with these bits writes (the clean one always); 0 for bits
+    outside the four."""
+    return load_library().grt_pipeline_sky_set_count(C.c_uint(sets))
+
+
+def make_sky(gclouds, gaerosols, S, sets):
+    """Pack the inputs of Pipeline.run_sky into a GrtSky struct (+ keep-alive references): gclouds (make_clouds, tables
+    of S subcolumns per column) or None, gaerosols (make_aerosols) or None, and the GRT_SKY_... bits of the sets that are
+    asked for.  keep["nsets"] is the number of sets per column the call writes."""
+    keep = {"clouds": gclouds, "aerosols": gaerosols, "nsets": sky_set_count(sets)}
+    gs = GrtSky(C.pointer(gclouds) if gclouds is not None else None,
+                C.pointer(gaerosols) if gaerosols is not None else None, int(S), int(sets))
+    gs.keep = keep             # (as make_cloud_model)
+    return gs, keep
+
+
 def make_surface(ncol, emissivity=None, albedo=None):
     """Pack per-column surface inputs into a GrtSurface struct (+ keep-alive arrays) for Pipeline.set_surface.
     emissivity: (grid, values) -- grid [NS] cm-1, strictly increasing, NS >= 2; values [ncol][NS] in [0, 1] -- or None: the
@@ -731,7 +760,7 @@ class Pipeline:
         return f[:, :GRT_FLUXES_PER_COLUMN].copy(), f[:, GRT_FLUXES_PER_COLUMN:].copy()
 
     def _profile_ptrs(self, name, sets):
-        """The levels, heating and fluxes pointers of run form `name`, `sets` sets per column (1 or 2)."""
+        """The levels, heating and fluxes pointers of run form `name`, `sets` sets per column."""
         V, n = self.num_levels, self.max_columns
         rows = (("levels", GRT_PROFILE_ROWS_PER_COLUMN * V), ("heating", GRT_HEATING_ROWS_PER_COLUMN * (V - 1)),
                 ("fluxes", GRT_FLUXES_PER_COLUMN))
@@ -910,6 +939,29 @@ class Pipeline:
     def aerosol_profiles(self, ncol):
         """The last run_aerosols(profiles=True): (clean, aerosol), allsky_profiles()' keys and shapes."""
         return self._read_profiles("aerosol_profiles", 2, ncol)
+
+    def run_sky(self, gcols, gsky, profiles=False):
+        """grt_pipeline_run_sky into this object's device buffers: the sets gsky (make_sky) asks for, in the six-row form
+        (sky_fluxes() reads it) or, profiles=True, the profile form (sky_profiles() reads it)."""
+        nsets = sky_set_count(gsky.sets)
+        if profiles:
+            ptrs = self._profile_ptrs("sky_profiles", max(nsets, 1))
+        else:
+            ptrs = [None, None, self._buffer("sky", 8 * GRT_FLUXES_PER_COLUMN * max(nsets, 1) * self.max_columns).ptr]
+        check(self.lib.grt_pipeline_run_sky(self.p, C.byref(gcols), C.byref(gsky), *ptrs))
+
+    def sky_fluxes(self, ncol, nsets):
+        """The last six-row run_sky of nsets sets: [ncol][nsets][12], the sets in bit order, each in grt_pipeline_run's
+        layout."""
+        self.sync()
+        return self.buffers["sky"].to_host((ncol, nsets, GRT_FLUXES_PER_COLUMN))
+
+    def sky_profiles(self, ncol, nsets):
+        """The last run_sky(profiles=True) of nsets sets: a dict with profiles()' keys, every array with a leading
+        [ncol][nsets] -- lw_up, lw_down, sw_up, sw_down [ncol][nsets][V], lw_heating, sw_heating [ncol][nsets][V-1] and
+        fluxes [ncol][nsets][12]."""
+        per_set = self._read_profiles("sky_profiles", nsets, ncol)
+        return {k: np.stack([s[k] for s in per_set], axis=1) for k in per_set[0]}
 
     def views(self, band):
         ptrs = [C.c_void_p() for _ in range(6)]

@@ -328,7 +328,9 @@ static inline int grt_sw_one_sweep(GrtSwArgs const *a)
 /* levels [ncol][sets][4][V] (up, down of band 0, then of band 1) -> heating [ncol][sets][2][V-1] K day-1 (NULL: not
    formed) from the level pressures pressure [ncol][V] mb, and fluxes [ncol][sets][12] (NULL: not formed) in
    grt_pipeline_run's layout; the rows of a band whose bit in `bands` is clear are zeroed, level fluxes included, in every
-   set.  sets = 1: grt_pipeline_run_profiles; 2: grt_pipeline_run_allsky_profiles (clear sky, then all-sky). */
+   set.  sets = 1: grt_pipeline_run_profiles; 2: grt_pipeline_run_allsky_profiles (clear sky, then all-sky); up to
+   GRT_PROFILE_MAX_SETS: grt_pipeline_run_sky. */
+#define GRT_PROFILE_MAX_SETS 4          /* grt_ext.h: GRT_SKY_MAX_SETS */
 int grt_launch_profile_finish(void *stream, int ncol, int sets, int num_levels, int bands, int user_level, double gravity,
                               double cp, double const *pressure, double *levels, double *heating, double *fluxes);
 
@@ -450,8 +452,9 @@ typedef enum GrtSolverOutput
     GRT_OUT_LEVEL_BINS      /* every level's up and down flux per wavenumber bin of `bins` */
 } GrtSolverOutput;
 /* ... and what joins gas and Rayleigh in a fused instance: nothing (clear sky: every pointer NULL), the cloud objects,
-   the aerosol object, or the cloud objects of several subcolumns per column; `bins` goes with GRT_OUT_LEVEL_BINS and
-   with nothing else.  The kind of instance follows from which pointers are set, and a kernel takes the structs that are
+   the aerosol object, or the cloud objects of several subcolumns per column -- or the aerosol object together with either
+   form of the clouds (GRT_OUT_ROWS and GRT_OUT_LEVELS: the five objects of sky_combine, optics_dev.h; the aerosol table
+   stays per column whatever the subcolumn); `bins` goes with GRT_OUT_LEVEL_BINS and with nothing else.  The kind of instance follows from which pointers are set, and a kernel takes the structs that are
    set as arguments after its band's own.  The next joined object is a pointer here, a line in grt_solver_instance_ok
    and a case in each band's list of instances. */
 typedef struct GrtSolverInstance
@@ -464,7 +467,8 @@ typedef struct GrtSolverInstance
 } GrtSolverInstance;
 typedef enum GrtSolverJoin
 {
-    GRT_JOIN_NONE, GRT_JOIN_CLOUDS, GRT_JOIN_AEROSOLS, GRT_JOIN_SUBCOLUMNS, GRT_JOIN_COUNT
+    GRT_JOIN_NONE, GRT_JOIN_CLOUDS, GRT_JOIN_AEROSOLS, GRT_JOIN_SUBCOLUMNS, GRT_JOIN_CLOUDS_AEROSOLS,
+    GRT_JOIN_SUBCOLUMNS_AEROSOLS, GRT_JOIN_COUNT
 } GrtSolverJoin;
 /* an instance as one integer: the case labels of a band's list of instances (the launchers' switches) */
 #define GRT_INSTANCE(out, join) ((int)(out)*(int)GRT_JOIN_COUNT + (int)(join))
@@ -476,10 +480,14 @@ typedef enum GrtSolverJoin
 GRT_FN int grt_out_fused(GrtSolverOutput out) { return out >= GRT_OUT_ROWS; }
 GRT_FN int grt_out_levels(GrtSolverOutput out) { return out >= GRT_OUT_LEVELS; }
 #undef GRT_FN
-/* which pointer is set -- of an instance grt_solver_instance_ok has passed: it refuses more than one join, and any join
-   of an output that is not fused, so the order of the tests here decides nothing and a band's switch sees no such case */
+/* which pointers are set -- of an instance grt_solver_instance_ok has passed: it refuses clouds together with
+   subcolumns, and any join of an output that is not fused, so a band's switch sees no such case */
 static inline GrtSolverJoin grt_solver_join(GrtSolverInstance const *in)
 {
+    if (in->aerosols != NULL && (in->clouds != NULL || in->subcolumns != NULL))
+    {
+        return in->clouds != NULL ? GRT_JOIN_CLOUDS_AEROSOLS : GRT_JOIN_SUBCOLUMNS_AEROSOLS;
+    }
     return in->clouds != NULL ? GRT_JOIN_CLOUDS : (in->aerosols != NULL ? GRT_JOIN_AEROSOLS :
            (in->subcolumns != NULL ? GRT_JOIN_SUBCOLUMNS : GRT_JOIN_NONE));
 }
@@ -610,9 +618,11 @@ template <typename Args>
 inline bool grt_solver_instance_ok(GrtSolverInstance const &in, Args const &a)
 {
     bool const fused = grt_out_fused(in.out), flux_rows = a.flux_up != nullptr && a.flux_down != nullptr;
-    int const joined = (in.clouds != nullptr) + (in.aerosols != nullptr) + (in.subcolumns != nullptr);
+    // (of the pairs, the aerosol object with either form of the clouds exists; clouds and subcolumns exclude each other)
+    int const cloud_forms = (in.clouds != nullptr) + (in.subcolumns != nullptr);
+    int const joined = cloud_forms + (in.aerosols != nullptr);
     return a.ncol >= 1 && a.nw >= 2 && a.num_levels >= 2 &&
-           joined <= (fused ? 1 : 0) && (in.bins != nullptr) == (in.out == GRT_OUT_LEVEL_BINS) &&
+           cloud_forms <= 1 && joined <= (fused ? 2 : 0) && (in.bins != nullptr) == (in.out == GRT_OUT_LEVEL_BINS) &&
            (in.clouds == nullptr || grt_cloud_args_ok(in.clouds)) &&
            (in.aerosols == nullptr || grt_aerosol_args_ok(in.aerosols)) &&
            (in.subcolumns == nullptr || grt_subcolumn_args_ok(in.subcolumns)) &&

@@ -16,8 +16,9 @@
 // batches share a launch.  lw_kernel has one instance per GrtSolverInstance that exists (grt_kernels.h; the list is in
 // grt_launch_lw): what leaves it is its OUT -- spectral fluxes (GRT_OUT_CHAINS), or, fused, the partial sums of the six
 // rows, of the six rows that are also stored at every point, of every level, or of every level per wavenumber bin -- and
-// what joins gas and Rayleigh is the types of its pack: nothing, GrtCloudArgs, GrtAerosolArgs or GrtSubcolumnArgs, and a
-// GrtBandArgs last where OUT is per bin.  The fused six-row clear-sky instance is the production pipeline's.
+// what joins gas and Rayleigh is the types of its pack: nothing, GrtCloudArgs, GrtAerosolArgs or GrtSubcolumnArgs, a
+// GrtAerosolArgs behind either form of the clouds where both join, and a GrtBandArgs last where OUT is per bin.  The
+// fused six-row clear-sky instance is the production pipeline's.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -102,8 +103,8 @@ __device__ __forceinline__ double surface_step(double (&I)[4], double emis, doub
 // GRT_OUT_LEVELS: every level's upward and downward flux leaves instead, 2 V rows per column; GRT_OUT_LEVEL_BINS: once per
 // wavenumber bin (the pack's GrtBandArgs); GRT_OUT_ROWS_POINTS: the six rows also leave at every point, unweighted
 // (LevelSink).
-// Joins (fused forms): clouds (a GrtCloudArgs, or the draws of a GrtSubcolumnArgs) or the aerosol object join per layer
-// (LayerOptics).  Only layer_tau changes: what leaves the kernel is OUT's.
+// Joins (fused forms): clouds (a GrtCloudArgs, or the draws of a GrtSubcolumnArgs), the aerosol object or both join per
+// layer (LayerOptics).  Only layer_tau changes: what leaves the kernel is OUT's.
 template <GrtSolverOutput OUT, typename... Joins>
 __global__ __launch_bounds__(kSolverBlock) void lw_kernel(GrtLwArgs a, Joins... joins)
 {
@@ -317,6 +318,14 @@ extern "C" int grt_launch_lw(void *stream, GrtSolverInstance const *in, GrtLwArg
     case GRT_INSTANCE(GRT_OUT_LEVEL_BINS, GRT_JOIN_CLOUDS):
         return launch<GRT_OUT_LEVEL_BINS>(s, *in, *a, *in->clouds, *in->bins);
     case GRT_INSTANCE(GRT_OUT_LEVEL_BINS, GRT_JOIN_NONE): return launch<GRT_OUT_LEVEL_BINS>(s, *in, *a, *in->bins);
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_CLOUDS_AEROSOLS):
+        return launch<GRT_OUT_ROWS>(s, *in, *a, *in->clouds, *in->aerosols);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS_AEROSOLS):
+        return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, *in->aerosols);
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
+        return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns, *in->aerosols);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
+        return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->aerosols);
     default:
         return (int)hipErrorInvalidValue;
     }

@@ -391,8 +391,8 @@ __device__ __forceinline__ double heating_rate(double gravity, double cp, double
     return (gravity/cp)*((net_top - net_bottom)/(100.*(p[j + 1] - p[j])))*86400.;
 }
 
-// Last step of grt_pipeline_run_profiles (sets = 1) and grt_pipeline_run_allsky_profiles (sets = 2: clear sky, then
-// all-sky): one thread per (column, set, band, layer j) reads the band's level fluxes
+// Last step of grt_pipeline_run_profiles (sets = 1), grt_pipeline_run_allsky_profiles (sets = 2: clear sky, then
+// all-sky) and grt_pipeline_run_sky (the sets it was asked for): one thread per (column, set, band, layer j) reads the band's level fluxes
 // levels[c][set][2 band + {0: up, 1: down}][V] and forms the heating rate of layer j (heating_rate),
 // and -- thread j = 0 -- the band's six rows of the six-row form (up top, up surface, up user, down top, down surface, down
 // user: grt_pipeline_run's layout).  A band that is not computed (bit clear in `bands`) gets zeros everywhere.
@@ -496,7 +496,8 @@ extern "C" int grt_launch_profile_finish(void *stream, int ncol, int sets, int n
                                          double gravity, double cp, double const *pressure, double *levels, double *heating,
                                          double *fluxes)
 {
-    if (ncol < 1 || sets < 1 || sets > 2 || num_levels < 2 || user_level >= num_levels || levels == nullptr ||
+    if (ncol < 1 || sets < 1 || sets > GRT_PROFILE_MAX_SETS || num_levels < 2 || user_level >= num_levels ||
+        levels == nullptr ||
         (heating && pressure == nullptr))
     {
         return (int)hipErrorInvalidValue;

@@ -20,7 +20,8 @@
 // GrtSolverInstance that exists (grt_kernels.h; the list is in grt_launch_sw): what leaves it is its OUT -- spectral
 // fluxes (GRT_OUT_CHAINS), or, fused, the partial sums of the six rows, of the six rows that are also stored at every
 // point, of every level, or of every level per wavenumber bin -- and what joins gas and Rayleigh is the types of its
-// pack: nothing, GrtCloudArgs, GrtAerosolArgs or GrtSubcolumnArgs, and a GrtBandArgs last where OUT is per bin.
+// pack: nothing, GrtCloudArgs, GrtAerosolArgs or GrtSubcolumnArgs, a GrtAerosolArgs behind either form of the clouds where
+// both join, and a GrtBandArgs last where OUT is per bin.
 // The in-kernel range checks of the reference are no-ops on device builds
 // (debug.h:105-116) and are not restated.
 #include <hip/hip_runtime.h>
@@ -245,8 +246,8 @@ __device__ __forceinline__ void put_level(Sink &sink, int lev, double up, double
 // downward-beam reflectances of EVERY level in rows 0 .. 2 V - 1 of the park block, the second produces up and down at
 // every level and the sink sums each across the wave at once (as lw_kernel's), per wavenumber bin with the pack's
 // GrtBandArgs.  GRT_OUT_ROWS_POINTS: the six rows also leave at every point, unweighted (LevelSink).
-// Joins (fused forms): clouds (a GrtCloudArgs, or the draws of a GrtSubcolumnArgs) or the aerosol object join per layer
-// (LayerOptics), as in lw_kernel; the one-sweep and two-sweep rule is OUT's own.  props_of is the only place that reads
+// Joins (fused forms): clouds (a GrtCloudArgs, or the draws of a GrtSubcolumnArgs), the aerosol object or both join per
+// layer (LayerOptics), as in lw_kernel; the one-sweep and two-sweep rule is OUT's own.  props_of is the only place that reads
 // the joined tables, and the fused forms call it in their first (or only) sweep: the two-sweep forms' second sweep reads
 // the parked properties.
 template <GrtSolverOutput OUT, typename... Joins>
@@ -571,6 +572,14 @@ extern "C" int grt_launch_sw(void *stream, GrtSolverInstance const *in, GrtSwArg
     case GRT_INSTANCE(GRT_OUT_LEVEL_BINS, GRT_JOIN_CLOUDS):
         return launch<GRT_OUT_LEVEL_BINS>(s, *in, *a, *in->clouds, *in->bins);
     case GRT_INSTANCE(GRT_OUT_LEVEL_BINS, GRT_JOIN_NONE): return launch<GRT_OUT_LEVEL_BINS>(s, *in, *a, *in->bins);
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_CLOUDS_AEROSOLS):
+        return launch<GRT_OUT_ROWS>(s, *in, *a, *in->clouds, *in->aerosols);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS_AEROSOLS):
+        return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, *in->aerosols);
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
+        return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns, *in->aerosols);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
+        return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->aerosols);
     default:
         return (int)hipErrorInvalidValue;
     }

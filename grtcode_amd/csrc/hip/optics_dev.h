@@ -80,6 +80,30 @@ __device__ __forceinline__ void aerosol_combine(double tg, double tr, double ta,
     tau = ts;
 }
 
+// add_optics({gas, rayleigh, aerosol, liquid cloud, ice cloud}) for one (layer, wavenumber): the physically complete set,
+// the sums of optics.c:138-145 term by term in that order -- the aerosol in slot 2, where driver.c:426-434 puts it, the
+// clouds behind it as in driver.c:518-530.  An aerosol of exact zeros adds exact zeros before the clouds: allsky_combine's
+// doubles; clouds of exact zeros add exact zeros after the aerosol: aerosol_combine's doubles.
+__device__ __forceinline__ void sky_combine(double tg, double tr, double ta, double oa, double ga, double tl, double ol,
+                                            double gl, double ti, double oi, double gi, double &tau, double &omega,
+                                            double &g)
+{
+    double gs = 0., os = 0., ts = 0.;
+    gs += 0.*0.*tg;  os += 0.*tg;  ts += tg;
+    gs += 0.*1.*tr;  os += 1.*tr;  ts += tr;
+    gs += ga*oa*ta;  os += oa*ta;  ts += ta;
+    gs += gl*ol*tl;  os += ol*tl;  ts += tl;
+    gs += gi*oi*ti;  os += oi*ti;  ts += ti;
+    if (!(gs == 0. && os > 0. && os < 1.7976931348623157e308))
+    {
+        gs /= os;           // (as clear_sky_combine: +0 over a positive finite number is +0)
+    }
+    os /= ts;
+    g = gs;
+    omega = os;
+    tau = ts;
+}
+
 // ---- fixed-order sums: the bit identities between the fused forms rest on every one of them adding in these orders ----
 // WAVE_SUM(s);  the double variable s of the 64 lanes of a wave by a shuffle tree; lane 0's s holds the sum.  (A statement
 // macro: as a function the tree comes out of the compiler in another instruction order in the level-sum instances.)
@@ -111,7 +135,8 @@ __device__ __forceinline__ double waves_sum(double const *part)
 
 // ---- what joins gas and Rayleigh in a solver kernel instance: its parameter pack ----
 // lw_kernel / sw_kernel take their joined arguments as a pack after the band's own (GrtSolverInstance, grt_kernels.h:
-// nothing, GrtCloudArgs, GrtAerosolArgs or GrtSubcolumnArgs, and a GrtBandArgs last in the per-bin instances), so that an
+// nothing, GrtCloudArgs, GrtAerosolArgs or GrtSubcolumnArgs, a GrtAerosolArgs behind a GrtCloudArgs or a GrtSubcolumnArgs
+// where both join, and a GrtBandArgs last in the per-bin instances), so that an
 // instance's kernel arguments hold what it reads and nothing else.  has<T, Pack...>: whether the pack holds a T;
 // pick<T>(pack...): that element, or a T of zeros and null pointers.
 template <typename T, typename... Pack> constexpr bool has = (std::is_same_v<T, Pack> || ... || false);
@@ -151,8 +176,8 @@ __device__ __forceinline__ GrtCloudArgs pick_clouds(Pack const &...pack)
     }
 }
 
-// What grid row blockIdx.y stands for: col, the column whose gas state (tau_gas, temperatures, sun) it reads; tab, its
-// cloud tables' column; slot, its partial sums' column; park, its rows of the shortwave park block.  All four are
+// What grid row blockIdx.y stands for: col, the column whose gas state (tau_gas, temperatures, sun) and aerosol table it
+// reads; tab, its cloud tables' column; slot, its partial sums' column; park, its rows of the shortwave park block.  All four are
 // blockIdx.y but in the subcolumn instances (GrtSubcolumnArgs: row y is column y / count, subcolumn first + y % count).
 struct SolverRow { int col, tab, slot, park; };
 
@@ -351,7 +376,10 @@ __device__ __forceinline__ double trapezoid_weight(uint64_t i, uint64_t nw, doub
 // structs carry; FUSED false (the spectral forms, which read their optics): nothing is loaded.  tab: the column of the
 // cloud tables (SolverRow; col but in the subcolumn instances).  AEROSOL (clear-sky forms): the aerosol object joins
 // (GrtAerosolArgs): the point reads its interval once, each layer forms the object from the column's slope and intercept
-// table (six loads, three multiply-adds) and aerosol_combine adds the three.
+// table (six loads, three multiply-adds) and aerosol_combine adds the three.  The aerosol table is the column's, whatever
+// the subcolumn: it is indexed by col, never by tab.  ALLSKY and AEROSOL: both join, and sky_combine adds the five; the
+// aerosol's slopes and intercepts are loaded per layer, as in the aerosol forms, so the thread holds the two band indices,
+// one interval and one more pointer on top of the all-sky forms' state.
 template <bool FUSED, bool ALLSKY, bool AEROSOL = false>
 struct LayerOptics
 {
@@ -395,7 +423,7 @@ struct LayerOptics
         ctab = ALLSKY ? (uint64_t)tab*3*(uint64_t)cl.num_bands*L : 0;
         ainterval = AEROSOL ? ae.interval[ii] : -1;
         aplane = AEROSOL ? 2*(uint64_t)ae.num_intervals*L : 0;
-        atab = AEROSOL ? ae.tables + (uint64_t)tab*3*aplane + (uint64_t)(ainterval < 0 ? 0 : ainterval)*2*L : nullptr;
+        atab = AEROSOL ? ae.tables + (uint64_t)col*3*aplane + (uint64_t)(ainterval < 0 ? 0 : ainterval)*2*L : nullptr;
     }
 
     __device__ __forceinline__ void at(int j, double &t, double &om, double &gg) const
@@ -405,7 +433,16 @@ struct LayerOptics
         {
             tg = continua_add(*c, pc, cstate, j, nw, ii, blk_lo, blk_hi, tg);
         }
-        if constexpr (ALLSKY)
+        if constexpr (ALLSKY && AEROSOL)
+        {
+            double const th = cl.thickness[(uint64_t)col*L + j];
+            double at_, ao, ag, lt, lo, lg, it, io, ig;
+            aerosol_layer(atab, aplane, L, ainterval, j, w, at_, ao, ag);
+            cloud_layer(cl.liquid + ctab, cl.num_bands, L, band_l, j, th, lt, lo, lg);
+            cloud_layer(cl.ice + ctab, cl.num_bands, L, band_i, j, th, it, io, ig);
+            sky_combine(tg, rayleigh_tau(w, nl[j]), at_, ao, ag, lt, lo, lg, it, io, ig, t, om, gg);
+        }
+        else if constexpr (ALLSKY)
         {
             double const th = cl.thickness[(uint64_t)col*L + j];
             double lt, lo, lg, it, io, ig;

@@ -29,6 +29,8 @@
  * grt_pipeline_run_aerosols runs the clear-clean pass of grt_pipeline_run or grt_pipeline_run_profiles and then, on the
  * same tau_gas, the clear-sky pass with aerosols of driver.c:426-472: the aerosol object formed inside the solvers from
  * per-column slope and intercept tables (or, materialised form, spread onto the grid and added by the add_optics kernel).
+ * grt_pipeline_run_sky runs up to four sets of one driver.c column -- clear-clean, with aerosol, with clouds, with both -- on
+ * one gas-optics launch per band: the passes of the entry points above, and the pass that joins aerosol and clouds.
  * grt_pipeline_run_band_profiles runs the profile form of the clear-sky pass and, with clouds, of the all-sky pass with
  * every level's flux integrated per wavenumber bin instead of over the whole grid, and one finishing launch for the bins'
  * heating rates.
@@ -457,10 +459,11 @@ EXTERN int grt_pipeline_set_surface(GrtPipeline_t *p, GrtSurface_t const *surfac
 
 /* ---- the run ------------------------------------------------------------------------------------------------------ */
 
-/* What joins the gas in a run's second set: nothing (all zero: the run has one set), clouds, or aerosols.  subcolumns > 0
-   (grt_pipeline_run_subcolumns): the all-sky pass is the mean over that many subcolumns (grt_band_solve_subcolumns);
-   with a sampler (grt_pipeline_run_cloud_fields), their tables are written on the device from `fields`, and clouds holds
-   the band limits and the thickness only. */
+/* What joins the gas in a run's sets after the first: nothing (all zero: the run has one set), clouds, aerosols, or both.
+   subcolumns > 0 (grt_pipeline_run_subcolumns): a pass with clouds is the mean over that many subcolumns
+   (grt_band_solve_subcolumns); with a sampler (grt_pipeline_run_cloud_fields), their tables are written on the device
+   from `fields`, and clouds holds the band limits and the thickness only.  sets: the GRT_SKY_... sets that leave, packed
+   in bit order (grt_pipeline_run_sky); 0: the clean set, then the set of whichever of clouds and aerosols is given. */
 typedef struct GrtJoin
 {
     GrtClouds_t const *clouds;
@@ -468,12 +471,40 @@ typedef struct GrtJoin
     GrtCloudFields_t const *fields;
     GrtAerosols_t const *aerosols;
     int subcolumns;
+    unsigned sets;
 } GrtJoin;
 
-/* What the run entry points share after their argument checks: the batch (and its clouds or aerosols) staged, then per
-   band the gas optics and the solves into rows->out, each a copy of `rows` (the run's form, output and bins) completed
-   into one pass: the clear-sky solve, then -- with aerosols or clouds -- the aerosol or all-sky one, whose rows follow the
-   clear-sky set's (grt_set_offset). */
+#define GRT_SKY_ALL (GRT_SKY_CLEAN | GRT_SKY_AEROSOL | GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL)
+_Static_assert(GRT_SKY_MAX_SETS == GRT_PROFILE_MAX_SETS, "the finishing kernel takes every set of grt_pipeline_run_sky");
+
+/* the sets of a run: the clean one always, whether or not its bit is given */
+static unsigned join_sets(GrtJoin const *join)
+{
+    if (join->sets != 0)
+    {
+        return join->sets | GRT_SKY_CLEAN;
+    }
+    return GRT_SKY_CLEAN | (join->aerosols != NULL ? GRT_SKY_AEROSOL : 0u) | (join->clouds != NULL ? GRT_SKY_CLOUD : 0u);
+}
+
+EXTERN int grt_pipeline_sky_set_count(unsigned sets)
+{
+    if ((sets & ~GRT_SKY_ALL) != 0)
+    {
+        return 0;
+    }
+    int n = 0;
+    for (unsigned bit = GRT_SKY_CLEAN; bit <= GRT_SKY_CLOUD_AEROSOL; bit <<= 1)
+    {
+        n += ((sets | GRT_SKY_CLEAN) & bit) != 0;
+    }
+    return n;
+}
+
+/* What the run entry points share after their argument checks: the batch (and its clouds and aerosols) staged, then per
+   band the gas optics, once, and one solve per set of the run (join_sets) into rows->out, each a copy of `rows` (the
+   run's form, output and bins) completed into one pass: the clear-sky solve, then in bit order the aerosol pass, the
+   all-sky pass and the pass with both, each set's rows behind the one before (grt_set_offset). */
 static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin const *join, GrtPass const *rows)
 {
     GrtClouds_t const *cl = join->clouds;
@@ -485,6 +516,7 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
     }
     GRT_TRY(stage_columns(p, cols));
     int const C = cols->ncol, S = join->subcolumns > 0 ? join->subcolumns : 1;
+    unsigned const sets = join_sets(join);
     if (cl != NULL && join->sampler != NULL)
     {
         /* (the kernel writes the tables where grt_stage_clouds puts them) */
@@ -506,16 +538,16 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
         {
             if (!rows->profile)
             {
-                /* a skipped band's six values (and its all-sky six) are zeros, as the profile forms' rows are: the
-                   caller's buffer is not left holding whatever it held before */
+                /* a skipped band's six values are zeros in every set, as the profile forms' rows are: the caller's
+                   buffer is not left holding whatever it held before */
                 void *s = grt_dev_stream(p->device);
                 for (int c = 0; c < C; ++c)
                 {
                     double *six = rows->out + (size_t)c*rows->out_stride + GRT_FLUXES_PER_BAND*bi;
-                    GRT_TRY(grt_dev_zero(p->device, six, sizeof(double)*GRT_FLUXES_PER_BAND, s));
-                    if (cl != NULL || ae != NULL)
+                    for (int k = 0; k < rows->sets; ++k)
                     {
-                        GRT_TRY(grt_dev_zero(p->device, six + grt_set_offset(p, 0), sizeof(double)*GRT_FLUXES_PER_BAND, s));
+                        GRT_TRY(grt_dev_zero(p->device, six + (size_t)k*grt_set_offset(p, 0),
+                                             sizeof(double)*GRT_FLUXES_PER_BAND, s));
                     }
                 }
             }
@@ -532,26 +564,29 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
         }
         GrtContinua continua;
         GrtPass ps = *rows;
+        GrtAerosolArgs aa;
+        int const band_aer = ae != NULL && grt_aerosol_points(ae, bi) > 0;
+        int aa_ready = 0;
         GRT_TRY(band_gas_optics(p, b, bi, cols, &continua, &ps.defer));
         ps.continua = &continua;
-        GRT_TRY(grt_band_solve(p, b, bi, C, &ps));
-        ps.set = 1;
-        if (ae != NULL)
+        for (unsigned bit = GRT_SKY_CLEAN; bit <= GRT_SKY_CLOUD_AEROSOL; bit <<= 1)
         {
-            /* the aerosol set follows the clear-clean one, as the all-sky set does */
-            GrtAerosolArgs aa;
-            ps.aer_pass = 1;
-            if (grt_aerosol_points(ae, bi) > 0)
+            if (!(sets & bit))
+            {
+                continue;
+            }
+            /* (a band that was given no aerosol runs its aerosol sets without the object) */
+            ps.aer_pass = (bit & (GRT_SKY_AEROSOL | GRT_SKY_CLOUD_AEROSOL)) != 0;
+            if (ps.aer_pass && band_aer && !aa_ready)
             {
                 GRT_TRY(grt_band_aerosols(p, b, bi, ae, C, &aa));
-                ps.aer = &aa;
+                aa_ready = 1;
             }
-            GRT_TRY(grt_band_solve(p, b, bi, C, &ps));
-        }
-        if (cl != NULL)
-        {
-            ps.clouds = &ca;
-            GRT_TRY(join->subcolumns > 0 ? grt_band_solve_subcolumns(p, b, bi, C, S, &ps) : grt_band_solve(p, b, bi, C, &ps));
+            ps.aer = ps.aer_pass && band_aer ? &aa : NULL;
+            ps.clouds = (bit & (GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL)) != 0 ? &ca : NULL;
+            GRT_TRY(ps.clouds != NULL && join->subcolumns > 0 ? grt_band_solve_subcolumns(p, b, bi, C, S, &ps) :
+                    grt_band_solve(p, b, bi, C, &ps));
+            ++ps.set;
         }
     }
     return GRTCODE_SUCCESS;
@@ -795,6 +830,65 @@ EXTERN int grt_pipeline_run_aerosols(GrtPipeline_t *p, GrtColumns_t const *cols,
     GRT_TRY(check_aerosol_band("shortwave", a.sw_num_points, a.sw_grid, a.sw_optics));
     GRT_TRY(check_columns(p, cols));
     GrtJoin const join = {.aerosols = &a};
+    GRT_TRY(pipeline_run(p, cols, &join, &rows));
+    GRT_TRY(finish_profiles(p, cols->ncol, &rows, heating_dev, fluxes_dev));
+    return GRTCODE_SUCCESS;
+}
+
+/* grt_ext.h: the sets of one driver.c column that are asked for, on one gas-optics pass per band */
+EXTERN int grt_pipeline_run_sky(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky, fp_t *level_fluxes_dev,
+                                fp_t *heating_dev, fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    if (sky == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "no sky inputs (GrtSky_t is NULL).%s", "");
+    }
+    int const nsets = grt_pipeline_sky_set_count(sky->sets);
+    if (nsets == 0)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "sets 0x%x: bits outside GRT_SKY_CLEAN | _AEROSOL | _CLOUD | _CLOUD_AEROSOL (0x%x).",
+                 sky->sets, GRT_SKY_ALL);
+    }
+    int const with_clouds = (sky->sets & (GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL)) != 0;
+    int const with_aerosols = (sky->sets & (GRT_SKY_AEROSOL | GRT_SKY_CLOUD_AEROSOL)) != 0;
+    if (with_clouds && sky->clouds == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "sets 0x%x ask for a cloud set, and clouds is NULL.", sky->sets);
+    }
+    if (with_aerosols && sky->aerosols == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "sets 0x%x ask for an aerosol set, and aerosols is NULL.", sky->sets);
+    }
+    if (with_clouds && (sky->num_subcolumns < 1 || sky->num_subcolumns > GRT_MAX_SUBCOLUMNS))
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d subcolumns asked for: 1 to %d.", sky->num_subcolumns, GRT_MAX_SUBCOLUMNS);
+    }
+    GrtPass rows;
+    GRT_TRY(output_form(p, nsets, level_fluxes_dev, fluxes_dev, &rows));
+    /* (inputs that no set asks for are not looked at; a band the pipeline does not have ignores its aerosol fields) */
+    GrtAerosols_t a;
+    memset(&a, 0, sizeof(a));
+    if (with_aerosols)
+    {
+        a = *sky->aerosols;
+        if (p->band[0].gas == NULL)
+        {
+            a.lw_num_points = 0;
+        }
+        if (p->band[1].gas == NULL)
+        {
+            a.sw_num_points = 0;
+        }
+        GRT_TRY(check_aerosol_band("longwave", a.lw_num_points, a.lw_grid, a.lw_optics));
+        GRT_TRY(check_aerosol_band("shortwave", a.sw_num_points, a.sw_grid, a.sw_optics));
+    }
+    GRT_TRY(with_clouds ? check_clouds(p, cols, sky->clouds) : check_columns(p, cols));
+    /* one draw per column: the all-sky instances of the solvers; more: their subcolumn instances and the mean */
+    GrtJoin const join = {.clouds = with_clouds ? sky->clouds : NULL, .aerosols = with_aerosols ? &a : NULL,
+                          .subcolumns = with_clouds && sky->num_subcolumns > 1 ? sky->num_subcolumns : 0,
+                          .sets = sky->sets | GRT_SKY_CLEAN};
     GRT_TRY(pipeline_run(p, cols, &join, &rows));
     GRT_TRY(finish_profiles(p, cols->ncol, &rows, heating_dev, fluxes_dev));
     return GRTCODE_SUCCESS;

@@ -40,9 +40,10 @@ enum
     GRT_SCRATCH_PARK,
     /* fused form, grt_pipeline_run_profiles (and _allsky_profiles: both passes in turn): [max_cols][2 V][nblocks] */
     GRT_SCRATCH_LEVEL_PARTIALS,
-    /* materialised form of the all-sky and the aerosol pass (they run in stream order, never in one call): Rayleigh
-       [3][L][n], zeros [L][n], then the spread objects' tau, omega, g [3 objects][max_cols][L][n] (liquid and ice: 6 arrays,
-       aerosol: 3), replaced when a pass needs more arrays */
+    /* materialised form of the all-sky and the aerosol pass and of grt_pipeline_run_sky's pass with both (the passes of
+       a call take the block in turn, in stream order): Rayleigh [3][L][n], zeros [L][n], then the spread objects' tau,
+       omega, g [3 objects][max_cols][L][n] (aerosol: 3 arrays, liquid and ice: 6, all three: 9, the aerosol first),
+       replaced when a pass needs more arrays */
     GRT_SCRATCH_SPREAD,
     /* grt_pipeline_run_spectral's and grt_pipeline_run_band_profiles' partial sums: [max_cols][6 or 2 V][bin_per_row] */
     GRT_SCRATCH_BIN_PARTIALS,
@@ -123,8 +124,8 @@ typedef struct GrtBins
 } GrtBins;
 
 /* One solve of a band on the run's tau_gas.  What joins gas and Rayleigh: nothing (clear sky), the cloud objects (all-sky
-   pass) or the aerosol object (aerosol pass; aer NULL there: a band that was given no aerosol, which runs the clear-sky
-   form under the aerosol pass's profile tags).  Which rows leave: the six of driver.c:272-280 or (profile) every level's
+   pass), the aerosol object (aerosol pass; aer NULL there: a band that was given no aerosol, which runs the form without
+   the object under the aerosol pass's profile tags) or both (grt_pipeline_run_sky's complete set).  Which rows leave: the six of driver.c:272-280 or (profile) every level's
    up then down flux, to set `set` of the `sets` in the column's out_stride doubles at out; with bins, the six rows at
    every point and their bins too (grt_pipeline_run_spectral) or (profile) every level's flux per bin of the edges
    instead, to out's [ncol][sets][2 lw bins + 2 sw bins][V] (grt_pipeline_run_band_profiles). */
@@ -139,11 +140,11 @@ typedef struct GrtPass
     double *out;
     int out_stride;
     int sets;
-    int set;                       /* 0: the clear-sky set; 1: the all-sky or aerosol set that follows it */
+    int set;                       /* its place among the column's sets: 0 the clear-sky set, then the others as packed */
     GrtBins const *bins;
 } GrtPass;
 
-/* the doubles from a column's clear-sky set to its all-sky or aerosol set */
+/* the doubles from one set of a column to the next */
 static inline int grt_set_offset(GrtPipeline_t const *p, int profile)
 {
     return profile ? GRT_PROFILE_ROWS_PER_COLUMN*p->num_levels : GRT_FLUXES_PER_COLUMN;

@@ -8,9 +8,9 @@
 /* the profile tag its solver is timed under */
 static int pass_tag(GrtPass const *ps, int bi)
 {
-    static int const tag[3][2] = {{GRT_TAG_SOLVER_LW, GRT_TAG_SOLVER_SW}, {GRT_TAG_ALLSKY_LW, GRT_TAG_ALLSKY_SW},
-                                  {GRT_TAG_AEROSOL_LW, GRT_TAG_AEROSOL_SW}};
-    return tag[ps->aer_pass ? 2 : (ps->clouds != NULL)][bi];
+    static int const tag[4][2] = {{GRT_TAG_SOLVER_LW, GRT_TAG_SOLVER_SW}, {GRT_TAG_ALLSKY_LW, GRT_TAG_ALLSKY_SW},
+                                  {GRT_TAG_AEROSOL_LW, GRT_TAG_AEROSOL_SW}, {GRT_TAG_SKY_LW, GRT_TAG_SKY_SW}};
+    return tag[(ps->aer_pass ? 2 : 0) + (ps->clouds != NULL)][bi];
 }
 
 /* the six rows at every point leave too (grt_pipeline_run_spectral) */
@@ -206,12 +206,14 @@ static int clear_sky_optics(GrtPipeline_t *p, GrtBand *b, int C)
     return GRTCODE_SUCCESS;
 }
 
-/* The cloud objects (driver.c:507-530: liquid, ice) or the aerosol object (driver.c:426-434) spread onto the grid, then
-   per column Rayleigh and add_optics({gas, rayleigh, the spread objects}) -- tau, omega, g of the band are the pass's */
+/* The aerosol object (driver.c:426-434), the cloud objects (driver.c:507-530: liquid, ice) or all three spread onto the
+   grid, then per column Rayleigh and add_optics({gas, rayleigh, the spread objects: the aerosol first, as in the fused
+   solvers' sky_combine}) -- tau, omega, g of the band are the pass's */
 static int spread_optics(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *ps)
 {
     SpectralGrid_t const *grid = &b->gas->grid;
-    int const L = p->num_levels - 1, objects = ps->aer != NULL ? 1 : 2;
+    int const L = p->num_levels - 1, first_cloud = ps->aer != NULL ? 1 : 0;
+    int const objects = first_cloud + (ps->clouds != NULL ? 2 : 0);
     uint64_t const per = (uint64_t)L*b->n, all = per*(uint64_t)p->max_cols;
     void *s = grt_dev_stream(p->device);
     GrtScratch *block = &b->scratch[GRT_SCRATCH_SPREAD];
@@ -221,7 +223,7 @@ static int spread_optics(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *ps)
     {
         GRT_TRY(grt_dev_zero(p->device, block->d + 3*per, sizeof(double)*per, s));
     }
-    double *ray = block->d, *zero = ray + 3*per, *x[6];
+    double *ray = block->d, *zero = ray + 3*per, *x[9];
     for (int k = 0; k < 3*objects; ++k)
     {
         x[k] = zero + per + k*all;
@@ -231,9 +233,10 @@ static int spread_optics(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *ps)
         GRT_TRY(grt_dev_check(grt_launch_spread_aerosols(s, L, C, grid->w0, grid->dw, b->n, ps->aer, x[0], x[1], x[2]),
                               "aerosol spreading kernel"));
     }
-    else
+    if (ps->clouds != NULL)
     {
-        GRT_TRY(grt_dev_check(grt_launch_spread_clouds(s, L, C, b->n, ps->clouds, x[0], x[1], x[2], x[3], x[4], x[5]),
+        double **y = x + 3*first_cloud;
+        GRT_TRY(grt_dev_check(grt_launch_spread_clouds(s, L, C, b->n, ps->clouds, y[0], y[1], y[2], y[3], y[4], y[5]),
                               "cloud spreading kernel"));
     }
     for (int c = 0; c < C; ++c)
@@ -251,7 +254,8 @@ static int spread_optics(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *ps)
             in.tau[2 + k] = x[3*k] + o; in.omega[2 + k] = x[3*k + 1] + o; in.g[2 + k] = x[3*k + 2] + o;
         }
         GRT_TRY(grt_dev_check(grt_launch_add_optics(s, per, 2 + objects, &in, b->tau + o, b->omega + o, b->g + o),
-                              ps->aer != NULL ? "add_optics kernel (aerosols)" : "add_optics kernel (all-sky)"));
+                              objects == 3 ? "add_optics kernel (aerosols and clouds)" :
+                              (ps->aer != NULL ? "add_optics kernel (aerosols)" : "add_optics kernel (all-sky)")));
     }
     return GRTCODE_SUCCESS;
 }
@@ -416,7 +420,7 @@ int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *p
 
 /* The all-sky pass of grt_pipeline_run_subcolumns for one band, S subcolumns of every column on this run's tau_gas
    (driver.c:503-589), its mean rows to out as grt_band_solve writes them.  ps->clouds: the band's tables staged
-   subcolumn-major.  Fused form: the subcolumn instance of the all-sky solver over C x S grid rows, each subcolumn's
+   subcolumn-major; ps->aer (grt_pipeline_run_sky): the aerosol object joins every subcolumn, from its column's table.  Fused form: the subcolumn instance of the all-sky solver over C x S grid rows, each subcolumn's
    partial sums in sub_partials, then their fixed-order mean (GRT_TAG_SUBCOLUMN_MEAN; S = 1: the fixed-order sum of
    grt_band_solve).  The shortwave's two-sweep forms park C x count columns at a time in the band's park block, count =
    what fits in its max_cols, in stream order.  Materialised form: per subcolumn the all-sky optics, the spectral solver

@@ -399,6 +399,55 @@ typedef struct GrtAerosols
 EXTERN int grt_pipeline_run_aerosols(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtAerosols_t const *aerosols,
                                      fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev);
 
+/* ---- clouds and aerosols in one call -----------------------------------------------------------------------------
+ * What driver.c's column_calculation (driver.c:360-597) writes for a cloudy column with aerosols, and the set it lacks,
+ * on ONE gas-optics launch per band: up to four sets per column, each solved once --
+ *   GRT_SKY_CLEAN          gas + Rayleigh, grt_pipeline_run's set; always formed, whether or not the bit is given;
+ *   GRT_SKY_AEROSOL        + aerosol: grt_pipeline_run_aerosols' second set (driver.c:426-472);
+ *   GRT_SKY_CLOUD          + liquid and ice cloud, aerosol-free: grt_pipeline_run_subcolumns' second set
+ *                          (driver.c:474-597), the mean over num_subcolumns draws;
+ *   GRT_SKY_CLOUD_AEROSOL  + aerosol + liquid and ice cloud, the physically complete all-sky set: add_optics of
+ *                          {gas, Rayleigh, aerosol, liquid, ice} -- the sums of optics.c:138-145 in that order, the aerosol
+ *                          in slot 2 where driver.c:426-434 puts it, the clouds behind it --, the same solvers, the mean
+ *                          over the same draws; every draw of a column takes that column's aerosol.
+ * The sets that are asked for leave packed, in bit order, clean first.  With N = grt_pipeline_sky_set_count(sets) sets:
+ *   level_fluxes_dev == NULL (six rows): fluxes_dev [ncol][N][GRT_FLUXES_PER_COLUMN] (required); grt_pipeline_run's
+ *                    shortwave sweep rule;
+ *   level_fluxes_dev != NULL (profiles): level_fluxes_dev [ncol][N][GRT_PROFILE_ROWS_PER_COLUMN][V], heating_dev
+ *                    [ncol][N][GRT_HEATING_ROWS_PER_COLUMN][V-1] and fluxes_dev [ncol][N][GRT_FLUXES_PER_COLUMN] (both may
+ *                    be NULL), each set as grt_pipeline_run_profiles writes its one; the shortwave always takes two sweeps.
+ * All DEVICE memory; asynchronous on the pipeline's lane.  clouds: as grt_pipeline_run_subcolumns takes them, tables per
+ * subcolumn; aerosols: as grt_pipeline_run_aerosols takes them; inputs that no requested set needs are not read.  A band
+ * the pipeline lacks gives zeros in every set; a band that was given no aerosol (num_points == 0) runs its aerosol sets
+ * without the object.  grt_pipeline_set_surface applies to every set.  The production form solves the complete set in
+ * instances of the fused solvers that hold both joins (GRT_TAG_SKY_LW and _SW; the other sets count under their own
+ * passes' tags); keep_spectra = 1 spreads the aerosol and the clouds and adds the five objects with add_optics' kernel,
+ * and grt_pipeline_views afterwards shows the last set's (last subcolumn's) tau, omega, g.  In the deterministic mode
+ * each set is, bit for bit, what the entry point named above writes for it; an aerosol of zeros makes the complete set
+ * the cloud set and cloud-free tables make it the aerosol set, bit for bit, in every mode.  GRTCODE_VALUE_ERR, with
+ * nothing launched and the outputs untouched, for: sky NULL; bits in `sets` outside the four; a cloud set without clouds;
+ * an aerosol set without aerosols; num_subcolumns outside 1 .. GRT_MAX_SUBCOLUMNS with a cloud set; what
+ * grt_pipeline_run_subcolumns refuses in the clouds and grt_pipeline_run_aerosols in the aerosols; both outputs NULL;
+ * fewer than 2 levels in the profile form; ncol outside 1 .. max_columns.  A night column: GRTCODE_RANGE_ERR, as
+ * everywhere. */
+#define GRT_SKY_CLEAN          1u  /* gas + Rayleigh; always formed, whether or not the bit is given */
+#define GRT_SKY_AEROSOL        2u  /* + aerosol                   (driver.c:426-472) */
+#define GRT_SKY_CLOUD          4u  /* + liquid and ice cloud      (driver.c:474-597, aerosol-free) */
+#define GRT_SKY_CLOUD_AEROSOL  8u  /* + aerosol + liquid and ice cloud */
+#define GRT_SKY_MAX_SETS       4
+
+typedef struct GrtSky
+{
+    GrtClouds_t const *clouds;       /* needed by the two cloud sets; tables per subcolumn as grt_pipeline_run_subcolumns takes them */
+    GrtAerosols_t const *aerosols;   /* needed by the two aerosol sets */
+    int num_subcolumns;              /* 1 .. GRT_MAX_SUBCOLUMNS: the cloud sets are the mean over that many draws */
+    unsigned sets;
+} GrtSky_t;
+
+EXTERN int grt_pipeline_sky_set_count(unsigned sets);   /* 1 .. 4; 0 for bits outside the four */
+EXTERN int grt_pipeline_run_sky(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtSky_t const *sky,
+                                fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev);
+
 /* ---- spectral and band-integrated fluxes ---------------------------------------------------------------------------
  * driver.c's output without -integrated (output_fluxes, driver.c:285-356): the six rows of grt_pipeline_run at EVERY grid
  * point, and -- where the caller gives bin edges -- the same rows integrated over wavenumber bins, for a batch of columns,
@@ -575,7 +624,11 @@ enum
     /* 15 = the surface-row kernel of grt_pipeline_set_surface (all its launches) */
     GRT_TAG_SURFACE = 15,
     /* 16 = the cloud-sampling kernel of grt_cloud_sampler_run and grt_pipeline_run_cloud_fields */
-    GRT_TAG_CLOUD_SAMPLER = 16
+    GRT_TAG_CLOUD_SAMPLER = 16,
+    /* 17 / 18 = LW / SW solver of the pass of grt_pipeline_run_sky that joins aerosol and clouds (GRT_SKY_CLOUD_AEROSOL; its
+       other sets count under GRT_TAG_SOLVER_..., GRT_TAG_AEROSOL_... and GRT_TAG_ALLSKY_...) */
+    GRT_TAG_SKY_LW = 17,
+    GRT_TAG_SKY_SW = 18
 };
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
