@@ -28,10 +28,12 @@ GRT_CLOUD_PHASE, GRT_CLOUD_MODEL, GRT_CLOUD_FIELDS = 7, 8, 9   # ... of GrtCloud
 # grt_profile_read's tags (grt_ext.h: GRT_TAG_..., where each one's bracket is described)
 (TAG_GAS_LW, TAG_GAS_SW, TAG_SOLVER_LW, TAG_SOLVER_SW, TAG_CLEAR_OPTICS, TAG_FAR_LW, TAG_FAR_SW, TAG_ALLSKY_LW,
  TAG_ALLSKY_SW, TAG_BINS, TAG_SUBCOLUMN_MEAN, TAG_AEROSOL_LW, TAG_AEROSOL_SW, TAG_BAND_PROFILES, TAG_SURFACE,
- TAG_CLOUD_SAMPLER, TAG_SKY_LW, TAG_SKY_SW) = range(1, 19)
+ TAG_CLOUD_SAMPLER, TAG_SKY_LW, TAG_SKY_SW, TAG_ZENITH_SW, TAG_ZENITH_MEAN) = range(1, 21)
 TAG_FAR_OFFSET = TAG_FAR_LW - TAG_GAS_LW    # from a line kernel's tag to its far-field gather's
 CLOUD_SAMPLER_TAG = TAG_CLOUD_SAMPLER
 GRT_MAX_SUBCOLUMNS = 64             # grt_pipeline_run_subcolumns: subcolumns per column, 1 .. this
+GRT_MAX_ZENITHS = 64                # grt_pipeline_run_zeniths: sun angles per column, 1 .. this
+GRT_ZENITH_CHUNK = 4                # csrc/grt_kernels.h: the angles one thread of the shared-layer shortwave kernel carries
 # grt_pipeline_run_sky's sets: clean (always formed), + aerosol, + clouds, + aerosol and clouds; packed in bit order
 GRT_SKY_CLEAN, GRT_SKY_AEROSOL, GRT_SKY_CLOUD, GRT_SKY_CLOUD_AEROSOL = 1, 2, 4, 8
 GRT_SKY_ALL = GRT_SKY_CLEAN | GRT_SKY_AEROSOL | GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL
@@ -176,6 +178,11 @@ class GrtSky(C.Structure):
                 ("sets", C.c_uint)]
 
 
+class GrtZeniths(C.Structure):
+    _fields_ = [("num_zeniths", C.c_int), ("cos_zenith", c_double_p), ("weight", c_double_p),
+                ("zenith_fluxes_dev", C.c_void_p), ("zenith_level_fluxes_dev", C.c_void_p)]
+
+
 class GrtSurface(C.Structure):
     _fields_ = [("ncol", C.c_int), ("emissivity_num_points", C.c_int), ("albedo_num_points", C.c_int),
                 ("emissivity_grid", c_double_p), ("albedo_grid", c_double_p), ("emissivity", c_double_p),
@@ -197,7 +204,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_pipeline_set_surface grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -256,6 +263,9 @@ def load_library(path=None):
     lib.grt_pipeline_run_sky.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky), C.c_void_p, C.c_void_p,
                                          C.c_void_p]
     lib.grt_pipeline_sky_set_count.argtypes = [C.c_uint]
+    if hasattr(lib, "grt_pipeline_run_zeniths"):    # (GRT_LIB_PATH may name an older library: a timing yardstick)
+        lib.grt_pipeline_run_zeniths.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtZeniths), C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]
     lib.grt_pipeline_set_surface.argtypes = [C.c_void_p, C.POINTER(GrtSurface)]
     lib.grt_multi_gather_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.grt_pipeline_sync.argtypes = [C.c_void_p]
@@ -724,6 +734,21 @@ def make_surface(ncol, emissivity=None, albedo=None):
     return gs, keep
 
 
+def make_zeniths(cos_zenith, weight=None):
+    """Pack the sun angles of a batch into a GrtZeniths struct (+ keep-alive arrays) for Pipeline.run_zeniths.
+    cos_zenith [ncol][Z], a value <= 0 a night sample; weight [ncol][Z] or None: the plain mean over the Z samples.  The
+    two per-angle output pointers are Pipeline.run_zeniths' to set.  keep["shape"] is (ncol, Z)."""
+    keep = {"mu": _f64(cos_zenith), "weight": None if weight is None else _f64(weight)}
+    if keep["mu"].ndim != 2:
+        raise ValueError(f"cos_zenith of shape {keep['mu'].shape}: [ncol][Z]")
+    if keep["weight"] is not None and keep["weight"].shape != keep["mu"].shape:
+        raise ValueError(f"weight of shape {keep['weight'].shape}: {keep['mu'].shape}")
+    keep["shape"] = keep["mu"].shape
+    gz = GrtZeniths(keep["mu"].shape[1], _dp(keep["mu"]), _opt_dp(keep["weight"]), None, None)
+    gz.keep = keep             # (as make_cloud_model)
+    return gz, keep
+
+
 class Pipeline:
     def __init__(self, lw_gas, sw_gas, max_columns, user_level, emissivity, albedo, solar, spectral=True):
         """spectral=True keeps tau/omega/g and the spectral fluxes (views(): what parity tests read);
@@ -962,6 +987,36 @@ class Pipeline:
         fluxes [ncol][nsets][12]."""
         per_set = self._read_profiles("sky_profiles", nsets, ncol)
         return {k: np.stack([s[k] for s in per_set], axis=1) for k in per_set[0]}
+
+    def run_zeniths(self, gcols, gzeniths, profiles=False):
+        """grt_pipeline_run_zeniths with gzeniths' (make_zeniths) sun angles per column into this object's device buffers,
+        every angle's own rows included: the six-row form (zenith_fluxes() reads it) or, profiles=True, the profile form
+        (zenith_profiles() reads it)."""
+        Z, V, n = gzeniths.num_zeniths, self.num_levels, self.max_columns
+        name = "zenith_profiles" if profiles else "zenith"
+        gzeniths.zenith_fluxes_dev = self._buffer(name + ".angles", 8 * n * max(Z, 1) * 6).ptr
+        gzeniths.zenith_level_fluxes_dev = self._buffer(name + ".angle_levels", 8 * n * max(Z, 1) * 2 * V).ptr if profiles else None
+        if profiles:
+            ptrs = self._profile_ptrs(name, 1)
+        else:
+            ptrs = [None, None, self._buffer(name, 8 * GRT_FLUXES_PER_COLUMN * n).ptr]
+        check(self.lib.grt_pipeline_run_zeniths(self.p, C.byref(gcols), C.byref(gzeniths), *ptrs))
+
+    def zenith_fluxes(self, ncol, Z):
+        """The last six-row run_zeniths: (fluxes [ncol][12] in grt_pipeline_run's layout, the shortwave six the mean over
+        the angles; angles [ncol][Z][6], every angle's shortwave six)."""
+        self.sync()
+        return (self.buffers["zenith"].to_host((ncol, GRT_FLUXES_PER_COLUMN)),
+                self.buffers["zenith.angles"].to_host((ncol, Z, 6)))
+
+    def zenith_profiles(self, ncol, Z):
+        """The last run_zeniths(profiles=True): profiles()' dict, the shortwave rows the mean over the angles, and with it
+        angle_fluxes [ncol][Z][6], angle_up and angle_down [ncol][Z][V]: every angle's shortwave rows."""
+        out = self._read_profiles("zenith_profiles", 1, ncol)[0]
+        lv = self.buffers["zenith_profiles.angle_levels"].to_host((ncol, Z, 2, self.num_levels))
+        out["angle_fluxes"] = self.buffers["zenith_profiles.angles"].to_host((ncol, Z, 6))
+        out["angle_up"], out["angle_down"] = lv[:, :, 0].copy(), lv[:, :, 1].copy()
+        return out
 
     def views(self, band):
         ptrs = [C.c_void_p() for _ in range(6)]

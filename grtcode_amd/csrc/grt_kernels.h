@@ -416,6 +416,41 @@ static inline int grt_subcolumn_args_ok(GrtSubcolumnArgs const *sc)
            sc->first + sc->count <= sc->subcolumns;
 }
 
+/* Zenith form of the two clear-sky fused forms (zeniths joined, six rows or every level; grt_pipeline_run_zeniths): one
+   launch solves sun angles first .. first + count - 1 of every column on the column's one tau_gas.  Row y of the grid is
+   column c = y / count, angle k = first + y % count, as the subcolumn form maps its rows: the row reads mu[c zeniths + k]
+   in place of GrtSwArgs.mu_dir, leaves its partial sums at the slot c zeniths + k and parks at y.  A row whose mu <= 0 is a
+   night sample: +0.0 partial sums, nothing solved.  Shortwave only.  grt_launch_zenith_mean reduces. */
+typedef struct GrtZenithArgs
+{
+    double const *mu;               /* DEVICE [ncol][zeniths] */
+    int zeniths, first, count;
+} GrtZenithArgs;
+static inline int grt_zenith_args_ok(GrtZenithArgs const *z)
+{
+    return z != NULL && z->mu != NULL && z->zeniths >= 1 && z->count >= 1 && z->first >= 0 &&
+           z->first + z->count <= z->zeniths;
+}
+/* The shared-layer kernel of the zenith form (k_shortwave.hip: sw_zenith_kernel), six rows in one sweep
+   (grt_sw_one_sweep(a) must hold: hipErrorInvalidValue otherwise): grid row y is column y / chunks and the
+   GRT_ZENITH_CHUNK consecutive angles from (y % chunks) GRT_ZENITH_CHUNK on, chunks = ceil(zeniths / GRT_ZENITH_CHUNK);
+   a thread forms a layer's optics, delta-scaling and diffuse Eddington solution once and the direct-beam solution per
+   angle.  Every angle's partial sums are, bit for bit, the zenith instance's of GRT_OUT_ROWS (first and count are not
+   read: one launch takes every angle). */
+#define GRT_ZENITH_CHUNK 4
+int grt_launch_sw_zeniths(void *stream, GrtSwArgs const *a, GrtZenithArgs const *z);
+/* The weighted mean over a column's angles of one output row, in a fixed order, and every angle's own rows: for column c
+   and row r (of `rows` per slot) each angle's blocks are added as grt_launch_reduce_partials adds them -- an angle whose
+   mu [ncol][zeniths] is <= 0 counts as +0.0 whatever its partial sums hold -- and stored at per_angle[(c zeniths + k) rows
+   + r] (per_angle NULL: not stored); then the angles k = 0 .. zeniths - 1 in order, each times weight[c zeniths + k], the
+   product rounded before it is added -- weight NULL: the plain sum, then one division by zeniths --, to
+   out[c out_stride + out_offset + r] (out NULL: not formed).  zeniths = 1 without weights gives
+   grt_launch_reduce_partials' bits.  six (or NULL; rows = 2 V, a column's up then down levels): every angle's six rows of
+   grt_pipeline_run's layout as well, [ncol][zeniths][6], from its level rows 0, V - 1 and user_level. */
+int grt_launch_zenith_mean(void *stream, double const *partials, int ncol, int zeniths, int rows, unsigned nblocks,
+                           double const *mu, double const *weight, double *per_angle, double *six, int user_level,
+                           double *out, int out_stride, int out_offset);
+
 /* Banded profile form of the two profile forms (GRT_OUT_LEVEL_BINS, clear sky or clouds joined;
    grt_pipeline_run_band_profiles): the profile form's arguments, sweeps and park block, but every level's
    flux leaves once per wavenumber bin that has a point in the workgroup's 128 grid points.  A point weights a level's
@@ -454,7 +489,8 @@ typedef enum GrtSolverOutput
 /* ... and what joins gas and Rayleigh in a fused instance: nothing (clear sky: every pointer NULL), the cloud objects,
    the aerosol object, or the cloud objects of several subcolumns per column -- or the aerosol object together with either
    form of the clouds (GRT_OUT_ROWS and GRT_OUT_LEVELS: the five objects of sky_combine, optics_dev.h; the aerosol table
-   stays per column whatever the subcolumn); `bins` goes with GRT_OUT_LEVEL_BINS and with nothing else.  The kind of instance follows from which pointers are set, and a kernel takes the structs that are
+   stays per column whatever the subcolumn); `bins` goes with GRT_OUT_LEVEL_BINS and with nothing else; `zeniths` (the
+   shortwave's GRT_OUT_ROWS and GRT_OUT_LEVELS) goes with no other join.  The kind of instance follows from which pointers are set, and a kernel takes the structs that are
    set as arguments after its band's own.  The next joined object is a pointer here, a line in grt_solver_instance_ok
    and a case in each band's list of instances. */
 typedef struct GrtSolverInstance
@@ -464,11 +500,12 @@ typedef struct GrtSolverInstance
     GrtAerosolArgs const *aerosols;
     GrtSubcolumnArgs const *subcolumns;
     GrtBandArgs const *bins;
+    GrtZenithArgs const *zeniths;
 } GrtSolverInstance;
 typedef enum GrtSolverJoin
 {
     GRT_JOIN_NONE, GRT_JOIN_CLOUDS, GRT_JOIN_AEROSOLS, GRT_JOIN_SUBCOLUMNS, GRT_JOIN_CLOUDS_AEROSOLS,
-    GRT_JOIN_SUBCOLUMNS_AEROSOLS, GRT_JOIN_COUNT
+    GRT_JOIN_SUBCOLUMNS_AEROSOLS, GRT_JOIN_ZENITHS, GRT_JOIN_COUNT
 } GrtSolverJoin;
 /* an instance as one integer: the case labels of a band's list of instances (the launchers' switches) */
 #define GRT_INSTANCE(out, join) ((int)(out)*(int)GRT_JOIN_COUNT + (int)(join))
@@ -481,9 +518,14 @@ GRT_FN int grt_out_fused(GrtSolverOutput out) { return out >= GRT_OUT_ROWS; }
 GRT_FN int grt_out_levels(GrtSolverOutput out) { return out >= GRT_OUT_LEVELS; }
 #undef GRT_FN
 /* which pointers are set -- of an instance grt_solver_instance_ok has passed: it refuses clouds together with
-   subcolumns, and any join of an output that is not fused, so a band's switch sees no such case */
+   subcolumns, zeniths together with anything, and any join of an output that is not fused, so a band's switch sees no
+   such case */
 static inline GrtSolverJoin grt_solver_join(GrtSolverInstance const *in)
 {
+    if (in->zeniths != NULL)
+    {
+        return GRT_JOIN_ZENITHS;
+    }
     if (in->aerosols != NULL && (in->clouds != NULL || in->subcolumns != NULL))
     {
         return in->clouds != NULL ? GRT_JOIN_CLOUDS_AEROSOLS : GRT_JOIN_SUBCOLUMNS_AEROSOLS;
@@ -491,10 +533,11 @@ static inline GrtSolverJoin grt_solver_join(GrtSolverInstance const *in)
     return in->clouds != NULL ? GRT_JOIN_CLOUDS : (in->aerosols != NULL ? GRT_JOIN_AEROSOLS :
            (in->subcolumns != NULL ? GRT_JOIN_SUBCOLUMNS : GRT_JOIN_NONE));
 }
-/* the rows of its grid: a column each, or (subcolumns) `count` subcolumns of every column */
+/* the rows of its grid: a column each, or (subcolumns, zeniths) `count` subcolumns or angles of every column */
 static inline uint64_t grt_solver_grid_rows(GrtSolverInstance const *in, int ncol)
 {
-    return (uint64_t)ncol*(uint64_t)(in->subcolumns != NULL ? in->subcolumns->count : 1);
+    return (uint64_t)ncol*(uint64_t)(in->subcolumns != NULL ? in->subcolumns->count :
+                                     (in->zeniths != NULL ? in->zeniths->count : 1));
 }
 /* its dynamic LDS: 2 V doubles per wave of its workgroup where every level leaves, that per bin of a block with bins */
 #define GRT_SOLVER_BLOCK 128
@@ -621,7 +664,10 @@ inline bool grt_solver_instance_ok(GrtSolverInstance const &in, Args const &a)
     // (of the pairs, the aerosol object with either form of the clouds exists; clouds and subcolumns exclude each other)
     int const cloud_forms = (in.clouds != nullptr) + (in.subcolumns != nullptr);
     int const joined = cloud_forms + (in.aerosols != nullptr);
-    return a.ncol >= 1 && a.nw >= 2 && a.num_levels >= 2 &&
+    // (the sun angles join the clear-sky six-row and level forms alone)
+    bool const zeniths_ok = in.zeniths == nullptr || (joined == 0 && grt_zenith_args_ok(in.zeniths) &&
+                                                      (in.out == GRT_OUT_ROWS || in.out == GRT_OUT_LEVELS));
+    return zeniths_ok && a.ncol >= 1 && a.nw >= 2 && a.num_levels >= 2 &&
            cloud_forms <= 1 && joined <= (fused ? 2 : 0) && (in.bins != nullptr) == (in.out == GRT_OUT_LEVEL_BINS) &&
            (in.clouds == nullptr || grt_cloud_args_ok(in.clouds)) &&
            (in.aerosols == nullptr || grt_aerosol_args_ok(in.aerosols)) &&

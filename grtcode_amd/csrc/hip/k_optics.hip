@@ -474,6 +474,59 @@ __global__ __launch_bounds__(kBlock) void band_profile_finish_kernel(int ncol, i
     heating[(cs*nb + q)*L + j] = heating_rate(gravity, cp, pressure + (uint64_t)c*V, up, dn, j);
 }
 
+// grt_pipeline_run_zeniths: every sun angle's own rows, and their weighted mean over a column's Z angles.  One wavefront
+// per (column, row): each angle's block sums by wave_strided_sum as reduce_partials_kernel adds them (a night angle,
+// mu <= 0: +0.0), stored per angle; then the angles in order -- w_k x_k, the product rounded before it is added, or,
+// without weights, the plain sum and one division by Z as subcolumn_mean_kernel's.  Z = 1 without weights:
+// reduce_partials_kernel's bits.  six (profile form, rows = 2 V: up then down levels): every angle's six rows too, its
+// level rows 0, V - 1 and user as profile_finish_kernel picks them.
+__global__ __launch_bounds__(64) void zenith_mean_kernel(double const *partials, int Z, int rows, unsigned nblocks,
+                                                         double const *mu, double const *weight, double *per_angle,
+                                                         double *six, int user, double *out, int out_stride,
+                                                         int out_offset)
+{
+    int const c = blockIdx.x/rows;
+    int const r = blockIdx.x - c*rows;
+    double m = 0.;
+    for (int k = 0; k < Z; ++k)
+    {
+        uint64_t const slot = (uint64_t)c*Z + k;
+        double x = wave_strided_sum(partials + (slot*rows + r)*nblocks, nblocks);
+        x = mu[slot] > 0. ? x : 0.;
+        if (per_angle != nullptr && threadIdx.x == 0)
+        {
+            per_angle[slot*rows + r] = x;
+        }
+        if (six != nullptr && threadIdx.x == 0)
+        {
+            int const V = rows/2, down = r/V, lev = r - down*V;
+            double *q = six + slot*6 + 3*down;
+            if (lev == 0)
+            {
+                q[0] = x;
+                if (user < 0)
+                {
+                    q[2] = 0.;
+                }
+            }
+            if (lev == V - 1)
+            {
+                q[1] = x;
+            }
+            if (lev == user)
+            {
+                q[2] = x;
+            }
+        }
+        double const term = weight != nullptr ? weight[slot]*x : x;
+        m = k == 0 ? term : m + term;
+    }
+    if (out != nullptr && threadIdx.x == 0)
+    {
+        out[(uint64_t)c*out_stride + out_offset + r] = weight != nullptr ? m : m/(double)Z;
+    }
+}
+
 } // namespace
 
 extern "C" int grt_launch_band_profile_finish(void *stream, int ncol, int sets, int num_levels, int lw_bins, int sw_bins,
@@ -531,6 +584,21 @@ extern "C" int grt_launch_subcolumn_mean(void *stream, double const *partials, i
     }
     hipLaunchKernelGGL(subcolumn_mean_kernel, dim3((unsigned)(ncol*rows)), dim3(64), 0, (hipStream_t)stream, partials,
                        subcolumns, rows, nblocks, out, out_stride, out_offset);
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_zenith_mean(void *stream, double const *partials, int ncol, int zeniths, int rows,
+                                      unsigned nblocks, double const *mu, double const *weight, double *per_angle,
+                                      double *six, int user_level, double *out, int out_stride, int out_offset)
+{
+    if (ncol < 1 || zeniths < 1 || rows < 1 || nblocks < 1 || (uint64_t)ncol*(uint64_t)rows > 0x7fffffffull ||
+        partials == nullptr || mu == nullptr || (out == nullptr && per_angle == nullptr && six == nullptr) ||
+        (six != nullptr && (rows % 2 != 0 || user_level >= rows/2)))
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(zenith_mean_kernel, dim3((unsigned)(ncol*rows)), dim3(64), 0, (hipStream_t)stream, partials, zeniths,
+                       rows, nblocks, mu, weight, per_angle, six, user_level, out, out_stride, out_offset);
     return (int)hipGetLastError();
 }
 

@@ -21,7 +21,7 @@
 // fluxes (GRT_OUT_CHAINS), or, fused, the partial sums of the six rows, of the six rows that are also stored at every
 // point, of every level, or of every level per wavenumber bin -- and what joins gas and Rayleigh is the types of its
 // pack: nothing, GrtCloudArgs, GrtAerosolArgs or GrtSubcolumnArgs, a GrtAerosolArgs behind either form of the clouds where
-// both join, and a GrtBandArgs last where OUT is per bin.
+// both join, a GrtBandArgs last where OUT is per bin, or a GrtZenithArgs alone (several sun angles per column).
 // The in-kernel range checks of the reference are no-ops on device builds
 // (debug.h:105-116) and are not restated.
 #include <hip/hip_runtime.h>
@@ -136,13 +136,12 @@ __device__ __forceinline__ LayerRT eddington(double omega, double tau, double mu
 
 struct LayerProps { double Rdir, Tdir, Tpure, Rdif, Tdif; };
 
-__device__ __forceinline__ LayerProps layer_props(double omega, double g, double tau,
-                                                  double mu_dir, double mu_dif)
+// shortwave.c:86-89.  With g = 0 exactly -- every clear-sky layer: Rayleigh scattering and absorbing gases -- the
+// scaling is the identity in floating point too (g/(g + 1) = 0, f = 0, (1 - 0) omega/(1 - omega 0) = omega/1,
+// tau (1 - 0) = tau: each step exact), so the two divisions are skipped and the same doubles go on
+__device__ __forceinline__ void delta_scaling(double omega, double g, double tau, double &os, double &gs, double &ts)
 {
-    // shortwave.c:86-89.  With g = 0 exactly -- every clear-sky layer: Rayleigh scattering and absorbing gases -- the
-    // scaling is the identity in floating point too (g/(g + 1) = 0, f = 0, (1 - 0) omega/(1 - omega 0) = omega/1,
-    // tau (1 - 0) = tau: each step exact), so the two divisions are skipped and the same doubles go on
-    double gs = g, os = omega, ts = tau;
+    gs = g; os = omega; ts = tau;
     if (g != 0. || !(omega*0. == 0.))           // (an infinite or NaN omega takes the expressions as written)
     {
         gs = g/(g + 1.);
@@ -150,6 +149,13 @@ __device__ __forceinline__ LayerProps layer_props(double omega, double g, double
         os = (1. - f)*omega/(1. - omega*f);
         ts = tau*(1. - omega*f);
     }
+}
+
+__device__ __forceinline__ LayerProps layer_props(double omega, double g, double tau,
+                                                  double mu_dir, double mu_dif)
+{
+    double gs, os, ts;
+    delta_scaling(omega, g, tau, os, gs, ts);
     ExpKt shared = {0., 0., 0., false};
     LayerRT const d = eddington<true>(os, ts, mu_dir, gs, shared);
     LayerRT const s = eddington<false>(os, ts, mu_dif, gs, shared);
@@ -238,6 +244,20 @@ __device__ __forceinline__ void put_level(Sink &sink, int lev, double up, double
     sink.put(lev, true, tsi*dn);
 }
 
+// the cosine of the zenith angle of a grid row: the column's, or -- zenith instances -- the row's angle's
+template <typename... Joins>
+__device__ __forceinline__ double row_mu(GrtSwArgs const &a, SolverRow const &row, Joins const &...joins)
+{
+    if constexpr (has<GrtZenithArgs, Joins...>)
+    {
+        return pick<GrtZenithArgs>(joins...).mu[row.slot];
+    }
+    else
+    {
+        return a.mu_dir[row.col];
+    }
+}
+
 // OUT fused (GRT_OUT_ROWS and after): the clear-sky tail in one kernel -- tau, omega, g of a layer are formed in registers
 // from tau_gas and the Rayleigh optical depth (LayerOptics: identical values), the first sweep's reflectances are parked
 // in a scratch block instead of the output rows, nothing spectral is written and the six integrated output rows leave as
@@ -270,8 +290,21 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Joins... 
     double const *tau = a.tau + (uint64_t)col*a.optics_stride + ii;
     double const *omega = FUSED ? nullptr : a.omega + (uint64_t)col*a.optics_stride + ii;
     double const *g = FUSED ? nullptr : a.g + (uint64_t)col*a.optics_stride + ii;
-    double const mu_dir = a.mu_dir[col];
+    double const mu_dir = row_mu(a, row, joins...);
     double const mu_dif = a.mu_dif;
+    if constexpr (has<GrtZenithArgs, Joins...>)
+    {
+        // a night sample (uniform per workgroup): +0.0 partial sums in the row's slot, nothing solved
+        if (!(mu_dir > 0.))
+        {
+            int const nrows = PROFILE ? 2*a.num_levels : 6;
+            for (int r = threadIdx.x; r < nrows; r += kSolverBlock)
+            {
+                a.partials[((uint64_t)row.slot*nrows + r)*gridDim.x + blockIdx.x] = 0.;
+            }
+            return;
+        }
+    }
     // where the first sweep parks R_dir_downward / R_dif_downward of every level
     uint64_t const park_rows = 2*(uint64_t)V + 5*(uint64_t)L;
     double *fu = FUSED ? a.park + ((uint64_t)row.park*park_rows + 0)*nw + ii : a.flux_up + (uint64_t)col*a.flux_stride + ii;
@@ -388,6 +421,100 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Joins... 
         put_level(sink, lev, up, dn, scale, tsi);
     }
     sink.finish(a);
+}
+
+// ---- several sun angles per column on one walk through the layers (grt_launch_sw_zeniths) ----
+// Of sw_kernel<GRT_OUT_ROWS>'s one sweep, a layer's optics (tau_gas, continua, Rayleigh: LayerOptics), its delta-scaling,
+// its diffuse Eddington solution with k and exp(+-t k), and C, Ru, Tu of the sweep depend on the optics alone; the angle's
+// own are the direct-beam solution, dir, dif, Rd and the scale at the surface.  Grid row y is a column and a chunk of ZN
+// consecutive angles: the thread does the shared part of a layer once and the angle's part ZN times, each in sw_kernel's
+// expressions and order on the same doubles (exp(+-t k) is a function of its argument, whichever call evaluates it
+// first), so every angle's partial sums are the zenith instance's of sw_kernel<GRT_OUT_ROWS>, bit for bit.  Angles past
+// the column's last and night angles (mu <= 0) are skipped by flags that are uniform per workgroup; a night angle's slot
+// gets +0.0.
+template <int ZN>
+__global__ __launch_bounds__(kSolverBlock) void sw_zenith_kernel(GrtSwArgs a, GrtZenithArgs zn)
+{
+    uint64_t const i = (uint64_t)blockIdx.x*kSolverBlock + threadIdx.x;
+    bool const live = i < a.nw;
+    uint64_t const ii = live ? i : a.nw - 1;      // (idle lanes of the last block follow along, weight 0)
+    int const Z = zn.zeniths, chunks = (Z + ZN - 1)/ZN;
+    int const y = blockIdx.y;
+    int const col = y/chunks;
+    int const k0 = (y - col*chunks)*ZN;
+    int const L = a.num_levels - 1;
+    double const mu_dif = a.mu_dif;
+    double mu[ZN];
+    bool day[ZN];
+    bool any = false;
+#pragma unroll
+    for (int u = 0; u < ZN; ++u)
+    {
+        mu[u] = k0 + u < Z ? zn.mu[(uint64_t)col*Z + k0 + u] : 0.;
+        day[u] = mu[u] > 0.;
+        any = any || day[u];
+    }
+    double dir[ZN], dif[ZN], Rd[ZN];
+#pragma unroll
+    for (int u = 0; u < ZN; ++u)
+    {
+        dir[u] = 1.; dif[u] = 0.; Rd[u] = 0.;
+    }
+    double Ru = 0., Tu = 1.;
+    if (any)
+    {
+        LayerOptics<true, false, false> const optics(a, GrtCloudArgs{}, col, col, ii);
+        for (int j = 0; j < L; ++j)
+        {
+            double t, om, gg, os, gs, ts;
+            optics.at(j, t, om, gg);
+            delta_scaling(om, gg, t, os, gs, ts);
+            ExpKt shared = {0., 0., 0., false};
+            LayerRT const s = eddington<false>(os, ts, mu_dif, gs, shared);
+            double const C = 1./(1. - s.R*Ru);
+#pragma unroll
+            for (int u = 0; u < ZN; ++u)
+            {
+                if (day[u])
+                {
+                    ExpKt mine = shared;
+                    LayerRT const d = eddington<true>(os, ts, mu[u], gs, mine);
+                    Rd[u] = Rd[u] + Tu*((dir[u]*d.R + dif[u]*s.R)*C);
+                    dif[u] = (dir[u]*d.R*Ru + dif[u])*s.T*C + dir[u]*(d.T - d.Tpure);      // shortwave.c:312-316
+                    dir[u] *= d.Tpure;
+                }
+            }
+            Tu = Tu*(s.T*C);
+            Ru = s.R + s.T*s.T*Ru*C;                                                         // :299-306
+        }
+    }
+    double const alb_dir = a.alb_dir[(uint64_t)col*a.alb_stride + ii], alb_dif = a.alb_dif[(uint64_t)col*a.alb_stride + ii];
+    double const solar = a.solar[ii], tsi = a.tsi[col];
+#pragma unroll
+    for (int u = 0; u < ZN; ++u)
+    {
+        if (k0 + u >= Z)
+        {
+            continue;
+        }
+        int const slot = col*Z + k0 + u;
+        if (!day[u])
+        {
+            if (threadIdx.x < 6)
+            {
+                a.partials[((uint64_t)slot*6 + threadIdx.x)*gridDim.x + blockIdx.x] = 0.;
+            }
+            continue;
+        }
+        LevelSink<true, false> sink(a, slot, i, live);
+        double const scale = solar*mu[u];
+        double up_s, dn_s;                                                          // :318-329 at the surface
+        level_flux(dir[u], dif[u], Ru, alb_dir, alb_dif, up_s, dn_s);
+        put_level(sink, 0, Rd[u] + Tu*up_s, 1., scale, tsi);
+        put_level(sink, L, up_s, dn_s, scale, tsi);
+        __syncthreads();                            // (block_partials' LDS is the angle before's: every wave has read it)
+        sink.finish(a);
+    }
 }
 
 // ---- spectral form of few columns: the layer properties first, by one thread per (layer, wavenumber) ----
@@ -580,7 +707,26 @@ extern "C" int grt_launch_sw(void *stream, GrtSolverInstance const *in, GrtSwArg
         return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns, *in->aerosols);
     case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
         return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->aerosols);
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->zeniths);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->zeniths);
     default:
         return (int)hipErrorInvalidValue;
     }
+}
+
+extern "C" int grt_launch_sw_zeniths(void *stream, GrtSwArgs const *a, GrtZenithArgs const *z)
+{
+    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (!grt_solver_instance_ok(in, *a) || z == nullptr || z->mu == nullptr || z->zeniths < 1 || !grt_sw_one_sweep(a))
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    uint64_t const rows = (uint64_t)a->ncol*(uint64_t)((z->zeniths + GRT_ZENITH_CHUNK - 1)/GRT_ZENITH_CHUNK);
+    if (rows > 65535u)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL((sw_zenith_kernel<GRT_ZENITH_CHUNK>), dim3(grt_solver_blocks(a->nw), (unsigned)rows, 1),
+                       dim3(kSolverBlock), 0, (hipStream_t)stream, *a, *z);
+    return (int)hipGetLastError();
 }

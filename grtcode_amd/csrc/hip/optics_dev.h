@@ -178,7 +178,9 @@ __device__ __forceinline__ GrtCloudArgs pick_clouds(Pack const &...pack)
 
 // What grid row blockIdx.y stands for: col, the column whose gas state (tau_gas, temperatures, sun) and aerosol table it
 // reads; tab, its cloud tables' column; slot, its partial sums' column; park, its rows of the shortwave park block.  All four are
-// blockIdx.y but in the subcolumn instances (GrtSubcolumnArgs: row y is column y / count, subcolumn first + y % count).
+// blockIdx.y but in the subcolumn instances (GrtSubcolumnArgs: row y is column y / count, subcolumn first + y % count) and
+// in the zenith instances (GrtZenithArgs: row y is column y / count, angle first + y % count; the slot, c zeniths + k, is
+// also where the row's cosine of the zenith angle lies in the join's mu).
 struct SolverRow { int col, tab, slot, park; };
 
 template <typename... Pack>
@@ -191,6 +193,13 @@ __device__ __forceinline__ SolverRow solver_row(int ncol, Pack const &...pack)
         int const c = y/sc.count;
         int const s = sc.first + (y - c*sc.count);
         return SolverRow{c, s*ncol + c, c*sc.subcolumns + s, y};
+    }
+    else if constexpr (has<GrtZenithArgs, Pack...>)
+    {
+        GrtZenithArgs const zn = pick<GrtZenithArgs>(pack...);
+        int const c = y/zn.count;
+        int const k = zn.first + (y - c*zn.count);
+        return SolverRow{c, c, c*zn.zeniths + k, y};
     }
     else
     {

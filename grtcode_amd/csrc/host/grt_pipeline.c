@@ -263,6 +263,7 @@ static void grt_pipeline_release(GrtPipeline_t **pipeline)
         grt_keyed_table_free(p, &p->band[b].bin_table);
         grt_keyed_table_free(p, &p->band[b].surf_map);
     }
+    grt_staging_free(p, &p->zen);
     grt_staging_free(p, &p->surf);
     grt_staging_free(p, &p->aer);
     grt_staging_free(p, &p->cloud);
@@ -341,8 +342,9 @@ static int check_lane(GrtPipeline_t const *p)
 }
 
 /* What grt_pipeline_run and grt_pipeline_run_profiles check and stage alike: the arguments, the lane, and the small
-   per-column inputs, uploaded to small.d on the library stream. */
-static int stage_columns(GrtPipeline_t *p, GrtColumns_t const *cols)
+   per-column inputs, uploaded to small.d on the library stream.  own_sun: the run brings its sun angles itself
+   (grt_pipeline_run_zeniths), and the columns' cos_zenith is not read. */
+static int stage_columns(GrtPipeline_t *p, GrtColumns_t const *cols, int own_sun)
 {
     GRT_REQUIRE_RANGE(cols->ncol, 1, p->max_cols);
     GRT_REQUIRE_EQ(cols->num_levels, p->num_levels);
@@ -385,9 +387,12 @@ static int stage_columns(GrtPipeline_t *p, GrtColumns_t const *cols)
     }
     if (p->band[1].gas != NULL)
     {
-        GRT_REQUIRE_PTR(cols->cos_zenith);
         GRT_REQUIRE_PTR(cols->total_solar_irradiance);
-        for (int c = 0; c < C; ++c)
+        if (!own_sun)
+        {
+            GRT_REQUIRE_PTR(cols->cos_zenith);
+        }
+        for (int c = 0; c < C && !own_sun; ++c)
         {
             if (!(cols->cos_zenith[c] > 0. && cols->cos_zenith[c] <= 1.))
             {
@@ -395,7 +400,10 @@ static int stage_columns(GrtPipeline_t *p, GrtColumns_t const *cols)
                          " (night columns are skipped by the caller: driver.c:706).", cols->cos_zenith[c], c);
             }
         }
-        memcpy(p->small.h + p->off_mu, cols->cos_zenith, sizeof(double)*(size_t)C);
+        if (!own_sun)
+        {
+            memcpy(p->small.h + p->off_mu, cols->cos_zenith, sizeof(double)*(size_t)C);
+        }
         memcpy(p->small.h + p->off_tsi, cols->total_solar_irradiance, sizeof(double)*(size_t)C);
     }
     GRT_TRY(grt_staging_upload(p, &p->small, p->small_doubles));
@@ -472,6 +480,7 @@ typedef struct GrtJoin
     GrtAerosols_t const *aerosols;
     int subcolumns;
     unsigned sets;
+    GrtZeniths_t const *zeniths;       /* grt_pipeline_run_zeniths: the shortwave's clean set is the mean over these angles */
 } GrtJoin;
 
 #define GRT_SKY_ALL (GRT_SKY_CLEAN | GRT_SKY_AEROSOL | GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL)
@@ -514,9 +523,14 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
         GRT_FAIL(GRTCODE_VALUE_ERR, "%d columns asked for, the surface in force (grt_pipeline_set_surface) has %d.",
                  cols->ncol, p->surface_ncol);
     }
-    GRT_TRY(stage_columns(p, cols));
+    GRT_TRY(stage_columns(p, cols, join->zeniths != NULL));
     int const C = cols->ncol, S = join->subcolumns > 0 ? join->subcolumns : 1;
     unsigned const sets = join_sets(join);
+    GrtZenithRun zr;
+    if (join->zeniths != NULL)
+    {
+        GRT_TRY(grt_stage_zeniths(p, join->zeniths, C, &zr));
+    }
     if (cl != NULL && join->sampler != NULL)
     {
         /* (the kernel writes the tables where grt_stage_clouds puts them) */
@@ -534,6 +548,10 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
     for (int bi = 0; bi < 2; ++bi)
     {
         GrtBand *b = &p->band[bi];
+        if (rows->out == NULL && (bi == 0 || b->gas == NULL))
+        {
+            continue;                  /* (grt_pipeline_run_zeniths for the angles' own rows alone: no longwave, no mean) */
+        }
         if (b->gas == NULL)
         {
             if (!rows->profile)
@@ -584,13 +602,24 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
             }
             ps.aer = ps.aer_pass && band_aer ? &aa : NULL;
             ps.clouds = (bit & (GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL)) != 0 ? &ca : NULL;
-            GRT_TRY(ps.clouds != NULL && join->subcolumns > 0 ? grt_band_solve_subcolumns(p, b, bi, C, S, &ps) :
-                    grt_band_solve(p, b, bi, C, &ps));
+            if (bi == 1 && join->zeniths != NULL)
+            {
+                zr.per_angle = rows->profile ? join->zeniths->zenith_level_fluxes_dev : join->zeniths->zenith_fluxes_dev;
+                zr.six = rows->profile ? join->zeniths->zenith_fluxes_dev : NULL;
+                GRT_TRY(grt_band_solve_zeniths(p, b, C, &ps, &zr));
+            }
+            else
+            {
+                GRT_TRY(ps.clouds != NULL && join->subcolumns > 0 ? grt_band_solve_subcolumns(p, b, bi, C, S, &ps) :
+                        grt_band_solve(p, b, bi, C, &ps));
+            }
             ++ps.set;
         }
     }
     return GRTCODE_SUCCESS;
 }
+
+/* ---- the entry points -------------------------------------------------------------------------------------------- */
 
 /* the checks the entry points share (each in that entry point's own order) */
 static int check_columns(GrtPipeline_t const *p, GrtColumns_t const *cols)
@@ -677,6 +706,83 @@ EXTERN int grt_pipeline_run_profiles(GrtPipeline_t *p, GrtColumns_t const *cols,
     GRT_TRY(output_form(p, 1, level_fluxes_dev, fluxes_dev, &rows));
     GRT_TRY(pipeline_run(p, cols, &join, &rows));
     GRT_TRY(finish_profiles(p, cols->ncol, &rows, heating_dev, fluxes_dev));
+    return GRTCODE_SUCCESS;
+}
+
+/* grt_ext.h: the clear-clean set under several sun angles per column, on one gas-optics pass per band */
+EXTERN int grt_pipeline_run_zeniths(GrtPipeline_t *p, GrtColumns_t const *cols, GrtZeniths_t const *zn,
+                                    fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    if (zn == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "no sun angles (GrtZeniths_t is NULL).%s", "");
+    }
+    if (zn->num_zeniths < 1 || zn->num_zeniths > GRT_MAX_ZENITHS)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d sun angles per column asked for: 1 to %d.", zn->num_zeniths, GRT_MAX_ZENITHS);
+    }
+    if (zn->cos_zenith == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "cos_zenith is NULL: the sun angles [ncol][%d] are the input.", zn->num_zeniths);
+    }
+    int const profile = level_fluxes_dev != NULL;
+    if (!profile && fluxes_dev == NULL && zn->zenith_fluxes_dev == NULL && zn->zenith_level_fluxes_dev == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "fluxes_dev, level_fluxes_dev and both per-angle outputs are NULL: nothing to write.%s",
+                 "");
+    }
+    if (!profile && zn->zenith_level_fluxes_dev != NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "zenith_level_fluxes_dev is given in the six-row form (level_fluxes_dev is NULL).%s", "");
+    }
+    GRT_TRY(check_columns(p, cols));
+    if (cols->num_levels != p->num_levels)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "columns of %d levels: this pipeline has %d.", cols->num_levels, p->num_levels);
+    }
+    if (profile)
+    {
+        GRT_TRY(check_two_levels(p));
+    }
+    size_t const n = (size_t)cols->ncol*(size_t)zn->num_zeniths;
+    for (size_t k = 0; k < n; ++k)
+    {
+        if (!(zn->cos_zenith[k] <= 1.))
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "cosine of zenith angle %zu of column %zu (%e) is NaN or above 1.",
+                     k % (size_t)zn->num_zeniths, k/(size_t)zn->num_zeniths, zn->cos_zenith[k]);
+        }
+        if (zn->weight != NULL && !(zn->weight[k] >= 0.))
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "weight of zenith angle %zu of column %zu (%e) is negative or NaN.",
+                     k % (size_t)zn->num_zeniths, k/(size_t)zn->num_zeniths, zn->weight[k]);
+        }
+    }
+    /* grt_pipeline_run's layout, or grt_pipeline_run_profiles' three; the shortwave rows the mean over the angles */
+    GrtJoin const join = {.zeniths = zn};
+    GrtPass rows;
+    memset(&rows, 0, sizeof(rows));
+    rows.profile = profile;
+    rows.out = profile ? level_fluxes_dev : fluxes_dev;
+    rows.sets = 1;
+    rows.out_stride = grt_set_offset(p, profile);
+    GRT_TRY(pipeline_run(p, cols, &join, &rows));
+    GRT_TRY(finish_profiles(p, cols->ncol, &rows, heating_dev, fluxes_dev));
+    if (p->band[1].gas == NULL)
+    {
+        /* no shortwave band: every angle's rows are zeros, as the band's rows of the mean are */
+        void *s = grt_dev_stream(p->device);
+        if (zn->zenith_fluxes_dev != NULL)
+        {
+            GRT_TRY(grt_dev_zero(p->device, zn->zenith_fluxes_dev, sizeof(double)*n*GRT_FLUXES_PER_BAND, s));
+        }
+        if (zn->zenith_level_fluxes_dev != NULL)
+        {
+            GRT_TRY(grt_dev_zero(p->device, zn->zenith_level_fluxes_dev, sizeof(double)*n*2*(size_t)p->num_levels, s));
+        }
+    }
     return GRTCODE_SUCCESS;
 }
 

@@ -42,6 +42,46 @@ void grt_staging_free(GrtPipeline_t *p, GrtStaging *st)
     grt_dev_event_destroy(p->device, &st->uploaded);
 }
 
+/* The sun angles of a batch (grt_pipeline_run_zeniths) into p->zen and onto the device: the cosines [C][Z], the weights
+   [C][Z] if given, and the cosines angle-major [Z][C] for the materialised form's loop over the angles, where a night
+   sample stands as its column's last day angle before it, else its first one after it, else 1 (the solver then has a
+   sun to solve for; the mean kernel zeroes the sample) */
+int grt_stage_zeniths(GrtPipeline_t *p, GrtZeniths_t const *zn, int C, GrtZenithRun *zr)
+{
+    size_t const Z = (size_t)zn->num_zeniths, n = (size_t)C*Z;
+    GRT_TRY(grt_staging_reserve(p, &p->zen, 3*n, 3*(size_t)p->max_cols*GRT_MAX_ZENITHS));
+    double *h = p->zen.h;
+    memcpy(h, zn->cos_zenith, sizeof(double)*n);
+    if (zn->weight != NULL)
+    {
+        memcpy(h + n, zn->weight, sizeof(double)*n);
+    }
+    else
+    {
+        memset(h + n, 0, sizeof(double)*n);
+    }
+    for (size_t c = 0; c < (size_t)C; ++c)
+    {
+        double const *mu = zn->cos_zenith + c*Z;
+        double stand_in = 1.;
+        for (size_t k = Z; k-- > 0;)
+        {
+            stand_in = mu[k] > 0. ? mu[k] : stand_in;        /* (ends as the column's first day angle) */
+        }
+        for (size_t k = 0; k < Z; ++k)
+        {
+            stand_in = mu[k] > 0. ? mu[k] : stand_in;
+            h[2*n + k*(size_t)C + c] = stand_in;
+        }
+    }
+    GRT_TRY(grt_staging_upload(p, &p->zen, 3*n));
+    zr->zeniths = zn->num_zeniths;
+    zr->mu = p->zen.d;
+    zr->weight = zn->weight != NULL ? p->zen.d + n : NULL;
+    zr->mu_by_angle = p->zen.d + 2*n;
+    return GRTCODE_SUCCESS;
+}
+
 /* t->table for `key`: as it is when it was built for the same bytes, else `ints` ints written by fill(ctx, .) on the host
    and uploaded.  The stored key is dropped before the device table is touched and set again only when the whole call
    succeeded, so a failure half way leaves a table that the next call rebuilds, whatever its key. */

@@ -55,6 +55,9 @@ enum
        (shortwave), and -- shortwave, when a diffuse albedo was given -- the diffuse albedo */
     GRT_SCRATCH_SURF_ROWS,
     GRT_SCRATCH_SURF_ROWS_DIF,
+    /* grt_pipeline_run_zeniths, shortwave: [max_cols][Z][6 or 2 V][nblocks] partial sums of every angle (materialised
+       form: [max_cols][Z][6 or 2 V] integrated rows) */
+    GRT_SCRATCH_ZEN_PARTIALS,
     GRT_SCRATCH_COUNT
 };
 
@@ -110,6 +113,9 @@ struct GrtPipeline
     /* grt_pipeline_set_surface's slope and intercept entries: the emissivity's [cols][NS + 1][2], then the direct albedo's,
        then the diffuse albedo's */
     GrtStaging surf;
+    /* grt_pipeline_run_zeniths' angles: cos_zenith [cols][Z], the weights [cols][Z], then -- materialised form -- the
+       cosines angle-major [Z][cols], night samples replaced by a day angle of their column */
+    GrtStaging zen;
     int surface_ncol;      /* columns of the surface in force; 0: none (the creation-time arrays apply) */
 };
 
@@ -144,6 +150,18 @@ typedef struct GrtPass
     GrtBins const *bins;
 } GrtPass;
 
+/* The sun angles of a grt_pipeline_run_zeniths call, staged (grt_stage_zeniths): Z per column, their cosines and weights
+   on the device, and where every angle's own rows go. */
+typedef struct GrtZenithRun
+{
+    int zeniths;
+    double const *mu;              /* DEVICE [ncol][Z] */
+    double const *weight;          /* DEVICE [ncol][Z], or NULL */
+    double const *mu_by_angle;     /* DEVICE [Z][ncol], a day angle everywhere (materialised form) */
+    double *per_angle;             /* DEVICE [ncol][Z][6 or 2 V], or NULL */
+    double *six;                   /* profile form: DEVICE [ncol][Z][6], every angle's six rows from its levels, or NULL */
+} GrtZenithRun;
+
 /* the doubles from one set of a column to the next */
 static inline int grt_set_offset(GrtPipeline_t const *p, int profile)
 {
@@ -175,10 +193,12 @@ GRT_PRIVATE int grt_check_grid(char const *name, char const *kind, char const *n
                                fp_t const *grid, fp_t const *values);
 GRT_PRIVATE int grt_check_surface(GrtPipeline_t const *p, GrtSurface_t const *sf, int np[2]);
 GRT_PRIVATE int grt_stage_surface(GrtPipeline_t *p, GrtSurface_t const *sf, int const np[2]);
+GRT_PRIVATE int grt_stage_zeniths(GrtPipeline_t *p, GrtZeniths_t const *zn, int C, GrtZenithRun *zr);
 GRT_PRIVATE int grt_band_bins(GrtPipeline_t *p, GrtBand *b, int const *edges, int nbins, int rows);
 
 /* grt_pipeline_solve.c */
 GRT_PRIVATE int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps);
 GRT_PRIVATE int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S, GrtPass const *ps);
+GRT_PRIVATE int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *ps, GrtZenithRun const *zr);
 
 #endif

@@ -24,7 +24,7 @@ static int pass_spectral(GrtPass const *ps)
 static GrtSolverInstance pass_instance(GrtPipeline_t const *p, GrtPass const *ps, GrtBandArgs const *bn,
                                        GrtSubcolumnArgs const *sc)
 {
-    GrtSolverInstance in = {GRT_OUT_CHAINS, NULL, NULL, NULL, NULL};
+    GrtSolverInstance in = {GRT_OUT_CHAINS, NULL, NULL, NULL, NULL, NULL};
     if (!p->keep_spectra)
     {
         in.out = pass_spectral(ps) ? GRT_OUT_ROWS_POINTS : (bn != NULL ? GRT_OUT_LEVEL_BINS :
@@ -484,5 +484,80 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
     GRT_TRY(grt_dev_check(grt_launch_flux_mean(s, per, flux_sum, S, b->flux_up), "flux mean kernel"));
     GRT_TRY(grt_dev_check(grt_launch_flux_mean(s, per, flux_sum + all, S, b->flux_down), "flux mean kernel"));
     GRT_TRY(integrate_rows(p, b, bi, C, ps));
+    return GRTCODE_SUCCESS;
+}
+
+/* The shortwave of grt_pipeline_run_zeniths: the clear-clean pass under zr->zeniths sun angles per column on this run's
+   tau_gas, every angle's rows to zr->per_angle and their weighted mean to out as grt_band_solve writes its rows (either
+   may be NULL).  Fused form: each angle's partial sums in zen_partials -- six rows in one sweep: the shared-layer kernel,
+   or, GRT_ZENITH_SHARED=0 in the environment (read per call), the zenith instance of the six-row solver over C x Z grid
+   rows; otherwise the zenith instance, the two-sweep forms C x count angles at a time in the band's park block, count =
+   what fits in its max_cols, in stream order (GRT_TAG_ZENITH_SW) -- then the fixed-order mean (GRT_TAG_ZENITH_MEAN).
+   Materialised form: per angle the spectral solver on the pass's optics and the row-wise trapezoid into the angle's
+   rows of zen_partials; then the same mean kernel (one block per row). */
+int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *ps, GrtZenithRun const *zr)
+{
+    int const Z = zr->zeniths, rows = pass_rows(p, ps), out_offset = pass_offset(p, ps, 1);
+    void *s = grt_dev_stream(p->device);
+    GrtScratch *block = &b->scratch[GRT_SCRATCH_ZEN_PARTIALS];
+    unsigned nblocks = 1;
+    if (!p->keep_spectra)
+    {
+        nblocks = b->nblocks;
+        GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*(size_t)Z*(size_t)rows*nblocks, NULL));
+        /* (in points at za: the loop below walks za.first and za.count, which the launcher alone reads) */
+        GrtZenithArgs za = {zr->mu, Z, 0, 0};
+        GrtSolverInstance in = pass_instance(p, ps, NULL, NULL);
+        in.zeniths = &za;
+        SolverArgs a;
+        GRT_TRY(solver_args(p, b, 1, C, ps, &in, block->d, &a));
+        char const *env = getenv("GRT_ZENITH_SHARED");
+        int const parks = grt_sw_parks(&in, &a.sw);
+        int const shared = !ps->profile && !parks && !(env != NULL && env[0] == '0');
+        /* (grid rows; a park block of max_cols columns) */
+        int group = parks ? p->max_cols/C : 65535/C;
+        group = group < Z ? group : Z;
+        int const slot = grt_profile_begin(s, GRT_TAG_ZENITH_SW);
+        int krc = 0;
+        if (shared)
+        {
+            krc = grt_launch_sw_zeniths(s, &a.sw, &za);
+        }
+        for (za.first = 0; !shared && za.first < Z && krc == 0; za.first += group)
+        {
+            za.count = Z - za.first < group ? Z - za.first : group;
+            krc = grt_launch_sw(s, &in, &a.sw);
+        }
+        grt_profile_end(s, slot);
+        GRT_TRY(grt_dev_check(krc, "shortwave zenith kernel"));
+    }
+    else
+    {
+        GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*(size_t)Z*(size_t)rows, NULL));
+        GRT_TRY(pass_optics(p, b, C, ps));
+        if (ps->profile)
+        {
+            GRT_TRY(level_rows(p, b));
+        }
+        GrtSolverInstance const in = pass_instance(p, ps, NULL, NULL);
+        SolverArgs a;
+        GRT_TRY(solver_args(p, b, 1, C, ps, &in, NULL, &a));
+        for (int k = 0; k < Z; ++k)
+        {
+            a.sw.mu_dir = zr->mu_by_angle + (size_t)k*C;
+            int const slot = grt_profile_begin(s, GRT_TAG_ZENITH_SW);
+            int const krc = grt_launch_sw(s, &in, &a.sw);
+            grt_profile_end(s, slot);
+            GRT_TRY(grt_dev_check(krc, "shortwave kernel"));
+            GRT_TRY(grt_dev_check(grt_launch_integrate_rows(s, (double const *const *)(ps->profile ? b->level_rows_d : b->rows_d),
+                                                            C*rows, b->n, b->gas->grid.dw, block->d, rows, Z*rows, k*rows),
+                                  "spectral integration kernel"));
+        }
+    }
+    int const mslot = grt_profile_begin(s, GRT_TAG_ZENITH_MEAN);
+    int const mrc = grt_launch_zenith_mean(s, block->d, C, Z, rows, nblocks, zr->mu, zr->weight, zr->per_angle, zr->six,
+                                           p->user_level, ps->out, ps->out_stride, out_offset);
+    grt_profile_end(s, mslot);
+    GRT_TRY(grt_dev_check(mrc, "zenith mean kernel"));
     return GRTCODE_SUCCESS;
 }

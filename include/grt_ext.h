@@ -555,6 +555,48 @@ typedef struct GrtSurface
 } GrtSurface_t;
 EXTERN int grt_pipeline_set_surface(GrtPipeline_t *pipeline, GrtSurface_t const *surface);
 
+/* ---- several sun angles per column on one gas-optics pass -----------------------------------------------------------
+ * The clear-clean set (gas and Rayleigh) of grt_pipeline_run or grt_pipeline_run_profiles under Z sun angles per column:
+ * a diurnal mean, a zenith sweep, a training set.  The optical depths do not depend on the sun, so each band's gas optics
+ * run once per column; the longwave is solved once, the shortwave once per angle, and the shortwave rows that leave are
+ * the weighted mean over the angles.  columns->cos_zenith is not read (it may be NULL); total_solar_irradiance stays per
+ * column.  A cos_zenith <= 0 is a night sample: its shortwave rows are +0.0 and nothing is solved for it.  Two forms, in
+ * grt_pipeline_run_subcolumns' manner:
+ *   level_fluxes_dev == NULL (six rows): fluxes_dev [ncol][GRT_FLUXES_PER_COLUMN] in grt_pipeline_run's layout (may be NULL
+ *                    when zenith_fluxes_dev is given: then neither the longwave nor the mean is formed); its shortwave
+ *                    sweep rule;
+ *   level_fluxes_dev != NULL (profiles): grt_pipeline_run_profiles' three layouts, the heating rates and the six rows
+ *                    formed from the mean level fluxes; the shortwave always takes two sweeps.
+ * The mean is taken in a fixed order: each angle's blocks as the other entry points add them, then the angles k = 0 ..
+ * Z - 1; without weights the sum and one division by Z (night samples included), with weights sum w_k F_k, each product
+ * rounded before it is added.  With Z = 1 and no weights every value is, bit for bit in the deterministic mode,
+ * grt_pipeline_run's or grt_pipeline_run_profiles' for that cos_zenith.  A surface set with grt_pipeline_set_surface
+ * applies; a pipeline without a shortwave band runs the longwave and zeroes the shortwave outputs.
+ * The production form (keep_spectra = 0) solves the angles in the zenith instances of the shortwave solver, grid row =
+ * (column, angle) -- the two-sweep forms in as many launches as the park block of max_columns columns needs -- or, six
+ * rows in one sweep, in the shared-layer kernel, which walks the layers once for GRT_ZENITH_CHUNK angles (k_shortwave.hip;
+ * GRT_ZENITH_SHARED=0 in the environment, read per call: the zenith instance instead, the same bits), all under
+ * GRT_TAG_ZENITH_SW, and reduces with a deterministic kernel (GRT_TAG_ZENITH_MEAN); it allocates per band
+ * [max_columns][Z][6 or 2 V][blocks] partial sums at the first call that needs more than it holds.  keep_spectra = 1:
+ * the literal loop -- per angle the spectral solver and the row-wise trapezoid (a column's night angle runs on its last
+ * day angle before it, else its first one after it, and is zeroed where the mean is taken); afterwards
+ * grt_pipeline_views shows each column's last day angle's fluxes.
+ * GRTCODE_VALUE_ERR, with nothing launched and the outputs untouched, for: num_zeniths outside 1 .. GRT_MAX_ZENITHS; a
+ * NULL cos_zenith, or an entry that is NaN or above 1; a weight that is negative or NaN; fluxes_dev, level_fluxes_dev and
+ * both per-angle outputs all NULL; zenith_level_fluxes_dev in the six-row form; what grt_pipeline_run and
+ * grt_pipeline_run_profiles refuse in ncol and the levels.  Asynchronous on the pipeline's lane. */
+#define GRT_MAX_ZENITHS 64
+typedef struct GrtZeniths
+{
+    int num_zeniths;                    /* Z, 1 .. GRT_MAX_ZENITHS */
+    fp_t const *cos_zenith;             /* HOST [ncol][Z]; a value <= 0 is a night sample: its shortwave rows are +0.0 */
+    fp_t const *weight;                 /* HOST [ncol][Z], or NULL: the plain mean over all Z samples, night ones included */
+    fp_t *zenith_fluxes_dev;            /* DEVICE [ncol][Z][GRT_FLUXES_PER_BAND], the shortwave six rows of every angle; may be NULL */
+    fp_t *zenith_level_fluxes_dev;      /* DEVICE [ncol][Z][2][V], shortwave up then down; profile form only; may be NULL */
+} GrtZeniths_t;
+EXTERN int grt_pipeline_run_zeniths(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtZeniths_t const *zeniths,
+                                    fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev);
+
 /* ---- columns across the GPUs of one node ------------------------------------
  * One process per GPU; contiguous ceil-sized column blocks; one gather of the [columns][GRT_FLUXES_PER_COLUMN]
  * flux blocks to rank 0.  The reference fans out processes with -x/-X column ranges and merges per-shard files
@@ -628,7 +670,11 @@ enum
     /* 17 / 18 = LW / SW solver of the pass of grt_pipeline_run_sky that joins aerosol and clouds (GRT_SKY_CLOUD_AEROSOL; its
        other sets count under GRT_TAG_SOLVER_..., GRT_TAG_AEROSOL_... and GRT_TAG_ALLSKY_...) */
     GRT_TAG_SKY_LW = 17,
-    GRT_TAG_SKY_SW = 18
+    GRT_TAG_SKY_SW = 18,
+    /* 19 = the shortwave solver launches of grt_pipeline_run_zeniths, every angle's together (its longwave counts under
+       GRT_TAG_SOLVER_LW); 20 = its mean kernel */
+    GRT_TAG_ZENITH_SW = 19,
+    GRT_TAG_ZENITH_MEAN = 20
 };
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
