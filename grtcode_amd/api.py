@@ -28,7 +28,7 @@ GRT_CLOUD_PHASE, GRT_CLOUD_MODEL, GRT_CLOUD_FIELDS = 7, 8, 9   # ... of GrtCloud
 # grt_profile_read's tags (grt_ext.h: GRT_TAG_..., where each one's bracket is described)
 (TAG_GAS_LW, TAG_GAS_SW, TAG_SOLVER_LW, TAG_SOLVER_SW, TAG_CLEAR_OPTICS, TAG_FAR_LW, TAG_FAR_SW, TAG_ALLSKY_LW,
  TAG_ALLSKY_SW, TAG_BINS, TAG_SUBCOLUMN_MEAN, TAG_AEROSOL_LW, TAG_AEROSOL_SW, TAG_BAND_PROFILES, TAG_SURFACE,
- TAG_CLOUD_SAMPLER, TAG_SKY_LW, TAG_SKY_SW, TAG_ZENITH_SW, TAG_ZENITH_MEAN) = range(1, 21)
+ TAG_CLOUD_SAMPLER, TAG_SKY_LW, TAG_SKY_SW, TAG_ZENITH_SW, TAG_ZENITH_MEAN, TAG_DIRECT_BEAM) = range(1, 22)
 TAG_FAR_OFFSET = TAG_FAR_LW - TAG_GAS_LW    # from a line kernel's tag to its far-field gather's
 CLOUD_SAMPLER_TAG = TAG_CLOUD_SAMPLER
 GRT_MAX_SUBCOLUMNS = 64             # grt_pipeline_run_subcolumns: subcolumns per column, 1 .. this
@@ -38,6 +38,7 @@ GRT_ZENITH_CHUNK = 4                # csrc/grt_kernels.h: the angles one thread 
 GRT_SKY_CLEAN, GRT_SKY_AEROSOL, GRT_SKY_CLOUD, GRT_SKY_CLOUD_AEROSOL = 1, 2, 4, 8
 GRT_SKY_ALL = GRT_SKY_CLEAN | GRT_SKY_AEROSOL | GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL
 GRT_SKY_MAX_SETS = 4
+GRT_DIRECT_ROWS_PER_SET = 3         # grt_pipeline_run_sky_direct: the direct beam at TOA, surface, user level
 RETURN_CODES = ["GRTCODE_SUCCESS", "GRTCODE_INVALID_ERR", "GRTCODE_DIVBYZERO_ERR", "GRTCODE_OVERFLOW_ERR",
                 "GRTCODE_UNDERFLOW_ERR", "GRTCODE_SENTINEL_ERR", "GRTCODE_NULL_ERR", "GRTCODE_NON_NULL_ERR",
                 "GRTCODE_RANGE_ERR", "GRTCODE_VALUE_ERR", "GRTCODE_COMPILER_ERR", "GRTCODE_IO_ERR",
@@ -178,6 +179,10 @@ class GrtSky(C.Structure):
                 ("sets", C.c_uint)]
 
 
+class GrtDirectBeam(C.Structure):
+    _fields_ = [("direct_fluxes_dev", C.c_void_p), ("direct_level_fluxes_dev", C.c_void_p)]
+
+
 class GrtZeniths(C.Structure):
     _fields_ = [("num_zeniths", C.c_int), ("cos_zenith", c_double_p), ("weight", c_double_p),
                 ("zenith_fluxes_dev", C.c_void_p), ("zenith_level_fluxes_dev", C.c_void_p)]
@@ -204,7 +209,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -262,6 +267,8 @@ def load_library(path=None):
                                               C.c_void_p, C.c_void_p]
     lib.grt_pipeline_run_sky.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky), C.c_void_p, C.c_void_p,
                                          C.c_void_p]
+    lib.grt_pipeline_run_sky_direct.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky),
+                                                C.POINTER(GrtDirectBeam), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.grt_pipeline_sky_set_count.argtypes = [C.c_uint]
     if hasattr(lib, "grt_pipeline_run_zeniths"):    # (GRT_LIB_PATH may name an older library: a timing yardstick)
         lib.grt_pipeline_run_zeniths.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtZeniths), C.c_void_p,
@@ -965,15 +972,41 @@ class Pipeline:
         """The last run_aerosols(profiles=True): (clean, aerosol), allsky_profiles()' keys and shapes."""
         return self._read_profiles("aerosol_profiles", 2, ncol)
 
+    def _sky_ptrs(self, gsky, profiles):
+        """The (levels, heating, fluxes) pointers of run_sky and run_sky_direct, and the sets per column they hold."""
+        nsets = max(sky_set_count(gsky.sets), 1)
+        if profiles:
+            return self._profile_ptrs("sky_profiles", nsets), nsets
+        return [None, None, self._buffer("sky", 8 * GRT_FLUXES_PER_COLUMN * nsets * self.max_columns).ptr], nsets
+
     def run_sky(self, gcols, gsky, profiles=False):
         """grt_pipeline_run_sky into this object's device buffers: the sets gsky (make_sky) asks for, in the six-row form
         (sky_fluxes() reads it) or, profiles=True, the profile form (sky_profiles() reads it)."""
-        nsets = sky_set_count(gsky.sets)
-        if profiles:
-            ptrs = self._profile_ptrs("sky_profiles", max(nsets, 1))
-        else:
-            ptrs = [None, None, self._buffer("sky", 8 * GRT_FLUXES_PER_COLUMN * max(nsets, 1) * self.max_columns).ptr]
+        ptrs, _ = self._sky_ptrs(gsky, profiles)
         check(self.lib.grt_pipeline_run_sky(self.p, C.byref(gcols), C.byref(gsky), *ptrs))
+
+    def run_sky_direct(self, gcols, gsky, profiles=False):
+        """grt_pipeline_run_sky_direct into this object's device buffers: run_sky's outputs where run_sky puts them
+        (sky_fluxes() / sky_profiles() read them) and the direct beam of every set's shortwave: its three rows
+        (sky_direct_fluxes() reads them) and, profiles=True, every level (sky_direct_profiles() reads both)."""
+        ptrs, nsets = self._sky_ptrs(gsky, profiles)
+        V, n = self.num_levels, self.max_columns
+        name = "sky_profiles" if profiles else "sky"
+        gdirect = GrtDirectBeam(self._buffer(name + ".direct", 8 * n * nsets * GRT_DIRECT_ROWS_PER_SET).ptr,
+                                self._buffer(name + ".direct_levels", 8 * n * nsets * V).ptr if profiles else None)
+        check(self.lib.grt_pipeline_run_sky_direct(self.p, C.byref(gcols), C.byref(gsky), C.byref(gdirect), *ptrs))
+
+    def sky_direct_fluxes(self, ncol, nsets, profiles=False):
+        """The last run_sky_direct (of that form) of nsets sets: [ncol][nsets][3], the direct beam of each set's shortwave
+        at the top of the atmosphere, the surface and the user level (W m-2; +0.0 without a user level)."""
+        self.sync()
+        return self.buffers[("sky_profiles" if profiles else "sky") + ".direct"].to_host((ncol, nsets, GRT_DIRECT_ROWS_PER_SET))
+
+    def sky_direct_profiles(self, ncol, nsets):
+        """The last run_sky_direct(profiles=True) of nsets sets: dict(direct=[ncol][nsets][3], as sky_direct_fluxes(), and
+        direct_levels=[ncol][nsets][V], the direct beam at every level, top first)."""
+        return dict(direct=self.sky_direct_fluxes(ncol, nsets, profiles=True),
+                    direct_levels=self.buffers["sky_profiles.direct_levels"].to_host((ncol, nsets, self.num_levels)))
 
     def sky_fluxes(self, ncol, nsets):
         """The last six-row run_sky of nsets sets: [ncol][nsets][12], the sets in bit order, each in grt_pipeline_run's

@@ -451,6 +451,30 @@ int grt_launch_zenith_mean(void *stream, double const *partials, int ncol, int z
                            double const *mu, double const *weight, double *per_angle, double *six, int user_level,
                            double *out, int out_stride, int out_offset);
 
+/* Direct-beam form of the shortwave's fused six-row and profile forms (direct joined, with any of the cloud and aerosol
+   joins or none; grt_pipeline_run_sky_direct): the instance's arguments, sweeps and partial sums, and beside them the
+   direct beam of the sweep -- the running product of the layers' T_pure (shortwave.c:306, :323), scaled as the other rows
+   are -- at the same levels, as trapezoid partial sums of its own: three rows per slot (TOA, surface, user level) at
+   partials[(slot 3 + k) nblocks + block] in the six-row form, V rows per slot (levels top first) at
+   partials[(slot V + level) nblocks + block] in the profile form, slot as the instance's own partial sums have it.  The
+   three (V) rows ride with the six (2 V) through the same wave and workgroup sums: rows 0, L and user_level of the
+   profile form are, bit for bit, the six-row form's three, in its one sweep and in its two.  The profile form's dynamic
+   LDS is 3 V x 2 doubles per workgroup.  Shortwave only; reduced as the instance's own rows are. */
+typedef struct GrtDirectArgs
+{
+    double *partials;
+} GrtDirectArgs;
+static inline int grt_direct_args_ok(GrtDirectArgs const *d)
+{
+    return d != NULL && d->partials != NULL;
+}
+/* Materialised form: the same direct beam from the tau, omega, g a pass has left on the grid (GrtSwArgs: tau, omega, g,
+   optics_stride, mu_dir, tsi, solar), one thread per column and grid point walking the layers with the solver's own
+   T_pure; direct [ncol][V][nw], levels top first, W m-2 per cm-1. */
+int grt_launch_sw_direct_beam(void *stream, GrtSwArgs const *a, double *direct);
+/* rows [n][3] (TOA, surface, user level; +0.0 with user_level < 0) from levels [n][V] */
+int grt_launch_direct_rows(void *stream, int n, int num_levels, int user_level, double const *levels, double *rows);
+
 /* Banded profile form of the two profile forms (GRT_OUT_LEVEL_BINS, clear sky or clouds joined;
    grt_pipeline_run_band_profiles): the profile form's arguments, sweeps and park block, but every level's
    flux leaves once per wavenumber bin that has a point in the workgroup's 128 grid points.  A point weights a level's
@@ -490,7 +514,9 @@ typedef enum GrtSolverOutput
    the aerosol object, or the cloud objects of several subcolumns per column -- or the aerosol object together with either
    form of the clouds (GRT_OUT_ROWS and GRT_OUT_LEVELS: the five objects of sky_combine, optics_dev.h; the aerosol table
    stays per column whatever the subcolumn); `bins` goes with GRT_OUT_LEVEL_BINS and with nothing else; `zeniths` (the
-   shortwave's GRT_OUT_ROWS and GRT_OUT_LEVELS) goes with no other join.  The kind of instance follows from which pointers are set, and a kernel takes the structs that are
+   shortwave's GRT_OUT_ROWS and GRT_OUT_LEVELS) goes with no other join; `direct` (the shortwave's GRT_OUT_ROWS and
+   GRT_OUT_LEVELS) goes with any join of clouds and aerosols or none, and selects instances of its own: the instance
+   without it is the one it was.  The kind of instance follows from which pointers are set, and a kernel takes the structs that are
    set as arguments after its band's own.  The next joined object is a pointer here, a line in grt_solver_instance_ok
    and a case in each band's list of instances. */
 typedef struct GrtSolverInstance
@@ -501,6 +527,7 @@ typedef struct GrtSolverInstance
     GrtSubcolumnArgs const *subcolumns;
     GrtBandArgs const *bins;
     GrtZenithArgs const *zeniths;
+    GrtDirectArgs const *direct;
 } GrtSolverInstance;
 typedef enum GrtSolverJoin
 {
@@ -539,11 +566,12 @@ static inline uint64_t grt_solver_grid_rows(GrtSolverInstance const *in, int nco
     return (uint64_t)ncol*(uint64_t)(in->subcolumns != NULL ? in->subcolumns->count :
                                      (in->zeniths != NULL ? in->zeniths->count : 1));
 }
-/* its dynamic LDS: 2 V doubles per wave of its workgroup where every level leaves, that per bin of a block with bins */
+/* its dynamic LDS: 2 V doubles per wave of its workgroup where every level leaves (3 V with the direct beam), that per bin
+   of a block with bins */
 #define GRT_SOLVER_BLOCK 128
 static inline size_t grt_solver_lds(GrtSolverInstance const *in, int num_levels)
 {
-    size_t const levels = sizeof(double)*2*(size_t)num_levels*(GRT_SOLVER_BLOCK/64);
+    size_t const levels = sizeof(double)*(in->direct != NULL ? 3 : 2)*(size_t)num_levels*(GRT_SOLVER_BLOCK/64);
     return !grt_out_levels(in->out) ? 0 : (in->bins != NULL ? levels*(size_t)in->bins->block_bins : levels);
 }
 /* whether the shortwave instance takes the two sweeps and needs `park` */
@@ -667,7 +695,10 @@ inline bool grt_solver_instance_ok(GrtSolverInstance const &in, Args const &a)
     // (the sun angles join the clear-sky six-row and level forms alone)
     bool const zeniths_ok = in.zeniths == nullptr || (joined == 0 && grt_zenith_args_ok(in.zeniths) &&
                                                       (in.out == GRT_OUT_ROWS || in.out == GRT_OUT_LEVELS));
-    return zeniths_ok && a.ncol >= 1 && a.nw >= 2 && a.num_levels >= 2 &&
+    // (the direct beam leaves the six-row and level forms, under one sun per column; the longwave launcher has no such case)
+    bool const direct_ok = in.direct == nullptr || (in.zeniths == nullptr && grt_direct_args_ok(in.direct) &&
+                                                    (in.out == GRT_OUT_ROWS || in.out == GRT_OUT_LEVELS));
+    return zeniths_ok && direct_ok && a.ncol >= 1 && a.nw >= 2 && a.num_levels >= 2 &&
            cloud_forms <= 1 && joined <= (fused ? 2 : 0) && (in.bins != nullptr) == (in.out == GRT_OUT_LEVEL_BINS) &&
            (in.clouds == nullptr || grt_cloud_args_ok(in.clouds)) &&
            (in.aerosols == nullptr || grt_aerosol_args_ok(in.aerosols)) &&

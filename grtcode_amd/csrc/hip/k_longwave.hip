@@ -289,7 +289,7 @@ extern "C" unsigned grt_solver_blocks(uint64_t nw)
 extern "C" int grt_launch_lw(void *stream, GrtSolverInstance const *in, GrtLwArgs const *a)
 {
     uint64_t const cells = (uint64_t)(a->num_levels - 1)*a->nw;
-    if (!grt_solver_instance_ok(*in, *a) ||
+    if (!grt_solver_instance_ok(*in, *a) || in->direct != nullptr ||        // (the direct beam is the shortwave's)
         (in->out == GRT_OUT_LAYERS && (a->layer_terms == nullptr || cells > 0xffffffffull*kTermsBlock)))
     {
         return (int)hipErrorInvalidValue;

@@ -21,7 +21,9 @@
 // fluxes (GRT_OUT_CHAINS), or, fused, the partial sums of the six rows, of the six rows that are also stored at every
 // point, of every level, or of every level per wavenumber bin -- and what joins gas and Rayleigh is the types of its
 // pack: nothing, GrtCloudArgs, GrtAerosolArgs or GrtSubcolumnArgs, a GrtAerosolArgs behind either form of the clouds where
-// both join, a GrtBandArgs last where OUT is per bin, or a GrtZenithArgs alone (several sun angles per column).
+// both join, a GrtBandArgs last where OUT is per bin, or a GrtZenithArgs alone (several sun angles per column); a
+// GrtDirectArgs last (six rows or every level, with any of the cloud and aerosol joins) makes the instance that also
+// leaves the direct beam of its sweep (LevelSink: DIRECT).
 // The in-kernel range checks of the reference are no-ops on device builds
 // (debug.h:105-116) and are not restated.
 #include <hip/hip_runtime.h>
@@ -44,85 +46,106 @@ struct LayerRT { double R, T, Tpure; };
 // exponentials (same arguments, same values) instead of evaluating them again
 struct ExpKt { double t, tkp, tkm; bool valid; };
 
+// The gammas of the Eddington approximation (shortwave.c:226-230) for a beam of cosine mu
+struct Gammas { double g1, g2, g3; };
+
+__device__ __forceinline__ Gammas eddington_gammas(double omega, double g, double mu)
+{
+    Gammas gm;
+    gm.g1 = 0.25*(7. - omega*(4. + 3.*g));
+    gm.g2 = -0.25*(1. - omega*(4. - 3.*g));
+    gm.g3 = 0.25*(2. - 3.*g*mu);
+    return gm;
+}
+
+// T_pure of a layer for a beam of cosine mu (shortwave.c:114-168): what passes through without being absorbed or
+// scattered -- exp(-tau/mu) without scattering, else exp(-t/mu) of the optical depth t that the clamp of :137-145 leaves, and
+// 1 for a layer that holds nothing (exp(t/mu) <= 1).  The one place T_pure is worked out: eddington() below and the direct
+// beam of the materialised form (sw_direct_beam_kernel) both call it.  rest(k, t, tp, tm) runs on the way, in a scattering
+// layer that holds something: what the rest of the Eddington solution there takes over -- k, t and exp(+-t/mu).
+template <typename Rest>
+__device__ __forceinline__ double pure_transmission(double omega, double tau, double mu, Gammas const &gm, Rest &&rest)
+{
+    if (omega <= 0.0)
+    {
+        return grt_exp(-tau/mu);         // (exp_pair.h: the constants this kernel holds anyway)
+    }
+    double const k = sqrt(gm.g1*gm.g1 - gm.g2*gm.g2);
+    double t = tau;
+    double const tau_over_mu = tau/mu;
+    if (1./mu > k && tau_over_mu > kMaxExpArg)
+    {
+        t = kMaxExpArg*mu;
+    }
+    else if (tau*k > kMaxExpArg)
+    {
+        t = kMaxExpArg/k;
+    }
+    // (t is tau unless a clamp struck: the quotient above is then t/mu -- the same division of the same doubles)
+    double t_over_mu = tau_over_mu;
+    if (t != tau)
+    {
+        t_over_mu = t/mu;
+    }
+    // (the three exponential pairs of a layer -- exp(+-t/mu) here and in the other beam's call, exp(+-t k) -- each
+    // through one shared reduction and polynomial: exp_pair.h)
+    double tp, tm;
+    grt_exp_pair(t_over_mu, &tp, &tm);
+    if (tp <= 1.0)
+    {
+        return 1.;
+    }
+    rest(k, t, tp, tm);
+    return tm;
+}
+
 // shortwave.c:97-207 (+ gamma definitions :226-230).  WITH_PURE mirrors T_pure != NULL.
 template <bool WITH_PURE>
 __device__ __forceinline__ LayerRT eddington(double omega, double tau, double mu, double g, ExpKt &shared)
 {
     LayerRT r;
-    double const gamma1 = 0.25*(7. - omega*(4. + 3.*g));
-    double const gamma2 = -0.25*(1. - omega*(4. - 3.*g));
-    double const gamma3 = 0.25*(2. - 3.*g*mu);
-    r.Tpure = 0.;
-    if (omega <= 0.0)
-    {
-        r.R = 0.;
-        r.T = grt_exp(-tau/mu);         // (exp_pair.h: the constants this kernel holds anyway)
-        r.Tpure = r.T;
-    }
-    else
+    Gammas const gm = eddington_gammas(omega, g, mu);
+    double const gamma1 = gm.g1, gamma2 = gm.g2, gamma3 = gm.g3;
+    bool solved = false;
+    r.R = 0.;
+    r.Tpure = pure_transmission(omega, tau, mu, gm, [&](double k, double t, double tp, double tm)
     {
         double const gamma4 = 1. - gamma3;
         double const alpha1 = gamma1*gamma4 + gamma2*gamma3;
         double const alpha2 = gamma1*gamma3 + gamma2*gamma4;
-        double const k = sqrt(gamma1*gamma1 - gamma2*gamma2);
-        double t = tau;
-        double const tau_over_mu = tau/mu;
-        if (1./mu > k && tau_over_mu > kMaxExpArg)
+        double tkm, tkp;
+        if (shared.valid && shared.t == t)
         {
-            t = kMaxExpArg*mu;
-        }
-        else if (tau*k > kMaxExpArg)
-        {
-            t = kMaxExpArg/k;
-        }
-        // (t is tau unless a clamp struck: the quotient above is then t/mu -- the same division of the same doubles)
-        double t_over_mu = tau_over_mu;
-        if (t != tau)
-        {
-            t_over_mu = t/mu;
-        }
-        // (the three exponential pairs of a layer -- exp(+-t/mu) here and in the other beam's call, exp(+-t k) -- each
-        // through one shared reduction and polynomial: exp_pair.h)
-        double tp, tm;
-        grt_exp_pair(t_over_mu, &tp, &tm);
-        if (tp <= 1.0)
-        {
-            r.R = 0.;
-            r.T = 1.;
-            r.Tpure = 1.;
+            tkm = shared.tkm;
+            tkp = shared.tkp;
         }
         else
         {
-            double tkm, tkp;
-            if (shared.valid && shared.t == t)
-            {
-                tkm = shared.tkm;
-                tkp = shared.tkp;
-            }
-            else
-            {
-                grt_exp_pair(t*k, &tkp, &tkm);
-                shared.t = t;
-                shared.tkm = tkm;
-                shared.tkp = tkp;
-                shared.valid = true;
-            }
-            r.Tpure = tm;
-            if (omega >= 1.)
-            {
-                r.R = (1./(1. + gamma1*t))*(gamma1*t + (gamma3 - gamma1*mu)*(1. - tm));
-                r.T = 1. - r.R;
-            }
-            else
-            {
-                r.R = (omega/((1. - k*k*mu*mu)*((k + gamma1)*tkp + (k - gamma1)*tkm)))*
-                      ((1. - k*mu)*(alpha2 + k*gamma3)*tkp - (1. + k*mu)*(alpha2 - k*gamma3)*tkm -
-                      2.*k*(gamma3 - alpha2*mu)*tm);
-                r.T = tm*(1. - (omega/((1. - k*k*mu*mu)*((k + gamma1)*tkp +
-                      (k - gamma1)*tkm)))*((1. + k*mu)*(alpha1 + k*gamma4)*tkp -
-                      (1. - k*mu)*(alpha1 - k*gamma4)*tkm - 2.*k*(gamma4 + alpha1*mu)*tp));
-            }
+            grt_exp_pair(t*k, &tkp, &tkm);
+            shared.t = t;
+            shared.tkm = tkm;
+            shared.tkp = tkp;
+            shared.valid = true;
         }
+        if (omega >= 1.)
+        {
+            r.R = (1./(1. + gamma1*t))*(gamma1*t + (gamma3 - gamma1*mu)*(1. - tm));
+            r.T = 1. - r.R;
+        }
+        else
+        {
+            r.R = (omega/((1. - k*k*mu*mu)*((k + gamma1)*tkp + (k - gamma1)*tkm)))*
+                  ((1. - k*mu)*(alpha2 + k*gamma3)*tkp - (1. + k*mu)*(alpha2 - k*gamma3)*tkm -
+                  2.*k*(gamma3 - alpha2*mu)*tm);
+            r.T = tm*(1. - (omega/((1. - k*k*mu*mu)*((k + gamma1)*tkp +
+                  (k - gamma1)*tkm)))*((1. + k*mu)*(alpha1 + k*gamma4)*tkp -
+                  (1. - k*mu)*(alpha1 - k*gamma4)*tkm - 2.*k*(gamma4 + alpha1*mu)*tp));
+        }
+        solved = true;
+    });
+    if (!solved)
+    {
+        r.T = r.Tpure;      // (no scattering, :117-122: R = 0, T = exp(-tau/mu); nothing in the layer, :152-157: R = 0, T = 1)
     }
     if (WITH_PURE)
     {
@@ -244,6 +267,14 @@ __device__ __forceinline__ void put_level(Sink &sink, int lev, double up, double
     sink.put(lev, true, tsi*dn);
 }
 
+// the direct beam that reaches a level (shortwave.c:306, :323), scaled as the downward flux beside it is
+template <typename Sink>
+__device__ __forceinline__ void put_direct(Sink &sink, int lev, double dir, double scale, double tsi)
+{
+    dir *= scale;
+    sink.put_direct(lev, tsi*dir);
+}
+
 // the cosine of the zenith angle of a grid row: the column's, or -- zenith instances -- the row's angle's
 template <typename... Joins>
 __device__ __forceinline__ double row_mu(GrtSwArgs const &a, SolverRow const &row, Joins const &...joins)
@@ -275,7 +306,10 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Joins... 
 {
     uint64_t const i = (uint64_t)blockIdx.x*kSolverBlock + threadIdx.x;
     constexpr bool FUSED = grt_out_fused(OUT), PROFILE = grt_out_levels(OUT), SPECTRAL = OUT == GRT_OUT_ROWS_POINTS;
+    constexpr bool DIRECT = has<GrtDirectArgs, Joins...>;
     static_assert(has<GrtBandArgs, Joins...> == (OUT == GRT_OUT_LEVEL_BINS), "bins go with GRT_OUT_LEVEL_BINS alone");
+    static_assert(!DIRECT || ((OUT == GRT_OUT_ROWS || OUT == GRT_OUT_LEVELS) && !has<GrtZenithArgs, Joins...>),
+                  "the direct beam leaves the six-row and level forms, one sun per column");
     SolverRow const row = solver_row(a.ncol, joins...);
     int const col = row.col;
     bool const live = i < a.nw;
@@ -314,7 +348,8 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Joins... 
     // divisions a layer, which is what this kernel's time is made of)
     double *pp = FUSED ? a.park + ((uint64_t)row.park*park_rows + 2*(uint64_t)V)*nw + ii : nullptr;
     int const user = a.user_level;
-    LevelSink<FUSED, PROFILE, SPECTRAL, has<GrtBandArgs, Joins...>> sink(a, row.slot, i, live, pick<GrtBandArgs>(joins...));
+    LevelSink<FUSED, PROFILE, SPECTRAL, has<GrtBandArgs, Joins...>, DIRECT> sink(a, row.slot, i, live, pick<GrtBandArgs>(joins...),
+                                                                                 pick<GrtDirectArgs>(joins...));
     LayerOptics<FUSED, has_clouds<Joins...>, has<GrtAerosolArgs, Joins...>> const optics(
         a, pick_clouds(joins...), col, row.tab, ii, pick<GrtAerosolArgs>(joins...));                    // (fused forms)
 
@@ -362,6 +397,11 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Joins... 
                    up_s, dn_s);
         put_level(sink, 0, Rd + Tu*up_s, 1., scale, tsi);
         put_level(sink, L, up_s, dn_s, scale, tsi);
+        if constexpr (DIRECT)
+        {
+            put_direct(sink, 0, 1., scale, tsi);
+            put_direct(sink, L, dir, scale, tsi);
+        }
         sink.finish(a);
         return;
     }
@@ -406,6 +446,10 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Joins... 
     double const tsi = a.tsi[col];
     Sweep2 s;
     put_level(sink, 0, s.dir*(FUSED ? Rdir_dn : fu[0]), s.dir, scale, tsi);   // R[0] = dir_beam*R_dir_downward[0], T[0]
+    if constexpr (DIRECT)
+    {
+        put_direct(sink, 0, s.dir, scale, tsi);
+    }
     for (int lev = 1; lev < V; ++lev)
     {
         sweep2_step(s, FUSED ? load_props(pp + (uint64_t)(5*(lev - 1))*nw, nw) : props_of(lev - 1), lev);
@@ -419,6 +463,10 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Joins... 
         double up, dn;
         level_flux(s.dir, s.dif, s.Rup, rdir, rdif, up, dn);
         put_level(sink, lev, up, dn, scale, tsi);
+        if constexpr (DIRECT)
+        {
+            put_direct(sink, lev, s.dir, scale, tsi);
+        }
     }
     sink.finish(a);
 }
@@ -654,6 +702,54 @@ __global__ __launch_bounds__(kSweepBlock) void sw_sweeps_kernel(GrtSwArgs a)
     }
 }
 
+// ---- the direct beam of the materialised form (grt_launch_sw_direct_beam) ----
+// One thread per (wavenumber, column) walks the layers of the tau, omega, g a pass left on the grid: the delta-scaling and
+// T_pure of layer_props()'s direct-beam solution (the same device functions on the same doubles: the solver's own dir),
+// the running product from the top, scaled as put_direct scales it.
+constexpr int kDirectBlock = 128;
+
+__global__ __launch_bounds__(kDirectBlock) void sw_direct_beam_kernel(GrtSwArgs a, double *direct)
+{
+    uint64_t const i = (uint64_t)blockIdx.x*kDirectBlock + threadIdx.x;
+    int const col = blockIdx.y;
+    if (i >= a.nw)
+    {
+        return;
+    }
+    int const V = a.num_levels;
+    uint64_t const nw = a.nw;
+    double const *tau = a.tau + (uint64_t)col*a.optics_stride + i;
+    double const *omega = a.omega + (uint64_t)col*a.optics_stride + i;
+    double const *g = a.g + (uint64_t)col*a.optics_stride + i;
+    double *out = direct + (uint64_t)col*(uint64_t)V*nw + i;
+    double const mu = a.mu_dir[col];
+    double const scale = a.solar[i]*mu;
+    double const tsi = a.tsi[col];
+    double dir = 1.;
+    out[0] = tsi*(dir*scale);
+    for (int lev = 1; lev < V; ++lev)
+    {
+        uint64_t const o = (uint64_t)(lev - 1)*nw;
+        double gs, os, ts;
+        delta_scaling(omega[o], g[o], tau[o], os, gs, ts);
+        dir *= pure_transmission(os, ts, mu, eddington_gammas(os, gs, mu), [](double, double, double, double) {});
+        out[(uint64_t)lev*nw] = tsi*(dir*scale);
+    }
+}
+
+// rows [n][3] of levels [n][V]: TOA, surface, the user level (+0.0 without one)
+__global__ __launch_bounds__(64) void direct_rows_kernel(int n, int V, int user, double const *levels, double *rows)
+{
+    int const k = blockIdx.x*64 + threadIdx.x;
+    if (k < n)
+    {
+        double const *lv = levels + (uint64_t)k*V;
+        rows[3*(uint64_t)k] = lv[0];
+        rows[3*(uint64_t)k + 1] = lv[V - 1];
+        rows[3*(uint64_t)k + 2] = user >= 0 ? lv[user] : 0.;
+    }
+}
+
 // the one launch site of sw_kernel: the instance of OUT and of the joined arguments' types, on the instance's grid and LDS
 template <GrtSolverOutput OUT, typename... Joins>
 int launch(hipStream_t s, GrtSolverInstance const &in, GrtSwArgs const &a, Joins const &...joins)
@@ -676,7 +772,33 @@ extern "C" int grt_launch_sw(void *stream, GrtSolverInstance const *in, GrtSwArg
         return (int)hipErrorInvalidValue;
     }
     hipStream_t const s = (hipStream_t)stream;
-    // every instance of sw_kernel there is
+    // every instance of sw_kernel that also leaves the direct beam (grt_pipeline_run_sky_direct's sets and forms) ...
+    if (in->direct != nullptr)
+    {
+        GrtDirectArgs const &d = *in->direct;
+        switch (GRT_INSTANCE(in->out, grt_solver_join(in)))
+        {
+        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_NONE): return launch<GRT_OUT_ROWS>(s, *in, *a, d);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_NONE): return launch<GRT_OUT_LEVELS>(s, *in, *a, d);
+        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->clouds, d);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, d);
+        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->aerosols, d);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->aerosols, d);
+        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns, d);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, d);
+        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_CLOUDS_AEROSOLS):
+            return launch<GRT_OUT_ROWS>(s, *in, *a, *in->clouds, *in->aerosols, d);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS_AEROSOLS):
+            return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, *in->aerosols, d);
+        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
+            return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns, *in->aerosols, d);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
+            return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->aerosols, d);
+        default:
+            return (int)hipErrorInvalidValue;
+        }
+    }
+    // ... and every other instance of sw_kernel there is
     switch (GRT_INSTANCE(in->out, grt_solver_join(in)))
     {
     case GRT_INSTANCE(GRT_OUT_LAYERS, GRT_JOIN_NONE):
@@ -716,7 +838,7 @@ extern "C" int grt_launch_sw(void *stream, GrtSolverInstance const *in, GrtSwArg
 
 extern "C" int grt_launch_sw_zeniths(void *stream, GrtSwArgs const *a, GrtZenithArgs const *z)
 {
-    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr};
+    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (!grt_solver_instance_ok(in, *a) || z == nullptr || z->mu == nullptr || z->zeniths < 1 || !grt_sw_one_sweep(a))
     {
         return (int)hipErrorInvalidValue;
@@ -728,5 +850,29 @@ extern "C" int grt_launch_sw_zeniths(void *stream, GrtSwArgs const *a, GrtZenith
     }
     hipLaunchKernelGGL((sw_zenith_kernel<GRT_ZENITH_CHUNK>), dim3(grt_solver_blocks(a->nw), (unsigned)rows, 1),
                        dim3(kSolverBlock), 0, (hipStream_t)stream, *a, *z);
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_sw_direct_beam(void *stream, GrtSwArgs const *a, double *direct)
+{
+    if (a == nullptr || direct == nullptr || a->ncol < 1 || a->ncol > 65535 || a->nw < 2 || a->num_levels < 2 ||
+        a->tau == nullptr || a->omega == nullptr || a->g == nullptr || a->mu_dir == nullptr || a->tsi == nullptr ||
+        a->solar == nullptr)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(sw_direct_beam_kernel, dim3((unsigned)((a->nw + kDirectBlock - 1)/kDirectBlock), a->ncol, 1),
+                       dim3(kDirectBlock), 0, (hipStream_t)stream, *a, direct);
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_direct_rows(void *stream, int n, int num_levels, int user_level, double const *levels, double *rows)
+{
+    if (n < 1 || num_levels < 2 || user_level >= num_levels || levels == nullptr || rows == nullptr)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(direct_rows_kernel, dim3((unsigned)((n + 63)/64)), dim3(64), 0, (hipStream_t)stream, n, num_levels,
+                       user_level, levels, rows);
     return (int)hipGetLastError();
 }

@@ -321,9 +321,11 @@ __device__ __forceinline__ double continua_add(GrtContinua const &c, PointContin
 // rows that are integrated; sum_i 0.5 (f_i + f_{i+1}) dw = sum_i weight_i f_i with weight dw (dw/2 at both ends).
 // WAVE_SUM, then waves_sum across the block's waves through LDS; thread v stores row v's sum at
 // partials[(row_base + v)*nblocks + block].  A second tiny launch adds the blocks in a fixed order (deterministic).
-template <int NV, int BLOCK>
+// SPLIT < NV: the rows from SPLIT on go to a second array, row v at partials2[(row_base2 + v - SPLIT)*nblocks + block]
+// (the direct-beam rows beside the six: summed as the six are, stored apart).
+template <int NV, int BLOCK, int SPLIT = NV>
 __device__ __forceinline__ void block_partials(double (&val)[NV], double *partials, uint64_t row_base, unsigned nblocks,
-                                               unsigned block)
+                                               unsigned block, double *partials2 = nullptr, uint64_t row_base2 = 0)
 {
     __shared__ double part[NV][BLOCK/64];
 #pragma unroll
@@ -337,9 +339,13 @@ __device__ __forceinline__ void block_partials(double (&val)[NV], double *partia
         }
     }
     __syncthreads();
-    if (threadIdx.x < NV)
+    if (threadIdx.x < SPLIT)
     {
         partials[(row_base + threadIdx.x)*nblocks + block] = waves_sum<BLOCK/64>(part[threadIdx.x]);
+    }
+    else if (SPLIT < NV && threadIdx.x < NV)
+    {
+        partials2[(row_base2 + threadIdx.x - SPLIT)*nblocks + block] = waves_sum<BLOCK/64>(part[threadIdx.x]);
     }
 }
 
@@ -488,9 +494,16 @@ struct LayerOptics
 // one that holds edges sums each level once per bin, the weight formed from the bin's two edges where it is used.  The
 // waves' sums wait in dynamic LDS, [bins of the block][2 V][kSolverBlock/64], and finish() stores bin b's at
 // partials[(c*2 V + r)*per_row + offset(b) + block - first_block(b)].
-template <bool FUSED, bool PROFILE, bool SPECTRAL = false, bool BANDED = false>
+// DIRECT (shortwave, fused six-row and profile forms; GrtDirectArgs): the direct beam at a level leaves too, by
+// put_direct() -- three more rows in registers (TOA, surface, user) that ride with the six through block_partials, or V
+// more rows of wave sums behind the 2 V in dynamic LDS (3 V x kSolverBlock/64 doubles) --, to the join's own partial sums.
+template <bool ON> struct DirectRows {};
+template <> struct DirectRows<true> { double out[3]; double *partials; };
+
+template <bool FUSED, bool PROFILE, bool SPECTRAL = false, bool BANDED = false, bool DIRECT = false>
 struct LevelSink
 {
+    static_assert(!DIRECT || (FUSED && !SPECTRAL && !BANDED), "the direct beam leaves the six-row and profile forms");
     double *fu, *fd;            // spectral forms (and SPECTRAL): flux_up / flux_down at this thread's point
     uint64_t nw, i;
     int V, user, col;
@@ -500,11 +513,18 @@ struct LevelSink
     GrtBandArgs bins;           // BANDED
     int bin_lo, bin_count;      // ... the first bin with a point in this workgroup, and how many there are
     double dw;
+    DirectRows<DIRECT> direct;  // DIRECT
 
     template <typename Args>
     __device__ __forceinline__ LevelSink(Args const &a, int col_, uint64_t i_, bool live_,
-                                         GrtBandArgs const &bins_ = GrtBandArgs{0, 0, nullptr, 0})
+                                         GrtBandArgs const &bins_ = GrtBandArgs{0, 0, nullptr, 0},
+                                         GrtDirectArgs const &direct_ = GrtDirectArgs{nullptr})
     {
+        if constexpr (DIRECT)
+        {
+            direct.partials = direct_.partials;
+            direct.out[0] = direct.out[1] = direct.out[2] = 0.;
+        }
         col = col_;
         i = i_;
         live = live_;
@@ -533,7 +553,7 @@ struct LevelSink
 
     static __device__ __forceinline__ double *level_sums()
     {
-        extern __shared__ double level_sums_[];     // PROFILE: [2 V][kSolverBlock/64]; BANDED: that per bin of the block
+        extern __shared__ double level_sums_[];     // PROFILE: [2 V][kSolverBlock/64] (DIRECT: [3 V]); BANDED: that per bin of the block
         return level_sums_;
     }
 
@@ -579,6 +599,21 @@ struct LevelSink
         }
     }
 
+    // DIRECT: level lev's direct beam at this point is x (for a level that is wanted())
+    __device__ __forceinline__ void put_direct(int lev, double x)
+    {
+        if constexpr (DIRECT && PROFILE)
+        {
+            wave_row_sum<kSolverBlock>(x*pwt, level_sums(), 2*V + lev);
+        }
+        else if constexpr (DIRECT)
+        {
+            direct.out[0] = lev == 0 ? x : direct.out[0];
+            direct.out[1] = lev + 1 == V ? x : direct.out[1];
+            direct.out[2] = lev == user ? x : direct.out[2];
+        }
+    }
+
     // ... is 0 at every point (its sums are 0 whatever the weights)
     __device__ __forceinline__ void put_zero(int lev, bool down)
     {
@@ -618,6 +653,24 @@ struct LevelSink
         else if (PROFILE)
         {
             block_row_partials<kSolverBlock>(level_sums(), 2*V, a.partials, (uint64_t)col*2*V, gridDim.x, blockIdx.x);
+            if constexpr (DIRECT)
+            {
+                block_row_partials<kSolverBlock>(level_sums() + 2*V*(kSolverBlock/64), V, direct.partials, (uint64_t)col*V,
+                                                 gridDim.x, blockIdx.x);
+            }
+        }
+        else if constexpr (DIRECT)
+        {
+            // (the six rows' weights and sums below, on nine)
+            double const wt = trapezoid_weight(i, nw, a.dw, live);
+            double nine[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k)
+            {
+                nine[k] = (k < 6 ? out[k] : direct.out[k - 6])*wt;
+            }
+            block_partials<9, kSolverBlock, 6>(nine, a.partials, (uint64_t)col*6, gridDim.x, blockIdx.x, direct.partials,
+                                               (uint64_t)col*3);
         }
         else if (FUSED)
         {

@@ -31,6 +31,8 @@
  * per-column slope and intercept tables (or, materialised form, spread onto the grid and added by the add_optics kernel).
  * grt_pipeline_run_sky runs up to four sets of one driver.c column -- clear-clean, with aerosol, with clouds, with both -- on
  * one gas-optics launch per band: the passes of the entry points above, and the pass that joins aerosol and clouds.
+ * grt_pipeline_run_sky_direct is grt_pipeline_run_sky with the direct beam of every set's shortwave beside its rows: taken
+ * out of the same solver launches (instances that leave it too), or -- materialised form -- formed from each set's optics.
  * grt_pipeline_run_band_profiles runs the profile form of the clear-sky pass and, with clouds, of the all-sky pass with
  * every level's flux integrated per wavenumber bin instead of over the whole grid, and one finishing launch for the bins'
  * heating rates.
@@ -254,6 +256,8 @@ static void grt_pipeline_release(GrtPipeline_t **pipeline)
         grt_dev_free(p->device, p->band[b].tau_gas);
         grt_dev_free(p->device, p->band[b].rows_d);
         grt_dev_free(p->device, p->band[b].level_rows_d);
+        grt_dev_free(p->device, p->band[b].direct_rows_d[0]);
+        grt_dev_free(p->device, p->band[b].direct_rows_d[1]);
         for (int k = 0; k < GRT_SCRATCH_COUNT; ++k)
         {
             grt_dev_free(p->device, p->band[b].scratch[k].d);
@@ -941,12 +945,24 @@ EXTERN int grt_pipeline_run_aerosols(GrtPipeline_t *p, GrtColumns_t const *cols,
     return GRTCODE_SUCCESS;
 }
 
-/* grt_ext.h: the sets of one driver.c column that are asked for, on one gas-optics pass per band */
-EXTERN int grt_pipeline_run_sky(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky, fp_t *level_fluxes_dev,
-                                fp_t *heating_dev, fp_t *fluxes_dev)
+/* grt_pipeline_run_sky and, with_direct, grt_pipeline_run_sky_direct: the same request, the direct outputs attached */
+static int run_sky(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky, int with_direct,
+                   GrtDirectBeam_t const *direct, fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev)
 {
     GRT_REQUIRE_PTR(p);
     GRT_REQUIRE_PTR(cols);
+    if (with_direct)
+    {
+        if (direct == NULL || direct->direct_fluxes_dev == NULL)
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "%s is NULL: the direct-beam rows [ncol][sets][%d] are the output.",
+                     direct == NULL ? "direct (GrtDirectBeam_t)" : "direct_fluxes_dev", GRT_DIRECT_ROWS_PER_SET);
+        }
+        if (level_fluxes_dev == NULL && direct->direct_level_fluxes_dev != NULL)
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "direct_level_fluxes_dev is given in the six-row form (level_fluxes_dev is NULL).%s", "");
+        }
+    }
     if (sky == NULL)
     {
         GRT_FAIL(GRTCODE_VALUE_ERR, "no sky inputs (GrtSky_t is NULL).%s", "");
@@ -995,8 +1011,59 @@ EXTERN int grt_pipeline_run_sky(GrtPipeline_t *p, GrtColumns_t const *cols, GrtS
     GrtJoin const join = {.clouds = with_clouds ? sky->clouds : NULL, .aerosols = with_aerosols ? &a : NULL,
                           .subcolumns = with_clouds && sky->num_subcolumns > 1 ? sky->num_subcolumns : 0,
                           .sets = sky->sets | GRT_SKY_CLEAN};
+    GrtBand *sw = &p->band[1];
+    int const V = p->num_levels;
+    if (with_direct && sw->gas != NULL)
+    {
+        /* the passes' direct rows: the caller's three per set, or -- profile form -- V levels per set, the caller's or the
+           pipeline's own, and the three rows from them afterwards */
+        rows.direct = rows.profile ? direct->direct_level_fluxes_dev : direct->direct_fluxes_dev;
+        if (rows.direct == NULL)
+        {
+            GRT_TRY(check_lane(p));
+            GrtScratch *own = &sw->scratch[GRT_SCRATCH_DIRECT_LEVELS];
+            GRT_TRY(grt_scratch_need(p, own, (size_t)p->max_cols*GRT_SKY_MAX_SETS*(size_t)V, NULL));
+            rows.direct = own->d;
+        }
+    }
     GRT_TRY(pipeline_run(p, cols, &join, &rows));
     GRT_TRY(finish_profiles(p, cols->ncol, &rows, heating_dev, fluxes_dev));
+    if (with_direct)
+    {
+        void *s = grt_dev_stream(p->device);
+        size_t const slots = (size_t)cols->ncol*(size_t)nsets;
+        if (sw->gas == NULL)
+        {
+            /* no shortwave band: zeros, as the band's rows are */
+            GRT_TRY(grt_dev_zero(p->device, direct->direct_fluxes_dev, sizeof(double)*slots*GRT_DIRECT_ROWS_PER_SET, s));
+            if (direct->direct_level_fluxes_dev != NULL)
+            {
+                GRT_TRY(grt_dev_zero(p->device, direct->direct_level_fluxes_dev, sizeof(double)*slots*(size_t)V, s));
+            }
+        }
+        else if (rows.profile)
+        {
+            GRT_TRY(grt_dev_check(grt_launch_direct_rows(s, (int)slots, V, p->user_level, rows.direct,
+                                                         direct->direct_fluxes_dev), "direct-beam row kernel"));
+        }
+    }
+    return GRTCODE_SUCCESS;
+}
+
+/* grt_ext.h: the sets of one driver.c column that are asked for, on one gas-optics pass per band */
+EXTERN int grt_pipeline_run_sky(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky, fp_t *level_fluxes_dev,
+                                fp_t *heating_dev, fp_t *fluxes_dev)
+{
+    GRT_TRY(run_sky(p, cols, sky, 0, NULL, level_fluxes_dev, heating_dev, fluxes_dev));
+    return GRTCODE_SUCCESS;
+}
+
+/* grt_ext.h: grt_pipeline_run_sky, and the direct beam of every set's shortwave */
+EXTERN int grt_pipeline_run_sky_direct(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky,
+                                       GrtDirectBeam_t const *direct, fp_t *level_fluxes_dev, fp_t *heating_dev,
+                                       fp_t *fluxes_dev)
+{
+    GRT_TRY(run_sky(p, cols, sky, 1, direct, level_fluxes_dev, heating_dev, fluxes_dev));
     return GRTCODE_SUCCESS;
 }
 

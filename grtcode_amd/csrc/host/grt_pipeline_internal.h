@@ -58,6 +58,14 @@ enum
     /* grt_pipeline_run_zeniths, shortwave: [max_cols][Z][6 or 2 V][nblocks] partial sums of every angle (materialised
        form: [max_cols][Z][6 or 2 V] integrated rows) */
     GRT_SCRATCH_ZEN_PARTIALS,
+    /* grt_pipeline_run_sky_direct, shortwave, fused form: [max_cols][S][3 or V][nblocks] partial sums of the direct beam */
+    GRT_SCRATCH_DIRECT_PARTIALS,
+    /* ... materialised form: [max_cols][V][n] the direct beam of the pass just solved (fixed size: direct_rows_d points
+       into it), and -- with subcolumns -- [max_cols][V][n] its sum */
+    GRT_SCRATCH_DIRECT_BEAM,
+    GRT_SCRATCH_DIRECT_SUM,
+    /* ... profile form without direct_level_fluxes_dev: [max_cols][GRT_SKY_MAX_SETS][V] the levels its three rows come from */
+    GRT_SCRATCH_DIRECT_LEVELS,
     GRT_SCRATCH_COUNT
 };
 
@@ -78,6 +86,9 @@ typedef struct GrtBand
     /* grt_pipeline_run_profiles (and _allsky_profiles), materialised form, allocated at the first call: [cols][2 V] device
        row pointers (up levels, then down levels) */
     double **level_rows_d;
+    /* grt_pipeline_run_sky_direct, materialised form, allocated at the first call of each form: device row pointers into
+       GRT_SCRATCH_DIRECT_BEAM, [0]: [cols][3] (TOA, surface, user level or the zero row), [1]: [cols][V] */
+    double **direct_rows_d[2];
     GrtScratch scratch[GRT_SCRATCH_COUNT];     /* what the calls allocate on demand (GRT_SCRATCH_...) */
     /* grt_pipeline_run_allsky (and _allsky_profiles): [2][n] cloud band of each grid point (liquid, ice), -1: none; its key:
        the band limits (B, num_ice_bands, liquid lo/hi, ice lo/hi) */
@@ -148,6 +159,9 @@ typedef struct GrtPass
     int sets;
     int set;                       /* its place among the column's sets: 0 the clear-sky set, then the others as packed */
     GrtBins const *bins;
+    /* grt_pipeline_run_sky_direct (NULL: not asked for): the shortwave's direct beam leaves too, the pass's three rows
+       (TOA, surface, user level) or -- profile -- V levels to set `set` of direct [ncol][sets][3 or V] */
+    double *direct;
 } GrtPass;
 
 /* The sun angles of a grt_pipeline_run_zeniths call, staged (grt_stage_zeniths): Z per column, their cosines and weights

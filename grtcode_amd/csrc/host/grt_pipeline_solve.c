@@ -20,11 +20,11 @@ static int pass_spectral(GrtPass const *ps)
 }
 
 /* its solver instance (materialised: the spectral form, after pass_optics); bn: its per-bin instance; sc: the pass's
-   clouds as the subcolumns of sc */
+   clouds as the subcolumns of sc; da: its instance that leaves the direct beam too */
 static GrtSolverInstance pass_instance(GrtPipeline_t const *p, GrtPass const *ps, GrtBandArgs const *bn,
-                                       GrtSubcolumnArgs const *sc)
+                                       GrtSubcolumnArgs const *sc, GrtDirectArgs const *da)
 {
-    GrtSolverInstance in = {GRT_OUT_CHAINS, NULL, NULL, NULL, NULL, NULL};
+    GrtSolverInstance in = {GRT_OUT_CHAINS, NULL, NULL, NULL, NULL, NULL, NULL};
     if (!p->keep_spectra)
     {
         in.out = pass_spectral(ps) ? GRT_OUT_ROWS_POINTS : (bn != NULL ? GRT_OUT_LEVEL_BINS :
@@ -33,8 +33,45 @@ static GrtSolverInstance pass_instance(GrtPipeline_t const *p, GrtPass const *ps
         in.aerosols = ps->aer;
         in.subcolumns = sc;
         in.bins = bn;
+        in.direct = da;
     }
     return in;
+}
+
+/* whether band bi's solve of the pass leaves the direct beam (the shortwave's, where it is asked for), its rows per set
+   and column, and where the pass's start in a column's direct_stride doubles of ps->direct */
+static int pass_direct(GrtPass const *ps, int bi)
+{
+    return ps->direct != NULL && bi == 1;
+}
+
+static int direct_rows(GrtPipeline_t const *p, GrtPass const *ps)
+{
+    return ps->profile ? p->num_levels : GRT_DIRECT_ROWS_PER_SET;
+}
+
+static int direct_stride(GrtPipeline_t const *p, GrtPass const *ps)
+{
+    return ps->sets*direct_rows(p, ps);
+}
+
+static int direct_offset(GrtPipeline_t const *p, GrtPass const *ps)
+{
+    return ps->set*direct_rows(p, ps);
+}
+
+/* fused form: the partial sums of the direct beam of `slots` slots per column, as *da, where the pass leaves it (else *da
+   stays empty and the caller passes no join) */
+static int direct_partials(GrtPipeline_t *p, GrtBand *b, int bi, GrtPass const *ps, int slots, GrtDirectArgs *da)
+{
+    da->partials = NULL;
+    if (pass_direct(ps, bi))
+    {
+        GrtScratch *block = &b->scratch[GRT_SCRATCH_DIRECT_PARTIALS];
+        GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*(size_t)slots*(size_t)direct_rows(p, ps)*b->nblocks, NULL));
+        da->partials = block->d;
+    }
+    return GRTCODE_SUCCESS;
 }
 
 /* its rows per band and column, and where band bi's start in a column's out_stride doubles */
@@ -178,11 +215,12 @@ static int solver_launch(void *s, int bi, GrtSolverInstance const *in, SolverArg
     return bi == 0 ? grt_launch_lw(s, in, &a->lw) : grt_launch_sw(s, in, &a->sw);
 }
 
-/* the band's solver in the pass's instance (bn: its per-bin one), timed under the pass's profile tag */
+/* the band's solver in the pass's instance (bn: its per-bin one; da: the one that leaves the direct beam too), timed under
+   the pass's profile tag */
 static int band_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps, double *partials,
-                       GrtBandArgs const *bn)
+                       GrtBandArgs const *bn, GrtDirectArgs const *da)
 {
-    GrtSolverInstance const in = pass_instance(p, ps, bn, NULL);
+    GrtSolverInstance const in = pass_instance(p, ps, bn, NULL, da);
     void *s = grt_dev_stream(p->device);
     SolverArgs a;
     GRT_TRY(solver_args(p, b, bi, C, ps, &in, partials, &a));
@@ -307,6 +345,57 @@ static int integrate_rows(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass c
     return GRTCODE_SUCCESS;
 }
 
+/* Materialised form of the direct beam: from the tau, omega, g the pass (its last subcolumn) has left in the band's arrays,
+   every level's direct beam on the grid, [C][V][n] in GRT_SCRATCH_DIRECT_BEAM (GRT_TAG_DIRECT_BEAM) */
+static int direct_beam(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *ps)
+{
+    void *s = grt_dev_stream(p->device);
+    GrtSwArgs a;
+    sw_args(p, b, C, 0, ps, &a);
+    GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_DIRECT_BEAM], (size_t)p->max_cols*(size_t)p->num_levels*b->n, NULL));
+    int const slot = grt_profile_begin(s, GRT_TAG_DIRECT_BEAM);
+    int const krc = grt_launch_sw_direct_beam(s, &a, b->scratch[GRT_SCRATCH_DIRECT_BEAM].d);
+    grt_profile_end(s, slot);
+    GRT_TRY(grt_dev_check(krc, "direct-beam kernel"));
+    return GRTCODE_SUCCESS;
+}
+
+/* ... and the row-wise trapezoid of it into the pass's direct rows: TOA, surface and the user level (the zero row without
+   one), or -- profile -- every level */
+static int direct_integrate(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *ps)
+{
+    size_t const V = (size_t)p->num_levels, cols = (size_t)p->max_cols, rows = (size_t)direct_rows(p, ps);
+    double *beam = b->scratch[GRT_SCRATCH_DIRECT_BEAM].d;
+    double ***table = &b->direct_rows_d[ps->profile != 0];
+    if (*table == NULL)
+    {
+        double **rows_h = malloc(sizeof(double *)*cols*rows);
+        if (rows_h == NULL)
+        {
+            GRT_FAIL(GRTCODE_NULL_ERR, "out of host memory for the direct-beam row table of %zu columns.", cols);
+        }
+        for (size_t c = 0; c < cols; ++c)
+        {
+            double *lev = beam + c*V*b->n;
+            for (size_t k = 0; k < rows && ps->profile; ++k)
+            {
+                rows_h[c*rows + k] = lev + k*b->n;
+            }
+            if (!ps->profile)
+            {
+                rows_h[c*rows + 0] = lev;
+                rows_h[c*rows + 1] = lev + (V - 1)*b->n;
+                rows_h[c*rows + 2] = p->user_level >= 0 ? lev + (size_t)p->user_level*b->n : b->zero_row;
+            }
+        }
+        GRT_TRY(grt_upload_rows(p, rows_h, cols*rows, table));
+    }
+    GRT_TRY(grt_dev_check(grt_launch_integrate_rows(grt_dev_stream(p->device), (double const *const *)*table, C*(int)rows,
+                                                    b->n, b->gas->grid.dw, ps->direct, (int)rows, direct_stride(p, ps),
+                                                    direct_offset(p, ps)), "spectral integration kernel"));
+    return GRTCODE_SUCCESS;
+}
+
 /* One solve of a band for grt_pipeline_run_spectral: the six rows at every point into the caller's spectral block, the
    -integrated six into out, and the bins.  Fused form: the spectral six-row solver (its rows stored where it weights
    them) and the fixed-order sum of its partial sums; materialised form: the spectral solver, its rows 0, L and the user
@@ -320,7 +409,7 @@ static int band_solve_spectral(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtP
     double *rows = spectral_rows(p, ps, bi, &stride);
     if (!p->keep_spectra)
     {
-        GRT_TRY(band_solver(p, b, bi, C, ps, b->partials, NULL));
+        GRT_TRY(band_solver(p, b, bi, C, ps, b->partials, NULL, NULL));
         GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, b->partials, C*GRT_FLUXES_PER_BAND, b->nblocks, ps->out,
                                                          GRT_FLUXES_PER_BAND, ps->out_stride, pass_offset(p, ps, bi)),
                               "flux reduction kernel"));
@@ -328,7 +417,7 @@ static int band_solve_spectral(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtP
     else
     {
         GRT_TRY(pass_optics(p, b, C, ps));
-        GRT_TRY(band_solver(p, b, bi, C, ps, NULL, NULL));
+        GRT_TRY(band_solver(p, b, bi, C, ps, NULL, NULL, NULL));
         GRT_TRY(grt_dev_check(grt_launch_copy_rows(s, (double const *const *)b->rows_d, C*GRT_FLUXES_PER_BAND, b->n,
                                                    rows, stride), "spectral row copy kernel"));
         GRT_TRY(integrate_rows(p, b, bi, C, ps));
@@ -368,14 +457,14 @@ static int band_solve_band_profiles(GrtPipeline_t *p, GrtBand *b, int bi, int C,
     if (!p->keep_spectra)
     {
         GrtBandArgs const bn = {nbins, grt_bin_block_max(bp->edges[bi], nbins), b->bin_table.table, b->bin_per_row};
-        GRT_TRY(band_solver(p, b, bi, C, ps, bin_partials, &bn));
+        GRT_TRY(band_solver(p, b, bi, C, ps, bin_partials, &bn, NULL));
         slot = grt_profile_begin(s, GRT_TAG_BAND_PROFILES);
         krc = grt_launch_bin_reduce(s, C*rows, V, nbins, b->bin_table.table, b->bin_per_row, bin_partials, out, out_stride);
     }
     else
     {
         GRT_TRY(pass_optics(p, b, C, ps));
-        GRT_TRY(band_solver(p, b, bi, C, ps, NULL, NULL));
+        GRT_TRY(band_solver(p, b, bi, C, ps, NULL, NULL, NULL));
         GRT_TRY(level_rows(p, b));
         slot = grt_profile_begin(s, GRT_TAG_BAND_PROFILES);
         krc = grt_launch_bin_level_rows(s, (double const *const *)b->level_rows_d, C*rows, V, b->n, b->gas->grid.dw, nbins,
@@ -401,20 +490,34 @@ int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *p
     if (p->keep_spectra)
     {
         GRT_TRY(pass_optics(p, b, C, ps));
-        GRT_TRY(band_solver(p, b, bi, C, ps, NULL, NULL));
+        GRT_TRY(band_solver(p, b, bi, C, ps, NULL, NULL, NULL));
         GRT_TRY(integrate_rows(p, b, bi, C, ps));
+        if (pass_direct(ps, bi))
+        {
+            GRT_TRY(direct_beam(p, b, C, ps));
+            GRT_TRY(direct_integrate(p, b, C, ps));
+        }
         return GRTCODE_SUCCESS;
     }
     int const rows = pass_rows(p, ps);
+    GrtDirectArgs da;
+    GRT_TRY(direct_partials(p, b, bi, ps, 1, &da));
     if (ps->profile)
     {
         GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_LEVEL_PARTIALS], (size_t)p->max_cols*(size_t)rows*b->nblocks,
                                  NULL));
     }
     double *partials = ps->profile ? b->scratch[GRT_SCRATCH_LEVEL_PARTIALS].d : b->partials;
-    GRT_TRY(band_solver(p, b, bi, C, ps, partials, NULL));
+    GRT_TRY(band_solver(p, b, bi, C, ps, partials, NULL, da.partials != NULL ? &da : NULL));
     GRT_TRY(grt_dev_check(grt_launch_reduce_partials(grt_dev_stream(p->device), partials, C*rows, b->nblocks, ps->out, rows,
                                                      ps->out_stride, pass_offset(p, ps, bi)), "flux reduction kernel"));
+    if (da.partials != NULL)
+    {
+        int const drows = direct_rows(p, ps);
+        GRT_TRY(grt_dev_check(grt_launch_reduce_partials(grt_dev_stream(p->device), da.partials, C*drows, b->nblocks,
+                                                         ps->direct, drows, direct_stride(p, ps), direct_offset(p, ps)),
+                              "direct-beam reduction kernel"));
+    }
     return GRTCODE_SUCCESS;
 }
 
@@ -436,7 +539,10 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
         double *sub_partials = b->scratch[GRT_SCRATCH_SUB_PARTIALS].d;
         /* (in points at sc: the loop below walks sc.first and sc.count, which the launcher alone reads) */
         GrtSubcolumnArgs sc = {*ps->clouds, S, 0, 0};
-        GrtSolverInstance const in = pass_instance(p, ps, NULL, &sc);
+        GrtDirectArgs da;
+        GRT_TRY(direct_partials(p, b, bi, ps, S, &da));
+        int const drows = direct_rows(p, ps);
+        GrtSolverInstance const in = pass_instance(p, ps, NULL, &sc, da.partials != NULL ? &da : NULL);
         SolverArgs a;
         GRT_TRY(solver_args(p, b, bi, C, ps, &in, sub_partials, &a));
         /* (grid rows; a park block of max_cols columns) */
@@ -455,11 +561,22 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
         {
             GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, sub_partials, C*rows, b->nblocks, ps->out, rows,
                                                              ps->out_stride, out_offset), "flux reduction kernel"));
+            if (da.partials != NULL)
+            {
+                GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, da.partials, C*drows, b->nblocks, ps->direct, drows,
+                                                                 direct_stride(p, ps), direct_offset(p, ps)),
+                                      "direct-beam reduction kernel"));
+            }
             return GRTCODE_SUCCESS;
         }
         int const mslot = grt_profile_begin(s, GRT_TAG_SUBCOLUMN_MEAN);
-        int const mrc = grt_launch_subcolumn_mean(s, sub_partials, C, S, rows, b->nblocks, ps->out, ps->out_stride,
-                                                  out_offset);
+        int mrc = grt_launch_subcolumn_mean(s, sub_partials, C, S, rows, b->nblocks, ps->out, ps->out_stride, out_offset);
+        if (mrc == 0 && da.partials != NULL)
+        {
+            /* (the same kernel: subcolumns 0 .. S - 1 in order, then one division by S) */
+            mrc = grt_launch_subcolumn_mean(s, da.partials, C, S, drows, b->nblocks, ps->direct, direct_stride(p, ps),
+                                            direct_offset(p, ps));
+        }
         grt_profile_end(s, mslot);
         GRT_TRY(grt_dev_check(mrc, "subcolumn mean kernel"));
         return GRTCODE_SUCCESS;
@@ -468,6 +585,11 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
     uint64_t const per = (uint64_t)C*(uint64_t)V*b->n, all = (uint64_t)p->max_cols*(uint64_t)V*b->n;
     GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_FLUX_SUM], 2*all, NULL));
     double *flux_sum = b->scratch[GRT_SCRATCH_FLUX_SUM].d;
+    if (pass_direct(ps, bi))
+    {
+        GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_DIRECT_SUM], all, NULL));
+    }
+    double *direct_sum = b->scratch[GRT_SCRATCH_DIRECT_SUM].d;
     for (int j = 0; j < S; ++j)
     {
         GrtCloudArgs cj = *ps->clouds;
@@ -476,14 +598,26 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
         GrtPass pj = *ps;
         pj.clouds = &cj;
         GRT_TRY(pass_optics(p, b, C, &pj));
-        GRT_TRY(band_solver(p, b, bi, C, &pj, NULL, NULL));
+        GRT_TRY(band_solver(p, b, bi, C, &pj, NULL, NULL, NULL));
         GRT_TRY(grt_dev_check(grt_launch_flux_accumulate(s, per, b->flux_up, flux_sum, j == 0), "flux sum kernel"));
         GRT_TRY(grt_dev_check(grt_launch_flux_accumulate(s, per, b->flux_down, flux_sum + all, j == 0),
                               "flux sum kernel"));
+        if (pass_direct(ps, bi))
+        {
+            GRT_TRY(direct_beam(p, b, C, &pj));
+            GRT_TRY(grt_dev_check(grt_launch_flux_accumulate(s, per, b->scratch[GRT_SCRATCH_DIRECT_BEAM].d, direct_sum,
+                                                             j == 0), "flux sum kernel"));
+        }
     }
     GRT_TRY(grt_dev_check(grt_launch_flux_mean(s, per, flux_sum, S, b->flux_up), "flux mean kernel"));
     GRT_TRY(grt_dev_check(grt_launch_flux_mean(s, per, flux_sum + all, S, b->flux_down), "flux mean kernel"));
     GRT_TRY(integrate_rows(p, b, bi, C, ps));
+    if (pass_direct(ps, bi))
+    {
+        GRT_TRY(grt_dev_check(grt_launch_flux_mean(s, per, direct_sum, S, b->scratch[GRT_SCRATCH_DIRECT_BEAM].d),
+                              "flux mean kernel"));
+        GRT_TRY(direct_integrate(p, b, C, ps));
+    }
     return GRTCODE_SUCCESS;
 }
 
@@ -507,7 +641,7 @@ int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *p
         GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*(size_t)Z*(size_t)rows*nblocks, NULL));
         /* (in points at za: the loop below walks za.first and za.count, which the launcher alone reads) */
         GrtZenithArgs za = {zr->mu, Z, 0, 0};
-        GrtSolverInstance in = pass_instance(p, ps, NULL, NULL);
+        GrtSolverInstance in = pass_instance(p, ps, NULL, NULL, NULL);
         in.zeniths = &za;
         SolverArgs a;
         GRT_TRY(solver_args(p, b, 1, C, ps, &in, block->d, &a));
@@ -539,7 +673,7 @@ int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *p
         {
             GRT_TRY(level_rows(p, b));
         }
-        GrtSolverInstance const in = pass_instance(p, ps, NULL, NULL);
+        GrtSolverInstance const in = pass_instance(p, ps, NULL, NULL, NULL);
         SolverArgs a;
         GRT_TRY(solver_args(p, b, 1, C, ps, &in, NULL, &a));
         for (int k = 0; k < Z; ++k)

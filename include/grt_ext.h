@@ -448,6 +448,45 @@ EXTERN int grt_pipeline_sky_set_count(unsigned sets);   /* 1 .. 4; 0 for bits ou
 EXTERN int grt_pipeline_run_sky(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtSky_t const *sky,
                                 fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev);
 
+/* ---- the direct beam of every sky set -------------------------------------------------------------------------------
+ * grt_pipeline_run_sky in every respect -- the sets and their packing order, both output forms, the shortwave sweep rule,
+ * the surface in force, the input checks -- and with it the part of each set's downward shortwave flux that is still in
+ * the direct solar beam.  With N = grt_pipeline_sky_set_count(sets):
+ *   direct_fluxes_dev       [ncol][N][GRT_DIRECT_ROWS_PER_SET] (required): the direct beam at the top of the atmosphere, at
+ *                           the surface and at the user level, W m-2; with user_level < 0 the user row is +0.0;
+ *   direct_level_fluxes_dev [ncol][N][V] (profile form only; may be NULL): the direct beam at every level, top first.
+ * The value is the reference's own dir_beam at that level (shortwave.c:306, :323): the running product, from the top, of
+ * the layers' T_pure (meador_weaver_1980, shortwave.c:118-121 and :147-168, the optical-depth clamp of :137-145
+ * included), times solar_flux[w] cos_zenith and the total solar irradiance as the other rows are (:401-405, :447-451),
+ * integrated over the band with the same trapezoid.  Two things to know about it:
+ *   - it is the DELTA-SCALED direct beam (Joseph, Wiscombe and Weinman 1976; shortwave.c:86-89): the optical depth of a
+ *     layer is tau (1 - omega g^2), so the beam includes the forward-scattered peak, as in every delta-two-stream model; it
+ *     is not what a pyrheliometer of narrow aperture sees under cloud;
+ *   - the diffuse downward flux is down - direct, formed by the caller from the matching row of fluxes_dev or
+ *     level_fluxes_dev.
+ * A cloud set's value is the mean over its num_subcolumns draws, taken as the other rows take theirs: subcolumns 0 .. S - 1
+ * in order, then one division by S.  sets == GRT_SKY_CLEAN with clouds and aerosols NULL is the clear-sky split on its own.
+ * A pipeline without a shortwave band writes zeros to both direct outputs.  All DEVICE memory; asynchronous on the
+ * pipeline's lane.  The production form takes the direct beam out of the solvers that compute the sets (instances of
+ * their own, which also leave the beam of their sweep: three more rows, or V, beside the set's own partial sums; the
+ * launches count under grt_pipeline_run_sky's tags); keep_spectra = 1 forms it from each set's tau, omega, g on the grid
+ * with a kernel of its own (GRT_TAG_DIRECT_BEAM) and the row-wise trapezoid.  In the deterministic mode every output
+ * grt_pipeline_run_sky also writes is grt_pipeline_run_sky's, bit for bit; the direct TOA row is the set's down TOA row;
+ * rows 0, V - 1 and user_level of direct_level_fluxes_dev are the six-row form's three direct rows, whichever sweep rule
+ * it ran under.  GRTCODE_VALUE_ERR, with nothing launched and every output untouched, for: direct NULL;
+ * direct_fluxes_dev NULL; direct_level_fluxes_dev given in the six-row form (level_fluxes_dev NULL); everything
+ * grt_pipeline_run_sky refuses.  A night column: GRTCODE_RANGE_ERR, as everywhere. */
+#define GRT_DIRECT_ROWS_PER_SET 3   /* direct-beam downward shortwave flux at TOA, surface, user level; W m-2 */
+typedef struct GrtDirectBeam
+{
+    fp_t *direct_fluxes_dev;        /* DEVICE [ncol][N][GRT_DIRECT_ROWS_PER_SET]; required */
+    fp_t *direct_level_fluxes_dev;  /* DEVICE [ncol][N][V], levels top first; profile form only; may be NULL */
+} GrtDirectBeam_t;
+
+EXTERN int grt_pipeline_run_sky_direct(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtSky_t const *sky,
+                                       GrtDirectBeam_t const *direct,
+                                       fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev);
+
 /* ---- spectral and band-integrated fluxes ---------------------------------------------------------------------------
  * driver.c's output without -integrated (output_fluxes, driver.c:285-356): the six rows of grt_pipeline_run at EVERY grid
  * point, and -- where the caller gives bin edges -- the same rows integrated over wavenumber bins, for a batch of columns,
@@ -674,7 +713,9 @@ enum
     /* 19 = the shortwave solver launches of grt_pipeline_run_zeniths, every angle's together (its longwave counts under
        GRT_TAG_SOLVER_LW); 20 = its mean kernel */
     GRT_TAG_ZENITH_SW = 19,
-    GRT_TAG_ZENITH_MEAN = 20
+    GRT_TAG_ZENITH_MEAN = 20,
+    /* 21 = the direct-beam kernel of grt_pipeline_run_sky_direct's materialised form (every set's, every subcolumn's) */
+    GRT_TAG_DIRECT_BEAM = 21
 };
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
