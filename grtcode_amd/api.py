@@ -28,7 +28,8 @@ GRT_CLOUD_PHASE, GRT_CLOUD_MODEL, GRT_CLOUD_FIELDS = 7, 8, 9   # ... of GrtCloud
 # grt_profile_read's tags (grt_ext.h: GRT_TAG_..., where each one's bracket is described)
 (TAG_GAS_LW, TAG_GAS_SW, TAG_SOLVER_LW, TAG_SOLVER_SW, TAG_CLEAR_OPTICS, TAG_FAR_LW, TAG_FAR_SW, TAG_ALLSKY_LW,
  TAG_ALLSKY_SW, TAG_BINS, TAG_SUBCOLUMN_MEAN, TAG_AEROSOL_LW, TAG_AEROSOL_SW, TAG_BAND_PROFILES, TAG_SURFACE,
- TAG_CLOUD_SAMPLER, TAG_SKY_LW, TAG_SKY_SW, TAG_ZENITH_SW, TAG_ZENITH_MEAN, TAG_DIRECT_BEAM) = range(1, 22)
+ TAG_CLOUD_SAMPLER, TAG_SKY_LW, TAG_SKY_SW, TAG_ZENITH_SW, TAG_ZENITH_MEAN, TAG_DIRECT_BEAM, TAG_SKY_ZENITH_SW,
+ TAG_SKY_ZENITH_MEAN) = range(1, 24)
 TAG_FAR_OFFSET = TAG_FAR_LW - TAG_GAS_LW    # from a line kernel's tag to its far-field gather's
 CLOUD_SAMPLER_TAG = TAG_CLOUD_SAMPLER
 GRT_MAX_SUBCOLUMNS = 64             # grt_pipeline_run_subcolumns: subcolumns per column, 1 .. this
@@ -209,7 +210,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_zeniths grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -273,6 +274,9 @@ def load_library(path=None):
     if hasattr(lib, "grt_pipeline_run_zeniths"):    # (GRT_LIB_PATH may name an older library: a timing yardstick)
         lib.grt_pipeline_run_zeniths.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtZeniths), C.c_void_p,
                                                  C.c_void_p, C.c_void_p]
+    if hasattr(lib, "grt_pipeline_run_sky_zeniths"):
+        lib.grt_pipeline_run_sky_zeniths.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky),
+                                                     C.POINTER(GrtZeniths), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.grt_pipeline_set_surface.argtypes = [C.c_void_p, C.POINTER(GrtSurface)]
     lib.grt_multi_gather_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.grt_pipeline_sync.argtypes = [C.c_void_p]
@@ -1049,6 +1053,40 @@ class Pipeline:
         lv = self.buffers["zenith_profiles.angle_levels"].to_host((ncol, Z, 2, self.num_levels))
         out["angle_fluxes"] = self.buffers["zenith_profiles.angles"].to_host((ncol, Z, 6))
         out["angle_up"], out["angle_down"] = lv[:, :, 0].copy(), lv[:, :, 1].copy()
+        return out
+
+    def run_sky_zeniths(self, gcols, gsky, gzeniths, profiles=False):
+        """grt_pipeline_run_sky_zeniths: the sets gsky (make_sky) asks for, the shortwave of each under gzeniths'
+        (make_zeniths) sun angles per column, into this object's device buffers, every angle's own rows of every set
+        included: the six-row form (sky_zenith_fluxes() reads it) or, profiles=True, the profile form
+        (sky_zenith_profiles() reads it)."""
+        nsets = max(sky_set_count(gsky.sets), 1)
+        Z, V, n = max(gzeniths.num_zeniths, 1), self.num_levels, self.max_columns
+        name = "sky_zenith_profiles" if profiles else "sky_zenith"
+        gzeniths.zenith_fluxes_dev = self._buffer(name + ".angles", 8 * n * nsets * Z * 6).ptr
+        gzeniths.zenith_level_fluxes_dev = self._buffer(name + ".angle_levels", 8 * n * nsets * Z * 2 * V).ptr if profiles else None
+        if profiles:
+            ptrs = self._profile_ptrs(name, nsets)
+        else:
+            ptrs = [None, None, self._buffer(name, 8 * GRT_FLUXES_PER_COLUMN * nsets * n).ptr]
+        check(self.lib.grt_pipeline_run_sky_zeniths(self.p, C.byref(gcols), C.byref(gsky), C.byref(gzeniths), *ptrs))
+
+    def sky_zenith_fluxes(self, ncol, nsets, Z):
+        """The last six-row run_sky_zeniths of nsets sets: (fluxes [ncol][nsets][12], sky_fluxes()' layout, the shortwave
+        six of each set the mean over the angles; angles [ncol][nsets][Z][6], every angle's shortwave six of every set)."""
+        self.sync()
+        return (self.buffers["sky_zenith"].to_host((ncol, nsets, GRT_FLUXES_PER_COLUMN)),
+                self.buffers["sky_zenith.angles"].to_host((ncol, nsets, Z, 6)))
+
+    def sky_zenith_profiles(self, ncol, nsets, Z):
+        """The last run_sky_zeniths(profiles=True) of nsets sets: sky_profiles()' dict, the shortwave rows the mean over
+        the angles, and with it angle_fluxes [ncol][nsets][Z][6], angle_up and angle_down [ncol][nsets][Z][V]: every
+        angle's shortwave rows of every set."""
+        per_set = self._read_profiles("sky_zenith_profiles", nsets, ncol)
+        out = {k: np.stack([s[k] for s in per_set], axis=1) for k in per_set[0]}
+        lv = self.buffers["sky_zenith_profiles.angle_levels"].to_host((ncol, nsets, Z, 2, self.num_levels))
+        out["angle_fluxes"] = self.buffers["sky_zenith_profiles.angles"].to_host((ncol, nsets, Z, 6))
+        out["angle_up"], out["angle_down"] = lv[:, :, :, 0].copy(), lv[:, :, :, 1].copy()
         return out
 
     def views(self, band):

@@ -420,7 +420,12 @@ static inline int grt_subcolumn_args_ok(GrtSubcolumnArgs const *sc)
    launch solves sun angles first .. first + count - 1 of every column on the column's one tau_gas.  Row y of the grid is
    column c = y / count, angle k = first + y % count, as the subcolumn form maps its rows: the row reads mu[c zeniths + k]
    in place of GrtSwArgs.mu_dir, leaves its partial sums at the slot c zeniths + k and parks at y.  A row whose mu <= 0 is a
-   night sample: +0.0 partial sums, nothing solved.  Shortwave only.  grt_launch_zenith_mean reduces. */
+   night sample: +0.0 partial sums, nothing solved.  Shortwave only.  grt_launch_zenith_mean reduces.
+   With aerosols, subcolumns or both joined as well (grt_pipeline_run_sky_zeniths: the sets of grt_pipeline_run_sky under
+   the angles): the aerosol table stays the column's; with subcolumns one launch solves subcolumns->count draws times
+   zeniths->count angles of every column, row y is column c = y / (draws x angles), draw s and angle k from the remainder
+   (the angles of a draw next to each other), the row reads mu[c zeniths + k] and the draw's cloud tables, leaves its partial
+   sums at the slot (c zeniths + k) subcolumns + s and parks at y.  grt_launch_sky_zenith_mean reduces. */
 typedef struct GrtZenithArgs
 {
     double const *mu;               /* DEVICE [ncol][zeniths] */
@@ -435,10 +440,19 @@ static inline int grt_zenith_args_ok(GrtZenithArgs const *z)
    (grt_sw_one_sweep(a) must hold: hipErrorInvalidValue otherwise): grid row y is column y / chunks and the
    GRT_ZENITH_CHUNK consecutive angles from (y % chunks) GRT_ZENITH_CHUNK on, chunks = ceil(zeniths / GRT_ZENITH_CHUNK);
    a thread forms a layer's optics, delta-scaling and diffuse Eddington solution once and the direct-beam solution per
-   angle.  Every angle's partial sums are, bit for bit, the zenith instance's of GRT_OUT_ROWS (first and count are not
-   read: one launch takes every angle). */
+   angle.  Every angle's partial sums are, bit for bit, the zenith instance's of GRT_OUT_ROWS (z's first and count are not
+   read: one launch takes every angle).  sc, ae (either may be NULL): the kernel's instance with the draws of sc, the
+   aerosol object or both joined, as the zenith instances join them -- grid row y is then (column, draw first + .. of
+   sc->count, chunk), the chunks of a draw next to each other, at most 65 535 rows, and the partial sums lie at the slot
+   (c zeniths + k) subcolumns + s.  Each instance carries the most angles of {2, 4} that leave it three waves per SIMD
+   and no scratch; grt_zenith_chunk names an instance's. */
 #define GRT_ZENITH_CHUNK 4
-int grt_launch_sw_zeniths(void *stream, GrtSwArgs const *a, GrtZenithArgs const *z);
+#define GRT_ZENITH_CHUNK_AEROSOLS 4
+#define GRT_ZENITH_CHUNK_SUBCOLUMNS 4
+#define GRT_ZENITH_CHUNK_SUBCOLUMNS_AEROSOLS 4
+int grt_zenith_chunk(GrtSubcolumnArgs const *sc, GrtAerosolArgs const *ae);
+int grt_launch_sw_zeniths(void *stream, GrtSwArgs const *a, GrtZenithArgs const *z, GrtSubcolumnArgs const *sc,
+                          GrtAerosolArgs const *ae);
 /* The weighted mean over a column's angles of one output row, in a fixed order, and every angle's own rows: for column c
    and row r (of `rows` per slot) each angle's blocks are added as grt_launch_reduce_partials adds them -- an angle whose
    mu [ncol][zeniths] is <= 0 counts as +0.0 whatever its partial sums hold -- and stored at per_angle[(c zeniths + k) rows
@@ -450,6 +464,16 @@ int grt_launch_sw_zeniths(void *stream, GrtSwArgs const *a, GrtZenithArgs const 
 int grt_launch_zenith_mean(void *stream, double const *partials, int ncol, int zeniths, int rows, unsigned nblocks,
                            double const *mu, double const *weight, double *per_angle, double *six, int user_level,
                            double *out, int out_stride, int out_offset);
+/* grt_pipeline_run_sky_zeniths' mean of one set: grt_launch_zenith_mean over partial sums that hold `subcolumns` draws per
+   angle, at the slot (c zeniths + k) subcolumns + s, and with the set dimension in the per-angle outputs.  For column c,
+   row r and angle k: each draw's blocks are added as grt_launch_reduce_partials adds them, the draws s = 0 .. S - 1 in
+   order, then -- S > 1 -- one division by S, as grt_launch_subcolumn_mean does; a night angle counts as +0.0; stored at
+   per_angle[((c sets + set) zeniths + k) rows + r] (NULL: not stored) and, rows = 2 V, the angle's six rows at
+   six[((c sets + set) zeniths + k) 6 ..] (NULL: not stored); then the angles fold as in grt_launch_zenith_mean, to
+   out[c out_stride + out_offset + r] (NULL: not formed).  subcolumns = 1 and sets = 1: grt_launch_zenith_mean's bits. */
+int grt_launch_sky_zenith_mean(void *stream, double const *partials, int ncol, int zeniths, int subcolumns, int rows,
+                               unsigned nblocks, double const *mu, double const *weight, double *per_angle, double *six,
+                               int sets, int set, int user_level, double *out, int out_stride, int out_offset);
 
 /* Direct-beam form of the shortwave's fused six-row and profile forms (direct joined, with any of the cloud and aerosol
    joins or none; grt_pipeline_run_sky_direct): the instance's arguments, sweeps and partial sums, and beside them the
@@ -514,7 +538,7 @@ typedef enum GrtSolverOutput
    the aerosol object, or the cloud objects of several subcolumns per column -- or the aerosol object together with either
    form of the clouds (GRT_OUT_ROWS and GRT_OUT_LEVELS: the five objects of sky_combine, optics_dev.h; the aerosol table
    stays per column whatever the subcolumn); `bins` goes with GRT_OUT_LEVEL_BINS and with nothing else; `zeniths` (the
-   shortwave's GRT_OUT_ROWS and GRT_OUT_LEVELS) goes with no other join; `direct` (the shortwave's GRT_OUT_ROWS and
+   shortwave's GRT_OUT_ROWS and GRT_OUT_LEVELS) goes alone or with aerosols, subcolumns or both, never with `clouds`; `direct` (the shortwave's GRT_OUT_ROWS and
    GRT_OUT_LEVELS) goes with any join of clouds and aerosols or none, and selects instances of its own: the instance
    without it is the one it was.  The kind of instance follows from which pointers are set, and a kernel takes the structs that are
    set as arguments after its band's own.  The next joined object is a pointer here, a line in grt_solver_instance_ok
@@ -532,7 +556,8 @@ typedef struct GrtSolverInstance
 typedef enum GrtSolverJoin
 {
     GRT_JOIN_NONE, GRT_JOIN_CLOUDS, GRT_JOIN_AEROSOLS, GRT_JOIN_SUBCOLUMNS, GRT_JOIN_CLOUDS_AEROSOLS,
-    GRT_JOIN_SUBCOLUMNS_AEROSOLS, GRT_JOIN_ZENITHS, GRT_JOIN_COUNT
+    GRT_JOIN_SUBCOLUMNS_AEROSOLS, GRT_JOIN_ZENITHS, GRT_JOIN_ZENITHS_AEROSOLS, GRT_JOIN_ZENITHS_SUBCOLUMNS,
+    GRT_JOIN_ZENITHS_SUBCOLUMNS_AEROSOLS, GRT_JOIN_COUNT
 } GrtSolverJoin;
 /* an instance as one integer: the case labels of a band's list of instances (the launchers' switches) */
 #define GRT_INSTANCE(out, join) ((int)(out)*(int)GRT_JOIN_COUNT + (int)(join))
@@ -545,13 +570,14 @@ GRT_FN int grt_out_fused(GrtSolverOutput out) { return out >= GRT_OUT_ROWS; }
 GRT_FN int grt_out_levels(GrtSolverOutput out) { return out >= GRT_OUT_LEVELS; }
 #undef GRT_FN
 /* which pointers are set -- of an instance grt_solver_instance_ok has passed: it refuses clouds together with
-   subcolumns, zeniths together with anything, and any join of an output that is not fused, so a band's switch sees no
+   subcolumns and with zeniths, and any join of an output that is not fused, so a band's switch sees no
    such case */
 static inline GrtSolverJoin grt_solver_join(GrtSolverInstance const *in)
 {
     if (in->zeniths != NULL)
     {
-        return GRT_JOIN_ZENITHS;
+        return in->subcolumns != NULL ? (in->aerosols != NULL ? GRT_JOIN_ZENITHS_SUBCOLUMNS_AEROSOLS : GRT_JOIN_ZENITHS_SUBCOLUMNS) :
+               (in->aerosols != NULL ? GRT_JOIN_ZENITHS_AEROSOLS : GRT_JOIN_ZENITHS);
     }
     if (in->aerosols != NULL && (in->clouds != NULL || in->subcolumns != NULL))
     {
@@ -560,11 +586,12 @@ static inline GrtSolverJoin grt_solver_join(GrtSolverInstance const *in)
     return in->clouds != NULL ? GRT_JOIN_CLOUDS : (in->aerosols != NULL ? GRT_JOIN_AEROSOLS :
            (in->subcolumns != NULL ? GRT_JOIN_SUBCOLUMNS : GRT_JOIN_NONE));
 }
-/* the rows of its grid: a column each, or (subcolumns, zeniths) `count` subcolumns or angles of every column */
+/* the rows of its grid: a column each, or (subcolumns, zeniths) `count` subcolumns or angles of every column -- with both,
+   every angle of every subcolumn of the launch */
 static inline uint64_t grt_solver_grid_rows(GrtSolverInstance const *in, int ncol)
 {
-    return (uint64_t)ncol*(uint64_t)(in->subcolumns != NULL ? in->subcolumns->count :
-                                     (in->zeniths != NULL ? in->zeniths->count : 1));
+    return (uint64_t)ncol*(uint64_t)(in->subcolumns != NULL ? in->subcolumns->count : 1)*
+           (uint64_t)(in->zeniths != NULL ? in->zeniths->count : 1);
 }
 /* its dynamic LDS: 2 V doubles per wave of its workgroup where every level leaves (3 V with the direct beam), that per bin
    of a block with bins */
@@ -692,8 +719,8 @@ inline bool grt_solver_instance_ok(GrtSolverInstance const &in, Args const &a)
     // (of the pairs, the aerosol object with either form of the clouds exists; clouds and subcolumns exclude each other)
     int const cloud_forms = (in.clouds != nullptr) + (in.subcolumns != nullptr);
     int const joined = cloud_forms + (in.aerosols != nullptr);
-    // (the sun angles join the clear-sky six-row and level forms alone)
-    bool const zeniths_ok = in.zeniths == nullptr || (joined == 0 && grt_zenith_args_ok(in.zeniths) &&
+    // (the sun angles join the six-row and level forms: clear sky, or with aerosols, subcolumns or both)
+    bool const zeniths_ok = in.zeniths == nullptr || (in.clouds == nullptr && grt_zenith_args_ok(in.zeniths) &&
                                                       (in.out == GRT_OUT_ROWS || in.out == GRT_OUT_LEVELS));
     // (the direct beam leaves the six-row and level forms, under one sun per column; the longwave launcher has no such case)
     bool const direct_ok = in.direct == nullptr || (in.zeniths == nullptr && grt_direct_args_ok(in.direct) &&

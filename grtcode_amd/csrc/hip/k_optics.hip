@@ -527,6 +527,63 @@ __global__ __launch_bounds__(64) void zenith_mean_kernel(double const *partials,
     }
 }
 
+// grt_pipeline_run_sky_zeniths: zenith_mean_kernel for one set of a column's `sets`, over partial sums that hold S cloud
+// draws per angle (slot (c Z + k) S + s).  One wavefront per (column, row): blocks as reduce_partials_kernel adds them,
+// the draws in order and one division by S as subcolumn_mean_kernel's (S = 1: none), a night angle +0.0, the angle's
+// value stored where the set's per-angle rows lie; then the angles as zenith_mean_kernel folds them.
+__global__ __launch_bounds__(64) void sky_zenith_mean_kernel(double const *partials, int Z, int S, int rows, unsigned nblocks,
+                                                             double const *mu, double const *weight, double *per_angle,
+                                                             double *six, int sets, int set, int user, double *out,
+                                                             int out_stride, int out_offset)
+{
+    int const c = blockIdx.x/rows;
+    int const r = blockIdx.x - c*rows;
+    double m = 0.;
+    for (int k = 0; k < Z; ++k)
+    {
+        uint64_t const sun = (uint64_t)c*Z + k, angle = ((uint64_t)c*sets + set)*Z + k;
+        double x = 0.;
+        for (int s = 0; s < S; ++s)
+        {
+            double const xs = wave_strided_sum(partials + ((sun*S + s)*rows + r)*nblocks, nblocks);
+            x = s == 0 ? xs : x + xs;
+        }
+        x = S > 1 ? x/(double)S : x;
+        x = mu[sun] > 0. ? x : 0.;
+        if (per_angle != nullptr && threadIdx.x == 0)
+        {
+            per_angle[angle*rows + r] = x;
+        }
+        if (six != nullptr && threadIdx.x == 0)
+        {
+            int const V = rows/2, down = r/V, lev = r - down*V;
+            double *q = six + angle*6 + 3*down;
+            if (lev == 0)
+            {
+                q[0] = x;
+                if (user < 0)
+                {
+                    q[2] = 0.;
+                }
+            }
+            if (lev == V - 1)
+            {
+                q[1] = x;
+            }
+            if (lev == user)
+            {
+                q[2] = x;
+            }
+        }
+        double const term = weight != nullptr ? weight[sun]*x : x;
+        m = k == 0 ? term : m + term;
+    }
+    if (out != nullptr && threadIdx.x == 0)
+    {
+        out[(uint64_t)c*out_stride + out_offset + r] = weight != nullptr ? m : m/(double)Z;
+    }
+}
+
 } // namespace
 
 extern "C" int grt_launch_band_profile_finish(void *stream, int ncol, int sets, int num_levels, int lw_bins, int sw_bins,
@@ -599,6 +656,24 @@ extern "C" int grt_launch_zenith_mean(void *stream, double const *partials, int 
     }
     hipLaunchKernelGGL(zenith_mean_kernel, dim3((unsigned)(ncol*rows)), dim3(64), 0, (hipStream_t)stream, partials, zeniths,
                        rows, nblocks, mu, weight, per_angle, six, user_level, out, out_stride, out_offset);
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_sky_zenith_mean(void *stream, double const *partials, int ncol, int zeniths, int subcolumns,
+                                          int rows, unsigned nblocks, double const *mu, double const *weight,
+                                          double *per_angle, double *six, int sets, int set, int user_level, double *out,
+                                          int out_stride, int out_offset)
+{
+    if (ncol < 1 || zeniths < 1 || subcolumns < 1 || rows < 1 || nblocks < 1 ||
+        (uint64_t)ncol*(uint64_t)rows > 0x7fffffffull || sets < 1 || set < 0 || set >= sets || partials == nullptr ||
+        mu == nullptr || (out == nullptr && per_angle == nullptr && six == nullptr) ||
+        (six != nullptr && (rows % 2 != 0 || user_level >= rows/2)))
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(sky_zenith_mean_kernel, dim3((unsigned)(ncol*rows)), dim3(64), 0, (hipStream_t)stream, partials,
+                       zeniths, subcolumns, rows, nblocks, mu, weight, per_angle, six, sets, set, user_level, out,
+                       out_stride, out_offset);
     return (int)hipGetLastError();
 }
 

@@ -21,8 +21,8 @@
 // fluxes (GRT_OUT_CHAINS), or, fused, the partial sums of the six rows, of the six rows that are also stored at every
 // point, of every level, or of every level per wavenumber bin -- and what joins gas and Rayleigh is the types of its
 // pack: nothing, GrtCloudArgs, GrtAerosolArgs or GrtSubcolumnArgs, a GrtAerosolArgs behind either form of the clouds where
-// both join, a GrtBandArgs last where OUT is per bin, or a GrtZenithArgs alone (several sun angles per column); a
-// GrtDirectArgs last (six rows or every level, with any of the cloud and aerosol joins) makes the instance that also
+// both join, a GrtBandArgs last where OUT is per bin, or a GrtZenithArgs (several sun angles per column: alone, or last
+// behind a GrtAerosolArgs, a GrtSubcolumnArgs or both, six rows or every level); a GrtDirectArgs last (six rows or every level, with any of the cloud and aerosol joins) makes the instance that also
 // leaves the direct beam of its sweep (LevelSink: DIRECT).
 // The in-kernel range checks of the reference are no-ops on device builds
 // (debug.h:105-116) and are not restated.
@@ -281,7 +281,7 @@ __device__ __forceinline__ double row_mu(GrtSwArgs const &a, SolverRow const &ro
 {
     if constexpr (has<GrtZenithArgs, Joins...>)
     {
-        return pick<GrtZenithArgs>(joins...).mu[row.slot];
+        return pick<GrtZenithArgs>(joins...).mu[row.sun];
     }
     else
     {
@@ -472,24 +472,35 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Joins... 
 }
 
 // ---- several sun angles per column on one walk through the layers (grt_launch_sw_zeniths) ----
-// Of sw_kernel<GRT_OUT_ROWS>'s one sweep, a layer's optics (tau_gas, continua, Rayleigh: LayerOptics), its delta-scaling,
-// its diffuse Eddington solution with k and exp(+-t k), and C, Ru, Tu of the sweep depend on the optics alone; the angle's
-// own are the direct-beam solution, dir, dif, Rd and the scale at the surface.  Grid row y is a column and a chunk of ZN
-// consecutive angles: the thread does the shared part of a layer once and the angle's part ZN times, each in sw_kernel's
-// expressions and order on the same doubles (exp(+-t k) is a function of its argument, whichever call evaluates it
-// first), so every angle's partial sums are the zenith instance's of sw_kernel<GRT_OUT_ROWS>, bit for bit.  Angles past
-// the column's last and night angles (mu <= 0) are skipped by flags that are uniform per workgroup; a night angle's slot
-// gets +0.0.
-template <int ZN>
-__global__ __launch_bounds__(kSolverBlock) void sw_zenith_kernel(GrtSwArgs a, GrtZenithArgs zn)
+// Of sw_kernel<GRT_OUT_ROWS>'s one sweep, a layer's optics (tau_gas, continua, Rayleigh and what joins them: LayerOptics),
+// its delta-scaling, its diffuse Eddington solution with k and exp(+-t k), and C, Ru, Tu of the sweep depend on the optics
+// alone; the angle's own are the direct-beam solution, dir, dif, Rd and the scale at the surface.  Grid row y is a column, a
+// cloud draw of it (Joins holds a GrtSubcolumnArgs: draws first .. first + count - 1, the chunks of a draw next to each
+// other) and a chunk of ZN consecutive angles: the thread does the shared part of a layer once and the angle's part ZN
+// times, each in sw_kernel's expressions and order on the same doubles (exp(+-t k) is a function of its argument, whichever
+// call evaluates it first), so every angle's partial sums are the zenith instance's of sw_kernel<GRT_OUT_ROWS> with the
+// same joins, bit for bit, at its slot (c zeniths + k) subcolumns + s.  Angles past the column's last and night angles
+// (mu <= 0) are skipped by flags that are uniform per workgroup; a night angle's slot gets +0.0.  Joins: nothing, a
+// GrtAerosolArgs, a GrtSubcolumnArgs, or a GrtAerosolArgs behind a GrtSubcolumnArgs.
+template <int ZN, typename... Joins>
+__global__ __launch_bounds__(kSolverBlock) void sw_zenith_kernel(GrtSwArgs a, GrtZenithArgs zn, Joins... joins)
 {
     uint64_t const i = (uint64_t)blockIdx.x*kSolverBlock + threadIdx.x;
     bool const live = i < a.nw;
     uint64_t const ii = live ? i : a.nw - 1;      // (idle lanes of the last block follow along, weight 0)
     int const Z = zn.zeniths, chunks = (Z + ZN - 1)/ZN;
     int const y = blockIdx.y;
-    int const col = y/chunks;
-    int const k0 = (y - col*chunks)*ZN;
+    int const cd = y/chunks;                      // (column, or -- subcolumns -- column and draw)
+    int const k0 = (y - cd*chunks)*ZN;
+    int col = cd, tab = cd, S = 1, draw = 0;
+    if constexpr (has<GrtSubcolumnArgs, Joins...>)
+    {
+        GrtSubcolumnArgs const sc = pick<GrtSubcolumnArgs>(joins...);
+        col = cd/sc.count;
+        draw = sc.first + (cd - col*sc.count);
+        tab = draw*a.ncol + col;
+        S = sc.subcolumns;
+    }
     int const L = a.num_levels - 1;
     double const mu_dif = a.mu_dif;
     double mu[ZN];
@@ -511,7 +522,8 @@ __global__ __launch_bounds__(kSolverBlock) void sw_zenith_kernel(GrtSwArgs a, Gr
     double Ru = 0., Tu = 1.;
     if (any)
     {
-        LayerOptics<true, false, false> const optics(a, GrtCloudArgs{}, col, col, ii);
+        LayerOptics<true, has_clouds<Joins...>, has<GrtAerosolArgs, Joins...>> const optics(
+            a, pick_clouds(joins...), col, tab, ii, pick<GrtAerosolArgs>(joins...));
         for (int j = 0; j < L; ++j)
         {
             double t, om, gg, os, gs, ts;
@@ -545,7 +557,7 @@ __global__ __launch_bounds__(kSolverBlock) void sw_zenith_kernel(GrtSwArgs a, Gr
         {
             continue;
         }
-        int const slot = col*Z + k0 + u;
+        int const slot = (col*Z + k0 + u)*S + draw;
         if (!day[u])
         {
             if (threadIdx.x < 6)
@@ -831,26 +843,70 @@ extern "C" int grt_launch_sw(void *stream, GrtSolverInstance const *in, GrtSwArg
         return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->aerosols);
     case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->zeniths);
     case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->zeniths);
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS_AEROSOLS):
+        return launch<GRT_OUT_ROWS>(s, *in, *a, *in->aerosols, *in->zeniths);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS_AEROSOLS):
+        return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->aerosols, *in->zeniths);
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS_SUBCOLUMNS):
+        return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns, *in->zeniths);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS_SUBCOLUMNS):
+        return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->zeniths);
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS_SUBCOLUMNS_AEROSOLS):
+        return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns, *in->aerosols, *in->zeniths);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS_SUBCOLUMNS_AEROSOLS):
+        return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->aerosols, *in->zeniths);
     default:
         return (int)hipErrorInvalidValue;
     }
 }
 
-extern "C" int grt_launch_sw_zeniths(void *stream, GrtSwArgs const *a, GrtZenithArgs const *z)
+namespace {
+
+// the one launch site of sw_zenith_kernel: ZN angles per thread, grid row = (column, draw of the launch, chunk)
+template <int ZN, typename... Joins>
+int launch_zeniths(hipStream_t s, GrtSwArgs const &a, GrtZenithArgs const &z, int draws, Joins const &...joins)
 {
-    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (!grt_solver_instance_ok(in, *a) || z == nullptr || z->mu == nullptr || z->zeniths < 1 || !grt_sw_one_sweep(a))
-    {
-        return (int)hipErrorInvalidValue;
-    }
-    uint64_t const rows = (uint64_t)a->ncol*(uint64_t)((z->zeniths + GRT_ZENITH_CHUNK - 1)/GRT_ZENITH_CHUNK);
+    uint64_t const rows = (uint64_t)a.ncol*(uint64_t)draws*(uint64_t)((z.zeniths + ZN - 1)/ZN);
     if (rows > 65535u)
     {
         return (int)hipErrorInvalidValue;
     }
-    hipLaunchKernelGGL((sw_zenith_kernel<GRT_ZENITH_CHUNK>), dim3(grt_solver_blocks(a->nw), (unsigned)rows, 1),
-                       dim3(kSolverBlock), 0, (hipStream_t)stream, *a, *z);
+    hipLaunchKernelGGL((sw_zenith_kernel<ZN, Joins...>), dim3(grt_solver_blocks(a.nw), (unsigned)rows, 1),
+                       dim3(kSolverBlock), 0, s, a, z, joins...);
     return (int)hipGetLastError();
+}
+
+} // namespace
+
+extern "C" int grt_zenith_chunk(GrtSubcolumnArgs const *sc, GrtAerosolArgs const *ae)
+{
+    return sc != nullptr ? (ae != nullptr ? GRT_ZENITH_CHUNK_SUBCOLUMNS_AEROSOLS : GRT_ZENITH_CHUNK_SUBCOLUMNS) :
+           (ae != nullptr ? GRT_ZENITH_CHUNK_AEROSOLS : GRT_ZENITH_CHUNK);
+}
+
+extern "C" int grt_launch_sw_zeniths(void *stream, GrtSwArgs const *a, GrtZenithArgs const *z, GrtSubcolumnArgs const *sc,
+                                     GrtAerosolArgs const *ae)
+{
+    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (!grt_solver_instance_ok(in, *a) || z == nullptr || z->mu == nullptr || z->zeniths < 1 || !grt_sw_one_sweep(a) ||
+        (sc != nullptr && !grt_subcolumn_args_ok(sc)) || (ae != nullptr && !grt_aerosol_args_ok(ae)))
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipStream_t const s = (hipStream_t)stream;
+    if (sc != nullptr && ae != nullptr)
+    {
+        return launch_zeniths<GRT_ZENITH_CHUNK_SUBCOLUMNS_AEROSOLS>(s, *a, *z, sc->count, *sc, *ae);
+    }
+    if (sc != nullptr)
+    {
+        return launch_zeniths<GRT_ZENITH_CHUNK_SUBCOLUMNS>(s, *a, *z, sc->count, *sc);
+    }
+    if (ae != nullptr)
+    {
+        return launch_zeniths<GRT_ZENITH_CHUNK_AEROSOLS>(s, *a, *z, 1, *ae);
+    }
+    return launch_zeniths<GRT_ZENITH_CHUNK>(s, *a, *z, 1);
 }
 
 extern "C" int grt_launch_sw_direct_beam(void *stream, GrtSwArgs const *a, double *direct)

@@ -177,33 +177,48 @@ __device__ __forceinline__ GrtCloudArgs pick_clouds(Pack const &...pack)
 }
 
 // What grid row blockIdx.y stands for: col, the column whose gas state (tau_gas, temperatures, sun) and aerosol table it
-// reads; tab, its cloud tables' column; slot, its partial sums' column; park, its rows of the shortwave park block.  All four are
-// blockIdx.y but in the subcolumn instances (GrtSubcolumnArgs: row y is column y / count, subcolumn first + y % count) and
-// in the zenith instances (GrtZenithArgs: row y is column y / count, angle first + y % count; the slot, c zeniths + k, is
-// also where the row's cosine of the zenith angle lies in the join's mu).
-struct SolverRow { int col, tab, slot, park; };
+// reads; tab, its cloud tables' column; slot, its partial sums' column; park, its rows of the shortwave park block; sun,
+// where its cosine of the zenith angle lies (the zenith instances: in the join's mu).  All are blockIdx.y but in the
+// subcolumn instances (GrtSubcolumnArgs: row y is column y / count, subcolumn first + y % count), in the zenith instances
+// (GrtZenithArgs: row y is column y / count, angle first + y % count; the slot is c zeniths + k, and so is sun) and in the
+// instances that hold both (row y is column y / (draws x angles), draw s and angle k from the remainder, the angles of a
+// draw next to each other; the slot is (c zeniths + k) subcolumns + s, sun stays c zeniths + k).
+struct SolverRow { int col, tab, slot, park, sun; };
 
 template <typename... Pack>
 __device__ __forceinline__ SolverRow solver_row(int ncol, Pack const &...pack)
 {
     int const y = blockIdx.y;
-    if constexpr (has<GrtSubcolumnArgs, Pack...>)
+    if constexpr (has<GrtSubcolumnArgs, Pack...> && has<GrtZenithArgs, Pack...>)
+    {
+        GrtSubcolumnArgs const sc = pick<GrtSubcolumnArgs>(pack...);
+        GrtZenithArgs const zn = pick<GrtZenithArgs>(pack...);
+        int const per = sc.count*zn.count;
+        int const c = y/per;
+        int const rest = y - c*per;
+        int const ds = rest/zn.count;
+        int const s = sc.first + ds;
+        int const k = zn.first + (rest - ds*zn.count);
+        int const sun = c*zn.zeniths + k;
+        return SolverRow{c, s*ncol + c, sun*sc.subcolumns + s, y, sun};
+    }
+    else if constexpr (has<GrtSubcolumnArgs, Pack...>)
     {
         GrtSubcolumnArgs const sc = pick<GrtSubcolumnArgs>(pack...);
         int const c = y/sc.count;
         int const s = sc.first + (y - c*sc.count);
-        return SolverRow{c, s*ncol + c, c*sc.subcolumns + s, y};
+        return SolverRow{c, s*ncol + c, c*sc.subcolumns + s, y, c};
     }
     else if constexpr (has<GrtZenithArgs, Pack...>)
     {
         GrtZenithArgs const zn = pick<GrtZenithArgs>(pack...);
         int const c = y/zn.count;
         int const k = zn.first + (y - c*zn.count);
-        return SolverRow{c, c, c*zn.zeniths + k, y};
+        return SolverRow{c, c, c*zn.zeniths + k, y, c*zn.zeniths + k};
     }
     else
     {
-        return SolverRow{y, y, y, y};
+        return SolverRow{y, y, y, y, y};
     }
 }
 

@@ -33,6 +33,8 @@
  * one gas-optics launch per band: the passes of the entry points above, and the pass that joins aerosol and clouds.
  * grt_pipeline_run_sky_direct is grt_pipeline_run_sky with the direct beam of every set's shortwave beside its rows: taken
  * out of the same solver launches (instances that leave it too), or -- materialised form -- formed from each set's optics.
+ * grt_pipeline_run_sky_zeniths is grt_pipeline_run_sky with the shortwave of every set solved under several sun angles per
+ * column, as grt_pipeline_run_zeniths solves the clean set's: one gas-optics launch per band, one set of cloud draws.
  * grt_pipeline_run_band_profiles runs the profile form of the clear-sky pass and, with clouds, of the all-sky pass with
  * every level's flux integrated per wavenumber bin instead of over the whole grid, and one finishing launch for the bins'
  * heating rates.
@@ -484,7 +486,8 @@ typedef struct GrtJoin
     GrtAerosols_t const *aerosols;
     int subcolumns;
     unsigned sets;
-    GrtZeniths_t const *zeniths;       /* grt_pipeline_run_zeniths: the shortwave's clean set is the mean over these angles */
+    GrtZeniths_t const *zeniths;       /* grt_pipeline_run_zeniths, _run_sky_zeniths: every set's shortwave is the mean over
+                                          these angles; with `sets`, the per-angle outputs hold every set's */
 } GrtJoin;
 
 #define GRT_SKY_ALL (GRT_SKY_CLEAN | GRT_SKY_AEROSOL | GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL)
@@ -534,6 +537,7 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
     if (join->zeniths != NULL)
     {
         GRT_TRY(grt_stage_zeniths(p, join->zeniths, C, &zr));
+        zr.sky = join->sets != 0;
     }
     if (cl != NULL && join->sampler != NULL)
     {
@@ -610,7 +614,7 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
             {
                 zr.per_angle = rows->profile ? join->zeniths->zenith_level_fluxes_dev : join->zeniths->zenith_fluxes_dev;
                 zr.six = rows->profile ? join->zeniths->zenith_fluxes_dev : NULL;
-                GRT_TRY(grt_band_solve_zeniths(p, b, C, &ps, &zr));
+                GRT_TRY(grt_band_solve_zeniths(p, b, C, S, &ps, &zr));
             }
             else
             {
@@ -713,12 +717,10 @@ EXTERN int grt_pipeline_run_profiles(GrtPipeline_t *p, GrtColumns_t const *cols,
     return GRTCODE_SUCCESS;
 }
 
-/* grt_ext.h: the clear-clean set under several sun angles per column, on one gas-optics pass per band */
-EXTERN int grt_pipeline_run_zeniths(GrtPipeline_t *p, GrtColumns_t const *cols, GrtZeniths_t const *zn,
-                                    fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev)
+/* grt_pipeline_run_zeniths' and grt_pipeline_run_sky_zeniths' checks of the sun angles, the outputs and the batch */
+static int check_zeniths(GrtPipeline_t const *p, GrtColumns_t const *cols, GrtZeniths_t const *zn, fp_t const *level_fluxes_dev,
+                         fp_t const *fluxes_dev)
 {
-    GRT_REQUIRE_PTR(p);
-    GRT_REQUIRE_PTR(cols);
     if (zn == NULL)
     {
         GRT_FAIL(GRTCODE_VALUE_ERR, "no sun angles (GrtZeniths_t is NULL).%s", "");
@@ -764,20 +766,28 @@ EXTERN int grt_pipeline_run_zeniths(GrtPipeline_t *p, GrtColumns_t const *cols, 
                      k % (size_t)zn->num_zeniths, k/(size_t)zn->num_zeniths, zn->weight[k]);
         }
     }
-    /* grt_pipeline_run's layout, or grt_pipeline_run_profiles' three; the shortwave rows the mean over the angles */
-    GrtJoin const join = {.zeniths = zn};
+    return GRTCODE_SUCCESS;
+}
+
+/* What closes both: the run of `sets` sets per column under the angles of join->zeniths, in the form the outputs ask for
+   (fluxes_dev may be NULL with a per-angle output: then neither the longwave nor the mean is formed) */
+static int run_under_zeniths(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin const *join, int sets,
+                             fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev)
+{
+    GrtZeniths_t const *zn = join->zeniths;
     GrtPass rows;
     memset(&rows, 0, sizeof(rows));
-    rows.profile = profile;
-    rows.out = profile ? level_fluxes_dev : fluxes_dev;
-    rows.sets = 1;
-    rows.out_stride = grt_set_offset(p, profile);
-    GRT_TRY(pipeline_run(p, cols, &join, &rows));
+    rows.profile = level_fluxes_dev != NULL;
+    rows.out = rows.profile ? level_fluxes_dev : fluxes_dev;
+    rows.sets = sets;
+    rows.out_stride = sets*grt_set_offset(p, rows.profile);
+    GRT_TRY(pipeline_run(p, cols, join, &rows));
     GRT_TRY(finish_profiles(p, cols->ncol, &rows, heating_dev, fluxes_dev));
     if (p->band[1].gas == NULL)
     {
         /* no shortwave band: every angle's rows are zeros, as the band's rows of the mean are */
         void *s = grt_dev_stream(p->device);
+        size_t const n = (size_t)cols->ncol*(size_t)sets*(size_t)zn->num_zeniths;
         if (zn->zenith_fluxes_dev != NULL)
         {
             GRT_TRY(grt_dev_zero(p->device, zn->zenith_fluxes_dev, sizeof(double)*n*GRT_FLUXES_PER_BAND, s));
@@ -787,6 +797,19 @@ EXTERN int grt_pipeline_run_zeniths(GrtPipeline_t *p, GrtColumns_t const *cols, 
             GRT_TRY(grt_dev_zero(p->device, zn->zenith_level_fluxes_dev, sizeof(double)*n*2*(size_t)p->num_levels, s));
         }
     }
+    return GRTCODE_SUCCESS;
+}
+
+/* grt_ext.h: the clear-clean set under several sun angles per column, on one gas-optics pass per band */
+EXTERN int grt_pipeline_run_zeniths(GrtPipeline_t *p, GrtColumns_t const *cols, GrtZeniths_t const *zn,
+                                    fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    GRT_TRY(check_zeniths(p, cols, zn, level_fluxes_dev, fluxes_dev));
+    /* grt_pipeline_run's layout, or grt_pipeline_run_profiles' three; the shortwave rows the mean over the angles */
+    GrtJoin const join = {.zeniths = zn};
+    GRT_TRY(run_under_zeniths(p, cols, &join, 1, level_fluxes_dev, heating_dev, fluxes_dev));
     return GRTCODE_SUCCESS;
 }
 
@@ -945,30 +968,16 @@ EXTERN int grt_pipeline_run_aerosols(GrtPipeline_t *p, GrtColumns_t const *cols,
     return GRTCODE_SUCCESS;
 }
 
-/* grt_pipeline_run_sky and, with_direct, grt_pipeline_run_sky_direct: the same request, the direct outputs attached */
-static int run_sky(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky, int with_direct,
-                   GrtDirectBeam_t const *direct, fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev)
+/* grt_pipeline_run_sky's (, _sky_direct's and _sky_zeniths') checks of the request: the sets, and that what they need is
+   there; *nsets: the sets per column */
+static int check_sky_sets(GrtSky_t const *sky, int *nsets)
 {
-    GRT_REQUIRE_PTR(p);
-    GRT_REQUIRE_PTR(cols);
-    if (with_direct)
-    {
-        if (direct == NULL || direct->direct_fluxes_dev == NULL)
-        {
-            GRT_FAIL(GRTCODE_VALUE_ERR, "%s is NULL: the direct-beam rows [ncol][sets][%d] are the output.",
-                     direct == NULL ? "direct (GrtDirectBeam_t)" : "direct_fluxes_dev", GRT_DIRECT_ROWS_PER_SET);
-        }
-        if (level_fluxes_dev == NULL && direct->direct_level_fluxes_dev != NULL)
-        {
-            GRT_FAIL(GRTCODE_VALUE_ERR, "direct_level_fluxes_dev is given in the six-row form (level_fluxes_dev is NULL).%s", "");
-        }
-    }
     if (sky == NULL)
     {
         GRT_FAIL(GRTCODE_VALUE_ERR, "no sky inputs (GrtSky_t is NULL).%s", "");
     }
-    int const nsets = grt_pipeline_sky_set_count(sky->sets);
-    if (nsets == 0)
+    *nsets = grt_pipeline_sky_set_count(sky->sets);
+    if (*nsets == 0)
     {
         GRT_FAIL(GRTCODE_VALUE_ERR, "sets 0x%x: bits outside GRT_SKY_CLEAN | _AEROSOL | _CLOUD | _CLOUD_AEROSOL (0x%x).",
                  sky->sets, GRT_SKY_ALL);
@@ -987,30 +996,65 @@ static int run_sky(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *s
     {
         GRT_FAIL(GRTCODE_VALUE_ERR, "%d subcolumns asked for: 1 to %d.", sky->num_subcolumns, GRT_MAX_SUBCOLUMNS);
     }
-    GrtPass rows;
-    GRT_TRY(output_form(p, nsets, level_fluxes_dev, fluxes_dev, &rows));
+    return GRTCODE_SUCCESS;
+}
+
+/* ... and of its inputs and the batch; *join: the run they describe, its aerosols in *a */
+static int sky_join(GrtPipeline_t const *p, GrtColumns_t const *cols, GrtSky_t const *sky, GrtAerosols_t *a, GrtJoin *join)
+{
+    int const with_clouds = (sky->sets & (GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL)) != 0;
+    int const with_aerosols = (sky->sets & (GRT_SKY_AEROSOL | GRT_SKY_CLOUD_AEROSOL)) != 0;
     /* (inputs that no set asks for are not looked at; a band the pipeline does not have ignores its aerosol fields) */
-    GrtAerosols_t a;
-    memset(&a, 0, sizeof(a));
+    memset(a, 0, sizeof(*a));
     if (with_aerosols)
     {
-        a = *sky->aerosols;
+        *a = *sky->aerosols;
         if (p->band[0].gas == NULL)
         {
-            a.lw_num_points = 0;
+            a->lw_num_points = 0;
         }
         if (p->band[1].gas == NULL)
         {
-            a.sw_num_points = 0;
+            a->sw_num_points = 0;
         }
-        GRT_TRY(check_aerosol_band("longwave", a.lw_num_points, a.lw_grid, a.lw_optics));
-        GRT_TRY(check_aerosol_band("shortwave", a.sw_num_points, a.sw_grid, a.sw_optics));
+        GRT_TRY(check_aerosol_band("longwave", a->lw_num_points, a->lw_grid, a->lw_optics));
+        GRT_TRY(check_aerosol_band("shortwave", a->sw_num_points, a->sw_grid, a->sw_optics));
     }
     GRT_TRY(with_clouds ? check_clouds(p, cols, sky->clouds) : check_columns(p, cols));
     /* one draw per column: the all-sky instances of the solvers; more: their subcolumn instances and the mean */
-    GrtJoin const join = {.clouds = with_clouds ? sky->clouds : NULL, .aerosols = with_aerosols ? &a : NULL,
-                          .subcolumns = with_clouds && sky->num_subcolumns > 1 ? sky->num_subcolumns : 0,
-                          .sets = sky->sets | GRT_SKY_CLEAN};
+    memset(join, 0, sizeof(*join));
+    join->clouds = with_clouds ? sky->clouds : NULL;
+    join->aerosols = with_aerosols ? a : NULL;
+    join->subcolumns = with_clouds && sky->num_subcolumns > 1 ? sky->num_subcolumns : 0;
+    join->sets = sky->sets | GRT_SKY_CLEAN;
+    return GRTCODE_SUCCESS;
+}
+
+/* grt_pipeline_run_sky and, with_direct, grt_pipeline_run_sky_direct: the same request, the direct outputs attached */
+static int run_sky(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky, int with_direct,
+                   GrtDirectBeam_t const *direct, fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    if (with_direct)
+    {
+        if (direct == NULL || direct->direct_fluxes_dev == NULL)
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "%s is NULL: the direct-beam rows [ncol][sets][%d] are the output.",
+                     direct == NULL ? "direct (GrtDirectBeam_t)" : "direct_fluxes_dev", GRT_DIRECT_ROWS_PER_SET);
+        }
+        if (level_fluxes_dev == NULL && direct->direct_level_fluxes_dev != NULL)
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "direct_level_fluxes_dev is given in the six-row form (level_fluxes_dev is NULL).%s", "");
+        }
+    }
+    int nsets;
+    GRT_TRY(check_sky_sets(sky, &nsets));
+    GrtPass rows;
+    GRT_TRY(output_form(p, nsets, level_fluxes_dev, fluxes_dev, &rows));
+    GrtAerosols_t a;
+    GrtJoin join;
+    GRT_TRY(sky_join(p, cols, sky, &a, &join));
     GrtBand *sw = &p->band[1];
     int const V = p->num_levels;
     if (with_direct && sw->gas != NULL)
@@ -1064,6 +1108,23 @@ EXTERN int grt_pipeline_run_sky_direct(GrtPipeline_t *p, GrtColumns_t const *col
                                        fp_t *fluxes_dev)
 {
     GRT_TRY(run_sky(p, cols, sky, 1, direct, level_fluxes_dev, heating_dev, fluxes_dev));
+    return GRTCODE_SUCCESS;
+}
+
+/* grt_ext.h: the sets of grt_pipeline_run_sky, the shortwave of each under several sun angles per column */
+EXTERN int grt_pipeline_run_sky_zeniths(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky,
+                                        GrtZeniths_t const *zn, fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    int nsets;
+    GRT_TRY(check_sky_sets(sky, &nsets));
+    GrtAerosols_t a;
+    GrtJoin join;
+    GRT_TRY(sky_join(p, cols, sky, &a, &join));
+    GRT_TRY(check_zeniths(p, cols, zn, level_fluxes_dev, fluxes_dev));
+    join.zeniths = zn;
+    GRT_TRY(run_under_zeniths(p, cols, &join, nsets, level_fluxes_dev, heating_dev, fluxes_dev));
     return GRTCODE_SUCCESS;
 }
 

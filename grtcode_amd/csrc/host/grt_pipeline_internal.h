@@ -55,8 +55,9 @@ enum
        (shortwave), and -- shortwave, when a diffuse albedo was given -- the diffuse albedo */
     GRT_SCRATCH_SURF_ROWS,
     GRT_SCRATCH_SURF_ROWS_DIF,
-    /* grt_pipeline_run_zeniths, shortwave: [max_cols][Z][6 or 2 V][nblocks] partial sums of every angle (materialised
-       form: [max_cols][Z][6 or 2 V] integrated rows) */
+    /* grt_pipeline_run_zeniths and grt_pipeline_run_sky_zeniths (its sets take the block in turn, in stream order),
+       shortwave: [max_cols][Z][S][6 or 2 V][nblocks] partial sums of every angle and cloud draw, S = 1 but in a cloud set
+       (materialised form: [max_cols][Z][S][6 or 2 V] integrated rows) */
     GRT_SCRATCH_ZEN_PARTIALS,
     /* grt_pipeline_run_sky_direct, shortwave, fused form: [max_cols][S][3 or V][nblocks] partial sums of the direct beam */
     GRT_SCRATCH_DIRECT_PARTIALS,
@@ -164,7 +165,7 @@ typedef struct GrtPass
     double *direct;
 } GrtPass;
 
-/* The sun angles of a grt_pipeline_run_zeniths call, staged (grt_stage_zeniths): Z per column, their cosines and weights
+/* The sun angles of a grt_pipeline_run_zeniths or grt_pipeline_run_sky_zeniths call, staged (grt_stage_zeniths): Z per column, their cosines and weights
    on the device, and where every angle's own rows go. */
 typedef struct GrtZenithRun
 {
@@ -174,6 +175,7 @@ typedef struct GrtZenithRun
     double const *mu_by_angle;     /* DEVICE [Z][ncol], a day angle everywhere (materialised form) */
     double *per_angle;             /* DEVICE [ncol][Z][6 or 2 V], or NULL */
     double *six;                   /* profile form: DEVICE [ncol][Z][6], every angle's six rows from its levels, or NULL */
+    int sky;                       /* grt_pipeline_run_sky_zeniths: both carry the pass's sets, [ncol][sets][Z][...] */
 } GrtZenithRun;
 
 /* the doubles from one set of a column to the next */
@@ -213,6 +215,7 @@ GRT_PRIVATE int grt_band_bins(GrtPipeline_t *p, GrtBand *b, int const *edges, in
 /* grt_pipeline_solve.c */
 GRT_PRIVATE int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps);
 GRT_PRIVATE int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S, GrtPass const *ps);
-GRT_PRIVATE int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *ps, GrtZenithRun const *zr);
+GRT_PRIVATE int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass const *ps,
+                                       GrtZenithRun const *zr);
 
 #endif

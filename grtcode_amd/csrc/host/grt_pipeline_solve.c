@@ -621,76 +621,125 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
     return GRTCODE_SUCCESS;
 }
 
-/* The shortwave of grt_pipeline_run_zeniths: the clear-clean pass under zr->zeniths sun angles per column on this run's
-   tau_gas, every angle's rows to zr->per_angle and their weighted mean to out as grt_band_solve writes its rows (either
-   may be NULL).  Fused form: each angle's partial sums in zen_partials -- six rows in one sweep: the shared-layer kernel,
-   or, GRT_ZENITH_SHARED=0 in the environment (read per call), the zenith instance of the six-row solver over C x Z grid
-   rows; otherwise the zenith instance, the two-sweep forms C x count angles at a time in the band's park block, count =
-   what fits in its max_cols, in stream order (GRT_TAG_ZENITH_SW) -- then the fixed-order mean (GRT_TAG_ZENITH_MEAN).
-   Materialised form: per angle the spectral solver on the pass's optics and the row-wise trapezoid into the angle's
-   rows of zen_partials; then the same mean kernel (one block per row). */
-int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *ps, GrtZenithRun const *zr)
+/* The shortwave of grt_pipeline_run_zeniths and of a set of grt_pipeline_run_sky_zeniths: the pass under zr->zeniths sun
+   angles per column on this run's tau_gas -- with clouds, as the mean over the S draws ps->clouds holds subcolumn-major,
+   the same draws under every angle --, every angle's rows to zr->per_angle and their weighted mean to out as
+   grt_band_solve writes its rows (either may be NULL).  Fused form: the partial sums of every (angle, draw) in
+   zen_partials, slot (c Z + k) S + s.  Here, and nowhere else, is decided which kernel leaves them: six rows in one sweep
+   may take the shared-layer kernel -- the clean pass unless GRT_ZENITH_SHARED=0 in the environment (read per call), a
+   pass with clouds or aerosols only with GRT_ZENITH_SHARED=1 --, in as many launches as 65 535 grid rows
+   of (column, draw, chunk) need; everything else takes the zenith instances of the solver over C x draws x angles grid
+   rows, the two-sweep forms as many (draw, angle) pairs at a time as fit the band's park block of max_cols columns, in
+   stream order.  The clean pass counts under GRT_TAG_ZENITH_SW, the others under GRT_TAG_SKY_ZENITH_SW.  Then the
+   fixed-order mean (GRT_TAG_ZENITH_MEAN; zr->sky: GRT_TAG_SKY_ZENITH_MEAN).  Materialised form: per draw the pass's
+   optics, per angle the spectral solver and the row-wise trapezoid into the (angle, draw) rows of zen_partials; then the
+   same mean kernel (one block per row). */
+int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass const *ps, GrtZenithRun const *zr)
 {
     int const Z = zr->zeniths, rows = pass_rows(p, ps), out_offset = pass_offset(p, ps, 1);
+    int const joined = ps->clouds != NULL || ps->aer != NULL;
+    int const sw_tag = ps->clouds != NULL || ps->aer_pass ? GRT_TAG_SKY_ZENITH_SW : GRT_TAG_ZENITH_SW;
     void *s = grt_dev_stream(p->device);
     GrtScratch *block = &b->scratch[GRT_SCRATCH_ZEN_PARTIALS];
     unsigned nblocks = 1;
+    S = ps->clouds != NULL ? S : 1;
     if (!p->keep_spectra)
     {
         nblocks = b->nblocks;
-        GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*(size_t)Z*(size_t)rows*nblocks, NULL));
-        /* (in points at za: the loop below walks za.first and za.count, which the launcher alone reads) */
+        GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*(size_t)Z*(size_t)S*(size_t)rows*nblocks, NULL));
+        /* (in points at za and sc: the loops below walk their first and count, which the launchers alone read) */
         GrtZenithArgs za = {zr->mu, Z, 0, 0};
-        GrtSolverInstance in = pass_instance(p, ps, NULL, NULL, NULL);
+        GrtSubcolumnArgs sc;
+        memset(&sc, 0, sizeof(sc));
+        if (ps->clouds != NULL)
+        {
+            sc.clouds = *ps->clouds;
+            sc.subcolumns = S;
+        }
+        GrtSubcolumnArgs *draws = ps->clouds != NULL ? &sc : NULL;
+        GrtSolverInstance in = pass_instance(p, ps, NULL, draws, NULL);
         in.zeniths = &za;
         SolverArgs a;
         GRT_TRY(solver_args(p, b, 1, C, ps, &in, block->d, &a));
         char const *env = getenv("GRT_ZENITH_SHARED");
         int const parks = grt_sw_parks(&in, &a.sw);
-        int const shared = !ps->profile && !parks && !(env != NULL && env[0] == '0');
         /* (grid rows; a park block of max_cols columns) */
-        int group = parks ? p->max_cols/C : 65535/C;
-        group = group < Z ? group : Z;
-        int const slot = grt_profile_begin(s, GRT_TAG_ZENITH_SW);
+        int const limit = parks ? p->max_cols/C : 65535/C;
+        int const chunks = (Z + grt_zenith_chunk(draws, ps->aer) - 1)/grt_zenith_chunk(draws, ps->aer);
+        int const shared = !ps->profile && !parks && chunks <= limit &&
+                           (joined ? env != NULL && env[0] == '1' : !(env != NULL && env[0] == '0'));
+        int const slot = grt_profile_begin(s, sw_tag);
         int krc = 0;
         if (shared)
         {
-            krc = grt_launch_sw_zeniths(s, &a.sw, &za);
+            int const group = limit/chunks < S ? limit/chunks : S;
+            sc.count = S;
+            for (sc.first = 0; sc.first < S && krc == 0; sc.first += group)
+            {
+                sc.count = S - sc.first < group ? S - sc.first : group;
+                krc = grt_launch_sw_zeniths(s, &a.sw, &za, draws, ps->aer);
+            }
         }
-        for (za.first = 0; !shared && za.first < Z && krc == 0; za.first += group)
+        else
         {
-            za.count = Z - za.first < group ? Z - za.first : group;
-            krc = grt_launch_sw(s, &in, &a.sw);
+            int const angles = limit < Z ? limit : Z;
+            int const group = limit/angles < S ? limit/angles : S;
+            for (sc.first = 0; sc.first < S && krc == 0; sc.first += group)
+            {
+                sc.count = S - sc.first < group ? S - sc.first : group;
+                for (za.first = 0; za.first < Z && krc == 0; za.first += angles)
+                {
+                    za.count = Z - za.first < angles ? Z - za.first : angles;
+                    krc = grt_launch_sw(s, &in, &a.sw);
+                }
+            }
         }
         grt_profile_end(s, slot);
         GRT_TRY(grt_dev_check(krc, "shortwave zenith kernel"));
     }
     else
     {
-        GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*(size_t)Z*(size_t)rows, NULL));
-        GRT_TRY(pass_optics(p, b, C, ps));
+        GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*(size_t)Z*(size_t)S*(size_t)rows, NULL));
         if (ps->profile)
         {
             GRT_TRY(level_rows(p, b));
         }
-        GrtSolverInstance const in = pass_instance(p, ps, NULL, NULL, NULL);
-        SolverArgs a;
-        GRT_TRY(solver_args(p, b, 1, C, ps, &in, NULL, &a));
-        for (int k = 0; k < Z; ++k)
+        size_t const tab = ps->clouds != NULL ? (size_t)C*3*(size_t)ps->clouds->num_bands*(size_t)(p->num_levels - 1) : 0;
+        for (int j = 0; j < S; ++j)
         {
-            a.sw.mu_dir = zr->mu_by_angle + (size_t)k*C;
-            int const slot = grt_profile_begin(s, GRT_TAG_ZENITH_SW);
-            int const krc = grt_launch_sw(s, &in, &a.sw);
-            grt_profile_end(s, slot);
-            GRT_TRY(grt_dev_check(krc, "shortwave kernel"));
-            GRT_TRY(grt_dev_check(grt_launch_integrate_rows(s, (double const *const *)(ps->profile ? b->level_rows_d : b->rows_d),
-                                                            C*rows, b->n, b->gas->grid.dw, block->d, rows, Z*rows, k*rows),
-                                  "spectral integration kernel"));
+            GrtCloudArgs cj;
+            GrtPass pj = *ps;
+            if (ps->clouds != NULL)
+            {
+                cj = *ps->clouds;
+                cj.liquid += (size_t)j*tab;
+                cj.ice += (size_t)j*tab;
+                pj.clouds = &cj;
+            }
+            GRT_TRY(pass_optics(p, b, C, &pj));
+            GrtSolverInstance const in = pass_instance(p, &pj, NULL, NULL, NULL);
+            SolverArgs a;
+            GRT_TRY(solver_args(p, b, 1, C, &pj, &in, NULL, &a));
+            for (int k = 0; k < Z; ++k)
+            {
+                a.sw.mu_dir = zr->mu_by_angle + (size_t)k*C;
+                int const slot = grt_profile_begin(s, sw_tag);
+                int const krc = grt_launch_sw(s, &in, &a.sw);
+                grt_profile_end(s, slot);
+                GRT_TRY(grt_dev_check(krc, "shortwave kernel"));
+                GRT_TRY(grt_dev_check(grt_launch_integrate_rows(s, (double const *const *)(ps->profile ? b->level_rows_d : b->rows_d),
+                                                                C*rows, b->n, b->gas->grid.dw, block->d, rows, Z*S*rows,
+                                                                (k*S + j)*rows),
+                                      "spectral integration kernel"));
+            }
         }
     }
-    int const mslot = grt_profile_begin(s, GRT_TAG_ZENITH_MEAN);
-    int const mrc = grt_launch_zenith_mean(s, block->d, C, Z, rows, nblocks, zr->mu, zr->weight, zr->per_angle, zr->six,
-                                           p->user_level, ps->out, ps->out_stride, out_offset);
+    int const mslot = grt_profile_begin(s, zr->sky ? GRT_TAG_SKY_ZENITH_MEAN : GRT_TAG_ZENITH_MEAN);
+    int const mrc = zr->sky ?
+        grt_launch_sky_zenith_mean(s, block->d, C, Z, S, rows, nblocks, zr->mu, zr->weight, zr->per_angle, zr->six, ps->sets,
+                                   ps->set, p->user_level, ps->out, ps->out_stride, out_offset) :
+        grt_launch_zenith_mean(s, block->d, C, Z, rows, nblocks, zr->mu, zr->weight, zr->per_angle, zr->six, p->user_level,
+                               ps->out, ps->out_stride, out_offset);
     grt_profile_end(s, mslot);
     GRT_TRY(grt_dev_check(mrc, "zenith mean kernel"));
     return GRTCODE_SUCCESS;

@@ -636,6 +636,46 @@ typedef struct GrtZeniths
 EXTERN int grt_pipeline_run_zeniths(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtZeniths_t const *zeniths,
                                     fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev);
 
+/* ---- every sky set under several sun angles per column, on one gas-optics pass --------------------------------------
+ * grt_pipeline_run_sky's sets -- N = grt_pipeline_sky_set_count(sky->sets) of them, packed as it packs them -- with the
+ * shortwave of every set solved under the Z = zeniths->num_zeniths sun angles of grt_pipeline_run_zeniths: a diurnal-mean
+ * cloud radiative effect, an aerosol forcing averaged over a day, an all-sky zenith sweep.  Each band's gas optics run
+ * once; the longwave of every set is solved once, as grt_pipeline_run_sky solves it; the cloud tables are staged once
+ * and the S draws of a column are the same under every angle.  GrtSky_t and GrtZeniths_t are the two entry points' own;
+ * columns->cos_zenith is not read; a cos_zenith <= 0 is a night sample: nothing is solved for it and its rows are +0.0
+ * in every set.  Two forms:
+ *   level_fluxes_dev == NULL (six rows): fluxes_dev [ncol][N][GRT_FLUXES_PER_COLUMN], the shortwave six of each set the
+ *                    mean over the angles (may be NULL when zenith_fluxes_dev is given: then neither the longwave nor
+ *                    the mean is formed);
+ *   level_fluxes_dev != NULL (profiles): grt_pipeline_run_sky's three layouts, the shortwave rows the mean over the
+ *                    angles, the heating rates and the six rows formed from the mean level fluxes.
+ * The per-angle outputs of GrtZeniths_t stay optional and gain the set dimension: zenith_fluxes_dev
+ * [ncol][N][Z][GRT_FLUXES_PER_BAND] in either form, zenith_level_fluxes_dev [ncol][N][Z][2][V] in the profile form.
+ * The mean is taken in a fixed order, for (column, set, angle): the blocks as the other entry points add them; in a
+ * cloud set the draws s = 0 .. S - 1 in order and one division by S; that is the angle's value, stored at the per-angle
+ * output; then the angles k = 0 .. Z - 1 by grt_pipeline_run_zeniths' rule (with weights sum w_k F_k, each product
+ * rounded before it is added; without, the sum and one division by Z, night samples included).  In the deterministic
+ * mode every angle's rows of every set are, bit for bit, grt_pipeline_run_sky's for that cos_zenith, the clean set's are
+ * grt_pipeline_run_zeniths', and the longwave rows are grt_pipeline_run_sky's.  A surface set with
+ * grt_pipeline_set_surface applies to every set and angle; a pipeline without a shortwave band runs the longwave sets
+ * and zeroes every shortwave output, the per-angle outputs included.
+ * The production form (keep_spectra = 0) solves a set's angles and draws in the zenith instances of the shortwave solver
+ * that hold the set's joins, grid row = (column, draw, angle), in as many launches as 65 535 grid rows and -- two-sweep
+ * forms -- the park block of max_columns columns need; the clean set takes grt_pipeline_run_zeniths' path (the
+ * shared-layer kernel for six rows in one sweep, GRT_TAG_ZENITH_SW), and GRT_ZENITH_SHARED=1 in the environment sends the
+ * other sets' one-sweep six-row form to the shared-layer kernel's instances with their joins too (the same bits; not the
+ * default until it is measured faster).  The joined sets' launches count under GRT_TAG_SKY_ZENITH_SW, the
+ * mean kernel under GRT_TAG_SKY_ZENITH_MEAN; per band [max_columns][Z][S][6 or 2 V][blocks] partial sums are allocated at
+ * the first call that needs more.  keep_spectra = 1: the literal loop -- per draw the set's optics, per angle the spectral
+ * solver and the row-wise trapezoid (night samples as in grt_pipeline_run_zeniths), then the same mean kernel.
+ * Not covered: cloud fields sampled on the device, the direct beam under several angles, spectral and per-bin outputs.
+ * GRTCODE_VALUE_ERR, with nothing launched and every output untouched, for everything grt_pipeline_run_sky refuses in
+ * `sky`, everything grt_pipeline_run_zeniths refuses in `zeniths`, and fluxes_dev, level_fluxes_dev and both per-angle
+ * outputs all NULL.  Asynchronous on the pipeline's lane. */
+EXTERN int grt_pipeline_run_sky_zeniths(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtSky_t const *sky,
+                                        GrtZeniths_t const *zeniths, fp_t *level_fluxes_dev, fp_t *heating_dev,
+                                        fp_t *fluxes_dev);
+
 /* ---- columns across the GPUs of one node ------------------------------------
  * One process per GPU; contiguous ceil-sized column blocks; one gather of the [columns][GRT_FLUXES_PER_COLUMN]
  * flux blocks to rank 0.  The reference fans out processes with -x/-X column ranges and merges per-shard files
@@ -715,7 +755,12 @@ enum
     GRT_TAG_ZENITH_SW = 19,
     GRT_TAG_ZENITH_MEAN = 20,
     /* 21 = the direct-beam kernel of grt_pipeline_run_sky_direct's materialised form (every set's, every subcolumn's) */
-    GRT_TAG_DIRECT_BEAM = 21
+    GRT_TAG_DIRECT_BEAM = 21,
+    /* 22 = the shortwave solver launches of grt_pipeline_run_sky_zeniths' sets with aerosol, clouds or both, every angle's
+       and draw's together (its clean set counts under GRT_TAG_ZENITH_SW, its longwave under grt_pipeline_run_sky's tags);
+       23 = its mean kernel, every set's */
+    GRT_TAG_SKY_ZENITH_SW = 22,
+    GRT_TAG_SKY_ZENITH_MEAN = 23
 };
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
