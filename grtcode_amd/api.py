@@ -29,7 +29,7 @@ GRT_CLOUD_PHASE, GRT_CLOUD_MODEL, GRT_CLOUD_FIELDS = 7, 8, 9   # ... of GrtCloud
 (TAG_GAS_LW, TAG_GAS_SW, TAG_SOLVER_LW, TAG_SOLVER_SW, TAG_CLEAR_OPTICS, TAG_FAR_LW, TAG_FAR_SW, TAG_ALLSKY_LW,
  TAG_ALLSKY_SW, TAG_BINS, TAG_SUBCOLUMN_MEAN, TAG_AEROSOL_LW, TAG_AEROSOL_SW, TAG_BAND_PROFILES, TAG_SURFACE,
  TAG_CLOUD_SAMPLER, TAG_SKY_LW, TAG_SKY_SW, TAG_ZENITH_SW, TAG_ZENITH_MEAN, TAG_DIRECT_BEAM, TAG_SKY_ZENITH_SW,
- TAG_SKY_ZENITH_MEAN) = range(1, 24)
+ TAG_SKY_ZENITH_MEAN, TAG_SURFACE_JACOBIAN) = range(1, 25)
 TAG_FAR_OFFSET = TAG_FAR_LW - TAG_GAS_LW    # from a line kernel's tag to its far-field gather's
 CLOUD_SAMPLER_TAG = TAG_CLOUD_SAMPLER
 GRT_MAX_SUBCOLUMNS = 64             # grt_pipeline_run_subcolumns: subcolumns per column, 1 .. this
@@ -40,6 +40,7 @@ GRT_SKY_CLEAN, GRT_SKY_AEROSOL, GRT_SKY_CLOUD, GRT_SKY_CLOUD_AEROSOL = 1, 2, 4, 
 GRT_SKY_ALL = GRT_SKY_CLEAN | GRT_SKY_AEROSOL | GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL
 GRT_SKY_MAX_SETS = 4
 GRT_DIRECT_ROWS_PER_SET = 3         # grt_pipeline_run_sky_direct: the direct beam at TOA, surface, user level
+GRT_JACOBIAN_ROWS_PER_SET = 3       # grt_pipeline_run_sky_jacobian: dF_up/dT_surf at TOA, surface, user level
 RETURN_CODES = ["GRTCODE_SUCCESS", "GRTCODE_INVALID_ERR", "GRTCODE_DIVBYZERO_ERR", "GRTCODE_OVERFLOW_ERR",
                 "GRTCODE_UNDERFLOW_ERR", "GRTCODE_SENTINEL_ERR", "GRTCODE_NULL_ERR", "GRTCODE_NON_NULL_ERR",
                 "GRTCODE_RANGE_ERR", "GRTCODE_VALUE_ERR", "GRTCODE_COMPILER_ERR", "GRTCODE_IO_ERR",
@@ -184,6 +185,10 @@ class GrtDirectBeam(C.Structure):
     _fields_ = [("direct_fluxes_dev", C.c_void_p), ("direct_level_fluxes_dev", C.c_void_p)]
 
 
+class GrtSurfaceJacobian(C.Structure):
+    _fields_ = [("jacobian_fluxes_dev", C.c_void_p), ("jacobian_level_fluxes_dev", C.c_void_p)]
+
+
 class GrtZeniths(C.Structure):
     _fields_ = [("num_zeniths", C.c_int), ("cos_zenith", c_double_p), ("weight", c_double_p),
                 ("zenith_fluxes_dev", C.c_void_p), ("zenith_level_fluxes_dev", C.c_void_p)]
@@ -210,7 +215,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_zeniths grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_zeniths grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -270,6 +275,9 @@ def load_library(path=None):
                                          C.c_void_p]
     lib.grt_pipeline_run_sky_direct.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky),
                                                 C.POINTER(GrtDirectBeam), C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "grt_pipeline_run_sky_jacobian"):    # (GRT_LIB_PATH may name an older library: a timing yardstick)
+        lib.grt_pipeline_run_sky_jacobian.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky),
+                                                      C.POINTER(GrtSurfaceJacobian), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.grt_pipeline_sky_set_count.argtypes = [C.c_uint]
     if hasattr(lib, "grt_pipeline_run_zeniths"):    # (GRT_LIB_PATH may name an older library: a timing yardstick)
         lib.grt_pipeline_run_zeniths.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtZeniths), C.c_void_p,
@@ -1011,6 +1019,31 @@ class Pipeline:
         direct_levels=[ncol][nsets][V], the direct beam at every level, top first)."""
         return dict(direct=self.sky_direct_fluxes(ncol, nsets, profiles=True),
                     direct_levels=self.buffers["sky_profiles.direct_levels"].to_host((ncol, nsets, self.num_levels)))
+
+    def run_sky_jacobian(self, gcols, gsky, profiles=False):
+        """grt_pipeline_run_sky_jacobian into this object's device buffers: run_sky's outputs where run_sky puts them
+        (sky_fluxes() / sky_profiles() read them) and the derivative of every set's upward longwave flux with respect to
+        the surface temperature: its three rows (sky_jacobian_fluxes() reads them) and, profiles=True, every level
+        (sky_jacobian_profiles() reads both)."""
+        ptrs, nsets = self._sky_ptrs(gsky, profiles)
+        V, n = self.num_levels, self.max_columns
+        name = "sky_profiles" if profiles else "sky"
+        gjac = GrtSurfaceJacobian(self._buffer(name + ".jacobian", 8 * n * nsets * GRT_JACOBIAN_ROWS_PER_SET).ptr,
+                                  self._buffer(name + ".jacobian_levels", 8 * n * nsets * V).ptr if profiles else None)
+        check(self.lib.grt_pipeline_run_sky_jacobian(self.p, C.byref(gcols), C.byref(gsky), C.byref(gjac), *ptrs))
+
+    def sky_jacobian_fluxes(self, ncol, nsets, profiles=False):
+        """The last run_sky_jacobian (of that form) of nsets sets: [ncol][nsets][3], dF_up/dT_surf of each set's longwave
+        at the top of the atmosphere, the surface and the user level (W m-2 K-1; +0.0 without a user level)."""
+        self.sync()
+        return self.buffers[("sky_profiles" if profiles else "sky") + ".jacobian"].to_host(
+            (ncol, nsets, GRT_JACOBIAN_ROWS_PER_SET))
+
+    def sky_jacobian_profiles(self, ncol, nsets):
+        """The last run_sky_jacobian(profiles=True) of nsets sets: dict(jacobian=[ncol][nsets][3], as
+        sky_jacobian_fluxes(), and jacobian_levels=[ncol][nsets][V], the derivative at every level, top first)."""
+        return dict(jacobian=self.sky_jacobian_fluxes(ncol, nsets, profiles=True),
+                    jacobian_levels=self.buffers["sky_profiles.jacobian_levels"].to_host((ncol, nsets, self.num_levels)))
 
     def sky_fluxes(self, ncol, nsets):
         """The last six-row run_sky of nsets sets: [ncol][nsets][12], the sets in bit order, each in grt_pipeline_run's

@@ -499,6 +499,29 @@ int grt_launch_sw_direct_beam(void *stream, GrtSwArgs const *a, double *direct);
 /* rows [n][3] (TOA, surface, user level; +0.0 with user_level < 0) from levels [n][V] */
 int grt_launch_direct_rows(void *stream, int n, int num_levels, int user_level, double const *levels, double *rows);
 
+/* Surface-temperature Jacobian form of the longwave's fused six-row and profile forms (jacobian joined, with any of the
+   cloud and aerosol joins or none; grt_pipeline_run_sky_jacobian): the instance's arguments, sweeps and partial sums, and
+   beside them dF_up/dT_surf of the upward sweep at the same levels.  The surface enters each stream once
+   (longwave.c:202), D_s = emis dB/dT(T_surf, w) there, every layer above multiplies D_s by the stream's extinction, and
+   a level's value is ((0 + c2[0] D_0) + c2[1] D_1) + c2[2] D_2) + c2[3] D_3; dB/dT = B (x/T) e/(e - 1), x = c2 w/T, e =
+   exp(x), and 0 where planck() clamps x.  It leaves as the direct beam of the shortwave does (GrtDirectArgs): three rows
+   per slot (TOA, surface, user level) at partials[(slot 3 + k) nblocks + block] in the six-row form, V rows per slot at
+   partials[(slot V + level) nblocks + block] in the profile form, through the same wave and workgroup sums -- rows 0, L
+   and user_level of the profile form are, bit for bit, the six-row form's three.  The profile form's dynamic LDS is 3 V x
+   2 doubles per workgroup.  Longwave only; reduced as the instance's own rows are. */
+typedef struct GrtJacobianArgs
+{
+    double *partials;
+} GrtJacobianArgs;
+static inline int grt_jacobian_args_ok(GrtJacobianArgs const *d)
+{
+    return d != NULL && d->partials != NULL;
+}
+/* Materialised form: the same Jacobian from the tau, omega a pass has left on the grid (GrtLwArgs: tau, omega,
+   optics_stride, t_surf, emis), one thread per column and grid point walking the layers upward from the surface with
+   the solver's own extinctions; jacobian [ncol][V][nw], levels top first, W m-2 K-1 per cm-1. */
+int grt_launch_lw_surface_jacobian(void *stream, GrtLwArgs const *a, double *jacobian);
+
 /* Banded profile form of the two profile forms (GRT_OUT_LEVEL_BINS, clear sky or clouds joined;
    grt_pipeline_run_band_profiles): the profile form's arguments, sweeps and park block, but every level's
    flux leaves once per wavenumber bin that has a point in the workgroup's 128 grid points.  A point weights a level's
@@ -540,7 +563,7 @@ typedef enum GrtSolverOutput
    stays per column whatever the subcolumn); `bins` goes with GRT_OUT_LEVEL_BINS and with nothing else; `zeniths` (the
    shortwave's GRT_OUT_ROWS and GRT_OUT_LEVELS) goes alone or with aerosols, subcolumns or both, never with `clouds`; `direct` (the shortwave's GRT_OUT_ROWS and
    GRT_OUT_LEVELS) goes with any join of clouds and aerosols or none, and selects instances of its own: the instance
-   without it is the one it was.  The kind of instance follows from which pointers are set, and a kernel takes the structs that are
+   without it is the one it was; `jacobian` is the same for the longwave's GRT_OUT_ROWS and GRT_OUT_LEVELS.  The kind of instance follows from which pointers are set, and a kernel takes the structs that are
    set as arguments after its band's own.  The next joined object is a pointer here, a line in grt_solver_instance_ok
    and a case in each band's list of instances. */
 typedef struct GrtSolverInstance
@@ -552,6 +575,7 @@ typedef struct GrtSolverInstance
     GrtBandArgs const *bins;
     GrtZenithArgs const *zeniths;
     GrtDirectArgs const *direct;
+    GrtJacobianArgs const *jacobian;
 } GrtSolverInstance;
 typedef enum GrtSolverJoin
 {
@@ -593,12 +617,12 @@ static inline uint64_t grt_solver_grid_rows(GrtSolverInstance const *in, int nco
     return (uint64_t)ncol*(uint64_t)(in->subcolumns != NULL ? in->subcolumns->count : 1)*
            (uint64_t)(in->zeniths != NULL ? in->zeniths->count : 1);
 }
-/* its dynamic LDS: 2 V doubles per wave of its workgroup where every level leaves (3 V with the direct beam), that per bin
-   of a block with bins */
+/* its dynamic LDS: 2 V doubles per wave of its workgroup where every level leaves (3 V with the direct beam or the
+   surface-temperature Jacobian), that per bin of a block with bins */
 #define GRT_SOLVER_BLOCK 128
 static inline size_t grt_solver_lds(GrtSolverInstance const *in, int num_levels)
 {
-    size_t const levels = sizeof(double)*(in->direct != NULL ? 3 : 2)*(size_t)num_levels*(GRT_SOLVER_BLOCK/64);
+    size_t const levels = sizeof(double)*(in->direct != NULL || in->jacobian != NULL ? 3 : 2)*(size_t)num_levels*(GRT_SOLVER_BLOCK/64);
     return !grt_out_levels(in->out) ? 0 : (in->bins != NULL ? levels*(size_t)in->bins->block_bins : levels);
 }
 /* whether the shortwave instance takes the two sweeps and needs `park` */
@@ -725,7 +749,11 @@ inline bool grt_solver_instance_ok(GrtSolverInstance const &in, Args const &a)
     // (the direct beam leaves the six-row and level forms, under one sun per column; the longwave launcher has no such case)
     bool const direct_ok = in.direct == nullptr || (in.zeniths == nullptr && grt_direct_args_ok(in.direct) &&
                                                     (in.out == GRT_OUT_ROWS || in.out == GRT_OUT_LEVELS));
-    return zeniths_ok && direct_ok && a.ncol >= 1 && a.nw >= 2 && a.num_levels >= 2 &&
+    // (the surface-temperature Jacobian leaves the same two forms; the shortwave launcher has no such case)
+    bool const jacobian_ok = in.jacobian == nullptr || (in.zeniths == nullptr && in.direct == nullptr &&
+                                                        grt_jacobian_args_ok(in.jacobian) &&
+                                                        (in.out == GRT_OUT_ROWS || in.out == GRT_OUT_LEVELS));
+    return zeniths_ok && direct_ok && jacobian_ok && a.ncol >= 1 && a.nw >= 2 && a.num_levels >= 2 &&
            cloud_forms <= 1 && joined <= (fused ? 2 : 0) && (in.bins != nullptr) == (in.out == GRT_OUT_LEVEL_BINS) &&
            (in.clouds == nullptr || grt_cloud_args_ok(in.clouds)) &&
            (in.aerosols == nullptr || grt_aerosol_args_ok(in.aerosols)) &&

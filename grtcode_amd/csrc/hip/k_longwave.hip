@@ -17,8 +17,10 @@
 // grt_launch_lw): what leaves it is its OUT -- spectral fluxes (GRT_OUT_CHAINS), or, fused, the partial sums of the six
 // rows, of the six rows that are also stored at every point, of every level, or of every level per wavenumber bin -- and
 // what joins gas and Rayleigh is the types of its pack: nothing, GrtCloudArgs, GrtAerosolArgs or GrtSubcolumnArgs, a
-// GrtAerosolArgs behind either form of the clouds where both join, and a GrtBandArgs last where OUT is per bin.  The
-// fused six-row clear-sky instance is the production pipeline's.
+// GrtAerosolArgs behind either form of the clouds where both join, and a GrtBandArgs last where OUT is per bin; a
+// GrtJacobianArgs last (six rows or every level, with any of the cloud and aerosol joins) makes the instance that also
+// leaves dF_up/dT_surf of its upward sweep (LevelSink: DIRECT, the third row group).  The fused six-row clear-sky
+// instance is the production pipeline's.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -46,6 +48,24 @@ __device__ __forceinline__ double planck(double T, double w)
     }
     e = exp(e);
     return (c1*w*w*w)/(e - 1.);
+}
+
+// planck(T, w) and with it dB/dT = B (x/T) e/(e - 1), x = c2 w/T, e = exp(x), from planck()'s own exponential (the same
+// expressions: the same B); 0 where planck() clamps x
+__device__ __forceinline__ double planck_dT(double T, double w, double &dbdt)
+{
+    double const c1 = 1.1910429526245744e-8;
+    double const c2 = 1.4387773538277202;
+    double x = c2*w/T;
+    bool const clamped = x > kMaxExpArg;
+    if (clamped)
+    {
+        x = kMaxExpArg;
+    }
+    double const e = exp(x);
+    double const b = (c1*w*w*w)/(e - 1.);
+    dbdt = clamped ? 0. : b*(x/T)*(e/(e - 1.));
+    return b;
 }
 
 // longwave.c:100-118 with the two Planck values supplied by the caller
@@ -84,6 +104,36 @@ __device__ __forceinline__ double stream_step(double (&I)[4], double val, Ext ex
     return f;
 }
 
+// sum_s c2[s] D_s, in stream_step's order: dF_up/dT_surf from the four streams' derivatives
+__device__ __forceinline__ double jacobian_flux(double const (&D)[4])
+{
+    double f = 0.;
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+    {
+        f += kC2[s]*D[s];
+    }
+    return f;
+}
+
+// stream_step on the way up with the streams' derivatives with respect to the surface temperature beside them: the layer
+// emits nothing that depends on it, so D_s <- D_s ext_s with the step's own extinctions; jac: sum_s c2[s] D_s
+__device__ __forceinline__ double stream_step_jacobian(double (&I)[4], double (&D)[4], double val, double t, double &jac)
+{
+    double f = 0.;
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+    {
+        double const e = extinction(s, t);
+        double const p = (1. - e)*val;                                   // longwave.c:193
+        I[s] = p + I[s]*e;
+        f += kC2[s]*I[s];                                                // longwave.c:195
+        D[s] = D[s]*e;
+    }
+    jac = jacobian_flux(D);
+    return f;
+}
+
 // The surface (longwave.c:202): emission bs at emissivity emis, the rest of each stream reflected; returns the flux
 __device__ __forceinline__ double surface_step(double (&I)[4], double emis, double bs)
 {
@@ -105,12 +155,16 @@ __device__ __forceinline__ double surface_step(double (&I)[4], double emis, doub
 // (LevelSink).
 // Joins (fused forms): clouds (a GrtCloudArgs, or the draws of a GrtSubcolumnArgs), the aerosol object or both join per
 // layer (LayerOptics).  Only layer_tau changes: what leaves the kernel is OUT's.
+// A GrtJacobianArgs in the pack (GRT_OUT_ROWS and GRT_OUT_LEVELS): the upward sweep carries D[4] beside I[4], seeded at
+// the surface with emis dB/dT(T_surf, w), and every level's sum_s c2[s] D_s leaves through the sink's third row group.
 template <GrtSolverOutput OUT, typename... Joins>
 __global__ __launch_bounds__(kSolverBlock) void lw_kernel(GrtLwArgs a, Joins... joins)
 {
     uint64_t const i = (uint64_t)blockIdx.x*kSolverBlock + threadIdx.x;
     constexpr bool FUSED = grt_out_fused(OUT), PROFILE = grt_out_levels(OUT), SPECTRAL = OUT == GRT_OUT_ROWS_POINTS;
     static_assert(has<GrtBandArgs, Joins...> == (OUT == GRT_OUT_LEVEL_BINS), "bins go with GRT_OUT_LEVEL_BINS alone");
+    constexpr bool JACOBIAN = has<GrtJacobianArgs, Joins...>;
+    static_assert(!JACOBIAN || OUT == GRT_OUT_ROWS || OUT == GRT_OUT_LEVELS, "the Jacobian leaves the six-row and level forms");
     SolverRow const row = solver_row(a.ncol, joins...);
     int const col = row.col;
     bool const live = i < a.nw;
@@ -127,7 +181,8 @@ __global__ __launch_bounds__(kSolverBlock) void lw_kernel(GrtLwArgs a, Joins... 
     double const *tl = a.t_layers + (uint64_t)col*L;
     double const *tv = a.t_levels + (uint64_t)col*V;
     double const emis = a.emis[(uint64_t)col*a.emis_stride + ii];
-    LevelSink<FUSED, PROFILE, SPECTRAL, has<GrtBandArgs, Joins...>> sink(a, row.slot, i, live, pick<GrtBandArgs>(joins...));
+    LevelSink<FUSED, PROFILE, SPECTRAL, has<GrtBandArgs, Joins...>, JACOBIAN> sink(
+        a, row.slot, i, live, pick<GrtBandArgs>(joins...), GrtDirectArgs{pick<GrtJacobianArgs>(joins...).partials});
     LayerOptics<FUSED, has_clouds<Joins...>, has<GrtAerosolArgs, Joins...>> const optics(
         a, pick_clouds(joins...), col, row.tab, ii, pick<GrtAerosolArgs>(joins...));                    // (fused forms)
 
@@ -152,14 +207,71 @@ __global__ __launch_bounds__(kSolverBlock) void lw_kernel(GrtLwArgs a, Joins... 
         double const val = effective_planck(planck(tl[j], w), planck(tv[j + 1], w), t);
         sink.put(j + 1, true, stream_step(I, val, [&](int s) { return extinction(s, t); }));
     }
-    sink.put(L, false, surface_step(I, emis, planck(a.t_surf[col], w)));
-    for (int j = L - 1; j >= 0; --j)
+    if constexpr (JACOBIAN)
     {
-        double const t = layer_tau(j);
-        double const val = effective_planck(planck(tl[j], w), planck(tv[j], w), t);
-        sink.put(j, false, stream_step(I, val, [&](int s) { return extinction(s, t); }));
+        double dbdt;
+        double const bs = planck_dT(a.t_surf[col], w, dbdt);
+        sink.put(L, false, surface_step(I, emis, bs));
+        double D[4] = {emis*dbdt, emis*dbdt, emis*dbdt, emis*dbdt};
+        sink.put_direct(L, jacobian_flux(D));
+        for (int j = L - 1; j >= 0; --j)
+        {
+            double const t = layer_tau(j);
+            double const val = effective_planck(planck(tl[j], w), planck(tv[j], w), t);
+            double jac;
+            sink.put(j, false, stream_step_jacobian(I, D, val, t, jac));
+            sink.put_direct(j, jac);
+        }
+    }
+    else
+    {
+        sink.put(L, false, surface_step(I, emis, planck(a.t_surf[col], w)));
+        for (int j = L - 1; j >= 0; --j)
+        {
+            double const t = layer_tau(j);
+            double const val = effective_planck(planck(tl[j], w), planck(tv[j], w), t);
+            sink.put(j, false, stream_step(I, val, [&](int s) { return extinction(s, t); }));
+        }
     }
     sink.finish(a);
+}
+
+// ---- the surface-temperature Jacobian of the materialised form (grt_launch_lw_surface_jacobian) ----
+// One thread per (wavenumber, column) walks the layers of the tau, omega a pass left on the grid upward from the surface:
+// the seed emis dB/dT(T_surf, w) in each stream, then the solver's own extinctions of tau (1 - omega), layer by layer.
+constexpr int kJacobianBlock = 128;
+
+__global__ __launch_bounds__(kJacobianBlock) void lw_surface_jacobian_kernel(GrtLwArgs a, double *jacobian)
+{
+    uint64_t const i = (uint64_t)blockIdx.x*kJacobianBlock + threadIdx.x;
+    int const col = blockIdx.y;
+    if (i >= a.nw)
+    {
+        return;
+    }
+    int const V = a.num_levels;
+    int const L = V - 1;
+    uint64_t const nw = a.nw;
+    double const w = a.w0 + i*a.dw;                                      // longwave.c:246
+    double const *tau = a.tau + (uint64_t)col*a.optics_stride + i;
+    double const *omega = a.omega ? a.omega + (uint64_t)col*a.optics_stride + i : nullptr;
+    double const emis = a.emis[(uint64_t)col*a.emis_stride + i];
+    double *out = jacobian + (uint64_t)col*(uint64_t)V*nw + i;
+    double dbdt;
+    planck_dT(a.t_surf[col], w, dbdt);
+    double D[4] = {emis*dbdt, emis*dbdt, emis*dbdt, emis*dbdt};
+    out[(uint64_t)L*nw] = jacobian_flux(D);
+    for (int j = L - 1; j >= 0; --j)
+    {
+        uint64_t const o = (uint64_t)j*nw;
+        double const t = omega ? tau[o]*(1. - omega[o]) : tau[o]*(1. - 0.);    // longwave.c:252
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+        {
+            D[s] = D[s]*extinction(s, t);
+        }
+        out[o] = jacobian_flux(D);
+    }
 }
 
 // ---- spectral form of few columns: the layers' terms first, by one thread per (layer, wavenumber) ----
@@ -295,7 +407,34 @@ extern "C" int grt_launch_lw(void *stream, GrtSolverInstance const *in, GrtLwArg
         return (int)hipErrorInvalidValue;
     }
     hipStream_t const s = (hipStream_t)stream;
-    // every instance of lw_kernel there is
+    // every instance of lw_kernel that also leaves the surface-temperature Jacobian (grt_pipeline_run_sky_jacobian's sets
+    // and forms) ...
+    if (in->jacobian != nullptr)
+    {
+        GrtJacobianArgs const &d = *in->jacobian;
+        switch (GRT_INSTANCE(in->out, grt_solver_join(in)))
+        {
+        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_NONE): return launch<GRT_OUT_ROWS>(s, *in, *a, d);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_NONE): return launch<GRT_OUT_LEVELS>(s, *in, *a, d);
+        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->clouds, d);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, d);
+        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->aerosols, d);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->aerosols, d);
+        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns, d);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, d);
+        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_CLOUDS_AEROSOLS):
+            return launch<GRT_OUT_ROWS>(s, *in, *a, *in->clouds, *in->aerosols, d);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS_AEROSOLS):
+            return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, *in->aerosols, d);
+        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
+            return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns, *in->aerosols, d);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
+            return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->aerosols, d);
+        default:
+            return (int)hipErrorInvalidValue;
+        }
+    }
+    // ... and every other instance of lw_kernel there is
     switch (GRT_INSTANCE(in->out, grt_solver_join(in)))
     {
     case GRT_INSTANCE(GRT_OUT_LAYERS, GRT_JOIN_NONE):
@@ -329,4 +468,16 @@ extern "C" int grt_launch_lw(void *stream, GrtSolverInstance const *in, GrtLwArg
     default:
         return (int)hipErrorInvalidValue;
     }
+}
+
+extern "C" int grt_launch_lw_surface_jacobian(void *stream, GrtLwArgs const *a, double *jacobian)
+{
+    if (a == nullptr || jacobian == nullptr || a->ncol < 1 || a->ncol > 65535 || a->nw < 2 || a->num_levels < 2 ||
+        a->tau == nullptr || a->t_surf == nullptr || a->emis == nullptr)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(lw_surface_jacobian_kernel, dim3((unsigned)((a->nw + kJacobianBlock - 1)/kJacobianBlock), a->ncol, 1),
+                       dim3(kJacobianBlock), 0, (hipStream_t)stream, *a, jacobian);
+    return (int)hipGetLastError();
 }

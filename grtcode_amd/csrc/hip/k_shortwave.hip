@@ -777,7 +777,8 @@ int launch(hipStream_t s, GrtSolverInstance const &in, GrtSwArgs const &a, Joins
 extern "C" int grt_launch_sw(void *stream, GrtSolverInstance const *in, GrtSwArgs const *a)
 {
     uint64_t const cells = (uint64_t)(a->num_levels - 1)*a->nw;
-    if (!grt_solver_instance_ok(*in, *a) || (grt_sw_parks(in, a) && a->park == nullptr) ||
+    if (!grt_solver_instance_ok(*in, *a) || in->jacobian != nullptr ||      // (the surface-temperature Jacobian is the longwave's)
+        (grt_sw_parks(in, a) && a->park == nullptr) ||
         (in->out == GRT_OUT_LAYERS && (a->layer_props == nullptr || cells > 0xffffffffull*kPropsBlock ||
                                        a->omega == nullptr || a->g == nullptr)))
     {
@@ -887,7 +888,7 @@ extern "C" int grt_zenith_chunk(GrtSubcolumnArgs const *sc, GrtAerosolArgs const
 extern "C" int grt_launch_sw_zeniths(void *stream, GrtSwArgs const *a, GrtZenithArgs const *z, GrtSubcolumnArgs const *sc,
                                      GrtAerosolArgs const *ae)
 {
-    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (!grt_solver_instance_ok(in, *a) || z == nullptr || z->mu == nullptr || z->zeniths < 1 || !grt_sw_one_sweep(a) ||
         (sc != nullptr && !grt_subcolumn_args_ok(sc)) || (ae != nullptr && !grt_aerosol_args_ok(ae)))
     {

@@ -512,6 +512,8 @@ struct LayerOptics
 // DIRECT (shortwave, fused six-row and profile forms; GrtDirectArgs): the direct beam at a level leaves too, by
 // put_direct() -- three more rows in registers (TOA, surface, user) that ride with the six through block_partials, or V
 // more rows of wave sums behind the 2 V in dynamic LDS (3 V x kSolverBlock/64 doubles) --, to the join's own partial sums.
+// The longwave's surface-temperature Jacobian (GrtJacobianArgs) is the same third row group: lw_kernel hands every level's
+// dF_up/dT_surf to put_direct() and its partial sums' array in a GrtDirectArgs.
 template <bool ON> struct DirectRows {};
 template <> struct DirectRows<true> { double out[3]; double *partials; };
 

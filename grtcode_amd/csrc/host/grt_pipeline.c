@@ -33,6 +33,8 @@
  * one gas-optics launch per band: the passes of the entry points above, and the pass that joins aerosol and clouds.
  * grt_pipeline_run_sky_direct is grt_pipeline_run_sky with the direct beam of every set's shortwave beside its rows: taken
  * out of the same solver launches (instances that leave it too), or -- materialised form -- formed from each set's optics.
+ * grt_pipeline_run_sky_jacobian is its longwave counterpart, by the same route: the derivative of every set's upward
+ * longwave flux with respect to the surface temperature beside the set's rows.
  * grt_pipeline_run_sky_zeniths is grt_pipeline_run_sky with the shortwave of every set solved under several sun angles per
  * column, as grt_pipeline_run_zeniths solves the clean set's: one gas-optics launch per band, one set of cloud draws.
  * grt_pipeline_run_band_profiles runs the profile form of the clear-sky pass and, with clouds, of the all-sky pass with
@@ -1030,22 +1032,33 @@ static int sky_join(GrtPipeline_t const *p, GrtColumns_t const *cols, GrtSky_t c
     return GRTCODE_SUCCESS;
 }
 
-/* grt_pipeline_run_sky and, with_direct, grt_pipeline_run_sky_direct: the same request, the direct outputs attached */
-static int run_sky(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky, int with_direct,
-                   GrtDirectBeam_t const *direct, fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev)
+/* The third row group a sky run may carry beside its rows, the outputs attached: the shortwave's direct beam
+   (grt_pipeline_run_sky_direct: band 1) or the longwave's surface-temperature Jacobian (grt_pipeline_run_sky_jacobian:
+   band 0); three: [ncol][sets][3], required; levels: [ncol][sets][V], profile form only, may be NULL */
+typedef struct SkyThird
+{
+    int band;
+    char const *what, *arg, *three_name, *levels_name;
+    fp_t *three, *levels;
+    int missing;                   /* the caller's struct is NULL */
+} SkyThird;
+
+/* grt_pipeline_run_sky and, with a third row group, grt_pipeline_run_sky_direct and _jacobian: the same request */
+static int run_sky(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky, SkyThird const *third,
+                   fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev)
 {
     GRT_REQUIRE_PTR(p);
     GRT_REQUIRE_PTR(cols);
-    if (with_direct)
+    if (third != NULL)
     {
-        if (direct == NULL || direct->direct_fluxes_dev == NULL)
+        if (third->missing || third->three == NULL)
         {
-            GRT_FAIL(GRTCODE_VALUE_ERR, "%s is NULL: the direct-beam rows [ncol][sets][%d] are the output.",
-                     direct == NULL ? "direct (GrtDirectBeam_t)" : "direct_fluxes_dev", GRT_DIRECT_ROWS_PER_SET);
+            GRT_FAIL(GRTCODE_VALUE_ERR, "%s is NULL: the %s rows [ncol][sets][%d] are the output.",
+                     third->missing ? third->arg : third->three_name, third->what, GRT_DIRECT_ROWS_PER_SET);
         }
-        if (level_fluxes_dev == NULL && direct->direct_level_fluxes_dev != NULL)
+        if (level_fluxes_dev == NULL && third->levels != NULL)
         {
-            GRT_FAIL(GRTCODE_VALUE_ERR, "direct_level_fluxes_dev is given in the six-row form (level_fluxes_dev is NULL).%s", "");
+            GRT_FAIL(GRTCODE_VALUE_ERR, "%s is given in the six-row form (level_fluxes_dev is NULL).", third->levels_name);
         }
     }
     int nsets;
@@ -1055,40 +1068,49 @@ static int run_sky(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *s
     GrtAerosols_t a;
     GrtJoin join;
     GRT_TRY(sky_join(p, cols, sky, &a, &join));
-    GrtBand *sw = &p->band[1];
+    GrtBand *tb = third != NULL ? &p->band[third->band] : NULL;
     int const V = p->num_levels;
-    if (with_direct && sw->gas != NULL)
+    double *third_rows = NULL;
+    if (third != NULL && tb->gas != NULL)
     {
-        /* the passes' direct rows: the caller's three per set, or -- profile form -- V levels per set, the caller's or the
+        /* the passes' third rows: the caller's three per set, or -- profile form -- V levels per set, the caller's or the
            pipeline's own, and the three rows from them afterwards */
-        rows.direct = rows.profile ? direct->direct_level_fluxes_dev : direct->direct_fluxes_dev;
-        if (rows.direct == NULL)
+        third_rows = rows.profile ? third->levels : third->three;
+        if (third_rows == NULL)
         {
             GRT_TRY(check_lane(p));
-            GrtScratch *own = &sw->scratch[GRT_SCRATCH_DIRECT_LEVELS];
+            GrtScratch *own = &tb->scratch[GRT_SCRATCH_DIRECT_LEVELS];
             GRT_TRY(grt_scratch_need(p, own, (size_t)p->max_cols*GRT_SKY_MAX_SETS*(size_t)V, NULL));
-            rows.direct = own->d;
+            third_rows = own->d;
+        }
+        if (third->band == 1)
+        {
+            rows.direct = third_rows;
+        }
+        else
+        {
+            rows.jacobian = third_rows;
         }
     }
     GRT_TRY(pipeline_run(p, cols, &join, &rows));
     GRT_TRY(finish_profiles(p, cols->ncol, &rows, heating_dev, fluxes_dev));
-    if (with_direct)
+    if (third != NULL)
     {
         void *s = grt_dev_stream(p->device);
         size_t const slots = (size_t)cols->ncol*(size_t)nsets;
-        if (sw->gas == NULL)
+        if (tb->gas == NULL)
         {
-            /* no shortwave band: zeros, as the band's rows are */
-            GRT_TRY(grt_dev_zero(p->device, direct->direct_fluxes_dev, sizeof(double)*slots*GRT_DIRECT_ROWS_PER_SET, s));
-            if (direct->direct_level_fluxes_dev != NULL)
+            /* the band is not there: zeros, as the band's rows are */
+            GRT_TRY(grt_dev_zero(p->device, third->three, sizeof(double)*slots*GRT_DIRECT_ROWS_PER_SET, s));
+            if (third->levels != NULL)
             {
-                GRT_TRY(grt_dev_zero(p->device, direct->direct_level_fluxes_dev, sizeof(double)*slots*(size_t)V, s));
+                GRT_TRY(grt_dev_zero(p->device, third->levels, sizeof(double)*slots*(size_t)V, s));
             }
         }
         else if (rows.profile)
         {
-            GRT_TRY(grt_dev_check(grt_launch_direct_rows(s, (int)slots, V, p->user_level, rows.direct,
-                                                         direct->direct_fluxes_dev), "direct-beam row kernel"));
+            GRT_TRY(grt_dev_check(grt_launch_direct_rows(s, (int)slots, V, p->user_level, third_rows, third->three),
+                                  "row pick kernel"));
         }
     }
     return GRTCODE_SUCCESS;
@@ -1098,7 +1120,7 @@ static int run_sky(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *s
 EXTERN int grt_pipeline_run_sky(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky, fp_t *level_fluxes_dev,
                                 fp_t *heating_dev, fp_t *fluxes_dev)
 {
-    GRT_TRY(run_sky(p, cols, sky, 0, NULL, level_fluxes_dev, heating_dev, fluxes_dev));
+    GRT_TRY(run_sky(p, cols, sky, NULL, level_fluxes_dev, heating_dev, fluxes_dev));
     return GRTCODE_SUCCESS;
 }
 
@@ -1107,7 +1129,22 @@ EXTERN int grt_pipeline_run_sky_direct(GrtPipeline_t *p, GrtColumns_t const *col
                                        GrtDirectBeam_t const *direct, fp_t *level_fluxes_dev, fp_t *heating_dev,
                                        fp_t *fluxes_dev)
 {
-    GRT_TRY(run_sky(p, cols, sky, 1, direct, level_fluxes_dev, heating_dev, fluxes_dev));
+    SkyThird const third = {1, "direct-beam", "direct (GrtDirectBeam_t)", "direct_fluxes_dev", "direct_level_fluxes_dev",
+                            direct != NULL ? direct->direct_fluxes_dev : NULL,
+                            direct != NULL ? direct->direct_level_fluxes_dev : NULL, direct == NULL};
+    GRT_TRY(run_sky(p, cols, sky, &third, level_fluxes_dev, heating_dev, fluxes_dev));
+    return GRTCODE_SUCCESS;
+}
+
+/* grt_ext.h: grt_pipeline_run_sky, and the surface-temperature Jacobian of every set's upward longwave */
+EXTERN int grt_pipeline_run_sky_jacobian(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky,
+                                         GrtSurfaceJacobian_t const *jacobian, fp_t *level_fluxes_dev, fp_t *heating_dev,
+                                         fp_t *fluxes_dev)
+{
+    SkyThird const third = {0, "surface Jacobian", "jacobian (GrtSurfaceJacobian_t)", "jacobian_fluxes_dev",
+                            "jacobian_level_fluxes_dev", jacobian != NULL ? jacobian->jacobian_fluxes_dev : NULL,
+                            jacobian != NULL ? jacobian->jacobian_level_fluxes_dev : NULL, jacobian == NULL};
+    GRT_TRY(run_sky(p, cols, sky, &third, level_fluxes_dev, heating_dev, fluxes_dev));
     return GRTCODE_SUCCESS;
 }
 

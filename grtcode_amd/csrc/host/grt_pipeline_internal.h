@@ -59,7 +59,9 @@ enum
        shortwave: [max_cols][Z][S][6 or 2 V][nblocks] partial sums of every angle and cloud draw, S = 1 but in a cloud set
        (materialised form: [max_cols][Z][S][6 or 2 V] integrated rows) */
     GRT_SCRATCH_ZEN_PARTIALS,
-    /* grt_pipeline_run_sky_direct, shortwave, fused form: [max_cols][S][3 or V][nblocks] partial sums of the direct beam */
+    /* grt_pipeline_run_sky_direct, shortwave, fused form: [max_cols][S][3 or V][nblocks] partial sums of the direct beam;
+       the longwave band's blocks of these four names hold the same of grt_pipeline_run_sky_jacobian's surface-temperature
+       Jacobian (each band has one such third row group at most) */
     GRT_SCRATCH_DIRECT_PARTIALS,
     /* ... materialised form: [max_cols][V][n] the direct beam of the pass just solved (fixed size: direct_rows_d points
        into it), and -- with subcolumns -- [max_cols][V][n] its sum */
@@ -87,7 +89,7 @@ typedef struct GrtBand
     /* grt_pipeline_run_profiles (and _allsky_profiles), materialised form, allocated at the first call: [cols][2 V] device
        row pointers (up levels, then down levels) */
     double **level_rows_d;
-    /* grt_pipeline_run_sky_direct, materialised form, allocated at the first call of each form: device row pointers into
+    /* grt_pipeline_run_sky_direct (longwave band: grt_pipeline_run_sky_jacobian), materialised form, allocated at the first call of each form: device row pointers into
        GRT_SCRATCH_DIRECT_BEAM, [0]: [cols][3] (TOA, surface, user level or the zero row), [1]: [cols][V] */
     double **direct_rows_d[2];
     GrtScratch scratch[GRT_SCRATCH_COUNT];     /* what the calls allocate on demand (GRT_SCRATCH_...) */
@@ -163,6 +165,8 @@ typedef struct GrtPass
     /* grt_pipeline_run_sky_direct (NULL: not asked for): the shortwave's direct beam leaves too, the pass's three rows
        (TOA, surface, user level) or -- profile -- V levels to set `set` of direct [ncol][sets][3 or V] */
     double *direct;
+    /* grt_pipeline_run_sky_jacobian (NULL: not asked for): the longwave's dF_up/dT_surf leaves too, laid out as direct is */
+    double *jacobian;
 } GrtPass;
 
 /* The sun angles of a grt_pipeline_run_zeniths or grt_pipeline_run_sky_zeniths call, staged (grt_stage_zeniths): Z per column, their cosines and weights

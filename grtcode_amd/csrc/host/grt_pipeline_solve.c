@@ -19,12 +19,23 @@ static int pass_spectral(GrtPass const *ps)
     return ps->bins != NULL && !ps->profile;
 }
 
-/* its solver instance (materialised: the spectral form, after pass_optics); bn: its per-bin instance; sc: the pass's
-   clouds as the subcolumns of sc; da: its instance that leaves the direct beam too */
-static GrtSolverInstance pass_instance(GrtPipeline_t const *p, GrtPass const *ps, GrtBandArgs const *bn,
-                                       GrtSubcolumnArgs const *sc, GrtDirectArgs const *da)
+/* The third row group of a pass beside its up and down rows: the shortwave's direct beam (grt_pipeline_run_sky_direct) or
+   the longwave's surface-temperature Jacobian (grt_pipeline_run_sky_jacobian) -- each band has at most one, so both go
+   one way through this file and share the band's scratch blocks.  The fused form's partial sums of it, as the join of
+   whichever band it is (partials NULL: the pass leaves none) */
+typedef struct ThirdRows
 {
-    GrtSolverInstance in = {GRT_OUT_CHAINS, NULL, NULL, NULL, NULL, NULL, NULL};
+    double *partials;
+    GrtDirectArgs direct;
+    GrtJacobianArgs jacobian;
+} ThirdRows;
+
+/* its solver instance (materialised: the spectral form, after pass_optics); bn: its per-bin instance; sc: the pass's
+   clouds as the subcolumns of sc; tr: band bi's instance that leaves the third row group too */
+static GrtSolverInstance pass_instance(GrtPipeline_t const *p, GrtPass const *ps, GrtBandArgs const *bn,
+                                       GrtSubcolumnArgs const *sc, ThirdRows const *tr, int bi)
+{
+    GrtSolverInstance in = {GRT_OUT_CHAINS, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
     if (!p->keep_spectra)
     {
         in.out = pass_spectral(ps) ? GRT_OUT_ROWS_POINTS : (bn != NULL ? GRT_OUT_LEVEL_BINS :
@@ -33,16 +44,26 @@ static GrtSolverInstance pass_instance(GrtPipeline_t const *p, GrtPass const *ps
         in.aerosols = ps->aer;
         in.subcolumns = sc;
         in.bins = bn;
-        in.direct = da;
+        if (tr != NULL && tr->partials != NULL)
+        {
+            in.direct = bi == 1 ? &tr->direct : NULL;
+            in.jacobian = bi == 0 ? &tr->jacobian : NULL;
+        }
     }
     return in;
 }
 
-/* whether band bi's solve of the pass leaves the direct beam (the shortwave's, where it is asked for), its rows per set
-   and column, and where the pass's start in a column's direct_stride doubles of ps->direct */
+/* where band bi's solve of the pass leaves its third row group (NULL: it has none): the shortwave's direct beam or the
+   longwave's Jacobian, where it is asked for; its rows per set and column, and where the pass's start in a column's
+   direct_stride doubles of it */
+static double *third_out(GrtPass const *ps, int bi)
+{
+    return bi == 1 ? ps->direct : ps->jacobian;
+}
+
 static int pass_direct(GrtPass const *ps, int bi)
 {
-    return ps->direct != NULL && bi == 1;
+    return third_out(ps, bi) != NULL;
 }
 
 static int direct_rows(GrtPipeline_t const *p, GrtPass const *ps)
@@ -60,16 +81,16 @@ static int direct_offset(GrtPipeline_t const *p, GrtPass const *ps)
     return ps->set*direct_rows(p, ps);
 }
 
-/* fused form: the partial sums of the direct beam of `slots` slots per column, as *da, where the pass leaves it (else *da
-   stays empty and the caller passes no join) */
-static int direct_partials(GrtPipeline_t *p, GrtBand *b, int bi, GrtPass const *ps, int slots, GrtDirectArgs *da)
+/* fused form: the partial sums of the third row group of `slots` slots per column, as *tr, where the pass leaves one (else
+   *tr stays empty and the instance has no such join) */
+static int direct_partials(GrtPipeline_t *p, GrtBand *b, int bi, GrtPass const *ps, int slots, ThirdRows *tr)
 {
-    da->partials = NULL;
+    memset(tr, 0, sizeof(*tr));
     if (pass_direct(ps, bi))
     {
         GrtScratch *block = &b->scratch[GRT_SCRATCH_DIRECT_PARTIALS];
         GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*(size_t)slots*(size_t)direct_rows(p, ps)*b->nblocks, NULL));
-        da->partials = block->d;
+        tr->partials = tr->direct.partials = tr->jacobian.partials = block->d;
     }
     return GRTCODE_SUCCESS;
 }
@@ -215,12 +236,12 @@ static int solver_launch(void *s, int bi, GrtSolverInstance const *in, SolverArg
     return bi == 0 ? grt_launch_lw(s, in, &a->lw) : grt_launch_sw(s, in, &a->sw);
 }
 
-/* the band's solver in the pass's instance (bn: its per-bin one; da: the one that leaves the direct beam too), timed under
-   the pass's profile tag */
+/* the band's solver in the pass's instance (bn: its per-bin one; tr: the one that leaves the third row group too), timed
+   under the pass's profile tag */
 static int band_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps, double *partials,
-                       GrtBandArgs const *bn, GrtDirectArgs const *da)
+                       GrtBandArgs const *bn, ThirdRows const *tr)
 {
-    GrtSolverInstance const in = pass_instance(p, ps, bn, NULL, da);
+    GrtSolverInstance const in = pass_instance(p, ps, bn, NULL, tr, bi);
     void *s = grt_dev_stream(p->device);
     SolverArgs a;
     GRT_TRY(solver_args(p, b, bi, C, ps, &in, partials, &a));
@@ -345,14 +366,25 @@ static int integrate_rows(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass c
     return GRTCODE_SUCCESS;
 }
 
-/* Materialised form of the direct beam: from the tau, omega, g the pass (its last subcolumn) has left in the band's arrays,
-   every level's direct beam on the grid, [C][V][n] in GRT_SCRATCH_DIRECT_BEAM (GRT_TAG_DIRECT_BEAM) */
-static int direct_beam(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *ps)
+/* Materialised form of the third row group: from the tau, omega, g the pass (its last subcolumn) has left in the band's
+   arrays, every level's direct beam (shortwave, GRT_TAG_DIRECT_BEAM) or surface-temperature Jacobian (longwave,
+   GRT_TAG_SURFACE_JACOBIAN) on the grid, [C][V][n] in GRT_SCRATCH_DIRECT_BEAM */
+static int direct_beam(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps)
 {
     void *s = grt_dev_stream(p->device);
+    GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_DIRECT_BEAM], (size_t)p->max_cols*(size_t)p->num_levels*b->n, NULL));
+    if (bi == 0)
+    {
+        GrtLwArgs a;
+        lw_args(p, b, C, 0, ps, &a);
+        int const slot = grt_profile_begin(s, GRT_TAG_SURFACE_JACOBIAN);
+        int const krc = grt_launch_lw_surface_jacobian(s, &a, b->scratch[GRT_SCRATCH_DIRECT_BEAM].d);
+        grt_profile_end(s, slot);
+        GRT_TRY(grt_dev_check(krc, "surface Jacobian kernel"));
+        return GRTCODE_SUCCESS;
+    }
     GrtSwArgs a;
     sw_args(p, b, C, 0, ps, &a);
-    GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_DIRECT_BEAM], (size_t)p->max_cols*(size_t)p->num_levels*b->n, NULL));
     int const slot = grt_profile_begin(s, GRT_TAG_DIRECT_BEAM);
     int const krc = grt_launch_sw_direct_beam(s, &a, b->scratch[GRT_SCRATCH_DIRECT_BEAM].d);
     grt_profile_end(s, slot);
@@ -360,9 +392,9 @@ static int direct_beam(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *ps)
     return GRTCODE_SUCCESS;
 }
 
-/* ... and the row-wise trapezoid of it into the pass's direct rows: TOA, surface and the user level (the zero row without
+/* ... and the row-wise trapezoid of it into the pass's third rows: TOA, surface and the user level (the zero row without
    one), or -- profile -- every level */
-static int direct_integrate(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *ps)
+static int direct_integrate(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps)
 {
     size_t const V = (size_t)p->num_levels, cols = (size_t)p->max_cols, rows = (size_t)direct_rows(p, ps);
     double *beam = b->scratch[GRT_SCRATCH_DIRECT_BEAM].d;
@@ -372,7 +404,8 @@ static int direct_integrate(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *
         double **rows_h = malloc(sizeof(double *)*cols*rows);
         if (rows_h == NULL)
         {
-            GRT_FAIL(GRTCODE_NULL_ERR, "out of host memory for the direct-beam row table of %zu columns.", cols);
+            GRT_FAIL(GRTCODE_NULL_ERR, "out of host memory for the %s row table of %zu columns.",
+                     bi == 1 ? "direct-beam" : "surface Jacobian", cols);
         }
         for (size_t c = 0; c < cols; ++c)
         {
@@ -391,7 +424,7 @@ static int direct_integrate(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *
         GRT_TRY(grt_upload_rows(p, rows_h, cols*rows, table));
     }
     GRT_TRY(grt_dev_check(grt_launch_integrate_rows(grt_dev_stream(p->device), (double const *const *)*table, C*(int)rows,
-                                                    b->n, b->gas->grid.dw, ps->direct, (int)rows, direct_stride(p, ps),
+                                                    b->n, b->gas->grid.dw, third_out(ps, bi), (int)rows, direct_stride(p, ps),
                                                     direct_offset(p, ps)), "spectral integration kernel"));
     return GRTCODE_SUCCESS;
 }
@@ -494,13 +527,13 @@ int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *p
         GRT_TRY(integrate_rows(p, b, bi, C, ps));
         if (pass_direct(ps, bi))
         {
-            GRT_TRY(direct_beam(p, b, C, ps));
-            GRT_TRY(direct_integrate(p, b, C, ps));
+            GRT_TRY(direct_beam(p, b, bi, C, ps));
+            GRT_TRY(direct_integrate(p, b, bi, C, ps));
         }
         return GRTCODE_SUCCESS;
     }
     int const rows = pass_rows(p, ps);
-    GrtDirectArgs da;
+    ThirdRows da;
     GRT_TRY(direct_partials(p, b, bi, ps, 1, &da));
     if (ps->profile)
     {
@@ -508,15 +541,16 @@ int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *p
                                  NULL));
     }
     double *partials = ps->profile ? b->scratch[GRT_SCRATCH_LEVEL_PARTIALS].d : b->partials;
-    GRT_TRY(band_solver(p, b, bi, C, ps, partials, NULL, da.partials != NULL ? &da : NULL));
+    GRT_TRY(band_solver(p, b, bi, C, ps, partials, NULL, &da));
     GRT_TRY(grt_dev_check(grt_launch_reduce_partials(grt_dev_stream(p->device), partials, C*rows, b->nblocks, ps->out, rows,
                                                      ps->out_stride, pass_offset(p, ps, bi)), "flux reduction kernel"));
     if (da.partials != NULL)
     {
         int const drows = direct_rows(p, ps);
         GRT_TRY(grt_dev_check(grt_launch_reduce_partials(grt_dev_stream(p->device), da.partials, C*drows, b->nblocks,
-                                                         ps->direct, drows, direct_stride(p, ps), direct_offset(p, ps)),
-                              "direct-beam reduction kernel"));
+                                                         third_out(ps, bi), drows, direct_stride(p, ps),
+                                                         direct_offset(p, ps)),
+                              bi == 1 ? "direct-beam reduction kernel" : "surface Jacobian reduction kernel"));
     }
     return GRTCODE_SUCCESS;
 }
@@ -539,10 +573,10 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
         double *sub_partials = b->scratch[GRT_SCRATCH_SUB_PARTIALS].d;
         /* (in points at sc: the loop below walks sc.first and sc.count, which the launcher alone reads) */
         GrtSubcolumnArgs sc = {*ps->clouds, S, 0, 0};
-        GrtDirectArgs da;
+        ThirdRows da;
         GRT_TRY(direct_partials(p, b, bi, ps, S, &da));
         int const drows = direct_rows(p, ps);
-        GrtSolverInstance const in = pass_instance(p, ps, NULL, &sc, da.partials != NULL ? &da : NULL);
+        GrtSolverInstance const in = pass_instance(p, ps, NULL, &sc, &da, bi);
         SolverArgs a;
         GRT_TRY(solver_args(p, b, bi, C, ps, &in, sub_partials, &a));
         /* (grid rows; a park block of max_cols columns) */
@@ -563,9 +597,9 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
                                                              ps->out_stride, out_offset), "flux reduction kernel"));
             if (da.partials != NULL)
             {
-                GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, da.partials, C*drows, b->nblocks, ps->direct, drows,
+                GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, da.partials, C*drows, b->nblocks, third_out(ps, bi), drows,
                                                                  direct_stride(p, ps), direct_offset(p, ps)),
-                                      "direct-beam reduction kernel"));
+                                      bi == 1 ? "direct-beam reduction kernel" : "surface Jacobian reduction kernel"));
             }
             return GRTCODE_SUCCESS;
         }
@@ -574,7 +608,7 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
         if (mrc == 0 && da.partials != NULL)
         {
             /* (the same kernel: subcolumns 0 .. S - 1 in order, then one division by S) */
-            mrc = grt_launch_subcolumn_mean(s, da.partials, C, S, drows, b->nblocks, ps->direct, direct_stride(p, ps),
+            mrc = grt_launch_subcolumn_mean(s, da.partials, C, S, drows, b->nblocks, third_out(ps, bi), direct_stride(p, ps),
                                             direct_offset(p, ps));
         }
         grt_profile_end(s, mslot);
@@ -604,7 +638,7 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
                               "flux sum kernel"));
         if (pass_direct(ps, bi))
         {
-            GRT_TRY(direct_beam(p, b, C, &pj));
+            GRT_TRY(direct_beam(p, b, bi, C, &pj));
             GRT_TRY(grt_dev_check(grt_launch_flux_accumulate(s, per, b->scratch[GRT_SCRATCH_DIRECT_BEAM].d, direct_sum,
                                                              j == 0), "flux sum kernel"));
         }
@@ -616,7 +650,7 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
     {
         GRT_TRY(grt_dev_check(grt_launch_flux_mean(s, per, direct_sum, S, b->scratch[GRT_SCRATCH_DIRECT_BEAM].d),
                               "flux mean kernel"));
-        GRT_TRY(direct_integrate(p, b, C, ps));
+        GRT_TRY(direct_integrate(p, b, bi, C, ps));
     }
     return GRTCODE_SUCCESS;
 }
@@ -657,7 +691,7 @@ int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass c
             sc.subcolumns = S;
         }
         GrtSubcolumnArgs *draws = ps->clouds != NULL ? &sc : NULL;
-        GrtSolverInstance in = pass_instance(p, ps, NULL, draws, NULL);
+        GrtSolverInstance in = pass_instance(p, ps, NULL, draws, NULL, 1);
         in.zeniths = &za;
         SolverArgs a;
         GRT_TRY(solver_args(p, b, 1, C, ps, &in, block->d, &a));
@@ -717,7 +751,7 @@ int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass c
                 pj.clouds = &cj;
             }
             GRT_TRY(pass_optics(p, b, C, &pj));
-            GrtSolverInstance const in = pass_instance(p, &pj, NULL, NULL, NULL);
+            GrtSolverInstance const in = pass_instance(p, &pj, NULL, NULL, NULL, 1);
             SolverArgs a;
             GRT_TRY(solver_args(p, b, 1, C, &pj, &in, NULL, &a));
             for (int k = 0; k < Z; ++k)

@@ -487,6 +487,49 @@ EXTERN int grt_pipeline_run_sky_direct(GrtPipeline_t *pipeline, GrtColumns_t con
                                        GrtDirectBeam_t const *direct,
                                        fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev);
 
+/* ---- the surface-temperature Jacobian of the longwave, of every sky set --------------------------------------------
+ * grt_pipeline_run_sky in every respect -- the sets and their packing order, both output forms, the shortwave sweep rule,
+ * the surface in force (the Jacobian takes that column's emissivity row), the input checks -- and with it the derivative
+ * of each set's upward longwave flux with respect to the surface temperature, dF_up(level)/dT_surf, which a host model
+ * that calls radiation less often than its surface changes uses to keep the longwave consistent with the surface
+ * (Hogan and Bozzo 2015; RRTMG's idrv = 1; ecRad's lw_derivatives).  With N = grt_pipeline_sky_set_count(sets):
+ *   jacobian_fluxes_dev       [ncol][N][GRT_JACOBIAN_ROWS_PER_SET] (required): the derivative at the top of the
+ *                             atmosphere, at the surface and at the user level, W m-2 K-1; with user_level < 0 the user
+ *                             row is +0.0;
+ *   jacobian_level_fluxes_dev [ncol][N][V] (profile form only; may be NULL): the derivative at every level, top first.
+ * The value is the exact derivative of the discrete four-stream solver, not a finite difference: the surface enters each
+ * stream once (longwave.c:202, I_s = emis B(T_surf) + (1 - emis) I_s), every layer above multiplies the stream by its
+ * extinction exp(c1[s] t), t = tau (1 - omega), and nothing else in the upward sweep depends on T_surf, so per grid point
+ *   D_s(surface) = emis(w) dB/dT(T_surf, w),   D_s(level j) = D_s(level j + 1) exp(c1[s] t_j),
+ *   J(level j, w) = (((0 + c2[0] D_0) + c2[1] D_1) + c2[2] D_2) + c2[3] D_3,
+ * with dB/dT = B (x/T) e/(e - 1), x = c2 w/T, e = exp(x), and 0 where planck_law clamps x (x > 700); integrated over the
+ * band with the same trapezoid as every other row.  The longwave has no scattering: the downward fluxes do not depend
+ * on T_surf, their derivative is identically zero and is not returned.  A cloud set's value is the mean over its
+ * num_subcolumns draws, taken as the other rows take theirs: subcolumns 0 .. S - 1 in order, then one division by S.
+ * sets == GRT_SKY_CLEAN with clouds and aerosols NULL is the clear-sky Jacobian on its own.  A pipeline without a longwave
+ * band writes zeros to both Jacobian outputs.  All DEVICE memory; asynchronous on the pipeline's lane.  The production
+ * form takes the Jacobian out of the solvers that compute the sets (instances of their own, whose upward sweep carries
+ * the four derivatives beside the four intensities: three more rows, or V, beside the set's own partial sums; the
+ * launches count under grt_pipeline_run_sky's tags); keep_spectra = 1 forms it from each set's tau and omega on the grid
+ * with a kernel of its own (GRT_TAG_SURFACE_JACOBIAN) and the row-wise trapezoid.  In the deterministic mode every output
+ * grt_pipeline_run_sky also writes is grt_pipeline_run_sky's, bit for bit; rows 0, V - 1 and user_level of
+ * jacobian_level_fluxes_dev are the six-row form's three rows; the surface row is the same double in every set of a
+ * column.  GRTCODE_VALUE_ERR, with nothing launched and every output untouched, for: jacobian NULL; jacobian_fluxes_dev
+ * NULL; jacobian_level_fluxes_dev given in the six-row form (level_fluxes_dev NULL); everything grt_pipeline_run_sky
+ * refuses.
+ * Not covered: the several-sun-angle entry points (the longwave does not depend on the sun: call this one beside them),
+ * cloud fields sampled on the device, and spectral or per-bin Jacobians. */
+#define GRT_JACOBIAN_ROWS_PER_SET 3   /* dF_up/dT_surf at TOA, surface, user level; W m-2 K-1 */
+typedef struct GrtSurfaceJacobian
+{
+    fp_t *jacobian_fluxes_dev;        /* DEVICE [ncol][N][GRT_JACOBIAN_ROWS_PER_SET]; required */
+    fp_t *jacobian_level_fluxes_dev;  /* DEVICE [ncol][N][V], levels top first; profile form only; may be NULL */
+} GrtSurfaceJacobian_t;
+
+EXTERN int grt_pipeline_run_sky_jacobian(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtSky_t const *sky,
+                                         GrtSurfaceJacobian_t const *jacobian,
+                                         fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev);
+
 /* ---- spectral and band-integrated fluxes ---------------------------------------------------------------------------
  * driver.c's output without -integrated (output_fluxes, driver.c:285-356): the six rows of grt_pipeline_run at EVERY grid
  * point, and -- where the caller gives bin edges -- the same rows integrated over wavenumber bins, for a batch of columns,
@@ -760,7 +803,10 @@ enum
        and draw's together (its clean set counts under GRT_TAG_ZENITH_SW, its longwave under grt_pipeline_run_sky's tags);
        23 = its mean kernel, every set's */
     GRT_TAG_SKY_ZENITH_SW = 22,
-    GRT_TAG_SKY_ZENITH_MEAN = 23
+    GRT_TAG_SKY_ZENITH_MEAN = 23,
+    /* 24 = the Jacobian kernel of grt_pipeline_run_sky_jacobian's materialised form (every set's, every subcolumn's; the
+       fused instances count under grt_pipeline_run_sky's tags) */
+    GRT_TAG_SURFACE_JACOBIAN = 24
 };
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
