@@ -195,6 +195,9 @@ void grt_profile_end(void *stream, int slot);
 int grt_launch_gas_optics_mp(void *stream, GrtGasOpticsArgs const *a);
 int grt_gas_optics_mp_shape(GrtGasOpticsArgs const *a);
 int grt_gas_optics_lean_shape(GrtGasOpticsArgs const *a);
+/* which (group, layer-and-column index) workgroup b of a line-kernel launch of nb = ngroups*per_group workgroups takes:
+   the kernels' own mapping (grt_work_order.h), compiled for the host (grt_gas_launch.c) */
+void grt_work_order(unsigned nb, unsigned per_group, unsigned ngroups, unsigned b, unsigned *group, unsigned *rem);
 int grt_tree_gather_by_wave(long long fsteps);   /* k_gas_optics_far.hip: the tree gather's near fields in 64-point blocks */
 uint64_t grt_gas_optics_moment_floats(uint64_t nw, int levels, int terms);   /* per (column, layer) block of gmom */
 double grt_gas_optics_moment_separation(int terms);   /* near field / |z|max that keeps the series' remainder at 7e-8 */

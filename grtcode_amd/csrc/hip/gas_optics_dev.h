@@ -6,6 +6,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "../grt_kernels.h"
+#include "../grt_work_order.h"
 #include "exp_pair.h"
 
 #pragma clang fp contract(off)
@@ -561,21 +562,20 @@ struct WorkItem
     unsigned group;
 };
 
-// XCD-aware work order.  Workgroups are dealt round-robin over the 8 XCDs (ids b and b+8 share
-// one), and all (layer, column) workgroups of one (tile, line slice) "group" read the SAME slice
-// of the line list.  Every XCD gets an equal, contiguous share of the work items, ordered group
-// by group with layer/column varying fastest, so the ~10^2 workgroups resident on an XCD share
-// one or two line slices (~1 MB) that live in its 4 MB L2 instead of being re-fetched over the
-// fabric (FETCH_SIZE 17 GB -> 0.06 GB per shortwave launch).  Groups are visited in a
-// golden-ratio stride permutation so that each XCD's share mixes cheap and expensive spectral
-// regions (high-wavenumber tiles carry more near-centre work).  Placement affects speed only.
-__device__ __forceinline__ WorkItem decode_work(GrtGasOpticsArgs const &a, unsigned ngroups, unsigned perm_stride)
+// Lockstep work order (grt_work_order.h).  All (layer, column) workgroups of one (tile, line slice) "group" read the SAME
+// slice of the line list, and workgroup b takes work item b: group by group, layer/column varying fastest.  The hardware
+// deals workgroup ids round-robin over the 8 XCDs (ids b and b+8 share one), so every XCD takes an eighth of EVERY group
+// and all eight march through the same sequence of groups: their shares are equal whatever a tile costs (high-wavenumber
+// tiles carry more near-centre work, the last tile is short), and the last group is drained by all eight.  The ~10^2
+// workgroups resident on an XCD still belong to one or two groups, whose line slices (~1 MB) live in its 4 MB L2 instead
+// of being re-fetched over the fabric for every workgroup; each slice is read into eight L2s instead of one.  Groups go in
+// spectral order: no permutation is left to balance anything, and the one there was measured slower.
+// Placement affects speed only.
+__device__ __forceinline__ WorkItem decode_work(GrtGasOpticsArgs const &a, unsigned ngroups)
 {
-    unsigned const nb = gridDim.x, xcd = blockIdx.x & 7u, q8 = nb >> 3, r8 = nb & 7u;
-    unsigned const work = (xcd < r8 ? xcd*(q8 + 1u) : r8*(q8 + 1u) + (xcd - r8)*q8) + (blockIdx.x >> 3);
     unsigned const per_group = (unsigned)a.lay.num_layers*(unsigned)a.ncol;
-    unsigned const pos = work/per_group, rem = work - pos*per_group;
-    unsigned const group = (unsigned)(((unsigned long long)pos*perm_stride) % ngroups);
+    unsigned group, rem;
+    grt_work_order_map(gridDim.x, per_group, ngroups, blockIdx.x, &group, &rem);
     WorkItem w;
     w.col = (int)(rem/(unsigned)a.lay.num_layers);
     w.layer = (int)(rem - (unsigned)w.col*(unsigned)a.lay.num_layers);
@@ -758,20 +758,6 @@ __device__ __forceinline__ void write_tile(GrtGasOpticsArgs const &a, double con
             if (has1) unsafeAtomicAdd(&out[f + 1], v1);
         }
     }
-}
-
-// stride of the group permutation: nearest integer to ngroups/phi^2 that is coprime with ngroups
-inline unsigned golden_stride(unsigned long long ngroups)
-{
-    unsigned stride = (unsigned)((double)ngroups*0.3819660112501051);
-    if (stride < 1) stride = 1;
-    for (;; ++stride)
-    {
-        unsigned x = stride, y = (unsigned)ngroups;
-        while (y != 0) { unsigned const t = x % y; x = y; y = t; }
-        if (x == 1) break;
-    }
-    return stride;
 }
 
 } // namespace

@@ -51,8 +51,7 @@ namespace {
 constexpr int kRingWaves = 4;
 template <bool FAST>
 __attribute__((amdgpu_waves_per_eu(kRingWaves, kRingWaves)))
-__global__ __launch_bounds__(kBlock) void gas_optics_kernel(GrtGasOpticsArgs a, long long fsteps, unsigned ngroups,
-                                                                                          unsigned perm_stride)
+__global__ __launch_bounds__(kBlock) void gas_optics_kernel(GrtGasOpticsArgs a, long long fsteps, unsigned ngroups)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double *acc = reinterpret_cast<double *>(smem);                               // [tile]
@@ -66,7 +65,7 @@ __global__ __launch_bounds__(kBlock) void gas_optics_kernel(GrtGasOpticsArgs a, 
     int const tid = threadIdx.x;
     int const lane = tid & 63;
     int const wave = tid >> 6;
-    WorkItem const wi = decode_work(a, ngroups, perm_stride);
+    WorkItem const wi = decode_work(a, ngroups);
     int const col = wi.col, layer = wi.layer, tile_idx = wi.tile_idx, slice = wi.slice;
     long long const nw = (long long)a.nw;
     long long const F0l = (long long)tile_idx*a.tile;
@@ -420,16 +419,15 @@ extern "C" int grt_launch_gas_optics(void *stream, GrtGasOpticsArgs const *a)
         return (int)hipErrorInvalidValue;
     }
     dim3 const grid((unsigned)blocks, 1, 1);
-    unsigned const stride = golden_stride(ngroups);
     size_t const lds = gas_optics_lds_bytes(a->tile);
     hipStream_t const s = (hipStream_t)stream;
     if (a->fast)
     {
-        hipLaunchKernelGGL(gas_optics_kernel<true>, grid, dim3(kBlock), lds, s, *a, fsteps, (unsigned)ngroups, stride);
+        hipLaunchKernelGGL(gas_optics_kernel<true>, grid, dim3(kBlock), lds, s, *a, fsteps, (unsigned)ngroups);
     }
     else
     {
-        hipLaunchKernelGGL(gas_optics_kernel<false>, grid, dim3(kBlock), lds, s, *a, fsteps, (unsigned)ngroups, stride);
+        hipLaunchKernelGGL(gas_optics_kernel<false>, grid, dim3(kBlock), lds, s, *a, fsteps, (unsigned)ngroups);
     }
     return (int)hipGetLastError();
 }

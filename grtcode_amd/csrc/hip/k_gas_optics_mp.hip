@@ -77,7 +77,7 @@ constexpr int kProbeWords = 24;
 constexpr int kLeanP = 2;
 template <bool TWO_PASS, bool TREE, int K, bool NARROW = false, bool PROBE = false, bool LEAN_LOOP = false>
 __device__ __forceinline__ void mp_kernel_body(GrtGasOpticsArgs const &a, long long fsteps_ll, unsigned ngroups,
-                                               unsigned perm_stride, int ncell, int nacc, int halo)
+                                               int ncell, int nacc, int halo)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     int const fsteps = (int)fsteps_ll;
@@ -100,7 +100,7 @@ __device__ __forceinline__ void mp_kernel_body(GrtGasOpticsArgs const &a, long l
     // (the same in every lane of a wave, and said so: line indices, queue positions and the addresses built on them then
     // live in scalar registers)
     int const wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    WorkItem const wi = decode_work(a, ngroups, perm_stride);
+    WorkItem const wi = decode_work(a, ngroups);
     int const col = wi.col, layer = wi.layer, tile_idx = wi.tile_idx, slice = wi.slice;
     if (TWO_PASS && a.tile_nphase > 1 && tile_idx % a.tile_nphase != a.tile_phase)
     {
@@ -627,9 +627,9 @@ __device__ __forceinline__ void mp_kernel_body(GrtGasOpticsArgs const &a, long l
 
 template <bool TWO_PASS, bool TREE = false, int K = kMom>
 __global__ __launch_bounds__(kBlock) void gas_optics_mp_kernel(GrtGasOpticsArgs a, long long fsteps_ll, unsigned ngroups,
-                                                                unsigned perm_stride, int ncell, int nacc, int halo)
+                                                                int ncell, int nacc, int halo)
 {
-    mp_kernel_body<TWO_PASS, TREE, K>(a, fsteps_ll, ngroups, perm_stride, ncell, nacc, halo);
+    mp_kernel_body<TWO_PASS, TREE, K>(a, fsteps_ll, ngroups, ncell, nacc, halo);
 }
 
 // The same, told to fit FIVE waves per SIMD (96 VGPRs, 8-16 of them spilled to scratch; five workgroups per CU with the
@@ -642,37 +642,37 @@ __global__ __launch_bounds__(kBlock) void gas_optics_mp_kernel(GrtGasOpticsArgs 
 constexpr int kMpWaves = 5;
 template <bool TWO_PASS, bool TREE, int K, bool NARROW = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kMpWaves, kMpWaves)))
-void gas_optics_mp_kernel_w5(GrtGasOpticsArgs a, long long fsteps_ll, unsigned ngroups, unsigned perm_stride, int ncell,
+void gas_optics_mp_kernel_w5(GrtGasOpticsArgs a, long long fsteps_ll, unsigned ngroups, int ncell,
                              int nacc, int halo)
 {
-    mp_kernel_body<TWO_PASS, TREE, K, NARROW>(a, fsteps_ll, ngroups, perm_stride, ncell, nacc, halo);
+    mp_kernel_body<TWO_PASS, TREE, K, NARROW>(a, fsteps_ll, ngroups, ncell, nacc, halo);
 }
 
 // First pass of the two-pass form with the lean line loop (see mp_kernel_body<..., LEAN_LOOP>).
 constexpr int kLeanWaves = 4;
 template <bool NARROW>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kLeanWaves, kLeanWaves)))
-void gas_optics_lean_kernel(GrtGasOpticsArgs a, long long fsteps_ll, unsigned ngroups, unsigned perm_stride, int ncell,
+void gas_optics_lean_kernel(GrtGasOpticsArgs a, long long fsteps_ll, unsigned ngroups, int ncell,
                             int nacc, int halo)
 {
-    mp_kernel_body<true, false, kMom, NARROW, false, true>(a, fsteps_ll, ngroups, perm_stride, ncell, nacc, halo);
+    mp_kernel_body<true, false, kMom, NARROW, false, true>(a, fsteps_ll, ngroups, ncell, nacc, halo);
 }
 
 // The instrumented instance of the tree form on sparse lines (twelve moments), see mp_kernel_body<..., PROBE>.
 __global__ __launch_bounds__(kBlock)
-void gas_optics_mp_probe_wide_kernel(GrtGasOpticsArgs a, long long fsteps_ll, unsigned ngroups, unsigned perm_stride, int ncell,
+void gas_optics_mp_probe_wide_kernel(GrtGasOpticsArgs a, long long fsteps_ll, unsigned ngroups, int ncell,
                                      int nacc, int halo)
 {
-    mp_kernel_body<true, true, kMomWide, false, true>(a, fsteps_ll, ngroups, perm_stride, ncell, nacc, halo);
+    mp_kernel_body<true, true, kMomWide, false, true>(a, fsteps_ll, ngroups, ncell, nacc, halo);
 }
 
 // The instrumented instance of the two-pass first pass (single-level form), see mp_kernel_body<..., PROBE>.
 template <bool NARROW>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4)))
-void gas_optics_mp_probe_kernel(GrtGasOpticsArgs a, long long fsteps_ll, unsigned ngroups, unsigned perm_stride, int ncell,
+void gas_optics_mp_probe_kernel(GrtGasOpticsArgs a, long long fsteps_ll, unsigned ngroups, int ncell,
                                 int nacc, int halo)
 {
-    mp_kernel_body<true, false, kMom, NARROW, true>(a, fsteps_ll, ngroups, perm_stride, ncell, nacc, halo);
+    mp_kernel_body<true, false, kMom, NARROW, true>(a, fsteps_ll, ngroups, ncell, nacc, halo);
 }
 
 // subtree_tile > 0: the tree form's first pass with moments straight to global memory, which ends by building the tile's
@@ -855,7 +855,7 @@ extern "C" int grt_launch_gas_optics_mp(void *stream, GrtGasOpticsArgs const *a)
         }
         // the first pass's instance: the tree form's (twelve moments, instrumented or not; eight), or the single-level form's --
         // instrumented, lean line loop or general loop, each for narrow Doppler widths (GrtGasOpticsArgs.narrow) or not
-        void (*first_pass)(GrtGasOpticsArgs, long long, unsigned, unsigned, int, int, int);
+        void (*first_pass)(GrtGasOpticsArgs, long long, unsigned, int, int, int);
         if (wide && a->probe != NULL) first_pass = gas_optics_mp_probe_wide_kernel;
         else if (wide) first_pass = gas_optics_mp_kernel<true, true, kMomWide>;
         else if (tree) first_pass = gas_optics_mp_kernel_w5<true, true, kMom>;
@@ -867,7 +867,7 @@ extern "C" int grt_launch_gas_optics_mp(void *stream, GrtGasOpticsArgs const *a)
             b.tile_phase = phase;
             b.tile_nphase = nphase;
             hipLaunchKernelGGL(first_pass, dim3((unsigned)blocks), dim3(kBlock), lds, s, b, fsteps, (unsigned)ngroups,
-                               golden_stride(ngroups), ncell, nacc, halo);
+                               ncell, nacc, halo);
         }
         if (a->profile_tag) grt_profile_end(stream, slot);
         b.nslice = 1;
@@ -881,6 +881,6 @@ extern "C" int grt_launch_gas_optics_mp(void *stream, GrtGasOpticsArgs const *a)
     int const ncell = a->tile + 2*(int)fsteps;
     size_t const lds = mp_lds_bytes(a->tile, ncell, (int)fsteps, a->lay.num_slots);
     hipLaunchKernelGGL((gas_optics_mp_kernel_w5<false, false, kMom>), dim3((unsigned)blocks), dim3(kBlock), lds, s, *a, fsteps,
-                       (unsigned)ngroups, golden_stride(ngroups), ncell, a->tile, 0);
+                       (unsigned)ngroups, ncell, a->tile, 0);
     return (int)hipGetLastError();
 }

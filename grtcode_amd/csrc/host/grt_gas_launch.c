@@ -4,6 +4,13 @@
 #include <stdlib.h>
 #include <string.h>
 #include "grt_internal.h"
+#include "../grt_work_order.h"
+
+/* the kernels' work order as a host function (tests/test_work_order.py walks it) */
+void grt_work_order(unsigned nb, unsigned per_group, unsigned ngroups, unsigned b, unsigned *group, unsigned *rem)
+{
+    grt_work_order_map(nb, per_group, ngroups, b, group, rem);
+}
 
 /* two-pass form: windows of more than this many points a side take the far field through the cell hierarchy */
 #define TREE_MIN_FSTEPS 200
