@@ -29,7 +29,7 @@ GRT_CLOUD_PHASE, GRT_CLOUD_MODEL, GRT_CLOUD_FIELDS = 7, 8, 9   # ... of GrtCloud
 (TAG_GAS_LW, TAG_GAS_SW, TAG_SOLVER_LW, TAG_SOLVER_SW, TAG_CLEAR_OPTICS, TAG_FAR_LW, TAG_FAR_SW, TAG_ALLSKY_LW,
  TAG_ALLSKY_SW, TAG_BINS, TAG_SUBCOLUMN_MEAN, TAG_AEROSOL_LW, TAG_AEROSOL_SW, TAG_BAND_PROFILES, TAG_SURFACE,
  TAG_CLOUD_SAMPLER, TAG_SKY_LW, TAG_SKY_SW, TAG_ZENITH_SW, TAG_ZENITH_MEAN, TAG_DIRECT_BEAM, TAG_SKY_ZENITH_SW,
- TAG_SKY_ZENITH_MEAN, TAG_SURFACE_JACOBIAN) = range(1, 25)
+ TAG_SKY_ZENITH_MEAN, TAG_SURFACE_JACOBIAN, TAG_RADIANCE) = range(1, 26)
 TAG_FAR_OFFSET = TAG_FAR_LW - TAG_GAS_LW    # from a line kernel's tag to its far-field gather's
 CLOUD_SAMPLER_TAG = TAG_CLOUD_SAMPLER
 GRT_MAX_SUBCOLUMNS = 64             # grt_pipeline_run_subcolumns: subcolumns per column, 1 .. this
@@ -41,6 +41,8 @@ GRT_SKY_ALL = GRT_SKY_CLEAN | GRT_SKY_AEROSOL | GRT_SKY_CLOUD | GRT_SKY_CLOUD_AE
 GRT_SKY_MAX_SETS = 4
 GRT_DIRECT_ROWS_PER_SET = 3         # grt_pipeline_run_sky_direct: the direct beam at TOA, surface, user level
 GRT_JACOBIAN_ROWS_PER_SET = 3       # grt_pipeline_run_sky_jacobian: dF_up/dT_surf at TOA, surface, user level
+GRT_MAX_VIEW_ANGLES = 16            # grt_pipeline_run_sky_radiances: viewing angles per column, 1 .. this
+GRT_RADIANCE_ROWS_PER_ANGLE = 2     # ... per angle: upward at the top of the atmosphere, downward at the surface
 RETURN_CODES = ["GRTCODE_SUCCESS", "GRTCODE_INVALID_ERR", "GRTCODE_DIVBYZERO_ERR", "GRTCODE_OVERFLOW_ERR",
                 "GRTCODE_UNDERFLOW_ERR", "GRTCODE_SENTINEL_ERR", "GRTCODE_NULL_ERR", "GRTCODE_NON_NULL_ERR",
                 "GRTCODE_RANGE_ERR", "GRTCODE_VALUE_ERR", "GRTCODE_COMPILER_ERR", "GRTCODE_IO_ERR",
@@ -189,6 +191,11 @@ class GrtSurfaceJacobian(C.Structure):
     _fields_ = [("jacobian_fluxes_dev", C.c_void_p), ("jacobian_level_fluxes_dev", C.c_void_p)]
 
 
+class GrtRadiances(C.Structure):
+    _fields_ = [("num_angles", C.c_int), ("view_secant", c_double_p), ("radiances_dev", C.c_void_p),
+                ("spectral_radiances_dev", C.c_void_p), ("brightness_dev", C.c_void_p)]
+
+
 class GrtZeniths(C.Structure):
     _fields_ = [("num_zeniths", C.c_int), ("cos_zenith", c_double_p), ("weight", c_double_p),
                 ("zenith_fluxes_dev", C.c_void_p), ("zenith_level_fluxes_dev", C.c_void_p)]
@@ -215,7 +222,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_zeniths grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_zeniths grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -278,6 +285,9 @@ def load_library(path=None):
     if hasattr(lib, "grt_pipeline_run_sky_jacobian"):    # (GRT_LIB_PATH may name an older library: a timing yardstick)
         lib.grt_pipeline_run_sky_jacobian.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky),
                                                       C.POINTER(GrtSurfaceJacobian), C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "grt_pipeline_run_sky_radiances"):   # (GRT_LIB_PATH may name an older library: a timing yardstick)
+        lib.grt_pipeline_run_sky_radiances.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky),
+                                                       C.POINTER(GrtRadiances), C.c_void_p]
     lib.grt_pipeline_sky_set_count.argtypes = [C.c_uint]
     if hasattr(lib, "grt_pipeline_run_zeniths"):    # (GRT_LIB_PATH may name an older library: a timing yardstick)
         lib.grt_pipeline_run_zeniths.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtZeniths), C.c_void_p,
@@ -1044,6 +1054,39 @@ class Pipeline:
         sky_jacobian_fluxes(), and jacobian_levels=[ncol][nsets][V], the derivative at every level, top first)."""
         return dict(jacobian=self.sky_jacobian_fluxes(ncol, nsets, profiles=True),
                     jacobian_levels=self.buffers["sky_profiles.jacobian_levels"].to_host((ncol, nsets, self.num_levels)))
+
+    def run_sky_radiances(self, gcols, gsky, secants, spectral=False, brightness=False, fluxes=True):
+        """grt_pipeline_run_sky_radiances into this object's device buffers: the longwave radiances of every set gsky asks
+        for at the viewing secants [ncol][A] (sky_radiances() reads them; spectral=True / brightness=True: at every grid
+        point too, sky_spectral_radiances() / sky_brightness()), and -- fluxes=True -- run_sky's six-row output where
+        run_sky puts it (sky_fluxes() reads it); fluxes=False: the radiances alone, no flux solver and no shortwave."""
+        m = _f64(secants)
+        if m.ndim != 2:
+            raise ValueError(f"secants of shape {m.shape}: [ncol][A]")
+        nsets = max(sky_set_count(gsky.sets), 1)
+        n, A = self.max_columns, m.shape[1]
+        rows = 8 * n * nsets * max(A, 1) * GRT_RADIANCE_ROWS_PER_ANGLE
+        grad = GrtRadiances(A, _dp(m), self._buffer("sky.radiances", rows).ptr,
+                            self._buffer("sky.spectral_radiances", rows * self.nw[0]).ptr if spectral else None,
+                            self._buffer("sky.brightness", rows * self.nw[0]).ptr if brightness else None)
+        out = self._sky_ptrs(gsky, False)[0][2] if fluxes else None
+        check(self.lib.grt_pipeline_run_sky_radiances(self.p, C.byref(gcols), C.byref(gsky), C.byref(grad), out))
+
+    def sky_radiances(self, ncol, nsets, nangles):
+        """The last run_sky_radiances of nsets sets at nangles angles: [ncol][nsets][nangles][2], band-integrated, W m-2
+        sr-1: the upward radiance at the top of the atmosphere, then the downward one at the surface."""
+        self.sync()
+        return self.buffers["sky.radiances"].to_host((ncol, nsets, nangles, GRT_RADIANCE_ROWS_PER_ANGLE))
+
+    def sky_spectral_radiances(self, ncol, nsets, nangles):
+        """... run with spectral=True: [ncol][nsets][nangles][2][n_lw], W m-2 sr-1 per cm-1."""
+        self.sync()
+        return self.buffers["sky.spectral_radiances"].to_host((ncol, nsets, nangles, GRT_RADIANCE_ROWS_PER_ANGLE, self.nw[0]))
+
+    def sky_brightness(self, ncol, nsets, nangles):
+        """... run with brightness=True: [ncol][nsets][nangles][2][n_lw], brightness temperatures, K."""
+        self.sync()
+        return self.buffers["sky.brightness"].to_host((ncol, nsets, nangles, GRT_RADIANCE_ROWS_PER_ANGLE, self.nw[0]))
 
     def sky_fluxes(self, ncol, nsets):
         """The last six-row run_sky of nsets sets: [ncol][nsets][12], the sets in bit order, each in grt_pipeline_run's

@@ -525,6 +525,39 @@ static inline int grt_jacobian_args_ok(GrtJacobianArgs const *d)
    the solver's own extinctions; jacobian [ncol][V][nw], levels top first, W m-2 K-1 per cm-1. */
 int grt_launch_lw_surface_jacobian(void *stream, GrtLwArgs const *a, double *jacobian);
 
+/* Longwave radiances at viewing angles (grt_pipeline_run_sky_radiances): a kernel of its own, lw_radiance_kernel, beside
+   the solver of a pass, on the pass's GrtLwArgs exactly as that solver gets it (fused form: tau_gas, n_layer and the
+   continua it may have to add; materialised form: the tau, omega the pass has left on the grid).  The four streams of the
+   solver are radiances at the secants -c1[s]; a radiance at secant m is the same recurrence with c1[s] replaced by -m:
+   per grid point t_j = tau_j (1 - omega_j), e_j = exp(min((-m) t_j, 700)), downward from I = 0 with I <- (1 - e_j) P_j +
+   I e_j, the surface I <- emis B(T_surf) + (1 - emis) I, and upward the same step; what leaves is the upward radiance at
+   the top and the downward one at the surface, W m-2 sr-1 per cm-1.  One thread per (grid point, grid row, chunk of up to
+   GRT_RADIANCE_CHUNK angles): the block is GRT_SOLVER_BLOCK, grid row y is the solver instance's (a column, or a column
+   and cloud draw: grt_solver_grid_rows), the chunk is blockIdx.z; a layer's optics and Planck terms are formed once and
+   shared by the chunk's angles, whose intensities stay in registers.  The padding angles of a last chunk repeat the last
+   real secant and write nothing.
+   secant: DEVICE [ncol][angles].  partials: the trapezoid partial sums [slot][angles][2][nblocks] (up at the top, then
+   down at the surface; idle lanes weigh 0), slot = the solver instance's (column, or column x subcolumns + draw; the
+   materialised form: column x subcolumns + draw with this struct's two fields), finished by grt_launch_reduce_partials
+   or grt_launch_subcolumn_mean on angles x 2 rows.  spectral, brightness (either may be NULL; one draw per column only):
+   the radiances and their brightness temperatures T_b = c2 w / log1p(c1 w^3 / I) (planck()'s constants; +0.0 where I <=
+   0) of column c at base + c col_stride + (k 2 + d) nw + i: a wave writes 64 consecutive points of one row. */
+#define GRT_RADIANCE_CHUNK 4
+typedef struct GrtRadianceArgs
+{
+    double const *secant;
+    int angles;
+    int subcolumns, draw;           /* materialised form: the slot is column x subcolumns + draw */
+    double *partials;
+    double *spectral, *brightness;
+    uint64_t col_stride;
+} GrtRadianceArgs;
+static inline int grt_radiance_args_ok(GrtRadianceArgs const *r)
+{
+    return r != NULL && r->secant != NULL && r->angles >= 1 && r->partials != NULL && r->subcolumns >= 1 && r->draw >= 0 &&
+           r->draw < r->subcolumns;
+}
+
 /* Banded profile form of the two profile forms (GRT_OUT_LEVEL_BINS, clear sky or clouds joined;
    grt_pipeline_run_band_profiles): the profile form's arguments, sweeps and park block, but every level's
    flux leaves once per wavenumber bin that has a point in the workgroup's 128 grid points.  A point weights a level's
@@ -638,6 +671,11 @@ static inline int grt_sw_parks(GrtSolverInstance const *in, GrtSwArgs const *a)
    cannot run or has no kernel behind it. */
 int grt_launch_lw(void *stream, GrtSolverInstance const *in, GrtLwArgs const *a);
 int grt_launch_sw(void *stream, GrtSolverInstance const *in, GrtSwArgs const *a);
+/* lw_radiance_kernel (GrtRadianceArgs) beside the longwave solver of instance `in`, on that solver's arguments: the
+   instance's joins select the kernel (none, clouds, aerosols, subcolumns, clouds or subcolumns with aerosols) and its grid
+   rows, a spectral output form (GRT_OUT_CHAINS, GRT_OUT_LAYERS) the materialised one; bins, zeniths, direct and jacobian
+   are not read. */
+int grt_launch_lw_radiances(void *stream, GrtSolverInstance const *in, GrtLwArgs const *a, GrtRadianceArgs const *r);
 /* The subcolumn mean of the partial sums above, in a fixed order: for column c and row r (of `rows` per slot) each
    subcolumn's blocks are added as grt_launch_reduce_partials adds them, then the subcolumns s = 0 .. S - 1 in order, then
    the sum is divided by S; out[c out_stride + out_offset + r].  S = 1 gives grt_launch_reduce_partials' bits. */

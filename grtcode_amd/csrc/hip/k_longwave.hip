@@ -20,7 +20,8 @@
 // GrtAerosolArgs behind either form of the clouds where both join, and a GrtBandArgs last where OUT is per bin; a
 // GrtJacobianArgs last (six rows or every level, with any of the cloud and aerosol joins) makes the instance that also
 // leaves dF_up/dT_surf of its upward sweep (LevelSink: DIRECT, the third row group).  The fused six-row clear-sky
-// instance is the production pipeline's.
+// instance is the production pipeline's.  lw_radiance_kernel, further down, is the radiance at viewing angles beside a
+// pass's solver (grt_launch_lw_radiances): the same recurrence with a stream's c1 replaced by minus the viewing secant.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -35,12 +36,15 @@ constexpr double kMaxExpArg = 700.;   // grtcode_config.h:41
 // the four streams' constants (longwave.c:160-168)
 constexpr double kC1[4] = {-14.402613260847248, -3.0302159969901132, -1.4925584280108841, -1.0746123148178333};
 constexpr double kC2[4] = {0.07587638482015649, 0.676114979733751, 1.3726594476601073, 1.0169418413757783};
+// planck_law's constants (longwave.c:70-71)
+constexpr double kPlanckC1 = 1.1910429526245744e-8;
+constexpr double kPlanckC2 = 1.4387773538277202;
 
 // longwave.c:68-94
 __device__ __forceinline__ double planck(double T, double w)
 {
-    double const c1 = 1.1910429526245744e-8;
-    double const c2 = 1.4387773538277202;
+    double const c1 = kPlanckC1;
+    double const c2 = kPlanckC2;
     double e = c2*w/T;
     if (e > kMaxExpArg)
     {
@@ -54,8 +58,8 @@ __device__ __forceinline__ double planck(double T, double w)
 // expressions: the same B); 0 where planck() clamps x
 __device__ __forceinline__ double planck_dT(double T, double w, double &dbdt)
 {
-    double const c1 = 1.1910429526245744e-8;
-    double const c2 = 1.4387773538277202;
+    double const c1 = kPlanckC1;
+    double const c2 = kPlanckC2;
     double x = c2*w/T;
     bool const clamped = x > kMaxExpArg;
     if (clamped)
@@ -76,15 +80,29 @@ __device__ __forceinline__ double effective_planck(double bc, double be, double 
     return (bc + (a*tau + b*tau*tau)*be)/(1. + a*tau + b*tau*tau);
 }
 
-// extinction of stream s over optical depth tau (longwave.c:177-183)
-__device__ __forceinline__ double extinction(int s, double tau)
+// extinction of a beam over optical depth tau (longwave.c:177-183): c1 is a stream's constant, or minus the secant of
+// a viewing angle
+__device__ __forceinline__ double beam_extinction(double c1, double tau)
 {
-    double e = kC1[s]*tau;
+    double e = c1*tau;
     if (e > kMaxExpArg)
     {
         e = kMaxExpArg;
     }
     return exp(e);
+}
+
+// ... of stream s
+__device__ __forceinline__ double extinction(int s, double tau)
+{
+    return beam_extinction(kC1[s], tau);
+}
+
+// One beam through one layer (longwave.c:193-194): I <- (1 - e) val + I e, e its extinction over the layer
+__device__ __forceinline__ double beam_step(double I, double val, double e)
+{
+    double const p = (1. - e)*val;                                       // longwave.c:193
+    return p + I*e;
 }
 
 // One layer of the four streams (longwave.c:186-195, 204-211): I_s <- (1 - ext_s) val + I_s ext_s; returns the flux
@@ -96,9 +114,7 @@ __device__ __forceinline__ double stream_step(double (&I)[4], double val, Ext ex
 #pragma unroll
     for (int s = 0; s < 4; ++s)
     {
-        double const e = ext(s);
-        double const p = (1. - e)*val;                                   // longwave.c:193
-        I[s] = p + I[s]*e;
+        I[s] = beam_step(I[s], val, ext(s));
         f += kC2[s]*I[s];                                                // longwave.c:195
     }
     return f;
@@ -274,6 +290,138 @@ __global__ __launch_bounds__(kJacobianBlock) void lw_surface_jacobian_kernel(Grt
     }
 }
 
+// ---- radiances at viewing angles (grt_launch_lw_radiances; GrtRadianceArgs, grt_kernels.h) ----
+// A stream of the solver is a radiance at the secant -c1[s]; lw_radiance_kernel carries a chunk of up to kRadianceChunk
+// viewing angles' radiances through the same two sweeps, on the arguments the pass's solver gets: FUSED, the layer optics
+// of the instance's joins formed in registers (LayerOptics, as lw_kernel's), else the tau, omega the pass left on the
+// grid.  A layer's optics and its two Planck terms are formed once per layer and sweep and shared by the chunk's angles;
+// the padding angles of a last chunk repeat its last real secant and write nothing.  What leaves: the upward radiance at
+// the top and the downward one at the surface, as trapezoid partial sums [slot][angles][2][nblocks] (idle lanes of the
+// last block follow along, weight 0) and, where asked for, at every point, with or as brightness temperatures.
+constexpr int kRadianceChunk = GRT_RADIANCE_CHUNK;
+
+// planck() solved for T: c2 w / log1p(c1 w^3 / I); +0.0 where there is no radiance
+__device__ __forceinline__ double brightness_temperature(double I, double w)
+{
+    return I > 0. ? kPlanckC2*w/log1p((kPlanckC1*w*w*w)/I) : 0.;
+}
+
+// the partial sums of a chunk's N real angles: rows (up, down) of angle q at row_base + 2 q
+template <int N>
+__device__ __forceinline__ void radiance_partials(double const (&up)[kRadianceChunk], double const (&dn)[kRadianceChunk],
+                                                  double wt, double *partials, uint64_t row_base)
+{
+    double val[2*N];
+#pragma unroll
+    for (int q = 0; q < N; ++q)
+    {
+        val[2*q] = up[q]*wt;
+        val[2*q + 1] = dn[q]*wt;
+    }
+    block_partials<2*N, kSolverBlock>(val, partials, row_base, gridDim.x, blockIdx.x);
+}
+
+template <bool FUSED, typename... Joins>
+__global__ __launch_bounds__(kSolverBlock) void lw_radiance_kernel(GrtLwArgs a, GrtRadianceArgs r, Joins... joins)
+{
+    static_assert(kRadianceChunk == 4, "the chunk's partial sums are listed for one to four angles");
+    uint64_t const i = (uint64_t)blockIdx.x*kSolverBlock + threadIdx.x;
+    SolverRow const row = solver_row(a.ncol, joins...);
+    int const col = row.col;
+    int const slot = FUSED ? row.slot : col*r.subcolumns + r.draw;
+    bool const live = i < a.nw;
+    uint64_t const ii = live ? i : a.nw - 1;      // (idle lanes of the last block follow along, weight 0)
+    int const V = a.num_levels;
+    int const L = V - 1;
+    double const w = a.w0 + ii*a.dw;                                     // longwave.c:246
+    double const *tau = a.tau + (uint64_t)col*a.optics_stride + ii;
+    double const *omega = (!FUSED && a.omega) ? a.omega + (uint64_t)col*a.optics_stride + ii : nullptr;
+    double const *tl = a.t_layers + (uint64_t)col*L;
+    double const *tv = a.t_levels + (uint64_t)col*V;
+    double const emis = a.emis[(uint64_t)col*a.emis_stride + ii];
+    LayerOptics<FUSED, has_clouds<Joins...>, has<GrtAerosolArgs, Joins...>> const optics(
+        a, pick_clouds(joins...), col, row.tab, ii, pick<GrtAerosolArgs>(joins...));                    // (fused forms)
+
+    // absorption optical depth of layer j: tau (1 - omega)  (longwave.c:252)
+    auto layer_tau = [&](int j) -> double
+    {
+        if (FUSED)
+        {
+            double t, om, gg;
+            optics.at(j, t, om, gg);
+            return t*(1. - om);
+        }
+        uint64_t const o = (uint64_t)j*a.nw;
+        return omega ? tau[o]*(1. - omega[o]) : tau[o]*(1. - 0.);
+    };
+
+    // this chunk's angles: n real ones from `first` on; c1 of angle q is minus its secant
+    int const first = (int)blockIdx.z*kRadianceChunk;
+    int const n = r.angles - first < kRadianceChunk ? r.angles - first : kRadianceChunk;
+    double c1[kRadianceChunk];
+#pragma unroll
+    for (int q = 0; q < kRadianceChunk; ++q)
+    {
+        c1[q] = -r.secant[(uint64_t)col*r.angles + first + (q < n ? q : n - 1)];
+    }
+
+    double I[kRadianceChunk] = {0., 0., 0., 0.};
+    for (int j = 0; j < L; ++j)
+    {
+        double const t = layer_tau(j);
+        double const val = effective_planck(planck(tl[j], w), planck(tv[j + 1], w), t);
+#pragma unroll
+        for (int q = 0; q < kRadianceChunk; ++q)
+        {
+            I[q] = beam_step(I[q], val, beam_extinction(c1[q], t));
+        }
+    }
+    double const down[kRadianceChunk] = {I[0], I[1], I[2], I[3]};
+    surface_step(I, emis, planck(a.t_surf[col], w));                     // (specular: the same angle, longwave.c:202)
+    for (int j = L - 1; j >= 0; --j)
+    {
+        double const t = layer_tau(j);
+        double const val = effective_planck(planck(tl[j], w), planck(tv[j], w), t);
+#pragma unroll
+        for (int q = 0; q < kRadianceChunk; ++q)
+        {
+            I[q] = beam_step(I[q], val, beam_extinction(c1[q], t));
+        }
+    }
+
+    if (live && (r.spectral != nullptr || r.brightness != nullptr))
+    {
+        uint64_t const base = (uint64_t)col*r.col_stride + (uint64_t)(2*first)*a.nw + i;
+#pragma unroll
+        for (int q = 0; q < kRadianceChunk; ++q)
+        {
+            if (q < n)
+            {
+                uint64_t const up_at = base + (uint64_t)(2*q)*a.nw, down_at = up_at + a.nw;
+                if (r.spectral != nullptr)
+                {
+                    r.spectral[up_at] = I[q];
+                    r.spectral[down_at] = down[q];
+                }
+                if (r.brightness != nullptr)
+                {
+                    r.brightness[up_at] = brightness_temperature(I[q], w);
+                    r.brightness[down_at] = brightness_temperature(down[q], w);
+                }
+            }
+        }
+    }
+    double const wt = trapezoid_weight(i, a.nw, a.dw, live);
+    uint64_t const row_base = ((uint64_t)slot*r.angles + first)*2;
+    switch (n)                                                           // (the same in every thread of the workgroup)
+    {
+    case 1: radiance_partials<1>(I, down, wt, r.partials, row_base); break;
+    case 2: radiance_partials<2>(I, down, wt, r.partials, row_base); break;
+    case 3: radiance_partials<3>(I, down, wt, r.partials, row_base); break;
+    default: radiance_partials<4>(I, down, wt, r.partials, row_base); break;
+    }
+}
+
 // ---- spectral form of few columns: the layers' terms first, by one thread per (layer, wavenumber) ----
 // One column of the longwave band is 3 250 threads for lw_kernel<GRT_OUT_CHAINS> -- fifty waves on a thousand SIMDs, each with 120
 // dependent layer steps of six exp.  What costs in a step does not depend on the step before: lw_terms_kernel fills
@@ -391,6 +539,17 @@ int launch(hipStream_t s, GrtSolverInstance const &in, GrtLwArgs const &a, Joins
     return (int)hipGetLastError();
 }
 
+// ... and of lw_radiance_kernel: the instance's grid rows, the chunks of angles along z
+template <bool FUSED, typename... Joins>
+int launch_radiances(hipStream_t s, GrtSolverInstance const &in, GrtLwArgs const &a, GrtRadianceArgs const &r,
+                     Joins const &...joins)
+{
+    dim3 const grid(grt_solver_blocks(a.nw), (unsigned)grt_solver_grid_rows(&in, a.ncol),
+                    (unsigned)((r.angles + kRadianceChunk - 1)/kRadianceChunk));
+    hipLaunchKernelGGL((lw_radiance_kernel<FUSED, Joins...>), grid, dim3(kSolverBlock), 0, s, a, r, joins...);
+    return (int)hipGetLastError();
+}
+
 } // namespace
 
 extern "C" unsigned grt_solver_blocks(uint64_t nw)
@@ -480,4 +639,43 @@ extern "C" int grt_launch_lw_surface_jacobian(void *stream, GrtLwArgs const *a, 
     hipLaunchKernelGGL(lw_surface_jacobian_kernel, dim3((unsigned)((a->nw + kJacobianBlock - 1)/kJacobianBlock), a->ncol, 1),
                        dim3(kJacobianBlock), 0, (hipStream_t)stream, *a, jacobian);
     return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_lw_radiances(void *stream, GrtSolverInstance const *in, GrtLwArgs const *a, GrtRadianceArgs const *r)
+{
+    if (in == nullptr || a == nullptr || !grt_radiance_args_ok(r) || in->zeniths != nullptr || a->ncol < 1 || a->nw < 2 ||
+        a->num_levels < 2 || grt_solver_grid_rows(in, a->ncol) > 65535 || a->t_layers == nullptr || a->t_levels == nullptr ||
+        a->t_surf == nullptr || a->emis == nullptr || (in->clouds != nullptr && in->subcolumns != nullptr) ||
+        (in->clouds != nullptr && !grt_cloud_args_ok(in->clouds)) ||
+        (in->aerosols != nullptr && !grt_aerosol_args_ok(in->aerosols)) ||
+        (in->subcolumns != nullptr && !grt_subcolumn_args_ok(in->subcolumns)))
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipStream_t const s = (hipStream_t)stream;
+    if (!grt_out_fused(in->out))
+    {
+        // the materialised instance: the pass's tau, omega on the grid
+        if (a->tau == nullptr || grt_solver_join(in) != GRT_JOIN_NONE)
+        {
+            return (int)hipErrorInvalidValue;
+        }
+        return launch_radiances<false>(s, *in, *a, *r);
+    }
+    if (a->tau_gas == nullptr || a->n_layer == nullptr)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    // every fused instance of lw_radiance_kernel there is: one per join
+    switch (grt_solver_join(in))
+    {
+    case GRT_JOIN_NONE: return launch_radiances<true>(s, *in, *a, *r);
+    case GRT_JOIN_CLOUDS: return launch_radiances<true>(s, *in, *a, *r, *in->clouds);
+    case GRT_JOIN_AEROSOLS: return launch_radiances<true>(s, *in, *a, *r, *in->aerosols);
+    case GRT_JOIN_SUBCOLUMNS: return launch_radiances<true>(s, *in, *a, *r, *in->subcolumns);
+    case GRT_JOIN_CLOUDS_AEROSOLS: return launch_radiances<true>(s, *in, *a, *r, *in->clouds, *in->aerosols);
+    case GRT_JOIN_SUBCOLUMNS_AEROSOLS: return launch_radiances<true>(s, *in, *a, *r, *in->subcolumns, *in->aerosols);
+    default:
+        return (int)hipErrorInvalidValue;
+    }
 }

@@ -35,6 +35,9 @@
  * out of the same solver launches (instances that leave it too), or -- materialised form -- formed from each set's optics.
  * grt_pipeline_run_sky_jacobian is its longwave counterpart, by the same route: the derivative of every set's upward
  * longwave flux with respect to the surface temperature beside the set's rows.
+ * grt_pipeline_run_sky_radiances is its six-row form with the longwave radiances at viewing angles of every set, from a
+ * kernel of their own queued behind each set's longwave solver -- or, without flux rows, in its place: then the shortwave
+ * band is not touched at all.
  * grt_pipeline_run_sky_zeniths is grt_pipeline_run_sky with the shortwave of every set solved under several sun angles per
  * column, as grt_pipeline_run_zeniths solves the clean set's: one gas-optics launch per band, one set of cloud draws.
  * grt_pipeline_run_band_profiles runs the profile form of the clear-sky pass and, with clouds, of the all-sky pass with
@@ -271,6 +274,7 @@ static void grt_pipeline_release(GrtPipeline_t **pipeline)
         grt_keyed_table_free(p, &p->band[b].bin_table);
         grt_keyed_table_free(p, &p->band[b].surf_map);
     }
+    grt_staging_free(p, &p->rad);
     grt_staging_free(p, &p->zen);
     grt_staging_free(p, &p->surf);
     grt_staging_free(p, &p->aer);
@@ -490,6 +494,8 @@ typedef struct GrtJoin
     unsigned sets;
     GrtZeniths_t const *zeniths;       /* grt_pipeline_run_zeniths, _run_sky_zeniths: every set's shortwave is the mean over
                                           these angles; with `sets`, the per-angle outputs hold every set's */
+    GrtRadiances_t const *radiances;   /* grt_pipeline_run_sky_radiances: every set's longwave leaves its radiances at these
+                                          viewing angles too; rows->out NULL: and nothing else runs */
 } GrtJoin;
 
 #define GRT_SKY_ALL (GRT_SKY_CLEAN | GRT_SKY_AEROSOL | GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL)
@@ -532,7 +538,8 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
         GRT_FAIL(GRTCODE_VALUE_ERR, "%d columns asked for, the surface in force (grt_pipeline_set_surface) has %d.",
                  cols->ncol, p->surface_ncol);
     }
-    GRT_TRY(stage_columns(p, cols, join->zeniths != NULL));
+    int const radiances_only = join->radiances != NULL && rows->out == NULL;
+    GRT_TRY(stage_columns(p, cols, join->zeniths != NULL || radiances_only));
     int const C = cols->ncol, S = join->subcolumns > 0 ? join->subcolumns : 1;
     unsigned const sets = join_sets(join);
     GrtZenithRun zr;
@@ -540,6 +547,11 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
     {
         GRT_TRY(grt_stage_zeniths(p, join->zeniths, C, &zr));
         zr.sky = join->sets != 0;
+    }
+    GrtRadianceRun rr;
+    if (join->radiances != NULL && p->band[0].gas != NULL)
+    {
+        GRT_TRY(grt_stage_radiances(p, join->radiances, C, &rr));
     }
     if (cl != NULL && join->sampler != NULL)
     {
@@ -558,7 +570,14 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
     for (int bi = 0; bi < 2; ++bi)
     {
         GrtBand *b = &p->band[bi];
-        if (rows->out == NULL && (bi == 0 || b->gas == NULL))
+        if (radiances_only)
+        {
+            if (bi == 1 || b->gas == NULL)
+            {
+                continue;              /* (grt_pipeline_run_sky_radiances for the radiances alone: no shortwave at all) */
+            }
+        }
+        else if (rows->out == NULL && (bi == 0 || b->gas == NULL))
         {
             continue;                  /* (grt_pipeline_run_zeniths for the angles' own rows alone: no longwave, no mean) */
         }
@@ -592,6 +611,7 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
         }
         GrtContinua continua;
         GrtPass ps = *rows;
+        ps.radiances = bi == 0 && join->radiances != NULL ? &rr : NULL;
         GrtAerosolArgs aa;
         int const band_aer = ae != NULL && grt_aerosol_points(ae, bi) > 0;
         int aa_ready = 0;
@@ -1145,6 +1165,49 @@ EXTERN int grt_pipeline_run_sky_jacobian(GrtPipeline_t *p, GrtColumns_t const *c
                             "jacobian_level_fluxes_dev", jacobian != NULL ? jacobian->jacobian_fluxes_dev : NULL,
                             jacobian != NULL ? jacobian->jacobian_level_fluxes_dev : NULL, jacobian == NULL};
     GRT_TRY(run_sky(p, cols, sky, &third, level_fluxes_dev, heating_dev, fluxes_dev));
+    return GRTCODE_SUCCESS;
+}
+
+/* grt_ext.h: grt_pipeline_run_sky's six-row form, and the longwave radiances of every set at the columns' viewing angles;
+   fluxes_dev NULL: the radiances alone */
+EXTERN int grt_pipeline_run_sky_radiances(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky,
+                                          GrtRadiances_t const *rd, fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    if (rd == NULL || rd->radiances_dev == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%s is NULL: the radiances [ncol][sets][angles][%d] are the output.",
+                 rd == NULL ? "radiances (GrtRadiances_t)" : "radiances_dev", GRT_RADIANCE_ROWS_PER_ANGLE);
+    }
+    int nsets;
+    GRT_TRY(check_sky_sets(sky, &nsets));
+    GrtAerosols_t a;
+    GrtJoin join;
+    GRT_TRY(sky_join(p, cols, sky, &a, &join));
+    GRT_TRY(grt_check_radiances(rd, cols->ncol));
+    int const spectral = rd->spectral_radiances_dev != NULL || rd->brightness_dev != NULL;
+    if (spectral && join.subcolumns > 0)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%s is given with a cloud set of %d draws: the radiances at every point are those of one "
+                 "draw per column.", rd->spectral_radiances_dev != NULL ? "spectral_radiances_dev" : "brightness_dev",
+                 join.subcolumns);
+    }
+    join.radiances = rd;
+    GrtPass rows;
+    memset(&rows, 0, sizeof(rows));
+    rows.out = fluxes_dev;
+    rows.sets = nsets;
+    rows.out_stride = nsets*grt_set_offset(p, 0);
+    GRT_TRY(pipeline_run(p, cols, &join, &rows));
+    if (p->band[0].gas == NULL)
+    {
+        /* no longwave band: zeros, as the band's rows are */
+        void *s = grt_dev_stream(p->device);
+        size_t const rows_all = (size_t)cols->ncol*(size_t)nsets*(size_t)rd->num_angles*GRT_RADIANCE_ROWS_PER_ANGLE;
+        GRT_TRY(grt_dev_zero(p->device, rd->radiances_dev, sizeof(double)*rows_all, s));
+        /* (a spectral row of such a pipeline has no points) */
+    }
     return GRTCODE_SUCCESS;
 }
 

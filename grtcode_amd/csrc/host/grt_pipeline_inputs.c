@@ -82,6 +82,46 @@ int grt_stage_zeniths(GrtPipeline_t *p, GrtZeniths_t const *zn, int C, GrtZenith
     return GRTCODE_SUCCESS;
 }
 
+/* grt_pipeline_run_sky_radiances' checks of the viewing angles of a batch of C columns: how many, and every secant finite
+   and at least 1 (nothing is touched) */
+int grt_check_radiances(GrtRadiances_t const *rd, int C)
+{
+    if (rd->num_angles < 1 || rd->num_angles > GRT_MAX_VIEW_ANGLES)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d viewing angles per column asked for: 1 to %d.", rd->num_angles, GRT_MAX_VIEW_ANGLES);
+    }
+    if (rd->view_secant == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "view_secant is NULL: the viewing secants [ncol][%d] are the input.", rd->num_angles);
+    }
+    size_t const n = (size_t)C*(size_t)rd->num_angles;
+    for (size_t k = 0; k < n; ++k)
+    {
+        /* (a NaN fails the first comparison, an infinity the second) */
+        if (!(rd->view_secant[k] >= 1.) || !(rd->view_secant[k] <= 1.79769313486231570815e+308))
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "secant of viewing angle %zu of column %zu (%e) is NaN, infinite or below 1.",
+                     k % (size_t)rd->num_angles, k/(size_t)rd->num_angles, rd->view_secant[k]);
+        }
+    }
+    return GRTCODE_SUCCESS;
+}
+
+/* The viewing secants of a batch (grt_pipeline_run_sky_radiances) into p->rad and onto the device, [C][A] */
+int grt_stage_radiances(GrtPipeline_t *p, GrtRadiances_t const *rd, int C, GrtRadianceRun *rr)
+{
+    size_t const n = (size_t)C*(size_t)rd->num_angles;
+    GRT_TRY(grt_staging_reserve(p, &p->rad, n, (size_t)p->max_cols*GRT_MAX_VIEW_ANGLES));
+    memcpy(p->rad.h, rd->view_secant, sizeof(double)*n);
+    GRT_TRY(grt_staging_upload(p, &p->rad, n));
+    rr->angles = rd->num_angles;
+    rr->secant = p->rad.d;
+    rr->integrated = rd->radiances_dev;
+    rr->spectral = rd->spectral_radiances_dev;
+    rr->brightness = rd->brightness_dev;
+    return GRTCODE_SUCCESS;
+}
+
 /* t->table for `key`: as it is when it was built for the same bytes, else `ints` ints written by fill(ctx, .) on the host
    and uploaded.  The stored key is dropped before the device table is touched and set again only when the whole call
    succeeded, so a failure half way leaves a table that the next call rebuilds, whatever its key. */

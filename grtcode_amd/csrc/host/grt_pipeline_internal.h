@@ -69,6 +69,9 @@ enum
     GRT_SCRATCH_DIRECT_SUM,
     /* ... profile form without direct_level_fluxes_dev: [max_cols][GRT_SKY_MAX_SETS][V] the levels its three rows come from */
     GRT_SCRATCH_DIRECT_LEVELS,
+    /* grt_pipeline_run_sky_radiances, longwave, both forms: [max_cols][S][A][2][nblocks] partial sums of the radiances of
+       every angle and cloud draw, S = 1 but in a cloud set of several draws; sized at the first call that needs more */
+    GRT_SCRATCH_RADIANCE_PARTIALS,
     GRT_SCRATCH_COUNT
 };
 
@@ -130,6 +133,8 @@ struct GrtPipeline
     /* grt_pipeline_run_zeniths' angles: cos_zenith [cols][Z], the weights [cols][Z], then -- materialised form -- the
        cosines angle-major [Z][cols], night samples replaced by a day angle of their column */
     GrtStaging zen;
+    /* grt_pipeline_run_sky_radiances' viewing secants [cols][A] */
+    GrtStaging rad;
     int surface_ncol;      /* columns of the surface in force; 0: none (the creation-time arrays apply) */
 };
 
@@ -142,6 +147,16 @@ typedef struct GrtBins
     int const *edges[2];
     int num_bins[2];
 } GrtBins;
+
+/* The viewing angles of a grt_pipeline_run_sky_radiances call, staged (grt_stage_radiances): A secants per column on the
+   device, and where every set's radiances go. */
+typedef struct GrtRadianceRun
+{
+    int angles;
+    double const *secant;          /* DEVICE [ncol][A] */
+    double *integrated;            /* DEVICE [ncol][sets][A][2] */
+    double *spectral, *brightness; /* DEVICE [ncol][sets][A][2][n], or NULL */
+} GrtRadianceRun;
 
 /* One solve of a band on the run's tau_gas.  What joins gas and Rayleigh: nothing (clear sky), the cloud objects (all-sky
    pass), the aerosol object (aerosol pass; aer NULL there: a band that was given no aerosol, which runs the form without
@@ -167,6 +182,9 @@ typedef struct GrtPass
     double *direct;
     /* grt_pipeline_run_sky_jacobian (NULL: not asked for): the longwave's dF_up/dT_surf leaves too, laid out as direct is */
     double *jacobian;
+    /* grt_pipeline_run_sky_radiances (NULL: not asked for): the longwave's radiance kernel is queued behind the pass's
+       solver -- out NULL: in its place --, the pass's to set `set` of each output */
+    GrtRadianceRun const *radiances;
 } GrtPass;
 
 /* The sun angles of a grt_pipeline_run_zeniths or grt_pipeline_run_sky_zeniths call, staged (grt_stage_zeniths): Z per column, their cosines and weights
@@ -214,6 +232,8 @@ GRT_PRIVATE int grt_check_grid(char const *name, char const *kind, char const *n
 GRT_PRIVATE int grt_check_surface(GrtPipeline_t const *p, GrtSurface_t const *sf, int np[2]);
 GRT_PRIVATE int grt_stage_surface(GrtPipeline_t *p, GrtSurface_t const *sf, int const np[2]);
 GRT_PRIVATE int grt_stage_zeniths(GrtPipeline_t *p, GrtZeniths_t const *zn, int C, GrtZenithRun *zr);
+GRT_PRIVATE int grt_check_radiances(GrtRadiances_t const *rd, int C);
+GRT_PRIVATE int grt_stage_radiances(GrtPipeline_t *p, GrtRadiances_t const *rd, int C, GrtRadianceRun *rr);
 GRT_PRIVATE int grt_band_bins(GrtPipeline_t *p, GrtBand *b, int const *edges, int nbins, int rows);
 
 /* grt_pipeline_solve.c */

@@ -252,6 +252,79 @@ static int band_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass cons
     return GRTCODE_SUCCESS;
 }
 
+/* whether band bi's solve of the pass leaves radiances too (grt_pipeline_run_sky_radiances: the longwave's) */
+static int pass_radiances(GrtPass const *ps, int bi)
+{
+    return bi == 0 && ps->radiances != NULL;
+}
+
+/* The pass's radiance launch (GRT_TAG_RADIANCE), queued behind its longwave solver -- or, a pass without flux rows, in its
+   place -- on that solver's instance and arguments (pass_instance, solver_args: the continua it may have to add
+   included).  Its partial sums go to GRT_SCRATCH_RADIANCE_PARTIALS, [max_cols][S][A][2][nblocks]; the spectral outputs,
+   where given, to the pass's set of [ncol][sets][A][2][n].  Fused form: sc, the pass's clouds as its subcolumns (NULL:
+   S = 1), walked in groups of grid rows as the solver's launches are; materialised form: the tau, omega left on the
+   grid, draw `draw` of S. */
+static int band_radiances(GrtPipeline_t *p, GrtBand *b, int C, int S, int draw, GrtPass const *ps, GrtSubcolumnArgs *sc)
+{
+    GrtRadianceRun const *rr = ps->radiances;
+    void *s = grt_dev_stream(p->device);
+    size_t const per_slot = (size_t)rr->angles*GRT_RADIANCE_ROWS_PER_ANGLE;
+    GrtScratch *block = &b->scratch[GRT_SCRATCH_RADIANCE_PARTIALS];
+    /* (the kernel's own blocks along the spectrum: the materialised form keeps no b->nblocks) */
+    GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*(size_t)S*per_slot*grt_solver_blocks(b->n), NULL));
+    GrtSolverInstance const in = pass_instance(p, ps, NULL, sc, NULL, 0);
+    SolverArgs a;
+    GRT_TRY(solver_args(p, b, 0, C, ps, &in, NULL, &a));
+    size_t const set_doubles = per_slot*b->n;
+    GrtRadianceArgs r;
+    memset(&r, 0, sizeof(r));
+    r.secant = rr->secant; r.angles = rr->angles; r.subcolumns = S; r.draw = draw; r.partials = block->d;
+    r.spectral = rr->spectral != NULL ? rr->spectral + (size_t)ps->set*set_doubles : NULL;
+    r.brightness = rr->brightness != NULL ? rr->brightness + (size_t)ps->set*set_doubles : NULL;
+    r.col_stride = (uint64_t)ps->sets*set_doubles;
+    int const slot = grt_profile_begin(s, GRT_TAG_RADIANCE);
+    int krc = 0;
+    if (sc != NULL)
+    {
+        int const group = 65535/C < S ? 65535/C : S;                  /* (grid rows) */
+        for (sc->first = 0; sc->first < S && krc == 0; sc->first += group)
+        {
+            sc->count = S - sc->first < group ? S - sc->first : group;
+            krc = grt_launch_lw_radiances(s, &in, &a.lw, &r);
+        }
+    }
+    else
+    {
+        krc = grt_launch_lw_radiances(s, &in, &a.lw, &r);
+    }
+    grt_profile_end(s, slot);
+    GRT_TRY(grt_dev_check(krc, "longwave radiance kernel"));
+    return GRTCODE_SUCCESS;
+}
+
+/* ... and what turns the partial sums of its S draws into the pass's set of the integrated radiances [ncol][sets][A][2]:
+   the fixed-order sum of the blocks, or -- S > 1 -- the subcolumn mean kernel (draws 0 .. S - 1 in order, one division) */
+static int finish_radiances(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass const *ps)
+{
+    GrtRadianceRun const *rr = ps->radiances;
+    void *s = grt_dev_stream(p->device);
+    int const rows = rr->angles*GRT_RADIANCE_ROWS_PER_ANGLE;
+    double const *partials = b->scratch[GRT_SCRATCH_RADIANCE_PARTIALS].d;
+    unsigned const nblocks = grt_solver_blocks(b->n);
+    if (S == 1)
+    {
+        GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, partials, C*rows, nblocks, rr->integrated, rows,
+                                                         ps->sets*rows, ps->set*rows), "radiance reduction kernel"));
+        return GRTCODE_SUCCESS;
+    }
+    int const mslot = grt_profile_begin(s, GRT_TAG_SUBCOLUMN_MEAN);
+    int const mrc = grt_launch_subcolumn_mean(s, partials, C, S, rows, nblocks, rr->integrated, ps->sets*rows,
+                                              ps->set*rows);
+    grt_profile_end(s, mslot);
+    GRT_TRY(grt_dev_check(mrc, "subcolumn mean kernel"));
+    return GRTCODE_SUCCESS;
+}
+
 /* Rayleigh + add_optics({gas, rayleigh}) (driver.c:268, 382-383) into the band's tau, omega, g */
 static int clear_sky_optics(GrtPipeline_t *p, GrtBand *b, int C)
 {
@@ -523,34 +596,51 @@ int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *p
     if (p->keep_spectra)
     {
         GRT_TRY(pass_optics(p, b, C, ps));
-        GRT_TRY(band_solver(p, b, bi, C, ps, NULL, NULL, NULL));
-        GRT_TRY(integrate_rows(p, b, bi, C, ps));
+        if (ps->out != NULL)
+        {
+            GRT_TRY(band_solver(p, b, bi, C, ps, NULL, NULL, NULL));
+            GRT_TRY(integrate_rows(p, b, bi, C, ps));
+        }
         if (pass_direct(ps, bi))
         {
             GRT_TRY(direct_beam(p, b, bi, C, ps));
             GRT_TRY(direct_integrate(p, b, bi, C, ps));
         }
+        if (pass_radiances(ps, bi))
+        {
+            GRT_TRY(band_radiances(p, b, C, 1, 0, ps, NULL));
+            GRT_TRY(finish_radiances(p, b, C, 1, ps));
+        }
         return GRTCODE_SUCCESS;
     }
-    int const rows = pass_rows(p, ps);
-    ThirdRows da;
-    GRT_TRY(direct_partials(p, b, bi, ps, 1, &da));
-    if (ps->profile)
+    if (ps->out != NULL)
     {
-        GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_LEVEL_PARTIALS], (size_t)p->max_cols*(size_t)rows*b->nblocks,
-                                 NULL));
+        int const rows = pass_rows(p, ps);
+        ThirdRows da;
+        GRT_TRY(direct_partials(p, b, bi, ps, 1, &da));
+        if (ps->profile)
+        {
+            GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_LEVEL_PARTIALS], (size_t)p->max_cols*(size_t)rows*b->nblocks,
+                                     NULL));
+        }
+        double *partials = ps->profile ? b->scratch[GRT_SCRATCH_LEVEL_PARTIALS].d : b->partials;
+        GRT_TRY(band_solver(p, b, bi, C, ps, partials, NULL, &da));
+        GRT_TRY(grt_dev_check(grt_launch_reduce_partials(grt_dev_stream(p->device), partials, C*rows, b->nblocks, ps->out,
+                                                         rows, ps->out_stride, pass_offset(p, ps, bi)),
+                              "flux reduction kernel"));
+        if (da.partials != NULL)
+        {
+            int const drows = direct_rows(p, ps);
+            GRT_TRY(grt_dev_check(grt_launch_reduce_partials(grt_dev_stream(p->device), da.partials, C*drows, b->nblocks,
+                                                             third_out(ps, bi), drows, direct_stride(p, ps),
+                                                             direct_offset(p, ps)),
+                                  bi == 1 ? "direct-beam reduction kernel" : "surface Jacobian reduction kernel"));
+        }
     }
-    double *partials = ps->profile ? b->scratch[GRT_SCRATCH_LEVEL_PARTIALS].d : b->partials;
-    GRT_TRY(band_solver(p, b, bi, C, ps, partials, NULL, &da));
-    GRT_TRY(grt_dev_check(grt_launch_reduce_partials(grt_dev_stream(p->device), partials, C*rows, b->nblocks, ps->out, rows,
-                                                     ps->out_stride, pass_offset(p, ps, bi)), "flux reduction kernel"));
-    if (da.partials != NULL)
+    if (pass_radiances(ps, bi))
     {
-        int const drows = direct_rows(p, ps);
-        GRT_TRY(grt_dev_check(grt_launch_reduce_partials(grt_dev_stream(p->device), da.partials, C*drows, b->nblocks,
-                                                         third_out(ps, bi), drows, direct_stride(p, ps),
-                                                         direct_offset(p, ps)),
-                              bi == 1 ? "direct-beam reduction kernel" : "surface Jacobian reduction kernel"));
+        GRT_TRY(band_radiances(p, b, C, 1, 0, ps, NULL));
+        GRT_TRY(finish_radiances(p, b, C, 1, ps));
     }
     return GRTCODE_SUCCESS;
 }
@@ -566,6 +656,14 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
 {
     int const V = p->num_levels, rows = pass_rows(p, ps), out_offset = pass_offset(p, ps, bi);
     void *s = grt_dev_stream(p->device);
+    if (!p->keep_spectra && ps->out == NULL)
+    {
+        /* (grt_pipeline_run_sky_radiances without flux rows: the radiance kernel in the solver's place) */
+        GrtSubcolumnArgs sc = {*ps->clouds, S, 0, 0};
+        GRT_TRY(band_radiances(p, b, C, S, 0, ps, &sc));
+        GRT_TRY(finish_radiances(p, b, C, S, ps));
+        return GRTCODE_SUCCESS;
+    }
     if (!p->keep_spectra)
     {
         GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_SUB_PARTIALS],
@@ -591,6 +689,11 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
         }
         grt_profile_end(s, slot);
         GRT_TRY(grt_dev_check(krc, bi == 0 ? "longwave subcolumn kernel" : "shortwave subcolumn kernel"));
+        if (pass_radiances(ps, bi))
+        {
+            GRT_TRY(band_radiances(p, b, C, S, 0, ps, &sc));
+            GRT_TRY(finish_radiances(p, b, C, S, ps));
+        }
         if (S == 1)
         {
             GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, sub_partials, C*rows, b->nblocks, ps->out, rows,
@@ -632,6 +735,14 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
         GrtPass pj = *ps;
         pj.clouds = &cj;
         GRT_TRY(pass_optics(p, b, C, &pj));
+        if (pass_radiances(ps, bi))
+        {
+            GRT_TRY(band_radiances(p, b, C, S, j, &pj, NULL));
+        }
+        if (ps->out == NULL)
+        {
+            continue;
+        }
         GRT_TRY(band_solver(p, b, bi, C, &pj, NULL, NULL, NULL));
         GRT_TRY(grt_dev_check(grt_launch_flux_accumulate(s, per, b->flux_up, flux_sum, j == 0), "flux sum kernel"));
         GRT_TRY(grt_dev_check(grt_launch_flux_accumulate(s, per, b->flux_down, flux_sum + all, j == 0),
@@ -642,6 +753,14 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
             GRT_TRY(grt_dev_check(grt_launch_flux_accumulate(s, per, b->scratch[GRT_SCRATCH_DIRECT_BEAM].d, direct_sum,
                                                              j == 0), "flux sum kernel"));
         }
+    }
+    if (pass_radiances(ps, bi))
+    {
+        GRT_TRY(finish_radiances(p, b, C, S, ps));
+    }
+    if (ps->out == NULL)
+    {
+        return GRTCODE_SUCCESS;
     }
     GRT_TRY(grt_dev_check(grt_launch_flux_mean(s, per, flux_sum, S, b->flux_up), "flux mean kernel"));
     GRT_TRY(grt_dev_check(grt_launch_flux_mean(s, per, flux_sum + all, S, b->flux_down), "flux mean kernel"));

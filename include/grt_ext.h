@@ -530,6 +530,53 @@ EXTERN int grt_pipeline_run_sky_jacobian(GrtPipeline_t *pipeline, GrtColumns_t c
                                          GrtSurfaceJacobian_t const *jacobian,
                                          fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev);
 
+/* ---- longwave radiances at viewing angles, of every sky set ----------------------------------------------------------
+ * grt_pipeline_run_sky's six-row form in every respect -- the sets and their packing order (N =
+ * grt_pipeline_sky_set_count(sets)), the surface in force (a radiance takes that column's emissivity row), the input checks,
+ * asynchronous on the pipeline's lane -- and with it the radiance an instrument sees along one line of sight: per column
+ * A viewing angles, given as secants m = 1/cos(viewing zenith angle), and per angle two rows: the upward radiance at the
+ * top of the atmosphere (a sounder's spectrum) and the downward radiance at the surface (an upward-looking
+ * interferometer's).  The definition is the reference's own longwave recurrence: its four streams are radiances at the
+ * Gauss-Legendre secants -c1[s] (longwave.c:160-168), and a radiance at secant m is the same recurrence with c1[s]
+ * replaced by -m.  Per grid point w, with t_j = tau_j (1 - omega_j) (longwave.c:252) and e_j = exp(min((-m) t_j, 700)):
+ *   downward from the top, I = 0, then for j = 0 .. L - 1: I <- (1 - e_j) P_j + I e_j, P_j = effective_planck(B(T_layer j),
+ *   B(T_level j + 1), t_j): after the last layer I is the downward radiance at the surface;
+ *   the surface, I <- emis B(T_surf) + (1 - emis) I (longwave.c:202: specular reflection of the same angle);
+ *   upward for j = L - 1 .. 0 with P_j from T_level j: after layer 0 I is the upward radiance at the top.
+ * Units: W m-2 sr-1 per cm-1, what planck_law returns; integrated over the band with the same trapezoid as every other
+ * row: W m-2 sr-1.  Radiances at the four secants -c1[s], weighted ((0 + c2[0] R_0) + c2[1] R_1) + c2[2] R_2) + c2[3] R_3,
+ * are the solver's flux at that point, bit for bit.  The brightness temperature of a point is T_b = c2 w / log1p(c1 w^3 /
+ * I) with planck_law's constants, +0.0 where I <= 0.
+ *   radiances_dev          [ncol][N][A][2] (required): band-integrated, up at the top then down at the surface;
+ *   spectral_radiances_dev [ncol][N][A][2][n_lw] (may be NULL): the same at every grid point of the longwave band;
+ *   brightness_dev         [ncol][N][A][2][n_lw] (may be NULL): their brightness temperatures, K.
+ * fluxes_dev is grt_pipeline_run_sky's [ncol][N][12], or NULL: then no flux solver and no shortwave gas optics run at all,
+ * only the longwave gas optics and the radiance kernel (a satellite simulation), columns->cos_zenith is not read and a
+ * night column is not an error.  A cloud set's integrated radiance is the mean over its num_subcolumns draws, taken as
+ * the other rows take theirs: draws 0 .. S - 1 in order, then one division by S.  A pipeline without a longwave band
+ * writes zeros to every radiance output.  The radiances come from a kernel of their own (GRT_TAG_RADIANCE), queued behind
+ * each set's longwave solver (with fluxes_dev NULL: in its place) on the solver's own arguments; in the deterministic mode
+ * every output grt_pipeline_run_sky also writes is grt_pipeline_run_sky's, bit for bit, and an angle's values do not
+ * depend on the other angles of the call.  GRTCODE_VALUE_ERR, with nothing launched and every output untouched, for:
+ * radiances NULL; radiances_dev NULL; view_secant NULL; num_angles outside 1 .. GRT_MAX_VIEW_ANGLES; a secant that is
+ * NaN, infinite or below 1; a spectral or brightness output together with a cloud set at num_subcolumns > 1; everything
+ * grt_pipeline_run_sky refuses.
+ * Not covered: spectral and brightness outputs of cloud sets with more than one draw, the profile form and radiances at
+ * interior levels, per-bin radiances, instrument line-shape convolution, shortwave (scattered solar) radiances, and cloud
+ * fields sampled on the device. */
+#define GRT_MAX_VIEW_ANGLES 16
+#define GRT_RADIANCE_ROWS_PER_ANGLE 2      /* upward at the top of the atmosphere, downward at the surface */
+typedef struct GrtRadiances
+{
+    int num_angles;                     /* A, 1 .. GRT_MAX_VIEW_ANGLES */
+    fp_t const *view_secant;            /* HOST [ncol][A]: 1/cos(viewing zenith angle), finite and >= 1 */
+    fp_t *radiances_dev;                /* DEVICE [ncol][N][A][2], band-integrated, W m-2 sr-1; required */
+    fp_t *spectral_radiances_dev;       /* DEVICE [ncol][N][A][2][n_lw], per cm-1; may be NULL */
+    fp_t *brightness_dev;               /* DEVICE [ncol][N][A][2][n_lw], K; may be NULL */
+} GrtRadiances_t;
+EXTERN int grt_pipeline_run_sky_radiances(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtSky_t const *sky,
+                                          GrtRadiances_t const *radiances, fp_t *fluxes_dev);
+
 /* ---- spectral and band-integrated fluxes ---------------------------------------------------------------------------
  * driver.c's output without -integrated (output_fluxes, driver.c:285-356): the six rows of grt_pipeline_run at EVERY grid
  * point, and -- where the caller gives bin edges -- the same rows integrated over wavenumber bins, for a batch of columns,
@@ -806,7 +853,9 @@ enum
     GRT_TAG_SKY_ZENITH_MEAN = 23,
     /* 24 = the Jacobian kernel of grt_pipeline_run_sky_jacobian's materialised form (every set's, every subcolumn's; the
        fused instances count under grt_pipeline_run_sky's tags) */
-    GRT_TAG_SURFACE_JACOBIAN = 24
+    GRT_TAG_SURFACE_JACOBIAN = 24,
+    /* 25 = the radiance kernel of grt_pipeline_run_sky_radiances (every set's, every draw's, in both forms) */
+    GRT_TAG_RADIANCE = 25
 };
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
