@@ -29,7 +29,7 @@ GRT_CLOUD_PHASE, GRT_CLOUD_MODEL, GRT_CLOUD_FIELDS = 7, 8, 9   # ... of GrtCloud
 (TAG_GAS_LW, TAG_GAS_SW, TAG_SOLVER_LW, TAG_SOLVER_SW, TAG_CLEAR_OPTICS, TAG_FAR_LW, TAG_FAR_SW, TAG_ALLSKY_LW,
  TAG_ALLSKY_SW, TAG_BINS, TAG_SUBCOLUMN_MEAN, TAG_AEROSOL_LW, TAG_AEROSOL_SW, TAG_BAND_PROFILES, TAG_SURFACE,
  TAG_CLOUD_SAMPLER, TAG_SKY_LW, TAG_SKY_SW, TAG_ZENITH_SW, TAG_ZENITH_MEAN, TAG_DIRECT_BEAM, TAG_SKY_ZENITH_SW,
- TAG_SKY_ZENITH_MEAN, TAG_SURFACE_JACOBIAN, TAG_RADIANCE) = range(1, 26)
+ TAG_SKY_ZENITH_MEAN, TAG_SURFACE_JACOBIAN, TAG_RADIANCE, TAG_CHANNELS) = range(1, 27)
 TAG_FAR_OFFSET = TAG_FAR_LW - TAG_GAS_LW    # from a line kernel's tag to its far-field gather's
 CLOUD_SAMPLER_TAG = TAG_CLOUD_SAMPLER
 GRT_MAX_SUBCOLUMNS = 64             # grt_pipeline_run_subcolumns: subcolumns per column, 1 .. this
@@ -43,6 +43,7 @@ GRT_DIRECT_ROWS_PER_SET = 3         # grt_pipeline_run_sky_direct: the direct be
 GRT_JACOBIAN_ROWS_PER_SET = 3       # grt_pipeline_run_sky_jacobian: dF_up/dT_surf at TOA, surface, user level
 GRT_MAX_VIEW_ANGLES = 16            # grt_pipeline_run_sky_radiances: viewing angles per column, 1 .. this
 GRT_RADIANCE_ROWS_PER_ANGLE = 2     # ... per angle: upward at the top of the atmosphere, downward at the surface
+GRT_MAX_CHANNELS = 16384            # grt_pipeline_run_sky_channels: channels of an instrument, 1 .. this
 RETURN_CODES = ["GRTCODE_SUCCESS", "GRTCODE_INVALID_ERR", "GRTCODE_DIVBYZERO_ERR", "GRTCODE_OVERFLOW_ERR",
                 "GRTCODE_UNDERFLOW_ERR", "GRTCODE_SENTINEL_ERR", "GRTCODE_NULL_ERR", "GRTCODE_NON_NULL_ERR",
                 "GRTCODE_RANGE_ERR", "GRTCODE_VALUE_ERR", "GRTCODE_COMPILER_ERR", "GRTCODE_IO_ERR",
@@ -196,6 +197,12 @@ class GrtRadiances(C.Structure):
                 ("spectral_radiances_dev", C.c_void_p), ("brightness_dev", C.c_void_p)]
 
 
+class GrtChannels(C.Structure):
+    _fields_ = [("num_channels", C.c_int), ("first", C.POINTER(C.c_int)), ("offset", C.POINTER(C.c_int)),
+                ("weights", c_double_p), ("center", c_double_p), ("channel_radiances_dev", C.c_void_p),
+                ("channel_brightness_dev", C.c_void_p)]
+
+
 class GrtZeniths(C.Structure):
     _fields_ = [("num_zeniths", C.c_int), ("cos_zenith", c_double_p), ("weight", c_double_p),
                 ("zenith_fluxes_dev", C.c_void_p), ("zenith_level_fluxes_dev", C.c_void_p)]
@@ -222,7 +229,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_zeniths grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_channels grt_channel_pair_count grt_pipeline_run_sky_zeniths grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -288,6 +295,11 @@ def load_library(path=None):
     if hasattr(lib, "grt_pipeline_run_sky_radiances"):   # (GRT_LIB_PATH may name an older library: a timing yardstick)
         lib.grt_pipeline_run_sky_radiances.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky),
                                                        C.POINTER(GrtRadiances), C.c_void_p]
+    if hasattr(lib, "grt_pipeline_run_sky_channels"):    # (GRT_LIB_PATH may name an older library: a timing yardstick)
+        lib.grt_pipeline_run_sky_channels.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky),
+                                                      C.POINTER(GrtRadiances), C.POINTER(GrtChannels), C.c_void_p]
+        lib.grt_channel_pair_count.argtypes = [C.POINTER(GrtChannels), C.c_longlong]
+        lib.grt_channel_pair_count.restype = C.c_longlong
     lib.grt_pipeline_sky_set_count.argtypes = [C.c_uint]
     if hasattr(lib, "grt_pipeline_run_zeniths"):    # (GRT_LIB_PATH may name an older library: a timing yardstick)
         lib.grt_pipeline_run_zeniths.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtZeniths), C.c_void_p,
@@ -778,6 +790,37 @@ def make_zeniths(cos_zenith, weight=None):
     return gz, keep
 
 
+def make_channels(first, weights_per_channel, center=None):
+    """Pack an instrument's channels into a GrtChannels struct (+ keep-alive arrays) for Pipeline.run_sky_channels and
+    channel_pair_count.  first [C]: the grid index of each channel's first point in the longwave band; weights_per_channel:
+    a list of C arrays, each channel's spectral response sampled on the grid from that point on (channels.gaussian and
+    channels.boxcar make both); center [C] cm-1 or None: the weighted centroid.  The two output pointers are
+    Pipeline.run_sky_channels' to set.  keep["counts"] is the points per channel."""
+    per = [_f64(w).ravel() for w in weights_per_channel]
+    keep = {"first": np.ascontiguousarray(first, dtype=np.int32).ravel(),
+            "counts": np.array([w.size for w in per], dtype=np.int64),
+            "center": None if center is None else _f64(center).ravel()}
+    if keep["first"].size != len(per):
+        raise ValueError(f"{keep['first'].size} first points for {len(per)} channels")
+    if keep["center"] is not None and keep["center"].size != len(per):
+        raise ValueError(f"{keep['center'].size} centers for {len(per)} channels")
+    if int(keep["counts"].sum()) >= 2**31:
+        raise ValueError(f"{int(keep['counts'].sum())} weights in all: fewer than 2^31")
+    keep["offset"] = np.ascontiguousarray(np.concatenate(([0], np.cumsum(keep["counts"]))), dtype=np.int32)
+    keep["weights"] = _f64(np.concatenate(per)) if per else np.zeros(0)
+    gc = GrtChannels(len(per), keep["first"].ctypes.data_as(c_int_p), keep["offset"].ctypes.data_as(c_int_p),
+                     _dp(keep["weights"]), _opt_dp(keep["center"]), None, None)
+    gc.keep = keep             # (as make_cloud_model)
+    return gc, keep
+
+
+def channel_pair_count(gchannels, num_points):
+    """grt_channel_pair_count: the (channel, 128-point solver block) pairs P of gchannels (make_channels) on a grid of
+    num_points points -- Pipeline.run_sky_channels takes max_columns x S x A x 2 x P doubles of scratch --, or -1 for
+    channels the call would refuse.  Host code only."""
+    return int(load_library().grt_channel_pair_count(C.byref(gchannels), C.c_longlong(int(num_points))))
+
+
 class Pipeline:
     def __init__(self, lw_gas, sw_gas, max_columns, user_level, emissivity, albedo, solar, spectral=True):
         """spectral=True keeps tau/omega/g and the spectral fluxes (views(): what parity tests read);
@@ -1087,6 +1130,39 @@ class Pipeline:
         """... run with brightness=True: [ncol][nsets][nangles][2][n_lw], brightness temperatures, K."""
         self.sync()
         return self.buffers["sky.brightness"].to_host((ncol, nsets, nangles, GRT_RADIANCE_ROWS_PER_ANGLE, self.nw[0]))
+
+    def run_sky_channels(self, gcols, gsky, secants, gchannels, brightness=False, spectral=False, fluxes=True):
+        """grt_pipeline_run_sky_channels into this object's device buffers: run_sky_radiances(gcols, gsky, secants,
+        spectral=spectral, fluxes=fluxes) and with it the radiances of the instrument channels gchannels (make_channels'
+        struct; its two output fields are set here) of every set, angle and row (sky_channel_radiances() reads them) and
+        -- brightness=True -- their brightness temperatures (sky_channel_brightness())."""
+        m = _f64(secants)
+        if m.ndim != 2:
+            raise ValueError(f"secants of shape {m.shape}: [ncol][A]")
+        nsets = max(sky_set_count(gsky.sets), 1)
+        n, A = self.max_columns, m.shape[1]
+        rows = n * nsets * max(A, 1) * GRT_RADIANCE_ROWS_PER_ANGLE
+        grad = GrtRadiances(A, _dp(m), self._buffer("sky.radiances", 8 * rows).ptr,
+                            self._buffer("sky.spectral_radiances", 8 * rows * self.nw[0]).ptr if spectral else None, None)
+        nch = max(int(gchannels.num_channels), 1)
+        gchannels.channel_radiances_dev = self._buffer("sky.channel_radiances", 8 * rows * nch).ptr
+        gchannels.channel_brightness_dev = (self._buffer("sky.channel_brightness", 8 * rows * nch).ptr
+                                            if brightness else None)
+        out = self._sky_ptrs(gsky, False)[0][2] if fluxes else None
+        check(self.lib.grt_pipeline_run_sky_channels(self.p, C.byref(gcols), C.byref(gsky), C.byref(grad),
+                                                     C.byref(gchannels), out))
+
+    def sky_channel_radiances(self, ncol, nsets, nangles, nchannels):
+        """The last run_sky_channels of nsets sets at nangles angles: [ncol][nsets][nangles][2][nchannels], W m-2 sr-1 per
+        cm-1: per channel the SRF-weighted mean of the upward radiance at the top, then of the downward one at the surface."""
+        self.sync()
+        return self.buffers["sky.channel_radiances"].to_host((ncol, nsets, nangles, GRT_RADIANCE_ROWS_PER_ANGLE, nchannels))
+
+    def sky_channel_brightness(self, ncol, nsets, nangles, nchannels):
+        """... run with brightness=True: [ncol][nsets][nangles][2][nchannels], K, at the channel centres (no band-correction
+        coefficients applied)."""
+        self.sync()
+        return self.buffers["sky.channel_brightness"].to_host((ncol, nsets, nangles, GRT_RADIANCE_ROWS_PER_ANGLE, nchannels))
 
     def sky_fluxes(self, ncol, nsets):
         """The last six-row run_sky of nsets sets: [ncol][nsets][12], the sets in bit order, each in grt_pipeline_run's

@@ -558,6 +558,40 @@ static inline int grt_radiance_args_ok(GrtRadianceArgs const *r)
            r->draw < r->subcolumns;
 }
 
+/* Instrument channels of those radiances (grt_pipeline_run_sky_channels): the channel form of lw_radiance_kernel, the
+   radiance form with a GrtChannelArgs last in its joins.  Channel c is the points first .. first + count - 1 of the grid
+   with the weights W_c at weights + its weight offset; a (channel, 128-point solver block) pair is a channel and a block
+   the channel has a point in, pair = the channel's first pair + block - its first block.  After the upward sweep a
+   workgroup forms, per channel of its block's list, real angle and row, sum_i W_c(i) value(i) over its 128 points -- a lane
+   outside the channel's span or past the grid weighs 0; WAVE_SUM, then the two waves in order, as block_partials adds a
+   row; a wave that holds no point of the channel adds +0.0 without the tree -- and stores it at partials[((slot angles +
+   angle) 2 + row) pairs + pair]: a channel's sums depend on its own weights and the grid alone.  The table
+   (grt_channel_table, host): doubles first -- every channel's weights, then sum_w [C] (summed in index order), then
+   center [C] (the caller's, or the centroid sum W w / sum W) --, then the ints: per channel GRT_CHANNEL_INTS (first point,
+   count, weight offset, first block, first pair), per block where its list starts in what follows [nblocks + 1], and the
+   lists [pairs], the channels of a block in ascending order.
+   grt_launch_channel_finish (channel_finish_kernel): one thread per (column, angle, row, channel); per draw s = 0 .. S - 1
+   in order the channel's pairs in block order, then -- S > 1 -- one division by S, one by sum_w, stored at out[c
+   out_stride + out_offset + (angle 2 + row) C + channel]; brightness (or NULL): T = c2 v / log1p(c1 v^3 / R) at v =
+   center, +0.0 where R <= 0, at the same place. */
+#define GRT_CHANNEL_INTS 5
+typedef struct GrtChannelArgs
+{
+    int channels;                   /* C */
+    uint64_t pairs;                 /* P */
+    int const *chan;                /* DEVICE [C][GRT_CHANNEL_INTS] */
+    int const *block_start;         /* DEVICE [nblocks + 1] */
+    int const *block_chan;          /* DEVICE [P] */
+    double const *weights;          /* DEVICE [the channels' points] */
+    double const *sum_w, *center;   /* DEVICE [C] each */
+    double *partials;               /* DEVICE [slot][angles][2][P] */
+} GrtChannelArgs;
+static inline int grt_channel_args_ok(GrtChannelArgs const *c)
+{
+    return c != NULL && c->channels >= 1 && c->pairs >= 1 && c->chan != NULL && c->block_start != NULL &&
+           c->block_chan != NULL && c->weights != NULL && c->sum_w != NULL && c->center != NULL && c->partials != NULL;
+}
+
 /* Banded profile form of the two profile forms (GRT_OUT_LEVEL_BINS, clear sky or clouds joined;
    grt_pipeline_run_band_profiles): the profile form's arguments, sweeps and park block, but every level's
    flux leaves once per wavenumber bin that has a point in the workgroup's 128 grid points.  A point weights a level's
@@ -676,6 +710,11 @@ int grt_launch_sw(void *stream, GrtSolverInstance const *in, GrtSwArgs const *a)
    rows, a spectral output form (GRT_OUT_CHAINS, GRT_OUT_LAYERS) the materialised one; bins, zeniths, direct and jacobian
    are not read. */
 int grt_launch_lw_radiances(void *stream, GrtSolverInstance const *in, GrtLwArgs const *a, GrtRadianceArgs const *r);
+/* ... its channel form (GrtChannelArgs): the same launch, and the channels' partial sums beside everything it leaves */
+int grt_launch_lw_channels(void *stream, GrtSolverInstance const *in, GrtLwArgs const *a, GrtRadianceArgs const *r,
+                           GrtChannelArgs const *c);
+int grt_launch_channel_finish(void *stream, GrtChannelArgs const *c, int ncol, int subcolumns, int angles, double *out,
+                              double *brightness, uint64_t out_stride, uint64_t out_offset);
 /* The subcolumn mean of the partial sums above, in a fixed order: for column c and row r (of `rows` per slot) each
    subcolumn's blocks are added as grt_launch_reduce_partials adds them, then the subcolumns s = 0 .. S - 1 in order, then
    the sum is divided by S; out[c out_stride + out_offset + r].  S = 1 gives grt_launch_reduce_partials' bits. */

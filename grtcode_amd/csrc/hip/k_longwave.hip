@@ -297,7 +297,8 @@ __global__ __launch_bounds__(kJacobianBlock) void lw_surface_jacobian_kernel(Grt
 // grid.  A layer's optics and its two Planck terms are formed once per layer and sweep and shared by the chunk's angles;
 // the padding angles of a last chunk repeat its last real secant and write nothing.  What leaves: the upward radiance at
 // the top and the downward one at the surface, as trapezoid partial sums [slot][angles][2][nblocks] (idle lanes of the
-// last block follow along, weight 0) and, where asked for, at every point, with or as brightness temperatures.
+// last block follow along, weight 0) and, where asked for, at every point, with or as brightness temperatures.  The
+// channel form (a GrtChannelArgs last in the joins; grt_launch_lw_channels) leaves the sums of an instrument's channels too.
 constexpr int kRadianceChunk = GRT_RADIANCE_CHUNK;
 
 // planck() solved for T: c2 w / log1p(c1 w^3 / I); +0.0 where there is no radiance
@@ -321,10 +322,74 @@ __device__ __forceinline__ void radiance_partials(double const (&up)[kRadianceCh
     block_partials<2*N, kSolverBlock>(val, partials, row_base, gridDim.x, blockIdx.x);
 }
 
+// The channel form's last step (GrtChannelArgs, grt_kernels.h): per channel of this block's list, real angle of the chunk
+// and row, sum_i W_c(i) value(i) over the block's points -- W_c(i) = 0 outside the channel's span and in the idle lanes
+// -- by WAVE_SUM, then waves_sum, as block_partials adds a row.  A wave none of whose 64 points lies in the span (the same
+// in all its lanes: the span is the table's) leaves +0.0 without the tree.  kChannelChunk channels are summed before their
+// sums are stored, one by each thread: row v of channel q at partials[(row_base + v) pairs + pair(q, block)].
+constexpr int kChannelChunk = kSolverBlock/(2*kRadianceChunk);
+
+__device__ __forceinline__ void channel_partials(GrtChannelArgs const &ch, double const (&up)[kRadianceChunk],
+                                                 double const (&dn)[kRadianceChunk], int n, uint64_t row_base, uint64_t i,
+                                                 bool live)
+{
+    static_assert(kChannelChunk*2*kRadianceChunk == kSolverBlock, "one thread stores one (channel, angle, row) of a chunk");
+    __shared__ double part[kChannelChunk][2*kRadianceChunk][kSolverBlock/64];
+    unsigned const block = blockIdx.x;
+    int const lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long long const at = (long long)i, wave_lo = at - lane, wave_hi = wave_lo + 63;
+    int const k_lo = ch.block_start[block], k_hi = ch.block_start[block + 1];
+    for (int k0 = k_lo; k0 < k_hi; k0 += kChannelChunk)
+    {
+        int const nb = k_hi - k0 < kChannelChunk ? k_hi - k0 : kChannelChunk;
+        for (int q = 0; q < nb; ++q)
+        {
+            int const *e = ch.chan + (uint64_t)GRT_CHANNEL_INTS*ch.block_chan[k0 + q];
+            long long const first = e[0], last = first + e[1] - 1;
+            if (first <= wave_hi && last >= wave_lo)
+            {
+                double const W = (live && at >= first && at <= last) ? ch.weights[(uint64_t)e[2] + (uint64_t)(at - first)] : 0.;
+#pragma unroll
+                for (int k = 0; k < kRadianceChunk; ++k)
+                {
+                    if (k < n)
+                    {
+                        double su = W*up[k], sd = W*dn[k];
+                        WAVE_SUM(su);
+                        WAVE_SUM(sd);
+                        if (lane == 0)
+                        {
+                            part[q][2*k][wave] = su;
+                            part[q][2*k + 1][wave] = sd;
+                        }
+                    }
+                }
+            }
+            else if (lane == 0)
+            {
+                for (int v = 0; v < 2*n; ++v)
+                {
+                    part[q][v][wave] = 0.;
+                }
+            }
+        }
+        __syncthreads();
+        int const q = threadIdx.x/(2*kRadianceChunk), v = threadIdx.x % (2*kRadianceChunk);
+        if (q < nb && v < 2*n)
+        {
+            int const *e = ch.chan + (uint64_t)GRT_CHANNEL_INTS*ch.block_chan[k0 + q];
+            uint64_t const pair = (uint64_t)e[4] + block - (unsigned)e[3];
+            ch.partials[(row_base + v)*ch.pairs + pair] = waves_sum<kSolverBlock/64>(part[q][v]);
+        }
+        __syncthreads();
+    }
+}
+
 template <bool FUSED, typename... Joins>
 __global__ __launch_bounds__(kSolverBlock) void lw_radiance_kernel(GrtLwArgs a, GrtRadianceArgs r, Joins... joins)
 {
     static_assert(kRadianceChunk == 4, "the chunk's partial sums are listed for one to four angles");
+    constexpr bool CHANNELS = has<GrtChannelArgs, Joins...>;     // (the channel form: a GrtChannelArgs last in the joins)
     uint64_t const i = (uint64_t)blockIdx.x*kSolverBlock + threadIdx.x;
     SolverRow const row = solver_row(a.ncol, joins...);
     int const col = row.col;
@@ -419,6 +484,49 @@ __global__ __launch_bounds__(kSolverBlock) void lw_radiance_kernel(GrtLwArgs a, 
     case 2: radiance_partials<2>(I, down, wt, r.partials, row_base); break;
     case 3: radiance_partials<3>(I, down, wt, r.partials, row_base); break;
     default: radiance_partials<4>(I, down, wt, r.partials, row_base); break;
+    }
+    if constexpr (CHANNELS)
+    {
+        channel_partials(pick<GrtChannelArgs>(joins...), I, down, n, row_base, i, live);
+    }
+}
+
+// grt_launch_channel_finish (grt_kernels.h): the channels' pairs into channel radiances and brightness temperatures
+constexpr int kChannelFinishBlock = 256;
+__global__ __launch_bounds__(kChannelFinishBlock) void channel_finish_kernel(GrtChannelArgs ch, int ncol, int S, int rows, double *out,
+                                                                double *brightness, uint64_t out_stride,
+                                                                uint64_t out_offset)
+{
+    uint64_t const t = (uint64_t)blockIdx.x*kChannelFinishBlock + threadIdx.x;
+    uint64_t const C = (uint64_t)ch.channels;
+    if (t >= (uint64_t)ncol*rows*C)
+    {
+        return;
+    }
+    uint64_t const c = t % C, r = (t/C) % rows, col = t/(C*rows);
+    int const *e = ch.chan + GRT_CHANNEL_INTS*c;
+    int const npairs = (e[0] + e[1] - 1)/kSolverBlock - e[3] + 1;
+    double m = 0.;
+    for (int s = 0; s < S; ++s)
+    {
+        double const *p = ch.partials + ((col*S + s)*rows + r)*ch.pairs + e[4];
+        double x = p[0];
+        for (int k = 1; k < npairs; ++k)
+        {
+            x += p[k];
+        }
+        m = s == 0 ? x : m + x;
+    }
+    if (S > 1)
+    {
+        m = m/(double)S;
+    }
+    double const R = m/ch.sum_w[c];
+    uint64_t const to = col*out_stride + out_offset + r*C + c;
+    out[to] = R;
+    if (brightness != nullptr)
+    {
+        brightness[to] = brightness_temperature(R, ch.center[c]);
     }
 }
 
@@ -641,7 +749,9 @@ extern "C" int grt_launch_lw_surface_jacobian(void *stream, GrtLwArgs const *a, 
     return (int)hipGetLastError();
 }
 
-extern "C" int grt_launch_lw_radiances(void *stream, GrtSolverInstance const *in, GrtLwArgs const *a, GrtRadianceArgs const *r)
+// grt_launch_lw_radiances, or -- c given -- grt_launch_lw_channels: the instance of the join, with c last in its joins
+static int launch_lw_radiances(void *stream, GrtSolverInstance const *in, GrtLwArgs const *a, GrtRadianceArgs const *r,
+                               GrtChannelArgs const *c)
 {
     if (in == nullptr || a == nullptr || !grt_radiance_args_ok(r) || in->zeniths != nullptr || a->ncol < 1 || a->nw < 2 ||
         a->num_levels < 2 || grt_solver_grid_rows(in, a->ncol) > 65535 || a->t_layers == nullptr || a->t_levels == nullptr ||
@@ -660,22 +770,52 @@ extern "C" int grt_launch_lw_radiances(void *stream, GrtSolverInstance const *in
         {
             return (int)hipErrorInvalidValue;
         }
-        return launch_radiances<false>(s, *in, *a, *r);
+        return c != nullptr ? launch_radiances<false>(s, *in, *a, *r, *c) : launch_radiances<false>(s, *in, *a, *r);
     }
     if (a->tau_gas == nullptr || a->n_layer == nullptr)
     {
         return (int)hipErrorInvalidValue;
     }
-    // every fused instance of lw_radiance_kernel there is: one per join
+    auto fused = [&](auto const &...joins) -> int
+    {
+        return c != nullptr ? launch_radiances<true>(s, *in, *a, *r, joins..., *c) : launch_radiances<true>(s, *in, *a, *r, joins...);
+    };
+    // every fused instance of lw_radiance_kernel there is: one per join, and its channel form
     switch (grt_solver_join(in))
     {
-    case GRT_JOIN_NONE: return launch_radiances<true>(s, *in, *a, *r);
-    case GRT_JOIN_CLOUDS: return launch_radiances<true>(s, *in, *a, *r, *in->clouds);
-    case GRT_JOIN_AEROSOLS: return launch_radiances<true>(s, *in, *a, *r, *in->aerosols);
-    case GRT_JOIN_SUBCOLUMNS: return launch_radiances<true>(s, *in, *a, *r, *in->subcolumns);
-    case GRT_JOIN_CLOUDS_AEROSOLS: return launch_radiances<true>(s, *in, *a, *r, *in->clouds, *in->aerosols);
-    case GRT_JOIN_SUBCOLUMNS_AEROSOLS: return launch_radiances<true>(s, *in, *a, *r, *in->subcolumns, *in->aerosols);
+    case GRT_JOIN_NONE: return fused();
+    case GRT_JOIN_CLOUDS: return fused(*in->clouds);
+    case GRT_JOIN_AEROSOLS: return fused(*in->aerosols);
+    case GRT_JOIN_SUBCOLUMNS: return fused(*in->subcolumns);
+    case GRT_JOIN_CLOUDS_AEROSOLS: return fused(*in->clouds, *in->aerosols);
+    case GRT_JOIN_SUBCOLUMNS_AEROSOLS: return fused(*in->subcolumns, *in->aerosols);
     default:
         return (int)hipErrorInvalidValue;
     }
+}
+
+extern "C" int grt_launch_lw_radiances(void *stream, GrtSolverInstance const *in, GrtLwArgs const *a, GrtRadianceArgs const *r)
+{
+    return launch_lw_radiances(stream, in, a, r, nullptr);
+}
+
+extern "C" int grt_launch_lw_channels(void *stream, GrtSolverInstance const *in, GrtLwArgs const *a, GrtRadianceArgs const *r,
+                                      GrtChannelArgs const *c)
+{
+    return grt_channel_args_ok(c) ? launch_lw_radiances(stream, in, a, r, c) : (int)hipErrorInvalidValue;
+}
+
+extern "C" int grt_launch_channel_finish(void *stream, GrtChannelArgs const *c, int ncol, int subcolumns, int angles,
+                                         double *out, double *brightness, uint64_t out_stride, uint64_t out_offset)
+{
+    if (!grt_channel_args_ok(c) || ncol < 1 || subcolumns < 1 || angles < 1 || out == nullptr)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    int const rows = 2*angles;
+    uint64_t const threads = (uint64_t)ncol*rows*(uint64_t)c->channels;
+    hipLaunchKernelGGL(channel_finish_kernel, dim3((unsigned)((threads + kChannelFinishBlock - 1)/kChannelFinishBlock)),
+                       dim3(kChannelFinishBlock), 0, (hipStream_t)stream, *c, ncol, subcolumns, rows, out, brightness,
+                       out_stride, out_offset);
+    return (int)hipGetLastError();
 }

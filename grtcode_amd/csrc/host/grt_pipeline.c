@@ -273,6 +273,7 @@ static void grt_pipeline_release(GrtPipeline_t **pipeline)
         grt_keyed_table_free(p, &p->band[b].aer_map);
         grt_keyed_table_free(p, &p->band[b].bin_table);
         grt_keyed_table_free(p, &p->band[b].surf_map);
+        grt_keyed_table_free(p, &p->band[b].channel_table);
     }
     grt_staging_free(p, &p->rad);
     grt_staging_free(p, &p->zen);
@@ -496,6 +497,8 @@ typedef struct GrtJoin
                                           these angles; with `sets`, the per-angle outputs hold every set's */
     GrtRadiances_t const *radiances;   /* grt_pipeline_run_sky_radiances: every set's longwave leaves its radiances at these
                                           viewing angles too; rows->out NULL: and nothing else runs */
+    GrtChannels_t const *channels;     /* grt_pipeline_run_sky_channels (with radiances): and the channels of an instrument */
+    long long channel_pairs;           /* ... their (channel, solver block) pairs on the longwave grid (grt_check_channels) */
 } GrtJoin;
 
 #define GRT_SKY_ALL (GRT_SKY_CLEAN | GRT_SKY_AEROSOL | GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL)
@@ -552,6 +555,12 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
     if (join->radiances != NULL && p->band[0].gas != NULL)
     {
         GRT_TRY(grt_stage_radiances(p, join->radiances, C, &rr));
+    }
+    GrtChannelRun cr;
+    if (join->channels != NULL && p->band[0].gas != NULL)
+    {
+        GRT_TRY(grt_stage_channels(p, &p->band[0], join->channels, join->channel_pairs, &cr));
+        cr.slots = (sets & (GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL)) != 0 ? S : 1;
     }
     if (cl != NULL && join->sampler != NULL)
     {
@@ -612,6 +621,7 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
         GrtContinua continua;
         GrtPass ps = *rows;
         ps.radiances = bi == 0 && join->radiances != NULL ? &rr : NULL;
+        ps.channels = bi == 0 && join->channels != NULL ? &cr : NULL;
         GrtAerosolArgs aa;
         int const band_aer = ae != NULL && grt_aerosol_points(ae, bi) > 0;
         int aa_ready = 0;
@@ -1168,10 +1178,10 @@ EXTERN int grt_pipeline_run_sky_jacobian(GrtPipeline_t *p, GrtColumns_t const *c
     return GRTCODE_SUCCESS;
 }
 
-/* grt_ext.h: grt_pipeline_run_sky's six-row form, and the longwave radiances of every set at the columns' viewing angles;
-   fluxes_dev NULL: the radiances alone */
-EXTERN int grt_pipeline_run_sky_radiances(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky,
-                                          GrtRadiances_t const *rd, fp_t *fluxes_dev)
+/* grt_pipeline_run_sky_radiances, and -- channels_asked -- grt_pipeline_run_sky_channels, which is the same call with the
+   channels of an instrument (ch; checked here, NULL included) */
+static int run_sky_radiances(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky, GrtRadiances_t const *rd,
+                             int channels_asked, GrtChannels_t const *ch, fp_t *fluxes_dev)
 {
     GRT_REQUIRE_PTR(p);
     GRT_REQUIRE_PTR(cols);
@@ -1186,6 +1196,16 @@ EXTERN int grt_pipeline_run_sky_radiances(GrtPipeline_t *p, GrtColumns_t const *
     GrtJoin join;
     GRT_TRY(sky_join(p, cols, sky, &a, &join));
     GRT_TRY(grt_check_radiances(rd, cols->ncol));
+    long long pairs = 0;
+    if (channels_asked)
+    {
+        GRT_TRY(grt_check_channels(ch, p->band[0].gas != NULL ? (long long)p->band[0].n : 0, &pairs));
+        if (ch->channel_radiances_dev == NULL)
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "channel_radiances_dev is NULL: the channel radiances [ncol][sets][angles][%d][%d] are "
+                     "the output.", GRT_RADIANCE_ROWS_PER_ANGLE, ch->num_channels);
+        }
+    }
     int const spectral = rd->spectral_radiances_dev != NULL || rd->brightness_dev != NULL;
     if (spectral && join.subcolumns > 0)
     {
@@ -1194,6 +1214,8 @@ EXTERN int grt_pipeline_run_sky_radiances(GrtPipeline_t *p, GrtColumns_t const *
                  join.subcolumns);
     }
     join.radiances = rd;
+    join.channels = channels_asked ? ch : NULL;
+    join.channel_pairs = pairs;
     GrtPass rows;
     memset(&rows, 0, sizeof(rows));
     rows.out = fluxes_dev;
@@ -1207,8 +1229,43 @@ EXTERN int grt_pipeline_run_sky_radiances(GrtPipeline_t *p, GrtColumns_t const *
         size_t const rows_all = (size_t)cols->ncol*(size_t)nsets*(size_t)rd->num_angles*GRT_RADIANCE_ROWS_PER_ANGLE;
         GRT_TRY(grt_dev_zero(p->device, rd->radiances_dev, sizeof(double)*rows_all, s));
         /* (a spectral row of such a pipeline has no points) */
+        if (channels_asked)
+        {
+            size_t const bytes = sizeof(double)*rows_all*(size_t)ch->num_channels;
+            GRT_TRY(grt_dev_zero(p->device, ch->channel_radiances_dev, bytes, s));
+            if (ch->channel_brightness_dev != NULL)
+            {
+                GRT_TRY(grt_dev_zero(p->device, ch->channel_brightness_dev, bytes, s));
+            }
+        }
     }
     return GRTCODE_SUCCESS;
+}
+
+/* grt_ext.h: grt_pipeline_run_sky's six-row form, and the longwave radiances of every set at the columns' viewing angles;
+   fluxes_dev NULL: the radiances alone */
+EXTERN int grt_pipeline_run_sky_radiances(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky,
+                                          GrtRadiances_t const *rd, fp_t *fluxes_dev)
+{
+    return run_sky_radiances(p, cols, sky, rd, 0, NULL, fluxes_dev);
+}
+
+/* grt_ext.h: ... and the radiances and brightness temperatures of an instrument's channels */
+EXTERN int grt_pipeline_run_sky_channels(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky,
+                                         GrtRadiances_t const *rd, GrtChannels_t const *ch, fp_t *fluxes_dev)
+{
+    return run_sky_radiances(p, cols, sky, rd, 1, ch, fluxes_dev);
+}
+
+/* grt_ext.h: the (channel, solver block) pairs of an instrument on a grid of num_points; -1: channels the call refuses */
+EXTERN long long grt_channel_pair_count(GrtChannels_t const *ch, long long num_points)
+{
+    long long pairs;
+    if (num_points < 1 || grt_check_channels(ch, num_points, &pairs) != GRTCODE_SUCCESS)
+    {
+        return -1;
+    }
+    return pairs;
 }
 
 /* grt_ext.h: the sets of grt_pipeline_run_sky, the shortwave of each under several sun angles per column */

@@ -1,6 +1,7 @@
 /* grt_pipeline_inputs.c -- what turns a caller's clouds, aerosols, surface and bin edges into device arguments of the batched
  * pipeline: the per-batch tables staged through pinned memory, and the per-point maps that depend only on band limits,
  * an aerosol grid or bin edges and are rebuilt when those change. */
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 #include "grt_pipeline_internal.h"
@@ -122,15 +123,33 @@ int grt_stage_radiances(GrtPipeline_t *p, GrtRadiances_t const *rd, int C, GrtRa
     return GRTCODE_SUCCESS;
 }
 
-/* t->table for `key`: as it is when it was built for the same bytes, else `ints` ints written by fill(ctx, .) on the host
-   and uploaded.  The stored key is dropped before the device table is touched and set again only when the whole call
-   succeeded, so a failure half way leaves a table that the next call rebuilds, whatever its key. */
-static int grt_keyed_table(GrtPipeline_t *p, GrtKeyedTable *t, void const *key, size_t key_bytes, size_t ints,
-                           GrtTableFill fill, void *ctx)
+/* a key given as parts that lie apart in the caller's memory: compared in place, copied only when the table is rebuilt */
+typedef struct GrtKeyPart { void const *bytes; size_t n; } GrtKeyPart;
+
+/* t->table for the key `parts`, taken one after the other: as it is when it was built for the same bytes, else `ints` ints
+   written by fill(ctx, .) on the host and uploaded.  The stored key is dropped before the device table is touched and set
+   again only when the whole call succeeded, so a failure half way leaves a table that the next call rebuilds, whatever its
+   key. */
+static int grt_keyed_table_parts(GrtPipeline_t *p, GrtKeyedTable *t, GrtKeyPart const *parts, int nparts, size_t ints,
+                                 GrtTableFill fill, void *ctx)
 {
-    if (t->key != NULL && t->key_bytes == key_bytes && memcmp(t->key, key, key_bytes) == 0)
+    size_t key_bytes = 0;
+    for (int k = 0; k < nparts; ++k)
     {
-        return GRTCODE_SUCCESS;
+        key_bytes += parts[k].n;
+    }
+    if (t->key != NULL && t->key_bytes == key_bytes)
+    {
+        char const *at = t->key;
+        int same = 1;
+        for (int k = 0; k < nparts && same; at += parts[k].n, ++k)
+        {
+            same = parts[k].n == 0 || memcmp(at, parts[k].bytes, parts[k].n) == 0;
+        }
+        if (same)
+        {
+            return GRTCODE_SUCCESS;
+        }
     }
     void *new_key = malloc(key_bytes);
     int *host = malloc(sizeof(int)*ints);
@@ -143,7 +162,14 @@ static int grt_keyed_table(GrtPipeline_t *p, GrtKeyedTable *t, void const *key, 
     int rc = fill(ctx, host);
     if (rc == GRTCODE_SUCCESS)
     {
-        memcpy(new_key, key, key_bytes);
+        char *to = new_key;
+        for (int k = 0; k < nparts; to += parts[k].n, ++k)
+        {
+            if (parts[k].n > 0)
+            {
+                memcpy(to, parts[k].bytes, parts[k].n);
+            }
+        }
         free(t->key);
         t->key = NULL;
         void *s = grt_dev_stream(p->device);
@@ -168,6 +194,14 @@ static int grt_keyed_table(GrtPipeline_t *p, GrtKeyedTable *t, void const *key, 
     t->key = new_key;
     t->key_bytes = key_bytes;
     return GRTCODE_SUCCESS;
+}
+
+/* ... for a key in one piece */
+static int grt_keyed_table(GrtPipeline_t *p, GrtKeyedTable *t, void const *key, size_t key_bytes, size_t ints,
+                           GrtTableFill fill, void *ctx)
+{
+    GrtKeyPart const part = {key, key_bytes};
+    return grt_keyed_table_parts(p, t, &part, 1, ints, fill, ctx);
 }
 
 void grt_keyed_table_free(GrtPipeline_t *p, GrtKeyedTable *t)
@@ -563,6 +597,168 @@ int grt_stage_surface(GrtPipeline_t *p, GrtSurface_t const *sf, int const np[2])
         grt_profile_end(s, slot);
         GRT_TRY(grt_dev_check(krc, "surface row kernel"));
     }
+    return GRTCODE_SUCCESS;
+}
+
+/* ---- instrument channels (grt_pipeline_run_sky_channels) ---- */
+
+/* What grt_pipeline_run_sky_channels and grt_channel_pair_count check of an instrument's channels on a grid of n points
+   (n < 1: a pipeline without a longwave band, no range check), the output pointers apart; *pairs: the (channel, solver
+   block) pairs in which a channel has a point (0 without a grid).  Nothing is touched. */
+int grt_check_channels(GrtChannels_t const *ch, long long n, long long *pairs)
+{
+    if (ch == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "channels (GrtChannels_t) is NULL: %s", "the instrument's channels are the input.");
+    }
+    if (ch->num_channels < 1 || ch->num_channels > GRT_MAX_CHANNELS)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d channels asked for: 1 to %d.", ch->num_channels, GRT_MAX_CHANNELS);
+    }
+    if (ch->first == NULL || ch->offset == NULL || ch->weights == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%s of the channels is NULL.",
+                 ch->first == NULL ? "first" : (ch->offset == NULL ? "offset" : "weights"));
+    }
+    int const C = ch->num_channels;
+    if (ch->offset[0] != 0)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "offset[0] of the channels is %d: the first channel's weights start at 0.", ch->offset[0]);
+    }
+    long long P = 0;
+    for (int c = 0; c < C; ++c)
+    {
+        if (ch->offset[c + 1] <= ch->offset[c])
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "offset[%d] = %d is not above offset[%d] = %d: a channel has at least one point.",
+                     c + 1, ch->offset[c + 1], c, ch->offset[c]);
+        }
+        long long const count = (long long)ch->offset[c + 1] - ch->offset[c];
+        if (n >= 1 && (ch->first[c] < 0 || ch->first[c] + count > n))
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "channel %d takes the points %d .. %lld of a longwave band of %lld.", c, ch->first[c],
+                     ch->first[c] + count - 1, n);
+        }
+        double sum = 0.;                  /* (in index order: what the table divides by) */
+        for (int k = ch->offset[c]; k < ch->offset[c + 1]; ++k)
+        {
+            if (!isfinite(ch->weights[k]))
+            {
+                GRT_FAIL(GRTCODE_VALUE_ERR, "weight %d of channel %d (%e) is NaN or infinite.", k - ch->offset[c], c,
+                         ch->weights[k]);
+            }
+            sum += ch->weights[k];
+        }
+        if (!(sum > 0.) || !isfinite(sum))
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "the weights of channel %d add up to %e: a sum that is finite and above 0 is needed.",
+                     c, sum);
+        }
+        if (ch->center != NULL && (!(ch->center[c] > 0.) || !isfinite(ch->center[c])))
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "center of channel %d (%e) is NaN, infinite or not above 0.", c, ch->center[c]);
+        }
+        if (n >= 1)
+        {
+            P += (ch->first[c] + count - 1)/GRT_SOLVER_BLOCK - ch->first[c]/GRT_SOLVER_BLOCK + 1;
+        }
+    }
+    *pairs = P;
+    return GRTCODE_SUCCESS;
+}
+
+/* The device table of an instrument on band b's grid (GrtChannelArgs, grt_kernels.h), as grt_keyed_table keeps it: the
+   doubles first (the table is a device allocation: aligned for them), then the ints. */
+typedef struct ChannelTableFill
+{
+    GrtChannels_t const *ch;
+    SpectralGrid_t const *grid;
+    size_t nblocks, doubles;
+    long long pairs;
+} ChannelTableFill;
+
+static int fill_channel_table(void *ctx, int *table)
+{
+    ChannelTableFill *f = ctx;
+    GrtChannels_t const *ch = f->ch;
+    int const C = ch->num_channels;
+    size_t const W = (size_t)ch->offset[C];
+    double *weights = (double *)table, *sum_w = weights + W, *center = sum_w + C;
+    int *chan = table + 2*f->doubles, *block_start = chan + (size_t)GRT_CHANNEL_INTS*C, *block_chan = block_start + f->nblocks + 1;
+    memcpy(weights, ch->weights, sizeof(double)*W);
+    memset(block_start, 0, sizeof(int)*(f->nblocks + 1));
+    int pair = 0;
+    for (int c = 0; c < C; ++c)
+    {
+        int const first = ch->first[c], count = ch->offset[c + 1] - ch->offset[c];
+        int const b_lo = first/GRT_SOLVER_BLOCK, b_hi = (first + count - 1)/GRT_SOLVER_BLOCK;
+        int *e = chan + (size_t)GRT_CHANNEL_INTS*c;
+        e[0] = first; e[1] = count; e[2] = ch->offset[c]; e[3] = b_lo; e[4] = pair;
+        pair += b_hi - b_lo + 1;
+        for (int k = b_lo; k <= b_hi; ++k)
+        {
+            ++block_start[k + 1];               /* (counts first, then their running sum) */
+        }
+        double sum = 0., wsum = 0.;       /* (both in index order) */
+        for (int k = 0; k < count; ++k)
+        {
+            double const W = ch->weights[ch->offset[c] + k];
+            sum += W;
+            wsum += W*(f->grid->w0 + (double)(first + k)*f->grid->dw);
+        }
+        sum_w[c] = sum;
+        center[c] = ch->center != NULL ? ch->center[c] : wsum/sum;
+    }
+    for (size_t k = 0; k < f->nblocks; ++k)
+    {
+        block_start[k + 1] += block_start[k];
+    }
+    /* the channels of a block in ascending order; fill[] walks each block's list */
+    int *fill = malloc(sizeof(int)*(f->nblocks > 0 ? f->nblocks : 1));
+    if (fill == NULL)
+    {
+        GRT_FAIL(GRTCODE_NULL_ERR, "out of host memory for a channel table of %zu blocks.", f->nblocks);
+    }
+    memcpy(fill, block_start, sizeof(int)*f->nblocks);
+    for (int c = 0; c < C; ++c)
+    {
+        int const *e = chan + (size_t)GRT_CHANNEL_INTS*c;
+        for (int k = e[3]; k <= (e[0] + e[1] - 1)/GRT_SOLVER_BLOCK; ++k)
+        {
+            block_chan[fill[k]++] = c;
+        }
+    }
+    free(fill);
+    return GRTCODE_SUCCESS;
+}
+
+/* The channels of a grt_pipeline_run_sky_channels call (checked by grt_check_channels on b's grid, which gave `pairs`) as
+   the longwave band's device table -- built and uploaded when first, offset, weights or center differ from the last
+   call's -- and where their outputs go */
+int grt_stage_channels(GrtPipeline_t *p, GrtBand *b, GrtChannels_t const *ch, long long pairs, GrtChannelRun *cr)
+{
+    int const C = ch->num_channels;
+    size_t const W = (size_t)ch->offset[C];
+    ChannelTableFill f = {ch, &b->gas->grid, grt_solver_blocks(b->n), W + 2*(size_t)C, pairs};
+    /* the key: the grid's points, C, whether centers are given, then first, offset, weights and the centers, where they are */
+    long long const h[3] = {(long long)b->n, C, ch->center != NULL};
+    GrtKeyPart const key[5] = {{h, sizeof(h)}, {ch->first, sizeof(int)*(size_t)C}, {ch->offset, sizeof(int)*((size_t)C + 1)},
+                               {ch->weights, sizeof(double)*W},
+                               {ch->center, ch->center != NULL ? sizeof(double)*(size_t)C : 0}};
+    size_t const table_ints = 2*f.doubles + (size_t)GRT_CHANNEL_INTS*C + f.nblocks + 1 + (size_t)f.pairs;
+    GRT_TRY(grt_keyed_table_parts(p, &b->channel_table, key, 5, table_ints, fill_channel_table, &f));
+    memset(cr, 0, sizeof(*cr));
+    GrtChannelArgs *a = &cr->args;
+    a->channels = C;
+    a->pairs = (uint64_t)f.pairs;
+    a->weights = (double const *)b->channel_table.table;
+    a->sum_w = a->weights + W;
+    a->center = a->sum_w + C;
+    a->chan = b->channel_table.table + 2*f.doubles;
+    a->block_start = a->chan + (size_t)GRT_CHANNEL_INTS*C;
+    a->block_chan = a->block_start + f.nblocks + 1;
+    cr->radiances = ch->channel_radiances_dev;
+    cr->brightness = ch->channel_brightness_dev;
     return GRTCODE_SUCCESS;
 }
 

@@ -72,6 +72,10 @@ enum
     /* grt_pipeline_run_sky_radiances, longwave, both forms: [max_cols][S][A][2][nblocks] partial sums of the radiances of
        every angle and cloud draw, S = 1 but in a cloud set of several draws; sized at the first call that needs more */
     GRT_SCRATCH_RADIANCE_PARTIALS,
+    /* grt_pipeline_run_sky_channels, longwave, both forms: [max_cols][S][A][2][P] the channels' partial sums per (channel,
+       solver block) pair of every angle and cloud draw, S the draws of the call's cloud sets (1 without one) for every
+       set of the call; sized at the first call that needs more */
+    GRT_SCRATCH_CHANNEL_PARTIALS,
     GRT_SCRATCH_COUNT
 };
 
@@ -109,6 +113,9 @@ typedef struct GrtBand
     /* grt_pipeline_set_surface: [n] entry of the band's surface grid each grid point takes (grt_surface_entry_map); its key:
        that grid */
     GrtKeyedTable surf_map;
+    /* grt_pipeline_run_sky_channels (longwave band): the instrument's table (GrtChannelArgs: weights, sums and centers,
+       then the channels' and the blocks' ints); its key: the grid's points and the channels' first, offset, weights, center */
+    GrtKeyedTable channel_table;
     int surf_set, surf_dif_set;    /* the surface in force gives this band rows (, and diffuse rows of their own) */
 } GrtBand;
 
@@ -158,6 +165,16 @@ typedef struct GrtRadianceRun
     double *spectral, *brightness; /* DEVICE [ncol][sets][A][2][n], or NULL */
 } GrtRadianceRun;
 
+/* The channels of a grt_pipeline_run_sky_channels call, staged (grt_stage_channels): the instrument's table on the device
+   (args.partials: set by the pass's launch), and where every set's channel outputs go. */
+typedef struct GrtChannelRun
+{
+    GrtChannelArgs args;
+    double *radiances, *brightness; /* DEVICE [ncol][sets][A][2][C]; brightness may be NULL */
+    int slots;                      /* slots per column of the scratch: the most draws any set of the call has, so that the
+                                       call's first set sizes GRT_SCRATCH_CHANNEL_PARTIALS for all of them */
+} GrtChannelRun;
+
 /* One solve of a band on the run's tau_gas.  What joins gas and Rayleigh: nothing (clear sky), the cloud objects (all-sky
    pass), the aerosol object (aerosol pass; aer NULL there: a band that was given no aerosol, which runs the form without
    the object under the aerosol pass's profile tags) or both (grt_pipeline_run_sky's complete set).  Which rows leave: the six of driver.c:272-280 or (profile) every level's
@@ -185,6 +202,9 @@ typedef struct GrtPass
     /* grt_pipeline_run_sky_radiances (NULL: not asked for): the longwave's radiance kernel is queued behind the pass's
        solver -- out NULL: in its place --, the pass's to set `set` of each output */
     GrtRadianceRun const *radiances;
+    /* grt_pipeline_run_sky_channels (NULL: not asked for; with radiances only): that kernel in its channel form, and the
+       channels' finishing kernel behind it */
+    GrtChannelRun const *channels;
 } GrtPass;
 
 /* The sun angles of a grt_pipeline_run_zeniths or grt_pipeline_run_sky_zeniths call, staged (grt_stage_zeniths): Z per column, their cosines and weights
@@ -234,6 +254,9 @@ GRT_PRIVATE int grt_stage_surface(GrtPipeline_t *p, GrtSurface_t const *sf, int 
 GRT_PRIVATE int grt_stage_zeniths(GrtPipeline_t *p, GrtZeniths_t const *zn, int C, GrtZenithRun *zr);
 GRT_PRIVATE int grt_check_radiances(GrtRadiances_t const *rd, int C);
 GRT_PRIVATE int grt_stage_radiances(GrtPipeline_t *p, GrtRadiances_t const *rd, int C, GrtRadianceRun *rr);
+GRT_PRIVATE int grt_check_channels(GrtChannels_t const *ch, long long n, long long *pairs);
+GRT_PRIVATE int grt_stage_channels(GrtPipeline_t *p, GrtBand *b, GrtChannels_t const *ch, long long pairs,
+                                   GrtChannelRun *cr);
 GRT_PRIVATE int grt_band_bins(GrtPipeline_t *p, GrtBand *b, int const *edges, int nbins, int rows);
 
 /* grt_pipeline_solve.c */

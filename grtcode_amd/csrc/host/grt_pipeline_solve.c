@@ -282,6 +282,17 @@ static int band_radiances(GrtPipeline_t *p, GrtBand *b, int C, int S, int draw, 
     r.spectral = rr->spectral != NULL ? rr->spectral + (size_t)ps->set*set_doubles : NULL;
     r.brightness = rr->brightness != NULL ? rr->brightness + (size_t)ps->set*set_doubles : NULL;
     r.col_stride = (uint64_t)ps->sets*set_doubles;
+    /* (grt_pipeline_run_sky_channels: the kernel's channel form, its pairs' sums to GRT_SCRATCH_CHANNEL_PARTIALS,
+       [max_cols][S][A][2][P]) */
+    GrtChannelArgs ch;
+    if (ps->channels != NULL)
+    {
+        ch = ps->channels->args;
+        GrtScratch *pairs = &b->scratch[GRT_SCRATCH_CHANNEL_PARTIALS];
+        int const slots = ps->channels->slots > S ? ps->channels->slots : S;   /* (the call's cloud sets': sized once) */
+        GRT_TRY(grt_scratch_need(p, pairs, (size_t)p->max_cols*(size_t)slots*per_slot*(size_t)ch.pairs, NULL));
+        ch.partials = pairs->d;
+    }
     int const slot = grt_profile_begin(s, GRT_TAG_RADIANCE);
     int krc = 0;
     if (sc != NULL)
@@ -290,12 +301,13 @@ static int band_radiances(GrtPipeline_t *p, GrtBand *b, int C, int S, int draw, 
         for (sc->first = 0; sc->first < S && krc == 0; sc->first += group)
         {
             sc->count = S - sc->first < group ? S - sc->first : group;
-            krc = grt_launch_lw_radiances(s, &in, &a.lw, &r);
+            krc = ps->channels != NULL ? grt_launch_lw_channels(s, &in, &a.lw, &r, &ch) :
+                                         grt_launch_lw_radiances(s, &in, &a.lw, &r);
         }
     }
     else
     {
-        krc = grt_launch_lw_radiances(s, &in, &a.lw, &r);
+        krc = ps->channels != NULL ? grt_launch_lw_channels(s, &in, &a.lw, &r, &ch) : grt_launch_lw_radiances(s, &in, &a.lw, &r);
     }
     grt_profile_end(s, slot);
     GRT_TRY(grt_dev_check(krc, "longwave radiance kernel"));
@@ -322,6 +334,27 @@ static int finish_radiances(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass 
                                               ps->set*rows);
     grt_profile_end(s, mslot);
     GRT_TRY(grt_dev_check(mrc, "subcolumn mean kernel"));
+    return GRTCODE_SUCCESS;
+}
+
+/* ... and -- grt_pipeline_run_sky_channels -- the pairs' sums of the S draws into the pass's set of the channel radiances
+   and brightness temperatures [ncol][sets][A][2][C] (GRT_TAG_CHANNELS); a pass without channels: nothing */
+static int finish_channels(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass const *ps)
+{
+    if (ps->channels == NULL)
+    {
+        return GRTCODE_SUCCESS;
+    }
+    GrtChannelRun const *cr = ps->channels;
+    void *s = grt_dev_stream(p->device);
+    GrtChannelArgs ch = cr->args;
+    ch.partials = b->scratch[GRT_SCRATCH_CHANNEL_PARTIALS].d;
+    uint64_t const set_doubles = (uint64_t)ps->radiances->angles*GRT_RADIANCE_ROWS_PER_ANGLE*(uint64_t)ch.channels;
+    int const slot = grt_profile_begin(s, GRT_TAG_CHANNELS);
+    int const krc = grt_launch_channel_finish(s, &ch, C, S, ps->radiances->angles, cr->radiances, cr->brightness,
+                                              (uint64_t)ps->sets*set_doubles, (uint64_t)ps->set*set_doubles);
+    grt_profile_end(s, slot);
+    GRT_TRY(grt_dev_check(krc, "channel finishing kernel"));
     return GRTCODE_SUCCESS;
 }
 
@@ -610,6 +643,7 @@ int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *p
         {
             GRT_TRY(band_radiances(p, b, C, 1, 0, ps, NULL));
             GRT_TRY(finish_radiances(p, b, C, 1, ps));
+            GRT_TRY(finish_channels(p, b, C, 1, ps));
         }
         return GRTCODE_SUCCESS;
     }
@@ -641,6 +675,7 @@ int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *p
     {
         GRT_TRY(band_radiances(p, b, C, 1, 0, ps, NULL));
         GRT_TRY(finish_radiances(p, b, C, 1, ps));
+        GRT_TRY(finish_channels(p, b, C, 1, ps));
     }
     return GRTCODE_SUCCESS;
 }
@@ -662,6 +697,7 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
         GrtSubcolumnArgs sc = {*ps->clouds, S, 0, 0};
         GRT_TRY(band_radiances(p, b, C, S, 0, ps, &sc));
         GRT_TRY(finish_radiances(p, b, C, S, ps));
+        GRT_TRY(finish_channels(p, b, C, S, ps));
         return GRTCODE_SUCCESS;
     }
     if (!p->keep_spectra)
@@ -693,6 +729,7 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
         {
             GRT_TRY(band_radiances(p, b, C, S, 0, ps, &sc));
             GRT_TRY(finish_radiances(p, b, C, S, ps));
+            GRT_TRY(finish_channels(p, b, C, S, ps));
         }
         if (S == 1)
         {
@@ -757,6 +794,7 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
     if (pass_radiances(ps, bi))
     {
         GRT_TRY(finish_radiances(p, b, C, S, ps));
+        GRT_TRY(finish_channels(p, b, C, S, ps));
     }
     if (ps->out == NULL)
     {

@@ -561,9 +561,9 @@ EXTERN int grt_pipeline_run_sky_jacobian(GrtPipeline_t *pipeline, GrtColumns_t c
  * radiances NULL; radiances_dev NULL; view_secant NULL; num_angles outside 1 .. GRT_MAX_VIEW_ANGLES; a secant that is
  * NaN, infinite or below 1; a spectral or brightness output together with a cloud set at num_subcolumns > 1; everything
  * grt_pipeline_run_sky refuses.
- * Not covered: spectral and brightness outputs of cloud sets with more than one draw, the profile form and radiances at
- * interior levels, per-bin radiances, instrument line-shape convolution, shortwave (scattered solar) radiances, and cloud
- * fields sampled on the device. */
+ * Not covered: the profile form and radiances at interior levels, per-bin radiances, shortwave (scattered solar)
+ * radiances, and cloud fields sampled on the device (instrument channels, cloud sets of several draws among them:
+ * grt_pipeline_run_sky_channels below). */
 #define GRT_MAX_VIEW_ANGLES 16
 #define GRT_RADIANCE_ROWS_PER_ANGLE 2      /* upward at the top of the atmosphere, downward at the surface */
 typedef struct GrtRadiances
@@ -576,6 +576,59 @@ typedef struct GrtRadiances
 } GrtRadiances_t;
 EXTERN int grt_pipeline_run_sky_radiances(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtSky_t const *sky,
                                           GrtRadiances_t const *radiances, fp_t *fluxes_dev);
+
+/* ---- instrument-channel radiances and brightness temperatures, of every sky set -------------------------------------
+ * grt_pipeline_run_sky_radiances in every respect -- the sets and their packing, the viewing angles, every output of
+ * `radiances`, fluxes_dev NULL or not, the surface in force, the input checks, asynchronous on the pipeline's lane, both
+ * forms of the pipeline -- and with it what an instrument channel measures: per column, set, viewing angle and row (the
+ * upward radiance at the top of the atmosphere, then the downward one at the surface) the mean of the spectral radiance
+ * weighted with the spectral response function (SRF) of each of C channels, reduced on the device so that no spectral
+ * row has to leave it.  Channel c is the grid points i = first[c] + k, k = 0 .. count_c - 1 (count_c = offset[c + 1] -
+ * offset[c]) of the longwave band with the weights W_k = weights[offset[c] + k], the SRF sampled on the grid:
+ *   R_c = (sum_k W_k I(i)) / (sum_k W_k),      W m-2 sr-1 per cm-1,
+ * I the radiance of grt_pipeline_run_sky_radiances at that point; sum_k W_k is summed on the host in index order.
+ * Channels may overlap, repeat, come in any order and be one point wide; a weight may be negative (the side lobes of an
+ * apodised line shape) as long as the channel's sum is > 0.  The brightness temperature of a channel is
+ *   T_c = c2 v_c / log1p(c1 v_c^3 / R_c),      K,
+ * with planck_law's constants, +0.0 where R_c <= 0, at v_c = center[c], or -- center NULL -- the centroid sum_k W_k w_i /
+ * sum_k W_k of the grid's w_i = w0 + i dw: the monochromatic-equivalent temperature at the channel centre.  NO
+ * band-correction coefficients are applied: an instrument team's (a, b) of T = a + b T_c is the caller's to apply.
+ *   channel_radiances_dev  [ncol][N][A][2][C] (required);
+ *   channel_brightness_dev [ncol][N][A][2][C] (may be NULL).
+ * A cloud set's channel radiance is the mean over its num_subcolumns draws, taken as the integrated rows take theirs:
+ * draws 0 .. S - 1 in order, then one division by S; its brightness temperature is that of the mean radiance.  Channel
+ * outputs are therefore allowed with S > 1; radiances->spectral_radiances_dev and brightness_dev keep their S = 1 rule.
+ * A pipeline without a longwave band writes zeros to both channel outputs (and does not look at first and offset's
+ * range).  The sums are formed inside the radiance kernel (its channel form, GRT_TAG_RADIANCE) per channel and 128-point
+ * solver block the channel has a point in, in a fixed order without atomics -- a channel's value does not depend on the
+ * other channels, angles or columns of the call --, and finished by a kernel of one thread per output
+ * (GRT_TAG_CHANNELS).  The call takes max_columns x S x A x 2 x P doubles of scratch at the first call that needs more, P
+ * = grt_channel_pair_count(channels, n_lw); the device table of an instrument is kept and reused as long as first, offset,
+ * weights and center hold the same values.  In the deterministic mode every output grt_pipeline_run_sky_radiances also
+ * writes is grt_pipeline_run_sky_radiances', bit for bit.
+ * grt_channel_pair_count: host code only.  P, the number of (channel, 128-point solver block) pairs in which a channel has
+ * at least one point on a grid of num_points points; -1 for anything the entry point would refuse in `channels` (the
+ * two output pointers are not looked at) and for num_points < 1.
+ * GRTCODE_VALUE_ERR, with nothing launched and every output untouched, for: channels NULL; channel_radiances_dev NULL;
+ * first, offset or weights NULL; num_channels outside 1 .. GRT_MAX_CHANNELS; offset[0] != 0 or offset not strictly
+ * increasing; first[c] < 0 or first[c] + count_c > n_lw; a weight that is NaN or infinite; a channel's sum of weights not
+ * finite or <= 0; a center that is NaN, infinite or <= 0; everything grt_pipeline_run_sky_radiances refuses.
+ * Not covered: shortwave (scattered solar) radiances, radiances at interior levels, cloud fields sampled on the device,
+ * the example drivers, band-correction coefficients. */
+#define GRT_MAX_CHANNELS 16384
+typedef struct GrtChannels
+{
+    int num_channels;              /* C, 1 .. GRT_MAX_CHANNELS */
+    int const *first;              /* HOST [C]: grid index of the channel's first point in the longwave band */
+    int const *offset;             /* HOST [C + 1]: offset[0] = 0, strictly increasing; channel c has offset[c+1]-offset[c] points */
+    fp_t const *weights;           /* HOST [offset[C]]: the SRF sampled on the grid, channel after channel; any finite sign */
+    fp_t const *center;            /* HOST [C] cm-1, finite and > 0, or NULL: the weighted centroid sum W w / sum W */
+    fp_t *channel_radiances_dev;   /* DEVICE [ncol][N][A][2][C], W m-2 sr-1 per cm-1; required */
+    fp_t *channel_brightness_dev;  /* DEVICE [ncol][N][A][2][C], K; may be NULL */
+} GrtChannels_t;
+EXTERN long long grt_channel_pair_count(GrtChannels_t const *channels, long long num_points);
+EXTERN int grt_pipeline_run_sky_channels(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtSky_t const *sky,
+                                         GrtRadiances_t const *radiances, GrtChannels_t const *channels, fp_t *fluxes_dev);
 
 /* ---- spectral and band-integrated fluxes ---------------------------------------------------------------------------
  * driver.c's output without -integrated (output_fluxes, driver.c:285-356): the six rows of grt_pipeline_run at EVERY grid
@@ -855,7 +908,10 @@ enum
        fused instances count under grt_pipeline_run_sky's tags) */
     GRT_TAG_SURFACE_JACOBIAN = 24,
     /* 25 = the radiance kernel of grt_pipeline_run_sky_radiances (every set's, every draw's, in both forms) */
-    GRT_TAG_RADIANCE = 25
+    GRT_TAG_RADIANCE = 25,
+    /* 26 = the finishing kernel of grt_pipeline_run_sky_channels (one launch per set; the channel form of the radiance
+       kernel counts under 25) */
+    GRT_TAG_CHANNELS = 26
 };
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
