@@ -29,7 +29,7 @@ GRT_CLOUD_PHASE, GRT_CLOUD_MODEL, GRT_CLOUD_FIELDS = 7, 8, 9   # ... of GrtCloud
 (TAG_GAS_LW, TAG_GAS_SW, TAG_SOLVER_LW, TAG_SOLVER_SW, TAG_CLEAR_OPTICS, TAG_FAR_LW, TAG_FAR_SW, TAG_ALLSKY_LW,
  TAG_ALLSKY_SW, TAG_BINS, TAG_SUBCOLUMN_MEAN, TAG_AEROSOL_LW, TAG_AEROSOL_SW, TAG_BAND_PROFILES, TAG_SURFACE,
  TAG_CLOUD_SAMPLER, TAG_SKY_LW, TAG_SKY_SW, TAG_ZENITH_SW, TAG_ZENITH_MEAN, TAG_DIRECT_BEAM, TAG_SKY_ZENITH_SW,
- TAG_SKY_ZENITH_MEAN, TAG_SURFACE_JACOBIAN, TAG_RADIANCE, TAG_CHANNELS) = range(1, 27)
+ TAG_SKY_ZENITH_MEAN, TAG_SURFACE_JACOBIAN, TAG_RADIANCE, TAG_CHANNELS, TAG_WEIGHTING, TAG_WEIGHTING_FINISH) = range(1, 29)
 TAG_FAR_OFFSET = TAG_FAR_LW - TAG_GAS_LW    # from a line kernel's tag to its far-field gather's
 CLOUD_SAMPLER_TAG = TAG_CLOUD_SAMPLER
 GRT_MAX_SUBCOLUMNS = 64             # grt_pipeline_run_subcolumns: subcolumns per column, 1 .. this
@@ -203,6 +203,10 @@ class GrtChannels(C.Structure):
                 ("channel_brightness_dev", C.c_void_p)]
 
 
+class GrtWeighting(C.Structure):
+    _fields_ = [("transmittance_dev", C.c_void_p), ("contribution_dev", C.c_void_p)]
+
+
 class GrtZeniths(C.Structure):
     _fields_ = [("num_zeniths", C.c_int), ("cos_zenith", c_double_p), ("weight", c_double_p),
                 ("zenith_fluxes_dev", C.c_void_p), ("zenith_level_fluxes_dev", C.c_void_p)]
@@ -229,7 +233,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_channels grt_channel_pair_count grt_pipeline_run_sky_zeniths grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_channels grt_channel_pair_count grt_pipeline_run_sky_weighting grt_pipeline_run_sky_zeniths grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -300,6 +304,10 @@ def load_library(path=None):
                                                       C.POINTER(GrtRadiances), C.POINTER(GrtChannels), C.c_void_p]
         lib.grt_channel_pair_count.argtypes = [C.POINTER(GrtChannels), C.c_longlong]
         lib.grt_channel_pair_count.restype = C.c_longlong
+    if hasattr(lib, "grt_pipeline_run_sky_weighting"):   # (GRT_LIB_PATH may name an older library: a timing yardstick)
+        lib.grt_pipeline_run_sky_weighting.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky),
+                                                       C.POINTER(GrtRadiances), C.POINTER(GrtChannels),
+                                                       C.POINTER(GrtWeighting), C.c_void_p]
     lib.grt_pipeline_sky_set_count.argtypes = [C.c_uint]
     if hasattr(lib, "grt_pipeline_run_zeniths"):    # (GRT_LIB_PATH may name an older library: a timing yardstick)
         lib.grt_pipeline_run_zeniths.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtZeniths), C.c_void_p,
@@ -1163,6 +1171,43 @@ class Pipeline:
         coefficients applied)."""
         self.sync()
         return self.buffers["sky.channel_brightness"].to_host((ncol, nsets, nangles, GRT_RADIANCE_ROWS_PER_ANGLE, nchannels))
+
+    def run_sky_weighting(self, gcols, gsky, secants, gchannels, transmittance=True, contribution=True, brightness=False,
+                          spectral=False, fluxes=True):
+        """grt_pipeline_run_sky_weighting into this object's device buffers: run_sky_channels(gcols, gsky, secants,
+        gchannels, brightness=brightness, spectral=spectral, fluxes=fluxes) and with it, for the upward radiance at the
+        top, the channels' level-to-space transmittance profiles (transmittance=True; sky_channel_transmittances() reads
+        them) and contribution functions (contribution=True; sky_channel_contributions()).  Neither: the call refuses."""
+        m = _f64(secants)
+        if m.ndim != 2:
+            raise ValueError(f"secants of shape {m.shape}: [ncol][A]")
+        nsets = max(sky_set_count(gsky.sets), 1)
+        n, A, V = self.max_columns, max(m.shape[1], 1), self.num_levels
+        rows = n * nsets * A * GRT_RADIANCE_ROWS_PER_ANGLE
+        grad = GrtRadiances(m.shape[1], _dp(m), self._buffer("sky.radiances", 8 * rows).ptr,
+                            self._buffer("sky.spectral_radiances", 8 * rows * self.nw[0]).ptr if spectral else None, None)
+        nch = max(int(gchannels.num_channels), 1)
+        gchannels.channel_radiances_dev = self._buffer("sky.channel_radiances", 8 * rows * nch).ptr
+        gchannels.channel_brightness_dev = (self._buffer("sky.channel_brightness", 8 * rows * nch).ptr
+                                            if brightness else None)
+        per_level = 8 * n * nsets * A * nch
+        gw = GrtWeighting(self._buffer("sky.channel_transmittances", per_level * V).ptr if transmittance else None,
+                          self._buffer("sky.channel_contributions", per_level * (V + 1)).ptr if contribution else None)
+        out = self._sky_ptrs(gsky, False)[0][2] if fluxes else None
+        check(self.lib.grt_pipeline_run_sky_weighting(self.p, C.byref(gcols), C.byref(gsky), C.byref(grad),
+                                                      C.byref(gchannels), C.byref(gw), out))
+
+    def sky_channel_transmittances(self, ncol, nsets, nangles, nchannels):
+        """The last run_sky_weighting of nsets sets at nangles angles: [ncol][nsets][nangles][V][nchannels], dimensionless: per
+        channel the SRF-weighted mean of the transmittance from level v (0: the top; V - 1: the surface) to space."""
+        self.sync()
+        return self.buffers["sky.channel_transmittances"].to_host((ncol, nsets, nangles, self.num_levels, nchannels))
+
+    def sky_channel_contributions(self, ncol, nsets, nangles, nchannels):
+        """... [ncol][nsets][nangles][V + 1][nchannels], W m-2 sr-1 per cm-1: what each layer 0 .. V - 2, the surface's
+        emission (row V - 1) and the reflected downwelling (row V) add to the channel's upward radiance at the top."""
+        self.sync()
+        return self.buffers["sky.channel_contributions"].to_host((ncol, nsets, nangles, self.num_levels + 1, nchannels))
 
     def sky_fluxes(self, ncol, nsets):
         """The last six-row run_sky of nsets sets: [ncol][nsets][12], the sets in bit order, each in grt_pipeline_run's

@@ -592,6 +592,36 @@ static inline int grt_channel_args_ok(GrtChannelArgs const *c)
            c->block_chan != NULL && c->weights != NULL && c->sum_w != NULL && c->center != NULL && c->partials != NULL;
 }
 
+/* Channel transmittance profiles and contribution functions of the upward radiance at the top
+   (grt_pipeline_run_sky_weighting): lw_weighting_kernel, behind the channel form of lw_radiance_kernel on that launch's
+   arguments, instance and grid.  It makes the downward sweep only.  Per grid point and angle of the chunk, with e_j the
+   layer's extinction at the viewing secant: T_0 = 1, T_{j+1} = T_j e_j (level to space); K_j = ((1 - e_j) P_j) T_j, P_j
+   the upward sweep's effective Planck term; the downward radiance steps as lw_radiance_kernel's; after the last layer
+   K_L = (emis B(T_surf)) T_L and K_{L+1} = ((1 - emis) I_dn) T_L.  The reduction is a gather through LDS: per layer every
+   thread writes its point's T_j and K_j of each real angle to a tile [quantity][angle][point] (two tiles in turn, one
+   barrier a layer); then the workgroup's threads take the channels of the block's list in turn and each adds, per real
+   angle and quantity, W_c(i) value(i) over the channel's points inside the block in ascending point index, one sequential
+   sum from +0.0 each, and stores it at partials[((slot angles + angle) R + row) pairs + pair], the pair of
+   GrtChannelArgs' table.  Points outside a channel's span and idle lanes are never read.  Rows: R = (transmittance ? V :
+   0) + (contribution ? V + 1 : 0), the V transmittance rows (level 0 .. V - 1) first where both are asked for.
+   grt_launch_weighting_finish: one thread per (column, angle, row, channel), the channel fastest; per draw s = 0 .. S - 1
+   in order the channel's pairs in block order, then -- S > 1 -- one division by S, one by sum_w; row r of the
+   transmittances at transmittance[c t_stride + t_offset + (angle V + r) C + channel], of the contributions at
+   contribution[c k_stride + k_offset + (angle (V + 1) + r) C + channel].  c->partials is not read by either launch. */
+typedef struct GrtWeightingArgs
+{
+    int transmittance, contribution;    /* which of the two row groups leave (not both 0) */
+    double *partials;                   /* DEVICE [slot][angles][R][P] */
+} GrtWeightingArgs;
+static inline int grt_weighting_rows(GrtWeightingArgs const *w, int num_levels)
+{
+    return (w->transmittance ? num_levels : 0) + (w->contribution ? num_levels + 1 : 0);
+}
+static inline int grt_weighting_args_ok(GrtWeightingArgs const *w)
+{
+    return w != NULL && (w->transmittance || w->contribution) && w->partials != NULL;
+}
+
 /* Banded profile form of the two profile forms (GRT_OUT_LEVEL_BINS, clear sky or clouds joined;
    grt_pipeline_run_band_profiles): the profile form's arguments, sweeps and park block, but every level's
    flux leaves once per wavenumber bin that has a point in the workgroup's 128 grid points.  A point weights a level's
@@ -715,6 +745,13 @@ int grt_launch_lw_channels(void *stream, GrtSolverInstance const *in, GrtLwArgs 
                            GrtChannelArgs const *c);
 int grt_launch_channel_finish(void *stream, GrtChannelArgs const *c, int ncol, int subcolumns, int angles, double *out,
                               double *brightness, uint64_t out_stride, uint64_t out_offset);
+/* ... and the channels' transmittance profiles and contribution functions (GrtWeightingArgs): the same instance, grid and
+   arguments, c->partials not read */
+int grt_launch_lw_weighting(void *stream, GrtSolverInstance const *in, GrtLwArgs const *a, GrtRadianceArgs const *r,
+                            GrtChannelArgs const *c, GrtWeightingArgs const *w);
+int grt_launch_weighting_finish(void *stream, GrtChannelArgs const *c, GrtWeightingArgs const *w, int ncol, int subcolumns,
+                                int angles, int num_levels, double *transmittance, uint64_t t_stride, uint64_t t_offset,
+                                double *contribution, uint64_t k_stride, uint64_t k_offset);
 /* The subcolumn mean of the partial sums above, in a fixed order: for column c and row r (of `rows` per slot) each
    subcolumn's blocks are added as grt_launch_reduce_partials adds them, then the subcolumns s = 0 .. S - 1 in order, then
    the sum is divided by S; out[c out_stride + out_offset + r].  S = 1 gives grt_launch_reduce_partials' bits. */

@@ -530,6 +530,204 @@ __global__ __launch_bounds__(kChannelFinishBlock) void channel_finish_kernel(Grt
     }
 }
 
+// ---- channel transmittances and contribution functions (grt_launch_lw_weighting; GrtWeightingArgs, grt_kernels.h) ----
+// lw_weighting_kernel runs behind the channel form of lw_radiance_kernel on its arguments, instance and grid, and makes the
+// downward sweep only: going down it knows a level's transmittance to space T_j, the layer's contribution K_j = ((1 - e_j)
+// P_j) T_j to the upward radiance at the top and the downward radiance, and after the last layer the two surface rows.
+// The rows of a layer leave at once, so no thread holds a profile: every thread writes its point's T_j and K_j of the
+// chunk's real angles to an LDS tile [quantity][angle][point] -- consecutive threads, consecutive doubles --, and after a
+// barrier the workgroup's threads take the channels of the block's list in turn -- consecutive threads, consecutive pairs --
+// and each adds, per real angle and quantity, W_c(i) value(i) over the channel's points inside the block in ascending point
+// index, one sequential sum from +0.0 each, a weight loaded once for all of them.  Two tiles in turn: a thread may still
+// gather layer j while another writes layer j + 1, and the barrier of layer j + 1 lies between the gather of j and the
+// writes of j + 2.  Idle lanes of the last block follow along to the barriers; what they write is never read, a channel's
+// span lies on the grid.
+__device__ __forceinline__ void weighting_gather(GrtChannelArgs const &ch, GrtWeightingArgs const &wa,
+                                                 double const (&tile)[2][kRadianceChunk][kSolverBlock], int n, bool with_t,
+                                                 uint64_t angle_base, uint64_t R, int k_row0, int row)
+{
+    unsigned const block = blockIdx.x;
+    int const blk_lo = (int)block*kSolverBlock, blk_hi = blk_lo + kSolverBlock - 1;
+    int const k_lo = ch.block_start[block], nch = ch.block_start[block + 1] - k_lo;
+    bool const put_t = with_t && wa.transmittance, put_k = wa.contribution != 0;
+    // one thread per channel of the block's list: a weight is loaded once for the chunk's angles and both quantities
+    for (int k = threadIdx.x; k < nch; k += kSolverBlock)
+    {
+        int const *e = ch.chan + (uint64_t)GRT_CHANNEL_INTS*ch.block_chan[k_lo + k];
+        int const first = e[0], last = first + e[1] - 1;
+        int const lo = first > blk_lo ? first : blk_lo, hi = last < blk_hi ? last : blk_hi;
+        double const *W = ch.weights + (uint64_t)e[2] + (uint64_t)(lo - first);
+        int const at = lo - blk_lo, count = hi - lo + 1;
+        // (eight weight loads in flight ahead of the sums)
+        double st[kRadianceChunk] = {0., 0., 0., 0.}, sk[kRadianceChunk] = {0., 0., 0., 0.};
+#pragma unroll 8
+        for (int p = 0; p < count; ++p)
+        {
+            double const wp = W[p];
+#pragma unroll
+            for (int q = 0; q < kRadianceChunk; ++q)
+            {
+                if (q < n)
+                {
+                    st[q] += wp*tile[0][q][at + p];
+                    sk[q] += wp*tile[1][q][at + p];
+                }
+            }
+        }
+        uint64_t const pair = (uint64_t)e[4] + block - (unsigned)e[3];
+#pragma unroll
+        for (int q = 0; q < kRadianceChunk; ++q)
+        {
+            if (q < n)
+            {
+                double *to = wa.partials + ((angle_base + q)*R + (uint64_t)row)*ch.pairs + pair;
+                if (put_t)
+                {
+                    to[0] = st[q];
+                }
+                if (put_k)
+                {
+                    to[(uint64_t)k_row0*ch.pairs] = sk[q];
+                }
+            }
+        }
+    }
+}
+
+template <bool FUSED, typename... Joins>
+__global__ __launch_bounds__(kSolverBlock) void lw_weighting_kernel(GrtLwArgs a, GrtRadianceArgs r, GrtChannelArgs ch,
+                                                                    GrtWeightingArgs wa, Joins... joins)
+{
+    __shared__ double tile[2][2][kRadianceChunk][kSolverBlock];      // [turn][T, K][angle][point]: 16 KiB
+    uint64_t const i = (uint64_t)blockIdx.x*kSolverBlock + threadIdx.x;
+    SolverRow const row = solver_row(a.ncol, joins...);
+    int const col = row.col;
+    int const slot = FUSED ? row.slot : col*r.subcolumns + r.draw;
+    bool const live = i < a.nw;
+    uint64_t const ii = live ? i : a.nw - 1;      // (idle lanes of the last block follow along, never read)
+    int const V = a.num_levels;
+    int const L = V - 1;
+    double const w = a.w0 + ii*a.dw;                                     // longwave.c:246
+    double const *tau = a.tau + (uint64_t)col*a.optics_stride + ii;
+    double const *omega = (!FUSED && a.omega) ? a.omega + (uint64_t)col*a.optics_stride + ii : nullptr;
+    double const *tl = a.t_layers + (uint64_t)col*L;
+    double const *tv = a.t_levels + (uint64_t)col*V;
+    double const emis = a.emis[(uint64_t)col*a.emis_stride + ii];
+    LayerOptics<FUSED, has_clouds<Joins...>, has<GrtAerosolArgs, Joins...>> const optics(
+        a, pick_clouds(joins...), col, row.tab, ii, pick<GrtAerosolArgs>(joins...));                    // (fused forms)
+
+    // absorption optical depth of layer j: tau (1 - omega)  (longwave.c:252)
+    auto layer_tau = [&](int j) -> double
+    {
+        if (FUSED)
+        {
+            double t, om, gg;
+            optics.at(j, t, om, gg);
+            return t*(1. - om);
+        }
+        uint64_t const o = (uint64_t)j*a.nw;
+        return omega ? tau[o]*(1. - omega[o]) : tau[o]*(1. - 0.);
+    };
+
+    // this chunk's angles, as lw_radiance_kernel's
+    int const first = (int)blockIdx.z*kRadianceChunk;
+    int const n = r.angles - first < kRadianceChunk ? r.angles - first : kRadianceChunk;
+    double c1[kRadianceChunk];
+#pragma unroll
+    for (int q = 0; q < kRadianceChunk; ++q)
+    {
+        c1[q] = -r.secant[(uint64_t)col*r.angles + first + (q < n ? q : n - 1)];
+    }
+    uint64_t const R = (uint64_t)((wa.transmittance ? V : 0) + (wa.contribution ? V + 1 : 0));
+    uint64_t const angle_base = (uint64_t)slot*r.angles + first;
+    int const k_row0 = wa.transmittance ? V : 0;                         // (the transmittance rows come first)
+
+    double I[kRadianceChunk] = {0., 0., 0., 0.};
+    double T[kRadianceChunk] = {1., 1., 1., 1.};
+    for (int j = 0; j < L; ++j)
+    {
+        double const t = layer_tau(j);
+        double const bc = planck(tl[j], w);
+        double const val = effective_planck(bc, planck(tv[j + 1], w), t);        // the downward sweep's
+        double const up = effective_planck(bc, planck(tv[j], w), t);             // the upward sweep's: P_j
+        double (&tl_)[2][kRadianceChunk][kSolverBlock] = tile[j & 1];
+#pragma unroll
+        for (int q = 0; q < kRadianceChunk; ++q)
+        {
+            double const e = beam_extinction(c1[q], t);
+            if (q < n)
+            {
+                tl_[0][q][threadIdx.x] = T[q];
+                tl_[1][q][threadIdx.x] = ((1. - e)*up)*T[q];
+            }
+            I[q] = beam_step(I[q], val, e);
+            T[q] = T[q]*e;
+        }
+        __syncthreads();
+        weighting_gather(ch, wa, tl_, n, true, angle_base, R, k_row0, j);
+    }
+    // level L and the surface's emission, then the reflected downwelling (specular, longwave.c:202)
+    double const bs = planck(a.t_surf[col], w);
+    for (int u = L; u <= L + 1; ++u)
+    {
+        double (&tl_)[2][kRadianceChunk][kSolverBlock] = tile[u & 1];
+#pragma unroll
+        for (int q = 0; q < kRadianceChunk; ++q)
+        {
+            if (q < n)
+            {
+                tl_[0][q][threadIdx.x] = T[q];
+                tl_[1][q][threadIdx.x] = u == L ? (emis*bs)*T[q] : ((1 - emis)*I[q])*T[q];
+            }
+        }
+        __syncthreads();
+        weighting_gather(ch, wa, tl_, n, u == L, angle_base, R, k_row0, u);
+    }
+}
+
+// grt_launch_weighting_finish (grt_kernels.h): the rows' pairs into transmittance profiles and contribution functions
+__global__ __launch_bounds__(kChannelFinishBlock) void weighting_finish_kernel(GrtChannelArgs ch, GrtWeightingArgs wa, int ncol,
+                                                                               int S, int A, int V, double *transmittance,
+                                                                               uint64_t t_stride, uint64_t t_offset,
+                                                                               double *contribution, uint64_t k_stride,
+                                                                               uint64_t k_offset)
+{
+    uint64_t const t = (uint64_t)blockIdx.x*kChannelFinishBlock + threadIdx.x;
+    uint64_t const C = (uint64_t)ch.channels, R = (uint64_t)((wa.transmittance ? V : 0) + (wa.contribution ? V + 1 : 0));
+    if (t >= (uint64_t)ncol*A*R*C)
+    {
+        return;
+    }
+    uint64_t const c = t % C, r = (t/C) % R, angle = (t/(C*R)) % A, col = t/(C*R*A);
+    int const *e = ch.chan + GRT_CHANNEL_INTS*c;
+    int const npairs = (e[0] + e[1] - 1)/kSolverBlock - e[3] + 1;
+    double m = 0.;
+    for (int s = 0; s < S; ++s)
+    {
+        double const *p = wa.partials + (((col*S + s)*A + angle)*R + r)*ch.pairs + e[4];
+        double x = p[0];
+        for (int k = 1; k < npairs; ++k)
+        {
+            x += p[k];
+        }
+        m = s == 0 ? x : m + x;
+    }
+    if (S > 1)
+    {
+        m = m/(double)S;
+    }
+    double const out = m/ch.sum_w[c];
+    uint64_t const nt = wa.transmittance ? (uint64_t)V : 0;
+    if (r < nt)
+    {
+        transmittance[col*t_stride + t_offset + (angle*V + r)*C + c] = out;
+    }
+    else
+    {
+        contribution[col*k_stride + k_offset + (angle*(V + 1) + (r - nt))*C + c] = out;
+    }
+}
+
 // ---- spectral form of few columns: the layers' terms first, by one thread per (layer, wavenumber) ----
 // One column of the longwave band is 3 250 threads for lw_kernel<GRT_OUT_CHAINS> -- fifty waves on a thousand SIMDs, each with 120
 // dependent layer steps of six exp.  What costs in a step does not depend on the step before: lw_terms_kernel fills
@@ -658,6 +856,17 @@ int launch_radiances(hipStream_t s, GrtSolverInstance const &in, GrtLwArgs const
     return (int)hipGetLastError();
 }
 
+// ... and of lw_weighting_kernel, on the same grid
+template <bool FUSED, typename... Joins>
+int launch_weighting(hipStream_t s, GrtSolverInstance const &in, GrtLwArgs const &a, GrtRadianceArgs const &r,
+                     GrtChannelArgs const &c, GrtWeightingArgs const &w, Joins const &...joins)
+{
+    dim3 const grid(grt_solver_blocks(a.nw), (unsigned)grt_solver_grid_rows(&in, a.ncol),
+                    (unsigned)((r.angles + kRadianceChunk - 1)/kRadianceChunk));
+    hipLaunchKernelGGL((lw_weighting_kernel<FUSED, Joins...>), grid, dim3(kSolverBlock), 0, s, a, r, c, w, joins...);
+    return (int)hipGetLastError();
+}
+
 } // namespace
 
 extern "C" unsigned grt_solver_blocks(uint64_t nw)
@@ -749,9 +958,10 @@ extern "C" int grt_launch_lw_surface_jacobian(void *stream, GrtLwArgs const *a, 
     return (int)hipGetLastError();
 }
 
-// grt_launch_lw_radiances, or -- c given -- grt_launch_lw_channels: the instance of the join, with c last in its joins
+// grt_launch_lw_radiances, or -- c given -- grt_launch_lw_channels: the instance of the join, with c last in its joins; or
+// -- w given too -- grt_launch_lw_weighting: lw_weighting_kernel's instance of the join
 static int launch_lw_radiances(void *stream, GrtSolverInstance const *in, GrtLwArgs const *a, GrtRadianceArgs const *r,
-                               GrtChannelArgs const *c)
+                               GrtChannelArgs const *c, GrtWeightingArgs const *w = nullptr)
 {
     if (in == nullptr || a == nullptr || !grt_radiance_args_ok(r) || in->zeniths != nullptr || a->ncol < 1 || a->nw < 2 ||
         a->num_levels < 2 || grt_solver_grid_rows(in, a->ncol) > 65535 || a->t_layers == nullptr || a->t_levels == nullptr ||
@@ -770,6 +980,10 @@ static int launch_lw_radiances(void *stream, GrtSolverInstance const *in, GrtLwA
         {
             return (int)hipErrorInvalidValue;
         }
+        if (w != nullptr)
+        {
+            return launch_weighting<false>(s, *in, *a, *r, *c, *w);
+        }
         return c != nullptr ? launch_radiances<false>(s, *in, *a, *r, *c) : launch_radiances<false>(s, *in, *a, *r);
     }
     if (a->tau_gas == nullptr || a->n_layer == nullptr)
@@ -778,9 +992,13 @@ static int launch_lw_radiances(void *stream, GrtSolverInstance const *in, GrtLwA
     }
     auto fused = [&](auto const &...joins) -> int
     {
+        if (w != nullptr)
+        {
+            return launch_weighting<true>(s, *in, *a, *r, *c, *w, joins...);
+        }
         return c != nullptr ? launch_radiances<true>(s, *in, *a, *r, joins..., *c) : launch_radiances<true>(s, *in, *a, *r, joins...);
     };
-    // every fused instance of lw_radiance_kernel there is: one per join, and its channel form
+    // every fused instance of lw_radiance_kernel there is: one per join, and its channel form; and of lw_weighting_kernel
     switch (grt_solver_join(in))
     {
     case GRT_JOIN_NONE: return fused();
@@ -817,5 +1035,33 @@ extern "C" int grt_launch_channel_finish(void *stream, GrtChannelArgs const *c, 
     hipLaunchKernelGGL(channel_finish_kernel, dim3((unsigned)((threads + kChannelFinishBlock - 1)/kChannelFinishBlock)),
                        dim3(kChannelFinishBlock), 0, (hipStream_t)stream, *c, ncol, subcolumns, rows, out, brightness,
                        out_stride, out_offset);
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_lw_weighting(void *stream, GrtSolverInstance const *in, GrtLwArgs const *a, GrtRadianceArgs const *r,
+                                       GrtChannelArgs const *c, GrtWeightingArgs const *w)
+{
+    return grt_channel_args_ok(c) && grt_weighting_args_ok(w) ? launch_lw_radiances(stream, in, a, r, c, w) :
+                                                                  (int)hipErrorInvalidValue;
+}
+
+extern "C" int grt_launch_weighting_finish(void *stream, GrtChannelArgs const *c, GrtWeightingArgs const *w, int ncol,
+                                           int subcolumns, int angles, int num_levels, double *transmittance,
+                                           uint64_t t_stride, uint64_t t_offset, double *contribution, uint64_t k_stride,
+                                           uint64_t k_offset)
+{
+    if (!grt_channel_args_ok(c) || !grt_weighting_args_ok(w) || ncol < 1 || subcolumns < 1 || angles < 1 || num_levels < 2 ||
+        (w->transmittance && transmittance == nullptr) || (w->contribution && contribution == nullptr))
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    uint64_t const threads = (uint64_t)ncol*angles*(uint64_t)grt_weighting_rows(w, num_levels)*(uint64_t)c->channels;
+    if ((threads + kChannelFinishBlock - 1)/kChannelFinishBlock > 0x7fffffffull)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(weighting_finish_kernel, dim3((unsigned)((threads + kChannelFinishBlock - 1)/kChannelFinishBlock)),
+                       dim3(kChannelFinishBlock), 0, (hipStream_t)stream, *c, *w, ncol, subcolumns, angles, num_levels,
+                       transmittance, t_stride, t_offset, contribution, k_stride, k_offset);
     return (int)hipGetLastError();
 }

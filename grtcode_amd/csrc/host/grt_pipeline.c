@@ -499,6 +499,8 @@ typedef struct GrtJoin
                                           viewing angles too; rows->out NULL: and nothing else runs */
     GrtChannels_t const *channels;     /* grt_pipeline_run_sky_channels (with radiances): and the channels of an instrument */
     long long channel_pairs;           /* ... their (channel, solver block) pairs on the longwave grid (grt_check_channels) */
+    GrtWeighting_t const *weighting;   /* grt_pipeline_run_sky_weighting (with channels): and the channels' transmittance
+                                          profiles and contribution functions */
 } GrtJoin;
 
 #define GRT_SKY_ALL (GRT_SKY_CLEAN | GRT_SKY_AEROSOL | GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL)
@@ -562,6 +564,11 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
         GRT_TRY(grt_stage_channels(p, &p->band[0], join->channels, join->channel_pairs, &cr));
         cr.slots = (sets & (GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL)) != 0 ? S : 1;
     }
+    GrtWeightingRun wr;
+    if (join->weighting != NULL)
+    {
+        grt_stage_weighting(join->weighting, &wr);
+    }
     if (cl != NULL && join->sampler != NULL)
     {
         /* (the kernel writes the tables where grt_stage_clouds puts them) */
@@ -622,6 +629,7 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
         GrtPass ps = *rows;
         ps.radiances = bi == 0 && join->radiances != NULL ? &rr : NULL;
         ps.channels = bi == 0 && join->channels != NULL ? &cr : NULL;
+        ps.weighting = ps.channels != NULL && join->weighting != NULL ? &wr : NULL;
         GrtAerosolArgs aa;
         int const band_aer = ae != NULL && grt_aerosol_points(ae, bi) > 0;
         int aa_ready = 0;
@@ -1181,7 +1189,8 @@ EXTERN int grt_pipeline_run_sky_jacobian(GrtPipeline_t *p, GrtColumns_t const *c
 /* grt_pipeline_run_sky_radiances, and -- channels_asked -- grt_pipeline_run_sky_channels, which is the same call with the
    channels of an instrument (ch; checked here, NULL included) */
 static int run_sky_radiances(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky, GrtRadiances_t const *rd,
-                             int channels_asked, GrtChannels_t const *ch, fp_t *fluxes_dev)
+                             int channels_asked, GrtChannels_t const *ch, int weighting_asked, GrtWeighting_t const *wt,
+                             fp_t *fluxes_dev)
 {
     GRT_REQUIRE_PTR(p);
     GRT_REQUIRE_PTR(cols);
@@ -1206,6 +1215,10 @@ static int run_sky_radiances(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_
                      "the output.", GRT_RADIANCE_ROWS_PER_ANGLE, ch->num_channels);
         }
     }
+    if (weighting_asked)
+    {
+        GRT_TRY(grt_check_weighting(wt));
+    }
     int const spectral = rd->spectral_radiances_dev != NULL || rd->brightness_dev != NULL;
     if (spectral && join.subcolumns > 0)
     {
@@ -1216,6 +1229,7 @@ static int run_sky_radiances(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_
     join.radiances = rd;
     join.channels = channels_asked ? ch : NULL;
     join.channel_pairs = pairs;
+    join.weighting = weighting_asked ? wt : NULL;
     GrtPass rows;
     memset(&rows, 0, sizeof(rows));
     rows.out = fluxes_dev;
@@ -1237,6 +1251,19 @@ static int run_sky_radiances(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_
             {
                 GRT_TRY(grt_dev_zero(p->device, ch->channel_brightness_dev, bytes, s));
             }
+            if (weighting_asked)
+            {
+                size_t const per_level = sizeof(double)*(size_t)cols->ncol*(size_t)nsets*(size_t)rd->num_angles*
+                                         (size_t)ch->num_channels;
+                if (wt->transmittance_dev != NULL)
+                {
+                    GRT_TRY(grt_dev_zero(p->device, wt->transmittance_dev, per_level*(size_t)p->num_levels, s));
+                }
+                if (wt->contribution_dev != NULL)
+                {
+                    GRT_TRY(grt_dev_zero(p->device, wt->contribution_dev, per_level*((size_t)p->num_levels + 1), s));
+                }
+            }
         }
     }
     return GRTCODE_SUCCESS;
@@ -1247,14 +1274,22 @@ static int run_sky_radiances(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_
 EXTERN int grt_pipeline_run_sky_radiances(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky,
                                           GrtRadiances_t const *rd, fp_t *fluxes_dev)
 {
-    return run_sky_radiances(p, cols, sky, rd, 0, NULL, fluxes_dev);
+    return run_sky_radiances(p, cols, sky, rd, 0, NULL, 0, NULL, fluxes_dev);
 }
 
 /* grt_ext.h: ... and the radiances and brightness temperatures of an instrument's channels */
 EXTERN int grt_pipeline_run_sky_channels(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky,
                                          GrtRadiances_t const *rd, GrtChannels_t const *ch, fp_t *fluxes_dev)
 {
-    return run_sky_radiances(p, cols, sky, rd, 1, ch, fluxes_dev);
+    return run_sky_radiances(p, cols, sky, rd, 1, ch, 0, NULL, fluxes_dev);
+}
+
+/* grt_ext.h: ... and the channels' level-to-space transmittance profiles and contribution functions */
+EXTERN int grt_pipeline_run_sky_weighting(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky,
+                                          GrtRadiances_t const *rd, GrtChannels_t const *ch, GrtWeighting_t const *wt,
+                                          fp_t *fluxes_dev)
+{
+    return run_sky_radiances(p, cols, sky, rd, 1, ch, 1, wt, fluxes_dev);
 }
 
 /* grt_ext.h: the (channel, solver block) pairs of an instrument on a grid of num_points; -1: channels the call refuses */

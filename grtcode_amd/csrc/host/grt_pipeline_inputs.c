@@ -762,6 +762,32 @@ int grt_stage_channels(GrtPipeline_t *p, GrtBand *b, GrtChannels_t const *ch, lo
     return GRTCODE_SUCCESS;
 }
 
+/* ---- channel transmittances and contribution functions (grt_pipeline_run_sky_weighting) ---- */
+
+/* What grt_pipeline_run_sky_weighting checks of its own argument.  Nothing is touched. */
+int grt_check_weighting(GrtWeighting_t const *wt)
+{
+    if (wt == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "weighting (GrtWeighting_t) is NULL: %s", "it names the outputs.");
+    }
+    if (wt->transmittance_dev == NULL && wt->contribution_dev == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "transmittance_dev and contribution_dev are both NULL: %s", "one of them is the output.");
+    }
+    return GRTCODE_SUCCESS;
+}
+
+/* ... staged: nothing of it lies on the host */
+void grt_stage_weighting(GrtWeighting_t const *wt, GrtWeightingRun *wr)
+{
+    memset(wr, 0, sizeof(*wr));
+    wr->args.transmittance = wt->transmittance_dev != NULL;
+    wr->args.contribution = wt->contribution_dev != NULL;
+    wr->transmittance = wt->transmittance_dev;
+    wr->contribution = wt->contribution_dev;
+}
+
 typedef struct BinTableFill { int const *edges; int nbins; uint64_t n; size_t per_row; } BinTableFill;
 
 static int fill_bin_table(void *ctx, int *table)

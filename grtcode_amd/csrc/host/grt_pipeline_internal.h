@@ -76,6 +76,10 @@ enum
        solver block) pair of every angle and cloud draw, S the draws of the call's cloud sets (1 without one) for every
        set of the call; sized at the first call that needs more */
     GRT_SCRATCH_CHANNEL_PARTIALS,
+    /* grt_pipeline_run_sky_weighting, longwave, both forms: [max_cols][S][A][R][P] the partial sums of the channels'
+       transmittance and contribution rows per (channel, solver block) pair, S as above, R the rows asked for (V
+       transmittances, V + 1 contributions; 2 V + 1 for both); sized at the first call that needs more */
+    GRT_SCRATCH_WEIGHTING_PARTIALS,
     GRT_SCRATCH_COUNT
 };
 
@@ -175,6 +179,15 @@ typedef struct GrtChannelRun
                                        call's first set sizes GRT_SCRATCH_CHANNEL_PARTIALS for all of them */
 } GrtChannelRun;
 
+/* The profiles of a grt_pipeline_run_sky_weighting call, staged (grt_stage_weighting): which row groups leave
+   (args.partials: set by the pass's launch), and where every set's go. */
+typedef struct GrtWeightingRun
+{
+    GrtWeightingArgs args;
+    double *transmittance;          /* DEVICE [ncol][sets][A][V][C], or NULL */
+    double *contribution;           /* DEVICE [ncol][sets][A][V + 1][C], or NULL */
+} GrtWeightingRun;
+
 /* One solve of a band on the run's tau_gas.  What joins gas and Rayleigh: nothing (clear sky), the cloud objects (all-sky
    pass), the aerosol object (aerosol pass; aer NULL there: a band that was given no aerosol, which runs the form without
    the object under the aerosol pass's profile tags) or both (grt_pipeline_run_sky's complete set).  Which rows leave: the six of driver.c:272-280 or (profile) every level's
@@ -205,6 +218,9 @@ typedef struct GrtPass
     /* grt_pipeline_run_sky_channels (NULL: not asked for; with radiances only): that kernel in its channel form, and the
        channels' finishing kernel behind it */
     GrtChannelRun const *channels;
+    /* grt_pipeline_run_sky_weighting (NULL: not asked for; with channels only): the weighting kernel behind that one, and
+       its finishing kernel beside the channels' */
+    GrtWeightingRun const *weighting;
 } GrtPass;
 
 /* The sun angles of a grt_pipeline_run_zeniths or grt_pipeline_run_sky_zeniths call, staged (grt_stage_zeniths): Z per column, their cosines and weights
@@ -257,6 +273,8 @@ GRT_PRIVATE int grt_stage_radiances(GrtPipeline_t *p, GrtRadiances_t const *rd, 
 GRT_PRIVATE int grt_check_channels(GrtChannels_t const *ch, long long n, long long *pairs);
 GRT_PRIVATE int grt_stage_channels(GrtPipeline_t *p, GrtBand *b, GrtChannels_t const *ch, long long pairs,
                                    GrtChannelRun *cr);
+GRT_PRIVATE int grt_check_weighting(GrtWeighting_t const *wt);
+GRT_PRIVATE void grt_stage_weighting(GrtWeighting_t const *wt, GrtWeightingRun *wr);
 GRT_PRIVATE int grt_band_bins(GrtPipeline_t *p, GrtBand *b, int const *edges, int nbins, int rows);
 
 /* grt_pipeline_solve.c */

@@ -293,6 +293,19 @@ static int band_radiances(GrtPipeline_t *p, GrtBand *b, int C, int S, int draw, 
         GRT_TRY(grt_scratch_need(p, pairs, (size_t)p->max_cols*(size_t)slots*per_slot*(size_t)ch.pairs, NULL));
         ch.partials = pairs->d;
     }
+    /* (grt_pipeline_run_sky_weighting: the weighting kernel's pairs' sums to GRT_SCRATCH_WEIGHTING_PARTIALS,
+       [max_cols][S][A][R][P]; the largest block of the call, asked for before either kernel of the pass is queued) */
+    GrtWeightingArgs wa;
+    memset(&wa, 0, sizeof(wa));
+    if (ps->weighting != NULL)
+    {
+        wa = ps->weighting->args;
+        GrtScratch *wpairs = &b->scratch[GRT_SCRATCH_WEIGHTING_PARTIALS];
+        int const wslots = ps->channels->slots > S ? ps->channels->slots : S;
+        GRT_TRY(grt_scratch_need(p, wpairs, (size_t)p->max_cols*(size_t)wslots*(size_t)rr->angles*
+                                                (size_t)grt_weighting_rows(&wa, p->num_levels)*(size_t)ch.pairs, NULL));
+        wa.partials = wpairs->d;
+    }
     int const slot = grt_profile_begin(s, GRT_TAG_RADIANCE);
     int krc = 0;
     if (sc != NULL)
@@ -311,6 +324,27 @@ static int band_radiances(GrtPipeline_t *p, GrtBand *b, int C, int S, int draw, 
     }
     grt_profile_end(s, slot);
     GRT_TRY(grt_dev_check(krc, "longwave radiance kernel"));
+    if (ps->weighting == NULL)
+    {
+        return GRTCODE_SUCCESS;
+    }
+    /* (the weighting kernel behind it on the same instance and arguments, GRT_TAG_WEIGHTING) */
+    int const wslot = grt_profile_begin(s, GRT_TAG_WEIGHTING);
+    if (sc != NULL)
+    {
+        int const group = 65535/C < S ? 65535/C : S;                  /* (grid rows) */
+        for (sc->first = 0; sc->first < S && krc == 0; sc->first += group)
+        {
+            sc->count = S - sc->first < group ? S - sc->first : group;
+            krc = grt_launch_lw_weighting(s, &in, &a.lw, &r, &ch, &wa);
+        }
+    }
+    else
+    {
+        krc = grt_launch_lw_weighting(s, &in, &a.lw, &r, &ch, &wa);
+    }
+    grt_profile_end(s, wslot);
+    GRT_TRY(grt_dev_check(krc, "longwave weighting kernel"));
     return GRTCODE_SUCCESS;
 }
 
@@ -355,6 +389,32 @@ static int finish_channels(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass c
                                               (uint64_t)ps->sets*set_doubles, (uint64_t)ps->set*set_doubles);
     grt_profile_end(s, slot);
     GRT_TRY(grt_dev_check(krc, "channel finishing kernel"));
+    return GRTCODE_SUCCESS;
+}
+
+/* ... and -- grt_pipeline_run_sky_weighting -- the rows' sums of the S draws into the pass's set of the transmittances
+   [ncol][sets][A][V][C] and contributions [ncol][sets][A][V + 1][C] (GRT_TAG_WEIGHTING_FINISH); a pass without: nothing */
+static int finish_weighting(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass const *ps)
+{
+    if (ps->weighting == NULL)
+    {
+        return GRTCODE_SUCCESS;
+    }
+    GrtWeightingRun const *wr = ps->weighting;
+    void *s = grt_dev_stream(p->device);
+    GrtChannelArgs ch = ps->channels->args;
+    ch.partials = b->scratch[GRT_SCRATCH_CHANNEL_PARTIALS].d;
+    GrtWeightingArgs wa = wr->args;
+    wa.partials = b->scratch[GRT_SCRATCH_WEIGHTING_PARTIALS].d;
+    int const A = ps->radiances->angles, V = p->num_levels;
+    uint64_t const t_set = (uint64_t)A*(uint64_t)V*(uint64_t)ch.channels;
+    uint64_t const k_set = (uint64_t)A*(uint64_t)(V + 1)*(uint64_t)ch.channels;
+    int const slot = grt_profile_begin(s, GRT_TAG_WEIGHTING_FINISH);
+    int const krc = grt_launch_weighting_finish(s, &ch, &wa, C, S, A, V, wr->transmittance, (uint64_t)ps->sets*t_set,
+                                                (uint64_t)ps->set*t_set, wr->contribution, (uint64_t)ps->sets*k_set,
+                                                (uint64_t)ps->set*k_set);
+    grt_profile_end(s, slot);
+    GRT_TRY(grt_dev_check(krc, "weighting finishing kernel"));
     return GRTCODE_SUCCESS;
 }
 
@@ -644,6 +704,7 @@ int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *p
             GRT_TRY(band_radiances(p, b, C, 1, 0, ps, NULL));
             GRT_TRY(finish_radiances(p, b, C, 1, ps));
             GRT_TRY(finish_channels(p, b, C, 1, ps));
+            GRT_TRY(finish_weighting(p, b, C, 1, ps));
         }
         return GRTCODE_SUCCESS;
     }
@@ -676,6 +737,7 @@ int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *p
         GRT_TRY(band_radiances(p, b, C, 1, 0, ps, NULL));
         GRT_TRY(finish_radiances(p, b, C, 1, ps));
         GRT_TRY(finish_channels(p, b, C, 1, ps));
+        GRT_TRY(finish_weighting(p, b, C, 1, ps));
     }
     return GRTCODE_SUCCESS;
 }
@@ -698,6 +760,7 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
         GRT_TRY(band_radiances(p, b, C, S, 0, ps, &sc));
         GRT_TRY(finish_radiances(p, b, C, S, ps));
         GRT_TRY(finish_channels(p, b, C, S, ps));
+        GRT_TRY(finish_weighting(p, b, C, S, ps));
         return GRTCODE_SUCCESS;
     }
     if (!p->keep_spectra)
@@ -730,6 +793,7 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
             GRT_TRY(band_radiances(p, b, C, S, 0, ps, &sc));
             GRT_TRY(finish_radiances(p, b, C, S, ps));
             GRT_TRY(finish_channels(p, b, C, S, ps));
+            GRT_TRY(finish_weighting(p, b, C, S, ps));
         }
         if (S == 1)
         {
@@ -795,6 +859,7 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
     {
         GRT_TRY(finish_radiances(p, b, C, S, ps));
         GRT_TRY(finish_channels(p, b, C, S, ps));
+        GRT_TRY(finish_weighting(p, b, C, S, ps));
     }
     if (ps->out == NULL)
     {

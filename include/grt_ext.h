@@ -630,6 +630,48 @@ EXTERN long long grt_channel_pair_count(GrtChannels_t const *channels, long long
 EXTERN int grt_pipeline_run_sky_channels(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtSky_t const *sky,
                                          GrtRadiances_t const *radiances, GrtChannels_t const *channels, fp_t *fluxes_dev);
 
+/* ---- channel transmittance profiles and contribution functions, of every sky set -----------------------------------
+ * grt_pipeline_run_sky_channels in every respect -- the sets and their packing, the viewing secants, every output of
+ * `radiances` and `channels`, fluxes_dev NULL or not, the surface in force, the input checks, asynchronous on the
+ * pipeline's lane, both forms of the pipeline -- and with it, for the UPWARD RADIANCE AT THE TOP OF THE ATMOSPHERE only,
+ * per column, set, viewing angle and channel the level-to-space transmittance profile (its differences are the weighting
+ * function) and the contribution function: how much of that radiance comes from each layer, from the surface's emission
+ * and from the reflected downwelling.  Per longwave grid point i, draw and viewing secant m, in the radiance kernel's own
+ * expressions: t_j = tau_j (1 - omega_j); e_j = exp(min((-m) t_j, 700)); T_0 = 1, T_{j+1} = T_j e_j (level 0 the top,
+ * level V - 1 the surface); P_j = effective_planck(B(T_layer j), B(T_level j), t_j), the upward sweep's; I_dn the downward
+ * radiance at the surface as grt_pipeline_run_sky_radiances forms it; and V + 1 contribution rows
+ *   K_j     = ((1 - e_j) P_j) T_j          layer j = 0 .. L - 1 (L = V - 1),
+ *   K_L     = (emis B(T_surf)) T_L         the surface's emission,
+ *   K_{L+1} = ((1 - emis) I_dn) T_L        the reflected downwelling (specular),
+ * whose sum is the upward radiance of grt_pipeline_run_sky_radiances at that point up to rounding.  Both are linear in
+ * the per-point values, so their SRF-weighted means are exact; with the W_k and sum of grt_pipeline_run_sky_channels
+ *   transmittance[v][c] = sum_k W_k T_v(i) / sum_k W_k,      dimensionless,
+ *   contribution[r][c]  = sum_k W_k K_r(i) / sum_k W_k,      W m-2 sr-1 per cm-1.
+ *   transmittance_dev [ncol][N][A][V][C]     (may be NULL);
+ *   contribution_dev  [ncol][N][A][V + 1][C] (may be NULL; not both).
+ * A cloud set of S draws gives the mean over the draws 0 .. S - 1 in order, then one division by S; the profiles are
+ * allowed with S > 1, as the channel outputs are.  A pipeline without a longwave band writes zeros to both.
+ * A kernel of its own (GRT_TAG_WEIGHTING) runs behind the radiance kernel of grt_pipeline_run_sky_channels, whose launches
+ * are queued unchanged: in the deterministic mode every output that call also writes is that call's, bit for bit.  It
+ * makes the downward sweep only and sums each row per channel and 128-point solver block in ascending point index,
+ * without atomics: a value does not depend on the other channels, angles or columns of the call, and repeated calls are
+ * bit-identical in either mode.  A kernel of one thread per output finishes (GRT_TAG_WEIGHTING_FINISH).  Scratch, beside
+ * grt_pipeline_run_sky_channels': max_columns x S x A x R x P doubles at the first call that needs more, P =
+ * grt_channel_pair_count(channels, n_lw), S the draws of the call's cloud sets (1 without one), R the rows asked for: V
+ * for the transmittances plus V + 1 for the contributions, 2 V + 1 for both.
+ * GRTCODE_VALUE_ERR, with nothing launched and every output untouched, for: weighting NULL; both of its pointers NULL;
+ * everything grt_pipeline_run_sky_channels refuses.
+ * Not covered: the contributions to the downward radiance, observer levels inside the atmosphere, per-point (spectral)
+ * profiles, shortwave, cloud fields sampled on the device, the example drivers. */
+typedef struct GrtWeighting
+{
+    fp_t *transmittance_dev;   /* DEVICE [ncol][N][A][V][C], dimensionless; may be NULL */
+    fp_t *contribution_dev;    /* DEVICE [ncol][N][A][V + 1][C], W m-2 sr-1 per cm-1; may be NULL */
+} GrtWeighting_t;              /* not both NULL */
+EXTERN int grt_pipeline_run_sky_weighting(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtSky_t const *sky,
+                                          GrtRadiances_t const *radiances, GrtChannels_t const *channels,
+                                          GrtWeighting_t const *weighting, fp_t *fluxes_dev);
+
 /* ---- spectral and band-integrated fluxes ---------------------------------------------------------------------------
  * driver.c's output without -integrated (output_fluxes, driver.c:285-356): the six rows of grt_pipeline_run at EVERY grid
  * point, and -- where the caller gives bin edges -- the same rows integrated over wavenumber bins, for a batch of columns,
@@ -911,7 +953,11 @@ enum
     GRT_TAG_RADIANCE = 25,
     /* 26 = the finishing kernel of grt_pipeline_run_sky_channels (one launch per set; the channel form of the radiance
        kernel counts under 25) */
-    GRT_TAG_CHANNELS = 26
+    GRT_TAG_CHANNELS = 26,
+    /* 27 = the transmittance and contribution kernel of grt_pipeline_run_sky_weighting (every set's, every draw's, in both
+       forms); 28 = its finishing kernel (one launch per set) */
+    GRT_TAG_WEIGHTING = 27,
+    GRT_TAG_WEIGHTING_FINISH = 28
 };
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
