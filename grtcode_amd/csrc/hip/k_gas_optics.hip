@@ -168,6 +168,11 @@ __global__ __launch_bounds__(kBlock) void gas_optics_kernel(GrtGasOpticsArgs a, 
         float const dc = (float)(wnoadj - ((double)c*a.wres + a.w0));
         float const cl = (repwid*y)*0.318309886f;                                     // 1/pi
         float const x0q = lorentz ? 0.f : xlim0*xlim0;
+        // y^2 of the FAST form's Lorentzian.  A line without a Lorentz width (y = 0: pure Doppler, :122-126) has cl = 0,
+        // and with its centre exactly on a grid point cl/(0 + 0) was 0 x inf = NaN in the ring and in the queue's kfar;
+        // y^2 below fp32's reciprocal range likewise.  Any denominator will do for such a line: its Lorentzian is below
+        // 1e-15 of its peak wherever the exact value does not replace it.
+        float const yq_lor = yq > 1e-30f ? yq : 1.f;
         // reference-order form
         float const num = repwid*y;                                                   // :103
         float const yrrtpi = y*kRsqrpi;                                               // :108
@@ -216,7 +221,7 @@ __global__ __launch_bounds__(kBlock) void gas_optics_kernel(GrtGasOpticsArgs a, 
                 float kfar = 0.f;
                 if (FAST && near)
                 {
-                    kfar = voigt_lorentzian_fast(cl, xi, yq);
+                    kfar = voigt_lorentzian_fast(cl, xi, yq_lor);
                 }
                 if (inner & !near)
                 {
@@ -274,7 +279,7 @@ __global__ __launch_bounds__(kBlock) void gas_optics_kernel(GrtGasOpticsArgs a, 
                     if (FAST)
                     {
                         float const xi = fmaf((float)(f - c), wr, ndcr);
-                        float const kf = voigt_lorentzian_fast(cl, xi, yq);
+                        float const kf = voigt_lorentzian_fast(cl, xi, yq_lor);
                         GRT_ACC_ADD(&acc[f - F0], amp*(double)kf);
                     }
                     else
@@ -316,7 +321,7 @@ __global__ __launch_bounds__(kBlock) void gas_optics_kernel(GrtGasOpticsArgs a, 
                 {
                     float const rel = base_rel + (float)slot;
                     float const xi = fmaf(rel, wr, ndcr);
-                    float kf = (fabsf(rel - mid) <= half) ? voigt_lorentzian_fast(cl, xi, yq) : 0.f;
+                    float kf = (fabsf(rel - mid) <= half) ? voigt_lorentzian_fast(cl, xi, yq_lor) : 0.f;
                     asm volatile("" : "+v"(kf));    // select in fp32, then widen once
                     token = fma(amp, (double)kf, token);
                     token = ring_pass(token);

@@ -41,8 +41,8 @@ def run(band, device, col, fast, tile=0, nslice=0, from_file=False):
 LEAN_TOL = 1.5e-6
 
 
-def check(band, device, oracle, lib, col, **kw):
-    want = band.oracle_tau(oracle, oracle, lib, col)
+def fused_forms(band, device, col, **kw):
+    """The four fused forms of one case: (moment kernel, ring kernel, lean two-pass, two-pass with the general loop)."""
     mp = run(band, device, col, 1, **kw)
     ring = run(band, device, col, 2, **kw)
     lean = run(band, device, col, 3, **kw)              # two-pass form: cell moments through global memory; lean line loop
@@ -51,6 +51,19 @@ def check(band, device, oracle, lib, col, **kw):
         two = run(band, device, col, 3, **kw)           # ... with the general line loop: the one-pass form's arithmetic
     finally:
         del os.environ["GRT_LEAN"]
+    return mp, ring, lean, two
+
+
+def check(band, device, oracle, lib, col, **kw):
+    want = band.oracle_tau(oracle, oracle, lib, col)
+    forms = fused_forms(band, device, col, **kw)
+    check_layer_norm(band, device, col, want, forms, **kw)
+    return forms[0], want
+
+
+def check_layer_norm(band, device, col, want, forms, **kw):
+    """The fused forms against the oracle and against each other, each error over its layer's largest optical depth."""
+    mp, ring, lean, two = forms
     e_mp, e_ring, e_between = tau_close(mp, want), tau_close(ring, want), tau_close(mp, ring)
     e_two, e_forms = tau_close(two, want), tau_close(two, mp)
     e_lean, e_lean_two = tau_close(lean, want), tau_close(lean, two)
@@ -70,7 +83,6 @@ def check(band, device, oracle, lib, col, **kw):
     # fast=1 is the ring kernel itself and the comparison is the one above): a handful of fp32 roundings of a layer's
     # largest tau apart (a soak of 5 000 cases met 3.15e-7 once)
     assert e_forms < (6e-7 if e_between > 1e-12 else BETWEEN_TOL)
-    return mp, want
 
 
 @pytest.mark.parametrize("tile,nslice", [(0, 0), (64, 1), (128, 3), (1024, 2)])
