@@ -29,7 +29,8 @@ GRT_CLOUD_PHASE, GRT_CLOUD_MODEL, GRT_CLOUD_FIELDS = 7, 8, 9   # ... of GrtCloud
 (TAG_GAS_LW, TAG_GAS_SW, TAG_SOLVER_LW, TAG_SOLVER_SW, TAG_CLEAR_OPTICS, TAG_FAR_LW, TAG_FAR_SW, TAG_ALLSKY_LW,
  TAG_ALLSKY_SW, TAG_BINS, TAG_SUBCOLUMN_MEAN, TAG_AEROSOL_LW, TAG_AEROSOL_SW, TAG_BAND_PROFILES, TAG_SURFACE,
  TAG_CLOUD_SAMPLER, TAG_SKY_LW, TAG_SKY_SW, TAG_ZENITH_SW, TAG_ZENITH_MEAN, TAG_DIRECT_BEAM, TAG_SKY_ZENITH_SW,
- TAG_SKY_ZENITH_MEAN, TAG_SURFACE_JACOBIAN, TAG_RADIANCE, TAG_CHANNELS, TAG_WEIGHTING, TAG_WEIGHTING_FINISH) = range(1, 29)
+ TAG_SKY_ZENITH_MEAN, TAG_SURFACE_JACOBIAN, TAG_RADIANCE, TAG_CHANNELS, TAG_WEIGHTING, TAG_WEIGHTING_FINISH,
+ TAG_KDIST) = range(1, 30)
 TAG_FAR_OFFSET = TAG_FAR_LW - TAG_GAS_LW    # from a line kernel's tag to its far-field gather's
 CLOUD_SAMPLER_TAG = TAG_CLOUD_SAMPLER
 GRT_MAX_SUBCOLUMNS = 64             # grt_pipeline_run_subcolumns: subcolumns per column, 1 .. this
@@ -44,6 +45,7 @@ GRT_JACOBIAN_ROWS_PER_SET = 3       # grt_pipeline_run_sky_jacobian: dF_up/dT_su
 GRT_MAX_VIEW_ANGLES = 16            # grt_pipeline_run_sky_radiances: viewing angles per column, 1 .. this
 GRT_RADIANCE_ROWS_PER_ANGLE = 2     # ... per angle: upward at the top of the atmosphere, downward at the surface
 GRT_MAX_CHANNELS = 16384            # grt_pipeline_run_sky_channels: channels of an instrument, 1 .. this
+KDIST_MAX_CLASSES = 1024            # grt_pipeline_run_kdist, grt_kdist_rows: classes of a k-distribution, 2 .. this
 RETURN_CODES = ["GRTCODE_SUCCESS", "GRTCODE_INVALID_ERR", "GRTCODE_DIVBYZERO_ERR", "GRTCODE_OVERFLOW_ERR",
                 "GRTCODE_UNDERFLOW_ERR", "GRTCODE_SENTINEL_ERR", "GRTCODE_NULL_ERR", "GRTCODE_NON_NULL_ERR",
                 "GRTCODE_RANGE_ERR", "GRTCODE_VALUE_ERR", "GRTCODE_COMPILER_ERR", "GRTCODE_IO_ERR",
@@ -207,6 +209,15 @@ class GrtWeighting(C.Structure):
     _fields_ = [("transmittance_dev", C.c_void_p), ("contribution_dev", C.c_void_p)]
 
 
+class GrtKdistBand(C.Structure):
+    _fields_ = [("edges", C.POINTER(C.c_int)), ("num_bins", C.c_int), ("weight", c_double_p), ("points_dev", C.c_void_p),
+                ("weight_dev", C.c_void_p), ("tau_dev", C.c_void_p)]
+
+
+class GrtKdist(C.Structure):
+    _fields_ = [("num_classes", C.c_int), ("class_edges", c_double_p), ("lw", GrtKdistBand), ("sw", GrtKdistBand)]
+
+
 class GrtZeniths(C.Structure):
     _fields_ = [("num_zeniths", C.c_int), ("cos_zenith", c_double_p), ("weight", c_double_p),
                 ("zenith_fluxes_dev", C.c_void_p), ("zenith_level_fluxes_dev", C.c_void_p)]
@@ -233,7 +244,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_channels grt_channel_pair_count grt_pipeline_run_sky_weighting grt_pipeline_run_sky_zeniths grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_channels grt_channel_pair_count grt_pipeline_run_sky_weighting grt_pipeline_run_sky_zeniths grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_kdist_rows grt_pipeline_run_kdist grt_kdist_chunk_points grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -308,6 +319,11 @@ def load_library(path=None):
         lib.grt_pipeline_run_sky_weighting.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky),
                                                        C.POINTER(GrtRadiances), C.POINTER(GrtChannels),
                                                        C.POINTER(GrtWeighting), C.c_void_p]
+    if hasattr(lib, "grt_pipeline_run_kdist"):           # (GRT_LIB_PATH may name an older library: a timing yardstick)
+        lib.grt_kdist_rows.argtypes = [C.c_int, C.c_void_p, C.c_longlong, C.c_longlong, C.c_double, C.c_int, c_double_p,
+                                       C.POINTER(GrtKdistBand)]
+        lib.grt_pipeline_run_kdist.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtKdist)]
+        lib.grt_kdist_chunk_points.argtypes = []
     lib.grt_pipeline_sky_set_count.argtypes = [C.c_uint]
     if hasattr(lib, "grt_pipeline_run_zeniths"):    # (GRT_LIB_PATH may name an older library: a timing yardstick)
         lib.grt_pipeline_run_zeniths.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtZeniths), C.c_void_p,
@@ -829,6 +845,54 @@ def channel_pair_count(gchannels, num_points):
     return int(load_library().grt_channel_pair_count(C.byref(gchannels), C.c_longlong(int(num_points))))
 
 
+def _kdist_band(edges, weight):
+    """One band of make_kdist: the struct with no outputs yet, and the arrays it points into."""
+    e = None if edges is None else np.ascontiguousarray(edges, dtype=np.int32).ravel()
+    w = None if weight is None else _f64(weight).ravel()
+    band = GrtKdistBand(None if e is None else e.ctypes.data_as(c_int_p), 0 if e is None else max(e.size - 1, 0),
+                        _opt_dp(w), None, None, None)
+    return band, (e, w)
+
+
+def make_kdist(class_edges, lw_edges=None, sw_edges=None, lw_weight=None, sw_weight=None):
+    """Pack the classes and the two bands' bins of a k-distribution into a GrtKdist struct (+ keep-alive arrays) for
+    Pipeline.run_kdist.  class_edges [K - 1]: strictly increasing optical depths that cut K classes; lw_edges, sw_edges:
+    grid-point indices, num_bins + 1 of them, None: that band is not computed; lw_weight, sw_weight [n]: a spectral weight
+    (a Planck or solar curve, say), None: 1.  The six output pointers are Pipeline.run_kdist's to set."""
+    keep = {"class_edges": _f64(class_edges).ravel()}
+    lw, keep["lw"] = _kdist_band(lw_edges, lw_weight)
+    sw, keep["sw"] = _kdist_band(sw_edges, sw_weight)
+    gk = GrtKdist(keep["class_edges"].size + 1, _dp(keep["class_edges"]), lw, sw)
+    gk.keep = keep             # (as make_cloud_model)
+    return gk, keep
+
+
+def kdist_rows(device, tau_ptr, rows, n, dw, class_edges, edges, weight=None):
+    """grt_kdist_rows on the device array tau_ptr [rows][n] of grid spacing dw: -> points (int32), weight, tau, each
+    [rows][num_bins][K], for the K classes that class_edges [K - 1] cut, the bins of edges (grid-point indices, num_bins +
+    1 of them) and the spectral weight [n] (None: 1).  Waits for the result."""
+    lib = load_library()
+    ce = _f64(class_edges).ravel()
+    band, _keep = _kdist_band(edges, weight)
+    K, nb = ce.size + 1, band.num_bins
+    shape = (int(rows), nb, K)
+    count = max(int(rows) * nb * K, 1)
+    bufs = [DeviceBuffer(device, 4 * count), DeviceBuffer(device, 8 * count), DeviceBuffer(device, 8 * count)]
+    try:
+        band.points_dev, band.weight_dev, band.tau_dev = (b.ptr for b in bufs)
+        addr = tau_ptr if isinstance(tau_ptr, int) or tau_ptr is None else C.cast(tau_ptr, C.c_void_p).value
+        check(lib.grt_kdist_rows(device, C.c_void_p(addr), int(rows), int(n), float(dw), K, _dp(ce), C.byref(band)))
+        return (bufs[0].to_host(shape, dtype=np.int32), bufs[1].to_host(shape), bufs[2].to_host(shape))
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def kdist_chunk_points():
+    """grt_kdist_chunk_points: the points of a bin the k-distribution kernel stages at a time."""
+    return int(load_library().grt_kdist_chunk_points())
+
+
 class Pipeline:
     def __init__(self, lw_gas, sw_gas, max_columns, user_level, emissivity, albedo, solar, spectral=True):
         """spectral=True keeps tau/omega/g and the spectral fluxes (views(): what parity tests read);
@@ -847,6 +911,7 @@ class Pipeline:
         self.buffers = {}       # every device buffer of this object by name: each run form's at its first call
         self.spec_shape = None  # (sets, longwave bins, shortwave bins) of the last run_spectral
         self.band_shape = None  # ... of the last run_band_profiles
+        self.kdist_shape = None  # (classes, longwave bins, shortwave bins) of the last run_kdist
         self.out = self._buffer("run", 8 * GRT_FLUXES_PER_COLUMN * max_columns)
 
     def _buffer(self, name, nbytes):
@@ -1002,6 +1067,38 @@ class Pipeline:
                 "sw_down": sw[:, :, 1].copy(),
                 "lw_heating": hr[:, :, :bl * (V - 1)].reshape(ncol, sets, bl, V - 1).copy(),
                 "sw_heating": hr[:, :, bl * (V - 1):].reshape(ncol, sets, bs, V - 1).copy()}
+
+    def run_kdist(self, gcols, class_edges, lw_edges=None, sw_edges=None, lw_weight=None, sw_weight=None):
+        """grt_pipeline_run_kdist into this object's device buffers (kdist() reads them): per column, layer and bin of
+        lw_edges / sw_edges (grid-point indices, num_bins + 1 of them; None: that band is not computed) the k-distribution
+        of the gas optical depth over the K classes that class_edges [K - 1] cut, with the spectral weights lw_weight /
+        sw_weight [n] (None: 1).  No solver runs."""
+        gk, _keep = make_kdist(class_edges, lw_edges, sw_edges, lw_weight, sw_weight)
+        K, rows = gk.num_classes, self.max_columns * (self.num_levels - 1)
+        for name, band in (("lw", gk.lw), ("sw", gk.sw)):
+            count = max(rows * band.num_bins * K, 1)
+            band.points_dev = self._buffer(f"kdist.{name}.points", 4 * count).ptr
+            band.weight_dev = self._buffer(f"kdist.{name}.weight", 8 * count).ptr
+            band.tau_dev = self._buffer(f"kdist.{name}.tau", 8 * count).ptr
+        self.kdist_shape = (K, gk.lw.num_bins, gk.sw.num_bins)
+        check(self.lib.grt_pipeline_run_kdist(self.p, C.byref(gcols), C.byref(gk)))
+
+    def kdist(self, ncol):
+        """The last run_kdist: {"lw": {"points", "weight", "tau"}, "sw": ...}, each [ncol][L][num_bins][K] -- the number of
+        the bin's points in each class (int32), the sum of their trapezoid weights and the sum of weight x optical depth
+        (grtcode_amd.kdist turns them into g and k(g))."""
+        self.sync()
+        K, nb_lw, nb_sw = self.kdist_shape
+        out = {}
+        for name, nb in (("lw", nb_lw), ("sw", nb_sw)):
+            shape = (ncol, self.num_levels - 1, nb, K)
+            if nb == 0:
+                out[name] = {"points": np.zeros(shape, dtype=np.int32), "weight": np.zeros(shape), "tau": np.zeros(shape)}
+                continue
+            out[name] = {"points": self.buffers[f"kdist.{name}.points"].to_host(shape, dtype=np.int32),
+                         "weight": self.buffers[f"kdist.{name}.weight"].to_host(shape),
+                         "tau": self.buffers[f"kdist.{name}.tau"].to_host(shape)}
+        return out
 
     def _six_row_or_profile_ptrs(self, name, profiles):
         """The (levels, heating, fluxes) pointers of a two-set entry point that writes either form: the six-row form's

@@ -19,9 +19,9 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 SO = os.path.join(LIB, "libgrtcode_hip.so")
 
 HOST_SRC = ["grt_error.c", "grt_util.c", "grt_grid.c", "grt_device.c", "grt_optics.c", "grt_tips.c",
-            "grt_hitran.c", "grt_line_store.c", "grt_gas_optics.c", "grt_gas_launch.c", "grt_solvers.c", "grt_pipeline.c", "grt_pipeline_inputs.c", "grt_pipeline_solve.c", "grt_multi.c", "grt_cloud_sampler.c", "grt_clouds.c"]
+            "grt_hitran.c", "grt_line_store.c", "grt_gas_optics.c", "grt_gas_launch.c", "grt_solvers.c", "grt_pipeline.c", "grt_pipeline_inputs.c", "grt_pipeline_solve.c", "grt_multi.c", "grt_cloud_sampler.c", "grt_kdist.c", "grt_clouds.c"]
 NOT_IN_SO = {"grt_clouds"}      # libclouds.a only: a maintainer links the reference's own libclouds.a in its place
-HIP_SRC = ["k_gas_optics.hip", "k_gas_optics_mp.hip", "k_gas_optics_far.hip", "k_gas_optics_sweep.hip", "k_optics.hip", "k_longwave.hip", "k_shortwave.hip", "k_cloud_sample.hip"]
+HIP_SRC = ["k_gas_optics.hip", "k_gas_optics_mp.hip", "k_gas_optics_far.hip", "k_gas_optics_sweep.hip", "k_optics.hip", "k_longwave.hip", "k_shortwave.hip", "k_cloud_sample.hip", "k_kdist.hip"]
 
 # the reference's archive names (*/src/Makefile.am): which objects go where
 ARCHIVES = {
@@ -30,7 +30,7 @@ ARCHIVES = {
     "liblongwave.a": ["k_longwave"],
     "libshortwave.a": ["k_shortwave"],
     # solvers' host entry points and the batched pipeline reference both bands
-    "libgrtcode_hip_ext.a": ["grt_solvers", "grt_pipeline", "grt_pipeline_inputs", "grt_pipeline_solve", "grt_multi", "grt_cloud_sampler", "k_cloud_sample"],
+    "libgrtcode_hip_ext.a": ["grt_solvers", "grt_pipeline", "grt_pipeline_inputs", "grt_pipeline_solve", "grt_multi", "grt_cloud_sampler", "k_cloud_sample", "grt_kdist", "k_kdist"],
     # the reference's cloud-optics archive name: entry points only (SURVEY §8 f-4 is not built), so that
     # framework/src/driver.c links unchanged
     "libclouds.a": ["grt_clouds"],

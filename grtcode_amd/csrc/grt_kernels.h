@@ -796,6 +796,29 @@ typedef struct GrtCloudSampleArgs
 } GrtCloudSampleArgs;
 int grt_launch_cloud_sample(void *stream, GrtCloudSampleArgs const *a);
 
+/* K-distributions of optical-depth rows (k_kdist.hip; grt_ext.h: grt_kdist_rows, which defines the reduction): per row of
+   tau [rows][n], bin b of edges [num_bins + 1] (grid-point indices, strictly increasing in 0 .. n - 1) and class k of the
+   num_classes that class_edges [num_classes - 1] (strictly increasing) cut -- the number of the bin's points in the class,
+   the sum of their trapezoid weights (dw, dw/2 at the bin's two end points, times weight [n] where that is given) and the
+   sum of weight x tau, each sum sequential in increasing grid index.  Everything is DEVICE memory; the outputs are
+   [rows][num_bins][num_classes], any of them NULL, not all.  One workgroup per (row, bin);
+   grt_kdist_chunk: the points it stages at a time. */
+#define GRT_KDIST_CLASS_LIMIT 1024      /* grt_ext.h: GRT_KDIST_MAX_CLASSES */
+typedef struct GrtKdistArgs
+{
+    double const *tau;
+    long long rows, n;
+    double dw;
+    int num_classes, num_bins;
+    double const *class_edges;
+    int const *edges;
+    double const *weight;           /* or NULL: 1 */
+    int *points;
+    double *weight_sum, *tau_sum;
+} GrtKdistArgs;
+int grt_kdist_chunk(void);
+int grt_launch_kdist(void *stream, GrtKdistArgs const *a);
+
 /* Fused Rayleigh + combine for the clear-sky driver sequence (rayleigh.c:39 +
    optics.c:138-145 with K=2, gas omega=g=0, Rayleigh omega=1,g=0):
    tau_tot = tau_gas + tau_R, omega = tau_R/tau_tot, g = 0/ tau_R.  n_layer [ncol][L]. */

@@ -1,0 +1,240 @@
+// k_kdist.hip -- k-distributions of optical-depth rows (grt_ext.h: grt_kdist_rows, grt_pipeline_run_kdist).
+//
+// One 256-thread workgroup per (row, bin).  A bin's points are classified against K - 1 class edges, and per class the
+// points are counted and their trapezoid weights W_i and the products T_i = W_i tau_i are summed -- each sum the plain
+// left-to-right sum in increasing grid index, from +0.0, every product rounded before it is added: the result is a pure
+// function of the inputs, bit-identical run to run and to a sequential model on the host.
+//
+// The workgroup walks its bin in chunks of kChunkPoints points, two phases a chunk:
+//   1. every thread takes the points tid, tid + 256, ... of the chunk (coalesced 8-byte loads), finds each one's class by
+//      bisection over the class edges in LDS and parks the class (16 bits), W_i and T_i in LDS;
+//   2. thread t owns the classes t, t + 256, ...: a wave walks the chunk's classes in index order -- every lane reads the
+//      same LDS addresses, a broadcast -- and W_i, T_i and 1 are added in the owner's registers.  With K <= 64 wave 0 owns
+//      every class and walks alone, in straight-line code; beyond, every wave that has classes walks, four points a
+//      step, and passes a point of another wave's class by on a scalar branch.  A wave none of whose classes exists goes
+//      straight to the barrier.
+// The accumulators stay in registers across the chunks and are stored once.  No atomics, no tree, no contraction.
+// LDS: 18 bytes a point and the class edges, 18 432 + 8 (K - 1) bytes, all in the dynamic region: the eight workgroups
+// that a CU's 32 waves allow up to K = 257, six at K = 1024.  (Measured, 64 columns of the bench grids, 16 bins, K = 64:
+// 7.9 ms with chunks of 2048 points, four workgroups a CU; 5.0 ms with 1024 -- phase 2 waits for LDS once every four
+// points, and a second resident wave per SIMD fills the wait.)
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../grt_kernels.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kChunkPoints = 1024;      // points staged at a time (grt_kdist_chunk_points)
+constexpr int kMaxClasses = GRT_KDIST_CLASS_LIMIT;
+constexpr int kStep = 4;                // points of phase 2 per LDS read
+constexpr unsigned kNoClass = 0xffffu;  // pads a chunk's last step: beyond every class (kMaxClasses <= 0xffff)
+
+static_assert(kChunkPoints % kThreads == 0, "every thread stages the same number of points of a full chunk");
+static_assert(kStep == 4 && kChunkPoints % kStep == 0, "load_step reads four points; a padded chunk fits its buffers");
+static_assert(kMaxClasses <= 4*kThreads, "a thread owns at most four classes");
+static_assert(kMaxClasses < (int)kNoClass, "the class of a point is parked in 16 bits, and the pad is none of them");
+
+// the number of class edges e[0 .. ne - 1] (ascending) with e[k] <= tau, by plain double comparisons: a NaN gives 0
+__device__ __forceinline__ int class_of(double const *e, int ne, double tau)
+{
+    int lo = 0, hi = ne;
+    while (lo < hi)
+    {
+        int const mid = (lo + hi) >> 1;
+        if (e[mid] <= tau) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// One step of phase 2: the classes (16 bits each), W and T of the four points from j on, in four wide LDS reads.  The
+// empty asm pins the values in registers here: without it the compiler moves each read behind the select that uses it,
+// under that point's lane mask, and waits for every one of them in turn.
+__device__ __forceinline__ void load_step(unsigned short const *c_s, double const *w_s, double const *t_s, int j,
+                                          uint64_t &four, double (&w)[kStep], double (&t)[kStep])
+{
+    four = *reinterpret_cast<uint64_t const *>(c_s + j);
+    double2 const w01 = *reinterpret_cast<double2 const *>(w_s + j), w23 = *reinterpret_cast<double2 const *>(w_s + j + 2);
+    double2 const t01 = *reinterpret_cast<double2 const *>(t_s + j), t23 = *reinterpret_cast<double2 const *>(t_s + j + 2);
+    w[0] = w01.x, w[1] = w01.y, w[2] = w23.x, w[3] = w23.y;
+    t[0] = t01.x, t[1] = t01.y, t[2] = t23.x, t[3] = t23.y;
+    asm volatile("" : "+v"(four), "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]), "+v"(t[0]), "+v"(t[1]), "+v"(t[2]),
+                 "+v"(t[3]));
+}
+
+// NC: the classes a thread owns (K <= NC x 256)
+template <int NC>
+__global__ __launch_bounds__(kThreads) void kdist_kernel(GrtKdistArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    double *w_s = reinterpret_cast<double *>(lds);                          // [kChunkPoints]
+    double *t_s = w_s + kChunkPoints;                                       // [kChunkPoints]
+    unsigned short *c_s = reinterpret_cast<unsigned short *>(t_s + kChunkPoints);   // [kChunkPoints]
+    double *e_s = reinterpret_cast<double *>(c_s + kChunkPoints);           // [K - 1]
+
+    int const tid = threadIdx.x, K = a.num_classes, ne = K - 1;
+    // (the wave's number in a scalar register: what it compares a point's class with is then a scalar branch)
+    int const wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    for (int k = tid; k < ne; k += kThreads)
+    {
+        e_s[k] = a.class_edges[k];
+    }
+    // (wave-uniform: the lowest class of this thread's wave)
+    bool const wave_has_classes = wave*64 < K;
+    double const half_dw = 0.5*a.dw;
+
+    long long const items = a.rows*(long long)a.num_bins;
+    for (long long item = blockIdx.x; item < items; item += gridDim.x)
+    {
+        long long const row = item/a.num_bins;
+        int const bin = (int)(item - row*a.num_bins);
+        int const first = a.edges[bin], last = a.edges[bin + 1];
+        double const *tau = a.tau + row*a.n;
+        int count[NC];
+        double wsum[NC], tsum[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+        {
+            count[c] = 0;
+            wsum[c] = 0.;
+            tsum[c] = 0.;
+        }
+        // (start in 64 bits: the last chunk of a bin that ends near 2^31 must not wrap)
+        for (long long start = first; start <= last; start += kChunkPoints)
+        {
+            int const m = (int)min((long long)kChunkPoints, last - start + 1);
+            int const padded = (m + kStep - 1) & ~(kStep - 1);
+            __syncthreads();               // the class edges are in place; the chunk before has been summed
+            for (int j = tid; j < m; j += kThreads)
+            {
+                long long const i = start + j;
+                double const x = tau[i];
+                double w = (i == first || i == last) ? half_dw : a.dw;
+                if (a.weight != nullptr)
+                {
+                    w = __dmul_rn(w, a.weight[i]);
+                }
+                w_s[j] = w;
+                t_s[j] = __dmul_rn(w, x);
+                c_s[j] = (unsigned short)class_of(e_s, ne, x);
+            }
+            for (int j = m + tid; j < padded; j += kThreads)
+            {
+                w_s[j] = 0.;
+                t_s[j] = 0.;
+                c_s[j] = (unsigned short)kNoClass;
+            }
+            __syncthreads();
+            // A point of another thread's class adds +0.0, which changes no bit of a sum that started from +0.0: x + (+0.0)
+            // is x for every x but -0.0, NaN and the infinities included, and such a sum is never -0.0 (only -0.0 + -0.0
+            // gives that).  So the select sits on the term, off the accumulators' dependency chain.
+            if (NC == 1 && K <= 64)
+            {
+                // one wave owns every class: straight-line code, no point passed by
+                if (wave == 0)
+                {
+                    for (int j = 0; j < padded; j += kStep)
+                    {
+                        uint64_t four;
+                        double w[kStep], t[kStep];
+                        load_step(c_s, w_s, t_s, j, four, w, t);
+#pragma unroll
+                        for (int q = 0; q < kStep; ++q)
+                        {
+                            bool const mine = ((unsigned)(four >> (16*q)) & 0xffffu) == (unsigned)tid;
+                            count[0] += mine ? 1 : 0;
+                            wsum[0] = __dadd_rn(wsum[0], mine ? w[q] : 0.);
+                            tsum[0] = __dadd_rn(tsum[0], mine ? t[q] : 0.);
+                        }
+                    }
+                }
+            }
+            else if (wave_has_classes)
+            {
+                for (int j = 0; j < padded; j += kStep)
+                {
+                    uint64_t four;
+                    double w[kStep], t[kStep];
+                    load_step(c_s, w_s, t_s, j, four, w, t);
+                    unsigned const lo = __builtin_amdgcn_readfirstlane((unsigned)four);
+                    unsigned const hi = __builtin_amdgcn_readfirstlane((unsigned)(four >> 32));
+#pragma unroll
+                    for (int q = 0; q < kStep; ++q)
+                    {
+                        // (the same for every lane, and in scalar registers: class = slot x 256 + wave x 64 + lane)
+                        unsigned const cls = ((q < 2 ? lo : hi) >> (16*(q & 1))) & 0xffffu;
+                        if (((cls >> 6) & 3u) != (unsigned)wave)
+                        {
+                            continue;      // another wave's class
+                        }
+                        unsigned const slot = cls >> 8;
+#pragma unroll
+                        for (int c = 0; c < NC; ++c)
+                        {
+                            if (NC == 1 || slot == (unsigned)c)
+                            {
+                                if (NC > 1)
+                                {
+                                    asm volatile("");      // (keeps the scalar branch a branch: not NC selects a point)
+                                }
+                                bool const mine = cls == (unsigned)(tid + c*kThreads);
+                                count[c] += mine ? 1 : 0;
+                                wsum[c] = __dadd_rn(wsum[c], mine ? w[q] : 0.);
+                                tsum[c] = __dadd_rn(tsum[c], mine ? t[q] : 0.);
+                            }
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+        {
+            int const cls = tid + c*kThreads;
+            if (cls < K)
+            {
+                long long const at = item*K + cls;
+                if (a.points != nullptr) a.points[at] = count[c];
+                if (a.weight_sum != nullptr) a.weight_sum[at] = wsum[c];
+                if (a.tau_sum != nullptr) a.tau_sum[at] = tsum[c];
+            }
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int grt_kdist_chunk(void)
+{
+    return kChunkPoints;
+}
+
+extern "C" int grt_launch_kdist(void *stream, GrtKdistArgs const *a)
+{
+    if (a == nullptr || a->tau == nullptr || a->rows < 1 || a->n < 2 || a->num_bins < 1 || a->edges == nullptr ||
+        a->num_classes < 2 || a->num_classes > kMaxClasses || a->class_edges == nullptr ||
+        (a->points == nullptr && a->weight_sum == nullptr && a->tau_sum == nullptr))
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    long long const items = a->rows*(long long)a->num_bins;
+    unsigned const blocks = (unsigned)(items < (1ll << 20) ? items : (1ll << 20));
+    size_t const lds = (size_t)kChunkPoints*(2*sizeof(double) + sizeof(unsigned short)) +
+                       sizeof(double)*(size_t)(a->num_classes - 1);
+    hipStream_t const s = (hipStream_t)stream;
+    if (a->num_classes <= kThreads)
+    {
+        hipLaunchKernelGGL(kdist_kernel<1>, dim3(blocks), dim3(kThreads), lds, s, *a);
+    }
+    else if (a->num_classes <= 2*kThreads)
+    {
+        hipLaunchKernelGGL(kdist_kernel<2>, dim3(blocks), dim3(kThreads), lds, s, *a);
+    }
+    else
+    {
+        hipLaunchKernelGGL(kdist_kernel<4>, dim3(blocks), dim3(kThreads), lds, s, *a);
+    }
+    return (int)hipGetLastError();
+}

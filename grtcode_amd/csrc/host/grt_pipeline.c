@@ -43,6 +43,8 @@
  * grt_pipeline_run_band_profiles runs the profile form of the clear-sky pass and, with clouds, of the all-sky pass with
  * every level's flux integrated per wavenumber bin instead of over the whole grid, and one finishing launch for the bins'
  * heating rates.
+ * grt_pipeline_run_kdist runs the prologue and the gas optics of the bands that have bins and no solver at all: tau_gas is
+ * reduced to its k-distribution per layer and bin (grt_kdist.c, k_kdist.hip).
  * grt_pipeline_set_surface gives the columns of the runs that follow their own surface emissivity and albedo
  * (driver.c:101-117): rows written on the device from each column's few knots, read by the solvers in place of the shared
  * creation-time arrays.
@@ -274,6 +276,7 @@ static void grt_pipeline_release(GrtPipeline_t **pipeline)
         grt_keyed_table_free(p, &p->band[b].bin_table);
         grt_keyed_table_free(p, &p->band[b].surf_map);
         grt_keyed_table_free(p, &p->band[b].channel_table);
+        grt_kdist_table_free(p->device, &p->band[b].kdist_table);
     }
     grt_staging_free(p, &p->rad);
     grt_staging_free(p, &p->zen);
@@ -1324,35 +1327,58 @@ EXTERN int grt_pipeline_run_sky_zeniths(GrtPipeline_t *p, GrtColumns_t const *co
 static int check_bins(GrtPipeline_t const *p, int bi, int const *edges, int num_bins, fp_t const *binned_dev)
 {
     char const *name = bi == 0 ? "longwave" : "shortwave";
-    if (num_bins < 0)
-    {
-        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s bins.", num_bins, name);
-    }
-    if (num_bins == 0)
-    {
-        return GRTCODE_SUCCESS;
-    }
-    if (p->band[bi].gas == NULL)
+    if (num_bins > 0 && p->band[bi].gas == NULL)
     {
         GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s bins asked for, and this pipeline has no %s band.", num_bins, name, name);
     }
-    if (edges == NULL || binned_dev == NULL)
+    GRT_TRY(grt_check_bin_edges(name, edges, num_bins, (long long)p->band[bi].n, binned_dev != NULL));
+    return GRTCODE_SUCCESS;
+}
+
+/* grt_ext.h: the k-distributions of the bands' tau_gas.  The entry point alone: the checks of the classes and of a band's
+   inputs, the tables and the launch are grt_kdist.c's. */
+EXTERN int grt_pipeline_run_kdist(GrtPipeline_t *p, GrtColumns_t const *cols, GrtKdist_t const *kd)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    if (kd == NULL)
     {
-        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s bins with NULL edges or a NULL binned_dev.", num_bins, name);
+        GRT_FAIL(GRTCODE_VALUE_ERR, "no k-distribution inputs (GrtKdist_t is NULL).%s", "");
     }
-    long long const n = (long long)p->band[bi].n;
-    if (edges[0] < 0 || (long long)edges[num_bins] > n - 1)
+    GRT_TRY(grt_kdist_check_classes(kd->num_classes, kd->class_edges));
+    GrtKdistBand_t const *kb[2] = {&kd->lw, &kd->sw};
+    for (int bi = 0; bi < 2; ++bi)
     {
-        GRT_FAIL(GRTCODE_VALUE_ERR, "%s bin edges %d .. %d outside the grid's points 0 .. %lld.", name, edges[0],
-                 edges[num_bins], n - 1);
-    }
-    for (int b = 0; b < num_bins; ++b)
-    {
-        if (edges[b + 1] <= edges[b])
+        /* (a band's output: any of its three) */
+        void const *out = kb[bi]->points_dev != NULL ? (void const *)kb[bi]->points_dev :
+                          kb[bi]->weight_dev != NULL ? (void const *)kb[bi]->weight_dev : (void const *)kb[bi]->tau_dev;
+        GRT_TRY(check_bins(p, bi, kb[bi]->edges, kb[bi]->num_bins, out));
+        if (kb[bi]->num_bins > 0)
         {
-            GRT_FAIL(GRTCODE_VALUE_ERR, "%s bin edges not strictly increasing (edges[%d] = %d, edges[%d] = %d).", name, b,
-                     edges[b], b + 1, edges[b + 1]);
+            GRT_TRY(grt_kdist_check_band(bi == 0 ? "longwave" : "shortwave", kb[bi], (long long)p->band[bi].n));
         }
+    }
+    if (kd->lw.num_bins + kd->sw.num_bins == 0)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "no bins in either band: nothing to write.%s", "");
+    }
+    GRT_TRY(check_columns(p, cols));
+    GRT_TRY(check_lane(p));
+    /* (no solver runs: the columns' sun angles are not read) */
+    GRT_TRY(stage_columns(p, cols, 1));
+    for (int bi = 0; bi < 2; ++bi)
+    {
+        GrtBand *b = &p->band[bi];
+        if (kb[bi]->num_bins == 0)
+        {
+            continue;                  /* (a band without bins is not computed: its line list is not touched) */
+        }
+        /* the whole of tau, the spectral tables' part included (band_gas_optics leaves that to a solver) */
+        GRT_TRY(grt_optical_depth_batch(b->gas, cols, b->tau_gas));
+        b->tau_gas_lacks_tables = 0;
+        b->last_cols = cols->ncol;
+        GRT_TRY(grt_kdist_reduce(p->device, &b->kdist_table, b->tau_gas, (long long)cols->ncol*(p->num_levels - 1),
+                                 (long long)b->n, b->gas->grid.dw, kd->num_classes, kd->class_edges, kb[bi]));
     }
     return GRTCODE_SUCCESS;
 }

@@ -788,6 +788,38 @@ void grt_stage_weighting(GrtWeighting_t const *wt, GrtWeightingRun *wr)
     wr->contribution = wt->contribution_dev;
 }
 
+/* one band's bins on a grid of n points: none, or num_bins + 1 strictly increasing grid-point indices in 0 .. n - 1 and
+   somewhere to write them (grt_pipeline_run_spectral, _run_band_profiles, _run_kdist, grt_kdist_rows) */
+int grt_check_bin_edges(char const *name, int const *edges, int num_bins, long long n, int has_output)
+{
+    if (num_bins < 0)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s bins.", num_bins, name);
+    }
+    if (num_bins == 0)
+    {
+        return GRTCODE_SUCCESS;
+    }
+    if (edges == NULL || !has_output)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s bins with NULL edges or a NULL binned_dev.", num_bins, name);
+    }
+    if (edges[0] < 0 || (long long)edges[num_bins] > n - 1)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%s bin edges %d .. %d outside the grid's points 0 .. %lld.", name, edges[0],
+                 edges[num_bins], n - 1);
+    }
+    for (int b = 0; b < num_bins; ++b)
+    {
+        if (edges[b + 1] <= edges[b])
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "%s bin edges not strictly increasing (edges[%d] = %d, edges[%d] = %d).", name, b,
+                     edges[b], b + 1, edges[b + 1]);
+        }
+    }
+    return GRTCODE_SUCCESS;
+}
+
 typedef struct BinTableFill { int const *edges; int nbins; uint64_t n; size_t per_row; } BinTableFill;
 
 static int fill_bin_table(void *ctx, int *table)

@@ -17,6 +17,18 @@ typedef struct GrtKeyedTable
 /* writes the host table for the key at hand from the caller's ctx */
 typedef int (*GrtTableFill)(void *ctx, int *table);
 
+/* The host inputs of a k-distribution call on the device (grt_kdist.c): one block -- the class edges [K - 1], the weight
+   [n] where one is given, then the bin edges [num_bins + 1] --, uploaded again when a call's bytes differ from the ones it
+   holds. */
+typedef struct GrtKdistTable
+{
+    void *block;           /* device */
+    void *key;             /* host: the bytes the block was uploaded from, in its order; NULL: nothing that can be relied on */
+    size_t key_bytes;
+    size_t num_edges;      /* class edges the block was laid out for */
+    size_t num_weights;    /* n, or 0: no weight */
+} GrtKdistTable;
+
 /* Per-batch inputs: a pinned host buffer, refilled every call, and its device copy. */
 typedef struct GrtStaging
 {
@@ -114,6 +126,8 @@ typedef struct GrtBand
        the edges [bin_count + 1] (its key) */
     GrtKeyedTable bin_table;
     size_t bin_per_row;    /* partial sums per row */
+    /* grt_pipeline_run_kdist: this band's class edges, weight and bin edges on the device */
+    GrtKdistTable kdist_table;
     /* grt_pipeline_set_surface: [n] entry of the band's surface grid each grid point takes (grt_surface_entry_map); its key:
        that grid */
     GrtKeyedTable surf_map;
@@ -276,6 +290,17 @@ GRT_PRIVATE int grt_stage_channels(GrtPipeline_t *p, GrtBand *b, GrtChannels_t c
 GRT_PRIVATE int grt_check_weighting(GrtWeighting_t const *wt);
 GRT_PRIVATE void grt_stage_weighting(GrtWeighting_t const *wt, GrtWeightingRun *wr);
 GRT_PRIVATE int grt_band_bins(GrtPipeline_t *p, GrtBand *b, int const *edges, int nbins, int rows);
+/* the rules of a band's bin edges on a grid of n points (`name`: the band's, for the messages): none, or num_bins + 1
+   strictly increasing grid-point indices in 0 .. n - 1, and an output to write them to */
+GRT_PRIVATE int grt_check_bin_edges(char const *name, int const *edges, int num_bins, long long n, int has_output);
+
+/* grt_kdist.c: the checks of the classes and of one band's inputs on a grid of n points (its edges apart); the band's
+   inputs brought up to date in *t and the reduction of tau_dev [rows][n] queued on the device's current lane; *t freed */
+GRT_PRIVATE int grt_kdist_check_classes(int num_classes, fp_t const *class_edges);
+GRT_PRIVATE int grt_kdist_check_band(char const *name, GrtKdistBand_t const *band, long long n);
+GRT_PRIVATE int grt_kdist_reduce(Device_t device, GrtKdistTable *t, fp_t const *tau_dev, long long rows, long long n,
+                                 fp_t dw, int num_classes, fp_t const *class_edges, GrtKdistBand_t const *band);
+GRT_PRIVATE void grt_kdist_table_free(Device_t device, GrtKdistTable *t);
 
 /* grt_pipeline_solve.c */
 GRT_PRIVATE int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps);

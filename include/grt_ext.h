@@ -741,6 +741,67 @@ EXTERN int grt_pipeline_run_band_profiles(GrtPipeline_t *pipeline, GrtColumns_t 
                                           fp_t *band_heating_dev);
 EXTERN int grt_pipeline_band_profile_bin_limit(GrtPipeline_t const *pipeline);
 
+/* ---- k-distributions of the layer optical depths ------------------------------------------------------------------------
+ * What a band model is built from: inside each wavenumber bin and each layer, the distribution of the line-by-line
+ * optical depth -- g(k) and the mean optical depth of each k-class, uniformly or source-weighted -- reduced on the device
+ * next to the array, so that [ncol][L][n] doubles of tau (1.5 GB per 64 columns of the 1 cm-1 shortwave band) leave as
+ * [ncol][L][bins][K] numbers.  The reduction, for one row tau[0 .. n - 1] on a grid of spacing dw:
+ *   bins     num_bins + 1 strictly increasing grid-point indices, as grt_pipeline_run_spectral takes them; adjacent bins
+ *            share their edge point;
+ *   classes  K - 1 strictly increasing, finite class edges e[0 .. K - 2] in units of tau;
+ *   weight   s[0 .. n - 1], each >= 0 and finite, or NULL: 1 (a Planck or solar curve, say).
+ * For bin b and each of its points i = edges[b] .. edges[b + 1]:
+ *   w_i = dw, 0.5 dw at the bin's two end points;  W_i = fl(w_i s_i) (w_i without a weight);  T_i = fl(W_i tau_i);
+ *   class(i) = the number of class edges e_k <= tau_i, by plain double comparisons: a tau equal to an edge goes to the
+ *   upper class; tau <= 0, tau below e[0] and NaN go to class 0; +inf goes to class K - 1.  No logarithm is taken.
+ * Per (row, bin, class k): points, the number of the bin's points in class k; weight, the sum of their W_i; tau, the sum
+ * of their T_i.  Each of the two sums is the plain left-to-right sum of its terms in increasing grid index, from +0.0,
+ * every product rounded before it is added (no fused multiply-add), without floating-point atomics and without a tree; an
+ * empty class gives 0, +0.0, +0.0.  The result is therefore a pure function of the inputs: bit-identical from run to run
+ * in the default and in the deterministic mode, and what a sequential sum on the host (numpy's cumsum) gives, bit for bit.
+ * From it: g at the upper edge of class k is cumsum(weight)/sum(weight); the class mean of tau is tau/weight; the sum of
+ * tau over the classes is the bin's trapezoid integral of s tau.
+ *
+ * grt_kdist_rows: the primitive.  tau_dev [rows][n] is any DEVICE array (what grt_optical_depth_batch wrote, say);
+ *   band's outputs are [rows][num_bins][K].  Asynchronous on the device's current lane.
+ * grt_pipeline_run_kdist: stages the columns, runs, for each band that has bins, the gas optics once -- the whole of it,
+ *   the spectral tables' part included: a following grt_pipeline_views(band, &tau_gas, ...) shows exactly the array that
+ *   was reduced and queues nothing -- and reduces tau_gas with rows = ncol L: a band's outputs are [ncol][L][num_bins][K].
+ *   No solver, no Rayleigh kernel and no clear-sky optics run; a band without bins is not computed at all (a call with
+ *   longwave bins only never touches the shortwave line list); the surface in force, clouds, aerosols and the columns'
+ *   sun angles play no part.  Asynchronous on the pipeline's lane like grt_pipeline_run.
+ * grt_kdist_chunk_points: the points the kernel stages at a time (tests sit on its multiples).
+ * One kernel (GRT_TAG_KDIST), one workgroup per (row, bin).  Bin edges, class edges and weights are uploaded when their
+ * bytes differ from the last call's (the call then waits for the lane); the same inputs again cost nothing.  The
+ * pipeline keeps them per band and frees them when it is destroyed; grt_kdist_rows keeps one set per device.
+ * GRTCODE_VALUE_ERR, with nothing launched and the outputs untouched, for: a NULL kdist, band or class_edges; K outside
+ * 2 .. GRT_KDIST_MAX_CLASSES; class edges that are not strictly increasing or not finite; everything
+ * grt_pipeline_run_spectral refuses in edges (bins for a band whose gas-optics object is NULL included); no bins in
+ * either band; a band with bins and all three outputs NULL; a weight that is negative or not finite; rows < 1, n < 2 or
+ * a dw that is not positive and finite (grt_kdist_rows); ncol outside 1 .. max_columns; a lane other than the
+ * pipeline's. */
+#define GRT_KDIST_MAX_CLASSES 1024
+typedef struct GrtKdistBand
+{
+    int const *edges;        /* HOST [num_bins + 1], as grt_pipeline_run_spectral's; NULL / 0: band not computed */
+    int num_bins;
+    fp_t const *weight;      /* HOST [n] spectral weight, >= 0 and finite, or NULL: 1 */
+    int *points_dev;         /* DEVICE [rows][num_bins][K], or NULL */
+    fp_t *weight_dev;        /* DEVICE [rows][num_bins][K], or NULL */
+    fp_t *tau_dev;           /* DEVICE [rows][num_bins][K], or NULL */
+} GrtKdistBand_t;
+typedef struct GrtKdist
+{
+    int num_classes;         /* K: 2 .. GRT_KDIST_MAX_CLASSES */
+    fp_t const *class_edges; /* HOST [K - 1], strictly increasing, finite */
+    GrtKdistBand_t lw, sw;
+} GrtKdist_t;
+
+EXTERN int grt_kdist_rows(Device_t device, fp_t const *tau_dev, long long rows, long long n, fp_t dw,
+                          int num_classes, fp_t const *class_edges, GrtKdistBand_t const *band);
+EXTERN int grt_pipeline_run_kdist(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtKdist_t const *kdist);
+EXTERN int grt_kdist_chunk_points(void);
+
 /* ---- per-column surface emissivity and albedo ----------------------------------------------------------------------
  * driver.c:101-117: each column's own surface emissivity and albedo, given on coarse wavenumber grids of NS points shared
  * by the columns and put on the band's grid as interpolate_to_grid(grid, x, y, NS, out, linear_sample,
@@ -957,7 +1018,10 @@ enum
     /* 27 = the transmittance and contribution kernel of grt_pipeline_run_sky_weighting (every set's, every draw's, in both
        forms); 28 = its finishing kernel (one launch per set) */
     GRT_TAG_WEIGHTING = 27,
-    GRT_TAG_WEIGHTING_FINISH = 28
+    GRT_TAG_WEIGHTING_FINISH = 28,
+    /* 29 = the k-distribution kernel of grt_kdist_rows and grt_pipeline_run_kdist (the latter's gas optics counts under
+       1 / 2 and 6 / 7) */
+    GRT_TAG_KDIST = 29
 };
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
