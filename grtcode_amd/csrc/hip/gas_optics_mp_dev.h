@@ -47,6 +47,10 @@ __device__ __forceinline__ double row_pass(double v)
     return __hiloint2double(hi, lo);
 }
 
+// The way back from ballot_b: a wave-uniform mask as the lanes' condition.  It stays in its scalar register pair -- no
+// vector instruction, where a ballot of anything but a bare compare costs a select and a compare.
+__device__ __forceinline__ bool lanes_of(unsigned long long mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
+
 template <int CTRL>
 __device__ __forceinline__ int dpp_i(int v)
 {
@@ -214,10 +218,16 @@ constexpr int kLeanMaxP = 4;
 constexpr int kLeanSlots = 16;
 struct LeanTables
 {
-    float ps[kLeanSlots], p_ps[kLeanSlots], dop[kLeanSlots];          // per slot: ps | p - ps | sqrt(ln 2) x doppler factor
-    float qn_m[kLeanSlots*GRT_MAX_ISO], qn_e[kLeanSlots*GRT_MAX_ISO]; // per (slot, isotopologue): N_s/Q as mantissa | exponent
+    // (the three per-slot tables lie more than 255 words apart, out of reach of ONE two-address LDS read: read as a pair,
+    // the values of a lane's two lines land in the wrong halves of two register pairs and cost three moves a block)
+    float ps[kLeanSlots];                                             // per slot: ps
+    float qn_m[kLeanSlots*GRT_MAX_ISO];                               // per (slot, isotopologue): N_s/Q as mantissa
+    float dop[kLeanSlots];                                            // per slot: sqrt(ln 2) x doppler factor
+    float qn_e[kLeanSlots*GRT_MAX_ISO];                               // per (slot, isotopologue): N_s/Q, exponent
     float ptab[kPowTable];                                            // (296/T)^(k/100)
+    float p_ps[kLeanSlots];                                           // per slot: p - ps
 };
+static_assert(kLeanSlots*GRT_MAX_ISO > 255 && kLeanSlots*GRT_MAX_ISO + kPowTable > 255, "ps, dop and p_ps within reach of a paired read");
 struct LeanRaw
 {
     unsigned long long xl_mask[kWaves][kLeanListCap][kLeanMaxP];

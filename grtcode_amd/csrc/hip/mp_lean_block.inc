@@ -184,8 +184,12 @@
             // (the tile's flags, tested where they are used: hoisted out of the loop, each test became a lane mask in two
             // scalar registers, spilled to a vector register's lanes and read back with v_readlane at every use)
             unsigned tfl = tflags;
-            asm volatile("" : "+s"(tfl));
-            bool const have[2] = {2*lane >= lo && 2*lane < hi, 2*lane + 1 < hi};
+            asm volatile("; lean block: begin" : "+s"(tfl));      // (the comments: scripts/lean_block_count.py counts between them)
+            // Which lanes hold a line, a line of this tile, a line the general form has to take: kept as the wave's masks
+            // (ballots of the bare compares -- a ballot of anything else costs a select and a compare -- combined on the
+            // scalar side, and handed back to the lanes as conditions: lanes_of).
+            // (lo is 0 or 1 and only lane 0 can hold a line before it: lane 0's bit cleared)
+            unsigned long long const have_m[2] = {ballot_b(2*lane < hi) & ~(unsigned long long)lo, ballot_b(2*lane < hi - 1)};
             unsigned const rc[2] = {rcc.x, rcc.y};
             v2f const d0 = {ra0.x, ra0.y};
             int const ci[2] = {__float_as_int(ra0.z), __float_as_int(ra0.w)};
@@ -200,13 +204,16 @@
             v2f const dl = u - kf;                              // offset of the shifted centre from grid point c, [-1/2, 1/2)
             v2f const gd = (t - kf) - 0.5f;
             int const c[2] = {ci[0] + (int)kf.x, ci[1] + (int)kf.y};
-            bool const guard[2] = {fabsf(gd.x) > 0.49999f, fabsf(gd.y) > 0.49999f};
-            bool const in_tile[2] = {(unsigned)(c[0] - F0) < (unsigned)(F1 - F0), (unsigned)(c[1] - F0) < (unsigned)(F1 - F0)};
+            unsigned long long const guard_m[2] = {ballot_b(fabsf(gd.x) > 0.49999f), ballot_b(fabsf(gd.y) > 0.49999f)};
+            unsigned long long const in_tile_m[2] = {ballot_b((unsigned)(c[0] - F0) < (unsigned)(F1 - F0)), ballot_b((unsigned)(c[1] - F0) < (unsigned)(F1 - F0))};
             v2f const wn = pk_fma(dsh, splat2(pavg_f), v0f);    // shifted centre [cm-1]
             // ---- S(T) N_s (kernels.c:83-85, :459) ----
             v2f const nz = rint2(en*kh2);
             v2f const rz = pk_fma(en, kl2, pk_fma(en, kh2, -nz));       // en c2 log2(e)/T - nz, to ~1e-8
-            unsigned const qi[2] = {(rc[0] >> 14) & 1023u, (rc[1] >> 14) & 1023u};
+            unsigned qi[2] = {(rc[0] >> 14) & 1023u, (rc[1] >> 14) & 1023u};
+            // (the index as such: one bit-field extract, then base + 4 index in one instruction; folded into the shift, the
+            // compiler takes a shift, a mask and an add)
+            asm("" : "+v"(qi[0]));
             v2f amp = (ss*(v2f){lt->qn_m[qi[0]], lt->qn_m[qi[1]]})*exp2_2(rz);
             {
                 v2f const ex = (v2f){lt->qn_e[qi[0]], lt->qn_e[qi[1]]} + nz;
@@ -247,10 +254,11 @@
             v2f const rep = pk_fma(pk_fma(-ad, r0, splat2(1.f)), r0, r0);       // REPWID (one Newton step: the far wings scale with it)
             v2f y = rep*gam;
             // (flagged by the loader: strength zeroed; RFM_voigt.c:122-126: no Lorentz width -- all of that is general_block's)
-            bool const exc[2] = {bool(!(ss.x > 0.f) | guard[0] | !(y.x > 0.000001f)), bool(!(ss.y > 0.f) | guard[1] | !(y.y > 0.000001f))};
-            bool const valid[2] = {bool(have[0] & in_tile[0] & !exc[0]), bool(have[1] & in_tile[1] & !exc[1])};
+            unsigned long long const exc_m[2] = {ballot_b(!(ss.x > 0.f)) | guard_m[0] | ballot_b(!(y.x > 0.000001f)),
+                                                 ballot_b(!(ss.y > 0.f)) | guard_m[1] | ballot_b(!(y.y > 0.000001f))};
+            bool const valid[2] = {lanes_of(have_m[0] & in_tile_m[0] & ~exc_m[0]), lanes_of(have_m[1] & in_tile_m[1] & ~exc_m[1])};
             {
-                unsigned long long const handed0 = ballot_b(have[0] & exc[0]), handed1 = ballot_b(have[1] & exc[1]);
+                unsigned long long const handed0 = have_m[0] & exc_m[0], handed1 = have_m[1] & exc_m[1];
                 if ((handed0 | handed1) != 0ull)
                 {
                     if (lane == 0)
@@ -273,17 +281,19 @@
             int cr;
             {
                 int const c_first = dpp_i<0x150>(c[0]);                             // row_newbcast:0 -- the row's first lane
-                cr = c_first < F0 ? F0 : (c_first > F1 - 1 ? F1 - 1 : c_first);
+                cr = max(min(c_first, F1 - 1), F0);                                 // (F0 <= F1 - 1: a tile has a cell)
             }
             // (a lane without a valid line has amp = 0 and adds nothing wherever it is put: it is put in cell cr, and from here
             // on nothing asks about validity -- its XLIM0 and XLIM1 below are zero, so it has no region 1 and no core point)
             int const o[2] = {valid[0] ? c[0] - cr : 0, valid[1] ? c[1] - cr : 0};
-            bool const odd[2] = {(unsigned)o[0] > 1u, (unsigned)o[1] > 1u};
             // (the longwave band's usual case, 308 lines per cell: no second cell, no weights; the instance that is not
             // NARROW -- the shortwave band, 30 lines per cell -- does not ask)
             bool const single = NARROW && ballot_b((o[0] | o[1]) != 0) == 0ull;
-            v2f const W0 = {o[0] == 0 ? 1.f : 0.f, o[1] == 0 ? 1.f : 0.f};
-            v2f const W1 = {o[0] == 1 ? 1.f : 0.f, o[1] == 1 ? 1.f : 0.f};
+            bool const in0[2] = {o[0] == 0, o[1] == 0}, in1[2] = {o[0] == 1, o[1] == 1};
+            v2f const W0 = {in0[0] ? 1.f : 0.f, in0[1] ? 1.f : 0.f};
+            v2f const W1 = {in1[0] ? 1.f : 0.f, in1[1] ? 1.f : 0.f};
+            // (in neither cell: what the four compares leave, as masks)
+            unsigned long long const odd_m[2] = {~(ballot_b(in0[0]) | ballot_b(in1[0])), ~(ballot_b(in0[1]) | ballot_b(in1[1]))};
             // ---- moments of the Lorentzian about the cell centre (see general_block) ----
             v2f const A = (amp*eta)*splat2(a_norm);                             // K(r) = A/((r - dl)^2 + eta^2)
             v2f m[kMom];
@@ -308,19 +318,20 @@
             v2f const cl = (rep*y)*0.318309886f;
             v2f const adl = {fabsf(dl.x), fabsf(dl.y)};
             v2f const ndcr = (-dl)*wr;                          // x of the line's own grid point
-            bool pre2[2] = {false, false};
+            unsigned long long pre2_m[2] = {0ull, 0ull};        // (masks, as above)
             if (tfl & kTfCorrected)
             {
                 // region 1 beyond the near field: folded into the moments, or (pre-pass 2 of general_block) point by point
                 v2f const e4 = (4.f - adl)*wr;
                 v2f const e4q = e4*e4, aw = adl*wr;
-                bool const reg1_far[2] = {e4q.x < x0q.x, e4q.y < x0q.y};
-                bool const fold[2] = {bool(reg1_far[0] & (aw.x <= 0.5f*kFoldWrMax)), bool(reg1_far[1] & (aw.y <= 0.5f*kFoldWrMax))};
-                pre2[0] = reg1_far[0] & !fold[0];
-                pre2[1] = reg1_far[1] & !fold[1];
+                unsigned long long const reg1_far_m[2] = {ballot_b(e4q.x < x0q.x), ballot_b(e4q.y < x0q.y)};
+                unsigned long long const fold_m[2] = {reg1_far_m[0] & ballot_b(aw.x <= 0.5f*kFoldWrMax), reg1_far_m[1] & ballot_b(aw.y <= 0.5f*kFoldWrMax)};
+                pre2_m[0] = reg1_far_m[0] & ~fold_m[0];
+                pre2_m[1] = reg1_far_m[1] & ~fold_m[1];
                 // (below ~15 000 cm-1 region 1 ends inside the near field: no line of the wave has anything to fold)
-                if (ballot_b(fold[0] | fold[1]) != 0ull)
+                if ((fold_m[0] | fold_m[1]) != 0ull)
                 {
+                    bool const fold[2] = {lanes_of(fold_m[0]), lanes_of(fold_m[1])};
                     v2f const rwr = ad*inv_wres2;                                   // 1/wr
                     v2f const rw2 = rwr*rwr;
                     v2f const t4 = sel2(fold[0], fold[1], A*rw2, splat2(0.f));
@@ -379,14 +390,15 @@
                     mom_add(lane & 7, cell, tsum);
                 }
             }
-            bool const any_odd = (!single || (tfl & kTfCorrected) != 0u) && ballot_b(odd[0] | odd[1] | pre2[0] | pre2[1]) != 0ull;
+            // (a wave of one cell has no odd lane)
+            bool const any_odd = (!single && (odd_m[0] | odd_m[1]) != 0ull) || (pre2_m[0] | pre2_m[1]) != 0ull;
             // (rare: a line in neither of its row's cells adds lane by lane)
             if (any_odd)
             {
 #pragma unroll
                 for (int h = 0; h < 2; ++h)
                 {
-                    if (odd[h])
+                    if (lanes_of(odd_m[h]))
                     {
 #pragma unroll
                         for (int k = 0; k < kMom; ++k)
@@ -402,6 +414,7 @@
             v2f v[7];
             v2f xq[7];                                      // x^2 of the seven points (the regimes fill what they test)
             unsigned ncm[2] = {0u, 0u};
+            bool any_nc;                                    // wave-uniform: some lane has noted a point
             if (tfl & kTfLreg)
             {
                 // every point but the line's own: the Lorentzian, A/(rel^2 + eta^2) (RFM_voigt.c:103,170,278)
@@ -423,6 +436,7 @@
                 v[3] = sel2(nc[0], nc[1], splat2(0.f), (amp*num)*rcp2(den));
                 ncm[0] = nc[0] ? 8u : 0u;
                 ncm[1] = nc[1] ? 8u : 0u;
+                any_nc = (ballot_b(nc[0]) | ballot_b(nc[1])) != 0ull;
                 xq[3] = xq0;
             }
             else
@@ -463,6 +477,7 @@
                     v[3] = sel2(nc[0], nc[1], splat2(0.f), v[3]);
                     ncm[0] = nc[0] ? 8u : 0u;
                     ncm[1] = nc[1] ? 8u : 0u;
+                    any_nc = (ballot_b(nc[0]) | ballot_b(nc[1])) != 0ull;
                 }
                 else if (tfl & kTfNcThree)
                 {
@@ -475,6 +490,7 @@
                         ncm[0] |= nc[0] ? (1u << k) : 0u;
                         ncm[1] |= nc[1] ? (1u << k) : 0u;
                     }
+                    any_nc = ballot_b((ncm[0] | ncm[1]) != 0u) != 0ull;
                 }
                 else
                 {
@@ -486,6 +502,7 @@
                         ncm[0] |= nc[0] ? (1u << k) : 0u;
                         ncm[1] |= nc[1] ? (1u << k) : 0u;
                     }
+                    any_nc = ballot_b((ncm[0] | ncm[1]) != 0u) != 0ull;
                 }
             }
             // ---- Humlicek region 2 (XLIM2 = 6.8 - y <= |x| < XLIM1, RFM_voigt.c:113, :187-199) is evaluated HERE (round 5):
@@ -495,7 +512,7 @@
             // (regions 3 and 4) still needs the reference's x and y to the bit and goes to the queues: 0.41 instead of 0.78
             // points per line and layer on the 1 cm-1 shortwave band.
             //   K = RSQRPI REPWID x RSQRPI y (E0 + XQ (E2 + XQ (E4 + XQ)))/(H0 + XQ (H2 + XQ (H4 + XQ (H6 + XQ)))) = cl num/den
-            if (ballot_b((ncm[0] | ncm[1]) != 0u) != 0ull)
+            if (any_nc)
             {
                 v2f const xl2 = 6.8f - y;
                 v2f const x2q = {xl2.x > 0.f ? xl2.x*xl2.x : 0.f, xl2.y > 0.f ? xl2.y*xl2.y : 0.f};     // XLIM2^2 (0: XLIM2 <= 0)
@@ -563,7 +580,7 @@
 #pragma unroll
                 for (int h = 0; h < 2; ++h)
                 {
-                    if (odd[h])
+                    if (lanes_of(odd_m[h]))
                     {
 #pragma unroll
                         for (int k = 0; k < 7; ++k)
@@ -574,7 +591,7 @@
                             }
                         }
                     }
-                    if (ballot_b(pre2[h]) != 0ull)
+                    if (pre2_m[h] != 0ull)
                     {
 #pragma unroll
                         for (int q = 0; q < 4; ++q)
@@ -584,7 +601,7 @@
                             float const xq = x*x;
                             float const den = fmaf(xq, d2r[h] + xq, d0r[h])*(xq + yq[h]);
                             float const corr = (amp[h]*cl[h])*fmaf(1.5f, xq, -0.5f*a0[h])*__builtin_amdgcn_rcpf(den);
-                            if (pre2[h] & (xq < x0q[h]))
+                            if (lanes_of(pre2_m[h]) & (xq < x0q[h]))
                             {
                                 GRT_ACC_ADD(&acc[c[h] + r - A0], (double)corr);
                             }
@@ -596,6 +613,7 @@
             // molecule slot and exponent index); full batches are given the reference's x and y (drain_raw).
             // Bits 0-6: points of the lane's first line, 7-13: of its second ----
             unsigned nc2 = ncm[0] | (ncm[1] << 7);
+            asm volatile("; lean block: core points" : "+v"(nc2));
             // (the wave's last lean block also empties the raw queue: ONE place in the code prepares entries, so the kernel
             // carries one copy less of that and of the four evaluation formulas behind it)
             bool const flush = base + walk_stride >= nrel || xcount == kLeanListCap;
@@ -635,5 +653,6 @@
             // Measured and dropped in the same round: the waves' leftover class queues evaluated as one list per workgroup
             // -- 75.4 ms either way)
             lean_fetch(base + walk_stride);
+            asm volatile("; lean block: end");
         }
     };
