@@ -21,7 +21,13 @@
 // GrtJacobianArgs last (six rows or every level, with any of the cloud and aerosol joins) makes the instance that also
 // leaves dF_up/dT_surf of its upward sweep (LevelSink: DIRECT, the third row group).  The fused six-row clear-sky
 // instance is the production pipeline's.  lw_radiance_kernel, further down, is the radiance at viewing angles beside a
-// pass's solver (grt_launch_lw_radiances): the same recurrence with a stream's c1 replaced by minus the viewing secant.
+// pass's solver (grt_launch_lw_radiances): the same recurrence with a stream's c1 replaced by minus the viewing secant;
+// lw_weighting_kernel behind it, the channels' transmittances and contribution functions.
+//
+// What these kernels must say alike, to the bit, is said once: LwPoint (a thread's row, point and layer optical depth),
+// absorption_tau (tau (1 - omega) of a materialised pass), AngleChunk (blockIdx.z's viewing angles), stream_step and
+// jacobian_step (a layer of the four streams and of their derivatives), channel_row_mean (a channel row from its pairs).
+// A new longwave kernel takes its point, its angles and its layer optical depth from these.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -106,18 +112,27 @@ __device__ __forceinline__ double beam_step(double I, double val, double e)
 }
 
 // One layer of the four streams (longwave.c:186-195, 204-211): I_s <- (1 - ext_s) val + I_s ext_s; returns the flux
-// sum_s c2[s] I_s.  ext(s) gives stream s's extinction where the step needs it (worked out there, or read ahead).
+// sum_s c2[s] I_s.  ext(s) gives stream s's extinction where the step needs it (worked out there, or read ahead); e takes
+// the four it used.
 template <typename Ext>
-__device__ __forceinline__ double stream_step(double (&I)[4], double val, Ext ext)
+__device__ __forceinline__ double stream_step(double (&I)[4], double val, Ext ext, double (&e)[4])
 {
     double f = 0.;
 #pragma unroll
     for (int s = 0; s < 4; ++s)
     {
-        I[s] = beam_step(I[s], val, ext(s));
+        e[s] = ext(s);
+        I[s] = beam_step(I[s], val, e[s]);
         f += kC2[s]*I[s];                                                // longwave.c:195
     }
     return f;
+}
+
+template <typename Ext>
+__device__ __forceinline__ double stream_step(double (&I)[4], double val, Ext ext)
+{
+    double e[4];
+    return stream_step(I, val, ext, e);
 }
 
 // sum_s c2[s] D_s, in stream_step's order: dF_up/dT_surf from the four streams' derivatives
@@ -132,22 +147,17 @@ __device__ __forceinline__ double jacobian_flux(double const (&D)[4])
     return f;
 }
 
-// stream_step on the way up with the streams' derivatives with respect to the surface temperature beside them: the layer
-// emits nothing that depends on it, so D_s <- D_s ext_s with the step's own extinctions; jac: sum_s c2[s] D_s
-__device__ __forceinline__ double stream_step_jacobian(double (&I)[4], double (&D)[4], double val, double t, double &jac)
+// One layer on the way up for the streams' derivatives with respect to the surface temperature: the layer emits nothing
+// that depends on it, so D_s <- D_s ext_s with the extinctions of the layer's stream_step; returns sum_s c2[s] D_s
+template <typename Ext>
+__device__ __forceinline__ double jacobian_step(double (&D)[4], Ext ext)
 {
-    double f = 0.;
 #pragma unroll
     for (int s = 0; s < 4; ++s)
     {
-        double const e = extinction(s, t);
-        double const p = (1. - e)*val;                                   // longwave.c:193
-        I[s] = p + I[s]*e;
-        f += kC2[s]*I[s];                                                // longwave.c:195
-        D[s] = D[s]*e;
+        D[s] = D[s]*ext(s);
     }
-    jac = jacobian_flux(D);
-    return f;
+    return jacobian_flux(D);
 }
 
 // The surface (longwave.c:202): emission bs at emissivity emis, the rest of each stream reflected; returns the flux
@@ -163,6 +173,59 @@ __device__ __forceinline__ double surface_step(double (&I)[4], double emis, doub
     return f;
 }
 
+// The four streams' derivatives with respect to the surface temperature beside lw_kernel's upward sweep: there with a
+// GrtJacobianArgs in the pack, nothing without
+template <bool ON> struct StreamDerivatives {};
+template <> struct StreamDerivatives<true> { double D[4]; };
+
+// Absorption optical depth of a layer of a materialised pass: tau (1 - omega) at offset o of the pass's rows, omega 0
+// where the pass left none  (longwave.c:252)
+__device__ __forceinline__ double absorption_tau(double const *tau, double const *omega, uint64_t o)
+{
+    return omega ? tau[o]*(1. - omega[o]) : tau[o]*(1. - 0.);
+}
+
+// One thread's point of a longwave pass, for every kernel that walks a column's layers at a grid point on a solver
+// instance's arguments (lw_kernel, lw_radiance_kernel, lw_weighting_kernel): the grid row, the point -- an idle lane of the
+// last block follows along at the last one --, its wavenumber, the column's temperatures and emissivity, and the layers'
+// absorption optical depth: FUSED, formed in registers from the instance's joins (LayerOptics), else read from the tau,
+// omega the pass left on the grid.
+template <bool FUSED, typename... Joins>
+struct LwPoint
+{
+    SolverRow const row;
+    int const col;
+    bool const live;
+    uint64_t const ii, nw;
+    int const V, L;
+    double const w;                                                      // longwave.c:246
+    double const *const tau, *const omega, *const tl, *const tv;
+    double const emis;
+    LayerOptics<FUSED, has_clouds<Joins...>, has<GrtAerosolArgs, Joins...>> const optics;                  // (fused forms)
+
+    __device__ __forceinline__ LwPoint(GrtLwArgs const &a, uint64_t i, Joins const &...joins)
+        : row(solver_row(a.ncol, joins...)), col(row.col), live(i < a.nw), ii(live ? i : a.nw - 1), nw(a.nw),
+          V(a.num_levels), L(V - 1), w(a.w0 + ii*a.dw), tau(a.tau + (uint64_t)col*a.optics_stride + ii),
+          omega((!FUSED && a.omega) ? a.omega + (uint64_t)col*a.optics_stride + ii : nullptr),
+          tl(a.t_layers + (uint64_t)col*L), tv(a.t_levels + (uint64_t)col*V),
+          emis(a.emis[(uint64_t)col*a.emis_stride + ii]),
+          optics(a, pick_clouds(joins...), col, row.tab, ii, pick<GrtAerosolArgs>(joins...))
+    {
+    }
+
+    // absorption optical depth of layer j: tau (1 - omega)  (longwave.c:252)
+    __device__ __forceinline__ double layer_tau(int j) const
+    {
+        if (FUSED)
+        {
+            double t, om, gg;
+            optics.at(j, t, om, gg);
+            return t*(1. - om);
+        }
+        return absorption_tau(tau, omega, (uint64_t)j*nw);
+    }
+};
+
 // OUT fused (GRT_OUT_ROWS and after): the clear-sky tail of the pipeline in one kernel -- Rayleigh and the two-object
 // optics combination are formed per layer in registers from tau_gas (LayerOptics: identical values), nothing spectral is
 // written, and the six integrated output rows leave as per-block trapezoid partial sums (LevelSink).
@@ -170,7 +233,7 @@ __device__ __forceinline__ double surface_step(double (&I)[4], double emis, doub
 // wavenumber bin (the pack's GrtBandArgs); GRT_OUT_ROWS_POINTS: the six rows also leave at every point, unweighted
 // (LevelSink).
 // Joins (fused forms): clouds (a GrtCloudArgs, or the draws of a GrtSubcolumnArgs), the aerosol object or both join per
-// layer (LayerOptics).  Only layer_tau changes: what leaves the kernel is OUT's.
+// layer (LayerOptics).  Only LwPoint::layer_tau changes: what leaves the kernel is OUT's.
 // A GrtJacobianArgs in the pack (GRT_OUT_ROWS and GRT_OUT_LEVELS): the upward sweep carries D[4] beside I[4], seeded at
 // the surface with emis dB/dT(T_surf, w), and every level's sum_s c2[s] D_s leaves through the sink's third row group.
 template <GrtSolverOutput OUT, typename... Joins>
@@ -181,72 +244,51 @@ __global__ __launch_bounds__(kSolverBlock) void lw_kernel(GrtLwArgs a, Joins... 
     static_assert(has<GrtBandArgs, Joins...> == (OUT == GRT_OUT_LEVEL_BINS), "bins go with GRT_OUT_LEVEL_BINS alone");
     constexpr bool JACOBIAN = has<GrtJacobianArgs, Joins...>;
     static_assert(!JACOBIAN || OUT == GRT_OUT_ROWS || OUT == GRT_OUT_LEVELS, "the Jacobian leaves the six-row and level forms");
-    SolverRow const row = solver_row(a.ncol, joins...);
-    int const col = row.col;
-    bool const live = i < a.nw;
-    if (!FUSED && !live)
+    if (!FUSED && i >= a.nw)                      // (fused form: idle lanes of the last block follow along, weight 0)
     {
         return;
     }
-    uint64_t const ii = live ? i : a.nw - 1;      // (fused form: idle lanes of the last block follow along, weight 0)
-    int const V = a.num_levels;
-    int const L = V - 1;
-    double const w = a.w0 + ii*a.dw;                                     // longwave.c:246
-    double const *tau = a.tau + (uint64_t)col*a.optics_stride + ii;
-    double const *omega = (!FUSED && a.omega) ? a.omega + (uint64_t)col*a.optics_stride + ii : nullptr;
-    double const *tl = a.t_layers + (uint64_t)col*L;
-    double const *tv = a.t_levels + (uint64_t)col*V;
-    double const emis = a.emis[(uint64_t)col*a.emis_stride + ii];
+    LwPoint<FUSED, Joins...> const p(a, i, joins...);
+    int const L = p.L;
+    double const w = p.w;
     LevelSink<FUSED, PROFILE, SPECTRAL, has<GrtBandArgs, Joins...>, JACOBIAN> sink(
-        a, row.slot, i, live, pick<GrtBandArgs>(joins...), GrtDirectArgs{pick<GrtJacobianArgs>(joins...).partials});
-    LayerOptics<FUSED, has_clouds<Joins...>, has<GrtAerosolArgs, Joins...>> const optics(
-        a, pick_clouds(joins...), col, row.tab, ii, pick<GrtAerosolArgs>(joins...));                    // (fused forms)
-
-    // absorption optical depth of layer j: tau (1 - omega)  (longwave.c:252)
-    auto layer_tau = [&](int j) -> double
-    {
-        if (FUSED)
-        {
-            double t, om, gg;
-            optics.at(j, t, om, gg);
-            return t*(1. - om);
-        }
-        uint64_t const o = (uint64_t)j*a.nw;
-        return omega ? tau[o]*(1. - omega[o]) : tau[o]*(1. - 0.);
-    };
+        a, p.row.slot, i, p.live, pick<GrtBandArgs>(joins...), GrtDirectArgs{pick<GrtJacobianArgs>(joins...).partials});
 
     double I[4] = {0., 0., 0., 0.};
     sink.put_zero(0, true);                                              // longwave.c:171
     for (int j = 0; j < L; ++j)
     {
-        double const t = layer_tau(j);
-        double const val = effective_planck(planck(tl[j], w), planck(tv[j + 1], w), t);
+        double const t = p.layer_tau(j);
+        double const val = effective_planck(planck(p.tl[j], w), planck(p.tv[j + 1], w), t);
         sink.put(j + 1, true, stream_step(I, val, [&](int s) { return extinction(s, t); }));
     }
+    // the surface, and with the Jacobian the seed of the streams' derivatives, from planck()'s own exponential
+    StreamDerivatives<JACOBIAN> d;
+    double bs;
     if constexpr (JACOBIAN)
     {
         double dbdt;
-        double const bs = planck_dT(a.t_surf[col], w, dbdt);
-        sink.put(L, false, surface_step(I, emis, bs));
-        double D[4] = {emis*dbdt, emis*dbdt, emis*dbdt, emis*dbdt};
-        sink.put_direct(L, jacobian_flux(D));
-        for (int j = L - 1; j >= 0; --j)
-        {
-            double const t = layer_tau(j);
-            double const val = effective_planck(planck(tl[j], w), planck(tv[j], w), t);
-            double jac;
-            sink.put(j, false, stream_step_jacobian(I, D, val, t, jac));
-            sink.put_direct(j, jac);
-        }
+        bs = planck_dT(a.t_surf[p.col], w, dbdt);
+        d.D[0] = d.D[1] = d.D[2] = d.D[3] = p.emis*dbdt;
     }
     else
     {
-        sink.put(L, false, surface_step(I, emis, planck(a.t_surf[col], w)));
-        for (int j = L - 1; j >= 0; --j)
+        bs = planck(a.t_surf[p.col], w);
+    }
+    sink.put(L, false, surface_step(I, p.emis, bs));
+    if constexpr (JACOBIAN)
+    {
+        sink.put_direct(L, jacobian_flux(d.D));
+    }
+    for (int j = L - 1; j >= 0; --j)
+    {
+        double const t = p.layer_tau(j);
+        double const val = effective_planck(planck(p.tl[j], w), planck(p.tv[j], w), t);
+        double e[4];
+        sink.put(j, false, stream_step(I, val, [&](int s) { return extinction(s, t); }, e));
+        if constexpr (JACOBIAN)
         {
-            double const t = layer_tau(j);
-            double const val = effective_planck(planck(tl[j], w), planck(tv[j], w), t);
-            sink.put(j, false, stream_step(I, val, [&](int s) { return extinction(s, t); }));
+            sink.put_direct(j, jacobian_step(d.D, [&](int s) { return e[s]; }));
         }
     }
     sink.finish(a);
@@ -280,13 +322,8 @@ __global__ __launch_bounds__(kJacobianBlock) void lw_surface_jacobian_kernel(Grt
     for (int j = L - 1; j >= 0; --j)
     {
         uint64_t const o = (uint64_t)j*nw;
-        double const t = omega ? tau[o]*(1. - omega[o]) : tau[o]*(1. - 0.);    // longwave.c:252
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-        {
-            D[s] = D[s]*extinction(s, t);
-        }
-        out[o] = jacobian_flux(D);
+        double const t = absorption_tau(tau, omega, o);
+        out[o] = jacobian_step(D, [&](int s) { return extinction(s, t); });
     }
 }
 
@@ -306,6 +343,31 @@ __device__ __forceinline__ double brightness_temperature(double I, double w)
 {
     return I > 0. ? kPlanckC2*w/log1p((kPlanckC1*w*w*w)/I) : 0.;
 }
+
+// The chunk of viewing angles of blockIdx.z, for the radiance and the weighting kernel: n real angles from `first` on, c1
+// of angle q minus its secant -- the padding angles of a last chunk repeat its last real one --, and angle_base, the chunk's
+// first angle among the partial sums' [slot][angles]: the slot is the grid row's in the fused form and (column, draw of the
+// launch) in the materialised one.
+template <bool FUSED>
+struct AngleChunk
+{
+    int first, n;
+    double c1[kRadianceChunk];
+    uint64_t angle_base;
+
+    __device__ __forceinline__ AngleChunk(GrtRadianceArgs const &r, SolverRow const &row)
+    {
+        int const slot = FUSED ? row.slot : row.col*r.subcolumns + r.draw;
+        first = (int)blockIdx.z*kRadianceChunk;
+        n = r.angles - first < kRadianceChunk ? r.angles - first : kRadianceChunk;
+#pragma unroll
+        for (int q = 0; q < kRadianceChunk; ++q)
+        {
+            c1[q] = -r.secant[(uint64_t)row.col*r.angles + first + (q < n ? q : n - 1)];
+        }
+        angle_base = (uint64_t)slot*r.angles + first;
+    }
+};
 
 // the partial sums of a chunk's N real angles: rows (up, down) of angle q at row_base + 2 q
 template <int N>
@@ -391,66 +453,33 @@ __global__ __launch_bounds__(kSolverBlock) void lw_radiance_kernel(GrtLwArgs a, 
     static_assert(kRadianceChunk == 4, "the chunk's partial sums are listed for one to four angles");
     constexpr bool CHANNELS = has<GrtChannelArgs, Joins...>;     // (the channel form: a GrtChannelArgs last in the joins)
     uint64_t const i = (uint64_t)blockIdx.x*kSolverBlock + threadIdx.x;
-    SolverRow const row = solver_row(a.ncol, joins...);
-    int const col = row.col;
-    int const slot = FUSED ? row.slot : col*r.subcolumns + r.draw;
-    bool const live = i < a.nw;
-    uint64_t const ii = live ? i : a.nw - 1;      // (idle lanes of the last block follow along, weight 0)
-    int const V = a.num_levels;
-    int const L = V - 1;
-    double const w = a.w0 + ii*a.dw;                                     // longwave.c:246
-    double const *tau = a.tau + (uint64_t)col*a.optics_stride + ii;
-    double const *omega = (!FUSED && a.omega) ? a.omega + (uint64_t)col*a.optics_stride + ii : nullptr;
-    double const *tl = a.t_layers + (uint64_t)col*L;
-    double const *tv = a.t_levels + (uint64_t)col*V;
-    double const emis = a.emis[(uint64_t)col*a.emis_stride + ii];
-    LayerOptics<FUSED, has_clouds<Joins...>, has<GrtAerosolArgs, Joins...>> const optics(
-        a, pick_clouds(joins...), col, row.tab, ii, pick<GrtAerosolArgs>(joins...));                    // (fused forms)
-
-    // absorption optical depth of layer j: tau (1 - omega)  (longwave.c:252)
-    auto layer_tau = [&](int j) -> double
-    {
-        if (FUSED)
-        {
-            double t, om, gg;
-            optics.at(j, t, om, gg);
-            return t*(1. - om);
-        }
-        uint64_t const o = (uint64_t)j*a.nw;
-        return omega ? tau[o]*(1. - omega[o]) : tau[o]*(1. - 0.);
-    };
-
-    // this chunk's angles: n real ones from `first` on; c1 of angle q is minus its secant
-    int const first = (int)blockIdx.z*kRadianceChunk;
-    int const n = r.angles - first < kRadianceChunk ? r.angles - first : kRadianceChunk;
-    double c1[kRadianceChunk];
-#pragma unroll
-    for (int q = 0; q < kRadianceChunk; ++q)
-    {
-        c1[q] = -r.secant[(uint64_t)col*r.angles + first + (q < n ? q : n - 1)];
-    }
+    LwPoint<FUSED, Joins...> const p(a, i, joins...);         // (idle lanes of the last block follow along, weight 0)
+    AngleChunk<FUSED> const ang(r, p.row);
+    int const col = p.col, L = p.L, first = ang.first, n = ang.n;
+    bool const live = p.live;
+    double const w = p.w;
 
     double I[kRadianceChunk] = {0., 0., 0., 0.};
     for (int j = 0; j < L; ++j)
     {
-        double const t = layer_tau(j);
-        double const val = effective_planck(planck(tl[j], w), planck(tv[j + 1], w), t);
+        double const t = p.layer_tau(j);
+        double const val = effective_planck(planck(p.tl[j], w), planck(p.tv[j + 1], w), t);
 #pragma unroll
         for (int q = 0; q < kRadianceChunk; ++q)
         {
-            I[q] = beam_step(I[q], val, beam_extinction(c1[q], t));
+            I[q] = beam_step(I[q], val, beam_extinction(ang.c1[q], t));
         }
     }
     double const down[kRadianceChunk] = {I[0], I[1], I[2], I[3]};
-    surface_step(I, emis, planck(a.t_surf[col], w));                     // (specular: the same angle, longwave.c:202)
+    surface_step(I, p.emis, planck(a.t_surf[col], w));                   // (specular: the same angle, longwave.c:202)
     for (int j = L - 1; j >= 0; --j)
     {
-        double const t = layer_tau(j);
-        double const val = effective_planck(planck(tl[j], w), planck(tv[j], w), t);
+        double const t = p.layer_tau(j);
+        double const val = effective_planck(planck(p.tl[j], w), planck(p.tv[j], w), t);
 #pragma unroll
         for (int q = 0; q < kRadianceChunk; ++q)
         {
-            I[q] = beam_step(I[q], val, beam_extinction(c1[q], t));
+            I[q] = beam_step(I[q], val, beam_extinction(ang.c1[q], t));
         }
     }
 
@@ -477,7 +506,7 @@ __global__ __launch_bounds__(kSolverBlock) void lw_radiance_kernel(GrtLwArgs a, 
         }
     }
     double const wt = trapezoid_weight(i, a.nw, a.dw, live);
-    uint64_t const row_base = ((uint64_t)slot*r.angles + first)*2;
+    uint64_t const row_base = ang.angle_base*2;
     switch (n)                                                           // (the same in every thread of the workgroup)
     {
     case 1: radiance_partials<1>(I, down, wt, r.partials, row_base); break;
@@ -489,6 +518,32 @@ __global__ __launch_bounds__(kSolverBlock) void lw_radiance_kernel(GrtLwArgs a, 
     {
         channel_partials(pick<GrtChannelArgs>(joins...), I, down, n, row_base, i, live);
     }
+}
+
+// The mean over the S draws of row `row` of channel c from its pairs, for both finishing kernels: a draw's pairs added in
+// ascending order from the first, the draws' sums in order (draw s's row lies s `stride` rows behind draw 0's), divided by
+// S where there is more than one, then by the sum of the channel's weights.
+__device__ __forceinline__ double channel_row_mean(GrtChannelArgs const &ch, double const *partials, uint64_t c, uint64_t row,
+                                                   uint64_t stride, int S)
+{
+    int const *e = ch.chan + GRT_CHANNEL_INTS*c;
+    int const npairs = (e[0] + e[1] - 1)/kSolverBlock - e[3] + 1;
+    double m = 0.;
+    for (int s = 0; s < S; ++s)
+    {
+        double const *p = partials + (row + s*stride)*ch.pairs + e[4];
+        double x = p[0];
+        for (int k = 1; k < npairs; ++k)
+        {
+            x += p[k];
+        }
+        m = s == 0 ? x : m + x;
+    }
+    if (S > 1)
+    {
+        m = m/(double)S;
+    }
+    return m/ch.sum_w[c];
 }
 
 // grt_launch_channel_finish (grt_kernels.h): the channels' pairs into channel radiances and brightness temperatures
@@ -504,24 +559,7 @@ __global__ __launch_bounds__(kChannelFinishBlock) void channel_finish_kernel(Grt
         return;
     }
     uint64_t const c = t % C, r = (t/C) % rows, col = t/(C*rows);
-    int const *e = ch.chan + GRT_CHANNEL_INTS*c;
-    int const npairs = (e[0] + e[1] - 1)/kSolverBlock - e[3] + 1;
-    double m = 0.;
-    for (int s = 0; s < S; ++s)
-    {
-        double const *p = ch.partials + ((col*S + s)*rows + r)*ch.pairs + e[4];
-        double x = p[0];
-        for (int k = 1; k < npairs; ++k)
-        {
-            x += p[k];
-        }
-        m = s == 0 ? x : m + x;
-    }
-    if (S > 1)
-    {
-        m = m/(double)S;
-    }
-    double const R = m/ch.sum_w[c];
+    double const R = channel_row_mean(ch, ch.partials, c, col*S*rows + r, rows, S);
     uint64_t const to = col*out_stride + out_offset + r*C + c;
     out[to] = R;
     if (brightness != nullptr)
@@ -600,61 +638,27 @@ __global__ __launch_bounds__(kSolverBlock) void lw_weighting_kernel(GrtLwArgs a,
 {
     __shared__ double tile[2][2][kRadianceChunk][kSolverBlock];      // [turn][T, K][angle][point]: 16 KiB
     uint64_t const i = (uint64_t)blockIdx.x*kSolverBlock + threadIdx.x;
-    SolverRow const row = solver_row(a.ncol, joins...);
-    int const col = row.col;
-    int const slot = FUSED ? row.slot : col*r.subcolumns + r.draw;
-    bool const live = i < a.nw;
-    uint64_t const ii = live ? i : a.nw - 1;      // (idle lanes of the last block follow along, never read)
-    int const V = a.num_levels;
-    int const L = V - 1;
-    double const w = a.w0 + ii*a.dw;                                     // longwave.c:246
-    double const *tau = a.tau + (uint64_t)col*a.optics_stride + ii;
-    double const *omega = (!FUSED && a.omega) ? a.omega + (uint64_t)col*a.optics_stride + ii : nullptr;
-    double const *tl = a.t_layers + (uint64_t)col*L;
-    double const *tv = a.t_levels + (uint64_t)col*V;
-    double const emis = a.emis[(uint64_t)col*a.emis_stride + ii];
-    LayerOptics<FUSED, has_clouds<Joins...>, has<GrtAerosolArgs, Joins...>> const optics(
-        a, pick_clouds(joins...), col, row.tab, ii, pick<GrtAerosolArgs>(joins...));                    // (fused forms)
-
-    // absorption optical depth of layer j: tau (1 - omega)  (longwave.c:252)
-    auto layer_tau = [&](int j) -> double
-    {
-        if (FUSED)
-        {
-            double t, om, gg;
-            optics.at(j, t, om, gg);
-            return t*(1. - om);
-        }
-        uint64_t const o = (uint64_t)j*a.nw;
-        return omega ? tau[o]*(1. - omega[o]) : tau[o]*(1. - 0.);
-    };
-
-    // this chunk's angles, as lw_radiance_kernel's
-    int const first = (int)blockIdx.z*kRadianceChunk;
-    int const n = r.angles - first < kRadianceChunk ? r.angles - first : kRadianceChunk;
-    double c1[kRadianceChunk];
-#pragma unroll
-    for (int q = 0; q < kRadianceChunk; ++q)
-    {
-        c1[q] = -r.secant[(uint64_t)col*r.angles + first + (q < n ? q : n - 1)];
-    }
+    LwPoint<FUSED, Joins...> const p(a, i, joins...);         // (idle lanes of the last block follow along, never read)
+    AngleChunk<FUSED> const ang(r, p.row);
+    int const V = p.V, L = p.L, n = ang.n;
+    double const w = p.w, emis = p.emis;
+    uint64_t const angle_base = ang.angle_base;
     uint64_t const R = (uint64_t)((wa.transmittance ? V : 0) + (wa.contribution ? V + 1 : 0));
-    uint64_t const angle_base = (uint64_t)slot*r.angles + first;
     int const k_row0 = wa.transmittance ? V : 0;                         // (the transmittance rows come first)
 
     double I[kRadianceChunk] = {0., 0., 0., 0.};
     double T[kRadianceChunk] = {1., 1., 1., 1.};
     for (int j = 0; j < L; ++j)
     {
-        double const t = layer_tau(j);
-        double const bc = planck(tl[j], w);
-        double const val = effective_planck(bc, planck(tv[j + 1], w), t);        // the downward sweep's
-        double const up = effective_planck(bc, planck(tv[j], w), t);             // the upward sweep's: P_j
+        double const t = p.layer_tau(j);
+        double const bc = planck(p.tl[j], w);
+        double const val = effective_planck(bc, planck(p.tv[j + 1], w), t);      // the downward sweep's
+        double const up = effective_planck(bc, planck(p.tv[j], w), t);           // the upward sweep's: P_j
         double (&tl_)[2][kRadianceChunk][kSolverBlock] = tile[j & 1];
 #pragma unroll
         for (int q = 0; q < kRadianceChunk; ++q)
         {
-            double const e = beam_extinction(c1[q], t);
+            double const e = beam_extinction(ang.c1[q], t);
             if (q < n)
             {
                 tl_[0][q][threadIdx.x] = T[q];
@@ -667,7 +671,7 @@ __global__ __launch_bounds__(kSolverBlock) void lw_weighting_kernel(GrtLwArgs a,
         weighting_gather(ch, wa, tl_, n, true, angle_base, R, k_row0, j);
     }
     // level L and the surface's emission, then the reflected downwelling (specular, longwave.c:202)
-    double const bs = planck(a.t_surf[col], w);
+    double const bs = planck(a.t_surf[p.col], w);
     for (int u = L; u <= L + 1; ++u)
     {
         double (&tl_)[2][kRadianceChunk][kSolverBlock] = tile[u & 1];
@@ -699,24 +703,7 @@ __global__ __launch_bounds__(kChannelFinishBlock) void weighting_finish_kernel(G
         return;
     }
     uint64_t const c = t % C, r = (t/C) % R, angle = (t/(C*R)) % A, col = t/(C*R*A);
-    int const *e = ch.chan + GRT_CHANNEL_INTS*c;
-    int const npairs = (e[0] + e[1] - 1)/kSolverBlock - e[3] + 1;
-    double m = 0.;
-    for (int s = 0; s < S; ++s)
-    {
-        double const *p = wa.partials + (((col*S + s)*A + angle)*R + r)*ch.pairs + e[4];
-        double x = p[0];
-        for (int k = 1; k < npairs; ++k)
-        {
-            x += p[k];
-        }
-        m = s == 0 ? x : m + x;
-    }
-    if (S > 1)
-    {
-        m = m/(double)S;
-    }
-    double const out = m/ch.sum_w[c];
+    double const out = channel_row_mean(ch, wa.partials, c, (col*S*A + angle)*R + r, A*R, S);
     uint64_t const nt = wa.transmittance ? (uint64_t)V : 0;
     if (r < nt)
     {
@@ -753,7 +740,7 @@ __global__ __launch_bounds__(kTermsBlock) void lw_terms_kernel(GrtLwArgs a)
     uint64_t const i = o - j*nw;
     double const w = a.w0 + i*a.dw;                                      // longwave.c:246
     uint64_t const at = (uint64_t)col*a.optics_stride + o;
-    double const t = a.omega ? a.tau[at]*(1. - a.omega[at]) : a.tau[at]*(1. - 0.);     // longwave.c:252
+    double const t = absorption_tau(a.tau, a.omega, at);
     double const *tl = a.t_layers + (uint64_t)col*L;
     double const *tv = a.t_levels + (uint64_t)col*V;
     double const bc = planck(tl[j], w);
@@ -845,6 +832,16 @@ int launch(hipStream_t s, GrtSolverInstance const &in, GrtLwArgs const &a, Joins
     return (int)hipGetLastError();
 }
 
+// a six-row or level instance: the one that also leaves the surface-temperature Jacobian (grt_pipeline_run_sky_jacobian's
+// sets and forms) -- third given, a GrtJacobianArgs last in its joins --, or the one without (grt_solver_instance_ok lets
+// a GrtJacobianArgs through with these two outputs alone)
+template <GrtSolverOutput OUT, typename... Joins>
+int launch_third_group(hipStream_t s, GrtSolverInstance const &in, GrtLwArgs const &a, GrtJacobianArgs const *third,
+                       Joins const &...joins)
+{
+    return third != nullptr ? launch<OUT>(s, in, a, joins..., *third) : launch<OUT>(s, in, a, joins...);
+}
+
 // ... and of lw_radiance_kernel: the instance's grid rows, the chunks of angles along z
 template <bool FUSED, typename... Joins>
 int launch_radiances(hipStream_t s, GrtSolverInstance const &in, GrtLwArgs const &a, GrtRadianceArgs const &r,
@@ -883,34 +880,8 @@ extern "C" int grt_launch_lw(void *stream, GrtSolverInstance const *in, GrtLwArg
         return (int)hipErrorInvalidValue;
     }
     hipStream_t const s = (hipStream_t)stream;
-    // every instance of lw_kernel that also leaves the surface-temperature Jacobian (grt_pipeline_run_sky_jacobian's sets
-    // and forms) ...
-    if (in->jacobian != nullptr)
-    {
-        GrtJacobianArgs const &d = *in->jacobian;
-        switch (GRT_INSTANCE(in->out, grt_solver_join(in)))
-        {
-        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_NONE): return launch<GRT_OUT_ROWS>(s, *in, *a, d);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_NONE): return launch<GRT_OUT_LEVELS>(s, *in, *a, d);
-        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->clouds, d);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, d);
-        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->aerosols, d);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->aerosols, d);
-        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns, d);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, d);
-        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_CLOUDS_AEROSOLS):
-            return launch<GRT_OUT_ROWS>(s, *in, *a, *in->clouds, *in->aerosols, d);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS_AEROSOLS):
-            return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, *in->aerosols, d);
-        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
-            return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns, *in->aerosols, d);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
-            return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->aerosols, d);
-        default:
-            return (int)hipErrorInvalidValue;
-        }
-    }
-    // ... and every other instance of lw_kernel there is
+    // every instance of lw_kernel there is; the six-row and level instances twice, as launch_third_group says
+    GrtJacobianArgs const *const d = in->jacobian;
     switch (GRT_INSTANCE(in->out, grt_solver_join(in)))
     {
     case GRT_INSTANCE(GRT_OUT_LAYERS, GRT_JOIN_NONE):
@@ -919,28 +890,31 @@ extern "C" int grt_launch_lw(void *stream, GrtSolverInstance const *in, GrtLwArg
         hipLaunchKernelGGL(lw_sweeps_kernel, dim3((unsigned)((a->nw + kSweepBlock - 1)/kSweepBlock), a->ncol, 1),
                            dim3(kSweepBlock), 0, s, *a);
         return (int)hipGetLastError();
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_NONE): return launch<GRT_OUT_ROWS>(s, *in, *a);
     case GRT_INSTANCE(GRT_OUT_CHAINS, GRT_JOIN_NONE): return launch<GRT_OUT_CHAINS>(s, *in, *a);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_NONE): return launch<GRT_OUT_LEVELS>(s, *in, *a);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->clouds);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds);
     case GRT_INSTANCE(GRT_OUT_ROWS_POINTS, GRT_JOIN_NONE): return launch<GRT_OUT_ROWS_POINTS>(s, *in, *a);
     case GRT_INSTANCE(GRT_OUT_ROWS_POINTS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_ROWS_POINTS>(s, *in, *a, *in->clouds);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->aerosols);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->aerosols);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns);
+    case GRT_INSTANCE(GRT_OUT_LEVEL_BINS, GRT_JOIN_NONE): return launch<GRT_OUT_LEVEL_BINS>(s, *in, *a, *in->bins);
     case GRT_INSTANCE(GRT_OUT_LEVEL_BINS, GRT_JOIN_CLOUDS):
         return launch<GRT_OUT_LEVEL_BINS>(s, *in, *a, *in->clouds, *in->bins);
-    case GRT_INSTANCE(GRT_OUT_LEVEL_BINS, GRT_JOIN_NONE): return launch<GRT_OUT_LEVEL_BINS>(s, *in, *a, *in->bins);
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_NONE): return launch_third_group<GRT_OUT_ROWS>(s, *in, *a, d);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_NONE): return launch_third_group<GRT_OUT_LEVELS>(s, *in, *a, d);
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_CLOUDS): return launch_third_group<GRT_OUT_ROWS>(s, *in, *a, d, *in->clouds);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS): return launch_third_group<GRT_OUT_LEVELS>(s, *in, *a, d, *in->clouds);
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_AEROSOLS): return launch_third_group<GRT_OUT_ROWS>(s, *in, *a, d, *in->aerosols);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_AEROSOLS):
+        return launch_third_group<GRT_OUT_LEVELS>(s, *in, *a, d, *in->aerosols);
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_SUBCOLUMNS):
+        return launch_third_group<GRT_OUT_ROWS>(s, *in, *a, d, *in->subcolumns);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS):
+        return launch_third_group<GRT_OUT_LEVELS>(s, *in, *a, d, *in->subcolumns);
     case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_CLOUDS_AEROSOLS):
-        return launch<GRT_OUT_ROWS>(s, *in, *a, *in->clouds, *in->aerosols);
+        return launch_third_group<GRT_OUT_ROWS>(s, *in, *a, d, *in->clouds, *in->aerosols);
     case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS_AEROSOLS):
-        return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, *in->aerosols);
+        return launch_third_group<GRT_OUT_LEVELS>(s, *in, *a, d, *in->clouds, *in->aerosols);
     case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
-        return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns, *in->aerosols);
+        return launch_third_group<GRT_OUT_ROWS>(s, *in, *a, d, *in->subcolumns, *in->aerosols);
     case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
-        return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->aerosols);
+        return launch_third_group<GRT_OUT_LEVELS>(s, *in, *a, d, *in->subcolumns, *in->aerosols);
     default:
         return (int)hipErrorInvalidValue;
     }
