@@ -30,7 +30,7 @@ GRT_CLOUD_PHASE, GRT_CLOUD_MODEL, GRT_CLOUD_FIELDS = 7, 8, 9   # ... of GrtCloud
  TAG_ALLSKY_SW, TAG_BINS, TAG_SUBCOLUMN_MEAN, TAG_AEROSOL_LW, TAG_AEROSOL_SW, TAG_BAND_PROFILES, TAG_SURFACE,
  TAG_CLOUD_SAMPLER, TAG_SKY_LW, TAG_SKY_SW, TAG_ZENITH_SW, TAG_ZENITH_MEAN, TAG_DIRECT_BEAM, TAG_SKY_ZENITH_SW,
  TAG_SKY_ZENITH_MEAN, TAG_SURFACE_JACOBIAN, TAG_RADIANCE, TAG_CHANNELS, TAG_WEIGHTING, TAG_WEIGHTING_FINISH,
- TAG_KDIST) = range(1, 30)
+ TAG_KDIST, TAG_KDIST_MAP, TAG_KDIST_MAPPED) = range(1, 32)
 TAG_FAR_OFFSET = TAG_FAR_LW - TAG_GAS_LW    # from a line kernel's tag to its far-field gather's
 CLOUD_SAMPLER_TAG = TAG_CLOUD_SAMPLER
 GRT_MAX_SUBCOLUMNS = 64             # grt_pipeline_run_subcolumns: subcolumns per column, 1 .. this
@@ -45,6 +45,7 @@ GRT_JACOBIAN_ROWS_PER_SET = 3       # grt_pipeline_run_sky_jacobian: dF_up/dT_su
 GRT_MAX_VIEW_ANGLES = 16            # grt_pipeline_run_sky_radiances: viewing angles per column, 1 .. this
 GRT_RADIANCE_ROWS_PER_ANGLE = 2     # ... per angle: upward at the top of the atmosphere, downward at the surface
 GRT_MAX_CHANNELS = 16384            # grt_pipeline_run_sky_channels: channels of an instrument, 1 .. this
+KDIST_KEY_ROW, KDIST_KEY_SUM = 0, 1    # grt_kdist_class_map, GrtKdistKey.kind: the key is one row / the sum of the rows
 KDIST_MAX_CLASSES = 1024            # grt_pipeline_run_kdist, grt_kdist_rows: classes of a k-distribution, 2 .. this
 RETURN_CODES = ["GRTCODE_SUCCESS", "GRTCODE_INVALID_ERR", "GRTCODE_DIVBYZERO_ERR", "GRTCODE_OVERFLOW_ERR",
                 "GRTCODE_UNDERFLOW_ERR", "GRTCODE_SENTINEL_ERR", "GRTCODE_NULL_ERR", "GRTCODE_NON_NULL_ERR",
@@ -218,6 +219,14 @@ class GrtKdist(C.Structure):
     _fields_ = [("num_classes", C.c_int), ("class_edges", c_double_p), ("lw", GrtKdistBand), ("sw", GrtKdistBand)]
 
 
+class GrtKdistKey(C.Structure):
+    _fields_ = [("kind", C.c_int), ("layer", C.c_int), ("map_dev", C.c_void_p)]
+
+
+class GrtKdistKeys(C.Structure):
+    _fields_ = [("lw", GrtKdistKey), ("sw", GrtKdistKey)]
+
+
 class GrtZeniths(C.Structure):
     _fields_ = [("num_zeniths", C.c_int), ("cos_zenith", c_double_p), ("weight", c_double_p),
                 ("zenith_fluxes_dev", C.c_void_p), ("zenith_level_fluxes_dev", C.c_void_p)]
@@ -244,7 +253,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_channels grt_channel_pair_count grt_pipeline_run_sky_weighting grt_pipeline_run_sky_zeniths grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_kdist_rows grt_pipeline_run_kdist grt_kdist_chunk_points grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_channels grt_channel_pair_count grt_pipeline_run_sky_weighting grt_pipeline_run_sky_zeniths grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_kdist_rows grt_pipeline_run_kdist grt_kdist_chunk_points grt_kdist_class_map grt_kdist_mapped_rows grt_pipeline_run_kdist_correlated grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -324,6 +333,13 @@ def load_library(path=None):
                                        C.POINTER(GrtKdistBand)]
         lib.grt_pipeline_run_kdist.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtKdist)]
         lib.grt_kdist_chunk_points.argtypes = []
+    if hasattr(lib, "grt_pipeline_run_kdist_correlated"):    # (GRT_LIB_PATH may name an older library: a timing yardstick)
+        lib.grt_kdist_class_map.argtypes = [C.c_int, C.c_void_p, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int,
+                                            C.c_longlong, C.c_int, c_double_p, C.c_void_p]
+        lib.grt_kdist_mapped_rows.argtypes = [C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_longlong,
+                                              C.c_longlong, C.c_double, C.c_int, C.POINTER(GrtKdistBand)]
+        lib.grt_pipeline_run_kdist_correlated.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtKdist),
+                                                          C.POINTER(GrtKdistKeys)]
     lib.grt_pipeline_sky_set_count.argtypes = [C.c_uint]
     if hasattr(lib, "grt_pipeline_run_zeniths"):    # (GRT_LIB_PATH may name an older library: a timing yardstick)
         lib.grt_pipeline_run_zeniths.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtZeniths), C.c_void_p,
@@ -880,9 +896,59 @@ def kdist_rows(device, tau_ptr, rows, n, dw, class_edges, edges, weight=None):
     bufs = [DeviceBuffer(device, 4 * count), DeviceBuffer(device, 8 * count), DeviceBuffer(device, 8 * count)]
     try:
         band.points_dev, band.weight_dev, band.tau_dev = (b.ptr for b in bufs)
-        addr = tau_ptr if isinstance(tau_ptr, int) or tau_ptr is None else C.cast(tau_ptr, C.c_void_p).value
-        check(lib.grt_kdist_rows(device, C.c_void_p(addr), int(rows), int(n), float(dw), K, _dp(ce), C.byref(band)))
+        check(lib.grt_kdist_rows(device, C.c_void_p(_addr(tau_ptr)), int(rows), int(n), float(dw), K, _dp(ce), C.byref(band)))
         return (bufs[0].to_host(shape, dtype=np.int32), bufs[1].to_host(shape), bufs[2].to_host(shape))
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def _addr(ptr):
+    """a device pointer as an int (or None)"""
+    return ptr if isinstance(ptr, int) or ptr is None else C.cast(ptr, C.c_void_p).value
+
+
+def _kdist_key(key):
+    """("sum",) or ("layer", r) -> (kind, layer) of a GrtKdistKey"""
+    if key[0] == "sum":
+        return KDIST_KEY_SUM, 0
+    if key[0] == "layer":
+        return KDIST_KEY_ROW, int(key[1])
+    raise ValueError(f"key {key!r}: ('sum',) or ('layer', r)")
+
+
+def kdist_class_map(device, x_ptr, groups, rows_per_group, n, class_edges, kind, key_row=0):
+    """grt_kdist_class_map on the device array x_ptr [groups][rows_per_group][n]: -> a DeviceBuffer (the caller's to free)
+    that holds the map [groups][n] of uint16 classes of the key -- row key_row of each group (kind KDIST_KEY_ROW) or the
+    sum of its rows (KDIST_KEY_SUM) -- among the K classes that class_edges [K - 1] cut."""
+    lib = load_library()
+    ce = _f64(class_edges).ravel()
+    buf = DeviceBuffer(device, 2 * max(int(groups) * int(n), 1))
+    try:
+        check(lib.grt_kdist_class_map(device, C.c_void_p(_addr(x_ptr)), int(groups), int(rows_per_group), int(n), int(kind),
+                                      int(key_row), ce.size + 1, _dp(ce), buf.ptr))
+    except Exception:
+        buf.free()
+        raise
+    return buf
+
+
+def kdist_mapped_rows(device, values_ptr, group_stride, map_ptr, groups, rows_per_group, n, dw, num_classes, edges,
+                      weight=None):
+    """grt_kdist_mapped_rows: the rows at values_ptr + g group_stride + r n (in doubles) reduced under the class map
+    map_ptr [groups][n] -> points (int32) and weight, each [groups][num_bins][K], and tau [groups][rows_per_group]
+    [num_bins][K], for the bins of edges and the spectral weight [n] (None: 1).  Waits for the result."""
+    lib = load_library()
+    band, _keep = _kdist_band(edges, weight)
+    G, R, K, nb = int(groups), int(rows_per_group), int(num_classes), band.num_bins
+    shared = max(G * nb * K, 1)
+    bufs = [DeviceBuffer(device, 4 * shared), DeviceBuffer(device, 8 * shared), DeviceBuffer(device, 8 * max(shared * R, 1))]
+    try:
+        band.points_dev, band.weight_dev, band.tau_dev = (b.ptr for b in bufs)
+        check(lib.grt_kdist_mapped_rows(device, C.c_void_p(_addr(values_ptr)), int(group_stride), C.c_void_p(_addr(map_ptr)),
+                                        G, R, int(n), float(dw), K, C.byref(band)))
+        return (bufs[0].to_host((G, nb, K), dtype=np.int32), bufs[1].to_host((G, nb, K)),
+                bufs[2].to_host((G, R, nb, K)))
     finally:
         for b in bufs:
             b.free()
@@ -912,6 +978,7 @@ class Pipeline:
         self.spec_shape = None  # (sets, longwave bins, shortwave bins) of the last run_spectral
         self.band_shape = None  # ... of the last run_band_profiles
         self.kdist_shape = None  # (classes, longwave bins, shortwave bins) of the last run_kdist
+        self.kdist_corr_shape = None  # ... of the last run_kdist_correlated, and whether it kept the maps
         self.out = self._buffer("run", 8 * GRT_FLUXES_PER_COLUMN * max_columns)
 
     def _buffer(self, name, nbytes):
@@ -1098,6 +1165,47 @@ class Pipeline:
             out[name] = {"points": self.buffers[f"kdist.{name}.points"].to_host(shape, dtype=np.int32),
                          "weight": self.buffers[f"kdist.{name}.weight"].to_host(shape),
                          "tau": self.buffers[f"kdist.{name}.tau"].to_host(shape)}
+        return out
+
+    def run_kdist_correlated(self, gcols, class_edges, lw_edges=None, sw_edges=None, lw_key=("sum",), sw_key=("sum",),
+                             lw_weight=None, sw_weight=None, keep_map=False):
+        """grt_pipeline_run_kdist_correlated into this object's device buffers (kdist_correlated() reads them): run_kdist's
+        arguments, and per band the key whose classes order the column's points -- ("sum",): the column's vertical optical
+        depth, ("layer", r): layer r's.  keep_map: the maps go to buffers of this object (kdist_correlated() returns them,
+        buffers["kdist_corr.lw.map"] is the device array for api.kdist_mapped_rows), else they stay in pipeline scratch."""
+        gk, _keep = make_kdist(class_edges, lw_edges, sw_edges, lw_weight, sw_weight)
+        K, L = gk.num_classes, self.num_levels - 1
+        keys = GrtKdistKeys()
+        for bi, (name, band, key, spec) in enumerate((("lw", gk.lw, keys.lw, lw_key), ("sw", gk.sw, keys.sw, sw_key))):
+            count = max(self.max_columns * band.num_bins * K, 1)
+            band.points_dev = self._buffer(f"kdist_corr.{name}.points", 4 * count).ptr
+            band.weight_dev = self._buffer(f"kdist_corr.{name}.weight", 8 * count).ptr
+            band.tau_dev = self._buffer(f"kdist_corr.{name}.tau", 8 * count * L).ptr
+            key.kind, key.layer = _kdist_key(spec)
+            key.map_dev = None
+            if keep_map and band.num_bins > 0:
+                key.map_dev = self._buffer(f"kdist_corr.{name}.map", 2 * self.max_columns * self.nw[bi]).ptr
+        self.kdist_corr_shape = (K, gk.lw.num_bins, gk.sw.num_bins, bool(keep_map))
+        check(self.lib.grt_pipeline_run_kdist_correlated(self.p, C.byref(gcols), C.byref(gk), C.byref(keys)))
+
+    def kdist_correlated(self, ncol):
+        """The last run_kdist_correlated: {"lw": {"points", "weight", "tau", "map"}, "sw": ...} -- points (int32) and weight
+        [ncol][num_bins][K], tau [ncol][L][num_bins][K], map uint16 [ncol][n] when it was kept, else None."""
+        self.sync()
+        K, nb_lw, nb_sw, kept = self.kdist_corr_shape
+        L = self.num_levels - 1
+        out = {}
+        for bi, (name, nb) in enumerate((("lw", nb_lw), ("sw", nb_sw))):
+            if nb == 0:
+                out[name] = {"points": np.zeros((ncol, 0, K), dtype=np.int32), "weight": np.zeros((ncol, 0, K)),
+                             "tau": np.zeros((ncol, L, 0, K)), "map": None}
+                continue
+            # (tau is laid out for ncol columns: [ncol][L][nb][K] from the buffer's start)
+            out[name] = {"points": self.buffers[f"kdist_corr.{name}.points"].to_host((ncol, nb, K), dtype=np.int32),
+                         "weight": self.buffers[f"kdist_corr.{name}.weight"].to_host((ncol, nb, K)),
+                         "tau": self.buffers[f"kdist_corr.{name}.tau"].to_host((ncol, L, nb, K)),
+                         "map": (self.buffers[f"kdist_corr.{name}.map"].to_host((ncol, self.nw[bi]), dtype=np.uint16)
+                                 if kept else None)}
         return out
 
     def _six_row_or_profile_ptrs(self, name, profiles):

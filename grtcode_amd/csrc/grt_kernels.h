@@ -819,6 +819,38 @@ typedef struct GrtKdistArgs
 int grt_kdist_chunk(void);
 int grt_launch_kdist(void *stream, GrtKdistArgs const *a);
 
+/* Correlated k-distributions (k_kdist.hip; grt_ext.h: grt_kdist_class_map and grt_kdist_mapped_rows, which define them).
+   The map: per group g of x [groups][rows_per_group][n] and point i, the class (as above) of the key -- x[g][key_row][i],
+   or with key_row < 0 the sum of the group's rows in order from +0.0 -- to map [groups][n].
+   The mapped reduction: row r of group g starts at values + g group_stride + r n; a point's class is map[g][i], and an
+   entry >= num_classes belongs to no class.  points and weight_sum are [groups][num_bins][num_classes] (the same for
+   every row), tau_sum [groups][rows_per_group][num_bins][num_classes]; any of them NULL, not all.  One workgroup per
+   (group, row, bin), per (group, bin) without tau_sum. */
+typedef struct GrtKdistMapArgs
+{
+    double const *x;
+    long long groups, rows_per_group, n;
+    long long key_row;              /* or < 0: the sum of the rows */
+    int num_classes;
+    double const *class_edges;
+    unsigned short *map;
+} GrtKdistMapArgs;
+typedef struct GrtKdistMappedArgs
+{
+    double const *values;
+    long long group_stride;
+    unsigned short const *map;
+    long long groups, rows_per_group, n;
+    double dw;
+    int num_classes, num_bins;
+    int const *edges;
+    double const *weight;           /* or NULL: 1 */
+    int *points;
+    double *weight_sum, *tau_sum;
+} GrtKdistMappedArgs;
+int grt_launch_kdist_map(void *stream, GrtKdistMapArgs const *a);
+int grt_launch_kdist_mapped(void *stream, GrtKdistMappedArgs const *a);
+
 /* Fused Rayleigh + combine for the clear-sky driver sequence (rayleigh.c:39 +
    optics.c:138-145 with K=2, gas omega=g=0, Rayleigh omega=1,g=0):
    tau_tot = tau_gas + tau_R, omega = tau_R/tau_tot, g = 0/ tau_R.  n_layer [ncol][L]. */

@@ -1,4 +1,5 @@
-// k_kdist.hip -- k-distributions of optical-depth rows (grt_ext.h: grt_kdist_rows, grt_pipeline_run_kdist).
+// k_kdist.hip -- k-distributions of optical-depth rows (grt_ext.h: grt_kdist_rows, grt_pipeline_run_kdist) and their
+// correlated form under one class map per group of rows.
 //
 // One 256-thread workgroup per (row, bin).  A bin's points are classified against K - 1 class edges, and per class the
 // points are counted and their trapezoid weights W_i and the products T_i = W_i tau_i are summed -- each sum the plain
@@ -18,6 +19,11 @@
 // that a CU's 32 waves allow up to K = 257, six at K = 1024.  (Measured, 64 columns of the bench grids, 16 bins, K = 64:
 // 7.9 ms with chunks of 2048 points, four workgroups a CU; 5.0 ms with 1024 -- phase 2 waits for LDS once every four
 // points, and a second resident wave per SIMD fills the wait.)
+//
+// The correlated form (grt_kdist_class_map, grt_kdist_mapped_rows, grt_pipeline_run_kdist_correlated) fixes one class per
+// (group, point) -- kdist_map_kernel: the class of a key row or of the sum of the group's rows, 16 bits a point -- and
+// reduces every row of the group under it: kdist_mapped_kernel is kdist_kernel with phase 1's bisection replaced by a
+// 2-byte load from the map; phase 2 (sum_chunk) is the same function for both.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../grt_kernels.h"
@@ -62,6 +68,83 @@ __device__ __forceinline__ void load_step(unsigned short const *c_s, double cons
     t[0] = t01.x, t[1] = t01.y, t[2] = t23.x, t[3] = t23.y;
     asm volatile("" : "+v"(four), "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]), "+v"(t[0]), "+v"(t[1]), "+v"(t[2]),
                  "+v"(t[3]));
+}
+
+// Phase 2 of a chunk, for both kernels: the owners of the classes add the chunk's `padded` parked points (a multiple of
+// kStep, the pad of class kNoClass) to their count, wsum and tsum, in index order.
+template <int NC>
+__device__ __forceinline__ void sum_chunk(unsigned short const *c_s, double const *w_s, double const *t_s, int padded,
+                                          int K, int tid, int wave, bool wave_has_classes, int (&count)[NC],
+                                          double (&wsum)[NC], double (&tsum)[NC])
+{
+    // A point of another thread's class adds +0.0, which changes no bit of a sum that started from +0.0: x + (+0.0)
+    // is x for every x but -0.0, NaN and the infinities included, and such a sum is never -0.0 (only -0.0 + -0.0
+    // gives that).  So the select sits on the term, off the accumulators' dependency chain.
+    if (NC == 1 && K <= 64)
+    {
+        // one wave owns every class: straight-line code, no point passed by
+        if (wave == 0)
+        {
+            for (int j = 0; j < padded; j += kStep)
+            {
+                uint64_t four;
+                double w[kStep], t[kStep];
+                load_step(c_s, w_s, t_s, j, four, w, t);
+#pragma unroll
+                for (int q = 0; q < kStep; ++q)
+                {
+                    bool const mine = ((unsigned)(four >> (16*q)) & 0xffffu) == (unsigned)tid;
+                    count[0] += mine ? 1 : 0;
+                    wsum[0] = __dadd_rn(wsum[0], mine ? w[q] : 0.);
+                    tsum[0] = __dadd_rn(tsum[0], mine ? t[q] : 0.);
+                }
+            }
+        }
+    }
+    else if (wave_has_classes)
+    {
+        for (int j = 0; j < padded; j += kStep)
+        {
+            uint64_t four;
+            double w[kStep], t[kStep];
+            load_step(c_s, w_s, t_s, j, four, w, t);
+            unsigned const lo = __builtin_amdgcn_readfirstlane((unsigned)four);
+            unsigned const hi = __builtin_amdgcn_readfirstlane((unsigned)(four >> 32));
+#pragma unroll
+            for (int q = 0; q < kStep; ++q)
+            {
+                // (the same for every lane, and in scalar registers: class = slot x 256 + wave x 64 + lane)
+                unsigned const cls = ((q < 2 ? lo : hi) >> (16*(q & 1))) & 0xffffu;
+                if (((cls >> 6) & 3u) != (unsigned)wave)
+                {
+                    continue;      // another wave's class
+                }
+                unsigned slot = cls >> 8;
+#pragma unroll
+                for (int c = 0; c < NC; ++c)
+                {
+                    if (NC > 1)
+                    {
+                        // (every test on a value of its own, in a scalar register: the NC tests stay a chain of scalar
+                        // branches where the compiler would else fold them into one switch over divergent blocks --
+                        // measured at K = 1024, 64 columns of the bench grids: 18.1 ms as a switch, 10.9 ms as the chain)
+                        asm volatile("" : "+s"(slot));
+                    }
+                    if (NC == 1 || slot == (unsigned)c)
+                    {
+                        if (NC > 1)
+                        {
+                            asm volatile("");      // (keeps the scalar branch a branch: not NC selects a point)
+                        }
+                        bool const mine = cls == (unsigned)(tid + c*kThreads);
+                        count[c] += mine ? 1 : 0;
+                        wsum[c] = __dadd_rn(wsum[c], mine ? w[q] : 0.);
+                        tsum[c] = __dadd_rn(tsum[c], mine ? t[q] : 0.);
+                    }
+                }
+            }
+        }
+    }
 }
 
 // NC: the classes a thread owns (K <= NC x 256)
@@ -127,67 +210,7 @@ __global__ __launch_bounds__(kThreads) void kdist_kernel(GrtKdistArgs a)
                 c_s[j] = (unsigned short)kNoClass;
             }
             __syncthreads();
-            // A point of another thread's class adds +0.0, which changes no bit of a sum that started from +0.0: x + (+0.0)
-            // is x for every x but -0.0, NaN and the infinities included, and such a sum is never -0.0 (only -0.0 + -0.0
-            // gives that).  So the select sits on the term, off the accumulators' dependency chain.
-            if (NC == 1 && K <= 64)
-            {
-                // one wave owns every class: straight-line code, no point passed by
-                if (wave == 0)
-                {
-                    for (int j = 0; j < padded; j += kStep)
-                    {
-                        uint64_t four;
-                        double w[kStep], t[kStep];
-                        load_step(c_s, w_s, t_s, j, four, w, t);
-#pragma unroll
-                        for (int q = 0; q < kStep; ++q)
-                        {
-                            bool const mine = ((unsigned)(four >> (16*q)) & 0xffffu) == (unsigned)tid;
-                            count[0] += mine ? 1 : 0;
-                            wsum[0] = __dadd_rn(wsum[0], mine ? w[q] : 0.);
-                            tsum[0] = __dadd_rn(tsum[0], mine ? t[q] : 0.);
-                        }
-                    }
-                }
-            }
-            else if (wave_has_classes)
-            {
-                for (int j = 0; j < padded; j += kStep)
-                {
-                    uint64_t four;
-                    double w[kStep], t[kStep];
-                    load_step(c_s, w_s, t_s, j, four, w, t);
-                    unsigned const lo = __builtin_amdgcn_readfirstlane((unsigned)four);
-                    unsigned const hi = __builtin_amdgcn_readfirstlane((unsigned)(four >> 32));
-#pragma unroll
-                    for (int q = 0; q < kStep; ++q)
-                    {
-                        // (the same for every lane, and in scalar registers: class = slot x 256 + wave x 64 + lane)
-                        unsigned const cls = ((q < 2 ? lo : hi) >> (16*(q & 1))) & 0xffffu;
-                        if (((cls >> 6) & 3u) != (unsigned)wave)
-                        {
-                            continue;      // another wave's class
-                        }
-                        unsigned const slot = cls >> 8;
-#pragma unroll
-                        for (int c = 0; c < NC; ++c)
-                        {
-                            if (NC == 1 || slot == (unsigned)c)
-                            {
-                                if (NC > 1)
-                                {
-                                    asm volatile("");      // (keeps the scalar branch a branch: not NC selects a point)
-                                }
-                                bool const mine = cls == (unsigned)(tid + c*kThreads);
-                                count[c] += mine ? 1 : 0;
-                                wsum[c] = __dadd_rn(wsum[c], mine ? w[q] : 0.);
-                                tsum[c] = __dadd_rn(tsum[c], mine ? t[q] : 0.);
-                            }
-                        }
-                    }
-                }
-            }
+            sum_chunk<NC>(c_s, w_s, t_s, padded, K, tid, wave, wave_has_classes, count, wsum, tsum);
         }
 #pragma unroll
         for (int c = 0; c < NC; ++c)
@@ -199,6 +222,124 @@ __global__ __launch_bounds__(kThreads) void kdist_kernel(GrtKdistArgs a)
                 if (a.points != nullptr) a.points[at] = count[c];
                 if (a.weight_sum != nullptr) a.weight_sum[at] = wsum[c];
                 if (a.tau_sum != nullptr) a.tau_sum[at] = tsum[c];
+            }
+        }
+    }
+}
+
+// The class map of grt_kdist_class_map: map[g][i] = class_of(key_i), the key row key_row of group g or (key_row < 0) the
+// sum of the group's rows in order from +0.0, every add rounded.  A workgroup takes kChunkPoints points of a group at a
+// time, thread t the points t, t + 256, ...: consecutive lanes read consecutive doubles of every row and store
+// consecutive shorts.
+__global__ __launch_bounds__(kThreads) void kdist_map_kernel(GrtKdistMapArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    double *e_s = reinterpret_cast<double *>(lds);                          // [K - 1]
+    int const tid = threadIdx.x, ne = a.num_classes - 1;
+    for (int k = tid; k < ne; k += kThreads)
+    {
+        e_s[k] = a.class_edges[k];
+    }
+    __syncthreads();
+    long long const tiles = (a.n + kChunkPoints - 1)/kChunkPoints, items = a.groups*tiles;
+    for (long long item = blockIdx.x; item < items; item += gridDim.x)
+    {
+        long long const g = item/tiles, start = (item - g*tiles)*kChunkPoints;
+        double const *x = a.x + g*a.rows_per_group*a.n;
+        long long const end = min(a.n, start + kChunkPoints);
+        for (long long i = start + tid; i < end; i += kThreads)
+        {
+            double key;
+            if (a.key_row >= 0)
+            {
+                key = x[a.key_row*a.n + i];
+            }
+            else
+            {
+                key = 0.;
+                for (long long r = 0; r < a.rows_per_group; ++r)
+                {
+                    key = __dadd_rn(key, x[r*a.n + i]);
+                }
+            }
+            a.map[g*a.n + i] = (unsigned short)class_of(e_s, ne, key);
+        }
+    }
+}
+
+// grt_kdist_mapped_rows: kdist_kernel's walk, one workgroup per (group, row, bin), with the class of a point read from the
+// group's map in place of the bisection -- an entry that names no class (>= K) becomes the pad, which no thread owns.  The
+// counts and the weight sums are the same for every row of a group: the workgroup of row 0 stores them.
+// LDS: 18 bytes a point, 18 432 bytes.
+template <int NC>
+__global__ __launch_bounds__(kThreads) void kdist_mapped_kernel(GrtKdistMappedArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    double *w_s = reinterpret_cast<double *>(lds);                          // [kChunkPoints]
+    double *t_s = w_s + kChunkPoints;                                       // [kChunkPoints]
+    unsigned short *c_s = reinterpret_cast<unsigned short *>(t_s + kChunkPoints);   // [kChunkPoints]
+
+    int const tid = threadIdx.x, K = a.num_classes;
+    int const wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    bool const wave_has_classes = wave*64 < K;
+    double const half_dw = 0.5*a.dw;
+
+    long long const per_group = a.rows_per_group*(long long)a.num_bins, items = a.groups*per_group;
+    for (long long item = blockIdx.x; item < items; item += gridDim.x)
+    {
+        long long const g = item/per_group, row = (item - g*per_group)/a.num_bins;
+        int const bin = (int)(item - g*per_group - row*a.num_bins);
+        int const first = a.edges[bin], last = a.edges[bin + 1];
+        double const *v = a.values + g*a.group_stride + row*a.n;
+        unsigned short const *map = a.map + g*a.n;
+        int count[NC];
+        double wsum[NC], tsum[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+        {
+            count[c] = 0;
+            wsum[c] = 0.;
+            tsum[c] = 0.;
+        }
+        for (long long start = first; start <= last; start += kChunkPoints)
+        {
+            int const m = (int)min((long long)kChunkPoints, last - start + 1);
+            int const padded = (m + kStep - 1) & ~(kStep - 1);
+            __syncthreads();               // the chunk before has been summed
+            for (int j = tid; j < m; j += kThreads)
+            {
+                long long const i = start + j;
+                double const x = v[i];
+                unsigned const cls = map[i];
+                double w = (i == first || i == last) ? half_dw : a.dw;
+                if (a.weight != nullptr)
+                {
+                    w = __dmul_rn(w, a.weight[i]);
+                }
+                w_s[j] = w;
+                t_s[j] = __dmul_rn(w, x);
+                c_s[j] = (unsigned short)(cls < (unsigned)K ? cls : kNoClass);
+            }
+            for (int j = m + tid; j < padded; j += kThreads)
+            {
+                w_s[j] = 0.;
+                t_s[j] = 0.;
+                c_s[j] = (unsigned short)kNoClass;
+            }
+            __syncthreads();
+            sum_chunk<NC>(c_s, w_s, t_s, padded, K, tid, wave, wave_has_classes, count, wsum, tsum);
+        }
+        bool const shared_out = row == 0;
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+        {
+            int const cls = tid + c*kThreads;
+            if (cls < K)
+            {
+                long long const at = (g*a.num_bins + bin)*K + cls;
+                if (shared_out && a.points != nullptr) a.points[at] = count[c];
+                if (shared_out && a.weight_sum != nullptr) a.weight_sum[at] = wsum[c];
+                if (a.tau_sum != nullptr) a.tau_sum[item*K + cls] = tsum[c];
             }
         }
     }
@@ -235,6 +376,54 @@ extern "C" int grt_launch_kdist(void *stream, GrtKdistArgs const *a)
     else
     {
         hipLaunchKernelGGL(kdist_kernel<4>, dim3(blocks), dim3(kThreads), lds, s, *a);
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_kdist_map(void *stream, GrtKdistMapArgs const *a)
+{
+    if (a == nullptr || a->x == nullptr || a->map == nullptr || a->groups < 1 || a->rows_per_group < 1 || a->n < 1 ||
+        a->key_row >= a->rows_per_group || a->num_classes < 2 || a->num_classes > kMaxClasses ||
+        a->class_edges == nullptr)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    long long const items = a->groups*((a->n + kChunkPoints - 1)/kChunkPoints);
+    unsigned const blocks = (unsigned)(items < (1ll << 20) ? items : (1ll << 20));
+    size_t const lds = sizeof(double)*(size_t)(a->num_classes - 1);
+    hipLaunchKernelGGL(kdist_map_kernel, dim3(blocks), dim3(kThreads), lds, (hipStream_t)stream, *a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_kdist_mapped(void *stream, GrtKdistMappedArgs const *args)
+{
+    if (args == nullptr || args->values == nullptr || args->map == nullptr || args->groups < 1 ||
+        args->rows_per_group < 1 || args->n < 2 || args->group_stride < args->rows_per_group*args->n ||
+        args->num_bins < 1 || args->edges == nullptr || args->num_classes < 2 || args->num_classes > kMaxClasses ||
+        (args->points == nullptr && args->weight_sum == nullptr && args->tau_sum == nullptr))
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    GrtKdistMappedArgs a = *args;
+    if (a.tau_sum == nullptr)
+    {
+        a.rows_per_group = 1;      // the counts and the weight sums are row 0's workgroups' alone
+    }
+    long long const items = a.groups*a.rows_per_group*(long long)a.num_bins;
+    unsigned const blocks = (unsigned)(items < (1ll << 20) ? items : (1ll << 20));
+    size_t const lds = (size_t)kChunkPoints*(2*sizeof(double) + sizeof(unsigned short));
+    hipStream_t const s = (hipStream_t)stream;
+    if (a.num_classes <= kThreads)
+    {
+        hipLaunchKernelGGL(kdist_mapped_kernel<1>, dim3(blocks), dim3(kThreads), lds, s, a);
+    }
+    else if (a.num_classes <= 2*kThreads)
+    {
+        hipLaunchKernelGGL(kdist_mapped_kernel<2>, dim3(blocks), dim3(kThreads), lds, s, a);
+    }
+    else
+    {
+        hipLaunchKernelGGL(kdist_mapped_kernel<4>, dim3(blocks), dim3(kThreads), lds, s, a);
     }
     return (int)hipGetLastError();
 }

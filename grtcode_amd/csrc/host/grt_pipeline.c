@@ -44,7 +44,8 @@
  * every level's flux integrated per wavenumber bin instead of over the whole grid, and one finishing launch for the bins'
  * heating rates.
  * grt_pipeline_run_kdist runs the prologue and the gas optics of the bands that have bins and no solver at all: tau_gas is
- * reduced to its k-distribution per layer and bin (grt_kdist.c, k_kdist.hip).
+ * reduced to its k-distribution per layer and bin (grt_kdist.c, k_kdist.hip); grt_pipeline_run_kdist_correlated reduces
+ * every layer under one class map per column, that of a key layer or of the column's vertical optical depth.
  * grt_pipeline_set_surface gives the columns of the runs that follow their own surface emissivity and albedo
  * (driver.c:101-117): rows written on the device from each column's few knots, read by the solvers in place of the shared
  * creation-time arrays.
@@ -1335,9 +1336,10 @@ static int check_bins(GrtPipeline_t const *p, int bi, int const *edges, int num_
     return GRTCODE_SUCCESS;
 }
 
-/* grt_ext.h: the k-distributions of the bands' tau_gas.  The entry point alone: the checks of the classes and of a band's
-   inputs, the tables and the launch are grt_kdist.c's. */
-EXTERN int grt_pipeline_run_kdist(GrtPipeline_t *p, GrtColumns_t const *cols, GrtKdist_t const *kd)
+/* grt_ext.h: the k-distributions of the bands' tau_gas -- each layer's own (keys NULL) or, correlated, every layer's under
+   the map of its band's key.  The entry points alone: the checks of the classes, of a band's inputs and of a key, the
+   tables and the launches are grt_kdist.c's. */
+static int run_kdist(GrtPipeline_t *p, GrtColumns_t const *cols, GrtKdist_t const *kd, GrtKdistKey_t const *const *keys)
 {
     GRT_REQUIRE_PTR(p);
     GRT_REQUIRE_PTR(cols);
@@ -1347,6 +1349,8 @@ EXTERN int grt_pipeline_run_kdist(GrtPipeline_t *p, GrtColumns_t const *cols, Gr
     }
     GRT_TRY(grt_kdist_check_classes(kd->num_classes, kd->class_edges));
     GrtKdistBand_t const *kb[2] = {&kd->lw, &kd->sw};
+    long long const L = p->num_levels - 1;
+    long long key_row[2] = {0, 0};
     for (int bi = 0; bi < 2; ++bi)
     {
         /* (a band's output: any of its three) */
@@ -1356,6 +1360,11 @@ EXTERN int grt_pipeline_run_kdist(GrtPipeline_t *p, GrtColumns_t const *cols, Gr
         if (kb[bi]->num_bins > 0)
         {
             GRT_TRY(grt_kdist_check_band(bi == 0 ? "longwave" : "shortwave", kb[bi], (long long)p->band[bi].n));
+            if (keys != NULL)
+            {
+                GRT_TRY(grt_kdist_check_key(bi == 0 ? "longwave" : "shortwave", keys[bi]->kind, keys[bi]->layer, L,
+                                            &key_row[bi]));
+            }
         }
     }
     if (kd->lw.num_bins + kd->sw.num_bins == 0)
@@ -1373,14 +1382,46 @@ EXTERN int grt_pipeline_run_kdist(GrtPipeline_t *p, GrtColumns_t const *cols, Gr
         {
             continue;                  /* (a band without bins is not computed: its line list is not touched) */
         }
+        unsigned short *map = keys != NULL ? keys[bi]->map_dev : NULL;
+        if (keys != NULL && map == NULL)
+        {
+            GrtScratch *own = &b->scratch[GRT_SCRATCH_KDIST_MAP];
+            GRT_TRY(grt_scratch_need(p, own, ((size_t)p->max_cols*b->n + 3)/4, NULL));
+            map = (unsigned short *)own->d;
+        }
         /* the whole of tau, the spectral tables' part included (band_gas_optics leaves that to a solver) */
         GRT_TRY(grt_optical_depth_batch(b->gas, cols, b->tau_gas));
         b->tau_gas_lacks_tables = 0;
         b->last_cols = cols->ncol;
-        GRT_TRY(grt_kdist_reduce(p->device, &b->kdist_table, b->tau_gas, (long long)cols->ncol*(p->num_levels - 1),
-                                 (long long)b->n, b->gas->grid.dw, kd->num_classes, kd->class_edges, kb[bi]));
+        if (keys == NULL)
+        {
+            GRT_TRY(grt_kdist_reduce(p->device, &b->kdist_table, b->tau_gas, cols->ncol*L, (long long)b->n,
+                                     b->gas->grid.dw, kd->num_classes, kd->class_edges, kb[bi]));
+        }
+        else
+        {
+            GRT_TRY(grt_kdist_reduce_correlated(p->device, &b->kdist_table, b->tau_gas, cols->ncol, L, (long long)b->n,
+                                                b->gas->grid.dw, kd->num_classes, kd->class_edges, key_row[bi], map,
+                                                kb[bi]));
+        }
     }
     return GRTCODE_SUCCESS;
+}
+
+EXTERN int grt_pipeline_run_kdist(GrtPipeline_t *p, GrtColumns_t const *cols, GrtKdist_t const *kd)
+{
+    return run_kdist(p, cols, kd, NULL);
+}
+
+EXTERN int grt_pipeline_run_kdist_correlated(GrtPipeline_t *p, GrtColumns_t const *cols, GrtKdist_t const *kd,
+                                             GrtKdistKeys_t const *keys)
+{
+    if (keys == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "no keys (GrtKdistKeys_t is NULL): grt_pipeline_run_kdist is the call without them.%s", "");
+    }
+    GrtKdistKey_t const *const by_band[2] = {&keys->lw, &keys->sw};
+    return run_kdist(p, cols, kd, by_band);
 }
 
 EXTERN int grt_pipeline_run_spectral(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl,

@@ -92,6 +92,9 @@ enum
        transmittance and contribution rows per (channel, solver block) pair, S as above, R the rows asked for (V
        transmittances, V + 1 contributions; 2 V + 1 for both); sized at the first call that needs more */
     GRT_SCRATCH_WEIGHTING_PARTIALS,
+    /* grt_pipeline_run_kdist_correlated without a map_dev of the caller's: the band's class map, [max_cols][n] unsigned
+       shorts (in doubles, rounded up) */
+    GRT_SCRATCH_KDIST_MAP,
     GRT_SCRATCH_COUNT
 };
 
@@ -301,6 +304,13 @@ GRT_PRIVATE int grt_kdist_check_band(char const *name, GrtKdistBand_t const *ban
 GRT_PRIVATE int grt_kdist_reduce(Device_t device, GrtKdistTable *t, fp_t const *tau_dev, long long rows, long long n,
                                  fp_t dw, int num_classes, fp_t const *class_edges, GrtKdistBand_t const *band);
 GRT_PRIVATE void grt_kdist_table_free(Device_t device, GrtKdistTable *t);
+/* ... the correlated form: a key's rules for groups of rows_per_group rows (*row: the key row, -1: the rows' sum); the map
+   of tau_dev [groups][rows_per_group][n] under that key queued to map_dev, and every row's reduction under it behind it */
+GRT_PRIVATE int grt_kdist_check_key(char const *name, int kind, long long key_row, long long rows_per_group, long long *row);
+GRT_PRIVATE int grt_kdist_reduce_correlated(Device_t device, GrtKdistTable *t, fp_t const *tau_dev, long long groups,
+                                            long long rows_per_group, long long n, fp_t dw, int num_classes,
+                                            fp_t const *class_edges, long long key_row, unsigned short *map_dev,
+                                            GrtKdistBand_t const *band);
 
 /* grt_pipeline_solve.c */
 GRT_PRIVATE int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps);

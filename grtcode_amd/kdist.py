@@ -42,3 +42,15 @@ def k_of_g(weight, tau, g_edges):
         at = np.interp(ge, g, integral)
         out[r] = np.diff(at) / np.diff(ge)
     return out.reshape(w.shape[:-1] + (ge.size - 1,))
+
+
+def correlated_k_of_g(weight, tau, g_edges):
+    """k_of_g for every row of a correlated reduction (Pipeline.run_kdist_correlated, api.kdist_mapped_rows): weight
+    [..., bins, K] is shared by the R rows of tau [..., R, bins, K] -- every row was summed over the same classes of points
+    -- and is broadcast over the row axis: [..., R, bins, G].  The g-intervals are then the same sets of spectral points in
+    every row, which is what makes the rows' k(g) correlated."""
+    w = np.asarray(weight, dtype=np.float64)
+    t = np.asarray(tau, dtype=np.float64)
+    if t.ndim != w.ndim + 1 or t.ndim < 3 or t.shape[:-3] != w.shape[:-2] or t.shape[-2:] != w.shape[-2:]:
+        raise ValueError(f"weight {w.shape} is not tau {t.shape} without its row axis")
+    return k_of_g(np.broadcast_to(w[..., None, :, :], t.shape), t, g_edges)

@@ -802,6 +802,65 @@ EXTERN int grt_kdist_rows(Device_t device, fp_t const *tau_dev, long long rows, 
 EXTERN int grt_pipeline_run_kdist(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtKdist_t const *kdist);
 EXTERN int grt_kdist_chunk_points(void);
 
+/* ---- correlated k-distributions: every row of a group under one class map --------------------------------------------------
+ * A correlated-k band model fixes one ordering of the spectral points per column and bin -- that of a reference layer, or
+ * of the column's vertical optical depth -- and averages every layer's optical depth, the source weights and the fluxes
+ * each g-point must carry over the same sets of points.  Here the ordering is the class of a key, kept on the device as a
+ * map of 16-bit classes, and any rows are reduced under it.  The values are x[g][r][i]: group g of G (a column), row r of R
+ * (a layer, the top one first, as in tau_gas [ncol][L][n]), grid point i of n.
+ *   key   GRT_KDIST_KEY_ROW: key_i = x[g][key_row][i];  GRT_KDIST_KEY_SUM: key_i = (((+0.0 + x[g][0][i]) + x[g][1][i]) + ...)
+ *         + x[g][R - 1][i], every add rounded, the rows in order, nothing contracted (a column's vertical optical depth);
+ *   map   map[g][i] = class(key_i), an unsigned short, by grt_kdist_rows' rule and no other: the number of class edges
+ *         e_k <= key_i; a NaN and anything below e[0] give 0, +inf gives K - 1.  It does not depend on bins.
+ * The mapped reduction, with grt_kdist_rows' bins, w_i, W_i = fl(w_i s_i) and weight s: per group, bin b and class k,
+ * points is the number of the bin's points with map[g][i] == k, weight the sum of their W_i and, per row r, tau the sum of
+ * fl(W_i v[g][r][i]) over them -- each sum left to right in increasing grid index from +0.0, every product rounded before
+ * it is added, no atomics, no tree: bit for bit a sequential sum on the host.  points and weight are the same for every
+ * row and have no row axis.  A map entry >= K belongs to no class and is counted nowhere: the reduction never indexes by
+ * it, so a bad map cannot write out of bounds.
+ *
+ * grt_kdist_class_map: map_dev [groups][n] from x_dev [groups][rows_per_group][n].  Asynchronous on the current lane.
+ * grt_kdist_mapped_rows: row r of group g starts at values_dev + g group_stride + r n (group_stride in doubles, >=
+ *   rows_per_group n); band's points_dev and weight_dev are [groups][num_bins][K], its tau_dev
+ *   [groups][rows_per_group][num_bins][K].  The stride applies the call to grt_pipeline_run_spectral's spectral_dev
+ *   [ncol][sets][6 n_lw + 6 n_sw]: the longwave rows with base spectral_dev, stride sets (6 n_lw + 6 n_sw) and 6 rows per
+ *   group, the shortwave rows with base + 6 n_lw.  With weight NULL the class sums of a flux row are W m-2 per class: the
+ *   line-by-line flux of each g-class.
+ * grt_pipeline_run_kdist_correlated: grt_pipeline_run_kdist -- the staging, the whole gas optics of each band that has bins,
+ *   no solver, grt_pipeline_views afterwards showing the array that was reduced, asynchronous on the pipeline's lane --
+ *   with, per band, the map built from tau_gas with that band's key (kind; layer in 0 .. L - 1 with GRT_KDIST_KEY_ROW,
+ *   ignored with GRT_KDIST_KEY_SUM) and every layer reduced under it: points_dev and weight_dev [ncol][num_bins][K],
+ *   tau_dev [ncol][L][num_bins][K].  The class edges classify the key only.  With map_dev NULL the map lives in pipeline
+ *   scratch (max_columns n shorts per band, allocated at the first call that needs it, freed with the pipeline); with
+ *   map_dev given the caller keeps it for later grt_kdist_mapped_rows calls.
+ * Two kernels (GRT_TAG_KDIST_MAP, GRT_TAG_KDIST_MAPPED), the latter one workgroup per (group, row, bin).
+ * GRTCODE_VALUE_ERR, with nothing launched and the outputs untouched, for: everything grt_kdist_rows and
+ * grt_pipeline_run_kdist refuse in classes, edges, bins, weights, dw, counts and lane; a NULL x_dev, values_dev, map_dev
+ * (of the two rows calls) or keys; groups < 1, rows_per_group < 1 or n < 2; a key kind other than the two; key_row outside
+ * 0 .. rows_per_group - 1 (layer outside 0 .. L - 1 for a band that has bins) with GRT_KDIST_KEY_ROW; group_stride <
+ * rows_per_group n. */
+enum { GRT_KDIST_KEY_ROW = 0, GRT_KDIST_KEY_SUM = 1 };
+
+EXTERN int grt_kdist_class_map(Device_t device, fp_t const *x_dev, long long groups, long long rows_per_group,
+                               long long n, int key_kind, long long key_row, int num_classes,
+                               fp_t const *class_edges, unsigned short *map_dev);
+EXTERN int grt_kdist_mapped_rows(Device_t device, fp_t const *values_dev, long long group_stride,
+                                 unsigned short const *map_dev, long long groups, long long rows_per_group,
+                                 long long n, fp_t dw, int num_classes, GrtKdistBand_t const *band);
+
+typedef struct GrtKdistKey
+{
+    int kind;                /* GRT_KDIST_KEY_ROW or GRT_KDIST_KEY_SUM */
+    int layer;               /* the key layer, 0 .. L - 1 (GRT_KDIST_KEY_ROW) */
+    unsigned short *map_dev; /* DEVICE [ncol][n], or NULL: the map stays in pipeline scratch */
+} GrtKdistKey_t;
+typedef struct GrtKdistKeys
+{
+    GrtKdistKey_t lw, sw;
+} GrtKdistKeys_t;
+EXTERN int grt_pipeline_run_kdist_correlated(GrtPipeline_t *pipeline, GrtColumns_t const *columns,
+                                             GrtKdist_t const *kdist, GrtKdistKeys_t const *keys);
+
 /* ---- per-column surface emissivity and albedo ----------------------------------------------------------------------
  * driver.c:101-117: each column's own surface emissivity and albedo, given on coarse wavenumber grids of NS points shared
  * by the columns and put on the band's grid as interpolate_to_grid(grid, x, y, NS, out, linear_sample,
@@ -1021,7 +1080,11 @@ enum
     GRT_TAG_WEIGHTING_FINISH = 28,
     /* 29 = the k-distribution kernel of grt_kdist_rows and grt_pipeline_run_kdist (the latter's gas optics counts under
        1 / 2 and 6 / 7) */
-    GRT_TAG_KDIST = 29
+    GRT_TAG_KDIST = 29,
+    /* 30 = the class-map kernel of grt_kdist_class_map and grt_pipeline_run_kdist_correlated; 31 = the mapped reduction of
+       grt_kdist_mapped_rows and grt_pipeline_run_kdist_correlated (the latter's gas optics counts under 1 / 2 and 6 / 7) */
+    GRT_TAG_KDIST_MAP = 30,
+    GRT_TAG_KDIST_MAPPED = 31
 };
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
