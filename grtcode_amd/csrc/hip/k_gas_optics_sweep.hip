@@ -287,7 +287,9 @@ __global__ __launch_bounds__(kSweepBlock) __attribute__((amdgpu_waves_per_eu(4, 
         uint64_t const nbin_local = 1, nbin_remote = 25;
         uint64_t nbin = nbin_local;
         double const leftw = j > nbin ? bins.w[kNip*(j - nbin)] : bins.w[0];
-        double const rightw = j >= (bins.n - 1) - nbin ? bins.w[kNip*bins.n - 1] : bins.w[kNip*(j + nbin + 1) - 1];
+        // (j + nbin on the left, not bins.n - 1 - nbin on the right: bins.n is unsigned, and a grid of nbin bins or fewer
+        // would wrap it and index bins.w past its end; for bins.n - 1 >= nbin the same operand is picked, bit for bit)
+        double const rightw = j + nbin >= bins.n - 1 ? bins.w[kNip*bins.n - 1] : bins.w[kNip*(j + nbin + 1) - 1];
         uint64_t left = 0, right = 0, tmp, has_local = 0;
         if (leftw <= v[num_lines - 1] && rightw >= v[0])
         {
@@ -315,7 +317,9 @@ __global__ __launch_bounds__(kSweepBlock) __attribute__((amdgpu_waves_per_eu(4, 
                 left_r = lr;
             }
         }
-        double const rightw_r = j >= (bins.n - 1) - nbin ? bins.w[kNip*bins.n - 1] : bins.w[kNip*(j + nbin + 1) - 1];
+        // (j + nbin on the left, not bins.n - 1 - nbin on the right: bins.n is unsigned, and a grid of nbin bins or fewer
+        // would wrap it and index bins.w past its end; for bins.n - 1 >= nbin the same operand is picked, bit for bit)
+        double const rightw_r = j + nbin >= bins.n - 1 ? bins.w[kNip*bins.n - 1] : bins.w[kNip*(j + nbin + 1) - 1];
         uint64_t first_r = 1, right_r = 0;      // empty remote-right range unless found below
         if (rightw <= v[num_lines - 1] && rightw_r >= v[0])
         {

@@ -437,7 +437,10 @@ void orc_bin_sweep(uint64_t num_lines, int num_layers, double const *vnn, double
             uint64_t const nbin_local = 1, nbin_remote = 25;
             uint64_t nbin = nbin_local;
             double const leftw = j > nbin ? bins->w[ORC_NIP*(j - nbin)] : bins->w[0];
-            double const rightw = j >= (bins->n - 1) - nbin ? bins->w[ORC_NIP*bins->n - 1]
+            /* (j + nbin on the left, not bins->n - 1 - nbin on the right: bins->n is unsigned, and a grid of nbin
+               bins or fewer would wrap it and index bins->w past its end; for bins->n - 1 >= nbin the same operand
+               is picked, bit for bit) */
+            double const rightw = j + nbin >= bins->n - 1 ? bins->w[ORC_NIP*bins->n - 1]
                                   : bins->w[ORC_NIP*(j + nbin + 1) - 1];
             uint64_t left = 0, right = 0, tmp;
             if (leftw <= v[num_lines - 1] && rightw >= v[0])
@@ -486,7 +489,10 @@ void orc_bin_sweep(uint64_t num_lines, int num_layers, double const *vnn, double
                     }
                 }
             }
-            double const rightw_r = j >= (bins->n - 1) - nbin ? bins->w[ORC_NIP*bins->n - 1]
+            /* (j + nbin on the left, not bins->n - 1 - nbin on the right: bins->n is unsigned, and a grid of nbin
+               bins or fewer would wrap it and index bins->w past its end; for bins->n - 1 >= nbin the same operand
+               is picked, bit for bit) */
+            double const rightw_r = j + nbin >= bins->n - 1 ? bins->w[ORC_NIP*bins->n - 1]
                                     : bins->w[ORC_NIP*(j + nbin + 1) - 1];
             if (rightw <= v[num_lines - 1] && rightw_r >= v[0])
             {

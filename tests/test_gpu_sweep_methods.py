@@ -18,10 +18,13 @@ pytestmark = pytest.mark.gpu
 WAVENUMBER_SWEEP, LINE_SWEEP = 0, 1
 
 
-def run(band, device, col, method, from_file=False):
+def run(band, device, col, method, from_file=False, inspect=None):
+    """inspect: called with the gas-optics object before it computes (to read its public fields)."""
     V = col["p"].size
     go, grid = band.gas_optics(device, V, from_file=from_file, method=method)
     assert go.c.optical_depth_method == (WAVENUMBER_SWEEP if method is None else method)
+    if inspect is not None:
+        inspect(go)
     band.set_column(go, col)
     opt = api.OpticsObject(V - 1, grid, device)
     go.calculate_optical_depth(col["p"], col["t"], opt)

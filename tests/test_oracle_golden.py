@@ -14,6 +14,7 @@ import os
 import numpy as np
 import pytest
 
+import sweep_cases
 from grtcode_amd import synthetic as syn
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -154,6 +155,9 @@ def test_optics_and_solvers_bit_exact_vs_fixture(oracle, fx):
 LIVE_FIXTURE = os.path.join(HERE, "golden", "live_reference.npz")
 COLUMN_CASES = [(11, 1.0), (12, 0.1), (13, 0.01)]
 SWEEP_CASES = [(21, 1.0, 140.0), (22, 0.1, 60.0), (23, 0.25, 80.0), (24, 0.02, 40.0)]
+# bin shapes of tests/sweep_cases.py, (ppb, last_ppb): a last bin of 2, 3 and 4 points under ppb 5, exact multiples, ppb 4
+# (bins of 1.2 cm-1), a four-point last bin under ppb 11 and one-point bins -- 41 or 40 bins each, 4-level columns
+SHAPE_GOLDEN = sweep_cases.SHAPE_GOLDEN
 BRACKET_ARRAY = np.array([1.0, 2.0, 2.0, 3.5, 7.0, 7.0, 7.0, 9.25])
 BRACKET_VALUES = (0.5, 1.0, 1.5, 2.0, 3.0, 3.5, 7.0, 8.0, 9.25, 10.0)
 
@@ -205,6 +209,10 @@ def reference_outputs(ref, orc, lib, root):
         band, col = sweep_case(os.path.join(root, f"sweep_{seed}"), seed, dw, span)
         for method in (0, 1):
             out[f"sweep_{seed}_{method}"] = band.oracle_tau(ref, orc, lib, col, method=method)
+    for ppb, last in SHAPE_GOLDEN:
+        for method in (0, 1):
+            band, col = sweep_cases.shape_case(os.path.join(root, f"shape_{ppb}_{last}_{method}"), ppb, last, method)
+            out[f"shape_{ppb}_{last}_{method}"] = band.oracle_tau(ref, orc, lib, col, method=method)
     # per value: [found (code 0), left, right]
     out["bracket"] = np.array([(rc == 0, l, r) for rc, l, r in (ref.bracket(BRACKET_ARRAY, v) for v in BRACKET_VALUES)],
                               dtype=np.int64)
@@ -264,6 +272,18 @@ def test_sweep_methods_bit_exact_vs_live_reference(oracle, live, lib, seed, dw, 
     # the sweeps approximate the far wings by a quadratic per 1 cm-1 bin: close to, not equal to, line_sample
     scale = np.abs(sample).max(axis=1, keepdims=True)
     assert 0.0 < np.max(np.abs(a - sample) / scale) < 0.05
+
+
+@pytest.mark.parametrize("method", [0, 1])
+@pytest.mark.parametrize("ppb,last", SHAPE_GOLDEN)
+def test_sweep_bin_shapes_bit_exact_vs_live_reference(oracle, live, lib, ppb, last, method, tmp_path):
+    """The sweeps where do_interp and do_last_interp differ, where the last bin's quadratic runs through four points, on
+    exact multiples of ppb and with bins that are not 1 cm-1 wide (ppb 4: line_sweep's bin_width is 1.2 cm-1)."""
+    band, col = sweep_cases.shape_case(str(tmp_path), ppb, last, method)
+    assert sweep_cases.shape_of(band.dw, band.nw)[:2] == (ppb, last)
+    a = band.oracle_tau(oracle, oracle, lib, col, method=method)
+    assert a.max() > 0.0
+    assert np.array_equal(a, live[f"shape_{ppb}_{last}_{method}"])
 
 
 def test_bracket_vs_live_reference(oracle, live):
