@@ -16,6 +16,51 @@ from scenario import MOLTAB, Band
 
 SPACING = 60.0                              # cm-1 between rungs; rung k is centred 30 cm-1 above the start of its 60
 FLOOR = 2.0 ** -53
+# The far wing, point by point.  A point at x = |w - centre| sqrt(ln 2)/alpha >= X_WING Doppler widths of EVERY line lies
+# beyond every line's XLIM0 (at most 123.4, RFM_voigt.c:109), where the oracle is a plain Lorentzian: no region 1, no
+# near-centre arithmetic, nothing a kernel adds and takes back.  There each point is judged against ITSELF,
+#     |got - want| <= E want + 2^-53,
+# where the peak norms above and tau_close divide by something orders of magnitude larger.
+X_WING = 130.0
+SQRT_LN2 = float(np.sqrt(np.log(2.0)))
+
+
+def judge_wings(got, want, E, wing, zero, what):
+    """`got` against `want` on the points `wing` ([L][n], want != 0 there), each within E (a number or [L][n]) of its own
+    value plus the floor; on the points `zero` (want == 0 there) got is zero.  Returns (per layer: dict of the worst
+    error in units of its bound, the worst plain relative error and the number of points; failures as text, one line
+    per layer with its worst point)."""
+    E = np.broadcast_to(np.asarray(E, dtype=np.float64), want.shape)
+    layers, bad = [], []
+    for j in range(want.shape[0]):
+        i = np.flatnonzero(wing[j])
+        entry = dict(points=int(i.size), of_bound=0.0, rel=0.0)
+        if not np.all(np.isfinite(got[j])):
+            bad.append(f"{what}: layer {j}: not finite")
+            entry["of_bound"] = entry["rel"] = float("inf")
+        elif i.size:
+            err = np.abs(got[j, i] - want[j, i])
+            size = np.abs(want[j, i])
+            ratio = err / (E[j, i] * size + FLOOR)
+            k = int(np.argmax(ratio))
+            entry.update(of_bound=float(ratio[k]), rel=float(np.max(err / size)), at=int(i[k]))
+            if ratio[k] > 1.0:
+                bad.append(f"{what}: layer {j}: {int(np.sum(ratio > 1.0))} of {i.size} wing points out of bounds, worst at "
+                           f"point {i[k]}: got {got[j, i[k]]:.9e}, want {want[j, i[k]]:.9e}, off by {err[k] / size[k]:.3e} "
+                           f"of it (bound {E[j, i[k]]:.3e}, {ratio[k]:.2f} of bound and floor)")
+        nz = np.flatnonzero(zero[j] & (got[j] != 0.0))
+        if nz.size:
+            bad.append(f"{what}: layer {j}: {nz.size} points not zero where the oracle is, first at point {nz[0]}: "
+                       f"{got[j, nz[0]]:.3e}")
+        layers.append(entry)
+    worst = max(e["of_bound"] for e in layers)
+    print(f"{what}: worst wing point {worst:.3f} of its bound, {max(e['rel'] for e in layers):.2e} of its own value")
+    return layers, bad
+
+
+def judged_share(want, wing, E):
+    """The share of the wing points that E can judge at all: E want at or above the floor."""
+    return float(np.mean(E * np.abs(want[wing]) >= FLOOR)) if np.any(wing) else 0.0
 MOLS = [syn.H2O, syn.CO2, syn.O3]           # rung k belongs to MOLS[k % 3]: the slots interleave in the merged store
 F32_KEYS = ("yair", "yself", "en", "nexp", "delta")     # what the loaders keep as floats (parse_HITRAN_file.c:197-212)
 #: an ordinary line, as synthetic.line_list draws them; `off`: the centre's offset from the rung's grid point [grid steps]
@@ -51,8 +96,9 @@ def layer_means(oracle, col):
 
 
 def bare_band(root, kind, span):
-    """`span` cm-1 of a ladder's grid with lines of MOLS only: no continua, CFCs or collision pairs, no lines yet."""
-    w0, dw, sw = LADDERS[kind]
+    """`span` cm-1 of a ladder's grid (its name, or another grid's (first wavenumber, step, shortwave tables)) with lines of
+    MOLS only: no continua, CFCs or collision pairs, no lines yet."""
+    w0, dw, sw = LADDERS[kind] if isinstance(kind, str) else kind
     return Band(root, w0, w0 + span, dw, 0, mols=MOLS, sw=sw, with_ctm=False, with_cfc=False, with_cia=False)
 
 
@@ -120,6 +166,24 @@ class Ladder:
             sel = [k for k, r in enumerate(self.rungs) if r["mol"] == m["id"]]
             vnn[:, sel], gamma[:, sel], alpha[:, sel] = v, g, a
         return vnn, gamma, alpha
+
+    # -- the far wing, point by point ---------------------------------------------------------------------------------- #
+    def locate(self, oracle, lib, col):
+        """Every grid point's distance from its rung's shifted centre in Doppler widths, [L][n], from the oracle's line
+        preparation: every point sees one line only, its rung's.  Kept for wing_failures."""
+        vnn, _, alpha = self.prepared(oracle, lib, col)
+        owner = np.searchsorted(self.starts, np.arange(self.band.nw), side="right") - 1
+        w = self.w0 + self.dw * np.arange(self.band.nw)
+        self.x = np.abs(w[None, :] - vnn[:, owner]) * SQRT_LN2 / alpha[:, owner]
+        return self.x
+
+    def wing_failures(self, got, want, E, what):
+        """got against want on the rungs' points at X_WING Doppler widths and more from the rung's own shifted centre
+        (locate), each within E(x_min, covering) -- a function, or a number -- of its own value plus the floor; zero where
+        the oracle is zero there.  One line a point: covering = 1."""
+        far = self.x >= X_WING
+        bound = E(self.x, np.ones(self.x.shape)) if callable(E) else E
+        return judge_wings(got, want, bound, far & (want != 0.0), far & (want == 0.0), what + ", wing points")[1]
 
     # -- the per-rung metric ------------------------------------------------------------------------------------------- #
     def per_rung(self, a):

@@ -7,7 +7,10 @@ Every ladder runs every form against the oracle, rung by rung:
     reference order (fast = 0), wavenumber sweep, line sweep                  1e-11 of the rung's peak
     moment kernel (1), ring kernel (2), two-pass lean (3), two-pass general (3, GRT_LEAN=0)   FAST_TOL (2e-6)
     lean loop against general loop    LEAN_TOL;       moment kernel against ring kernel    BETWEEN_TOL
-each plus the floor 2^-53, and the layer-norm assertions of test_gpu_moment_kernel.py as well.  The columns run from 1e-6 mb
+each plus the floor 2^-53, and the layer-norm assertions of test_gpu_moment_kernel.py as well.  A rung's points at 130 Doppler
+widths and more from its shifted centre are also judged one by one against their OWN value (Ladder.wing_failures: 1e-9 for the
+first row, far_wing_cases.fused_bound with one covering line for the second), and every ladder states, from the oracle, the
+least share of those points that lie above the floor (min_judged: the thin top layers of an ordinary line do not).  The columns run from 1e-6 mb
 and 150 K at the top to 3 atm and 340 K at the bottom.  The ladders (line_ladder.LADDERS): 1 cm-1 from 70 cm-1 (the first
 rungs lie below 0.7 T: the series for 1 - e^x of the lean loop, kTfFarir), 0.05 cm-1 from 700 cm-1 (the cell hierarchy),
 1 cm-1 from 30 000 cm-1 (a grid step is tens of Doppler widths: the lean loop evaluates Humlicek region 2 itself), and
@@ -18,7 +21,9 @@ The witnesses -- that a ladder really has rungs on both sides of a branch -- com
 import numpy as np
 import pytest
 
-from line_ladder import LADDERS, SPACING, Ladder, bare_band, column, complete, layer_means, lines_of, mark, rung
+from far_wing_cases import E_STRICT, fused_bound
+from line_ladder import (LADDERS, SPACING, X_WING, Ladder, bare_band, column, complete, judged_share, layer_means, lines_of,
+                         mark, rung)
 from test_gpu_moment_kernel import BETWEEN_TOL, FAST_TOL, LEAN_TOL, check_layer_norm, fused_forms, run
 from test_gpu_sweep_methods import LINE_SWEEP, WAVENUMBER_SWEEP
 from test_gpu_sweep_methods import run as run_sweep
@@ -30,20 +35,40 @@ KINDS = list(LADDERS)
 LEAN_S_MIN, LEAN_S_MAX = 2.0 ** -196, 2.0 ** 4
 
 
-def check_ladder(lad, device, oracle, lib, col, from_file=False):
-    """Every form on the ladder, rung by rung; then the layer norm."""
+def wing_points(lad, oracle, lib, col, want, min_judged):
+    """The ladder's wing points from the oracle (Ladder.locate); at least `min_judged` of them are large enough for the
+    fused forms' E to judge them above the floor -- the witness that the pointwise judgement is not empty.  The shares the
+    oracle gives, the same to two digits on all four grids (the thin top layers put an ordinary line's wings below 2^-53
+    whatever the ladder; the bottom layers are judged to 0.55 - 1.00): strengths 0.21 (six of its twelve rungs are weaker
+    than anything can judge; 1e-30 to 1e-16 and the pair at the top of the lean range are judged), energies 0.32 - 0.33,
+    widths 0.45 (not the pure Doppler rungs: exact zeros there), centres 0.44, shifts 0.40 - 0.46, file 0.43."""
+    x = lad.locate(oracle, lib, col)
+    wing = (x >= X_WING) & (want != 0.0)
+    share = judged_share(want, wing, fused_bound(x, 1.0)[wing])
+    print(f"wing points: {int(wing.sum())}, {share:.3f} of them judged above the floor (at least {min_judged})")
+    assert share >= min_judged, (share, min_judged)
+
+
+def check_ladder(lad, device, oracle, lib, col, min_judged, from_file=False):
+    """Every form on the ladder, rung by rung and on the rungs' far wings point by point; then the layer norm."""
     band = lad.band
     want = band.oracle_tau(oracle, oracle, lib, col)
     assert np.all(np.isfinite(want))
-    bad = lad.rung_failures(run(band, device, col, 0, from_file=from_file), want, STRICT_TOL, "reference order")
+    wing_points(lad, oracle, lib, col, want, min_judged)
+    strict = run(band, device, col, 0, from_file=from_file)
+    bad = lad.rung_failures(strict, want, STRICT_TOL, "reference order")
+    bad += lad.wing_failures(strict, want, E_STRICT, "reference order")
     for method, name in ((WAVENUMBER_SWEEP, "wavenumber sweep"), (LINE_SWEEP, "line sweep")):
         want_sweep = band.oracle_tau(oracle, oracle, lib, col, method=method)
-        bad += lad.rung_failures(run_sweep(band, device, col, method, from_file=from_file), want_sweep, STRICT_TOL, name)
+        got = run_sweep(band, device, col, method, from_file=from_file)
+        bad += lad.rung_failures(got, want_sweep, STRICT_TOL, name)
+        bad += lad.wing_failures(got, want_sweep, E_STRICT, name)
     forms = fused_forms(band, device, col, from_file=from_file)
     mp, ring, lean, two = forms
     for got, name in ((mp, "moment kernel"), (ring, "ring kernel"), (lean, "two-pass, lean loop"),
                       (two, "two-pass, general loop")):
         bad += lad.rung_failures(got, want, FAST_TOL, name)
+        bad += lad.wing_failures(got, want, fused_bound, name)
     bad += lad.rung_failures(lean, two, LEAN_TOL, "lean loop against general loop", peak_of=want)
     bad += lad.rung_failures(mp, ring, BETWEEN_TOL, "moment kernel against ring kernel", peak_of=want)
     assert not bad, "\n".join(bad)
@@ -82,7 +107,7 @@ def test_strengths_from_1e_45_to_1e_16_and_across_the_lean_range(tmp_path, oracl
     assert any(x < LEAN_S_MIN and near(x, LEAN_S_MIN) for x in s) and any(x >= LEAN_S_MIN and near(x, LEAN_S_MIN) for x in s)
     assert any(x <= LEAN_S_MAX and near(x, LEAN_S_MAX) for x in s) and any(x > LEAN_S_MAX and near(x, LEAN_S_MAX) for x in s)
     assert s[7] == 0.0 and np.all((s[:7] > LEAN_S_MIN) & (s[:7] < LEAN_S_MAX))
-    check_ladder(lad, device, oracle, lib, col)
+    check_ladder(lad, device, oracle, lib, col, 0.18)
 
 
 @pytest.mark.parametrize("kind", KINDS)
@@ -95,7 +120,7 @@ def test_lower_state_energies_from_unknown_to_20000(tmp_path, oracle, lib, devic
              for s in (1e-19, 1e-27)] + [rung("ordinary")]
     lad = Ladder(str(tmp_path), kind, rungs)
     assert lad.K % 2 == 1                                   # (an odd store: the lean records end in a line of padding)
-    check_ladder(lad, device, oracle, lib, column(9))
+    check_ladder(lad, device, oracle, lib, column(9), 0.29)
 
 
 WIDTHS = [("self width 0", 0.07, 0.0), ("air width 0", 0.0, 0.3), ("pure Doppler", 0.0, 0.0), ("air width .0001", 0.0001, 0.35),
@@ -123,7 +148,7 @@ def test_widths_from_none_to_broad_on_and_off_grid_points(tmp_path, oracle, lib,
     if kind != "far_infrared":      # the thin top layers do it with ordinary widths
         ordinary = [k for k, r in enumerate(lad.rungs) if r["yair"] > 0.05 and 0.3 < r["yself"] < 0.4]
         assert len(ordinary) == 3 and np.any(y[:, ordinary] <= 1e-6) and np.any(y[:, ordinary] > 1e-6), y[:, ordinary]
-    check_ladder(lad, device, oracle, lib, col)
+    check_ladder(lad, device, oracle, lib, col, 0.40)
 
 
 @pytest.mark.parametrize("kind", KINDS)
@@ -156,7 +181,7 @@ def test_centres_on_inside_and_outside_the_guard_band(tmp_path, oracle, lib, dev
     for g, (delta, j) in enumerate(groups):
         d = from_mark[j, 5 * g:5 * g + 5]
         assert np.allclose(d, eps, rtol=0.0, atol=1e-8), (delta, j, d)      # on, inside (1e-5) and outside, either side
-    check_ladder(lad, device, oracle, lib, col)
+    check_ladder(lad, device, oracle, lib, col, 0.40)
 
 
 @pytest.mark.parametrize("kind", KINDS)
@@ -196,7 +221,7 @@ def test_shifts_of_a_tenth_per_atmosphere(tmp_path, oracle, lib, device, kind):
         lean_layers &= reach < 4.0
         assert np.any(lean_layers & np.any(c[:, 1:4] - c[0, 1:4] >= 2.0, axis=1)), (gamma / dw, reach, moved)
         assert np.any(lean_layers & np.any(c[:, 4:7] - c[0, 4:7] <= -1.0, axis=1)), (gamma / dw, reach, moved)
-    check_ladder(lad, device, oracle, lib, col)
+    check_ladder(lad, device, oracle, lib, col, 0.36)
 
 
 UNUSUAL = [dict(), dict(yself=0.0), dict(yair=0.0), dict(yair=0.0, yself=0.0), dict(s0=0.0), dict(s0=1e-20, en=20000.0),
@@ -246,4 +271,4 @@ def test_the_same_through_a_hitran_file(tmp_path, oracle, lib, device, kind):
         text = f.read()
     for field in (".0001", "0.000", "-1.0000", "-.100000", "1.000E-45"):
         assert field in text, field
-    check_ladder(lad, device, oracle, lib, column(8), from_file=True)
+    check_ladder(lad, device, oracle, lib, column(8), 0.38, from_file=True)
