@@ -254,7 +254,7 @@ create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
 grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_channels grt_channel_pair_count grt_pipeline_run_sky_weighting grt_pipeline_run_sky_zeniths grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_kdist_rows grt_pipeline_run_kdist grt_kdist_chunk_points grt_kdist_class_map grt_kdist_mapped_rows grt_pipeline_run_kdist_correlated grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
-grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_line_strengths grt_profile_enable grt_profile_read
+grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_voigt_points grt_debug_device_math grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
 grt_err_begin grt_err_frame grt_log grt_gmalloc grt_gfree grt_gmemset grt_gmemcpy
@@ -1513,6 +1513,33 @@ def debug_voigt(device, fast, w_start, npts, wres, center, gamma, alpha):
     lib.grt_debug_voigt.argtypes = [C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double, c_double_p]
     check(lib.grt_debug_voigt(device, int(fast), w_start, npts, wres, center, gamma, alpha, _dp(K)))
     return K
+
+
+def debug_voigt_points(device, variant, x, y):
+    """voigt_class / voigt_near at given fp32 (x, y) on the device (grt_debug_voigt_points): K [n] before the scaling of
+    RFM_voigt.c:278, cls [n] (int32; -1: no class involved)."""
+    lib = load_library()
+    x, y = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(y, dtype=np.float64)
+    assert x.shape == y.shape and x.ndim == 1
+    K, cls = np.zeros(x.size), np.zeros(x.size, dtype=np.int32)
+    lib.grt_debug_voigt_points.argtypes = [C.c_int, C.c_int, C.c_uint64, c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int)]
+    check(lib.grt_debug_voigt_points(device, int(variant), x.size, _dp(x), _dp(y), _dp(K), cls.ctypes.data_as(C.POINTER(C.c_int))))
+    return K, cls
+
+
+#: the ops of grt_debug_device_math
+DEVICE_MATH_OPS = {"exp_pair": 0, "exp": 1, "exp_fast": 2, "exp_fp64": 3, "repwid": 4}
+
+
+def debug_device_math(device, op, a):
+    """One device math function at the arguments a [n] (grt_debug_device_math): (out0, out1); out1 is e^-a for
+    "exp_pair" and None for the other ops."""
+    lib = load_library()
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    out0, out1 = np.zeros(a.size), np.zeros(a.size)
+    lib.grt_debug_device_math.argtypes = [C.c_int, C.c_int, C.c_uint64, c_double_p, c_double_p, c_double_p]
+    check(lib.grt_debug_device_math(device, DEVICE_MATH_OPS[op], a.size, _dp(a), _dp(out0), _dp(out1)))
+    return out0, (out1 if op == "exp_pair" else None)
 
 
 def use_lane(device, lane):

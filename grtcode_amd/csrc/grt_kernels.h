@@ -232,6 +232,17 @@ int grt_launch_line_prep(void *stream, GrtGasOpticsArgs const *a, int col,
 int grt_launch_voigt_debug(void *stream, int fast, double w_start, uint64_t n, double wres, double center,
                            double gamma, double alpha, double *K_dev);
 
+/* Debug/parity hook: the near-centre line shape at n given fp32 (x, y), by the variant of voigt_class / voigt_near the
+   line kernels instantiate (0-4: see voigt_points_kernel); K before the scaling of RFM_voigt.c:278, cls the class chosen
+   (-1: none).  Unknown variant or n == 0: hipErrorInvalidValue. */
+int grt_launch_voigt_points(void *stream, int variant, uint64_t n, double const *x_dev, double const *y_dev,
+                            double *K_dev, int *cls_dev);
+
+/* Debug/parity hook: one device math function at n arguments.  op 0: grt_exp_pair (out0 = e^a, out1 = e^-a), 1: grt_exp,
+   2: exp_fast, 3: exp_fp64, 4: reference_repwid (widened); out1 is written by op 0 alone.  Unknown op or n == 0:
+   hipErrorInvalidValue. */
+int grt_launch_device_math(void *stream, int op, uint64_t n, double const *a_dev, double *out0_dev, double *out1_dev);
+
 /* rayleigh.c:29-68: n_layer [L] on the HOST (it travels as a kernel argument). */
 int grt_launch_rayleigh(void *stream, int num_layers, double w0, double dw, uint64_t nw,
                         double const *n_layer_host, double *tau, double *omega, double *g);

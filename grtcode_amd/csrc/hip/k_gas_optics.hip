@@ -532,6 +532,126 @@ extern "C" int grt_launch_voigt_debug(void *stream, int fast, double w_start, ui
     return (int)hipGetLastError();
 }
 
+namespace {
+
+// Parity hook: the near-centre line shape at given fp32 (x, y), one thread per point, K as voigt_near returns it (before the
+// scaling of RFM_voigt.c:278) and the class voigt_class sorted the point into (-1: no class involved).  VARIANT:
+//   0  voigt_near<false>                                 1  voigt_near<true>
+//   2  voigt_class<true, false>, then ONLY = 0 / 1 / 2   3  voigt_class<true, true>, then ONLY = 4 / 1 / 2 / 3
+//   4  as 3, classes 1 and 2 with PACKED4: the dispatch of the lean, non-narrow two-pass instance (k_gas_optics_mp.hip:320-324)
+// Variants 0 and 1 also take the points voigt_near's callers keep from it, by the branches those callers use (REPWID = 1):
+// y >= 70.55 (RFM_voigt.c:97-106; K as :103 leaves it, it has no :278) and |x| >= XLIM0 (:170, likewise before :278:
+// the fused form's Lorentzian with cl = Y RSQRPI).
+template <int VARIANT>
+__global__ __launch_bounds__(kBlock) void voigt_points_kernel(uint64_t n, double const *x, double const *yv, double *K, int *cls)
+{
+    uint64_t const i = (uint64_t)blockIdx.x*kBlock + threadIdx.x;
+    if (i >= n)
+    {
+        return;
+    }
+    constexpr bool FAST = VARIANT != 0;
+    constexpr bool SPLIT = VARIANT >= 3;
+    constexpr bool PACKED4 = VARIANT == 4;
+    float const xi = (float)x[i], y = (float)yv[i];
+    double k;
+    int c = -1;
+    if constexpr (VARIANT <= 1)
+    {
+        float const yq = y*y;
+        float const abx = fabsf(xi);
+        float const xq = abx*abx;
+        float const r0 = 15100.0f + y*(40.0f - y*3.6f);
+        float const xlim0 = FAST ? __builtin_amdgcn_sqrtf(r0) : (float)sqrt((double)r0);      // (as voigt_limits takes its roots)
+        bool const lorentz = (y >= 70.55f);
+        bool const far = FAST ? xi*xi >= xlim0*xlim0 : abx >= xlim0;
+        if (lorentz | far)
+        {
+            k = FAST ? (double)voigt_lorentzian_fast(lorentz ? y*0.318309886f : y*kRsqrpi, xi, yq)
+                     : (lorentz ? voigt_lorentz_ref(y, xq, yq) : (double)voigt_far_ref(y*kRsqrpi, xq, yq));
+        }
+        else
+        {
+            k = voigt_near<FAST>(xi, y);
+        }
+    }
+    else
+    {
+        c = voigt_class<true, SPLIT>(xi, y);
+        if (c == 0) k = voigt_near<true, SPLIT ? 4 : 0, false>(xi, y);
+        else if (c == 1) k = voigt_near<true, 1, PACKED4>(xi, y);
+        else if (c == 2) k = voigt_near<true, 2, PACKED4>(xi, y);
+        else k = voigt_near<true, 3, false>(xi, y);
+    }
+    K[i] = k;
+    cls[i] = c;
+}
+
+// Parity hook: the device's exponentials and REPWID, one thread per argument.  op 0: grt_exp_pair (e^a, e^-a), 1: grt_exp,
+// 2: exp_fast, 3: exp_fp64, 4: reference_repwid widened to double; out1 is written by op 0 alone.
+template <int OP>
+__global__ __launch_bounds__(kBlock) void device_math_kernel(uint64_t n, double const *a, double *out0, double *out1)
+{
+    uint64_t const i = (uint64_t)blockIdx.x*kBlock + threadIdx.x;
+    if (i >= n)
+    {
+        return;
+    }
+    double const v = a[i];
+    if constexpr (OP == 0)
+    {
+        double p, m;
+        grt_exp_pair(v, &p, &m);
+        out0[i] = p;
+        out1[i] = m;
+    }
+    else if constexpr (OP == 1) out0[i] = grt_exp(v);
+    else if constexpr (OP == 2) out0[i] = exp_fast(v);
+    else if constexpr (OP == 3) out0[i] = exp_fp64(v);
+    else out0[i] = (double)reference_repwid(v);
+}
+
+} // namespace
+
+extern "C" int grt_launch_voigt_points(void *stream, int variant, uint64_t n, double const *x_dev, double const *y_dev,
+                                       double *K_dev, int *cls_dev)
+{
+    if (n == 0 || n > 0x7fffffffull || variant < 0 || variant > 4)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    dim3 const grid((unsigned)((n + kBlock - 1)/kBlock));
+    hipStream_t const s = (hipStream_t)stream;
+    switch (variant)
+    {
+        case 0: hipLaunchKernelGGL(voigt_points_kernel<0>, grid, dim3(kBlock), 0, s, n, x_dev, y_dev, K_dev, cls_dev); break;
+        case 1: hipLaunchKernelGGL(voigt_points_kernel<1>, grid, dim3(kBlock), 0, s, n, x_dev, y_dev, K_dev, cls_dev); break;
+        case 2: hipLaunchKernelGGL(voigt_points_kernel<2>, grid, dim3(kBlock), 0, s, n, x_dev, y_dev, K_dev, cls_dev); break;
+        case 3: hipLaunchKernelGGL(voigt_points_kernel<3>, grid, dim3(kBlock), 0, s, n, x_dev, y_dev, K_dev, cls_dev); break;
+        default: hipLaunchKernelGGL(voigt_points_kernel<4>, grid, dim3(kBlock), 0, s, n, x_dev, y_dev, K_dev, cls_dev); break;
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_device_math(void *stream, int op, uint64_t n, double const *a_dev, double *out0_dev, double *out1_dev)
+{
+    if (n == 0 || n > 0x7fffffffull || op < 0 || op > 4)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    dim3 const grid((unsigned)((n + kBlock - 1)/kBlock));
+    hipStream_t const s = (hipStream_t)stream;
+    switch (op)
+    {
+        case 0: hipLaunchKernelGGL(device_math_kernel<0>, grid, dim3(kBlock), 0, s, n, a_dev, out0_dev, out1_dev); break;
+        case 1: hipLaunchKernelGGL(device_math_kernel<1>, grid, dim3(kBlock), 0, s, n, a_dev, out0_dev, out1_dev); break;
+        case 2: hipLaunchKernelGGL(device_math_kernel<2>, grid, dim3(kBlock), 0, s, n, a_dev, out0_dev, out1_dev); break;
+        case 3: hipLaunchKernelGGL(device_math_kernel<3>, grid, dim3(kBlock), 0, s, n, a_dev, out0_dev, out1_dev); break;
+        default: hipLaunchKernelGGL(device_math_kernel<4>, grid, dim3(kBlock), 0, s, n, a_dev, out0_dev, out1_dev); break;
+    }
+    return (int)hipGetLastError();
+}
+
 extern "C" int grt_launch_line_prep(void *stream, GrtGasOpticsArgs const *a, int col,
                                     double *vnn, double *snn, double *gamma, double *alpha,
                                     int64_t *win_s, int64_t *win_e)

@@ -1036,3 +1036,61 @@ EXTERN int grt_debug_voigt(Device_t device, int fast, fp_t w, uint64_t num_wpoin
     GRT_TRY(rc);
     return GRTCODE_SUCCESS;
 }
+
+/* The two point hooks (which = 0: Voigt points, 1: device math) on one device block: three columns of n doubles -- the
+   nin inputs first, the outputs after them -- and n ints.  in[k] go up; the launch runs; nout outputs (and cls) come back. */
+static int debug_points_run(Device_t device, int which, int sel, uint64_t n, double const *const *in, int nin,
+                            double *const *out, int nout, int *cls)
+{
+    GRT_TRY(grt_dev_require(device));
+    void *s = grt_dev_stream(device);
+    double *d = NULL;
+    size_t const col = sizeof(double)*n;
+    GRT_TRY(grt_dev_alloc(device, (void **)&d, col*3 + sizeof(int)*n));     /* (either hook: three columns at the most) */
+    int *dcls = (int *)(d + 3*n);
+    int rc = GRTCODE_SUCCESS;
+    for (int k = 0; k < nin && rc == GRTCODE_SUCCESS; ++k)
+    {
+        rc = grt_dev_upload(device, d + (size_t)k*n, in[k], col, s);
+    }
+    if (rc == GRTCODE_SUCCESS)
+    {
+        rc = which == 0 ? grt_dev_check(grt_launch_voigt_points(s, sel, n, d, d + n, d + 2*n, dcls), "voigt points kernel")
+                        : grt_dev_check(grt_launch_device_math(s, sel, n, d, d + n, d + 2*n), "device math kernel");
+    }
+    for (int k = 0; k < nout && rc == GRTCODE_SUCCESS; ++k)
+    {
+        rc = grt_dev_download(device, out[k], d + (size_t)(nin + k)*n, col, s);
+    }
+    if (rc == GRTCODE_SUCCESS && cls != NULL) rc = grt_dev_download(device, cls, dcls, sizeof(int)*n, s);
+    if (rc == GRTCODE_SUCCESS) rc = grt_dev_sync(device, s);
+    grt_dev_free(device, d);
+    GRT_TRY(rc);
+    return GRTCODE_SUCCESS;
+}
+
+EXTERN int grt_debug_voigt_points(Device_t device, int variant, uint64_t n, fp_t const *x, fp_t const *y, fp_t *K, int *cls)
+{
+    GRT_REQUIRE_PTR(x);
+    GRT_REQUIRE_PTR(y);
+    GRT_REQUIRE_PTR(K);
+    GRT_REQUIRE_PTR(cls);
+    GRT_REQUIRE_RANGE(variant, 0, 4);
+    GRT_REQUIRE_RANGE(n, 1, 1u << 30);
+    double const *in[2] = {x, y};
+    double *out[1] = {K};
+    return debug_points_run(device, 0, variant, n, in, 2, out, 1, cls);
+}
+
+EXTERN int grt_debug_device_math(Device_t device, int op, uint64_t n, fp_t const *a, fp_t *out0, fp_t *out1)
+{
+    GRT_REQUIRE_PTR(a);
+    GRT_REQUIRE_PTR(out0);
+    GRT_REQUIRE_PTR(out1);
+    GRT_REQUIRE_RANGE(op, 0, 4);
+    GRT_REQUIRE_RANGE(n, 1, 1u << 30);
+    double const *in[1] = {a};
+    double *out[2] = {out0, out1};
+    /* (out1 is the kernel's for op 0 alone: the others leave their half of the block unwritten, so it is not read back) */
+    return debug_points_run(device, 1, op, n, in, 1, out, op == 0 ? 2 : 1, NULL);
+}

@@ -1147,6 +1147,19 @@ EXTERN int grt_debug_line_strengths(GasOptics_t *gas_optics, uint64_t *num_lines
 EXTERN int grt_debug_voigt(Device_t device, int fast, fp_t w, uint64_t num_wpoints, fp_t wres, fp_t line_center,
                            fp_t gamma, fp_t alpha, fp_t *K);
 
+/* ---- parity hook: the near-centre line shape point by point.  x[i], y[i], i < n: doubles that hold fp32 values (X and Y
+ * of RFM_voigt.c:165/95); K[i]: what the device's voigt_near returns there, BEFORE the scaling of RFM_voigt.c:278;
+ * cls[i]: the class of formula voigt_class sorted the point into, -1 where no class is involved.  variant 0: reference
+ * operation order; 1: fused arithmetic; 2: sorted into classes 0 / 1 / 2 and evaluated by that class's code alone;
+ * 3: classes 0 / 1 / 2 / 3 (region 3 apart); 4: as 3, region 4 in packed registers -- the production instance's own
+ * dispatch.  Variants 0 and 1 also take |x| >= XLIM0 (K as :170 leaves it, likewise before :278) and
+ * y >= 70.55 (K of :103, which has no :278), with REPWID = 1. */
+EXTERN int grt_debug_voigt_points(Device_t device, int variant, uint64_t n, fp_t const *x, fp_t const *y, fp_t *K, int *cls);
+
+/* ---- parity hook: the device's own exponentials and REPWID at n arguments.  op 0: grt_exp_pair (out0 = e^a, out1 = e^-a);
+ * 1: grt_exp; 2: exp_fast; 3: exp_fp64; 4: reference_repwid(a), widened to double.  out1 is written for op 0 only. */
+EXTERN int grt_debug_device_math(Device_t device, int op, uint64_t n, fp_t const *a, fp_t *out0, fp_t *out1);
+
 /* ---- parity hook: the 1/Q(T, iso) block of one column's state as the DEVICE holds it (the path of
  * calc_partition_functions, kernels.c:52-66: evaluated on the host per layer and isotopologue, shipped inside the
  * column state, read by the line kernels as q[slot][layer][iso-1]).  q_out: host [num_molecules][L][GRT_MAX_ISO = 18],

@@ -92,6 +92,14 @@ class Oracle:
                            C.c_double(center), C.c_double(gamma), C.c_double(alpha), _dp(K))
         return K
 
+    def voigt_xy(self, x, y, force=-1):
+        """K before the scaling of RFM_voigt.c:278 at fp32 points (x, y); force: -1 the reference's choice of branch,
+        0 far wing, 1-3 regions 1-3, 4 / 5 region 4's inner / outer sums, 6 pure Lorentz (grt_oracle.h)."""
+        x, y = _f64(x), _f64(y)
+        K = np.zeros(x.size)
+        self.lib.orc_voigt_xy(C.c_uint64(x.size), _dp(x), _dp(y), C.c_int(force), _dp(K))
+        return K
+
     def line_sample(self, vnn, snn, gamma, alpha, ns, w0, wres, nw, windows=False):
         vnn, snn, gamma, alpha, ns = map(_f64, (vnn, snn, gamma, alpha, ns))
         L, N = vnn.shape

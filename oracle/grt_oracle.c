@@ -241,6 +241,145 @@ void orc_voigt(double w_start, uint64_t num_wpoints, double wres, double line_ce
     }
 }
 
+/* The same function point by point, at given fp32 (X, Y) instead of a grid and two widths: K[i] as the branch leaves it
+   BEFORE the scaling of :278 (REPWID = 1 where a branch uses it).  force = -1: the branch the reference's own tests
+   choose (:97, :168-257); otherwise that branch's formula whatever the tests say -- 0: far wing (:170), 1-3: regions 1-3
+   (:181-182, :197-198, :227-229), 4: region 4, inner sums (:261), 5: region 4, outer sums (:269-275), 6: pure Lorentz
+   (:103: K complete, that branch has no :278).  A point next to a limit can so be judged against either neighbour's
+   formula at the same x.  (Written out a second time, not shared with orc_voigt: that one keeps a line's coefficients
+   out of its point loop; tests/test_oracle_voigt_points.py holds this one to the reference's compiled function.) */
+void orc_voigt_xy(uint64_t n, double const *x, double const *yv, int force, double *K)
+{
+    float const rsqrpi = 0.56418958f;
+    static float const C[6] = {1.0117281f, -0.75197147f, 0.012557727f,
+                               0.010022008f, -0.00024206814f, 0.00000050084806f};
+    static float const S[6] = {1.393237f, 0.23115241f, -0.15535147f,
+                               0.0062183662f, 0.000091908299f, -0.00000062752596f};
+    static float const T[6] = {0.31424038f, 0.94778839f, 1.5976826f,
+                               2.2795071f, 3.0206370f, 3.8897249f};
+    for (uint64_t i = 0; i < n; ++i)
+    {
+        float const xi = x[i];
+        float const y = yv[i];
+        float const yq = y*y;
+        float const abx = fabs(xi);
+        float const xq = abx*abx;
+        int region = force;
+        if (region < 0)
+        {
+            float const xlim0 = sqrt(15100.0f + y*(40.0f - y*3.6f));         /* :109 */
+            float xlim1 = (y >= 8.425f) ? 0.0f : (float)sqrt(164.0f - y*(4.3f + y*1.8f)); /* :111-118 */
+            float xlim2 = 6.8f - y;
+            float const xlim3 = 2.4f*y;
+            float const xlim4 = 18.1f*y + 1.65f;
+            if (y <= 0.000001f)
+            {
+                xlim1 = xlim0;
+                xlim2 = xlim0;
+            }
+            region = y >= 70.55f ? 6 : abx >= xlim0 ? 0 : abx >= xlim1 ? 1 : abx >= xlim2 ? 2 : abx < xlim3 ? 3
+                     : abx <= xlim4 ? 4 : 5;
+        }
+        double k;
+        if (region == 6)
+        {
+            float const repwid = 1.0f;
+            k = repwid*y/(M_PI*(xi*xi + yq));                                /* :103 */
+        }
+        else if (region == 0)
+        {
+            float const yrrtpi = y*rsqrpi;                                   /* :108 */
+            k = yrrtpi/(xq + yq);                                            /* :170 */
+        }
+        else if (region == 1)
+        {
+            float const a0 = yq + 0.5;                                       /* :177 */
+            float const d0 = a0*a0;
+            float const d2 = yq + yq - 1.0;                                  /* :179 */
+            float const d = rsqrpi/(d0 + xq*(d2 + xq));                      /* :181-182 */
+            k = d*y*(a0 + xq);
+        }
+        else if (region == 2)
+        {
+            float const h0 = 0.5625f + yq*(4.5f + yq*(10.5f + yq*(6.0f + yq)));
+            float const h2 = -4.5f + yq*(9.0f + yq*(6.0f + yq*4.0f));
+            float const h4 = 10.5f - yq*(6.0f - yq*6.0f);
+            float const h6 = -6.0f + yq*4.0f;
+            float const e0 = 1.875f + yq*(8.25f + yq*(5.5f + yq));
+            float const e2 = 5.25f + yq*(1.0f + yq*3.0f);
+            float const e4 = 0.75f*h6;
+            float const d = rsqrpi/(h0 + xq*(h2 + xq*(h4 + xq*(h6 + xq))));   /* :197-198 */
+            k = d*y*(e0 + xq*(e2 + xq*(e4 + xq)));
+        }
+        else if (region == 3)
+        {
+            float const z0 = 272.1014f + y*(1280.829f + y*(2802.870f + y*(3764.966f
+                             + y*(3447.629f + y*(2256.981f + y*(1074.409f + y*(369.1989f
+                             + y*(88.26741f + y*(13.39880f + y)))))))));
+            float const z2 = 211.678f + y*(902.3066f + y*(1758.336f + y*(2037.310f
+                             + y*(1549.675f + y*(793.4273f + y*(266.2987f
+                             + y*(53.59518f + y*5.0f)))))));
+            float const z4 = 78.86585f + y*(308.1852f + y*(497.3014f + y*(479.2576f
+                             + y*(269.2916f + y*(80.39278f + y*10.0f)))));
+            float const z6 = 22.03523f + y*(55.02933f + y*(92.75679f + y*(53.59518f
+                             + y*10.0f)));
+            float const z8 = 1.496460f + y*(13.39880f + y*5.0f);
+            float const p0 = 153.5168f + y*(549.3954f + y*(919.4955f + y*(946.8970f
+                             + y*(662.8097f + y*(328.2151f + y*(115.3772f + y*(27.93941f
+                             + y*(4.264678f + y*0.3183291f))))))));
+            float const p2 = -34.16955f + y*(-1.322256f + y*(124.5975f + y*(189.7730f
+                             + y*(139.4665f + y*(56.81652f + y*(12.79458f
+                             + y*1.2733163f))))));
+            float const p4 = 2.584042f + y*(10.46332f + y*(24.01655f + y*(29.81482f
+                             + y*(12.79568f + y*1.9099744f))));
+            float const p6 = -0.07272979f + y*(0.9377051f + y*(4.266322f + y*1.273316f));
+            float const p8 = 0.0005480304f + y*0.3183291f;
+            float const d = 1.7724538f/(z0 + xq*(z2 + xq*(z4 + xq*(z6 + xq*(z8 + xq)))));  /* :227-229 */
+            k = d*(p0 + xq*(p2 + xq*(p4 + xq*(p6 + xq*p8))));
+        }
+        else
+        {
+            /* :233-276 */
+            float const y0 = 1.5f, y0py0 = 3.f, y0q = 2.25f;
+            float const ypy0 = y + y0;
+            float const ypy0q = ypy0*ypy0;
+            float mq[6], mf[6], xm[6], ym[6], pq[6], pf[6], xp[6], yp[6];
+            for (int J = 0; J < 6; ++J)
+            {
+                float d = xi - T[J];
+                mq[J] = d*d;
+                mf[J] = 1.0f/(mq[J] + ypy0q);
+                xm[J] = mf[J]*d;
+                ym[J] = mf[J]*ypy0;
+                d = xi + T[J];
+                pq[J] = d*d;
+                pf[J] = 1.0f/(pq[J] + ypy0q);
+                xp[J] = pf[J]*d;
+                yp[J] = pf[J]*ypy0;
+            }
+            k = 0.0f;
+            if (region == 4)
+            {
+                for (int J = 0; J < 6; ++J)
+                {
+                    k = k + C[J]*(ym[J] + yp[J]) - S[J]*(xm[J] - xp[J]);
+                }
+            }
+            else
+            {
+                float const yf = y + y0py0;
+                for (int J = 0; J < 6; ++J)
+                {
+                    k = k + (C[J]*(mq[J]*mf[J] - y0*ym[J]) + S[J]*yf*xm[J])/(mq[J] + y0q)
+                          + (C[J]*(pq[J]*pf[J] - y0*yp[J]) - S[J]*yf*xp[J])/(pq[J] + y0q);
+                }
+                k = y*k + exp(-xq);
+            }
+        }
+        K[i] = k;
+    }
+}
+
 /* ------------------------------------------------------------------------- */
 /* Line sampling -- gas-optics/src/kernels.c:410-465                         */
 /* Serial order: layer -> line -> point (the reference's one-thread order).   */

@@ -61,6 +61,10 @@ void orc_line_prep(uint64_t num_lines, int num_layers, int num_iso, double mass,
 void orc_voigt(double w_start, uint64_t num_wpoints, double wres, double line_center,
                double lorentz_hwhm, double doppler_hwhm, double *K);
 
+/* ... per point at given fp32 (x, y), before the scaling of :278.  force = -1: the reference's own choice of branch;
+   0: far wing, 1-3: regions 1-3, 4 / 5: region 4's inner / outer sums, 6: pure Lorentz (complete: no :278 there) */
+void orc_voigt_xy(uint64_t n, double const *x, double const *y, int force, double *K);
+
 /* kernels.c:410-465 (pedestal branch dead: launch.c:90-91).  Also reports, per
  * (layer,line), the integer window [s,e] (or s=1,e=0 when the line is skipped)
  * when win_s/win_e are non-NULL -- used for the bit-exact index tests. */
