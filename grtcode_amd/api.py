@@ -30,7 +30,7 @@ GRT_CLOUD_PHASE, GRT_CLOUD_MODEL, GRT_CLOUD_FIELDS = 7, 8, 9   # ... of GrtCloud
  TAG_ALLSKY_SW, TAG_BINS, TAG_SUBCOLUMN_MEAN, TAG_AEROSOL_LW, TAG_AEROSOL_SW, TAG_BAND_PROFILES, TAG_SURFACE,
  TAG_CLOUD_SAMPLER, TAG_SKY_LW, TAG_SKY_SW, TAG_ZENITH_SW, TAG_ZENITH_MEAN, TAG_DIRECT_BEAM, TAG_SKY_ZENITH_SW,
  TAG_SKY_ZENITH_MEAN, TAG_SURFACE_JACOBIAN, TAG_RADIANCE, TAG_CHANNELS, TAG_WEIGHTING, TAG_WEIGHTING_FINISH,
- TAG_KDIST, TAG_KDIST_MAP, TAG_KDIST_MAPPED) = range(1, 32)
+ TAG_KDIST, TAG_KDIST_MAP, TAG_KDIST_MAPPED, TAG_CK_SOURCES, TAG_CK_LW, TAG_CK_SW) = range(1, 35)
 TAG_FAR_OFFSET = TAG_FAR_LW - TAG_GAS_LW    # from a line kernel's tag to its far-field gather's
 CLOUD_SAMPLER_TAG = TAG_CLOUD_SAMPLER
 GRT_MAX_SUBCOLUMNS = 64             # grt_pipeline_run_subcolumns: subcolumns per column, 1 .. this
@@ -227,6 +227,17 @@ class GrtKdistKeys(C.Structure):
     _fields_ = [("lw", GrtKdistKey), ("sw", GrtKdistKey)]
 
 
+class GrtCkBand(C.Structure):
+    _fields_ = [("edges", C.POINTER(C.c_int)), ("num_bins", C.c_int), ("key", GrtKdistKey), ("map_given_dev", C.c_void_p),
+                ("points_dev", C.c_void_p), ("weight_dev", C.c_void_p), ("tau_dev", C.c_void_p), ("source_dev", C.c_void_p),
+                ("flux_up_dev", C.c_void_p), ("flux_down_dev", C.c_void_p), ("bin_up_dev", C.c_void_p),
+                ("bin_down_dev", C.c_void_p)]
+
+
+class GrtCkFluxes(C.Structure):
+    _fields_ = [("num_classes", C.c_int), ("class_edges", c_double_p), ("lw", GrtCkBand), ("sw", GrtCkBand)]
+
+
 class GrtZeniths(C.Structure):
     _fields_ = [("num_zeniths", C.c_int), ("cos_zenith", c_double_p), ("weight", c_double_p),
                 ("zenith_fluxes_dev", C.c_void_p), ("zenith_level_fluxes_dev", C.c_void_p)]
@@ -253,7 +264,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_channels grt_channel_pair_count grt_pipeline_run_sky_weighting grt_pipeline_run_sky_zeniths grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_kdist_rows grt_pipeline_run_kdist grt_kdist_chunk_points grt_kdist_class_map grt_kdist_mapped_rows grt_pipeline_run_kdist_correlated grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_channels grt_channel_pair_count grt_pipeline_run_sky_weighting grt_pipeline_run_sky_zeniths grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_kdist_rows grt_pipeline_run_kdist grt_kdist_chunk_points grt_kdist_class_map grt_kdist_mapped_rows grt_pipeline_run_kdist_correlated grt_pipeline_run_ck_fluxes grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_voigt_points grt_debug_device_math grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -340,6 +351,8 @@ def load_library(path=None):
                                               C.c_longlong, C.c_double, C.c_int, C.POINTER(GrtKdistBand)]
         lib.grt_pipeline_run_kdist_correlated.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtKdist),
                                                           C.POINTER(GrtKdistKeys)]
+    if hasattr(lib, "grt_pipeline_run_ck_fluxes"):       # (GRT_LIB_PATH may name an older library: a timing yardstick)
+        lib.grt_pipeline_run_ck_fluxes.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtCkFluxes)]
     lib.grt_pipeline_sky_set_count.argtypes = [C.c_uint]
     if hasattr(lib, "grt_pipeline_run_zeniths"):    # (GRT_LIB_PATH may name an older library: a timing yardstick)
         lib.grt_pipeline_run_zeniths.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtZeniths), C.c_void_p,
@@ -979,6 +992,7 @@ class Pipeline:
         self.band_shape = None  # ... of the last run_band_profiles
         self.kdist_shape = None  # (classes, longwave bins, shortwave bins) of the last run_kdist
         self.kdist_corr_shape = None  # ... of the last run_kdist_correlated, and whether it kept the maps
+        self.ck_shape = None    # ... of the last run_ck_fluxes, and whether it kept the maps
         self.out = self._buffer("run", 8 * GRT_FLUXES_PER_COLUMN * max_columns)
 
     def _buffer(self, name, nbytes):
@@ -1206,6 +1220,75 @@ class Pipeline:
                          "tau": self.buffers[f"kdist_corr.{name}.tau"].to_host((ncol, L, nb, K)),
                          "map": (self.buffers[f"kdist_corr.{name}.map"].to_host((ncol, self.nw[bi]), dtype=np.uint16)
                                  if kept else None)}
+        return out
+
+    def run_ck_fluxes(self, gcols, class_edges, lw_edges=None, sw_edges=None, lw_key=("sum",), sw_key=("sum",),
+                      lw_map=None, sw_map=None, keep_map=False):
+        """grt_pipeline_run_ck_fluxes into this object's device buffers (ck_fluxes() reads them): the clear-clean fluxes of
+        the correlated-k model that the classes, bins and keys of run_kdist_correlated define, every level per (bin,
+        class) and per bin, with the class weights, the class sums of tau and of the sources they were solved from.
+        lw_map / sw_map: a DeviceBuffer or pointer to a class map [ncol][n] of uint16 that is used as it is in place of
+        the key's (class_edges may then be None; K is then its own argument: pass class_edges as the int K).  keep_map:
+        the maps the call builds go to buffers of this object (ck_fluxes() returns them)."""
+        if isinstance(class_edges, (int, np.integer)):
+            K, ce = int(class_edges), None
+        else:
+            ce = _f64(class_edges).ravel()
+            K = ce.size + 1
+        gk = GrtCkFluxes()
+        gk.num_classes, gk.class_edges = K, _opt_dp(ce)
+        V, L, C_ = self.num_levels, self.num_levels - 1, self.max_columns
+        keep = [ce]
+        given = []
+        for bi, (name, band, edges, spec, m) in enumerate((("lw", gk.lw, lw_edges, lw_key, lw_map),
+                                                            ("sw", gk.sw, sw_edges, sw_key, sw_map))):
+            e = None if edges is None else np.ascontiguousarray(edges, dtype=np.int32).ravel()
+            keep.append(e)
+            band.edges = None if e is None else e.ctypes.data_as(c_int_p)
+            band.num_bins = 0 if e is None else max(e.size - 1, 0)
+            count = max(C_ * band.num_bins * K, 1)
+            R = 2 * V + 1 if bi == 0 else 4
+            band.points_dev = self._buffer(f"ck.{name}.points", 4 * count).ptr
+            band.weight_dev = self._buffer(f"ck.{name}.weight", 8 * count).ptr
+            band.tau_dev = self._buffer(f"ck.{name}.tau", 8 * count * L).ptr
+            band.source_dev = self._buffer(f"ck.{name}.source", 8 * count * R).ptr
+            band.flux_up_dev = self._buffer(f"ck.{name}.up", 8 * count * V).ptr
+            band.flux_down_dev = self._buffer(f"ck.{name}.down", 8 * count * V).ptr
+            band.bin_up_dev = self._buffer(f"ck.{name}.bin_up", 8 * max(C_ * band.num_bins * V, 1)).ptr
+            band.bin_down_dev = self._buffer(f"ck.{name}.bin_down", 8 * max(C_ * band.num_bins * V, 1)).ptr
+            band.key.kind, band.key.layer = _kdist_key(spec)
+            band.key.map_dev = None
+            band.map_given_dev = None
+            if m is not None:
+                band.map_given_dev = C.c_void_p(_addr(m.ptr if isinstance(m, DeviceBuffer) else m))
+            elif keep_map and band.num_bins > 0:
+                band.key.map_dev = self._buffer(f"ck.{name}.map", 2 * C_ * self.nw[bi]).ptr
+            given.append(m is not None)
+        self.ck_shape = (K, gk.lw.num_bins, gk.sw.num_bins, bool(keep_map), tuple(given))
+        check(self.lib.grt_pipeline_run_ck_fluxes(self.p, C.byref(gcols), C.byref(gk)))
+        del keep
+
+    def ck_fluxes(self, ncol):
+        """The last run_ck_fluxes: {"lw": {...}, "sw": {...}} with points (int32) and weight [ncol][num_bins][K], tau
+        [ncol][L][num_bins][K], source [ncol][R][num_bins][K] (R = 2 V + 1 longwave, 4 shortwave), up and down
+        [ncol][V][num_bins][K] (W m-2 per class), bin_up and bin_down [ncol][V][num_bins] (W m-2), and map, uint16
+        [ncol][n], when the call built and kept it, else None.  grtcode_amd.kdist.ck_means gives the class means."""
+        self.sync()
+        K, nb_lw, nb_sw, kept, given = self.ck_shape
+        V, L = self.num_levels, self.num_levels - 1
+        out = {}
+        for bi, (name, nb) in enumerate((("lw", nb_lw), ("sw", nb_sw))):
+            R = 2 * V + 1 if bi == 0 else 4
+            shapes = {"points": (ncol, nb, K), "weight": (ncol, nb, K), "tau": (ncol, L, nb, K), "source": (ncol, R, nb, K),
+                      "up": (ncol, V, nb, K), "down": (ncol, V, nb, K), "bin_up": (ncol, V, nb), "bin_down": (ncol, V, nb)}
+            if nb == 0:
+                out[name] = {k: np.zeros(sh, dtype=np.int32 if k == "points" else np.float64) for k, sh in shapes.items()}
+                out[name]["map"] = None
+                continue
+            out[name] = {k: self.buffers[f"ck.{name}.{k}"].to_host(sh, dtype=np.int32 if k == "points" else np.float64)
+                         for k, sh in shapes.items()}
+            out[name]["map"] = (self.buffers[f"ck.{name}.map"].to_host((ncol, self.nw[bi]), dtype=np.uint16)
+                                if kept and not given[bi] else None)
         return out
 
     def _six_row_or_profile_ptrs(self, name, profiles):

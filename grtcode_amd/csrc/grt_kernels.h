@@ -862,6 +862,55 @@ typedef struct GrtKdistMappedArgs
 int grt_launch_kdist_map(void *stream, GrtKdistMapArgs const *a);
 int grt_launch_kdist_mapped(void *stream, GrtKdistMappedArgs const *a);
 
+/* Flux solves of a correlated-k model on its g-classes (grt_ext.h: grt_pipeline_run_ck_fluxes, which defines them).
+   The source sums (k_kdist.hip: kdist_sources_kernel): the mapped reduction's walk, one workgroup per (column, source row,
+   bin), with the row's value at a point computed -- the Planck function at a level's, a layer's or the surface's
+   temperature (longwave rows 0 .. V - 1, V .. 2 V - 2, 2 V - 1), the Rayleigh cross-section (shortwave row 0) -- or loaded
+   from a data row -- data[0] (longwave row 2 V: the emissivity), data[0 .. 2] (shortwave rows 1 .. 3: the solar curve, the
+   direct and the diffuse albedo), column c's at data[k] + c data_stride[k].  source_sum is [ncol][R][num_bins]
+   [num_classes], R = 2 V + 1 or 4.  A map entry >= num_classes belongs to no class. */
+typedef struct GrtCkSourceArgs
+{
+    int longwave;                   /* != 0: the longwave's rows */
+    int num_levels;
+    long long ncol, n;
+    double w0, dw;
+    int num_classes, num_bins;
+    int const *edges;
+    unsigned short const *map;      /* [ncol][n] */
+    double const *t_levels, *t_layers, *t_surf;     /* longwave: [ncol][V], [ncol][V - 1], [ncol] */
+    double const *data[3];
+    uint64_t data_stride[3];
+    double *source_sum;
+} GrtCkSourceArgs;
+int grt_launch_ck_sources(void *stream, GrtCkSourceArgs const *a);
+/* The solve (k_longwave.hip: ck_lw_kernel, k_shortwave.hip: ck_sw_kernel): one thread per (column, bin, class) walks the
+   column's layers on the class means -- weight_sum [ncol][num_bins][num_classes], tau_sum [ncol][V - 1][..][..],
+   source_sum [ncol][R][..][..] -- and leaves every level's flux of the class in W m-2 at flux_up, flux_down
+   [ncol][V][..][..]; +0.0 for a class of weight 0 and (shortwave) for a column with mu_dir <= 0.  The shortwave reads
+   n_layer [ncol][V - 1], mu_dir and tsi [ncol] and mu_dif too. */
+typedef struct GrtCkSolveArgs
+{
+    int num_levels, ncol, num_bins, num_classes;
+    double const *weight_sum, *tau_sum, *source_sum;
+    double *flux_up, *flux_down;
+    double const *n_layer, *mu_dir, *tsi;
+    double mu_dif;
+} GrtCkSolveArgs;
+static inline int grt_ck_solve_args_ok(GrtCkSolveArgs const *a)
+{
+    return a != NULL && a->num_levels >= 2 && a->ncol >= 1 && a->num_bins >= 1 && a->num_classes >= 2 &&
+           a->num_classes <= GRT_KDIST_CLASS_LIMIT && a->weight_sum != NULL && a->tau_sum != NULL &&
+           a->source_sum != NULL && a->flux_up != NULL && a->flux_down != NULL &&
+           /* (a grid of workgroups of GRT_SOLVER_BLOCK threads) */
+           ((uint64_t)a->ncol*(uint64_t)a->num_bins*(uint64_t)a->num_classes + GRT_SOLVER_BLOCK - 1)/GRT_SOLVER_BLOCK <= 0x7fffffffull;
+}
+int grt_launch_ck_lw(void *stream, GrtCkSolveArgs const *a);
+int grt_launch_ck_sw(void *stream, GrtCkSolveArgs const *a);
+/* The bin sums (k_kdist.hip: ck_bin_sum_kernel): out[r] = (((+0.0 + in[r K]) + in[r K + 1]) + ...) + in[r K + K - 1] for
+   every row r < rows, one thread a row. */
+int grt_launch_ck_bin_sum(void *stream, double const *in, long long rows, int num_classes, double *out);
+
 /* Fused Rayleigh + combine for the clear-sky driver sequence (rayleigh.c:39 +
    optics.c:138-145 with K=2, gas omega=g=0, Rayleigh omega=1,g=0):
    tau_tot = tau_gas + tau_R, omega = tau_R/tau_tot, g = 0/ tau_R.  n_layer [ncol][L]. */

@@ -24,9 +24,15 @@
 // (group, point) -- kdist_map_kernel: the class of a key row or of the sum of the group's rows, 16 bits a point -- and
 // reduces every row of the group under it: kdist_mapped_kernel is kdist_kernel with phase 1's bisection replaced by a
 // 2-byte load from the map; phase 2 (sum_chunk) is the same function for both.
+//
+// The flux solves on g-classes (grt_pipeline_run_ck_fluxes) take two more kernels from here: kdist_sources_kernel, the
+// mapped kernel with the row's value at a point computed -- the solvers' own Planck function and Rayleigh cross-section --
+// instead of loaded, and ck_bin_sum_kernel, the sequential sum of a bin's class fluxes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../grt_kernels.h"
+#include "optics_dev.h"
+#include "planck_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -345,7 +351,157 @@ __global__ __launch_bounds__(kThreads) void kdist_mapped_kernel(GrtKdistMappedAr
     }
 }
 
+// The value of source row `row` of column g at grid point i (GrtCkSourceArgs, grt_kernels.h): the longwave's Planck rows
+// by the solver's own planck() at the solver's own wavenumber (planck_dev.h), the shortwave's Rayleigh cross-section by
+// the solver's rayleigh_tau with n = 1 (optics_dev.h); the data rows are loaded.
+__device__ __forceinline__ double source_value(GrtCkSourceArgs const &a, long long g, int row, long long i)
+{
+    int const V = a.num_levels;
+    if (a.longwave)
+    {
+        if (row == 2*V)
+        {
+            return a.data[0][(uint64_t)g*a.data_stride[0] + (uint64_t)i];
+        }
+        double const T = row < V ? a.t_levels[g*V + row] : (row < 2*V - 1 ? a.t_layers[g*(V - 1) + (row - V)] : a.t_surf[g]);
+        return planck(T, grid_wavenumber(a.w0, a.dw, (uint64_t)i));
+    }
+    if (row == 0)
+    {
+        return rayleigh_tau(grid_wavenumber(a.w0, a.dw, (uint64_t)i), 1.0);
+    }
+    return a.data[row - 1][(uint64_t)g*a.data_stride[row - 1] + (uint64_t)i];
+}
+
+// The source sums of a correlated-k model: kdist_mapped_kernel's walk, one workgroup per (column, source row, bin), phase 1
+// with the row's value at the point computed (source_value) instead of loaded; phase 2 is sum_chunk.  Only the sums of
+// weight x value leave: the counts and the weight sums are the mapped reduction's.
+// LDS: 18 bytes a point, 18 432 bytes.
+// OWNED: the classes a thread owns, as the other kernels' NC
+template <int OWNED>
+__global__ __launch_bounds__(kThreads) void kdist_sources_kernel(GrtCkSourceArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    double *w_s = reinterpret_cast<double *>(lds);                          // [kChunkPoints]
+    double *t_s = w_s + kChunkPoints;                                       // [kChunkPoints]
+    unsigned short *c_s = reinterpret_cast<unsigned short *>(t_s + kChunkPoints);   // [kChunkPoints]
+
+    int const tid = threadIdx.x, K = a.num_classes;
+    int const wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    bool const wave_has_classes = wave*64 < K;
+    double const half_dw = 0.5*a.dw;
+    int const R = a.longwave ? 2*a.num_levels + 1 : 4;
+
+    long long const per_group = R*(long long)a.num_bins, items = a.ncol*per_group;
+    for (long long item = blockIdx.x; item < items; item += gridDim.x)
+    {
+        long long const g = item/per_group;
+        int const row = (int)((item - g*per_group)/a.num_bins);
+        int const bin = (int)(item - g*per_group - (long long)row*a.num_bins);
+        int const first = a.edges[bin], last = a.edges[bin + 1];
+        unsigned short const *map = a.map + g*a.n;
+        int count[OWNED];
+        double wsum[OWNED], tsum[OWNED];
+#pragma unroll
+        for (int c = 0; c < OWNED; ++c)
+        {
+            count[c] = 0;
+            wsum[c] = 0.;
+            tsum[c] = 0.;
+        }
+        for (long long start = first; start <= last; start += kChunkPoints)
+        {
+            int const m = (int)min((long long)kChunkPoints, last - start + 1);
+            int const padded = (m + kStep - 1) & ~(kStep - 1);
+            __syncthreads();               // the chunk before has been summed
+            for (int j = tid; j < m; j += kThreads)
+            {
+                long long const i = start + j;
+                double const x = source_value(a, g, row, i);
+                unsigned const cls = map[i];
+                double const w = (i == first || i == last) ? half_dw : a.dw;
+                w_s[j] = w;
+                t_s[j] = __dmul_rn(w, x);
+                c_s[j] = (unsigned short)(cls < (unsigned)K ? cls : kNoClass);
+            }
+            for (int j = m + tid; j < padded; j += kThreads)
+            {
+                w_s[j] = 0.;
+                t_s[j] = 0.;
+                c_s[j] = (unsigned short)kNoClass;
+            }
+            __syncthreads();
+            sum_chunk<OWNED>(c_s, w_s, t_s, padded, K, tid, wave, wave_has_classes, count, wsum, tsum);
+        }
+#pragma unroll
+        for (int c = 0; c < OWNED; ++c)
+        {
+            int const cls = tid + c*kThreads;
+            if (cls < K)
+            {
+                a.source_sum[item*K + cls] = tsum[c];
+            }
+        }
+    }
+}
+
+// The bin sums of a correlated-k model's class fluxes: one thread per row of K classes adds them in class order from +0.0.
+__global__ __launch_bounds__(kThreads) void ck_bin_sum_kernel(double const *in, long long rows, int K, double *out)
+{
+    long long const r = (long long)blockIdx.x*kThreads + threadIdx.x;
+    if (r >= rows)
+    {
+        return;
+    }
+    double const *x = in + r*K;
+    double sum = 0.;
+    for (int k = 0; k < K; ++k)
+    {
+        sum = __dadd_rn(sum, x[k]);
+    }
+    out[r] = sum;
+}
+
 }  // namespace
+
+extern "C" int grt_launch_ck_sources(void *stream, GrtCkSourceArgs const *a)
+{
+    if (a == nullptr || a->map == nullptr || a->source_sum == nullptr || a->edges == nullptr || a->ncol < 1 || a->n < 2 ||
+        a->num_levels < 2 || a->num_bins < 1 || a->num_classes < 2 || a->num_classes > kMaxClasses || a->data[0] == nullptr ||
+        (a->longwave ? a->t_levels == nullptr || a->t_layers == nullptr || a->t_surf == nullptr
+                     : a->data[1] == nullptr || a->data[2] == nullptr))
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    long long const items = a->ncol*(a->longwave ? 2*a->num_levels + 1 : 4)*(long long)a->num_bins;
+    unsigned const blocks = (unsigned)(items < (1ll << 20) ? items : (1ll << 20));
+    size_t const lds = (size_t)kChunkPoints*(2*sizeof(double) + sizeof(unsigned short));
+    hipStream_t const s = (hipStream_t)stream;
+    if (a->num_classes <= kThreads)
+    {
+        hipLaunchKernelGGL(kdist_sources_kernel<1>, dim3(blocks), dim3(kThreads), lds, s, *a);
+    }
+    else if (a->num_classes <= 2*kThreads)
+    {
+        hipLaunchKernelGGL(kdist_sources_kernel<2>, dim3(blocks), dim3(kThreads), lds, s, *a);
+    }
+    else
+    {
+        hipLaunchKernelGGL(kdist_sources_kernel<4>, dim3(blocks), dim3(kThreads), lds, s, *a);
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_ck_bin_sum(void *stream, double const *in, long long rows, int num_classes, double *out)
+{
+    if (in == nullptr || out == nullptr || rows < 1 || num_classes < 1 || (rows + kThreads - 1)/kThreads > 0x7fffffffll)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(ck_bin_sum_kernel, dim3((unsigned)((rows + kThreads - 1)/kThreads)), dim3(kThreads), 0,
+                       (hipStream_t)stream, in, rows, num_classes, out);
+    return (int)hipGetLastError();
+}
 
 extern "C" int grt_kdist_chunk(void)
 {

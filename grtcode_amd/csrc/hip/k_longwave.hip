@@ -33,6 +33,7 @@
 #include <stdint.h>
 #include "../grt_kernels.h"
 #include "optics_dev.h"
+#include "planck_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -42,23 +43,7 @@ constexpr double kMaxExpArg = 700.;   // grtcode_config.h:41
 // the four streams' constants (longwave.c:160-168)
 constexpr double kC1[4] = {-14.402613260847248, -3.0302159969901132, -1.4925584280108841, -1.0746123148178333};
 constexpr double kC2[4] = {0.07587638482015649, 0.676114979733751, 1.3726594476601073, 1.0169418413757783};
-// planck_law's constants (longwave.c:70-71)
-constexpr double kPlanckC1 = 1.1910429526245744e-8;
-constexpr double kPlanckC2 = 1.4387773538277202;
-
-// longwave.c:68-94
-__device__ __forceinline__ double planck(double T, double w)
-{
-    double const c1 = kPlanckC1;
-    double const c2 = kPlanckC2;
-    double e = c2*w/T;
-    if (e > kMaxExpArg)
-    {
-        e = kMaxExpArg;
-    }
-    e = exp(e);
-    return (c1*w*w*w)/(e - 1.);
-}
+// (planck_law and its constants, longwave.c:68-94: planck_dev.h, shared with the correlated-k source sums)
 
 // planck(T, w) and with it dB/dT = B (x/T) e/(e - 1), x = c2 w/T, e = exp(x), from planck()'s own exponential (the same
 // expressions: the same B); 0 where planck() clamps x
@@ -292,6 +277,52 @@ __global__ __launch_bounds__(kSolverBlock) void lw_kernel(GrtLwArgs a, Joins... 
         }
     }
     sink.finish(a);
+}
+
+// ---- the longwave of a correlated-k model on its g-points (grt_launch_ck_lw; GrtCkSolveArgs, grt_kernels.h) ----
+// One thread per (column, bin, class), the class fastest: every read of a layer's class sums and every store of a level
+// is coalesced.  The g-point's layer optical depths, Planck terms and emissivity are the class means sum/W; then
+// lw_kernel's two sweeps on them, operation for operation, gas only (omega = 0).  The four streams stay in registers; no
+// LDS, no cross-lane traffic.  The flux per cm-1 times W, the class's W m-2, leaves at every level.  An empty class
+// (W = 0) leaves +0.0 and solves nothing.
+__global__ __launch_bounds__(kSolverBlock) void ck_lw_kernel(GrtCkSolveArgs a)
+{
+    uint64_t const per_col = (uint64_t)a.num_bins*(uint64_t)a.num_classes;
+    uint64_t const t = (uint64_t)blockIdx.x*kSolverBlock + threadIdx.x;
+    if (t >= (uint64_t)a.ncol*per_col)
+    {
+        return;
+    }
+    uint64_t const col = t/per_col, at = t - col*per_col;
+    int const V = a.num_levels, L = V - 1;
+    double const W = a.weight_sum[col*per_col + at];
+    double const *T = a.tau_sum + col*(uint64_t)L*per_col + at;              // layer j at T[j per_col]
+    double const *S = a.source_sum + col*(uint64_t)(2*V + 1)*per_col + at;   // source row r at S[r per_col]
+    double *up = a.flux_up + col*(uint64_t)V*per_col + at, *dn = a.flux_down + col*(uint64_t)V*per_col + at;
+    if (!(W > 0.))
+    {
+        for (int lev = 0; lev < V; ++lev)
+        {
+            up[(uint64_t)lev*per_col] = 0.;
+            dn[(uint64_t)lev*per_col] = 0.;
+        }
+        return;
+    }
+    double I[4] = {0., 0., 0., 0.};
+    dn[0] = 0.;                                                          // longwave.c:171
+    for (int j = 0; j < L; ++j)
+    {
+        double const tl = T[(uint64_t)j*per_col]/W;
+        double const val = effective_planck(S[(uint64_t)(V + j)*per_col]/W, S[(uint64_t)(j + 1)*per_col]/W, tl);
+        dn[(uint64_t)(j + 1)*per_col] = stream_step(I, val, [&](int s) { return extinction(s, tl); })*W;
+    }
+    up[(uint64_t)L*per_col] = surface_step(I, S[(uint64_t)(2*V)*per_col]/W, S[(uint64_t)(2*V - 1)*per_col]/W)*W;
+    for (int j = L - 1; j >= 0; --j)
+    {
+        double const tl = T[(uint64_t)j*per_col]/W;
+        double const val = effective_planck(S[(uint64_t)(V + j)*per_col]/W, S[(uint64_t)j*per_col]/W, tl);
+        up[(uint64_t)j*per_col] = stream_step(I, val, [&](int s) { return extinction(s, tl); })*W;
+    }
 }
 
 // ---- the surface-temperature Jacobian of the materialised form (grt_launch_lw_surface_jacobian) ----
@@ -869,6 +900,18 @@ int launch_weighting(hipStream_t s, GrtSolverInstance const &in, GrtLwArgs const
 extern "C" unsigned grt_solver_blocks(uint64_t nw)
 {
     return (unsigned)((nw + kSolverBlock - 1)/kSolverBlock);
+}
+
+extern "C" int grt_launch_ck_lw(void *stream, GrtCkSolveArgs const *a)
+{
+    if (!grt_ck_solve_args_ok(a))
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    uint64_t const threads = (uint64_t)a->ncol*(uint64_t)a->num_bins*(uint64_t)a->num_classes;
+    hipLaunchKernelGGL(ck_lw_kernel, dim3((unsigned)((threads + kSolverBlock - 1)/kSolverBlock)), dim3(kSolverBlock), 0,
+                       (hipStream_t)stream, *a);
+    return (int)hipGetLastError();
 }
 
 extern "C" int grt_launch_lw(void *stream, GrtSolverInstance const *in, GrtLwArgs const *a)

@@ -471,6 +471,82 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Joins... 
     sink.finish(a);
 }
 
+// ---- the shortwave of a correlated-k model on its g-points (grt_launch_ck_sw; GrtCkSolveArgs, grt_kernels.h) ----
+// One thread per (column, bin, class), the class fastest: every read of a layer's class sums and every store of a level
+// is coalesced.  The g-point's gas optical depth of a layer is the class mean sum/W, its Rayleigh optical depth the layer's
+// air column times the class sum of the cross-section, over W; clear_sky_combine and layer_props on them, then the
+// reference's two sweeps (sw_kernel's materialised form): the first parks the two downward-beam reflectances of every level
+// in the output arrays, the second consumes each pair and overwrites it with the level's fluxes.  The scale is the class
+// SUM of the solar curve times mu_dir, then tsi, in put_level's order: W m-2 per class.  An empty class (W = 0) and a
+// night column (mu_dir <= 0) leave +0.0 and solve nothing.
+__global__ __launch_bounds__(kSolverBlock) void ck_sw_kernel(GrtCkSolveArgs a)
+{
+    uint64_t const per_col = (uint64_t)a.num_bins*(uint64_t)a.num_classes;
+    uint64_t const t = (uint64_t)blockIdx.x*kSolverBlock + threadIdx.x;
+    if (t >= (uint64_t)a.ncol*per_col)
+    {
+        return;
+    }
+    uint64_t const col = t/per_col, at = t - col*per_col;
+    int const V = a.num_levels, L = V - 1;
+    double const W = a.weight_sum[col*per_col + at];
+    double const *T = a.tau_sum + col*(uint64_t)L*per_col + at;              // layer j at T[j per_col]
+    double const *S = a.source_sum + col*(uint64_t)4*per_col + at;           // source row r at S[r per_col]
+    double const *nl = a.n_layer + col*(uint64_t)L;
+    double *fu = a.flux_up + col*(uint64_t)V*per_col + at, *fd = a.flux_down + col*(uint64_t)V*per_col + at;
+    double const mu_dir = a.mu_dir[col], mu_dif = a.mu_dif;
+    if (!(W > 0.) || !(mu_dir > 0.))
+    {
+        for (int lev = 0; lev < V; ++lev)
+        {
+            fu[(uint64_t)lev*per_col] = 0.;
+            fd[(uint64_t)lev*per_col] = 0.;
+        }
+        return;
+    }
+    double const ray = S[0];
+
+    auto props_of = [&](int j) -> LayerProps
+    {
+        double const tg = T[(uint64_t)j*per_col]/W, tr = (nl[j]*ray)/W;
+        double tt, om, gg;
+        clear_sky_combine(tg, tr, tt, om, gg);
+        return layer_props(om, gg, tt, mu_dir, mu_dif);
+    };
+
+    // sweep 1: shortwave.c:280-294
+    double Rdir_dn = S[2*per_col]/W;
+    double Rdif_dn = S[3*per_col]/W;
+    fu[(uint64_t)L*per_col] = Rdir_dn;
+    fd[(uint64_t)L*per_col] = Rdif_dn;
+    for (int j = L - 1; j >= 0; --j)
+    {
+        sweep1_step(props_of(j), Rdir_dn, Rdif_dn);
+        fu[(uint64_t)j*per_col] = Rdir_dn;
+        fd[(uint64_t)j*per_col] = Rdif_dn;
+    }
+
+    // sweep 2: shortwave.c:299-329, then the scalings of :401-405 and :447-451 (put_level's)
+    double const scale = S[per_col]*mu_dir;
+    double const tsi = a.tsi[col];
+    auto put = [&](int lev, double up, double dn)
+    {
+        up *= scale;
+        dn *= scale;
+        fu[(uint64_t)lev*per_col] = tsi*up;
+        fd[(uint64_t)lev*per_col] = tsi*dn;
+    };
+    Sweep2 s;
+    put(0, s.dir*Rdir_dn, s.dir);                 // R[0] = dir_beam*R_dir_downward[0], T[0]
+    for (int lev = 1; lev < V; ++lev)
+    {
+        sweep2_step(s, props_of(lev - 1), lev);
+        double up, dn;
+        level_flux(s.dir, s.dif, s.Rup, fu[(uint64_t)lev*per_col], fd[(uint64_t)lev*per_col], up, dn);
+        put(lev, up, dn);
+    }
+}
+
 // ---- several sun angles per column on one walk through the layers (grt_launch_sw_zeniths) ----
 // Of sw_kernel<GRT_OUT_ROWS>'s one sweep, a layer's optics (tau_gas, continua, Rayleigh and what joins them: LayerOptics),
 // its delta-scaling, its diffuse Eddington solution with k and exp(+-t k), and C, Ru, Tu of the sweep depend on the optics
@@ -773,6 +849,18 @@ int launch(hipStream_t s, GrtSolverInstance const &in, GrtSwArgs const &a, Joins
 }
 
 } // namespace
+
+extern "C" int grt_launch_ck_sw(void *stream, GrtCkSolveArgs const *a)
+{
+    if (!grt_ck_solve_args_ok(a) || a->n_layer == nullptr || a->mu_dir == nullptr || a->tsi == nullptr)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    uint64_t const threads = (uint64_t)a->ncol*(uint64_t)a->num_bins*(uint64_t)a->num_classes;
+    hipLaunchKernelGGL(ck_sw_kernel, dim3((unsigned)((threads + kSolverBlock - 1)/kSolverBlock)), dim3(kSolverBlock), 0,
+                       (hipStream_t)stream, *a);
+    return (int)hipGetLastError();
+}
 
 extern "C" int grt_launch_sw(void *stream, GrtSolverInstance const *in, GrtSwArgs const *a)
 {

@@ -1,8 +1,9 @@
 /* grt_kdist.c -- the host side of the k-distributions of optical-depth rows (grt_ext.h: grt_kdist_rows,
  * grt_pipeline_run_kdist, grt_kdist_chunk_points) and of the correlated ones under one class map per group
  * (grt_kdist_class_map, grt_kdist_mapped_rows, grt_pipeline_run_kdist_correlated): the argument checks, the class edges,
- * weight and bin edges of a call kept on the device until a call brings other ones, the launches (k_kdist.hip).  The two
- * pipeline entry points themselves, which run the gas optics in front of the reduction, are grt_pipeline.c's. */
+ * weight and bin edges of a call kept on the device until a call brings other ones, the launches (k_kdist.hip).  The
+ * pipeline entry points themselves, which run the gas optics in front of the reduction, are grt_pipeline.c's;
+ * grt_pipeline_run_ck_fluxes takes its map and its mapped reduction from here too (grt_kdist_reduce_ck). */
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -230,6 +231,24 @@ int grt_kdist_reduce_correlated(Device_t device, GrtKdistTable *t, fp_t const *t
     GRT_TRY(launch_map(device, doubles, tau_dev, groups, rows_per_group, n, key_row, num_classes, map_dev));
     GRT_TRY(launch_mapped(device, tau_dev, rows_per_group*n, map_dev, groups, rows_per_group, n, dw, num_classes,
                           nw > 0 ? doubles + ne : NULL, (int const *)(doubles + ne + nw), band));
+    return GRTCODE_SUCCESS;
+}
+
+int grt_kdist_reduce_ck(Device_t device, GrtKdistTable *t, fp_t const *tau_dev, long long groups, long long rows_per_group,
+                        long long n, fp_t dw, int num_classes, fp_t const *class_edges, long long key_row,
+                        unsigned short const *map_given_dev, unsigned short *map_dev, GrtKdistBand_t const *band,
+                        int const **edges_dev)
+{
+    size_t const ne = class_edges != NULL ? (size_t)num_classes - 1 : 0;
+    GRT_TRY(kdist_table(device, t, class_edges, ne, NULL, 0, band->edges, (size_t)band->num_bins));
+    double const *doubles = t->block;
+    *edges_dev = (int const *)(doubles + ne);
+    if (map_given_dev == NULL)
+    {
+        GRT_TRY(launch_map(device, doubles, tau_dev, groups, rows_per_group, n, key_row, num_classes, map_dev));
+    }
+    GRT_TRY(launch_mapped(device, tau_dev, rows_per_group*n, map_given_dev != NULL ? map_given_dev : map_dev, groups,
+                          rows_per_group, n, dw, num_classes, NULL, *edges_dev, band));
     return GRTCODE_SUCCESS;
 }
 

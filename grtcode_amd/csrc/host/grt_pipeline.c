@@ -359,8 +359,10 @@ static int check_lane(GrtPipeline_t const *p)
 }
 
 /* What grt_pipeline_run and grt_pipeline_run_profiles check and stage alike: the arguments, the lane, and the small
-   per-column inputs, uploaded to small.d on the library stream.  own_sun: the run brings its sun angles itself
-   (grt_pipeline_run_zeniths), and the columns' cos_zenith is not read. */
+   per-column inputs, uploaded to small.d on the library stream.  own_sun 1: the run brings its sun angles itself
+   (grt_pipeline_run_zeniths), and the columns' cos_zenith is not read; GRT_SUN_MAY_BE_DOWN: cos_zenith is read and a
+   column may be a night column (grt_pipeline_run_ck_fluxes, whose solver leaves zeros there). */
+#define GRT_SUN_MAY_BE_DOWN 2
 static int stage_columns(GrtPipeline_t *p, GrtColumns_t const *cols, int own_sun)
 {
     GRT_REQUIRE_RANGE(cols->ncol, 1, p->max_cols);
@@ -405,9 +407,17 @@ static int stage_columns(GrtPipeline_t *p, GrtColumns_t const *cols, int own_sun
     if (p->band[1].gas != NULL)
     {
         GRT_REQUIRE_PTR(cols->total_solar_irradiance);
-        if (!own_sun)
+        if (own_sun != 1)
         {
             GRT_REQUIRE_PTR(cols->cos_zenith);
+        }
+        for (int c = 0; c < C && own_sun == GRT_SUN_MAY_BE_DOWN; ++c)
+        {
+            /* (a NaN fails the comparison) */
+            if (!(cols->cos_zenith[c] <= 1.))
+            {
+                GRT_FAIL(GRTCODE_RANGE_ERR, "cosine of zenith angle (%e) of column %d above 1.", cols->cos_zenith[c], c);
+            }
         }
         for (int c = 0; c < C && !own_sun; ++c)
         {
@@ -417,7 +427,7 @@ static int stage_columns(GrtPipeline_t *p, GrtColumns_t const *cols, int own_sun
                          " (night columns are skipped by the caller: driver.c:706).", cols->cos_zenith[c], c);
             }
         }
-        if (!own_sun)
+        if (own_sun != 1)
         {
             memcpy(p->small.h + p->off_mu, cols->cos_zenith, sizeof(double)*(size_t)C);
         }
@@ -1422,6 +1432,110 @@ EXTERN int grt_pipeline_run_kdist_correlated(GrtPipeline_t *p, GrtColumns_t cons
     }
     GrtKdistKey_t const *const by_band[2] = {&keys->lw, &keys->sw};
     return run_kdist(p, cols, kd, by_band);
+}
+
+/* grt_ext.h: the fluxes of the correlated-k model on its g-classes.  Per band that has bins: run_kdist's gas optics, map
+   and mapped reduction (grt_kdist.c), with the caller's map in place of the key's where one is given and pipeline scratch
+   in place of the outputs the caller does not take; then the source sums, the solve and the bin sums
+   (grt_pipeline_solve.c). */
+EXTERN int grt_pipeline_run_ck_fluxes(GrtPipeline_t *p, GrtColumns_t const *cols, GrtCkFluxes_t const *ck)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    if (ck == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "no correlated-k inputs (GrtCkFluxes_t is NULL).%s", "");
+    }
+    GrtCkBand_t const *cb[2] = {&ck->lw, &ck->sw};
+    if (ck->class_edges != NULL)
+    {
+        GRT_TRY(grt_kdist_check_classes(ck->num_classes, ck->class_edges));
+    }
+    else if (ck->num_classes < 2 || ck->num_classes > GRT_KDIST_MAX_CLASSES)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d classes asked for: 2 to %d.", ck->num_classes, GRT_KDIST_MAX_CLASSES);
+    }
+    long long const L = p->num_levels - 1;
+    long long key_row[2] = {0, 0};
+    for (int bi = 0; bi < 2; ++bi)
+    {
+        char const *name = bi == 0 ? "longwave" : "shortwave";
+        GrtCkBand_t const *c = cb[bi];
+        GRT_TRY(check_bins(p, bi, c->edges, c->num_bins, c->flux_up_dev != NULL && c->flux_down_dev != NULL ? c->flux_up_dev : NULL));
+        if (c->num_bins == 0)
+        {
+            continue;
+        }
+        if ((c->bin_up_dev != NULL) != (c->bin_down_dev != NULL))
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "%s %s is NULL and the other is not: both bin sums or neither.", name,
+                     c->bin_up_dev == NULL ? "bin_up_dev" : "bin_down_dev");
+        }
+        if (c->map_given_dev == NULL)
+        {
+            if (ck->class_edges == NULL)
+            {
+                GRT_FAIL(GRTCODE_VALUE_ERR, "class_edges is NULL and the %s band is given no map: the class edges classify "
+                         "its key.", name);
+            }
+            GRT_TRY(grt_kdist_check_key(name, c->key.kind, c->key.layer, L, &key_row[bi]));
+        }
+    }
+    if (ck->lw.num_bins + ck->sw.num_bins == 0)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "no bins in either band: nothing to write.%s", "");
+    }
+    GRT_TRY(check_two_levels(p));
+    GRT_TRY(check_columns(p, cols));
+    GRT_TRY(check_lane(p));
+    /* (the sun angles are read where the shortwave is solved, and a night column is solved to zeros) */
+    GRT_TRY(stage_columns(p, cols, ck->sw.num_bins > 0 ? GRT_SUN_MAY_BE_DOWN : 1));
+    for (int bi = 0; bi < 2; ++bi)
+    {
+        GrtBand *b = &p->band[bi];
+        GrtCkBand_t const *c = cb[bi];
+        if (c->num_bins == 0)
+        {
+            continue;                  /* (a band without bins is not computed: its line list is not touched) */
+        }
+        size_t const classes = (size_t)p->max_cols*(size_t)c->num_bins*(size_t)ck->num_classes;
+        size_t const source_rows = bi == 0 ? 2*(size_t)p->num_levels + 1 : 4;
+        unsigned short *map = c->key.map_dev;
+        if (c->map_given_dev == NULL && map == NULL)
+        {
+            GrtScratch *own = &b->scratch[GRT_SCRATCH_KDIST_MAP];
+            GRT_TRY(grt_scratch_need(p, own, ((size_t)p->max_cols*b->n + 3)/4, NULL));
+            map = (unsigned short *)own->d;
+        }
+        double *weight = c->weight_dev, *tau = c->tau_dev, *source = c->source_dev;
+        if (weight == NULL)
+        {
+            GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_CK_WEIGHT], classes, NULL));
+            weight = b->scratch[GRT_SCRATCH_CK_WEIGHT].d;
+        }
+        if (tau == NULL)
+        {
+            GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_CK_TAU], classes*(size_t)L, NULL));
+            tau = b->scratch[GRT_SCRATCH_CK_TAU].d;
+        }
+        if (source == NULL)
+        {
+            GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_CK_SOURCE], classes*source_rows, NULL));
+            source = b->scratch[GRT_SCRATCH_CK_SOURCE].d;
+        }
+        /* the whole of tau, the spectral tables' part included (band_gas_optics leaves that to a solver) */
+        GRT_TRY(grt_optical_depth_batch(b->gas, cols, b->tau_gas));
+        b->tau_gas_lacks_tables = 0;
+        b->last_cols = cols->ncol;
+        GrtKdistBand_t const sums = {.edges = c->edges, .num_bins = c->num_bins, .points_dev = c->points_dev,
+                                     .weight_dev = weight, .tau_dev = tau};
+        int const *edges_dev;
+        GRT_TRY(grt_kdist_reduce_ck(p->device, &b->kdist_table, b->tau_gas, cols->ncol, L, (long long)b->n, b->gas->grid.dw,
+                                    ck->num_classes, ck->class_edges, key_row[bi], c->map_given_dev, map, &sums, &edges_dev));
+        GRT_TRY(grt_band_solve_ck(p, b, bi, cols->ncol, ck->num_classes, edges_dev,
+                                  c->map_given_dev != NULL ? c->map_given_dev : map, weight, tau, source, c));
+    }
+    return GRTCODE_SUCCESS;
 }
 
 EXTERN int grt_pipeline_run_spectral(GrtPipeline_t *p, GrtColumns_t const *cols, GrtClouds_t const *cl,

@@ -95,6 +95,12 @@ enum
     /* grt_pipeline_run_kdist_correlated without a map_dev of the caller's: the band's class map, [max_cols][n] unsigned
        shorts (in doubles, rounded up) */
     GRT_SCRATCH_KDIST_MAP,
+    /* grt_pipeline_run_ck_fluxes, what the caller takes no copy of: the class weights [max_cols][bins][K], the class sums of
+       tau [max_cols][L][bins][K] and of the sources [max_cols][2 V + 1 or 4][bins][K]; each replaced when a call's bins x K
+       need more (its map: GRT_SCRATCH_KDIST_MAP) */
+    GRT_SCRATCH_CK_WEIGHT,
+    GRT_SCRATCH_CK_TAU,
+    GRT_SCRATCH_CK_SOURCE,
     GRT_SCRATCH_COUNT
 };
 
@@ -311,8 +317,19 @@ GRT_PRIVATE int grt_kdist_reduce_correlated(Device_t device, GrtKdistTable *t, f
                                             long long rows_per_group, long long n, fp_t dw, int num_classes,
                                             fp_t const *class_edges, long long key_row, unsigned short *map_dev,
                                             GrtKdistBand_t const *band);
+/* ... grt_pipeline_run_ck_fluxes' form of it: the class edges may be NULL (none on the device), a given map takes the
+   place of the key's (no map kernel, map_dev not written), no weight; *edges_dev: the bin edges on the device */
+GRT_PRIVATE int grt_kdist_reduce_ck(Device_t device, GrtKdistTable *t, fp_t const *tau_dev, long long groups,
+                                    long long rows_per_group, long long n, fp_t dw, int num_classes,
+                                    fp_t const *class_edges, long long key_row, unsigned short const *map_given_dev,
+                                    unsigned short *map_dev, GrtKdistBand_t const *band, int const **edges_dev);
 
 /* grt_pipeline_solve.c */
+/* the source sums, the solve and the bin sums of grt_pipeline_run_ck_fluxes for one band, on the class weights and class
+   sums of tau the mapped reduction left at weight_sum, tau_sum */
+GRT_PRIVATE int grt_band_solve_ck(GrtPipeline_t *p, GrtBand *b, int bi, int C, int num_classes, int const *edges_dev,
+                                  unsigned short const *map_dev, double const *weight_sum, double const *tau_sum,
+                                  double *source_sum, GrtCkBand_t const *out);
 GRT_PRIVATE int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps);
 GRT_PRIVATE int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S, GrtPass const *ps);
 GRT_PRIVATE int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass const *ps,

@@ -1000,3 +1000,61 @@ int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass c
     GRT_TRY(grt_dev_check(mrc, "zenith mean kernel"));
     return GRTCODE_SUCCESS;
 }
+
+/* grt_pipeline_run_ck_fluxes, one band: the class sums of the sources under the map (k_kdist.hip), the solve of every
+   g-point on the class means (k_longwave.hip / k_shortwave.hip: the solvers' own layer steps) and the classes' sum per bin.
+   The temperatures, the surface in force, the sun and the solar curve are the ones the band's line-by-line solver reads. */
+int grt_band_solve_ck(GrtPipeline_t *p, GrtBand *b, int bi, int C, int num_classes, int const *edges_dev,
+                      unsigned short const *map_dev, double const *weight_sum, double const *tau_sum, double *source_sum,
+                      GrtCkBand_t const *out)
+{
+    void *s = grt_dev_stream(p->device);
+    int const V = p->num_levels;
+    GrtPass ps;
+    memset(&ps, 0, sizeof(ps));
+    GrtCkSourceArgs src;
+    memset(&src, 0, sizeof(src));
+    src.longwave = bi == 0; src.num_levels = V; src.ncol = C; src.n = (long long)b->n;
+    src.w0 = b->gas->grid.w0; src.dw = b->gas->grid.dw;
+    src.num_classes = num_classes; src.num_bins = out->num_bins; src.edges = edges_dev; src.map = map_dev;
+    src.source_sum = source_sum;
+    GrtCkSolveArgs a;
+    memset(&a, 0, sizeof(a));
+    a.num_levels = V; a.ncol = C; a.num_bins = out->num_bins; a.num_classes = num_classes;
+    a.weight_sum = weight_sum; a.tau_sum = tau_sum; a.source_sum = source_sum;
+    a.flux_up = out->flux_up_dev; a.flux_down = out->flux_down_dev;
+    if (bi == 0)
+    {
+        GrtLwArgs lw;
+        lw_args(p, b, C, 1, &ps, &lw);
+        src.t_levels = lw.t_levels; src.t_layers = lw.t_layers; src.t_surf = lw.t_surf;
+        src.data[0] = lw.emis; src.data_stride[0] = lw.emis_stride;
+    }
+    else
+    {
+        GrtSwArgs sw;
+        sw_args(p, b, C, 1, &ps, &sw);
+        src.data[0] = sw.solar; src.data_stride[0] = 0;
+        src.data[1] = sw.alb_dir; src.data_stride[1] = sw.alb_stride;
+        src.data[2] = sw.alb_dif; src.data_stride[2] = sw.alb_stride;
+        a.n_layer = sw.n_layer; a.mu_dir = sw.mu_dir; a.tsi = sw.tsi; a.mu_dif = sw.mu_dif;
+    }
+    int slot = grt_profile_begin(s, GRT_TAG_CK_SOURCES);
+    int krc = grt_launch_ck_sources(s, &src);
+    grt_profile_end(s, slot);
+    GRT_TRY(grt_dev_check(krc, "correlated-k source kernel"));
+    slot = grt_profile_begin(s, bi == 0 ? GRT_TAG_CK_LW : GRT_TAG_CK_SW);
+    krc = bi == 0 ? grt_launch_ck_lw(s, &a) : grt_launch_ck_sw(s, &a);
+    if (krc == 0 && out->bin_up_dev != NULL)
+    {
+        long long const rows = (long long)C*V*out->num_bins;
+        krc = grt_launch_ck_bin_sum(s, out->flux_up_dev, rows, num_classes, out->bin_up_dev);
+        if (krc == 0)
+        {
+            krc = grt_launch_ck_bin_sum(s, out->flux_down_dev, rows, num_classes, out->bin_down_dev);
+        }
+    }
+    grt_profile_end(s, slot);
+    GRT_TRY(grt_dev_check(krc, bi == 0 ? "correlated-k longwave kernel" : "correlated-k shortwave kernel"));
+    return GRTCODE_SUCCESS;
+}

@@ -54,3 +54,22 @@ def correlated_k_of_g(weight, tau, g_edges):
     if t.ndim != w.ndim + 1 or t.ndim < 3 or t.shape[:-3] != w.shape[:-2] or t.shape[-2:] != w.shape[-2:]:
         raise ValueError(f"weight {w.shape} is not tau {t.shape} without its row axis")
     return k_of_g(np.broadcast_to(w[..., None, :, :], t.shape), t, g_edges)
+
+
+def ck_means(weight, tau, source):
+    """The class means a correlated-k flux solve works on (Pipeline.run_ck_fluxes / ck_fluxes; grt_ext.h:
+    grt_pipeline_run_ck_fluxes): weight [..., bins, K] -> (tau_mean [..., L, bins, K], source_mean [..., R, bins, K]), each
+    class sum divided by its class weight, 0 where the weight is 0 (a class of no points, which the solver skips).  The
+    longwave's source rows are then the Planck function per cm-1 at the levels, the layers and the surface and the
+    emissivity of each g-point; the shortwave's row 1, the solar curve, goes into the solver as its sum, not its mean."""
+    w = np.asarray(weight, dtype=np.float64)
+    out = []
+    for x in (tau, source):
+        x = np.asarray(x, dtype=np.float64)
+        if x.ndim != w.ndim + 1 or x.ndim < 3 or x.shape[:-3] != w.shape[:-2] or x.shape[-2:] != w.shape[-2:]:
+            raise ValueError(f"weight {w.shape} is not {x.shape} without its row axis")
+        wb = np.broadcast_to(w[..., None, :, :], x.shape)
+        mean = np.zeros(x.shape)
+        np.divide(x, wb, out=mean, where=wb > 0.0)
+        out.append(mean)
+    return tuple(out)

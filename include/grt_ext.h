@@ -861,6 +861,69 @@ typedef struct GrtKdistKeys
 EXTERN int grt_pipeline_run_kdist_correlated(GrtPipeline_t *pipeline, GrtColumns_t const *columns,
                                              GrtKdist_t const *kdist, GrtKdistKeys_t const *keys);
 
+/* ---- flux solves of a correlated-k model on its g-classes -------------------------------------------------------------------
+ * The other half of the loop: the clear-clean fluxes of the band model that the class map defines, every level, per
+ * (bin, class) and per bin, next to grt_pipeline_run_band_profiles' line-by-line bins of the same columns.  Per band,
+ * column c, bin b with points i = edges[b] .. edges[b + 1], w_i = dw (0.5 dw at the bin's two ends), v_i = w0 + i dw as
+ * the solvers form it, class k = the bin's points with map[c][i] == k.  Every sum below is the mapped reduction's: left to
+ * right in grid order from +0.0, each product rounded before it is added, no atomics, no tree, nothing contracted.  No
+ * spectral weight.
+ *   map, W, T  exactly grt_pipeline_run_kdist_correlated's: the map of the band's key over tau_gas -- or map_given_dev,
+ *              used as is, the key ignored --, W[c][b][k] = sum w_i, T[c][l][b][k] = sum fl(w_i tau_i), grt_kdist_mapped_rows'
+ *              bits.
+ *   sources    sum fl(w_i x_i) per class, [ncol][R][bins][K].  Longwave, R = 2 V + 1: rows 0 .. V - 1 x = B(t_levels[c][v],
+ *              v_i), rows V .. 2 V - 2 x = B(t_layers[c][l], v_i), row 2 V - 1 x = B(t_surf[c], v_i), B the longwave
+ *              solver's own Planck function; row 2 V x = the emissivity in force at the point.  Shortwave, R = 4: row 0 the
+ *              Rayleigh optical depth of one molecule per cm2 (the solvers' expression with n = 1), row 1 the solar
+ *              curve, rows 2 and 3 the direct and the diffuse albedo in force.  The data rows are grt_kdist_mapped_rows of
+ *              those rows, bit for bit; the Rayleigh row has no transcendental and is reproduced by a host restatement bit
+ *              for bit.
+ *   the solve  one g-point per (c, b, k) with W > 0.  Longwave: t_l = T[l]/W (gas only, omega = 0), the Planck terms and
+ *              the emissivity row/W, then the longwave solver's two sweeps, operation for operation; the result per cm-1
+ *              is multiplied by W last.  Shortwave: t_gas = T[l]/W, t_ray = fl(n_layer[c][l] row0)/W, combined as the
+ *              clear-sky optics combine them, the layer's delta-Eddington properties with the column's cos_zenith and
+ *              the diffuse cosine 0.5, the reference's two sweeps with the albedos row2/W, row3/W; scaled by row1
+ *              cos_zenith, then by the column's total solar irradiance: the flux is linear in the solar term, so the class
+ *              SUM of the solar curve goes in.  flux_up_dev, flux_down_dev [ncol][V][bins][K]: W m-2 per class.  A class of
+ *              no points gives +0.0 at every level and solves nothing; so does, in the shortwave, a column with cos_zenith
+ *              <= 0 (night columns are allowed in this call: cos_zenith <= 1 is all that is asked).
+ *   bin sums   bin_up_dev, bin_down_dev [ncol][V][bins]: (((+0.0 + f[0]) + f[1]) + ...) + f[K - 1] over the classes.
+ * What runs, asynchronously on the pipeline's lane, per band that has bins: the whole gas optics as grt_pipeline_run_kdist
+ * runs it; the map kernel (GRT_TAG_KDIST_MAP) unless a map is given; the mapped reduction (GRT_TAG_KDIST_MAPPED); the source
+ * sums (GRT_TAG_CK_SOURCES), the mapped kernel with the row's value computed at the point; the solve, one thread per
+ * (column, bin, class), and behind it the bin sums where asked for (GRT_TAG_CK_LW / GRT_TAG_CK_SW, one bracket).  No
+ * line-by-line solver, Rayleigh or clear-sky optics kernel runs; a band without bins is not computed at all; a following
+ * grt_pipeline_views shows the tau_gas that was reduced.  Whatever of weight_dev, tau_dev, source_dev and the map the caller
+ * leaves NULL lives in pipeline scratch (max_columns bins K (1 + L + R) doubles and max_columns n shorts per band),
+ * allocated at the first call that needs it, freed with the pipeline.  Class edges and bin edges share
+ * grt_pipeline_run_kdist's per-band block: the same classes and bins again cost a comparison.  The class edges classify
+ * the key only: with a map given in every band that has bins, class_edges may be NULL.  A given map's entry >= K belongs
+ * to no class, is counted nowhere and indexes nothing.
+ * GRTCODE_VALUE_ERR, with nothing launched and the outputs untouched, for: everything grt_pipeline_run_kdist_correlated
+ * refuses in classes, edges, bins, key, counts and lane; a NULL ck; no bins in either band; bins for a band whose gas-optics
+ * object is NULL; a band with bins and flux_up_dev or flux_down_dev NULL; one of bin_up_dev, bin_down_dev without the other;
+ * class_edges NULL while a band with bins has no given map. */
+typedef struct GrtCkBand
+{
+    int const *edges;                      /* HOST [num_bins + 1], as grt_pipeline_run_kdist's; NULL / 0: band not computed */
+    int num_bins;
+    GrtKdistKey_t key;                     /* kind, layer, map_dev (DEVICE out [ncol][n], or NULL: pipeline scratch) */
+    unsigned short const *map_given_dev;   /* DEVICE [ncol][n] or NULL; given: used as is, key ignored, map_dev not written */
+    int *points_dev;                       /* DEVICE [ncol][num_bins][K], or NULL */
+    fp_t *weight_dev;                      /* DEVICE [ncol][num_bins][K], or NULL */
+    fp_t *tau_dev;                         /* DEVICE [ncol][L][num_bins][K], or NULL */
+    fp_t *source_dev;                      /* DEVICE [ncol][R][num_bins][K], or NULL (R = 2 V + 1 longwave, 4 shortwave) */
+    fp_t *flux_up_dev, *flux_down_dev;     /* DEVICE [ncol][V][num_bins][K]; both required for a band with bins */
+    fp_t *bin_up_dev, *bin_down_dev;       /* DEVICE [ncol][V][num_bins], or NULL (both or neither) */
+} GrtCkBand_t;
+typedef struct GrtCkFluxes
+{
+    int num_classes;                       /* K: 2 .. GRT_KDIST_MAX_CLASSES */
+    fp_t const *class_edges;               /* HOST [K - 1], or NULL where every band with bins is given its map */
+    GrtCkBand_t lw, sw;
+} GrtCkFluxes_t;
+EXTERN int grt_pipeline_run_ck_fluxes(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtCkFluxes_t const *ck);
+
 /* ---- per-column surface emissivity and albedo ----------------------------------------------------------------------
  * driver.c:101-117: each column's own surface emissivity and albedo, given on coarse wavenumber grids of NS points shared
  * by the columns and put on the band's grid as interpolate_to_grid(grid, x, y, NS, out, linear_sample,
@@ -1084,7 +1147,13 @@ enum
     /* 30 = the class-map kernel of grt_kdist_class_map and grt_pipeline_run_kdist_correlated; 31 = the mapped reduction of
        grt_kdist_mapped_rows and grt_pipeline_run_kdist_correlated (the latter's gas optics counts under 1 / 2 and 6 / 7) */
     GRT_TAG_KDIST_MAP = 30,
-    GRT_TAG_KDIST_MAPPED = 31
+    GRT_TAG_KDIST_MAPPED = 31,
+    /* 32 = the source sums of grt_pipeline_run_ck_fluxes (one launch per band that has bins); 33 / 34 = its LW / SW solve on
+       the g-classes with the bin sums behind it (its gas optics counts under 1 / 2 and 6 / 7, its map and its mapped
+       reduction under 30 and 31) */
+    GRT_TAG_CK_SOURCES = 32,
+    GRT_TAG_CK_LW = 33,
+    GRT_TAG_CK_SW = 34
 };
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
