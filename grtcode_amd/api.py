@@ -30,11 +30,14 @@ GRT_CLOUD_PHASE, GRT_CLOUD_MODEL, GRT_CLOUD_FIELDS = 7, 8, 9   # ... of GrtCloud
  TAG_ALLSKY_SW, TAG_BINS, TAG_SUBCOLUMN_MEAN, TAG_AEROSOL_LW, TAG_AEROSOL_SW, TAG_BAND_PROFILES, TAG_SURFACE,
  TAG_CLOUD_SAMPLER, TAG_SKY_LW, TAG_SKY_SW, TAG_ZENITH_SW, TAG_ZENITH_MEAN, TAG_DIRECT_BEAM, TAG_SKY_ZENITH_SW,
  TAG_SKY_ZENITH_MEAN, TAG_SURFACE_JACOBIAN, TAG_RADIANCE, TAG_CHANNELS, TAG_WEIGHTING, TAG_WEIGHTING_FINISH,
- TAG_KDIST, TAG_KDIST_MAP, TAG_KDIST_MAPPED, TAG_CK_SOURCES, TAG_CK_LW, TAG_CK_SW) = range(1, 35)
+ TAG_KDIST, TAG_KDIST_MAP, TAG_KDIST_MAPPED, TAG_CK_SOURCES, TAG_CK_LW, TAG_CK_SW, TAG_TILE_LW, TAG_TILE_SW,
+ TAG_TILE_MEAN) = range(1, 38)
 TAG_FAR_OFFSET = TAG_FAR_LW - TAG_GAS_LW    # from a line kernel's tag to its far-field gather's
 CLOUD_SAMPLER_TAG = TAG_CLOUD_SAMPLER
 GRT_MAX_SUBCOLUMNS = 64             # grt_pipeline_run_subcolumns: subcolumns per column, 1 .. this
 GRT_MAX_ZENITHS = 64                # grt_pipeline_run_zeniths: sun angles per column, 1 .. this
+GRT_MAX_TILES = 16                  # grt_pipeline_run_sky_tiles: surface tiles per column, 1 .. this
+GRT_TILE_CHUNK = 4                  # csrc/grt_kernels.h: the tiles one thread of the tile kernels carries (every instance's)
 GRT_ZENITH_CHUNK = 4                # csrc/grt_kernels.h: the angles one thread of the shared-layer shortwave kernel carries
 # grt_pipeline_run_sky's sets: clean (always formed), + aerosol, + clouds, + aerosol and clouds; packed in bit order
 GRT_SKY_CLEAN, GRT_SKY_AEROSOL, GRT_SKY_CLOUD, GRT_SKY_CLOUD_AEROSOL = 1, 2, 4, 8
@@ -243,6 +246,13 @@ class GrtZeniths(C.Structure):
                 ("zenith_fluxes_dev", C.c_void_p), ("zenith_level_fluxes_dev", C.c_void_p)]
 
 
+class GrtSurfaceTiles(C.Structure):
+    _fields_ = [("num_tiles", C.c_int), ("fraction", c_double_p), ("surface_temperature", c_double_p),
+                ("num_emissivity_points", C.c_int), ("num_albedo_points", C.c_int),
+                ("emissivity_grid", c_double_p), ("albedo_grid", c_double_p), ("emissivity", c_double_p),
+                ("direct_albedo", c_double_p), ("diffuse_albedo", c_double_p), ("tile_fluxes_dev", C.c_void_p)]
+
+
 class GrtSurface(C.Structure):
     _fields_ = [("ncol", C.c_int), ("emissivity_num_points", C.c_int), ("albedo_num_points", C.c_int),
                 ("emissivity_grid", c_double_p), ("albedo_grid", c_double_p), ("emissivity", c_double_p),
@@ -264,7 +274,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_channels grt_channel_pair_count grt_pipeline_run_sky_weighting grt_pipeline_run_sky_zeniths grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_kdist_rows grt_pipeline_run_kdist grt_kdist_chunk_points grt_kdist_class_map grt_kdist_mapped_rows grt_pipeline_run_kdist_correlated grt_pipeline_run_ck_fluxes grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_channels grt_channel_pair_count grt_pipeline_run_sky_weighting grt_pipeline_run_sky_zeniths grt_pipeline_run_sky_tiles grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_kdist_rows grt_pipeline_run_kdist grt_kdist_chunk_points grt_kdist_class_map grt_kdist_mapped_rows grt_pipeline_run_kdist_correlated grt_pipeline_run_ck_fluxes grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_voigt_points grt_debug_device_math grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -360,6 +370,9 @@ def load_library(path=None):
     if hasattr(lib, "grt_pipeline_run_sky_zeniths"):
         lib.grt_pipeline_run_sky_zeniths.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky),
                                                      C.POINTER(GrtZeniths), C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "grt_pipeline_run_sky_tiles"):
+        lib.grt_pipeline_run_sky_tiles.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky),
+                                                   C.POINTER(GrtSurfaceTiles), C.c_void_p]
     lib.grt_pipeline_set_surface.argtypes = [C.c_void_p, C.POINTER(GrtSurface)]
     lib.grt_multi_gather_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.grt_pipeline_sync.argtypes = [C.c_void_p]
@@ -826,6 +839,47 @@ def make_surface(ncol, emissivity=None, albedo=None):
     gs = GrtSurface(keep["ncol"], *keep["num_points"], *[_opt_dp(keep[k]) for k in (
         "emissivity_grid", "albedo_grid", "emissivity", "direct_albedo", "diffuse_albedo")])
     return gs, keep
+
+
+def make_surface_tiles(ncol, t_surf, fraction=None, emissivity=None, albedo=None):
+    """Pack the surface tiles of a batch into a GrtSurfaceTiles struct (+ keep-alive arrays) for Pipeline.run_sky_tiles.
+    t_surf [ncol][T] K (None only for a pipeline without a longwave band: then T comes from the other arrays); fraction
+    [ncol][T] or None: the plain mean over the tiles.  emissivity: (grid, values) -- grid [NS], values [ncol][T][NS] -- or
+    None: every tile takes the surface in force in the longwave.  albedo: (grid, direct) or (grid, direct, diffuse), each
+    of values' shape, or None.  The per-tile output pointer is Pipeline.run_sky_tiles' to set.  keep["shape"] is
+    (ncol, T)."""
+    keep = {"t_surf": None if t_surf is None else _f64(t_surf), "fraction": None if fraction is None else _f64(fraction),
+            "num_points": [0, 0]}
+    for k in ("emissivity_grid", "albedo_grid", "emissivity", "direct_albedo", "diffuse_albedo"):
+        keep[k] = None
+    shapes = [keep[k].shape for k in ("t_surf", "fraction") if keep[k] is not None]
+    for band, (name, given, arrays) in enumerate((("emissivity", emissivity, ("emissivity",)),
+                                                  ("albedo", albedo, ("direct_albedo", "diffuse_albedo")))):
+        if given is None:
+            continue
+        grid = _f64(given[0])
+        if grid.ndim != 1 or grid.size < 2:
+            raise ValueError(f"{name} grid of {grid.size} point(s): at least 2")
+        keep[name + "_grid"] = grid
+        keep["num_points"][band] = grid.size
+        for k, v in zip(arrays, given[1:]):
+            if v is None:
+                continue
+            keep[k] = _f64(v)
+            if keep[k].ndim != 3 or keep[k].shape[2] != grid.size:
+                raise ValueError(f"{k} of shape {keep[k].shape}: [ncol][T][{grid.size}]")
+            shapes.append(keep[k].shape[:2])
+        if keep[arrays[0]] is None:
+            raise ValueError(f"{name} grid without values")
+    if not shapes or any(len(sh) != 2 or sh != shapes[0] or sh[0] != int(ncol) for sh in shapes):
+        raise ValueError(f"tile arrays of shapes {shapes}: all [{int(ncol)}][T]")
+    keep["shape"] = tuple(shapes[0])
+    keep["num_points"] = tuple(keep["num_points"])
+    gt = GrtSurfaceTiles(keep["shape"][1], _opt_dp(keep["fraction"]), _opt_dp(keep["t_surf"]), *keep["num_points"],
+                         *[_opt_dp(keep[k]) for k in ("emissivity_grid", "albedo_grid", "emissivity", "direct_albedo",
+                                                      "diffuse_albedo")], None)
+    gt.keep = keep             # (as make_cloud_model)
+    return gt, keep
 
 
 def make_zeniths(cos_zenith, weight=None):
@@ -1539,6 +1593,23 @@ class Pipeline:
         out["angle_fluxes"] = self.buffers["zenith_profiles.angles"].to_host((ncol, Z, 6))
         out["angle_up"], out["angle_down"] = lv[:, :, 0].copy(), lv[:, :, 1].copy()
         return out
+
+    def run_sky_tiles(self, gcols, gsky, gtiles):
+        """grt_pipeline_run_sky_tiles: the sets gsky (make_sky) asks for, six rows, over gtiles' (make_surface_tiles)
+        surfaces per column, into this object's device buffers: every tile's twelve rows of every set and their mean
+        (sky_tile_fluxes() reads both)."""
+        nsets = max(sky_set_count(gsky.sets), 1)
+        T, n = max(gtiles.num_tiles, 1), self.max_columns
+        gtiles.tile_fluxes_dev = self._buffer("sky_tiles.tiles", 8 * n * nsets * T * GRT_FLUXES_PER_COLUMN).ptr
+        out = self._buffer("sky_tiles", 8 * n * nsets * GRT_FLUXES_PER_COLUMN).ptr
+        check(self.lib.grt_pipeline_run_sky_tiles(self.p, C.byref(gcols), C.byref(gsky), C.byref(gtiles), out))
+
+    def sky_tile_fluxes(self, ncol, nsets, T):
+        """The last run_sky_tiles of nsets sets and T tiles: (fluxes [ncol][nsets][12], sky_fluxes()' layout, the mean over
+        the tiles; tiles [ncol][nsets][T][12], every tile's own rows)."""
+        self.sync()
+        return (self.buffers["sky_tiles"].to_host((ncol, nsets, GRT_FLUXES_PER_COLUMN)),
+                self.buffers["sky_tiles.tiles"].to_host((ncol, nsets, T, GRT_FLUXES_PER_COLUMN)))
 
     def run_sky_zeniths(self, gcols, gsky, gzeniths, profiles=False):
         """grt_pipeline_run_sky_zeniths: the sets gsky (make_sky) asks for, the shortwave of each under gzeniths'

@@ -489,6 +489,55 @@ int grt_launch_sky_zenith_mean(void *stream, double const *partials, int ncol, i
                                unsigned nblocks, double const *mu, double const *weight, double *per_angle, double *six,
                                int sets, int set, int user_level, double *out, int out_stride, int out_offset);
 
+/* Surface-tile form of the two fused six-row forms (grt_pipeline_run_sky_tiles): `tiles` surfaces per column on the column's
+   one atmosphere.  lw_tile_kernel (k_longwave.hip) and sw_tile_kernel (k_shortwave.hip) take the six-row instance's
+   arguments and, as joins, nothing, a GrtAerosolArgs, a GrtSubcolumnArgs or a GrtAerosolArgs behind a GrtSubcolumnArgs
+   (one draw per column is a GrtSubcolumnArgs of one subcolumn: the same tables, the same doubles).  Grid rows (y) are the
+   instance's -- a column, or (column, draw first + .. of count) --, and blockIdx.z is a chunk of TN consecutive tiles,
+   chunk_first + z: a thread does everything that does not see the surface once -- the longwave's downward sweep and, on
+   the way up, a layer's optical depth, Planck terms and four extinctions; the shortwave's layer properties and whichever
+   of its sweeps carry no albedo -- and the surface's part per tile, each in lw_kernel's / sw_kernel's expressions and
+   order on the same doubles, so every tile's partial sums are, bit for bit, the six-row instance's with that tile's rows
+   and temperature, at the slot (c tiles + t) subcolumns + s.  Tiles past the column's last are skipped by a flag that is
+   uniform per workgroup.  The shortwave takes sw_kernel's rule for one sweep or two; its two-sweep form parks the layer
+   properties in sw_kernel's fused layout at park row z gridDim.y + y (no per-tile rows are parked), so a launch's
+   rows x chunk_count must fit the park block.
+   t_surf: DEVICE [ncol][tiles] (longwave).  rows: DEVICE [ncol][tiles][nw], the tiles' emissivity (longwave) or direct
+   albedo (shortwave) on the band's grid, as grt_launch_spread_surface writes them; NULL: every tile takes the instance's
+   own (a->emis / a->alb_dir, a->alb_dif).  rows_dif: the diffuse albedo, or NULL: the direct one.
+   Each instance carries the most tiles of {2, 4, 8} that leave it three waves per SIMD and no scratch in both bands
+   (DESIGN.md 3.3); grt_tile_chunk names an instance's. */
+typedef struct GrtTileArgs
+{
+    int tiles;                      /* T >= 1 */
+    int chunk_first, chunk_count;   /* the launch's chunks: gridDim.z = chunk_count */
+    double const *t_surf;
+    double const *rows, *rows_dif;
+} GrtTileArgs;
+#define GRT_TILE_CHUNK 4
+#define GRT_TILE_CHUNK_AEROSOLS 4
+#define GRT_TILE_CHUNK_SUBCOLUMNS 4
+#define GRT_TILE_CHUNK_SUBCOLUMNS_AEROSOLS 4
+static inline int grt_tile_args_ok(GrtTileArgs const *t, int chunk)
+{
+    return t != NULL && t->tiles >= 1 && t->chunk_first >= 0 && t->chunk_count >= 1 &&
+           (t->chunk_first + t->chunk_count - 1)*chunk < t->tiles && (t->rows != NULL || t->rows_dif == NULL);
+}
+int grt_tile_chunk(GrtSubcolumnArgs const *sc, GrtAerosolArgs const *ae);
+int grt_launch_lw_tiles(void *stream, GrtLwArgs const *a, GrtTileArgs const *t, GrtSubcolumnArgs const *sc,
+                        GrtAerosolArgs const *ae);
+int grt_launch_sw_tiles(void *stream, GrtSwArgs const *a, GrtTileArgs const *t, GrtSubcolumnArgs const *sc,
+                        GrtAerosolArgs const *ae);
+/* grt_pipeline_run_sky_tiles' mean of one band of one set, in a fixed order: for column c, row r (of 6) and tile t each
+   draw's blocks are added as grt_launch_reduce_partials adds them, the draws s = 0 .. S - 1 in order, then -- S > 1 -- one
+   division by S, as grt_launch_subcolumn_mean does; stored at per_tile[(((c sets + set) tiles + t) 12 + 6 band + r]
+   (NULL: not stored); then the tiles t = 0 .. tiles - 1 in order, each times fraction[c tiles + t], the product rounded
+   before it is added -- fraction NULL: the plain sum, then one division by tiles --, to out[c out_stride + out_offset + r]
+   (NULL: not formed).  One wavefront per (column, row).  tiles = 1 without fractions: grt_launch_subcolumn_mean's bits. */
+int grt_launch_tile_mean(void *stream, double const *partials, int ncol, int tiles, int subcolumns, unsigned nblocks,
+                         double const *fraction, double *per_tile, int sets, int set, int band, double *out,
+                         int out_stride, int out_offset);
+
 /* Direct-beam form of the shortwave's fused six-row and profile forms (direct joined, with any of the cloud and aerosol
    joins or none; grt_pipeline_run_sky_direct): the instance's arguments, sweeps and partial sums, and beside them the
    direct beam of the sweep -- the running product of the layers' T_pure (shortwave.c:306, :323), scaled as the other rows

@@ -23,6 +23,9 @@
 // instance is the production pipeline's.  lw_radiance_kernel, further down, is the radiance at viewing angles beside a
 // pass's solver (grt_launch_lw_radiances): the same recurrence with a stream's c1 replaced by minus the viewing secant;
 // lw_weighting_kernel behind it, the channels' transmittances and contribution functions.
+// lw_tile_kernel, behind the spectral form, is the six-row instance for several surface tiles per column
+// (grt_launch_lw_tiles): one downward sweep and one set of layer terms for a chunk of tiles, the surface and the streams
+// per tile.
 //
 // What these kernels must say alike, to the bit, is said once: LwPoint (a thread's row, point and layer optical depth),
 // absorption_tau (tau (1 - omega) of a materialised pass), AngleChunk (blockIdx.z's viewing angles), stream_step and
@@ -853,6 +856,103 @@ __global__ __launch_bounds__(kSweepBlock) void lw_sweeps_kernel(GrtLwArgs a)
     }
 }
 
+// ---- several surface tiles per column on one walk through the layers (grt_launch_lw_tiles; GrtTileArgs, grt_kernels.h) ----
+// Of lw_kernel<GRT_OUT_ROWS>, the downward sweep does not know the surface, and a layer of the upward sweep is I_s <-
+// (1 - e_s) val + I_s e_s with val and the four e_s the atmosphere's alone.  Grid row y is the six-row instance's (a
+// column, or a column and cloud draw: LwPoint as it is), blockIdx.z a chunk of TN consecutive tiles: the thread makes the
+// downward sweep once, gives each tile of its chunk its own copy of the four streams at the surface -- the tile's
+// emissivity row, planck() of the tile's temperature, surface_step --, and on the way up forms a layer's optical depth, its
+// two Planck terms and its four extinctions once and runs beam_step and the c2 sum per tile, in stream_step's order.
+// Every tile's six rows leave through a LevelSink at the tile's slot (c tiles + t) subcolumns + s: lw_kernel's doubles
+// through lw_kernel's sums.  Tiles past the column's last are skipped by a flag that is uniform per workgroup.
+// the three rows of one direction, as LevelSink::put keeps them (TOA, surface, user level)
+__device__ __forceinline__ void keep_row(double (&three)[3], int lev, int V, int user, double x)
+{
+    three[0] = lev == 0 ? x : three[0];
+    three[1] = lev + 1 == V ? x : three[1];
+    three[2] = lev == user ? x : three[2];
+}
+
+template <int TN, typename... Joins>
+__global__ __launch_bounds__(kSolverBlock) void lw_tile_kernel(GrtLwArgs a, GrtTileArgs tl, Joins... joins)
+{
+    uint64_t const i = (uint64_t)blockIdx.x*kSolverBlock + threadIdx.x;
+    LwPoint<true, Joins...> const p(a, i, joins...);             // (idle lanes of the last block follow along, weight 0)
+    int const L = p.L, V = p.V, T = tl.tiles, user = a.user_level;
+    int const k0 = (tl.chunk_first + (int)blockIdx.z)*TN;
+    double const w = p.w;
+    int S = 1;
+    if constexpr (has<GrtSubcolumnArgs, Joins...>)
+    {
+        S = pick<GrtSubcolumnArgs>(joins...).subcolumns;
+    }
+    int const draw = p.row.slot - p.col*S;
+
+    // the downward sweep, shared by the tiles
+    double down[3] = {0., 0., 0.};                                       // longwave.c:171
+    double I0[4] = {0., 0., 0., 0.};
+    for (int j = 0; j < L; ++j)
+    {
+        double const t = p.layer_tau(j);
+        double const val = effective_planck(planck(p.tl[j], w), planck(p.tv[j + 1], w), t);
+        keep_row(down, j + 1, V, user, stream_step(I0, val, [&](int s) { return extinction(s, t); }));
+    }
+    // the surface of each tile of the chunk, on its own copy of the streams
+    double I[TN][4], up[TN][3];
+#pragma unroll
+    for (int u = 0; u < TN; ++u)
+    {
+        up[u][0] = up[u][1] = up[u][2] = 0.;
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+        {
+            I[u][s] = I0[s];
+        }
+        if (k0 + u < T)
+        {
+            uint64_t const tile = (uint64_t)p.col*T + k0 + u;
+            double const emis = tl.rows != nullptr ? tl.rows[tile*p.nw + p.ii] : p.emis;
+            keep_row(up[u], L, V, user, surface_step(I[u], emis, planck(tl.t_surf[tile], w)));
+        }
+    }
+    for (int j = L - 1; j >= 0; --j)
+    {
+        double const t = p.layer_tau(j);
+        double const val = effective_planck(planck(p.tl[j], w), planck(p.tv[j], w), t);
+        double e[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+        {
+            e[s] = extinction(s, t);
+        }
+#pragma unroll
+        for (int u = 0; u < TN; ++u)
+        {
+            if (k0 + u < T)
+            {
+                keep_row(up[u], j, V, user, stream_step(I[u], val, [&](int s) { return e[s]; }));
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < TN; ++u)
+    {
+        if (k0 + u >= T)
+        {
+            continue;
+        }
+        LevelSink<true, false> sink(a, (p.col*T + k0 + u)*S + draw, i, p.live);
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+        {
+            sink.out[k] = up[u][k];
+            sink.out[3 + k] = down[k];
+        }
+        __syncthreads();                            // (block_partials' LDS is the tile before's: every wave has read it)
+        sink.finish(a);
+    }
+}
+
 // the one launch site of lw_kernel: the instance of OUT and of the joined arguments' types, on the instance's grid and LDS
 template <GrtSolverOutput OUT, typename... Joins>
 int launch(hipStream_t s, GrtSolverInstance const &in, GrtLwArgs const &a, Joins const &...joins)
@@ -892,6 +992,19 @@ int launch_weighting(hipStream_t s, GrtSolverInstance const &in, GrtLwArgs const
     dim3 const grid(grt_solver_blocks(a.nw), (unsigned)grt_solver_grid_rows(&in, a.ncol),
                     (unsigned)((r.angles + kRadianceChunk - 1)/kRadianceChunk));
     hipLaunchKernelGGL((lw_weighting_kernel<FUSED, Joins...>), grid, dim3(kSolverBlock), 0, s, a, r, c, w, joins...);
+    return (int)hipGetLastError();
+}
+
+// ... and of lw_tile_kernel: TN tiles per thread, the six-row instance's grid rows, the launch's chunks along z
+template <int TN, typename... Joins>
+int launch_tiles(hipStream_t s, GrtLwArgs const &a, GrtTileArgs const &t, int draws, Joins const &...joins)
+{
+    if (!grt_tile_args_ok(&t, TN) || t.t_surf == nullptr || (uint64_t)a.ncol*(uint64_t)draws > 65535u || t.chunk_count > 65535)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL((lw_tile_kernel<TN, Joins...>), dim3(grt_solver_blocks(a.nw), (unsigned)(a.ncol*draws), (unsigned)t.chunk_count),
+                       dim3(kSolverBlock), 0, s, a, t, joins...);
     return (int)hipGetLastError();
 }
 
@@ -1081,4 +1194,35 @@ extern "C" int grt_launch_weighting_finish(void *stream, GrtChannelArgs const *c
                        dim3(kChannelFinishBlock), 0, (hipStream_t)stream, *c, *w, ncol, subcolumns, angles, num_levels,
                        transmittance, t_stride, t_offset, contribution, k_stride, k_offset);
     return (int)hipGetLastError();
+}
+
+extern "C" int grt_tile_chunk(GrtSubcolumnArgs const *sc, GrtAerosolArgs const *ae)
+{
+    return sc != nullptr ? (ae != nullptr ? GRT_TILE_CHUNK_SUBCOLUMNS_AEROSOLS : GRT_TILE_CHUNK_SUBCOLUMNS) :
+           (ae != nullptr ? GRT_TILE_CHUNK_AEROSOLS : GRT_TILE_CHUNK);
+}
+
+extern "C" int grt_launch_lw_tiles(void *stream, GrtLwArgs const *a, GrtTileArgs const *t, GrtSubcolumnArgs const *sc,
+                                   GrtAerosolArgs const *ae)
+{
+    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (a == nullptr || t == nullptr || !grt_solver_instance_ok(in, *a) || a->t_layers == nullptr || a->t_levels == nullptr ||
+        a->emis == nullptr || (sc != nullptr && !grt_subcolumn_args_ok(sc)) || (ae != nullptr && !grt_aerosol_args_ok(ae)))
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipStream_t const s = (hipStream_t)stream;
+    if (sc != nullptr && ae != nullptr)
+    {
+        return launch_tiles<GRT_TILE_CHUNK_SUBCOLUMNS_AEROSOLS>(s, *a, *t, sc->count, *sc, *ae);
+    }
+    if (sc != nullptr)
+    {
+        return launch_tiles<GRT_TILE_CHUNK_SUBCOLUMNS>(s, *a, *t, sc->count, *sc);
+    }
+    if (ae != nullptr)
+    {
+        return launch_tiles<GRT_TILE_CHUNK_AEROSOLS>(s, *a, *t, 1, *ae);
+    }
+    return launch_tiles<GRT_TILE_CHUNK>(s, *a, *t, 1);
 }

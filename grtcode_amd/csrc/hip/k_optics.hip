@@ -584,7 +584,56 @@ __global__ __launch_bounds__(64) void sky_zenith_mean_kernel(double const *parti
     }
 }
 
+// grt_pipeline_run_sky_tiles: one band of one set of a column's `sets`, over partial sums that hold S cloud draws per tile
+// (slot (c T + t) S + s).  One wavefront per (column, row of the six): blocks as reduce_partials_kernel adds them, the
+// draws in order and one division by S as subcolumn_mean_kernel's (S = 1: none); the tile's value stored where the set's
+// per-tile rows lie; then the tiles in order, each times its fraction, the product rounded before it is added -- no
+// fractions: the plain sum and one division by T.
+__global__ __launch_bounds__(64) void tile_mean_kernel(double const *partials, int T, int S, unsigned nblocks,
+                                                       double const *fraction, double *per_tile, int sets, int set,
+                                                       int band, double *out, int out_stride, int out_offset)
+{
+    int const c = blockIdx.x/6;
+    int const r = blockIdx.x - c*6;
+    double m = 0.;
+    for (int t = 0; t < T; ++t)
+    {
+        uint64_t const tile = (uint64_t)c*T + t;
+        double x = 0.;
+        for (int s = 0; s < S; ++s)
+        {
+            double const xs = wave_strided_sum(partials + ((tile*S + s)*6 + r)*nblocks, nblocks);
+            x = s == 0 ? xs : x + xs;
+        }
+        x = S > 1 ? x/(double)S : x;
+        if (per_tile != nullptr && threadIdx.x == 0)
+        {
+            per_tile[(((uint64_t)c*sets + set)*T + t)*12 + 6*band + r] = x;
+        }
+        double const term = fraction != nullptr ? fraction[tile]*x : x;
+        m = t == 0 ? term : m + term;
+    }
+    if (out != nullptr && threadIdx.x == 0)
+    {
+        out[(uint64_t)c*out_stride + out_offset + r] = fraction != nullptr ? m : m/(double)T;
+    }
+}
+
 } // namespace
+
+extern "C" int grt_launch_tile_mean(void *stream, double const *partials, int ncol, int tiles, int subcolumns,
+                                    unsigned nblocks, double const *fraction, double *per_tile, int sets, int set, int band,
+                                    double *out, int out_stride, int out_offset)
+{
+    if (ncol < 1 || tiles < 1 || subcolumns < 1 || nblocks < 1 || sets < 1 || set < 0 || set >= sets || band < 0 || band > 1 ||
+        partials == nullptr || (out == nullptr && per_tile == nullptr))
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(tile_mean_kernel, dim3((unsigned)(ncol*6)), dim3(64), 0, (hipStream_t)stream, partials, tiles,
+                       subcolumns, nblocks, fraction, per_tile, sets, set, band, out, out_stride, out_offset);
+    return (int)hipGetLastError();
+}
 
 extern "C" int grt_launch_band_profile_finish(void *stream, int ncol, int sets, int num_levels, int lw_bins, int sw_bins,
                                               double gravity, double cp, double const *pressure, double const *levels,

@@ -24,6 +24,8 @@
 // both join, a GrtBandArgs last where OUT is per bin, or a GrtZenithArgs (several sun angles per column: alone, or last
 // behind a GrtAerosolArgs, a GrtSubcolumnArgs or both, six rows or every level); a GrtDirectArgs last (six rows or every level, with any of the cloud and aerosol joins) makes the instance that also
 // leaves the direct beam of its sweep (LevelSink: DIRECT).
+// sw_tile_kernel, behind sw_zenith_kernel, is the six-row instance for several surface tiles per column
+// (grt_launch_sw_tiles): the layer properties once for a chunk of tiles, what reads the albedo per tile.
 // The in-kernel range checks of the reference are no-ops on device builds
 // (debug.h:105-116) and are not restated.
 #include <hip/hip_runtime.h>
@@ -653,6 +655,150 @@ __global__ __launch_bounds__(kSolverBlock) void sw_zenith_kernel(GrtSwArgs a, Gr
     }
 }
 
+// ---- several surface tiles per column on one walk through the layers (grt_launch_sw_tiles; GrtTileArgs, grt_kernels.h) ----
+// Of sw_kernel<GRT_OUT_ROWS>, only level_flux at a level and Rd + Tu x (the upward flux at the surface) read the albedo in
+// the one sweep; of its two sweeps, only sweep1_step, through the pair (R_dir_downward, R_dif_downward) it carries up from
+// the albedos.  Grid row y is the six-row instance's (a column, or a column and cloud draw), blockIdx.z a chunk of TN
+// consecutive tiles.  One sweep (sw_kernel's rule): the walk once, level_flux and the top's upward flux per tile.  Two
+// sweeps: the layer properties are formed and parked once (sw_kernel's fused layout, at park row z gridDim.y + y),
+// sweep1_step runs per tile on the tile's pair, the user level's pair kept per tile; the second sweep runs once, its
+// beams and R_dif_upward kept where it passes the user level; then level_flux per tile at the top, the user level and
+// the surface.  Every tile's six rows leave through a LevelSink at the tile's slot (c tiles + t) subcolumns + s:
+// sw_kernel's doubles through sw_kernel's sums.  Tiles past the column's last are skipped by a flag that is uniform per
+// workgroup.
+template <int TN, typename... Joins>
+__global__ __launch_bounds__(kSolverBlock) void sw_tile_kernel(GrtSwArgs a, GrtTileArgs tl, Joins... joins)
+{
+    uint64_t const i = (uint64_t)blockIdx.x*kSolverBlock + threadIdx.x;
+    SolverRow const row = solver_row(a.ncol, joins...);
+    int const col = row.col;
+    bool const live = i < a.nw;
+    uint64_t const ii = live ? i : a.nw - 1;      // (idle lanes of the last block follow along, weight 0)
+    int const V = a.num_levels, L = V - 1, T = tl.tiles, user = a.user_level;
+    int const k0 = (tl.chunk_first + (int)blockIdx.z)*TN;
+    uint64_t const nw = a.nw;
+    int S = 1;
+    if constexpr (has<GrtSubcolumnArgs, Joins...>)
+    {
+        S = pick<GrtSubcolumnArgs>(joins...).subcolumns;
+    }
+    int const draw = row.slot - col*S;
+    double const mu_dir = a.mu_dir[col], mu_dif = a.mu_dif;
+    LayerOptics<true, has_clouds<Joins...>, has<GrtAerosolArgs, Joins...>> const optics(
+        a, pick_clouds(joins...), col, row.tab, ii, pick<GrtAerosolArgs>(joins...));
+    auto props_of = [&](int j) -> LayerProps
+    {
+        double t, om, gg;
+        optics.at(j, t, om, gg);
+        return layer_props(om, gg, t, mu_dir, mu_dif);
+    };
+    // the tiles' albedos: their own rows, or -- no rows -- the instance's for every tile
+    double alb_dir[TN], alb_dif[TN];
+#pragma unroll
+    for (int u = 0; u < TN; ++u)
+    {
+        alb_dir[u] = alb_dif[u] = 0.;
+        if (k0 + u < T)
+        {
+            uint64_t const at = ((uint64_t)col*T + k0 + u)*nw + ii;
+            alb_dir[u] = tl.rows != nullptr ? tl.rows[at] : a.alb_dir[(uint64_t)col*a.alb_stride + ii];
+            alb_dif[u] = tl.rows != nullptr ? (tl.rows_dif != nullptr ? tl.rows_dif[at] : tl.rows[at]) :
+                                              a.alb_dif[(uint64_t)col*a.alb_stride + ii];
+        }
+    }
+    double const scale = a.solar[ii]*mu_dir;
+    double const tsi = a.tsi[col];
+
+    if ((user < 0 || user == 0 || user == L) && a.one_sweep)
+    {
+        // sw_kernel's one sweep, top to surface
+        double dir = 1., dif = 0., Ru = 0., Rd = 0., Tu = 1.;
+        for (int j = 0; j < L; ++j)
+        {
+            LayerProps const p = props_of(j);
+            double const C = 1./(1. - p.Rdif*Ru);
+            Rd = Rd + Tu*((dir*p.Rdir + dif*p.Rdif)*C);
+            Tu = Tu*(p.Tdif*C);
+            dif = (dir*p.Rdir*Ru + dif)*p.Tdif*C + dir*(p.Tdir - p.Tpure);          // shortwave.c:312-316
+            Ru = p.Rdif + p.Tdif*p.Tdif*Ru*C;                                        // :299-306
+            dir *= p.Tpure;
+        }
+#pragma unroll
+        for (int u = 0; u < TN; ++u)
+        {
+            if (k0 + u >= T)
+            {
+                continue;
+            }
+            LevelSink<true, false> sink(a, (col*T + k0 + u)*S + draw, i, live);
+            double up_s, dn_s;                                                      // :318-329 at the surface
+            level_flux(dir, dif, Ru, alb_dir[u], alb_dif[u], up_s, dn_s);
+            put_level(sink, 0, Rd + Tu*up_s, 1., scale, tsi);
+            put_level(sink, L, up_s, dn_s, scale, tsi);
+            __syncthreads();                        // (block_partials' LDS is the tile before's: every wave has read it)
+            sink.finish(a);
+        }
+        return;
+    }
+
+    // sweep 1 (shortwave.c:280-294): the layer properties once, parked; the downward-beam reflectances per tile
+    uint64_t const park_rows = 2*(uint64_t)V + 5*(uint64_t)L;
+    uint64_t const park_row = (uint64_t)blockIdx.z*gridDim.y + (uint64_t)row.park;
+    double *pp = a.park + (park_row*park_rows + 2*(uint64_t)V)*nw + ii;
+    double Rdir_dn[TN], Rdif_dn[TN], user_rdir[TN], user_rdif[TN];
+#pragma unroll
+    for (int u = 0; u < TN; ++u)
+    {
+        Rdir_dn[u] = user_rdir[u] = alb_dir[u];             // (the user level is the surface, or set below)
+        Rdif_dn[u] = user_rdif[u] = alb_dif[u];
+    }
+    for (int j = L - 1; j >= 0; --j)
+    {
+        LayerProps const p = props_of(j);
+        store_props(pp + (uint64_t)(5*j)*nw, nw, p);
+#pragma unroll
+        for (int u = 0; u < TN; ++u)
+        {
+            if (k0 + u < T)
+            {
+                sweep1_step(p, Rdir_dn[u], Rdif_dn[u]);
+                user_rdir[u] = j == user ? Rdir_dn[u] : user_rdir[u];
+                user_rdif[u] = j == user ? Rdif_dn[u] : user_rdif[u];
+            }
+        }
+    }
+    // sweep 2 (shortwave.c:299-316), once: what reaches the user level, then what reaches the surface
+    Sweep2 s, at_user;
+    for (int lev = 1; lev < V; ++lev)
+    {
+        sweep2_step(s, load_props(pp + (uint64_t)(5*(lev - 1))*nw, nw), lev);
+        if (lev == user)
+        {
+            at_user = s;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < TN; ++u)
+    {
+        if (k0 + u >= T)
+        {
+            continue;
+        }
+        LevelSink<true, false> sink(a, (col*T + k0 + u)*S + draw, i, live);
+        put_level(sink, 0, 1.*Rdir_dn[u], 1., scale, tsi);     // R[0] = dir_beam*R_dir_downward[0], T[0]
+        double up, dn;
+        if (user > 0 && user < L)
+        {
+            level_flux(at_user.dir, at_user.dif, at_user.Rup, user_rdir[u], user_rdif[u], up, dn);
+            put_level(sink, user, up, dn, scale, tsi);
+        }
+        level_flux(s.dir, s.dif, s.Rup, alb_dir[u], alb_dif[u], up, dn);             // :318-329 at the surface
+        put_level(sink, L, up, dn, scale, tsi);
+        __syncthreads();                            // (block_partials' LDS is the tile before's: every wave has read it)
+        sink.finish(a);
+    }
+}
+
 // ---- spectral form of few columns: the layer properties first, by one thread per (layer, wavenumber) ----
 // One column of the 1 cm-1 shortwave band is 50 000 threads for sw_kernel<GRT_OUT_CHAINS>: not one wave per SIMD, each working
 // through 120 layer steps of two delta-Eddington solutions (six exp and a dozen divisions) one after the other.  The
@@ -996,6 +1142,48 @@ extern "C" int grt_launch_sw_zeniths(void *stream, GrtSwArgs const *a, GrtZenith
         return launch_zeniths<GRT_ZENITH_CHUNK_AEROSOLS>(s, *a, *z, 1, *ae);
     }
     return launch_zeniths<GRT_ZENITH_CHUNK>(s, *a, *z, 1);
+}
+
+namespace {
+
+// the one launch site of sw_tile_kernel: TN tiles per thread, the six-row instance's grid rows, the launch's chunks along z
+template <int TN, typename... Joins>
+int launch_tiles(hipStream_t s, GrtSwArgs const &a, GrtTileArgs const &t, int draws, Joins const &...joins)
+{
+    if (!grt_tile_args_ok(&t, TN) || (uint64_t)a.ncol*(uint64_t)draws > 65535u || t.chunk_count > 65535)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL((sw_tile_kernel<TN, Joins...>), dim3(grt_solver_blocks(a.nw), (unsigned)(a.ncol*draws), (unsigned)t.chunk_count),
+                       dim3(kSolverBlock), 0, s, a, t, joins...);
+    return (int)hipGetLastError();
+}
+
+} // namespace
+
+extern "C" int grt_launch_sw_tiles(void *stream, GrtSwArgs const *a, GrtTileArgs const *t, GrtSubcolumnArgs const *sc,
+                                   GrtAerosolArgs const *ae)
+{
+    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (a == nullptr || t == nullptr || !grt_solver_instance_ok(in, *a) || (!grt_sw_one_sweep(a) && a->park == nullptr) ||
+        (sc != nullptr && !grt_subcolumn_args_ok(sc)) || (ae != nullptr && !grt_aerosol_args_ok(ae)))
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipStream_t const s = (hipStream_t)stream;
+    if (sc != nullptr && ae != nullptr)
+    {
+        return launch_tiles<GRT_TILE_CHUNK_SUBCOLUMNS_AEROSOLS>(s, *a, *t, sc->count, *sc, *ae);
+    }
+    if (sc != nullptr)
+    {
+        return launch_tiles<GRT_TILE_CHUNK_SUBCOLUMNS>(s, *a, *t, sc->count, *sc);
+    }
+    if (ae != nullptr)
+    {
+        return launch_tiles<GRT_TILE_CHUNK_AEROSOLS>(s, *a, *t, 1, *ae);
+    }
+    return launch_tiles<GRT_TILE_CHUNK>(s, *a, *t, 1);
 }
 
 extern "C" int grt_launch_sw_direct_beam(void *stream, GrtSwArgs const *a, double *direct)

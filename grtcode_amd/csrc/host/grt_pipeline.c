@@ -40,6 +40,9 @@
  * band is not touched at all.
  * grt_pipeline_run_sky_zeniths is grt_pipeline_run_sky with the shortwave of every set solved under several sun angles per
  * column, as grt_pipeline_run_zeniths solves the clean set's: one gas-optics launch per band, one set of cloud draws.
+ * grt_pipeline_run_sky_tiles is grt_pipeline_run_sky's six-row form with several surfaces per column -- emissivity, albedo
+ * and skin temperature per tile -- solved on the column's one atmosphere: one gas-optics launch per band, the solvers' walk
+ * through the layers shared by a chunk of tiles, every tile's rows and their weighted mean.
  * grt_pipeline_run_band_profiles runs the profile form of the clear-sky pass and, with clouds, of the all-sky pass with
  * every level's flux integrated per wavenumber bin instead of over the whole grid, and one finishing launch for the bins'
  * heating rates.
@@ -277,8 +280,10 @@ static void grt_pipeline_release(GrtPipeline_t **pipeline)
         grt_keyed_table_free(p, &p->band[b].bin_table);
         grt_keyed_table_free(p, &p->band[b].surf_map);
         grt_keyed_table_free(p, &p->band[b].channel_table);
+        grt_keyed_table_free(p, &p->band[b].tile_map);
         grt_kdist_table_free(p->device, &p->band[b].kdist_table);
     }
+    grt_staging_free(p, &p->tile);
     grt_staging_free(p, &p->rad);
     grt_staging_free(p, &p->zen);
     grt_staging_free(p, &p->surf);
@@ -361,10 +366,14 @@ static int check_lane(GrtPipeline_t const *p)
 /* What grt_pipeline_run and grt_pipeline_run_profiles check and stage alike: the arguments, the lane, and the small
    per-column inputs, uploaded to small.d on the library stream.  own_sun 1: the run brings its sun angles itself
    (grt_pipeline_run_zeniths), and the columns' cos_zenith is not read; GRT_SUN_MAY_BE_DOWN: cos_zenith is read and a
-   column may be a night column (grt_pipeline_run_ck_fluxes, whose solver leaves zeros there). */
+   column may be a night column (grt_pipeline_run_ck_fluxes, whose solver leaves zeros there); with GRT_SURFACE_IS_TILES
+   added, the run brings its surface temperatures itself (grt_pipeline_run_sky_tiles), and the columns' are not read. */
 #define GRT_SUN_MAY_BE_DOWN 2
+#define GRT_SURFACE_IS_TILES 4
 static int stage_columns(GrtPipeline_t *p, GrtColumns_t const *cols, int own_sun)
 {
+    int const own_surface = (own_sun & GRT_SURFACE_IS_TILES) != 0;
+    own_sun &= ~GRT_SURFACE_IS_TILES;
     GRT_REQUIRE_RANGE(cols->ncol, 1, p->max_cols);
     GRT_REQUIRE_EQ(cols->num_levels, p->num_levels);
     GRT_REQUIRE_PTR(cols->pressure);
@@ -391,10 +400,16 @@ static int stage_columns(GrtPipeline_t *p, GrtColumns_t const *cols, int own_sun
     if (p->band[0].gas != NULL)
     {
         GRT_REQUIRE_PTR(cols->layer_temperature);
-        GRT_REQUIRE_PTR(cols->surface_temperature);
+        if (!own_surface)
+        {
+            GRT_REQUIRE_PTR(cols->surface_temperature);
+        }
         for (int c = 0; c < C; ++c)
         {
-            GRT_REQUIRE_RANGE(cols->surface_temperature[c], MIN_TEMPERATURE, MAX_TEMPERATURE);
+            if (!own_surface)
+            {
+                GRT_REQUIRE_RANGE(cols->surface_temperature[c], MIN_TEMPERATURE, MAX_TEMPERATURE);
+            }
             for (int i = 0; i < L; ++i)
             {
                 GRT_REQUIRE_RANGE(cols->layer_temperature[(size_t)c*L + i], MIN_TEMPERATURE, MAX_TEMPERATURE);
@@ -402,7 +417,10 @@ static int stage_columns(GrtPipeline_t *p, GrtColumns_t const *cols, int own_sun
         }
         memcpy(p->small.h + p->off_tl, cols->layer_temperature, sizeof(double)*(size_t)C*L);
         memcpy(p->small.h + p->off_tv, cols->temperature, sizeof(double)*(size_t)C*V);
-        memcpy(p->small.h + p->off_ts, cols->surface_temperature, sizeof(double)*(size_t)C);
+        if (!own_surface)
+        {
+            memcpy(p->small.h + p->off_ts, cols->surface_temperature, sizeof(double)*(size_t)C);
+        }
     }
     if (p->band[1].gas != NULL)
     {
@@ -515,6 +533,9 @@ typedef struct GrtJoin
     long long channel_pairs;           /* ... their (channel, solver block) pairs on the longwave grid (grt_check_channels) */
     GrtWeighting_t const *weighting;   /* grt_pipeline_run_sky_weighting (with channels): and the channels' transmittance
                                           profiles and contribution functions */
+    GrtSurfaceTiles_t const *tiles;    /* grt_pipeline_run_sky_tiles: every set of both bands is solved over these surfaces
+                                          per column (six rows; rows->out NULL: the tiles' own rows alone) */
+    int tile_points[2];                /* ... the knots each band takes of them (grt_check_tiles) */
 } GrtJoin;
 
 #define GRT_SKY_ALL (GRT_SKY_CLEAN | GRT_SKY_AEROSOL | GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL)
@@ -558,7 +579,7 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
                  cols->ncol, p->surface_ncol);
     }
     int const radiances_only = join->radiances != NULL && rows->out == NULL;
-    GRT_TRY(stage_columns(p, cols, join->zeniths != NULL || radiances_only));
+    GRT_TRY(stage_columns(p, cols, (join->zeniths != NULL || radiances_only) | (join->tiles != NULL ? GRT_SURFACE_IS_TILES : 0)));
     int const C = cols->ncol, S = join->subcolumns > 0 ? join->subcolumns : 1;
     unsigned const sets = join_sets(join);
     GrtZenithRun zr;
@@ -582,6 +603,26 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
     if (join->weighting != NULL)
     {
         grt_stage_weighting(join->weighting, &wr);
+    }
+    GrtTileRun tr;
+    if (join->tiles != NULL)
+    {
+        GRT_TRY(grt_stage_tiles(p, join->tiles, C, join->tile_points, &tr));
+        if (p->band[0].gas == NULL || p->band[1].gas == NULL)
+        {
+            /* a band that is not there: its rows are zeros in both outputs -- everything is zeroed here, in stream order
+               ahead of the kernels that write the other band's rows */
+            void *s = grt_dev_stream(p->device);
+            size_t const slots = (size_t)C*(size_t)rows->sets;
+            if (rows->out != NULL)
+            {
+                GRT_TRY(grt_dev_zero(p->device, rows->out, sizeof(double)*slots*GRT_FLUXES_PER_COLUMN, s));
+            }
+            if (tr.per_tile != NULL)
+            {
+                GRT_TRY(grt_dev_zero(p->device, tr.per_tile, sizeof(double)*slots*(size_t)tr.tiles*GRT_FLUXES_PER_COLUMN, s));
+            }
+        }
     }
     if (cl != NULL && join->sampler != NULL)
     {
@@ -607,13 +648,13 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
                 continue;              /* (grt_pipeline_run_sky_radiances for the radiances alone: no shortwave at all) */
             }
         }
-        else if (rows->out == NULL && (bi == 0 || b->gas == NULL))
+        else if (rows->out == NULL && join->tiles == NULL && (bi == 0 || b->gas == NULL))
         {
             continue;                  /* (grt_pipeline_run_zeniths for the angles' own rows alone: no longwave, no mean) */
         }
         if (b->gas == NULL)
         {
-            if (!rows->profile)
+            if (!rows->profile && join->tiles == NULL)
             {
                 /* a skipped band's six values are zeros in every set, as the profile forms' rows are: the caller's
                    buffer is not left holding whatever it held before */
@@ -644,6 +685,7 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
         ps.radiances = bi == 0 && join->radiances != NULL ? &rr : NULL;
         ps.channels = bi == 0 && join->channels != NULL ? &cr : NULL;
         ps.weighting = ps.channels != NULL && join->weighting != NULL ? &wr : NULL;
+        ps.tiles = join->tiles != NULL ? &tr : NULL;
         GrtAerosolArgs aa;
         int const band_aer = ae != NULL && grt_aerosol_points(ae, bi) > 0;
         int aa_ready = 0;
@@ -664,7 +706,11 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
             }
             ps.aer = ps.aer_pass && band_aer ? &aa : NULL;
             ps.clouds = (bit & (GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL)) != 0 ? &ca : NULL;
-            if (bi == 1 && join->zeniths != NULL)
+            if (join->tiles != NULL)
+            {
+                GRT_TRY(grt_band_solve_tiles(p, b, bi, C, S, &ps));
+            }
+            else if (bi == 1 && join->zeniths != NULL)
             {
                 zr.per_angle = rows->profile ? join->zeniths->zenith_level_fluxes_dev : join->zeniths->zenith_fluxes_dev;
                 zr.six = rows->profile ? join->zeniths->zenith_fluxes_dev : NULL;
@@ -1331,6 +1377,42 @@ EXTERN int grt_pipeline_run_sky_zeniths(GrtPipeline_t *p, GrtColumns_t const *co
     GRT_TRY(check_zeniths(p, cols, zn, level_fluxes_dev, fluxes_dev));
     join.zeniths = zn;
     GRT_TRY(run_under_zeniths(p, cols, &join, nsets, level_fluxes_dev, heating_dev, fluxes_dev));
+    return GRTCODE_SUCCESS;
+}
+
+/* grt_ext.h: the sets of grt_pipeline_run_sky's six-row form over several surface tiles per column */
+EXTERN int grt_pipeline_run_sky_tiles(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky,
+                                      GrtSurfaceTiles_t const *tiles, fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    int nsets;
+    GRT_TRY(check_sky_sets(sky, &nsets));
+    if (tiles == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "no surface tiles (GrtSurfaceTiles_t is NULL).%s", "");
+    }
+    if (fluxes_dev == NULL && tiles->tile_fluxes_dev == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "fluxes_dev and tile_fluxes_dev are both NULL: nothing to write.%s", "");
+    }
+    GrtAerosols_t a;
+    GrtJoin join;
+    GRT_TRY(sky_join(p, cols, sky, &a, &join));
+    if (cols->num_levels != p->num_levels)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "columns of %d levels: this pipeline has %d.", cols->num_levels, p->num_levels);
+    }
+    GRT_TRY(grt_check_tiles(p, tiles, cols->ncol, join.tile_points));
+    join.tiles = tiles;
+    /* (the draws of a cloud set go through the subcolumn form, one draw included: the cloud form's doubles) */
+    join.subcolumns = join.clouds != NULL ? sky->num_subcolumns : 0;
+    GrtPass rows;
+    memset(&rows, 0, sizeof(rows));
+    rows.out = fluxes_dev;
+    rows.sets = nsets;
+    rows.out_stride = nsets*grt_set_offset(p, 0);
+    GRT_TRY(pipeline_run(p, cols, &join, &rows));
     return GRTCODE_SUCCESS;
 }
 

@@ -600,6 +600,117 @@ int grt_stage_surface(GrtPipeline_t *p, GrtSurface_t const *sf, int const np[2])
     return GRTCODE_SUCCESS;
 }
 
+/* ---- surface tiles (grt_pipeline_run_sky_tiles) ---- */
+
+/* What grt_pipeline_run_sky_tiles refuses in its tiles for a batch of C columns, the output pointers apart (nothing is
+   touched): the tile count, the surface's rules for grids, counts and knot values on C x T rows, the temperatures of a
+   pipeline with a longwave band, the fractions.  np: the knots each band takes (0: a band the pipeline does not have, or
+   one whose tiles all take the surface in force). */
+int grt_check_tiles(GrtPipeline_t const *p, GrtSurfaceTiles_t const *tl, int C, int np[2])
+{
+    if (tl->num_tiles < 1 || tl->num_tiles > GRT_MAX_TILES)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d surface tiles per column asked for: 1 to %d.", tl->num_tiles, GRT_MAX_TILES);
+    }
+    int const rows = C*tl->num_tiles;
+    np[0] = p->band[0].gas != NULL ? tl->num_emissivity_points : 0;
+    np[1] = p->band[1].gas != NULL ? tl->num_albedo_points : 0;
+    GRT_TRY(check_surface_band("tile emissivity", np[0], rows, tl->emissivity_grid, tl->emissivity, NULL));
+    GRT_TRY(check_surface_band("tile albedo", np[1], rows, tl->albedo_grid, tl->direct_albedo, tl->diffuse_albedo));
+    if (p->band[0].gas != NULL)
+    {
+        if (tl->surface_temperature == NULL)
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "surface_temperature is NULL: the tiles' temperatures [ncol][%d] are the input of "
+                     "the longwave band.", tl->num_tiles);
+        }
+        for (int k = 0; k < rows; ++k)
+        {
+            /* (a NaN fails the comparison) */
+            if (!(tl->surface_temperature[k] >= MIN_TEMPERATURE && tl->surface_temperature[k] <= MAX_TEMPERATURE))
+            {
+                GRT_FAIL(GRTCODE_VALUE_ERR, "temperature of tile %d of column %d (%e) is NaN or outside %g .. %g.",
+                         k % tl->num_tiles, k/tl->num_tiles, tl->surface_temperature[k], (double)MIN_TEMPERATURE,
+                         (double)MAX_TEMPERATURE);
+            }
+        }
+    }
+    for (int k = 0; k < rows && tl->fraction != NULL; ++k)
+    {
+        if (!(tl->fraction[k] >= 0.))
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "fraction of tile %d of column %d (%e) is negative or NaN.", k % tl->num_tiles,
+                     k/tl->num_tiles, tl->fraction[k]);
+        }
+    }
+    return GRTCODE_SUCCESS;
+}
+
+/* Checked tiles (grt_check_tiles' np) to the device, as grt_stage_surface brings a surface there: the temperatures and
+   fractions, the C x T rows' slope and intercept entries (grt_surface_tables), each band's per-point entries
+   (grt_surface_entry_map; built when the band's tile grid differs from the last call's), and one launch per band and
+   array of the surface-row kernel (GRT_TAG_SURFACE) that writes the tiles' rows [C T][n] into the band's
+   GRT_SCRATCH_TILE_ROWS(_DIF).  The surface in force and its rows are not touched. */
+int grt_stage_tiles(GrtPipeline_t *p, GrtSurfaceTiles_t const *tl, int C, int const np[2], GrtTileRun *tr)
+{
+    size_t const T = (size_t)tl->num_tiles, R = (size_t)C*T, M = (size_t)p->max_cols*T;
+    fp_t const *values[3] = {np[0] > 0 ? tl->emissivity : NULL, np[1] > 0 ? tl->direct_albedo : NULL,
+                             np[1] > 0 ? tl->diffuse_albedo : NULL};
+    size_t off[3], need = 3*R, want = 3*M;
+    for (int k = 0; k < 3; ++k)
+    {
+        size_t const per = values[k] != NULL ? 2*((size_t)np[k > 0] + 1) : 0;
+        off[k] = need;
+        need += R*per;
+        want += M*per;
+    }
+    GRT_TRY(grt_staging_reserve(p, &p->tile, need, want));
+    double *h = p->tile.h;
+    for (size_t k = 0; k < R; ++k)
+    {
+        double const ts = tl->surface_temperature != NULL && p->band[0].gas != NULL ? tl->surface_temperature[k] : 0.;
+        h[k] = ts;
+        h[R + (k % T)*(size_t)C + k/T] = ts;
+        h[2*R + k] = tl->fraction != NULL ? tl->fraction[k] : 0.;
+    }
+    for (int k = 0; k < 3; ++k)
+    {
+        if (values[k] != NULL)
+        {
+            grt_surface_tables(k == 0 ? tl->emissivity_grid : tl->albedo_grid, np[k > 0], (int)R, values[k], h + off[k]);
+        }
+    }
+    GRT_TRY(grt_staging_upload(p, &p->tile, need));
+    void *s = grt_dev_stream(p->device);
+    for (int k = 0; k < 3; ++k)
+    {
+        if (values[k] == NULL)
+        {
+            continue;
+        }
+        GrtBand *b = &p->band[k > 0];
+        SpectralGrid_t const *grid = &b->gas->grid;
+        GridMapFill f = {grid, k == 0 ? tl->emissivity_grid : tl->albedo_grid, np[k > 0], 1};
+        GRT_TRY(grt_keyed_table(p, &b->tile_map, f.x, sizeof(double)*(size_t)f.nx, b->n, fill_grid_map, &f));
+        GrtScratch *rows = &b->scratch[k == 2 ? GRT_SCRATCH_TILE_ROWS_DIF : GRT_SCRATCH_TILE_ROWS];
+        GRT_TRY(grt_scratch_need(p, rows, M*b->n, NULL));
+        GrtSurfaceArgs const sa = {f.nx + 1, b->tile_map.table, p->tile.d + off[k]};
+        int const slot = grt_profile_begin(s, GRT_TAG_SURFACE);
+        int const krc = grt_launch_spread_surface(s, (int)R, grid->w0, grid->dw, b->n, &sa, rows->d);
+        grt_profile_end(s, slot);
+        GRT_TRY(grt_dev_check(krc, "surface row kernel"));
+    }
+    tr->tiles = tl->num_tiles;
+    tr->t_surf = p->tile.d;
+    tr->t_surf_by_tile = p->tile.d + R;
+    tr->fraction = tl->fraction != NULL ? p->tile.d + 2*R : NULL;
+    tr->np[0] = np[0];
+    tr->np[1] = np[1];
+    tr->dif = values[2] != NULL;
+    tr->per_tile = tl->tile_fluxes_dev;
+    return GRTCODE_SUCCESS;
+}
+
 /* ---- instrument channels (grt_pipeline_run_sky_channels) ---- */
 
 /* What grt_pipeline_run_sky_channels and grt_channel_pair_count check of an instrument's channels on a grid of n points

@@ -101,6 +101,14 @@ enum
     GRT_SCRATCH_CK_WEIGHT,
     GRT_SCRATCH_CK_TAU,
     GRT_SCRATCH_CK_SOURCE,
+    /* grt_pipeline_run_sky_tiles: the tiles' rows [max_cols T][n] -- the emissivity (longwave) or the direct albedo
+       (shortwave), and -- shortwave, when a diffuse albedo was given -- the diffuse albedo; replaced when a call's T needs
+       more */
+    GRT_SCRATCH_TILE_ROWS,
+    GRT_SCRATCH_TILE_ROWS_DIF,
+    /* ... [max_cols][T][S][6][nblocks] partial sums of every tile and cloud draw, S = 1 but in a cloud set, its sets in
+       turn in stream order (materialised form: [max_cols][T][S][6] integrated rows); replaced when a call needs more */
+    GRT_SCRATCH_TILE_PARTIALS,
     GRT_SCRATCH_COUNT
 };
 
@@ -143,6 +151,8 @@ typedef struct GrtBand
     /* grt_pipeline_run_sky_channels (longwave band): the instrument's table (GrtChannelArgs: weights, sums and centers,
        then the channels' and the blocks' ints); its key: the grid's points and the channels' first, offset, weights, center */
     GrtKeyedTable channel_table;
+    /* grt_pipeline_run_sky_tiles: [n] entry of the band's tile grid each grid point takes, as surf_map; its key: that grid */
+    GrtKeyedTable tile_map;
     int surf_set, surf_dif_set;    /* the surface in force gives this band rows (, and diffuse rows of their own) */
 } GrtBand;
 
@@ -169,6 +179,10 @@ struct GrtPipeline
     GrtStaging zen;
     /* grt_pipeline_run_sky_radiances' viewing secants [cols][A] */
     GrtStaging rad;
+    /* grt_pipeline_run_sky_tiles' inputs: the temperatures [cols][T], the same tile-major [T][cols] (materialised form), the
+       fractions [cols][T], then the slope and intercept entries of the tiles' emissivity [cols T][NS + 1][2], direct albedo
+       and diffuse albedo */
+    GrtStaging tile;
     int surface_ncol;      /* columns of the surface in force; 0: none (the creation-time arrays apply) */
 };
 
@@ -244,7 +258,24 @@ typedef struct GrtPass
     /* grt_pipeline_run_sky_weighting (NULL: not asked for; with channels only): the weighting kernel behind that one, and
        its finishing kernel beside the channels' */
     GrtWeightingRun const *weighting;
+    /* grt_pipeline_run_sky_tiles (NULL: not asked for; six rows only): every band's solve is grt_band_solve_tiles', the mean
+       over the tiles to out (may be NULL) and every tile's rows to the pass's set of tiles->per_tile */
+    struct GrtTileRun const *tiles;
 } GrtPass;
+
+/* The surface tiles of a grt_pipeline_run_sky_tiles call, staged (grt_stage_tiles): T per column, their temperatures and
+   fractions on the device, each band's rows in its GRT_SCRATCH_TILE_ROWS(_DIF) where the band was given knots, and where
+   every tile's own rows go. */
+typedef struct GrtTileRun
+{
+    int tiles;
+    double const *t_surf;          /* DEVICE [ncol][T] */
+    double const *t_surf_by_tile;  /* DEVICE [T][ncol] (materialised form) */
+    double const *fraction;        /* DEVICE [ncol][T], or NULL */
+    int np[2];                     /* the knots each band was given; 0: every tile takes the surface in force */
+    int dif;                       /* the shortwave was given a diffuse albedo of its own */
+    double *per_tile;              /* DEVICE [ncol][sets][T][12], or NULL */
+} GrtTileRun;
 
 /* The sun angles of a grt_pipeline_run_zeniths or grt_pipeline_run_sky_zeniths call, staged (grt_stage_zeniths): Z per column, their cosines and weights
    on the device, and where every angle's own rows go. */
@@ -290,6 +321,8 @@ GRT_PRIVATE int grt_check_grid(char const *name, char const *kind, char const *n
                                fp_t const *grid, fp_t const *values);
 GRT_PRIVATE int grt_check_surface(GrtPipeline_t const *p, GrtSurface_t const *sf, int np[2]);
 GRT_PRIVATE int grt_stage_surface(GrtPipeline_t *p, GrtSurface_t const *sf, int const np[2]);
+GRT_PRIVATE int grt_check_tiles(GrtPipeline_t const *p, GrtSurfaceTiles_t const *tl, int C, int np[2]);
+GRT_PRIVATE int grt_stage_tiles(GrtPipeline_t *p, GrtSurfaceTiles_t const *tl, int C, int const np[2], GrtTileRun *tr);
 GRT_PRIVATE int grt_stage_zeniths(GrtPipeline_t *p, GrtZeniths_t const *zn, int C, GrtZenithRun *zr);
 GRT_PRIVATE int grt_check_radiances(GrtRadiances_t const *rd, int C);
 GRT_PRIVATE int grt_stage_radiances(GrtPipeline_t *p, GrtRadiances_t const *rd, int C, GrtRadianceRun *rr);
@@ -332,6 +365,7 @@ GRT_PRIVATE int grt_band_solve_ck(GrtPipeline_t *p, GrtBand *b, int bi, int C, i
                                   double *source_sum, GrtCkBand_t const *out);
 GRT_PRIVATE int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps);
 GRT_PRIVATE int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S, GrtPass const *ps);
+GRT_PRIVATE int grt_band_solve_tiles(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S, GrtPass const *ps);
 GRT_PRIVATE int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass const *ps,
                                        GrtZenithRun const *zr);
 

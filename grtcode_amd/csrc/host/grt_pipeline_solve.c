@@ -1001,6 +1001,119 @@ int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass c
     return GRTCODE_SUCCESS;
 }
 
+/* One set of grt_pipeline_run_sky_tiles for one band: the pass over ps->tiles->tiles surfaces per column on this run's
+   tau_gas -- with clouds, as the mean over the S draws ps->clouds holds subcolumn-major, the same draws over every tile --,
+   every tile's six rows to the pass's set of tiles->per_tile and their mean to out as grt_band_solve writes its rows
+   (either may be NULL).  A band that was given knots reads the tiles' rows in GRT_SCRATCH_TILE_ROWS(_DIF); one that was
+   not, the surface in force for every tile.  Fused form: the tile kernel of the pass's joins (GRT_TAG_TILE_LW / _SW), grid
+   row = (column, draw of the launch), its chunks of grt_tile_chunk tiles along z, in as many launches as 65 535 grid rows
+   and -- the shortwave's two sweeps -- the park block of max_cols rows need; the partial sums of every (tile, draw) in
+   tile_partials, slot (c T + t) S + s.  Materialised form: per draw the pass's optics, per tile the spectral solver on the
+   tile's rows and temperature and the row-wise trapezoid into the (tile, draw) rows of tile_partials.  Then the
+   fixed-order mean (GRT_TAG_TILE_MEAN; materialised form: one block per row). */
+int grt_band_solve_tiles(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S, GrtPass const *ps)
+{
+    GrtTileRun const *tr = ps->tiles;
+    int const T = tr->tiles, rows = GRT_FLUXES_PER_BAND, tag = bi == 0 ? GRT_TAG_TILE_LW : GRT_TAG_TILE_SW;
+    void *s = grt_dev_stream(p->device);
+    GrtScratch *block = &b->scratch[GRT_SCRATCH_TILE_PARTIALS];
+    double const *tile_rows = tr->np[bi] > 0 ? b->scratch[GRT_SCRATCH_TILE_ROWS].d : NULL;
+    double const *tile_rows_dif = tile_rows != NULL && bi == 1 && tr->dif ? b->scratch[GRT_SCRATCH_TILE_ROWS_DIF].d : NULL;
+    unsigned nblocks = 1;
+    S = ps->clouds != NULL ? S : 1;
+    if (!p->keep_spectra)
+    {
+        nblocks = b->nblocks;
+        GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*(size_t)T*(size_t)S*(size_t)rows*nblocks, NULL));
+        /* (the loops below walk sc's and ta's first and count, which the launchers alone read) */
+        GrtSubcolumnArgs sc;
+        memset(&sc, 0, sizeof(sc));
+        if (ps->clouds != NULL)
+        {
+            sc.clouds = *ps->clouds;
+            sc.subcolumns = S;
+        }
+        GrtSubcolumnArgs *draws = ps->clouds != NULL ? &sc : NULL;
+        GrtSolverInstance const in = pass_instance(p, ps, NULL, draws, NULL, bi);
+        SolverArgs a;
+        GRT_TRY(solver_args(p, b, bi, C, ps, &in, block->d, &a));
+        GrtTileArgs ta = {T, 0, 0, tr->t_surf, tile_rows, tile_rows_dif};
+        int const chunk = grt_tile_chunk(draws, ps->aer), chunks = (T + chunk - 1)/chunk;
+        /* (grid rows; the two sweeps: (draw, chunk) pairs of C rows each in a park block of max_cols rows) */
+        int const parks = bi == 1 && grt_sw_parks(&in, &a.sw);
+        int const per_launch = parks ? (p->max_cols/C < chunks ? p->max_cols/C : chunks) : chunks;
+        int group = parks ? p->max_cols/C/per_launch : 65535/C;
+        group = group < S ? group : S;
+        int const slot = grt_profile_begin(s, tag);
+        int krc = 0;
+        for (sc.first = 0; sc.first < S && krc == 0; sc.first += group)
+        {
+            sc.count = S - sc.first < group ? S - sc.first : group;
+            for (ta.chunk_first = 0; ta.chunk_first < chunks && krc == 0; ta.chunk_first += per_launch)
+            {
+                ta.chunk_count = chunks - ta.chunk_first < per_launch ? chunks - ta.chunk_first : per_launch;
+                krc = bi == 0 ? grt_launch_lw_tiles(s, &a.lw, &ta, draws, ps->aer) :
+                                grt_launch_sw_tiles(s, &a.sw, &ta, draws, ps->aer);
+            }
+        }
+        grt_profile_end(s, slot);
+        GRT_TRY(grt_dev_check(krc, bi == 0 ? "longwave tile kernel" : "shortwave tile kernel"));
+    }
+    else
+    {
+        GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*(size_t)T*(size_t)S*(size_t)rows, NULL));
+        size_t const tab = ps->clouds != NULL ? (size_t)C*3*(size_t)ps->clouds->num_bands*(size_t)(p->num_levels - 1) : 0;
+        for (int j = 0; j < S; ++j)
+        {
+            GrtCloudArgs cj;
+            GrtPass pj = *ps;
+            if (ps->clouds != NULL)
+            {
+                cj = *ps->clouds;
+                cj.liquid += (size_t)j*tab;
+                cj.ice += (size_t)j*tab;
+                pj.clouds = &cj;
+            }
+            GRT_TRY(pass_optics(p, b, C, &pj));
+            GrtSolverInstance const in = pass_instance(p, &pj, NULL, NULL, NULL, bi);
+            SolverArgs a;
+            GRT_TRY(solver_args(p, b, bi, C, &pj, &in, NULL, &a));
+            for (int t = 0; t < T; ++t)
+            {
+                /* the tile's rows and temperature in the columns' place */
+                if (bi == 0)
+                {
+                    a.lw.t_surf = tr->t_surf_by_tile + (size_t)t*C;
+                    if (tile_rows != NULL)
+                    {
+                        a.lw.emis = tile_rows + (size_t)t*b->n;
+                        a.lw.emis_stride = (uint64_t)T*b->n;
+                    }
+                }
+                else if (tile_rows != NULL)
+                {
+                    a.sw.alb_dir = tile_rows + (size_t)t*b->n;
+                    a.sw.alb_dif = (tile_rows_dif != NULL ? tile_rows_dif : tile_rows) + (size_t)t*b->n;
+                    a.sw.alb_stride = (uint64_t)T*b->n;
+                }
+                int const slot = grt_profile_begin(s, tag);
+                int const krc = solver_launch(s, bi, &in, &a);
+                grt_profile_end(s, slot);
+                GRT_TRY(grt_dev_check(krc, bi == 0 ? "longwave kernel" : "shortwave kernel"));
+                GRT_TRY(grt_dev_check(grt_launch_integrate_rows(s, (double const *const *)b->rows_d, C*rows, b->n,
+                                                                b->gas->grid.dw, block->d, rows, T*S*rows, (t*S + j)*rows),
+                                      "spectral integration kernel"));
+            }
+        }
+    }
+    int const mslot = grt_profile_begin(s, GRT_TAG_TILE_MEAN);
+    int const mrc = grt_launch_tile_mean(s, block->d, C, T, S, nblocks, tr->fraction, tr->per_tile, ps->sets, ps->set, bi,
+                                         ps->out, ps->out_stride, pass_offset(p, ps, bi));
+    grt_profile_end(s, mslot);
+    GRT_TRY(grt_dev_check(mrc, "tile mean kernel"));
+    return GRTCODE_SUCCESS;
+}
+
 /* grt_pipeline_run_ck_fluxes, one band: the class sums of the sources under the map (k_kdist.hip), the solve of every
    g-point on the class means (k_longwave.hip / k_shortwave.hip: the solvers' own layer steps) and the classes' sum per bin.
    The temperatures, the surface in force, the sun and the solar curve are the ones the band's line-by-line solver reads. */

@@ -1044,6 +1044,55 @@ EXTERN int grt_pipeline_run_sky_zeniths(GrtPipeline_t *pipeline, GrtColumns_t co
                                         GrtZeniths_t const *zeniths, fp_t *level_fluxes_dev, fp_t *heating_dev,
                                         fp_t *fluxes_dev);
 
+/* ---- several surface tiles per column on one gas-optics pass -----------------------------------------------------------
+ * grt_pipeline_run_sky (its six-row form) with T surfaces per column: land, open water, sea ice, snow -- each tile with its
+ * own emissivity, albedo and skin temperature under the column's one atmosphere.  Each band's gas optics run once; the
+ * solvers walk the layers once for a chunk of tiles and do only the surface's part per tile (k_longwave.hip:
+ * lw_tile_kernel, k_shortwave.hip: sw_tile_kernel).  N = grt_pipeline_sky_set_count(sky->sets) sets, packed as
+ * grt_pipeline_run_sky packs them; the S draws of a column's cloud sets are the same over every tile.
+ * A tile's rows on the band grids are grt_pipeline_set_surface's for its knots, to the bit (the same host pairs, the same
+ * kernel).  A band with a point count of 0 takes, for every tile, the surface in force: grt_pipeline_set_surface's rows,
+ * else the creation-time arrays -- tiles that differ only in temperature are a valid call.  The surface in force is not
+ * changed by this call and applies again afterwards.  columns->surface_temperature is not read and may be NULL.
+ * tile_fluxes_dev [ncol][N][T][GRT_FLUXES_PER_COLUMN]: every tile's twelve rows in grt_pipeline_run's layout;
+ * fluxes_dev [ncol][N][GRT_FLUXES_PER_COLUMN]: the mean over the tiles; at least one of the two is given.  The mean is
+ * taken in a fixed order, for (column, set, tile): the blocks as the other entry points add them; in a cloud set the draws
+ * s = 0 .. S - 1 in order and one division by S; that is the tile's value, stored at tile_fluxes_dev; then the tiles
+ * t = 0 .. T - 1 -- with fractions sum f_t F_t, each product rounded before it is added (the fractions need not sum to
+ * one); without, the sum and one division by T.  In the deterministic mode tile t's rows of every set are, bit for bit,
+ * grt_pipeline_run_sky's after grt_pipeline_set_surface with tile t's knots and columns->surface_temperature set to tile
+ * t's; with T = 1 and no fractions the whole fluxes_dev is.  A pipeline without a shortwave band zeroes the shortwave
+ * rows of both outputs; without a longwave band, the longwave rows.
+ * The production form (keep_spectra = 0) launches under GRT_TAG_TILE_LW and GRT_TAG_TILE_SW and reduces with a
+ * deterministic kernel (GRT_TAG_TILE_MEAN); the tiles' rows are written by grt_pipeline_set_surface's kernel
+ * (GRT_TAG_SURFACE) into [max_columns T][n] doubles of pipeline scratch per band and array, and per band
+ * [max_columns][T][S][6][blocks] partial sums are allocated at the first call that needs more.  keep_spectra = 1: the
+ * literal loop -- per draw the set's optics, per tile the spectral solver on the tile's rows and temperature and the
+ * row-wise trapezoid, then the same mean kernel.
+ * Not covered: the profile, spectral and per-bin forms; the direct beam, the surface-temperature Jacobian and radiances
+ * per tile; several sun angles with tiles; cloud fields sampled on the device; multi-GPU gathers of tile_fluxes_dev; the
+ * example drivers.
+ * GRTCODE_VALUE_ERR, with nothing launched and every output untouched, for: everything grt_pipeline_run_sky refuses in
+ * `sky`; everything grt_pipeline_set_surface refuses in grids, counts and values (NaN included); num_tiles outside
+ * 1 .. GRT_MAX_TILES; a NULL tiles; a NULL surface_temperature with a longwave band; a tile temperature outside
+ * MIN_TEMPERATURE .. MAX_TEMPERATURE, or NaN; a fraction that is negative or NaN; both outputs NULL; ncol outside
+ * 1 .. max_columns.  Asynchronous on the pipeline's lane. */
+#define GRT_MAX_TILES 16
+typedef struct GrtSurfaceTiles
+{
+    int num_tiles;                         /* T, 1 .. GRT_MAX_TILES */
+    fp_t const *fraction;                  /* HOST [ncol][T] or NULL */
+    fp_t const *surface_temperature;       /* HOST [ncol][T] K; required with a longwave band */
+    int num_emissivity_points, num_albedo_points;          /* NS_e, NS_a: 0 or >= 2, as in GrtSurface_t */
+    fp_t const *emissivity_grid, *albedo_grid;             /* HOST [NS], strictly increasing, shared */
+    fp_t const *emissivity;                /* HOST [ncol][T][NS_e] */
+    fp_t const *direct_albedo;             /* HOST [ncol][T][NS_a] */
+    fp_t const *diffuse_albedo;            /* HOST [ncol][T][NS_a] or NULL: the direct one */
+    fp_t *tile_fluxes_dev;                 /* DEVICE [ncol][N][T][12] or NULL */
+} GrtSurfaceTiles_t;
+EXTERN int grt_pipeline_run_sky_tiles(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtSky_t const *sky,
+                                      GrtSurfaceTiles_t const *tiles, fp_t *fluxes_dev /* [ncol][N][12] or NULL */);
+
 /* ---- columns across the GPUs of one node ------------------------------------
  * One process per GPU; contiguous ceil-sized column blocks; one gather of the [columns][GRT_FLUXES_PER_COLUMN]
  * flux blocks to rank 0.  The reference fans out processes with -x/-X column ranges and merges per-shard files
@@ -1153,7 +1202,13 @@ enum
        reduction under 30 and 31) */
     GRT_TAG_CK_SOURCES = 32,
     GRT_TAG_CK_LW = 33,
-    GRT_TAG_CK_SW = 34
+    GRT_TAG_CK_SW = 34,
+    /* 35 / 36 = the LW / SW tile kernels of grt_pipeline_run_sky_tiles, every set's launches (keep_spectra = 1: its spectral
+       solver launches; its gas optics counts under 1 / 2 and 6 / 7, the tiles' rows under 15); 37 = its mean kernel, one
+       launch per band and set */
+    GRT_TAG_TILE_LW = 35,
+    GRT_TAG_TILE_SW = 36,
+    GRT_TAG_TILE_MEAN = 37
 };
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
