@@ -48,6 +48,7 @@ GRT_JACOBIAN_ROWS_PER_SET = 3       # grt_pipeline_run_sky_jacobian: dF_up/dT_su
 GRT_MAX_VIEW_ANGLES = 16            # grt_pipeline_run_sky_radiances: viewing angles per column, 1 .. this
 GRT_RADIANCE_ROWS_PER_ANGLE = 2     # ... per angle: upward at the top of the atmosphere, downward at the surface
 GRT_MAX_CHANNELS = 16384            # grt_pipeline_run_sky_channels: channels of an instrument, 1 .. this
+GRT_MAX_RESPONSES = 256             # grt_pipeline_run_sky_weighted: spectral responses per band, 0 .. this
 KDIST_KEY_ROW, KDIST_KEY_SUM = 0, 1    # grt_kdist_class_map, GrtKdistKey.kind: the key is one row / the sum of the rows
 KDIST_MAX_CLASSES = 1024            # grt_pipeline_run_kdist, grt_kdist_rows: classes of a k-distribution, 2 .. this
 RETURN_CODES = ["GRTCODE_SUCCESS", "GRTCODE_INVALID_ERR", "GRTCODE_DIVBYZERO_ERR", "GRTCODE_OVERFLOW_ERR",
@@ -209,6 +210,13 @@ class GrtChannels(C.Structure):
                 ("channel_brightness_dev", C.c_void_p)]
 
 
+class GrtResponses(C.Structure):
+    _fields_ = [("lw_num_responses", C.c_int), ("lw_first", C.POINTER(C.c_int)), ("lw_offset", C.POINTER(C.c_int)),
+                ("lw_weights", c_double_p), ("sw_num_responses", C.c_int), ("sw_first", C.POINTER(C.c_int)),
+                ("sw_offset", C.POINTER(C.c_int)), ("sw_weights", c_double_p), ("weighted_levels_dev", C.c_void_p),
+                ("actinic_levels_dev", C.c_void_p)]
+
+
 class GrtWeighting(C.Structure):
     _fields_ = [("transmittance_dev", C.c_void_p), ("contribution_dev", C.c_void_p)]
 
@@ -274,7 +282,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_channels grt_channel_pair_count grt_pipeline_run_sky_weighting grt_pipeline_run_sky_zeniths grt_pipeline_run_sky_tiles grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_kdist_rows grt_pipeline_run_kdist grt_kdist_chunk_points grt_kdist_class_map grt_kdist_mapped_rows grt_pipeline_run_kdist_correlated grt_pipeline_run_ck_fluxes grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_channels grt_channel_pair_count grt_pipeline_run_sky_weighting grt_pipeline_run_sky_weighted grt_response_pair_count grt_pipeline_response_block_limit grt_pipeline_run_sky_zeniths grt_pipeline_run_sky_tiles grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_kdist_rows grt_pipeline_run_kdist grt_kdist_chunk_points grt_kdist_class_map grt_kdist_mapped_rows grt_pipeline_run_kdist_correlated grt_pipeline_run_ck_fluxes grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_voigt_points grt_debug_device_math grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -349,6 +357,12 @@ def load_library(path=None):
         lib.grt_pipeline_run_sky_weighting.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky),
                                                        C.POINTER(GrtRadiances), C.POINTER(GrtChannels),
                                                        C.POINTER(GrtWeighting), C.c_void_p]
+    if hasattr(lib, "grt_pipeline_run_sky_weighted"):    # (GRT_LIB_PATH may name an older library: a timing yardstick)
+        lib.grt_pipeline_run_sky_weighted.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky),
+                                                      C.POINTER(GrtResponses), C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.grt_response_pair_count.argtypes = [C.POINTER(GrtResponses), C.c_int, C.c_longlong]
+        lib.grt_response_pair_count.restype = C.c_longlong
+        lib.grt_pipeline_response_block_limit.argtypes = [C.c_void_p, C.c_int]
     if hasattr(lib, "grt_pipeline_run_kdist"):           # (GRT_LIB_PATH may name an older library: a timing yardstick)
         lib.grt_kdist_rows.argtypes = [C.c_int, C.c_void_p, C.c_longlong, C.c_longlong, C.c_double, C.c_int, c_double_p,
                                        C.POINTER(GrtKdistBand)]
@@ -928,6 +942,42 @@ def channel_pair_count(gchannels, num_points):
     return int(load_library().grt_channel_pair_count(C.byref(gchannels), C.c_longlong(int(num_points))))
 
 
+def make_responses(lw=None, sw=None):
+    """Pack the spectral responses of the two bands into a GrtResponses struct (+ keep-alive arrays) for
+    Pipeline.run_sky_weighted and response_pair_count.  lw, sw: None (the band has no responses) or (first, weights_list)
+    -- first [R]: the grid index of each response's first point in that band; weights_list: R arrays, each response sampled
+    on the grid from that point on, not normalised (the functions of grtcode_amd.responses return such pairs; several are
+    joined with responses.join).  The two output pointers are Pipeline.run_sky_weighted's to set.  keep["lw_counts"],
+    keep["sw_counts"]: the points per response."""
+    keep, fields = {}, []
+    for name, band in (("lw", lw), ("sw", sw)):
+        first, weights_list = band if band is not None else ((), ())
+        per = [_f64(w).ravel() for w in weights_list]
+        keep[name + "_first"] = np.ascontiguousarray(first, dtype=np.int32).ravel()
+        keep[name + "_counts"] = np.array([w.size for w in per], dtype=np.int64)
+        if keep[name + "_first"].size != len(per):
+            raise ValueError(f"{keep[name + '_first'].size} first points for {len(per)} {name} responses")
+        if int(keep[name + "_counts"].sum()) >= 2**31:
+            raise ValueError(f"{int(keep[name + '_counts'].sum())} {name} weights in all: fewer than 2^31")
+        keep[name + "_offset"] = np.ascontiguousarray(np.concatenate(([0], np.cumsum(keep[name + "_counts"]))), dtype=np.int32)
+        keep[name + "_weights"] = _f64(np.concatenate(per)) if per else np.zeros(1)
+        if per:
+            fields += [len(per), keep[name + "_first"].ctypes.data_as(c_int_p), keep[name + "_offset"].ctypes.data_as(c_int_p),
+                       _dp(keep[name + "_weights"])]
+        else:
+            fields += [0, None, None, None]
+    gr = GrtResponses(*fields, None, None)
+    gr.keep = keep             # (as make_cloud_model)
+    return gr, keep
+
+
+def response_pair_count(gresponses, band, num_points):
+    """grt_response_pair_count: the (response, 128-point solver block) pairs P of band `band` (0 longwave, 1 shortwave) of
+    gresponses (make_responses) on a grid of num_points points -- Pipeline.run_sky_weighted takes max_columns x S x P x G V
+    doubles of scratch per band --, or -1 for responses the call would refuse.  Host code only."""
+    return int(load_library().grt_response_pair_count(C.byref(gresponses), int(band), C.c_longlong(int(num_points))))
+
+
 def _kdist_band(edges, weight):
     """One band of make_kdist: the struct with no outputs yet, and the arrays it points into."""
     e = None if edges is None else np.ascontiguousarray(edges, dtype=np.int32).ravel()
@@ -1047,6 +1097,7 @@ class Pipeline:
         self.kdist_shape = None  # (classes, longwave bins, shortwave bins) of the last run_kdist
         self.kdist_corr_shape = None  # ... of the last run_kdist_correlated, and whether it kept the maps
         self.ck_shape = None    # ... of the last run_ck_fluxes, and whether it kept the maps
+        self.weighted_shape = (0, 0)  # (longwave responses, shortwave responses) of the last run_sky_weighted
         self.out = self._buffer("run", 8 * GRT_FLUXES_PER_COLUMN * max_columns)
 
     def _buffer(self, name, nbytes):
@@ -1422,6 +1473,40 @@ class Pipeline:
         direct_levels=[ncol][nsets][V], the direct beam at every level, top first)."""
         return dict(direct=self.sky_direct_fluxes(ncol, nsets, profiles=True),
                     direct_levels=self.buffers["sky_profiles.direct_levels"].to_host((ncol, nsets, self.num_levels)))
+
+    def response_block_limit(self, band):
+        """grt_pipeline_response_block_limit: the most responses of band `band` (0 longwave, 1 shortwave) that may have a
+        point in one block of 128 consecutive grid points at this object's number of levels."""
+        return int(self.lib.grt_pipeline_response_block_limit(self.p, int(band)))
+
+    def run_sky_weighted(self, gcols, gsky, gresp):
+        """grt_pipeline_run_sky_weighted into this object's device buffers: run_sky(gcols, gsky, profiles=True) -- its
+        outputs where run_sky puts them (sky_profiles() reads them) -- and with it every set's level rows under the
+        responses gresp (make_responses' struct; its two output fields are set here), and the actinic flux of the
+        shortwave's (sky_weighted() reads both)."""
+        ptrs, nsets = self._sky_ptrs(gsky, True)
+        V, n = self.num_levels, self.max_columns
+        r_lw, r_sw = max(int(gresp.lw_num_responses), 0), max(int(gresp.sw_num_responses), 0)
+        self.weighted_shape = (r_lw, r_sw)
+        gresp.weighted_levels_dev = self._buffer("sky.weighted_levels", 8 * n * nsets * max(2 * r_lw + 3 * r_sw, 1) * V).ptr
+        gresp.actinic_levels_dev = self._buffer("sky.actinic_levels", 8 * n * nsets * r_sw * V).ptr if r_sw > 0 else None
+        check(self.lib.grt_pipeline_run_sky_weighted(self.p, C.byref(gcols), C.byref(gsky), C.byref(gresp), *ptrs))
+
+    def sky_weighted(self, ncol, nsets):
+        """The last run_sky_weighted of nsets sets: a dict of lw_up, lw_down [ncol][nsets][R_lw][V] and sw_up, sw_down,
+        sw_direct, sw_actinic [ncol][nsets][R_sw][V] -- the level rows under each response, levels top first, W m-2 x the
+        unit of the response; sw_actinic: the actinic flux (S/mu0 + (D - S)/mu_dif) + U/mu_dif of the delta-scaled beam."""
+        self.sync()
+        V = self.num_levels
+        r_lw, r_sw = self.weighted_shape
+        rows = 2 * r_lw + 3 * r_sw
+        w = self.buffers["sky.weighted_levels"].to_host((ncol, nsets, rows * V)) if rows else np.zeros((ncol, nsets, 0))
+        lw = w[:, :, :2 * r_lw * V].reshape(ncol, nsets, r_lw, 2, V)
+        sw = w[:, :, 2 * r_lw * V:].reshape(ncol, nsets, r_sw, 3, V)
+        act = (self.buffers["sky.actinic_levels"].to_host((ncol, nsets, r_sw, V)) if r_sw > 0
+               else np.zeros((ncol, nsets, 0, V)))
+        return dict(lw_up=lw[:, :, :, 0].copy(), lw_down=lw[:, :, :, 1].copy(), sw_up=sw[:, :, :, 0].copy(),
+                    sw_down=sw[:, :, :, 1].copy(), sw_direct=sw[:, :, :, 2].copy(), sw_actinic=act)
 
     def run_sky_jacobian(self, gcols, gsky, profiles=False):
         """grt_pipeline_run_sky_jacobian into this object's device buffers: run_sky's outputs where run_sky puts them

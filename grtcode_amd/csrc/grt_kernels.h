@@ -704,6 +704,56 @@ static inline int grt_band_args_ok(GrtBandArgs const *bn)
     return bn != NULL && bn->num_bins >= 1 && bn->block_bins >= 1 && bn->table != NULL && bn->per_row >= 1;
 }
 
+/* Response form of the two profile forms (GRT_OUT_LEVELS with any of the cloud and aerosol joins or none, the shortwave's
+   always together with `direct`; grt_pipeline_run_sky_weighted): the profile form's arguments, sweeps, park block and
+   partial sums -- the broadband rows are summed exactly as without it --, and beside them every level's rows under
+   spectral response functions.  Response k is the points first .. first + count - 1 of the grid with the weights r_k at
+   weights + its weight offset (not normalised, any finite sign; responses overlap freely, so a block has an explicit list
+   of them, not a range); a (response, 128-point solver block) pair is a response and a block it has a point in, pair = the
+   response's first pair + block - its first block.  A workgroup stages t_i r_k(i) -- t_i the band's trapezoid weight, 0
+   for idle lanes and outside the response's span -- for the responses of its block's list in dynamic LDS, [responses of
+   the block][128], once at kernel start; every level's value x then leaves once more per response of the list as the
+   wave sums of x (t r), in its own group of G V rows behind the broadband group (G = 2: up, down; 3 with the third row
+   group), and finish() stores the list's sums at partials[(slot P + pair) G V + row], row = level (up), V + level (down),
+   2 V + level (third group): without atomics, a fixed place per (slot, response, row, block).  A workgroup whose list is
+   empty does exactly the profile form's work.  Dynamic LDS: (1 + block_max) G V x 2 doubles of wave sums and block_max x
+   128 doubles of weights.
+   The table (grt_stage_responses, host): the doubles first -- every response's weights --, then the ints: per response
+   GRT_RESPONSE_INTS (first point, count, weight offset, first block, first pair), per block where its list starts in what
+   follows [nblocks + 1], and the lists [P], the responses of a block in ascending order.
+   grt_launch_response_rows: the materialised form's twin -- the same weights, wave and workgroup sums on rows [slots][G]
+   [V][nw] the spectral solvers (and the direct-beam kernel) left on the grid, row group g of slot c at rows[g] + c V nw,
+   to the same partial sums.
+   grt_launch_response_finish: one thread per output row (column, response, row of the G V): per draw s = 0 .. S - 1 in
+   order the response's blocks in the association grt_launch_reduce_partials has for that many blocks, then one division by
+   S as grt_launch_subcolumn_mean's, to out[c out_stride + out_offset + (k G + g) V + level].
+   grt_launch_actinic_rows: from finished shortwave rows [n][R][3][V] (row group stride `stride` doubles per n) the actinic
+   flux (S/mu0 + (D - S)/mu_dif) + U/mu_dif, in that order, to actinic[i a_stride + (k V + level)]; mu0 [ncol], i = c sets +
+   set. */
+#define GRT_RESPONSE_INTS 5
+typedef struct GrtResponseArgs
+{
+    int responses;                  /* R */
+    int block_max;                  /* the most responses with a point in one workgroup: sizes the dynamic LDS */
+    uint64_t per_row;               /* P: the (response, block) pairs, partial sums per row and slot */
+    int const *resp;                /* DEVICE [R][GRT_RESPONSE_INTS] */
+    int const *block_start;         /* DEVICE [nblocks + 1] */
+    int const *block_resp;          /* DEVICE [P] */
+    double const *weights;          /* DEVICE [the responses' points] */
+    double *partials;               /* DEVICE [slot][P][G V] */
+} GrtResponseArgs;
+static inline int grt_response_args_ok(GrtResponseArgs const *r)
+{
+    return r != NULL && r->responses >= 1 && r->block_max >= 1 && r->per_row >= 1 && r->resp != NULL &&
+           r->block_start != NULL && r->block_resp != NULL && r->weights != NULL && r->partials != NULL;
+}
+int grt_launch_response_rows(void *stream, GrtResponseArgs const *r, double const *const rows[3], int groups, int slots,
+                             int num_levels, uint64_t nw, double dw);
+int grt_launch_response_finish(void *stream, GrtResponseArgs const *r, int groups, int ncol, int subcolumns, int num_levels,
+                               double *out, uint64_t out_stride, uint64_t out_offset);
+int grt_launch_actinic_rows(void *stream, double const *weighted, uint64_t stride, int ncol, int sets, int responses,
+                            int num_levels, double const *mu0, double mu_dif, double *actinic);
+
 /* One instance of lw_kernel / sw_kernel (k_longwave.hip, k_shortwave.hip), described once for the launchers, the kernels
    and the pipeline: what leaves the kernel ... */
 typedef enum GrtSolverOutput
@@ -723,7 +773,7 @@ typedef enum GrtSolverOutput
    stays per column whatever the subcolumn); `bins` goes with GRT_OUT_LEVEL_BINS and with nothing else; `zeniths` (the
    shortwave's GRT_OUT_ROWS and GRT_OUT_LEVELS) goes alone or with aerosols, subcolumns or both, never with `clouds`; `direct` (the shortwave's GRT_OUT_ROWS and
    GRT_OUT_LEVELS) goes with any join of clouds and aerosols or none, and selects instances of its own: the instance
-   without it is the one it was; `jacobian` is the same for the longwave's GRT_OUT_ROWS and GRT_OUT_LEVELS.  The kind of instance follows from which pointers are set, and a kernel takes the structs that are
+   without it is the one it was; `jacobian` is the same for the longwave's GRT_OUT_ROWS and GRT_OUT_LEVELS; `responses` goes with GRT_OUT_LEVELS alone, in the shortwave always together with `direct`, never with `bins`, `zeniths` or `jacobian`, and selects instances of its own as `direct` does.  The kind of instance follows from which pointers are set, and a kernel takes the structs that are
    set as arguments after its band's own.  The next joined object is a pointer here, a line in grt_solver_instance_ok
    and a case in each band's list of instances. */
 typedef struct GrtSolverInstance
@@ -736,6 +786,7 @@ typedef struct GrtSolverInstance
     GrtZenithArgs const *zeniths;
     GrtDirectArgs const *direct;
     GrtJacobianArgs const *jacobian;
+    GrtResponseArgs const *responses;
 } GrtSolverInstance;
 typedef enum GrtSolverJoin
 {
@@ -778,12 +829,25 @@ static inline uint64_t grt_solver_grid_rows(GrtSolverInstance const *in, int nco
            (uint64_t)(in->zeniths != NULL ? in->zeniths->count : 1);
 }
 /* its dynamic LDS: 2 V doubles per wave of its workgroup where every level leaves (3 V with the direct beam or the
-   surface-temperature Jacobian), that per bin of a block with bins */
+   surface-temperature Jacobian), that per bin of a block with bins; with responses, that once more per response of a
+   block and the block's staged weights, 128 doubles per response */
 #define GRT_SOLVER_BLOCK 128
 static inline size_t grt_solver_lds(GrtSolverInstance const *in, int num_levels)
 {
     size_t const levels = sizeof(double)*(in->direct != NULL || in->jacobian != NULL ? 3 : 2)*(size_t)num_levels*(GRT_SOLVER_BLOCK/64);
+    if (grt_out_levels(in->out) && in->responses != NULL)
+    {
+        return levels*(1 + (size_t)in->responses->block_max) + sizeof(double)*GRT_SOLVER_BLOCK*(size_t)in->responses->block_max;
+    }
     return !grt_out_levels(in->out) ? 0 : (in->bins != NULL ? levels*(size_t)in->bins->block_bins : levels);
+}
+/* the most responses one block may hold at num_levels levels and `groups` row groups (2; 3 with the third row group):
+   16 G V (1 + R_b) + 1024 R_b <= 65536 */
+static inline int grt_response_block_limit(int num_levels, int groups)
+{
+    long long const levels = 16ll*groups*num_levels;
+    long long const r = (65536 - levels)/(levels + 8*GRT_SOLVER_BLOCK);
+    return r < 0 ? 0 : (int)r;
 }
 /* whether the shortwave instance takes the two sweeps and needs `park` */
 static inline int grt_sw_parks(GrtSolverInstance const *in, GrtSwArgs const *a)
@@ -1034,7 +1098,10 @@ inline bool grt_solver_instance_ok(GrtSolverInstance const &in, Args const &a)
     bool const jacobian_ok = in.jacobian == nullptr || (in.zeniths == nullptr && in.direct == nullptr &&
                                                         grt_jacobian_args_ok(in.jacobian) &&
                                                         (in.out == GRT_OUT_ROWS || in.out == GRT_OUT_LEVELS));
-    return zeniths_ok && direct_ok && jacobian_ok && a.ncol >= 1 && a.nw >= 2 && a.num_levels >= 2 &&
+    // (the response rows leave the level form beside its own: no bins, sun angles or Jacobian with them)
+    bool const responses_ok = in.responses == nullptr || (in.out == GRT_OUT_LEVELS && in.bins == nullptr && in.zeniths == nullptr &&
+                                                          in.jacobian == nullptr && grt_response_args_ok(in.responses));
+    return zeniths_ok && direct_ok && jacobian_ok && responses_ok && a.ncol >= 1 && a.nw >= 2 && a.num_levels >= 2 &&
            cloud_forms <= 1 && joined <= (fused ? 2 : 0) && (in.bins != nullptr) == (in.out == GRT_OUT_LEVEL_BINS) &&
            (in.clouds == nullptr || grt_cloud_args_ok(in.clouds)) &&
            (in.aerosols == nullptr || grt_aerosol_args_ok(in.aerosols)) &&

@@ -239,8 +239,11 @@ __global__ __launch_bounds__(kSolverBlock) void lw_kernel(GrtLwArgs a, Joins... 
     LwPoint<FUSED, Joins...> const p(a, i, joins...);
     int const L = p.L;
     double const w = p.w;
-    LevelSink<FUSED, PROFILE, SPECTRAL, has<GrtBandArgs, Joins...>, JACOBIAN> sink(
-        a, p.row.slot, i, p.live, pick<GrtBandArgs>(joins...), GrtDirectArgs{pick<GrtJacobianArgs>(joins...).partials});
+    constexpr bool RESPONSES = has<GrtResponseArgs, Joins...>;
+    static_assert(!RESPONSES || (OUT == GRT_OUT_LEVELS && !JACOBIAN), "the response rows leave the level form, without the Jacobian");
+    LevelSink<FUSED, PROFILE, SPECTRAL, has<GrtBandArgs, Joins...>, JACOBIAN, RESPONSES> sink(
+        a, p.row.slot, i, p.live, pick<GrtBandArgs>(joins...), GrtDirectArgs{pick<GrtJacobianArgs>(joins...).partials},
+        pick<GrtResponseArgs>(joins...));
 
     double I[4] = {0., 0., 0., 0.};
     sink.put_zero(0, true);                                              // longwave.c:171
@@ -1036,7 +1039,25 @@ extern "C" int grt_launch_lw(void *stream, GrtSolverInstance const *in, GrtLwArg
         return (int)hipErrorInvalidValue;
     }
     hipStream_t const s = (hipStream_t)stream;
-    // every instance of lw_kernel there is; the six-row and level instances twice, as launch_third_group says
+    // the level instances that leave the response rows beside their own (grt_pipeline_run_sky_weighted's sets) ...
+    if (in->responses != nullptr)
+    {
+        GrtResponseArgs const &r = *in->responses;
+        switch (GRT_INSTANCE(in->out, grt_solver_join(in)))
+        {
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_NONE): return launch<GRT_OUT_LEVELS>(s, *in, *a, r);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, r);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->aerosols, r);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, r);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS_AEROSOLS):
+            return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, *in->aerosols, r);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
+            return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->aerosols, r);
+        default:
+            return (int)hipErrorInvalidValue;
+        }
+    }
+    // ... and every other instance of lw_kernel there is; the six-row and level instances twice, as launch_third_group says
     GrtJacobianArgs const *const d = in->jacobian;
     switch (GRT_INSTANCE(in->out, grt_solver_join(in)))
     {
@@ -1205,7 +1226,7 @@ extern "C" int grt_tile_chunk(GrtSubcolumnArgs const *sc, GrtAerosolArgs const *
 extern "C" int grt_launch_lw_tiles(void *stream, GrtLwArgs const *a, GrtTileArgs const *t, GrtSubcolumnArgs const *sc,
                                    GrtAerosolArgs const *ae)
 {
-    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (a == nullptr || t == nullptr || !grt_solver_instance_ok(in, *a) || a->t_layers == nullptr || a->t_levels == nullptr ||
         a->emis == nullptr || (sc != nullptr && !grt_subcolumn_args_ok(sc)) || (ae != nullptr && !grt_aerosol_args_ok(ae)))
     {

@@ -994,3 +994,176 @@ extern "C" int grt_launch_copy_rows(void *stream, double const *const *rows_dev,
                        (hipStream_t)stream, rows_dev, nrows, nw, out, out_stride);
     return (int)hipGetLastError();
 }
+
+// ---- response-weighted level rows (grt_pipeline_run_sky_weighted; GrtResponseArgs, grt_kernels.h) ----
+namespace {
+
+constexpr int kResponseChunk = 64;      // responses of one block summed before their block sums are stored
+constexpr int kResponseFinishBlock = 256;
+
+// The materialised form's twin of LevelSink's response form: one workgroup per (128-point block, slot).  Row (g, level) of
+// the slot is rows.p[g] + (slot V + level) nw; per response of the block's list, sum_i x_i (t_i r(i)) as the sink sums it
+// (WAVE_SUM, then waves_sum), stored at partials[(slot P + pair) G V + g V + level].
+struct ResponseRowGroups { double const *p[3]; };
+
+__global__ __launch_bounds__(kSolverBlock) void response_rows_kernel(GrtResponseArgs r, ResponseRowGroups rows, int G, int V,
+                                                                     uint64_t nw, double dw)
+{
+    __shared__ double part[kResponseChunk][kSolverBlock/64];
+    unsigned const block = blockIdx.x, slot = blockIdx.y;
+    int const lo = r.block_start[block], hi = r.block_start[block + 1];
+    uint64_t const i = (uint64_t)block*kSolverBlock + threadIdx.x;
+    bool const live = i < nw;
+    double const pwt = trapezoid_weight(i, nw, dw, live);
+    int const nrows = G*V;
+    for (int row = 0; row < nrows; ++row)
+    {
+        int const g = row/V, lev = row - g*V;
+        double const x = live ? rows.p[g][((uint64_t)slot*V + lev)*nw + i] : 0.;
+        for (int q0 = lo; q0 < hi; q0 += kResponseChunk)
+        {
+            int const nq = hi - q0 < kResponseChunk ? hi - q0 : kResponseChunk;
+            for (int q = 0; q < nq; ++q)
+            {
+                int const *e = r.resp + GRT_RESPONSE_INTS*r.block_resp[q0 + q];
+                long long const at = (long long)i - e[0];
+                double const w = live && at >= 0 && at < e[1] ? pwt*r.weights[e[2] + at] : 0.;
+                double s = x*w;
+                WAVE_SUM(s);
+                if ((threadIdx.x & 63) == 0)
+                {
+                    part[q][threadIdx.x >> 6] = s;
+                }
+            }
+            __syncthreads();
+            if ((int)threadIdx.x < nq)
+            {
+                int const *e = r.resp + GRT_RESPONSE_INTS*r.block_resp[q0 + threadIdx.x];
+                uint64_t const pair = (uint64_t)(e[4] + (int)block - e[3]);
+                r.partials[((uint64_t)slot*r.per_row + pair)*nrows + row] = waves_sum<kSolverBlock/64>(part[threadIdx.x]);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// n partial sums p[0], p[stride], ... added by ONE thread in wave_strided_sum's association: 64 lane sums, each from +0.0
+// over every 64th term in order, then the shuffle tree of WAVE_SUM (lane l takes lane l + off, off = 32 .. 1) -- what
+// reduce_partials_kernel gives for a row of n blocks, to the bit.
+__device__ __forceinline__ double strided_tree_sum(double const *p, unsigned n, uint64_t stride)
+{
+    double lane[64];
+#pragma unroll
+    for (int l = 0; l < 64; ++l)
+    {
+        double s = 0.;
+        for (unsigned b = l; b < n; b += 64)
+        {
+            s += p[(uint64_t)b*stride];
+        }
+        lane[l] = s;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+    {
+#pragma unroll
+        for (int l = 0; l < off; ++l)
+        {
+            lane[l] += lane[l + off];
+        }
+    }
+    return lane[0];
+}
+
+// one thread per output row (column, response, row group, level), the level fastest: per draw s = 0 .. S - 1 in order the
+// response's blocks as reduce_partials_kernel adds that many, then one division by S as subcolumn_mean_kernel's
+__global__ __launch_bounds__(kResponseFinishBlock) void response_finish_kernel(GrtResponseArgs r, int G, int ncol, int S,
+                                                                               int V, double *out, uint64_t out_stride,
+                                                                               uint64_t out_offset)
+{
+    uint64_t const t = (uint64_t)blockIdx.x*kResponseFinishBlock + threadIdx.x;
+    uint64_t const rows = (uint64_t)G*V;
+    if (t >= (uint64_t)ncol*r.responses*rows)
+    {
+        return;
+    }
+    uint64_t const row = t % rows, k = (t/rows) % (uint64_t)r.responses, c = t/(rows*(uint64_t)r.responses);
+    int const *e = r.resp + GRT_RESPONSE_INTS*k;
+    unsigned const nblk = (unsigned)((e[0] + e[1] - 1)/kSolverBlock - e[3]) + 1;
+    double m = 0.;
+    for (int s = 0; s < S; ++s)
+    {
+        double const x = strided_tree_sum(r.partials + ((c*S + s)*r.per_row + (uint64_t)e[4])*rows + row, nblk, rows);
+        m = s == 0 ? x : m + x;
+    }
+    out[c*out_stride + out_offset + k*rows + row] = m/(double)S;
+}
+
+// the actinic flux of every (column, set, response, level) from the three finished shortwave rows, in this order
+__global__ __launch_bounds__(kResponseFinishBlock) void actinic_rows_kernel(double const *weighted, uint64_t stride, int ncol,
+                                                                            int sets, int R, int V, double const *mu0,
+                                                                            double mu_dif, double *actinic)
+{
+    uint64_t const t = (uint64_t)blockIdx.x*kResponseFinishBlock + threadIdx.x;
+    uint64_t const per = (uint64_t)R*V;
+    if (t >= (uint64_t)ncol*sets*per)
+    {
+        return;
+    }
+    uint64_t const lev = t % V, k = (t/V) % (uint64_t)R, i = t/per, c = i/(uint64_t)sets;
+    double const *three = weighted + i*stride + k*3*V + lev;
+    double const up = three[0], down = three[V], beam = three[2*(uint64_t)V];
+    double const m = mu0[c];
+    actinic[t] = (beam/m + (down - beam)/mu_dif) + up/mu_dif;
+}
+
+} // namespace
+
+extern "C" int grt_launch_response_rows(void *stream, GrtResponseArgs const *r, double const *const rows[3], int groups,
+                                        int slots, int num_levels, uint64_t nw, double dw)
+{
+    if (!grt_response_args_ok(r) || rows == nullptr || groups < 2 || groups > 3 || slots < 1 || slots > 65535 ||
+        num_levels < 1 || nw < 2)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    ResponseRowGroups g = {{rows[0], rows[1], groups == 3 ? rows[2] : nullptr}};
+    for (int k = 0; k < groups; ++k)
+    {
+        if (g.p[k] == nullptr)
+        {
+            return (int)hipErrorInvalidValue;
+        }
+    }
+    hipLaunchKernelGGL(response_rows_kernel, dim3(bin_blocks(nw), (unsigned)slots), dim3(kSolverBlock), 0, (hipStream_t)stream,
+                       *r, g, groups, num_levels, nw, dw);
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_response_finish(void *stream, GrtResponseArgs const *r, int groups, int ncol, int subcolumns,
+                                          int num_levels, double *out, uint64_t out_stride, uint64_t out_offset)
+{
+    if (!grt_response_args_ok(r) || groups < 2 || groups > 3 || ncol < 1 || subcolumns < 1 || num_levels < 1 || out == nullptr)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    uint64_t const threads = (uint64_t)ncol*(uint64_t)r->responses*(uint64_t)groups*(uint64_t)num_levels;
+    hipLaunchKernelGGL(response_finish_kernel, dim3((unsigned)((threads + kResponseFinishBlock - 1)/kResponseFinishBlock)),
+                       dim3(kResponseFinishBlock), 0, (hipStream_t)stream, *r, groups, ncol, subcolumns, num_levels, out,
+                       out_stride, out_offset);
+    return (int)hipGetLastError();
+}
+
+extern "C" int grt_launch_actinic_rows(void *stream, double const *weighted, uint64_t stride, int ncol, int sets, int responses,
+                                       int num_levels, double const *mu0, double mu_dif, double *actinic)
+{
+    if (weighted == nullptr || ncol < 1 || sets < 1 || responses < 1 || num_levels < 1 || mu0 == nullptr || actinic == nullptr)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    uint64_t const threads = (uint64_t)ncol*(uint64_t)sets*(uint64_t)responses*(uint64_t)num_levels;
+    hipLaunchKernelGGL(actinic_rows_kernel, dim3((unsigned)((threads + kResponseFinishBlock - 1)/kResponseFinishBlock)),
+                       dim3(kResponseFinishBlock), 0, (hipStream_t)stream, weighted, stride, ncol, sets, responses, num_levels,
+                       mu0, mu_dif, actinic);
+    return (int)hipGetLastError();
+}

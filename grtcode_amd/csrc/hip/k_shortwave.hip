@@ -312,6 +312,8 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Joins... 
     static_assert(has<GrtBandArgs, Joins...> == (OUT == GRT_OUT_LEVEL_BINS), "bins go with GRT_OUT_LEVEL_BINS alone");
     static_assert(!DIRECT || ((OUT == GRT_OUT_ROWS || OUT == GRT_OUT_LEVELS) && !has<GrtZenithArgs, Joins...>),
                   "the direct beam leaves the six-row and level forms, one sun per column");
+    constexpr bool RESPONSES = has<GrtResponseArgs, Joins...>;
+    static_assert(!RESPONSES || (OUT == GRT_OUT_LEVELS && DIRECT), "the response rows leave the level form, the direct beam with them");
     SolverRow const row = solver_row(a.ncol, joins...);
     int const col = row.col;
     bool const live = i < a.nw;
@@ -350,8 +352,8 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Joins... 
     // divisions a layer, which is what this kernel's time is made of)
     double *pp = FUSED ? a.park + ((uint64_t)row.park*park_rows + 2*(uint64_t)V)*nw + ii : nullptr;
     int const user = a.user_level;
-    LevelSink<FUSED, PROFILE, SPECTRAL, has<GrtBandArgs, Joins...>, DIRECT> sink(a, row.slot, i, live, pick<GrtBandArgs>(joins...),
-                                                                                 pick<GrtDirectArgs>(joins...));
+    LevelSink<FUSED, PROFILE, SPECTRAL, has<GrtBandArgs, Joins...>, DIRECT, RESPONSES> sink(
+        a, row.slot, i, live, pick<GrtBandArgs>(joins...), pick<GrtDirectArgs>(joins...), pick<GrtResponseArgs>(joins...));
     LayerOptics<FUSED, has_clouds<Joins...>, has<GrtAerosolArgs, Joins...>> const optics(
         a, pick_clouds(joins...), col, row.tab, ii, pick<GrtAerosolArgs>(joins...));                    // (fused forms)
 
@@ -1019,6 +1021,30 @@ extern "C" int grt_launch_sw(void *stream, GrtSolverInstance const *in, GrtSwArg
         return (int)hipErrorInvalidValue;
     }
     hipStream_t const s = (hipStream_t)stream;
+    // the level instances that leave the response rows beside their own and the direct beam's (grt_pipeline_run_sky_weighted's
+    // sets) ...
+    if (in->responses != nullptr)
+    {
+        if (in->direct == nullptr)
+        {
+            return (int)hipErrorInvalidValue;
+        }
+        GrtDirectArgs const &d = *in->direct;
+        GrtResponseArgs const &r = *in->responses;
+        switch (GRT_INSTANCE(in->out, grt_solver_join(in)))
+        {
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_NONE): return launch<GRT_OUT_LEVELS>(s, *in, *a, d, r);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, d, r);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->aerosols, d, r);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, d, r);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS_AEROSOLS):
+            return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, *in->aerosols, d, r);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
+            return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->aerosols, d, r);
+        default:
+            return (int)hipErrorInvalidValue;
+        }
+    }
     // every instance of sw_kernel that also leaves the direct beam (grt_pipeline_run_sky_direct's sets and forms) ...
     if (in->direct != nullptr)
     {
@@ -1122,7 +1148,7 @@ extern "C" int grt_zenith_chunk(GrtSubcolumnArgs const *sc, GrtAerosolArgs const
 extern "C" int grt_launch_sw_zeniths(void *stream, GrtSwArgs const *a, GrtZenithArgs const *z, GrtSubcolumnArgs const *sc,
                                      GrtAerosolArgs const *ae)
 {
-    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (!grt_solver_instance_ok(in, *a) || z == nullptr || z->mu == nullptr || z->zeniths < 1 || !grt_sw_one_sweep(a) ||
         (sc != nullptr && !grt_subcolumn_args_ok(sc)) || (ae != nullptr && !grt_aerosol_args_ok(ae)))
     {
@@ -1164,7 +1190,7 @@ int launch_tiles(hipStream_t s, GrtSwArgs const &a, GrtTileArgs const &t, int dr
 extern "C" int grt_launch_sw_tiles(void *stream, GrtSwArgs const *a, GrtTileArgs const *t, GrtSubcolumnArgs const *sc,
                                    GrtAerosolArgs const *ae)
 {
-    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (a == nullptr || t == nullptr || !grt_solver_instance_ok(in, *a) || (!grt_sw_one_sweep(a) && a->park == nullptr) ||
         (sc != nullptr && !grt_subcolumn_args_ok(sc)) || (ae != nullptr && !grt_aerosol_args_ok(ae)))
     {

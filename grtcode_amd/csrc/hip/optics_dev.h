@@ -514,13 +514,25 @@ struct LayerOptics
 // more rows of wave sums behind the 2 V in dynamic LDS (3 V x kSolverBlock/64 doubles) --, to the join's own partial sums.
 // The longwave's surface-temperature Jacobian (GrtJacobianArgs) is the same third row group: lw_kernel hands every level's
 // dF_up/dT_surf to put_direct() and its partial sums' array in a GrtDirectArgs.
+// RESPONSES (profile form only, with or without DIRECT; GrtResponseArgs, grt_pipeline_run_sky_weighted): the broadband
+// group of G V rows (G = 2, 3 with DIRECT) is summed as without it -- x*pwt, the same wave_row_sum, the same rows --, and
+// each response of the block's list (block_start / block_resp: an explicit list, responses overlap) gets a group of G V
+// wave sums of its own behind it, of x*(pwt*r).  The products pwt*r of the list wait in dynamic LDS behind the wave sums,
+// [responses of the block][kSolverBlock], written once by the constructor -- each thread writes and reads its own entries
+// only, so no barrier is needed --: a list indexed per thread in registers would live in scratch memory.  finish() stores
+// response q's sums at its partials[(slot P + pair) G V + r], pair = first pair + block - first block of the response.  A
+// workgroup with an empty list does exactly the profile form's work.
 template <bool ON> struct DirectRows {};
 template <> struct DirectRows<true> { double out[3]; double *partials; };
+template <bool ON> struct ResponseRows {};
+template <> struct ResponseRows<true> { GrtResponseArgs a; int lo, count; double const *wt; };
 
-template <bool FUSED, bool PROFILE, bool SPECTRAL = false, bool BANDED = false, bool DIRECT = false>
+template <bool FUSED, bool PROFILE, bool SPECTRAL = false, bool BANDED = false, bool DIRECT = false, bool RESPONSES = false>
 struct LevelSink
 {
     static_assert(!DIRECT || (FUSED && !SPECTRAL && !BANDED), "the direct beam leaves the six-row and profile forms");
+    static_assert(!RESPONSES || (PROFILE && !BANDED), "the response rows leave the profile form");
+    static constexpr int GROUPS = DIRECT ? 3 : 2;   // RESPONSES: row groups of V rows per response (and of the broadband group)
     double *fu, *fd;            // spectral forms (and SPECTRAL): flux_up / flux_down at this thread's point
     uint64_t nw, i;
     int V, user, col;
@@ -531,11 +543,13 @@ struct LevelSink
     int bin_lo, bin_count;      // ... the first bin with a point in this workgroup, and how many there are
     double dw;
     DirectRows<DIRECT> direct;  // DIRECT
+    ResponseRows<RESPONSES> resp;   // RESPONSES
 
     template <typename Args>
     __device__ __forceinline__ LevelSink(Args const &a, int col_, uint64_t i_, bool live_,
                                          GrtBandArgs const &bins_ = GrtBandArgs{0, 0, nullptr, 0},
-                                         GrtDirectArgs const &direct_ = GrtDirectArgs{nullptr})
+                                         GrtDirectArgs const &direct_ = GrtDirectArgs{nullptr},
+                                         GrtResponseArgs const &resp_ = GrtResponseArgs{0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr})
     {
         if constexpr (DIRECT)
         {
@@ -566,12 +580,41 @@ struct LevelSink
         {
             out[k] = 0.;
         }
+        if constexpr (RESPONSES)
+        {
+            resp.a = resp_;
+            resp.lo = resp_.block_start[blockIdx.x];
+            resp.count = resp_.block_start[blockIdx.x + 1] - resp.lo;
+            // this thread's pwt*r of the block's responses, behind the (1 + count) groups of wave sums
+            double *wt = level_sums() + (size_t)(1 + resp.count)*GROUPS*V*(kSolverBlock/64) + threadIdx.x;
+            resp.wt = wt;
+            for (int q = 0; q < resp.count; ++q)
+            {
+                int const *e = resp_.resp + GRT_RESPONSE_INTS*resp_.block_resp[resp.lo + q];
+                long long const at = (long long)i - e[0];
+                wt[q*kSolverBlock] = live && at >= 0 && at < e[1] ? pwt*resp_.weights[e[2] + at] : 0.;
+            }
+        }
     }
 
     static __device__ __forceinline__ double *level_sums()
     {
-        extern __shared__ double level_sums_[];     // PROFILE: [2 V][kSolverBlock/64] (DIRECT: [3 V]); BANDED: that per bin of the block
+        // PROFILE: [2 V][kSolverBlock/64] (DIRECT: [3 V]); BANDED: that per bin of the block; RESPONSES: that once more per
+        // response of the block, then the staged weights [responses of the block][kSolverBlock]
+        extern __shared__ double level_sums_[];
         return level_sums_;
+    }
+
+    // RESPONSES: the value x of broadband row `row` once more per response of the block's list, weighted with its pwt*r
+    __device__ __forceinline__ void put_responses(int row, double x)
+    {
+        if constexpr (RESPONSES)
+        {
+            for (int q = 0; q < resp.count; ++q)
+            {
+                wave_row_sum<kSolverBlock>(x*resp.wt[q*kSolverBlock], level_sums(), (1 + q)*GROUPS*V + row);
+            }
+        }
     }
 
     // BANDED: this point's trapezoid weight in bin b -- dw/2 at the bin's two edges, dw between them, 0 elsewhere (an idle
@@ -602,6 +645,7 @@ struct LevelSink
         else if (PROFILE)
         {
             wave_row_sum<kSolverBlock>(x*pwt, level_sums(), (down ? V : 0) + lev);
+            put_responses((down ? V : 0) + lev, x);
         }
         else if (FUSED)
         {
@@ -622,6 +666,7 @@ struct LevelSink
         if constexpr (DIRECT && PROFILE)
         {
             wave_row_sum<kSolverBlock>(x*pwt, level_sums(), 2*V + lev);
+            put_responses(2*V + lev, x);
         }
         else if constexpr (DIRECT)
         {
@@ -641,6 +686,13 @@ struct LevelSink
                 for (int q = 0; q < (BANDED ? bin_count : 1); ++q)
                 {
                     level_sums()[(q*2*V + (down ? V : 0) + lev)*(kSolverBlock/64) + (threadIdx.x >> 6)] = 0.;
+                }
+                if constexpr (RESPONSES)
+                {
+                    for (int q = 1; q <= resp.count; ++q)
+                    {
+                        level_sums()[(q*GROUPS*V + (down ? V : 0) + lev)*(kSolverBlock/64) + (threadIdx.x >> 6)] = 0.;
+                    }
                 }
             }
         }
@@ -674,6 +726,20 @@ struct LevelSink
             {
                 block_row_partials<kSolverBlock>(level_sums() + 2*V*(kSolverBlock/64), V, direct.partials, (uint64_t)col*V,
                                                  gridDim.x, blockIdx.x);
+            }
+            if constexpr (RESPONSES)
+            {
+                // (block_row_partials per response of the block's list, behind its barrier)
+                int const rows = GROUPS*V;
+                double const *lds = level_sums() + rows*(kSolverBlock/64);
+                for (int k = threadIdx.x; k < resp.count*rows; k += kSolverBlock)
+                {
+                    int const q = k/rows, r = k - q*rows;
+                    int const *e = resp.a.resp + GRT_RESPONSE_INTS*resp.a.block_resp[resp.lo + q];
+                    uint64_t const pair = (uint64_t)(e[4] + (int)blockIdx.x - e[3]);
+                    resp.a.partials[((uint64_t)col*resp.a.per_row + pair)*rows + r] =
+                        waves_sum<kSolverBlock/64>(lds + k*(kSolverBlock/64));
+                }
             }
         }
         else if constexpr (DIRECT)

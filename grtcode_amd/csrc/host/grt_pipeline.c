@@ -281,6 +281,7 @@ static void grt_pipeline_release(GrtPipeline_t **pipeline)
         grt_keyed_table_free(p, &p->band[b].surf_map);
         grt_keyed_table_free(p, &p->band[b].channel_table);
         grt_keyed_table_free(p, &p->band[b].tile_map);
+        grt_keyed_table_free(p, &p->band[b].response_table);
         grt_kdist_table_free(p->device, &p->band[b].kdist_table);
     }
     grt_staging_free(p, &p->tile);
@@ -536,6 +537,10 @@ typedef struct GrtJoin
     GrtSurfaceTiles_t const *tiles;    /* grt_pipeline_run_sky_tiles: every set of both bands is solved over these surfaces
                                           per column (six rows; rows->out NULL: the tiles' own rows alone) */
     int tile_points[2];                /* ... the knots each band takes of them (grt_check_tiles) */
+    GrtResponses_t const *responses;   /* grt_pipeline_run_sky_weighted (profile form): every set's level rows of a band leave
+                                          under the band's responses too */
+    long long response_pairs[2];       /* ... each band's (response, solver block) pairs and the most responses in one */
+    int response_block_max[2];         /* block (grt_check_responses) */
 } GrtJoin;
 
 #define GRT_SKY_ALL (GRT_SKY_CLEAN | GRT_SKY_AEROSOL | GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL)
@@ -686,6 +691,17 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
         ps.channels = bi == 0 && join->channels != NULL ? &cr : NULL;
         ps.weighting = ps.channels != NULL && join->weighting != NULL ? &wr : NULL;
         ps.tiles = join->tiles != NULL ? &tr : NULL;
+        GrtResponseRun rsr;
+        if (join->responses != NULL && (bi == 0 ? join->responses->lw_num_responses : join->responses->sw_num_responses) > 0)
+        {
+            GrtResponses_t const *rs = join->responses;
+            GRT_TRY(grt_stage_responses(p, b, bi, rs, join->response_pairs[bi], join->response_block_max[bi], &rsr));
+            size_t const V = (size_t)p->num_levels, lw_rows = 2*(size_t)rs->lw_num_responses*V;
+            rsr.out = rs->weighted_levels_dev + (bi == 1 ? lw_rows : 0);
+            rsr.set_doubles = (uint64_t)(lw_rows + 3*(size_t)rs->sw_num_responses*V);
+            rsr.slots = (sets & (GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL)) != 0 ? S : 1;
+            ps.responses = &rsr;
+        }
         GrtAerosolArgs aa;
         int const band_aer = ae != NULL && grt_aerosol_points(ae, bi) > 0;
         int aa_ready = 0;
@@ -1244,6 +1260,96 @@ EXTERN int grt_pipeline_run_sky_jacobian(GrtPipeline_t *p, GrtColumns_t const *c
                             jacobian != NULL ? jacobian->jacobian_level_fluxes_dev : NULL, jacobian == NULL};
     GRT_TRY(run_sky(p, cols, sky, &third, level_fluxes_dev, heating_dev, fluxes_dev));
     return GRTCODE_SUCCESS;
+}
+
+/* grt_ext.h: grt_pipeline_run_sky's profile form, and every set's level rows under the bands' spectral responses */
+EXTERN int grt_pipeline_run_sky_weighted(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky,
+                                         GrtResponses_t const *rs, fp_t *level_fluxes_dev, fp_t *heating_dev,
+                                         fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    if (rs == NULL || rs->weighted_levels_dev == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%s is NULL: the weighted level rows [ncol][sets][2 R_lw + 3 R_sw][V] are the output.",
+                 rs == NULL ? "responses (GrtResponses_t)" : "weighted_levels_dev");
+    }
+    GrtJoin weighted;
+    memset(&weighted, 0, sizeof(weighted));
+    for (int bi = 0; bi < 2; ++bi)
+    {
+        GrtBand const *b = &p->band[bi];
+        GRT_TRY(grt_check_responses(rs, bi, b->gas != NULL ? (long long)b->n : 0, grt_pipeline_response_block_limit(p, bi),
+                                    &weighted.response_pairs[bi], &weighted.response_block_max[bi]));
+    }
+    if (rs->lw_num_responses == 0 && rs->sw_num_responses == 0)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "no responses in either band: nothing to weight.%s", "");
+    }
+    if (rs->actinic_levels_dev != NULL && rs->sw_num_responses == 0)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "actinic_levels_dev is given without shortwave responses.%s", "");
+    }
+    if (level_fluxes_dev == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "level_fluxes_dev is NULL: the call is grt_pipeline_run_sky's profile form.%s", "");
+    }
+    int nsets;
+    GRT_TRY(check_sky_sets(sky, &nsets));
+    GrtPass rows;
+    GRT_TRY(output_form(p, nsets, level_fluxes_dev, fluxes_dev, &rows));
+    GrtAerosols_t a;
+    GrtJoin join;
+    GRT_TRY(sky_join(p, cols, sky, &a, &join));
+    join.responses = rs;
+    memcpy(join.response_pairs, weighted.response_pairs, sizeof(join.response_pairs));
+    memcpy(join.response_block_max, weighted.response_block_max, sizeof(join.response_block_max));
+    int const V = p->num_levels;
+    if (rs->sw_num_responses > 0)
+    {
+        /* the shortwave's response rows ride with the direct beam's: its levels go to the pipeline's own block */
+        GRT_TRY(check_lane(p));
+        GrtScratch *own = &p->band[1].scratch[GRT_SCRATCH_DIRECT_LEVELS];
+        GRT_TRY(grt_scratch_need(p, own, (size_t)p->max_cols*GRT_SKY_MAX_SETS*(size_t)V, NULL));
+        rows.direct = own->d;
+    }
+    GRT_TRY(pipeline_run(p, cols, &join, &rows));
+    GRT_TRY(finish_profiles(p, cols->ncol, &rows, heating_dev, fluxes_dev));
+    if (rs->actinic_levels_dev != NULL)
+    {
+        void *s = grt_dev_stream(p->device);
+        uint64_t const lw_rows = 2*(uint64_t)rs->lw_num_responses*(uint64_t)V;
+        int const slot = grt_profile_begin(s, GRT_TAG_BAND_PROFILES);
+        int const krc = grt_launch_actinic_rows(s, rs->weighted_levels_dev + lw_rows,
+                                                lw_rows + 3*(uint64_t)rs->sw_num_responses*(uint64_t)V, cols->ncol, nsets,
+                                                rs->sw_num_responses, V, p->small.d + p->off_mu, 0.5, rs->actinic_levels_dev);
+        grt_profile_end(s, slot);
+        GRT_TRY(grt_dev_check(krc, "actinic flux kernel"));
+    }
+    return GRTCODE_SUCCESS;
+}
+
+/* grt_ext.h: the (response, solver block) pairs of a band's responses on a grid of num_points; -1: responses the call refuses */
+EXTERN long long grt_response_pair_count(GrtResponses_t const *rs, int band, long long num_points)
+{
+    long long pairs;
+    int block_max;
+    if (rs == NULL || band < 0 || band > 1 || num_points < 1 ||
+        grt_check_responses(rs, band, num_points, -1, &pairs, &block_max) != GRTCODE_SUCCESS)
+    {
+        return -1;
+    }
+    return pairs;
+}
+
+/* grt_ext.h: the most responses of a band with a point in one solver block at this pipeline's V */
+EXTERN int grt_pipeline_response_block_limit(GrtPipeline_t const *p, int band)
+{
+    if (p == NULL || band < 0 || band > 1)
+    {
+        return -1;
+    }
+    return grt_response_block_limit(p->num_levels, band == 0 ? 2 : 3);
 }
 
 /* grt_pipeline_run_sky_radiances, and -- channels_asked -- grt_pipeline_run_sky_channels, which is the same call with the

@@ -873,6 +873,184 @@ int grt_stage_channels(GrtPipeline_t *p, GrtBand *b, GrtChannels_t const *ch, lo
     return GRTCODE_SUCCESS;
 }
 
+/* ---- spectral responses of the level fluxes (grt_pipeline_run_sky_weighted) ---- */
+
+/* band bi's four fields of rs */
+typedef struct BandResponses { int count; int const *first, *offset; fp_t const *weights; } BandResponses;
+
+static BandResponses band_responses(GrtResponses_t const *rs, int bi)
+{
+    BandResponses const lw = {rs->lw_num_responses, rs->lw_first, rs->lw_offset, rs->lw_weights};
+    BandResponses const sw = {rs->sw_num_responses, rs->sw_first, rs->sw_offset, rs->sw_weights};
+    return bi == 0 ? lw : sw;
+}
+
+/* What grt_pipeline_run_sky_weighted and grt_response_pair_count check of one band's responses on a grid of n points (a
+   band without responses: nothing).  Nothing is touched. */
+int grt_check_responses(GrtResponses_t const *rs, int bi, long long n, int block_limit, long long *pairs, int *block_max)
+{
+    char const *name = bi == 0 ? "longwave" : "shortwave";
+    BandResponses const r = band_responses(rs, bi);
+    *pairs = 0;
+    *block_max = 0;
+    if (r.count < 0 || r.count > GRT_MAX_RESPONSES)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s responses asked for: 0 to %d.", r.count, name, GRT_MAX_RESPONSES);
+    }
+    if (r.count == 0)
+    {
+        return GRTCODE_SUCCESS;
+    }
+    if (r.first == NULL || r.offset == NULL || r.weights == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%s of the %s responses is NULL.",
+                 r.first == NULL ? "first" : (r.offset == NULL ? "offset" : "weights"), name);
+    }
+    if (n < 1)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s responses, and this pipeline has no %s band.", r.count, name, name);
+    }
+    if (r.offset[0] != 0)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "offset[0] of the %s responses is %d: the first response's weights start at 0.", name,
+                 r.offset[0]);
+    }
+    long long P = 0;
+    for (int k = 0; k < r.count; ++k)
+    {
+        if (r.offset[k + 1] <= r.offset[k])
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "%s offset[%d] = %d is not above offset[%d] = %d: a response has at least one point.",
+                     name, k + 1, r.offset[k + 1], k, r.offset[k]);
+        }
+        long long const count = (long long)r.offset[k + 1] - r.offset[k];
+        if (r.first[k] < 0 || r.first[k] + count > n)
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "%s response %d takes the points %d .. %lld of a band of %lld.", name, k, r.first[k],
+                     r.first[k] + count - 1, n);
+        }
+        for (int j = r.offset[k]; j < r.offset[k + 1]; ++j)
+        {
+            if (!isfinite(r.weights[j]))
+            {
+                GRT_FAIL(GRTCODE_VALUE_ERR, "weight %d of %s response %d (%e) is NaN or infinite.", j - r.offset[k], name, k,
+                         r.weights[j]);
+            }
+        }
+        P += (r.first[k] + count - 1)/GRT_SOLVER_BLOCK - r.first[k]/GRT_SOLVER_BLOCK + 1;
+    }
+    /* the most responses with a point in one block: a count per block */
+    size_t const nblocks = (size_t)((n + GRT_SOLVER_BLOCK - 1)/GRT_SOLVER_BLOCK);
+    int *held = calloc(nblocks, sizeof(int));
+    if (held == NULL)
+    {
+        GRT_FAIL(GRTCODE_NULL_ERR, "out of host memory for the response counts of %zu blocks.", nblocks);
+    }
+    int most = 0, most_at = 0;
+    for (int k = 0; k < r.count; ++k)
+    {
+        long long const last = r.first[k] + ((long long)r.offset[k + 1] - r.offset[k]) - 1;
+        for (long long blk = r.first[k]/GRT_SOLVER_BLOCK; blk <= last/GRT_SOLVER_BLOCK; ++blk)
+        {
+            if (++held[blk] > most)
+            {
+                most = held[blk];
+                most_at = (int)blk;
+            }
+        }
+    }
+    free(held);
+    if (block_limit >= 0 && most > block_limit)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s responses have a point in block %d (points %d .. %d): at most %d "
+                 "(grt_pipeline_response_block_limit).", most, name, most_at, most_at*GRT_SOLVER_BLOCK,
+                 most_at*GRT_SOLVER_BLOCK + GRT_SOLVER_BLOCK - 1, block_limit);
+    }
+    *pairs = P;
+    *block_max = most;
+    return GRTCODE_SUCCESS;
+}
+
+/* The device table of a band's responses (GrtResponseArgs, grt_kernels.h), as grt_keyed_table keeps it: the doubles first
+   (the table is a device allocation: aligned for them), then the ints. */
+typedef struct ResponseTableFill
+{
+    BandResponses r;
+    size_t nblocks, doubles;
+} ResponseTableFill;
+
+static int fill_response_table(void *ctx, int *table)
+{
+    ResponseTableFill *f = ctx;
+    BandResponses const *r = &f->r;
+    int const R = r->count;
+    int *resp = table + 2*f->doubles, *block_start = resp + (size_t)GRT_RESPONSE_INTS*R, *block_resp = block_start + f->nblocks + 1;
+    memcpy(table, r->weights, sizeof(double)*f->doubles);
+    memset(block_start, 0, sizeof(int)*(f->nblocks + 1));
+    int pair = 0;
+    for (int k = 0; k < R; ++k)
+    {
+        int const first = r->first[k], count = r->offset[k + 1] - r->offset[k];
+        int const b_lo = first/GRT_SOLVER_BLOCK, b_hi = (first + count - 1)/GRT_SOLVER_BLOCK;
+        int *e = resp + (size_t)GRT_RESPONSE_INTS*k;
+        e[0] = first; e[1] = count; e[2] = r->offset[k]; e[3] = b_lo; e[4] = pair;
+        pair += b_hi - b_lo + 1;
+        for (int b = b_lo; b <= b_hi; ++b)
+        {
+            ++block_start[b + 1];               /* (counts first, then their running sum) */
+        }
+    }
+    for (size_t b = 0; b < f->nblocks; ++b)
+    {
+        block_start[b + 1] += block_start[b];
+    }
+    /* the responses of a block in ascending order; fill[] walks each block's list */
+    int *fill = malloc(sizeof(int)*(f->nblocks > 0 ? f->nblocks : 1));
+    if (fill == NULL)
+    {
+        GRT_FAIL(GRTCODE_NULL_ERR, "out of host memory for a response table of %zu blocks.", f->nblocks);
+    }
+    memcpy(fill, block_start, sizeof(int)*f->nblocks);
+    for (int k = 0; k < R; ++k)
+    {
+        int const *e = resp + (size_t)GRT_RESPONSE_INTS*k;
+        for (int b = e[3]; b <= (e[0] + e[1] - 1)/GRT_SOLVER_BLOCK; ++b)
+        {
+            block_resp[fill[b]++] = k;
+        }
+    }
+    free(fill);
+    return GRTCODE_SUCCESS;
+}
+
+/* Band bi's responses of a grt_pipeline_run_sky_weighted call (checked by grt_check_responses on b's grid, which gave
+   `pairs` and `block_max`) as the band's device table -- built and uploaded when first, offset or weights differ from the
+   last call's */
+int grt_stage_responses(GrtPipeline_t *p, GrtBand *b, int bi, GrtResponses_t const *rs, long long pairs, int block_max,
+                        GrtResponseRun *rr)
+{
+    ResponseTableFill f = {band_responses(rs, bi), grt_solver_blocks(b->n), 0};
+    int const R = f.r.count;
+    f.doubles = (size_t)f.r.offset[R];
+    /* the key: the grid's points and R, then first, offset and weights */
+    long long const h[2] = {(long long)b->n, R};
+    GrtKeyPart const key[4] = {{h, sizeof(h)}, {f.r.first, sizeof(int)*(size_t)R}, {f.r.offset, sizeof(int)*((size_t)R + 1)},
+                               {f.r.weights, sizeof(double)*f.doubles}};
+    size_t const table_ints = 2*f.doubles + (size_t)GRT_RESPONSE_INTS*R + f.nblocks + 1 + (size_t)pairs;
+    GRT_TRY(grt_keyed_table_parts(p, &b->response_table, key, 4, table_ints, fill_response_table, &f));
+    memset(rr, 0, sizeof(*rr));
+    GrtResponseArgs *a = &rr->args;
+    a->responses = R;
+    a->block_max = block_max;
+    a->per_row = (uint64_t)pairs;
+    a->weights = (double const *)b->response_table.table;
+    a->resp = b->response_table.table + 2*f.doubles;
+    a->block_start = a->resp + (size_t)GRT_RESPONSE_INTS*R;
+    a->block_resp = a->block_start + f.nblocks + 1;
+    rr->groups = bi == 0 ? 2 : 3;
+    return GRTCODE_SUCCESS;
+}
+
 /* ---- channel transmittances and contribution functions (grt_pipeline_run_sky_weighting) ---- */
 
 /* What grt_pipeline_run_sky_weighting checks of its own argument.  Nothing is touched. */

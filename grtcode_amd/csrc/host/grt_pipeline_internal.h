@@ -109,6 +109,10 @@ enum
     /* ... [max_cols][T][S][6][nblocks] partial sums of every tile and cloud draw, S = 1 but in a cloud set, its sets in
        turn in stream order (materialised form: [max_cols][T][S][6] integrated rows); replaced when a call needs more */
     GRT_SCRATCH_TILE_PARTIALS,
+    /* grt_pipeline_run_sky_weighted, both forms: [max_cols][S][P][G V] the responses' partial sums per (response, solver
+       block) pair, S the draws of the call's cloud sets (1 without one) for every set of the call, G = 2 (longwave) or 3
+       (shortwave); sized at the first call that needs more */
+    GRT_SCRATCH_RESPONSE_PARTIALS,
     GRT_SCRATCH_COUNT
 };
 
@@ -153,6 +157,9 @@ typedef struct GrtBand
     GrtKeyedTable channel_table;
     /* grt_pipeline_run_sky_tiles: [n] entry of the band's tile grid each grid point takes, as surf_map; its key: that grid */
     GrtKeyedTable tile_map;
+    /* grt_pipeline_run_sky_weighted: the band's response table (GrtResponseArgs: the weights, then the responses' and the
+       blocks' ints); its key: the grid's points and the responses' first, offset, weights */
+    GrtKeyedTable response_table;
     int surf_set, surf_dif_set;    /* the surface in force gives this band rows (, and diffuse rows of their own) */
 } GrtBand;
 
@@ -225,6 +232,17 @@ typedef struct GrtWeightingRun
     double *contribution;           /* DEVICE [ncol][sets][A][V + 1][C], or NULL */
 } GrtWeightingRun;
 
+/* The responses of a grt_pipeline_run_sky_weighted call on one band, staged (grt_stage_responses): the band's table on the
+   device (args.partials: set by the pass's launch), and where every set's rows of the band go. */
+typedef struct GrtResponseRun
+{
+    GrtResponseArgs args;
+    int groups;                     /* G: 2 (longwave: up, down) or 3 (shortwave: up, down, direct) */
+    double *out;                    /* DEVICE: the band's rows of column 0, set 0 in weighted_levels_dev */
+    uint64_t set_doubles;           /* (2 R_lw + 3 R_sw) V: from one set to the next */
+    int slots;                      /* slots per column of the scratch: the most draws any set of the call has */
+} GrtResponseRun;
+
 /* One solve of a band on the run's tau_gas.  What joins gas and Rayleigh: nothing (clear sky), the cloud objects (all-sky
    pass), the aerosol object (aerosol pass; aer NULL there: a band that was given no aerosol, which runs the form without
    the object under the aerosol pass's profile tags) or both (grt_pipeline_run_sky's complete set).  Which rows leave: the six of driver.c:272-280 or (profile) every level's
@@ -261,6 +279,9 @@ typedef struct GrtPass
     /* grt_pipeline_run_sky_tiles (NULL: not asked for; six rows only): every band's solve is grt_band_solve_tiles', the mean
        over the tiles to out (may be NULL) and every tile's rows to the pass's set of tiles->per_tile */
     struct GrtTileRun const *tiles;
+    /* grt_pipeline_run_sky_weighted (NULL: not asked for, or the band has no responses; profile form only, the shortwave
+       with `direct`): the band's level rows leave under its responses too, to the pass's set of responses->out */
+    GrtResponseRun const *responses;
 } GrtPass;
 
 /* The surface tiles of a grt_pipeline_run_sky_tiles call, staged (grt_stage_tiles): T per column, their temperatures and
@@ -329,6 +350,12 @@ GRT_PRIVATE int grt_stage_radiances(GrtPipeline_t *p, GrtRadiances_t const *rd, 
 GRT_PRIVATE int grt_check_channels(GrtChannels_t const *ch, long long n, long long *pairs);
 GRT_PRIVATE int grt_stage_channels(GrtPipeline_t *p, GrtBand *b, GrtChannels_t const *ch, long long pairs,
                                    GrtChannelRun *cr);
+/* one band's responses (bi: 0 longwave, 1 shortwave) on a grid of n points and at most block_limit in one block (< 0: not
+   checked); *pairs, *block_max: its (response, block) pairs and the most responses in one block */
+GRT_PRIVATE int grt_check_responses(GrtResponses_t const *rs, int bi, long long n, int block_limit, long long *pairs,
+                                    int *block_max);
+GRT_PRIVATE int grt_stage_responses(GrtPipeline_t *p, GrtBand *b, int bi, GrtResponses_t const *rs, long long pairs,
+                                    int block_max, GrtResponseRun *rr);
 GRT_PRIVATE int grt_check_weighting(GrtWeighting_t const *wt);
 GRT_PRIVATE void grt_stage_weighting(GrtWeighting_t const *wt, GrtWeightingRun *wr);
 GRT_PRIVATE int grt_band_bins(GrtPipeline_t *p, GrtBand *b, int const *edges, int nbins, int rows);

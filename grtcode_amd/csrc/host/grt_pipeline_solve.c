@@ -28,6 +28,9 @@ typedef struct ThirdRows
     double *partials;
     GrtDirectArgs direct;
     GrtJacobianArgs jacobian;
+    /* grt_pipeline_run_sky_weighted: the band's response rows leave too (response_partials; with_responses 0: they do not) */
+    int with_responses;
+    GrtResponseArgs responses;
 } ThirdRows;
 
 /* its solver instance (materialised: the spectral form, after pass_optics); bn: its per-bin instance; sc: the pass's
@@ -35,7 +38,7 @@ typedef struct ThirdRows
 static GrtSolverInstance pass_instance(GrtPipeline_t const *p, GrtPass const *ps, GrtBandArgs const *bn,
                                        GrtSubcolumnArgs const *sc, ThirdRows const *tr, int bi)
 {
-    GrtSolverInstance in = {GRT_OUT_CHAINS, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
+    GrtSolverInstance in = {GRT_OUT_CHAINS, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
     if (!p->keep_spectra)
     {
         in.out = pass_spectral(ps) ? GRT_OUT_ROWS_POINTS : (bn != NULL ? GRT_OUT_LEVEL_BINS :
@@ -49,6 +52,7 @@ static GrtSolverInstance pass_instance(GrtPipeline_t const *p, GrtPass const *ps
             in.direct = bi == 1 ? &tr->direct : NULL;
             in.jacobian = bi == 0 ? &tr->jacobian : NULL;
         }
+        in.responses = tr != NULL && tr->with_responses ? &tr->responses : NULL;
     }
     return in;
 }
@@ -92,6 +96,67 @@ static int direct_partials(GrtPipeline_t *p, GrtBand *b, int bi, GrtPass const *
         GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*(size_t)slots*(size_t)direct_rows(p, ps)*b->nblocks, NULL));
         tr->partials = tr->direct.partials = tr->jacobian.partials = block->d;
     }
+    return GRTCODE_SUCCESS;
+}
+
+/* grt_pipeline_run_sky_weighted: the pass's response table with the band's partial sums of `slots` slots per column
+   (GRT_SCRATCH_RESPONSE_PARTIALS, [max_cols][slots][P][G V], sized for the call's largest set at once), as *ra */
+static int response_partials(GrtPipeline_t *p, GrtBand *b, GrtPass const *ps, int slots, GrtResponseArgs *ra)
+{
+    GrtResponseRun const *rr = ps->responses;
+    GrtScratch *block = &b->scratch[GRT_SCRATCH_RESPONSE_PARTIALS];
+    size_t const most = (size_t)(rr->slots > slots ? rr->slots : slots);
+    GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*most*(size_t)rr->args.per_row*(size_t)rr->groups*
+                                       (size_t)p->num_levels, NULL));
+    *ra = rr->args;
+    ra->partials = block->d;
+    return GRTCODE_SUCCESS;
+}
+
+/* ... fused form: as the join of the pass's instance in *tr, behind direct_partials (a pass without responses: nothing) */
+static int response_join(GrtPipeline_t *p, GrtBand *b, GrtPass const *ps, int slots, ThirdRows *tr)
+{
+    if (ps->responses != NULL)
+    {
+        GRT_TRY(response_partials(p, b, ps, slots, &tr->responses));
+        tr->with_responses = 1;
+    }
+    return GRTCODE_SUCCESS;
+}
+
+/* ... and what turns the partial sums of its S draws into the pass's set of the band's response rows: the finishing kernel
+   (GRT_TAG_BAND_PROFILES), each response's blocks in the fixed-order sum's association, the draws in order, one division */
+static int finish_responses(GrtPipeline_t *p, int C, int S, GrtPass const *ps, GrtResponseArgs const *ra)
+{
+    GrtResponseRun const *rr = ps->responses;
+    void *s = grt_dev_stream(p->device);
+    int const slot = grt_profile_begin(s, GRT_TAG_BAND_PROFILES);
+    int const krc = grt_launch_response_finish(s, ra, rr->groups, C, S, p->num_levels, rr->out,
+                                               (uint64_t)ps->sets*rr->set_doubles, (uint64_t)ps->set*rr->set_doubles);
+    grt_profile_end(s, slot);
+    GRT_TRY(grt_dev_check(krc, "response finishing kernel"));
+    return GRTCODE_SUCCESS;
+}
+
+/* Materialised form of the response rows: from the [C][V][n] fluxes the pass (the mean over its subcolumns) has left in the
+   band's arrays -- and, shortwave, its direct beam in GRT_SCRATCH_DIRECT_BEAM --, the same weights and sums into the same
+   partial sums, one slot per column, then the same finishing kernel (both under GRT_TAG_BAND_PROFILES) */
+static int response_rows(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *ps)
+{
+    if (ps->responses == NULL)
+    {
+        return GRTCODE_SUCCESS;
+    }
+    GrtResponseRun const *rr = ps->responses;
+    void *s = grt_dev_stream(p->device);
+    GrtResponseArgs ra;
+    GRT_TRY(response_partials(p, b, ps, 1, &ra));
+    double const *const rows[3] = {b->flux_up, b->flux_down, rr->groups == 3 ? b->scratch[GRT_SCRATCH_DIRECT_BEAM].d : NULL};
+    int const slot = grt_profile_begin(s, GRT_TAG_BAND_PROFILES);
+    int const krc = grt_launch_response_rows(s, &ra, rows, rr->groups, C, p->num_levels, b->n, b->gas->grid.dw);
+    grt_profile_end(s, slot);
+    GRT_TRY(grt_dev_check(krc, "response row kernel"));
+    GRT_TRY(finish_responses(p, C, 1, ps, &ra));
     return GRTCODE_SUCCESS;
 }
 
@@ -699,6 +764,7 @@ int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *p
             GRT_TRY(direct_beam(p, b, bi, C, ps));
             GRT_TRY(direct_integrate(p, b, bi, C, ps));
         }
+        GRT_TRY(response_rows(p, b, C, ps));
         if (pass_radiances(ps, bi))
         {
             GRT_TRY(band_radiances(p, b, C, 1, 0, ps, NULL));
@@ -713,6 +779,7 @@ int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *p
         int const rows = pass_rows(p, ps);
         ThirdRows da;
         GRT_TRY(direct_partials(p, b, bi, ps, 1, &da));
+        GRT_TRY(response_join(p, b, ps, 1, &da));
         if (ps->profile)
         {
             GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_LEVEL_PARTIALS], (size_t)p->max_cols*(size_t)rows*b->nblocks,
@@ -730,6 +797,10 @@ int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *p
                                                              third_out(ps, bi), drows, direct_stride(p, ps),
                                                              direct_offset(p, ps)),
                                   bi == 1 ? "direct-beam reduction kernel" : "surface Jacobian reduction kernel"));
+        }
+        if (da.with_responses)
+        {
+            GRT_TRY(finish_responses(p, C, 1, ps, &da.responses));
         }
     }
     if (pass_radiances(ps, bi))
@@ -772,6 +843,7 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
         GrtSubcolumnArgs sc = {*ps->clouds, S, 0, 0};
         ThirdRows da;
         GRT_TRY(direct_partials(p, b, bi, ps, S, &da));
+        GRT_TRY(response_join(p, b, ps, S, &da));
         int const drows = direct_rows(p, ps);
         GrtSolverInstance const in = pass_instance(p, ps, NULL, &sc, &da, bi);
         SolverArgs a;
@@ -794,6 +866,10 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
             GRT_TRY(finish_radiances(p, b, C, S, ps));
             GRT_TRY(finish_channels(p, b, C, S, ps));
             GRT_TRY(finish_weighting(p, b, C, S, ps));
+        }
+        if (da.with_responses)
+        {
+            GRT_TRY(finish_responses(p, C, S, ps, &da.responses));
         }
         if (S == 1)
         {
@@ -874,6 +950,7 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
                               "flux mean kernel"));
         GRT_TRY(direct_integrate(p, b, bi, C, ps));
     }
+    GRT_TRY(response_rows(p, b, C, ps));
     return GRTCODE_SUCCESS;
 }
 

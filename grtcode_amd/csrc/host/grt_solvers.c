@@ -208,7 +208,7 @@ EXTERN int calculate_lw_fluxes(Longwave_t * const lw, Optics_t const * const opt
     /* GRT_LW_COLUMN_CHAINS=1: one thread per wavenumber through all the layers, as before round 4 (same fluxes) */
     char const *chains = getenv("GRT_LW_COLUMN_CHAINS");
     GrtSolverInstance const in = {(chains != NULL && chains[0] == '1') || !block_has_scratch(lw->device, lw->layer_temperature, lw->flux_down + n*(size_t)V, sizeof(fp_t)*6*n*(size_t)(V - 1))
-                                  ? GRT_OUT_CHAINS : GRT_OUT_LAYERS, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
+                                  ? GRT_OUT_CHAINS : GRT_OUT_LAYERS, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
     a.layer_terms = in.out == GRT_OUT_LAYERS ? lw->flux_down + n*(size_t)V : NULL;
     GRT_TRY(grt_dev_check(grt_launch_lw(s, &in, &a), "longwave kernel"));
     GRT_TRY(download_fluxes(lw->device, V, n, flux_up, flux_down, lw->flux_up, lw->flux_down, s));
@@ -299,7 +299,7 @@ EXTERN int calculate_sw_fluxes(Shortwave_t * const sw, Optics_t const * const op
     /* GRT_SW_COLUMN_CHAINS=1: one thread per wavenumber through all the layers, as before round 4 (same fluxes) */
     char const *chains = getenv("GRT_SW_COLUMN_CHAINS");
     GrtSolverInstance const in = {(chains != NULL && chains[0] == '1') || !block_has_scratch(sw->device, sw->solar_flux, sw->flux_down + n*(size_t)V, sizeof(fp_t)*5*n*(size_t)(V - 1))
-                                  ? GRT_OUT_CHAINS : GRT_OUT_LAYERS, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
+                                  ? GRT_OUT_CHAINS : GRT_OUT_LAYERS, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
     a.layer_props = in.out == GRT_OUT_LAYERS ? sw->flux_down + n*(size_t)V : NULL;
     GRT_TRY(grt_dev_check(grt_launch_sw(s, &in, &a), "shortwave kernel"));
     GRT_TRY(download_fluxes(sw->device, V, n, flux_up, flux_down, sw->flux_up, sw->flux_down, s));

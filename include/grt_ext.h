@@ -1093,6 +1093,79 @@ typedef struct GrtSurfaceTiles
 EXTERN int grt_pipeline_run_sky_tiles(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtSky_t const *sky,
                                       GrtSurfaceTiles_t const *tiles, fp_t *fluxes_dev /* [ncol][N][12] or NULL */);
 
+/* ---- response-weighted level fluxes and actinic flux, of every sky set ----------------------------------------------
+ * grt_pipeline_run_sky in its PROFILE FORM in every respect -- the sets and their packing, the surface in force, the input
+ * checks, asynchronous on the pipeline's lane, the two-sweep shortwave, every output it writes (level_fluxes_dev is
+ * required; heating_dev and fluxes_dev may be NULL) -- and beside them the same level rows under spectral weights that
+ * are not a box: a photolysis cross-section times quantum yield, the erythemal action spectrum, photon-weighted PAR, the
+ * response of a pyranometer, a pyrgeometer dome or a window channel -- reduced on the device, so that no [V][n] row has
+ * to leave it.  Response k of a band is the grid points i = first[k] + j, j = 0 .. count_k - 1 (count_k = offset[k + 1] -
+ * offset[k]) with r_k(i) = weights[offset[k] + j], and 0 elsewhere.  Responses may overlap, repeat, come in any order, be
+ * one point wide and carry any finite sign; they are NOT normalised.  With t_i the whole band's trapezoid weight (dw, dw/2
+ * at the points 0 and n - 1),
+ *   X_k(level) = sum_i (t_i r_k(i)) F_i(level),      W m-2 x the unit of r,
+ * each term formed as F (t r); F is the level's upward flux, its downward flux and, in the shortwave, its direct beam
+ * (grt_pipeline_run_sky_direct's: the delta-scaled beam, per unit horizontal area).
+ *   weighted_levels_dev [ncol][N][2 R_lw + 3 R_sw][V] (required): per set the longwave's [R_lw][2][V] (up, down), then the
+ *                       shortwave's [R_sw][3][V] (up, down, direct); levels top first.  A band with no responses takes no
+ *                       room; at least one band must have some.
+ *   actinic_levels_dev  [ncol][N][R_sw][V] (may be NULL): the actinic flux of the shortwave responses,
+ *                         A_k(level) = (S_k/mu0 + (D_k - S_k)/mu_dif) + U_k/mu_dif,
+ *                       formed in that order from the three finished rows (S direct, D down, U up); mu0 the column's
+ *                       cos_zenith, mu_dif the solver's 0.5 (driver.c:110).  The direct beam counts once per unit area
+ *                       normal to it, each diffuse hemisphere is taken as isotropic, as every delta-two-stream actinic
+ *                       flux is; the beam is the DELTA-SCALED one, so forward-scattered light counts as beam.
+ * A cloud set's row is the mean over its num_subcolumns draws, 0 .. S - 1 in order, then one division by S; its actinic
+ * flux is formed from the means.  A band the pipeline lacks can carry no responses and has no rows here (its rows of
+ * level_fluxes_dev are zeros, as grt_pipeline_run_sky writes them).
+ * Identities (deterministic mode, bit for bit): every output grt_pipeline_run_sky also writes is grt_pipeline_run_sky's;
+ * the response r = 1 on the whole grid gives level_fluxes_dev's rows of the band and grt_pipeline_run_sky_direct's
+ * direct_level_fluxes_dev; a response's rows do not depend on the other responses, columns or sets of the call; 2 r gives
+ * twice the rows, -r their negatives; D_k = S_k at the top level.
+ * How it runs (keep_spectra = 0): the profile solvers in their response form (the passes' own tags) -- the broadband rows
+ * summed as ever, and per response that has a point in a workgroup's 128 grid points one more group of wave sums, the
+ * products t r staged in LDS; a workgroup outside every response does the profile form's work --, their sums stored
+ * without atomics per (response, solver block) pair; then a finishing kernel of one thread per output row and the actinic
+ * kernel (both under GRT_TAG_BAND_PROFILES).  keep_spectra = 1: the spectral solvers and the direct-beam kernel
+ * (GRT_TAG_DIRECT_BEAM), a kernel that applies the same weights and sums to the [V][n] rows, the same finishing kernels.
+ * Scratch per band: max_columns x S x P x G V doubles at the first call that needs more, G = 2 (longwave) or 3
+ * (shortwave), S the draws of the call's cloud sets (1 without one), P = grt_response_pair_count(responses, band, n) --
+ * about n/128 for a response over the whole grid: broad responses are the expensive ones.  The device tables are kept and
+ * reused while first, offset and weights hold the same values.
+ * grt_response_pair_count: host code only.  P, the number of (response, 128-point solver block) pairs in which a response
+ * of `band` (0 longwave, 1 shortwave) has a point on a grid of num_points points; 0 for a band without responses; -1 for
+ * anything the entry point would refuse in that band's four fields, for another band and for num_points < 1.
+ * grt_pipeline_response_block_limit: the most responses that may have a point in one block of 128 consecutive grid points
+ * (block b: points 128 b .. 128 b + 127) at this pipeline's V: the workgroup's wave sums and staged weights must fit its
+ * 64 KiB of LDS, 16 G V (1 + R_b) + 1024 R_b <= 65536 -- 15 in the shortwave and 21 in the longwave at V = 61.  -1 for
+ * another band.
+ * GRTCODE_VALUE_ERR, with nothing launched and every output untouched, for: responses NULL; weighted_levels_dev NULL;
+ * both counts 0; a count outside 0 .. GRT_MAX_RESPONSES; a count > 0 with first, offset or weights NULL; responses for a
+ * band the pipeline lacks; offset[0] != 0 or offset not strictly increasing; first[k] < 0 or first[k] + count_k > n; a
+ * weight that is NaN or infinite; more responses in one block than the limit; actinic_levels_dev with sw_num_responses
+ * == 0; level_fluxes_dev NULL; everything grt_pipeline_run_sky refuses.  A night column: GRTCODE_RANGE_ERR, as everywhere.
+ * Not covered: the several-sun-angle and surface-tile entry points, cloud fields sampled on the device, weighted heating
+ * rates, the Jacobian rows, the example drivers. */
+#define GRT_MAX_RESPONSES 256                 /* per band */
+typedef struct GrtResponses
+{
+    int lw_num_responses;          /* R_lw, 0 .. GRT_MAX_RESPONSES */
+    int const *lw_first;           /* HOST [R_lw]: grid index of the response's first point in the longwave band */
+    int const *lw_offset;          /* HOST [R_lw + 1]: offset[0] = 0, strictly increasing */
+    fp_t const *lw_weights;        /* HOST [lw_offset[R_lw]]: r_k sampled on the grid, response after response */
+    int sw_num_responses;          /* R_sw: the same of the shortwave band */
+    int const *sw_first;
+    int const *sw_offset;
+    fp_t const *sw_weights;
+    fp_t *weighted_levels_dev;     /* DEVICE [ncol][N][2 R_lw + 3 R_sw][V]; required */
+    fp_t *actinic_levels_dev;      /* DEVICE [ncol][N][R_sw][V]; may be NULL */
+} GrtResponses_t;
+EXTERN int grt_pipeline_run_sky_weighted(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtSky_t const *sky,
+                                         GrtResponses_t const *responses, fp_t *level_fluxes_dev, fp_t *heating_dev,
+                                         fp_t *fluxes_dev);
+EXTERN long long grt_response_pair_count(GrtResponses_t const *responses, int band /* 0 lw, 1 sw */, long long num_points);
+EXTERN int grt_pipeline_response_block_limit(GrtPipeline_t const *pipeline, int band);
+
 /* ---- columns across the GPUs of one node ------------------------------------
  * One process per GPU; contiguous ceil-sized column blocks; one gather of the [columns][GRT_FLUXES_PER_COLUMN]
  * flux blocks to rank 0.  The reference fans out processes with -x/-X column ranges and merges per-shard files
@@ -1157,7 +1230,9 @@ enum
     GRT_TAG_AEROSOL_LW = 12,
     GRT_TAG_AEROSOL_SW = 13,
     /* 14 = the per-bin reduction and the heating-rate kernel of grt_pipeline_run_band_profiles (its solvers count under
-       GRT_TAG_SOLVER_... and GRT_TAG_ALLSKY_...) */
+       GRT_TAG_SOLVER_... and GRT_TAG_ALLSKY_...); and of grt_pipeline_run_sky_weighted the finishing kernel of the response
+       rows (one launch per band and set; keep_spectra = 1: with the kernel that weights the [V][n] rows before it) and the
+       actinic kernel (its solvers count under grt_pipeline_run_sky's tags) */
     GRT_TAG_BAND_PROFILES = 14,
     /* 15 = the surface-row kernel of grt_pipeline_set_surface (all its launches) */
     GRT_TAG_SURFACE = 15,
