@@ -25,13 +25,14 @@ GRT_ALLSKY_PROFILE_ROWS_PER_COLUMN = 2 * GRT_PROFILE_ROWS_PER_COLUMN   # the cle
 GRT_ALLSKY_HEATING_ROWS_PER_COLUMN = 2 * GRT_HEATING_ROWS_PER_COLUMN   # the clear-sky two rows, then the all-sky two
 GRT_CLOUDS = 6                      # grt_sizeof kind of GrtClouds
 GRT_CLOUD_PHASE, GRT_CLOUD_MODEL, GRT_CLOUD_FIELDS = 7, 8, 9   # ... of GrtCloudPhase, GrtCloudModel, GrtCloudFields
+GRT_LW_SCATTER = 10                 # ... of GrtLwScatter
 # grt_profile_read's tags (grt_ext.h: GRT_TAG_..., where each one's bracket is described)
 (TAG_GAS_LW, TAG_GAS_SW, TAG_SOLVER_LW, TAG_SOLVER_SW, TAG_CLEAR_OPTICS, TAG_FAR_LW, TAG_FAR_SW, TAG_ALLSKY_LW,
  TAG_ALLSKY_SW, TAG_BINS, TAG_SUBCOLUMN_MEAN, TAG_AEROSOL_LW, TAG_AEROSOL_SW, TAG_BAND_PROFILES, TAG_SURFACE,
  TAG_CLOUD_SAMPLER, TAG_SKY_LW, TAG_SKY_SW, TAG_ZENITH_SW, TAG_ZENITH_MEAN, TAG_DIRECT_BEAM, TAG_SKY_ZENITH_SW,
  TAG_SKY_ZENITH_MEAN, TAG_SURFACE_JACOBIAN, TAG_RADIANCE, TAG_CHANNELS, TAG_WEIGHTING, TAG_WEIGHTING_FINISH,
  TAG_KDIST, TAG_KDIST_MAP, TAG_KDIST_MAPPED, TAG_CK_SOURCES, TAG_CK_LW, TAG_CK_SW, TAG_TILE_LW, TAG_TILE_SW,
- TAG_TILE_MEAN) = range(1, 38)
+ TAG_TILE_MEAN, TAG_SCATTER_LW, TAG_SCATTER_FINISH) = range(1, 40)
 TAG_FAR_OFFSET = TAG_FAR_LW - TAG_GAS_LW    # from a line kernel's tag to its far-field gather's
 CLOUD_SAMPLER_TAG = TAG_CLOUD_SAMPLER
 GRT_MAX_SUBCOLUMNS = 64             # grt_pipeline_run_subcolumns: subcolumns per column, 1 .. this
@@ -249,6 +250,14 @@ class GrtCkFluxes(C.Structure):
     _fields_ = [("num_classes", C.c_int), ("class_edges", c_double_p), ("lw", GrtCkBand), ("sw", GrtCkBand)]
 
 
+class GrtLwScatter(C.Structure):
+    _fields_ = [("ncol", C.c_int), ("num_levels", C.c_int), ("n", C.c_longlong), ("w0", C.c_double), ("dw", C.c_double),
+                ("tau_dev", C.c_void_p), ("omega_dev", C.c_void_p), ("g_dev", C.c_void_p),
+                ("layer_temperature_dev", C.c_void_p), ("level_temperature_dev", C.c_void_p),
+                ("surface_temperature_dev", C.c_void_p), ("emissivity_dev", C.c_void_p), ("delta_up_dev", C.c_void_p),
+                ("delta_down_dev", C.c_void_p), ("flux_up_dev", C.c_void_p), ("flux_down_dev", C.c_void_p)]
+
+
 class GrtZeniths(C.Structure):
     _fields_ = [("num_zeniths", C.c_int), ("cos_zenith", c_double_p), ("weight", c_double_p),
                 ("zenith_fluxes_dev", C.c_void_p), ("zenith_level_fluxes_dev", C.c_void_p)]
@@ -282,7 +291,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_channels grt_channel_pair_count grt_pipeline_run_sky_weighting grt_pipeline_run_sky_weighted grt_response_pair_count grt_pipeline_response_block_limit grt_pipeline_run_sky_zeniths grt_pipeline_run_sky_tiles grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_kdist_rows grt_pipeline_run_kdist grt_kdist_chunk_points grt_kdist_class_map grt_kdist_mapped_rows grt_pipeline_run_kdist_correlated grt_pipeline_run_ck_fluxes grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_channels grt_channel_pair_count grt_pipeline_run_sky_weighting grt_pipeline_run_sky_weighted grt_response_pair_count grt_pipeline_response_block_limit grt_pipeline_run_sky_zeniths grt_pipeline_run_sky_tiles grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_kdist_rows grt_pipeline_run_kdist grt_kdist_chunk_points grt_kdist_class_map grt_kdist_mapped_rows grt_pipeline_run_kdist_correlated grt_pipeline_run_ck_fluxes grt_pipeline_run_sky_scattering grt_lw_scatter_levels grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_voigt_points grt_debug_device_math grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -377,6 +386,9 @@ def load_library(path=None):
                                                           C.POINTER(GrtKdistKeys)]
     if hasattr(lib, "grt_pipeline_run_ck_fluxes"):       # (GRT_LIB_PATH may name an older library: a timing yardstick)
         lib.grt_pipeline_run_ck_fluxes.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtCkFluxes)]
+    if hasattr(lib, "grt_pipeline_run_sky_scattering"):  # (GRT_LIB_PATH may name an older library: a timing yardstick)
+        lib.grt_pipeline_run_sky_scattering.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky)] + [C.c_void_p] * 5
+        lib.grt_lw_scatter_levels.argtypes = [C.c_int, C.POINTER(GrtLwScatter)]
     lib.grt_pipeline_sky_set_count.argtypes = [C.c_uint]
     if hasattr(lib, "grt_pipeline_run_zeniths"):    # (GRT_LIB_PATH may name an older library: a timing yardstick)
         lib.grt_pipeline_run_zeniths.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtZeniths), C.c_void_p,
@@ -1071,6 +1083,46 @@ def kdist_mapped_rows(device, values_ptr, group_stride, map_ptr, groups, rows_pe
             b.free()
 
 
+def lw_scatter_levels(device, tau, omega, g, t_layers, t_levels, t_surf, emis, w0, dw, fluxes=False):
+    """grt_lw_scatter_levels: the longwave scattering correction of the layer optics tau, omega, g [ncol][L][n] (omega, g
+    None: 0) under the temperatures t_layers [ncol][L], t_levels [ncol][L + 1], t_surf [ncol] and the emissivity emis
+    [ncol][n] on the grid w0 + i dw -> (delta_up, delta_down), each [ncol][L + 1][n], W m-2 per cm-1: the two-stream
+    fluxes of the optics minus those of their absorption twin tau (1 - omega).  fluxes=True: and (flux_up, flux_down), the
+    scattering solve's own.  Host arrays in and out; waits for the result."""
+    lib = load_library()
+    tau = _f64(tau)
+    ncol, L, n = tau.shape
+    V = L + 1
+    host = [tau, None if omega is None else _f64(omega), None if g is None else _f64(g), _f64(t_layers), _f64(t_levels),
+            _f64(t_surf), _f64(emis)]
+    shapes = [(ncol, L, n)] * 3 + [(ncol, L), (ncol, V), (ncol,), (ncol, n)]
+    for x, shape in zip(host, shapes):
+        if x is not None and x.shape != shape:
+            raise ValueError(f"an input of shape {x.shape}: {shape} expected")
+    bufs = []
+    try:
+        ins = []
+        for x in host:
+            if x is None:
+                ins.append(None)
+                continue
+            b = DeviceBuffer(device, max(x.nbytes, 8))
+            bufs.append(b)
+            check(lib.grt_host_to_device(device, b.ptr, x.ctypes.data_as(C.c_void_p), x.nbytes))
+            ins.append(b.ptr)
+        outs = []
+        for _ in range(4 if fluxes else 2):
+            b = DeviceBuffer(device, 8 * ncol * V * n)
+            bufs.append(b)
+            outs.append(b)
+        sc = GrtLwScatter(ncol, V, n, float(w0), float(dw), *ins, *[b.ptr for b in outs], *([None] * (4 - len(outs))))
+        check(lib.grt_lw_scatter_levels(device, C.byref(sc)))
+        return tuple(b.to_host((ncol, V, n)) for b in outs)
+    finally:
+        for b in bufs:
+            b.free()
+
+
 def kdist_chunk_points():
     """grt_kdist_chunk_points: the points of a bin the k-distribution kernel stages at a time."""
     return int(load_library().grt_kdist_chunk_points())
@@ -1450,6 +1502,32 @@ class Pipeline:
         (sky_fluxes() reads it) or, profiles=True, the profile form (sky_profiles() reads it)."""
         ptrs, _ = self._sky_ptrs(gsky, profiles)
         check(self.lib.grt_pipeline_run_sky(self.p, C.byref(gcols), C.byref(gsky), *ptrs))
+
+    def run_sky_scattering(self, gcols, gsky, profiles=False):
+        """grt_pipeline_run_sky_scattering into this object's device buffers: run_sky's outputs where run_sky puts them
+        (sky_fluxes() / sky_profiles() read them), every longwave value with its scattering correction added, and the
+        corrections themselves: their six rows per set (sky_scatter_fluxes() reads them) and, profiles=True, every level
+        (sky_scatter_profiles() reads both)."""
+        ptrs, nsets = self._sky_ptrs(gsky, profiles)
+        V, n = self.num_levels, self.max_columns
+        name = "sky_profiles" if profiles else "sky"
+        six = self._buffer(name + ".scatter", 8 * n * nsets * 6).ptr
+        levels = self._buffer(name + ".scatter_levels", 8 * n * nsets * 2 * V).ptr if profiles else None
+        check(self.lib.grt_pipeline_run_sky_scattering(self.p, C.byref(gcols), C.byref(gsky), *ptrs, levels, six))
+
+    def sky_scatter_fluxes(self, ncol, nsets, profiles=False):
+        """The last run_sky_scattering (of that form) of nsets sets: [ncol][nsets][6], the scattering correction of each
+        set's longwave: up at the top of the atmosphere, the surface and the user level, then down at the same three (W m-2;
+        +0.0 without a user level)."""
+        self.sync()
+        return self.buffers[("sky_profiles" if profiles else "sky") + ".scatter"].to_host((ncol, nsets, 6))
+
+    def sky_scatter_profiles(self, ncol, nsets):
+        """The last run_sky_scattering(profiles=True) of nsets sets: dict(scatter=[ncol][nsets][6], as
+        sky_scatter_fluxes(), scatter_up and scatter_down=[ncol][nsets][V], the correction at every level, top first)."""
+        six = self.sky_scatter_fluxes(ncol, nsets, profiles=True)
+        lv = self.buffers["sky_profiles.scatter_levels"].to_host((ncol, nsets, 2, self.num_levels))
+        return dict(scatter=six, scatter_up=lv[:, :, 0].copy(), scatter_down=lv[:, :, 1].copy())
 
     def run_sky_direct(self, gcols, gsky, profiles=False):
         """grt_pipeline_run_sky_direct into this object's device buffers: run_sky's outputs where run_sky puts them

@@ -21,13 +21,13 @@ SO = os.path.join(LIB, "libgrtcode_hip.so")
 HOST_SRC = ["grt_error.c", "grt_util.c", "grt_grid.c", "grt_device.c", "grt_optics.c", "grt_tips.c",
             "grt_hitran.c", "grt_line_store.c", "grt_gas_optics.c", "grt_gas_launch.c", "grt_solvers.c", "grt_pipeline.c", "grt_pipeline_inputs.c", "grt_pipeline_solve.c", "grt_multi.c", "grt_cloud_sampler.c", "grt_kdist.c", "grt_clouds.c"]
 NOT_IN_SO = {"grt_clouds"}      # libclouds.a only: a maintainer links the reference's own libclouds.a in its place
-HIP_SRC = ["k_gas_optics.hip", "k_gas_optics_mp.hip", "k_gas_optics_far.hip", "k_gas_optics_sweep.hip", "k_optics.hip", "k_longwave.hip", "k_shortwave.hip", "k_cloud_sample.hip", "k_kdist.hip"]
+HIP_SRC = ["k_gas_optics.hip", "k_gas_optics_mp.hip", "k_gas_optics_far.hip", "k_gas_optics_sweep.hip", "k_optics.hip", "k_longwave.hip", "k_longwave_scatter.hip", "k_shortwave.hip", "k_cloud_sample.hip", "k_kdist.hip"]
 
 # the reference's archive names (*/src/Makefile.am): which objects go where
 ARCHIVES = {
     "libgrtcode_utilities.a": ["grt_error", "grt_util", "grt_grid", "grt_device", "grt_optics", "k_optics"],
     "libgas_optics.a": ["grt_tips", "grt_hitran", "grt_line_store", "grt_gas_optics", "grt_gas_launch", "k_gas_optics", "k_gas_optics_mp", "k_gas_optics_far", "k_gas_optics_sweep"],
-    "liblongwave.a": ["k_longwave"],
+    "liblongwave.a": ["k_longwave", "k_longwave_scatter"],
     "libshortwave.a": ["k_shortwave"],
     # solvers' host entry points and the batched pipeline reference both bands
     "libgrtcode_hip_ext.a": ["grt_solvers", "grt_pipeline", "grt_pipeline_inputs", "grt_pipeline_solve", "grt_multi", "grt_cloud_sampler", "k_cloud_sample", "grt_kdist", "k_kdist"],
@@ -84,7 +84,7 @@ def build(force=False, verbose=False):
     force = force or _flags_changed()
     headers = [os.path.join(ROOT, "include", h) for h in ("grtcode_hip_api.h", "grt_ext.h")]
     headers += [os.path.join(CSRC, "grt_kernels.h"), os.path.join(CSRC, "grt_work_order.h"), os.path.join(CSRC, "hip", "gas_optics_dev.h"), os.path.join(CSRC, "hip", "gas_optics_mp_dev.h"), os.path.join(CSRC, "hip", "mp_general_block.inc"), os.path.join(CSRC, "hip", "mp_lean_block.inc"),
-                os.path.join(CSRC, "hip", "optics_dev.h"), os.path.join(CSRC, "hip", "exp_pair.h"), os.path.join(CSRC, "hip", "planck_dev.h"),os.path.join(CSRC, "host", "grt_internal.h"), os.path.join(CSRC, "host", "grt_pipeline_internal.h"), os.path.join(CSRC, "host", "grt_molecule_table.h")]
+                os.path.join(CSRC, "hip", "optics_dev.h"), os.path.join(CSRC, "hip", "exp_pair.h"), os.path.join(CSRC, "hip", "planck_dev.h"), os.path.join(CSRC, "hip", "longwave_dev.h"), os.path.join(CSRC, "host", "grt_internal.h"), os.path.join(CSRC, "host", "grt_pipeline_internal.h"), os.path.join(CSRC, "host", "grt_molecule_table.h")]
     objs, jobs = [], []
     for f in HOST_SRC:
         src, obj = os.path.join(CSRC, "host", f), os.path.join(OBJ, f[:-2] + ".o")

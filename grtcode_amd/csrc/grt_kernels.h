@@ -754,6 +754,47 @@ int grt_launch_response_finish(void *stream, GrtResponseArgs const *r, int group
 int grt_launch_actinic_rows(void *stream, double const *weighted, uint64_t stride, int ncol, int sets, int responses,
                             int num_levels, double const *mu0, double mu_dif, double *actinic);
 
+/* Longwave scattering correction (k_longwave_scatter.hip: lw_scatter_kernel; grt_pipeline_run_sky_scattering,
+   grt_lw_scatter_levels).  lw_kernel takes every particle as an absorber, tau (1 - omega).  The correction is the
+   difference of two two-stream adding solves of the same code at every grid point,
+     delta_i = F_i[tau, omega, g] - F_i[tau (1 - omega), 0, 0]      (upward and downward, every level i),
+   so a point none of whose layers scatters gets exactly +0.0.  Per layer, D = 1.66:
+     gamma1 = D (1 - omega (1 + g)/2), gamma2 = D omega (1 - g)/2, k = sqrt(max((gamma1 - gamma2)(gamma1 + gamma2), 1e-12)),
+     x = min(k tau, 700), e = exp(-x), E = -expm1(-2 x), m = -expm1(-x), den = k (1 + e e) + gamma1 E,
+     R = gamma2 E/den, T = 2 k e/den, eps = (k m m + (gamma1 - gamma2) E)/den      (= 1 - R - T without the cancellation),
+     S_up = eps pi effective_planck(B(t_layer), B(t_level j), tau (1 - omega)), S_down = ... B(t_level j + 1) ...:
+   planck and effective_planck are lw_kernel's, on lw_kernel's arguments.  Adding, level V - 1 the surface:
+     A_L = 1 - emis, U_L = emis pi B(t_surf);
+     up:   beta_j = 1/(1 - A_{j+1} R_j), A_j = R_j + T_j T_j A_{j+1} beta_j, U_j = S_up_j + T_j (U_{j+1} + A_{j+1} S_down_j) beta_j;
+     down: F_down_0 = 0, F_up_0 = U_0, F_down_{j+1} = (T_j F_down_j + R_j U_{j+1} + S_down_j) beta_j,
+           F_up_{j+1} = A_{j+1} F_down_{j+1} + U_{j+1}.
+   One thread per grid point and grid row, GRT_SOLVER_BLOCK threads a workgroup, as lw_kernel: the first sweep runs from the
+   surface to the top with (A, U) of both solves in registers and parks, per layer j, GRT_SCATTER_PARK_ROWS rows -- R_j,
+   T_j, S_down_j, A_{j+1}, U_{j+1} of the scattering solve, then of its absorption twin -- at
+   park[((y L + j) GRT_SCATTER_PARK_ROWS + r) pw + i], y the grid row of the launch and pw = workgroups x GRT_SOLVER_BLOCK
+   (every thread its own place: idle lanes of the last block park too); the second sweep runs from the top down, reads
+   them back and hands both differences of every level to a LevelSink.  park_rows: the grid rows the block has room for --
+   a launch of more is refused.  Instances: GRT_OUT_CHAINS -- the tau, omega of GrtLwArgs and g (NULL: 0) on the grid, the
+   differences to GrtLwArgs' flux_up / flux_down [ncol][V][nw] and, where given, the scattering solve's own fluxes to
+   flux_up / flux_down here --, and GRT_OUT_ROWS and GRT_OUT_LEVELS with every join of clouds and aerosols lw_kernel has,
+   the differences' partial sums to GrtLwArgs' partials, laid out as lw_kernel's. */
+#define GRT_SCATTER_PARK_ROWS 10
+typedef struct GrtScatterArgs
+{
+    double *park;
+    uint64_t park_rows;
+    double const *g;                /* GRT_OUT_CHAINS: [ncol][L][nw] at GrtLwArgs' optics_stride, or NULL */
+    double *flux_up, *flux_down;    /* GRT_OUT_CHAINS: [ncol][V][nw] at GrtLwArgs' flux_stride, or NULL */
+} GrtScatterArgs;
+static inline int grt_scatter_args_ok(GrtScatterArgs const *sa)
+{
+    return sa != NULL && sa->park != NULL && sa->park_rows >= 1 && (sa->flux_up != NULL) == (sa->flux_down != NULL);
+}
+/* corrected[c out_stride + out_offset + r] += delta[c delta_stride + delta_offset + r], r < rows, c < n: one fp64
+   addition each (grt_pipeline_run_sky_scattering: a set's longwave rows and their differences) */
+int grt_launch_scatter_add(void *stream, int n, int rows, double *corrected, uint64_t out_stride, uint64_t out_offset,
+                           double const *delta, uint64_t delta_stride, uint64_t delta_offset);
+
 /* One instance of lw_kernel / sw_kernel (k_longwave.hip, k_shortwave.hip), described once for the launchers, the kernels
    and the pipeline: what leaves the kernel ... */
 typedef enum GrtSolverOutput
@@ -773,7 +814,9 @@ typedef enum GrtSolverOutput
    stays per column whatever the subcolumn); `bins` goes with GRT_OUT_LEVEL_BINS and with nothing else; `zeniths` (the
    shortwave's GRT_OUT_ROWS and GRT_OUT_LEVELS) goes alone or with aerosols, subcolumns or both, never with `clouds`; `direct` (the shortwave's GRT_OUT_ROWS and
    GRT_OUT_LEVELS) goes with any join of clouds and aerosols or none, and selects instances of its own: the instance
-   without it is the one it was; `jacobian` is the same for the longwave's GRT_OUT_ROWS and GRT_OUT_LEVELS; `responses` goes with GRT_OUT_LEVELS alone, in the shortwave always together with `direct`, never with `bins`, `zeniths` or `jacobian`, and selects instances of its own as `direct` does.  The kind of instance follows from which pointers are set, and a kernel takes the structs that are
+   without it is the one it was; `jacobian` is the same for the longwave's GRT_OUT_ROWS and GRT_OUT_LEVELS; `responses` goes with GRT_OUT_LEVELS alone, in the shortwave always together with `direct`, never with `bins`, `zeniths` or `jacobian`, and selects instances of its own as `direct` does; `scatter` (the longwave's GRT_OUT_CHAINS, GRT_OUT_ROWS and GRT_OUT_LEVELS, with any
+   join of clouds and aerosols or none, never with the others) names the instances of lw_scatter_kernel, which
+   grt_launch_lw_scatter alone launches.  The kind of instance follows from which pointers are set, and a kernel takes the structs that are
    set as arguments after its band's own.  The next joined object is a pointer here, a line in grt_solver_instance_ok
    and a case in each band's list of instances. */
 typedef struct GrtSolverInstance
@@ -787,6 +830,7 @@ typedef struct GrtSolverInstance
     GrtDirectArgs const *direct;
     GrtJacobianArgs const *jacobian;
     GrtResponseArgs const *responses;
+    GrtScatterArgs const *scatter;  /* grt_launch_lw_scatter's instances (GRT_OUT_CHAINS, _ROWS, _LEVELS): no other launcher's */
 } GrtSolverInstance;
 typedef enum GrtSolverJoin
 {
@@ -841,6 +885,12 @@ static inline size_t grt_solver_lds(GrtSolverInstance const *in, int num_levels)
     }
     return !grt_out_levels(in->out) ? 0 : (in->bins != NULL ? levels*(size_t)in->bins->block_bins : levels);
 }
+/* the doubles of a scattering park block (GrtScatterArgs) for `rows` grid rows of a band of nw points and num_levels levels */
+static inline uint64_t grt_scatter_park_doubles(uint64_t rows, int num_levels, uint64_t nw)
+{
+    uint64_t const pw = (nw + GRT_SOLVER_BLOCK - 1)/GRT_SOLVER_BLOCK*GRT_SOLVER_BLOCK;
+    return rows*(uint64_t)(num_levels - 1)*GRT_SCATTER_PARK_ROWS*pw;
+}
 /* the most responses one block may hold at num_levels levels and `groups` row groups (2; 3 with the third row group):
    16 G V (1 + R_b) + 1024 R_b <= 65536 */
 static inline int grt_response_block_limit(int num_levels, int groups)
@@ -859,6 +909,11 @@ static inline int grt_sw_parks(GrtSolverInstance const *in, GrtSwArgs const *a)
    cannot run or has no kernel behind it. */
 int grt_launch_lw(void *stream, GrtSolverInstance const *in, GrtLwArgs const *a);
 int grt_launch_sw(void *stream, GrtSolverInstance const *in, GrtSwArgs const *a);
+/* lw_scatter_kernel (GrtScatterArgs, in->scatter) in the instance of in's output and joins, on the longwave solver's
+   arguments: GRT_OUT_CHAINS writes the differences where that solver writes its fluxes, the fused forms leave their partial
+   sums where it leaves its own.  hipErrorInvalidValue for an instance without `scatter`, one that cannot run, or a grid of
+   more rows than the park block holds. */
+int grt_launch_lw_scatter(void *stream, GrtSolverInstance const *in, GrtLwArgs const *a);
 /* lw_radiance_kernel (GrtRadianceArgs) beside the longwave solver of instance `in`, on that solver's arguments: the
    instance's joins select the kernel (none, clouds, aerosols, subcolumns, clouds or subcolumns with aerosols) and its grid
    rows, a spectral output form (GRT_OUT_CHAINS, GRT_OUT_LAYERS) the materialised one; bins, zeniths, direct and jacobian
@@ -1101,7 +1156,14 @@ inline bool grt_solver_instance_ok(GrtSolverInstance const &in, Args const &a)
     // (the response rows leave the level form beside its own: no bins, sun angles or Jacobian with them)
     bool const responses_ok = in.responses == nullptr || (in.out == GRT_OUT_LEVELS && in.bins == nullptr && in.zeniths == nullptr &&
                                                           in.jacobian == nullptr && grt_response_args_ok(in.responses));
-    return zeniths_ok && direct_ok && jacobian_ok && responses_ok && a.ncol >= 1 && a.nw >= 2 && a.num_levels >= 2 &&
+    // (the scattering correction: the chain, six-row and level forms, with the cloud and aerosol joins alone)
+    bool const scatter_ok = in.scatter == nullptr || (in.bins == nullptr && in.zeniths == nullptr && in.direct == nullptr &&
+                                                      in.jacobian == nullptr && in.responses == nullptr &&
+                                                      grt_scatter_args_ok(in.scatter) && grt_solver_grid_rows(&in, a.ncol) <= in.scatter->park_rows &&
+                                                      (in.out == GRT_OUT_CHAINS || in.out == GRT_OUT_ROWS || in.out == GRT_OUT_LEVELS));
+    // (two grid points for a trapezoid; the chain form of the scattering correction integrates nothing: one will do)
+    uint64_t const least_points = in.scatter != nullptr && !fused ? 1 : 2;
+    return zeniths_ok && direct_ok && jacobian_ok && responses_ok && scatter_ok && a.ncol >= 1 && a.nw >= least_points && a.num_levels >= 2 &&
            cloud_forms <= 1 && joined <= (fused ? 2 : 0) && (in.bins != nullptr) == (in.out == GRT_OUT_LEVEL_BINS) &&
            (in.clouds == nullptr || grt_cloud_args_ok(in.clouds)) &&
            (in.aerosols == nullptr || grt_aerosol_args_ok(in.aerosols)) &&

@@ -30,19 +30,20 @@
 // What these kernels must say alike, to the bit, is said once: LwPoint (a thread's row, point and layer optical depth),
 // absorption_tau (tau (1 - omega) of a materialised pass), AngleChunk (blockIdx.z's viewing angles), stream_step and
 // jacobian_step (a layer of the four streams and of their derivatives), channel_row_mean (a channel row from its pairs).
-// A new longwave kernel takes its point, its angles and its layer optical depth from these.
+// A new longwave kernel takes its point, its angles and its layer optical depth from these.  LwPoint, absorption_tau and
+// effective_planck live in longwave_dev.h: k_longwave_scatter.hip takes its point and its source terms from there too.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include "../grt_kernels.h"
 #include "optics_dev.h"
 #include "planck_dev.h"
+#include "longwave_dev.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr double kMaxExpArg = 700.;   // grtcode_config.h:41
 // the four streams' constants (longwave.c:160-168)
 constexpr double kC1[4] = {-14.402613260847248, -3.0302159969901132, -1.4925584280108841, -1.0746123148178333};
 constexpr double kC2[4] = {0.07587638482015649, 0.676114979733751, 1.3726594476601073, 1.0169418413757783};
@@ -64,14 +65,6 @@ __device__ __forceinline__ double planck_dT(double T, double w, double &dbdt)
     double const b = (c1*w*w*w)/(e - 1.);
     dbdt = clamped ? 0. : b*(x/T)*(e/(e - 1.));
     return b;
-}
-
-// longwave.c:100-118 with the two Planck values supplied by the caller
-__device__ __forceinline__ double effective_planck(double bc, double be, double tau)
-{
-    double const a = 0.193;
-    double const b = 0.013;
-    return (bc + (a*tau + b*tau*tau)*be)/(1. + a*tau + b*tau*tau);
 }
 
 // extinction of a beam over optical depth tau (longwave.c:177-183): c1 is a stream's constant, or minus the secant of
@@ -165,54 +158,6 @@ __device__ __forceinline__ double surface_step(double (&I)[4], double emis, doub
 // GrtJacobianArgs in the pack, nothing without
 template <bool ON> struct StreamDerivatives {};
 template <> struct StreamDerivatives<true> { double D[4]; };
-
-// Absorption optical depth of a layer of a materialised pass: tau (1 - omega) at offset o of the pass's rows, omega 0
-// where the pass left none  (longwave.c:252)
-__device__ __forceinline__ double absorption_tau(double const *tau, double const *omega, uint64_t o)
-{
-    return omega ? tau[o]*(1. - omega[o]) : tau[o]*(1. - 0.);
-}
-
-// One thread's point of a longwave pass, for every kernel that walks a column's layers at a grid point on a solver
-// instance's arguments (lw_kernel, lw_radiance_kernel, lw_weighting_kernel): the grid row, the point -- an idle lane of the
-// last block follows along at the last one --, its wavenumber, the column's temperatures and emissivity, and the layers'
-// absorption optical depth: FUSED, formed in registers from the instance's joins (LayerOptics), else read from the tau,
-// omega the pass left on the grid.
-template <bool FUSED, typename... Joins>
-struct LwPoint
-{
-    SolverRow const row;
-    int const col;
-    bool const live;
-    uint64_t const ii, nw;
-    int const V, L;
-    double const w;                                                      // longwave.c:246
-    double const *const tau, *const omega, *const tl, *const tv;
-    double const emis;
-    LayerOptics<FUSED, has_clouds<Joins...>, has<GrtAerosolArgs, Joins...>> const optics;                  // (fused forms)
-
-    __device__ __forceinline__ LwPoint(GrtLwArgs const &a, uint64_t i, Joins const &...joins)
-        : row(solver_row(a.ncol, joins...)), col(row.col), live(i < a.nw), ii(live ? i : a.nw - 1), nw(a.nw),
-          V(a.num_levels), L(V - 1), w(a.w0 + ii*a.dw), tau(a.tau + (uint64_t)col*a.optics_stride + ii),
-          omega((!FUSED && a.omega) ? a.omega + (uint64_t)col*a.optics_stride + ii : nullptr),
-          tl(a.t_layers + (uint64_t)col*L), tv(a.t_levels + (uint64_t)col*V),
-          emis(a.emis[(uint64_t)col*a.emis_stride + ii]),
-          optics(a, pick_clouds(joins...), col, row.tab, ii, pick<GrtAerosolArgs>(joins...))
-    {
-    }
-
-    // absorption optical depth of layer j: tau (1 - omega)  (longwave.c:252)
-    __device__ __forceinline__ double layer_tau(int j) const
-    {
-        if (FUSED)
-        {
-            double t, om, gg;
-            optics.at(j, t, om, gg);
-            return t*(1. - om);
-        }
-        return absorption_tau(tau, omega, (uint64_t)j*nw);
-    }
-};
 
 // OUT fused (GRT_OUT_ROWS and after): the clear-sky tail of the pipeline in one kernel -- Rayleigh and the two-object
 // optics combination are formed per layer in registers from tau_gas (LayerOptics: identical values), nothing spectral is
@@ -1034,6 +979,7 @@ extern "C" int grt_launch_lw(void *stream, GrtSolverInstance const *in, GrtLwArg
 {
     uint64_t const cells = (uint64_t)(a->num_levels - 1)*a->nw;
     if (!grt_solver_instance_ok(*in, *a) || in->direct != nullptr ||        // (the direct beam is the shortwave's)
+        in->scatter != nullptr ||                                           // (grt_launch_lw_scatter's)
         (in->out == GRT_OUT_LAYERS && (a->layer_terms == nullptr || cells > 0xffffffffull*kTermsBlock)))
     {
         return (int)hipErrorInvalidValue;
@@ -1226,7 +1172,7 @@ extern "C" int grt_tile_chunk(GrtSubcolumnArgs const *sc, GrtAerosolArgs const *
 extern "C" int grt_launch_lw_tiles(void *stream, GrtLwArgs const *a, GrtTileArgs const *t, GrtSubcolumnArgs const *sc,
                                    GrtAerosolArgs const *ae)
 {
-    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (a == nullptr || t == nullptr || !grt_solver_instance_ok(in, *a) || a->t_layers == nullptr || a->t_levels == nullptr ||
         a->emis == nullptr || (sc != nullptr && !grt_subcolumn_args_ok(sc)) || (ae != nullptr && !grt_aerosol_args_ok(ae)))
     {

@@ -1014,6 +1014,7 @@ extern "C" int grt_launch_sw(void *stream, GrtSolverInstance const *in, GrtSwArg
 {
     uint64_t const cells = (uint64_t)(a->num_levels - 1)*a->nw;
     if (!grt_solver_instance_ok(*in, *a) || in->jacobian != nullptr ||      // (the surface-temperature Jacobian is the longwave's)
+        in->scatter != nullptr ||                                           // (the scattering correction too)
         (grt_sw_parks(in, a) && a->park == nullptr) ||
         (in->out == GRT_OUT_LAYERS && (a->layer_props == nullptr || cells > 0xffffffffull*kPropsBlock ||
                                        a->omega == nullptr || a->g == nullptr)))
@@ -1148,7 +1149,7 @@ extern "C" int grt_zenith_chunk(GrtSubcolumnArgs const *sc, GrtAerosolArgs const
 extern "C" int grt_launch_sw_zeniths(void *stream, GrtSwArgs const *a, GrtZenithArgs const *z, GrtSubcolumnArgs const *sc,
                                      GrtAerosolArgs const *ae)
 {
-    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (!grt_solver_instance_ok(in, *a) || z == nullptr || z->mu == nullptr || z->zeniths < 1 || !grt_sw_one_sweep(a) ||
         (sc != nullptr && !grt_subcolumn_args_ok(sc)) || (ae != nullptr && !grt_aerosol_args_ok(ae)))
     {
@@ -1190,7 +1191,7 @@ int launch_tiles(hipStream_t s, GrtSwArgs const &a, GrtTileArgs const &t, int dr
 extern "C" int grt_launch_sw_tiles(void *stream, GrtSwArgs const *a, GrtTileArgs const *t, GrtSubcolumnArgs const *sc,
                                    GrtAerosolArgs const *ae)
 {
-    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (a == nullptr || t == nullptr || !grt_solver_instance_ok(in, *a) || (!grt_sw_one_sweep(a) && a->park == nullptr) ||
         (sc != nullptr && !grt_subcolumn_args_ok(sc)) || (ae != nullptr && !grt_aerosol_args_ok(ae)))
     {

@@ -485,6 +485,7 @@ EXTERN size_t grt_sizeof(int kind)
         case GRT_CLOUD_PHASE: return sizeof(GrtCloudPhase_t);
         case GRT_CLOUD_MODEL: return sizeof(GrtCloudModel_t);
         case GRT_CLOUD_FIELDS: return sizeof(GrtCloudFields_t);
+        case GRT_LW_SCATTER: return sizeof(GrtLwScatter_t);
         default: return 0;
     }
 }

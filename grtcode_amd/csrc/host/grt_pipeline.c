@@ -1238,6 +1238,60 @@ EXTERN int grt_pipeline_run_sky(GrtPipeline_t *p, GrtColumns_t const *cols, GrtS
     return GRTCODE_SUCCESS;
 }
 
+/* grt_ext.h: grt_pipeline_run_sky, and the scattering correction of every set's longwave, added to its rows */
+EXTERN int grt_pipeline_run_sky_scattering(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky,
+                                           fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev,
+                                           fp_t *scatter_levels_dev, fp_t *scatter_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    if (scatter_levels_dev == NULL && scatter_dev == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "scatter_levels_dev and scatter_dev are both NULL: the differences are the output.%s", "");
+    }
+    if (level_fluxes_dev == NULL && scatter_levels_dev != NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "scatter_levels_dev is given in the six-row form (level_fluxes_dev is NULL).%s", "");
+    }
+    if (p->band[0].gas == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "this pipeline has no longwave band: nothing to correct.%s", "");
+    }
+    int nsets;
+    GRT_TRY(check_sky_sets(sky, &nsets));
+    GrtPass rows;
+    GRT_TRY(output_form(p, nsets, level_fluxes_dev, fluxes_dev, &rows));
+    GrtAerosols_t a;
+    GrtJoin join;
+    GRT_TRY(sky_join(p, cols, sky, &a, &join));
+    int const V = p->num_levels, C = cols->ncol, lw_rows = rows.profile ? 2*V : GRT_FLUXES_PER_BAND;
+    /* the passes' differences: the caller's six per set, or -- profile form -- 2 V levels per set, the caller's or the
+       pipeline's own, and the six rows from them afterwards */
+    GrtScatterRun sr = {rows.profile ? scatter_levels_dev : scatter_dev};
+    if (sr.out == NULL)
+    {
+        GRT_TRY(check_lane(p));
+        GrtScratch *own = &p->band[0].scratch[GRT_SCRATCH_SCATTER_LEVELS];
+        GRT_TRY(grt_scratch_need(p, own, (size_t)p->max_cols*GRT_SKY_MAX_SETS*2*(size_t)V, NULL));
+        sr.out = own->d;
+    }
+    rows.scatter = &sr;
+    GRT_TRY(pipeline_run(p, cols, &join, &rows));
+    /* every longwave row of every set += its difference, then the heating rates and six rows of the corrected levels */
+    void *s = grt_dev_stream(p->device);
+    int const slot = grt_profile_begin(s, GRT_TAG_SCATTER_FINISH);
+    int krc = grt_launch_scatter_add(s, C*nsets, lw_rows, rows.out, (uint64_t)grt_set_offset(p, rows.profile), 0, sr.out,
+                                     (uint64_t)lw_rows, 0);
+    if (krc == 0 && rows.profile && scatter_dev != NULL)
+    {
+        krc = grt_launch_direct_rows(s, C*nsets*2, V, p->user_level, sr.out, scatter_dev);
+    }
+    grt_profile_end(s, slot);
+    GRT_TRY(grt_dev_check(krc, "scattering addition kernel"));
+    GRT_TRY(finish_profiles(p, C, &rows, heating_dev, fluxes_dev));
+    return GRTCODE_SUCCESS;
+}
+
 /* grt_ext.h: grt_pipeline_run_sky, and the direct beam of every set's shortwave */
 EXTERN int grt_pipeline_run_sky_direct(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky,
                                        GrtDirectBeam_t const *direct, fp_t *level_fluxes_dev, fp_t *heating_dev,

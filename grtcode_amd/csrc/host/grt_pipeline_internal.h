@@ -113,6 +113,15 @@ enum
        block) pair, S the draws of the call's cloud sets (1 without one) for every set of the call, G = 2 (longwave) or 3
        (shortwave); sized at the first call that needs more */
     GRT_SCRATCH_RESPONSE_PARTIALS,
+    /* grt_pipeline_run_sky_scattering, longwave, both forms: the scattering kernel's park block (GrtScatterArgs), max_cols
+       grid rows of (V - 1) x GRT_SCATTER_PARK_ROWS rows of the band's points rounded up to the solver block; allocated at
+       the first such call */
+    GRT_SCRATCH_SCATTER_PARK,
+    /* ... [max_cols][S][6 or 2 V][nblocks] partial sums of the differences of every draw, S = 1 but in a cloud set of
+       several draws, its sets in turn in stream order (materialised form: [max_cols][S][6 or 2 V] integrated rows) */
+    GRT_SCRATCH_SCATTER_PARTIALS,
+    /* ... profile form without scatter_levels_dev: [max_cols][GRT_SKY_MAX_SETS][2][V] the levels its six rows come from */
+    GRT_SCRATCH_SCATTER_LEVELS,
     GRT_SCRATCH_COUNT
 };
 
@@ -243,6 +252,13 @@ typedef struct GrtResponseRun
     int slots;                      /* slots per column of the scratch: the most draws any set of the call has */
 } GrtResponseRun;
 
+/* The scattering correction of a grt_pipeline_run_sky_scattering call: where every set's differences go, in the layout of
+   the run's longwave rows -- [ncol][sets][6], or (profile) [ncol][sets][2][V], up then down. */
+typedef struct GrtScatterRun
+{
+    double *out;
+} GrtScatterRun;
+
 /* One solve of a band on the run's tau_gas.  What joins gas and Rayleigh: nothing (clear sky), the cloud objects (all-sky
    pass), the aerosol object (aerosol pass; aer NULL there: a band that was given no aerosol, which runs the form without
    the object under the aerosol pass's profile tags) or both (grt_pipeline_run_sky's complete set).  Which rows leave: the six of driver.c:272-280 or (profile) every level's
@@ -282,6 +298,9 @@ typedef struct GrtPass
     /* grt_pipeline_run_sky_weighted (NULL: not asked for, or the band has no responses; profile form only, the shortwave
        with `direct`): the band's level rows leave under its responses too, to the pass's set of responses->out */
     GrtResponseRun const *responses;
+    /* grt_pipeline_run_sky_scattering (NULL: not asked for): the longwave's scattering kernel is queued behind the pass's
+       solver, on its instance and arguments, and the pass's differences go to set `set` of scatter->out */
+    GrtScatterRun const *scatter;
 } GrtPass;
 
 /* The surface tiles of a grt_pipeline_run_sky_tiles call, staged (grt_stage_tiles): T per column, their temperatures and

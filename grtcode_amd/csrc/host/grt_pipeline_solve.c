@@ -38,7 +38,7 @@ typedef struct ThirdRows
 static GrtSolverInstance pass_instance(GrtPipeline_t const *p, GrtPass const *ps, GrtBandArgs const *bn,
                                        GrtSubcolumnArgs const *sc, ThirdRows const *tr, int bi)
 {
-    GrtSolverInstance in = {GRT_OUT_CHAINS, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
+    GrtSolverInstance in = {GRT_OUT_CHAINS, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
     if (!p->keep_spectra)
     {
         in.out = pass_spectral(ps) ? GRT_OUT_ROWS_POINTS : (bn != NULL ? GRT_OUT_LEVEL_BINS :
@@ -660,6 +660,114 @@ static int direct_integrate(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass
     return GRTCODE_SUCCESS;
 }
 
+/* ---- grt_pipeline_run_sky_scattering: the longwave's scattering correction behind a pass's solver ---- */
+static int pass_scatter(GrtPass const *ps, int bi)
+{
+    return bi == 0 && ps->scatter != NULL;
+}
+
+/* the park block of the longwave band, max_cols grid rows: allocated at the first call that scatters, as *sa */
+static int scatter_park(GrtPipeline_t *p, GrtBand *b, GrtScatterArgs *sa)
+{
+    GrtScratch *park = &b->scratch[GRT_SCRATCH_SCATTER_PARK];
+    GRT_TRY(grt_scratch_need(p, park, (size_t)grt_scatter_park_doubles((uint64_t)p->max_cols, p->num_levels, b->n), NULL));
+    memset(sa, 0, sizeof(*sa));
+    sa->park = park->d;
+    sa->park_rows = (uint64_t)p->max_cols;
+    return GRTCODE_SUCCESS;
+}
+
+/* what turns the block's [C][S][rows] rows of nblocks partial sums each into the pass's set of the differences: the
+   fixed-order sum, or -- S > 1 -- the subcolumn mean kernel, draws 0 .. S - 1 in order, one division (GRT_TAG_SCATTER_FINISH) */
+static int scatter_finish(GrtPipeline_t *p, GrtBand *b, int C, int S, unsigned nblocks, GrtPass const *ps)
+{
+    void *s = grt_dev_stream(p->device);
+    int const rows = pass_rows(p, ps);
+    double const *partials = b->scratch[GRT_SCRATCH_SCATTER_PARTIALS].d;
+    int const slot = grt_profile_begin(s, GRT_TAG_SCATTER_FINISH);
+    int const krc = S == 1 ? grt_launch_reduce_partials(s, partials, C*rows, nblocks, ps->scatter->out, rows, ps->sets*rows,
+                                                        ps->set*rows) :
+                             grt_launch_subcolumn_mean(s, partials, C, S, rows, nblocks, ps->scatter->out, ps->sets*rows,
+                                                       ps->set*rows);
+    grt_profile_end(s, slot);
+    GRT_TRY(grt_dev_check(krc, "scattering reduction kernel"));
+    return GRTCODE_SUCCESS;
+}
+
+/* Fused form: the scattering kernel in the pass's instance (sc: its clouds as the subcolumns of sc, S of them; NULL:
+   S = 1), its partial sums to GRT_SCRATCH_SCATTER_PARTIALS at the solver's slots, as many draws a launch as the park block
+   of max_cols grid rows holds -- the rule of the shortwave's two-sweep forms --, in stream order; then scatter_finish */
+static int scatter_fused(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass const *ps, GrtSubcolumnArgs *sc)
+{
+    void *s = grt_dev_stream(p->device);
+    int const rows = pass_rows(p, ps);
+    GrtScratch *block = &b->scratch[GRT_SCRATCH_SCATTER_PARTIALS];
+    GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*(size_t)S*(size_t)rows*b->nblocks, NULL));
+    GrtScatterArgs sa;
+    GRT_TRY(scatter_park(p, b, &sa));
+    GrtSolverInstance in = pass_instance(p, ps, NULL, sc, NULL, 0);
+    in.scatter = &sa;
+    SolverArgs a;
+    GRT_TRY(solver_args(p, b, 0, C, ps, &in, block->d, &a));
+    int const slot = grt_profile_begin(s, GRT_TAG_SCATTER_LW);
+    int krc = 0;
+    if (sc != NULL)
+    {
+        int group = p->max_cols/C;                                    /* (a park block of max_cols grid rows) */
+        group = group < S ? group : S;
+        for (sc->first = 0; sc->first < S && krc == 0; sc->first += group)
+        {
+            sc->count = S - sc->first < group ? S - sc->first : group;
+            krc = grt_launch_lw_scatter(s, &in, &a.lw);
+        }
+    }
+    else
+    {
+        krc = grt_launch_lw_scatter(s, &in, &a.lw);
+    }
+    grt_profile_end(s, slot);
+    GRT_TRY(grt_dev_check(krc, "longwave scattering kernel"));
+    GRT_TRY(scatter_finish(p, b, C, S, b->nblocks, ps));
+    return GRTCODE_SUCCESS;
+}
+
+/* Materialised form, draw j of S: the chain instance on the tau, omega, g the pass has left in the band's arrays.  The
+   differences take the place of the fluxes in the band's flux arrays -- the pass's solver has run, and its fluxes are
+   integrated or summed --, and their row-wise trapezoid goes to row (c S + j) of GRT_SCRATCH_SCATTER_PARTIALS, one
+   value a row; scatter_finish after the last draw */
+static int scatter_spectral(GrtPipeline_t *p, GrtBand *b, int C, int S, int j, GrtPass const *ps)
+{
+    void *s = grt_dev_stream(p->device);
+    int const rows = pass_rows(p, ps);
+    GrtScratch *block = &b->scratch[GRT_SCRATCH_SCATTER_PARTIALS];
+    GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*(size_t)S*(size_t)rows, NULL));
+    GrtScatterArgs sa;
+    GRT_TRY(scatter_park(p, b, &sa));
+    sa.g = b->g;
+    GrtSolverInstance in = pass_instance(p, ps, NULL, NULL, NULL, 0);
+    in.scatter = &sa;
+    GrtLwArgs a;
+    lw_args(p, b, C, 0, ps, &a);
+    int const slot = grt_profile_begin(s, GRT_TAG_SCATTER_LW);
+    int const krc = grt_launch_lw_scatter(s, &in, &a);
+    grt_profile_end(s, slot);
+    GRT_TRY(grt_dev_check(krc, "longwave scattering kernel"));
+    if (ps->profile)
+    {
+        GRT_TRY(level_rows(p, b));
+    }
+    int const fslot = grt_profile_begin(s, GRT_TAG_SCATTER_FINISH);
+    int const irc = grt_launch_integrate_rows(s, (double const *const *)(ps->profile ? b->level_rows_d : b->rows_d), C*rows,
+                                              b->n, b->gas->grid.dw, block->d, rows, S*rows, j*rows);
+    grt_profile_end(s, fslot);
+    GRT_TRY(grt_dev_check(irc, "spectral integration kernel"));
+    if (j == S - 1)
+    {
+        GRT_TRY(scatter_finish(p, b, C, S, 1, ps));
+    }
+    return GRTCODE_SUCCESS;
+}
+
 /* One solve of a band for grt_pipeline_run_spectral: the six rows at every point into the caller's spectral block, the
    -integrated six into out, and the bins.  Fused form: the spectral six-row solver (its rows stored where it weights
    them) and the fixed-order sum of its partial sums; materialised form: the spectral solver, its rows 0, L and the user
@@ -765,6 +873,10 @@ int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *p
             GRT_TRY(direct_integrate(p, b, bi, C, ps));
         }
         GRT_TRY(response_rows(p, b, C, ps));
+        if (pass_scatter(ps, bi))
+        {
+            GRT_TRY(scatter_spectral(p, b, C, 1, 0, ps));
+        }
         if (pass_radiances(ps, bi))
         {
             GRT_TRY(band_radiances(p, b, C, 1, 0, ps, NULL));
@@ -802,6 +914,10 @@ int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *p
         {
             GRT_TRY(finish_responses(p, C, 1, ps, &da.responses));
         }
+    }
+    if (pass_scatter(ps, bi))
+    {
+        GRT_TRY(scatter_fused(p, b, C, 1, ps, NULL));
     }
     if (pass_radiances(ps, bi))
     {
@@ -860,6 +976,10 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
         }
         grt_profile_end(s, slot);
         GRT_TRY(grt_dev_check(krc, bi == 0 ? "longwave subcolumn kernel" : "shortwave subcolumn kernel"));
+        if (pass_scatter(ps, bi))
+        {
+            GRT_TRY(scatter_fused(p, b, C, S, ps, &sc));
+        }
         if (pass_radiances(ps, bi))
         {
             GRT_TRY(band_radiances(p, b, C, S, 0, ps, &sc));
@@ -924,6 +1044,10 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
         GRT_TRY(grt_dev_check(grt_launch_flux_accumulate(s, per, b->flux_up, flux_sum, j == 0), "flux sum kernel"));
         GRT_TRY(grt_dev_check(grt_launch_flux_accumulate(s, per, b->flux_down, flux_sum + all, j == 0),
                               "flux sum kernel"));
+        if (pass_scatter(ps, bi))
+        {
+            GRT_TRY(scatter_spectral(p, b, C, S, j, &pj));
+        }
         if (pass_direct(ps, bi))
         {
             GRT_TRY(direct_beam(p, b, bi, C, &pj));

@@ -5,6 +5,7 @@
  * (rayleigh.c:100-144), solar_flux.h:37-46 (solar_flux.c:27-99).
  * Each call copies its small inputs to the device, launches the batched kernel with
  * ncol = 1 and copies the (level, wavenumber) fluxes back, as the signatures demand. */
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 #include "grt_internal.h"
@@ -208,11 +209,67 @@ EXTERN int calculate_lw_fluxes(Longwave_t * const lw, Optics_t const * const opt
     /* GRT_LW_COLUMN_CHAINS=1: one thread per wavenumber through all the layers, as before round 4 (same fluxes) */
     char const *chains = getenv("GRT_LW_COLUMN_CHAINS");
     GrtSolverInstance const in = {(chains != NULL && chains[0] == '1') || !block_has_scratch(lw->device, lw->layer_temperature, lw->flux_down + n*(size_t)V, sizeof(fp_t)*6*n*(size_t)(V - 1))
-                                  ? GRT_OUT_CHAINS : GRT_OUT_LAYERS, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
+                                  ? GRT_OUT_CHAINS : GRT_OUT_LAYERS, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
     a.layer_terms = in.out == GRT_OUT_LAYERS ? lw->flux_down + n*(size_t)V : NULL;
     GRT_TRY(grt_dev_check(grt_launch_lw(s, &in, &a), "longwave kernel"));
     GRT_TRY(download_fluxes(lw->device, V, n, flux_up, flux_down, lw->flux_up, lw->flux_down, s));
     GRT_TRY(grt_dev_sync(lw->device, s));
+    return GRTCODE_SUCCESS;
+}
+
+/* grt_ext.h: the longwave scattering correction of ncol columns on optics of the caller's, every array on the device */
+EXTERN int grt_lw_scatter_levels(Device_t device, GrtLwScatter_t const *sc)
+{
+    if (sc == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "no inputs (GrtLwScatter_t is NULL).%s", "");
+    }
+    if (sc->tau_dev == NULL || sc->layer_temperature_dev == NULL || sc->level_temperature_dev == NULL ||
+        sc->surface_temperature_dev == NULL || sc->emissivity_dev == NULL || sc->delta_up_dev == NULL ||
+        sc->delta_down_dev == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "tau_dev, the three temperatures, emissivity_dev, delta_up_dev and delta_down_dev are "
+                 "required: one of them is NULL.%s", "");
+    }
+    if ((sc->flux_up_dev != NULL) != (sc->flux_down_dev != NULL))
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "flux_up_dev and flux_down_dev: both or neither.%s", "");
+    }
+    if (sc->ncol < 1 || sc->ncol > 65535 || sc->num_levels < 2 || sc->n < 1)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d columns (1 to 65535) of %d levels (at least 2) and %lld points (at least 1).",
+                 sc->ncol, sc->num_levels, sc->n);
+    }
+    if (!(sc->dw > 0.) || !isfinite(sc->dw))
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "grid spacing (%e) is not positive and finite.", sc->dw);
+    }
+    GRT_TRY(grt_dev_require(device));
+    int const V = sc->num_levels, L = V - 1;
+    uint64_t const n = (uint64_t)sc->n;
+    GrtLwArgs a;
+    memset(&a, 0, sizeof(a));
+    a.num_levels = V; a.ncol = sc->ncol; a.w0 = sc->w0; a.dw = sc->dw; a.nw = n;
+    a.tau = sc->tau_dev; a.omega = sc->omega_dev; a.optics_stride = (uint64_t)L*n;
+    a.t_layers = sc->layer_temperature_dev; a.t_levels = sc->level_temperature_dev; a.t_surf = sc->surface_temperature_dev;
+    a.emis = sc->emissivity_dev; a.emis_stride = n;
+    a.flux_up = sc->delta_up_dev; a.flux_down = sc->delta_down_dev; a.flux_stride = (uint64_t)V*n;
+    a.user_level = -1;
+    void *park = NULL;
+    GRT_TRY(grt_dev_alloc(device, &park, sizeof(double)*grt_scatter_park_doubles((uint64_t)sc->ncol, V, n)));
+    GrtScatterArgs const sa = {park, (uint64_t)sc->ncol, sc->g_dev, sc->flux_up_dev, sc->flux_down_dev};
+    GrtSolverInstance const in = {GRT_OUT_CHAINS, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, &sa};
+    void *s = grt_dev_stream(device);
+    int const slot = grt_profile_begin(s, GRT_TAG_SCATTER_LW);
+    int const krc = grt_launch_lw_scatter(s, &in, &a);
+    grt_profile_end(s, slot);
+    int rc = grt_dev_check(krc, "longwave scattering kernel");
+    if (rc == GRTCODE_SUCCESS)
+    {
+        rc = grt_dev_sync(device, s);
+    }
+    grt_dev_free(device, park);
+    GRT_TRY(rc);
     return GRTCODE_SUCCESS;
 }
 
@@ -299,7 +356,7 @@ EXTERN int calculate_sw_fluxes(Shortwave_t * const sw, Optics_t const * const op
     /* GRT_SW_COLUMN_CHAINS=1: one thread per wavenumber through all the layers, as before round 4 (same fluxes) */
     char const *chains = getenv("GRT_SW_COLUMN_CHAINS");
     GrtSolverInstance const in = {(chains != NULL && chains[0] == '1') || !block_has_scratch(sw->device, sw->solar_flux, sw->flux_down + n*(size_t)V, sizeof(fp_t)*5*n*(size_t)(V - 1))
-                                  ? GRT_OUT_CHAINS : GRT_OUT_LAYERS, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
+                                  ? GRT_OUT_CHAINS : GRT_OUT_LAYERS, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
     a.layer_props = in.out == GRT_OUT_LAYERS ? sw->flux_down + n*(size_t)V : NULL;
     GRT_TRY(grt_dev_check(grt_launch_sw(s, &in, &a), "shortwave kernel"));
     GRT_TRY(download_fluxes(sw->device, V, n, flux_up, flux_down, sw->flux_up, sw->flux_down, s));

@@ -42,7 +42,7 @@ EXTERN int grt_hitran_index_stats(long long stats[3]);
 enum grt_struct_kind
 {
     GRT_SPECTRAL_GRID = 0, GRT_OPTICS, GRT_GAS_OPTICS, GRT_SOLAR_FLUX, GRT_LONGWAVE, GRT_SHORTWAVE, GRT_CLOUDS,
-    GRT_CLOUD_PHASE, GRT_CLOUD_MODEL, GRT_CLOUD_FIELDS
+    GRT_CLOUD_PHASE, GRT_CLOUD_MODEL, GRT_CLOUD_FIELDS, GRT_LW_SCATTER
 };
 EXTERN size_t grt_sizeof(int kind);
 
@@ -1166,6 +1166,64 @@ EXTERN int grt_pipeline_run_sky_weighted(GrtPipeline_t *pipeline, GrtColumns_t c
 EXTERN long long grt_response_pair_count(GrtResponses_t const *responses, int band /* 0 lw, 1 sw */, long long num_points);
 EXTERN int grt_pipeline_response_block_limit(GrtPipeline_t const *pipeline, int band);
 
+/* ---- longwave scattering by clouds and aerosols ------------------------------------------
+ * The longwave solver (calculate_lw_fluxes, and the longwave of every grt_pipeline_run_...) treats every particle as a
+ * pure absorber: a layer's optical depth is tau (1 - omega), and g is never read (longwave.c:252).  That stays so.
+ * grt_pipeline_run_sky_scattering is grt_pipeline_run_sky, and with it the scattering correction of every set's longwave:
+ * the difference of two two-stream adding solves of the same code at every grid point,
+ *   delta_up_i = F_up_i[tau, omega, g] - F_up_i[tau (1 - omega), 0, 0]     (the same for down; every level i),
+ * integrated over the band as the fluxes are, and   corrected = four-stream + delta.   Per layer, with D = 1.66:
+ *   gamma1 = D (1 - omega (1 + g)/2),  gamma2 = D omega (1 - g)/2,  k = sqrt(max((gamma1 - gamma2)(gamma1 + gamma2), 1e-12)),
+ *   x = min(k tau, 700),  e = exp(-x),  E = -expm1(-2 x),  m = -expm1(-x),  den = k (1 + e e) + gamma1 E,
+ *   R = gamma2 E/den,  T = 2 k e/den,  eps = (k m m + (gamma1 - gamma2) E)/den      (= 1 - R - T),
+ *   S_up = eps pi effective_planck(B(t_layer_j), B(t_level_j), tau (1 - omega)),  S_down = ... B(t_level_j+1) ...
+ * with the solver's own planck_law and effective_planck (longwave.c:68-118).  Adding, level V - 1 the surface:
+ *   A_L = 1 - emis,  U_L = emis pi B(t_surf)
+ *   up:    beta_j = 1/(1 - A_{j+1} R_j);  A_j = R_j + T_j T_j A_{j+1} beta_j;  U_j = S_up_j + T_j (U_{j+1} + A_{j+1} S_down_j) beta_j
+ *   down:  F_down_0 = 0, F_up_0 = U_0;  F_down_{j+1} = (T_j F_down_j + R_j U_{j+1} + S_down_j) beta_j;
+ *          F_up_{j+1} = A_{j+1} F_down_{j+1} + U_{j+1}
+ * Where no layer of a point scatters both solves see the same numbers and the difference is exactly +0.0.
+ *
+ * Outputs.  level_fluxes_dev, heating_dev, fluxes_dev: grt_pipeline_run_sky's, in its layouts and forms
+ * (level_fluxes_dev == NULL: the six-row form); every longwave value is grt_pipeline_run_sky's plus its difference, one
+ * fp64 addition; the heating rates are formed from the corrected levels; the shortwave values are grt_pipeline_run_sky's
+ * bit for bit.  scatter_dev [ncol][N][6] (N sets, as packed there): the differences of up TOA, up surface, up user level,
+ * down TOA, down surface, down user level (+0.0 without a user level), W m-2.  scatter_levels_dev [ncol][N][2][V], profile
+ * form only: up then down at every level, top first; its rows 0, V - 1 and the user level are scatter_dev's.  Either may
+ * be NULL, not both.  Every set gets its differences, the clean one too (Rayleigh scattering: tiny, not zero); a cloud
+ * set's are the mean over its draws, in grt_pipeline_run_subcolumns' order and arithmetic.  grt_pipeline_set_surface
+ * applies.  With keep_spectra = 1 the correction runs on the tau, omega, g each pass leaves on the grid.
+ * Memory: the first call allocates the longwave band's park block, max_columns x (V - 1) x 10 rows of the band's points
+ * rounded up to 128; a cloud set of more draws than fit is solved in several launches.  Other calls allocate nothing more.
+ * Counted under GRT_TAG_SCATTER_LW and GRT_TAG_SCATTER_FINISH.
+ * GRTCODE_VALUE_ERR, with nothing launched and the outputs untouched, for: everything grt_pipeline_run_sky refuses; both
+ * scatter outputs NULL; scatter_levels_dev in the six-row form; a pipeline without a longwave band.
+ * Not covered: the radiance, channel, weighting, Jacobian, tile, zenith, weighted, band-profile and ck entry points, and
+ * calculate_lw_fluxes, which keep the reference's semantics; more than two streams.
+ *
+ * grt_lw_scatter_levels: the same kernel on optics of the caller's, everything a DEVICE array: tau, omega, g
+ * [ncol][V - 1][n] (omega, g may be NULL: 0), the temperatures [ncol][V - 1], [ncol][V], [ncol], the emissivity
+ * [ncol][n], on the grid w0 + i dw.  delta_up_dev, delta_down_dev [ncol][V][n]: the spectral differences, W m-2 per
+ * cm-1; flux_up_dev, flux_down_dev (both or neither): the scattering solve's own fluxes.  It allocates and frees its
+ * park block and waits for the result.  GRTCODE_VALUE_ERR for a NULL struct, a required pointer that is NULL, ncol < 1 or
+ * > 65535, num_levels < 2, n < 1, a dw that is not positive and finite, one of flux_up_dev and flux_down_dev alone. */
+typedef struct GrtLwScatter
+{
+    int ncol;
+    int num_levels;
+    long long n;
+    fp_t w0, dw;
+    fp_t const *tau_dev, *omega_dev, *g_dev;
+    fp_t const *layer_temperature_dev, *level_temperature_dev, *surface_temperature_dev;
+    fp_t const *emissivity_dev;
+    fp_t *delta_up_dev, *delta_down_dev;
+    fp_t *flux_up_dev, *flux_down_dev;
+} GrtLwScatter_t;
+EXTERN int grt_lw_scatter_levels(Device_t device, GrtLwScatter_t const *scatter);
+EXTERN int grt_pipeline_run_sky_scattering(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtSky_t const *sky,
+                                           fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev,
+                                           fp_t *scatter_levels_dev, fp_t *scatter_dev);
+
 /* ---- columns across the GPUs of one node ------------------------------------
  * One process per GPU; contiguous ceil-sized column blocks; one gather of the [columns][GRT_FLUXES_PER_COLUMN]
  * flux blocks to rank 0.  The reference fans out processes with -x/-X column ranges and merges per-shard files
@@ -1284,6 +1342,15 @@ enum
     GRT_TAG_TILE_LW = 35,
     GRT_TAG_TILE_SW = 36,
     GRT_TAG_TILE_MEAN = 37
+};
+/* ... continued behind the last of them: 38 = the scattering-correction kernel of grt_pipeline_run_sky_scattering, every
+   set's launches (its solvers count under grt_pipeline_run_sky's tags), and of grt_lw_scatter_levels; 39 = what turns its
+   partial sums or spectral rows into a set's differences and adds them to the set's longwave rows (the reductions, the
+   subcolumn mean, the addition, the row pick) */
+enum
+{
+    GRT_TAG_SCATTER_LW = GRT_TAG_TILE_MEAN + 1,
+    GRT_TAG_SCATTER_FINISH
 };
 EXTERN int grt_profile_enable(int on);
 EXTERN int grt_profile_read(int tag, double *total_ms, int *launches, int reset);
