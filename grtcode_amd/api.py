@@ -26,6 +26,7 @@ GRT_ALLSKY_HEATING_ROWS_PER_COLUMN = 2 * GRT_HEATING_ROWS_PER_COLUMN   # the cle
 GRT_CLOUDS = 6                      # grt_sizeof kind of GrtClouds
 GRT_CLOUD_PHASE, GRT_CLOUD_MODEL, GRT_CLOUD_FIELDS = 7, 8, 9   # ... of GrtCloudPhase, GrtCloudModel, GrtCloudFields
 GRT_LW_SCATTER = 10                 # ... of GrtLwScatter
+GRT_ZENITH_SURFACE, GRT_ZENITH_DIRECT = 11, 12     # ... of GrtZenithSurface, GrtZenithDirect
 # grt_profile_read's tags (grt_ext.h: GRT_TAG_..., where each one's bracket is described)
 (TAG_GAS_LW, TAG_GAS_SW, TAG_SOLVER_LW, TAG_SOLVER_SW, TAG_CLEAR_OPTICS, TAG_FAR_LW, TAG_FAR_SW, TAG_ALLSKY_LW,
  TAG_ALLSKY_SW, TAG_BINS, TAG_SUBCOLUMN_MEAN, TAG_AEROSOL_LW, TAG_AEROSOL_SW, TAG_BAND_PROFILES, TAG_SURFACE,
@@ -263,6 +264,15 @@ class GrtZeniths(C.Structure):
                 ("zenith_fluxes_dev", C.c_void_p), ("zenith_level_fluxes_dev", C.c_void_p)]
 
 
+class GrtZenithSurface(C.Structure):
+    _fields_ = [("albedo_num_points", C.c_int), ("albedo_grid", c_double_p), ("direct_albedo", c_double_p)]
+
+
+class GrtZenithDirect(C.Structure):
+    _fields_ = [("direct_fluxes_dev", C.c_void_p), ("direct_level_fluxes_dev", C.c_void_p),
+                ("zenith_direct_fluxes_dev", C.c_void_p), ("zenith_direct_level_fluxes_dev", C.c_void_p)]
+
+
 class GrtSurfaceTiles(C.Structure):
     _fields_ = [("num_tiles", C.c_int), ("fraction", c_double_p), ("surface_temperature", c_double_p),
                 ("num_emissivity_points", C.c_int), ("num_albedo_points", C.c_int),
@@ -291,7 +301,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_channels grt_channel_pair_count grt_pipeline_run_sky_weighting grt_pipeline_run_sky_weighted grt_response_pair_count grt_pipeline_response_block_limit grt_pipeline_run_sky_zeniths grt_pipeline_run_sky_tiles grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_kdist_rows grt_pipeline_run_kdist grt_kdist_chunk_points grt_kdist_class_map grt_kdist_mapped_rows grt_pipeline_run_kdist_correlated grt_pipeline_run_ck_fluxes grt_pipeline_run_sky_scattering grt_lw_scatter_levels grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_channels grt_channel_pair_count grt_pipeline_run_sky_weighting grt_pipeline_run_sky_weighted grt_response_pair_count grt_pipeline_response_block_limit grt_pipeline_run_sky_zeniths grt_pipeline_run_sky_zeniths_direct grt_zenith_surface_tables grt_pipeline_run_sky_tiles grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_kdist_rows grt_pipeline_run_kdist grt_kdist_chunk_points grt_kdist_class_map grt_kdist_mapped_rows grt_pipeline_run_kdist_correlated grt_pipeline_run_ck_fluxes grt_pipeline_run_sky_scattering grt_lw_scatter_levels grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_voigt_points grt_debug_device_math grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -396,6 +406,12 @@ def load_library(path=None):
     if hasattr(lib, "grt_pipeline_run_sky_zeniths"):
         lib.grt_pipeline_run_sky_zeniths.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky),
                                                      C.POINTER(GrtZeniths), C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "grt_pipeline_run_sky_zeniths_direct"):
+        lib.grt_pipeline_run_sky_zeniths_direct.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky),
+                                                            C.POINTER(GrtZeniths), C.POINTER(GrtZenithSurface),
+                                                            C.POINTER(GrtZenithDirect), C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.grt_zenith_surface_tables.argtypes = [c_double_p, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p]
+        lib.grt_zenith_surface_tables.restype = None
     if hasattr(lib, "grt_pipeline_run_sky_tiles"):
         lib.grt_pipeline_run_sky_tiles.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky),
                                                    C.POINTER(GrtSurfaceTiles), C.c_void_p]
@@ -921,6 +937,22 @@ def make_zeniths(cos_zenith, weight=None):
     gz = GrtZeniths(keep["mu"].shape[1], _dp(keep["mu"]), _opt_dp(keep["weight"]), None, None)
     gz.keep = keep             # (as make_cloud_model)
     return gz, keep
+
+
+def make_zenith_surface(grid, direct_albedo):
+    """Pack a direct-beam albedo per (column, sun angle) into a GrtZenithSurface struct (+ keep-alive arrays) for
+    Pipeline.run_sky_zeniths_direct.  grid [NS] cm-1, strictly increasing, NS >= 2, shared by columns and angles;
+    direct_albedo [ncol][Z][NS], each in [0, 1] (surfaces.ocean_direct_albedo fills open water's).  keep["shape"] is
+    (ncol, Z)."""
+    keep = {"albedo_grid": _f64(grid), "direct_albedo": _f64(direct_albedo)}
+    if keep["albedo_grid"].ndim != 1 or keep["albedo_grid"].size < 2:
+        raise ValueError(f"albedo grid of {keep['albedo_grid'].size} point(s): at least 2")
+    if keep["direct_albedo"].ndim != 3 or keep["direct_albedo"].shape[2] != keep["albedo_grid"].size:
+        raise ValueError(f"direct_albedo of shape {keep['direct_albedo'].shape}: [ncol][Z][{keep['albedo_grid'].size}]")
+    keep["shape"] = keep["direct_albedo"].shape[:2]
+    gs = GrtZenithSurface(keep["albedo_grid"].size, _dp(keep["albedo_grid"]), _dp(keep["direct_albedo"]))
+    gs.keep = keep             # (as make_cloud_model)
+    return gs, keep
 
 
 def make_channels(first, weights_per_channel, center=None):
@@ -1806,6 +1838,62 @@ class Pipeline:
         lv = self.buffers["sky_zenith_profiles.angle_levels"].to_host((ncol, nsets, Z, 2, self.num_levels))
         out["angle_fluxes"] = self.buffers["sky_zenith_profiles.angles"].to_host((ncol, nsets, Z, 6))
         out["angle_up"], out["angle_down"] = lv[:, :, :, 0].copy(), lv[:, :, :, 1].copy()
+        return out
+
+    def run_sky_zeniths_direct(self, gcols, gsky, gzeniths, gsurface=None, direct=True, profiles=False):
+        """grt_pipeline_run_sky_zeniths_direct: run_sky_zeniths with gsurface's (make_zenith_surface; None: the surface
+        in force) direct-beam albedo per (column, angle) and, direct=True, every angle's direct beam and its mean over the
+        angles, into device buffers of this call's own: the six-row form (sky_zenith_direct_fluxes() reads it) or,
+        profiles=True, the profile form (sky_zenith_direct_profiles() reads it)."""
+        nsets = max(sky_set_count(gsky.sets), 1)
+        Z, V, n = max(gzeniths.num_zeniths, 1), self.num_levels, self.max_columns
+        name = "sky_zenith_direct_profiles" if profiles else "sky_zenith_direct"
+        gzeniths.zenith_fluxes_dev = self._buffer(name + ".angles", 8 * n * nsets * Z * 6).ptr
+        gzeniths.zenith_level_fluxes_dev = self._buffer(name + ".angle_levels", 8 * n * nsets * Z * 2 * V).ptr if profiles else None
+        gdirect = None
+        if direct:
+            rows = GRT_DIRECT_ROWS_PER_SET
+            gdirect = GrtZenithDirect(self._buffer(name + ".direct", 8 * n * nsets * rows).ptr,
+                                      self._buffer(name + ".direct_levels", 8 * n * nsets * V).ptr if profiles else None,
+                                      self._buffer(name + ".angle_direct", 8 * n * nsets * Z * rows).ptr,
+                                      self._buffer(name + ".angle_direct_levels", 8 * n * nsets * Z * V).ptr if profiles else None)
+        self._zenith_direct_given = bool(direct)
+        if profiles:
+            ptrs = self._profile_ptrs(name, nsets)
+        else:
+            ptrs = [None, None, self._buffer(name, 8 * GRT_FLUXES_PER_COLUMN * nsets * n).ptr]
+        check(self.lib.grt_pipeline_run_sky_zeniths_direct(self.p, C.byref(gcols), C.byref(gsky), C.byref(gzeniths),
+                                                           None if gsurface is None else C.byref(gsurface),
+                                                           None if gdirect is None else C.byref(gdirect), *ptrs))
+
+    def sky_zenith_direct_fluxes(self, ncol, nsets, Z):
+        """The last six-row run_sky_zeniths_direct of nsets sets: dict(fluxes=[ncol][nsets][12] and
+        angle_fluxes=[ncol][nsets][Z][6], sky_zenith_fluxes()' pair; with direct=True also direct=[ncol][nsets][3], the mean over
+        the angles of the direct beam at the top of the atmosphere, the surface and the user level (W m-2; +0.0 without a
+        user level), and angle_direct=[ncol][nsets][Z][3], every angle's)."""
+        self.sync()
+        out = dict(fluxes=self.buffers["sky_zenith_direct"].to_host((ncol, nsets, GRT_FLUXES_PER_COLUMN)),
+                   angle_fluxes=self.buffers["sky_zenith_direct.angles"].to_host((ncol, nsets, Z, 6)))
+        if self._zenith_direct_given:
+            out["direct"] = self.buffers["sky_zenith_direct.direct"].to_host((ncol, nsets, GRT_DIRECT_ROWS_PER_SET))
+            out["angle_direct"] = self.buffers["sky_zenith_direct.angle_direct"].to_host((ncol, nsets, Z, GRT_DIRECT_ROWS_PER_SET))
+        return out
+
+    def sky_zenith_direct_profiles(self, ncol, nsets, Z):
+        """The last run_sky_zeniths_direct(profiles=True) of nsets sets: sky_zenith_profiles()' dict and, with direct=True,
+        direct=[ncol][nsets][3], direct_levels=[ncol][nsets][V] (the mean over the angles at every level, top first),
+        angle_direct=[ncol][nsets][Z][3] and angle_direct_levels=[ncol][nsets][Z][V]."""
+        name, V = "sky_zenith_direct_profiles", self.num_levels
+        per_set = self._read_profiles(name, nsets, ncol)
+        out = {k: np.stack([s[k] for s in per_set], axis=1) for k in per_set[0]}
+        lv = self.buffers[name + ".angle_levels"].to_host((ncol, nsets, Z, 2, V))
+        out["angle_fluxes"] = self.buffers[name + ".angles"].to_host((ncol, nsets, Z, 6))
+        out["angle_up"], out["angle_down"] = lv[:, :, :, 0].copy(), lv[:, :, :, 1].copy()
+        if self._zenith_direct_given:
+            out["direct"] = self.buffers[name + ".direct"].to_host((ncol, nsets, GRT_DIRECT_ROWS_PER_SET))
+            out["direct_levels"] = self.buffers[name + ".direct_levels"].to_host((ncol, nsets, V))
+            out["angle_direct"] = self.buffers[name + ".angle_direct"].to_host((ncol, nsets, Z, GRT_DIRECT_ROWS_PER_SET))
+            out["angle_direct_levels"] = self.buffers[name + ".angle_direct_levels"].to_host((ncol, nsets, Z, V))
         return out
 
     def views(self, band):

@@ -450,6 +450,22 @@ static inline int grt_zenith_args_ok(GrtZenithArgs const *z)
     return z != NULL && z->mu != NULL && z->zeniths >= 1 && z->count >= 1 && z->first >= 0 &&
            z->first + z->count <= z->zeniths;
 }
+/* The direct-beam albedo of every (column, angle) of a zenith instance (grt_pipeline_run_sky_zeniths_direct): joined behind
+   a GrtZenithArgs, the row of column c under angle k reads, in place of a->alb_dir, slope w + intercept of entry
+   entry[i] of tables[(c zeniths + k) num_entries ..] -- GrtSurfaceArgs' entries and pairs (grt_surface_entry_map,
+   grt_surface_tables over ncol x zeniths knot rows), evaluated per thread as grt_launch_spread_surface evaluates them
+   (multiply, then add: the same double), so no [ncol][zeniths][nw] rows exist.  The diffuse albedo stays a->alb_dif.
+   entry: DEVICE [nw]; tables: DEVICE [ncol][zeniths][num_entries][2]. */
+typedef struct GrtZenithSurfaceArgs
+{
+    int num_entries;                /* NS + 1 >= 3 */
+    int const *entry;
+    double const *tables;
+} GrtZenithSurfaceArgs;
+static inline int grt_zenith_surface_args_ok(GrtZenithSurfaceArgs const *c)
+{
+    return c != NULL && c->num_entries >= 3 && c->entry != NULL && c->tables != NULL;
+}
 /* The shared-layer kernel of the zenith form (k_shortwave.hip: sw_zenith_kernel), six rows in one sweep
    (grt_sw_one_sweep(a) must hold: hipErrorInvalidValue otherwise): grid row y is column y / chunks and the
    GRT_ZENITH_CHUNK consecutive angles from (y % chunks) GRT_ZENITH_CHUNK on, chunks = ceil(zeniths / GRT_ZENITH_CHUNK);
@@ -458,15 +474,24 @@ static inline int grt_zenith_args_ok(GrtZenithArgs const *z)
    read: one launch takes every angle).  sc, ae (either may be NULL): the kernel's instance with the draws of sc, the
    aerosol object or both joined, as the zenith instances join them -- grid row y is then (column, draw first + .. of
    sc->count, chunk), the chunks of a draw next to each other, at most 65 535 rows, and the partial sums lie at the slot
-   (c zeniths + k) subcolumns + s.  Each instance carries the most angles of {2, 4} that leave it three waves per SIMD
-   and no scratch; grt_zenith_chunk names an instance's. */
+   (c zeniths + k) subcolumns + s.  d, zs (either may be NULL; grt_pipeline_run_sky_zeniths_direct): the instances that
+   also leave every angle's direct beam at the top and the surface (GrtDirectArgs: three rows at the angle's slot, riding
+   with its six), that read every angle's own direct albedo (GrtZenithSurfaceArgs), or both, behind each of the four
+   joins.  Each instance carries the most angles of {2, 4} that leave it three waves per SIMD and no scratch
+   (DESIGN.md 3.3); grt_zenith_chunk names an instance's -- GRT_ZENITH_CHUNK_DIRECT, _SURFACE and _DIRECT_SURFACE are the
+   chunks of the instances with d, zs and both, the same behind each of the four joins. */
 #define GRT_ZENITH_CHUNK 4
 #define GRT_ZENITH_CHUNK_AEROSOLS 4
 #define GRT_ZENITH_CHUNK_SUBCOLUMNS 4
 #define GRT_ZENITH_CHUNK_SUBCOLUMNS_AEROSOLS 4
-int grt_zenith_chunk(GrtSubcolumnArgs const *sc, GrtAerosolArgs const *ae);
+#define GRT_ZENITH_CHUNK_DIRECT 4
+#define GRT_ZENITH_CHUNK_SURFACE 4
+#define GRT_ZENITH_CHUNK_DIRECT_SURFACE 4
+struct GrtDirectArgs;
+int grt_zenith_chunk(GrtSubcolumnArgs const *sc, GrtAerosolArgs const *ae, struct GrtDirectArgs const *d,
+                     GrtZenithSurfaceArgs const *zs);
 int grt_launch_sw_zeniths(void *stream, GrtSwArgs const *a, GrtZenithArgs const *z, GrtSubcolumnArgs const *sc,
-                          GrtAerosolArgs const *ae);
+                          GrtAerosolArgs const *ae, struct GrtDirectArgs const *d, GrtZenithSurfaceArgs const *zs);
 /* The weighted mean over a column's angles of one output row, in a fixed order, and every angle's own rows: for column c
    and row r (of `rows` per slot) each angle's blocks are added as grt_launch_reduce_partials adds them -- an angle whose
    mu [ncol][zeniths] is <= 0 counts as +0.0 whatever its partial sums hold -- and stored at per_angle[(c zeniths + k) rows
@@ -546,7 +571,9 @@ int grt_launch_tile_mean(void *stream, double const *partials, int ncol, int til
    partials[(slot V + level) nblocks + block] in the profile form, slot as the instance's own partial sums have it.  The
    three (V) rows ride with the six (2 V) through the same wave and workgroup sums: rows 0, L and user_level of the
    profile form are, bit for bit, the six-row form's three, in its one sweep and in its two.  The profile form's dynamic
-   LDS is 3 V x 2 doubles per workgroup.  Shortwave only; reduced as the instance's own rows are. */
+   LDS is 3 V x 2 doubles per workgroup.  Shortwave only; reduced as the instance's own rows are.  Behind a GrtZenithArgs
+   (grt_pipeline_run_sky_zeniths_direct: with a GrtZenithSurfaceArgs between them, or without) the slot is the zenith
+   instance's, (c zeniths + k) subcolumns + s, a night sample's rows are +0.0, and grt_launch_sky_zenith_mean reduces. */
 typedef struct GrtDirectArgs
 {
     double *partials;
@@ -813,8 +840,8 @@ typedef enum GrtSolverOutput
    form of the clouds (GRT_OUT_ROWS and GRT_OUT_LEVELS: the five objects of sky_combine, optics_dev.h; the aerosol table
    stays per column whatever the subcolumn); `bins` goes with GRT_OUT_LEVEL_BINS and with nothing else; `zeniths` (the
    shortwave's GRT_OUT_ROWS and GRT_OUT_LEVELS) goes alone or with aerosols, subcolumns or both, never with `clouds`; `direct` (the shortwave's GRT_OUT_ROWS and
-   GRT_OUT_LEVELS) goes with any join of clouds and aerosols or none, and selects instances of its own: the instance
-   without it is the one it was; `jacobian` is the same for the longwave's GRT_OUT_ROWS and GRT_OUT_LEVELS; `responses` goes with GRT_OUT_LEVELS alone, in the shortwave always together with `direct`, never with `bins`, `zeniths` or `jacobian`, and selects instances of its own as `direct` does; `scatter` (the longwave's GRT_OUT_CHAINS, GRT_OUT_ROWS and GRT_OUT_LEVELS, with any
+   GRT_OUT_LEVELS) goes with any join of clouds and aerosols or none, or behind `zeniths` and what joins them, and selects instances of its own: the instance
+   without it is the one it was; `zenith_surface` (every angle's own direct albedo) goes with `zeniths` alone, with or without `direct`, and selects instances of its own likewise; `jacobian` is the same for the longwave's GRT_OUT_ROWS and GRT_OUT_LEVELS; `responses` goes with GRT_OUT_LEVELS alone, in the shortwave always together with `direct`, never with `bins`, `zeniths` or `jacobian`, and selects instances of its own as `direct` does; `scatter` (the longwave's GRT_OUT_CHAINS, GRT_OUT_ROWS and GRT_OUT_LEVELS, with any
    join of clouds and aerosols or none, never with the others) names the instances of lw_scatter_kernel, which
    grt_launch_lw_scatter alone launches.  The kind of instance follows from which pointers are set, and a kernel takes the structs that are
    set as arguments after its band's own.  The next joined object is a pointer here, a line in grt_solver_instance_ok
@@ -831,6 +858,7 @@ typedef struct GrtSolverInstance
     GrtJacobianArgs const *jacobian;
     GrtResponseArgs const *responses;
     GrtScatterArgs const *scatter;  /* grt_launch_lw_scatter's instances (GRT_OUT_CHAINS, _ROWS, _LEVELS): no other launcher's */
+    GrtZenithSurfaceArgs const *zenith_surface;
 } GrtSolverInstance;
 typedef enum GrtSolverJoin
 {
@@ -1146,9 +1174,13 @@ inline bool grt_solver_instance_ok(GrtSolverInstance const &in, Args const &a)
     // (the sun angles join the six-row and level forms: clear sky, or with aerosols, subcolumns or both)
     bool const zeniths_ok = in.zeniths == nullptr || (in.clouds == nullptr && grt_zenith_args_ok(in.zeniths) &&
                                                       (in.out == GRT_OUT_ROWS || in.out == GRT_OUT_LEVELS));
-    // (the direct beam leaves the six-row and level forms, under one sun per column; the longwave launcher has no such case)
-    bool const direct_ok = in.direct == nullptr || (in.zeniths == nullptr && grt_direct_args_ok(in.direct) &&
+    // (the direct beam leaves the six-row and level forms, under one sun per column or several; the longwave launcher has no
+    // such case)
+    bool const direct_ok = in.direct == nullptr || (grt_direct_args_ok(in.direct) &&
                                                     (in.out == GRT_OUT_ROWS || in.out == GRT_OUT_LEVELS));
+    // (every angle's own direct albedo: the zenith instances alone)
+    bool const zenith_surface_ok = in.zenith_surface == nullptr || (in.zeniths != nullptr && in.jacobian == nullptr &&
+                                                                    grt_zenith_surface_args_ok(in.zenith_surface));
     // (the surface-temperature Jacobian leaves the same two forms; the shortwave launcher has no such case)
     bool const jacobian_ok = in.jacobian == nullptr || (in.zeniths == nullptr && in.direct == nullptr &&
                                                         grt_jacobian_args_ok(in.jacobian) &&
@@ -1163,7 +1195,7 @@ inline bool grt_solver_instance_ok(GrtSolverInstance const &in, Args const &a)
                                                       (in.out == GRT_OUT_CHAINS || in.out == GRT_OUT_ROWS || in.out == GRT_OUT_LEVELS));
     // (two grid points for a trapezoid; the chain form of the scattering correction integrates nothing: one will do)
     uint64_t const least_points = in.scatter != nullptr && !fused ? 1 : 2;
-    return zeniths_ok && direct_ok && jacobian_ok && responses_ok && scatter_ok && a.ncol >= 1 && a.nw >= least_points && a.num_levels >= 2 &&
+    return zeniths_ok && direct_ok && zenith_surface_ok && jacobian_ok && responses_ok && scatter_ok && a.ncol >= 1 && a.nw >= least_points && a.num_levels >= 2 &&
            cloud_forms <= 1 && joined <= (fused ? 2 : 0) && (in.bins != nullptr) == (in.out == GRT_OUT_LEVEL_BINS) &&
            (in.clouds == nullptr || grt_cloud_args_ok(in.clouds)) &&
            (in.aerosols == nullptr || grt_aerosol_args_ok(in.aerosols)) &&

@@ -23,7 +23,8 @@
 // pack: nothing, GrtCloudArgs, GrtAerosolArgs or GrtSubcolumnArgs, a GrtAerosolArgs behind either form of the clouds where
 // both join, a GrtBandArgs last where OUT is per bin, or a GrtZenithArgs (several sun angles per column: alone, or last
 // behind a GrtAerosolArgs, a GrtSubcolumnArgs or both, six rows or every level); a GrtDirectArgs last (six rows or every level, with any of the cloud and aerosol joins) makes the instance that also
-// leaves the direct beam of its sweep (LevelSink: DIRECT).
+// leaves the direct beam of its sweep (LevelSink: DIRECT).  Behind a GrtZenithArgs a GrtZenithSurfaceArgs (every angle's own
+// direct albedo: row_alb_dir), a GrtDirectArgs or both may follow (grt_pipeline_run_sky_zeniths_direct).
 // sw_tile_kernel, behind sw_zenith_kernel, is the six-row instance for several surface tiles per column
 // (grt_launch_sw_tiles): the layer properties once for a chunk of tiles, what reads the albedo per tile.
 // The in-kernel range checks of the reference are no-ops on device builds
@@ -291,6 +292,25 @@ __device__ __forceinline__ double row_mu(GrtSwArgs const &a, SolverRow const &ro
     }
 }
 
+// the direct-beam albedo of column col at grid point ii: the column's row, or -- a GrtZenithSurfaceArgs is joined -- the
+// pair of sun angle `sun` (c zeniths + k) at the point's entry, evaluated as spread_surface_kernel evaluates it (multiply,
+// then add: the double that kernel would write into the angle's row)
+template <typename... Joins>
+__device__ __forceinline__ double row_alb_dir(GrtSwArgs const &a, int col, int sun, uint64_t ii, Joins const &...joins)
+{
+    if constexpr (has<GrtZenithSurfaceArgs, Joins...>)
+    {
+        GrtZenithSurfaceArgs const zs = pick<GrtZenithSurfaceArgs>(joins...);
+        double const *mb = zs.tables + ((uint64_t)sun*(uint64_t)zs.num_entries + (uint64_t)zs.entry[ii])*2;
+        double const w = a.w0 + ii*a.dw;
+        return mb[0]*w + mb[1];
+    }
+    else
+    {
+        return a.alb_dir[(uint64_t)col*a.alb_stride + ii];
+    }
+}
+
 // OUT fused (GRT_OUT_ROWS and after): the clear-sky tail in one kernel -- tau, omega, g of a layer are formed in registers
 // from tau_gas and the Rayleigh optical depth (LayerOptics: identical values), the first sweep's reflectances are parked
 // in a scratch block instead of the output rows, nothing spectral is written and the six integrated output rows leave as
@@ -310,8 +330,9 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Joins... 
     constexpr bool FUSED = grt_out_fused(OUT), PROFILE = grt_out_levels(OUT), SPECTRAL = OUT == GRT_OUT_ROWS_POINTS;
     constexpr bool DIRECT = has<GrtDirectArgs, Joins...>;
     static_assert(has<GrtBandArgs, Joins...> == (OUT == GRT_OUT_LEVEL_BINS), "bins go with GRT_OUT_LEVEL_BINS alone");
-    static_assert(!DIRECT || ((OUT == GRT_OUT_ROWS || OUT == GRT_OUT_LEVELS) && !has<GrtZenithArgs, Joins...>),
-                  "the direct beam leaves the six-row and level forms, one sun per column");
+    static_assert(!DIRECT || OUT == GRT_OUT_ROWS || OUT == GRT_OUT_LEVELS, "the direct beam leaves the six-row and level forms");
+    static_assert(!has<GrtZenithSurfaceArgs, Joins...> || has<GrtZenithArgs, Joins...>,
+                  "every angle's own direct albedo goes with the sun angles");
     constexpr bool RESPONSES = has<GrtResponseArgs, Joins...>;
     static_assert(!RESPONSES || (OUT == GRT_OUT_LEVELS && DIRECT), "the response rows leave the level form, the direct beam with them");
     SolverRow const row = solver_row(a.ncol, joins...);
@@ -339,6 +360,15 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Joins... 
             for (int r = threadIdx.x; r < nrows; r += kSolverBlock)
             {
                 a.partials[((uint64_t)row.slot*nrows + r)*gridDim.x + blockIdx.x] = 0.;
+            }
+            if constexpr (DIRECT)
+            {
+                int const drows = PROFILE ? a.num_levels : 3;
+                double *dp = pick<GrtDirectArgs>(joins...).partials;
+                for (int r = threadIdx.x; r < drows; r += kSolverBlock)
+                {
+                    dp[((uint64_t)row.slot*drows + r)*gridDim.x + blockIdx.x] = 0.;
+                }
             }
             return;
         }
@@ -397,7 +427,7 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Joins... 
         double const scale = a.solar[ii]*mu_dir;
         double const tsi = a.tsi[col];
         double up_s, dn_s;                                                          // :318-329 at the surface
-        level_flux(dir, dif, Ru, a.alb_dir[(uint64_t)col*a.alb_stride + ii], a.alb_dif[(uint64_t)col*a.alb_stride + ii],
+        level_flux(dir, dif, Ru, row_alb_dir(a, col, row.sun, ii, joins...), a.alb_dif[(uint64_t)col*a.alb_stride + ii],
                    up_s, dn_s);
         put_level(sink, 0, Rd + Tu*up_s, 1., scale, tsi);
         put_level(sink, L, up_s, dn_s, scale, tsi);
@@ -411,7 +441,7 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Joins... 
     }
 
     // sweep 1: shortwave.c:280-294
-    double Rdir_dn = a.alb_dir[(uint64_t)col*a.alb_stride + ii];
+    double Rdir_dn = row_alb_dir(a, col, row.sun, ii, joins...);
     double Rdif_dn = a.alb_dif[(uint64_t)col*a.alb_stride + ii];
     // Fused form: only three levels' fluxes leave the kernel (top, surface, the user's), so the downward-beam reflectances
     // of the other levels are never needed again -- the surface's are the albedos, the top's and the user level's stay in
@@ -561,7 +591,10 @@ __global__ __launch_bounds__(kSolverBlock) void ck_sw_kernel(GrtCkSolveArgs a)
 // call evaluates it first), so every angle's partial sums are the zenith instance's of sw_kernel<GRT_OUT_ROWS> with the
 // same joins, bit for bit, at its slot (c zeniths + k) subcolumns + s.  Angles past the column's last and night angles
 // (mu <= 0) are skipped by flags that are uniform per workgroup; a night angle's slot gets +0.0.  Joins: nothing, a
-// GrtAerosolArgs, a GrtSubcolumnArgs, or a GrtAerosolArgs behind a GrtSubcolumnArgs.
+// GrtAerosolArgs, a GrtSubcolumnArgs, or a GrtAerosolArgs behind a GrtSubcolumnArgs; behind any of the four a
+// GrtZenithSurfaceArgs (the angle's own direct albedo at the surface, in place of the column's), a GrtDirectArgs (the angle's
+// direct beam at the top and the surface -- 1 and dir[u], scaled as the rows beside them -- through the sink's three more
+// rows) or both: sw_kernel's zenith instances with those joins, bit for bit.
 template <int ZN, typename... Joins>
 __global__ __launch_bounds__(kSolverBlock) void sw_zenith_kernel(GrtSwArgs a, GrtZenithArgs zn, Joins... joins)
 {
@@ -628,7 +661,10 @@ __global__ __launch_bounds__(kSolverBlock) void sw_zenith_kernel(GrtSwArgs a, Gr
             Ru = s.R + s.T*s.T*Ru*C;                                                         // :299-306
         }
     }
-    double const alb_dir = a.alb_dir[(uint64_t)col*a.alb_stride + ii], alb_dif = a.alb_dif[(uint64_t)col*a.alb_stride + ii];
+    constexpr bool DIRECT = has<GrtDirectArgs, Joins...>, SURFACE = has<GrtZenithSurfaceArgs, Joins...>;
+    // (the column's direct albedo, once; with a GrtZenithSurfaceArgs every angle reads its own below)
+    double const alb_col = SURFACE ? 0. : a.alb_dir[(uint64_t)col*a.alb_stride + ii];
+    double const alb_dif = a.alb_dif[(uint64_t)col*a.alb_stride + ii];
     double const solar = a.solar[ii], tsi = a.tsi[col];
 #pragma unroll
     for (int u = 0; u < ZN; ++u)
@@ -637,21 +673,35 @@ __global__ __launch_bounds__(kSolverBlock) void sw_zenith_kernel(GrtSwArgs a, Gr
         {
             continue;
         }
-        int const slot = (col*Z + k0 + u)*S + draw;
+        int const sun = col*Z + k0 + u, slot = sun*S + draw;
         if (!day[u])
         {
             if (threadIdx.x < 6)
             {
                 a.partials[((uint64_t)slot*6 + threadIdx.x)*gridDim.x + blockIdx.x] = 0.;
             }
+            if constexpr (DIRECT)
+            {
+                if (threadIdx.x < 3)
+                {
+                    pick<GrtDirectArgs>(joins...).partials[((uint64_t)slot*3 + threadIdx.x)*gridDim.x + blockIdx.x] = 0.;
+                }
+            }
             continue;
         }
-        LevelSink<true, false> sink(a, slot, i, live);
+        // (six rows, and -- a GrtDirectArgs is joined -- the angle's direct beam at the top and the surface beside them)
+        LevelSink<true, false, false, false, DIRECT> sink(a, slot, i, live, GrtBandArgs{0, 0, nullptr, 0},
+                                                          pick<GrtDirectArgs>(joins...));
         double const scale = solar*mu[u];
         double up_s, dn_s;                                                          // :318-329 at the surface
-        level_flux(dir[u], dif[u], Ru, alb_dir, alb_dif, up_s, dn_s);
+        level_flux(dir[u], dif[u], Ru, SURFACE ? row_alb_dir(a, col, sun, ii, joins...) : alb_col, alb_dif, up_s, dn_s);
         put_level(sink, 0, Rd[u] + Tu*up_s, 1., scale, tsi);
         put_level(sink, L, up_s, dn_s, scale, tsi);
+        if constexpr (DIRECT)
+        {
+            put_direct(sink, 0, 1., scale, tsi);
+            put_direct(sink, L, dir[u], scale, tsi);
+        }
         __syncthreads();                            // (block_partials' LDS is the angle before's: every wave has read it)
         sink.finish(a);
     }
@@ -996,6 +1046,22 @@ int launch(hipStream_t s, GrtSolverInstance const &in, GrtSwArgs const &a, Joins
     return (int)hipGetLastError();
 }
 
+// the zenith instance of OUT behind the joins `front` that also leaves every angle's direct beam (a GrtDirectArgs last),
+// reads every angle's own direct albedo (a GrtZenithSurfaceArgs behind the GrtZenithArgs) or both
+template <GrtSolverOutput OUT, typename... Front>
+int launch_zenith_forms(hipStream_t s, GrtSolverInstance const &in, GrtSwArgs const &a, Front const &...front)
+{
+    if (in.zenith_surface != nullptr && in.direct != nullptr)
+    {
+        return launch<OUT>(s, in, a, front..., *in.zeniths, *in.zenith_surface, *in.direct);
+    }
+    if (in.zenith_surface != nullptr)
+    {
+        return launch<OUT>(s, in, a, front..., *in.zeniths, *in.zenith_surface);
+    }
+    return launch<OUT>(s, in, a, front..., *in.zeniths, *in.direct);
+}
+
 } // namespace
 
 extern "C" int grt_launch_ck_sw(void *stream, GrtCkSolveArgs const *a)
@@ -1042,6 +1108,30 @@ extern "C" int grt_launch_sw(void *stream, GrtSolverInstance const *in, GrtSwArg
             return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, *in->aerosols, d, r);
         case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
             return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->aerosols, d, r);
+        default:
+            return (int)hipErrorInvalidValue;
+        }
+    }
+    // the zenith instances that also leave the direct beam, read every angle's own direct albedo or both
+    // (grt_pipeline_run_sky_zeniths_direct's sets and forms: three instances a case, launch_zenith_forms) ...
+    if (in->zeniths != nullptr && (in->direct != nullptr || in->zenith_surface != nullptr))
+    {
+        switch (GRT_INSTANCE(in->out, grt_solver_join(in)))
+        {
+        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS): return launch_zenith_forms<GRT_OUT_ROWS>(s, *in, *a);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS): return launch_zenith_forms<GRT_OUT_LEVELS>(s, *in, *a);
+        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS_AEROSOLS):
+            return launch_zenith_forms<GRT_OUT_ROWS>(s, *in, *a, *in->aerosols);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS_AEROSOLS):
+            return launch_zenith_forms<GRT_OUT_LEVELS>(s, *in, *a, *in->aerosols);
+        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS_SUBCOLUMNS):
+            return launch_zenith_forms<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS_SUBCOLUMNS):
+            return launch_zenith_forms<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns);
+        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS_SUBCOLUMNS_AEROSOLS):
+            return launch_zenith_forms<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns, *in->aerosols);
+        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS_SUBCOLUMNS_AEROSOLS):
+            return launch_zenith_forms<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->aerosols);
         default:
             return (int)hipErrorInvalidValue;
         }
@@ -1138,24 +1228,65 @@ int launch_zeniths(hipStream_t s, GrtSwArgs const &a, GrtZenithArgs const &z, in
     return (int)hipGetLastError();
 }
 
+// ... of the instance behind the joins `front` that leaves the direct beam, reads every angle's own albedo or both
+template <typename... Front>
+int launch_zenith_forms(hipStream_t s, GrtSwArgs const &a, GrtZenithArgs const &z, int draws, GrtDirectArgs const *d,
+                        GrtZenithSurfaceArgs const *zs, Front const &...front)
+{
+    if (d != nullptr && zs != nullptr)
+    {
+        return launch_zeniths<GRT_ZENITH_CHUNK_DIRECT_SURFACE>(s, a, z, draws, front..., *zs, *d);
+    }
+    if (zs != nullptr)
+    {
+        return launch_zeniths<GRT_ZENITH_CHUNK_SURFACE>(s, a, z, draws, front..., *zs);
+    }
+    return launch_zeniths<GRT_ZENITH_CHUNK_DIRECT>(s, a, z, draws, front..., *d);
+}
+
 } // namespace
 
-extern "C" int grt_zenith_chunk(GrtSubcolumnArgs const *sc, GrtAerosolArgs const *ae)
+extern "C" int grt_zenith_chunk(GrtSubcolumnArgs const *sc, GrtAerosolArgs const *ae, GrtDirectArgs const *d,
+                                GrtZenithSurfaceArgs const *zs)
 {
+    if (d != nullptr || zs != nullptr)
+    {
+        return d != nullptr ? (zs != nullptr ? GRT_ZENITH_CHUNK_DIRECT_SURFACE : GRT_ZENITH_CHUNK_DIRECT) : GRT_ZENITH_CHUNK_SURFACE;
+    }
     return sc != nullptr ? (ae != nullptr ? GRT_ZENITH_CHUNK_SUBCOLUMNS_AEROSOLS : GRT_ZENITH_CHUNK_SUBCOLUMNS) :
            (ae != nullptr ? GRT_ZENITH_CHUNK_AEROSOLS : GRT_ZENITH_CHUNK);
 }
 
 extern "C" int grt_launch_sw_zeniths(void *stream, GrtSwArgs const *a, GrtZenithArgs const *z, GrtSubcolumnArgs const *sc,
-                                     GrtAerosolArgs const *ae)
+                                     GrtAerosolArgs const *ae, GrtDirectArgs const *d, GrtZenithSurfaceArgs const *zs)
 {
-    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                  nullptr};
     if (!grt_solver_instance_ok(in, *a) || z == nullptr || z->mu == nullptr || z->zeniths < 1 || !grt_sw_one_sweep(a) ||
-        (sc != nullptr && !grt_subcolumn_args_ok(sc)) || (ae != nullptr && !grt_aerosol_args_ok(ae)))
+        (sc != nullptr && !grt_subcolumn_args_ok(sc)) || (ae != nullptr && !grt_aerosol_args_ok(ae)) ||
+        (d != nullptr && !grt_direct_args_ok(d)) || (zs != nullptr && !grt_zenith_surface_args_ok(zs)))
     {
         return (int)hipErrorInvalidValue;
     }
     hipStream_t const s = (hipStream_t)stream;
+    // the instances that also leave the direct beam, read every angle's own direct albedo or both, behind each join ...
+    if (d != nullptr || zs != nullptr)
+    {
+        if (sc != nullptr && ae != nullptr)
+        {
+            return launch_zenith_forms(s, *a, *z, sc->count, d, zs, *sc, *ae);
+        }
+        if (sc != nullptr)
+        {
+            return launch_zenith_forms(s, *a, *z, sc->count, d, zs, *sc);
+        }
+        if (ae != nullptr)
+        {
+            return launch_zenith_forms(s, *a, *z, 1, d, zs, *ae);
+        }
+        return launch_zenith_forms(s, *a, *z, 1, d, zs);
+    }
+    // ... and the four without
     if (sc != nullptr && ae != nullptr)
     {
         return launch_zeniths<GRT_ZENITH_CHUNK_SUBCOLUMNS_AEROSOLS>(s, *a, *z, sc->count, *sc, *ae);
@@ -1191,7 +1322,7 @@ int launch_tiles(hipStream_t s, GrtSwArgs const &a, GrtTileArgs const &t, int dr
 extern "C" int grt_launch_sw_tiles(void *stream, GrtSwArgs const *a, GrtTileArgs const *t, GrtSubcolumnArgs const *sc,
                                    GrtAerosolArgs const *ae)
 {
-    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (a == nullptr || t == nullptr || !grt_solver_instance_ok(in, *a) || (!grt_sw_one_sweep(a) && a->park == nullptr) ||
         (sc != nullptr && !grt_subcolumn_args_ok(sc)) || (ae != nullptr && !grt_aerosol_args_ok(ae)))
     {

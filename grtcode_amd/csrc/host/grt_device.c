@@ -486,6 +486,8 @@ EXTERN size_t grt_sizeof(int kind)
         case GRT_CLOUD_MODEL: return sizeof(GrtCloudModel_t);
         case GRT_CLOUD_FIELDS: return sizeof(GrtCloudFields_t);
         case GRT_LW_SCATTER: return sizeof(GrtLwScatter_t);
+        case GRT_ZENITH_SURFACE: return sizeof(GrtZenithSurface_t);
+        case GRT_ZENITH_DIRECT: return sizeof(GrtZenithDirect_t);
         default: return 0;
     }
 }

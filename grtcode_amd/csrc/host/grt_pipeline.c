@@ -282,8 +282,10 @@ static void grt_pipeline_release(GrtPipeline_t **pipeline)
         grt_keyed_table_free(p, &p->band[b].channel_table);
         grt_keyed_table_free(p, &p->band[b].tile_map);
         grt_keyed_table_free(p, &p->band[b].response_table);
+        grt_keyed_table_free(p, &p->band[b].zen_surf_map);
         grt_kdist_table_free(p->device, &p->band[b].kdist_table);
     }
+    grt_staging_free(p, &p->zen_surf);
     grt_staging_free(p, &p->tile);
     grt_staging_free(p, &p->rad);
     grt_staging_free(p, &p->zen);
@@ -541,6 +543,11 @@ typedef struct GrtJoin
                                           under the band's responses too */
     long long response_pairs[2];       /* ... each band's (response, solver block) pairs and the most responses in one */
     int response_block_max[2];         /* block (grt_check_responses) */
+    GrtZenithSurface_t const *zenith_surface;  /* grt_pipeline_run_sky_zeniths_direct (with zeniths and sets): every angle's
+                                                  shortwave reads its own direct albedo */
+    int zenith_direct;                 /* ... every angle's direct beam leaves too, in the run's form (three rows, or V): */
+    double *zenith_direct_out;         /* DEVICE [ncol][sets][3 or V], the mean over the angles, or NULL */
+    double *zenith_direct_per_angle;   /* DEVICE [ncol][sets][Z][3 or V], or NULL */
 } GrtJoin;
 
 #define GRT_SKY_ALL (GRT_SKY_CLEAN | GRT_SKY_AEROSOL | GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL)
@@ -592,6 +599,13 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
     {
         GRT_TRY(grt_stage_zeniths(p, join->zeniths, C, &zr));
         zr.sky = join->sets != 0;
+        if (join->zenith_surface != NULL && p->band[1].gas != NULL)
+        {
+            GRT_TRY(grt_stage_zenith_surface(p, join->zenith_surface, C, &zr));
+        }
+        zr.direct = join->zenith_direct;
+        zr.direct_out = join->zenith_direct_out;
+        zr.direct_per_angle = join->zenith_direct_per_angle;
     }
     GrtRadianceRun rr;
     if (join->radiances != NULL && p->band[0].gas != NULL)
@@ -1537,6 +1551,105 @@ EXTERN int grt_pipeline_run_sky_zeniths(GrtPipeline_t *p, GrtColumns_t const *co
     GRT_TRY(check_zeniths(p, cols, zn, level_fluxes_dev, fluxes_dev));
     join.zeniths = zn;
     GRT_TRY(run_under_zeniths(p, cols, &join, nsets, level_fluxes_dev, heating_dev, fluxes_dev));
+    return GRTCODE_SUCCESS;
+}
+
+/* grt_ext.h: grt_pipeline_run_sky_zeniths with a direct-beam albedo per (column, angle), every angle's direct beam, or both */
+EXTERN int grt_pipeline_run_sky_zeniths_direct(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky,
+                                               GrtZeniths_t const *zn, GrtZenithSurface_t const *surface,
+                                               GrtZenithDirect_t const *direct, fp_t *level_fluxes_dev, fp_t *heating_dev,
+                                               fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    int nsets;
+    GRT_TRY(check_sky_sets(sky, &nsets));
+    GrtAerosols_t a;
+    GrtJoin join;
+    GRT_TRY(sky_join(p, cols, sky, &a, &join));
+    GRT_TRY(check_zeniths(p, cols, zn, level_fluxes_dev, fluxes_dev));
+    if (surface == NULL && direct == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "surface and direct are both NULL: grt_pipeline_run_sky_zeniths is that call.%s", "");
+    }
+    int const profile = level_fluxes_dev != NULL, V = p->num_levels, Z = zn->num_zeniths;
+    if (direct != NULL)
+    {
+        if (direct->direct_fluxes_dev == NULL && direct->direct_level_fluxes_dev == NULL &&
+            direct->zenith_direct_fluxes_dev == NULL && direct->zenith_direct_level_fluxes_dev == NULL)
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "the four outputs of direct (GrtZenithDirect_t) are all NULL: nothing to write.%s", "");
+        }
+        if (!profile && (direct->direct_level_fluxes_dev != NULL || direct->zenith_direct_level_fluxes_dev != NULL))
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "%s is given in the six-row form (level_fluxes_dev is NULL).",
+                     direct->direct_level_fluxes_dev != NULL ? "direct_level_fluxes_dev" : "zenith_direct_level_fluxes_dev");
+        }
+    }
+    if (surface != NULL)
+    {
+        GRT_TRY(grt_check_zenith_surface(surface, cols->ncol, Z));
+    }
+    join.zeniths = zn;
+    join.zenith_surface = surface;
+    GrtBand *sw = &p->band[1];
+    if (direct != NULL && sw->gas != NULL)
+    {
+        /* the passes' direct rows: the caller's three per set (and angle), or -- profile form -- V levels, the caller's or
+           the pipeline's own, and the three rows from them afterwards */
+        join.zenith_direct = 1;
+        join.zenith_direct_out = profile ? direct->direct_level_fluxes_dev : direct->direct_fluxes_dev;
+        join.zenith_direct_per_angle = profile ? direct->zenith_direct_level_fluxes_dev : direct->zenith_direct_fluxes_dev;
+        if (profile && join.zenith_direct_out == NULL && direct->direct_fluxes_dev != NULL)
+        {
+            GRT_TRY(check_lane(p));
+            GrtScratch *own = &sw->scratch[GRT_SCRATCH_DIRECT_LEVELS];
+            GRT_TRY(grt_scratch_need(p, own, (size_t)p->max_cols*GRT_SKY_MAX_SETS*(size_t)V, NULL));
+            join.zenith_direct_out = own->d;
+        }
+        if (profile && join.zenith_direct_per_angle == NULL && direct->zenith_direct_fluxes_dev != NULL)
+        {
+            GRT_TRY(check_lane(p));
+            GrtScratch *own = &sw->scratch[GRT_SCRATCH_ZEN_DIRECT_LEVELS];
+            GRT_TRY(grt_scratch_need(p, own, (size_t)p->max_cols*GRT_SKY_MAX_SETS*(size_t)Z*(size_t)V, NULL));
+            join.zenith_direct_per_angle = own->d;
+        }
+    }
+    GRT_TRY(run_under_zeniths(p, cols, &join, nsets, level_fluxes_dev, heating_dev, fluxes_dev));
+    if (direct == NULL)
+    {
+        return GRTCODE_SUCCESS;
+    }
+    void *s = grt_dev_stream(p->device);
+    size_t const slots = (size_t)cols->ncol*(size_t)nsets;
+    if (sw->gas == NULL)
+    {
+        /* no shortwave band: zeros, as the band's rows are */
+        fp_t *const out[4] = {direct->direct_fluxes_dev, direct->zenith_direct_fluxes_dev, direct->direct_level_fluxes_dev,
+                              direct->zenith_direct_level_fluxes_dev};
+        for (int k = 0; k < 4; ++k)
+        {
+            if (out[k] != NULL)
+            {
+                GRT_TRY(grt_dev_zero(p->device, out[k], sizeof(double)*slots*(size_t)(k & 1 ? Z : 1)*
+                                                        (size_t)(k < 2 ? GRT_DIRECT_ROWS_PER_SET : V), s));
+            }
+        }
+    }
+    else if (profile)
+    {
+        if (direct->direct_fluxes_dev != NULL)
+        {
+            GRT_TRY(grt_dev_check(grt_launch_direct_rows(s, (int)slots, V, p->user_level, join.zenith_direct_out,
+                                                         direct->direct_fluxes_dev), "row pick kernel"));
+        }
+        if (direct->zenith_direct_fluxes_dev != NULL)
+        {
+            GRT_TRY(grt_dev_check(grt_launch_direct_rows(s, (int)(slots*(size_t)Z), V, p->user_level,
+                                                         join.zenith_direct_per_angle, direct->zenith_direct_fluxes_dev),
+                                  "row pick kernel"));
+        }
+    }
     return GRTCODE_SUCCESS;
 }
 

@@ -50,6 +50,7 @@ void grt_staging_free(GrtPipeline_t *p, GrtStaging *st)
 int grt_stage_zeniths(GrtPipeline_t *p, GrtZeniths_t const *zn, int C, GrtZenithRun *zr)
 {
     size_t const Z = (size_t)zn->num_zeniths, n = (size_t)C*Z;
+    memset(zr, 0, sizeof(*zr));
     GRT_TRY(grt_staging_reserve(p, &p->zen, 3*n, 3*(size_t)p->max_cols*GRT_MAX_ZENITHS));
     double *h = p->zen.h;
     memcpy(h, zn->cos_zenith, sizeof(double)*n);
@@ -708,6 +709,59 @@ int grt_stage_tiles(GrtPipeline_t *p, GrtSurfaceTiles_t const *tl, int C, int co
     tr->np[1] = np[1];
     tr->dif = values[2] != NULL;
     tr->per_tile = tl->tile_fluxes_dev;
+    return GRTCODE_SUCCESS;
+}
+
+/* ---- a direct-beam albedo per sun angle (grt_pipeline_run_sky_zeniths_direct) ---- */
+
+/* grt_ext.h: grt_surface_tables over the ncol x zeniths knot rows, and the same pairs angle-major where asked for */
+EXTERN void grt_zenith_surface_tables(fp_t const *x, int ns, int ncol, int zeniths, fp_t const *values, fp_t *tables,
+                                      fp_t *by_angle)
+{
+    size_t const Z = (size_t)zeniths, C = (size_t)ncol, per = 2*((size_t)ns + 1);
+    grt_surface_tables(x, ns, ncol*zeniths, values, tables);
+    for (size_t r = 0; by_angle != NULL && r < C*Z; ++r)
+    {
+        memcpy(by_angle + ((r % Z)*C + r/Z)*per, tables + r*per, sizeof(double)*per);
+    }
+}
+
+/* What grt_pipeline_run_sky_zeniths_direct refuses in its surface for a batch of C columns under Z angles (nothing is
+   touched): fewer than two knots, a NULL grid or albedo array, a grid that is not strictly increasing, a knot of any
+   (column, angle) -- a night angle's too -- outside [0, 1] or not finite. */
+int grt_check_zenith_surface(GrtZenithSurface_t const *zs, int C, int Z)
+{
+    if (zs->albedo_num_points < 2)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d knots of the per-angle direct albedo: at least 2.", zs->albedo_num_points);
+    }
+    GRT_TRY(check_surface_band("per-angle direct albedo", zs->albedo_num_points, C*Z, zs->albedo_grid, zs->direct_albedo,
+                               NULL));
+    return GRTCODE_SUCCESS;
+}
+
+/* A checked surface to the device, as grt_stage_surface brings a column's there: the C x Z knot rows' slope and intercept
+   entries (grt_surface_tables) -- column-major for the fused form's join, angle-major for the materialised form's loop --
+   and the shortwave band's per-point entries (grt_surface_entry_map; built when the grid differs from the last call's).
+   No rows are written here, and the surface in force is not touched. */
+int grt_stage_zenith_surface(GrtPipeline_t *p, GrtZenithSurface_t const *zs, int C, GrtZenithRun *zr)
+{
+    GrtBand *b = &p->band[1];
+    int const ns = zs->albedo_num_points;
+    size_t const per = 2*((size_t)ns + 1), rows = (size_t)C*(size_t)zr->zeniths;
+    /* (both layouts are staged; the form in use is uploaded) */
+    GRT_TRY(grt_staging_reserve(p, &p->zen_surf, 2*rows*per, 2*(size_t)p->max_cols*GRT_MAX_ZENITHS*per));
+    grt_zenith_surface_tables(zs->albedo_grid, ns, C, zr->zeniths, zs->direct_albedo, p->zen_surf.h, p->zen_surf.h + rows*per);
+    if (p->keep_spectra)
+    {
+        memcpy(p->zen_surf.h, p->zen_surf.h + rows*per, sizeof(double)*rows*per);
+    }
+    GRT_TRY(grt_staging_upload(p, &p->zen_surf, rows*per));
+    GridMapFill f = {&b->gas->grid, zs->albedo_grid, ns, 1};
+    GRT_TRY(grt_keyed_table(p, &b->zen_surf_map, f.x, sizeof(double)*(size_t)ns, b->n, fill_grid_map, &f));
+    zr->surface.num_entries = ns + 1;
+    zr->surface.entry = b->zen_surf_map.table;
+    zr->surface.tables = p->zen_surf.d;
     return GRTCODE_SUCCESS;
 }
 

@@ -122,6 +122,16 @@ enum
     GRT_SCRATCH_SCATTER_PARTIALS,
     /* ... profile form without scatter_levels_dev: [max_cols][GRT_SKY_MAX_SETS][2][V] the levels its six rows come from */
     GRT_SCRATCH_SCATTER_LEVELS,
+    /* grt_pipeline_run_sky_zeniths_direct, shortwave, fused form: [max_cols][Z][S][3 or V][nblocks] partial sums of the
+       direct beam of every angle and cloud draw, its sets in turn in stream order (materialised form: [max_cols][Z][S][3 or
+       V] integrated rows); replaced when a call needs more */
+    GRT_SCRATCH_ZEN_DIRECT_PARTIALS,
+    /* ... profile form without zenith_direct_level_fluxes_dev: [max_cols][GRT_SKY_MAX_SETS][Z][V] the levels every angle's
+       three rows come from (the mean's: GRT_SCRATCH_DIRECT_LEVELS) */
+    GRT_SCRATCH_ZEN_DIRECT_LEVELS,
+    /* ... materialised form with a GrtZenithSurface_t: [max_cols][n] the direct-albedo rows of the angle being solved (the
+       rows of the surface in force, GRT_SCRATCH_SURF_ROWS, are not written) */
+    GRT_SCRATCH_ZEN_SURF_ROWS,
     GRT_SCRATCH_COUNT
 };
 
@@ -169,7 +179,10 @@ typedef struct GrtBand
     /* grt_pipeline_run_sky_weighted: the band's response table (GrtResponseArgs: the weights, then the responses' and the
        blocks' ints); its key: the grid's points and the responses' first, offset, weights */
     GrtKeyedTable response_table;
-    int surf_set, surf_dif_set;    /* the surface in force gives this band rows (, and diffuse rows of their own) */
+    /* grt_pipeline_run_sky_zeniths_direct (shortwave band): [n] entry of the call's albedo grid each grid point takes, as
+       surf_map; its key: that grid */
+    GrtKeyedTable zen_surf_map;
+    int surf_set, surf_dif_set;   /* the surface in force gives this band rows (, and diffuse rows of their own) */
 } GrtBand;
 
 struct GrtPipeline
@@ -199,7 +212,10 @@ struct GrtPipeline
        fractions [cols][T], then the slope and intercept entries of the tiles' emissivity [cols T][NS + 1][2], direct albedo
        and diffuse albedo */
     GrtStaging tile;
-    int surface_ncol;      /* columns of the surface in force; 0: none (the creation-time arrays apply) */
+    /* grt_pipeline_run_sky_zeniths_direct's slope and intercept entries of the direct albedo: [cols][Z][NS + 1][2], or --
+       materialised form -- angle-major [Z][cols][NS + 1][2] */
+    GrtStaging zen_surf;
+    int surface_ncol;     /* columns of the surface in force; 0: none (the creation-time arrays apply) */
 };
 
 /* The bins of a run, per band.  Of a six-row run (grt_pipeline_run_spectral): with the six rows at every point, to
@@ -328,6 +344,14 @@ typedef struct GrtZenithRun
     double *per_angle;             /* DEVICE [ncol][Z][6 or 2 V], or NULL */
     double *six;                   /* profile form: DEVICE [ncol][Z][6], every angle's six rows from its levels, or NULL */
     int sky;                       /* grt_pipeline_run_sky_zeniths: both carry the pass's sets, [ncol][sets][Z][...] */
+    /* grt_pipeline_run_sky_zeniths_direct (all zero: not asked for).  The (column, angle) direct albedo, staged
+       (grt_stage_zenith_surface): surface.tables [ncol][Z][E][2] -- materialised form: [Z][ncol][E][2], angle k's columns
+       at k ncol E 2 --, surface.entry the band's map; surface.tables NULL: the surface in force under every angle */
+    GrtZenithSurfaceArgs surface;
+    /* ... the direct beam leaves too (direct != 0): every angle's rows to direct_per_angle, DEVICE [ncol][sets][Z][3 or V],
+       and their mean to direct_out, DEVICE [ncol][sets][3 or V] (either may be NULL, not both) */
+    int direct;
+    double *direct_per_angle, *direct_out;
 } GrtZenithRun;
 
 /* the doubles from one set of a column to the next */
@@ -364,6 +388,10 @@ GRT_PRIVATE int grt_stage_surface(GrtPipeline_t *p, GrtSurface_t const *sf, int 
 GRT_PRIVATE int grt_check_tiles(GrtPipeline_t const *p, GrtSurfaceTiles_t const *tl, int C, int np[2]);
 GRT_PRIVATE int grt_stage_tiles(GrtPipeline_t *p, GrtSurfaceTiles_t const *tl, int C, int const np[2], GrtTileRun *tr);
 GRT_PRIVATE int grt_stage_zeniths(GrtPipeline_t *p, GrtZeniths_t const *zn, int C, GrtZenithRun *zr);
+/* what grt_pipeline_run_sky_zeniths_direct refuses in its surface for C columns under Z angles (nothing is touched); the
+   checked surface's pairs to the device and the shortwave band's entry map brought up to date, as zr->surface */
+GRT_PRIVATE int grt_check_zenith_surface(GrtZenithSurface_t const *zs, int C, int Z);
+GRT_PRIVATE int grt_stage_zenith_surface(GrtPipeline_t *p, GrtZenithSurface_t const *zs, int C, GrtZenithRun *zr);
 GRT_PRIVATE int grt_check_radiances(GrtRadiances_t const *rd, int C);
 GRT_PRIVATE int grt_stage_radiances(GrtPipeline_t *p, GrtRadiances_t const *rd, int C, GrtRadianceRun *rr);
 GRT_PRIVATE int grt_check_channels(GrtChannels_t const *ch, long long n, long long *pairs);

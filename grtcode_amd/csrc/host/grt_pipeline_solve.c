@@ -38,7 +38,7 @@ typedef struct ThirdRows
 static GrtSolverInstance pass_instance(GrtPipeline_t const *p, GrtPass const *ps, GrtBandArgs const *bn,
                                        GrtSubcolumnArgs const *sc, ThirdRows const *tr, int bi)
 {
-    GrtSolverInstance in = {GRT_OUT_CHAINS, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
+    GrtSolverInstance in = {GRT_OUT_CHAINS, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
     if (!p->keep_spectra)
     {
         in.out = pass_spectral(ps) ? GRT_OUT_ROWS_POINTS : (bn != NULL ? GRT_OUT_LEVEL_BINS :
@@ -623,9 +623,10 @@ static int direct_beam(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass cons
     return GRTCODE_SUCCESS;
 }
 
-/* ... and the row-wise trapezoid of it into the pass's third rows: TOA, surface and the user level (the zero row without
-   one), or -- profile -- every level */
-static int direct_integrate(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps)
+/* ... and the row-wise trapezoid of it into three rows -- TOA, surface and the user level (the zero row without one) -- or,
+   profile, every level: column c's at out[c out_stride + out_offset ..] */
+static int direct_integrate_to(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps, double *out, int out_stride,
+                               int out_offset)
 {
     size_t const V = (size_t)p->num_levels, cols = (size_t)p->max_cols, rows = (size_t)direct_rows(p, ps);
     double *beam = b->scratch[GRT_SCRATCH_DIRECT_BEAM].d;
@@ -655,8 +656,15 @@ static int direct_integrate(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass
         GRT_TRY(grt_upload_rows(p, rows_h, cols*rows, table));
     }
     GRT_TRY(grt_dev_check(grt_launch_integrate_rows(grt_dev_stream(p->device), (double const *const *)*table, C*(int)rows,
-                                                    b->n, b->gas->grid.dw, third_out(ps, bi), (int)rows, direct_stride(p, ps),
-                                                    direct_offset(p, ps)), "spectral integration kernel"));
+                                                    b->n, b->gas->grid.dw, out, (int)rows, out_stride, out_offset),
+                          "spectral integration kernel"));
+    return GRTCODE_SUCCESS;
+}
+
+/* ... into the pass's own third rows */
+static int direct_integrate(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps)
+{
+    GRT_TRY(direct_integrate_to(p, b, bi, C, ps, third_out(ps, bi), direct_stride(p, ps), direct_offset(p, ps)));
     return GRTCODE_SUCCESS;
 }
 
@@ -1090,7 +1098,12 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
    stream order.  The clean pass counts under GRT_TAG_ZENITH_SW, the others under GRT_TAG_SKY_ZENITH_SW.  Then the
    fixed-order mean (GRT_TAG_ZENITH_MEAN; zr->sky: GRT_TAG_SKY_ZENITH_MEAN).  Materialised form: per draw the pass's
    optics, per angle the spectral solver and the row-wise trapezoid into the (angle, draw) rows of zen_partials; then the
-   same mean kernel (one block per row). */
+   same mean kernel (one block per row).
+   grt_pipeline_run_sky_zeniths_direct (zr->surface, zr->direct): with a staged surface the fused instances take the
+   GrtZenithSurfaceArgs join, and the materialised loop writes each angle's direct-albedo rows into a buffer of its own
+   ahead of the angle's solve; with the direct beam the fused instances take the GrtDirectArgs join too (partial sums in
+   GRT_SCRATCH_ZEN_DIRECT_PARTIALS at the same slots), the materialised loop runs the direct-beam kernel and its trapezoid
+   per (angle, draw), and the same mean kernel folds the three rows or V into zr->direct_per_angle and zr->direct_out. */
 int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass const *ps, GrtZenithRun const *zr)
 {
     int const Z = zr->zeniths, rows = pass_rows(p, ps), out_offset = pass_offset(p, ps, 1);
@@ -1098,12 +1111,21 @@ int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass c
     int const sw_tag = ps->clouds != NULL || ps->aer_pass ? GRT_TAG_SKY_ZENITH_SW : GRT_TAG_ZENITH_SW;
     void *s = grt_dev_stream(p->device);
     GrtScratch *block = &b->scratch[GRT_SCRATCH_ZEN_PARTIALS];
+    /* grt_pipeline_run_sky_zeniths_direct: every angle's direct beam beside its rows, three rows or V at the same slots */
+    GrtScratch *dblock = &b->scratch[GRT_SCRATCH_ZEN_DIRECT_PARTIALS];
+    int const drows = direct_rows(p, ps);
+    GrtZenithSurfaceArgs const *zs = zr->surface.tables != NULL ? &zr->surface : NULL;
     unsigned nblocks = 1;
     S = ps->clouds != NULL ? S : 1;
     if (!p->keep_spectra)
     {
         nblocks = b->nblocks;
         GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*(size_t)Z*(size_t)S*(size_t)rows*nblocks, NULL));
+        if (zr->direct)
+        {
+            GRT_TRY(grt_scratch_need(p, dblock, (size_t)p->max_cols*(size_t)Z*(size_t)S*(size_t)drows*nblocks, NULL));
+        }
+        GrtDirectArgs const da = {dblock->d};
         /* (in points at za and sc: the loops below walk their first and count, which the launchers alone read) */
         GrtZenithArgs za = {zr->mu, Z, 0, 0};
         GrtSubcolumnArgs sc;
@@ -1116,13 +1138,15 @@ int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass c
         GrtSubcolumnArgs *draws = ps->clouds != NULL ? &sc : NULL;
         GrtSolverInstance in = pass_instance(p, ps, NULL, draws, NULL, 1);
         in.zeniths = &za;
+        in.direct = zr->direct ? &da : NULL;
+        in.zenith_surface = zs;
         SolverArgs a;
         GRT_TRY(solver_args(p, b, 1, C, ps, &in, block->d, &a));
         char const *env = getenv("GRT_ZENITH_SHARED");
         int const parks = grt_sw_parks(&in, &a.sw);
         /* (grid rows; a park block of max_cols columns) */
         int const limit = parks ? p->max_cols/C : 65535/C;
-        int const chunks = (Z + grt_zenith_chunk(draws, ps->aer) - 1)/grt_zenith_chunk(draws, ps->aer);
+        int const chunk = grt_zenith_chunk(draws, ps->aer, in.direct, zs), chunks = (Z + chunk - 1)/chunk;
         int const shared = !ps->profile && !parks && chunks <= limit &&
                            (joined ? env != NULL && env[0] == '1' : !(env != NULL && env[0] == '0'));
         int const slot = grt_profile_begin(s, sw_tag);
@@ -1134,7 +1158,7 @@ int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass c
             for (sc.first = 0; sc.first < S && krc == 0; sc.first += group)
             {
                 sc.count = S - sc.first < group ? S - sc.first : group;
-                krc = grt_launch_sw_zeniths(s, &a.sw, &za, draws, ps->aer);
+                krc = grt_launch_sw_zeniths(s, &a.sw, &za, draws, ps->aer, in.direct, zs);
             }
         }
         else
@@ -1162,6 +1186,30 @@ int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass c
             GRT_TRY(level_rows(p, b));
         }
         size_t const tab = ps->clouds != NULL ? (size_t)C*3*(size_t)ps->clouds->num_bands*(size_t)(p->num_levels - 1) : 0;
+        if (zr->direct)
+        {
+            GRT_TRY(grt_scratch_need(p, dblock, (size_t)p->max_cols*(size_t)Z*(size_t)S*(size_t)drows, NULL));
+            GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_DIRECT_BEAM], (size_t)p->max_cols*(size_t)p->num_levels*b->n,
+                                     NULL));
+        }
+        /* every angle's own direct albedo: the angle's rows [C][n] in a buffer of the call's own -- the rows of the surface
+           in force are not written -- and, where the diffuse albedo is the creation-time array, a copy of it per column
+           behind them: the solver reads both albedos at one stride */
+        double *angle_rows = NULL, *dif_rows = NULL;
+        if (zs != NULL)
+        {
+            GrtScratch *own = &b->scratch[GRT_SCRATCH_ZEN_SURF_ROWS];
+            GRT_TRY(grt_scratch_need(p, own, 2*(size_t)p->max_cols*b->n, NULL));
+            angle_rows = own->d;
+            if (!b->surf_set)
+            {
+                dif_rows = own->d + (size_t)p->max_cols*b->n;
+                for (int c = 0; c < C; ++c)
+                {
+                    GRT_TRY(grt_dev_copy(p->device, dif_rows + (size_t)c*b->n, p->albedo_d, sizeof(double)*b->n, s));
+                }
+            }
+        }
         for (int j = 0; j < S; ++j)
         {
             GrtCloudArgs cj;
@@ -1180,6 +1228,18 @@ int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass c
             for (int k = 0; k < Z; ++k)
             {
                 a.sw.mu_dir = zr->mu_by_angle + (size_t)k*C;
+                if (zs != NULL)
+                {
+                    GrtSurfaceArgs const sa = {zs->num_entries, zs->entry,
+                                               zs->tables + (size_t)k*(size_t)C*(size_t)zs->num_entries*2};
+                    int const rslot = grt_profile_begin(s, GRT_TAG_SURFACE);
+                    int const rrc = grt_launch_spread_surface(s, C, b->gas->grid.w0, b->gas->grid.dw, b->n, &sa, angle_rows);
+                    grt_profile_end(s, rslot);
+                    GRT_TRY(grt_dev_check(rrc, "surface row kernel"));
+                    a.sw.alb_dir = angle_rows;
+                    a.sw.alb_dif = dif_rows != NULL ? dif_rows : a.sw.alb_dif;
+                    a.sw.alb_stride = b->n;
+                }
                 int const slot = grt_profile_begin(s, sw_tag);
                 int const krc = grt_launch_sw(s, &in, &a.sw);
                 grt_profile_end(s, slot);
@@ -1188,6 +1248,15 @@ int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass c
                                                                 C*rows, b->n, b->gas->grid.dw, block->d, rows, Z*S*rows,
                                                                 (k*S + j)*rows),
                                       "spectral integration kernel"));
+                if (zr->direct)
+                {
+                    /* the angle's direct beam on the grid from the draw's optics, and its row-wise trapezoid */
+                    int const dslot = grt_profile_begin(s, GRT_TAG_DIRECT_BEAM);
+                    int const drc = grt_launch_sw_direct_beam(s, &a.sw, b->scratch[GRT_SCRATCH_DIRECT_BEAM].d);
+                    grt_profile_end(s, dslot);
+                    GRT_TRY(grt_dev_check(drc, "direct-beam kernel"));
+                    GRT_TRY(direct_integrate_to(p, b, 1, C, ps, dblock->d, Z*S*drows, (k*S + j)*drows));
+                }
             }
         }
     }
@@ -1199,6 +1268,16 @@ int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass c
                                ps->out, ps->out_stride, out_offset);
     grt_profile_end(s, mslot);
     GRT_TRY(grt_dev_check(mrc, "zenith mean kernel"));
+    if (zr->direct)
+    {
+        /* (the same kernel on the direct beam's three rows or V: the draws, one division, then the angles) */
+        int const dslot = grt_profile_begin(s, GRT_TAG_SKY_ZENITH_MEAN);
+        int const drc = grt_launch_sky_zenith_mean(s, dblock->d, C, Z, S, drows, nblocks, zr->mu, zr->weight,
+                                                   zr->direct_per_angle, NULL, ps->sets, ps->set, p->user_level,
+                                                   zr->direct_out, direct_stride(p, ps), direct_offset(p, ps));
+        grt_profile_end(s, dslot);
+        GRT_TRY(grt_dev_check(drc, "zenith mean kernel"));
+    }
     return GRTCODE_SUCCESS;
 }
 

@@ -44,6 +44,11 @@ enum grt_struct_kind
     GRT_SPECTRAL_GRID = 0, GRT_OPTICS, GRT_GAS_OPTICS, GRT_SOLAR_FLUX, GRT_LONGWAVE, GRT_SHORTWAVE, GRT_CLOUDS,
     GRT_CLOUD_PHASE, GRT_CLOUD_MODEL, GRT_CLOUD_FIELDS, GRT_LW_SCATTER
 };
+/* ... and the kinds that came after it, in the same numbering: GrtZenithSurface_t, GrtZenithDirect_t */
+enum grt_struct_kind_more
+{
+    GRT_ZENITH_SURFACE = GRT_LW_SCATTER + 1, GRT_ZENITH_DIRECT
+};
 EXTERN size_t grt_sizeof(int kind);
 
 /* ---- line lists from memory ------------------------------------------------------
@@ -1036,13 +1041,65 @@ EXTERN int grt_pipeline_run_zeniths(GrtPipeline_t *pipeline, GrtColumns_t const 
  * mean kernel under GRT_TAG_SKY_ZENITH_MEAN; per band [max_columns][Z][S][6 or 2 V][blocks] partial sums are allocated at
  * the first call that needs more.  keep_spectra = 1: the literal loop -- per draw the set's optics, per angle the spectral
  * solver and the row-wise trapezoid (night samples as in grt_pipeline_run_zeniths), then the same mean kernel.
- * Not covered: cloud fields sampled on the device, the direct beam under several angles, spectral and per-bin outputs.
+ * Not covered: cloud fields sampled on the device, spectral and per-bin outputs (the direct beam under several angles:
+ * grt_pipeline_run_sky_zeniths_direct below).
  * GRTCODE_VALUE_ERR, with nothing launched and every output untouched, for everything grt_pipeline_run_sky refuses in
  * `sky`, everything grt_pipeline_run_zeniths refuses in `zeniths`, and fluxes_dev, level_fluxes_dev and both per-angle
  * outputs all NULL.  Asynchronous on the pipeline's lane. */
 EXTERN int grt_pipeline_run_sky_zeniths(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtSky_t const *sky,
                                         GrtZeniths_t const *zeniths, fp_t *level_fluxes_dev, fp_t *heating_dev,
                                         fp_t *fluxes_dev);
+
+/* ---- ... with a direct-beam albedo per sun angle, and every angle's direct beam --------------------------------------
+ * grt_pipeline_run_sky_zeniths in every respect -- sets and packing, both output forms, sweep rule, the per-angle outputs
+ * of GrtZeniths_t, night samples, the fold over the angles, the longwave -- with two additions, either or both:
+ *   surface != NULL: the direct-beam albedo of column c under angle k is that (column, angle)'s knots, put on the band's
+ *     grid by grt_pipeline_set_surface's rule (the two constant ranges, the last segment's value above the grid, m w + b as
+ *     multiply, then add): the double that entry point would leave in a column's row for those knots.  Open water, snow
+ *     and most land reflect more of a low sun.  The diffuse albedo, the emissivity and the longwave stay those of the
+ *     surface in force (grt_pipeline_set_surface, or the creation-time arrays), which this call does not touch.  A night
+ *     angle's knots are checked but not read.
+ *   direct != NULL: grt_pipeline_run_sky_direct's direct beam -- delta-scaled, the running product of T_pure, scaled and
+ *     integrated as the other rows are -- per angle and folded over the angles in the order and arithmetic of the other
+ *     rows (a cloud set's draws first, one division by S, then the angles: with weights the sum of w_k F_k, each product
+ *     rounded; without, the sum and one division by Z).  A night angle's direct rows are +0.0.  The level outputs belong
+ *     to the profile form; there the three rows are levels 0, V - 1 and the user level of the V.
+ * In the deterministic mode every angle's rows of every set, the direct ones included, are, bit for bit,
+ * grt_pipeline_run_sky_direct's under that cos_zenith with that angle's knots as the direct albedo of the surface in
+ * force; with surface == NULL every output grt_pipeline_run_sky_zeniths also writes has its bits.  A pipeline without a
+ * shortwave band runs the longwave and writes +0.0 to every shortwave and direct output.
+ * The production form (keep_spectra = 0) evaluates the albedo per thread from the staged (column, angle) pairs -- no
+ * [ncol][Z][points] rows exist -- in zenith instances of the shortwave solver and of the shared-layer kernel of their
+ * own (k_shortwave.hip; routing and GRT_ZENITH_SHARED as in grt_pipeline_run_sky_zeniths), and allocates per band
+ * [max_columns][Z][S][3 or V][blocks] partial sums of the direct beam at the first call that needs more.  keep_spectra =
+ * 1: the literal loop -- per angle the angle's rows are written into a buffer of the call's own [max_columns][points],
+ * then the spectral solver, the direct-beam kernel and the row-wise trapezoids run.
+ * GRTCODE_VALUE_ERR, with nothing launched and every output and the surface in force untouched, for everything
+ * grt_pipeline_run_sky_zeniths refuses; surface and direct both NULL; all four outputs of `direct` NULL; a level output
+ * of `direct` in the six-row form; albedo_num_points < 2; a NULL albedo_grid or direct_albedo; a grid that is not
+ * strictly increasing; a knot outside [0, 1] or not finite.  Asynchronous on the pipeline's lane. */
+typedef struct GrtZenithSurface
+{
+    int albedo_num_points;              /* NS >= 2 */
+    fp_t const *albedo_grid;            /* HOST [NS] cm-1, strictly increasing, shared by columns and angles */
+    fp_t const *direct_albedo;          /* HOST [ncol][Z][NS], each in [0, 1] */
+} GrtZenithSurface_t;
+typedef struct GrtZenithDirect
+{
+    fp_t *direct_fluxes_dev;                /* DEVICE [ncol][N][GRT_DIRECT_ROWS_PER_SET]: mean over the angles; TOA, surface, user level */
+    fp_t *direct_level_fluxes_dev;          /* DEVICE [ncol][N][V]: mean, every level; profile form only */
+    fp_t *zenith_direct_fluxes_dev;         /* DEVICE [ncol][N][Z][GRT_DIRECT_ROWS_PER_SET] */
+    fp_t *zenith_direct_level_fluxes_dev;   /* DEVICE [ncol][N][Z][V]; profile form only */
+} GrtZenithDirect_t;                        /* any may be NULL, not all four */
+EXTERN int grt_pipeline_run_sky_zeniths_direct(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtSky_t const *sky,
+                                               GrtZeniths_t const *zeniths, GrtZenithSurface_t const *surface,
+                                               GrtZenithDirect_t const *direct, fp_t *level_fluxes_dev, fp_t *heating_dev,
+                                               fp_t *fluxes_dev);
+/* the host staging of `surface` (pure host code): values [ncol][zeniths][ns] on the grid x [ns] -> grt_pipeline_set_surface's
+   slope and intercept entries of every (column, angle) knot row, tables [ncol][zeniths][ns + 1][2], and -- by_angle != NULL --
+   the same pairs angle-major, [zeniths][ncol][ns + 1][2] (the materialised form's) */
+EXTERN void grt_zenith_surface_tables(fp_t const *x, int ns, int ncol, int zeniths, fp_t const *values, fp_t *tables,
+                                      fp_t *by_angle);
 
 /* ---- several surface tiles per column on one gas-optics pass -----------------------------------------------------------
  * grt_pipeline_run_sky (its six-row form) with T surfaces per column: land, open water, sea ice, snow -- each tile with its
