@@ -27,6 +27,7 @@ GRT_CLOUDS = 6                      # grt_sizeof kind of GrtClouds
 GRT_CLOUD_PHASE, GRT_CLOUD_MODEL, GRT_CLOUD_FIELDS = 7, 8, 9   # ... of GrtCloudPhase, GrtCloudModel, GrtCloudFields
 GRT_LW_SCATTER = 10                 # ... of GrtLwScatter
 GRT_ZENITH_SURFACE, GRT_ZENITH_DIRECT = 11, 12     # ... of GrtZenithSurface, GrtZenithDirect
+GRT_ZENITH_SLANT = 13                               # ... of GrtZenithSlant
 # grt_profile_read's tags (grt_ext.h: GRT_TAG_..., where each one's bracket is described)
 (TAG_GAS_LW, TAG_GAS_SW, TAG_SOLVER_LW, TAG_SOLVER_SW, TAG_CLEAR_OPTICS, TAG_FAR_LW, TAG_FAR_SW, TAG_ALLSKY_LW,
  TAG_ALLSKY_SW, TAG_BINS, TAG_SUBCOLUMN_MEAN, TAG_AEROSOL_LW, TAG_AEROSOL_SW, TAG_BAND_PROFILES, TAG_SURFACE,
@@ -41,6 +42,7 @@ GRT_MAX_ZENITHS = 64                # grt_pipeline_run_zeniths: sun angles per c
 GRT_MAX_TILES = 16                  # grt_pipeline_run_sky_tiles: surface tiles per column, 1 .. this
 GRT_TILE_CHUNK = 4                  # csrc/grt_kernels.h: the tiles one thread of the tile kernels carries (every instance's)
 GRT_ZENITH_CHUNK = 4                # csrc/grt_kernels.h: the angles one thread of the shared-layer shortwave kernel carries
+GRT_ZENITH_CHUNK_SLANT = GRT_ZENITH_CHUNK_SLANT_SURFACE = 4    # ... of its instances with a sun cosine per layer (run_sky_zeniths_slant)
 # grt_pipeline_run_sky's sets: clean (always formed), + aerosol, + clouds, + aerosol and clouds; packed in bit order
 GRT_SKY_CLEAN, GRT_SKY_AEROSOL, GRT_SKY_CLOUD, GRT_SKY_CLOUD_AEROSOL = 1, 2, 4, 8
 GRT_SKY_ALL = GRT_SKY_CLEAN | GRT_SKY_AEROSOL | GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL
@@ -273,6 +275,10 @@ class GrtZenithDirect(C.Structure):
                 ("zenith_direct_fluxes_dev", C.c_void_p), ("zenith_direct_level_fluxes_dev", C.c_void_p)]
 
 
+class GrtZenithSlant(C.Structure):
+    _fields_ = [("layer_cos_zenith", c_double_p)]
+
+
 class GrtSurfaceTiles(C.Structure):
     _fields_ = [("num_tiles", C.c_int), ("fraction", c_double_p), ("surface_temperature", c_double_p),
                 ("num_emissivity_points", C.c_int), ("num_albedo_points", C.c_int),
@@ -301,7 +307,7 @@ create_shortwave destroy_shortwave calculate_sw_fluxes rayleigh_scattering
 create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
-grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_channels grt_channel_pair_count grt_pipeline_run_sky_weighting grt_pipeline_run_sky_weighted grt_response_pair_count grt_pipeline_response_block_limit grt_pipeline_run_sky_zeniths grt_pipeline_run_sky_zeniths_direct grt_zenith_surface_tables grt_pipeline_run_sky_tiles grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_kdist_rows grt_pipeline_run_kdist grt_kdist_chunk_points grt_kdist_class_map grt_kdist_mapped_rows grt_pipeline_run_kdist_correlated grt_pipeline_run_ck_fluxes grt_pipeline_run_sky_scattering grt_lw_scatter_levels grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
+grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_channels grt_channel_pair_count grt_pipeline_run_sky_weighting grt_pipeline_run_sky_weighted grt_response_pair_count grt_pipeline_response_block_limit grt_pipeline_run_sky_zeniths grt_pipeline_run_sky_zeniths_direct grt_zenith_surface_tables grt_pipeline_run_sky_zeniths_slant grt_slant_cosines grt_pipeline_run_sky_tiles grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_kdist_rows grt_pipeline_run_kdist grt_kdist_chunk_points grt_kdist_class_map grt_kdist_mapped_rows grt_pipeline_run_kdist_correlated grt_pipeline_run_ck_fluxes grt_pipeline_run_sky_scattering grt_lw_scatter_levels grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
 grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_voigt_points grt_debug_device_math grt_debug_line_strengths grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
@@ -412,6 +418,12 @@ def load_library(path=None):
                                                             C.POINTER(GrtZenithDirect), C.c_void_p, C.c_void_p, C.c_void_p]
         lib.grt_zenith_surface_tables.argtypes = [c_double_p, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p]
         lib.grt_zenith_surface_tables.restype = None
+    if hasattr(lib, "grt_pipeline_run_sky_zeniths_slant"):
+        lib.grt_pipeline_run_sky_zeniths_slant.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky),
+                                                           C.POINTER(GrtZeniths), C.POINTER(GrtZenithSlant),
+                                                           C.POINTER(GrtZenithSurface), C.POINTER(GrtZenithDirect),
+                                                           C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.grt_slant_cosines.argtypes = [C.c_double, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p]
     if hasattr(lib, "grt_pipeline_run_sky_tiles"):
         lib.grt_pipeline_run_sky_tiles.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky),
                                                    C.POINTER(GrtSurfaceTiles), C.c_void_p]
@@ -951,6 +963,19 @@ def make_zenith_surface(grid, direct_albedo):
         raise ValueError(f"direct_albedo of shape {keep['direct_albedo'].shape}: [ncol][Z][{keep['albedo_grid'].size}]")
     keep["shape"] = keep["direct_albedo"].shape[:2]
     gs = GrtZenithSurface(keep["albedo_grid"].size, _dp(keep["albedo_grid"]), _dp(keep["direct_albedo"]))
+    gs.keep = keep             # (as make_cloud_model)
+    return gs, keep
+
+
+def make_zenith_slant(layer_cos_zenith):
+    """Pack the direct beam's cosine per layer into a GrtZenithSlant struct (+ keep-alive array) for
+    Pipeline.run_sky_zeniths_slant.  layer_cos_zenith [ncol][Z][L], top layer first, each day entry in (0, 1]
+    (geometry.slant_cosines fills a spherical planet's).  keep["shape"] is (ncol, Z, L)."""
+    keep = {"layer_cos_zenith": _f64(layer_cos_zenith)}
+    if keep["layer_cos_zenith"].ndim != 3:
+        raise ValueError(f"layer_cos_zenith of shape {keep['layer_cos_zenith'].shape}: [ncol][Z][L]")
+    keep["shape"] = keep["layer_cos_zenith"].shape
+    gs = GrtZenithSlant(_dp(keep["layer_cos_zenith"]))
     gs.keep = keep             # (as make_cloud_model)
     return gs, keep
 
@@ -1845,6 +1870,24 @@ class Pipeline:
         in force) direct-beam albedo per (column, angle) and, direct=True, every angle's direct beam and its mean over the
         angles, into device buffers of this call's own: the six-row form (sky_zenith_direct_fluxes() reads it) or,
         profiles=True, the profile form (sky_zenith_direct_profiles() reads it)."""
+        gdirect, ptrs = self._zenith_direct_outputs(gsky, gzeniths, direct, profiles)
+        check(self.lib.grt_pipeline_run_sky_zeniths_direct(self.p, C.byref(gcols), C.byref(gsky), C.byref(gzeniths),
+                                                           None if gsurface is None else C.byref(gsurface),
+                                                           None if gdirect is None else C.byref(gdirect), *ptrs))
+
+    def run_sky_zeniths_slant(self, gcols, gsky, gzeniths, gslant, gsurface=None, direct=True, profiles=False):
+        """grt_pipeline_run_sky_zeniths_slant: run_sky_zeniths_direct with gslant's (make_zenith_slant; None: that call)
+        cosine per layer for the direct beam -- the pseudo-spherical approximation.  Buffers and readers are
+        run_sky_zeniths_direct's: sky_zenith_direct_fluxes(), sky_zenith_direct_profiles()."""
+        gdirect, ptrs = self._zenith_direct_outputs(gsky, gzeniths, direct, profiles)
+        check(self.lib.grt_pipeline_run_sky_zeniths_slant(self.p, C.byref(gcols), C.byref(gsky), C.byref(gzeniths),
+                                                          None if gslant is None else C.byref(gslant),
+                                                          None if gsurface is None else C.byref(gsurface),
+                                                          None if gdirect is None else C.byref(gdirect), *ptrs))
+
+    def _zenith_direct_outputs(self, gsky, gzeniths, direct, profiles):
+        """The device buffers both calls write: gzeniths' per-angle outputs set, (the GrtZenithDirect or None, the three
+        output pointers)."""
         nsets = max(sky_set_count(gsky.sets), 1)
         Z, V, n = max(gzeniths.num_zeniths, 1), self.num_levels, self.max_columns
         name = "sky_zenith_direct_profiles" if profiles else "sky_zenith_direct"
@@ -1862,9 +1905,7 @@ class Pipeline:
             ptrs = self._profile_ptrs(name, nsets)
         else:
             ptrs = [None, None, self._buffer(name, 8 * GRT_FLUXES_PER_COLUMN * nsets * n).ptr]
-        check(self.lib.grt_pipeline_run_sky_zeniths_direct(self.p, C.byref(gcols), C.byref(gsky), C.byref(gzeniths),
-                                                           None if gsurface is None else C.byref(gsurface),
-                                                           None if gdirect is None else C.byref(gdirect), *ptrs))
+        return gdirect, ptrs
 
     def sky_zenith_direct_fluxes(self, ncol, nsets, Z):
         """The last six-row run_sky_zeniths_direct of nsets sets: dict(fluxes=[ncol][nsets][12] and

@@ -408,6 +408,21 @@ static inline int grt_surface_args_ok(GrtSurfaceArgs const *c)
 {
     return c != NULL && c->num_entries >= 3 && c->entry != NULL && c->tables != NULL;
 }
+/* A sun cosine per layer for the direct beam of a zenith instance (grt_pipeline_run_sky_zeniths_slant: the pseudo-spherical
+   approximation): joined behind a GrtZenithArgs, the row of column c under angle k uses, in layer j (top layer first),
+   mu_layer[(c zeniths + k) L + j] wherever its direct-beam solution uses the row's cosine -- eddington<true>, its gamma3,
+   the optical-depth clamp, T_pure and so the running direct beam.  The diffuse solution, the sweeps, the level expressions
+   and the flux scale solar x mu[c zeniths + k] stay the row's.  A night row (mu <= 0) reads none of its entries.  The index
+   is uniform per workgroup: scalar loads.  A slant instance always carries a GrtDirectArgs.
+   mu_layer: DEVICE [ncol][zeniths][L], each day entry in (0, 1]. */
+typedef struct GrtZenithSlantArgs
+{
+    double const *mu_layer;
+} GrtZenithSlantArgs;
+static inline int grt_zenith_slant_args_ok(GrtZenithSlantArgs const *c)
+{
+    return c != NULL && c->mu_layer != NULL;
+}
 int grt_launch_spread_surface(void *stream, int ncol, double w0, double dw, uint64_t nw, GrtSurfaceArgs const *c,
                               double *rows);
 
@@ -479,7 +494,10 @@ static inline int grt_zenith_surface_args_ok(GrtZenithSurfaceArgs const *c)
    with its six), that read every angle's own direct albedo (GrtZenithSurfaceArgs), or both, behind each of the four
    joins.  Each instance carries the most angles of {2, 4} that leave it three waves per SIMD and no scratch
    (DESIGN.md 3.3); grt_zenith_chunk names an instance's -- GRT_ZENITH_CHUNK_DIRECT, _SURFACE and _DIRECT_SURFACE are the
-   chunks of the instances with d, zs and both, the same behind each of the four joins. */
+   chunks of the instances with d, zs and both, the same behind each of the four joins.  sl (or NULL;
+   grt_pipeline_run_sky_zeniths_slant; d must be set with it): the instances whose direct beam reads a cosine per layer
+   (GrtZenithSlantArgs), with zs or without, behind each of the four joins: GRT_ZENITH_CHUNK_SLANT_SURFACE and
+   GRT_ZENITH_CHUNK_SLANT. */
 #define GRT_ZENITH_CHUNK 4
 #define GRT_ZENITH_CHUNK_AEROSOLS 4
 #define GRT_ZENITH_CHUNK_SUBCOLUMNS 4
@@ -487,11 +505,14 @@ static inline int grt_zenith_surface_args_ok(GrtZenithSurfaceArgs const *c)
 #define GRT_ZENITH_CHUNK_DIRECT 4
 #define GRT_ZENITH_CHUNK_SURFACE 4
 #define GRT_ZENITH_CHUNK_DIRECT_SURFACE 4
+#define GRT_ZENITH_CHUNK_SLANT 4
+#define GRT_ZENITH_CHUNK_SLANT_SURFACE 4
 struct GrtDirectArgs;
 int grt_zenith_chunk(GrtSubcolumnArgs const *sc, GrtAerosolArgs const *ae, struct GrtDirectArgs const *d,
-                     GrtZenithSurfaceArgs const *zs);
+                     GrtZenithSurfaceArgs const *zs, GrtZenithSlantArgs const *sl);
 int grt_launch_sw_zeniths(void *stream, GrtSwArgs const *a, GrtZenithArgs const *z, GrtSubcolumnArgs const *sc,
-                          GrtAerosolArgs const *ae, struct GrtDirectArgs const *d, GrtZenithSurfaceArgs const *zs);
+                          GrtAerosolArgs const *ae, struct GrtDirectArgs const *d, GrtZenithSurfaceArgs const *zs,
+                          GrtZenithSlantArgs const *sl);
 /* The weighted mean over a column's angles of one output row, in a fixed order, and every angle's own rows: for column c
    and row r (of `rows` per slot) each angle's blocks are added as grt_launch_reduce_partials adds them -- an angle whose
    mu [ncol][zeniths] is <= 0 counts as +0.0 whatever its partial sums hold -- and stored at per_angle[(c zeniths + k) rows
@@ -841,7 +862,7 @@ typedef enum GrtSolverOutput
    stays per column whatever the subcolumn); `bins` goes with GRT_OUT_LEVEL_BINS and with nothing else; `zeniths` (the
    shortwave's GRT_OUT_ROWS and GRT_OUT_LEVELS) goes alone or with aerosols, subcolumns or both, never with `clouds`; `direct` (the shortwave's GRT_OUT_ROWS and
    GRT_OUT_LEVELS) goes with any join of clouds and aerosols or none, or behind `zeniths` and what joins them, and selects instances of its own: the instance
-   without it is the one it was; `zenith_surface` (every angle's own direct albedo) goes with `zeniths` alone, with or without `direct`, and selects instances of its own likewise; `jacobian` is the same for the longwave's GRT_OUT_ROWS and GRT_OUT_LEVELS; `responses` goes with GRT_OUT_LEVELS alone, in the shortwave always together with `direct`, never with `bins`, `zeniths` or `jacobian`, and selects instances of its own as `direct` does; `scatter` (the longwave's GRT_OUT_CHAINS, GRT_OUT_ROWS and GRT_OUT_LEVELS, with any
+   without it is the one it was; `zenith_surface` (every angle's own direct albedo) goes with `zeniths` alone, with or without `direct`, and selects instances of its own likewise; `zenith_slant` (a sun cosine per layer for the direct beam) goes with `zeniths` and `direct` together, with or without `zenith_surface`, and selects instances of its own likewise; `jacobian` is the same for the longwave's GRT_OUT_ROWS and GRT_OUT_LEVELS; `responses` goes with GRT_OUT_LEVELS alone, in the shortwave always together with `direct`, never with `bins`, `zeniths` or `jacobian`, and selects instances of its own as `direct` does; `scatter` (the longwave's GRT_OUT_CHAINS, GRT_OUT_ROWS and GRT_OUT_LEVELS, with any
    join of clouds and aerosols or none, never with the others) names the instances of lw_scatter_kernel, which
    grt_launch_lw_scatter alone launches.  The kind of instance follows from which pointers are set, and a kernel takes the structs that are
    set as arguments after its band's own.  The next joined object is a pointer here, a line in grt_solver_instance_ok
@@ -859,6 +880,7 @@ typedef struct GrtSolverInstance
     GrtResponseArgs const *responses;
     GrtScatterArgs const *scatter;  /* grt_launch_lw_scatter's instances (GRT_OUT_CHAINS, _ROWS, _LEVELS): no other launcher's */
     GrtZenithSurfaceArgs const *zenith_surface;
+    GrtZenithSlantArgs const *zenith_slant;
 } GrtSolverInstance;
 typedef enum GrtSolverJoin
 {
@@ -1181,6 +1203,10 @@ inline bool grt_solver_instance_ok(GrtSolverInstance const &in, Args const &a)
     // (every angle's own direct albedo: the zenith instances alone)
     bool const zenith_surface_ok = in.zenith_surface == nullptr || (in.zeniths != nullptr && in.jacobian == nullptr &&
                                                                     grt_zenith_surface_args_ok(in.zenith_surface));
+    // (a sun cosine per layer: the zenith instances that leave the direct beam)
+    bool const zenith_slant_ok = in.zenith_slant == nullptr || (in.zeniths != nullptr && in.direct != nullptr &&
+                                                                in.jacobian == nullptr &&
+                                                                grt_zenith_slant_args_ok(in.zenith_slant));
     // (the surface-temperature Jacobian leaves the same two forms; the shortwave launcher has no such case)
     bool const jacobian_ok = in.jacobian == nullptr || (in.zeniths == nullptr && in.direct == nullptr &&
                                                         grt_jacobian_args_ok(in.jacobian) &&
@@ -1195,7 +1221,7 @@ inline bool grt_solver_instance_ok(GrtSolverInstance const &in, Args const &a)
                                                       (in.out == GRT_OUT_CHAINS || in.out == GRT_OUT_ROWS || in.out == GRT_OUT_LEVELS));
     // (two grid points for a trapezoid; the chain form of the scattering correction integrates nothing: one will do)
     uint64_t const least_points = in.scatter != nullptr && !fused ? 1 : 2;
-    return zeniths_ok && direct_ok && zenith_surface_ok && jacobian_ok && responses_ok && scatter_ok && a.ncol >= 1 && a.nw >= least_points && a.num_levels >= 2 &&
+    return zeniths_ok && direct_ok && zenith_surface_ok && zenith_slant_ok && jacobian_ok && responses_ok && scatter_ok && a.ncol >= 1 && a.nw >= least_points && a.num_levels >= 2 &&
            cloud_forms <= 1 && joined <= (fused ? 2 : 0) && (in.bins != nullptr) == (in.out == GRT_OUT_LEVEL_BINS) &&
            (in.clouds == nullptr || grt_cloud_args_ok(in.clouds)) &&
            (in.aerosols == nullptr || grt_aerosol_args_ok(in.aerosols)) &&

@@ -24,7 +24,8 @@
 // both join, a GrtBandArgs last where OUT is per bin, or a GrtZenithArgs (several sun angles per column: alone, or last
 // behind a GrtAerosolArgs, a GrtSubcolumnArgs or both, six rows or every level); a GrtDirectArgs last (six rows or every level, with any of the cloud and aerosol joins) makes the instance that also
 // leaves the direct beam of its sweep (LevelSink: DIRECT).  Behind a GrtZenithArgs a GrtZenithSurfaceArgs (every angle's own
-// direct albedo: row_alb_dir), a GrtDirectArgs or both may follow (grt_pipeline_run_sky_zeniths_direct).
+// direct albedo: row_alb_dir), a GrtDirectArgs or both may follow (grt_pipeline_run_sky_zeniths_direct); with the GrtDirectArgs a
+// GrtZenithSlantArgs ahead of it (a sun cosine per layer for the direct beam: layer_mu; grt_pipeline_run_sky_zeniths_slant).
 // sw_tile_kernel, behind sw_zenith_kernel, is the six-row instance for several surface tiles per column
 // (grt_launch_sw_tiles): the layer properties once for a chunk of tiles, what reads the albedo per tile.
 // The in-kernel range checks of the reference are no-ops on device builds
@@ -292,6 +293,22 @@ __device__ __forceinline__ double row_mu(GrtSwArgs const &a, SolverRow const &ro
     }
 }
 
+// the cosine the direct beam has in layer j of the row whose own cosine is mu_row: that cosine, or -- a GrtZenithSlantArgs
+// is joined -- the layer's own of sun angle `sun` (c zeniths + k) of L layers.  The index is made of blockIdx, the layer
+// counter and kernel arguments alone: a scalar load, no vector register
+template <typename... Joins>
+__device__ __forceinline__ double layer_mu(double mu_row, int sun, int L, int j, Joins const &...joins)
+{
+    if constexpr (has<GrtZenithSlantArgs, Joins...>)
+    {
+        return pick<GrtZenithSlantArgs>(joins...).mu_layer[(uint64_t)sun*(uint64_t)L + (uint64_t)j];
+    }
+    else
+    {
+        return mu_row;
+    }
+}
+
 // the direct-beam albedo of column col at grid point ii: the column's row, or -- a GrtZenithSurfaceArgs is joined -- the
 // pair of sun angle `sun` (c zeniths + k) at the point's entry, evaluated as spread_surface_kernel evaluates it (multiply,
 // then add: the double that kernel would write into the angle's row)
@@ -333,6 +350,8 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Joins... 
     static_assert(!DIRECT || OUT == GRT_OUT_ROWS || OUT == GRT_OUT_LEVELS, "the direct beam leaves the six-row and level forms");
     static_assert(!has<GrtZenithSurfaceArgs, Joins...> || has<GrtZenithArgs, Joins...>,
                   "every angle's own direct albedo goes with the sun angles");
+    static_assert(!has<GrtZenithSlantArgs, Joins...> || (has<GrtZenithArgs, Joins...> && DIRECT && FUSED),
+                  "a sun cosine per layer goes with the sun angles and the direct beam, fused forms");
     constexpr bool RESPONSES = has<GrtResponseArgs, Joins...>;
     static_assert(!RESPONSES || (OUT == GRT_OUT_LEVELS && DIRECT), "the response rows leave the level form, the direct beam with them");
     SolverRow const row = solver_row(a.ncol, joins...);
@@ -393,7 +412,16 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Joins... 
         {
             double t, om, gg;
             optics.at(j, t, om, gg);
-            return layer_props(om, gg, t, mu_dir, mu_dif);
+            // (a sun cosine per layer: named in the slant instances alone, so that every other instance's closure, and with
+            // it its code, stays what it was)
+            if constexpr (has<GrtZenithSlantArgs, Joins...>)
+            {
+                return layer_props(om, gg, t, layer_mu(mu_dir, row.sun, L, j, joins...), mu_dif);
+            }
+            else
+            {
+                return layer_props(om, gg, t, mu_dir, mu_dif);
+            }
         }
         uint64_t const o = (uint64_t)j*nw;
         return layer_props(omega[o], g[o], tau[o], mu_dir, mu_dif);
@@ -594,7 +622,9 @@ __global__ __launch_bounds__(kSolverBlock) void ck_sw_kernel(GrtCkSolveArgs a)
 // GrtAerosolArgs, a GrtSubcolumnArgs, or a GrtAerosolArgs behind a GrtSubcolumnArgs; behind any of the four a
 // GrtZenithSurfaceArgs (the angle's own direct albedo at the surface, in place of the column's), a GrtDirectArgs (the angle's
 // direct beam at the top and the surface -- 1 and dir[u], scaled as the rows beside them -- through the sink's three more
-// rows) or both: sw_kernel's zenith instances with those joins, bit for bit.
+// rows) or both: sw_kernel's zenith instances with those joins, bit for bit.  With a GrtZenithSlantArgs ahead of the
+// GrtDirectArgs the direct-beam solution of angle u in layer j takes layer_mu's cosine in place of mu[u]; the scale stays
+// solar x mu[u].
 template <int ZN, typename... Joins>
 __global__ __launch_bounds__(kSolverBlock) void sw_zenith_kernel(GrtSwArgs a, GrtZenithArgs zn, Joins... joins)
 {
@@ -651,7 +681,9 @@ __global__ __launch_bounds__(kSolverBlock) void sw_zenith_kernel(GrtSwArgs a, Gr
                 if (day[u])
                 {
                     ExpKt mine = shared;
-                    LayerRT const d = eddington<true>(os, ts, mu[u], gs, mine);
+                    // (the angle's cosine in this layer: asked for where it is used -- the kernel holds every scalar register
+                    // there is, and a cosine asked for earlier in the layer displaces others for longer)
+                    LayerRT const d = eddington<true>(os, ts, layer_mu(mu[u], col*Z + k0 + u, L, j, joins...), gs, mine);
                     Rd[u] = Rd[u] + Tu*((dir[u]*d.R + dif[u]*s.R)*C);
                     dif[u] = (dir[u]*d.R*Ru + dif[u])*s.T*C + dir[u]*(d.T - d.Tpure);      // shortwave.c:312-316
                     dir[u] *= d.Tpure;
@@ -662,6 +694,7 @@ __global__ __launch_bounds__(kSolverBlock) void sw_zenith_kernel(GrtSwArgs a, Gr
         }
     }
     constexpr bool DIRECT = has<GrtDirectArgs, Joins...>, SURFACE = has<GrtZenithSurfaceArgs, Joins...>;
+    static_assert(!has<GrtZenithSlantArgs, Joins...> || DIRECT, "a sun cosine per layer goes with the direct beam");
     // (the column's direct albedo, once; with a GrtZenithSurfaceArgs every angle reads its own below)
     double const alb_col = SURFACE ? 0. : a.alb_dir[(uint64_t)col*a.alb_stride + ii];
     double const alb_dif = a.alb_dif[(uint64_t)col*a.alb_stride + ii];
@@ -1062,6 +1095,14 @@ int launch_zenith_forms(hipStream_t s, GrtSolverInstance const &in, GrtSwArgs co
     return launch<OUT>(s, in, a, front..., *in.zeniths, *in.direct);
 }
 
+// the zenith instances whose direct beam reads a cosine per layer (grt_pipeline_run_sky_zeniths_slant), of sw_kernel and of
+// the shared-layer kernel: named at the end of this file, so that they are instantiated behind every instance that was
+// here before them
+int launch_slant(hipStream_t s, GrtSolverInstance const &in, GrtSwArgs const &a);
+int launch_zeniths_slant(hipStream_t s, GrtSwArgs const &a, GrtZenithArgs const &z, GrtSubcolumnArgs const *sc,
+                         GrtAerosolArgs const *ae, GrtDirectArgs const &d, GrtZenithSurfaceArgs const *zs,
+                         GrtZenithSlantArgs const &sl);
+
 } // namespace
 
 extern "C" int grt_launch_ck_sw(void *stream, GrtCkSolveArgs const *a)
@@ -1111,6 +1152,11 @@ extern "C" int grt_launch_sw(void *stream, GrtSolverInstance const *in, GrtSwArg
         default:
             return (int)hipErrorInvalidValue;
         }
+    }
+    // the zenith instances whose direct beam reads a cosine per layer (grt_pipeline_run_sky_zeniths_slant's sets and forms) ...
+    if (in->zenith_slant != nullptr)
+    {
+        return launch_slant(s, *in, *a);
     }
     // the zenith instances that also leave the direct beam, read every angle's own direct albedo or both
     // (grt_pipeline_run_sky_zeniths_direct's sets and forms: three instances a case, launch_zenith_forms) ...
@@ -1247,8 +1293,12 @@ int launch_zenith_forms(hipStream_t s, GrtSwArgs const &a, GrtZenithArgs const &
 } // namespace
 
 extern "C" int grt_zenith_chunk(GrtSubcolumnArgs const *sc, GrtAerosolArgs const *ae, GrtDirectArgs const *d,
-                                GrtZenithSurfaceArgs const *zs)
+                                GrtZenithSurfaceArgs const *zs, GrtZenithSlantArgs const *sl)
 {
+    if (sl != nullptr)
+    {
+        return zs != nullptr ? GRT_ZENITH_CHUNK_SLANT_SURFACE : GRT_ZENITH_CHUNK_SLANT;
+    }
     if (d != nullptr || zs != nullptr)
     {
         return d != nullptr ? (zs != nullptr ? GRT_ZENITH_CHUNK_DIRECT_SURFACE : GRT_ZENITH_CHUNK_DIRECT) : GRT_ZENITH_CHUNK_SURFACE;
@@ -1258,17 +1308,24 @@ extern "C" int grt_zenith_chunk(GrtSubcolumnArgs const *sc, GrtAerosolArgs const
 }
 
 extern "C" int grt_launch_sw_zeniths(void *stream, GrtSwArgs const *a, GrtZenithArgs const *z, GrtSubcolumnArgs const *sc,
-                                     GrtAerosolArgs const *ae, GrtDirectArgs const *d, GrtZenithSurfaceArgs const *zs)
+                                     GrtAerosolArgs const *ae, GrtDirectArgs const *d, GrtZenithSurfaceArgs const *zs,
+                                     GrtZenithSlantArgs const *sl)
 {
     GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                  nullptr};
+                                  nullptr, nullptr};
     if (!grt_solver_instance_ok(in, *a) || z == nullptr || z->mu == nullptr || z->zeniths < 1 || !grt_sw_one_sweep(a) ||
         (sc != nullptr && !grt_subcolumn_args_ok(sc)) || (ae != nullptr && !grt_aerosol_args_ok(ae)) ||
-        (d != nullptr && !grt_direct_args_ok(d)) || (zs != nullptr && !grt_zenith_surface_args_ok(zs)))
+        (d != nullptr && !grt_direct_args_ok(d)) || (zs != nullptr && !grt_zenith_surface_args_ok(zs)) ||
+        (sl != nullptr && (!grt_zenith_slant_args_ok(sl) || d == nullptr)))
     {
         return (int)hipErrorInvalidValue;
     }
     hipStream_t const s = (hipStream_t)stream;
+    // the instances whose direct beam reads a cosine per layer, behind each join ...
+    if (sl != nullptr)
+    {
+        return launch_zeniths_slant(s, *a, *z, sc, ae, *d, zs, *sl);
+    }
     // the instances that also leave the direct beam, read every angle's own direct albedo or both, behind each join ...
     if (d != nullptr || zs != nullptr)
     {
@@ -1322,7 +1379,7 @@ int launch_tiles(hipStream_t s, GrtSwArgs const &a, GrtTileArgs const &t, int dr
 extern "C" int grt_launch_sw_tiles(void *stream, GrtSwArgs const *a, GrtTileArgs const *t, GrtSubcolumnArgs const *sc,
                                    GrtAerosolArgs const *ae)
 {
-    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (a == nullptr || t == nullptr || !grt_solver_instance_ok(in, *a) || (!grt_sw_one_sweep(a) && a->park == nullptr) ||
         (sc != nullptr && !grt_subcolumn_args_ok(sc)) || (ae != nullptr && !grt_aerosol_args_ok(ae)))
     {
@@ -1367,3 +1424,77 @@ extern "C" int grt_launch_direct_rows(void *stream, int n, int num_levels, int u
                        user_level, levels, rows);
     return (int)hipGetLastError();
 }
+
+namespace {
+
+// ---- a sun cosine per layer for the direct beam (GrtZenithSlantArgs): the launch sites of its instances ----
+// A slant instance always carries the direct beam (a GrtDirectArgs last), with every angle's own direct albedo (a
+// GrtZenithSurfaceArgs behind the GrtZenithArgs) or without.
+
+// ... of sw_kernel, OUT behind the joins `front`
+template <GrtSolverOutput OUT, typename... Front>
+int launch_slant_forms(hipStream_t s, GrtSolverInstance const &in, GrtSwArgs const &a, Front const &...front)
+{
+    if (in.zenith_surface != nullptr)
+    {
+        return launch<OUT>(s, in, a, front..., *in.zeniths, *in.zenith_surface, *in.zenith_slant, *in.direct);
+    }
+    return launch<OUT>(s, in, a, front..., *in.zeniths, *in.zenith_slant, *in.direct);
+}
+
+int launch_slant(hipStream_t s, GrtSolverInstance const &in, GrtSwArgs const &a)
+{
+    if (in.zeniths == nullptr || in.direct == nullptr)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    switch (GRT_INSTANCE(in.out, grt_solver_join(&in)))
+    {
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS): return launch_slant_forms<GRT_OUT_ROWS>(s, in, a);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS): return launch_slant_forms<GRT_OUT_LEVELS>(s, in, a);
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS_AEROSOLS): return launch_slant_forms<GRT_OUT_ROWS>(s, in, a, *in.aerosols);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS_AEROSOLS): return launch_slant_forms<GRT_OUT_LEVELS>(s, in, a, *in.aerosols);
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS_SUBCOLUMNS): return launch_slant_forms<GRT_OUT_ROWS>(s, in, a, *in.subcolumns);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS_SUBCOLUMNS):
+        return launch_slant_forms<GRT_OUT_LEVELS>(s, in, a, *in.subcolumns);
+    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS_SUBCOLUMNS_AEROSOLS):
+        return launch_slant_forms<GRT_OUT_ROWS>(s, in, a, *in.subcolumns, *in.aerosols);
+    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS_SUBCOLUMNS_AEROSOLS):
+        return launch_slant_forms<GRT_OUT_LEVELS>(s, in, a, *in.subcolumns, *in.aerosols);
+    default:
+        return (int)hipErrorInvalidValue;
+    }
+}
+
+// ... of sw_zenith_kernel behind the joins `front`
+template <typename... Front>
+int launch_zeniths_slant_forms(hipStream_t s, GrtSwArgs const &a, GrtZenithArgs const &z, int draws, GrtDirectArgs const &d,
+                               GrtZenithSurfaceArgs const *zs, GrtZenithSlantArgs const &sl, Front const &...front)
+{
+    if (zs != nullptr)
+    {
+        return launch_zeniths<GRT_ZENITH_CHUNK_SLANT_SURFACE>(s, a, z, draws, front..., *zs, sl, d);
+    }
+    return launch_zeniths<GRT_ZENITH_CHUNK_SLANT>(s, a, z, draws, front..., sl, d);
+}
+
+int launch_zeniths_slant(hipStream_t s, GrtSwArgs const &a, GrtZenithArgs const &z, GrtSubcolumnArgs const *sc,
+                         GrtAerosolArgs const *ae, GrtDirectArgs const &d, GrtZenithSurfaceArgs const *zs,
+                         GrtZenithSlantArgs const &sl)
+{
+    if (sc != nullptr && ae != nullptr)
+    {
+        return launch_zeniths_slant_forms(s, a, z, sc->count, d, zs, sl, *sc, *ae);
+    }
+    if (sc != nullptr)
+    {
+        return launch_zeniths_slant_forms(s, a, z, sc->count, d, zs, sl, *sc);
+    }
+    if (ae != nullptr)
+    {
+        return launch_zeniths_slant_forms(s, a, z, 1, d, zs, sl, *ae);
+    }
+    return launch_zeniths_slant_forms(s, a, z, 1, d, zs, sl);
+}
+
+} // namespace

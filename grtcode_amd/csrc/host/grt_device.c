@@ -488,6 +488,7 @@ EXTERN size_t grt_sizeof(int kind)
         case GRT_LW_SCATTER: return sizeof(GrtLwScatter_t);
         case GRT_ZENITH_SURFACE: return sizeof(GrtZenithSurface_t);
         case GRT_ZENITH_DIRECT: return sizeof(GrtZenithDirect_t);
+        case GRT_ZENITH_SLANT: return sizeof(GrtZenithSlant_t);
         default: return 0;
     }
 }

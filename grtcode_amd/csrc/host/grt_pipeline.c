@@ -548,6 +548,8 @@ typedef struct GrtJoin
     int zenith_direct;                 /* ... every angle's direct beam leaves too, in the run's form (three rows, or V): */
     double *zenith_direct_out;         /* DEVICE [ncol][sets][3 or V], the mean over the angles, or NULL */
     double *zenith_direct_per_angle;   /* DEVICE [ncol][sets][Z][3 or V], or NULL */
+    GrtZenithSlant_t const *zenith_slant;      /* grt_pipeline_run_sky_zeniths_slant (with zeniths and sets; the fused form):
+                                                  every angle's direct beam reads a cosine per layer */
 } GrtJoin;
 
 #define GRT_SKY_ALL (GRT_SKY_CLEAN | GRT_SKY_AEROSOL | GRT_SKY_CLOUD | GRT_SKY_CLOUD_AEROSOL)
@@ -602,6 +604,10 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
         if (join->zenith_surface != NULL && p->band[1].gas != NULL)
         {
             GRT_TRY(grt_stage_zenith_surface(p, join->zenith_surface, C, &zr));
+        }
+        if (join->zenith_slant != NULL && p->band[1].gas != NULL)
+        {
+            GRT_TRY(grt_stage_zenith_slant(p, join->zenith_slant, C, &zr));
         }
         zr.direct = join->zenith_direct;
         zr.direct_out = join->zenith_direct_out;
@@ -1554,21 +1560,18 @@ EXTERN int grt_pipeline_run_sky_zeniths(GrtPipeline_t *p, GrtColumns_t const *co
     return GRTCODE_SUCCESS;
 }
 
-/* grt_ext.h: grt_pipeline_run_sky_zeniths with a direct-beam albedo per (column, angle), every angle's direct beam, or both */
-EXTERN int grt_pipeline_run_sky_zeniths_direct(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky,
-                                               GrtZeniths_t const *zn, GrtZenithSurface_t const *surface,
-                                               GrtZenithDirect_t const *direct, fp_t *level_fluxes_dev, fp_t *heating_dev,
-                                               fp_t *fluxes_dev)
+/* grt_pipeline_run_sky_zeniths_direct and, with slant, grt_pipeline_run_sky_zeniths_slant: one body */
+static int sky_zeniths_direct(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky, GrtZeniths_t const *zn,
+                              GrtZenithSlant_t const *slant, GrtZenithSurface_t const *surface,
+                              GrtZenithDirect_t const *direct, fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev)
 {
-    GRT_REQUIRE_PTR(p);
-    GRT_REQUIRE_PTR(cols);
     int nsets;
     GRT_TRY(check_sky_sets(sky, &nsets));
     GrtAerosols_t a;
     GrtJoin join;
     GRT_TRY(sky_join(p, cols, sky, &a, &join));
     GRT_TRY(check_zeniths(p, cols, zn, level_fluxes_dev, fluxes_dev));
-    if (surface == NULL && direct == NULL)
+    if (surface == NULL && direct == NULL && slant == NULL)
     {
         GRT_FAIL(GRTCODE_VALUE_ERR, "surface and direct are both NULL: grt_pipeline_run_sky_zeniths is that call.%s", "");
     }
@@ -1590,8 +1593,18 @@ EXTERN int grt_pipeline_run_sky_zeniths_direct(GrtPipeline_t *p, GrtColumns_t co
     {
         GRT_TRY(grt_check_zenith_surface(surface, cols->ncol, Z));
     }
+    if (slant != NULL)
+    {
+        if (p->keep_spectra)
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "a pipeline in the materialised form (keep_spectra = 1): the layer cosines join the "
+                     "fused solver alone.%s", "");
+        }
+        GRT_TRY(grt_check_zenith_slant(slant, zn, cols->ncol, V - 1));
+    }
     join.zeniths = zn;
     join.zenith_surface = surface;
+    join.zenith_slant = slant;
     GrtBand *sw = &p->band[1];
     if (direct != NULL && sw->gas != NULL)
     {
@@ -1650,6 +1663,30 @@ EXTERN int grt_pipeline_run_sky_zeniths_direct(GrtPipeline_t *p, GrtColumns_t co
                                   "row pick kernel"));
         }
     }
+    return GRTCODE_SUCCESS;
+}
+
+/* grt_ext.h: grt_pipeline_run_sky_zeniths with a direct-beam albedo per (column, angle), every angle's direct beam, or both */
+EXTERN int grt_pipeline_run_sky_zeniths_direct(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky,
+                                               GrtZeniths_t const *zn, GrtZenithSurface_t const *surface,
+                                               GrtZenithDirect_t const *direct, fp_t *level_fluxes_dev, fp_t *heating_dev,
+                                               fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    GRT_TRY(sky_zeniths_direct(p, cols, sky, zn, NULL, surface, direct, level_fluxes_dev, heating_dev, fluxes_dev));
+    return GRTCODE_SUCCESS;
+}
+
+/* grt_ext.h: ... with a sun cosine per layer for the direct beam (slant NULL: the call above) */
+EXTERN int grt_pipeline_run_sky_zeniths_slant(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *sky,
+                                              GrtZeniths_t const *zn, GrtZenithSlant_t const *slant,
+                                              GrtZenithSurface_t const *surface, GrtZenithDirect_t const *direct,
+                                              fp_t *level_fluxes_dev, fp_t *heating_dev, fp_t *fluxes_dev)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(cols);
+    GRT_TRY(sky_zeniths_direct(p, cols, sky, zn, slant, surface, direct, level_fluxes_dev, heating_dev, fluxes_dev));
     return GRTCODE_SUCCESS;
 }
 

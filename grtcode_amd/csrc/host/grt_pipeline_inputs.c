@@ -765,6 +765,117 @@ int grt_stage_zenith_surface(GrtPipeline_t *p, GrtZenithSurface_t const *zs, int
     return GRTCODE_SUCCESS;
 }
 
+/* ---- a sun cosine per layer for the direct beam (grt_pipeline_run_sky_zeniths_slant) ---- */
+
+/* grt_ext.h: the layer cosines of the straight ray that reaches the column's lowest level */
+EXTERN int grt_slant_cosines(double radius_m, int ncol, int num_levels, int num_zeniths, double const *height_m,
+                             double const *cos_zenith, double *layer_cos_zenith)
+{
+    GRT_REQUIRE_PTR(height_m);
+    GRT_REQUIRE_PTR(cos_zenith);
+    GRT_REQUIRE_PTR(layer_cos_zenith);
+    if (!(radius_m >= 0.) || !isfinite(radius_m))
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "planet radius %e m: finite and at least 0 (0: a flat planet).", radius_m);
+    }
+    if (ncol < 1 || num_levels < 2 || num_zeniths < 1)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d columns of %d levels under %d angles: at least 1, 2 and 1.", ncol, num_levels,
+                 num_zeniths);
+    }
+    size_t const C = (size_t)ncol, V = (size_t)num_levels, L = V - 1, Z = (size_t)num_zeniths;
+    for (size_t c = 0; c < C; ++c)
+    {
+        double const *h = height_m + c*V;
+        for (size_t j = 0; j < V; ++j)
+        {
+            if (!isfinite(h[j]) || (j > 0 && !(h[j] < h[j - 1])))
+            {
+                GRT_FAIL(GRTCODE_VALUE_ERR, "height of level %zu of column %zu (%e m) is not finite or not below the level "
+                         "above it: top first, strictly descending.", j, c, h[j]);
+            }
+        }
+        for (size_t k = 0; k < Z; ++k)
+        {
+            if (!(fabs(cos_zenith[c*Z + k]) <= 1.))
+            {
+                GRT_FAIL(GRTCODE_VALUE_ERR, "cosine of zenith angle %zu of column %zu (%e) is NaN or beyond 1 in size.", k, c,
+                         cos_zenith[c*Z + k]);
+            }
+        }
+    }
+    for (size_t c = 0; c < C; ++c)
+    {
+        double const *h = height_m + c*V;
+        double const r0 = radius_m + h[V - 1];
+        for (size_t k = 0; k < Z; ++k)
+        {
+            double const mu0 = cos_zenith[c*Z + k];
+            double *out = layer_cos_zenith + (c*Z + k)*L;
+            double const s2 = r0*r0*(1. - mu0*mu0);
+            for (size_t j = 0; j < L; ++j)
+            {
+                if (mu0 < 0.)
+                {
+                    out[j] = 0.;            /* (night; mu0 = 0 is the horizon's ray: finite, though no entry point reads it) */
+                }
+                else if (radius_m == 0.)
+                {
+                    out[j] = mu0;
+                }
+                else
+                {
+                    double const rt = radius_m + h[j], rb = radius_m + h[j + 1];
+                    double const a = sqrt(rt*rt - s2), b = sqrt(rb*rb - s2);
+                    out[j] = (a + b)/(rt + rb);
+                }
+            }
+        }
+    }
+    return GRTCODE_SUCCESS;
+}
+
+/* What grt_pipeline_run_sky_zeniths_slant refuses in its layer cosines (nothing is touched): a NULL array, and under a day
+   sample (cos_zenith > 0) a layer cosine that is not finite, is <= 0 or is > 1.  A night sample's entries are not read. */
+int grt_check_zenith_slant(GrtZenithSlant_t const *sl, GrtZeniths_t const *zn, int C, int L)
+{
+    if (sl->layer_cos_zenith == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "layer_cos_zenith is NULL: the layer cosines [ncol][%d][%d] are the input.",
+                 zn->num_zeniths, L);
+    }
+    size_t const n = (size_t)C*(size_t)zn->num_zeniths;
+    for (size_t r = 0; r < n; ++r)
+    {
+        if (!(zn->cos_zenith[r] > 0.))
+        {
+            continue;
+        }
+        double const *mu = sl->layer_cos_zenith + r*(size_t)L;
+        for (int j = 0; j < L; ++j)
+        {
+            if (!(mu[j] > 0.) || !(mu[j] <= 1.))
+            {
+                GRT_FAIL(GRTCODE_VALUE_ERR, "cosine of layer %d under zenith angle %zu of column %zu (%e) is not in (0, 1].", j,
+                         r % (size_t)zn->num_zeniths, r/(size_t)zn->num_zeniths, mu[j]);
+            }
+        }
+    }
+    return GRTCODE_SUCCESS;
+}
+
+/* The checked cosines to the device, once per call: a block of the shortwave band's, [max_cols][Z][L] at this call's Z.
+   (The copy reads the caller's pageable array before it returns, as every copy from such memory does.) */
+int grt_stage_zenith_slant(GrtPipeline_t *p, GrtZenithSlant_t const *sl, int C, GrtZenithRun *zr)
+{
+    GrtScratch *block = &p->band[1].scratch[GRT_SCRATCH_ZEN_SLANT];
+    size_t const per = (size_t)zr->zeniths*(size_t)(p->num_levels - 1);
+    GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*per, NULL));
+    GRT_TRY(grt_dev_upload(p->device, block->d, sl->layer_cos_zenith, sizeof(double)*(size_t)C*per, grt_dev_stream(p->device)));
+    zr->slant.mu_layer = block->d;
+    return GRTCODE_SUCCESS;
+}
+
 /* ---- instrument channels (grt_pipeline_run_sky_channels) ---- */
 
 /* What grt_pipeline_run_sky_channels and grt_channel_pair_count check of an instrument's channels on a grid of n points

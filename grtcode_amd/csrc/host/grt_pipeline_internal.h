@@ -132,6 +132,9 @@ enum
     /* ... materialised form with a GrtZenithSurface_t: [max_cols][n] the direct-albedo rows of the angle being solved (the
        rows of the surface in force, GRT_SCRATCH_SURF_ROWS, are not written) */
     GRT_SCRATCH_ZEN_SURF_ROWS,
+    /* grt_pipeline_run_sky_zeniths_slant, shortwave: [max_cols][Z][L] the direct beam's cosine of every layer under every
+       angle, copied from the caller's array once per call; replaced when a call needs more */
+    GRT_SCRATCH_ZEN_SLANT,
     GRT_SCRATCH_COUNT
 };
 
@@ -352,6 +355,9 @@ typedef struct GrtZenithRun
        and their mean to direct_out, DEVICE [ncol][sets][3 or V] (either may be NULL, not both) */
     int direct;
     double *direct_per_angle, *direct_out;
+    /* grt_pipeline_run_sky_zeniths_slant (mu_layer NULL: not asked for): the direct beam's cosine per layer, DEVICE
+       [ncol][Z][L]; the fused instances then carry the direct beam whether or not `direct` asks for its rows */
+    GrtZenithSlantArgs slant;
 } GrtZenithRun;
 
 /* the doubles from one set of a column to the next */
@@ -392,6 +398,10 @@ GRT_PRIVATE int grt_stage_zeniths(GrtPipeline_t *p, GrtZeniths_t const *zn, int 
    checked surface's pairs to the device and the shortwave band's entry map brought up to date, as zr->surface */
 GRT_PRIVATE int grt_check_zenith_surface(GrtZenithSurface_t const *zs, int C, int Z);
 GRT_PRIVATE int grt_stage_zenith_surface(GrtPipeline_t *p, GrtZenithSurface_t const *zs, int C, GrtZenithRun *zr);
+/* what grt_pipeline_run_sky_zeniths_slant refuses in its layer cosines for C columns of L layers under the angles of zn
+   (nothing is touched); the checked cosines to the shortwave band's device block, as zr->slant */
+GRT_PRIVATE int grt_check_zenith_slant(GrtZenithSlant_t const *sl, GrtZeniths_t const *zn, int C, int L);
+GRT_PRIVATE int grt_stage_zenith_slant(GrtPipeline_t *p, GrtZenithSlant_t const *sl, int C, GrtZenithRun *zr);
 GRT_PRIVATE int grt_check_radiances(GrtRadiances_t const *rd, int C);
 GRT_PRIVATE int grt_stage_radiances(GrtPipeline_t *p, GrtRadiances_t const *rd, int C, GrtRadianceRun *rr);
 GRT_PRIVATE int grt_check_channels(GrtChannels_t const *ch, long long n, long long *pairs);

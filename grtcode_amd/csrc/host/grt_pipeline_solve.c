@@ -38,7 +38,7 @@ typedef struct ThirdRows
 static GrtSolverInstance pass_instance(GrtPipeline_t const *p, GrtPass const *ps, GrtBandArgs const *bn,
                                        GrtSubcolumnArgs const *sc, ThirdRows const *tr, int bi)
 {
-    GrtSolverInstance in = {GRT_OUT_CHAINS, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
+    GrtSolverInstance in = {GRT_OUT_CHAINS, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
     if (!p->keep_spectra)
     {
         in.out = pass_spectral(ps) ? GRT_OUT_ROWS_POINTS : (bn != NULL ? GRT_OUT_LEVEL_BINS :
@@ -1103,7 +1103,8 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
    GrtZenithSurfaceArgs join, and the materialised loop writes each angle's direct-albedo rows into a buffer of its own
    ahead of the angle's solve; with the direct beam the fused instances take the GrtDirectArgs join too (partial sums in
    GRT_SCRATCH_ZEN_DIRECT_PARTIALS at the same slots), the materialised loop runs the direct-beam kernel and its trapezoid
-   per (angle, draw), and the same mean kernel folds the three rows or V into zr->direct_per_angle and zr->direct_out. */
+   per (angle, draw), and the same mean kernel folds the three rows or V into zr->direct_per_angle and zr->direct_out.
+   grt_pipeline_run_sky_zeniths_slant (zr->slant; fused form alone): the instances take the GrtZenithSlantArgs join as well. */
 int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass const *ps, GrtZenithRun const *zr)
 {
     int const Z = zr->zeniths, rows = pass_rows(p, ps), out_offset = pass_offset(p, ps, 1);
@@ -1115,13 +1116,16 @@ int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass c
     GrtScratch *dblock = &b->scratch[GRT_SCRATCH_ZEN_DIRECT_PARTIALS];
     int const drows = direct_rows(p, ps);
     GrtZenithSurfaceArgs const *zs = zr->surface.tables != NULL ? &zr->surface : NULL;
+    /* grt_pipeline_run_sky_zeniths_slant (fused form): the direct beam's cosine per layer; its instances always carry the
+       direct beam, whose rows are folded below only where zr->direct asks for them */
+    GrtZenithSlantArgs const *sl = zr->slant.mu_layer != NULL ? &zr->slant : NULL;
     unsigned nblocks = 1;
     S = ps->clouds != NULL ? S : 1;
     if (!p->keep_spectra)
     {
         nblocks = b->nblocks;
         GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*(size_t)Z*(size_t)S*(size_t)rows*nblocks, NULL));
-        if (zr->direct)
+        if (zr->direct || sl != NULL)
         {
             GRT_TRY(grt_scratch_need(p, dblock, (size_t)p->max_cols*(size_t)Z*(size_t)S*(size_t)drows*nblocks, NULL));
         }
@@ -1138,15 +1142,16 @@ int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass c
         GrtSubcolumnArgs *draws = ps->clouds != NULL ? &sc : NULL;
         GrtSolverInstance in = pass_instance(p, ps, NULL, draws, NULL, 1);
         in.zeniths = &za;
-        in.direct = zr->direct ? &da : NULL;
+        in.direct = zr->direct || sl != NULL ? &da : NULL;
         in.zenith_surface = zs;
+        in.zenith_slant = sl;
         SolverArgs a;
         GRT_TRY(solver_args(p, b, 1, C, ps, &in, block->d, &a));
         char const *env = getenv("GRT_ZENITH_SHARED");
         int const parks = grt_sw_parks(&in, &a.sw);
         /* (grid rows; a park block of max_cols columns) */
         int const limit = parks ? p->max_cols/C : 65535/C;
-        int const chunk = grt_zenith_chunk(draws, ps->aer, in.direct, zs), chunks = (Z + chunk - 1)/chunk;
+        int const chunk = grt_zenith_chunk(draws, ps->aer, in.direct, zs, sl), chunks = (Z + chunk - 1)/chunk;
         int const shared = !ps->profile && !parks && chunks <= limit &&
                            (joined ? env != NULL && env[0] == '1' : !(env != NULL && env[0] == '0'));
         int const slot = grt_profile_begin(s, sw_tag);
@@ -1158,7 +1163,7 @@ int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass c
             for (sc.first = 0; sc.first < S && krc == 0; sc.first += group)
             {
                 sc.count = S - sc.first < group ? S - sc.first : group;
-                krc = grt_launch_sw_zeniths(s, &a.sw, &za, draws, ps->aer, in.direct, zs);
+                krc = grt_launch_sw_zeniths(s, &a.sw, &za, draws, ps->aer, in.direct, zs, sl);
             }
         }
         else

@@ -209,7 +209,7 @@ EXTERN int calculate_lw_fluxes(Longwave_t * const lw, Optics_t const * const opt
     /* GRT_LW_COLUMN_CHAINS=1: one thread per wavenumber through all the layers, as before round 4 (same fluxes) */
     char const *chains = getenv("GRT_LW_COLUMN_CHAINS");
     GrtSolverInstance const in = {(chains != NULL && chains[0] == '1') || !block_has_scratch(lw->device, lw->layer_temperature, lw->flux_down + n*(size_t)V, sizeof(fp_t)*6*n*(size_t)(V - 1))
-                                  ? GRT_OUT_CHAINS : GRT_OUT_LAYERS, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
+                                  ? GRT_OUT_CHAINS : GRT_OUT_LAYERS, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
     a.layer_terms = in.out == GRT_OUT_LAYERS ? lw->flux_down + n*(size_t)V : NULL;
     GRT_TRY(grt_dev_check(grt_launch_lw(s, &in, &a), "longwave kernel"));
     GRT_TRY(download_fluxes(lw->device, V, n, flux_up, flux_down, lw->flux_up, lw->flux_down, s));
@@ -258,7 +258,7 @@ EXTERN int grt_lw_scatter_levels(Device_t device, GrtLwScatter_t const *sc)
     void *park = NULL;
     GRT_TRY(grt_dev_alloc(device, &park, sizeof(double)*grt_scatter_park_doubles((uint64_t)sc->ncol, V, n)));
     GrtScatterArgs const sa = {park, (uint64_t)sc->ncol, sc->g_dev, sc->flux_up_dev, sc->flux_down_dev};
-    GrtSolverInstance const in = {GRT_OUT_CHAINS, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, &sa, NULL};
+    GrtSolverInstance const in = {GRT_OUT_CHAINS, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, &sa, NULL, NULL};
     void *s = grt_dev_stream(device);
     int const slot = grt_profile_begin(s, GRT_TAG_SCATTER_LW);
     int const krc = grt_launch_lw_scatter(s, &in, &a);
@@ -356,7 +356,7 @@ EXTERN int calculate_sw_fluxes(Shortwave_t * const sw, Optics_t const * const op
     /* GRT_SW_COLUMN_CHAINS=1: one thread per wavenumber through all the layers, as before round 4 (same fluxes) */
     char const *chains = getenv("GRT_SW_COLUMN_CHAINS");
     GrtSolverInstance const in = {(chains != NULL && chains[0] == '1') || !block_has_scratch(sw->device, sw->solar_flux, sw->flux_down + n*(size_t)V, sizeof(fp_t)*5*n*(size_t)(V - 1))
-                                  ? GRT_OUT_CHAINS : GRT_OUT_LAYERS, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
+                                  ? GRT_OUT_CHAINS : GRT_OUT_LAYERS, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
     a.layer_props = in.out == GRT_OUT_LAYERS ? sw->flux_down + n*(size_t)V : NULL;
     GRT_TRY(grt_dev_check(grt_launch_sw(s, &in, &a), "shortwave kernel"));
     GRT_TRY(download_fluxes(sw->device, V, n, flux_up, flux_down, sw->flux_up, sw->flux_down, s));

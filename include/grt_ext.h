@@ -49,6 +49,11 @@ enum grt_struct_kind_more
 {
     GRT_ZENITH_SURFACE = GRT_LW_SCATTER + 1, GRT_ZENITH_DIRECT
 };
+/* ... GrtZenithSlant_t */
+enum grt_struct_kind_slant
+{
+    GRT_ZENITH_SLANT = GRT_ZENITH_DIRECT + 1
+};
 EXTERN size_t grt_sizeof(int kind);
 
 /* ---- line lists from memory ------------------------------------------------------
@@ -1100,6 +1105,58 @@ EXTERN int grt_pipeline_run_sky_zeniths_direct(GrtPipeline_t *pipeline, GrtColum
    the same pairs angle-major, [zeniths][ncol][ns + 1][2] (the materialised form's) */
 EXTERN void grt_zenith_surface_tables(fp_t const *x, int ns, int ncol, int zeniths, fp_t const *values, fp_t *tables,
                                       fp_t *by_angle);
+
+/* ---- ... with a sun cosine per layer for the direct beam: the pseudo-spherical approximation ---------------------------
+ * grt_pipeline_run_sky_zeniths_direct in every respect -- sets and packing, both output forms, sweep rule, the per-angle
+ * outputs, the fold over the angles, the optional surface and direct beam, the longwave -- but the geometry of the direct
+ * beam.  A plane-parallel column attenuates the beam in every layer by exp(-tau/mu0): an air mass of 1/mu0, 1000 at
+ * mu0 = 1e-3, where a spherical planet has about 38 at the horizon.  Here the direct beam sees, in each layer, the cosine
+ * it has there; the diffuse field stays plane-parallel.
+ *   - For column c, angle k and layer j (top layer first), the caller gives layer_cos_zenith[c][k][j] in (0, 1].
+ *   - In layer j the direct-beam solution uses that value wherever it uses mu_dir today.  That covers eddington<true>, its
+ *     gamma3, the optical-depth clamp, T_pure and so the running direct beam.
+ *   - The diffuse solution (mu_dif), the adding sweeps and the level expressions are untouched.
+ *   - The flux scale stays solar * cos_zenith[c][k].  That is the angle's own cosine, the one at the column's lowest level,
+ *     as put_level and put_direct apply it today.
+ *   - The surface albedo rules of grt_pipeline_set_surface and of `zenith_surface` are untouched.
+ *   - cos_zenith <= 0 stays a night sample: +0.0, nothing solved, the angle's layer cosines not read.
+ * slant == NULL: grt_pipeline_run_sky_zeniths_direct with the other arguments, refusals included.  With a slant,
+ * zenith_surface and zenith_direct may both be NULL.  In the deterministic mode, with every layer's cosine equal to the
+ * angle's cos_zenith, every output has grt_pipeline_run_sky_zeniths_direct's bits.  Outputs and their layouts are that
+ * call's.  A pipeline without a shortwave band runs the longwave and writes +0.0 to every shortwave and direct output.
+ * The cosines are copied once per call into a device block [max_columns][Z][L] of the pipeline's own and joined to zenith
+ * instances of the shortwave solver and of the shared-layer kernel of their own (k_shortwave.hip: GrtZenithSlantArgs;
+ * routing and GRT_ZENITH_SHARED as in grt_pipeline_run_sky_zeniths); every slant instance carries the direct beam, so
+ * its partial sums are allocated whether or not zenith_direct asks for them.
+ * Not covered: a sun below the horizon that still lights upper layers (cos_zenith <= 0 is night at every level); a
+ * pipeline in the materialised form (keep_spectra = 1); refraction; what grt_pipeline_run_sky_zeniths does not cover.
+ * GRTCODE_VALUE_ERR, with nothing launched and every output untouched, for everything
+ * grt_pipeline_run_sky_zeniths_direct refuses (but surface and direct both NULL, which is allowed here); a NULL
+ * layer_cos_zenith; a day sample (cos_zenith > 0) with a layer cosine that is not finite, is <= 0 or is > 1; a pipeline
+ * in the materialised form.  Asynchronous on the pipeline's lane. */
+typedef struct GrtZenithSlant
+{
+    fp_t const *layer_cos_zenith;       /* HOST [ncol][Z][L], top layer first */
+} GrtZenithSlant_t;
+EXTERN int grt_pipeline_run_sky_zeniths_slant(GrtPipeline_t *pipeline, GrtColumns_t const *columns, GrtSky_t const *sky,
+                                              GrtZeniths_t const *zeniths, GrtZenithSlant_t const *slant,
+                                              GrtZenithSurface_t const *zenith_surface,
+                                              GrtZenithDirect_t const *zenith_direct, fp_t *level_fluxes_dev,
+                                              fp_t *heating_dev, fp_t *fluxes_dev);
+/* The layer cosines of the straight ray that reaches the column's lowest level under cos_zenith, on a sphere of radius
+   radius_m (pure host code).  height_m [ncol][V], top first, strictly descending; cos_zenith [ncol][Z];
+   layer_cos_zenith [ncol][Z][L], L = V - 1.  With r0 = radius + height[V-1], rt = radius + height[j],
+   rb = radius + height[j+1], s2 = r0 r0 (1 - mu0 mu0), a = sqrt(rt rt - s2), b = sqrt(rb rb - s2), layer j's cosine is
+   (a + b)/(rt + rb): the layer's thickness over the ray's path length in it, written so that nothing cancels -- finite at
+   mu0 = 0 and exactly 1 at mu0 = 1.  radius_m == 0 is a flat planet: every layer gets mu0 itself, bit for bit.  The
+   entries of an angle below the horizon (cos_zenith < 0) are set to 0; cos_zenith = 0 gets the horizon ray's cosines;
+   the pipeline, where cos_zenith <= 0 is a night sample, reads neither.  The ray to the surface is the exact
+   geometry for the beam at the surface and an approximation for the levels above it, whose own rays cross the upper
+   layers a little more steeply.  GRTCODE_VALUE_ERR, with nothing written, for a negative or non-finite radius,
+   num_levels < 2, ncol or num_zeniths < 1, heights that are not finite or not strictly descending, |cos_zenith| > 1 or
+   NaN; GRTCODE_NULL_ERR for a NULL pointer. */
+EXTERN int grt_slant_cosines(double radius_m, int ncol, int num_levels, int num_zeniths, double const *height_m,
+                             double const *cos_zenith, double *layer_cos_zenith);
 
 /* ---- several surface tiles per column on one gas-optics pass -----------------------------------------------------------
  * grt_pipeline_run_sky (its six-row form) with T surfaces per column: land, open water, sea ice, snow -- each tile with its
