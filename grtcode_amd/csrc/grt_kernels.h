@@ -856,17 +856,12 @@ typedef enum GrtSolverOutput
     GRT_OUT_LEVELS,         /* every level's up and down flux */
     GRT_OUT_LEVEL_BINS      /* every level's up and down flux per wavenumber bin of `bins` */
 } GrtSolverOutput;
-/* ... and what joins gas and Rayleigh in a fused instance: nothing (clear sky: every pointer NULL), the cloud objects,
-   the aerosol object, or the cloud objects of several subcolumns per column -- or the aerosol object together with either
-   form of the clouds (GRT_OUT_ROWS and GRT_OUT_LEVELS: the five objects of sky_combine, optics_dev.h; the aerosol table
-   stays per column whatever the subcolumn); `bins` goes with GRT_OUT_LEVEL_BINS and with nothing else; `zeniths` (the
-   shortwave's GRT_OUT_ROWS and GRT_OUT_LEVELS) goes alone or with aerosols, subcolumns or both, never with `clouds`; `direct` (the shortwave's GRT_OUT_ROWS and
-   GRT_OUT_LEVELS) goes with any join of clouds and aerosols or none, or behind `zeniths` and what joins them, and selects instances of its own: the instance
-   without it is the one it was; `zenith_surface` (every angle's own direct albedo) goes with `zeniths` alone, with or without `direct`, and selects instances of its own likewise; `zenith_slant` (a sun cosine per layer for the direct beam) goes with `zeniths` and `direct` together, with or without `zenith_surface`, and selects instances of its own likewise; `jacobian` is the same for the longwave's GRT_OUT_ROWS and GRT_OUT_LEVELS; `responses` goes with GRT_OUT_LEVELS alone, in the shortwave always together with `direct`, never with `bins`, `zeniths` or `jacobian`, and selects instances of its own as `direct` does; `scatter` (the longwave's GRT_OUT_CHAINS, GRT_OUT_ROWS and GRT_OUT_LEVELS, with any
-   join of clouds and aerosols or none, never with the others) names the instances of lw_scatter_kernel, which
-   grt_launch_lw_scatter alone launches.  The kind of instance follows from which pointers are set, and a kernel takes the structs that are
-   set as arguments after its band's own.  The next joined object is a pointer here, a line in grt_solver_instance_ok
-   and a case in each band's list of instances. */
+/* ... and what joins gas and Rayleigh in a fused instance, or rides with it: every pointer NULL is clear sky.  The kind of
+   instance follows from which pointers are set, and a kernel takes the structs that are set as arguments after its band's
+   own, in the order of the GRT_JOIN_ bits below.  Which sets exist is said once per kernel family, by the rules behind
+   grt_sw_instance_exists and its kin at the end of this file; grt_launch_joined (hip/solver_dispatch.h) turns a set into the
+   kernel's template arguments.  The next joined object is a pointer here, a bit in the order, a line in a rule and a
+   `pick` where the kernel reads it. */
 typedef struct GrtSolverInstance
 {
     GrtSolverOutput out;
@@ -882,14 +877,15 @@ typedef struct GrtSolverInstance
     GrtZenithSurfaceArgs const *zenith_surface;
     GrtZenithSlantArgs const *zenith_slant;
 } GrtSolverInstance;
-typedef enum GrtSolverJoin
+/* a join as a bit, in the order the kernels take the joins in their packs (grt_solver_joins lists the pointers in it);
+   GRT_JOIN_CHANNELS is the GrtChannelArgs last in lw_radiance_kernel's pack, which no GrtSolverInstance carries, and
+   `scatter` has no bit: lw_scatter_kernel takes its GrtScatterArgs as a parameter of its own, ahead of the pack */
+enum
 {
-    GRT_JOIN_NONE, GRT_JOIN_CLOUDS, GRT_JOIN_AEROSOLS, GRT_JOIN_SUBCOLUMNS, GRT_JOIN_CLOUDS_AEROSOLS,
-    GRT_JOIN_SUBCOLUMNS_AEROSOLS, GRT_JOIN_ZENITHS, GRT_JOIN_ZENITHS_AEROSOLS, GRT_JOIN_ZENITHS_SUBCOLUMNS,
-    GRT_JOIN_ZENITHS_SUBCOLUMNS_AEROSOLS, GRT_JOIN_COUNT
-} GrtSolverJoin;
-/* an instance as one integer: the case labels of a band's list of instances (the launchers' switches) */
-#define GRT_INSTANCE(out, join) ((int)(out)*(int)GRT_JOIN_COUNT + (int)(join))
+    GRT_JOIN_CLOUDS = 1 << 0, GRT_JOIN_SUBCOLUMNS = 1 << 1, GRT_JOIN_AEROSOLS = 1 << 2, GRT_JOIN_ZENITHS = 1 << 3,
+    GRT_JOIN_ZENITH_SURFACE = 1 << 4, GRT_JOIN_ZENITH_SLANT = 1 << 5, GRT_JOIN_DIRECT = 1 << 6, GRT_JOIN_JACOBIAN = 1 << 7,
+    GRT_JOIN_RESPONSES = 1 << 8, GRT_JOIN_BINS = 1 << 9, GRT_JOIN_CHANNELS = 1 << 10, GRT_JOIN_BITS = 11
+};
 #ifdef __cplusplus
 #define GRT_FN constexpr
 #else
@@ -898,23 +894,6 @@ typedef enum GrtSolverJoin
 GRT_FN int grt_out_fused(GrtSolverOutput out) { return out >= GRT_OUT_ROWS; }
 GRT_FN int grt_out_levels(GrtSolverOutput out) { return out >= GRT_OUT_LEVELS; }
 #undef GRT_FN
-/* which pointers are set -- of an instance grt_solver_instance_ok has passed: it refuses clouds together with
-   subcolumns and with zeniths, and any join of an output that is not fused, so a band's switch sees no
-   such case */
-static inline GrtSolverJoin grt_solver_join(GrtSolverInstance const *in)
-{
-    if (in->zeniths != NULL)
-    {
-        return in->subcolumns != NULL ? (in->aerosols != NULL ? GRT_JOIN_ZENITHS_SUBCOLUMNS_AEROSOLS : GRT_JOIN_ZENITHS_SUBCOLUMNS) :
-               (in->aerosols != NULL ? GRT_JOIN_ZENITHS_AEROSOLS : GRT_JOIN_ZENITHS);
-    }
-    if (in->aerosols != NULL && (in->clouds != NULL || in->subcolumns != NULL))
-    {
-        return in->clouds != NULL ? GRT_JOIN_CLOUDS_AEROSOLS : GRT_JOIN_SUBCOLUMNS_AEROSOLS;
-    }
-    return in->clouds != NULL ? GRT_JOIN_CLOUDS : (in->aerosols != NULL ? GRT_JOIN_AEROSOLS :
-           (in->subcolumns != NULL ? GRT_JOIN_SUBCOLUMNS : GRT_JOIN_NONE));
-}
 /* the rows of its grid: a column each, or (subcolumns, zeniths) `count` subcolumns or angles of every column -- with both,
    every angle of every subcolumn of the launch */
 static inline uint64_t grt_solver_grid_rows(GrtSolverInstance const *in, int ncol)
@@ -1182,51 +1161,144 @@ int grt_launch_copy_rows(void *stream, double const *const *rows_dev, int nrows,
 
 #ifdef __cplusplus
 }
+#include <tuple>
 
-/* Whether the instance `in` can run on `a` (GrtLwArgs or GrtSwArgs: the fields both carry), for both launchers: the
-   combinations that exist, each set pointer's own fields, what the output reads and writes, a grid of at most 65 535
-   rows and the 64 KiB of LDS. */
+/* The pointers of an instance in the order of the GRT_JOIN_ bits -- the order of a kernel's pack -- and the bit-set of
+   those that are set, of these or of any such tuple (entry k is bit k). */
+inline auto grt_solver_joins(GrtSolverInstance const &in)
+{
+    return std::make_tuple(in.clouds, in.subcolumns, in.aerosols, in.zeniths, in.zenith_surface, in.zenith_slant, in.direct,
+                           in.jacobian, in.responses, in.bins);
+}
+template <typename... P>
+inline unsigned grt_join_set(std::tuple<P...> const &joins)
+{
+    return std::apply([](auto const *...p)
+                      {
+                          unsigned set = 0, bit = 1;
+                          ((set |= p != nullptr ? bit : 0u, bit <<= 1), ...);
+                          return set;
+                      }, joins);
+}
+
+/* Which instances exist: one rule per kernel family, on the output and the bit-set `m` of the joins.  The launchers
+   instantiate exactly these (grt_launch_joined, hip/solver_dispatch.h) and grt_solver_instance_ok refuses every other.
+   GRT_OUT_LAYERS is the two-kernel form, no instance of these templates: its launchers take it with no join at all. */
+constexpr unsigned GRT_JOIN_FRONT = GRT_JOIN_CLOUDS | GRT_JOIN_SUBCOLUMNS | GRT_JOIN_AEROSOLS;
+/* the joins every fused output shares: the clouds in one form at most, the aerosol object with either or alone */
+constexpr bool grt_front_exists(unsigned m) { return (m & GRT_JOIN_CLOUDS) == 0 || (m & GRT_JOIN_SUBCOLUMNS) == 0; }
+/* ... and what the outputs other than the six rows and the levels take, in both bands: the chains nothing, the six rows at
+   every point the clouds or nothing, the bins `bins` behind the clouds or behind nothing */
+constexpr bool grt_plain_instance_exists(GrtSolverOutput out, unsigned m)
+{
+    return out == GRT_OUT_CHAINS ? m == 0 : out == GRT_OUT_ROWS_POINTS ? (m & ~GRT_JOIN_CLOUDS) == 0 :
+           out == GRT_OUT_LEVEL_BINS && (m & ~GRT_JOIN_CLOUDS) == GRT_JOIN_BINS;
+}
+constexpr bool grt_sw_instance_exists(GrtSolverOutput out, unsigned m)
+{
+    if (out != GRT_OUT_ROWS && out != GRT_OUT_LEVELS)
+    {
+        return grt_plain_instance_exists(out, m);
+    }
+    bool const direct = (m & GRT_JOIN_DIRECT) != 0;
+    if (!grt_front_exists(m) || (m & (GRT_JOIN_JACOBIAN | GRT_JOIN_BINS | GRT_JOIN_CHANNELS)) != 0)
+    {
+        return false;
+    }
+    if ((m & GRT_JOIN_ZENITHS) != 0)    // never with clouds or responses; a cosine per layer needs the direct beam
+    {
+        return (m & (GRT_JOIN_CLOUDS | GRT_JOIN_RESPONSES)) == 0 && ((m & GRT_JOIN_ZENITH_SLANT) == 0 || direct);
+    }
+    // what goes behind the zeniths goes with nothing else; the responses leave the levels beside the direct beam
+    return (m & (GRT_JOIN_ZENITH_SURFACE | GRT_JOIN_ZENITH_SLANT)) == 0 &&
+           ((m & GRT_JOIN_RESPONSES) == 0 || (direct && out == GRT_OUT_LEVELS));
+}
+constexpr bool grt_lw_instance_exists(GrtSolverOutput out, unsigned m)
+{
+    if (out != GRT_OUT_ROWS && out != GRT_OUT_LEVELS)
+    {
+        return grt_plain_instance_exists(out, m);
+    }
+    // the Jacobian or the responses (the levels') behind the front, not both
+    unsigned const behind = m & ~GRT_JOIN_FRONT;
+    return grt_front_exists(m) && (behind == 0 || behind == GRT_JOIN_JACOBIAN ||
+                                   (behind == GRT_JOIN_RESPONSES && out == GRT_OUT_LEVELS));
+}
+/* lw_scatter_kernel (the GrtScatterArgs is a parameter of its own, ahead of the pack) */
+constexpr bool grt_lw_scatter_instance_exists(GrtSolverOutput out, unsigned m)
+{
+    return out == GRT_OUT_CHAINS ? m == 0 : (out == GRT_OUT_ROWS || out == GRT_OUT_LEVELS) && grt_front_exists(m) &&
+                                            (m & ~GRT_JOIN_FRONT) == 0;
+}
+/* lw_radiance_kernel, with the channels last or without, and -- never with GRT_JOIN_CHANNELS: the GrtChannelArgs is a
+   parameter of its own there -- lw_weighting_kernel: the front behind the fused form, nothing behind the materialised one */
+constexpr bool grt_lw_radiance_instance_exists(bool fused, unsigned m)
+{
+    return grt_front_exists(m) && (m & ~(GRT_JOIN_FRONT | GRT_JOIN_CHANNELS)) == 0 && (fused || (m & GRT_JOIN_FRONT) == 0);
+}
+/* sw_zenith_kernel (the GrtZenithArgs is a parameter of its own): what a zenith instance of the six rows takes behind it */
+constexpr bool grt_sw_zenith_instance_exists(unsigned m)
+{
+    return (m & GRT_JOIN_ZENITHS) == 0 && grt_sw_instance_exists(GRT_OUT_ROWS, m | GRT_JOIN_ZENITHS);
+}
+/* lw_tile_kernel and sw_tile_kernel */
+constexpr bool grt_tile_instance_exists(unsigned m)
+{
+    return (m & ~(GRT_JOIN_SUBCOLUMNS | GRT_JOIN_AEROSOLS)) == 0;
+}
+/* the angles per thread of a shared-layer instance and the tiles per thread of a tile instance (grt_zenith_chunk,
+   grt_tile_chunk) */
+constexpr int grt_zenith_chunk_of(unsigned m)
+{
+    bool const surface = (m & GRT_JOIN_ZENITH_SURFACE) != 0, aerosols = (m & GRT_JOIN_AEROSOLS) != 0;
+    return (m & GRT_JOIN_ZENITH_SLANT) != 0 ? (surface ? GRT_ZENITH_CHUNK_SLANT_SURFACE : GRT_ZENITH_CHUNK_SLANT) :
+           (m & GRT_JOIN_DIRECT) != 0 ? (surface ? GRT_ZENITH_CHUNK_DIRECT_SURFACE : GRT_ZENITH_CHUNK_DIRECT) :
+           surface ? GRT_ZENITH_CHUNK_SURFACE :
+           (m & GRT_JOIN_SUBCOLUMNS) != 0 ? (aerosols ? GRT_ZENITH_CHUNK_SUBCOLUMNS_AEROSOLS : GRT_ZENITH_CHUNK_SUBCOLUMNS) :
+           aerosols ? GRT_ZENITH_CHUNK_AEROSOLS : GRT_ZENITH_CHUNK;
+}
+constexpr int grt_tile_chunk_of(unsigned m)
+{
+    bool const aerosols = (m & GRT_JOIN_AEROSOLS) != 0;
+    return (m & GRT_JOIN_SUBCOLUMNS) != 0 ? (aerosols ? GRT_TILE_CHUNK_SUBCOLUMNS_AEROSOLS : GRT_TILE_CHUNK_SUBCOLUMNS) :
+           aerosols ? GRT_TILE_CHUNK_AEROSOLS : GRT_TILE_CHUNK;
+}
+/* ... and the band's rule for an instance as the launchers get it: the longwave's with `scatter` is lw_scatter_kernel's */
+inline bool grt_band_instance_exists(GrtSolverInstance const &in, GrtSwArgs const &)
+{
+    unsigned const m = grt_join_set(grt_solver_joins(in));
+    return in.scatter == nullptr && (in.out == GRT_OUT_LAYERS ? m == 0 : grt_sw_instance_exists(in.out, m));
+}
+inline bool grt_band_instance_exists(GrtSolverInstance const &in, GrtLwArgs const &)
+{
+    unsigned const m = grt_join_set(grt_solver_joins(in));
+    return in.scatter != nullptr ? grt_lw_scatter_instance_exists(in.out, m) :
+           in.out == GRT_OUT_LAYERS ? m == 0 : grt_lw_instance_exists(in.out, m);
+}
+
+/* Whether the instance `in` can run on `a` (GrtLwArgs or GrtSwArgs: the fields both carry), for both launchers: that it
+   exists in a's band, each set pointer's own fields, what the output reads and writes, a grid of at most 65 535 rows and the
+   64 KiB of LDS. */
 template <typename Args>
 inline bool grt_solver_instance_ok(GrtSolverInstance const &in, Args const &a)
 {
     bool const fused = grt_out_fused(in.out), flux_rows = a.flux_up != nullptr && a.flux_down != nullptr;
-    // (of the pairs, the aerosol object with either form of the clouds exists; clouds and subcolumns exclude each other)
-    int const cloud_forms = (in.clouds != nullptr) + (in.subcolumns != nullptr);
-    int const joined = cloud_forms + (in.aerosols != nullptr);
-    // (the sun angles join the six-row and level forms: clear sky, or with aerosols, subcolumns or both)
-    bool const zeniths_ok = in.zeniths == nullptr || (in.clouds == nullptr && grt_zenith_args_ok(in.zeniths) &&
-                                                      (in.out == GRT_OUT_ROWS || in.out == GRT_OUT_LEVELS));
-    // (the direct beam leaves the six-row and level forms, under one sun per column or several; the longwave launcher has no
-    // such case)
-    bool const direct_ok = in.direct == nullptr || (grt_direct_args_ok(in.direct) &&
-                                                    (in.out == GRT_OUT_ROWS || in.out == GRT_OUT_LEVELS));
-    // (every angle's own direct albedo: the zenith instances alone)
-    bool const zenith_surface_ok = in.zenith_surface == nullptr || (in.zeniths != nullptr && in.jacobian == nullptr &&
-                                                                    grt_zenith_surface_args_ok(in.zenith_surface));
-    // (a sun cosine per layer: the zenith instances that leave the direct beam)
-    bool const zenith_slant_ok = in.zenith_slant == nullptr || (in.zeniths != nullptr && in.direct != nullptr &&
-                                                                in.jacobian == nullptr &&
-                                                                grt_zenith_slant_args_ok(in.zenith_slant));
-    // (the surface-temperature Jacobian leaves the same two forms; the shortwave launcher has no such case)
-    bool const jacobian_ok = in.jacobian == nullptr || (in.zeniths == nullptr && in.direct == nullptr &&
-                                                        grt_jacobian_args_ok(in.jacobian) &&
-                                                        (in.out == GRT_OUT_ROWS || in.out == GRT_OUT_LEVELS));
-    // (the response rows leave the level form beside its own: no bins, sun angles or Jacobian with them)
-    bool const responses_ok = in.responses == nullptr || (in.out == GRT_OUT_LEVELS && in.bins == nullptr && in.zeniths == nullptr &&
-                                                          in.jacobian == nullptr && grt_response_args_ok(in.responses));
-    // (the scattering correction: the chain, six-row and level forms, with the cloud and aerosol joins alone)
-    bool const scatter_ok = in.scatter == nullptr || (in.bins == nullptr && in.zeniths == nullptr && in.direct == nullptr &&
-                                                      in.jacobian == nullptr && in.responses == nullptr &&
-                                                      grt_scatter_args_ok(in.scatter) && grt_solver_grid_rows(&in, a.ncol) <= in.scatter->park_rows &&
-                                                      (in.out == GRT_OUT_CHAINS || in.out == GRT_OUT_ROWS || in.out == GRT_OUT_LEVELS));
     // (two grid points for a trapezoid; the chain form of the scattering correction integrates nothing: one will do)
     uint64_t const least_points = in.scatter != nullptr && !fused ? 1 : 2;
-    return zeniths_ok && direct_ok && zenith_surface_ok && zenith_slant_ok && jacobian_ok && responses_ok && scatter_ok && a.ncol >= 1 && a.nw >= least_points && a.num_levels >= 2 &&
-           cloud_forms <= 1 && joined <= (fused ? 2 : 0) && (in.bins != nullptr) == (in.out == GRT_OUT_LEVEL_BINS) &&
+    // (the scattering correction parks per grid row: no more of them than its block holds)
+    bool const scatter_ok = in.scatter == nullptr || (grt_scatter_args_ok(in.scatter) &&
+                                                      grt_solver_grid_rows(&in, a.ncol) <= in.scatter->park_rows);
+    return grt_band_instance_exists(in, a) && scatter_ok && a.ncol >= 1 && a.nw >= least_points && a.num_levels >= 2 &&
            (in.clouds == nullptr || grt_cloud_args_ok(in.clouds)) &&
            (in.aerosols == nullptr || grt_aerosol_args_ok(in.aerosols)) &&
            (in.subcolumns == nullptr || grt_subcolumn_args_ok(in.subcolumns)) &&
            (in.bins == nullptr || grt_band_args_ok(in.bins)) &&
+           (in.zeniths == nullptr || grt_zenith_args_ok(in.zeniths)) &&
+           (in.zenith_surface == nullptr || grt_zenith_surface_args_ok(in.zenith_surface)) &&
+           (in.zenith_slant == nullptr || grt_zenith_slant_args_ok(in.zenith_slant)) &&
+           (in.direct == nullptr || grt_direct_args_ok(in.direct)) &&
+           (in.jacobian == nullptr || grt_jacobian_args_ok(in.jacobian)) &&
+           (in.responses == nullptr || grt_response_args_ok(in.responses)) &&
            (fused ? a.tau_gas != nullptr && a.n_layer != nullptr && a.partials != nullptr : flux_rows) &&
            (in.out != GRT_OUT_ROWS_POINTS || flux_rows) &&
            grt_solver_grid_rows(&in, a.ncol) <= 65535u && grt_solver_lds(&in, a.num_levels) <= 65536;

@@ -37,6 +37,7 @@
 #include <stdint.h>
 #include "../grt_kernels.h"
 #include "optics_dev.h"
+#include "solver_dispatch.h"
 #include "planck_dev.h"
 #include "longwave_dev.h"
 
@@ -911,16 +912,6 @@ int launch(hipStream_t s, GrtSolverInstance const &in, GrtLwArgs const &a, Joins
     return (int)hipGetLastError();
 }
 
-// a six-row or level instance: the one that also leaves the surface-temperature Jacobian (grt_pipeline_run_sky_jacobian's
-// sets and forms) -- third given, a GrtJacobianArgs last in its joins --, or the one without (grt_solver_instance_ok lets
-// a GrtJacobianArgs through with these two outputs alone)
-template <GrtSolverOutput OUT, typename... Joins>
-int launch_third_group(hipStream_t s, GrtSolverInstance const &in, GrtLwArgs const &a, GrtJacobianArgs const *third,
-                       Joins const &...joins)
-{
-    return third != nullptr ? launch<OUT>(s, in, a, joins..., *third) : launch<OUT>(s, in, a, joins...);
-}
-
 // ... and of lw_radiance_kernel: the instance's grid rows, the chunks of angles along z
 template <bool FUSED, typename... Joins>
 int launch_radiances(hipStream_t s, GrtSolverInstance const &in, GrtLwArgs const &a, GrtRadianceArgs const &r,
@@ -978,69 +969,23 @@ extern "C" int grt_launch_ck_lw(void *stream, GrtCkSolveArgs const *a)
 extern "C" int grt_launch_lw(void *stream, GrtSolverInstance const *in, GrtLwArgs const *a)
 {
     uint64_t const cells = (uint64_t)(a->num_levels - 1)*a->nw;
-    if (!grt_solver_instance_ok(*in, *a) || in->direct != nullptr ||        // (the direct beam is the shortwave's)
-        in->scatter != nullptr ||                                           // (grt_launch_lw_scatter's)
+    if (!grt_solver_instance_ok(*in, *a) || in->scatter != nullptr ||       // (grt_launch_lw_scatter's)
         (in->out == GRT_OUT_LAYERS && (a->layer_terms == nullptr || cells > 0xffffffffull*kTermsBlock)))
     {
         return (int)hipErrorInvalidValue;
     }
     hipStream_t const s = (hipStream_t)stream;
-    // the level instances that leave the response rows beside their own (grt_pipeline_run_sky_weighted's sets) ...
-    if (in->responses != nullptr)
+    if (in->out == GRT_OUT_LAYERS)
     {
-        GrtResponseArgs const &r = *in->responses;
-        switch (GRT_INSTANCE(in->out, grt_solver_join(in)))
-        {
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_NONE): return launch<GRT_OUT_LEVELS>(s, *in, *a, r);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, r);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->aerosols, r);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, r);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS_AEROSOLS):
-            return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, *in->aerosols, r);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
-            return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->aerosols, r);
-        default:
-            return (int)hipErrorInvalidValue;
-        }
-    }
-    // ... and every other instance of lw_kernel there is; the six-row and level instances twice, as launch_third_group says
-    GrtJacobianArgs const *const d = in->jacobian;
-    switch (GRT_INSTANCE(in->out, grt_solver_join(in)))
-    {
-    case GRT_INSTANCE(GRT_OUT_LAYERS, GRT_JOIN_NONE):
         hipLaunchKernelGGL(lw_terms_kernel, dim3((unsigned)((cells + kTermsBlock - 1)/kTermsBlock), a->ncol, 1),
                            dim3(kTermsBlock), 0, s, *a);
         hipLaunchKernelGGL(lw_sweeps_kernel, dim3((unsigned)((a->nw + kSweepBlock - 1)/kSweepBlock), a->ncol, 1),
                            dim3(kSweepBlock), 0, s, *a);
         return (int)hipGetLastError();
-    case GRT_INSTANCE(GRT_OUT_CHAINS, GRT_JOIN_NONE): return launch<GRT_OUT_CHAINS>(s, *in, *a);
-    case GRT_INSTANCE(GRT_OUT_ROWS_POINTS, GRT_JOIN_NONE): return launch<GRT_OUT_ROWS_POINTS>(s, *in, *a);
-    case GRT_INSTANCE(GRT_OUT_ROWS_POINTS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_ROWS_POINTS>(s, *in, *a, *in->clouds);
-    case GRT_INSTANCE(GRT_OUT_LEVEL_BINS, GRT_JOIN_NONE): return launch<GRT_OUT_LEVEL_BINS>(s, *in, *a, *in->bins);
-    case GRT_INSTANCE(GRT_OUT_LEVEL_BINS, GRT_JOIN_CLOUDS):
-        return launch<GRT_OUT_LEVEL_BINS>(s, *in, *a, *in->clouds, *in->bins);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_NONE): return launch_third_group<GRT_OUT_ROWS>(s, *in, *a, d);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_NONE): return launch_third_group<GRT_OUT_LEVELS>(s, *in, *a, d);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_CLOUDS): return launch_third_group<GRT_OUT_ROWS>(s, *in, *a, d, *in->clouds);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS): return launch_third_group<GRT_OUT_LEVELS>(s, *in, *a, d, *in->clouds);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_AEROSOLS): return launch_third_group<GRT_OUT_ROWS>(s, *in, *a, d, *in->aerosols);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_AEROSOLS):
-        return launch_third_group<GRT_OUT_LEVELS>(s, *in, *a, d, *in->aerosols);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_SUBCOLUMNS):
-        return launch_third_group<GRT_OUT_ROWS>(s, *in, *a, d, *in->subcolumns);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS):
-        return launch_third_group<GRT_OUT_LEVELS>(s, *in, *a, d, *in->subcolumns);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_CLOUDS_AEROSOLS):
-        return launch_third_group<GRT_OUT_ROWS>(s, *in, *a, d, *in->clouds, *in->aerosols);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS_AEROSOLS):
-        return launch_third_group<GRT_OUT_LEVELS>(s, *in, *a, d, *in->clouds, *in->aerosols);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
-        return launch_third_group<GRT_OUT_ROWS>(s, *in, *a, d, *in->subcolumns, *in->aerosols);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
-        return launch_third_group<GRT_OUT_LEVELS>(s, *in, *a, d, *in->subcolumns, *in->aerosols);
-    default:
-        return (int)hipErrorInvalidValue;
     }
+    // every instance of lw_kernel there is (grt_lw_instance_exists)
+    auto const site = [&](auto, auto out, auto const &...joins) { return launch<decltype(out)::value>(s, *in, *a, joins...); };
+    return grt_launch_output<grt_lw_instance_exists>(in->out, grt_solver_joins(*in), site);
 }
 
 extern "C" int grt_launch_lw_surface_jacobian(void *stream, GrtLwArgs const *a, double *jacobian)
@@ -1070,43 +1015,28 @@ static int launch_lw_radiances(void *stream, GrtSolverInstance const *in, GrtLwA
         return (int)hipErrorInvalidValue;
     }
     hipStream_t const s = (hipStream_t)stream;
-    if (!grt_out_fused(in->out))
-    {
-        // the materialised instance: the pass's tau, omega on the grid
-        if (a->tau == nullptr || grt_solver_join(in) != GRT_JOIN_NONE)
-        {
-            return (int)hipErrorInvalidValue;
-        }
-        if (w != nullptr)
-        {
-            return launch_weighting<false>(s, *in, *a, *r, *c, *w);
-        }
-        return c != nullptr ? launch_radiances<false>(s, *in, *a, *r, *c) : launch_radiances<false>(s, *in, *a, *r);
-    }
-    if (a->tau_gas == nullptr || a->n_layer == nullptr)
+    // (the materialised instance reads the pass's tau, omega on the grid; bins, zeniths, direct and jacobian are not read)
+    GrtSolverInstance const front = {in->out, in->clouds, in->aerosols, in->subcolumns};
+    if (grt_out_fused(in->out) ? a->tau_gas == nullptr || a->n_layer == nullptr : a->tau == nullptr)
     {
         return (int)hipErrorInvalidValue;
     }
-    auto fused = [&](auto const &...joins) -> int
+    // every instance of lw_radiance_kernel there is, c last in its joins where given, and of lw_weighting_kernel
+    // (grt_lw_radiance_instance_exists)
+    auto const launch_form = [&](auto fused) -> int
     {
+        constexpr bool FUSED = decltype(fused)::value;
         if (w != nullptr)
         {
-            return launch_weighting<true>(s, *in, *a, *r, *c, *w, joins...);
+            auto const site = [&](auto, auto, auto const &...joins)
+            { return launch_weighting<FUSED>(s, *in, *a, *r, *c, *w, joins...); };
+            return grt_launch_joined<grt_lw_radiance_instance_exists, FUSED>(grt_solver_joins(front), site);
         }
-        return c != nullptr ? launch_radiances<true>(s, *in, *a, *r, joins..., *c) : launch_radiances<true>(s, *in, *a, *r, joins...);
+        auto const site = [&](auto, auto, auto const &...joins) { return launch_radiances<FUSED>(s, *in, *a, *r, joins...); };
+        return grt_launch_joined<grt_lw_radiance_instance_exists, FUSED>(std::tuple_cat(grt_solver_joins(front), std::make_tuple(c)),
+                                                                         site);
     };
-    // every fused instance of lw_radiance_kernel there is: one per join, and its channel form; and of lw_weighting_kernel
-    switch (grt_solver_join(in))
-    {
-    case GRT_JOIN_NONE: return fused();
-    case GRT_JOIN_CLOUDS: return fused(*in->clouds);
-    case GRT_JOIN_AEROSOLS: return fused(*in->aerosols);
-    case GRT_JOIN_SUBCOLUMNS: return fused(*in->subcolumns);
-    case GRT_JOIN_CLOUDS_AEROSOLS: return fused(*in->clouds, *in->aerosols);
-    case GRT_JOIN_SUBCOLUMNS_AEROSOLS: return fused(*in->subcolumns, *in->aerosols);
-    default:
-        return (int)hipErrorInvalidValue;
-    }
+    return grt_out_fused(in->out) ? launch_form(std::true_type{}) : launch_form(std::false_type{});
 }
 
 extern "C" int grt_launch_lw_radiances(void *stream, GrtSolverInstance const *in, GrtLwArgs const *a, GrtRadianceArgs const *r)
@@ -1165,31 +1095,22 @@ extern "C" int grt_launch_weighting_finish(void *stream, GrtChannelArgs const *c
 
 extern "C" int grt_tile_chunk(GrtSubcolumnArgs const *sc, GrtAerosolArgs const *ae)
 {
-    return sc != nullptr ? (ae != nullptr ? GRT_TILE_CHUNK_SUBCOLUMNS_AEROSOLS : GRT_TILE_CHUNK_SUBCOLUMNS) :
-           (ae != nullptr ? GRT_TILE_CHUNK_AEROSOLS : GRT_TILE_CHUNK);
+    GrtSolverInstance const joined = {GRT_OUT_ROWS, nullptr, ae, sc};
+    return grt_tile_chunk_of(grt_join_set(grt_solver_joins(joined)));
 }
 
 extern "C" int grt_launch_lw_tiles(void *stream, GrtLwArgs const *a, GrtTileArgs const *t, GrtSubcolumnArgs const *sc,
                                    GrtAerosolArgs const *ae)
 {
-    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    GrtSolverInstance const in = {GRT_OUT_ROWS}, joined = {GRT_OUT_ROWS, nullptr, ae, sc};
     if (a == nullptr || t == nullptr || !grt_solver_instance_ok(in, *a) || a->t_layers == nullptr || a->t_levels == nullptr ||
         a->emis == nullptr || (sc != nullptr && !grt_subcolumn_args_ok(sc)) || (ae != nullptr && !grt_aerosol_args_ok(ae)))
     {
         return (int)hipErrorInvalidValue;
     }
     hipStream_t const s = (hipStream_t)stream;
-    if (sc != nullptr && ae != nullptr)
-    {
-        return launch_tiles<GRT_TILE_CHUNK_SUBCOLUMNS_AEROSOLS>(s, *a, *t, sc->count, *sc, *ae);
-    }
-    if (sc != nullptr)
-    {
-        return launch_tiles<GRT_TILE_CHUNK_SUBCOLUMNS>(s, *a, *t, sc->count, *sc);
-    }
-    if (ae != nullptr)
-    {
-        return launch_tiles<GRT_TILE_CHUNK_AEROSOLS>(s, *a, *t, 1, *ae);
-    }
-    return launch_tiles<GRT_TILE_CHUNK>(s, *a, *t, 1);
+    int const draws = sc != nullptr ? sc->count : 1;
+    auto const site = [&](auto set, auto const &...joins)
+    { return launch_tiles<grt_tile_chunk_of(decltype(set)::value)>(s, *a, *t, draws, joins...); };
+    return grt_launch_joined<grt_tile_instance_exists>(grt_solver_joins(joined), site);
 }

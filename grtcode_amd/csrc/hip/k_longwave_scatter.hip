@@ -40,6 +40,7 @@
 #include <stdint.h>
 #include "../grt_kernels.h"
 #include "optics_dev.h"
+#include "solver_dispatch.h"
 #include "planck_dev.h"
 #include "longwave_dev.h"
 
@@ -218,29 +219,9 @@ extern "C" int grt_launch_lw_scatter(void *stream, GrtSolverInstance const *in, 
         return (int)hipErrorInvalidValue;
     }
     hipStream_t const s = (hipStream_t)stream;
-    // every instance of lw_scatter_kernel there is
-    switch (GRT_INSTANCE(in->out, grt_solver_join(in)))
-    {
-    case GRT_INSTANCE(GRT_OUT_CHAINS, GRT_JOIN_NONE): return launch<GRT_OUT_CHAINS>(s, *in, *a);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_NONE): return launch<GRT_OUT_ROWS>(s, *in, *a);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_NONE): return launch<GRT_OUT_LEVELS>(s, *in, *a);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->clouds);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->aerosols);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->aerosols);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_CLOUDS_AEROSOLS):
-        return launch<GRT_OUT_ROWS>(s, *in, *a, *in->clouds, *in->aerosols);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS_AEROSOLS):
-        return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, *in->aerosols);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
-        return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns, *in->aerosols);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
-        return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->aerosols);
-    default:
-        return (int)hipErrorInvalidValue;
-    }
+    // every instance of lw_scatter_kernel there is (grt_lw_scatter_instance_exists)
+    auto const site = [&](auto, auto out, auto const &...joins) { return launch<decltype(out)::value>(s, *in, *a, joins...); };
+    return grt_launch_output<grt_lw_scatter_instance_exists>(in->out, grt_solver_joins(*in), site);
 }
 
 extern "C" int grt_launch_scatter_add(void *stream, int n, int rows, double *corrected, uint64_t out_stride,

@@ -17,16 +17,11 @@
 // not HBM-bound.  The fused six-row clear-sky instance, the production pipeline's, therefore trades bytes for flops: its
 // first sweep parks the five properties of every layer with the reflectances and its second sweep reads them back (the
 // same doubles: identical fluxes) -- 0.69 instead of 1.04 ms for 8 columns, at 4.2 TB/s.  sw_kernel has one instance per
-// GrtSolverInstance that exists (grt_kernels.h; the list is in grt_launch_sw): what leaves it is its OUT -- spectral
-// fluxes (GRT_OUT_CHAINS), or, fused, the partial sums of the six rows, of the six rows that are also stored at every
-// point, of every level, or of every level per wavenumber bin -- and what joins gas and Rayleigh is the types of its
-// pack: nothing, GrtCloudArgs, GrtAerosolArgs or GrtSubcolumnArgs, a GrtAerosolArgs behind either form of the clouds where
-// both join, a GrtBandArgs last where OUT is per bin, or a GrtZenithArgs (several sun angles per column: alone, or last
-// behind a GrtAerosolArgs, a GrtSubcolumnArgs or both, six rows or every level); a GrtDirectArgs last (six rows or every level, with any of the cloud and aerosol joins) makes the instance that also
-// leaves the direct beam of its sweep (LevelSink: DIRECT).  Behind a GrtZenithArgs a GrtZenithSurfaceArgs (every angle's own
-// direct albedo: row_alb_dir), a GrtDirectArgs or both may follow (grt_pipeline_run_sky_zeniths_direct); with the GrtDirectArgs a
-// GrtZenithSlantArgs ahead of it (a sun cosine per layer for the direct beam: layer_mu; grt_pipeline_run_sky_zeniths_slant).
-// sw_tile_kernel, behind sw_zenith_kernel, is the six-row instance for several surface tiles per column
+// GrtSolverInstance that exists: what leaves it is its OUT, and what joins gas and Rayleigh or rides with them is the types
+// of its pack, in the order of the GRT_JOIN_ bits.  Which instances exist is grt_sw_instance_exists' rule (grt_kernels.h),
+// and grt_launch_joined (solver_dispatch.h) takes a launch from the pointers that are set to the kernel's pack.
+// sw_zenith_kernel is the six-row instance for several sun angles per column on shared layer properties
+// (grt_launch_sw_zeniths), and sw_tile_kernel, behind it, the six-row instance for several surface tiles per column
 // (grt_launch_sw_tiles): the layer properties once for a chunk of tiles, what reads the albedo per tile.
 // The in-kernel range checks of the reference are no-ops on device builds
 // (debug.h:105-116) and are not restated.
@@ -35,6 +30,7 @@
 #include <stdint.h>
 #include "../grt_kernels.h"
 #include "optics_dev.h"
+#include "solver_dispatch.h"
 #include "exp_pair.h"
 
 #pragma clang fp contract(off)
@@ -1079,29 +1075,32 @@ int launch(hipStream_t s, GrtSolverInstance const &in, GrtSwArgs const &a, Joins
     return (int)hipGetLastError();
 }
 
-// the zenith instance of OUT behind the joins `front` that also leaves every angle's direct beam (a GrtDirectArgs last),
-// reads every angle's own direct albedo (a GrtZenithSurfaceArgs behind the GrtZenithArgs) or both
-template <GrtSolverOutput OUT, typename... Front>
-int launch_zenith_forms(hipStream_t s, GrtSolverInstance const &in, GrtSwArgs const &a, Front const &...front)
+// ... of sw_zenith_kernel: ZN angles per thread, grid row = (column, draw of the launch, chunk)
+template <int ZN, typename... Joins>
+int launch_zeniths(hipStream_t s, GrtSwArgs const &a, GrtZenithArgs const &z, int draws, Joins const &...joins)
 {
-    if (in.zenith_surface != nullptr && in.direct != nullptr)
+    uint64_t const rows = (uint64_t)a.ncol*(uint64_t)draws*(uint64_t)((z.zeniths + ZN - 1)/ZN);
+    if (rows > 65535u)
     {
-        return launch<OUT>(s, in, a, front..., *in.zeniths, *in.zenith_surface, *in.direct);
+        return (int)hipErrorInvalidValue;
     }
-    if (in.zenith_surface != nullptr)
-    {
-        return launch<OUT>(s, in, a, front..., *in.zeniths, *in.zenith_surface);
-    }
-    return launch<OUT>(s, in, a, front..., *in.zeniths, *in.direct);
+    hipLaunchKernelGGL((sw_zenith_kernel<ZN, Joins...>), dim3(grt_solver_blocks(a.nw), (unsigned)rows, 1),
+                       dim3(kSolverBlock), 0, s, a, z, joins...);
+    return (int)hipGetLastError();
 }
 
-// the zenith instances whose direct beam reads a cosine per layer (grt_pipeline_run_sky_zeniths_slant), of sw_kernel and of
-// the shared-layer kernel: named at the end of this file, so that they are instantiated behind every instance that was
-// here before them
-int launch_slant(hipStream_t s, GrtSolverInstance const &in, GrtSwArgs const &a);
-int launch_zeniths_slant(hipStream_t s, GrtSwArgs const &a, GrtZenithArgs const &z, GrtSubcolumnArgs const *sc,
-                         GrtAerosolArgs const *ae, GrtDirectArgs const &d, GrtZenithSurfaceArgs const *zs,
-                         GrtZenithSlantArgs const &sl);
+// ... and of sw_tile_kernel: TN tiles per thread, the six-row instance's grid rows, the launch's chunks along z
+template <int TN, typename... Joins>
+int launch_tiles(hipStream_t s, GrtSwArgs const &a, GrtTileArgs const &t, int draws, Joins const &...joins)
+{
+    if (!grt_tile_args_ok(&t, TN) || (uint64_t)a.ncol*(uint64_t)draws > 65535u || t.chunk_count > 65535)
+    {
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL((sw_tile_kernel<TN, Joins...>), dim3(grt_solver_blocks(a.nw), (unsigned)(a.ncol*draws), (unsigned)t.chunk_count),
+                       dim3(kSolverBlock), 0, s, a, t, joins...);
+    return (int)hipGetLastError();
+}
 
 } // namespace
 
@@ -1120,174 +1119,39 @@ extern "C" int grt_launch_ck_sw(void *stream, GrtCkSolveArgs const *a)
 extern "C" int grt_launch_sw(void *stream, GrtSolverInstance const *in, GrtSwArgs const *a)
 {
     uint64_t const cells = (uint64_t)(a->num_levels - 1)*a->nw;
-    if (!grt_solver_instance_ok(*in, *a) || in->jacobian != nullptr ||      // (the surface-temperature Jacobian is the longwave's)
-        in->scatter != nullptr ||                                           // (the scattering correction too)
-        (grt_sw_parks(in, a) && a->park == nullptr) ||
+    if (!grt_solver_instance_ok(*in, *a) || (grt_sw_parks(in, a) && a->park == nullptr) ||
         (in->out == GRT_OUT_LAYERS && (a->layer_props == nullptr || cells > 0xffffffffull*kPropsBlock ||
                                        a->omega == nullptr || a->g == nullptr)))
     {
         return (int)hipErrorInvalidValue;
     }
     hipStream_t const s = (hipStream_t)stream;
-    // the level instances that leave the response rows beside their own and the direct beam's (grt_pipeline_run_sky_weighted's
-    // sets) ...
-    if (in->responses != nullptr)
+    if (in->out == GRT_OUT_LAYERS)
     {
-        if (in->direct == nullptr)
-        {
-            return (int)hipErrorInvalidValue;
-        }
-        GrtDirectArgs const &d = *in->direct;
-        GrtResponseArgs const &r = *in->responses;
-        switch (GRT_INSTANCE(in->out, grt_solver_join(in)))
-        {
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_NONE): return launch<GRT_OUT_LEVELS>(s, *in, *a, d, r);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, d, r);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->aerosols, d, r);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, d, r);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS_AEROSOLS):
-            return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, *in->aerosols, d, r);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
-            return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->aerosols, d, r);
-        default:
-            return (int)hipErrorInvalidValue;
-        }
-    }
-    // the zenith instances whose direct beam reads a cosine per layer (grt_pipeline_run_sky_zeniths_slant's sets and forms) ...
-    if (in->zenith_slant != nullptr)
-    {
-        return launch_slant(s, *in, *a);
-    }
-    // the zenith instances that also leave the direct beam, read every angle's own direct albedo or both
-    // (grt_pipeline_run_sky_zeniths_direct's sets and forms: three instances a case, launch_zenith_forms) ...
-    if (in->zeniths != nullptr && (in->direct != nullptr || in->zenith_surface != nullptr))
-    {
-        switch (GRT_INSTANCE(in->out, grt_solver_join(in)))
-        {
-        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS): return launch_zenith_forms<GRT_OUT_ROWS>(s, *in, *a);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS): return launch_zenith_forms<GRT_OUT_LEVELS>(s, *in, *a);
-        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS_AEROSOLS):
-            return launch_zenith_forms<GRT_OUT_ROWS>(s, *in, *a, *in->aerosols);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS_AEROSOLS):
-            return launch_zenith_forms<GRT_OUT_LEVELS>(s, *in, *a, *in->aerosols);
-        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS_SUBCOLUMNS):
-            return launch_zenith_forms<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS_SUBCOLUMNS):
-            return launch_zenith_forms<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns);
-        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS_SUBCOLUMNS_AEROSOLS):
-            return launch_zenith_forms<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns, *in->aerosols);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS_SUBCOLUMNS_AEROSOLS):
-            return launch_zenith_forms<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->aerosols);
-        default:
-            return (int)hipErrorInvalidValue;
-        }
-    }
-    // every instance of sw_kernel that also leaves the direct beam (grt_pipeline_run_sky_direct's sets and forms) ...
-    if (in->direct != nullptr)
-    {
-        GrtDirectArgs const &d = *in->direct;
-        switch (GRT_INSTANCE(in->out, grt_solver_join(in)))
-        {
-        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_NONE): return launch<GRT_OUT_ROWS>(s, *in, *a, d);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_NONE): return launch<GRT_OUT_LEVELS>(s, *in, *a, d);
-        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->clouds, d);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, d);
-        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->aerosols, d);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->aerosols, d);
-        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns, d);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, d);
-        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_CLOUDS_AEROSOLS):
-            return launch<GRT_OUT_ROWS>(s, *in, *a, *in->clouds, *in->aerosols, d);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS_AEROSOLS):
-            return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, *in->aerosols, d);
-        case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
-            return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns, *in->aerosols, d);
-        case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
-            return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->aerosols, d);
-        default:
-            return (int)hipErrorInvalidValue;
-        }
-    }
-    // ... and every other instance of sw_kernel there is
-    switch (GRT_INSTANCE(in->out, grt_solver_join(in)))
-    {
-    case GRT_INSTANCE(GRT_OUT_LAYERS, GRT_JOIN_NONE):
         hipLaunchKernelGGL(sw_props_kernel, dim3((unsigned)((cells + kPropsBlock - 1)/kPropsBlock), a->ncol, 1),
                            dim3(kPropsBlock), 0, s, *a);
         hipLaunchKernelGGL(sw_sweeps_kernel, dim3((unsigned)((a->nw + kSweepBlock - 1)/kSweepBlock), a->ncol, 1),
                            dim3(kSweepBlock), 0, s, *a);
         return (int)hipGetLastError();
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_NONE): return launch<GRT_OUT_ROWS>(s, *in, *a);
-    case GRT_INSTANCE(GRT_OUT_CHAINS, GRT_JOIN_NONE): return launch<GRT_OUT_CHAINS>(s, *in, *a);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_NONE): return launch<GRT_OUT_LEVELS>(s, *in, *a);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->clouds);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds);
-    case GRT_INSTANCE(GRT_OUT_ROWS_POINTS, GRT_JOIN_NONE): return launch<GRT_OUT_ROWS_POINTS>(s, *in, *a);
-    case GRT_INSTANCE(GRT_OUT_ROWS_POINTS, GRT_JOIN_CLOUDS): return launch<GRT_OUT_ROWS_POINTS>(s, *in, *a, *in->clouds);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->aerosols);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_AEROSOLS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->aerosols);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_SUBCOLUMNS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns);
-    case GRT_INSTANCE(GRT_OUT_LEVEL_BINS, GRT_JOIN_CLOUDS):
-        return launch<GRT_OUT_LEVEL_BINS>(s, *in, *a, *in->clouds, *in->bins);
-    case GRT_INSTANCE(GRT_OUT_LEVEL_BINS, GRT_JOIN_NONE): return launch<GRT_OUT_LEVEL_BINS>(s, *in, *a, *in->bins);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_CLOUDS_AEROSOLS):
-        return launch<GRT_OUT_ROWS>(s, *in, *a, *in->clouds, *in->aerosols);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_CLOUDS_AEROSOLS):
-        return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->clouds, *in->aerosols);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
-        return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns, *in->aerosols);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_SUBCOLUMNS_AEROSOLS):
-        return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->aerosols);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS): return launch<GRT_OUT_ROWS>(s, *in, *a, *in->zeniths);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS): return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->zeniths);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS_AEROSOLS):
-        return launch<GRT_OUT_ROWS>(s, *in, *a, *in->aerosols, *in->zeniths);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS_AEROSOLS):
-        return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->aerosols, *in->zeniths);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS_SUBCOLUMNS):
-        return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns, *in->zeniths);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS_SUBCOLUMNS):
-        return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->zeniths);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS_SUBCOLUMNS_AEROSOLS):
-        return launch<GRT_OUT_ROWS>(s, *in, *a, *in->subcolumns, *in->aerosols, *in->zeniths);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS_SUBCOLUMNS_AEROSOLS):
-        return launch<GRT_OUT_LEVELS>(s, *in, *a, *in->subcolumns, *in->aerosols, *in->zeniths);
-    default:
-        return (int)hipErrorInvalidValue;
     }
+    // every instance of sw_kernel there is (grt_sw_instance_exists)
+    auto const site = [&](auto, auto out, auto const &...joins) { return launch<decltype(out)::value>(s, *in, *a, joins...); };
+    return grt_launch_output<grt_sw_instance_exists>(in->out, grt_solver_joins(*in), site);
 }
 
 namespace {
 
-// the one launch site of sw_zenith_kernel: ZN angles per thread, grid row = (column, draw of the launch, chunk)
-template <int ZN, typename... Joins>
-int launch_zeniths(hipStream_t s, GrtSwArgs const &a, GrtZenithArgs const &z, int draws, Joins const &...joins)
+// the joins of a shared-layer or a tile launch as an instance's (its GrtZenithArgs or GrtTileArgs is a parameter of its own)
+GrtSolverInstance joined(GrtSubcolumnArgs const *sc, GrtAerosolArgs const *ae, GrtDirectArgs const *d = nullptr,
+                         GrtZenithSurfaceArgs const *zs = nullptr, GrtZenithSlantArgs const *sl = nullptr)
 {
-    uint64_t const rows = (uint64_t)a.ncol*(uint64_t)draws*(uint64_t)((z.zeniths + ZN - 1)/ZN);
-    if (rows > 65535u)
-    {
-        return (int)hipErrorInvalidValue;
-    }
-    hipLaunchKernelGGL((sw_zenith_kernel<ZN, Joins...>), dim3(grt_solver_blocks(a.nw), (unsigned)rows, 1),
-                       dim3(kSolverBlock), 0, s, a, z, joins...);
-    return (int)hipGetLastError();
-}
-
-// ... of the instance behind the joins `front` that leaves the direct beam, reads every angle's own albedo or both
-template <typename... Front>
-int launch_zenith_forms(hipStream_t s, GrtSwArgs const &a, GrtZenithArgs const &z, int draws, GrtDirectArgs const *d,
-                        GrtZenithSurfaceArgs const *zs, Front const &...front)
-{
-    if (d != nullptr && zs != nullptr)
-    {
-        return launch_zeniths<GRT_ZENITH_CHUNK_DIRECT_SURFACE>(s, a, z, draws, front..., *zs, *d);
-    }
-    if (zs != nullptr)
-    {
-        return launch_zeniths<GRT_ZENITH_CHUNK_SURFACE>(s, a, z, draws, front..., *zs);
-    }
-    return launch_zeniths<GRT_ZENITH_CHUNK_DIRECT>(s, a, z, draws, front..., *d);
+    GrtSolverInstance in = {GRT_OUT_ROWS};
+    in.subcolumns = sc;
+    in.aerosols = ae;
+    in.direct = d;
+    in.zenith_surface = zs;
+    in.zenith_slant = sl;
+    return in;
 }
 
 } // namespace
@@ -1295,110 +1159,43 @@ int launch_zenith_forms(hipStream_t s, GrtSwArgs const &a, GrtZenithArgs const &
 extern "C" int grt_zenith_chunk(GrtSubcolumnArgs const *sc, GrtAerosolArgs const *ae, GrtDirectArgs const *d,
                                 GrtZenithSurfaceArgs const *zs, GrtZenithSlantArgs const *sl)
 {
-    if (sl != nullptr)
-    {
-        return zs != nullptr ? GRT_ZENITH_CHUNK_SLANT_SURFACE : GRT_ZENITH_CHUNK_SLANT;
-    }
-    if (d != nullptr || zs != nullptr)
-    {
-        return d != nullptr ? (zs != nullptr ? GRT_ZENITH_CHUNK_DIRECT_SURFACE : GRT_ZENITH_CHUNK_DIRECT) : GRT_ZENITH_CHUNK_SURFACE;
-    }
-    return sc != nullptr ? (ae != nullptr ? GRT_ZENITH_CHUNK_SUBCOLUMNS_AEROSOLS : GRT_ZENITH_CHUNK_SUBCOLUMNS) :
-           (ae != nullptr ? GRT_ZENITH_CHUNK_AEROSOLS : GRT_ZENITH_CHUNK);
+    return grt_zenith_chunk_of(grt_join_set(grt_solver_joins(joined(sc, ae, d, zs, sl))));
 }
 
 extern "C" int grt_launch_sw_zeniths(void *stream, GrtSwArgs const *a, GrtZenithArgs const *z, GrtSubcolumnArgs const *sc,
                                      GrtAerosolArgs const *ae, GrtDirectArgs const *d, GrtZenithSurfaceArgs const *zs,
                                      GrtZenithSlantArgs const *sl)
 {
-    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                  nullptr, nullptr};
+    GrtSolverInstance const in = {GRT_OUT_ROWS};
     if (!grt_solver_instance_ok(in, *a) || z == nullptr || z->mu == nullptr || z->zeniths < 1 || !grt_sw_one_sweep(a) ||
         (sc != nullptr && !grt_subcolumn_args_ok(sc)) || (ae != nullptr && !grt_aerosol_args_ok(ae)) ||
         (d != nullptr && !grt_direct_args_ok(d)) || (zs != nullptr && !grt_zenith_surface_args_ok(zs)) ||
-        (sl != nullptr && (!grt_zenith_slant_args_ok(sl) || d == nullptr)))
+        (sl != nullptr && !grt_zenith_slant_args_ok(sl)))
     {
         return (int)hipErrorInvalidValue;
     }
     hipStream_t const s = (hipStream_t)stream;
-    // the instances whose direct beam reads a cosine per layer, behind each join ...
-    if (sl != nullptr)
-    {
-        return launch_zeniths_slant(s, *a, *z, sc, ae, *d, zs, *sl);
-    }
-    // the instances that also leave the direct beam, read every angle's own direct albedo or both, behind each join ...
-    if (d != nullptr || zs != nullptr)
-    {
-        if (sc != nullptr && ae != nullptr)
-        {
-            return launch_zenith_forms(s, *a, *z, sc->count, d, zs, *sc, *ae);
-        }
-        if (sc != nullptr)
-        {
-            return launch_zenith_forms(s, *a, *z, sc->count, d, zs, *sc);
-        }
-        if (ae != nullptr)
-        {
-            return launch_zenith_forms(s, *a, *z, 1, d, zs, *ae);
-        }
-        return launch_zenith_forms(s, *a, *z, 1, d, zs);
-    }
-    // ... and the four without
-    if (sc != nullptr && ae != nullptr)
-    {
-        return launch_zeniths<GRT_ZENITH_CHUNK_SUBCOLUMNS_AEROSOLS>(s, *a, *z, sc->count, *sc, *ae);
-    }
-    if (sc != nullptr)
-    {
-        return launch_zeniths<GRT_ZENITH_CHUNK_SUBCOLUMNS>(s, *a, *z, sc->count, *sc);
-    }
-    if (ae != nullptr)
-    {
-        return launch_zeniths<GRT_ZENITH_CHUNK_AEROSOLS>(s, *a, *z, 1, *ae);
-    }
-    return launch_zeniths<GRT_ZENITH_CHUNK>(s, *a, *z, 1);
+    int const draws = sc != nullptr ? sc->count : 1;
+    // every instance of sw_zenith_kernel there is (grt_sw_zenith_instance_exists: a cosine per layer needs the direct beam)
+    auto const site = [&](auto set, auto const &...joins)
+    { return launch_zeniths<grt_zenith_chunk_of(decltype(set)::value)>(s, *a, *z, draws, joins...); };
+    return grt_launch_joined<grt_sw_zenith_instance_exists>(grt_solver_joins(joined(sc, ae, d, zs, sl)), site);
 }
-
-namespace {
-
-// the one launch site of sw_tile_kernel: TN tiles per thread, the six-row instance's grid rows, the launch's chunks along z
-template <int TN, typename... Joins>
-int launch_tiles(hipStream_t s, GrtSwArgs const &a, GrtTileArgs const &t, int draws, Joins const &...joins)
-{
-    if (!grt_tile_args_ok(&t, TN) || (uint64_t)a.ncol*(uint64_t)draws > 65535u || t.chunk_count > 65535)
-    {
-        return (int)hipErrorInvalidValue;
-    }
-    hipLaunchKernelGGL((sw_tile_kernel<TN, Joins...>), dim3(grt_solver_blocks(a.nw), (unsigned)(a.ncol*draws), (unsigned)t.chunk_count),
-                       dim3(kSolverBlock), 0, s, a, t, joins...);
-    return (int)hipGetLastError();
-}
-
-} // namespace
 
 extern "C" int grt_launch_sw_tiles(void *stream, GrtSwArgs const *a, GrtTileArgs const *t, GrtSubcolumnArgs const *sc,
                                    GrtAerosolArgs const *ae)
 {
-    GrtSolverInstance const in = {GRT_OUT_ROWS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    GrtSolverInstance const in = {GRT_OUT_ROWS};
     if (a == nullptr || t == nullptr || !grt_solver_instance_ok(in, *a) || (!grt_sw_one_sweep(a) && a->park == nullptr) ||
         (sc != nullptr && !grt_subcolumn_args_ok(sc)) || (ae != nullptr && !grt_aerosol_args_ok(ae)))
     {
         return (int)hipErrorInvalidValue;
     }
     hipStream_t const s = (hipStream_t)stream;
-    if (sc != nullptr && ae != nullptr)
-    {
-        return launch_tiles<GRT_TILE_CHUNK_SUBCOLUMNS_AEROSOLS>(s, *a, *t, sc->count, *sc, *ae);
-    }
-    if (sc != nullptr)
-    {
-        return launch_tiles<GRT_TILE_CHUNK_SUBCOLUMNS>(s, *a, *t, sc->count, *sc);
-    }
-    if (ae != nullptr)
-    {
-        return launch_tiles<GRT_TILE_CHUNK_AEROSOLS>(s, *a, *t, 1, *ae);
-    }
-    return launch_tiles<GRT_TILE_CHUNK>(s, *a, *t, 1);
+    int const draws = sc != nullptr ? sc->count : 1;
+    auto const site = [&](auto set, auto const &...joins)
+    { return launch_tiles<grt_tile_chunk_of(decltype(set)::value)>(s, *a, *t, draws, joins...); };
+    return grt_launch_joined<grt_tile_instance_exists>(grt_solver_joins(joined(sc, ae)), site);
 }
 
 extern "C" int grt_launch_sw_direct_beam(void *stream, GrtSwArgs const *a, double *direct)
@@ -1424,77 +1221,3 @@ extern "C" int grt_launch_direct_rows(void *stream, int n, int num_levels, int u
                        user_level, levels, rows);
     return (int)hipGetLastError();
 }
-
-namespace {
-
-// ---- a sun cosine per layer for the direct beam (GrtZenithSlantArgs): the launch sites of its instances ----
-// A slant instance always carries the direct beam (a GrtDirectArgs last), with every angle's own direct albedo (a
-// GrtZenithSurfaceArgs behind the GrtZenithArgs) or without.
-
-// ... of sw_kernel, OUT behind the joins `front`
-template <GrtSolverOutput OUT, typename... Front>
-int launch_slant_forms(hipStream_t s, GrtSolverInstance const &in, GrtSwArgs const &a, Front const &...front)
-{
-    if (in.zenith_surface != nullptr)
-    {
-        return launch<OUT>(s, in, a, front..., *in.zeniths, *in.zenith_surface, *in.zenith_slant, *in.direct);
-    }
-    return launch<OUT>(s, in, a, front..., *in.zeniths, *in.zenith_slant, *in.direct);
-}
-
-int launch_slant(hipStream_t s, GrtSolverInstance const &in, GrtSwArgs const &a)
-{
-    if (in.zeniths == nullptr || in.direct == nullptr)
-    {
-        return (int)hipErrorInvalidValue;
-    }
-    switch (GRT_INSTANCE(in.out, grt_solver_join(&in)))
-    {
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS): return launch_slant_forms<GRT_OUT_ROWS>(s, in, a);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS): return launch_slant_forms<GRT_OUT_LEVELS>(s, in, a);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS_AEROSOLS): return launch_slant_forms<GRT_OUT_ROWS>(s, in, a, *in.aerosols);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS_AEROSOLS): return launch_slant_forms<GRT_OUT_LEVELS>(s, in, a, *in.aerosols);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS_SUBCOLUMNS): return launch_slant_forms<GRT_OUT_ROWS>(s, in, a, *in.subcolumns);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS_SUBCOLUMNS):
-        return launch_slant_forms<GRT_OUT_LEVELS>(s, in, a, *in.subcolumns);
-    case GRT_INSTANCE(GRT_OUT_ROWS, GRT_JOIN_ZENITHS_SUBCOLUMNS_AEROSOLS):
-        return launch_slant_forms<GRT_OUT_ROWS>(s, in, a, *in.subcolumns, *in.aerosols);
-    case GRT_INSTANCE(GRT_OUT_LEVELS, GRT_JOIN_ZENITHS_SUBCOLUMNS_AEROSOLS):
-        return launch_slant_forms<GRT_OUT_LEVELS>(s, in, a, *in.subcolumns, *in.aerosols);
-    default:
-        return (int)hipErrorInvalidValue;
-    }
-}
-
-// ... of sw_zenith_kernel behind the joins `front`
-template <typename... Front>
-int launch_zeniths_slant_forms(hipStream_t s, GrtSwArgs const &a, GrtZenithArgs const &z, int draws, GrtDirectArgs const &d,
-                               GrtZenithSurfaceArgs const *zs, GrtZenithSlantArgs const &sl, Front const &...front)
-{
-    if (zs != nullptr)
-    {
-        return launch_zeniths<GRT_ZENITH_CHUNK_SLANT_SURFACE>(s, a, z, draws, front..., *zs, sl, d);
-    }
-    return launch_zeniths<GRT_ZENITH_CHUNK_SLANT>(s, a, z, draws, front..., sl, d);
-}
-
-int launch_zeniths_slant(hipStream_t s, GrtSwArgs const &a, GrtZenithArgs const &z, GrtSubcolumnArgs const *sc,
-                         GrtAerosolArgs const *ae, GrtDirectArgs const &d, GrtZenithSurfaceArgs const *zs,
-                         GrtZenithSlantArgs const &sl)
-{
-    if (sc != nullptr && ae != nullptr)
-    {
-        return launch_zeniths_slant_forms(s, a, z, sc->count, d, zs, sl, *sc, *ae);
-    }
-    if (sc != nullptr)
-    {
-        return launch_zeniths_slant_forms(s, a, z, sc->count, d, zs, sl, *sc);
-    }
-    if (ae != nullptr)
-    {
-        return launch_zeniths_slant_forms(s, a, z, 1, d, zs, sl, *ae);
-    }
-    return launch_zeniths_slant_forms(s, a, z, 1, d, zs, sl);
-}
-
-} // namespace
