@@ -308,7 +308,7 @@ create_solar_flux destroy_solar_flux disort_shortwave
 grt_tips_load grt_tips_reset grt_tips_is_table grt_tips_source grt_sizeof grt_add_molecule_lines grt_gas_optics_tune grt_gas_optics_last_launch grt_hitran_index_stats
 grt_optical_depth_batch grt_pipeline_create grt_pipeline_create_ex grt_pipeline_destroy grt_pipeline_run grt_pipeline_sync
 grt_pipeline_stream grt_pipeline_views grt_pipeline_run_profiles grt_pipeline_run_allsky grt_pipeline_run_allsky_profiles grt_pipeline_run_spectral grt_pipeline_run_subcolumns grt_pipeline_run_cloud_fields grt_cloud_sampler_create grt_cloud_sampler_destroy grt_cloud_sampler_run grt_pipeline_run_aerosols grt_pipeline_run_sky grt_pipeline_run_sky_direct grt_pipeline_run_sky_jacobian grt_pipeline_run_sky_radiances grt_pipeline_run_sky_channels grt_channel_pair_count grt_pipeline_run_sky_weighting grt_pipeline_run_sky_weighted grt_response_pair_count grt_pipeline_response_block_limit grt_pipeline_run_sky_zeniths grt_pipeline_run_sky_zeniths_direct grt_zenith_surface_tables grt_pipeline_run_sky_zeniths_slant grt_slant_cosines grt_pipeline_run_sky_tiles grt_pipeline_sky_set_count grt_pipeline_run_band_profiles grt_pipeline_band_profile_bin_limit grt_kdist_rows grt_pipeline_run_kdist grt_kdist_chunk_points grt_kdist_class_map grt_kdist_mapped_rows grt_pipeline_run_kdist_correlated grt_pipeline_run_ck_fluxes grt_pipeline_run_sky_scattering grt_lw_scatter_levels grt_pipeline_set_surface grt_pipeline_run_zeniths grt_device_malloc grt_device_free grt_device_to_host
-grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_voigt_points grt_debug_device_math grt_debug_line_strengths grt_profile_enable grt_profile_read
+grt_host_to_device grt_debug_line_prep grt_debug_partition_functions grt_debug_tile_items grt_debug_voigt grt_debug_voigt_points grt_debug_device_math grt_debug_line_strengths grt_debug_pipeline_holdings grt_profile_enable grt_profile_read
 grt_set_deterministic grt_deterministic grt_gas_optics_probe grt_optics_cache_flush grt_device_use_lane grt_device_synchronize
 grt_multi_shard grt_multi_create grt_multi_destroy grt_multi_gather_rows grt_multi_gather_fluxes grt_multi_broadcast grt_multi_max
 grt_err_begin grt_err_frame grt_log grt_gmalloc grt_gfree grt_gmemset grt_gmemcpy
@@ -428,6 +428,8 @@ def load_library(path=None):
         lib.grt_pipeline_run_sky_tiles.argtypes = [C.c_void_p, C.POINTER(GrtColumns), C.POINTER(GrtSky),
                                                    C.POINTER(GrtSurfaceTiles), C.c_void_p]
     lib.grt_pipeline_set_surface.argtypes = [C.c_void_p, C.POINTER(GrtSurface)]
+    if hasattr(lib, "grt_debug_pipeline_holdings"):      # (GRT_LIB_PATH may name an older library: a timing yardstick)
+        lib.grt_debug_pipeline_holdings.argtypes = [C.c_void_p, C.POINTER(C.c_int)] + [C.POINTER(C.c_uint64)] * 3
     lib.grt_multi_gather_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.grt_pipeline_sync.argtypes = [C.c_void_p]
     lib.grt_pipeline_stream.argtypes = [C.c_void_p]
@@ -1936,6 +1938,20 @@ class Pipeline:
             out["angle_direct"] = self.buffers[name + ".angle_direct"].to_host((ncol, nsets, Z, GRT_DIRECT_ROWS_PER_SET))
             out["angle_direct_levels"] = self.buffers[name + ".angle_direct_levels"].to_host((ncol, nsets, Z, V))
         return out
+
+    def holdings(self):
+        """grt_debug_pipeline_holdings: (scratch [2][slots], staging [buffers], key_bytes [2][tables]) -- the capacity in
+        doubles of every on-demand scratch slot per band and of every pinned staging buffer, and the length in bytes of
+        the key every keyed table of a band holds (0: none), each in the order grt_pipeline_internal.h declares them.
+        Host bookkeeping only: nothing is launched and nothing waits."""
+        counts = (C.c_int * 3)()
+        check(self.lib.grt_debug_pipeline_holdings(self.p, counts, None, None, None))
+        scratch = np.zeros((2, counts[0]), dtype=np.uint64)
+        staging = np.zeros(counts[1], dtype=np.uint64)
+        keys = np.zeros((2, counts[2]), dtype=np.uint64)
+        check(self.lib.grt_debug_pipeline_holdings(self.p, counts, *[a.ctypes.data_as(C.POINTER(C.c_uint64))
+                                                                     for a in (scratch, staging, keys)]))
+        return scratch, staging, keys
 
     def views(self, band):
         ptrs = [C.c_void_p() for _ in range(6)]

@@ -2017,3 +2017,45 @@ EXTERN int grt_pipeline_run_band_profiles(GrtPipeline_t *p, GrtColumns_t const *
     }
     return GRTCODE_SUCCESS;
 }
+
+/* what the object holds on demand, read from its bookkeeping (grt_ext.h): the members in the order
+   grt_pipeline_internal.h declares them */
+EXTERN int grt_debug_pipeline_holdings(GrtPipeline_t const *p, int *counts, uint64_t *scratch_doubles,
+                                       uint64_t *staging_doubles, uint64_t *key_bytes)
+{
+    GRT_REQUIRE_PTR(p);
+    GRT_REQUIRE_PTR(counts);
+    GrtStaging const *const staging[] = {&p->small, &p->cloud, &p->aer, &p->surf, &p->zen, &p->rad, &p->tile, &p->zen_surf};
+    int const num_staging = (int)(sizeof(staging)/sizeof(staging[0]));
+    int num_tables = 0;
+    for (int bi = 0; bi < 2; ++bi)
+    {
+        GrtBand const *b = &p->band[bi];
+        size_t const held[] = {b->cloud_map.key != NULL ? b->cloud_map.key_bytes : 0,
+                               b->aer_map.key != NULL ? b->aer_map.key_bytes : 0,
+                               b->bin_table.key != NULL ? b->bin_table.key_bytes : 0,
+                               b->kdist_table.key != NULL ? b->kdist_table.key_bytes : 0,
+                               b->surf_map.key != NULL ? b->surf_map.key_bytes : 0,
+                               b->channel_table.key != NULL ? b->channel_table.key_bytes : 0,
+                               b->tile_map.key != NULL ? b->tile_map.key_bytes : 0,
+                               b->response_table.key != NULL ? b->response_table.key_bytes : 0,
+                               b->zen_surf_map.key != NULL ? b->zen_surf_map.key_bytes : 0};
+        num_tables = (int)(sizeof(held)/sizeof(held[0]));
+        for (int k = 0; k < num_tables && key_bytes != NULL; ++k)
+        {
+            key_bytes[bi*num_tables + k] = held[k];
+        }
+        for (int k = 0; k < GRT_SCRATCH_COUNT && scratch_doubles != NULL; ++k)
+        {
+            scratch_doubles[bi*GRT_SCRATCH_COUNT + k] = b->scratch[k].doubles;
+        }
+    }
+    for (int k = 0; k < num_staging && staging_doubles != NULL; ++k)
+    {
+        staging_doubles[k] = staging[k]->doubles;
+    }
+    counts[0] = GRT_SCRATCH_COUNT;
+    counts[1] = num_staging;
+    counts[2] = num_tables;
+    return GRTCODE_SUCCESS;
+}

@@ -1553,4 +1553,15 @@ EXTERN int grt_debug_partition_functions(GasOptics_t *gas_optics, fp_t *pressure
 EXTERN int grt_debug_tile_items(GasOptics_t *gas_optics, uint32_t *num_items, uint32_t *items, uint64_t *num_tiles,
                                 uint32_t *ranges);
 
+/* ---- test hook: what a pipeline object holds between calls, from its host bookkeeping alone (nothing is launched, nothing
+ * waits).  counts [3]: the scratch slots per band (the GRT_SCRATCH_... enumerators of grt_pipeline_internal.h), the
+ * pinned staging buffers of the object and the keyed tables per band, always written.  scratch_doubles: host [2][counts[0]],
+ * the capacity in doubles of every slot of the longwave, then of the shortwave band, in the enumerators' order;
+ * staging_doubles: host [counts[1]], the capacity of every GrtStaging member of the object in the order the struct
+ * declares them; key_bytes: host [2][counts[2]], the length of the key every GrtKeyedTable of a band was built for and of its
+ * kdist_table, in the order the struct declares them, 0 where none is stored.  Any of the three may be NULL: a caller asks
+ * for the counts first (tests/test_gpu_pipeline_history.py). */
+EXTERN int grt_debug_pipeline_holdings(GrtPipeline_t const *pipeline, int *counts, uint64_t *scratch_doubles,
+                                       uint64_t *staging_doubles, uint64_t *key_bytes);
+
 #endif
