@@ -22,6 +22,18 @@ void grt_log(int level, char const *file, int line, char const *fmt, ...);
 #define GRT_TRY(expr) \
     do { int rc_ = (expr); if (rc_ != GRTCODE_SUCCESS) { grt_err_frame(__FILE__, __LINE__); return rc_; } } while (0)
 
+/* One timed launch: the profile span of `tag` on `stream` around expr -- an int, the launch's HIP error or the first of the
+   few launches one span covers --, then the check of it as `what`.  GRT_UNTIMED for tag: the check alone, for a step that
+   some of its callers time and others do not. */
+#define GRT_UNTIMED 0
+_Static_assert(GRT_TAG_GAS_LW > GRT_UNTIMED, "the profile tags start above GRT_UNTIMED: no tag is taken for it");
+#define GRT_TIMED(stream, tag, what, expr) \
+    do { void *s_ = (stream); int const tag_ = (tag); \
+         int const slot_ = tag_ != GRT_UNTIMED ? grt_profile_begin(s_, tag_) : -1; \
+         int const krc_ = (expr); \
+         grt_profile_end(s_, slot_); \
+         GRT_TRY(grt_dev_check(krc_, (what))); } while (0)
+
 #define GRT_REQUIRE_PTR(p) \
     do { if ((p) == NULL) GRT_FAIL(GRTCODE_NULL_ERR, "null pointer for argument '%s'.", #p); } while (0)
 

@@ -366,6 +366,28 @@ static int check_lane(GrtPipeline_t const *p)
     return GRTCODE_SUCCESS;
 }
 
+/* A block of the pipeline's own for what a profile run's rows are picked from where the caller takes no copy of it: max_cols
+   x GRT_SKY_MAX_SETS x per_set doubles in scratch block `slot` of band b, as *block */
+static int own_levels(GrtPipeline_t *p, GrtBand *b, int slot, size_t per_set, double **block)
+{
+    GRT_TRY(check_lane(p));
+    GrtScratch *own = &b->scratch[slot];
+    GRT_TRY(grt_scratch_need(p, own, (size_t)p->max_cols*GRT_SKY_MAX_SETS*per_set, NULL));
+    *block = own->d;
+    return GRTCODE_SUCCESS;
+}
+
+/* A band that is not there leaves zeros, as its rows are, and not whatever the caller's buffer held before: n doubles of
+   `out`, where that output is given */
+static int zero_absent(GrtPipeline_t *p, fp_t *out, size_t n)
+{
+    if (out != NULL)
+    {
+        GRT_TRY(grt_dev_zero(p->device, out, sizeof(double)*n, grt_dev_stream(p->device)));
+    }
+    return GRTCODE_SUCCESS;
+}
+
 /* What grt_pipeline_run and grt_pipeline_run_profiles check and stage alike: the arguments, the lane, and the small
    per-column inputs, uploaded to small.d on the library stream.  own_sun 1: the run brings its sun angles itself
    (grt_pipeline_run_zeniths), and the columns' cos_zenith is not read; GRT_SUN_MAY_BE_DOWN: cos_zenith is read and a
@@ -637,16 +659,9 @@ static int pipeline_run(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin cons
         {
             /* a band that is not there: its rows are zeros in both outputs -- everything is zeroed here, in stream order
                ahead of the kernels that write the other band's rows */
-            void *s = grt_dev_stream(p->device);
             size_t const slots = (size_t)C*(size_t)rows->sets;
-            if (rows->out != NULL)
-            {
-                GRT_TRY(grt_dev_zero(p->device, rows->out, sizeof(double)*slots*GRT_FLUXES_PER_COLUMN, s));
-            }
-            if (tr.per_tile != NULL)
-            {
-                GRT_TRY(grt_dev_zero(p->device, tr.per_tile, sizeof(double)*slots*(size_t)tr.tiles*GRT_FLUXES_PER_COLUMN, s));
-            }
+            GRT_TRY(zero_absent(p, rows->out, slots*GRT_FLUXES_PER_COLUMN));
+            GRT_TRY(zero_absent(p, tr.per_tile, slots*(size_t)tr.tiles*GRT_FLUXES_PER_COLUMN));
         }
     }
     if (cl != NULL && join->sampler != NULL)
@@ -785,24 +800,29 @@ static int check_two_levels(GrtPipeline_t const *p)
 }
 
 /* The rows of a run of `sets` sets per column in the form its two outputs ask for: the profile form, to
-   level_fluxes_dev, when that is given (it needs two levels), else the six-row form, to fluxes_dev; one of the two is
-   needed. */
+   level_fluxes_dev, when that is given, else the six-row form, to fluxes_dev.  rows_form: for the runs that have checked
+   their outputs themselves and may leave without rows (the angles' own rows, the radiances or the tiles' rows alone);
+   output_form: one of the two is needed, and the profile form needs two levels. */
+static void rows_form(GrtPipeline_t const *p, int sets, fp_t *level_fluxes_dev, fp_t *fluxes_dev, GrtPass *rows)
+{
+    memset(rows, 0, sizeof(*rows));
+    rows->profile = level_fluxes_dev != NULL;
+    rows->out = rows->profile ? level_fluxes_dev : fluxes_dev;
+    rows->sets = sets;
+    rows->out_stride = sets*grt_set_offset(p, rows->profile);
+}
+
 static int output_form(GrtPipeline_t const *p, int sets, fp_t *level_fluxes_dev, fp_t *fluxes_dev, GrtPass *rows)
 {
     if (level_fluxes_dev == NULL && fluxes_dev == NULL)
     {
         GRT_FAIL(GRTCODE_VALUE_ERR, "level_fluxes_dev and fluxes_dev are both NULL: nothing to write.%s", "");
     }
-    int const profile = level_fluxes_dev != NULL;
-    if (profile)
+    if (level_fluxes_dev != NULL)
     {
         GRT_TRY(check_two_levels(p));
     }
-    memset(rows, 0, sizeof(*rows));
-    rows->profile = profile;
-    rows->out = profile ? level_fluxes_dev : fluxes_dev;
-    rows->sets = sets;
-    rows->out_stride = sets*grt_set_offset(p, profile);
+    rows_form(p, sets, level_fluxes_dev, fluxes_dev, rows);
     return GRTCODE_SUCCESS;
 }
 
@@ -912,26 +932,15 @@ static int run_under_zeniths(GrtPipeline_t *p, GrtColumns_t const *cols, GrtJoin
 {
     GrtZeniths_t const *zn = join->zeniths;
     GrtPass rows;
-    memset(&rows, 0, sizeof(rows));
-    rows.profile = level_fluxes_dev != NULL;
-    rows.out = rows.profile ? level_fluxes_dev : fluxes_dev;
-    rows.sets = sets;
-    rows.out_stride = sets*grt_set_offset(p, rows.profile);
+    rows_form(p, sets, level_fluxes_dev, fluxes_dev, &rows);
     GRT_TRY(pipeline_run(p, cols, join, &rows));
     GRT_TRY(finish_profiles(p, cols->ncol, &rows, heating_dev, fluxes_dev));
     if (p->band[1].gas == NULL)
     {
         /* no shortwave band: every angle's rows are zeros, as the band's rows of the mean are */
-        void *s = grt_dev_stream(p->device);
         size_t const n = (size_t)cols->ncol*(size_t)sets*(size_t)zn->num_zeniths;
-        if (zn->zenith_fluxes_dev != NULL)
-        {
-            GRT_TRY(grt_dev_zero(p->device, zn->zenith_fluxes_dev, sizeof(double)*n*GRT_FLUXES_PER_BAND, s));
-        }
-        if (zn->zenith_level_fluxes_dev != NULL)
-        {
-            GRT_TRY(grt_dev_zero(p->device, zn->zenith_level_fluxes_dev, sizeof(double)*n*2*(size_t)p->num_levels, s));
-        }
+        GRT_TRY(zero_absent(p, zn->zenith_fluxes_dev, n*GRT_FLUXES_PER_BAND));
+        GRT_TRY(zero_absent(p, zn->zenith_level_fluxes_dev, n*2*(size_t)p->num_levels));
     }
     return GRTCODE_SUCCESS;
 }
@@ -1212,10 +1221,7 @@ static int run_sky(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *s
         third_rows = rows.profile ? third->levels : third->three;
         if (third_rows == NULL)
         {
-            GRT_TRY(check_lane(p));
-            GrtScratch *own = &tb->scratch[GRT_SCRATCH_DIRECT_LEVELS];
-            GRT_TRY(grt_scratch_need(p, own, (size_t)p->max_cols*GRT_SKY_MAX_SETS*(size_t)V, NULL));
-            third_rows = own->d;
+            GRT_TRY(own_levels(p, tb, GRT_SCRATCH_DIRECT_LEVELS, (size_t)V, &third_rows));
         }
         if (third->band == 1)
         {
@@ -1230,21 +1236,16 @@ static int run_sky(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_t const *s
     GRT_TRY(finish_profiles(p, cols->ncol, &rows, heating_dev, fluxes_dev));
     if (third != NULL)
     {
-        void *s = grt_dev_stream(p->device);
         size_t const slots = (size_t)cols->ncol*(size_t)nsets;
         if (tb->gas == NULL)
         {
-            /* the band is not there: zeros, as the band's rows are */
-            GRT_TRY(grt_dev_zero(p->device, third->three, sizeof(double)*slots*GRT_DIRECT_ROWS_PER_SET, s));
-            if (third->levels != NULL)
-            {
-                GRT_TRY(grt_dev_zero(p->device, third->levels, sizeof(double)*slots*(size_t)V, s));
-            }
+            GRT_TRY(zero_absent(p, third->three, slots*GRT_DIRECT_ROWS_PER_SET));
+            GRT_TRY(zero_absent(p, third->levels, slots*(size_t)V));
         }
         else if (rows.profile)
         {
-            GRT_TRY(grt_dev_check(grt_launch_direct_rows(s, (int)slots, V, p->user_level, third_rows, third->three),
-                                  "row pick kernel"));
+            GRT_TRY(grt_dev_check(grt_launch_direct_rows(grt_dev_stream(p->device), (int)slots, V, p->user_level, third_rows,
+                                                         third->three), "row pick kernel"));
         }
     }
     return GRTCODE_SUCCESS;
@@ -1290,10 +1291,7 @@ EXTERN int grt_pipeline_run_sky_scattering(GrtPipeline_t *p, GrtColumns_t const 
     GrtScatterRun sr = {rows.profile ? scatter_levels_dev : scatter_dev};
     if (sr.out == NULL)
     {
-        GRT_TRY(check_lane(p));
-        GrtScratch *own = &p->band[0].scratch[GRT_SCRATCH_SCATTER_LEVELS];
-        GRT_TRY(grt_scratch_need(p, own, (size_t)p->max_cols*GRT_SKY_MAX_SETS*2*(size_t)V, NULL));
-        sr.out = own->d;
+        GRT_TRY(own_levels(p, &p->band[0], GRT_SCRATCH_SCATTER_LEVELS, 2*(size_t)V, &sr.out));
     }
     rows.scatter = &sr;
     GRT_TRY(pipeline_run(p, cols, &join, &rows));
@@ -1382,10 +1380,7 @@ EXTERN int grt_pipeline_run_sky_weighted(GrtPipeline_t *p, GrtColumns_t const *c
     if (rs->sw_num_responses > 0)
     {
         /* the shortwave's response rows ride with the direct beam's: its levels go to the pipeline's own block */
-        GRT_TRY(check_lane(p));
-        GrtScratch *own = &p->band[1].scratch[GRT_SCRATCH_DIRECT_LEVELS];
-        GRT_TRY(grt_scratch_need(p, own, (size_t)p->max_cols*GRT_SKY_MAX_SETS*(size_t)V, NULL));
-        rows.direct = own->d;
+        GRT_TRY(own_levels(p, &p->band[1], GRT_SCRATCH_DIRECT_LEVELS, (size_t)V, &rows.direct));
     }
     GRT_TRY(pipeline_run(p, cols, &join, &rows));
     GRT_TRY(finish_profiles(p, cols->ncol, &rows, heating_dev, fluxes_dev));
@@ -1393,12 +1388,10 @@ EXTERN int grt_pipeline_run_sky_weighted(GrtPipeline_t *p, GrtColumns_t const *c
     {
         void *s = grt_dev_stream(p->device);
         uint64_t const lw_rows = 2*(uint64_t)rs->lw_num_responses*(uint64_t)V;
-        int const slot = grt_profile_begin(s, GRT_TAG_BAND_PROFILES);
-        int const krc = grt_launch_actinic_rows(s, rs->weighted_levels_dev + lw_rows,
-                                                lw_rows + 3*(uint64_t)rs->sw_num_responses*(uint64_t)V, cols->ncol, nsets,
-                                                rs->sw_num_responses, V, p->small.d + p->off_mu, 0.5, rs->actinic_levels_dev);
-        grt_profile_end(s, slot);
-        GRT_TRY(grt_dev_check(krc, "actinic flux kernel"));
+        GRT_TIMED(s, GRT_TAG_BAND_PROFILES, "actinic flux kernel",
+                  grt_launch_actinic_rows(s, rs->weighted_levels_dev + lw_rows,
+                                          lw_rows + 3*(uint64_t)rs->sw_num_responses*(uint64_t)V, cols->ncol, nsets,
+                                          rs->sw_num_responses, V, p->small.d + p->off_mu, 0.5, rs->actinic_levels_dev));
     }
     return GRTCODE_SUCCESS;
 }
@@ -1471,38 +1464,23 @@ static int run_sky_radiances(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky_
     join.channel_pairs = pairs;
     join.weighting = weighting_asked ? wt : NULL;
     GrtPass rows;
-    memset(&rows, 0, sizeof(rows));
-    rows.out = fluxes_dev;
-    rows.sets = nsets;
-    rows.out_stride = nsets*grt_set_offset(p, 0);
+    rows_form(p, nsets, NULL, fluxes_dev, &rows);
     GRT_TRY(pipeline_run(p, cols, &join, &rows));
     if (p->band[0].gas == NULL)
     {
-        /* no longwave band: zeros, as the band's rows are */
-        void *s = grt_dev_stream(p->device);
-        size_t const rows_all = (size_t)cols->ncol*(size_t)nsets*(size_t)rd->num_angles*GRT_RADIANCE_ROWS_PER_ANGLE;
-        GRT_TRY(grt_dev_zero(p->device, rd->radiances_dev, sizeof(double)*rows_all, s));
-        /* (a spectral row of such a pipeline has no points) */
+        /* no longwave band (a spectral row of such a pipeline has no points) */
+        size_t const per_level = (size_t)cols->ncol*(size_t)nsets*(size_t)rd->num_angles;
+        size_t const rows_all = per_level*GRT_RADIANCE_ROWS_PER_ANGLE;
+        GRT_TRY(zero_absent(p, rd->radiances_dev, rows_all));
         if (channels_asked)
         {
-            size_t const bytes = sizeof(double)*rows_all*(size_t)ch->num_channels;
-            GRT_TRY(grt_dev_zero(p->device, ch->channel_radiances_dev, bytes, s));
-            if (ch->channel_brightness_dev != NULL)
-            {
-                GRT_TRY(grt_dev_zero(p->device, ch->channel_brightness_dev, bytes, s));
-            }
+            size_t const channels = (size_t)ch->num_channels, V = (size_t)p->num_levels;
+            GRT_TRY(zero_absent(p, ch->channel_radiances_dev, rows_all*channels));
+            GRT_TRY(zero_absent(p, ch->channel_brightness_dev, rows_all*channels));
             if (weighting_asked)
             {
-                size_t const per_level = sizeof(double)*(size_t)cols->ncol*(size_t)nsets*(size_t)rd->num_angles*
-                                         (size_t)ch->num_channels;
-                if (wt->transmittance_dev != NULL)
-                {
-                    GRT_TRY(grt_dev_zero(p->device, wt->transmittance_dev, per_level*(size_t)p->num_levels, s));
-                }
-                if (wt->contribution_dev != NULL)
-                {
-                    GRT_TRY(grt_dev_zero(p->device, wt->contribution_dev, per_level*((size_t)p->num_levels + 1), s));
-                }
+                GRT_TRY(zero_absent(p, wt->transmittance_dev, per_level*channels*V));
+                GRT_TRY(zero_absent(p, wt->contribution_dev, per_level*channels*(V + 1)));
             }
         }
     }
@@ -1615,17 +1593,11 @@ static int sky_zeniths_direct(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky
         join.zenith_direct_per_angle = profile ? direct->zenith_direct_level_fluxes_dev : direct->zenith_direct_fluxes_dev;
         if (profile && join.zenith_direct_out == NULL && direct->direct_fluxes_dev != NULL)
         {
-            GRT_TRY(check_lane(p));
-            GrtScratch *own = &sw->scratch[GRT_SCRATCH_DIRECT_LEVELS];
-            GRT_TRY(grt_scratch_need(p, own, (size_t)p->max_cols*GRT_SKY_MAX_SETS*(size_t)V, NULL));
-            join.zenith_direct_out = own->d;
+            GRT_TRY(own_levels(p, sw, GRT_SCRATCH_DIRECT_LEVELS, (size_t)V, &join.zenith_direct_out));
         }
         if (profile && join.zenith_direct_per_angle == NULL && direct->zenith_direct_fluxes_dev != NULL)
         {
-            GRT_TRY(check_lane(p));
-            GrtScratch *own = &sw->scratch[GRT_SCRATCH_ZEN_DIRECT_LEVELS];
-            GRT_TRY(grt_scratch_need(p, own, (size_t)p->max_cols*GRT_SKY_MAX_SETS*(size_t)Z*(size_t)V, NULL));
-            join.zenith_direct_per_angle = own->d;
+            GRT_TRY(own_levels(p, sw, GRT_SCRATCH_ZEN_DIRECT_LEVELS, (size_t)Z*(size_t)V, &join.zenith_direct_per_angle));
         }
     }
     GRT_TRY(run_under_zeniths(p, cols, &join, nsets, level_fluxes_dev, heating_dev, fluxes_dev));
@@ -1642,11 +1614,7 @@ static int sky_zeniths_direct(GrtPipeline_t *p, GrtColumns_t const *cols, GrtSky
                               direct->zenith_direct_level_fluxes_dev};
         for (int k = 0; k < 4; ++k)
         {
-            if (out[k] != NULL)
-            {
-                GRT_TRY(grt_dev_zero(p->device, out[k], sizeof(double)*slots*(size_t)(k & 1 ? Z : 1)*
-                                                        (size_t)(k < 2 ? GRT_DIRECT_ROWS_PER_SET : V), s));
-            }
+            GRT_TRY(zero_absent(p, out[k], slots*(size_t)(k & 1 ? Z : 1)*(size_t)(k < 2 ? GRT_DIRECT_ROWS_PER_SET : V)));
         }
     }
     else if (profile)
@@ -1718,10 +1686,7 @@ EXTERN int grt_pipeline_run_sky_tiles(GrtPipeline_t *p, GrtColumns_t const *cols
     /* (the draws of a cloud set go through the subcolumn form, one draw included: the cloud form's doubles) */
     join.subcolumns = join.clouds != NULL ? sky->num_subcolumns : 0;
     GrtPass rows;
-    memset(&rows, 0, sizeof(rows));
-    rows.out = fluxes_dev;
-    rows.sets = nsets;
-    rows.out_stride = nsets*grt_set_offset(p, 0);
+    rows_form(p, nsets, NULL, fluxes_dev, &rows);
     GRT_TRY(pipeline_run(p, cols, &join, &rows));
     return GRTCODE_SUCCESS;
 }
@@ -2008,12 +1973,10 @@ EXTERN int grt_pipeline_run_band_profiles(GrtPipeline_t *p, GrtColumns_t const *
     if (band_heating_dev != NULL)
     {
         void *s = grt_dev_stream(p->device);
-        int const slot = grt_profile_begin(s, GRT_TAG_BAND_PROFILES);
-        int const krc = grt_launch_band_profile_finish(s, cols->ncol, sets, V, lw_num_bins, sw_num_bins, GRT_GRAVITY,
-                                                       GRT_SPECIFIC_HEAT_AIR, p->small.d + p->off_p, band_levels_dev,
-                                                       band_heating_dev);
-        grt_profile_end(s, slot);
-        GRT_TRY(grt_dev_check(krc, "band heating rate kernel"));
+        GRT_TIMED(s, GRT_TAG_BAND_PROFILES, "band heating rate kernel",
+                  grt_launch_band_profile_finish(s, cols->ncol, sets, V, lw_num_bins, sw_num_bins, GRT_GRAVITY,
+                                                 GRT_SPECIFIC_HEAT_AIR, p->small.d + p->off_p, band_levels_dev,
+                                                 band_heating_dev));
     }
     return GRTCODE_SUCCESS;
 }

@@ -130,11 +130,9 @@ static int finish_responses(GrtPipeline_t *p, int C, int S, GrtPass const *ps, G
 {
     GrtResponseRun const *rr = ps->responses;
     void *s = grt_dev_stream(p->device);
-    int const slot = grt_profile_begin(s, GRT_TAG_BAND_PROFILES);
-    int const krc = grt_launch_response_finish(s, ra, rr->groups, C, S, p->num_levels, rr->out,
-                                               (uint64_t)ps->sets*rr->set_doubles, (uint64_t)ps->set*rr->set_doubles);
-    grt_profile_end(s, slot);
-    GRT_TRY(grt_dev_check(krc, "response finishing kernel"));
+    GRT_TIMED(s, GRT_TAG_BAND_PROFILES, "response finishing kernel",
+              grt_launch_response_finish(s, ra, rr->groups, C, S, p->num_levels, rr->out, (uint64_t)ps->sets*rr->set_doubles,
+                                         (uint64_t)ps->set*rr->set_doubles));
     return GRTCODE_SUCCESS;
 }
 
@@ -152,10 +150,8 @@ static int response_rows(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *ps)
     GrtResponseArgs ra;
     GRT_TRY(response_partials(p, b, ps, 1, &ra));
     double const *const rows[3] = {b->flux_up, b->flux_down, rr->groups == 3 ? b->scratch[GRT_SCRATCH_DIRECT_BEAM].d : NULL};
-    int const slot = grt_profile_begin(s, GRT_TAG_BAND_PROFILES);
-    int const krc = grt_launch_response_rows(s, &ra, rows, rr->groups, C, p->num_levels, b->n, b->gas->grid.dw);
-    grt_profile_end(s, slot);
-    GRT_TRY(grt_dev_check(krc, "response row kernel"));
+    GRT_TIMED(s, GRT_TAG_BAND_PROFILES, "response row kernel",
+              grt_launch_response_rows(s, &ra, rows, rr->groups, C, p->num_levels, b->n, b->gas->grid.dw));
     GRT_TRY(finish_responses(p, C, 1, ps, &ra));
     return GRTCODE_SUCCESS;
 }
@@ -310,11 +306,72 @@ static int band_solver(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass cons
     void *s = grt_dev_stream(p->device);
     SolverArgs a;
     GRT_TRY(solver_args(p, b, bi, C, ps, &in, partials, &a));
-    int const slot = grt_profile_begin(s, pass_tag(ps, bi));
-    int const krc = solver_launch(s, bi, &in, &a);
-    grt_profile_end(s, slot);
-    GRT_TRY(grt_dev_check(krc, bi == 0 ? "longwave kernel" : "shortwave kernel"));
+    GRT_TIMED(s, pass_tag(ps, bi), bi == 0 ? "longwave kernel" : "shortwave kernel", solver_launch(s, bi, &in, &a));
     return GRTCODE_SUCCESS;
+}
+
+/* A walk over `total` items -- a pass's draws, its sun angles, its tile chunks -- in launches of at most `step`, on the
+   first/count pair the launcher reads: for (first = count = 0; krc == 0 && walk(total, step, &first, &count); ) krc = the
+   launch.  The first launch error stops it, and what is not queued then stays not queued.  One span covers a whole walk,
+   so those spans are opened and closed by hand.
+   The step is what one launch may hold.  row_limit: the grid rows of C columns each, 65 535 along the grid's y or --
+   parks: the launch parks every row, as the shortwave's two-sweep forms and the longwave's scattering kernel do -- the
+   max_cols of the band's park block.  A walk with another nested in it (angles, tile chunks) takes row_limit/(the inner
+   walk's items per launch) of it.
+   walk needs first = count = 0 before its first call, as the for above sets them, and step >= 1: a step of 0 never ends.
+   row_limit is 1 or more because a run has C <= max_cols columns and a pipeline max_cols <= 65 535
+   (grt_pipeline_create_ex), and every nested divisor is itself cut to the limit it divides. */
+static int walk(int total, int step, int *first, int *count)
+{
+    *first += *count;
+    *count = total - *first < step ? total - *first : step;
+    return *first < total;
+}
+
+static int row_limit(GrtPipeline_t const *p, int C, int parks)
+{
+    return (parks ? p->max_cols : 65535)/C;
+}
+
+/* the pass's clouds as the S subcolumns of *sc, for the instances and launchers that take them so (they point at *sc and
+   read the first and count a walk leaves there); NULL for a pass without clouds, whose one draw is walked on *sc all the
+   same */
+static GrtSubcolumnArgs *pass_subcolumns(GrtPass const *ps, int S, GrtSubcolumnArgs *sc)
+{
+    memset(sc, 0, sizeof(*sc));
+    if (ps->clouds == NULL)
+    {
+        return NULL;
+    }
+    sc->clouds = *ps->clouds;
+    sc->subcolumns = S;
+    return sc;
+}
+
+/* Draw j of a pass whose clouds hold their draws subcolumn-major, for the materialised loops: the pass on draw j's tables,
+   which *cj holds (a pass without clouds: the pass itself) */
+static GrtPass pass_draw(GrtPipeline_t const *p, GrtPass const *ps, int C, int j, GrtCloudArgs *cj)
+{
+    GrtPass pj = *ps;
+    if (ps->clouds != NULL)
+    {
+        size_t const tab = (size_t)C*3*(size_t)ps->clouds->num_bands*(size_t)(p->num_levels - 1);
+        *cj = *ps->clouds;
+        cj->liquid += (size_t)j*tab;
+        cj->ice += (size_t)j*tab;
+        pj.clouds = cj;
+    }
+    return pj;
+}
+
+/* What turns a block's [C][S][rows] rows of nblocks partial sums each into column c's rows at out[c stride + offset ..]:
+   the fixed-order sum of the blocks or -- S > 1 -- the subcolumn mean kernel, draws 0 .. S - 1 in order, then one division
+   by S.  The launch alone: whether it is timed, and as what it is checked, is its caller's. */
+static int partial_rows(void *s, double const *partials, int C, int S, int rows, unsigned nblocks, double *out, int stride,
+                        int offset)
+{
+    return S == 1 ? grt_launch_reduce_partials(s, partials, C*rows, nblocks, out, rows, stride, offset) :
+                    grt_launch_subcolumn_mean(s, partials, C, S, rows, nblocks, out, stride, offset);
 }
 
 /* whether band bi's solve of the pass leaves radiances too (grt_pipeline_run_sky_radiances: the longwave's) */
@@ -371,19 +428,12 @@ static int band_radiances(GrtPipeline_t *p, GrtBand *b, int C, int S, int draw, 
                                                 (size_t)grt_weighting_rows(&wa, p->num_levels)*(size_t)ch.pairs, NULL));
         wa.partials = wpairs->d;
     }
+    /* (a launch without subcolumns is a walk of one step, on a pair that no launcher reads) */
+    GrtSubcolumnArgs one, *w = sc != NULL ? sc : &one;
+    int const draws = sc != NULL ? S : 1, group = row_limit(p, C, 0);
     int const slot = grt_profile_begin(s, GRT_TAG_RADIANCE);
     int krc = 0;
-    if (sc != NULL)
-    {
-        int const group = 65535/C < S ? 65535/C : S;                  /* (grid rows) */
-        for (sc->first = 0; sc->first < S && krc == 0; sc->first += group)
-        {
-            sc->count = S - sc->first < group ? S - sc->first : group;
-            krc = ps->channels != NULL ? grt_launch_lw_channels(s, &in, &a.lw, &r, &ch) :
-                                         grt_launch_lw_radiances(s, &in, &a.lw, &r);
-        }
-    }
-    else
+    for (w->first = w->count = 0; krc == 0 && walk(draws, group, &w->first, &w->count); )
     {
         krc = ps->channels != NULL ? grt_launch_lw_channels(s, &in, &a.lw, &r, &ch) : grt_launch_lw_radiances(s, &in, &a.lw, &r);
     }
@@ -395,16 +445,7 @@ static int band_radiances(GrtPipeline_t *p, GrtBand *b, int C, int S, int draw, 
     }
     /* (the weighting kernel behind it on the same instance and arguments, GRT_TAG_WEIGHTING) */
     int const wslot = grt_profile_begin(s, GRT_TAG_WEIGHTING);
-    if (sc != NULL)
-    {
-        int const group = 65535/C < S ? 65535/C : S;                  /* (grid rows) */
-        for (sc->first = 0; sc->first < S && krc == 0; sc->first += group)
-        {
-            sc->count = S - sc->first < group ? S - sc->first : group;
-            krc = grt_launch_lw_weighting(s, &in, &a.lw, &r, &ch, &wa);
-        }
-    }
-    else
+    for (w->first = w->count = 0; krc == 0 && walk(draws, group, &w->first, &w->count); )
     {
         krc = grt_launch_lw_weighting(s, &in, &a.lw, &r, &ch, &wa);
     }
@@ -413,26 +454,16 @@ static int band_radiances(GrtPipeline_t *p, GrtBand *b, int C, int S, int draw, 
     return GRTCODE_SUCCESS;
 }
 
-/* ... and what turns the partial sums of its S draws into the pass's set of the integrated radiances [ncol][sets][A][2]:
-   the fixed-order sum of the blocks, or -- S > 1 -- the subcolumn mean kernel (draws 0 .. S - 1 in order, one division) */
+/* ... and what turns the partial sums of its S draws into the pass's set of the integrated radiances [ncol][sets][A][2]
+   (partial_rows; the mean of several draws counts under GRT_TAG_SUBCOLUMN_MEAN, the sum of one is not timed) */
 static int finish_radiances(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass const *ps)
 {
     GrtRadianceRun const *rr = ps->radiances;
     void *s = grt_dev_stream(p->device);
     int const rows = rr->angles*GRT_RADIANCE_ROWS_PER_ANGLE;
-    double const *partials = b->scratch[GRT_SCRATCH_RADIANCE_PARTIALS].d;
-    unsigned const nblocks = grt_solver_blocks(b->n);
-    if (S == 1)
-    {
-        GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, partials, C*rows, nblocks, rr->integrated, rows,
-                                                         ps->sets*rows, ps->set*rows), "radiance reduction kernel"));
-        return GRTCODE_SUCCESS;
-    }
-    int const mslot = grt_profile_begin(s, GRT_TAG_SUBCOLUMN_MEAN);
-    int const mrc = grt_launch_subcolumn_mean(s, partials, C, S, rows, nblocks, rr->integrated, ps->sets*rows,
-                                              ps->set*rows);
-    grt_profile_end(s, mslot);
-    GRT_TRY(grt_dev_check(mrc, "subcolumn mean kernel"));
+    GRT_TIMED(s, S == 1 ? GRT_UNTIMED : GRT_TAG_SUBCOLUMN_MEAN, S == 1 ? "radiance reduction kernel" : "subcolumn mean kernel",
+              partial_rows(s, b->scratch[GRT_SCRATCH_RADIANCE_PARTIALS].d, C, S, rows, grt_solver_blocks(b->n), rr->integrated,
+                           ps->sets*rows, ps->set*rows));
     return GRTCODE_SUCCESS;
 }
 
@@ -449,11 +480,9 @@ static int finish_channels(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass c
     GrtChannelArgs ch = cr->args;
     ch.partials = b->scratch[GRT_SCRATCH_CHANNEL_PARTIALS].d;
     uint64_t const set_doubles = (uint64_t)ps->radiances->angles*GRT_RADIANCE_ROWS_PER_ANGLE*(uint64_t)ch.channels;
-    int const slot = grt_profile_begin(s, GRT_TAG_CHANNELS);
-    int const krc = grt_launch_channel_finish(s, &ch, C, S, ps->radiances->angles, cr->radiances, cr->brightness,
-                                              (uint64_t)ps->sets*set_doubles, (uint64_t)ps->set*set_doubles);
-    grt_profile_end(s, slot);
-    GRT_TRY(grt_dev_check(krc, "channel finishing kernel"));
+    GRT_TIMED(s, GRT_TAG_CHANNELS, "channel finishing kernel",
+              grt_launch_channel_finish(s, &ch, C, S, ps->radiances->angles, cr->radiances, cr->brightness,
+                                        (uint64_t)ps->sets*set_doubles, (uint64_t)ps->set*set_doubles));
     return GRTCODE_SUCCESS;
 }
 
@@ -474,12 +503,31 @@ static int finish_weighting(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass 
     int const A = ps->radiances->angles, V = p->num_levels;
     uint64_t const t_set = (uint64_t)A*(uint64_t)V*(uint64_t)ch.channels;
     uint64_t const k_set = (uint64_t)A*(uint64_t)(V + 1)*(uint64_t)ch.channels;
-    int const slot = grt_profile_begin(s, GRT_TAG_WEIGHTING_FINISH);
-    int const krc = grt_launch_weighting_finish(s, &ch, &wa, C, S, A, V, wr->transmittance, (uint64_t)ps->sets*t_set,
-                                                (uint64_t)ps->set*t_set, wr->contribution, (uint64_t)ps->sets*k_set,
-                                                (uint64_t)ps->set*k_set);
-    grt_profile_end(s, slot);
-    GRT_TRY(grt_dev_check(krc, "weighting finishing kernel"));
+    GRT_TIMED(s, GRT_TAG_WEIGHTING_FINISH, "weighting finishing kernel",
+              grt_launch_weighting_finish(s, &ch, &wa, C, S, A, V, wr->transmittance, (uint64_t)ps->sets*t_set,
+                                          (uint64_t)ps->set*t_set, wr->contribution, (uint64_t)ps->sets*k_set,
+                                          (uint64_t)ps->set*k_set));
+    return GRTCODE_SUCCESS;
+}
+
+/* The radiances of a pass in two halves: band_radiances queues the launches, radiance_outputs the three finishing steps
+   behind them (a materialised pass of several draws: a launch per draw, then the finish).  pass_radiance_tail is both in
+   a row, for the pass whose draws one launch walk covers (a pass without radiances: nothing). */
+static int radiance_outputs(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass const *ps)
+{
+    GRT_TRY(finish_radiances(p, b, C, S, ps));
+    GRT_TRY(finish_channels(p, b, C, S, ps));
+    GRT_TRY(finish_weighting(p, b, C, S, ps));
+    return GRTCODE_SUCCESS;
+}
+
+static int pass_radiance_tail(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S, GrtPass const *ps, GrtSubcolumnArgs *sc)
+{
+    if (pass_radiances(ps, bi))
+    {
+        GRT_TRY(band_radiances(p, b, C, S, 0, ps, sc));
+        GRT_TRY(radiance_outputs(p, b, C, S, ps));
+    }
     return GRTCODE_SUCCESS;
 }
 
@@ -488,11 +536,9 @@ static int clear_sky_optics(GrtPipeline_t *p, GrtBand *b, int C)
 {
     SpectralGrid_t const *grid = &b->gas->grid;
     void *s = grt_dev_stream(p->device);
-    int const slot = grt_profile_begin(s, GRT_TAG_CLEAR_OPTICS);
-    int const krc = grt_launch_clear_sky_optics(s, p->num_levels - 1, C, grid->w0, grid->dw, b->n, p->small.d + p->off_n,
-                                                b->tau_gas, b->tau, b->omega, b->g);
-    grt_profile_end(s, slot);
-    GRT_TRY(grt_dev_check(krc, "clear-sky optics kernel"));
+    GRT_TIMED(s, GRT_TAG_CLEAR_OPTICS, "clear-sky optics kernel",
+              grt_launch_clear_sky_optics(s, p->num_levels - 1, C, grid->w0, grid->dw, b->n, p->small.d + p->off_n, b->tau_gas,
+                                          b->tau, b->omega, b->g));
     return GRTCODE_SUCCESS;
 }
 
@@ -582,18 +628,27 @@ static int level_rows(GrtPipeline_t *p, GrtBand *b)
     return GRTCODE_SUCCESS;
 }
 
-/* the row-wise trapezoid of the band's spectral fluxes into the pass's rows */
-static int integrate_rows(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps)
+/* the row-wise trapezoid of the band's spectral fluxes, the pass's six rows or 2 V of every column: column c's to
+   out[c out_stride + out_offset ..], under the profile tag `tag` (GRT_UNTIMED: not timed) */
+static int integrate_rows_to(GrtPipeline_t *p, GrtBand *b, int C, GrtPass const *ps, int tag, double *out, int out_stride,
+                             int out_offset)
 {
+    void *s = grt_dev_stream(p->device);
     int const rows = pass_rows(p, ps);
     if (ps->profile)
     {
         GRT_TRY(level_rows(p, b));
     }
-    GRT_TRY(grt_dev_check(grt_launch_integrate_rows(grt_dev_stream(p->device),
-                                                    (double const *const *)(ps->profile ? b->level_rows_d : b->rows_d),
-                                                    C*rows, b->n, b->gas->grid.dw, ps->out, rows, ps->out_stride,
-                                                    pass_offset(p, ps, bi)), "spectral integration kernel"));
+    GRT_TIMED(s, tag, "spectral integration kernel",
+              grt_launch_integrate_rows(s, (double const *const *)(ps->profile ? b->level_rows_d : b->rows_d), C*rows, b->n,
+                                        b->gas->grid.dw, out, rows, out_stride, out_offset));
+    return GRTCODE_SUCCESS;
+}
+
+/* ... into the pass's own rows */
+static int integrate_rows(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *ps)
+{
+    GRT_TRY(integrate_rows_to(p, b, C, ps, GRT_UNTIMED, ps->out, ps->out_stride, pass_offset(p, ps, bi)));
     return GRTCODE_SUCCESS;
 }
 
@@ -608,18 +663,14 @@ static int direct_beam(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass cons
     {
         GrtLwArgs a;
         lw_args(p, b, C, 0, ps, &a);
-        int const slot = grt_profile_begin(s, GRT_TAG_SURFACE_JACOBIAN);
-        int const krc = grt_launch_lw_surface_jacobian(s, &a, b->scratch[GRT_SCRATCH_DIRECT_BEAM].d);
-        grt_profile_end(s, slot);
-        GRT_TRY(grt_dev_check(krc, "surface Jacobian kernel"));
+        GRT_TIMED(s, GRT_TAG_SURFACE_JACOBIAN, "surface Jacobian kernel",
+                  grt_launch_lw_surface_jacobian(s, &a, b->scratch[GRT_SCRATCH_DIRECT_BEAM].d));
         return GRTCODE_SUCCESS;
     }
     GrtSwArgs a;
     sw_args(p, b, C, 0, ps, &a);
-    int const slot = grt_profile_begin(s, GRT_TAG_DIRECT_BEAM);
-    int const krc = grt_launch_sw_direct_beam(s, &a, b->scratch[GRT_SCRATCH_DIRECT_BEAM].d);
-    grt_profile_end(s, slot);
-    GRT_TRY(grt_dev_check(krc, "direct-beam kernel"));
+    GRT_TIMED(s, GRT_TAG_DIRECT_BEAM, "direct-beam kernel",
+              grt_launch_sw_direct_beam(s, &a, b->scratch[GRT_SCRATCH_DIRECT_BEAM].d));
     return GRTCODE_SUCCESS;
 }
 
@@ -685,26 +736,21 @@ static int scatter_park(GrtPipeline_t *p, GrtBand *b, GrtScatterArgs *sa)
     return GRTCODE_SUCCESS;
 }
 
-/* what turns the block's [C][S][rows] rows of nblocks partial sums each into the pass's set of the differences: the
-   fixed-order sum, or -- S > 1 -- the subcolumn mean kernel, draws 0 .. S - 1 in order, one division (GRT_TAG_SCATTER_FINISH) */
+/* what turns the block's [C][S][rows] rows of nblocks partial sums each into the pass's set of the differences
+   (partial_rows; one draw or several, under GRT_TAG_SCATTER_FINISH) */
 static int scatter_finish(GrtPipeline_t *p, GrtBand *b, int C, int S, unsigned nblocks, GrtPass const *ps)
 {
     void *s = grt_dev_stream(p->device);
     int const rows = pass_rows(p, ps);
-    double const *partials = b->scratch[GRT_SCRATCH_SCATTER_PARTIALS].d;
-    int const slot = grt_profile_begin(s, GRT_TAG_SCATTER_FINISH);
-    int const krc = S == 1 ? grt_launch_reduce_partials(s, partials, C*rows, nblocks, ps->scatter->out, rows, ps->sets*rows,
-                                                        ps->set*rows) :
-                             grt_launch_subcolumn_mean(s, partials, C, S, rows, nblocks, ps->scatter->out, ps->sets*rows,
-                                                       ps->set*rows);
-    grt_profile_end(s, slot);
-    GRT_TRY(grt_dev_check(krc, "scattering reduction kernel"));
+    GRT_TIMED(s, GRT_TAG_SCATTER_FINISH, "scattering reduction kernel",
+              partial_rows(s, b->scratch[GRT_SCRATCH_SCATTER_PARTIALS].d, C, S, rows, nblocks, ps->scatter->out, ps->sets*rows,
+                           ps->set*rows));
     return GRTCODE_SUCCESS;
 }
 
 /* Fused form: the scattering kernel in the pass's instance (sc: its clouds as the subcolumns of sc, S of them; NULL:
-   S = 1), its partial sums to GRT_SCRATCH_SCATTER_PARTIALS at the solver's slots, as many draws a launch as the park block
-   of max_cols grid rows holds -- the rule of the shortwave's two-sweep forms --, in stream order; then scatter_finish */
+   S = 1), its partial sums to GRT_SCRATCH_SCATTER_PARTIALS at the solver's slots, as many draws a launch as its park block
+   holds (row_limit), in stream order; then scatter_finish */
 static int scatter_fused(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass const *ps, GrtSubcolumnArgs *sc)
 {
     void *s = grt_dev_stream(p->device);
@@ -717,19 +763,10 @@ static int scatter_fused(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass con
     in.scatter = &sa;
     SolverArgs a;
     GRT_TRY(solver_args(p, b, 0, C, ps, &in, block->d, &a));
+    GrtSubcolumnArgs one, *w = sc != NULL ? sc : &one;                /* (as band_radiances walks) */
     int const slot = grt_profile_begin(s, GRT_TAG_SCATTER_LW);
     int krc = 0;
-    if (sc != NULL)
-    {
-        int group = p->max_cols/C;                                    /* (a park block of max_cols grid rows) */
-        group = group < S ? group : S;
-        for (sc->first = 0; sc->first < S && krc == 0; sc->first += group)
-        {
-            sc->count = S - sc->first < group ? S - sc->first : group;
-            krc = grt_launch_lw_scatter(s, &in, &a.lw);
-        }
-    }
-    else
+    for (w->first = w->count = 0; krc == 0 && walk(sc != NULL ? S : 1, row_limit(p, C, 1), &w->first, &w->count); )
     {
         krc = grt_launch_lw_scatter(s, &in, &a.lw);
     }
@@ -756,19 +793,8 @@ static int scatter_spectral(GrtPipeline_t *p, GrtBand *b, int C, int S, int j, G
     in.scatter = &sa;
     GrtLwArgs a;
     lw_args(p, b, C, 0, ps, &a);
-    int const slot = grt_profile_begin(s, GRT_TAG_SCATTER_LW);
-    int const krc = grt_launch_lw_scatter(s, &in, &a);
-    grt_profile_end(s, slot);
-    GRT_TRY(grt_dev_check(krc, "longwave scattering kernel"));
-    if (ps->profile)
-    {
-        GRT_TRY(level_rows(p, b));
-    }
-    int const fslot = grt_profile_begin(s, GRT_TAG_SCATTER_FINISH);
-    int const irc = grt_launch_integrate_rows(s, (double const *const *)(ps->profile ? b->level_rows_d : b->rows_d), C*rows,
-                                              b->n, b->gas->grid.dw, block->d, rows, S*rows, j*rows);
-    grt_profile_end(s, fslot);
-    GRT_TRY(grt_dev_check(irc, "spectral integration kernel"));
+    GRT_TIMED(s, GRT_TAG_SCATTER_LW, "longwave scattering kernel", grt_launch_lw_scatter(s, &in, &a));
+    GRT_TRY(integrate_rows_to(p, b, C, ps, GRT_TAG_SCATTER_FINISH, block->d, S*rows, j*rows));
     if (j == S - 1)
     {
         GRT_TRY(scatter_finish(p, b, C, S, 1, ps));
@@ -790,9 +816,8 @@ static int band_solve_spectral(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtP
     if (!p->keep_spectra)
     {
         GRT_TRY(band_solver(p, b, bi, C, ps, b->partials, NULL, NULL));
-        GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, b->partials, C*GRT_FLUXES_PER_BAND, b->nblocks, ps->out,
-                                                         GRT_FLUXES_PER_BAND, ps->out_stride, pass_offset(p, ps, bi)),
-                              "flux reduction kernel"));
+        GRT_TRY(grt_dev_check(partial_rows(s, b->partials, C, 1, GRT_FLUXES_PER_BAND, b->nblocks, ps->out, ps->out_stride,
+                                           pass_offset(p, ps, bi)), "flux reduction kernel"));
     }
     else
     {
@@ -809,12 +834,9 @@ static int band_solve_spectral(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtP
         size_t bstride;
         double *binned = so->binned + bins_offset(ps, bi, GRT_FLUXES_PER_BAND, (size_t)so->num_bins[0],
                                                   (size_t)so->num_bins[1], &bstride);
-        int const slot = grt_profile_begin(s, GRT_TAG_BINS);
-        int const krc = grt_launch_bin_rows(s, rows, stride, C*GRT_FLUXES_PER_BAND, b->n, b->gas->grid.dw, nbins,
-                                            b->bin_table.table, b->bin_per_row, b->scratch[GRT_SCRATCH_BIN_PARTIALS].d, binned,
-                                            bstride);
-        grt_profile_end(s, slot);
-        GRT_TRY(grt_dev_check(krc, "spectral binning kernel"));
+        GRT_TIMED(s, GRT_TAG_BINS, "spectral binning kernel",
+                  grt_launch_bin_rows(s, rows, stride, C*GRT_FLUXES_PER_BAND, b->n, b->gas->grid.dw, nbins, b->bin_table.table,
+                                      b->bin_per_row, b->scratch[GRT_SCRATCH_BIN_PARTIALS].d, binned, bstride));
     }
     return GRTCODE_SUCCESS;
 }
@@ -833,25 +855,65 @@ static int band_solve_band_profiles(GrtPipeline_t *p, GrtBand *b, int bi, int C,
     double *out = ps->out + bins_offset(ps, bi, (size_t)rows, (size_t)bp->num_bins[0], (size_t)bp->num_bins[1], &out_stride);
     GRT_TRY(grt_band_bins(p, b, bp->edges[bi], nbins, rows));
     double *bin_partials = b->scratch[GRT_SCRATCH_BIN_PARTIALS].d;
-    int slot, krc;
     if (!p->keep_spectra)
     {
         GrtBandArgs const bn = {nbins, grt_bin_block_max(bp->edges[bi], nbins), b->bin_table.table, b->bin_per_row};
         GRT_TRY(band_solver(p, b, bi, C, ps, bin_partials, &bn, NULL));
-        slot = grt_profile_begin(s, GRT_TAG_BAND_PROFILES);
-        krc = grt_launch_bin_reduce(s, C*rows, V, nbins, b->bin_table.table, b->bin_per_row, bin_partials, out, out_stride);
+        GRT_TIMED(s, GRT_TAG_BAND_PROFILES, "level binning kernel",
+                  grt_launch_bin_reduce(s, C*rows, V, nbins, b->bin_table.table, b->bin_per_row, bin_partials, out, out_stride));
+        return GRTCODE_SUCCESS;
     }
-    else
+    GRT_TRY(pass_optics(p, b, C, ps));
+    GRT_TRY(band_solver(p, b, bi, C, ps, NULL, NULL, NULL));
+    GRT_TRY(level_rows(p, b));
+    GRT_TIMED(s, GRT_TAG_BAND_PROFILES, "level binning kernel",
+              grt_launch_bin_level_rows(s, (double const *const *)b->level_rows_d, C*rows, V, b->n, b->gas->grid.dw, nbins,
+                                        b->bin_table.table, b->bin_per_row, bin_partials, out, out_stride));
+    return GRTCODE_SUCCESS;
+}
+
+/* The steps the fused forms of grt_band_solve and grt_band_solve_subcolumns share, each in its own order.  pass_rows_out:
+   what turns the partial sums of the pass's S draws -- its rows' in `partials`, its third row group's in tr->partials
+   where it leaves one -- into its rows and third rows (partial_rows).  One draw: two fixed-order sums, not timed; several:
+   the two means under one span of GRT_TAG_SUBCOLUMN_MEAN. */
+static int pass_rows_out(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S, GrtPass const *ps, double const *partials,
+                         ThirdRows const *tr)
+{
+    void *s = grt_dev_stream(p->device);
+    int const rows = pass_rows(p, ps), drows = direct_rows(p, ps), offset = pass_offset(p, ps, bi);
+    if (S == 1)
     {
-        GRT_TRY(pass_optics(p, b, C, ps));
-        GRT_TRY(band_solver(p, b, bi, C, ps, NULL, NULL, NULL));
-        GRT_TRY(level_rows(p, b));
-        slot = grt_profile_begin(s, GRT_TAG_BAND_PROFILES);
-        krc = grt_launch_bin_level_rows(s, (double const *const *)b->level_rows_d, C*rows, V, b->n, b->gas->grid.dw, nbins,
-                                        b->bin_table.table, b->bin_per_row, bin_partials, out, out_stride);
+        GRT_TRY(grt_dev_check(partial_rows(s, partials, C, 1, rows, b->nblocks, ps->out, ps->out_stride, offset),
+                              "flux reduction kernel"));
+        if (tr->partials != NULL)
+        {
+            GRT_TRY(grt_dev_check(partial_rows(s, tr->partials, C, 1, drows, b->nblocks, third_out(ps, bi), direct_stride(p, ps),
+                                               direct_offset(p, ps)),
+                                  bi == 1 ? "direct-beam reduction kernel" : "surface Jacobian reduction kernel"));
+        }
+        return GRTCODE_SUCCESS;
+    }
+    int const slot = grt_profile_begin(s, GRT_TAG_SUBCOLUMN_MEAN);
+    int krc = partial_rows(s, partials, C, S, rows, b->nblocks, ps->out, ps->out_stride, offset);
+    if (krc == 0 && tr->partials != NULL)
+    {
+        krc = partial_rows(s, tr->partials, C, S, drows, b->nblocks, third_out(ps, bi), direct_stride(p, ps),
+                           direct_offset(p, ps));
     }
     grt_profile_end(s, slot);
-    GRT_TRY(grt_dev_check(krc, "level binning kernel"));
+    GRT_TRY(grt_dev_check(krc, "subcolumn mean kernel"));
+    return GRTCODE_SUCCESS;
+}
+
+/* ... the longwave's scattering correction and radiances behind the pass's solver (sc: its clouds as the subcolumns of sc;
+   NULL: S = 1) */
+static int pass_scatter_radiances(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S, GrtPass const *ps, GrtSubcolumnArgs *sc)
+{
+    if (pass_scatter(ps, bi))
+    {
+        GRT_TRY(scatter_fused(p, b, C, S, ps, sc));
+    }
+    GRT_TRY(pass_radiance_tail(p, b, bi, C, S, ps, sc));
     return GRTCODE_SUCCESS;
 }
 
@@ -885,55 +947,28 @@ int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *p
         {
             GRT_TRY(scatter_spectral(p, b, C, 1, 0, ps));
         }
-        if (pass_radiances(ps, bi))
-        {
-            GRT_TRY(band_radiances(p, b, C, 1, 0, ps, NULL));
-            GRT_TRY(finish_radiances(p, b, C, 1, ps));
-            GRT_TRY(finish_channels(p, b, C, 1, ps));
-            GRT_TRY(finish_weighting(p, b, C, 1, ps));
-        }
+        GRT_TRY(pass_radiance_tail(p, b, bi, C, 1, ps, NULL));
         return GRTCODE_SUCCESS;
     }
     if (ps->out != NULL)
     {
-        int const rows = pass_rows(p, ps);
         ThirdRows da;
         GRT_TRY(direct_partials(p, b, bi, ps, 1, &da));
         GRT_TRY(response_join(p, b, ps, 1, &da));
         if (ps->profile)
         {
-            GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_LEVEL_PARTIALS], (size_t)p->max_cols*(size_t)rows*b->nblocks,
-                                     NULL));
+            GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_LEVEL_PARTIALS],
+                                     (size_t)p->max_cols*(size_t)pass_rows(p, ps)*b->nblocks, NULL));
         }
         double *partials = ps->profile ? b->scratch[GRT_SCRATCH_LEVEL_PARTIALS].d : b->partials;
         GRT_TRY(band_solver(p, b, bi, C, ps, partials, NULL, &da));
-        GRT_TRY(grt_dev_check(grt_launch_reduce_partials(grt_dev_stream(p->device), partials, C*rows, b->nblocks, ps->out,
-                                                         rows, ps->out_stride, pass_offset(p, ps, bi)),
-                              "flux reduction kernel"));
-        if (da.partials != NULL)
-        {
-            int const drows = direct_rows(p, ps);
-            GRT_TRY(grt_dev_check(grt_launch_reduce_partials(grt_dev_stream(p->device), da.partials, C*drows, b->nblocks,
-                                                             third_out(ps, bi), drows, direct_stride(p, ps),
-                                                             direct_offset(p, ps)),
-                                  bi == 1 ? "direct-beam reduction kernel" : "surface Jacobian reduction kernel"));
-        }
+        GRT_TRY(pass_rows_out(p, b, bi, C, 1, ps, partials, &da));
         if (da.with_responses)
         {
             GRT_TRY(finish_responses(p, C, 1, ps, &da.responses));
         }
     }
-    if (pass_scatter(ps, bi))
-    {
-        GRT_TRY(scatter_fused(p, b, C, 1, ps, NULL));
-    }
-    if (pass_radiances(ps, bi))
-    {
-        GRT_TRY(band_radiances(p, b, C, 1, 0, ps, NULL));
-        GRT_TRY(finish_radiances(p, b, C, 1, ps));
-        GRT_TRY(finish_channels(p, b, C, 1, ps));
-        GRT_TRY(finish_weighting(p, b, C, 1, ps));
-    }
+    GRT_TRY(pass_scatter_radiances(p, b, bi, C, 1, ps, NULL));
     return GRTCODE_SUCCESS;
 }
 
@@ -946,84 +981,44 @@ int grt_band_solve(GrtPipeline_t *p, GrtBand *b, int bi, int C, GrtPass const *p
    and the sum of its fluxes; then the mean into the band's flux arrays, and the row-wise trapezoid. */
 int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S, GrtPass const *ps)
 {
-    int const V = p->num_levels, rows = pass_rows(p, ps), out_offset = pass_offset(p, ps, bi);
+    int const V = p->num_levels;
     void *s = grt_dev_stream(p->device);
-    if (!p->keep_spectra && ps->out == NULL)
-    {
-        /* (grt_pipeline_run_sky_radiances without flux rows: the radiance kernel in the solver's place) */
-        GrtSubcolumnArgs sc = {*ps->clouds, S, 0, 0};
-        GRT_TRY(band_radiances(p, b, C, S, 0, ps, &sc));
-        GRT_TRY(finish_radiances(p, b, C, S, ps));
-        GRT_TRY(finish_channels(p, b, C, S, ps));
-        GRT_TRY(finish_weighting(p, b, C, S, ps));
-        return GRTCODE_SUCCESS;
-    }
     if (!p->keep_spectra)
     {
-        GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_SUB_PARTIALS],
-                                 (size_t)p->max_cols*(size_t)S*(size_t)rows*b->nblocks, NULL));
-        double *sub_partials = b->scratch[GRT_SCRATCH_SUB_PARTIALS].d;
-        /* (in points at sc: the loop below walks sc.first and sc.count, which the launcher alone reads) */
+        /* (in points at sc: the walks go over sc.first and sc.count, which the launchers alone read) */
         GrtSubcolumnArgs sc = {*ps->clouds, S, 0, 0};
+        if (ps->out == NULL)
+        {
+            /* (grt_pipeline_run_sky_radiances without flux rows: the radiance kernel in the solver's place) */
+            GRT_TRY(pass_radiance_tail(p, b, bi, C, S, ps, &sc));
+            return GRTCODE_SUCCESS;
+        }
+        GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_SUB_PARTIALS],
+                                 (size_t)p->max_cols*(size_t)S*(size_t)pass_rows(p, ps)*b->nblocks, NULL));
+        double *sub_partials = b->scratch[GRT_SCRATCH_SUB_PARTIALS].d;
         ThirdRows da;
         GRT_TRY(direct_partials(p, b, bi, ps, S, &da));
         GRT_TRY(response_join(p, b, ps, S, &da));
-        int const drows = direct_rows(p, ps);
         GrtSolverInstance const in = pass_instance(p, ps, NULL, &sc, &da, bi);
         SolverArgs a;
         GRT_TRY(solver_args(p, b, bi, C, ps, &in, sub_partials, &a));
-        /* (grid rows; a park block of max_cols columns) */
-        int group = bi == 1 && grt_sw_parks(&in, &a.sw) ? p->max_cols/C : 65535/C;
-        group = group < S ? group : S;
+        int const group = row_limit(p, C, bi == 1 && grt_sw_parks(&in, &a.sw));
         int const slot = grt_profile_begin(s, pass_tag(ps, bi));
         int krc = 0;
-        for (sc.first = 0; sc.first < S && krc == 0; sc.first += group)
+        for (sc.first = sc.count = 0; krc == 0 && walk(S, group, &sc.first, &sc.count); )
         {
-            sc.count = S - sc.first < group ? S - sc.first : group;
             krc = solver_launch(s, bi, &in, &a);
         }
         grt_profile_end(s, slot);
         GRT_TRY(grt_dev_check(krc, bi == 0 ? "longwave subcolumn kernel" : "shortwave subcolumn kernel"));
-        if (pass_scatter(ps, bi))
-        {
-            GRT_TRY(scatter_fused(p, b, C, S, ps, &sc));
-        }
-        if (pass_radiances(ps, bi))
-        {
-            GRT_TRY(band_radiances(p, b, C, S, 0, ps, &sc));
-            GRT_TRY(finish_radiances(p, b, C, S, ps));
-            GRT_TRY(finish_channels(p, b, C, S, ps));
-            GRT_TRY(finish_weighting(p, b, C, S, ps));
-        }
+        GRT_TRY(pass_scatter_radiances(p, b, bi, C, S, ps, &sc));
         if (da.with_responses)
         {
             GRT_TRY(finish_responses(p, C, S, ps, &da.responses));
         }
-        if (S == 1)
-        {
-            GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, sub_partials, C*rows, b->nblocks, ps->out, rows,
-                                                             ps->out_stride, out_offset), "flux reduction kernel"));
-            if (da.partials != NULL)
-            {
-                GRT_TRY(grt_dev_check(grt_launch_reduce_partials(s, da.partials, C*drows, b->nblocks, third_out(ps, bi), drows,
-                                                                 direct_stride(p, ps), direct_offset(p, ps)),
-                                      bi == 1 ? "direct-beam reduction kernel" : "surface Jacobian reduction kernel"));
-            }
-            return GRTCODE_SUCCESS;
-        }
-        int const mslot = grt_profile_begin(s, GRT_TAG_SUBCOLUMN_MEAN);
-        int mrc = grt_launch_subcolumn_mean(s, sub_partials, C, S, rows, b->nblocks, ps->out, ps->out_stride, out_offset);
-        if (mrc == 0 && da.partials != NULL)
-        {
-            /* (the same kernel: subcolumns 0 .. S - 1 in order, then one division by S) */
-            mrc = grt_launch_subcolumn_mean(s, da.partials, C, S, drows, b->nblocks, third_out(ps, bi), direct_stride(p, ps),
-                                            direct_offset(p, ps));
-        }
-        grt_profile_end(s, mslot);
-        GRT_TRY(grt_dev_check(mrc, "subcolumn mean kernel"));
+        GRT_TRY(pass_rows_out(p, b, bi, C, S, ps, sub_partials, &da));
         return GRTCODE_SUCCESS;
     }
-    size_t const tab = (size_t)C*3*(size_t)ps->clouds->num_bands*(size_t)(V - 1);
     uint64_t const per = (uint64_t)C*(uint64_t)V*b->n, all = (uint64_t)p->max_cols*(uint64_t)V*b->n;
     GRT_TRY(grt_scratch_need(p, &b->scratch[GRT_SCRATCH_FLUX_SUM], 2*all, NULL));
     double *flux_sum = b->scratch[GRT_SCRATCH_FLUX_SUM].d;
@@ -1034,11 +1029,8 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
     double *direct_sum = b->scratch[GRT_SCRATCH_DIRECT_SUM].d;
     for (int j = 0; j < S; ++j)
     {
-        GrtCloudArgs cj = *ps->clouds;
-        cj.liquid += (size_t)j*tab;
-        cj.ice += (size_t)j*tab;
-        GrtPass pj = *ps;
-        pj.clouds = &cj;
+        GrtCloudArgs cj;
+        GrtPass const pj = pass_draw(p, ps, C, j, &cj);
         GRT_TRY(pass_optics(p, b, C, &pj));
         if (pass_radiances(ps, bi))
         {
@@ -1065,9 +1057,7 @@ int grt_band_solve_subcolumns(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S
     }
     if (pass_radiances(ps, bi))
     {
-        GRT_TRY(finish_radiances(p, b, C, S, ps));
-        GRT_TRY(finish_channels(p, b, C, S, ps));
-        GRT_TRY(finish_weighting(p, b, C, S, ps));
+        GRT_TRY(radiance_outputs(p, b, C, S, ps));
     }
     if (ps->out == NULL)
     {
@@ -1132,14 +1122,7 @@ int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass c
         GrtDirectArgs const da = {dblock->d};
         /* (in points at za and sc: the loops below walk their first and count, which the launchers alone read) */
         GrtZenithArgs za = {zr->mu, Z, 0, 0};
-        GrtSubcolumnArgs sc;
-        memset(&sc, 0, sizeof(sc));
-        if (ps->clouds != NULL)
-        {
-            sc.clouds = *ps->clouds;
-            sc.subcolumns = S;
-        }
-        GrtSubcolumnArgs *draws = ps->clouds != NULL ? &sc : NULL;
+        GrtSubcolumnArgs sc, *draws = pass_subcolumns(ps, S, &sc);
         GrtSolverInstance in = pass_instance(p, ps, NULL, draws, NULL, 1);
         in.zeniths = &za;
         in.direct = zr->direct || sl != NULL ? &da : NULL;
@@ -1148,36 +1131,25 @@ int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass c
         SolverArgs a;
         GRT_TRY(solver_args(p, b, 1, C, ps, &in, block->d, &a));
         char const *env = getenv("GRT_ZENITH_SHARED");
-        int const parks = grt_sw_parks(&in, &a.sw);
-        /* (grid rows; a park block of max_cols columns) */
-        int const limit = parks ? p->max_cols/C : 65535/C;
+        int const parks = grt_sw_parks(&in, &a.sw), limit = row_limit(p, C, parks);
         int const chunk = grt_zenith_chunk(draws, ps->aer, in.direct, zs, sl), chunks = (Z + chunk - 1)/chunk;
         int const shared = !ps->profile && !parks && chunks <= limit &&
                            (joined ? env != NULL && env[0] == '1' : !(env != NULL && env[0] == '0'));
+        /* the grid rows a draw of a column takes in one launch: every chunk of the shared-layer kernel, which walks no
+           angles (za stays as it is), or the angles of a launch of the zenith instances */
+        int const per_draw = shared ? chunks : (limit < Z ? limit : Z);
         int const slot = grt_profile_begin(s, sw_tag);
         int krc = 0;
-        if (shared)
+        for (sc.first = sc.count = 0; krc == 0 && walk(S, limit/per_draw, &sc.first, &sc.count); )
         {
-            int const group = limit/chunks < S ? limit/chunks : S;
-            sc.count = S;
-            for (sc.first = 0; sc.first < S && krc == 0; sc.first += group)
+            if (shared)
             {
-                sc.count = S - sc.first < group ? S - sc.first : group;
                 krc = grt_launch_sw_zeniths(s, &a.sw, &za, draws, ps->aer, in.direct, zs, sl);
+                continue;
             }
-        }
-        else
-        {
-            int const angles = limit < Z ? limit : Z;
-            int const group = limit/angles < S ? limit/angles : S;
-            for (sc.first = 0; sc.first < S && krc == 0; sc.first += group)
+            for (za.first = za.count = 0; krc == 0 && walk(Z, per_draw, &za.first, &za.count); )
             {
-                sc.count = S - sc.first < group ? S - sc.first : group;
-                for (za.first = 0; za.first < Z && krc == 0; za.first += angles)
-                {
-                    za.count = Z - za.first < angles ? Z - za.first : angles;
-                    krc = grt_launch_sw(s, &in, &a.sw);
-                }
+                krc = grt_launch_sw(s, &in, &a.sw);
             }
         }
         grt_profile_end(s, slot);
@@ -1188,9 +1160,8 @@ int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass c
         GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*(size_t)Z*(size_t)S*(size_t)rows, NULL));
         if (ps->profile)
         {
-            GRT_TRY(level_rows(p, b));
+            GRT_TRY(level_rows(p, b));         /* (the table ahead of the call's other blocks, not at the first trapezoid) */
         }
-        size_t const tab = ps->clouds != NULL ? (size_t)C*3*(size_t)ps->clouds->num_bands*(size_t)(p->num_levels - 1) : 0;
         if (zr->direct)
         {
             GRT_TRY(grt_scratch_need(p, dblock, (size_t)p->max_cols*(size_t)Z*(size_t)S*(size_t)drows, NULL));
@@ -1218,14 +1189,7 @@ int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass c
         for (int j = 0; j < S; ++j)
         {
             GrtCloudArgs cj;
-            GrtPass pj = *ps;
-            if (ps->clouds != NULL)
-            {
-                cj = *ps->clouds;
-                cj.liquid += (size_t)j*tab;
-                cj.ice += (size_t)j*tab;
-                pj.clouds = &cj;
-            }
+            GrtPass const pj = pass_draw(p, ps, C, j, &cj);
             GRT_TRY(pass_optics(p, b, C, &pj));
             GrtSolverInstance const in = pass_instance(p, &pj, NULL, NULL, NULL, 1);
             SolverArgs a;
@@ -1237,51 +1201,36 @@ int grt_band_solve_zeniths(GrtPipeline_t *p, GrtBand *b, int C, int S, GrtPass c
                 {
                     GrtSurfaceArgs const sa = {zs->num_entries, zs->entry,
                                                zs->tables + (size_t)k*(size_t)C*(size_t)zs->num_entries*2};
-                    int const rslot = grt_profile_begin(s, GRT_TAG_SURFACE);
-                    int const rrc = grt_launch_spread_surface(s, C, b->gas->grid.w0, b->gas->grid.dw, b->n, &sa, angle_rows);
-                    grt_profile_end(s, rslot);
-                    GRT_TRY(grt_dev_check(rrc, "surface row kernel"));
+                    GRT_TIMED(s, GRT_TAG_SURFACE, "surface row kernel",
+                              grt_launch_spread_surface(s, C, b->gas->grid.w0, b->gas->grid.dw, b->n, &sa, angle_rows));
                     a.sw.alb_dir = angle_rows;
                     a.sw.alb_dif = dif_rows != NULL ? dif_rows : a.sw.alb_dif;
                     a.sw.alb_stride = b->n;
                 }
-                int const slot = grt_profile_begin(s, sw_tag);
-                int const krc = grt_launch_sw(s, &in, &a.sw);
-                grt_profile_end(s, slot);
-                GRT_TRY(grt_dev_check(krc, "shortwave kernel"));
-                GRT_TRY(grt_dev_check(grt_launch_integrate_rows(s, (double const *const *)(ps->profile ? b->level_rows_d : b->rows_d),
-                                                                C*rows, b->n, b->gas->grid.dw, block->d, rows, Z*S*rows,
-                                                                (k*S + j)*rows),
-                                      "spectral integration kernel"));
+                GRT_TIMED(s, sw_tag, "shortwave kernel", grt_launch_sw(s, &in, &a.sw));
+                GRT_TRY(integrate_rows_to(p, b, C, ps, GRT_UNTIMED, block->d, Z*S*rows, (k*S + j)*rows));
                 if (zr->direct)
                 {
                     /* the angle's direct beam on the grid from the draw's optics, and its row-wise trapezoid */
-                    int const dslot = grt_profile_begin(s, GRT_TAG_DIRECT_BEAM);
-                    int const drc = grt_launch_sw_direct_beam(s, &a.sw, b->scratch[GRT_SCRATCH_DIRECT_BEAM].d);
-                    grt_profile_end(s, dslot);
-                    GRT_TRY(grt_dev_check(drc, "direct-beam kernel"));
+                    GRT_TIMED(s, GRT_TAG_DIRECT_BEAM, "direct-beam kernel",
+                              grt_launch_sw_direct_beam(s, &a.sw, b->scratch[GRT_SCRATCH_DIRECT_BEAM].d));
                     GRT_TRY(direct_integrate_to(p, b, 1, C, ps, dblock->d, Z*S*drows, (k*S + j)*drows));
                 }
             }
         }
     }
-    int const mslot = grt_profile_begin(s, zr->sky ? GRT_TAG_SKY_ZENITH_MEAN : GRT_TAG_ZENITH_MEAN);
-    int const mrc = zr->sky ?
-        grt_launch_sky_zenith_mean(s, block->d, C, Z, S, rows, nblocks, zr->mu, zr->weight, zr->per_angle, zr->six, ps->sets,
-                                   ps->set, p->user_level, ps->out, ps->out_stride, out_offset) :
-        grt_launch_zenith_mean(s, block->d, C, Z, rows, nblocks, zr->mu, zr->weight, zr->per_angle, zr->six, p->user_level,
-                               ps->out, ps->out_stride, out_offset);
-    grt_profile_end(s, mslot);
-    GRT_TRY(grt_dev_check(mrc, "zenith mean kernel"));
+    GRT_TIMED(s, zr->sky ? GRT_TAG_SKY_ZENITH_MEAN : GRT_TAG_ZENITH_MEAN, "zenith mean kernel", zr->sky ?
+              grt_launch_sky_zenith_mean(s, block->d, C, Z, S, rows, nblocks, zr->mu, zr->weight, zr->per_angle, zr->six,
+                                         ps->sets, ps->set, p->user_level, ps->out, ps->out_stride, out_offset) :
+              grt_launch_zenith_mean(s, block->d, C, Z, rows, nblocks, zr->mu, zr->weight, zr->per_angle, zr->six,
+                                     p->user_level, ps->out, ps->out_stride, out_offset));
     if (zr->direct)
     {
         /* (the same kernel on the direct beam's three rows or V: the draws, one division, then the angles) */
-        int const dslot = grt_profile_begin(s, GRT_TAG_SKY_ZENITH_MEAN);
-        int const drc = grt_launch_sky_zenith_mean(s, dblock->d, C, Z, S, drows, nblocks, zr->mu, zr->weight,
-                                                   zr->direct_per_angle, NULL, ps->sets, ps->set, p->user_level,
-                                                   zr->direct_out, direct_stride(p, ps), direct_offset(p, ps));
-        grt_profile_end(s, dslot);
-        GRT_TRY(grt_dev_check(drc, "zenith mean kernel"));
+        GRT_TIMED(s, GRT_TAG_SKY_ZENITH_MEAN, "zenith mean kernel",
+                  grt_launch_sky_zenith_mean(s, dblock->d, C, Z, S, drows, nblocks, zr->mu, zr->weight, zr->direct_per_angle,
+                                             NULL, ps->sets, ps->set, p->user_level, zr->direct_out, direct_stride(p, ps),
+                                             direct_offset(p, ps)));
     }
     return GRTCODE_SUCCESS;
 }
@@ -1311,32 +1260,22 @@ int grt_band_solve_tiles(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S, Grt
         nblocks = b->nblocks;
         GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*(size_t)T*(size_t)S*(size_t)rows*nblocks, NULL));
         /* (the loops below walk sc's and ta's first and count, which the launchers alone read) */
-        GrtSubcolumnArgs sc;
-        memset(&sc, 0, sizeof(sc));
-        if (ps->clouds != NULL)
-        {
-            sc.clouds = *ps->clouds;
-            sc.subcolumns = S;
-        }
-        GrtSubcolumnArgs *draws = ps->clouds != NULL ? &sc : NULL;
+        GrtSubcolumnArgs sc, *draws = pass_subcolumns(ps, S, &sc);
         GrtSolverInstance const in = pass_instance(p, ps, NULL, draws, NULL, bi);
         SolverArgs a;
         GRT_TRY(solver_args(p, b, bi, C, ps, &in, block->d, &a));
         GrtTileArgs ta = {T, 0, 0, tr->t_surf, tile_rows, tile_rows_dif};
         int const chunk = grt_tile_chunk(draws, ps->aer), chunks = (T + chunk - 1)/chunk;
-        /* (grid rows; the two sweeps: (draw, chunk) pairs of C rows each in a park block of max_cols rows) */
-        int const parks = bi == 1 && grt_sw_parks(&in, &a.sw);
-        int const per_launch = parks ? (p->max_cols/C < chunks ? p->max_cols/C : chunks) : chunks;
-        int group = parks ? p->max_cols/C/per_launch : 65535/C;
-        group = group < S ? group : S;
+        /* (the chunks lie along the grid's z, so they count against the park block alone: the two sweeps park (draw, chunk)
+           pairs of C rows each) */
+        int const parks = bi == 1 && grt_sw_parks(&in, &a.sw), limit = row_limit(p, C, parks);
+        int const per_launch = parks && limit < chunks ? limit : chunks;
         int const slot = grt_profile_begin(s, tag);
         int krc = 0;
-        for (sc.first = 0; sc.first < S && krc == 0; sc.first += group)
+        for (sc.first = sc.count = 0; krc == 0 && walk(S, parks ? limit/per_launch : limit, &sc.first, &sc.count); )
         {
-            sc.count = S - sc.first < group ? S - sc.first : group;
-            for (ta.chunk_first = 0; ta.chunk_first < chunks && krc == 0; ta.chunk_first += per_launch)
+            for (ta.chunk_first = ta.chunk_count = 0; krc == 0 && walk(chunks, per_launch, &ta.chunk_first, &ta.chunk_count); )
             {
-                ta.chunk_count = chunks - ta.chunk_first < per_launch ? chunks - ta.chunk_first : per_launch;
                 krc = bi == 0 ? grt_launch_lw_tiles(s, &a.lw, &ta, draws, ps->aer) :
                                 grt_launch_sw_tiles(s, &a.sw, &ta, draws, ps->aer);
             }
@@ -1347,18 +1286,10 @@ int grt_band_solve_tiles(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S, Grt
     else
     {
         GRT_TRY(grt_scratch_need(p, block, (size_t)p->max_cols*(size_t)T*(size_t)S*(size_t)rows, NULL));
-        size_t const tab = ps->clouds != NULL ? (size_t)C*3*(size_t)ps->clouds->num_bands*(size_t)(p->num_levels - 1) : 0;
         for (int j = 0; j < S; ++j)
         {
             GrtCloudArgs cj;
-            GrtPass pj = *ps;
-            if (ps->clouds != NULL)
-            {
-                cj = *ps->clouds;
-                cj.liquid += (size_t)j*tab;
-                cj.ice += (size_t)j*tab;
-                pj.clouds = &cj;
-            }
+            GrtPass const pj = pass_draw(p, ps, C, j, &cj);
             GRT_TRY(pass_optics(p, b, C, &pj));
             GrtSolverInstance const in = pass_instance(p, &pj, NULL, NULL, NULL, bi);
             SolverArgs a;
@@ -1381,21 +1312,14 @@ int grt_band_solve_tiles(GrtPipeline_t *p, GrtBand *b, int bi, int C, int S, Grt
                     a.sw.alb_dif = (tile_rows_dif != NULL ? tile_rows_dif : tile_rows) + (size_t)t*b->n;
                     a.sw.alb_stride = (uint64_t)T*b->n;
                 }
-                int const slot = grt_profile_begin(s, tag);
-                int const krc = solver_launch(s, bi, &in, &a);
-                grt_profile_end(s, slot);
-                GRT_TRY(grt_dev_check(krc, bi == 0 ? "longwave kernel" : "shortwave kernel"));
-                GRT_TRY(grt_dev_check(grt_launch_integrate_rows(s, (double const *const *)b->rows_d, C*rows, b->n,
-                                                                b->gas->grid.dw, block->d, rows, T*S*rows, (t*S + j)*rows),
-                                      "spectral integration kernel"));
+                GRT_TIMED(s, tag, bi == 0 ? "longwave kernel" : "shortwave kernel", solver_launch(s, bi, &in, &a));
+                GRT_TRY(integrate_rows_to(p, b, C, ps, GRT_UNTIMED, block->d, T*S*rows, (t*S + j)*rows));
             }
         }
     }
-    int const mslot = grt_profile_begin(s, GRT_TAG_TILE_MEAN);
-    int const mrc = grt_launch_tile_mean(s, block->d, C, T, S, nblocks, tr->fraction, tr->per_tile, ps->sets, ps->set, bi,
-                                         ps->out, ps->out_stride, pass_offset(p, ps, bi));
-    grt_profile_end(s, mslot);
-    GRT_TRY(grt_dev_check(mrc, "tile mean kernel"));
+    GRT_TIMED(s, GRT_TAG_TILE_MEAN, "tile mean kernel",
+              grt_launch_tile_mean(s, block->d, C, T, S, nblocks, tr->fraction, tr->per_tile, ps->sets, ps->set, bi, ps->out,
+                                   ps->out_stride, pass_offset(p, ps, bi)));
     return GRTCODE_SUCCESS;
 }
 
