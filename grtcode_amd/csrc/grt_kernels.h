@@ -326,10 +326,12 @@ typedef struct GrtSwArgs
        doubles through the same expressions: identical fluxes) */
     double *layer_props;
 } GrtSwArgs;
-/* whether the fused form takes its one sweep (the rule above; sw_kernel keeps its own copy) */
+/* whether the fused form takes its one sweep (the rule above): the one expression, for the kernels on their own copies of
+   the user level, the last level's index and the flag, and for the host on the arguments */
+#define GRT_SW_ONE_SWEEP(user, last, one_sweep) (((user) < 0 || (user) == 0 || (user) == (last)) && (one_sweep))
 static inline int grt_sw_one_sweep(GrtSwArgs const *a)
 {
-    return a->one_sweep && (a->user_level < 0 || a->user_level == 0 || a->user_level == a->num_levels - 1);
+    return GRT_SW_ONE_SWEEP(a->user_level, a->num_levels - 1, a->one_sweep);
 }
 
 /* Profile form of the fused solvers (GRT_OUT_LEVELS, grt_pipeline_run_profiles): the fused form's arguments, but every

@@ -813,7 +813,8 @@ __global__ __launch_bounds__(kSweepBlock) void lw_sweeps_kernel(GrtLwArgs a)
 // emissivity row, planck() of the tile's temperature, surface_step --, and on the way up forms a layer's optical depth, its
 // two Planck terms and its four extinctions once and runs beam_step and the c2 sum per tile, in stream_step's order.
 // Every tile's six rows leave through a LevelSink at the tile's slot (c tiles + t) subcolumns + s: lw_kernel's doubles
-// through lw_kernel's sums.  Tiles past the column's last are skipped by a flag that is uniform per workgroup.
+// through lw_kernel's sums.  What the chunk is and which of its tiles the column has: TileChunk (optics_dev.h); tiles past
+// the column's last are skipped by a flag that is uniform per workgroup.
 // the three rows of one direction, as LevelSink::put keeps them (TOA, surface, user level)
 __device__ __forceinline__ void keep_row(double (&three)[3], int lev, int V, int user, double x)
 {
@@ -827,15 +828,10 @@ __global__ __launch_bounds__(kSolverBlock) void lw_tile_kernel(GrtLwArgs a, GrtT
 {
     uint64_t const i = (uint64_t)blockIdx.x*kSolverBlock + threadIdx.x;
     LwPoint<true, Joins...> const p(a, i, joins...);             // (idle lanes of the last block follow along, weight 0)
-    int const L = p.L, V = p.V, T = tl.tiles, user = a.user_level;
-    int const k0 = (tl.chunk_first + (int)blockIdx.z)*TN;
+    int const L = p.L, V = p.V, user = a.user_level;
+    TileChunk<TN> const chunk(tl, p.row, joins...);
+    int const T = chunk.T, k0 = chunk.k0, S = chunk.S, draw = chunk.draw;
     double const w = p.w;
-    int S = 1;
-    if constexpr (has<GrtSubcolumnArgs, Joins...>)
-    {
-        S = pick<GrtSubcolumnArgs>(joins...).subcolumns;
-    }
-    int const draw = p.row.slot - p.col*S;
 
     // the downward sweep, shared by the tiles
     double down[3] = {0., 0., 0.};                                       // longwave.c:171
@@ -857,7 +853,7 @@ __global__ __launch_bounds__(kSolverBlock) void lw_tile_kernel(GrtLwArgs a, GrtT
         {
             I[u][s] = I0[s];
         }
-        if (k0 + u < T)
+        if (chunk.live(u))
         {
             uint64_t const tile = (uint64_t)p.col*T + k0 + u;
             double const emis = tl.rows != nullptr ? tl.rows[tile*p.nw + p.ii] : p.emis;
@@ -877,7 +873,7 @@ __global__ __launch_bounds__(kSolverBlock) void lw_tile_kernel(GrtLwArgs a, GrtT
 #pragma unroll
         for (int u = 0; u < TN; ++u)
         {
-            if (k0 + u < T)
+            if (chunk.live(u))
             {
                 keep_row(up[u], j, V, user, stream_step(I[u], val, [&](int s) { return e[s]; }));
             }
@@ -886,11 +882,11 @@ __global__ __launch_bounds__(kSolverBlock) void lw_tile_kernel(GrtLwArgs a, GrtT
 #pragma unroll
     for (int u = 0; u < TN; ++u)
     {
-        if (k0 + u >= T)
+        if (!chunk.live(u))
         {
             continue;
         }
-        LevelSink<true, false> sink(a, (p.col*T + k0 + u)*S + draw, i, p.live);
+        LevelSink<true, false> sink(a, (p.col*T + k0 + u)*S + draw, i, p.live);       // (TileChunk's slot rule: a copy)
 #pragma unroll
         for (int k = 0; k < 3; ++k)
         {

@@ -265,6 +265,26 @@ __global__ __launch_bounds__(64) void subcolumn_mean_kernel(double const *partia
     }
 }
 
+// The mean over the draws of output row r, in subcolumn_mean_kernel's order: draw s of S lies at slot first + s of `rows`
+// rows; each draw's blocks by wave_strided_sum, the draws in order, then one division by S.  S = 1: the slot's sum as it
+// is, behind a branch of its own -- written as a select, the division is evaluated for every row and thrown away.
+// (subcolumn_mean_kernel keeps its own loop: it divides whatever S is, and through this helper its code grew by seven
+// instructions and changed registers.)
+__device__ __forceinline__ double draws_mean(double const *partials, uint64_t first, int S, int rows, int r, unsigned nblocks)
+{
+    if (S == 1)
+    {
+        return wave_strided_sum(partials + (first*rows + r)*nblocks, nblocks);
+    }
+    double x = 0.;
+    for (int s = 0; s < S; ++s)
+    {
+        double const xs = wave_strided_sum(partials + ((first + s)*rows + r)*nblocks, nblocks);
+        x = s == 0 ? xs : x + xs;
+    }
+    return x/(double)S;
+}
+
 // The materialised form's subcolumn loop (driver.c:503-589): sum += x per subcolumn (first: the sum starts at 0), then
 // x = sum/S
 __global__ __launch_bounds__(kBlock) void flux_accumulate_kernel(uint64_t n, double const *x, double *sum, int first)
@@ -474,63 +494,36 @@ __global__ __launch_bounds__(kBlock) void band_profile_finish_kernel(int ncol, i
     heating[(cs*nb + q)*L + j] = heating_rate(gravity, cp, pressure + (uint64_t)c*V, up, dn, j);
 }
 
-// grt_pipeline_run_zeniths: every sun angle's own rows, and their weighted mean over a column's Z angles.  One wavefront
-// per (column, row): each angle's block sums by wave_strided_sum as reduce_partials_kernel adds them (a night angle,
-// mu <= 0: +0.0), stored per angle; then the angles in order -- w_k x_k, the product rounded before it is added, or,
-// without weights, the plain sum and one division by Z as subcolumn_mean_kernel's.  Z = 1 without weights:
-// reduce_partials_kernel's bits.  six (profile form, rows = 2 V: up then down levels): every angle's six rows too, its
-// level rows 0, V - 1 and user as profile_finish_kernel picks them.
-__global__ __launch_bounds__(64) void zenith_mean_kernel(double const *partials, int Z, int rows, unsigned nblocks,
-                                                         double const *mu, double const *weight, double *per_angle,
-                                                         double *six, int user, double *out, int out_stride,
-                                                         int out_offset)
+// Level row r of the profile form's rows = 2 V (up then down levels) among the six rows at `six`: rows 0, V - 1 and user as
+// profile_finish_kernel picks them, +0.0 without a user level
+__device__ __forceinline__ void keep_six_rows(double *six, int rows, int r, int user, double x)
 {
-    int const c = blockIdx.x/rows;
-    int const r = blockIdx.x - c*rows;
-    double m = 0.;
-    for (int k = 0; k < Z; ++k)
+    int const V = rows/2, down = r/V, lev = r - down*V;
+    double *q = six + 3*down;
+    if (lev == 0)
     {
-        uint64_t const slot = (uint64_t)c*Z + k;
-        double x = wave_strided_sum(partials + (slot*rows + r)*nblocks, nblocks);
-        x = mu[slot] > 0. ? x : 0.;
-        if (per_angle != nullptr && threadIdx.x == 0)
+        q[0] = x;
+        if (user < 0)
         {
-            per_angle[slot*rows + r] = x;
+            q[2] = 0.;
         }
-        if (six != nullptr && threadIdx.x == 0)
-        {
-            int const V = rows/2, down = r/V, lev = r - down*V;
-            double *q = six + slot*6 + 3*down;
-            if (lev == 0)
-            {
-                q[0] = x;
-                if (user < 0)
-                {
-                    q[2] = 0.;
-                }
-            }
-            if (lev == V - 1)
-            {
-                q[1] = x;
-            }
-            if (lev == user)
-            {
-                q[2] = x;
-            }
-        }
-        double const term = weight != nullptr ? weight[slot]*x : x;
-        m = k == 0 ? term : m + term;
     }
-    if (out != nullptr && threadIdx.x == 0)
+    if (lev == V - 1)
     {
-        out[(uint64_t)c*out_stride + out_offset + r] = weight != nullptr ? m : m/(double)Z;
+        q[1] = x;
+    }
+    if (lev == user)
+    {
+        q[2] = x;
     }
 }
 
-// grt_pipeline_run_sky_zeniths: zenith_mean_kernel for one set of a column's `sets`, over partial sums that hold S cloud
-// draws per angle (slot (c Z + k) S + s).  One wavefront per (column, row): blocks as reduce_partials_kernel adds them,
-// the draws in order and one division by S as subcolumn_mean_kernel's (S = 1: none), a night angle +0.0, the angle's
-// value stored where the set's per-angle rows lie; then the angles as zenith_mean_kernel folds them.
+// grt_pipeline_run_zeniths (S = 1, sets = 1, set = 0) and grt_pipeline_run_sky_zeniths, one set of a column's `sets`: every
+// sun angle's own rows, and their weighted mean over a column's Z angles, over partial sums that hold S cloud draws per
+// angle (slot (c Z + k) S + s).  One wavefront per (column, row): the angle's draws_mean (a night angle, mu <= 0: +0.0),
+// stored where the set's per-angle rows lie; then the angles in order -- w_k x_k, the product rounded before it is added,
+// or, without weights, the plain sum and one division by Z as subcolumn_mean_kernel's.  Z = 1 and S = 1 without weights:
+// reduce_partials_kernel's bits.  six (profile form): every angle's six rows too (keep_six_rows).
 __global__ __launch_bounds__(64) void sky_zenith_mean_kernel(double const *partials, int Z, int S, int rows, unsigned nblocks,
                                                              double const *mu, double const *weight, double *per_angle,
                                                              double *six, int sets, int set, int user, double *out,
@@ -542,13 +535,7 @@ __global__ __launch_bounds__(64) void sky_zenith_mean_kernel(double const *parti
     for (int k = 0; k < Z; ++k)
     {
         uint64_t const sun = (uint64_t)c*Z + k, angle = ((uint64_t)c*sets + set)*Z + k;
-        double x = 0.;
-        for (int s = 0; s < S; ++s)
-        {
-            double const xs = wave_strided_sum(partials + ((sun*S + s)*rows + r)*nblocks, nblocks);
-            x = s == 0 ? xs : x + xs;
-        }
-        x = S > 1 ? x/(double)S : x;
+        double x = draws_mean(partials, sun*S, S, rows, r, nblocks);
         x = mu[sun] > 0. ? x : 0.;
         if (per_angle != nullptr && threadIdx.x == 0)
         {
@@ -556,24 +543,7 @@ __global__ __launch_bounds__(64) void sky_zenith_mean_kernel(double const *parti
         }
         if (six != nullptr && threadIdx.x == 0)
         {
-            int const V = rows/2, down = r/V, lev = r - down*V;
-            double *q = six + angle*6 + 3*down;
-            if (lev == 0)
-            {
-                q[0] = x;
-                if (user < 0)
-                {
-                    q[2] = 0.;
-                }
-            }
-            if (lev == V - 1)
-            {
-                q[1] = x;
-            }
-            if (lev == user)
-            {
-                q[2] = x;
-            }
+            keep_six_rows(six + angle*6, rows, r, user, x);
         }
         double const term = weight != nullptr ? weight[sun]*x : x;
         m = k == 0 ? term : m + term;
@@ -585,8 +555,7 @@ __global__ __launch_bounds__(64) void sky_zenith_mean_kernel(double const *parti
 }
 
 // grt_pipeline_run_sky_tiles: one band of one set of a column's `sets`, over partial sums that hold S cloud draws per tile
-// (slot (c T + t) S + s).  One wavefront per (column, row of the six): blocks as reduce_partials_kernel adds them, the
-// draws in order and one division by S as subcolumn_mean_kernel's (S = 1: none); the tile's value stored where the set's
+// (slot (c T + t) S + s).  One wavefront per (column, row of the six): the tile's draws_mean, stored where the set's
 // per-tile rows lie; then the tiles in order, each times its fraction, the product rounded before it is added -- no
 // fractions: the plain sum and one division by T.
 __global__ __launch_bounds__(64) void tile_mean_kernel(double const *partials, int T, int S, unsigned nblocks,
@@ -599,13 +568,7 @@ __global__ __launch_bounds__(64) void tile_mean_kernel(double const *partials, i
     for (int t = 0; t < T; ++t)
     {
         uint64_t const tile = (uint64_t)c*T + t;
-        double x = 0.;
-        for (int s = 0; s < S; ++s)
-        {
-            double const xs = wave_strided_sum(partials + ((tile*S + s)*6 + r)*nblocks, nblocks);
-            x = s == 0 ? xs : x + xs;
-        }
-        x = S > 1 ? x/(double)S : x;
+        double const x = draws_mean(partials, tile*S, S, 6, r, nblocks);
         if (per_tile != nullptr && threadIdx.x == 0)
         {
             per_tile[(((uint64_t)c*sets + set)*T + t)*12 + 6*band + r] = x;
@@ -703,8 +666,9 @@ extern "C" int grt_launch_zenith_mean(void *stream, double const *partials, int 
     {
         return (int)hipErrorInvalidValue;
     }
-    hipLaunchKernelGGL(zenith_mean_kernel, dim3((unsigned)(ncol*rows)), dim3(64), 0, (hipStream_t)stream, partials, zeniths,
-                       rows, nblocks, mu, weight, per_angle, six, user_level, out, out_stride, out_offset);
+    // (no draws, one set: the sky kernel at S = 1, sets = 1, set = 0)
+    hipLaunchKernelGGL(sky_zenith_mean_kernel, dim3((unsigned)(ncol*rows)), dim3(64), 0, (hipStream_t)stream, partials,
+                       zeniths, 1, rows, nblocks, mu, weight, per_angle, six, 1, 0, user_level, out, out_stride, out_offset);
     return (int)hipGetLastError();
 }
 

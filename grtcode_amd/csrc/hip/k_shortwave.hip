@@ -23,6 +23,10 @@
 // sw_zenith_kernel is the six-row instance for several sun angles per column on shared layer properties
 // (grt_launch_sw_zeniths), and sw_tile_kernel, behind it, the six-row instance for several surface tiles per column
 // (grt_launch_sw_tiles): the layer properties once for a chunk of tiles, what reads the albedo per tile.
+// Said once for the three: the one sweep's state and step (OneSweep), what leaves it at the surface (one_sweep_exit), its
+// rule (GRT_SW_ONE_SWEEP, grt_kernels.h), a night row's zeros (night_fill), a grid row and a chunk of tiles (solver_row,
+// TileChunk: optics_dev.h).  sw_zenith_kernel keeps its own grid row and split of the step, and the tile kernels their
+// slot: each says at the copy which shared text it follows (as members they cost scalar spills or instructions).
 // The in-kernel range checks of the reference are no-ops on device builds
 // (debug.h:105-116) and are not restated.
 #include <hip/hip_runtime.h>
@@ -275,6 +279,67 @@ __device__ __forceinline__ void put_direct(Sink &sink, int lev, double dir, doub
     sink.put_direct(lev, tsi*dir);
 }
 
+// The one sweep of the fused six-row forms when no flux is asked for between the top and the surface (GRT_SW_ONE_SWEEP's
+// rule: user level -1, 0 or L -- the pipeline's usual call), top to surface, nothing parked.  The reference's downward
+// sweep (shortwave.c:299-329) carries the direct beam, the diffuse beam over a black lower boundary and the reflectance
+// Ru of the atmosphere above; two more numbers ride along -- Rd, the reflectance of the slab above to the direct beam, and
+// Tu, its transmission of diffuse light from below to the top: adding layer p below the slab,
+//     Rd' = Rd + Tu (dir Rdir_p + dif Rdif_p) C,   Tu' = Tu Tdif_p C,   C = 1/(1 - Rdif_p Ru)
+// (the slab's own reflection plus what layer p sends back up through it; all orders of reflection between the two in
+// C).  At the surface the reference's expressions give the fluxes there, and the top's upward flux is
+// Rd + Tu x (the upward flux at the surface): the adding method's identity for what shortwave.c:280-294 builds from
+// the bottom (R_dir_downward[0]) -- the same number to rounding (1e-15), not to the bit; the surface fluxes are the
+// reference's own operations.  Two delta-Eddington solutions per layer, and no 80 bytes per layer and wavenumber parked.
+struct OneSweep
+{
+    double dir = 1., dif = 0., Ru = 0., Rd = 0., Tu = 1.;
+    // layer p below the slab (C, Tu and Ru depend on the optics alone; Rd and dif read the slab as it was above the layer)
+    __device__ __forceinline__ void step(LayerProps const &p)
+    {
+        double const C = 1./(1. - p.Rdif*Ru);
+        Rd = Rd + Tu*((dir*p.Rdir + dif*p.Rdif)*C);
+        Tu = Tu*(p.Tdif*C);
+        dif = (dir*p.Rdir*Ru + dif)*p.Tdif*C + dir*(p.Tdir - p.Tpure);          // shortwave.c:312-316
+        Ru = p.Rdif + p.Tdif*p.Tdif*Ru*C;                                        // :299-306
+        dir *= p.Tpure;
+    }
+};
+
+// ... and what leaves it over a surface of these albedos: the fluxes there, the top's upward flux and, DIRECT, the beam at both
+template <bool DIRECT, typename Sink>
+__device__ __forceinline__ void one_sweep_exit(Sink &sink, int L, OneSweep const &s, double alb_dir, double alb_dif,
+                                               double scale, double tsi)
+{
+    double up_s, dn_s;                                                          // :318-329 at the surface
+    level_flux(s.dir, s.dif, s.Ru, alb_dir, alb_dif, up_s, dn_s);
+    put_level(sink, 0, s.Rd + s.Tu*up_s, 1., scale, tsi);
+    put_level(sink, L, up_s, dn_s, scale, tsi);
+    if constexpr (DIRECT)
+    {
+        put_direct(sink, 0, 1., scale, tsi);
+        put_direct(sink, L, s.dir, scale, tsi);
+    }
+}
+
+// a night row or angle (uniform per workgroup): +0.0 in this workgroup's nrows partial sums of the slot and -- a
+// GrtDirectArgs is joined -- in its drows of the direct beam's; nothing is solved
+template <typename... Joins>
+__device__ __forceinline__ void night_fill(GrtSwArgs const &a, int slot, int nrows, int drows, Joins const &...joins)
+{
+    for (int r = threadIdx.x; r < nrows; r += kSolverBlock)
+    {
+        a.partials[((uint64_t)slot*nrows + r)*gridDim.x + blockIdx.x] = 0.;
+    }
+    if constexpr (has<GrtDirectArgs, Joins...>)
+    {
+        double *dp = pick<GrtDirectArgs>(joins...).partials;
+        for (int r = threadIdx.x; r < drows; r += kSolverBlock)
+        {
+            dp[((uint64_t)slot*drows + r)*gridDim.x + blockIdx.x] = 0.;
+        }
+    }
+}
+
 // the cosine of the zenith angle of a grid row: the column's, or -- zenith instances -- the row's angle's
 template <typename... Joins>
 __device__ __forceinline__ double row_mu(GrtSwArgs const &a, SolverRow const &row, Joins const &...joins)
@@ -368,23 +433,9 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Joins... 
     double const mu_dif = a.mu_dif;
     if constexpr (has<GrtZenithArgs, Joins...>)
     {
-        // a night sample (uniform per workgroup): +0.0 partial sums in the row's slot, nothing solved
         if (!(mu_dir > 0.))
         {
-            int const nrows = PROFILE ? 2*a.num_levels : 6;
-            for (int r = threadIdx.x; r < nrows; r += kSolverBlock)
-            {
-                a.partials[((uint64_t)row.slot*nrows + r)*gridDim.x + blockIdx.x] = 0.;
-            }
-            if constexpr (DIRECT)
-            {
-                int const drows = PROFILE ? a.num_levels : 3;
-                double *dp = pick<GrtDirectArgs>(joins...).partials;
-                for (int r = threadIdx.x; r < drows; r += kSolverBlock)
-                {
-                    dp[((uint64_t)row.slot*drows + r)*gridDim.x + blockIdx.x] = 0.;
-                }
-            }
+            night_fill(a, row.slot, PROFILE ? 2*a.num_levels : 6, PROFILE ? a.num_levels : 3, joins...);
             return;
         }
     }
@@ -423,43 +474,17 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Joins... 
         return layer_props(omega[o], g[o], tau[o], mu_dir, mu_dif);
     };
 
-    // Fused form, no flux asked for between the top and the surface (user level -1, 0 or L -- the pipeline's usual call):
-    // ONE sweep, top to surface, nothing parked.  The reference's downward sweep (shortwave.c:299-329) carries the direct
-    // beam, the diffuse beam over a black lower boundary and the reflectance R_up of the atmosphere above; two more numbers
-    // ride along -- Rd, the reflectance of the slab above to the direct beam, and Tu, its transmission of diffuse light
-    // from below to the top: adding layer p below the slab,
-    //     Rd' = Rd + Tu (dir Rdir_p + dif Rdif_p) C,   Tu' = Tu Tdif_p C,   C = 1/(1 - Rdif_p R_up)
-    // (the slab's own reflection plus what layer p sends back up through it; all orders of reflection between the two in
-    // C).  At the surface the reference's expressions give the fluxes there, and the top's upward flux is
-    // Rd + Tu x (the upward flux at the surface): the adding method's identity for what shortwave.c:280-294 builds from
-    // the bottom (R_dir_downward[0]) -- the same number to rounding (1e-15), not to the bit; the surface fluxes are the
-    // reference's own operations.  Two delta-Eddington solutions per layer instead of two plus 80 bytes per layer and
-    // wavenumber written and read back (16.8 GB per launch of 64 columns).
-    if (FUSED && !PROFILE && (user < 0 || user == 0 || user == L) && a.one_sweep)
+    if (FUSED && !PROFILE && GRT_SW_ONE_SWEEP(user, L, a.one_sweep))
     {
-        double dir = 1., dif = 0., Ru = 0., Rd = 0., Tu = 1.;
+        OneSweep sweep;
         for (int j = 0; j < L; ++j)
         {
-            LayerProps const p = props_of(j);
-            double const C = 1./(1. - p.Rdif*Ru);
-            Rd = Rd + Tu*((dir*p.Rdir + dif*p.Rdif)*C);
-            Tu = Tu*(p.Tdif*C);
-            dif = (dir*p.Rdir*Ru + dif)*p.Tdif*C + dir*(p.Tdir - p.Tpure);          // shortwave.c:312-316
-            Ru = p.Rdif + p.Tdif*p.Tdif*Ru*C;                                        // :299-306
-            dir *= p.Tpure;
+            sweep.step(props_of(j));
         }
         double const scale = a.solar[ii]*mu_dir;
         double const tsi = a.tsi[col];
-        double up_s, dn_s;                                                          // :318-329 at the surface
-        level_flux(dir, dif, Ru, row_alb_dir(a, col, row.sun, ii, joins...), a.alb_dif[(uint64_t)col*a.alb_stride + ii],
-                   up_s, dn_s);
-        put_level(sink, 0, Rd + Tu*up_s, 1., scale, tsi);
-        put_level(sink, L, up_s, dn_s, scale, tsi);
-        if constexpr (DIRECT)
-        {
-            put_direct(sink, 0, 1., scale, tsi);
-            put_direct(sink, L, dir, scale, tsi);
-        }
+        one_sweep_exit<DIRECT>(sink, L, sweep, row_alb_dir(a, col, row.sun, ii, joins...),
+                               a.alb_dif[(uint64_t)col*a.alb_stride + ii], scale, tsi);
         sink.finish(a);
         return;
     }
@@ -535,8 +560,15 @@ __global__ __launch_bounds__(kSolverBlock) void sw_kernel(GrtSwArgs a, Joins... 
 // air column times the class sum of the cross-section, over W; clear_sky_combine and layer_props on them, then the
 // reference's two sweeps (sw_kernel's materialised form): the first parks the two downward-beam reflectances of every level
 // in the output arrays, the second consumes each pair and overwrites it with the level's fluxes.  The scale is the class
-// SUM of the solar curve times mu_dir, then tsi, in put_level's order: W m-2 per class.  An empty class (W = 0) and a
+// SUM of the solar curve times mu_dir, then tsi, by put_level into a PairSink: W m-2 per class.  An empty class (W = 0) and a
 // night column (mu_dir <= 0) leave +0.0 and solve nothing.
+struct PairSink        // (put_level's sink over two arrays: level lev's pair at fu[lev stride], fd[lev stride])
+{
+    double *fu, *fd;
+    uint64_t stride;
+    __device__ __forceinline__ void put(int lev, bool down, double x) { (down ? fd : fu)[(uint64_t)lev*stride] = x; }
+};
+
 __global__ __launch_bounds__(kSolverBlock) void ck_sw_kernel(GrtCkSolveArgs a)
 {
     uint64_t const per_col = (uint64_t)a.num_bins*(uint64_t)a.num_classes;
@@ -584,32 +616,27 @@ __global__ __launch_bounds__(kSolverBlock) void ck_sw_kernel(GrtCkSolveArgs a)
         fd[(uint64_t)j*per_col] = Rdif_dn;
     }
 
-    // sweep 2: shortwave.c:299-329, then the scalings of :401-405 and :447-451 (put_level's)
+    // sweep 2: shortwave.c:299-329, then the scalings of :401-405 and :447-451
     double const scale = S[per_col]*mu_dir;
     double const tsi = a.tsi[col];
-    auto put = [&](int lev, double up, double dn)
-    {
-        up *= scale;
-        dn *= scale;
-        fu[(uint64_t)lev*per_col] = tsi*up;
-        fd[(uint64_t)lev*per_col] = tsi*dn;
-    };
+    PairSink sink = {fu, fd, per_col};
     Sweep2 s;
-    put(0, s.dir*Rdir_dn, s.dir);                 // R[0] = dir_beam*R_dir_downward[0], T[0]
+    put_level(sink, 0, s.dir*Rdir_dn, s.dir, scale, tsi);      // R[0] = dir_beam*R_dir_downward[0], T[0]
     for (int lev = 1; lev < V; ++lev)
     {
         sweep2_step(s, props_of(lev - 1), lev);
         double up, dn;
         level_flux(s.dir, s.dif, s.Rup, fu[(uint64_t)lev*per_col], fd[(uint64_t)lev*per_col], up, dn);
-        put(lev, up, dn);
+        put_level(sink, lev, up, dn, scale, tsi);
     }
 }
 
 // ---- several sun angles per column on one walk through the layers (grt_launch_sw_zeniths) ----
 // Of sw_kernel<GRT_OUT_ROWS>'s one sweep, a layer's optics (tau_gas, continua, Rayleigh and what joins them: LayerOptics),
 // its delta-scaling, its diffuse Eddington solution with k and exp(+-t k), and C, Ru, Tu of the sweep depend on the optics
-// alone; the angle's own are the direct-beam solution, dir, dif, Rd and the scale at the surface.  Grid row y is a column, a
-// cloud draw of it (Joins holds a GrtSubcolumnArgs: draws first .. first + count - 1, the chunks of a draw next to each
+// alone; the angle's own are the direct-beam solution, dir, dif, Rd and the scale at the surface: OneSweep::step's lines,
+// split by hand into the two (a member per part costs this kernel scalar spills), then one_sweep_exit.  Grid row y is a column,
+// a cloud draw of it (Joins holds a GrtSubcolumnArgs: draws first .. first + count - 1, the chunks of a draw next to each
 // other) and a chunk of ZN consecutive angles: the thread does the shared part of a layer once and the angle's part ZN
 // times, each in sw_kernel's expressions and order on the same doubles (exp(+-t k) is a function of its argument, whichever
 // call evaluates it first), so every angle's partial sums are the zenith instance's of sw_kernel<GRT_OUT_ROWS> with the
@@ -628,6 +655,7 @@ __global__ __launch_bounds__(kSolverBlock) void sw_zenith_kernel(GrtSwArgs a, Gr
     bool const live = i < a.nw;
     uint64_t const ii = live ? i : a.nw - 1;      // (idle lanes of the last block follow along, weight 0)
     int const Z = zn.zeniths, chunks = (Z + ZN - 1)/ZN;
+    // (solver_row's subcolumn rule on y / chunks, by hand: through solver_row the subcolumn instances gain instructions)
     int const y = blockIdx.y;
     int const cd = y/chunks;                      // (column, or -- subcolumns -- column and draw)
     int const k0 = (y - cd*chunks)*ZN;
@@ -670,6 +698,7 @@ __global__ __launch_bounds__(kSolverBlock) void sw_zenith_kernel(GrtSwArgs a, Gr
             delta_scaling(om, gg, t, os, gs, ts);
             ExpKt shared = {0., 0., 0., false};
             LayerRT const s = eddington<false>(os, ts, mu_dif, gs, shared);
+            // (OneSweep::step's lines from here on, its C, Tu, Ru once and its Rd, dif, dir per angle: a copy, see above)
             double const C = 1./(1. - s.R*Ru);
 #pragma unroll
             for (int u = 0; u < ZN; ++u)
@@ -705,32 +734,14 @@ __global__ __launch_bounds__(kSolverBlock) void sw_zenith_kernel(GrtSwArgs a, Gr
         int const sun = col*Z + k0 + u, slot = sun*S + draw;
         if (!day[u])
         {
-            if (threadIdx.x < 6)
-            {
-                a.partials[((uint64_t)slot*6 + threadIdx.x)*gridDim.x + blockIdx.x] = 0.;
-            }
-            if constexpr (DIRECT)
-            {
-                if (threadIdx.x < 3)
-                {
-                    pick<GrtDirectArgs>(joins...).partials[((uint64_t)slot*3 + threadIdx.x)*gridDim.x + blockIdx.x] = 0.;
-                }
-            }
+            night_fill(a, slot, 6, 3, joins...);
             continue;
         }
         // (six rows, and -- a GrtDirectArgs is joined -- the angle's direct beam at the top and the surface beside them)
         LevelSink<true, false, false, false, DIRECT> sink(a, slot, i, live, GrtBandArgs{0, 0, nullptr, 0},
                                                           pick<GrtDirectArgs>(joins...));
-        double const scale = solar*mu[u];
-        double up_s, dn_s;                                                          // :318-329 at the surface
-        level_flux(dir[u], dif[u], Ru, SURFACE ? row_alb_dir(a, col, sun, ii, joins...) : alb_col, alb_dif, up_s, dn_s);
-        put_level(sink, 0, Rd[u] + Tu*up_s, 1., scale, tsi);
-        put_level(sink, L, up_s, dn_s, scale, tsi);
-        if constexpr (DIRECT)
-        {
-            put_direct(sink, 0, 1., scale, tsi);
-            put_direct(sink, L, dir[u], scale, tsi);
-        }
+        one_sweep_exit<DIRECT>(sink, L, OneSweep{dir[u], dif[u], Ru, Rd[u], Tu},
+                               SURFACE ? row_alb_dir(a, col, sun, ii, joins...) : alb_col, alb_dif, solar*mu[u], tsi);
         __syncthreads();                            // (block_partials' LDS is the angle before's: every wave has read it)
         sink.finish(a);
     }
@@ -740,13 +751,12 @@ __global__ __launch_bounds__(kSolverBlock) void sw_zenith_kernel(GrtSwArgs a, Gr
 // Of sw_kernel<GRT_OUT_ROWS>, only level_flux at a level and Rd + Tu x (the upward flux at the surface) read the albedo in
 // the one sweep; of its two sweeps, only sweep1_step, through the pair (R_dir_downward, R_dif_downward) it carries up from
 // the albedos.  Grid row y is the six-row instance's (a column, or a column and cloud draw), blockIdx.z a chunk of TN
-// consecutive tiles.  One sweep (sw_kernel's rule): the walk once, level_flux and the top's upward flux per tile.  Two
+// consecutive tiles: a TileChunk (optics_dev.h).  One sweep (GRT_SW_ONE_SWEEP): OneSweep once, one_sweep_exit per tile.  Two
 // sweeps: the layer properties are formed and parked once (sw_kernel's fused layout, at park row z gridDim.y + y),
 // sweep1_step runs per tile on the tile's pair, the user level's pair kept per tile; the second sweep runs once, its
 // beams and R_dif_upward kept where it passes the user level; then level_flux per tile at the top, the user level and
-// the surface.  Every tile's six rows leave through a LevelSink at the tile's slot (c tiles + t) subcolumns + s:
-// sw_kernel's doubles through sw_kernel's sums.  Tiles past the column's last are skipped by a flag that is uniform per
-// workgroup.
+// the surface.  Every tile's six rows leave through a LevelSink at the tile's slot: sw_kernel's doubles through
+// sw_kernel's sums.  Tiles past the column's last are skipped by a flag that is uniform per workgroup.
 template <int TN, typename... Joins>
 __global__ __launch_bounds__(kSolverBlock) void sw_tile_kernel(GrtSwArgs a, GrtTileArgs tl, Joins... joins)
 {
@@ -755,15 +765,10 @@ __global__ __launch_bounds__(kSolverBlock) void sw_tile_kernel(GrtSwArgs a, GrtT
     int const col = row.col;
     bool const live = i < a.nw;
     uint64_t const ii = live ? i : a.nw - 1;      // (idle lanes of the last block follow along, weight 0)
-    int const V = a.num_levels, L = V - 1, T = tl.tiles, user = a.user_level;
-    int const k0 = (tl.chunk_first + (int)blockIdx.z)*TN;
+    int const V = a.num_levels, L = V - 1, user = a.user_level;
+    TileChunk<TN> const chunk(tl, row, joins...);
+    int const T = chunk.T, k0 = chunk.k0, S = chunk.S, draw = chunk.draw;
     uint64_t const nw = a.nw;
-    int S = 1;
-    if constexpr (has<GrtSubcolumnArgs, Joins...>)
-    {
-        S = pick<GrtSubcolumnArgs>(joins...).subcolumns;
-    }
-    int const draw = row.slot - col*S;
     double const mu_dir = a.mu_dir[col], mu_dif = a.mu_dif;
     LayerOptics<true, has_clouds<Joins...>, has<GrtAerosolArgs, Joins...>> const optics(
         a, pick_clouds(joins...), col, row.tab, ii, pick<GrtAerosolArgs>(joins...));
@@ -779,7 +784,7 @@ __global__ __launch_bounds__(kSolverBlock) void sw_tile_kernel(GrtSwArgs a, GrtT
     for (int u = 0; u < TN; ++u)
     {
         alb_dir[u] = alb_dif[u] = 0.;
-        if (k0 + u < T)
+        if (chunk.live(u))
         {
             uint64_t const at = ((uint64_t)col*T + k0 + u)*nw + ii;
             alb_dir[u] = tl.rows != nullptr ? tl.rows[at] : a.alb_dir[(uint64_t)col*a.alb_stride + ii];
@@ -790,32 +795,22 @@ __global__ __launch_bounds__(kSolverBlock) void sw_tile_kernel(GrtSwArgs a, GrtT
     double const scale = a.solar[ii]*mu_dir;
     double const tsi = a.tsi[col];
 
-    if ((user < 0 || user == 0 || user == L) && a.one_sweep)
+    if (GRT_SW_ONE_SWEEP(user, L, a.one_sweep))
     {
-        // sw_kernel's one sweep, top to surface
-        double dir = 1., dif = 0., Ru = 0., Rd = 0., Tu = 1.;
+        OneSweep sweep;
         for (int j = 0; j < L; ++j)
         {
-            LayerProps const p = props_of(j);
-            double const C = 1./(1. - p.Rdif*Ru);
-            Rd = Rd + Tu*((dir*p.Rdir + dif*p.Rdif)*C);
-            Tu = Tu*(p.Tdif*C);
-            dif = (dir*p.Rdir*Ru + dif)*p.Tdif*C + dir*(p.Tdir - p.Tpure);          // shortwave.c:312-316
-            Ru = p.Rdif + p.Tdif*p.Tdif*Ru*C;                                        // :299-306
-            dir *= p.Tpure;
+            sweep.step(props_of(j));
         }
 #pragma unroll
         for (int u = 0; u < TN; ++u)
         {
-            if (k0 + u >= T)
+            if (!chunk.live(u))
             {
                 continue;
             }
-            LevelSink<true, false> sink(a, (col*T + k0 + u)*S + draw, i, live);
-            double up_s, dn_s;                                                      // :318-329 at the surface
-            level_flux(dir, dif, Ru, alb_dir[u], alb_dif[u], up_s, dn_s);
-            put_level(sink, 0, Rd + Tu*up_s, 1., scale, tsi);
-            put_level(sink, L, up_s, dn_s, scale, tsi);
+            LevelSink<true, false> sink(a, (col*T + k0 + u)*S + draw, i, live);       // (TileChunk's slot rule: a copy)
+            one_sweep_exit<false>(sink, L, sweep, alb_dir[u], alb_dif[u], scale, tsi);
             __syncthreads();                        // (block_partials' LDS is the tile before's: every wave has read it)
             sink.finish(a);
         }
@@ -840,7 +835,7 @@ __global__ __launch_bounds__(kSolverBlock) void sw_tile_kernel(GrtSwArgs a, GrtT
 #pragma unroll
         for (int u = 0; u < TN; ++u)
         {
-            if (k0 + u < T)
+            if (chunk.live(u))
             {
                 sweep1_step(p, Rdir_dn[u], Rdif_dn[u]);
                 user_rdir[u] = j == user ? Rdir_dn[u] : user_rdir[u];
@@ -861,11 +856,11 @@ __global__ __launch_bounds__(kSolverBlock) void sw_tile_kernel(GrtSwArgs a, GrtT
 #pragma unroll
     for (int u = 0; u < TN; ++u)
     {
-        if (k0 + u >= T)
+        if (!chunk.live(u))
         {
             continue;
         }
-        LevelSink<true, false> sink(a, (col*T + k0 + u)*S + draw, i, live);
+        LevelSink<true, false> sink(a, (col*T + k0 + u)*S + draw, i, live);           // (TileChunk's slot rule: a copy)
         put_level(sink, 0, 1.*Rdir_dn[u], 1., scale, tsi);     // R[0] = dir_beam*R_dir_downward[0], T[0]
         double up, dn;
         if (user > 0 && user < L)

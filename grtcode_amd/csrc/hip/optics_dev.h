@@ -222,6 +222,30 @@ __device__ __forceinline__ SolverRow solver_row(int ncol, Pack const &...pack)
     }
 }
 
+// The chunk of a tile kernel's workgroup (sw_tile_kernel, lw_tile_kernel; GrtTileArgs): grid row y is the six-row
+// instance's `row`, blockIdx.z a chunk of TN consecutive tiles from k0 on.  Tile k0 + u is live(u) when the column has it;
+// it is tile c T + k0 + u of the launch, and its partial sums lie at slot (c T + k0 + u) S + draw (the kernels say both where
+// they use them: a member per rule costs lw_tile_kernel instructions).
+template <int TN>
+struct TileChunk
+{
+    int T, k0, S, draw;
+
+    template <typename... Pack>
+    __device__ __forceinline__ TileChunk(GrtTileArgs const &tl, SolverRow const &row, Pack const &...pack)
+    {
+        T = tl.tiles;
+        k0 = (tl.chunk_first + (int)blockIdx.z)*TN;
+        S = 1;
+        if constexpr (has<GrtSubcolumnArgs, Pack...>)
+        {
+            S = pick<GrtSubcolumnArgs>(pack...).subcolumns;
+        }
+        draw = row.slot - row.col*S;
+    }
+    __device__ __forceinline__ bool live(int u) const { return k0 + u < T; }
+};
+
 // One cloud object's optics at (layer j, a point that takes band `band`) from a column's band table tab [3][B][L]
 // (extinction, albedo, asymmetry; GrtCloudArgs): optical depth = extinction x layer thickness (driver.c:518-526); no band
 // (band < 0): no cloud.
