@@ -982,26 +982,33 @@ def make_zenith_slant(layer_cos_zenith):
     return gs, keep
 
 
+def _pack_windows(first, weights_list, what, band="", empty=0):
+    """What make_channels and make_responses pack of a band's windows: first [N] int32, the points per window, their
+    running offsets [N + 1] int32 and the weights end to end (np.zeros(empty) for no window), then the three ctypes
+    pointers (first, offset, weights).  The messages call the windows `band` + `what`."""
+    per = [_f64(w).ravel() for w in weights_list]
+    first = np.ascontiguousarray(first, dtype=np.int32).ravel()
+    counts = np.array([w.size for w in per], dtype=np.int64)
+    if first.size != len(per):
+        raise ValueError(f"{first.size} first points for {len(per)} {band}{what}")
+    if int(counts.sum()) >= 2**31:
+        raise ValueError(f"{int(counts.sum())} {band}weights in all: fewer than 2^31")
+    offset = np.ascontiguousarray(np.concatenate(([0], np.cumsum(counts))), dtype=np.int32)
+    weights = _f64(np.concatenate(per)) if per else np.zeros(empty)
+    return first, counts, offset, weights, (first.ctypes.data_as(c_int_p), offset.ctypes.data_as(c_int_p), _dp(weights))
+
+
 def make_channels(first, weights_per_channel, center=None):
     """Pack an instrument's channels into a GrtChannels struct (+ keep-alive arrays) for Pipeline.run_sky_channels and
     channel_pair_count.  first [C]: the grid index of each channel's first point in the longwave band; weights_per_channel:
     a list of C arrays, each channel's spectral response sampled on the grid from that point on (channels.gaussian and
     channels.boxcar make both); center [C] cm-1 or None: the weighted centroid.  The two output pointers are
     Pipeline.run_sky_channels' to set.  keep["counts"] is the points per channel."""
-    per = [_f64(w).ravel() for w in weights_per_channel]
-    keep = {"first": np.ascontiguousarray(first, dtype=np.int32).ravel(),
-            "counts": np.array([w.size for w in per], dtype=np.int64),
-            "center": None if center is None else _f64(center).ravel()}
-    if keep["first"].size != len(per):
-        raise ValueError(f"{keep['first'].size} first points for {len(per)} channels")
-    if keep["center"] is not None and keep["center"].size != len(per):
-        raise ValueError(f"{keep['center'].size} centers for {len(per)} channels")
-    if int(keep["counts"].sum()) >= 2**31:
-        raise ValueError(f"{int(keep['counts'].sum())} weights in all: fewer than 2^31")
-    keep["offset"] = np.ascontiguousarray(np.concatenate(([0], np.cumsum(keep["counts"]))), dtype=np.int32)
-    keep["weights"] = _f64(np.concatenate(per)) if per else np.zeros(0)
-    gc = GrtChannels(len(per), keep["first"].ctypes.data_as(c_int_p), keep["offset"].ctypes.data_as(c_int_p),
-                     _dp(keep["weights"]), _opt_dp(keep["center"]), None, None)
+    keep = {"center": None if center is None else _f64(center).ravel()}
+    keep["first"], keep["counts"], keep["offset"], keep["weights"], ptrs = _pack_windows(first, weights_per_channel, "channels")
+    if keep["center"] is not None and keep["center"].size != keep["counts"].size:
+        raise ValueError(f"{keep['center'].size} centers for {keep['counts'].size} channels")
+    gc = GrtChannels(keep["counts"].size, *ptrs, _opt_dp(keep["center"]), None, None)
     gc.keep = keep             # (as make_cloud_model)
     return gc, keep
 
@@ -1022,21 +1029,10 @@ def make_responses(lw=None, sw=None):
     keep["sw_counts"]: the points per response."""
     keep, fields = {}, []
     for name, band in (("lw", lw), ("sw", sw)):
-        first, weights_list = band if band is not None else ((), ())
-        per = [_f64(w).ravel() for w in weights_list]
-        keep[name + "_first"] = np.ascontiguousarray(first, dtype=np.int32).ravel()
-        keep[name + "_counts"] = np.array([w.size for w in per], dtype=np.int64)
-        if keep[name + "_first"].size != len(per):
-            raise ValueError(f"{keep[name + '_first'].size} first points for {len(per)} {name} responses")
-        if int(keep[name + "_counts"].sum()) >= 2**31:
-            raise ValueError(f"{int(keep[name + '_counts'].sum())} {name} weights in all: fewer than 2^31")
-        keep[name + "_offset"] = np.ascontiguousarray(np.concatenate(([0], np.cumsum(keep[name + "_counts"]))), dtype=np.int32)
-        keep[name + "_weights"] = _f64(np.concatenate(per)) if per else np.zeros(1)
-        if per:
-            fields += [len(per), keep[name + "_first"].ctypes.data_as(c_int_p), keep[name + "_offset"].ctypes.data_as(c_int_p),
-                       _dp(keep[name + "_weights"])]
-        else:
-            fields += [0, None, None, None]
+        packed = _pack_windows(*(band if band is not None else ((), ())), "responses", name + " ", empty=1)
+        for key, array in zip(("_first", "_counts", "_offset", "_weights"), packed):
+            keep[name + key] = array
+        fields += [packed[1].size, *packed[4]] if packed[1].size else [0, None, None, None]
     gr = GrtResponses(*fields, None, None)
     gr.keep = keep             # (as make_cloud_model)
     return gr, keep

@@ -668,38 +668,43 @@ static inline int grt_radiance_args_ok(GrtRadianceArgs const *r)
            r->draw < r->subcolumns;
 }
 
+/* ---- The window table (grt_window_table, host; Window, optics_dev.h) ----
+   A window is the grid points first .. first + count - 1 with a weight each, at weights + its weight offset.  Instrument
+   channels (GrtChannelArgs) and spectral responses (GrtResponseArgs) are windows; they overlap freely, so a 128-point
+   solver block has an explicit list of its windows, not a range.  A (window, block) pair is a window and a block it has a
+   point in: pair = the window's first pair + block - its first block.  One device allocation holds the doubles first --
+   every window's weights, then what the kind adds --, then the ints:
+     entry [count][GRT_WINDOW_INTS]   per window: first point, count, weight offset, first block, first pair;
+     block_start [nblocks + 1]        where block b's list starts in block_list;
+     block_list [pairs]               the windows of block 0, of block 1, ...: each list in ascending order. */
+#define GRT_WINDOW_INTS 5
+
 /* Instrument channels of those radiances (grt_pipeline_run_sky_channels): the channel form of lw_radiance_kernel, the
-   radiance form with a GrtChannelArgs last in its joins.  Channel c is the points first .. first + count - 1 of the grid
-   with the weights W_c at weights + its weight offset; a (channel, 128-point solver block) pair is a channel and a block
-   the channel has a point in, pair = the channel's first pair + block - its first block.  After the upward sweep a
-   workgroup forms, per channel of its block's list, real angle and row, sum_i W_c(i) value(i) over its 128 points -- a lane
+   radiance form with a GrtChannelArgs last in its joins.  The channels are the windows of a window table, W_c the weights
+   of channel c.  After the upward sweep a workgroup forms, per channel of its block's list, real angle and row, sum_i W_c(i) value(i) over its 128 points -- a lane
    outside the channel's span or past the grid weighs 0; WAVE_SUM, then the two waves in order, as block_partials adds a
    row; a wave that holds no point of the channel adds +0.0 without the tree -- and stores it at partials[((slot angles +
-   angle) 2 + row) pairs + pair]: a channel's sums depend on its own weights and the grid alone.  The table
-   (grt_channel_table, host): doubles first -- every channel's weights, then sum_w [C] (summed in index order), then
-   center [C] (the caller's, or the centroid sum W w / sum W) --, then the ints: per channel GRT_CHANNEL_INTS (first point,
-   count, weight offset, first block, first pair), per block where its list starts in what follows [nblocks + 1], and the
-   lists [pairs], the channels of a block in ascending order.
+   angle) 2 + row) pairs + pair]: a channel's sums depend on its own weights and the grid alone.  Behind the weights
+   the table's doubles hold sum_w [C] (summed in index order) and center [C] (the caller's, or the centroid sum W w / sum W).
    grt_launch_channel_finish (channel_finish_kernel): one thread per (column, angle, row, channel); per draw s = 0 .. S - 1
    in order the channel's pairs in block order, then -- S > 1 -- one division by S, one by sum_w, stored at out[c
    out_stride + out_offset + (angle 2 + row) C + channel]; brightness (or NULL): T = c2 v / log1p(c1 v^3 / R) at v =
    center, +0.0 where R <= 0, at the same place. */
-#define GRT_CHANNEL_INTS 5
 typedef struct GrtChannelArgs
 {
     int channels;                   /* C */
     uint64_t pairs;                 /* P */
-    int const *chan;                /* DEVICE [C][GRT_CHANNEL_INTS] */
+    int const *entry;               /* DEVICE [C][GRT_WINDOW_INTS] */
     int const *block_start;         /* DEVICE [nblocks + 1] */
-    int const *block_chan;          /* DEVICE [P] */
+    int const *block_list;          /* DEVICE [P] */
     double const *weights;          /* DEVICE [the channels' points] */
     double const *sum_w, *center;   /* DEVICE [C] each */
     double *partials;               /* DEVICE [slot][angles][2][P] */
 } GrtChannelArgs;
 static inline int grt_channel_args_ok(GrtChannelArgs const *c)
 {
-    return c != NULL && c->channels >= 1 && c->pairs >= 1 && c->chan != NULL && c->block_start != NULL &&
-           c->block_chan != NULL && c->weights != NULL && c->sum_w != NULL && c->center != NULL && c->partials != NULL;
+    return c != NULL && c->channels >= 1 && c->pairs >= 1 && c->entry != NULL && c->block_start != NULL &&
+           c->block_list != NULL && c->weights != NULL && c->sum_w != NULL && c->center != NULL && c->partials != NULL;
 }
 
 /* Channel transmittance profiles and contribution functions of the upward radiance at the top
@@ -757,10 +762,8 @@ static inline int grt_band_args_ok(GrtBandArgs const *bn)
 /* Response form of the two profile forms (GRT_OUT_LEVELS with any of the cloud and aerosol joins or none, the shortwave's
    always together with `direct`; grt_pipeline_run_sky_weighted): the profile form's arguments, sweeps, park block and
    partial sums -- the broadband rows are summed exactly as without it --, and beside them every level's rows under
-   spectral response functions.  Response k is the points first .. first + count - 1 of the grid with the weights r_k at
-   weights + its weight offset (not normalised, any finite sign; responses overlap freely, so a block has an explicit list
-   of them, not a range); a (response, 128-point solver block) pair is a response and a block it has a point in, pair = the
-   response's first pair + block - its first block.  A workgroup stages t_i r_k(i) -- t_i the band's trapezoid weight, 0
+   spectral response functions.  The responses are the windows of a window table (above GrtChannelArgs), r_k
+   the weights of response k: not normalised, any finite sign, and the table's only doubles.  A workgroup stages t_i r_k(i) -- t_i the band's trapezoid weight, 0
    for idle lanes and outside the response's span -- for the responses of its block's list in dynamic LDS, [responses of
    the block][128], once at kernel start; every level's value x then leaves once more per response of the list as the
    wave sums of x (t r), in its own group of G V rows behind the broadband group (G = 2: up, down; 3 with the third row
@@ -768,9 +771,6 @@ static inline int grt_band_args_ok(GrtBandArgs const *bn)
    2 V + level (third group): without atomics, a fixed place per (slot, response, row, block).  A workgroup whose list is
    empty does exactly the profile form's work.  Dynamic LDS: (1 + block_max) G V x 2 doubles of wave sums and block_max x
    128 doubles of weights.
-   The table (grt_stage_responses, host): the doubles first -- every response's weights --, then the ints: per response
-   GRT_RESPONSE_INTS (first point, count, weight offset, first block, first pair), per block where its list starts in what
-   follows [nblocks + 1], and the lists [P], the responses of a block in ascending order.
    grt_launch_response_rows: the materialised form's twin -- the same weights, wave and workgroup sums on rows [slots][G]
    [V][nw] the spectral solvers (and the direct-beam kernel) left on the grid, row group g of slot c at rows[g] + c V nw,
    to the same partial sums.
@@ -780,22 +780,21 @@ static inline int grt_band_args_ok(GrtBandArgs const *bn)
    grt_launch_actinic_rows: from finished shortwave rows [n][R][3][V] (row group stride `stride` doubles per n) the actinic
    flux (S/mu0 + (D - S)/mu_dif) + U/mu_dif, in that order, to actinic[i a_stride + (k V + level)]; mu0 [ncol], i = c sets +
    set. */
-#define GRT_RESPONSE_INTS 5
 typedef struct GrtResponseArgs
 {
     int responses;                  /* R */
     int block_max;                  /* the most responses with a point in one workgroup: sizes the dynamic LDS */
     uint64_t per_row;               /* P: the (response, block) pairs, partial sums per row and slot */
-    int const *resp;                /* DEVICE [R][GRT_RESPONSE_INTS] */
+    int const *entry;               /* DEVICE [R][GRT_WINDOW_INTS] */
     int const *block_start;         /* DEVICE [nblocks + 1] */
-    int const *block_resp;          /* DEVICE [P] */
+    int const *block_list;          /* DEVICE [P] */
     double const *weights;          /* DEVICE [the responses' points] */
     double *partials;               /* DEVICE [slot][P][G V] */
 } GrtResponseArgs;
 static inline int grt_response_args_ok(GrtResponseArgs const *r)
 {
-    return r != NULL && r->responses >= 1 && r->block_max >= 1 && r->per_row >= 1 && r->resp != NULL &&
-           r->block_start != NULL && r->block_resp != NULL && r->weights != NULL && r->partials != NULL;
+    return r != NULL && r->responses >= 1 && r->block_max >= 1 && r->per_row >= 1 && r->entry != NULL &&
+           r->block_start != NULL && r->block_list != NULL && r->weights != NULL && r->partials != NULL;
 }
 int grt_launch_response_rows(void *stream, GrtResponseArgs const *r, double const *const rows[3], int groups, int slots,
                              int num_levels, uint64_t nw, double dw);

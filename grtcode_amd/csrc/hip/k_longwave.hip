@@ -389,11 +389,11 @@ __device__ __forceinline__ void channel_partials(GrtChannelArgs const &ch, doubl
         int const nb = k_hi - k0 < kChannelChunk ? k_hi - k0 : kChannelChunk;
         for (int q = 0; q < nb; ++q)
         {
-            int const *e = ch.chan + (uint64_t)GRT_CHANNEL_INTS*ch.block_chan[k0 + q];
-            long long const first = e[0], last = first + e[1] - 1;
+            Window const w = window_of<uint64_t>(ch.entry, ch.block_list, k0 + q);
+            long long const first = w.first(), last = first + w.count() - 1;    // (Window: span, weight, as first <= i <= last)
             if (first <= wave_hi && last >= wave_lo)
             {
-                double const W = (live && at >= first && at <= last) ? ch.weights[(uint64_t)e[2] + (uint64_t)(at - first)] : 0.;
+                double const W = (live && at >= first && at <= last) ? ch.weights[(uint64_t)w.weight_at() + (uint64_t)(at - first)] : 0.;
 #pragma unroll
                 for (int k = 0; k < kRadianceChunk; ++k)
                 {
@@ -422,8 +422,8 @@ __device__ __forceinline__ void channel_partials(GrtChannelArgs const &ch, doubl
         int const q = threadIdx.x/(2*kRadianceChunk), v = threadIdx.x % (2*kRadianceChunk);
         if (q < nb && v < 2*n)
         {
-            int const *e = ch.chan + (uint64_t)GRT_CHANNEL_INTS*ch.block_chan[k0 + q];
-            uint64_t const pair = (uint64_t)e[4] + block - (unsigned)e[3];
+            Window const w = window_of<uint64_t>(ch.entry, ch.block_list, k0 + q);
+            uint64_t const pair = (uint64_t)w.first_pair() + block - (unsigned)w.first_block();     // (Window: pair)
             ch.partials[(row_base + v)*ch.pairs + pair] = waves_sum<kSolverBlock/64>(part[q][v]);
         }
         __syncthreads();
@@ -509,12 +509,12 @@ __global__ __launch_bounds__(kSolverBlock) void lw_radiance_kernel(GrtLwArgs a, 
 __device__ __forceinline__ double channel_row_mean(GrtChannelArgs const &ch, double const *partials, uint64_t c, uint64_t row,
                                                    uint64_t stride, int S)
 {
-    int const *e = ch.chan + GRT_CHANNEL_INTS*c;
-    int const npairs = (e[0] + e[1] - 1)/kSolverBlock - e[3] + 1;
+    Window const w = window_at(ch.entry, c);
+    int const npairs = (w.first() + w.count() - 1)/kSolverBlock - w.first_block() + 1;    // (Window::blocks, which moves the loop)
     double m = 0.;
     for (int s = 0; s < S; ++s)
     {
-        double const *p = partials + (row + s*stride)*ch.pairs + e[4];
+        double const *p = partials + (row + s*stride)*ch.pairs + w.first_pair();
         double x = p[0];
         for (int k = 1; k < npairs; ++k)
         {
@@ -574,10 +574,10 @@ __device__ __forceinline__ void weighting_gather(GrtChannelArgs const &ch, GrtWe
     // one thread per channel of the block's list: a weight is loaded once for the chunk's angles and both quantities
     for (int k = threadIdx.x; k < nch; k += kSolverBlock)
     {
-        int const *e = ch.chan + (uint64_t)GRT_CHANNEL_INTS*ch.block_chan[k_lo + k];
-        int const first = e[0], last = first + e[1] - 1;
+        Window const w = window_of<uint64_t>(ch.entry, ch.block_list, k_lo + k);
+        int const first = w.first(), last = first + w.count() - 1;              // (Window: span, weight, cut to the block)
         int const lo = first > blk_lo ? first : blk_lo, hi = last < blk_hi ? last : blk_hi;
-        double const *W = ch.weights + (uint64_t)e[2] + (uint64_t)(lo - first);
+        double const *W = ch.weights + (uint64_t)w.weight_at() + (uint64_t)(lo - first);
         int const at = lo - blk_lo, count = hi - lo + 1;
         // (eight weight loads in flight ahead of the sums)
         double st[kRadianceChunk] = {0., 0., 0., 0.}, sk[kRadianceChunk] = {0., 0., 0., 0.};
@@ -595,7 +595,7 @@ __device__ __forceinline__ void weighting_gather(GrtChannelArgs const &ch, GrtWe
                 }
             }
         }
-        uint64_t const pair = (uint64_t)e[4] + block - (unsigned)e[3];
+        uint64_t const pair = (uint64_t)w.first_pair() + block - (unsigned)w.first_block();     // (Window: pair)
 #pragma unroll
         for (int q = 0; q < kRadianceChunk; ++q)
         {

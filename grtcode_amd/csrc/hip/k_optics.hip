@@ -989,9 +989,9 @@ __global__ __launch_bounds__(kSolverBlock) void response_rows_kernel(GrtResponse
             int const nq = hi - q0 < kResponseChunk ? hi - q0 : kResponseChunk;
             for (int q = 0; q < nq; ++q)
             {
-                int const *e = r.resp + GRT_RESPONSE_INTS*r.block_resp[q0 + q];
-                long long const at = (long long)i - e[0];
-                double const w = live && at >= 0 && at < e[1] ? pwt*r.weights[e[2] + at] : 0.;
+                Window const win = window_of(r.entry, r.block_list, q0 + q);
+                long long const at = (long long)i - win.first();                // (Window: span, weight)
+                double const w = live && at >= 0 && at < win.count() ? pwt*r.weights[win.weight_at() + at] : 0.;
                 double s = x*w;
                 WAVE_SUM(s);
                 if ((threadIdx.x & 63) == 0)
@@ -1002,8 +1002,8 @@ __global__ __launch_bounds__(kSolverBlock) void response_rows_kernel(GrtResponse
             __syncthreads();
             if ((int)threadIdx.x < nq)
             {
-                int const *e = r.resp + GRT_RESPONSE_INTS*r.block_resp[q0 + threadIdx.x];
-                uint64_t const pair = (uint64_t)(e[4] + (int)block - e[3]);
+                Window const win = window_at(r.entry, r.block_list[q0 + threadIdx.x]);
+                uint64_t const pair = (uint64_t)(win.first_pair() + (int)block - win.first_block());    // (Window: pair)
                 r.partials[((uint64_t)slot*r.per_row + pair)*nrows + row] = waves_sum<kSolverBlock/64>(part[threadIdx.x]);
             }
             __syncthreads();
@@ -1052,12 +1052,12 @@ __global__ __launch_bounds__(kResponseFinishBlock) void response_finish_kernel(G
         return;
     }
     uint64_t const row = t % rows, k = (t/rows) % (uint64_t)r.responses, c = t/(rows*(uint64_t)r.responses);
-    int const *e = r.resp + GRT_RESPONSE_INTS*k;
-    unsigned const nblk = (unsigned)((e[0] + e[1] - 1)/kSolverBlock - e[3]) + 1;
+    Window const w = window_at(r.entry, k);
+    unsigned const nblk = (unsigned)w.blocks();
     double m = 0.;
     for (int s = 0; s < S; ++s)
     {
-        double const x = strided_tree_sum(r.partials + ((c*S + s)*r.per_row + (uint64_t)e[4])*rows + row, nblk, rows);
+        double const x = strided_tree_sum(r.partials + ((c*S + s)*r.per_row + (uint64_t)w.first_pair())*rows + row, nblk, rows);
         m = s == 0 ? x : m + x;
     }
     out[c*out_stride + out_offset + k*rows + row] = m/(double)S;

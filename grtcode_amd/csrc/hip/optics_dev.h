@@ -517,6 +517,35 @@ struct LayerOptics
     }
 };
 
+// One window of a window table (grt_kernels.h): its five ints by name, each read where a kernel asks for it.  Three
+// rules on them are written out at the kernels' sites, each marked `(Window: <rule>)`, because a member function that holds
+// one moves instructions in every kernel it was tried in; the canonical forms, which a site writes in its own integer width:
+//   pair    the window's pair in solver block b, one it has a point in:   first_pair + b - first_block
+//   span    grid point i is one of its points:                            0 <= i - first < count
+//   weight  ... and its weight there:                                     weights[weight_at + (i - first)]
+struct Window
+{
+    int const *e;
+    __device__ __forceinline__ int first() const { return e[0]; }
+    __device__ __forceinline__ int count() const { return e[1]; }
+    __device__ __forceinline__ int weight_at() const { return e[2]; }
+    __device__ __forceinline__ int first_block() const { return e[3]; }
+    __device__ __forceinline__ int first_pair() const { return e[4]; }
+    // the blocks it has a point in, which is how many pairs it has
+    __device__ __forceinline__ int blocks() const { return (e[0] + e[1] - 1)/kSolverBlock - e[3] + 1; }
+};
+// window k of the entries (K: the index arithmetic of the site), and the q-th window of a block list
+template <typename K>
+__device__ __forceinline__ Window window_at(int const *entries, K k)
+{
+    return Window{entries + (K)GRT_WINDOW_INTS*k};
+}
+template <typename K = int>
+__device__ __forceinline__ Window window_of(int const *entries, int const *block_list, int q)
+{
+    return window_at<K>(entries, block_list[q]);
+}
+
 // Where a solver's level fluxes go, level lev top first.  Spectral forms (FUSED false): the rows flux_up / flux_down
 // [V][nw] at this thread's point.  Fused form: the six integrated output rows in registers (up TOA, up surface, up user,
 // down TOA, down surface, down user) and, at finish(), their trapezoid partial sums (block_partials).  PROFILE (fused
@@ -540,7 +569,7 @@ struct LayerOptics
 // dF_up/dT_surf to put_direct() and its partial sums' array in a GrtDirectArgs.
 // RESPONSES (profile form only, with or without DIRECT; GrtResponseArgs, grt_pipeline_run_sky_weighted): the broadband
 // group of G V rows (G = 2, 3 with DIRECT) is summed as without it -- x*pwt, the same wave_row_sum, the same rows --, and
-// each response of the block's list (block_start / block_resp: an explicit list, responses overlap) gets a group of G V
+// each response of the block's list (block_start / block_list: an explicit list, responses overlap) gets a group of G V
 // wave sums of its own behind it, of x*(pwt*r).  The products pwt*r of the list wait in dynamic LDS behind the wave sums,
 // [responses of the block][kSolverBlock], written once by the constructor -- each thread writes and reads its own entries
 // only, so no barrier is needed --: a list indexed per thread in registers would live in scratch memory.  finish() stores
@@ -614,9 +643,9 @@ struct LevelSink
             resp.wt = wt;
             for (int q = 0; q < resp.count; ++q)
             {
-                int const *e = resp_.resp + GRT_RESPONSE_INTS*resp_.block_resp[resp.lo + q];
-                long long const at = (long long)i - e[0];
-                wt[q*kSolverBlock] = live && at >= 0 && at < e[1] ? pwt*resp_.weights[e[2] + at] : 0.;
+                Window const w = window_of(resp_.entry, resp_.block_list, resp.lo + q);
+                long long const at = (long long)i - w.first();                  // (Window: span, weight)
+                wt[q*kSolverBlock] = live && at >= 0 && at < w.count() ? pwt*resp_.weights[w.weight_at() + at] : 0.;
             }
         }
     }
@@ -759,8 +788,8 @@ struct LevelSink
                 for (int k = threadIdx.x; k < resp.count*rows; k += kSolverBlock)
                 {
                     int const q = k/rows, r = k - q*rows;
-                    int const *e = resp.a.resp + GRT_RESPONSE_INTS*resp.a.block_resp[resp.lo + q];
-                    uint64_t const pair = (uint64_t)(e[4] + (int)blockIdx.x - e[3]);
+                    Window const w = window_of(resp.a.entry, resp.a.block_list, resp.lo + q);
+                    uint64_t const pair = (uint64_t)(w.first_pair() + (int)blockIdx.x - w.first_block());   // (Window: pair)
                     resp.a.partials[((uint64_t)col*resp.a.per_row + pair)*rows + r] =
                         waves_sum<kSolverBlock/64>(lds + k*(kSolverBlock/64));
                 }

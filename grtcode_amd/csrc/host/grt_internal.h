@@ -199,6 +199,11 @@ void grt_aerosol_tables(double const *x, int na, int ncol, int num_layers, doubl
 void grt_surface_entry_map(double w0, double dw, uint64_t n, double const *x, int ns, int *entry);
 void grt_surface_tables(double const *x, int ns, int ncol, double const *values, double *tables);
 void grt_cloud_band_map(double const *lo, double const *hi, int own, int nb, double const *w, int n, int *idx);
+/* ... and of grt_pipeline_run_sky_channels' and _run_sky_weighted's windows (the window table, grt_kernels.h): how many ints
+   `count` windows with `pairs` (window, block) pairs take on a grid of nblocks solver blocks, and those ints for the
+   windows first [count], offset [count + 1] -- every window with at least one point, all of them on the grid */
+size_t grt_window_table_ints(int count, size_t nblocks, long long pairs);
+void grt_window_table(int const *first, int const *offset, int count, size_t nblocks, int *ints);
 
 /* grt_cloud_sampler.c, for the pipeline's grt_pipeline_run_cloud_fields: the argument checks the two entry points share
    (need_temperature: fields->temperature must be given), the fields staged and the kernel enqueued into tables_dev

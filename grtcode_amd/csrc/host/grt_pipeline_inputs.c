@@ -548,37 +548,41 @@ int grt_check_surface(GrtPipeline_t const *p, GrtSurface_t const *sf, int np[2])
     return GRTCODE_SUCCESS;
 }
 
-/* A checked surface (grt_check_surface's np) to the device: the columns' slope and intercept entries staged and uploaded,
-   each band's per-point entries built on the host when its surface grid differs from the last call's, and one launch per
-   band and array that writes the columns' rows (GRT_TAG_SURFACE).  The bands' surf_set / surf_dif_set say what is in
-   force afterwards; the caller sets them when this has succeeded. */
-int grt_stage_surface(GrtPipeline_t *p, GrtSurface_t const *sf, int const np[2])
+/* The three arrays of a surface, by band: values[k] is emissivity, direct albedo, diffuse albedo where band k > 0 takes
+   points (np) and the array is given, else NULL.  Returns the doubles their slope and intercept entries take per row. */
+static size_t surface_arrays(int const np[2], fp_t const *emissivity, fp_t const *direct, fp_t const *diffuse,
+                             fp_t const *values[3])
 {
-    size_t const C = (size_t)sf->ncol, M = (size_t)p->max_cols;
-    fp_t const *values[3] = {np[0] > 0 ? sf->emissivity : NULL, np[1] > 0 ? sf->direct_albedo : NULL,
-                             np[1] > 0 ? sf->diffuse_albedo : NULL};
-    size_t off[3], need = 0, want = 0;
+    values[0] = np[0] > 0 ? emissivity : NULL;
+    values[1] = np[1] > 0 ? direct : NULL;
+    values[2] = np[1] > 0 ? diffuse : NULL;
+    size_t per = 0;
     for (int k = 0; k < 3; ++k)
     {
-        size_t const per = values[k] != NULL ? 2*((size_t)np[k > 0] + 1) : 0;
+        per += values[k] != NULL ? 2*((size_t)np[k > 0] + 1) : 0;
+    }
+    return per;
+}
+
+/* `rows` rows of a surface (surface_arrays' values on grid[band]) to the device through st, which the caller reserved for
+   `front` doubles of its own, written already, and the rows' entries behind them: the entries (grt_surface_tables), array
+   after array, the upload, and per array the band's per-point entry map -- its tile_map (tiles) or surf_map, built
+   when the grid differs from the last call's --, `cap` rows of scratch (id[1]: the diffuse albedo's, id[0]: the others') and
+   the launch that writes the rows there (GRT_TAG_SURFACE). */
+static int stage_surface_rows(GrtPipeline_t *p, GrtStaging *st, int tiles, int const id[2], size_t rows, size_t cap,
+                              fp_t const *const grid[2], int const np[2], fp_t const *const values[3], size_t front)
+{
+    size_t off[3], need = front;
+    for (int k = 0; k < 3; ++k)
+    {
         off[k] = need;
-        need += C*per;
-        want += M*per;
-    }
-    if (need == 0)
-    {
-        return GRTCODE_SUCCESS;
-    }
-    GRT_TRY(grt_staging_reserve(p, &p->surf, need, want));
-    for (int k = 0; k < 3; ++k)
-    {
         if (values[k] != NULL)
         {
-            grt_surface_tables(k == 0 ? sf->emissivity_grid : sf->albedo_grid, np[k > 0], sf->ncol, values[k],
-                               p->surf.h + off[k]);
+            grt_surface_tables(grid[k > 0], np[k > 0], (int)rows, values[k], st->h + off[k]);
+            need += rows*2*((size_t)np[k > 0] + 1);
         }
     }
-    GRT_TRY(grt_staging_upload(p, &p->surf, need));
+    GRT_TRY(grt_staging_upload(p, st, need));
     void *s = grt_dev_stream(p->device);
     for (int k = 0; k < 3; ++k)
     {
@@ -587,18 +591,36 @@ int grt_stage_surface(GrtPipeline_t *p, GrtSurface_t const *sf, int const np[2])
             continue;
         }
         GrtBand *b = &p->band[k > 0];
-        SpectralGrid_t const *grid = &b->gas->grid;
-        GridMapFill f = {grid, k == 0 ? sf->emissivity_grid : sf->albedo_grid, np[k > 0], 1};
-        GRT_TRY(grt_keyed_table(p, &b->surf_map, f.x, sizeof(double)*(size_t)f.nx, b->n, fill_grid_map, &f));
-        GrtScratch *rows = &b->scratch[k == 2 ? GRT_SCRATCH_SURF_ROWS_DIF : GRT_SCRATCH_SURF_ROWS];
-        GRT_TRY(grt_scratch_need(p, rows, M*b->n, NULL));
-        GrtSurfaceArgs const sa = {f.nx + 1, b->surf_map.table, p->surf.d + off[k]};
+        GrtKeyedTable *map = tiles ? &b->tile_map : &b->surf_map;
+        SpectralGrid_t const *g = &b->gas->grid;
+        GridMapFill f = {g, grid[k > 0], np[k > 0], 1};
+        GRT_TRY(grt_keyed_table(p, map, f.x, sizeof(double)*(size_t)f.nx, b->n, fill_grid_map, &f));
+        GrtScratch *out = &b->scratch[id[k == 2]];
+        GRT_TRY(grt_scratch_need(p, out, cap*b->n, NULL));
+        GrtSurfaceArgs const sa = {f.nx + 1, map->table, st->d + off[k]};
         int const slot = grt_profile_begin(s, GRT_TAG_SURFACE);
-        int const krc = grt_launch_spread_surface(s, sf->ncol, grid->w0, grid->dw, b->n, &sa, rows->d);
+        int const krc = grt_launch_spread_surface(s, (int)rows, g->w0, g->dw, b->n, &sa, out->d);
         grt_profile_end(s, slot);
         GRT_TRY(grt_dev_check(krc, "surface row kernel"));
     }
     return GRTCODE_SUCCESS;
+}
+
+/* A checked surface (grt_check_surface's np) to the device: the columns' rows, stage_surface_rows into the bands'
+   GRT_SCRATCH_SURF_ROWS(_DIF) through their surf_map.  The bands' surf_set / surf_dif_set say what is in force afterwards;
+   the caller sets them when this has succeeded. */
+int grt_stage_surface(GrtPipeline_t *p, GrtSurface_t const *sf, int const np[2])
+{
+    size_t const C = (size_t)sf->ncol, M = (size_t)p->max_cols;
+    fp_t const *values[3], *const grid[2] = {sf->emissivity_grid, sf->albedo_grid};
+    size_t const per = surface_arrays(np, sf->emissivity, sf->direct_albedo, sf->diffuse_albedo, values);
+    int const id[2] = {GRT_SCRATCH_SURF_ROWS, GRT_SCRATCH_SURF_ROWS_DIF};
+    if (per == 0)
+    {
+        return GRTCODE_SUCCESS;
+    }
+    GRT_TRY(grt_staging_reserve(p, &p->surf, C*per, M*per));
+    return stage_surface_rows(p, &p->surf, 0, id, C, M, grid, np, values, 0);
 }
 
 /* ---- surface tiles (grt_pipeline_run_sky_tiles) ---- */
@@ -647,25 +669,16 @@ int grt_check_tiles(GrtPipeline_t const *p, GrtSurfaceTiles_t const *tl, int C, 
     return GRTCODE_SUCCESS;
 }
 
-/* Checked tiles (grt_check_tiles' np) to the device, as grt_stage_surface brings a surface there: the temperatures and
-   fractions, the C x T rows' slope and intercept entries (grt_surface_tables), each band's per-point entries
-   (grt_surface_entry_map; built when the band's tile grid differs from the last call's), and one launch per band and
-   array of the surface-row kernel (GRT_TAG_SURFACE) that writes the tiles' rows [C T][n] into the band's
-   GRT_SCRATCH_TILE_ROWS(_DIF).  The surface in force and its rows are not touched. */
+/* Checked tiles (grt_check_tiles' np) to the device, as grt_stage_surface brings a surface there: the temperatures [C T]
+   and [T][C] and the fractions in front, then the C x T rows, stage_surface_rows into the bands' GRT_SCRATCH_TILE_ROWS(_DIF)
+   through a map of the tiles' own (tile_map).  The surface in force and its rows are not touched. */
 int grt_stage_tiles(GrtPipeline_t *p, GrtSurfaceTiles_t const *tl, int C, int const np[2], GrtTileRun *tr)
 {
     size_t const T = (size_t)tl->num_tiles, R = (size_t)C*T, M = (size_t)p->max_cols*T;
-    fp_t const *values[3] = {np[0] > 0 ? tl->emissivity : NULL, np[1] > 0 ? tl->direct_albedo : NULL,
-                             np[1] > 0 ? tl->diffuse_albedo : NULL};
-    size_t off[3], need = 3*R, want = 3*M;
-    for (int k = 0; k < 3; ++k)
-    {
-        size_t const per = values[k] != NULL ? 2*((size_t)np[k > 0] + 1) : 0;
-        off[k] = need;
-        need += R*per;
-        want += M*per;
-    }
-    GRT_TRY(grt_staging_reserve(p, &p->tile, need, want));
+    fp_t const *values[3], *const grid[2] = {tl->emissivity_grid, tl->albedo_grid};
+    size_t const per = surface_arrays(np, tl->emissivity, tl->direct_albedo, tl->diffuse_albedo, values);
+    int const id[2] = {GRT_SCRATCH_TILE_ROWS, GRT_SCRATCH_TILE_ROWS_DIF};
+    GRT_TRY(grt_staging_reserve(p, &p->tile, R*(3 + per), M*(3 + per)));
     double *h = p->tile.h;
     for (size_t k = 0; k < R; ++k)
     {
@@ -674,33 +687,7 @@ int grt_stage_tiles(GrtPipeline_t *p, GrtSurfaceTiles_t const *tl, int C, int co
         h[R + (k % T)*(size_t)C + k/T] = ts;
         h[2*R + k] = tl->fraction != NULL ? tl->fraction[k] : 0.;
     }
-    for (int k = 0; k < 3; ++k)
-    {
-        if (values[k] != NULL)
-        {
-            grt_surface_tables(k == 0 ? tl->emissivity_grid : tl->albedo_grid, np[k > 0], (int)R, values[k], h + off[k]);
-        }
-    }
-    GRT_TRY(grt_staging_upload(p, &p->tile, need));
-    void *s = grt_dev_stream(p->device);
-    for (int k = 0; k < 3; ++k)
-    {
-        if (values[k] == NULL)
-        {
-            continue;
-        }
-        GrtBand *b = &p->band[k > 0];
-        SpectralGrid_t const *grid = &b->gas->grid;
-        GridMapFill f = {grid, k == 0 ? tl->emissivity_grid : tl->albedo_grid, np[k > 0], 1};
-        GRT_TRY(grt_keyed_table(p, &b->tile_map, f.x, sizeof(double)*(size_t)f.nx, b->n, fill_grid_map, &f));
-        GrtScratch *rows = &b->scratch[k == 2 ? GRT_SCRATCH_TILE_ROWS_DIF : GRT_SCRATCH_TILE_ROWS];
-        GRT_TRY(grt_scratch_need(p, rows, M*b->n, NULL));
-        GrtSurfaceArgs const sa = {f.nx + 1, b->tile_map.table, p->tile.d + off[k]};
-        int const slot = grt_profile_begin(s, GRT_TAG_SURFACE);
-        int const krc = grt_launch_spread_surface(s, (int)R, grid->w0, grid->dw, b->n, &sa, rows->d);
-        grt_profile_end(s, slot);
-        GRT_TRY(grt_dev_check(krc, "surface row kernel"));
-    }
+    GRT_TRY(stage_surface_rows(p, &p->tile, 1, id, R, M, grid, np, values, 3*R));
     tr->tiles = tl->num_tiles;
     tr->t_surf = p->tile.d;
     tr->t_surf_by_tile = p->tile.d + R;
@@ -876,7 +863,166 @@ int grt_stage_zenith_slant(GrtPipeline_t *p, GrtZenithSlant_t const *sl, int C, 
     return GRTCODE_SUCCESS;
 }
 
-/* ---- instrument channels (grt_pipeline_run_sky_channels) ---- */
+/* ---- windows: instrument channels (grt_pipeline_run_sky_channels) and spectral responses (_run_sky_weighted) ---- */
+
+static GrtWindows channel_windows(GrtChannels_t const *ch)
+{
+    GrtWindows const w = {ch->num_channels, ch->first, ch->offset, ch->weights, "channel", ""};
+    return w;
+}
+
+static GrtWindows response_windows(GrtResponses_t const *rs, int bi)
+{
+    GrtWindows const lw = {rs->lw_num_responses, rs->lw_first, rs->lw_offset, rs->lw_weights, "response", "longwave "};
+    GrtWindows const sw = {rs->sw_num_responses, rs->sw_first, rs->sw_offset, rs->sw_weights, "response", "shortwave "};
+    return bi == 0 ? lw : sw;
+}
+
+/* What every window set is refused for on a grid of n points (n < 1: no grid, so no range check and no pairs), its count
+   apart, which the caller has checked: a NULL field, weights that do not start at 0, a window without a point or off the
+   grid, a weight that is not finite.  *pairs: the (window, solver block) pairs in which a window has a point.  Nothing is
+   touched. */
+int grt_check_windows(GrtWindows const *w, long long n, long long *pairs)
+{
+    if (w->first == NULL || w->offset == NULL || w->weights == NULL)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%s of the %s%ss is NULL.",
+                 w->first == NULL ? "first" : (w->offset == NULL ? "offset" : "weights"), w->band, w->kind);
+    }
+    if (w->offset[0] != 0)
+    {
+        GRT_FAIL(GRTCODE_VALUE_ERR, "offset[0] of the %s%ss is %d: the first %s's weights start at 0.", w->band, w->kind,
+                 w->offset[0], w->kind);
+    }
+    long long P = 0;
+    for (int k = 0; k < w->count; ++k)
+    {
+        if (w->offset[k + 1] <= w->offset[k])
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "%soffset[%d] = %d is not above offset[%d] = %d: a %s has at least one point.", w->band,
+                     k + 1, w->offset[k + 1], k, w->offset[k], w->kind);
+        }
+        long long const count = (long long)w->offset[k + 1] - w->offset[k];
+        if (n >= 1 && (w->first[k] < 0 || w->first[k] + count > n))
+        {
+            GRT_FAIL(GRTCODE_VALUE_ERR, "%s%s %d takes the points %d .. %lld of a band of %lld.", w->band, w->kind, k,
+                     w->first[k], w->first[k] + count - 1, n);
+        }
+        for (int j = w->offset[k]; j < w->offset[k + 1]; ++j)
+        {
+            if (!isfinite(w->weights[j]))
+            {
+                GRT_FAIL(GRTCODE_VALUE_ERR, "weight %d of %s%s %d (%e) is NaN or infinite.", j - w->offset[k], w->band, w->kind,
+                         k, w->weights[j]);
+            }
+        }
+        if (n >= 1)
+        {
+            P += (w->first[k] + count - 1)/GRT_SOLVER_BLOCK - w->first[k]/GRT_SOLVER_BLOCK + 1;
+        }
+    }
+    *pairs = P;
+    return GRTCODE_SUCCESS;
+}
+
+/* the ints of the window table (grt_kernels.h) of `count` windows with `pairs` pairs on a grid of nblocks solver blocks */
+size_t grt_window_table_ints(int count, size_t nblocks, long long pairs)
+{
+    return (size_t)GRT_WINDOW_INTS*(size_t)count + nblocks + 1 + (size_t)pairs;
+}
+
+/* ... written to ints for the checked windows first, offset [count]: the entries, block_start, the block lists */
+void grt_window_table(int const *first, int const *offset, int count, size_t nblocks, int *ints)
+{
+    int *block_start = ints + (size_t)GRT_WINDOW_INTS*(size_t)count, *block_list = block_start + nblocks + 1;
+    memset(block_start, 0, sizeof(int)*(nblocks + 1));
+    int pair = 0;
+    for (int k = 0; k < count; ++k)
+    {
+        int const points = offset[k + 1] - offset[k];
+        int const b_lo = first[k]/GRT_SOLVER_BLOCK, b_hi = (first[k] + points - 1)/GRT_SOLVER_BLOCK;
+        int *e = ints + (size_t)GRT_WINDOW_INTS*(size_t)k;
+        e[0] = first[k]; e[1] = points; e[2] = offset[k]; e[3] = b_lo; e[4] = pair;
+        pair += b_hi - b_lo + 1;
+        for (int b = b_lo; b <= b_hi; ++b)
+        {
+            ++block_start[b + 1];               /* (counts first, then their running sum) */
+        }
+    }
+    for (size_t b = 0; b < nblocks; ++b)
+    {
+        block_start[b + 1] += block_start[b];
+    }
+    /* the windows of a block in ascending order: block_start[b] walks block b's list and ends where the next one starts,
+       then every start moves back up by one block */
+    for (int k = 0; k < count; ++k)
+    {
+        int const *e = ints + (size_t)GRT_WINDOW_INTS*(size_t)k;
+        for (int b = e[3]; b <= (e[0] + e[1] - 1)/GRT_SOLVER_BLOCK; ++b)
+        {
+            block_list[block_start[b]++] = k;
+        }
+    }
+    memmove(block_start + 1, block_start, sizeof(int)*nblocks);
+    block_start[0] = 0;
+}
+
+/* The device table of windows on band b's grid, as grt_keyed_table keeps it: the doubles first (the table is a device
+   allocation: aligned for them) -- the weights and, of channels, sum_w and center [count] each --, then the window table. */
+typedef struct WindowTableFill
+{
+    GrtWindows w;
+    GrtChannels_t const *ch;          /* the channels the windows are, or NULL */
+    SpectralGrid_t const *grid;
+    size_t nblocks, doubles;
+} WindowTableFill;
+
+static int fill_window_table(void *ctx, int *table)
+{
+    WindowTableFill const *f = ctx;
+    GrtWindows const *w = &f->w;
+    size_t const W = (size_t)w->offset[w->count];
+    double *weights = (double *)table, *sum_w = weights + W, *center = sum_w + w->count;
+    memcpy(weights, w->weights, sizeof(double)*W);
+    for (int c = 0; f->ch != NULL && c < w->count; ++c)
+    {
+        double sum = 0., wsum = 0.;       /* (both in index order) */
+        for (int k = w->offset[c]; k < w->offset[c + 1]; ++k)
+        {
+            sum += w->weights[k];
+            wsum += w->weights[k]*(f->grid->w0 + (double)(w->first[c] + k - w->offset[c])*f->grid->dw);
+        }
+        sum_w[c] = sum;
+        center[c] = f->ch->center != NULL ? f->ch->center[c] : wsum/sum;
+    }
+    grt_window_table(w->first, w->offset, w->count, f->nblocks, table + 2*f->doubles);
+    return GRTCODE_SUCCESS;
+}
+
+/* The checked windows w (`pairs`: grt_check_windows' on b's grid) as b's device table t -- built and uploaded when the
+   grid's points, the count, first, offset, weights or, of channels ch, the centers differ from the last call's -- and
+   where its parts lie. */
+typedef struct WindowTable { double const *weights; int const *entry, *block_start, *block_list; } WindowTable;
+
+static int stage_windows(GrtPipeline_t *p, GrtBand *b, GrtKeyedTable *t, GrtWindows const *w, GrtChannels_t const *ch,
+                         long long pairs, WindowTable *wt)
+{
+    size_t const N = (size_t)w->count, W = (size_t)w->offset[N];
+    WindowTableFill f = {*w, ch, &b->gas->grid, grt_solver_blocks(b->n), W + (ch != NULL ? 2*N : 0)};
+    /* the key: the grid's points, the count and -- channels -- whether centers are given, then first, offset, weights and
+       the centers, where they are */
+    long long const h[3] = {(long long)b->n, w->count, ch != NULL && ch->center != NULL};
+    GrtKeyPart const key[5] = {{h, sizeof(long long)*(ch != NULL ? 3 : 2)}, {w->first, sizeof(int)*N},
+                               {w->offset, sizeof(int)*(N + 1)}, {w->weights, sizeof(double)*W},
+                               {ch != NULL ? ch->center : NULL, h[2] ? sizeof(double)*N : 0}};
+    size_t const ints = 2*f.doubles + grt_window_table_ints(w->count, f.nblocks, pairs);
+    GRT_TRY(grt_keyed_table_parts(p, t, key, ch != NULL ? 5 : 4, ints, fill_window_table, &f));
+    wt->weights = (double const *)t->table;
+    wt->entry = t->table + 2*f.doubles;
+    wt->block_start = wt->entry + (size_t)GRT_WINDOW_INTS*N;
+    wt->block_list = wt->block_start + f.nblocks + 1;
+    return GRTCODE_SUCCESS;
+}
 
 /* What grt_pipeline_run_sky_channels and grt_channel_pair_count check of an instrument's channels on a grid of n points
    (n < 1: a pipeline without a longwave band, no range check), the output pointers apart; *pairs: the (channel, solver
@@ -891,38 +1037,14 @@ int grt_check_channels(GrtChannels_t const *ch, long long n, long long *pairs)
     {
         GRT_FAIL(GRTCODE_VALUE_ERR, "%d channels asked for: 1 to %d.", ch->num_channels, GRT_MAX_CHANNELS);
     }
-    if (ch->first == NULL || ch->offset == NULL || ch->weights == NULL)
+    GrtWindows const w = channel_windows(ch);
+    long long P;
+    GRT_TRY(grt_check_windows(&w, n, &P));
+    for (int c = 0; c < ch->num_channels; ++c)
     {
-        GRT_FAIL(GRTCODE_VALUE_ERR, "%s of the channels is NULL.",
-                 ch->first == NULL ? "first" : (ch->offset == NULL ? "offset" : "weights"));
-    }
-    int const C = ch->num_channels;
-    if (ch->offset[0] != 0)
-    {
-        GRT_FAIL(GRTCODE_VALUE_ERR, "offset[0] of the channels is %d: the first channel's weights start at 0.", ch->offset[0]);
-    }
-    long long P = 0;
-    for (int c = 0; c < C; ++c)
-    {
-        if (ch->offset[c + 1] <= ch->offset[c])
-        {
-            GRT_FAIL(GRTCODE_VALUE_ERR, "offset[%d] = %d is not above offset[%d] = %d: a channel has at least one point.",
-                     c + 1, ch->offset[c + 1], c, ch->offset[c]);
-        }
-        long long const count = (long long)ch->offset[c + 1] - ch->offset[c];
-        if (n >= 1 && (ch->first[c] < 0 || ch->first[c] + count > n))
-        {
-            GRT_FAIL(GRTCODE_VALUE_ERR, "channel %d takes the points %d .. %lld of a longwave band of %lld.", c, ch->first[c],
-                     ch->first[c] + count - 1, n);
-        }
         double sum = 0.;                  /* (in index order: what the table divides by) */
         for (int k = ch->offset[c]; k < ch->offset[c + 1]; ++k)
         {
-            if (!isfinite(ch->weights[k]))
-            {
-                GRT_FAIL(GRTCODE_VALUE_ERR, "weight %d of channel %d (%e) is NaN or infinite.", k - ch->offset[c], c,
-                         ch->weights[k]);
-            }
             sum += ch->weights[k];
         }
         if (!(sum > 0.) || !isfinite(sum))
@@ -934,176 +1056,54 @@ int grt_check_channels(GrtChannels_t const *ch, long long n, long long *pairs)
         {
             GRT_FAIL(GRTCODE_VALUE_ERR, "center of channel %d (%e) is NaN, infinite or not above 0.", c, ch->center[c]);
         }
-        if (n >= 1)
-        {
-            P += (ch->first[c] + count - 1)/GRT_SOLVER_BLOCK - ch->first[c]/GRT_SOLVER_BLOCK + 1;
-        }
     }
     *pairs = P;
     return GRTCODE_SUCCESS;
 }
 
-/* The device table of an instrument on band b's grid (GrtChannelArgs, grt_kernels.h), as grt_keyed_table keeps it: the
-   doubles first (the table is a device allocation: aligned for them), then the ints. */
-typedef struct ChannelTableFill
-{
-    GrtChannels_t const *ch;
-    SpectralGrid_t const *grid;
-    size_t nblocks, doubles;
-    long long pairs;
-} ChannelTableFill;
-
-static int fill_channel_table(void *ctx, int *table)
-{
-    ChannelTableFill *f = ctx;
-    GrtChannels_t const *ch = f->ch;
-    int const C = ch->num_channels;
-    size_t const W = (size_t)ch->offset[C];
-    double *weights = (double *)table, *sum_w = weights + W, *center = sum_w + C;
-    int *chan = table + 2*f->doubles, *block_start = chan + (size_t)GRT_CHANNEL_INTS*C, *block_chan = block_start + f->nblocks + 1;
-    memcpy(weights, ch->weights, sizeof(double)*W);
-    memset(block_start, 0, sizeof(int)*(f->nblocks + 1));
-    int pair = 0;
-    for (int c = 0; c < C; ++c)
-    {
-        int const first = ch->first[c], count = ch->offset[c + 1] - ch->offset[c];
-        int const b_lo = first/GRT_SOLVER_BLOCK, b_hi = (first + count - 1)/GRT_SOLVER_BLOCK;
-        int *e = chan + (size_t)GRT_CHANNEL_INTS*c;
-        e[0] = first; e[1] = count; e[2] = ch->offset[c]; e[3] = b_lo; e[4] = pair;
-        pair += b_hi - b_lo + 1;
-        for (int k = b_lo; k <= b_hi; ++k)
-        {
-            ++block_start[k + 1];               /* (counts first, then their running sum) */
-        }
-        double sum = 0., wsum = 0.;       /* (both in index order) */
-        for (int k = 0; k < count; ++k)
-        {
-            double const W = ch->weights[ch->offset[c] + k];
-            sum += W;
-            wsum += W*(f->grid->w0 + (double)(first + k)*f->grid->dw);
-        }
-        sum_w[c] = sum;
-        center[c] = ch->center != NULL ? ch->center[c] : wsum/sum;
-    }
-    for (size_t k = 0; k < f->nblocks; ++k)
-    {
-        block_start[k + 1] += block_start[k];
-    }
-    /* the channels of a block in ascending order; fill[] walks each block's list */
-    int *fill = malloc(sizeof(int)*(f->nblocks > 0 ? f->nblocks : 1));
-    if (fill == NULL)
-    {
-        GRT_FAIL(GRTCODE_NULL_ERR, "out of host memory for a channel table of %zu blocks.", f->nblocks);
-    }
-    memcpy(fill, block_start, sizeof(int)*f->nblocks);
-    for (int c = 0; c < C; ++c)
-    {
-        int const *e = chan + (size_t)GRT_CHANNEL_INTS*c;
-        for (int k = e[3]; k <= (e[0] + e[1] - 1)/GRT_SOLVER_BLOCK; ++k)
-        {
-            block_chan[fill[k]++] = c;
-        }
-    }
-    free(fill);
-    return GRTCODE_SUCCESS;
-}
-
 /* The channels of a grt_pipeline_run_sky_channels call (checked by grt_check_channels on b's grid, which gave `pairs`) as
-   the longwave band's device table -- built and uploaded when first, offset, weights or center differ from the last
-   call's -- and where their outputs go */
+   the longwave band's device table, and where their outputs go */
 int grt_stage_channels(GrtPipeline_t *p, GrtBand *b, GrtChannels_t const *ch, long long pairs, GrtChannelRun *cr)
 {
-    int const C = ch->num_channels;
-    size_t const W = (size_t)ch->offset[C];
-    ChannelTableFill f = {ch, &b->gas->grid, grt_solver_blocks(b->n), W + 2*(size_t)C, pairs};
-    /* the key: the grid's points, C, whether centers are given, then first, offset, weights and the centers, where they are */
-    long long const h[3] = {(long long)b->n, C, ch->center != NULL};
-    GrtKeyPart const key[5] = {{h, sizeof(h)}, {ch->first, sizeof(int)*(size_t)C}, {ch->offset, sizeof(int)*((size_t)C + 1)},
-                               {ch->weights, sizeof(double)*W},
-                               {ch->center, ch->center != NULL ? sizeof(double)*(size_t)C : 0}};
-    size_t const table_ints = 2*f.doubles + (size_t)GRT_CHANNEL_INTS*C + f.nblocks + 1 + (size_t)f.pairs;
-    GRT_TRY(grt_keyed_table_parts(p, &b->channel_table, key, 5, table_ints, fill_channel_table, &f));
+    GrtWindows const w = channel_windows(ch);
+    WindowTable wt;
+    GRT_TRY(stage_windows(p, b, &b->channel_table, &w, ch, pairs, &wt));
     memset(cr, 0, sizeof(*cr));
     GrtChannelArgs *a = &cr->args;
-    a->channels = C;
-    a->pairs = (uint64_t)f.pairs;
-    a->weights = (double const *)b->channel_table.table;
-    a->sum_w = a->weights + W;
-    a->center = a->sum_w + C;
-    a->chan = b->channel_table.table + 2*f.doubles;
-    a->block_start = a->chan + (size_t)GRT_CHANNEL_INTS*C;
-    a->block_chan = a->block_start + f.nblocks + 1;
+    a->channels = w.count;
+    a->pairs = (uint64_t)pairs;
+    a->entry = wt.entry;
+    a->block_start = wt.block_start;
+    a->block_list = wt.block_list;
+    a->weights = wt.weights;
+    a->sum_w = a->weights + w.offset[w.count];
+    a->center = a->sum_w + w.count;
     cr->radiances = ch->channel_radiances_dev;
     cr->brightness = ch->channel_brightness_dev;
     return GRTCODE_SUCCESS;
 }
 
-/* ---- spectral responses of the level fluxes (grt_pipeline_run_sky_weighted) ---- */
-
-/* band bi's four fields of rs */
-typedef struct BandResponses { int count; int const *first, *offset; fp_t const *weights; } BandResponses;
-
-static BandResponses band_responses(GrtResponses_t const *rs, int bi)
-{
-    BandResponses const lw = {rs->lw_num_responses, rs->lw_first, rs->lw_offset, rs->lw_weights};
-    BandResponses const sw = {rs->sw_num_responses, rs->sw_first, rs->sw_offset, rs->sw_weights};
-    return bi == 0 ? lw : sw;
-}
-
 /* What grt_pipeline_run_sky_weighted and grt_response_pair_count check of one band's responses on a grid of n points (a
-   band without responses: nothing).  Nothing is touched. */
+   band without responses: nothing) and at most block_limit of them in one block (< 0: not checked).  Nothing is touched. */
 int grt_check_responses(GrtResponses_t const *rs, int bi, long long n, int block_limit, long long *pairs, int *block_max)
 {
-    char const *name = bi == 0 ? "longwave" : "shortwave";
-    BandResponses const r = band_responses(rs, bi);
+    GrtWindows const r = response_windows(rs, bi);
     *pairs = 0;
     *block_max = 0;
     if (r.count < 0 || r.count > GRT_MAX_RESPONSES)
     {
-        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s responses asked for: 0 to %d.", r.count, name, GRT_MAX_RESPONSES);
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %sresponses asked for: 0 to %d.", r.count, r.band, GRT_MAX_RESPONSES);
     }
     if (r.count == 0)
     {
         return GRTCODE_SUCCESS;
     }
-    if (r.first == NULL || r.offset == NULL || r.weights == NULL)
-    {
-        GRT_FAIL(GRTCODE_VALUE_ERR, "%s of the %s responses is NULL.",
-                 r.first == NULL ? "first" : (r.offset == NULL ? "offset" : "weights"), name);
-    }
     if (n < 1)
     {
-        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s responses, and this pipeline has no %s band.", r.count, name, name);
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %sresponses, and this pipeline has no %sband.", r.count, r.band, r.band);
     }
-    if (r.offset[0] != 0)
-    {
-        GRT_FAIL(GRTCODE_VALUE_ERR, "offset[0] of the %s responses is %d: the first response's weights start at 0.", name,
-                 r.offset[0]);
-    }
-    long long P = 0;
-    for (int k = 0; k < r.count; ++k)
-    {
-        if (r.offset[k + 1] <= r.offset[k])
-        {
-            GRT_FAIL(GRTCODE_VALUE_ERR, "%s offset[%d] = %d is not above offset[%d] = %d: a response has at least one point.",
-                     name, k + 1, r.offset[k + 1], k, r.offset[k]);
-        }
-        long long const count = (long long)r.offset[k + 1] - r.offset[k];
-        if (r.first[k] < 0 || r.first[k] + count > n)
-        {
-            GRT_FAIL(GRTCODE_VALUE_ERR, "%s response %d takes the points %d .. %lld of a band of %lld.", name, k, r.first[k],
-                     r.first[k] + count - 1, n);
-        }
-        for (int j = r.offset[k]; j < r.offset[k + 1]; ++j)
-        {
-            if (!isfinite(r.weights[j]))
-            {
-                GRT_FAIL(GRTCODE_VALUE_ERR, "weight %d of %s response %d (%e) is NaN or infinite.", j - r.offset[k], name, k,
-                         r.weights[j]);
-            }
-        }
-        P += (r.first[k] + count - 1)/GRT_SOLVER_BLOCK - r.first[k]/GRT_SOLVER_BLOCK + 1;
-    }
+    long long P;
+    GRT_TRY(grt_check_windows(&r, n, &P));
     /* the most responses with a point in one block: a count per block */
     size_t const nblocks = (size_t)((n + GRT_SOLVER_BLOCK - 1)/GRT_SOLVER_BLOCK);
     int *held = calloc(nblocks, sizeof(int));
@@ -1127,8 +1127,8 @@ int grt_check_responses(GrtResponses_t const *rs, int bi, long long n, int block
     free(held);
     if (block_limit >= 0 && most > block_limit)
     {
-        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %s responses have a point in block %d (points %d .. %d): at most %d "
-                 "(grt_pipeline_response_block_limit).", most, name, most_at, most_at*GRT_SOLVER_BLOCK,
+        GRT_FAIL(GRTCODE_VALUE_ERR, "%d %sresponses have a point in block %d (points %d .. %d): at most %d "
+                 "(grt_pipeline_response_block_limit).", most, r.band, most_at, most_at*GRT_SOLVER_BLOCK,
                  most_at*GRT_SOLVER_BLOCK + GRT_SOLVER_BLOCK - 1, block_limit);
     }
     *pairs = P;
@@ -1136,82 +1136,23 @@ int grt_check_responses(GrtResponses_t const *rs, int bi, long long n, int block
     return GRTCODE_SUCCESS;
 }
 
-/* The device table of a band's responses (GrtResponseArgs, grt_kernels.h), as grt_keyed_table keeps it: the doubles first
-   (the table is a device allocation: aligned for them), then the ints. */
-typedef struct ResponseTableFill
-{
-    BandResponses r;
-    size_t nblocks, doubles;
-} ResponseTableFill;
-
-static int fill_response_table(void *ctx, int *table)
-{
-    ResponseTableFill *f = ctx;
-    BandResponses const *r = &f->r;
-    int const R = r->count;
-    int *resp = table + 2*f->doubles, *block_start = resp + (size_t)GRT_RESPONSE_INTS*R, *block_resp = block_start + f->nblocks + 1;
-    memcpy(table, r->weights, sizeof(double)*f->doubles);
-    memset(block_start, 0, sizeof(int)*(f->nblocks + 1));
-    int pair = 0;
-    for (int k = 0; k < R; ++k)
-    {
-        int const first = r->first[k], count = r->offset[k + 1] - r->offset[k];
-        int const b_lo = first/GRT_SOLVER_BLOCK, b_hi = (first + count - 1)/GRT_SOLVER_BLOCK;
-        int *e = resp + (size_t)GRT_RESPONSE_INTS*k;
-        e[0] = first; e[1] = count; e[2] = r->offset[k]; e[3] = b_lo; e[4] = pair;
-        pair += b_hi - b_lo + 1;
-        for (int b = b_lo; b <= b_hi; ++b)
-        {
-            ++block_start[b + 1];               /* (counts first, then their running sum) */
-        }
-    }
-    for (size_t b = 0; b < f->nblocks; ++b)
-    {
-        block_start[b + 1] += block_start[b];
-    }
-    /* the responses of a block in ascending order; fill[] walks each block's list */
-    int *fill = malloc(sizeof(int)*(f->nblocks > 0 ? f->nblocks : 1));
-    if (fill == NULL)
-    {
-        GRT_FAIL(GRTCODE_NULL_ERR, "out of host memory for a response table of %zu blocks.", f->nblocks);
-    }
-    memcpy(fill, block_start, sizeof(int)*f->nblocks);
-    for (int k = 0; k < R; ++k)
-    {
-        int const *e = resp + (size_t)GRT_RESPONSE_INTS*k;
-        for (int b = e[3]; b <= (e[0] + e[1] - 1)/GRT_SOLVER_BLOCK; ++b)
-        {
-            block_resp[fill[b]++] = k;
-        }
-    }
-    free(fill);
-    return GRTCODE_SUCCESS;
-}
-
 /* Band bi's responses of a grt_pipeline_run_sky_weighted call (checked by grt_check_responses on b's grid, which gave
-   `pairs` and `block_max`) as the band's device table -- built and uploaded when first, offset or weights differ from the
-   last call's */
+   `pairs` and `block_max`) as the band's device table */
 int grt_stage_responses(GrtPipeline_t *p, GrtBand *b, int bi, GrtResponses_t const *rs, long long pairs, int block_max,
                         GrtResponseRun *rr)
 {
-    ResponseTableFill f = {band_responses(rs, bi), grt_solver_blocks(b->n), 0};
-    int const R = f.r.count;
-    f.doubles = (size_t)f.r.offset[R];
-    /* the key: the grid's points and R, then first, offset and weights */
-    long long const h[2] = {(long long)b->n, R};
-    GrtKeyPart const key[4] = {{h, sizeof(h)}, {f.r.first, sizeof(int)*(size_t)R}, {f.r.offset, sizeof(int)*((size_t)R + 1)},
-                               {f.r.weights, sizeof(double)*f.doubles}};
-    size_t const table_ints = 2*f.doubles + (size_t)GRT_RESPONSE_INTS*R + f.nblocks + 1 + (size_t)pairs;
-    GRT_TRY(grt_keyed_table_parts(p, &b->response_table, key, 4, table_ints, fill_response_table, &f));
+    GrtWindows const w = response_windows(rs, bi);
+    WindowTable wt;
+    GRT_TRY(stage_windows(p, b, &b->response_table, &w, NULL, pairs, &wt));
     memset(rr, 0, sizeof(*rr));
     GrtResponseArgs *a = &rr->args;
-    a->responses = R;
+    a->responses = w.count;
     a->block_max = block_max;
     a->per_row = (uint64_t)pairs;
-    a->weights = (double const *)b->response_table.table;
-    a->resp = b->response_table.table + 2*f.doubles;
-    a->block_start = a->resp + (size_t)GRT_RESPONSE_INTS*R;
-    a->block_resp = a->block_start + f.nblocks + 1;
+    a->entry = wt.entry;
+    a->block_start = wt.block_start;
+    a->block_list = wt.block_list;
+    a->weights = wt.weights;
     rr->groups = bi == 0 ? 2 : 3;
     return GRTCODE_SUCCESS;
 }

@@ -404,6 +404,17 @@ GRT_PRIVATE int grt_check_zenith_slant(GrtZenithSlant_t const *sl, GrtZeniths_t 
 GRT_PRIVATE int grt_stage_zenith_slant(GrtPipeline_t *p, GrtZenithSlant_t const *sl, int C, GrtZenithRun *zr);
 GRT_PRIVATE int grt_check_radiances(GrtRadiances_t const *rd, int C);
 GRT_PRIVATE int grt_stage_radiances(GrtPipeline_t *p, GrtRadiances_t const *rd, int C, GrtRadianceRun *rr);
+/* One band's windows as the caller gave them: window k is the points first[k] .. of the grid, offset[k + 1] - offset[k] of
+   them, with the weights at weights + offset[k].  The messages call one `band` + `kind` ("shortwave " + "response", "" +
+   "channel").  grt_check_windows: what both kinds are refused for on a grid of n points, and their (window, block) pairs. */
+typedef struct GrtWindows
+{
+    int count;
+    int const *first, *offset;
+    fp_t const *weights;
+    char const *kind, *band;
+} GrtWindows;
+GRT_PRIVATE int grt_check_windows(GrtWindows const *w, long long n, long long *pairs);
 GRT_PRIVATE int grt_check_channels(GrtChannels_t const *ch, long long n, long long *pairs);
 GRT_PRIVATE int grt_stage_channels(GrtPipeline_t *p, GrtBand *b, GrtChannels_t const *ch, long long pairs,
                                    GrtChannelRun *cr);
